@@ -7,6 +7,7 @@ builds the 4-level pyramid and tracks it against its previous frame with the ref
 value = sequences x steps x ranks / wall time.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ the last timed step's outputs as DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -74,8 +75,8 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--prefetch", action="store_true", help="build the pyramid of frame k+1 on the library's low-priority side stream while frame k "
-                    "tracks (dvo_batch_prefetch_*): +1 % frames/s, but k_track_gn then shares the chip with k_pyramid and its per-launch "
-                    "time -- the roofline figure -- reads 7 % longer; default: every pyramid in order on the tracking stream")
+                    "tracks (dvo_batch_prefetch_*): +1 %% frames/s, but k_track_gn then shares the chip with k_pyramid and its per-launch "
+                    "time -- the roofline figure -- reads 7 %% longer; default: every pyramid in order on the tracking stream")
     ap.add_argument("--no-prefetch", action="store_true", help="(the default since round 2; kept for old command lines)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the side legs (single stream, mono batch, SYN-1080, converging configuration)")
     ap.add_argument("--pcie-steps", type=int, default=300, help="frames streamed per sequence in the PCIe-inclusive measurement (0 = skip)")
@@ -83,6 +84,10 @@ def parse():
     ap.add_argument("--step-scale", type=float, default=1.0, help="multiplies the reference's per-level step literals (optimize.cpp:22-26); "
                     "1 = the reference.  Used by the converging side leg only")
     ap.add_argument("--min-residual", type=float, default=-1.0, help="stop threshold on the mean squared residual (tracker.cpp:16); < 0 = the reference's 5e-3")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0's sequences) as DIR/<name>.npy: "
+                         "syn640 / syn1080 xi_rel [B][6] + T_rel [B][4][4], syn640-mono xi_world + T_world + is_keyframe; float32, at most "
+                         "64 MB in all (beyond that a fixed, seeded sample of sequences, listed in sequence_index.npy)")
     return ap.parse_args()
 
 
@@ -163,6 +168,26 @@ def diff_stats(dx, within=1e-3):
         return {"pairs": 0}
     return {"pairs": int(dx.size), "pairs_within_1e-3": int(np.sum(dx < within)), "median_abs_pose_diff": float(np.median(dx)),
             "p90_abs_pose_diff": float(np.percentile(dx, 90)), "max_abs_pose_diff": float(np.max(dx))}
+
+
+DUMP_BUDGET = 64_000_000 - 64 * 1024   # bytes of --dump-outputs in all (the slack covers the .npy headers)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: {name: array with the sequence as first axis} -> path/<name>.npy in float32 (float64 stays float64).
+    Above DUMP_BUDGET bytes the same fixed, seeded sample of sequences is taken from every array and written as sequence_index.npy."""
+    arrays = {k: np.ascontiguousarray(v, np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = next(iter(arrays.values())).shape[0]
+    row_bytes = sum(v[0].nbytes for v in arrays.values())
+    rows = None
+    if n * row_bytes > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET // (row_bytes + 8), replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sequence_index"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    return {"dir": path, "files": sorted(k + ".npy" for k in arrays), "sequences": n if rows is None else int(rows.size), "of_sequences": n}
 
 
 def render_sequences(env, B, F, W, H, K, want_depth=True, n_gt=32):
@@ -314,6 +339,10 @@ def run_depth(a, env, role="headline", data=None):
     fps = B * a.steps * world / dt
     log0 = batch.last_track_log(0)
     finite = bool(torch.isfinite(poses_out).all().item())
+    dumped = None
+    if head and rank == 0 and a.dump_outputs:   # the last timed step's poses as dvo_batch_last_poses hands them to a caller
+        xi_last, T_last = batch.last_poses()
+        dumped = dump_outputs(a.dump_outputs, {"xi_rel": xi_last, "T_rel": T_last})
     batch.close()   # (its pyramids are freed before the next pass allocates its own)
 
     out = {
@@ -331,6 +360,8 @@ def run_depth(a, env, role="headline", data=None):
                    "fixed_iterations": a.fixed_iters, "iterations_per_level_seq0": log0["n_iter"],
                    "poses_finite": finite, "gather_ms": gather_ms, "datagen_s": round(t_gen, 2)},
     }
+    if dumped:
+        out["dump_outputs"] = dumped
     if tracker_over:
         out["config"]["non_reference_tracker_constants"] = tracker_over
     elif a.workload == "syn640":
@@ -785,6 +816,10 @@ def run_mono(a, env, role="headline", gray=None):
     kf0 = mb.keyframe(0)
     vu = [mb.keyframe(b)["valid_updates"] for b in range(min(B, 64))]
     stats = [mb.stats(b) for b in range(min(B, 64))]
+    dumped = None
+    if head and rank == 0 and a.dump_outputs:   # the last timed step's world poses and keyframe flags as dvo_batch_world_poses hands them out
+        xi_w, T_w, key = mb.world_poses()
+        dumped = dump_outputs(a.dump_outputs, {"xi_world": xi_w, "T_world": T_w, "is_keyframe": key})
     mb.close()
     keys = keys_out.float().mean().item()
     out = {"metric": "tracked frames/sec (640x480 mono: tracking + inverse-depth filter)", "value": B * a.steps * world / dt, "unit": "frames/s",
@@ -802,6 +837,8 @@ def run_mono(a, env, role="headline", gray=None):
                       "ring_note": "FrameHistory is a ring of %d keyframes per sequence (the reference's is unbounded): a pixel older than the ring is "
                                    "searched against the oldest retained keyframe; ring_clamped_pixels counts how often that happened" % a.ring,
                       "poses_finite": bool(torch.isfinite(poses_out).all().item()), "datagen_s": round(t_gen, 2)}}
+    if dumped:
+        out["dump_outputs"] = dumped
     if head and a.pcie_steps > 0:   # co-headline: every frame streamed from pinned host memory, every pose copied back
         PB = min(B, a.pcie_batch)
         hb = dvo.MonoBatch(PB, K, W, H, ring_keyframes=a.ring, cfg=dvo.default_config(device=env.local, stream=env.stream, rng_seed=1))

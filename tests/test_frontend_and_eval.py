@@ -39,10 +39,16 @@ def test_png_reader_errors_are_status_codes(tmp_path):
         dvo.imread(str(bad))
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/data/logicool0/0000.png"), reason="reference data not mounted")
 def test_png_reader_on_the_reference_frames():
-    for p in ("/root/reference/data/logicool0/0000.png", "/root/reference/data/KINECT_50MM/depth01.png"):
-        np.testing.assert_array_equal(dvo.imread(p), np.asarray(Image.open(p)))
+    """8-bit RGB and 16-bit depth PNGs of the reference's KINECT_50MM pixels (tests/golden/make_png_fixtures.py)."""
+    gold = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    fx = np.load(os.path.join(gold, "kinect50mm_excerpt.npz"))
+    for name, want in (("kinect50mm_rgb8.png", fx["rgba"][..., :3]), ("kinect50mm_depth16.png", fx["depth16"])):
+        p = os.path.join(gold, name)
+        got = dvo.imread(p)
+        assert got.dtype == want.dtype and got.shape == want.shape
+        np.testing.assert_array_equal(got, np.asarray(Image.open(p)))
+        np.testing.assert_array_equal(got, want)
 
 
 # ---------------------------------------------------------------- datasets (CPU)
