@@ -355,6 +355,27 @@ int dvo_batch_synchronize(dvo_batch* b)
     return DVO_OK;
 }
 
+int dvo_batch_set_actions(dvo_batch* b, const uint8_t* actions, int actions_on_device)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_actions: a mono batch advances in lockstep (per-sequence actions need dvo_batch_create)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->impl.set_actions(actions, actions_on_device != 0);
+}
+
+int dvo_batch_last_status(dvo_batch* b, int* status)
+{
+    if (!b || !status) return DVO_ERR_BAD_ARGUMENT;
+    DVO_NOT_MONO(b);
+    return b->impl.status_of_last(status, false);
+}
+
+int dvo_batch_copy_status_device(dvo_batch* b, int* status_dev)
+{
+    if (!b || !status_dev) return DVO_ERR_BAD_ARGUMENT;
+    DVO_NOT_MONO(b);
+    return b->impl.status_of_last(status_dev, true);
+}
+
 int dvo_shard_range(int n_sequences, int world_size, int rank, int* first, int* count)
 {
     if (n_sequences < 0 || world_size < 1 || rank < 0 || rank >= world_size || !first || !count) return DVO_ERR_BAD_ARGUMENT;

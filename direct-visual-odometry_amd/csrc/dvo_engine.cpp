@@ -206,8 +206,18 @@ static void fuse_prep(PyramidArgs& a, const FrameSet& fs)
     a.sigma_min = fs.sigma_min; a.sigma_max = fs.sigma_max;
 }
 
+static void plan_copy(PyramidArgs& a, const uint8_t* seq_action, const FrameSet* from)
+{
+    if (!seq_action || !from) return;
+    a.seq_action = seq_action;
+    for (int l = 0; l < from->g.levels; l++) {
+        a.ref[0][l] = from->gray[l]; a.ref[1][l] = from->depth[l]; a.ref[2][l] = from->sigma[l];
+        a.ref_wgt[l] = from->wgt[l];
+    }
+}
+
 void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma,
-                   bool rows_decimated)
+                   bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from)
 {
     PyramidArgs a;
     memset(&a, 0, sizeof a);
@@ -223,12 +233,13 @@ void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, 
     a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
     fs.sigma_by_validity = false;
     if (depth_dev && sigma_dev) fuse_prep(a, fs);  // wgt written by the same launch (no k_prep_ref pass)
+    plan_copy(a, seq_action, copy_from);
     launch_pyramid(a, fs.n_seq, s);
 }
 
-void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma)
+void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from)
 {
-    if (!in.raw()) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated); return; }
+    if (!in.raw()) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
     PyramidArgs a;
     memset(&a, 0, sizeof a);
     a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_depth = in.depth16;
@@ -251,6 +262,7 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     } else if (dep) {
         fuse_prep(a, fs);
     }
+    plan_copy(a, seq_action, copy_from);
     launch_pyramid(a, fs.n_seq, s);
 }
 
@@ -479,11 +491,11 @@ void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, in
     else launch_track_gn(a, count, ppt[level], group[level], s, grid_seqs);
 }
 
-int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
+int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan)
 {
     last_obj = &obj; last_ref = &ref;
     persist_used = false;
-    if (persist_ok && !persist_failed && h_result) {   // the whole call in one launch (k_track_persist)
+    if (persist_ok && !persist_failed && h_result && !plan) {   // the whole call in one launch (k_track_persist)
         PersistArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.levels = g.levels;
@@ -518,7 +530,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
             return DVO_OK;
         }
     }
-    launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
+    if (!plan) launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
     // level does not pay for its remaining (empty) launches.  Big batches run the fixed schedule sync-free.
@@ -546,7 +558,21 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
     if (any_single) DVO_HIP(hipMemsetAsync(rep_set, 0, sizeof(int) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS, s));
     static const char* const kLevelName[DVO_MAX_LEVELS] = {"track level 0", "track level 1", "track level 2", "track level 3", "track level 4",
                                                            "track level 5", "track level 6", "track level 7"};
-    for (int level = 0; level < g.levels; level++) {  // tracker.cpp:32
+    // adaptive schedule with a plan: k_plan's word says how many sequences track; with none, no level is launched at all
+    int n_levels = g.levels;
+    if (adaptive && plan && plan->ready) {
+        long spins = 0;
+        while (*plan->ready == 0) {
+            if (++spins > 2000000000L) {
+                (void)hipStreamSynchronize(s);
+                set_error("adaptive schedule: the GPU made no progress");
+                return DVO_ERR_HIP;
+            }
+            __builtin_ia32_pause();
+        }
+        if (*plan->ready - 1 == 0) n_levels = 0;
+    }
+    for (int level = 0; level < n_levels; level++) {  // tracker.cpp:32
         TraceRange tr(kLevelName[level]);
         const bool lists = tile_margin == 0 && !single_launch[level];  // (k_track_gn_tile keeps the per-sequence active flag test)
         const size_t level_px = (size_t)g.w[level] * g.h[level];
@@ -583,6 +609,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
                 if (ga.ref_wgt) ga.ref_wgt += q0 * level_px;
                 ga.state += q0;
                 ga.partials += (size_t)q0 * nblk[level] * 32;
+                // with a plan a level starts with the plan's sequences of this sub-batch, not all of them
+                const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
+                if (plan) ga.plan_action = plan->action + q0;
                 if (single_launch[level]) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
                     SolveArgs fa;
                     fa.state = state.as<SeqState>() + q0;
@@ -614,7 +643,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
                 }
                 // iteration `it` evaluates the sequences k_gn_solve(it - 1) left active (all of them when it == 0) and
                 // clears the list k_gn_solve(it) appends to
-                const int* list_prev = (first || !lists) ? nullptr : work_list(k, it - 1);
+                const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
                 ga.list = list_prev;
                 ga.next_count = lists ? work_list(k, it) : nullptr;
                 if (cfg.profile) {
@@ -1234,6 +1263,12 @@ Batch::~Batch()
     }
     if (ev_last_track) (void)hipEventDestroy(ev_last_track);
     for (int i = 0; i < 3; i++) if (ev_built[i]) (void)hipEventDestroy(ev_built[i]);
+    if (stream && (h_act[0] || h_ready)) (void)hipStreamSynchronize(stream);
+    for (int i = 0; i < 2; i++) {
+        if (h_act[i]) (void)hipHostFree(h_act[i]);
+        if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
+    }
+    if (h_ready) (void)hipHostFree(h_ready);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1264,8 +1299,18 @@ int Batch::init(int n, const float K9[9], int w, int h, int levels, int culls, c
 // One frame of every sequence from HOST memory: up to three buffers (float gray / depth / sigma, or raw rgb / depth16) go to the
 // staging slot of this push on the copy stream; the tracking stream waits for that copy only.  Slot k & 1 is reused by push k + 2,
 // whose copy waits until push k (pyramid build + tracking) is done with it.
+int Batch::check_actions_input(const FrameInput& in) const
+{
+    if (act_pending && cur >= 0 && weights_by_validity(fs[cur], in) != fs[cur].sigma_by_validity) {   // (a SKIP copies the weight storage)
+        set_error("dvo_batch_set_actions: a push with actions must keep the weight storage of the references (raw frames vs float maps)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    return DVO_OK;
+}
+
 int Batch::push_host_frame(const void* p0, size_t n0, const void* p1, size_t n1, const void* p2, size_t n2, FrameInput in)
 {
+    DVO_TRY(check_actions_input(in));   // (before the copies are queued)
     DVO_TRY(select_device(device));
     if (!cstream) {
         DVO_HIP(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
@@ -1311,6 +1356,7 @@ int Batch::push_host_frame(const void* p0, size_t n0, const void* p1, size_t n1,
 int Batch::prefetch(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
+    if (act_pending) { set_error("dvo_batch_prefetch: actions are pending for the next push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
     const int slot = free_slot();
     if (npre >= 2 || slot < 0) { set_error("dvo_batch_prefetch_device: two prefetched frames are already waiting for their push"); return DVO_ERR_NOT_READY; }
@@ -1328,27 +1374,142 @@ int Batch::push(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(device));
+    // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan)
+    const bool planned = act_pending || act_used;
+    DVO_TRY(check_actions_input(in));
     int target;
+    bool built = false;
     if (npre > 0 && pre_key[0][0] == in.key0() && pre_key[0][1] == in.key1()) {
         target = preq[0];                                   // built by prefetch: the tracker waits for that build
         DVO_HIP(hipStreamWaitEvent(stream, ev_built[target], 0));
         preq[0] = preq[1];
         for (int i = 0; i < 2; i++) pre_key[0][i] = pre_key[1][i];
         npre--;
+        built = true;
     } else {
         target = (cur < 0 && npre == 0) ? 0 : free_slot();
         if (target < 0) { set_error("dvo_batch_push_device: the frames prefetched must be pushed first, in order"); return DVO_ERR_BAD_ARGUMENT; }
-        build_pyramid(fs[target], in, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
     }
-    if (cur >= 0) {
-        DVO_TRY(trk.track(fs[target], fs[cur], stream));    // system.hpp:88
-        DVO_HIP(hipEventRecord(ev_last_track, stream));
-        tracked_once = true;
+    if (!planned) {
+        if (!built) build_pyramid(fs[target], in, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
+        if (cur >= 0) {
+            DVO_TRY(trk.track(fs[target], fs[cur], stream));    // system.hpp:88
+            DVO_HIP(hipEventRecord(ev_last_track, stream));
+            tracked_once = true;
+            have_poses = true;
+        }
+    } else {
+        // k_plan first (it reads only the actions and has_ref), then the pyramid: SKIP sequences copy their reference forward, so the
+        // whole new frame set becomes the reference below (cur = target) and k_track_gn addresses frame sets as it always does
+        const bool skips = act_pending;   // (without pending actions every sequence builds: a prefetched set needs nothing more)
+        DVO_TRY(launch_plan(cur >= 0));
+        if (!built) build_pyramid(fs[target], in, stream, /*keep_sigma=*/false, skips ? eff.as<uint8_t>() : nullptr, cur >= 0 ? &fs[cur] : &fs[target]);
+        if (cur >= 0) {
+            TrackPlan tp;
+            tp.action = eff.as<uint8_t>();
+            tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
+            tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
+            DVO_TRY(trk.track(fs[target], fs[cur], stream, &tp));
+            DVO_HIP(hipEventRecord(ev_last_track, stream));
+            tracked_once = true;
+        } else {   // no frame set to track against yet: every sequence starts (or stays without a reference); k_plan zeroed the twists
+            launch_export_poses(trk.state.as<SeqState>(), trk.xi_out.as<float>(), trk.T_out.as<float>(), n_seq, stream);
+        }
         have_poses = true;
+        act_pending = false;
+        act_used = true;
+        plan_parity ^= 1;
     }
+    n_push++;
     prev = cur;
     cur = target;                                           // system.hpp:91
     DVO_HIP(hipGetLastError());
+    return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: per-sequence actions
+int Batch::alloc_plan()
+{
+    if (has_ref.p) return DVO_OK;
+    DVO_TRY(act_dev.alloc((size_t)n_seq));
+    DVO_TRY(has_ref.alloc((size_t)n_seq));
+    DVO_TRY(eff.alloc((size_t)n_seq));
+    DVO_TRY(status.alloc(sizeof(int) * (size_t)n_seq));
+    DVO_TRY(plan_lists.alloc(2 * sizeof(int) * (size_t)trk.n_sub * (size_t)(n_seq + 4)));
+    DVO_TRY(plan_tally.alloc(2 * sizeof(int)));
+    for (int i = 0; i < 2; i++) {
+        DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_act[i]), (size_t)n_seq, hipHostMallocDefault));
+        DVO_HIP(hipEventCreateWithFlags(&ev_act[i], hipEventDisableTiming));
+    }
+    DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_ready), 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    h_ready[0] = h_ready[1] = 0;
+    DVO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_ready), h_ready, 0));
+    // in stream order: every sequence that a plain push gave a frame has a reference; the list counts start at zero
+    DVO_HIP(hipMemsetAsync(has_ref.p, cur >= 0 ? 1 : 0, has_ref.bytes, stream));
+    DVO_HIP(hipMemsetAsync(plan_lists.p, 0, plan_lists.bytes, stream));
+    DVO_HIP(hipMemsetAsync(plan_tally.p, 0, plan_tally.bytes, stream));
+    return DVO_OK;
+}
+
+int Batch::set_actions(const uint8_t* actions, bool on_device)
+{
+    if (npre > 0) { set_error("dvo_batch_set_actions: a prefetched frame is waiting for its push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
+    if (!actions) { act_pending = false; act_src = nullptr; return DVO_OK; }
+    DVO_TRY(select_device(device));
+    DVO_TRY(alloc_plan());
+    if (on_device) {
+        act_src = actions;   // read by k_plan in stream order
+    } else {
+        // copied now into pinned staging, then to the device in stream order (after the k_plan of every earlier push)
+        const int k = act_slot;
+        act_slot ^= 1;
+        if (act_staged[k]) DVO_HIP(hipEventSynchronize(ev_act[k]));   // (that copy was queued two calls ago)
+        memcpy(h_act[k], actions, (size_t)n_seq);
+        DVO_HIP(hipMemcpyAsync(act_dev.p, h_act[k], (size_t)n_seq, hipMemcpyHostToDevice, stream));
+        DVO_HIP(hipEventRecord(ev_act[k], stream));
+        act_staged[k] = true;
+        act_src = act_dev.as<uint8_t>();
+    }
+    act_pending = true;
+    return DVO_OK;
+}
+
+int Batch::launch_plan(bool track_follows)
+{
+    DVO_TRY(alloc_plan());
+    PlanArgs a;
+    memset(&a, 0, sizeof a);
+    a.actions = act_pending ? act_src : nullptr;
+    a.has_ref = has_ref.as<uint8_t>(); a.eff = eff.as<uint8_t>(); a.status = status.as<int>();
+    a.state = trk.state.as<SeqState>(); a.log = trk.log.as<dvo_track_log>(); a.levels = g.levels;
+    const size_t set = (size_t)trk.n_sub * (size_t)(n_seq + 4);
+    a.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
+    a.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
+    a.list_stride = n_seq + 4; a.n_sub = trk.n_sub; a.n_seq = n_seq;
+    if (trk.adaptive && track_follows) {   // Tracker::track waits for this word (the one of this parity was last used two plans ago)
+        h_ready[plan_parity] = 0;
+        a.ready = d_ready + plan_parity;
+        a.tally = plan_tally.as<int>();
+    }
+    dvo::launch_plan(a, stream);
+    DVO_HIP(hipGetLastError());
+    return DVO_OK;
+}
+
+int Batch::status_of_last(int* out, bool out_on_device)
+{
+    if (n_push == 0) { set_error("dvo_batch_last_status: nothing has been pushed yet"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    const size_t bytes = sizeof(int) * (size_t)n_seq;
+    if (!act_used) {   // plain pushes: the first one starts every sequence, every later one tracks every sequence
+        const int v = n_push == 1 ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
+        if (out_on_device) { DVO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), v, (size_t)n_seq, stream)); return DVO_OK; }
+        DVO_HIP(hipStreamSynchronize(stream));   // (as a read-back of the device buffer would)
+        for (int q = 0; q < n_seq; q++) out[q] = v;
+        return DVO_OK;
+    }
+    DVO_HIP(hipMemcpyAsync(out, status.p, bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
     return DVO_OK;
 }
 

@@ -90,8 +90,9 @@ struct FrameSet {  // n_seq frames: gray/depth/sigma pyramids, level l stored as
 
 // Builds pyramids of (gray, depth, sigma) device inputs [n_seq][src_h][src_w]; depth/sigma may be null.
 // keep_sigma = false: the sigma pyramid is only folded into `wgt`, not stored (frame-to-frame tracking never reads it again)
+// seq_action / copy_from (Batch plan): the sequences whose effective action is DVO_SEQ_SKIP read no input and take copy_from's values
 void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma = true,
-                   bool rows_decimated = false);
+                   bool rows_decimated = false, const uint8_t* seq_action = nullptr, const FrameSet* copy_from = nullptr);
 // One frame of every sequence as handed over by the caller: float maps (gray [+ depth + sigma]) or raw sensor frames
 // (u8 gray / RGB / RGBA [+ u16 depth], converted while the pyramid is built: loader.cpp:55-60,137-147, transform.cpp:60-76).
 struct FrameInput {
@@ -103,7 +104,10 @@ struct FrameInput {
     const void* key1() const { return raw() ? (const void*)depth16 : (const void*)depth; }
     bool has_depth() const { return raw() ? depth16 != nullptr : (depth != nullptr && sigma != nullptr); }
 };
-void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma = true);
+void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma = true, const uint8_t* seq_action = nullptr,
+                   const FrameSet* copy_from = nullptr);
+// the sigma_by_validity a build of `in` into `fs` with keep_sigma = false would leave (the weight storage of the frame set)
+inline bool weights_by_validity(const FrameSet& fs, const FrameInput& in) { return in.raw() && in.depth16 != nullptr && fs.allow_const_weight; }
 // Host -> device copy of n_img images (raw or float; rows of row_bytes bytes).  With culls > 0 and decimate set only every
 // 2^culls-th row of each image is transferred (one strided DMA): the pyramid never reads the others (Convert::cullImage keeps
 // pixels whose coordinates are multiples of 2^culls), so 1 - 2^-culls of the PCIe traffic carries nothing.  Returns the bytes
@@ -113,6 +117,13 @@ int upload_rows(void* dst, const void* src, size_t row_bytes, int img_rows, size
 inline bool can_decimate_rows(const Geometry& g) { return g.culls > 0 && (g.src_h % (1 << g.culls)) == 0; }
 // Frame::updateDepthSigma / updateDepth (frame.cpp:39-61): re-decimate from a top-level map (may alias the top level)
 void redecimate(FrameSet& fs, const float* depth_top, const float* sigma_top, hipStream_t s);
+
+// The per-sequence actions of one Batch push, resolved on the device by k_plan (Batch::launch_plan)
+struct TrackPlan {
+    const uint8_t* action = nullptr;   // [n_seq] effective action: only DVO_SEQ_TRACK sequences are evaluated
+    const int* lists = nullptr;        // n_sub lists ([0] = count, [4..] = local ids) of those sequences, n_seq + 4 ints apart
+    volatile int* ready = nullptr;     // adaptive schedule: mapped host word, (tracked sequences + 1) once k_plan has run; nullptr: none
+};
 
 struct Tracker {  // Track::Tracker for n_seq sequences at once
     Geometry g;
@@ -175,7 +186,8 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     GnParams level_params(int level) const;
     GnArgs gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const;
     // Tracker::track (tracker.cpp:22-85): enqueue the whole coarse-to-fine loop; poses land in xi_out / T_out
-    int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s);
+    // With a plan (Batch): k_plan has done k_track_begin's work, and a level's first iteration runs the plan's sequences, not all
+    int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);
     int collect_profile(hipStream_t s);
 };
 
@@ -294,6 +306,22 @@ struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sen
     }
     int prefetch(const FrameInput& in);
     int push(const FrameInput& in);
+    // Per-sequence skip / restart (dvo_batch_set_actions).  Allocated on first use; a batch that never sets actions runs the plain path.
+    DevBuf act_dev, has_ref, eff, status, plan_lists, plan_tally;
+    uint8_t* h_act[2] = {nullptr, nullptr};     // pinned staging of host actions, alternately (ev_act: their copy has been read)
+    hipEvent_t ev_act[2] = {nullptr, nullptr};
+    bool act_staged[2] = {false, false};
+    int act_slot = 0;
+    int* h_ready = nullptr;                     // mapped host words of TrackPlan::ready, one per plan parity
+    int* d_ready = nullptr;
+    const uint8_t* act_src = nullptr;           // actions of the next push (device memory)
+    bool act_pending = false, act_used = false;
+    int plan_parity = 0, n_push = 0;
+    int alloc_plan();
+    int set_actions(const uint8_t* actions, bool on_device);
+    int launch_plan(bool track_follows);
+    int status_of_last(int* out, bool out_on_device);
+    int check_actions_input(const FrameInput& in) const;
 };
 
 int select_device(int device);

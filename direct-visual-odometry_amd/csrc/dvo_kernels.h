@@ -38,6 +38,12 @@ struct PyramidArgs {
     // (src_h, culls) for a whole frame, (src_h >> culls, 0) when the host uploaded only the rows the pyramid keeps (upload_rows)
     int src_img_rows, src_row_shift;
     float raw_gray_scale, raw_depth_scale, raw_sigma_valid, raw_sigma_invalid;
+    // optional copy-forward (Batch plan, seq_action != nullptr): the workgroups of a sequence whose effective action is DVO_SEQ_SKIP
+    // read no input; they write what a build writes, taken from the reference set (same layout): gray / depth / sigma at the top
+    // level (lower levels are pass_valid of it, which is what a build stores there) and wgt level by level.
+    const uint8_t* seq_action;                 // [n_seq] effective action (k_plan)
+    const float* ref[3][DVO_MAX_LEVELS];       // gray, depth, sigma of the reference set
+    const float* ref_wgt[DVO_MAX_LEVELS];
 };
 
 // Grids of the per-(sequence, pixel) kernels: x = workgroups of one sequence, (y, z) = the sequence -- seq = z * 32768 + y, so the
@@ -77,6 +83,9 @@ struct GnArgs {
     // k_track_gn_tile only: 64 x (4*PPT) pixel tiles with the reference patch staged in LDS
     int tiles_x, tiles_y;    // nblk = tiles_x * tiles_y
     int margin;              // patch = tile grown by margin+1 (left/top) and margin+2 (right/bottom) pixels
+    // Batch plan: the effective action of each sequence of the launch (k_plan); only DVO_SEQ_TRACK sequences start a level.  Read by the
+    // kernels that test per-sequence flags (k_track_gn_tile, k_track_gn_fused, k_track_level); k_track_gn gets the plan's list instead.
+    const uint8_t* plan_action = nullptr;
 };
 
 struct PrepArgs {  // per-pixel constants of a reference frame, all levels in one launch
@@ -350,6 +359,23 @@ struct RegDecArgs {
 void launch_regularize_redecimate(const RegDecArgs& a, hipStream_t s);
 
 void launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
+
+// k_plan: the per-sequence actions of one Batch push (dvo_batch_set_actions), resolved on the device before the pyramid is built.
+struct PlanArgs {
+    const uint8_t* actions;  // [n_seq] requested actions; nullptr = every sequence DVO_SEQ_TRACK
+    uint8_t* has_ref;        // [n_seq] in / out: the sequence has a reference frame
+    uint8_t* eff;            // [n_seq] out: effective action (DVO_SEQ_SKIP / TRACK / RESTART)
+    int* status;             // [n_seq] out: DVO_SEQ_TRACKED / SKIPPED / STARTED / BAD_ACTION
+    SeqState* state;         // [n_seq] what k_track_begin writes; active = 1 for tracked sequences only
+    dvo_track_log* log;      // [n_seq] levels + n_iter reset
+    int levels;
+    int* lists;              // n_sub lists of list_stride ints ([0] = count, [4..] = local ids): the tracked sequences per sub-batch
+    int* lists_clear;        // the other set of lists: their counts are cleared here for the next plan
+    int list_stride, n_sub, n_seq;
+    int* tally;              // optional (with `ready`): two device counters, zero between launches
+    int* ready;              // optional, mapped HOST memory: the last workgroup stores (tracked sequences + 1)
+};
+void launch_plan(const PlanArgs& a, hipStream_t s);
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s);
 void launch_gradient(const float* img, int w, int h, int xdir, float* out, hipStream_t s);
 void launch_warp_image(const float* gray, const float* depth, int w, int h, const Intr& k, const Pose& pose, float* out, hipStream_t s);

@@ -135,6 +135,9 @@ __device__ __forceinline__ void split_index(int i, int w, float inv_w, int& x, i
 // One thread per TOP-level pixel reads src(x<<culls, y<<culls) once and writes every level it lands on
 // (level t shifts below the top keep pixels whose coordinates are multiples of 2^t).
 // ------------------------------------------------------------------------------------------------
+// PLAN (Batch plan, PyramidArgs::seq_action): the workgroups of a DVO_SEQ_SKIP sequence copy the reference set's values forward instead
+// (the sequence comes from blockIdx.y/z: the branch is uniform per workgroup).  PLAN = false is the plain build.
+template <bool PLAN>
 __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
 {
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
@@ -143,6 +146,34 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     if (i >= tw * th || seq >= a.n_seq) return;
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
+    if constexpr (PLAN) {
+        if (a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy-forward: every value this thread's build would write, none of its input
+            const int T = a.levels - 1;
+            const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x;
+            bool have[3];
+            have[0] = true;
+            have[1] = have[2] = a.raw_rgb != nullptr ? a.raw_depth != nullptr : false;
+            if (a.raw_rgb == nullptr)
+                for (int m = 0; m < 3; m++) have[m] = a.src[m] != nullptr;
+            const bool prep = a.wgt[0] != nullptr && have[1] && have[2];
+            float top[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int m = 0; m < 3; m++)
+                if (have[m] && a.dst[m][T] != nullptr) top[m] = __builtin_nontemporal_load(a.ref[m][T] + ot);
+            for (int t = 0; t < a.levels; t++) {
+                const int msk = (1 << t) - 1;
+                if ((x & msk) | (y & msk)) break;
+                const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
+                if (lx >= a.w[l] || ly >= a.h[l]) continue;
+                const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+#pragma unroll
+                for (int m = 0; m < 3; m++)
+                    if (have[m] && a.dst[m][l] != nullptr) __builtin_nontemporal_store(t == 0 ? top[m] : pass_valid(top[m]), a.dst[m][l] + o);
+                if (prep) __builtin_nontemporal_store(__builtin_nontemporal_load(a.ref_wgt[l] + o), a.wgt[l] + o);
+            }
+            return;
+        }
+    }
     const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + (x << a.culls);
     float raw[3] = {0.0f, 0.0f, 0.0f};
     bool have[3];
@@ -194,7 +225,8 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
 // two dwordx2/x4 loads, and writes its four top-level values per map as one dwordx4 store.  Same conversions, same float
 // operations as k_ingest + k_pyramid: bit-identical (tests/test_frontend_and_eval.py).
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-template <int CULLS>
+typedef float f4 __attribute__((ext_vector_type(4)));
+template <int CULLS, bool PLAN>
 __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
 {
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1], gw = tw >> 2;
@@ -204,6 +236,43 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
     int y, xg;
     split_index(gi, gw, a.inv_tw * 4.0f, xg, y);   // (4 / tw = 1 / gw up to an ulp: split_index corrects +-1)
     const int x0 = xg << 2;
+    if constexpr (PLAN) {
+        if (a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy-forward (see k_pyramid): the four top-level values per map, one 16-byte load each
+            const bool dep = a.raw_depth != nullptr, prep = a.wgt[0] != nullptr && dep;
+            const int T = a.levels - 1;
+            const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x0;
+            f4 top[3];
+#pragma unroll
+            for (int m = 0; m < 3; m++) {
+                top[m] = f4{0.0f, 0.0f, 0.0f, 0.0f};
+                if ((m == 0 || dep) && a.dst[m][T] != nullptr) {
+                    top[m] = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref[m][T] + ot));
+                    __builtin_nontemporal_store(top[m], reinterpret_cast<f4*>(a.dst[m][T] + ot));
+                }
+            }
+            if (prep) __builtin_nontemporal_store(__builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref_wgt[T] + ot)),
+                                                  reinterpret_cast<f4*>(a.wgt[T] + ot));
+            for (int t = 1; t < a.levels; t++) {
+                const int msk = (1 << t) - 1;
+                if (y & msk) break;
+                const int l = a.levels - 1 - t, ly = y >> t;
+                if (ly >= a.h[l]) continue;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const int x = x0 + k;
+                    if (x & msk) continue;
+                    const int lx = x >> t;
+                    if (lx >= a.w[l]) continue;
+                    const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+#pragma unroll
+                    for (int m = 0; m < 3; m++)
+                        if ((m == 0 || dep) && a.dst[m][l] != nullptr) __builtin_nontemporal_store(pass_valid(top[m][k]), a.dst[m][l] + o);
+                    if (prep) __builtin_nontemporal_store(__builtin_nontemporal_load(a.ref_wgt[l] + o), a.wgt[l] + o);
+                }
+            }
+            return;
+        }
+    }
     const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + ((size_t)x0 << CULLS);
     constexpr int GW = 1 << CULLS;       // 32-bit words of gray bytes this thread reads (2 or 4)
     unsigned gwords[GW], dwords[2 * GW];
@@ -240,7 +309,6 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
     {
         const int l = a.levels - 1;
         const size_t o = (size_t)seq * tw * th + (size_t)y * tw + x0;
-        typedef float f4 __attribute__((ext_vector_type(4)));
         f4 v[3], wgv;
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -738,6 +806,7 @@ __global__ void __launch_bounds__(256) k_track_gn_tile(GnArgs a)
     const int seq = id / a.nblk, tile = id - seq * a.nblk;
     const SeqState& st = a.state[seq];
     if (!a.ignore_active && st.active == 0) return;  // converged sequences cost nothing
+    if (a.plan_action && a.plan_action[seq] != DVO_SEQ_TRACK) return;   // not tracked by this push (Batch plan): ignore_active does not enable it
     const Pose pose = st.pose;
     const int w = a.w, h = a.h;
     constexpr int TH = 4 * PPT;
@@ -1077,7 +1146,8 @@ __global__ void __launch_bounds__(256) k_track_gn_fused(GnArgs a, SolveArgs sa, 
             __hip_atomic_store(f.progress, act + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
     };
-    if (!sa.ignore_active && st.active == 0) {                   // converged sequence: its first tile reports, nobody works
+    const bool off = a.plan_action && a.plan_action[seq] != DVO_SEQ_TRACK;   // not tracked by this push (Batch plan)
+    if (off || (!sa.ignore_active && st.active == 0)) {          // converged sequence: its first tile reports, nobody works
         if (blk == a.blk_first && threadIdx.x == 0) report(0);
         return;
     }
@@ -1368,6 +1438,7 @@ __global__ void __launch_bounds__(256) k_track_level(GnArgs ga, SolveArgs sa)
     __shared__ float pose_s[12];
     __shared__ int flag_s;
     const int seq = blockIdx.x;
+    if (ga.plan_action && ga.plan_action[seq] != DVO_SEQ_TRACK) return;   // not tracked by this push (Batch plan)
     SeqState& st = sa.state[seq];
     // thread 0 owns the serial state of the sequence across iterations
     float xi[6];
@@ -1447,6 +1518,65 @@ __global__ void __launch_bounds__(256) k_track_begin(SeqState* state, dvo_track_
         log[s].levels = levels;
         for (int l = 0; l < DVO_MAX_LEVELS; l++) log[s].n_iter[l] = 0;
     }
+}
+
+// k_plan: the actions of one Batch push (dvo_batch_set_actions), one thread per sequence.  Resolves the effective action and status,
+// updates has_ref, resets every SeqState and log as k_track_begin does (active only for the sequences that track), and compacts
+// the tracked sequences into one list per sub-batch (the Tracker::work_list format, local ids): workgroup-local slots from LDS
+// counters, one global atomic per (workgroup, sub-batch).  List order is irrelevant to the results (as in k_gn_solve).
+__global__ void __launch_bounds__(256) k_plan(PlanArgs a)
+{
+    __shared__ int cnt[8], base[8];
+    const int s = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (threadIdx.x < 8) cnt[threadIdx.x] = 0;
+    if (blockIdx.x == 0 && (int)threadIdx.x < a.n_sub) a.lists_clear[(size_t)threadIdx.x * a.list_stride] = 0;
+    __syncthreads();
+    int sub = 0, local = -1, pos = 0;
+    if (s < a.n_seq) {
+        const int req = a.actions ? (int)a.actions[s] : DVO_SEQ_TRACK;
+        const int had = a.has_ref[s] != 0;
+        int eff, status;
+        if (req == DVO_SEQ_TRACK && had) { eff = DVO_SEQ_TRACK; status = DVO_SEQ_TRACKED; }
+        else if (req == DVO_SEQ_TRACK || req == DVO_SEQ_RESTART) { eff = DVO_SEQ_RESTART; status = DVO_SEQ_STARTED; }
+        else { eff = DVO_SEQ_SKIP; status = req == DVO_SEQ_SKIP ? DVO_SEQ_SKIPPED : DVO_SEQ_BAD_ACTION; }
+        a.eff[s] = (uint8_t)eff;
+        a.status[s] = status;
+        if (eff != DVO_SEQ_SKIP) a.has_ref[s] = 1;
+        SeqState& st = a.state[s];
+        for (int i = 0; i < 6; i++) st.xi[i] = 0.0f;
+        for (int i = 0; i < 9; i++) st.pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+        for (int i = 0; i < 3; i++) st.pose.t[i] = 0.0f;
+        for (int i = 0; i < 12; i++) st.Tc[i] = (i < 9 && i % 4 == 0) ? 1.0 : 0.0;
+        st.active = eff == DVO_SEQ_TRACK ? 1 : 0;
+        st.iter = 0;
+        a.log[s].levels = a.levels;
+        for (int l = 0; l < DVO_MAX_LEVELS; l++) a.log[s].n_iter[l] = 0;
+        if (eff == DVO_SEQ_TRACK) {   // sub-batch k holds [n_seq * k / n_sub, n_seq * (k + 1) / n_sub) (Tracker::sub_first)
+            int q0 = 0;
+            for (int k = 1; k < a.n_sub; k++) {
+                const int f = (int)(((long long)a.n_seq * k) / a.n_sub);
+                if (s >= f) { sub = k; q0 = f; }
+            }
+            local = s - q0;
+            pos = atomicAdd(&cnt[sub], 1);
+        }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < a.n_sub && cnt[threadIdx.x] > 0)
+        base[threadIdx.x] = atomicAdd(&a.lists[(size_t)threadIdx.x * a.list_stride], cnt[threadIdx.x]);
+    if (a.ready && threadIdx.x == 0) {   // the adaptive schedule's word: the last workgroup to finish publishes the tracked count
+        int n = 0;
+        for (int k = 0; k < a.n_sub && k < 8; k++) n += cnt[k];
+        __hip_atomic_fetch_add(&a.tally[0], n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int t = __hip_atomic_fetch_add(&a.tally[1], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == (int)gridDim.x - 1) {
+            const int total = __hip_atomic_load(&a.tally[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            a.tally[0] = 0; a.tally[1] = 0;   // (zero for the next launch: kernel boundary)
+            __hip_atomic_store(a.ready, total + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    __syncthreads();
+    if (local >= 0) a.lists[(size_t)sub * a.list_stride + 4 + base[sub] + pos] = local;
 }
 
 // k_set_pose: load a caller-supplied twist (operator-level gn_step / probes)
@@ -1732,13 +1862,25 @@ void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
         for (const void* p : tops) aligned = aligned && (reinterpret_cast<uintptr_t>(p) % 16) == 0;
         aligned = aligned && ((size_t)tw * th % 4) == 0;
     }
+    const bool plan = a.seq_action != nullptr;
+    if (plan) {   // copy-forward: the reference tops are read with the same 16-byte accesses
+        const int T = a.levels - 1;
+        const void* tops[4] = {a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]};
+        for (const void* p : tops) aligned = aligned && (reinterpret_cast<uintptr_t>(p) % 16) == 0;
+    }
     if (vec && aligned) {
         const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)n_seq);
-        if (a.culls == 1) hipLaunchKernelGGL(k_pyramid_raw4<1>, grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pyramid_raw4<2>, grid, dim3(256), 0, s, a);
+        if (plan) {
+            if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, true>), grid, dim3(256), 0, s, a);
+            else hipLaunchKernelGGL((k_pyramid_raw4<2, true>), grid, dim3(256), 0, s, a);
+            return;
+        }
+        if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, false>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_pyramid_raw4<2, false>), grid, dim3(256), 0, s, a);
         return;
     }
-    hipLaunchKernelGGL(k_pyramid, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+    if (plan) hipLaunchKernelGGL(k_pyramid<true>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_pyramid<false>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
 }
 
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s)
@@ -1914,6 +2056,11 @@ void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s)
 void launch_track_begin(SeqState* state, dvo_track_log* log, int n_seq, int levels, hipStream_t s)
 {
     hipLaunchKernelGGL(k_track_begin, dim3(cdiv(n_seq, 256)), dim3(256), 0, s, state, log, n_seq, levels);
+}
+
+void launch_plan(const PlanArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_plan, dim3(cdiv((unsigned)a.n_seq, 256)), dim3(256), 0, s, a);
 }
 
 void launch_set_pose(SeqState* state, const float* xi_dev, int n_seq, hipStream_t s)

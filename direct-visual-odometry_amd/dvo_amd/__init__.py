@@ -97,7 +97,12 @@ EXPORTS = [
     "dvo_eval_ate", "dvo_eval_rpe", "dvo_pose_inverse", "dvo_traj_write_tum",
     "dvo_vo_save", "dvo_vo_load", "dvo_vo_set_history_limit", "dvo_op_visualize", "dvo_ppm_write",
     "dvo_selftest_reciprocal", "dvo_selftest_sqrt", "dvo_selftest_division", "dvo_selftest_trig",
+    "dvo_batch_set_actions", "dvo_batch_last_status", "dvo_batch_copy_status_device",
 ]
+
+# per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
+SEQ_SKIP, SEQ_TRACK, SEQ_RESTART = 0, 1, 2
+SEQ_TRACKED, SEQ_SKIPPED, SEQ_STARTED, SEQ_BAD_ACTION = 0, 1, 2, 3
 
 _lib = None
 
@@ -570,6 +575,29 @@ class Batch:
         log = TrackLog()
         _check(lib().dvo_batch_last_track_log(self._p, seq, C.byref(log)))
         return log.to_dict()
+
+    def set_actions(self, actions, on_device=False):
+        """Per-sequence action of the NEXT push (SEQ_SKIP / SEQ_TRACK / SEQ_RESTART): a numpy uint8 [n_seq] (copied now), an int device
+        pointer to uint8 [n_seq] with on_device=True (read in stream order when the push runs), or None to clear."""
+        if actions is None:
+            _check(lib().dvo_batch_set_actions(self._p, None, 0))
+        elif on_device:
+            _check(lib().dvo_batch_set_actions(self._p, C.c_void_p(int(actions)), 1))
+        else:
+            a = np.ascontiguousarray(actions, np.uint8)
+            if a.shape != (self.n_seq,):
+                raise ValueError("set_actions: expected uint8[%d], got shape %s" % (self.n_seq, a.shape))
+            _check(lib().dvo_batch_set_actions(self._p, a.ctypes.data_as(C.c_void_p), 0))
+
+    def last_status(self):
+        """int32 [n_seq]: SEQ_TRACKED / SEQ_SKIPPED / SEQ_STARTED / SEQ_BAD_ACTION of the last push (synchronises)."""
+        st = np.zeros(self.n_seq, np.int32)
+        _check(lib().dvo_batch_last_status(self._p, st.ctypes.data_as(C.c_void_p)))
+        return st
+
+    def copy_status_device(self, ptr):
+        """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""
+        _check(lib().dvo_batch_copy_status_device(self._p, C.c_void_p(int(ptr))))
 
     def synchronize(self):
         _check(lib().dvo_batch_synchronize(self._p))

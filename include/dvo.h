@@ -167,6 +167,37 @@ int dvo_batch_last_poses(dvo_batch* b, float* xi_rel, float* T_rel);
 int dvo_batch_copy_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_dev);
 int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log);
 int dvo_batch_synchronize(dvo_batch* b);
+/* ---- per-sequence skip and restart (sensor-depth batches) -------------------------------------------------------------------
+ * dvo_batch_set_actions gives every sequence an action for the NEXT push (any of dvo_batch_push_device / _host / _raw_device /
+ * _raw_host); afterwards the actions are spent.  actions[n_seq]: host memory (actions_on_device = 0) is copied before the call
+ * returns; device memory (actions_on_device = 1) is read in stream order on the handle's stream when that push runs, under the
+ * same rule as the push_device inputs (so actions can be computed on the GPU, e.g. from the previous poses).  NULL clears them.
+ *   SKIP     the sequence's input slot is never read (it may hold anything); its reference stays the frame it had; its relative
+ *            pose is the zero twist / identity T and its track log has n_iter = 0 on every level.  A SKIP on a sequence with no
+ *            reference leaves it without one.
+ *   TRACK    as a plain push, bit for bit: track against the sequence's reference, then the frame becomes the reference.
+ *            On a sequence with no reference yet it acts as RESTART.
+ *   RESTART  forget the reference: the frame is the sequence's first frame (system.hpp:83-86), pose zero / identity.
+ * Whether a sequence has a reference is per-sequence device state, empty after dvo_batch_create.  A batch that never sets
+ * actions runs exactly the launches it always ran; dvo_batch_last_status then reports all STARTED after the first push and
+ * all TRACKED after later ones.  Once a batch has used actions, a push without dvo_batch_set_actions is an all-TRACK push of
+ * the per-sequence path (a sequence skipped from the start then reports STARTED), and every such push has poses
+ * (dvo_batch_last_poses), even one in which no sequence tracked.
+ * Errors, returned before anything is enqueued: a mono batch or a NULL handle -> DVO_ERR_BAD_ARGUMENT; actions together with
+ * prefetch are not supported: set_actions while a prefetched frame waits, or dvo_batch_prefetch_* while actions are pending ->
+ * DVO_ERR_NOT_READY; a push with actions whose weight storage differs from the current references' (float maps after raw frames
+ * or the reverse) -> DVO_ERR_BAD_ARGUMENT.  Mono batches (dvo_batch_create_mono) advance in lockstep and refuse actions. */
+#define DVO_SEQ_SKIP    0   /* no frame for this sequence this step: input slot NOT read, reference kept */
+#define DVO_SEQ_TRACK   1   /* as today: track against the sequence's reference, then the frame becomes the reference */
+#define DVO_SEQ_RESTART 2   /* forget the reference: the frame is the sequence's first frame (system.hpp:83-86) */
+/* per-sequence outcome of the last push */
+#define DVO_SEQ_TRACKED    0
+#define DVO_SEQ_SKIPPED    1
+#define DVO_SEQ_STARTED    2   /* RESTART, or TRACK on a sequence that had no reference yet */
+#define DVO_SEQ_BAD_ACTION 3   /* action value not in {0,1,2}: handled as SKIP */
+int dvo_batch_set_actions(dvo_batch* b, const uint8_t* actions, int actions_on_device);   /* [n_seq]; NULL clears */
+int dvo_batch_last_status(dvo_batch* b, int* status);             /* [n_seq], host, synchronises; DVO_ERR_NOT_READY before the first push */
+int dvo_batch_copy_status_device(dvo_batch* b, int* status_dev);  /* [n_seq], async device-to-device copy on the handle's stream */
 /* ---- one block of sequences per GPU (BASELINE config 5) -------------------------------------------
  * The path shards across sequences only (frame t of a sequence tracks against state from frames < t: system.hpp:48,57,67): every
  * rank -- one process per GPU -- owns a contiguous block of the sequences and tracks it with no communication.

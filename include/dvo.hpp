@@ -153,6 +153,16 @@ public:
         check(dvo_batch_last_poses(b_, nullptr, out[0].data()));
         return out;
     }
+    // per-sequence action of the next push (DVO_SEQ_SKIP / TRACK / RESTART, [n_seq]; nullptr clears), see dvo_batch_set_actions
+    void setActions(const uint8_t* actions, bool onDevice = false) { check(dvo_batch_set_actions(b_, actions, onDevice ? 1 : 0)); }
+    // per-sequence outcome of the last push (DVO_SEQ_TRACKED / SKIPPED / STARTED / BAD_ACTION)
+    std::vector<int> lastStatus()
+    {
+        std::vector<int> out(n_);
+        check(dvo_batch_last_status(b_, out.data()));
+        return out;
+    }
+    void copyStatusDevice(int* statusDev) { check(dvo_batch_copy_status_device(b_, statusDev)); }
     dvo_batch* handle() { return b_; }
 
 private:
