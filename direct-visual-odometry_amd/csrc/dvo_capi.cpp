@@ -362,6 +362,21 @@ int dvo_batch_set_actions(dvo_batch* b, const uint8_t* actions, int actions_on_d
     return b->impl.set_actions(actions, actions_on_device != 0);
 }
 
+int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_intrinsics: a mono batch has one K (per-sequence intrinsics need dvo_batch_create)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->impl.set_intrinsics(K);
+}
+
+int dvo_batch_get_intrinsics(dvo_batch* b, float* K)
+{
+    if (!b || !K) return DVO_ERR_BAD_ARGUMENT;
+    DVO_NOT_MONO(b);
+    memcpy(K, b->impl.cam_K.data(), sizeof(float) * b->impl.cam_K.size());
+    return DVO_OK;
+}
+
 int dvo_batch_last_status(dvo_batch* b, int* status)
 {
     if (!b || !status) return DVO_ERR_BAD_ARGUMENT;

@@ -154,6 +154,16 @@ int make_geometry(const float K[9], int w, int h, int levels, int culls, Geometr
     return DVO_OK;
 }
 
+void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS])
+{   // make_geometry's steps, in its order: cull to the pyramid base, then to each level
+    float Kb[9], Kl[9];
+    cull_intrinsic(K, g.culls, Kb);
+    for (int i = 0; i < g.levels; i++) {
+        cull_intrinsic(Kb, g.levels - 1 - i, Kl);
+        out[i] = make_intr(Kl);
+    }
+}
+
 static float level_step(const dvo_config& c, int level)
 {  // optimize.cpp:22-26
     if (level == 1) return c.step_level1;
@@ -379,6 +389,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
         if ((size_t)nblk[l] > max_part) max_part = nblk[l];
     }
     DVO_TRY(state.alloc(sizeof(SeqState) * (size_t)n_seq));
+    part_rows = max_part;
     DVO_TRY(partials.alloc(sizeof(float) * 32 * max_part * (size_t)n_seq));
     DVO_TRY(log.alloc(sizeof(dvo_track_log) * (size_t)n_seq));
     DVO_TRY(counters.alloc(2 * sizeof(unsigned long long)));
@@ -608,10 +619,13 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 ga.obj_gray += q0 * level_px; ga.ref_gray += q0 * level_px; ga.ref_depth += q0 * level_px;
                 if (ga.ref_wgt) ga.ref_wgt += q0 * level_px;
                 ga.state += q0;
-                ga.partials += (size_t)q0 * nblk[level] * 32;
+                // (a level-independent stride: with q0 * nblk[level], sub-batch k at a coarse level wrote into the rows of sub-batch k - 1
+                //  at a finer level while both ran -- the nondeterminism of track_streams = 2 recorded in DESIGN.md section 12)
+                ga.partials += (size_t)q0 * part_rows * 32;
                 // with a plan a level starts with the plan's sequences of this sub-batch, not all of them
                 const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
                 if (plan) ga.plan_action = plan->action + q0;
+                if (plan && plan->seq_k) ga.seq_k = plan->seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
                 if (single_launch[level]) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
                     SolveArgs fa;
                     fa.state = state.as<SeqState>() + q0;
@@ -1269,6 +1283,11 @@ Batch::~Batch()
         if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
     }
     if (h_ready) (void)hipHostFree(h_ready);
+    if (stream && h_cam[0]) (void)hipStreamSynchronize(stream);
+    for (int i = 0; i < 2; i++) {
+        if (h_cam[i]) (void)hipHostFree(h_cam[i]);
+        if (ev_cam[i]) (void)hipEventDestroy(ev_cam[i]);
+    }
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1281,6 +1300,10 @@ int Batch::init(int n, const float K9[9], int w, int h, int levels, int culls, c
     if (cfg.stream) stream = (hipStream_t)cfg.stream;
     else { DVO_HIP(hipStreamCreate(&stream)); own_stream = true; }
     DVO_TRY(make_geometry(K9, w, h, levels, culls, g));
+    memcpy(K_create, K9, sizeof K_create);
+    cam_K.resize((size_t)n * 9);
+    for (int q = 0; q < n; q++) memcpy(&cam_K[(size_t)q * 9], K9, 9 * sizeof(float));
+    cam_K_used = cam_K;
     for (int i = 0; i < 3; i++) DVO_TRY(fs[i].alloc(g, n, cfg));
     DVO_TRY(trk.init(g, n, cfg));
     {   // lowest priority: the pyramid build should fill what the tracker leaves idle, not compete with it
@@ -1374,8 +1397,8 @@ int Batch::push(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(device));
-    // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan)
-    const bool planned = act_pending || act_used;
+    // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan), or per-sequence intrinsics
+    const bool planned = act_pending || act_used || cam_used;
     DVO_TRY(check_actions_input(in));
     int target;
     bool built = false;
@@ -1409,6 +1432,7 @@ int Batch::push(const FrameInput& in)
             tp.action = eff.as<uint8_t>();
             tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
             tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
+            tp.seq_k = cam_table();
             DVO_TRY(trk.track(fs[target], fs[cur], stream, &tp));
             DVO_HIP(hipEventRecord(ev_last_track, stream));
             tracked_once = true;
@@ -1418,6 +1442,7 @@ int Batch::push(const FrameInput& in)
         have_poses = true;
         act_pending = false;
         act_used = true;
+        if (cam_pending) { cam_K_used = cam_K; cam_pending = false; }   // (k_plan has read this push's camera-changed bytes)
         plan_parity ^= 1;
     }
     n_push++;
@@ -1486,6 +1511,7 @@ int Batch::launch_plan(bool track_follows)
     a.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
     a.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
     a.list_stride = n_seq + 4; a.n_sub = trk.n_sub; a.n_seq = n_seq;
+    a.cam_changed = cam_pending ? cam_changed() : nullptr;
     if (trk.adaptive && track_follows) {   // Tracker::track waits for this word (the one of this parity was last used two plans ago)
         h_ready[plan_parity] = 0;
         a.ready = d_ready + plan_parity;
@@ -1510,6 +1536,53 @@ int Batch::status_of_last(int* out, bool out_on_device)
     }
     DVO_HIP(hipMemcpyAsync(out, status.p, bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
     if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
+    return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: per-sequence intrinsics
+int Batch::set_intrinsics(const float* K)
+{
+    if (npre > 0) { set_error("dvo_batch_set_intrinsics: a prefetched frame is waiting for its push"); return DVO_ERR_NOT_READY; }
+    const size_t n = (size_t)n_seq;
+    if (K) {
+        for (size_t q = 0; q < n; q++) {
+            const float* k = K + q * 9;
+            for (int i = 0; i < 9; i++)
+                if (!std::isfinite(k[i])) { set_error("dvo_batch_set_intrinsics: sequence " + std::to_string(q) + ": K has a non-finite entry"); return DVO_ERR_BAD_ARGUMENT; }
+            if (!(k[0] > 0.0f) || !(k[4] > 0.0f)) { set_error("dvo_batch_set_intrinsics: sequence " + std::to_string(q) + ": fx and fy must be > 0"); return DVO_ERR_BAD_ARGUMENT; }
+        }
+    }
+    DVO_TRY(select_device(device));
+    const size_t table = sizeof(Intr) * (size_t)g.levels * n, bytes = table + n;
+    if (!cam_dev.p) {
+        DVO_TRY(cam_dev.alloc(bytes));
+        for (int i = 0; i < 2; i++) {
+            DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_cam[i]), bytes, hipHostMallocDefault));
+            DVO_HIP(hipEventCreateWithFlags(&ev_cam[i], hipEventDisableTiming));
+        }
+    }
+    // pinned staging (the copy of two calls ago has been read by then), then one copy in stream order: every push queued before
+    // this call has finished reading the device table when it is overwritten, and the next push reads the new one
+    const int k = cam_slot;
+    cam_slot ^= 1;
+    if (cam_staged[k]) DVO_HIP(hipEventSynchronize(ev_cam[k]));
+    Intr* tab = reinterpret_cast<Intr*>(h_cam[k]);
+    uint8_t* changed = h_cam[k] + table;
+    for (size_t q = 0; q < n; q++) {
+        const float* kq = K ? K + q * 9 : K_create;
+        Intr lv[DVO_MAX_LEVELS];
+        level_intrinsics(kq, g, lv);
+        for (int l = 0; l < g.levels; l++) tab[(size_t)l * n + q] = lv[l];
+        // camera-change rule: fx, fy, cx or cy differ in bits from the table of the last push
+        const float* ku = &cam_K_used[q * 9];
+        changed[q] = (memcmp(&kq[0], &ku[0], 4) | memcmp(&kq[4], &ku[4], 4) | memcmp(&kq[2], &ku[2], 4) | memcmp(&kq[5], &ku[5], 4)) != 0;
+        memcpy(&cam_K[q * 9], kq, 9 * sizeof(float));
+    }
+    DVO_HIP(hipMemcpyAsync(cam_dev.p, h_cam[k], bytes, hipMemcpyHostToDevice, stream));
+    DVO_HIP(hipEventRecord(ev_cam[k], stream));
+    cam_staged[k] = true;
+    cam_pending = true;
+    cam_used = true;
     return DVO_OK;
 }
 

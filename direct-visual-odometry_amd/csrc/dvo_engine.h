@@ -66,6 +66,8 @@ struct Geometry {  // pyramid shape of Frame(gray, K, levels, culls): frame.hpp:
     int top() const { return levels - 1; }
 };
 int make_geometry(const float K[9], int w, int h, int levels, int culls, Geometry& g);
+// The per-level Intr make_geometry derives from K for the pyramid shape of g (the same operations: the same bits)
+void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS]);
 
 struct FrameSet {  // n_seq frames: gray/depth/sigma pyramids, level l stored as [n_seq][h_l][w_l]
     Geometry g;
@@ -123,6 +125,7 @@ struct TrackPlan {
     const uint8_t* action = nullptr;   // [n_seq] effective action: only DVO_SEQ_TRACK sequences are evaluated
     const int* lists = nullptr;        // n_sub lists ([0] = count, [4..] = local ids) of those sequences, n_seq + 4 ints apart
     volatile int* ready = nullptr;     // adaptive schedule: mapped host word, (tracked sequences + 1) once k_plan has run; nullptr: none
+    const Intr* seq_k = nullptr;       // per-sequence intrinsics [level][n_seq] (dvo_batch_set_intrinsics); nullptr: Geometry::k
 };
 
 struct Tracker {  // Track::Tracker for n_seq sequences at once
@@ -130,6 +133,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int n_seq = 0;
     dvo_config cfg;
     DevBuf state, partials, log, counters, xi_out, T_out;
+    // partial rows reserved per sequence: the largest nblk of any level.  A sub-batch's rows start at q0 * part_rows on every level,
+    // so sub-batches on concurrent streams, which reach the levels at different times, never share a row
+    size_t part_rows = 0;
     // Two active-sequence lists per sub-batch ([0] = count, [4..] = ids local to the sub-batch), written by k_gn_solve,
     // read by the next k_track_gn.
     DevBuf work;
@@ -322,6 +328,19 @@ struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sen
     int launch_plan(bool track_follows);
     int status_of_last(int* out, bool out_on_device);
     int check_actions_input(const FrameInput& in) const;
+    // Per-sequence intrinsics (dvo_batch_set_intrinsics).  Allocated on first use; once set, every push runs the per-sequence path.
+    float K_create[9] = {0};                    // the K of dvo_batch_create (set_intrinsics(NULL) goes back to it)
+    std::vector<float> cam_K;                   // [n_seq][9] the table of the next push (creation K until set)
+    std::vector<float> cam_K_used;              // [n_seq][9] the table of the last push (the camera-change rule compares the two)
+    DevBuf cam_dev;                             // [level][n_seq] Intr, then [n_seq] camera-changed bytes of the next push
+    uint8_t* h_cam[2] = {nullptr, nullptr};     // pinned staging of cam_dev, alternately (ev_cam: their copy has been read)
+    hipEvent_t ev_cam[2] = {nullptr, nullptr};
+    bool cam_staged[2] = {false, false};
+    int cam_slot = 0;
+    bool cam_pending = false, cam_used = false;
+    int set_intrinsics(const float* K);
+    const Intr* cam_table() const { return cam_used ? cam_dev.as<Intr>() : nullptr; }
+    const uint8_t* cam_changed() const { return reinterpret_cast<const uint8_t*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq); }
 };
 
 int select_device(int device);

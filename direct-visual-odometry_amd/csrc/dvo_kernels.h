@@ -86,6 +86,9 @@ struct GnArgs {
     // Batch plan: the effective action of each sequence of the launch (k_plan); only DVO_SEQ_TRACK sequences start a level.  Read by the
     // kernels that test per-sequence flags (k_track_gn_tile, k_track_gn_fused, k_track_level); k_track_gn gets the plan's list instead.
     const uint8_t* plan_action = nullptr;
+    // Per-sequence intrinsics (dvo_batch_set_intrinsics): the level's row of the Batch table, one Intr per sequence of the launch.
+    // Set: the per-camera instantiations run and load seq_k[seq] once per workgroup (scalar loads); nullptr: every sequence uses `k`.
+    const Intr* seq_k = nullptr;
 };
 
 struct PrepArgs {  // per-pixel constants of a reference frame, all levels in one launch
@@ -374,6 +377,7 @@ struct PlanArgs {
     int list_stride, n_sub, n_seq;
     int* tally;              // optional (with `ready`): two device counters, zero between launches
     int* ready;              // optional, mapped HOST memory: the last workgroup stores (tracked sequences + 1)
+    const uint8_t* cam_changed;  // optional [n_seq]: 1 = the sequence's intrinsics change at this push, so it loses its reference first
 };
 void launch_plan(const PlanArgs& a, hipStream_t s);
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s);

@@ -551,6 +551,17 @@ __global__ void __launch_bounds__(256) k_prep_ref(PrepArgs a)
     a.wgt[i] = gn_weight(step, a.sigma_min, a.sigma_max, a.sigma[i]);
 }
 
+// The intrinsics a tracking kernel uses for its sequence: a.k, or (PCAM: the per-camera instantiations) `cam`, the sequence's entry
+// of the per-sequence table GnArgs::seq_k, which the kernel loads once at its start -- ahead of every store and barrier, so the
+// 24 bytes (wave-uniform address) arrive by scalar loads into SGPRs.  Called at each use, with a.k not bound to a local: PCAM =
+// false is then the very code it always was (binding it, or passing it as a used parameter, reschedules k_track_gn).
+template <bool PCAM>
+__device__ __forceinline__ const Intr& seq_intr(const GnArgs& a, const Intr& cam)
+{
+    if constexpr (PCAM) return cam;
+    else return a.k;
+}
+
 // LDS of one gn_tile() evaluation (the caller owns it: k_track_gn once, k_track_level once per tile and iteration)
 template <int PPT>
 struct GnTileLds {
@@ -561,18 +572,19 @@ struct GnTileLds {
 
 // gn_tile: one 256 x PPT pixel tile (`blk`) of sequence `seq` at pose `pose` -> its 32-float partial row `out_row`
 // (global or LDS).  Called by all 256 threads of a workgroup; contains two barriers.
+// PCAM: the sequence's own intrinsics `cam` instead of a.k (seq_intr; `cam` is unused otherwise).
 // T2D: the tile is 64 columns x 4*PPT rows (lane = column, wave w owns rows w*PPT .. w*PPT+PPT-1) instead of 256*PPT
 // consecutive raster pixels.  Used when the level width is a multiple of 64: only tiles on the image border then hold
 // deferred (border) pixels, a thread's pixels share their column (one int->float conversion and one (x - cx) for PPT
 // pixels) and there is no row-wrap arithmetic.
-template <int PPT, int G, bool MASK, bool T2D>
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row);
+                                        float* out_row, const Intr& cam);
 
-template <int PPT, int G, bool MASK, bool T2D = false>
 #if !defined(DVO_GN_WAVES)
 #define DVO_GN_WAVES 6   /* waves per SIMD the hot variants are compiled for: 6 = up to 84 VGPRs (78 used, no scratch); at 7 (72 VGPRs) the border sampler spills 24 bytes per lane: 54 MB of extra HBM writes per full-batch launch for the same speed (profiles/r03_patch_sampler_ab.txt) */
 #endif
+template <int PPT, int G, bool MASK, bool T2D = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) k_track_gn(GnArgs a)
 {
     __shared__ GnTileLds<PPT> lds;
@@ -598,13 +610,40 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) 
     const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
     const int seq = a.list ? a.list[4 + slot] : slot;
     const Pose pose = a.state[seq].pose;              // wave-uniform -> scalar loads
-    gn_tile<PPT, G, MASK, T2D>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32);
+    gn_tile<PPT, G, MASK, T2D>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, a.k);
     clear_next();
 }
 
-template <int PPT, int G, bool MASK, bool T2D>
+// k_track_gn with per-sequence intrinsics (dvo_batch_set_intrinsics, GnArgs::seq_k): line for line k_track_gn, with gn_tile's PCAM
+// set.  (A separate kernel rather than a fifth template parameter, and a copy rather than a shared inline body: either of those
+// changed the default k_track_gn's instruction schedule.)
+template <int PPT, int G, bool MASK, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) k_track_gn_cam(GnArgs a)
+{
+    __shared__ GnTileLds<PPT> lds;
+    auto clear_next = [&]() {
+        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
+            if (threadIdx.x == 0) *a.next_count = 0;
+        }
+    };
+    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
+    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
+    const int tile_id = xcd * t8 + tile_in_xcd;
+    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
+        clear_next();
+        return;
+    }
+    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
+    const int seq = a.list ? a.list[4 + slot] : slot;
+    const Pose pose = a.state[seq].pose;
+    const Intr cam = a.seq_k[seq];
+    gn_tile<PPT, G, MASK, T2D, true>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam);
+    clear_next();
+}
+
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row)
+                                        float* out_row, const Intr& cam)
 {
     float (&red)[4][32] = lds.red;
     int (&slow_q)[4][PPT * 64] = lds.slow_q;
@@ -686,7 +725,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             if (a.prm.crop) crop_ok = (xs[k] >= 20) & (xs[k] <= 140) & (ys[k] >= 20) & (ys[k] <= 100);  // wave-uniform branch
             gate[k] = inA[g0 + k] & crop_ok & !(d[k] < a.prm.min_depth) & !is_invalid(I1[k]);
             iz[k] = recip_gated(d[k], gate[k]);   // 1.0f / depth (optimize.cpp:70-74) of the pixels that can contribute
-            warp(pose, a.k, (float)xs[k], (float)ys[k], d[k], u[k], v[k]);
+            warp(pose, seq_intr<PCAM>(a, cam), (float)xs[k], (float)ys[k], d[k], u[k], v[k]);
             inter[k] = gate[k] & (u[k] >= 1.0f) & (v[k] >= 1.0f) & (u[k] < wlim) & (v[k] < hlim);  // false for NaN
             x0[k] = inter[k] ? (int)u[k] : 1;
             y0[k] = inter[k] ? (int)v[k] : 1;
@@ -733,7 +772,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             // predicated accumulation: rejected pixels add exact zeros, so no control flow merges the 29 accumulators
             const bool ok = okf[k];
             float J[6], r, rw;
-            gn_jacobian_pre(a.k, xs[k], ys[k], d[k], iz[k], wg[k], gx[k], gy[k], I1[k], I2[k], J, r, rw);
+            gn_jacobian_pre(seq_intr<PCAM>(a, cam), xs[k], ys[k], d[k], iz[k], wg[k], gx[k], gy[k], I1[k], I2[k], J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
@@ -754,7 +793,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             // (carrying d and I1 through LDS with the index instead of re-loading them: measured in the LAT form, no change)
             const float d = dep[i], I1 = obj[i], iz = recip_gated(dep[i], true), wg = wgp ? wgp[i] : a.wgt_const;
             float u, v;
-            warp(pose, a.k, (float)x, (float)y, d, u, v);  // same operations on the same inputs as in the main loop
+            warp(pose, seq_intr<PCAM>(a, cam), (float)x, (float)y, d, u, v);  // same operations on the same inputs as in the main loop
             // inlined (single site): a call here would pin the 29 live accumulators to callee-saved registers and
             // raise the kernel's VGPR allocation.  (Tried: the sampler on a register patch of 12 taps loaded up front from
             // clamped coordinates -- one round trip, no divergent loads.  Slower by 20 % on the probe: the branches of the
@@ -763,7 +802,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             ss.ok = gn_sample_patch(refp, w, h, d, u, v, ss.I2, ss.gx, ss.gy) ? 1 : 0;
             const bool ok = ss.ok != 0;
             float J[6], r, rw;
-            gn_jacobian_pre(a.k, x, y, d, iz, wg, ss.gx, ss.gy, I1, ss.I2, J, r, rw);
+            gn_jacobian_pre(seq_intr<PCAM>(a, cam), x, y, d, iz, wg, ss.gx, ss.gy, I1, ss.I2, J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
@@ -796,7 +835,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
 // leaves the staged patch (large motion) gather from global memory; borders / INVALID taps take the generic
 // sampler.  All three sources hold the same floats, so results are bit-identical.
 // ------------------------------------------------------------------------------------------------
-template <int PPT, bool MASK>
+template <int PPT, bool MASK, bool PCAM>   // PCAM: per-sequence intrinsics (seq_intr)
 __global__ void __launch_bounds__(256) k_track_gn_tile(GnArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];  // [0,128): reduction scratch, then the patch
@@ -808,6 +847,8 @@ __global__ void __launch_bounds__(256) k_track_gn_tile(GnArgs a)
     if (!a.ignore_active && st.active == 0) return;  // converged sequences cost nothing
     if (a.plan_action && a.plan_action[seq] != DVO_SEQ_TRACK) return;   // not tracked by this push (Batch plan): ignore_active does not enable it
     const Pose pose = st.pose;
+    Intr cam;
+    if constexpr (PCAM) cam = a.seq_k[seq];   // (before the patch stores and the barrier: scalar loads)
     const int w = a.w, h = a.h;
     constexpr int TH = 4 * PPT;
     const int tyi = tile / a.tiles_x, txi = tile - tyi * a.tiles_x;
@@ -852,7 +893,7 @@ __global__ void __launch_bounds__(256) k_track_gn_tile(GnArgs a)
         const bool gate = (x < w) & (y < h) & (crop_ok != 0) & !(d[k] < a.prm.min_depth) & !is_invalid(I1[k]);
         iz[k] = recip_gated(d[k], gate);
         float u, v;
-        warp(pose, a.k, (float)x, (float)y, d[k], u, v);
+        warp(pose, seq_intr<PCAM>(a, cam), (float)x, (float)y, d[k], u, v);
         const bool inter = gate & (u >= 1.0f) & (v >= 1.0f) & (u < wlim) & (v < hlim);  // false for NaN
         const int x0 = inter ? (int)u : 1, y0 = inter ? (int)v : 1;
         const bool inpatch = inter & (x0 - 1 >= px0) & (x0 + 2 < px1) & (y0 - 1 >= py0) & (y0 + 2 < py1);
@@ -884,7 +925,7 @@ __global__ void __launch_bounds__(256) k_track_gn_tile(GnArgs a)
         }
         const bool ok = s > 0;
         float J[6], r, rw;
-        gn_jacobian_pre(a.k, x, y, d[k], iz[k], wg[k], gx, gy, I1[k], I2, J, r, rw);
+        gn_jacobian_pre(seq_intr<PCAM>(a, cam), x, y, d[k], iz[k], wg[k], gx, gy, I1[k], I2, J, r, rw);
 #pragma unroll
         for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
         acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
@@ -1128,7 +1169,7 @@ struct FusedArgs {
     int n_seq;
 };
 
-template <int PPT, int G, bool T2D>
+template <int PPT, int G, bool T2D, bool PCAM>   // PCAM: per-sequence intrinsics (seq_intr)
 __global__ void __launch_bounds__(256) k_track_gn_fused(GnArgs a, SolveArgs sa, FusedArgs f)
 {
     __shared__ GnTileLds<PPT> lds;
@@ -1152,7 +1193,9 @@ __global__ void __launch_bounds__(256) k_track_gn_fused(GnArgs a, SolveArgs sa, 
         return;
     }
     const Pose pose = st.pose;                                   // wave-uniform -> scalar loads
-    gn_tile<PPT, G, false, T2D>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32);
+    Intr cam;
+    if constexpr (PCAM) cam = a.seq_k[seq];
+    gn_tile<PPT, G, false, T2D, PCAM>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // this wave's row stores have left
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1275,10 +1318,10 @@ __global__ void __launch_bounds__(256) k_track_persist(PersistArgs p)   // expon
             for (int t = me; t < L.blk_count; t += n_work) {
                 float* row = p.partials + (size_t)(L.blk_first + t) * 32;
                 if constexpr (PPT == 4) {
-                    if (L.t2d) gn_tile<PPT, G, false, true>(a, pose, 0, L.blk_first + t, lds, row);
-                    else gn_tile<PPT, G, false, false>(a, pose, 0, L.blk_first + t, lds, row);
+                    if (L.t2d) gn_tile<PPT, G, false, true>(a, pose, 0, L.blk_first + t, lds, row, a.k);
+                    else gn_tile<PPT, G, false, false>(a, pose, 0, L.blk_first + t, lds, row, a.k);
                 } else {
-                    gn_tile<PPT, G, false, false>(a, pose, 0, L.blk_first + t, lds, row);
+                    gn_tile<PPT, G, false, false>(a, pose, 0, L.blk_first + t, lds, row, a.k);
                 }
                 __syncthreads();   // (the next tile reuses the LDS scratch)
             }
@@ -1428,7 +1471,7 @@ __global__ void __launch_bounds__(256) k_track_persist(PersistArgs p)   // expon
 // sequence stops.  A dependent kernel boundary costs ~8 us on this GPU, whatever the kernel does: for levels of a few
 // tiles the 2 x max_iterations launches of the unfused schedule were all boundary; here there is one.
 // ------------------------------------------------------------------------------------------------
-template <int PPT, int G>
+template <int PPT, int G, bool PCAM>   // PCAM: per-sequence intrinsics (seq_intr)
 __global__ void __launch_bounds__(256) k_track_level(GnArgs ga, SolveArgs sa)
 {
     __shared__ GnTileLds<PPT> lds;
@@ -1439,6 +1482,8 @@ __global__ void __launch_bounds__(256) k_track_level(GnArgs ga, SolveArgs sa)
     __shared__ int flag_s;
     const int seq = blockIdx.x;
     if (ga.plan_action && ga.plan_action[seq] != DVO_SEQ_TRACK) return;   // not tracked by this push (Batch plan)
+    Intr cam;
+    if constexpr (PCAM) cam = ga.seq_k[seq];   // (ahead of every store and barrier: scalar loads)
     SeqState& st = sa.state[seq];
     // thread 0 owns the serial state of the sequence across iterations
     float xi[6];
@@ -1464,7 +1509,7 @@ __global__ void __launch_bounds__(256) k_track_level(GnArgs ga, SolveArgs sa)
         for (int i = 0; i < 9; i++) pose.R[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pose_s[i])));
 #pragma unroll
         for (int i = 0; i < 3; i++) pose.t[i] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, pose_s[9 + i])));
-        for (int blk = live0; blk < live1; blk++) gn_tile<PPT, G, false, false>(ga, pose, seq, blk, lds, rows[blk]);
+        for (int blk = live0; blk < live1; blk++) gn_tile<PPT, G, false, false, PCAM>(ga, pose, seq, blk, lds, rows[blk], cam);
         __syncthreads();
         {  // second reduction stage, as in k_gn_solve (rows outside the live range are exact zeros)
             double s = 0.0;
@@ -1534,7 +1579,9 @@ __global__ void __launch_bounds__(256) k_plan(PlanArgs a)
     int sub = 0, local = -1, pos = 0;
     if (s < a.n_seq) {
         const int req = a.actions ? (int)a.actions[s] : DVO_SEQ_TRACK;
-        const int had = a.has_ref[s] != 0;
+        // a reference belongs to the camera it was taken with: a sequence whose intrinsics change at this push has none
+        const int changed = a.cam_changed ? (int)a.cam_changed[s] : 0;
+        const int had = a.has_ref[s] != 0 && !changed;
         int eff, status;
         if (req == DVO_SEQ_TRACK && had) { eff = DVO_SEQ_TRACK; status = DVO_SEQ_TRACKED; }
         else if (req == DVO_SEQ_TRACK || req == DVO_SEQ_RESTART) { eff = DVO_SEQ_RESTART; status = DVO_SEQ_STARTED; }
@@ -1542,6 +1589,7 @@ __global__ void __launch_bounds__(256) k_plan(PlanArgs a)
         a.eff[s] = (uint8_t)eff;
         a.status[s] = status;
         if (eff != DVO_SEQ_SKIP) a.has_ref[s] = 1;
+        else if (changed) a.has_ref[s] = 0;
         SeqState& st = a.state[s];
         for (int i = 0; i < 6; i++) st.xi[i] = 0.0f;
         for (int i = 0; i < 9; i++) st.pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
@@ -1905,6 +1953,18 @@ template <int PPT, int G>
 static void launch_track_gn_t(const GnArgs& a, unsigned tiles, hipStream_t s)
 {
     const unsigned g = (tiles + 7u) & ~7u;  // a multiple of 8: blockIdx % 8 is the XCD
+    if (a.seq_k) {   // per-sequence intrinsics: the same choice among the k_track_gn_cam instantiations
+        if constexpr (PPT == 4) {
+            if (gn_tiling(a.w, a.h, PPT, a.prm.crop).t2d) {
+                if (a.mask) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, true, true>), dim3(g), dim3(256), 0, s, a);
+                else hipLaunchKernelGGL((k_track_gn_cam<PPT, G, false, true>), dim3(g), dim3(256), 0, s, a);
+                return;
+            }
+        }
+        if (a.mask) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, true>), dim3(g), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_track_gn_cam<PPT, G, false>), dim3(g), dim3(256), 0, s, a);
+        return;
+    }
     if constexpr (PPT == 4) {
         if (gn_tiling(a.w, a.h, PPT, a.prm.crop).t2d) {  // 2-D tiles
             if (a.mask) hipLaunchKernelGGL((k_track_gn<PPT, G, true, true>), dim3(g), dim3(256), 0, s, a);
@@ -1959,10 +2019,18 @@ bool launch_track_gn_fused(const GnArgs& a0, const SolveArgs& sa0, int n_seq, in
     FusedArgs f{ticket, report, progress, n_seq};
     const dim3 grid((unsigned)a.blk_count * (unsigned)n_seq);
     const int key = ppt * 10 + group;
-    if (key == 11) hipLaunchKernelGGL((k_track_gn_fused<1, 1, false>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 22) hipLaunchKernelGGL((k_track_gn_fused<2, 2, false>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 42 && tl.t2d) hipLaunchKernelGGL((k_track_gn_fused<4, 2, true>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 42) hipLaunchKernelGGL((k_track_gn_fused<4, 2, false>), grid, dim3(256), 0, s, a, sa, f);
+    if (a.seq_k) {   // per-sequence intrinsics
+        if (key == 11) hipLaunchKernelGGL((k_track_gn_fused<1, 1, false, true>), grid, dim3(256), 0, s, a, sa, f);
+        else if (key == 22) hipLaunchKernelGGL((k_track_gn_fused<2, 2, false, true>), grid, dim3(256), 0, s, a, sa, f);
+        else if (key == 42 && tl.t2d) hipLaunchKernelGGL((k_track_gn_fused<4, 2, true, true>), grid, dim3(256), 0, s, a, sa, f);
+        else if (key == 42) hipLaunchKernelGGL((k_track_gn_fused<4, 2, false, true>), grid, dim3(256), 0, s, a, sa, f);
+        else return false;
+        return true;
+    }
+    if (key == 11) hipLaunchKernelGGL((k_track_gn_fused<1, 1, false, false>), grid, dim3(256), 0, s, a, sa, f);
+    else if (key == 22) hipLaunchKernelGGL((k_track_gn_fused<2, 2, false, false>), grid, dim3(256), 0, s, a, sa, f);
+    else if (key == 42 && tl.t2d) hipLaunchKernelGGL((k_track_gn_fused<4, 2, true, false>), grid, dim3(256), 0, s, a, sa, f);
+    else if (key == 42) hipLaunchKernelGGL((k_track_gn_fused<4, 2, false, false>), grid, dim3(256), 0, s, a, sa, f);
     else return false;
     return true;
 }
@@ -2017,15 +2085,21 @@ void launch_track_level(const GnArgs& ga0, const SolveArgs& sa0, int n_seq, hipS
     const GnTiling tl = gn_tiling(ga.w, ga.h, 4, ga.prm.crop);  // (the caller made sure these are raster tiles: !tl.t2d)
     ga.blk_first = tl.live_first; ga.blk_count = tl.live_count;
     sa.list_in = nullptr; sa.list_out = nullptr; sa.result = nullptr;
-    hipLaunchKernelGGL((k_track_level<4, 2>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
+    if (ga.seq_k) hipLaunchKernelGGL((k_track_level<4, 2, true>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
+    else hipLaunchKernelGGL((k_track_level<4, 2, false>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
 }
 
 template <int PPT>
 static void launch_track_gn_tile_t(const GnArgs& a, const dim3& grid, hipStream_t s)
 {
     const size_t lds = (128 + (size_t)(4 * PPT + 2 * a.margin + 3) * (64 + 2 * a.margin + 3)) * sizeof(float);
-    if (a.mask) hipLaunchKernelGGL((k_track_gn_tile<PPT, true>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_track_gn_tile<PPT, false>), grid, dim3(256), lds, s, a);
+    if (a.seq_k) {   // per-sequence intrinsics
+        if (a.mask) hipLaunchKernelGGL((k_track_gn_tile<PPT, true, true>), grid, dim3(256), lds, s, a);
+        else hipLaunchKernelGGL((k_track_gn_tile<PPT, false, true>), grid, dim3(256), lds, s, a);
+        return;
+    }
+    if (a.mask) hipLaunchKernelGGL((k_track_gn_tile<PPT, true, false>), grid, dim3(256), lds, s, a);
+    else hipLaunchKernelGGL((k_track_gn_tile<PPT, false, false>), grid, dim3(256), lds, s, a);
 }
 
 void launch_track_gn_tile(const GnArgs& a, int n_seq, int ppt, hipStream_t s)

@@ -98,6 +98,7 @@ EXPORTS = [
     "dvo_vo_save", "dvo_vo_load", "dvo_vo_set_history_limit", "dvo_op_visualize", "dvo_ppm_write",
     "dvo_selftest_reciprocal", "dvo_selftest_sqrt", "dvo_selftest_division", "dvo_selftest_trig",
     "dvo_batch_set_actions", "dvo_batch_last_status", "dvo_batch_copy_status_device",
+    "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -594,6 +595,23 @@ class Batch:
         st = np.zeros(self.n_seq, np.int32)
         _check(lib().dvo_batch_last_status(self._p, st.ctypes.data_as(C.c_void_p)))
         return st
+
+    def set_intrinsics(self, K):
+        """Per-sequence camera intrinsics from the NEXT push on: float [n_seq, 3, 3] or [n_seq, 9] (row-major, copied now), or None for
+        the creation K of every sequence.  A sequence whose fx, fy, cx or cy change loses its reference at that push (include/dvo.h)."""
+        if K is None:
+            _check(lib().dvo_batch_set_intrinsics(self._p, None))
+            return
+        k = np.ascontiguousarray(K, np.float32)
+        if k.shape not in ((self.n_seq, 3, 3), (self.n_seq, 9)):
+            raise ValueError("set_intrinsics: expected float[%d, 3, 3] or float[%d, 9], got shape %s" % (self.n_seq, self.n_seq, k.shape))
+        _check(lib().dvo_batch_set_intrinsics(self._p, k.ctypes.data_as(C.c_void_p)))
+
+    def intrinsics(self):
+        """float32 [n_seq, 3, 3]: the intrinsics the next push uses (the creation K until set_intrinsics)."""
+        k = np.zeros((self.n_seq, 3, 3), np.float32)
+        _check(lib().dvo_batch_get_intrinsics(self._p, k.ctypes.data_as(C.c_void_p)))
+        return k
 
     def copy_status_device(self, ptr):
         """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""

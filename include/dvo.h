@@ -198,6 +198,24 @@ int dvo_batch_synchronize(dvo_batch* b);
 int dvo_batch_set_actions(dvo_batch* b, const uint8_t* actions, int actions_on_device);   /* [n_seq]; NULL clears */
 int dvo_batch_last_status(dvo_batch* b, int* status);             /* [n_seq], host, synchronises; DVO_ERR_NOT_READY before the first push */
 int dvo_batch_copy_status_device(dvo_batch* b, int* status_dev);  /* [n_seq], async device-to-device copy on the handle's stream */
+/* ---- per-sequence camera intrinsics (sensor-depth batches) ------------------------------------------------------------------
+ * dvo_batch_set_intrinsics gives every sequence its own K: K[n_seq][9], host memory, row-major 3x3 (fx = K[0], cx = K[2],
+ * fy = K[4], cy = K[5]), copied before the call returns; NULL puts every sequence back on the K of dvo_batch_create.  The table
+ * takes effect at the NEXT push (any of the four push entry points) and stays in force after it.  The frame size, pyramid shape,
+ * configuration and raw depth_scale stay per handle.  Each level's intrinsics are derived from K exactly as dvo_batch_create
+ * derives them, so a sequence tracks bit for bit as a one-sequence batch created with its K would.
+ * Camera-change rule: a reference frame belongs to the camera it was taken with.  A sequence whose fx, fy, cx or cy differ (in
+ * bits) at a push from the table of the previous push loses its reference at that push, before its action is resolved:
+ *   TRACK (or no actions)  starts instead: status DVO_SEQ_STARTED, zero twist, identity T; the frame becomes its reference
+ *   SKIP / bad action      reported as usual (SKIPPED / BAD_ACTION); the sequence is left without a reference
+ *   RESTART                unchanged
+ * Once intrinsics have been set, every push runs the per-sequence path (as after dvo_batch_set_actions); a batch that never sets
+ * them runs exactly the launches it always ran.  dvo_batch_probe_gn keeps using the creation K.
+ * Errors, returned before anything is enqueued: a mono batch, a NULL handle, or a K with a non-finite entry or fx / fy <= 0 ->
+ * DVO_ERR_BAD_ARGUMENT; a prefetched frame waiting for its push -> DVO_ERR_NOT_READY.
+ * dvo_batch_get_intrinsics copies the table the next push uses ([n_seq][9], host, synchronous): the creation K until set. */
+int dvo_batch_set_intrinsics(dvo_batch* b, const float* K);   /* [n_seq][9]; NULL = the creation K for every sequence */
+int dvo_batch_get_intrinsics(dvo_batch* b, float* K);         /* [n_seq][9] */
 /* ---- one block of sequences per GPU (BASELINE config 5) -------------------------------------------
  * The path shards across sequences only (frame t of a sequence tracks against state from frames < t: system.hpp:48,57,67): every
  * rank -- one process per GPU -- owns a contiguous block of the sequences and tracks it with no communication.

@@ -163,6 +163,14 @@ public:
         return out;
     }
     void copyStatusDevice(int* statusDev) { check(dvo_batch_copy_status_device(b_, statusDev)); }
+    // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
+    void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
+    std::vector<Mat3> intrinsics()
+    {
+        std::vector<Mat3> out(n_);
+        check(dvo_batch_get_intrinsics(b_, out[0].data()));
+        return out;
+    }
     dvo_batch* handle() { return b_; }
 
 private:
