@@ -154,14 +154,27 @@ int make_geometry(const float K[9], int w, int h, int levels, int culls, Geometr
     return DVO_OK;
 }
 
-void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS])
+void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS], float (*K9_out)[9])
 {   // make_geometry's steps, in its order: cull to the pyramid base, then to each level
     float Kb[9], Kl[9];
     cull_intrinsic(K, g.culls, Kb);
     for (int i = 0; i < g.levels; i++) {
         cull_intrinsic(Kb, g.levels - 1 - i, Kl);
         out[i] = make_intr(Kl);
+        if (K9_out) memcpy(K9_out[i], Kl, sizeof Kl);
     }
+}
+
+int check_intrinsics(const char* who, const float* K, size_t n)
+{
+    if (!K) { set_error(std::string(who) + ": K is NULL"); return DVO_ERR_BAD_ARGUMENT; }
+    for (size_t q = 0; q < n; q++) {
+        const float* k = K + q * 9;
+        for (int i = 0; i < 9; i++)
+            if (!std::isfinite(k[i])) { set_error(std::string(who) + ": sequence " + std::to_string(q) + ": K has a non-finite entry"); return DVO_ERR_BAD_ARGUMENT; }
+        if (!(k[0] > 0.0f) || !(k[4] > 0.0f)) { set_error(std::string(who) + ": sequence " + std::to_string(q) + ": fx and fy must be > 0"); return DVO_ERR_BAD_ARGUMENT; }
+    }
+    return DVO_OK;
 }
 
 static float level_step(const dvo_config& c, int level)
@@ -506,7 +519,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
 {
     last_obj = &obj; last_ref = &ref;
     persist_used = false;
-    if (persist_ok && !persist_failed && h_result && !plan) {   // the whole call in one launch (k_track_persist)
+    // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
+    const Intr* seq_k = plan ? plan->seq_k : cam_k;
+    if (persist_ok && !persist_failed && h_result && !plan && !cam_k) {   // the whole call in one launch (k_track_persist)
         PersistArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.levels = g.levels;
@@ -625,7 +640,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 // with a plan a level starts with the plan's sequences of this sub-batch, not all of them
                 const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
                 if (plan) ga.plan_action = plan->action + q0;
-                if (plan && plan->seq_k) ga.seq_k = plan->seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
+                if (seq_k) ga.seq_k = seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
                 if (single_launch[level]) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
                     SolveArgs fa;
                     fa.state = state.as<SeqState>() + q0;
@@ -1544,14 +1559,7 @@ int Batch::set_intrinsics(const float* K)
 {
     if (npre > 0) { set_error("dvo_batch_set_intrinsics: a prefetched frame is waiting for its push"); return DVO_ERR_NOT_READY; }
     const size_t n = (size_t)n_seq;
-    if (K) {
-        for (size_t q = 0; q < n; q++) {
-            const float* k = K + q * 9;
-            for (int i = 0; i < 9; i++)
-                if (!std::isfinite(k[i])) { set_error("dvo_batch_set_intrinsics: sequence " + std::to_string(q) + ": K has a non-finite entry"); return DVO_ERR_BAD_ARGUMENT; }
-            if (!(k[0] > 0.0f) || !(k[4] > 0.0f)) { set_error("dvo_batch_set_intrinsics: sequence " + std::to_string(q) + ": fx and fy must be > 0"); return DVO_ERR_BAD_ARGUMENT; }
-        }
-    }
+    if (K) DVO_TRY(check_intrinsics("dvo_batch_set_intrinsics", K, n));
     DVO_TRY(select_device(device));
     const size_t table = sizeof(Intr) * (size_t)g.levels * n, bytes = table + n;
     if (!cam_dev.p) {

@@ -66,8 +66,12 @@ struct Geometry {  // pyramid shape of Frame(gray, K, levels, culls): frame.hpp:
     int top() const { return levels - 1; }
 };
 int make_geometry(const float K[9], int w, int h, int levels, int culls, Geometry& g);
-// The per-level Intr make_geometry derives from K for the pyramid shape of g (the same operations: the same bits)
-void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS]);
+// The per-level Intr make_geometry derives from K for the pyramid shape of g (the same operations: the same bits), and optionally
+// the culled per-level K9 it derives them from
+void level_intrinsics(const float K[9], const Geometry& g, Intr out[DVO_MAX_LEVELS], float (*K9_out)[9] = nullptr);
+// Per-sequence intrinsics tables K[n][9] (dvo_batch_set_intrinsics, dvo_batch_create_mono_cameras): every entry finite, fx > 0 and
+// fy > 0.  Otherwise DVO_ERR_BAD_ARGUMENT, with `who` and the index of the first bad sequence in the error message.
+int check_intrinsics(const char* who, const float* K, size_t n);
 
 struct FrameSet {  // n_seq frames: gray/depth/sigma pyramids, level l stored as [n_seq][h_l][w_l]
     Geometry g;
@@ -168,6 +172,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // One launch per track() call (k_track_persist) for a single sequence whose result is handed over through h_result: eligible
     // when every level fits the kernel's wide reduction and shares one tile size; `persist_failed` = a launch gave up waiting
     // (GPU oversubscribed): the handle then stays on the launch-per-iteration schedule.
+    // per-sequence intrinsics [level][n_seq] of a per-camera mono batch (dvo_batch_create_mono_cameras), used when track() has no
+    // plan (a plan brings its own, TrackPlan::seq_k); nullptr: Geometry::k.  Never set together with prefer_persist.
+    const Intr* cam_k = nullptr;
     bool prefer_persist = false;   // set before init() by the owner whose results go through enable_host_result() (VisualOdometry's sensor-depth tracker)
     bool persist_ok = false, persist_failed = false, persist_used = false;
     int persist_grid = 0, persist_spin_limit = 1 << 18;
@@ -374,7 +381,13 @@ struct MonoBatch {
     float* depth_alt = nullptr;  // the second top-level depth buffer of `ref` (k_regularize_redecimate ping-pongs between the two)
     int latest_id = -1;      // Frame::latest_id, frame.cpp:5 (all sequences advance in lockstep)
     bool have_init = false;
-    int init(int n, const float K9[9], int w, int h, int ring, const dvo_config* c);
+    // Per-camera batch (dvo_batch_create_mono_cameras): [level][n_seq] Intr (the tracker's table, Tracker::cam_k; its top-level row
+    // is the mapping kernels' Intr), then [n_seq] MapK (culled top-level K9 + k_sparse).  Fixed at creation.  Empty: one K.
+    DevBuf cam_dev;
+    const Intr* cam_top() const { return cam_dev.p ? cam_dev.as<Intr>() + (size_t)g.top() * n_seq : nullptr; }
+    const MapK* cam_map() const { return cam_dev.p ? reinterpret_cast<const MapK*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq) : nullptr; }
+    // K: [9] for every sequence, or (per_camera) [n][9], one per sequence
+    int init(int n, const float* K, int w, int h, int ring, const dvo_config* c, bool per_camera = false);
     ~MonoBatch();
     int set_initial_depth(const float* depth_host, const float* sigma_host);              // one map, broadcast to every sequence
     int set_initial_depth_device(const float* depth_dev, const float* sigma_dev);         // [n_seq][th][tw]

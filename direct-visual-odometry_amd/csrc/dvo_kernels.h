@@ -287,6 +287,17 @@ struct AgeTableArgs {  // k_age_table: AgeEntry of every retained keyframe, once
     int* zero_word = nullptr; // optional: cleared by this launch (the single handle's valid-update counter, UpdateArgs::valid_updates)
 };
 
+// The culled top-level K of one sequence of a per-camera mono batch, as the mapping kernels read it (UpdateArgs::seq_K9)
+struct MapK {
+    float K9[9];
+    int k_sparse;   // k9_sparse(K9)
+};
+// K9 = [fx 0 cx; 0 fy cy; 0 0 1] exactly: depthEstimate may skip the products with the zeros (UpdateArgs::k_sparse)
+inline int k9_sparse(const float K9[9])
+{
+    return (K9[1] == 0.0f && K9[3] == 0.0f && K9[6] == 0.0f && K9[7] == 0.0f && K9[8] == 1.0f) ? 1 : 0;
+}
+
 struct UpdateArgs {
     float* ref_depth; float* ref_sigma; float* ref_age;   // [n_seq][h][w], in place (top level of the reference keyframes)
     const float* obj_gray;                                 // [n_seq][h][w]
@@ -304,6 +315,10 @@ struct UpdateArgs {
     Pose rel_pose;           // exp(+rel_xi)          } operator level only (meta == nullptr)
     float rel_tz;            // rel_xi[2]             }
     int* valid_updates;      //                       }
+    // Per-sequence intrinsics (dvo_batch_create_mono_cameras): the top-level row of the tracker's [level][n_seq] Intr table and
+    // each sequence's culled top-level K9 + k_sparse.  Set: k_depth_update_cam runs and reads them instead of k / K9 / k_sparse.
+    const Intr* seq_k = nullptr;
+    const MapK* seq_K9 = nullptr;
 };
 
 struct PropArgs {      // Implement::propagate (implement.cpp:217-256)
@@ -321,6 +336,9 @@ struct PropArgs {      // Implement::propagate (implement.cpp:217-256)
     // that works.  nullptr: every sequence (or its `meta` flag).
     const int* need_list = nullptr;
     int n_slots = 0;
+    // Per-sequence intrinsics (dvo_batch_create_mono_cameras): [n_seq] top-level Intr.  Set: k_propagate_owner_cam warps with the
+    // sequence's entry instead of `k`.
+    const Intr* seq_k = nullptr;
 };
 
 #define DVO_PROMOTE_MAX_SEG 8

@@ -31,6 +31,28 @@ __device__ __forceinline__ void split_row(int i, int w, float inv_w, int& x, int
     x += (lo - hi) * w;
 }
 
+// Per-camera mono batches (dvo_batch_create_mono_cameras): the intrinsics a mapping kernel uses for its sequence -- a.k, or (PCAM:
+// the per-camera kernels) `cam`, the sequence's entry of the per-sequence table, loaded once per workgroup.  Called at each use,
+// with a.k not bound to a local, as seq_intr in dvo_kernels.hip: PCAM = false is then the code the kernel always was.
+template <bool PCAM, class Args>
+__device__ __forceinline__ const Intr& map_intr(const Args& a, const Intr& cam)
+{
+    if constexpr (PCAM) return cam;
+    else return a.k;
+}
+// Entry `i` of a per-sequence table the kernel only reads, at an index that is uniform across the workgroup: through the constant
+// address space, so the loads are scalar (s_load into SGPRs) even after the kernel's own stores and atomics, and with the index
+// made provably uniform (readfirstlane of a value every lane holds) where it came from a list in memory.
+template <class T>
+__device__ __forceinline__ T load_seq_entry(const T* table, int i)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ((const __attribute__((address_space(4))) T*)table)[__builtin_amdgcn_readfirstlane(i)];
+#else
+    return table[i];   // (the host pass only parses device code)
+#endif
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_mono_decide: what System::VisualOdometry::odometrize does between Tracker::track and Mapper::estimate
 // (system.hpp:57-73, frame.cpp:7-14, mapper.cpp:45-60), one thread per sequence, in the double-precision pose algebra of
@@ -154,12 +176,17 @@ __global__ void __launch_bounds__(256) k_propagate_init(PropArgs a)
     }
 }
 
-__global__ void __launch_bounds__(256) k_propagate_owner(PropArgs a)
+// PCAM: per-sequence intrinsics (PropArgs::seq_k, k_propagate_owner_cam).  The arguments are taken by value: by reference, the
+// default kernel's instruction stream changed.
+template <bool PCAM>
+__device__ __forceinline__ void propagate_owner(PropArgs a)
 {
     int seq, cursor = -1;
     const int w = a.w, h = a.h, n = w * h, i0 = prop_chunk(seq);
     while (next_listed_seq(a.need_list, a.n_slots, a.n_seq, a.meta, cursor, seq)) {
         const Pose pose = a.meta ? a.meta[seq].rel_pose : a.pose;   // wave-uniform
+        Intr cam;
+        if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
 #pragma unroll
         for (int k = 0; k < DVO_PROP_PER_THREAD; k++) {
             const int i = i0 + k * 256;
@@ -169,7 +196,7 @@ __global__ void __launch_bounds__(256) k_propagate_owner(PropArgs a)
             const float rd = a.ref_depth[(size_t)seq * n + i];
             if (is_epsilon(rd)) continue;
             float pu, pv;
-            warp(pose, a.k, (float)x, (float)y, rd, pu, pv);
+            warp(pose, map_intr<PCAM>(a, cam), (float)x, (float)y, rd, pu, pv);
             int qx, qy;
             if (!round_coord(pu, qx) || !round_coord(pv, qy)) continue;
             if (qx < 0 || w <= qx || qy < 0 || h <= qy) continue;
@@ -177,6 +204,9 @@ __global__ void __launch_bounds__(256) k_propagate_owner(PropArgs a)
         }
     }
 }
+
+__global__ void __launch_bounds__(256) k_propagate_owner(PropArgs a) { propagate_owner<false>(a); }
+__global__ void __launch_bounds__(256) k_propagate_owner_cam(PropArgs a) { propagate_owner<true>(a); }
 
 __global__ void __launch_bounds__(256) k_propagate_pull(PropArgs a)
 {
@@ -308,7 +338,9 @@ struct UpdHead {   // what the head of the per-pixel computation hands to the se
 
 // Head: mapper.cpp:90-107 + EpipolarSegment (implement.cpp:23-47).  Returns the number of search steps the pixel will take
 // (an upper bound within one step; 0 = the pixel leaves before the search: nothing to do).
-__device__ __forceinline__ int depth_update_head(const UpdateArgs& a, const int seq, const int x, const int y, UpdHead& hd)
+// PCAM: the sequence's intrinsics `cam` instead of a.k (map_intr).
+template <bool PCAM>
+__device__ __forceinline__ int depth_update_head(const UpdateArgs& a, const int seq, const int x, const int y, UpdHead& hd, const Intr& cam)
 {
     const int w = a.w, h = a.h, npix = w * h;
     const MonoSeq* m = a.meta ? a.meta + seq : nullptr;
@@ -320,7 +352,7 @@ __device__ __forceinline__ int depth_update_head(const UpdateArgs& a, const int 
     if (m && a.ring_gray) n_hist = m->n_total < a.R ? m->n_total : a.R;
     const float d = a.ref_depth[base + i];
     float pu, pv;
-    warp(rel_pose, a.k, (float)x, (float)y, d, pu, pv);               // mapper.cpp:94
+    warp(rel_pose, map_intr<PCAM>(a, cam), (float)x, (float)y, d, pu, pv);   // mapper.cpp:94
     int qx, qy;
     if (!round_coord(pu, qx) || !round_coord(pv, qy)) return 0;
     if (qx < 0 || w <= qx || qy < 0 || h <= qy) return 0;
@@ -338,8 +370,8 @@ __device__ __forceinline__ int depth_update_head(const UpdateArgs& a, const int 
     const float dmin = (depth - sigma) < 0.10f ? 0.10f : (depth - sigma);
     const float dmax = depth + sigma;
     float sx, sy, ex, ey;
-    warp(born.pose, a.k, (float)qx, (float)qy, dmax, sx, sy);
-    warp(born.pose, a.k, (float)qx, (float)qy, dmin, ex, ey);
+    warp(born.pose, map_intr<PCAM>(a, cam), (float)qx, (float)qy, dmax, sx, sy);
+    warp(born.pose, map_intr<PCAM>(a, cam), (float)qx, (float)qy, dmin, ex, ey);
     const float sex = sx - ex, sey = sy - ey;
     const float length = (float)sqrt((double)sex * (double)sex + (double)sey * (double)sey);
     hd.sx = sx; hd.sy = sy; hd.ex = ex; hd.ey = ey; hd.length = length; hd.depth = depth; hd.sigma = sigma; hd.dmin = dmin; hd.dmax = dmax;
@@ -350,7 +382,10 @@ __device__ __forceinline__ int depth_update_head(const UpdateArgs& a, const int 
 }
 
 // Tail: doMatching, depthEstimate, sigmaEstimate and the fusion (implement.cpp:49-152,182-214, mapper.cpp:122-131) of one pixel.
-__device__ __forceinline__ void depth_update_tail(const UpdateArgs& a, const int seq, const int x, const int y, const UpdHead& hd)
+// PCAM: the sequence's intrinsics `cam` and culled K9 / k_sparse `mk` instead of a.k, a.K9 and a.k_sparse.
+template <bool PCAM>
+__device__ __forceinline__ void depth_update_tail(const UpdateArgs& a, const int seq, const int x, const int y, const UpdHead& hd, const Intr& cam,
+                                                  const MapK& mk)
 {
     const int w = a.w, h = a.h, npix = w * h;
     const MonoSeq* m = a.meta ? a.meta + seq : nullptr;
@@ -452,29 +487,31 @@ __device__ __forceinline__ void depth_update_tail(const UpdateArgs& a, const int
     float nd;
     {
         float q0f, q1f, q2f;
-        back_project(a.k, (float)qx, (float)qy, 1.0f, q0f, q1f, q2f);
+        back_project(map_intr<PCAM>(a, cam), (float)qx, (float)qy, 1.0f, q0f, q1f, q2f);
         const double q0 = q0f, q1 = q1f, q2 = q2f;
         const double t[3] = {(double)born.tneg[0], (double)born.tneg[1], (double)born.tneg[2]};
         const double xi3[3] = {(double)bestx, (double)besty, 1.0};
         double Rq[3], KRq[3], Kt[3];
         for (int r = 0; r < 3; r++)
             Rq[r] = (double)born.pose.R[3 * r] * q0 + (double)born.pose.R[3 * r + 1] * q1 + (double)born.pose.R[3 * r + 2] * q2;
-        if (a.k_sparse) {
+        const float* K9 = PCAM ? mk.K9 : a.K9;
+        const int k_sparse = PCAM ? mk.k_sparse : a.k_sparse;
+        if (k_sparse) {
             // K = [fx 0 cx; 0 fy cy; 0 0 1]: a product with an exact zero adds an exact zero, so (fx x + 0 y) + cx z is fx x + cx z and
             // (0 x + 0 y) + 1 z is z -- the same doubles as the three-term rows below (for finite x, y, z: they are), 12 instead of 30
             // fp64 operations per pixel for K R q and K t.
-            const double fx = (double)a.K9[0], cx = (double)a.K9[2], fy = (double)a.K9[4], cy = (double)a.K9[5];
+            const double fx = (double)K9[0], cx = (double)K9[2], fy = (double)K9[4], cy = (double)K9[5];
             KRq[0] = fx * Rq[0] + cx * Rq[2]; KRq[1] = fy * Rq[1] + cy * Rq[2]; KRq[2] = Rq[2];
             Kt[0] = fx * t[0] + cx * t[2]; Kt[1] = fy * t[1] + cy * t[2]; Kt[2] = t[2];
         } else {
             for (int r = 0; r < 3; r++) {
-                KRq[r] = (double)a.K9[3 * r] * Rq[0] + (double)a.K9[3 * r + 1] * Rq[1] + (double)a.K9[3 * r + 2] * Rq[2];
-                Kt[r] = (double)a.K9[3 * r] * t[0] + (double)a.K9[3 * r + 1] * t[1] + (double)a.K9[3 * r + 2] * t[2];
+                KRq[r] = (double)K9[3 * r] * Rq[0] + (double)K9[3 * r + 1] * Rq[1] + (double)K9[3 * r + 2] * Rq[2];
+                Kt[r] = (double)K9[3 * r] * t[0] + (double)K9[3 * r + 1] * t[1] + (double)K9[3 * r + 2] * t[2];
             }
         }
         double aa = 0.0, ab = 0.0;
         // (sparse K: the third components are Rq[2] * 1 - Rq[2] and t[2] * 1 - t[2], exact zeros whose products add exact zeros)
-        const int nr = a.k_sparse ? 2 : 3;
+        const int nr = k_sparse ? 2 : 3;
         for (int r = 0; r < nr; r++) {
             const double va = Rq[2] * xi3[r] - KRq[r];
             const double vb = t[2] * xi3[r] - Kt[r];
@@ -520,7 +557,10 @@ __device__ __forceinline__ void depth_update_tail(const UpdateArgs& a, const int
 // hands them out in that order: each wave then holds pixels of similar length and finishes together.  Pixels that leave before
 // the search are dropped from the list.  Pixels are independent and the valid-update count is an integer sum, so the order changes
 // no result (bit-exact vs the oracle and the one-pass form: tests/test_gpu_parity.py, tests/test_real_data.py).
-__global__ void __launch_bounds__(256) k_depth_update(UpdateArgs a)
+// PCAM (k_depth_update_cam): per-sequence intrinsics (UpdateArgs::seq_k, seq_K9), loaded once per workgroup into SGPRs.  The
+// arguments are taken by value, as in propagate_owner.
+template <bool PCAM>
+__device__ __forceinline__ void depth_update(UpdateArgs a)
 {
     __shared__ int bucket_cnt[128];     // pixels per step count, index 127 - steps (longest first)
     __shared__ int bucket_off[128];
@@ -537,6 +577,9 @@ __global__ void __launch_bounds__(256) k_depth_update(UpdateArgs a)
     const bool mine = seq_pixel(ww * wh, a.n_seq, seq, j);       // (seq is block-uniform; only the last block of a sequence has idle threads)
     if (seq >= a.n_seq) return;
     if (a.meta && a.ring_gray && a.meta[seq].need) return;   // this sequence created a keyframe instead (mapper.cpp:23-27); block-uniform
+    Intr cam;
+    MapK mk;
+    if constexpr (PCAM) { cam = load_seq_entry(a.seq_k, seq); mk = load_seq_entry(a.seq_K9, seq); }
     const int j0 = j - (int)threadIdx.x;                 // window index of this workgroup's first thread
     if (threadIdx.x < 128) bucket_cnt[threadIdx.x] = 0;
     __syncthreads();
@@ -545,7 +588,7 @@ __global__ void __launch_bounds__(256) k_depth_update(UpdateArgs a)
         int wx, wy;
         split_row(j, ww, a.inv_ww, wx, wy);
         UpdHead hd;
-        steps = depth_update_head(a, seq, x_lo + wx, y_lo + wy, hd);
+        steps = depth_update_head<PCAM>(a, seq, x_lo + wx, y_lo + wy, hd, cam);
         if (steps > 0) {
             rank = atomicAdd(&bucket_cnt[127 - steps], 1);
             const int t = (int)threadIdx.x;
@@ -581,9 +624,12 @@ __global__ void __launch_bounds__(256) k_depth_update(UpdateArgs a)
         const int jq = j0 + p;
         int wx, wy;
         split_row(jq, ww, a.inv_ww, wx, wy);
-        depth_update_tail(a, seq, x_lo + wx, y_lo + wy, hd);
+        depth_update_tail<PCAM>(a, seq, x_lo + wx, y_lo + wy, hd, cam, mk);
     }
 }
+
+__global__ void __launch_bounds__(256) k_depth_update(UpdateArgs a) { depth_update<false>(a); }
+__global__ void __launch_bounds__(256) k_depth_update_cam(UpdateArgs a) { depth_update<true>(a); }
 
 // ------------------------------------------------------------------------------------------------
 // k_promote: the tracked frame becomes the newest keyframe (Mapper::estimate's needNewFrame branch, mapper.cpp:23-27 +
@@ -685,7 +731,8 @@ void launch_propagate_batch(const PropArgs& a0, hipStream_t s)
     a.n_slots = a.need_list ? (a.n_seq < DVO_LIST_SLOTS ? a.n_seq : DVO_LIST_SLOTS) : 0;
     const dim3 grid = seq_grid(cdiv_u(a.w * a.h, 256 * DVO_PROP_PER_THREAD), a.need_list ? (unsigned)a.n_slots : (unsigned)a.n_seq);
     hipLaunchKernelGGL(k_propagate_init, grid, dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_propagate_owner, grid, dim3(256), 0, s, a);
+    if (a.seq_k) hipLaunchKernelGGL(k_propagate_owner_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+    else hipLaunchKernelGGL(k_propagate_owner, grid, dim3(256), 0, s, a);
     hipLaunchKernelGGL(k_propagate_pull, grid, dim3(256), 0, s, a);
 }
 
@@ -723,8 +770,10 @@ void launch_depth_update(const UpdateArgs& a0, hipStream_t s)
     const int ww = a.crop ? ((a.w - 1 < 144 ? a.w - 1 : 144) - 16 + 1) : a.w, wh = a.crop ? ((a.h - 1 < 108 ? a.h - 1 : 108) - 12 + 1) : a.h;
     if (ww <= 0 || wh <= 0) return;
     a.inv_ww = 1.0f / (float)ww;
-    a.k_sparse = (a.K9[1] == 0.0f && a.K9[3] == 0.0f && a.K9[6] == 0.0f && a.K9[7] == 0.0f && a.K9[8] == 1.0f) ? 1 : 0;
-    hipLaunchKernelGGL(k_depth_update, seq_grid(cdiv_u(ww * wh, 256), (unsigned)a.n_seq), dim3(256), 0, s, a);
+    a.k_sparse = k9_sparse(a.K9);
+    const dim3 grid = seq_grid(cdiv_u(ww * wh, 256), (unsigned)a.n_seq);
+    if (a.seq_k) hipLaunchKernelGGL(k_depth_update_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics (a.seq_K9 set too)
+    else hipLaunchKernelGGL(k_depth_update, grid, dim3(256), 0, s, a);
 }
 
 }  // namespace dvo

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <string>
+#include <vector>
 #include <new>
 #include <utility>
 
@@ -39,18 +41,38 @@ int MonoBatch::collect_map_profile()
     return DVO_OK;
 }
 
-int MonoBatch::init(int n, const float K9[9], int w, int h, int ring, const dvo_config* c)
+int MonoBatch::init(int n, const float* K, int w, int h, int ring, const dvo_config* c, bool per_camera)
 {
-    if (n < 1 || !K9 || w < 64 || h < 64 || ring < 1 || ring > 64) { set_error("dvo_batch_create_mono: bad arguments"); return DVO_ERR_BAD_ARGUMENT; }
+    const char* who = per_camera ? "dvo_batch_create_mono_cameras" : "dvo_batch_create_mono";
+    if (n < 1 || (!K && !per_camera) || w < 64 || h < 64 || ring < 1 || ring > 64) { set_error(std::string(who) + ": bad arguments"); return DVO_ERR_BAD_ARGUMENT; }
+    if (per_camera) DVO_TRY(check_intrinsics(who, K, (size_t)n));
     if (c) cfg = *c; else dvo_config_default(&cfg);
     n_seq = n; R = ring; device = cfg.device;
     DVO_TRY(select_device(device));
     if (cfg.stream) stream = (hipStream_t)cfg.stream;
     else { DVO_HIP(hipStreamCreate(&stream)); own_stream = true; }
-    DVO_TRY(make_geometry(K9, w, h, 3, 2, g));  // Frame(gray, K, 3, 2), system.hpp:47
+    // (per camera: the frame and pyramid shape do not depend on K; the tracker and mapping kernels read the per-sequence tables)
+    DVO_TRY(make_geometry(K, w, h, 3, 2, g));  // Frame(gray, K, 3, 2), system.hpp:47
     DVO_TRY(ref.alloc(g, n, cfg));
     DVO_TRY(frm.alloc(g, n, cfg));
     DVO_TRY(trk.init(g, n, cfg));
+    if (per_camera) {   // the tables, once: each sequence's K through the steps make_geometry applies to one K (the same bits)
+        const size_t ns = (size_t)n, tab = sizeof(Intr) * (size_t)g.levels * ns;
+        std::vector<uint8_t> h_cam(tab + sizeof(MapK) * ns);
+        Intr* lv_tab = reinterpret_cast<Intr*>(h_cam.data());
+        MapK* map_tab = reinterpret_cast<MapK*>(h_cam.data() + tab);
+        for (size_t q = 0; q < ns; q++) {
+            Intr lv[DVO_MAX_LEVELS];
+            float K9[DVO_MAX_LEVELS][9];
+            level_intrinsics(K + q * 9, g, lv, K9);
+            for (int l = 0; l < g.levels; l++) lv_tab[(size_t)l * ns + q] = lv[l];
+            memcpy(map_tab[q].K9, K9[g.top()], sizeof map_tab[q].K9);
+            map_tab[q].k_sparse = k9_sparse(map_tab[q].K9);   // (launch_depth_update's test)
+        }
+        DVO_TRY(cam_dev.alloc(h_cam.size()));
+        DVO_HIP(hipMemcpy(cam_dev.p, h_cam.data(), h_cam.size(), hipMemcpyHostToDevice));
+        trk.cam_k = cam_dev.as<Intr>();
+    }
     const size_t np = (size_t)top_pixels(), all = np * (size_t)n * sizeof(float);
     DVO_TRY(ref_age.alloc(all)); DVO_TRY(frm_age.alloc(all)); DVO_TRY(owner.alloc(all)); DVO_TRY(tmp.alloc(all));
     DVO_TRY(ring_gray.alloc(all * (size_t)R));
@@ -185,6 +207,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         a.w = tw; a.h = th; a.n_seq = n_seq; a.k = g.k[T]; a.meta = m;
         memset(&a.pose, 0, sizeof a.pose); a.tz = 0.0f;
         a.need_list = need_list.as<int>();
+        a.seq_k = cam_top();   // (per-camera batch: k_propagate_owner_cam)
         if (pe) DVO_HIP(hipEventRecord(pe->e[0], stream));
         launch_propagate_batch(a, stream);
         if (pe) DVO_HIP(hipEventRecord(pe->e[1], stream));
@@ -205,6 +228,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         a.seed = cfg.rng_seed;
         a.k = g.k[T];
         memcpy(a.K9, g.K9[T], sizeof a.K9);
+        a.seq_k = cam_top(); a.seq_K9 = cam_map();   // (per-camera batch: k_depth_update_cam)
         launch_depth_update(a, stream);
         if (pe) DVO_HIP(hipEventRecord(pe->e[3], stream));
     }
@@ -253,7 +277,7 @@ using namespace dvo;
 
 extern "C" {
 
-int dvo_batch_create_mono(int n_seq, const float K[9], int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out)
+static int create_mono(int n_seq, const float* K, bool per_camera, int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out)
 {
     if (!out) return DVO_ERR_BAD_ARGUMENT;
     *out = nullptr;
@@ -261,10 +285,20 @@ int dvo_batch_create_mono(int n_seq, const float K[9], int width, int height, in
     if (!b) return DVO_ERR_OUT_OF_MEMORY;
     b->mono.reset(new (std::nothrow) MonoBatch());
     if (!b->mono) { delete b; return DVO_ERR_OUT_OF_MEMORY; }
-    const int st = b->mono->init(n_seq, K, width, height, ring_keyframes > 0 ? ring_keyframes : 8, cfg);
+    const int st = b->mono->init(n_seq, K, width, height, ring_keyframes > 0 ? ring_keyframes : 8, cfg, per_camera);
     if (st != DVO_OK) { delete b; return st; }
     *out = b;
     return DVO_OK;
+}
+
+int dvo_batch_create_mono(int n_seq, const float K[9], int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out)
+{
+    return create_mono(n_seq, K, false, width, height, ring_keyframes, cfg, out);
+}
+
+int dvo_batch_create_mono_cameras(int n_seq, const float* K, int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out)
+{
+    return create_mono(n_seq, K, true, width, height, ring_keyframes, cfg, out);
 }
 
 #define DVO_NEED_MONO(b)                                                                                      \

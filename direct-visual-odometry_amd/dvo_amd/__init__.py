@@ -98,7 +98,7 @@ EXPORTS = [
     "dvo_vo_save", "dvo_vo_load", "dvo_vo_set_history_limit", "dvo_op_visualize", "dvo_ppm_write",
     "dvo_selftest_reciprocal", "dvo_selftest_sqrt", "dvo_selftest_division", "dvo_selftest_trig",
     "dvo_batch_set_actions", "dvo_batch_last_status", "dvo_batch_copy_status_device",
-    "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics",
+    "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics", "dvo_batch_create_mono_cameras",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -635,10 +635,19 @@ class MonoBatch:
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 
-    def __init__(self, n_seq, K, width, height, ring_keyframes=8, cfg=None):
-        K = f32(K).reshape(9)
+    def __init__(self, n_seq, K, width, height, ring_keyframes=8, cfg=None, per_sequence_K=False):
+        """K: one camera for every sequence, float [3, 3] or [9].  per_sequence_K=True: K is a table with one camera per sequence,
+        float [n_seq, 3, 3] or [n_seq, 9], fixed for the life of the batch (dvo_batch_create_mono_cameras)."""
         self.n_seq, self.width, self.height = n_seq, width, height
         self._p = C.c_void_p()
+        if per_sequence_K:
+            k = np.ascontiguousarray(K, np.float32)
+            if k.shape not in ((n_seq, 3, 3), (n_seq, 9)):
+                raise ValueError("MonoBatch: per_sequence_K expects float[%d, 3, 3] or float[%d, 9], got shape %s" % (n_seq, n_seq, k.shape))
+            _check(lib().dvo_batch_create_mono_cameras(n_seq, fp(k), width, height, ring_keyframes,
+                                                       C.byref(cfg) if cfg is not None else None, C.byref(self._p)))
+            return
+        K = f32(K).reshape(9)
         _check(lib().dvo_batch_create_mono(n_seq, fp(K), width, height, ring_keyframes,
                                            C.byref(cfg) if cfg is not None else None, C.byref(self._p)))
 

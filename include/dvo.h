@@ -247,6 +247,16 @@ int dvo_batch_probe_gn(dvo_batch* b, int level, int n_launches, float* avg_ms, u
  * dvo_vo_set_history_limit(ring_keyframes)).
  * ------------------------------------------------------------------------------------------------ */
 int dvo_batch_create_mono(int n_seq, const float K[9], int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out);
+/* The same with one K per sequence: K[n_seq][9], host memory, row-major 3x3 (fx = K[0], cx = K[2], fy = K[4], cy = K[5]), copied
+ * before the call returns.  Same arguments and results as dvo_batch_create_mono otherwise, and every other mono entry point works
+ * unchanged on the handle.  A sequence's K is fixed at creation: its keyframe ring and depth maps belong to that camera (there is no
+ * mono restart; dvo_batch_set_intrinsics, dvo_batch_get_intrinsics and dvo_batch_set_actions refuse a mono batch).  Each sequence
+ * gives the bits a dvo_vo handle created with that sequence's K and the same config gives (past `ring_keyframes` keyframes, one with
+ * dvo_vo_set_history_limit(ring_keyframes)).  Frame size, pyramid shape and config stay per handle.
+ * Errors, returned before anything touches the GPU: K == NULL, or a sequence's K with a non-finite entry or fx / fy <= 0 ->
+ * DVO_ERR_BAD_ARGUMENT, with the index of the first bad sequence in dvo_last_error. */
+int dvo_batch_create_mono_cameras(int n_seq, const float* K /*[n_seq][9]*/, int width, int height, int ring_keyframes,
+                                  const dvo_config* cfg, dvo_batch** out);
 /* Initial depth / sigma of the first keyframes (replaces cv::randn, frame.hpp:17-21) at width/4 x height/4: one host map for every
  * sequence, or device maps [n_seq][height/4][width/4].  Optional; default as dvo_vo. Call before the first frame. */
 int dvo_batch_set_initial_depth(dvo_batch* b, const float* depth, const float* sigma);

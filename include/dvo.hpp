@@ -186,6 +186,11 @@ public:
     {
         check(dvo_batch_create_mono(n_seq, K.data(), width, height, ring_keyframes, cfg, &b_));
     }
+    // one K per sequence (K[n_seq], fixed at creation), see dvo_batch_create_mono_cameras
+    BatchMono(int n_seq, const Mat3* K, int width, int height, int ring_keyframes = 8, const dvo_config* cfg = nullptr) : n_(n_seq)
+    {
+        check(dvo_batch_create_mono_cameras(n_seq, K ? K[0].data() : nullptr, width, height, ring_keyframes, cfg, &b_));
+    }
     ~BatchMono() { dvo_batch_destroy(b_); }
     BatchMono(const BatchMono&) = delete;
     BatchMono& operator=(const BatchMono&) = delete;
