@@ -119,6 +119,12 @@ int dvo_vo_odometrize_raw(dvo_vo* vo, const uint8_t* rgb, int channels, float T_
     return vo->impl.odometrize(nullptr, T_world, is_keyframe, rgb, channels);
 }
 
+int dvo_vo_set_distortion(dvo_vo* vo, const float D[5])
+{
+    if (!vo) return DVO_ERR_BAD_ARGUMENT;
+    return vo->impl.set_distortion(D);
+}
+
 int dvo_vo_odometrize_depth(dvo_vo* vo, const float* gray, const float* depth, const float* sigma, float T_rel[16])
 {
     if (!vo) return DVO_ERR_BAD_ARGUMENT;

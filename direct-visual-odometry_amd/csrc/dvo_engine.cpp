@@ -262,6 +262,23 @@ void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, 
 
 void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from)
 {
+    if (in.remap) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames, no plan
+        PyramidArgs a;
+        memset(&a, 0, sizeof a);
+        a.src[0] = in.gray;
+        a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);   // (k_ingest's scale)
+        a.src_w = fs.g.src_w; a.src_h = fs.g.src_h; a.culls = fs.g.culls; a.levels = fs.g.levels;
+        a.src_img_rows = fs.g.src_h; a.src_row_shift = fs.g.culls;
+        for (int l = 0; l < fs.g.levels; l++) {
+            a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l];
+            a.dst[0][l] = fs.gray[l];
+        }
+        a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
+        a.remap = in.remap; a.remap_cam = in.remap_cam;
+        fs.sigma_by_validity = false;
+        launch_pyramid(a, fs.n_seq, s);
+        return;
+    }
     if (!in.raw()) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
     PyramidArgs a;
     memset(&a, 0, sizeof a);
@@ -900,9 +917,26 @@ void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vec
     }
 }
 
+int VisualOdometry::set_distortion(const float D[5])
+{
+    if (fed) { set_error("dvo_vo_set_distortion: the handle has consumed a frame (D is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    return und.set("dvo_vo_set_distortion", D, false, 1, K, false, geoM, stream);
+}
+
+// the sensor-depth entry points and init_keyframe have no defined meaning on a handle that undistorts (include/dvo.h)
+static int refuse_distorted(const VisualOdometry& vo, const char* who)
+{
+    if (!vo.und.enabled()) return DVO_OK;
+    set_error(std::string(who) + ": the handle undistorts its frames (dvo_vo_set_distortion); sensor-depth input is not undistorted");
+    return DVO_ERR_BAD_ARGUMENT;
+}
+
 int VisualOdometry::init_keyframe(const float* gray, const float* depth, const float* sigma)
 {  // system.hpp:24-32 with the mono geometry (deviation D9)
+    DVO_TRY(refuse_distorted(*this, "dvo_vo_init_keyframe"));
     if (!gray || !depth || !sigma) { set_error("null image"); return DVO_ERR_BAD_ARGUMENT; }
+    fed = true;
     DVO_TRY(select_device(device));
     const size_t n = (size_t)w * h * sizeof(float);
     DVO_HIP(hipMemcpyAsync(in_gray.p, gray, n, hipMemcpyHostToDevice, stream));
@@ -1044,6 +1078,7 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     if ((!gray && !raw) || !T_world) { set_error("null argument"); return DVO_ERR_BAD_ARGUMENT; }
     if (raw && raw_channels != 1 && raw_channels != 3 && raw_channels != 4) { set_error("bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(device));
+    fed = true;
     if (!trkM_ready) {   // one launch per track() call (k_track_persist), as the sensor-depth tracker
         trkM.prefer_persist = true;
         if (const char* e = getenv("DVO_MONO_PERSIST")) trkM.prefer_persist = atoi(e) != 0;
@@ -1063,7 +1098,8 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     // profiles/r03_mono_single_trace_final.txt) drops out.  The block was last read by the previous frame's pyramid, which that call waited
     // for.  DVO_MONO_STAGE=0: the copy on the side stream, as before.
     FrameInput fin;
-    fin.rows_decimated = decimate_host_rows && can_decimate_rows(geoM);   // only the rows the pyramid keeps are copied / cross PCIe
+    // only the rows the pyramid keeps are copied / cross PCIe -- whole frames when they are undistorted (the remap reads any row)
+    fin.rows_decimated = decimate_host_rows && can_decimate_rows(geoM) && !und.enabled();
     const size_t row_bytes = raw ? (size_t)w * raw_channels : (size_t)w * sizeof(float);
     // (a thread's memcpy beats the runtime's copy path up to about half a megabyte -- measured at 77-460 KB; above that the DMA engine wins)
     const bool stage_rows = stage_mono_rows && row_bytes * (size_t)(fin.rows_decimated ? h >> geoM.culls : h) <= kStageLimitBytes;
@@ -1096,6 +1132,7 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     Keyframe& frame = *scratch;
     frame.id = ++latest_id;
     for (int i = 0; i < 6; i++) { frame.xi[i] = 0; frame.rel_xi[i] = 0; }
+    und.apply(fin, 1);   // dvo_vo_set_distortion: k_pyramid_remap
     build_pyramid(frame.fs, fin, stream);
     if (is_key) *is_key = 0;
     const int T = geoM.top();
@@ -1185,7 +1222,9 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
 
 int VisualOdometry::odometrize_depth(const float* gray, const float* depth, const float* sigma, float T_rel[16])
 {  // system.hpp:77-93
+    DVO_TRY(refuse_distorted(*this, "dvo_vo_odometrize_depth"));
     if (!gray || !depth || !sigma || !T_rel) { set_error("null argument"); return DVO_ERR_BAD_ARGUMENT; }
+    fed = true;
     DVO_TRY(select_device(device));
     if (!trkD_ready) { trkD.prefer_persist = true; DVO_TRY(trkD.init(geoD, 1, cfg)); trkD_ready = true; }
     FrameInput in;   // float maps: only the rows the pyramid keeps cross PCIe (upload_rows)
@@ -1219,7 +1258,9 @@ int VisualOdometry::odometrize_depth(const float* gray, const float* depth, cons
 
 int VisualOdometry::odometrize_depth_raw(const uint8_t* rgb, int channels, const uint16_t* depth16, float depth_scale, float T_rel[16])
 {  // the same call fed with raw sensor frames: u8 gray/RGB(A) + u16 depth, converted on the device while the pyramid is built
+    DVO_TRY(refuse_distorted(*this, "dvo_vo_odometrize_depth_raw"));
     if (!rgb || !depth16 || !T_rel || (channels != 1 && channels != 3 && channels != 4)) { set_error("bad raw frame"); return DVO_ERR_BAD_ARGUMENT; }
+    fed = true;
     DVO_TRY(select_device(device));
     const size_t px = (size_t)w * h;
     if (raw_rgb.bytes < px * 4) { DVO_TRY(raw_rgb.alloc(px * 4)); DVO_TRY(raw_depth.alloc(px * 2)); }

@@ -105,6 +105,10 @@ struct FrameInput {
     const float* gray = nullptr; const float* depth = nullptr; const float* sigma = nullptr;
     const uint8_t* rgb = nullptr; int channels = 0; const uint16_t* depth16 = nullptr; float depth_scale = 1.0f / 5000.0f;
     bool rows_decimated = false;  // the buffers hold only the rows the pyramid keeps (every 2^culls-th), see upload_rows
+    // mono frames with lens undistortion (Undistortion::apply): k_pyramid_remap gathers each kept pixel through its camera's table.
+    // Gray only, whole frames (rows_decimated = false).
+    const int* remap = nullptr;       // [n_cam][th][tw] source indices
+    const int* remap_cam = nullptr;   // [n_seq] camera of each sequence
     bool raw() const { return rgb != nullptr; }
     const void* key0() const { return raw() ? (const void*)rgb : (const void*)gray; }
     const void* key1() const { return raw() ? (const void*)depth16 : (const void*)depth; }
@@ -123,6 +127,26 @@ int upload_rows(void* dst, const void* src, size_t row_bytes, int img_rows, size
 inline bool can_decimate_rows(const Geometry& g) { return g.culls > 0 && (g.src_h % (1 << g.culls)) == 0; }
 // Frame::updateDepthSigma / updateDepth (frame.cpp:39-61): re-decimate from a top-level map (may alias the top level)
 void redecimate(FrameSet& fs, const float* depth_top, const float* sigma_top, hipStream_t s);
+
+// Lens undistortion fused into the mono pyramid (dvo_batch_set_distortion, dvo_vo_set_distortion): Loader::getNormalizedUndistortedImages
+// (loader.cpp:15-42) = dvo_op_undistort(frame, K_s, D_s) with each sequence's full-resolution creation K, applied to every frame before
+// the pyramid.  The cameras are deduplicated by the bits of (fx, fy, cx, cy, D); k_undistort_map writes one table per camera, once.
+struct Undistortion {
+    std::vector<float> D;   // [n_seq][5] as set; empty: no undistortion (the handle runs exactly the kernels it runs without)
+    DevBuf dev;             // [n_seq] int camera index (padded to 16 bytes), then [n_cam][th][tw] int tables
+    int n_cam = 0;
+    const int* cam() const { return dev.as<int>(); }
+    const int* table(int n_seq) const { return dev.as<int>() + (((size_t)n_seq + 3) & ~(size_t)3); }
+    bool enabled() const { return !D.empty(); }
+    // D: [5] (per_sequence = false) or [n_seq][5], nullptr clears; K_full: [n_seq][9], or [1][9] for every sequence (per_camera = false).
+    // A non-finite coefficient: DVO_ERR_BAD_ARGUMENT naming `who` and the first bad sequence, nothing changed.
+    int set(const char* who, const float* Dh, bool per_sequence, int n_seq, const float* K_full, bool per_camera, const Geometry& g, hipStream_t s);
+    void apply(FrameInput& in, int n_seq) const
+    {
+        if (!enabled()) return;
+        in.remap = table(n_seq); in.remap_cam = cam();   // (the caller uploads whole frames: rows_decimated = false)
+    }
+};
 
 // The per-sequence actions of one Batch push, resolved on the device by k_plan (Batch::launch_plan)
 struct TrackPlan {
@@ -258,6 +282,9 @@ struct VisualOdometry {  // System::VisualOdometry, system.hpp:12-104
     int odometrize_depth_raw(const uint8_t* rgb, int channels, const uint16_t* depth16, float depth_scale, float T_rel[16]);
     int odometrize_depth_staged(float T_rel[16], const struct FrameInput* raw = nullptr,   // frame already staged on the device
                                 const std::function<int()>* after_launch = nullptr);
+    Undistortion und;      // dvo_vo_set_distortion: the mono frames (odometrize) are undistorted while their pyramid is built
+    bool fed = false;      // a frame went through odometrize* or init_keyframe (dvo_vo_load does not count): D is fixed from then on
+    int set_distortion(const float D[5]);
     DevBuf raw_rgb, raw_depth;
     // the maps of one frame go up on separate streams: three strided copies queued on one stream run one after the other with
     // ~9 us between them (98 us from the end of one frame's tracking to the next pyramid, profiles/r03_single_hip_trace.txt)
@@ -386,6 +413,9 @@ struct MonoBatch {
     DevBuf cam_dev;
     const Intr* cam_top() const { return cam_dev.p ? cam_dev.as<Intr>() + (size_t)g.top() * n_seq : nullptr; }
     const MapK* cam_map() const { return cam_dev.p ? reinterpret_cast<const MapK*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq) : nullptr; }
+    std::vector<float> K_full;   // the creation K at full resolution: [9], or (per camera) [n_seq][9] -- the undistortion's camera
+    Undistortion und;            // dvo_batch_set_distortion (before the first frame)
+    int set_distortion(const float* D, bool per_sequence);
     // K: [9] for every sequence, or (per_camera) [n][9], one per sequence
     int init(int n, const float* K, int w, int h, int ring, const dvo_config* c, bool per_camera = false);
     ~MonoBatch();

@@ -44,6 +44,16 @@ struct PyramidArgs {
     const uint8_t* seq_action;                 // [n_seq] effective action (k_plan)
     const float* ref[3][DVO_MAX_LEVELS];       // gray, depth, sigma of the reference set
     const float* ref_wgt[DVO_MAX_LEVELS];
+    // optional lens undistortion of mono frames (remap != nullptr; gray only, whole frames, no plan): k_pyramid_remap gathers each
+    // kept pixel through its sequence's camera table (k_undistort_map) -- launch_pyramid then never picks k_pyramid / k_pyramid_raw4
+    const int* remap = nullptr;       // [n_cam][th][tw] source index into the full frame, -1 = border (INVALID)
+    const int* remap_cam = nullptr;   // [n_seq] camera (table) of each sequence
+};
+
+// One distinct camera of the fused undistortion: the full-resolution K (fx, fy, cx, cy) and D = (k1, k2, p1, p2, k3)
+struct UndistortCam {
+    Intr k;
+    float D[5];
 };
 
 // Grids of the per-(sequence, pixel) kernels: x = workgroups of one sequence, (y, z) = the sequence -- seq = z * 32768 + y, so the
@@ -54,6 +64,19 @@ inline dim3 seq_grid(unsigned blocks_per_seq, unsigned n_seq)
 {
     const unsigned gy = n_seq < DVO_GRID_SEQ_Y ? (n_seq ? n_seq : 1u) : DVO_GRID_SEQ_Y;
     return dim3(blocks_per_seq ? blocks_per_seq : 1u, gy, (n_seq + gy - 1u) / gy);
+}
+
+// Entry `i` of a per-sequence table the kernel only reads, at an index that is uniform across the workgroup: through the constant
+// address space, so the loads are scalar (s_load into SGPRs) even after the kernel's own stores and atomics, and with the index
+// made provably uniform (readfirstlane of a value every lane holds) where it came from a list in memory.
+template <class T>
+__device__ __forceinline__ T load_seq_entry(const T* table, int i)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ((const __attribute__((address_space(4))) T*)table)[__builtin_amdgcn_readfirstlane(i)];
+#else
+    return table[i];   // (the host pass only parses device code)
+#endif
 }
 #endif
 
@@ -436,5 +459,7 @@ void launch_selftest_division(unsigned b_first, unsigned b_stride, unsigned b_co
 void launch_selftest_reciprocal(unsigned long long* out3, hipStream_t s);  // out3 = {fast-path inputs, mismatches, first bad pattern}, pre-set {0, 0, ~0}
 void launch_visualize(int mode, const float* a, const float* b, int n, uint8_t* rgb, hipStream_t s);
 void launch_undistort(const float* src, int w, int h, const Intr& k, const float D[5], float border, float* dst, hipStream_t s);
+// k_undistort_map: table[c][y][x] = undistort_source((x, y) << culls) of camera c (full-resolution w x h), tw x th top-level pixels
+void launch_undistort_map(const UndistortCam* cams_dev, int n_cam, int w, int h, int culls, int tw, int th, int* table, hipStream_t s);
 
 }  // namespace dvo

@@ -219,6 +219,49 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     }
 }
 
+// k_pyramid_remap: k_pyramid of MONO frames (gray only, no plan) with the lens undistortion fused in (dvo_batch_set_distortion,
+// dvo_vo_set_distortion).  Under nearest-neighbour remapping, kept pixel (x << culls, y << culls) of the undistorted frame is ONE
+// pixel of the distorted input: the thread reads its index from the sequence's camera table (k_undistort_map; -1 = outside the
+// image = k_undistort's INVALID border), gathers that one u8 (k_pyramid's raw conversion) or float, and writes every level as
+// k_pyramid does.  The same operations as k_undistort followed by k_pyramid: bit-identical, and no undistorted frame is stored.
+// The table is read with plain loads (it is shared by every sequence of the camera and stays in L2), the frame and the levels
+// with k_pyramid's nontemporal accesses.  The input holds whole frames (src_img_rows = src_h): the gather reads any row.
+__global__ void __launch_bounds__(256) k_pyramid_remap(PyramidArgs a)
+{
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tw * th || seq >= a.n_seq) return;
+    int x, y;
+    split_index(i, tw, a.inv_tw, x, y);
+    const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
+    const int si = a.remap[(size_t)cam * tw * th + (size_t)y * tw + x];
+    float raw = kInvalid;
+    if (si >= 0) {
+        const size_t src_off = (size_t)seq * a.src_w * a.src_h + (size_t)si;
+        if (a.raw_rgb != nullptr) {
+            unsigned g8;
+            if (a.raw_channels == 1) {
+                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
+            } else {
+                const uint8_t* p = a.raw_rgb + src_off * (size_t)a.raw_channels;
+                g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
+            }
+            raw = (float)g8 * a.raw_gray_scale;
+        } else {
+            raw = __builtin_nontemporal_load(a.src[0] + src_off);
+        }
+    }
+    for (int t = 0; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if ((x & msk) | (y & msk)) break;
+        const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
+        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+        const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+        __builtin_nontemporal_store((t == 0 && a.culls == 0) ? raw : pass_valid(raw), a.dst[0][l] + o);
+    }
+}
+
 // k_pyramid_raw4: the raw-sensor form of k_pyramid for 1-channel u8 gray (+ u16 depth) with CULLS = 1 or 2, four kept pixels
 // per thread.  The scalar form spends one byte / short load per lane (a full vector-memory instruction for 1-2 useful bytes and
 // half-empty sectors); here a thread owns 4 consecutive top-level pixels = 4 << CULLS source pixels of one row, fetched by one or
@@ -1726,15 +1769,26 @@ __global__ void __launch_bounds__(256) k_undistort(const float* __restrict__ src
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= w * h) return;
     const int v = i / w, u = i - v * w;
-    const double x = ((double)u - k.cx) / k.fx, y = ((double)v - k.cy) / k.fy;
-    const double r2 = x * x + y * y, radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
-    const double xd = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
-    const double yd = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
-    const float mx = (float)(xd * k.fx + k.cx), my = (float)(yd * k.fy + k.cy);
-    int sx, sy;
+    int si;
     float out = border;
-    if (round_coord(mx, sx) && round_coord(my, sy) && sx >= 0 && sx < w && sy >= 0 && sy < h) out = src[sy * w + sx];
+    if (undistort_source(k, v, u, k1, k2, p1, p2, k3, w, h, si)) out = src[si];   // (dvo_math.h)
     dst[i] = out;
+}
+
+// k_undistort_map: the remap table of the undistortion fused into the mono pyramid (k_pyramid_remap), once per set_distortion.
+// One thread per TOP-level pixel per distinct camera: the source index undistort_source gives full-resolution pixel
+// (x << culls, y << culls), or -1.  Table [n_cam][th][tw]; grid seq_grid(., n_cam), the camera in place of the sequence.
+__global__ void __launch_bounds__(256) k_undistort_map(const UndistortCam* __restrict__ cams, int n_cam, int w, int h, int culls, int tw,
+                                                       int th, int* __restrict__ table)
+{
+    const int cam = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tw * th || cam >= n_cam) return;
+    const int y = i / tw, x = i - y * tw;
+    const UndistortCam q = cams[cam];
+    int si;
+    if (!undistort_source(q.k, y << culls, x << culls, q.D[0], q.D[1], q.D[2], q.D[3], q.D[4], w, h, si)) si = -1;
+    table[(size_t)cam * tw * th + i] = si;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1895,11 +1949,20 @@ void launch_undistort(const float* src, int w, int h, const Intr& k, const float
 
 static inline unsigned cdiv(unsigned a, unsigned b) { return (a + b - 1) / b; }
 
+void launch_undistort_map(const UndistortCam* cams_dev, int n_cam, int w, int h, int culls, int tw, int th, int* table, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_undistort_map, seq_grid(cdiv(tw * th, 256), (unsigned)n_cam), dim3(256), 0, s, cams_dev, n_cam, w, h, culls, tw, th, table);
+}
+
 void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
 {
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
+    if (a.remap != nullptr) {   // lens undistortion fused in (mono frames): never k_pyramid_raw4 / k_pyramid
+        hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+        return;
+    }
     // raw 1-channel frames with the usual alignment: four kept pixels per thread, wide loads and stores
     const bool vec = a.raw_rgb != nullptr && a.raw_channels == 1 && (a.culls == 1 || a.culls == 2) && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 &&
                      (reinterpret_cast<uintptr_t>(a.raw_rgb) % 16) == 0 && (reinterpret_cast<uintptr_t>(a.raw_depth) % 16) == 0;

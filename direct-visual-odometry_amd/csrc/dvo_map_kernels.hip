@@ -40,18 +40,6 @@ __device__ __forceinline__ const Intr& map_intr(const Args& a, const Intr& cam)
     if constexpr (PCAM) return cam;
     else return a.k;
 }
-// Entry `i` of a per-sequence table the kernel only reads, at an index that is uniform across the workgroup: through the constant
-// address space, so the loads are scalar (s_load into SGPRs) even after the kernel's own stores and atomics, and with the index
-// made provably uniform (readfirstlane of a value every lane holds) where it came from a list in memory.
-template <class T>
-__device__ __forceinline__ T load_seq_entry(const T* table, int i)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return ((const __attribute__((address_space(4))) T*)table)[__builtin_amdgcn_readfirstlane(i)];
-#else
-    return table[i];   // (the host pass only parses device code)
-#endif
-}
 
 // ------------------------------------------------------------------------------------------------
 // k_mono_decide: what System::VisualOdometry::odometrize does between Tracker::track and Mapper::estimate

@@ -780,4 +780,27 @@ DVO_HD bool round_coord(float v, int& out)
     return true;
 }
 
+// One pixel of Loader::getNormalizedUndistortedImages (loader.cpp:15-42): cv::initUndistortRectifyMap(K, D, I, K) +
+// cv::remap(INTER_NEAREST, BORDER_CONSTANT), restated from the radial-tangential model definition.  Sets si = sy * w + sx, the
+// source pixel destination pixel (u, v) takes, and returns true; false where that lies outside the image (the border).  k_undistort
+// and k_undistort_map (the table of the fused mono ingest, -1 for the border) both call it: one arithmetic, the same bits
+// (-ffp-contract=off).  The shape -- K by value first, then the row before the column, a bool and an out-parameter -- keeps
+// k_undistort's instruction stream what it was before the body moved here: LLVM orders the operands of the commutative adds by
+// the rank of the values they come from (argument position in this function, before it is inlined), and this order ranks them
+// as the kernel's own code did (tools/isa_compare.py: identical).
+DVO_HD bool undistort_source(Intr k, int v, int u, float k1, float k2, float p1, float p2, float k3, int w, int h, int& si)
+{
+    const double x = ((double)u - k.cx) / k.fx, y = ((double)v - k.cy) / k.fy;
+    const double r2 = x * x + y * y, radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3));
+    const double xd = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x);
+    const double yd = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y;
+    const float mx = (float)(xd * k.fx + k.cx), my = (float)(yd * k.fy + k.cy);
+    int sx, sy;
+    if (round_coord(mx, sx) && round_coord(my, sy) && sx >= 0 && sx < w && sy >= 0 && sy < h) {
+        si = sy * w + sx;
+        return true;
+    }
+    return false;
+}
+
 }  // namespace dvo

@@ -4,7 +4,10 @@
 // the mapping kernels test per sequence.  Reference citations: file:line under the reference tree.
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <cmath>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 #include <new>
@@ -48,6 +51,7 @@ int MonoBatch::init(int n, const float* K, int w, int h, int ring, const dvo_con
     if (per_camera) DVO_TRY(check_intrinsics(who, K, (size_t)n));
     if (c) cfg = *c; else dvo_config_default(&cfg);
     n_seq = n; R = ring; device = cfg.device;
+    K_full.assign(K, K + (per_camera ? (size_t)n * 9 : 9));
     DVO_TRY(select_device(device));
     if (cfg.stream) stream = (hipStream_t)cfg.stream;
     else { DVO_HIP(hipStreamCreate(&stream)); own_stream = true; }
@@ -87,6 +91,57 @@ int MonoBatch::init(int n, const float* K, int w, int h, int ring, const dvo_con
     DVO_HIP(hipMemset(meta.p, 0, meta.bytes));
     DVO_HIP(hipMemset(hist_xi.p, 0, hist_xi.bytes));
     return DVO_OK;
+}
+
+int Undistortion::set(const char* who, const float* Dh, bool per_sequence, int n_seq, const float* K_full, bool per_camera, const Geometry& g,
+                      hipStream_t s)
+{
+    if (!Dh) { D.clear(); dev.release(); n_cam = 0; return DVO_OK; }
+    const int nd = per_sequence ? n_seq : 1;
+    for (int q = 0; q < nd; q++)
+        for (int j = 0; j < 5; j++)
+            if (!std::isfinite(Dh[(size_t)q * 5 + j])) {
+                set_error(std::string(who) + ": distortion coefficient " + std::to_string(j) + " of sequence " + std::to_string(q) + " is not finite");
+                return DVO_ERR_BAD_ARGUMENT;
+            }
+    // one table per distinct (fx, fy, cx, cy, D): the bits of the camera the table is computed from
+    std::map<std::array<uint32_t, 9>, int> ids;
+    std::vector<UndistortCam> cams;
+    std::vector<int> cam_of((size_t)n_seq);
+    for (int q = 0; q < n_seq; q++) {
+        UndistortCam c;
+        c.k = make_intr(K_full + (per_camera ? (size_t)q * 9 : 0));
+        memcpy(c.D, Dh + (per_sequence ? (size_t)q * 5 : 0), sizeof c.D);
+        std::array<uint32_t, 9> key;
+        const float f[9] = {c.k.fx, c.k.fy, c.k.cx, c.k.cy, c.D[0], c.D[1], c.D[2], c.D[3], c.D[4]};
+        memcpy(key.data(), f, sizeof f);
+        auto it = ids.emplace(key, (int)cams.size());
+        if (it.second) cams.push_back(c);
+        cam_of[(size_t)q] = it.first->second;
+    }
+    const int T = g.top(), tw = g.w[T], th = g.h[T];
+    const size_t head = ((size_t)n_seq + 3) & ~(size_t)3, tab = (size_t)tw * th * cams.size();
+    DevBuf cams_dev;
+    DVO_TRY(cams_dev.alloc(sizeof(UndistortCam) * cams.size()));
+    DVO_HIP(hipStreamSynchronize(s));   // (the previous tables may still be read by queued work: none before the first frame)
+    D.clear(); n_cam = 0;               // (a failure from here on leaves no undistortion rather than a half-built one)
+    DVO_TRY(dev.alloc(sizeof(int) * (head + tab)));
+    DVO_HIP(hipMemcpyAsync(cams_dev.p, cams.data(), cams_dev.bytes, hipMemcpyHostToDevice, s));
+    DVO_HIP(hipMemcpyAsync(dev.p, cam_of.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
+    n_cam = (int)cams.size();
+    launch_undistort_map(cams_dev.as<UndistortCam>(), n_cam, g.src_w, g.src_h, g.culls, tw, th, dev.as<int>() + head, s);
+    DVO_HIP(hipGetLastError());
+    DVO_HIP(hipStreamSynchronize(s));   // (cams_dev and cam_of go out of scope)
+    D.resize((size_t)n_seq * 5);
+    for (int q = 0; q < n_seq; q++) memcpy(&D[(size_t)q * 5], Dh + (per_sequence ? (size_t)q * 5 : 0), 5 * sizeof(float));
+    return DVO_OK;
+}
+
+int MonoBatch::set_distortion(const float* D, bool per_sequence)
+{
+    if (latest_id >= 0) { set_error("dvo_batch_set_distortion: the batch has consumed a frame (D is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    return und.set("dvo_batch_set_distortion", D, per_sequence, n_seq, K_full.data(), K_full.size() > 9, g, stream);
 }
 
 int MonoBatch::set_initial_depth(const float* depth_host, const float* sigma_host)
@@ -131,11 +186,14 @@ int MonoBatch::odometrize_host(const void* frames, size_t bytes, FrameInput in)
     Stage& st = stage[n_host & 1];
     if (st.buf.bytes < bytes) DVO_TRY(st.buf.alloc(bytes));
     if (st.used) DVO_HIP(hipStreamWaitEvent(cstream, st.consumed, 0));
-    if (in.raw()) {  // only the rows the pyramid keeps cross PCIe (Batch::push_host_frame)
-        in.rows_decimated = decimate_host_rows && can_decimate_rows(g);
+    // only the rows the pyramid keeps cross PCIe (Batch::push_host_frame) -- unless the frames are undistorted: the remap reads any
+    // row, so whole frames go up (4x the bytes at cull 2)
+    const bool decimate = decimate_host_rows && can_decimate_rows(g) && !und.enabled();
+    if (in.raw()) {
+        in.rows_decimated = decimate;
         DVO_TRY(upload_rows(st.buf.p, frames, (size_t)g.src_w * in.channels, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
     } else {
-        in.rows_decimated = decimate_host_rows && can_decimate_rows(g);
+        in.rows_decimated = decimate;
         DVO_TRY(upload_rows(st.buf.p, frames, (size_t)g.src_w * sizeof(float), g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
     }
     DVO_HIP(hipEventRecord(st.copied, cstream));
@@ -158,6 +216,8 @@ int MonoBatch::odometrize(const FrameInput& in)
     if (!in.key0() || (in.raw() && in.channels != 1 && in.channels != 3 && in.channels != 4)) { set_error("null device pointer / bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
     FrameInput gin = in;          // mono: gray only
     gin.depth = nullptr; gin.sigma = nullptr; gin.depth16 = nullptr;
+    if (und.enabled() && gin.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
+    und.apply(gin, n_seq);        // dvo_batch_set_distortion: k_pyramid_remap
     DVO_TRY(select_device(device));
     const int T = g.top(), tw = g.w[T], th = g.h[T], np = tw * th;
     // Frame::latest_id (frame.cpp:5) advances only once the frame's launches were queued: a call that fails leaves the batch where it
@@ -349,6 +409,25 @@ int dvo_batch_odometrize_raw_host(dvo_batch* b, const uint8_t* rgb, int channels
     FrameInput in;
     in.rgb = rgb; in.channels = channels;
     return b->mono->odometrize_host(rgb, (size_t)channels * b->mono->n_seq * b->mono->g.src_w * b->mono->g.src_h, in);
+}
+
+int dvo_batch_set_distortion(dvo_batch* b, const float* D, int per_sequence)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->mono) { set_error("dvo_batch_set_distortion: needs a mono batch (sensor-depth batches do not undistort)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->mono->set_distortion(D, per_sequence != 0);
+}
+
+int dvo_batch_get_distortion(dvo_batch* b, float* D, int* enabled)
+{
+    DVO_NEED_MONO(b);
+    const MonoBatch& M = *b->mono;
+    if (D) {
+        if (M.und.enabled()) memcpy(D, M.und.D.data(), sizeof(float) * M.und.D.size());
+        else memset(D, 0, sizeof(float) * 5 * (size_t)M.n_seq);
+    }
+    if (enabled) *enabled = M.und.enabled() ? 1 : 0;
+    return DVO_OK;
 }
 
 int dvo_batch_world_poses(dvo_batch* b, float* xi_world, float* T_world, int* is_keyframe)

@@ -99,6 +99,7 @@ EXPORTS = [
     "dvo_selftest_reciprocal", "dvo_selftest_sqrt", "dvo_selftest_division", "dvo_selftest_trig",
     "dvo_batch_set_actions", "dvo_batch_last_status", "dvo_batch_copy_status_device",
     "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics", "dvo_batch_create_mono_cameras",
+    "dvo_batch_set_distortion", "dvo_batch_get_distortion", "dvo_vo_set_distortion",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -447,6 +448,17 @@ class VisualOdometry:
         g = f32(gray); d = f32(depth); s = f32(sigma)
         _check(lib().dvo_vo_init_keyframe(self._p, fp(g), fp(d), fp(s)))
 
+    def setDistortion(self, D):
+        """Undistort every mono frame (Loader::getNormalizedUndistortedImages) with the creation K and D = (k1, k2, p1, p2, k3);
+        None clears.  Before the first frame (dvo_vo_set_distortion)."""
+        if D is None:
+            _check(lib().dvo_vo_set_distortion(self._p, None))
+            return
+        d = f32(D)
+        if d.shape != (5,):
+            raise ValueError("setDistortion: expected float[5], got shape %s" % (d.shape,))
+        _check(lib().dvo_vo_set_distortion(self._p, fp(d)))
+
     def odometrize(self, gray):
         g = f32(gray); T = np.zeros(16, np.float32); key = C.c_int(0)
         _check(lib().dvo_vo_odometrize(self._p, fp(g), fp(T), C.byref(key)))
@@ -666,6 +678,23 @@ class MonoBatch:
         d = f32(depth); s = f32(sigma)
         assert d.shape == (self.height // 4, self.width // 4)
         _check(lib().dvo_batch_set_initial_depth(self._p, fp(d), fp(s)))
+
+    def set_distortion(self, D):
+        """Undistort every frame (Loader::getNormalizedUndistortedImages) with each sequence's creation K: D float [5] for every
+        sequence or [n_seq, 5], OpenCV order (k1, k2, p1, p2, k3); None clears.  Before the first frame (dvo_batch_set_distortion)."""
+        if D is None:
+            _check(lib().dvo_batch_set_distortion(self._p, None, 0))
+            return
+        d = f32(D)
+        if d.shape not in ((5,), (self.n_seq, 5)):
+            raise ValueError("set_distortion: expected float[5] or float[%d, 5], got shape %s" % (self.n_seq, d.shape))
+        _check(lib().dvo_batch_set_distortion(self._p, fp(d), 1 if d.ndim == 2 else 0))
+
+    def distortion(self):
+        """(D float32 [n_seq, 5], enabled): the coefficients in use (zeros when none)."""
+        d = np.zeros((self.n_seq, 5), np.float32); en = C.c_int(0)
+        _check(lib().dvo_batch_get_distortion(self._p, fp(d), C.byref(en)))
+        return d, bool(en.value)
 
     def setInitialDepthDevice(self, depth_ptr, sigma_ptr):
         _check(lib().dvo_batch_set_initial_depth_device(self._p, C.c_void_p(depth_ptr), C.c_void_p(sigma_ptr)))

@@ -94,6 +94,14 @@ int dvo_vo_odometrize(dvo_vo* vo, const float* gray, float T_world[16], int* is_
 int dvo_vo_odometrize_raw(dvo_vo* vo, const uint8_t* rgb, int channels, float T_world[16], int* is_keyframe);
 /* cv::Mat1f odometrizeUsingDepth(gray, depth, sigma), system.hpp:77-93 -> 4x4 RELATIVE pose. */
 int dvo_vo_odometrize_depth(dvo_vo* vo, const float* gray, const float* depth, const float* sigma, float T_rel[16]);
+/* Lens undistortion of every mono frame (Loader::getNormalizedUndistortedImages, loader.cpp:15-42), fused into the pyramid build:
+ * D = (k1, k2, p1, p2, k3) in OpenCV order, host memory, copied before the call returns; NULL clears.  Rules as
+ * dvo_batch_set_distortion (one sequence, the K of dvo_vo_create): dvo_vo_odometrize and dvo_vo_odometrize_raw then give the bits a
+ * plain handle gives fed dvo_op_undistort(frame, K, D), track log included.  Before the first frame only: after dvo_vo_odometrize*
+ * or dvo_vo_init_keyframe -> DVO_ERR_NOT_READY, nothing changed (dvo_vo_load is not a frame and D is not stored: give a restored
+ * handle its D again).  A handle with D set refuses dvo_vo_odometrize_depth, dvo_vo_odometrize_depth_raw and dvo_vo_init_keyframe
+ * with DVO_ERR_BAD_ARGUMENT (sensor-depth frames are not undistorted). */
+int dvo_vo_set_distortion(dvo_vo* vo, const float D[5]);
 
 /* FrameHistory (include/system/frame.hpp:146-188): keyframe / depth-map access. index 0 = oldest. */
 int dvo_vo_keyframe_count(const dvo_vo* vo);
@@ -276,6 +284,26 @@ int dvo_batch_copy_world_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_
  * only), its world twist, id, the number of keyframes the sequence has created and the valid-update count of the last frame */
 int dvo_batch_keyframe_get(dvo_batch* b, int seq, int level, float* gray, float* depth, float* sigma, float* age, float xi[6], int* id,
                            int* n_keyframes, int* valid_updates);
+/* Lens undistortion of every frame of a mono batch (Loader::getNormalizedUndistortedImages, loader.cpp:15-42; main.cpp:44-49 feeds
+ * its output to odometrize): D = [5] for every sequence (per_sequence = 0) or [n_seq][5] (per_sequence = 1), OpenCV order
+ * (k1, k2, p1, p2, k3), host memory, copied before the call returns.  NULL clears.  From then on every frame that enters through
+ * any odometrize entry point -- float or raw, device or host -- is undistorted first: sequence s gives, bit for bit, the world poses,
+ * keyframe flags, keyframe maps and mono stats a plain handle with the same K, config and initial depth gives when it is fed
+ * dvo_op_undistort(frame_s, K_s, D_s) (raw frames: of their dvo_op_ingest gray).
+ *  - The undistortion K of a sequence is its creation K at full resolution: the K of dvo_batch_create_mono, or row s of
+ *    dvo_batch_create_mono_cameras.  The new camera matrix is that same K (initUndistortRectifyMap(K, D, I, K)), nearest
+ *    neighbour, DVO_INVALID outside the image.
+ *  - An all-zero D is still applied: it gives what dvo_op_undistort gives with zero D.
+ *  - The remap is computed once here (one table of int32 source indices per distinct (K, D), (width/4) x (height/4) entries) and
+ *    gathered inside the pyramid kernel: no undistorted frame is stored.  The host entry points then upload whole frames instead of
+ *    the one row in four the pyramid keeps (4x the PCIe bytes).
+ *  - Errors, returned before anything is enqueued: a NULL handle, a non-finite coefficient (dvo_last_error names the first bad
+ *    sequence) or a sensor-depth batch (dvo_batch_create) -> DVO_ERR_BAD_ARGUMENT; a call after the batch has consumed a frame
+ *    -> DVO_ERR_NOT_READY, nothing changed (D is fixed for the life of the keyframes, as K).
+ * A batch that never sets D runs exactly the kernels it runs without this call.
+ * get: D [n_seq][5] as set (zeros when none; may be NULL) and *enabled = 1 when set (may be NULL). */
+int dvo_batch_set_distortion(dvo_batch* b, const float* D, int per_sequence);
+int dvo_batch_get_distortion(dvo_batch* b, float* D /*[n_seq][5]*/, int* enabled);
 /* Per-sequence counters of a mono batch.  `clamped_pixels` makes the one deviation of the ring from the reference's unbounded
  * FrameHistory (frame.hpp:146-188) visible: a pixel older than the `ring_keyframes` retained keyframes is searched against the
  * oldest retained one instead of the keyframe it was born in (mapper.cpp:99-101, frame_history[age]); the count is cumulative and

@@ -63,6 +63,9 @@ public:
 
     // replaces the cv::randn initial depth (include/system/frame.hpp:17-21): maps at width/4 x height/4
     void setInitialDepth(const float* depth, const float* sigma) { check(dvo_vo_set_initial_depth(vo_, depth, sigma)); }
+    // Loader::getNormalizedUndistortedImages (src/core/loader.cpp:15-42) fused into odometrize / odometrizeRaw: D = (k1, k2, p1, p2, k3)
+    // with the creation K, before the first frame (dvo_vo_set_distortion)
+    void setDistortion(const std::array<float, 5>& D) { check(dvo_vo_set_distortion(vo_, D.data())); }
 
     // cv::Mat1f odometrize(const cv::Mat1f& gray), system.hpp:44-74: 4x4 world pose exp(m_xi)
     Mat4 odometrize(const float* gray, bool* is_keyframe = nullptr)
@@ -195,6 +198,17 @@ public:
     BatchMono(const BatchMono&) = delete;
     BatchMono& operator=(const BatchMono&) = delete;
     void setInitialDepth(const float* depth, const float* sigma) { check(dvo_batch_set_initial_depth(b_, depth, sigma)); }
+    // lens undistortion of every frame, before the first one: D[5] for every sequence, or (perSequence) D[n_seq][5]; nullptr clears
+    // (dvo_batch_set_distortion).  distortion(): the [n_seq][5] coefficients in use (empty when none).
+    void setDistortion(const float* D, bool perSequence = false) { check(dvo_batch_set_distortion(b_, D, perSequence ? 1 : 0)); }
+    std::vector<std::array<float, 5>> distortion()
+    {
+        std::vector<std::array<float, 5>> D(n_);
+        int enabled = 0;
+        check(dvo_batch_get_distortion(b_, D[0].data(), &enabled));
+        if (!enabled) D.clear();
+        return D;
+    }
     void odometrizeDevice(const float* gray) { check(dvo_batch_odometrize_device(b_, gray)); }
     void odometrizeRawDevice(const uint8_t* rgb, int channels) { check(dvo_batch_odometrize_raw_device(b_, rgb, channels)); }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
