@@ -669,17 +669,42 @@ def test_randomized_propagate_and_regularize_sweep():
         exp = orc.propagate(dpos, sigma, age, xi, K)
         for name, a, b in zip(("depth", "sigma", "age"), got, exp):
             np.testing.assert_array_equal(a, b, err_msg="propagate %s %d %dx%d" % (name, case, w, h))
+    # propagate with an anisotropic camera (fy = 0.6 fx) and a principal point far off the map's centre
+    for case in range(8):
+        w, h = sizes[3 + case % 6]
+        depth = rng.normal(1.5, 0.5, (h, w)).astype(np.float32)
+        sigma = (np.abs(rng.normal(0.3, 0.2, (h, w))) + 0.01).astype(np.float32)
+        depth[rng.uniform(size=depth.shape) < 0.05] = INV
+        age = rng.randint(0, 10, depth.shape).astype(np.float32)
+        f = 0.9 * max(w, h)
+        K = (np.array([f, 0, w / 2.0, 0, 0.6 * f, h / 2.0, 0, 0, 1], np.float32) if case % 2 == 0 else
+             np.array([f, 0, 0.15 * w, 0, f, 0.85 * h, 0, 0, 1], np.float32))
+        xi = (np.array([0.02, 0.02, 0.25, 0.03, 0.03, 0.05]) * rng.standard_normal(6)).astype(np.float32)
+        got = dvo.Implement.propagate(depth, sigma, age, xi, K)
+        exp = orc.propagate(depth, sigma, age, xi, K)
+        for name, a, b in zip(("depth", "sigma", "age"), got, exp):
+            np.testing.assert_array_equal(a, b, err_msg="propagate (camera %d) %s %d %dx%d" % (case % 2, name, case, w, h))
+        assert (exp[2] > 0).sum() > w * h // 8, (case, w, h)   # a good part of the map was carried over (age > 0)
+
+
+# cameras of the sweep cases that do not use K640 scaled to the frame (keyed by the case's seed): a skew term (depthEstimate's full-K
+# branch, k_sparse == 0) and a strongly anisotropic camera
+_SWEEP_K = {11: np.array([[525.0, 1.5, 319.5], [0, 525.0, 239.5], [0, 0, 1]], np.float32),
+            12: np.array([[600.0, 0, 319.5], [0, 450.0, 239.5], [0, 0, 1]], np.float32)}
 
 
 @pytest.mark.parametrize("seed,w,h,gain,sig,young", [(1, 640, 480, 20.0, 0.3, 0.5), (2, 640, 480, 20.0, 0.2, 0.9), (5, 640, 480, 40.0, 0.5, 0.0),
-                                                     (6, 640, 480, 30.0, 0.4, 0.3), (9, 648, 488, 25.0, 0.3, 0.5)])
+                                                     (6, 640, 480, 30.0, 0.4, 0.3), (9, 648, 488, 25.0, 0.3, 0.5),
+                                                     (11, 640, 480, 20.0, 0.3, 0.5), (12, 640, 480, 25.0, 0.3, 0.5), (17, 320, 240, 30.0, 0.3, 0.5)])
 def test_mapper_update_sweep(seed, w, h, gain, sig, young):
     """Mapper::update / Implement::update (mapper.cpp:76-137, implement.cpp:23-152,182-214) on three keyframes over baselines from
     short (few search steps) to long (the 102-step cap), a map size that is no multiple of the workgroup's pixel count, prior sigmas
     from 0.2 to the 0.5 clamp and age maps from 'all born in the newest keyframe' to 'all born in the oldest': depth, sigma, age and
-    the valid-update count bit-exact."""
+    the valid-update count bit-exact.  Seeds 11 and 12 use the cameras of _SWEEP_K; 320 x 240 clips the mapping window of
+    mapper.cpp:90 at the 80 x 60 map's right and bottom edges."""
     K = np.array(K640, np.float32).copy()
     K[0] *= w / 640.0; K[1] *= h / 480.0
+    K = _SWEEP_K.get(seed, K)
     from dvo_amd import synth
     g, d, s, poses = synth.sequence(6, width=w, height_px=h, K=K, seed=30 + seed, sigma_value=0.5)
     g, d = g.numpy(), d.numpy()
