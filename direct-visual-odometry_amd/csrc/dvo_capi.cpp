@@ -383,6 +383,26 @@ int dvo_batch_get_intrinsics(dvo_batch* b, float* K)
     return DVO_OK;
 }
 
+int dvo_batch_set_sensor_distortion(dvo_batch* b, const float* D, int per_sequence)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_sensor_distortion: needs a sensor-depth batch (a mono batch takes D through dvo_batch_set_distortion)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->impl.set_sensor_distortion(D, per_sequence != 0);
+}
+
+int dvo_batch_get_sensor_distortion(dvo_batch* b, float* D, int* enabled)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    DVO_NOT_MONO(b);
+    const Undistortion& u = b->impl.und;
+    if (D) {
+        if (u.enabled()) memcpy(D, u.D.data(), sizeof(float) * u.D.size());
+        else memset(D, 0, sizeof(float) * 5 * (size_t)b->impl.n_seq);
+    }
+    if (enabled) *enabled = u.enabled() ? 1 : 0;
+    return DVO_OK;
+}
+
 int dvo_batch_last_status(dvo_batch* b, int* status)
 {
     if (!b || !status) return DVO_ERR_BAD_ARGUMENT;

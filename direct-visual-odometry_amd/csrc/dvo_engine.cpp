@@ -239,10 +239,10 @@ static void plan_copy(PyramidArgs& a, const uint8_t* seq_action, const FrameSet*
     }
 }
 
-void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma,
-                   bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from)
+// the arguments of a build from float maps (the caller adds the plan's copy-forward and, optionally, the remap)
+static void float_args(PyramidArgs& a, FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, bool keep_sigma,
+                       bool rows_decimated)
 {
-    PyramidArgs a;
     memset(&a, 0, sizeof a);
     a.src[0] = gray_dev; a.src[1] = depth_dev; a.src[2] = sigma_dev;
     a.src_w = fs.g.src_w; a.src_h = fs.g.src_h; a.culls = fs.g.culls; a.levels = fs.g.levels;
@@ -256,13 +256,20 @@ void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, 
     a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
     fs.sigma_by_validity = false;
     if (depth_dev && sigma_dev) fuse_prep(a, fs);  // wgt written by the same launch (no k_prep_ref pass)
+}
+
+void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma,
+                   bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from)
+{
+    PyramidArgs a;
+    float_args(a, fs, gray_dev, depth_dev, sigma_dev, keep_sigma, rows_decimated);
     plan_copy(a, seq_action, copy_from);
     launch_pyramid(a, fs.n_seq, s);
 }
 
 void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from)
 {
-    if (in.remap) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames, no plan
+    if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames, no plan
         PyramidArgs a;
         memset(&a, 0, sizeof a);
         a.src[0] = in.gray;
@@ -279,7 +286,17 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         launch_pyramid(a, fs.n_seq, s);
         return;
     }
-    if (!in.raw()) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
+    // sensor-depth frames with lens undistortion (dvo_batch_set_sensor_distortion): the arguments of the plain build plus the remap,
+    // whole frames -- launch_pyramid picks k_pyramid_remap_depth
+    if (!in.raw()) {
+        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
+        PyramidArgs a;
+        float_args(a, fs, in.gray, in.depth, in.sigma, keep_sigma, false);
+        a.remap = in.remap; a.remap_cam = in.remap_cam;
+        plan_copy(a, seq_action, copy_from);
+        launch_pyramid(a, fs.n_seq, s);
+        return;
+    }
     PyramidArgs a;
     memset(&a, 0, sizeof a);
     a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_depth = in.depth16;
@@ -302,6 +319,7 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     } else if (dep) {
         fuse_prep(a, fs);
     }
+    a.remap = in.remap; a.remap_cam = in.remap_cam;   // (set only with depth here, and then on whole frames)
     plan_copy(a, seq_action, copy_from);
     launch_pyramid(a, fs.n_seq, s);
 }
@@ -1407,12 +1425,15 @@ int Batch::push_host_frame(const void* p0, size_t n0, const void* p1, size_t n1,
     if (p1 && st.b.bytes < n1) DVO_TRY(st.b.alloc(n1));
     if (p2 && st.c.bytes < n2) DVO_TRY(st.c.alloc(n2));
     if (st.used) DVO_HIP(hipStreamWaitEvent(cstream, st.consumed, 0));
-    if (in.raw()) {  // only the rows the pyramid keeps cross PCIe (the staging buffers are sized for whole frames)
-        in.rows_decimated = decimate_host_rows && can_decimate_rows(g);
+    // only the rows the pyramid keeps cross PCIe (the staging buffers are sized for whole frames) -- unless the frames are undistorted:
+    // the remap reads any row, so whole frames go up
+    const bool decimate = decimate_host_rows && can_decimate_rows(g) && !und.enabled();
+    if (in.raw()) {
+        in.rows_decimated = decimate;
         DVO_TRY(upload_rows(st.a.p, p0, (size_t)g.src_w * in.channels, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
         DVO_TRY(upload_rows(st.b.p, p1, (size_t)g.src_w * 2, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
     } else {
-        in.rows_decimated = decimate_host_rows && can_decimate_rows(g);
+        in.rows_decimated = decimate;
         const size_t rb = (size_t)g.src_w * sizeof(float);
         DVO_TRY(upload_rows(st.a.p, p0, rb, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
         if (p1) DVO_TRY(upload_rows(st.b.p, p1, rb, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
@@ -1439,8 +1460,10 @@ int Batch::prefetch(const FrameInput& in)
     DVO_TRY(select_device(device));
     const int slot = free_slot();
     if (npre >= 2 || slot < 0) { set_error("dvo_batch_prefetch_device: two prefetched frames are already waiting for their push"); return DVO_ERR_NOT_READY; }
+    FrameInput fin = in;
+    und.apply(fin, n_seq);   // dvo_batch_set_sensor_distortion: k_pyramid_remap_depth (device frames: whole)
     if (tracked_once) DVO_HIP(hipStreamWaitEvent(pstream, ev_last_track, 0));
-    build_pyramid(fs[slot], in, pstream, /*keep_sigma=*/false);
+    build_pyramid(fs[slot], fin, pstream, /*keep_sigma=*/false);
     DVO_HIP(hipEventRecord(ev_built[slot], pstream));
     preq[npre] = slot;
     pre_key[npre][0] = in.key0(); pre_key[npre][1] = in.key1();
@@ -1456,6 +1479,9 @@ int Batch::push(const FrameInput& in)
     // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan), or per-sequence intrinsics
     const bool planned = act_pending || act_used || cam_used;
     DVO_TRY(check_actions_input(in));
+    if (und.enabled() && in.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
+    FrameInput fin = in;
+    und.apply(fin, n_seq);   // dvo_batch_set_sensor_distortion: k_pyramid_remap_depth
     int target;
     bool built = false;
     if (npre > 0 && pre_key[0][0] == in.key0() && pre_key[0][1] == in.key1()) {
@@ -1470,7 +1496,7 @@ int Batch::push(const FrameInput& in)
         if (target < 0) { set_error("dvo_batch_push_device: the frames prefetched must be pushed first, in order"); return DVO_ERR_BAD_ARGUMENT; }
     }
     if (!planned) {
-        if (!built) build_pyramid(fs[target], in, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
+        if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
         if (cur >= 0) {
             DVO_TRY(trk.track(fs[target], fs[cur], stream));    // system.hpp:88
             DVO_HIP(hipEventRecord(ev_last_track, stream));
@@ -1482,7 +1508,7 @@ int Batch::push(const FrameInput& in)
         // whole new frame set becomes the reference below (cur = target) and k_track_gn addresses frame sets as it always does
         const bool skips = act_pending;   // (without pending actions every sequence builds: a prefetched set needs nothing more)
         DVO_TRY(launch_plan(cur >= 0));
-        if (!built) build_pyramid(fs[target], in, stream, /*keep_sigma=*/false, skips ? eff.as<uint8_t>() : nullptr, cur >= 0 ? &fs[cur] : &fs[target]);
+        if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, skips ? eff.as<uint8_t>() : nullptr, cur >= 0 ? &fs[cur] : &fs[target]);
         if (cur >= 0) {
             TrackPlan tp;
             tp.action = eff.as<uint8_t>();
@@ -1501,6 +1527,7 @@ int Batch::push(const FrameInput& in)
         if (cam_pending) { cam_K_used = cam_K; cam_pending = false; }   // (k_plan has read this push's camera-changed bytes)
         plan_parity ^= 1;
     }
+    if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
     n_push++;
     prev = cur;
     cur = target;                                           // system.hpp:91
@@ -1602,6 +1629,27 @@ int Batch::set_intrinsics(const float* K)
     const size_t n = (size_t)n_seq;
     if (K) DVO_TRY(check_intrinsics("dvo_batch_set_intrinsics", K, n));
     DVO_TRY(select_device(device));
+    if (und.enabled()) {   // the undistortion camera of a sequence is its current K: new tables where fx, fy, cx or cy change
+        std::vector<float> Kn(n * 9);
+        bool moved = false;
+        for (size_t q = 0; q < n; q++) {
+            memcpy(&Kn[q * 9], K ? K + q * 9 : K_create, 9 * sizeof(float));
+            for (int j : {0, 4, 2, 5}) moved = moved || memcmp(&Kn[q * 9 + j], &cam_K[q * 9 + j], sizeof(float)) != 0;
+        }
+        if (moved) {
+            const std::vector<float> D = und.D;
+            DVO_HIP(hipStreamSynchronize(stream));   // no queued push or (consumed) prefetch still reads the tables it replaces
+            DVO_TRY(und.set("dvo_batch_set_intrinsics", D.data(), true, n_seq, Kn.data(), true, g, stream));
+        }
+    }
+    return stage_cameras(K);
+}
+
+// the intrinsics table of the next push (pinned staging, then one copy in stream order) and its camera-changed bytes; the batch runs
+// the per-sequence path from then on
+int Batch::stage_cameras(const float* K)
+{
+    const size_t n = (size_t)n_seq;
     const size_t table = sizeof(Intr) * (size_t)g.levels * n, bytes = table + n;
     if (!cam_dev.p) {
         DVO_TRY(cam_dev.alloc(bytes));
@@ -1622,16 +1670,32 @@ int Batch::set_intrinsics(const float* K)
         Intr lv[DVO_MAX_LEVELS];
         level_intrinsics(kq, g, lv);
         for (int l = 0; l < g.levels; l++) tab[(size_t)l * n + q] = lv[l];
-        // camera-change rule: fx, fy, cx or cy differ in bits from the table of the last push
+        // camera-change rule: fx, fy, cx or cy differ in bits from the table of the last push, or D does (or goes between none and a row)
         const float* ku = &cam_K_used[q * 9];
-        changed[q] = (memcmp(&kq[0], &ku[0], 4) | memcmp(&kq[4], &ku[4], 4) | memcmp(&kq[2], &ku[2], 4) | memcmp(&kq[5], &ku[5], 4)) != 0;
-        memcpy(&cam_K[q * 9], kq, 9 * sizeof(float));
+        changed[q] = (memcmp(&kq[0], &ku[0], 4) | memcmp(&kq[4], &ku[4], 4) | memcmp(&kq[2], &ku[2], 4) | memcmp(&kq[5], &ku[5], 4)) != 0 ||
+                     distortion_changed(q);
+        if (kq != &cam_K[q * 9]) memcpy(&cam_K[q * 9], kq, 9 * sizeof(float));
     }
     DVO_HIP(hipMemcpyAsync(cam_dev.p, h_cam[k], bytes, hipMemcpyHostToDevice, stream));
     DVO_HIP(hipEventRecord(ev_cam[k], stream));
     cam_staged[k] = true;
     cam_pending = true;
     cam_used = true;
+    return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: lens undistortion
+int Batch::set_sensor_distortion(const float* D, bool per_sequence)
+{
+    if (npre > 0) { set_error("dvo_batch_set_sensor_distortion: a prefetched frame is waiting for its push"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    // Synchronous: the tables are replaced only once no queued push or (consumed) prefetch can still read them
+    DVO_HIP(hipStreamSynchronize(stream));
+    DVO_TRY(und.set("dvo_batch_set_sensor_distortion", D, per_sequence, n_seq, cam_K.data(), true, g, stream));
+    und_pending = true;
+    // before the first push nothing has a reference: the batch stays on the plain path.  After it, the change of camera goes to k_plan
+    // through the camera-changed bytes, on the per-sequence path, as dvo_batch_set_intrinsics
+    if (n_push > 0) return stage_cameras(cam_K.data());
     return DVO_OK;
 }
 

@@ -7,6 +7,7 @@
 // There is NO CPU fallback: every entry point fails with DVO_ERR_NO_DEVICE / DVO_ERR_HIP without a GPU.
 #pragma once
 #include <cstdlib>
+#include <cstring>
 #include <hip/hip_runtime_api.h>
 
 #include <functional>
@@ -105,8 +106,8 @@ struct FrameInput {
     const float* gray = nullptr; const float* depth = nullptr; const float* sigma = nullptr;
     const uint8_t* rgb = nullptr; int channels = 0; const uint16_t* depth16 = nullptr; float depth_scale = 1.0f / 5000.0f;
     bool rows_decimated = false;  // the buffers hold only the rows the pyramid keeps (every 2^culls-th), see upload_rows
-    // mono frames with lens undistortion (Undistortion::apply): k_pyramid_remap gathers each kept pixel through its camera's table.
-    // Gray only, whole frames (rows_decimated = false).
+    // frames with lens undistortion (Undistortion::apply): k_pyramid_remap (mono: gray only) or k_pyramid_remap_depth (sensor depth)
+    // gathers each kept pixel through its camera's table.  Whole frames (rows_decimated = false).
     const int* remap = nullptr;       // [n_cam][th][tw] source indices
     const int* remap_cam = nullptr;   // [n_seq] camera of each sequence
     bool raw() const { return rgb != nullptr; }
@@ -373,6 +374,19 @@ struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sen
     int cam_slot = 0;
     bool cam_pending = false, cam_used = false;
     int set_intrinsics(const float* K);
+    int stage_cameras(const float* K);          // the table of the next push + its camera-changed bytes (K: [n_seq][9], nullptr: creation K)
+    // Lens undistortion of the sensor-depth frames (dvo_batch_set_sensor_distortion): k_pyramid_remap_depth gathers every kept pixel
+    // through the table of the sequence's (current K, D).  A sequence's camera is (fx, fy, cx, cy, D or none): a change of D at a push
+    // sets its camera-changed byte as a change of K does.
+    Undistortion und;                           // D and the tables of the next push (built from cam_K)
+    std::vector<float> und_D_used;              // [n_seq][5] the D of the last push (empty: none)
+    bool und_pending = false;                   // und changed since the last push
+    int set_sensor_distortion(const float* D, bool per_sequence);
+    bool distortion_changed(size_t q) const
+    {
+        if (und.enabled() != !und_D_used.empty()) return true;
+        return und.enabled() && memcmp(&und.D[q * 5], &und_D_used[q * 5], 5 * sizeof(float)) != 0;
+    }
     const Intr* cam_table() const { return cam_used ? cam_dev.as<Intr>() : nullptr; }
     const uint8_t* cam_changed() const { return reinterpret_cast<const uint8_t*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq); }
 };

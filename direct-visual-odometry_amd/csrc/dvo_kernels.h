@@ -44,8 +44,9 @@ struct PyramidArgs {
     const uint8_t* seq_action;                 // [n_seq] effective action (k_plan)
     const float* ref[3][DVO_MAX_LEVELS];       // gray, depth, sigma of the reference set
     const float* ref_wgt[DVO_MAX_LEVELS];
-    // optional lens undistortion of mono frames (remap != nullptr; gray only, whole frames, no plan): k_pyramid_remap gathers each
-    // kept pixel through its sequence's camera table (k_undistort_map) -- launch_pyramid then never picks k_pyramid / k_pyramid_raw4
+    // optional lens undistortion (remap != nullptr; whole frames): k_pyramid_remap (mono frames: gray only, no plan) or, with depth
+    // (raw_depth or src[1] set), k_pyramid_remap_depth gathers each kept pixel through its sequence's camera table (k_undistort_map)
+    // -- launch_pyramid then never picks k_pyramid / k_pyramid_raw4
     const int* remap = nullptr;       // [n_cam][th][tw] source index into the full frame, -1 = border (INVALID)
     const int* remap_cam = nullptr;   // [n_seq] camera (table) of each sequence
 };

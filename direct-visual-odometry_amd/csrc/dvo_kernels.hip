@@ -385,6 +385,136 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
     }
 }
 
+// k_pyramid_remap_depth: k_pyramid of SENSOR-DEPTH frames (gray + depth + sigma, float maps or raw u8 gray/RGB(A) + u16 depth)
+// with the lens undistortion fused in (dvo_batch_set_sensor_distortion).  As k_pyramid_remap, kept pixel (x << culls, y << culls)
+// of the undistorted frame is ONE source pixel: the thread reads its index from the sequence's camera table (k_undistort_map, -1 =
+// border) and gathers gray, depth and sigma (raw: the u8 gray / RGB(A) and the u16 depth) from that one index.  The conversions
+// are per pixel, so they commute with the gather: k_pyramid's raw conversion applied to the gathered bytes gives the bits of
+// dvo_op_undistort applied to each of dvo_op_ingest's three maps.  A border pixel is DVO_INVALID in all three maps, as
+// dvo_op_undistort writes it (its depth, -2, is below any min_depth: it never contributes).  Every level and the fused wgt maps are
+// written with k_pyramid's operations.  PPT = 4 (the usual case: tw % 4 == 0, 16-byte aligned tops and table) reads four table
+// entries with one 16-byte load and writes the four top-level values of each map with one 16-byte store, as k_pyramid_raw4;
+// PPT = 1 is the scalar fallback.  PLAN: the workgroups of a DVO_SEQ_SKIP sequence copy their reference forward, as k_pyramid<true>.
+// The table is read with plain loads (one table serves every sequence of the camera and stays in L2), the frames and the levels
+// with nontemporal accesses.  The input holds whole frames (src_img_rows = src_h): the gather reads any row.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+template <int PPT, bool PLAN>
+__global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
+{
+    static_assert(PPT == 1 || PPT == 4, "one or four kept pixels per thread");
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1], gw = tw / PPT;
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int gi = (int)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= gw * th || seq >= a.n_seq) return;
+    int y, xg;
+    split_index(gi, gw, a.inv_tw * (float)PPT, xg, y);
+    const int x0 = xg * PPT, T = a.levels - 1;
+    const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x0;
+    const bool prep = a.wgt[0] != nullptr;   // (depth and sigma are always present here)
+    bool skip = false;
+    if constexpr (PLAN) skip = a.seq_action[seq] == DVO_SEQ_SKIP;   // (uniform per workgroup)
+    float top[3][PPT];   // the top-level value of each map: what the build stores there (lower levels: pass_valid of it)
+#pragma unroll
+    for (int m = 0; m < 3; m++)
+#pragma unroll
+        for (int k = 0; k < PPT; k++) top[m][k] = 0.0f;
+    if (skip) {   // copy-forward: every value this thread's build would write, none of its input
+#pragma unroll
+        for (int m = 0; m < 3; m++) {
+            if (a.dst[m][T] == nullptr) continue;
+            if constexpr (PPT == 4) {
+                const f4 v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref[m][T] + ot));
+                top[m][0] = v.x; top[m][1] = v.y; top[m][2] = v.z; top[m][3] = v.w;
+            } else {
+                top[m][0] = __builtin_nontemporal_load(a.ref[m][T] + ot);
+            }
+        }
+    } else {
+        const int cam = load_seq_entry(a.remap_cam, seq);   // (one scalar load)
+        const int* tab = a.remap + (size_t)cam * tw * th + (size_t)y * tw + x0;
+        int si[PPT];
+        if constexpr (PPT == 4) {
+            const i32x4 e = *reinterpret_cast<const i32x4*>(tab);
+            si[0] = e.x; si[1] = e.y; si[2] = e.z; si[3] = e.w;
+        } else {
+            si[0] = tab[0];
+        }
+        const size_t base = (size_t)seq * a.src_w * a.src_h;
+#pragma unroll
+        for (int k = 0; k < PPT; k++) {
+            float raw[3] = {kInvalid, kInvalid, kInvalid};
+            if (si[k] >= 0) {
+                const size_t so = base + (size_t)si[k];
+                if (a.raw_rgb != nullptr) {   // k_pyramid's raw conversion of the one gathered pixel
+                    unsigned g8;
+                    if (a.raw_channels == 1) {
+                        g8 = __builtin_nontemporal_load(a.raw_rgb + so);
+                    } else {
+                        const uint8_t* p = a.raw_rgb + so * (size_t)a.raw_channels;
+                        g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
+                    }
+                    raw[0] = (float)g8 * a.raw_gray_scale;
+                    const unsigned d = __builtin_nontemporal_load(a.raw_depth + so);
+                    raw[1] = (float)d * a.raw_depth_scale;
+                    raw[2] = d > 0 ? a.raw_sigma_valid : a.raw_sigma_invalid;
+                    if (a.raw_invalidate_gray && d == 0) raw[0] = kInvalid;
+                } else {
+#pragma unroll
+                    for (int m = 0; m < 3; m++) raw[m] = __builtin_nontemporal_load(a.src[m] + so);
+                }
+            }
+            // top level: cullImage(src, culls); culls == 0 aliases the input (convert.cpp:9-10), no pass_valid
+#pragma unroll
+            for (int m = 0; m < 3; m++) top[m][k] = a.culls == 0 ? raw[m] : pass_valid(raw[m]);
+        }
+    }
+    // top level (t = 0)
+    if constexpr (PPT == 4) {
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+            if (a.dst[m][T] != nullptr)
+                __builtin_nontemporal_store(f4{top[m][0], top[m][1], top[m][2], top[m][3]}, reinterpret_cast<f4*>(a.dst[m][T] + ot));
+        if (prep) {
+            f4 wgv;
+            if (skip) {
+                wgv = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref_wgt[T] + ot));
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; k++) wgv[k] = gn_weight(a.step[T], a.sigma_min, a.sigma_max, top[2][k]);
+            }
+            __builtin_nontemporal_store(wgv, reinterpret_cast<f4*>(a.wgt[T] + ot));
+        }
+    } else {
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+            if (a.dst[m][T] != nullptr) __builtin_nontemporal_store(top[m][0], a.dst[m][T] + ot);
+        if (prep)
+            __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[T] + ot) : gn_weight(a.step[T], a.sigma_min, a.sigma_max, top[2][0]),
+                                        a.wgt[T] + ot);
+    }
+    for (int t = 1; t < a.levels; t++) {   // lower levels: pixels whose coordinates are multiples of 2^t
+        const int msk = (1 << t) - 1;
+        if (y & msk) break;
+        const int l = a.levels - 1 - t, ly = y >> t;
+        if (ly >= a.h[l]) continue;
+#pragma unroll
+        for (int k = 0; k < PPT; k++) {
+            const int x = x0 + k;
+            if (x & msk) continue;
+            const int lx = x >> t;
+            if (lx >= a.w[l]) continue;
+            const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+            const float sg = pass_valid(top[2][k]);
+#pragma unroll
+            for (int m = 0; m < 3; m++)
+                if (a.dst[m][l] != nullptr) __builtin_nontemporal_store(m == 2 ? sg : pass_valid(top[m][k]), a.dst[m][l] + o);
+            if (prep)
+                __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[l] + o) : gn_weight(a.step[l], a.sigma_min, a.sigma_max, sg),
+                                            a.wgt[l] + o);
+        }
+    }
+}
+
 // k_cull: a single Convert::cullImage (operator-level parity)
 __global__ void __launch_bounds__(256) k_cull(const float* __restrict__ src, int w, int h, int times, float* __restrict__ dst)
 {
@@ -1954,11 +2084,35 @@ void launch_undistort_map(const UndistortCam* cams_dev, int n_cam, int w, int h,
     hipLaunchKernelGGL(k_undistort_map, seq_grid(cdiv(tw * th, 256), (unsigned)n_cam), dim3(256), 0, s, cams_dev, n_cam, w, h, culls, tw, th, table);
 }
 
+// k_pyramid_remap_depth: four kept pixels per thread where the top-level width and every 16-byte access allow it, else one
+// (DVO_REMAP_DEPTH_SCALAR set: always one -- A/B runs, tools/bench_sensor_undistort.py)
+static void launch_pyramid_remap_depth(const PyramidArgs& a, hipStream_t s)
+{
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    bool vec = (tw % 4) == 0 && (reinterpret_cast<uintptr_t>(a.remap) % 16) == 0 && getenv("DVO_REMAP_DEPTH_SCALAR") == nullptr;
+    const void* tops[8] = {a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T], a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]};
+    for (const void* p : tops) vec = vec && (reinterpret_cast<uintptr_t>(p) % 16) == 0;   // (nullptr passes: not accessed)
+    const bool plan = a.seq_action != nullptr;
+    if (vec) {
+        const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)a.n_seq);
+        if (plan) hipLaunchKernelGGL((k_pyramid_remap_depth<4, true>), grid, dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_pyramid_remap_depth<4, false>), grid, dim3(256), 0, s, a);
+        return;
+    }
+    const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
+    if (plan) hipLaunchKernelGGL((k_pyramid_remap_depth<1, true>), grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_pyramid_remap_depth<1, false>), grid, dim3(256), 0, s, a);
+}
+
 void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
 {
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
+    if (a.remap != nullptr && (a.raw_depth != nullptr || a.src[1] != nullptr)) {   // sensor-depth frames, lens undistortion fused in
+        launch_pyramid_remap_depth(a, s);
+        return;
+    }
     if (a.remap != nullptr) {   // lens undistortion fused in (mono frames): never k_pyramid_raw4 / k_pyramid
         hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
         return;

@@ -100,6 +100,7 @@ EXPORTS = [
     "dvo_batch_set_actions", "dvo_batch_last_status", "dvo_batch_copy_status_device",
     "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics", "dvo_batch_create_mono_cameras",
     "dvo_batch_set_distortion", "dvo_batch_get_distortion", "dvo_vo_set_distortion",
+    "dvo_batch_set_sensor_distortion", "dvo_batch_get_sensor_distortion",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -624,6 +625,24 @@ class Batch:
         k = np.zeros((self.n_seq, 3, 3), np.float32)
         _check(lib().dvo_batch_get_intrinsics(self._p, k.ctypes.data_as(C.c_void_p)))
         return k
+
+    def set_distortion(self, D):
+        """Undistort every frame from the NEXT push on with each sequence's current K: D float [5] for every sequence or [n_seq, 5],
+        OpenCV order (k1, k2, p1, p2, k3); None clears.  A sequence whose D changes loses its reference at that push
+        (dvo_batch_set_sensor_distortion)."""
+        if D is None:
+            _check(lib().dvo_batch_set_sensor_distortion(self._p, None, 0))
+            return
+        d = f32(D)
+        if d.shape not in ((5,), (self.n_seq, 5)):
+            raise ValueError("set_distortion: expected float[5] or float[%d, 5], got shape %s" % (self.n_seq, d.shape))
+        _check(lib().dvo_batch_set_sensor_distortion(self._p, fp(d), 1 if d.ndim == 2 else 0))
+
+    def distortion(self):
+        """(D float32 [n_seq, 5], enabled): the coefficients the next push uses (zeros when none)."""
+        d = np.zeros((self.n_seq, 5), np.float32); en = C.c_int(0)
+        _check(lib().dvo_batch_get_sensor_distortion(self._p, fp(d), C.byref(en)))
+        return d, bool(en.value)
 
     def copy_status_device(self, ptr):
         """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""

@@ -224,6 +224,34 @@ int dvo_batch_copy_status_device(dvo_batch* b, int* status_dev);  /* [n_seq], as
  * dvo_batch_get_intrinsics copies the table the next push uses ([n_seq][9], host, synchronous): the creation K until set. */
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K);   /* [n_seq][9]; NULL = the creation K for every sequence */
 int dvo_batch_get_intrinsics(dvo_batch* b, float* K);         /* [n_seq][9] */
+/* ---- lens undistortion of sensor-depth frames (RGB-D cameras) -------------------------------------------------------------
+ * dvo_batch_set_sensor_distortion undistorts every frame of a sensor-depth batch (dvo_batch_create) while its pyramid is built:
+ * D = [5] for every sequence (per_sequence = 0) or [n_seq][5] (per_sequence = 1), OpenCV order (k1, k2, p1, p2, k3), host memory,
+ * copied before the call returns.  NULL clears.  Applies from the NEXT push on (any push or prefetch entry point, float or raw,
+ * device or host): sequence s then gives, bit for bit, the poses, status and track log a plain batch with the same creation K,
+ * intrinsics table, config, actions and feeds gives when it is fed dvo_op_undistort(m, K_s, D_s) of each of gray, depth and sigma
+ * (raw frames: of each of the three maps dvo_op_ingest returns).
+ *  - The undistortion camera of s is its CURRENT full-resolution K: the creation K, or row s of the dvo_batch_set_intrinsics table in
+ *    force at that push.  The new camera matrix is that same K (initUndistortRectifyMap(K, D, I, K)), nearest neighbour: depth is
+ *    z-depth and is never interpolated.  Outside the image all three maps are DVO_INVALID (such a pixel never contributes).
+ *  - An all-zero D row is still applied: it gives what dvo_op_undistort gives with zero D (a mixed rig marks an undistorted camera so).
+ *  - Camera-change rule: a sequence's camera is (fx, fy, cx, cy, D or none).  A sequence whose D changes in bits at a push, or goes
+ *    between none and a row, loses its reference there exactly as for a change of K (see dvo_batch_set_intrinsics).
+ *  - Before the first push the call only selects the kernel: a batch that sets D there and no actions or intrinsics stays on the
+ *    plain path.  After it, the batch runs the per-sequence path from then on, as after dvo_batch_set_intrinsics.
+ *  - The remap is computed here (one table of int32 source indices per distinct (fx, fy, cx, cy, D), (width >> culls) x
+ *    (height >> culls) entries: 307 KB at 640x480, cull 1) and gathered inside the pyramid kernel: no undistorted frame is stored.
+ *    The host entry points then upload whole frames instead of the rows the pyramid keeps.
+ *  - SYNCHRONOUS: this call, and dvo_batch_set_intrinsics while D is set and a sequence's K changes, wait for the work queued on the
+ *    handle's stream before they replace the tables (camera swaps are rare).  Pushes queued before the call give the same results.
+ *  - Errors, returned before anything changes: a NULL handle, a non-finite coefficient (dvo_last_error names the first bad
+ *    sequence) or a mono batch (use dvo_batch_set_distortion) -> DVO_ERR_BAD_ARGUMENT; a prefetched frame waiting for its push ->
+ *    DVO_ERR_NOT_READY.
+ * A batch that never sets D runs exactly the kernels it runs without this call.  The single-stream dvo_vo depth entry points do not
+ * undistort (a one-sequence batch does).
+ * get: the D the next push uses, [n_seq][5] (zeros when none; may be NULL), and *enabled = 1 when set (may be NULL). */
+int dvo_batch_set_sensor_distortion(dvo_batch* b, const float* D, int per_sequence);
+int dvo_batch_get_sensor_distortion(dvo_batch* b, float* D /*[n_seq][5], may be NULL*/, int* enabled /*may be NULL*/);
 /* ---- one block of sequences per GPU (BASELINE config 5) -------------------------------------------
  * The path shards across sequences only (frame t of a sequence tracks against state from frames < t: system.hpp:48,57,67): every
  * rank -- one process per GPU -- owns a contiguous block of the sequences and tracks it with no communication.

@@ -174,6 +174,17 @@ public:
         check(dvo_batch_get_intrinsics(b_, out[0].data()));
         return out;
     }
+    // lens undistortion of every frame from the next push on: D[5] for every sequence, or (perSequence) D[n_seq][5]; nullptr clears
+    // (dvo_batch_set_sensor_distortion).  distortion(): the [n_seq][5] coefficients the next push uses (empty when none).
+    void setDistortion(const float* D, bool perSequence = false) { check(dvo_batch_set_sensor_distortion(b_, D, perSequence ? 1 : 0)); }
+    std::vector<std::array<float, 5>> distortion()
+    {
+        std::vector<std::array<float, 5>> D(n_);
+        int enabled = 0;
+        check(dvo_batch_get_sensor_distortion(b_, D[0].data(), &enabled));
+        if (!enabled) D.clear();
+        return D;
+    }
     dvo_batch* handle() { return b_; }
 
 private:
