@@ -269,7 +269,8 @@ void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, 
 
 void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from)
 {
-    if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames, no plan
+    if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
+                                         // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
         PyramidArgs a;
         memset(&a, 0, sizeof a);
         a.src[0] = in.gray;
@@ -282,6 +283,7 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         }
         a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
         a.remap = in.remap; a.remap_cam = in.remap_cam;
+        a.seq_action = seq_action;
         fs.sigma_by_validity = false;
         launch_pyramid(a, fs.n_seq, s);
         return;

@@ -420,7 +420,8 @@ struct MonoBatch {
     DevBuf xi_world, T_world, is_key;
     DevBuf need_list;        // [0] = number of sequences that create a keyframe on this frame, [4..] their ids (k_mono_decide)
     float* depth_alt = nullptr;  // the second top-level depth buffer of `ref` (k_regularize_redecimate ping-pongs between the two)
-    int latest_id = -1;      // Frame::latest_id, frame.cpp:5 (all sequences advance in lockstep)
+    int latest_id = -1;      // Frame::latest_id, frame.cpp:5 (all sequences advance in lockstep); with actions: calls made - 1
+                             // (each sequence's own frame id is then MonoSeq::frame_id)
     bool have_init = false;
     // Per-camera batch (dvo_batch_create_mono_cameras): [level][n_seq] Intr (the tracker's table, Tracker::cam_k; its top-level row
     // is the mapping kernels' Intr), then [n_seq] MapK (culled top-level K9 + k_sparse).  Fixed at creation.  Empty: one K.
@@ -450,6 +451,28 @@ struct MonoBatch {
     double prof_update_ms = 0, prof_regularize_ms = 0, prof_propagate_ms = 0;
     uint64_t prof_frames = 0;
     int collect_map_profile();
+    // Per-sequence skip / restart (dvo_batch_set_mono_actions).  Allocated on first use; a batch that never sets
+    // actions runs the plain path.  k_plan resolves the actions with has_kf = "has a keyframe"; started = has started before (the
+    // first start keeps the slot's own initial maps); need_save parks MonoSeq::need of the sequences that do not track.
+    DevBuf act_dev, has_kf, eff, status, plan_lists, plan_tally, started, need_save;
+    uint8_t* h_act[2] = {nullptr, nullptr};     // pinned staging of host actions, alternately (ev_act: their copy has been read)
+    hipEvent_t ev_act[2] = {nullptr, nullptr};
+    bool act_staged[2] = {false, false};
+    int act_slot = 0;
+    int* h_ready = nullptr;                     // mapped host words of TrackPlan::ready, one per plan parity
+    int* d_ready = nullptr;
+    const uint8_t* act_src = nullptr;           // actions of the next call (device memory)
+    bool act_pending = false, act_used = false;
+    int plan_parity = 0;
+    const float* start_depth = nullptr;         // start maps of the next call (dvo_batch_set_mono_start_depth_device)
+    const float* start_sigma = nullptr;
+    bool host_init = false;                     // init_depth holds the host map of set_initial_depth (else, once planned, the default)
+    int alloc_plan();
+    int set_actions(const uint8_t* actions, bool on_device);
+    int set_start_depth(const float* depth_dev, const float* sigma_dev);
+    int status_of_last(int* out, bool out_on_device);
+    int odometrize_planned(const FrameInput& gin, int call_id);
+    int started_of(int seq, bool* out);         // (synchronises) whether sequence `seq` has a keyframe
 };
 
 void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vector<float>& s);

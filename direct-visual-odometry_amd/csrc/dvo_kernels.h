@@ -44,9 +44,9 @@ struct PyramidArgs {
     const uint8_t* seq_action;                 // [n_seq] effective action (k_plan)
     const float* ref[3][DVO_MAX_LEVELS];       // gray, depth, sigma of the reference set
     const float* ref_wgt[DVO_MAX_LEVELS];
-    // optional lens undistortion (remap != nullptr; whole frames): k_pyramid_remap (mono frames: gray only, no plan) or, with depth
-    // (raw_depth or src[1] set), k_pyramid_remap_depth gathers each kept pixel through its sequence's camera table (k_undistort_map)
-    // -- launch_pyramid then never picks k_pyramid / k_pyramid_raw4
+    // optional lens undistortion (remap != nullptr; whole frames): k_pyramid_remap (mono frames: gray only; with a plan
+    // k_pyramid_remap_plan) or, with depth (raw_depth or src[1] set), k_pyramid_remap_depth gathers each kept pixel through its
+    // sequence's camera table (k_undistort_map) -- launch_pyramid then never picks k_pyramid / k_pyramid_raw4
     const int* remap = nullptr;       // [n_cam][th][tw] source index into the full frame, -1 = border (INVALID)
     const int* remap_cam = nullptr;   // [n_seq] camera (table) of each sequence
 };
@@ -402,6 +402,42 @@ struct RegDecArgs {
     float inv_w = 0.0f;                       // 1 / top-level width (set by the launch wrapper)
 };
 void launch_regularize_redecimate(const RegDecArgs& a, hipStream_t s);
+
+// ---- the per-sequence plan of a mono batch (dvo_batch_set_mono_actions) ----------------------------------------------------------
+// k_plan resolves the actions (has_ref = "has a keyframe"); these kernels replace k_mono_decide, k_mono_commit and
+// k_regularize_redecimate in a planned call.  Plan state lives in separate per-sequence arrays, never in MonoSeq.
+struct MonoPlanArgs {   // k_mono_decide_plan, k_mono_commit_plan
+    MonoSeq* meta;
+    const SeqState* state;
+    const uint8_t* eff;      // [n_seq] effective action (k_plan)
+    uint8_t* started;        // [n_seq] the sequence has started (read by decide, set by commit)
+    int* need_save;          // [n_seq] MonoSeq::need of a sequence that does not track, restored by commit
+    float* hist_xi;          // [n_seq][R][6]
+    float* xi_world; float* T_world; int* is_key;
+    int* need_list;          // as k_mono_decide's
+    int n_seq, R, max_frames;
+    float min_translation;
+};
+void launch_mono_decide_plan(const MonoPlanArgs& a, hipStream_t s);
+void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s);
+// k_regularize_redecimate_plan: k_regularize_redecimate for the TRACK sequences; a SKIP sequence copies its top-level depth forward to
+// depth_top_out (nothing else is written); a RESTART sequence starts: its keyframe becomes the frame's gray pyramid (ring slot 0 too),
+// the start map's depth and sigma with every level re-decimated and the weights, age 0 (the first frame of system.hpp:49-54).
+struct MonoStartArgs {
+    const uint8_t* eff;            // [n_seq] effective action (k_plan)
+    const uint8_t* started;        // [n_seq] the sequence started before this call (its first start keeps its own top-level maps)
+    const float* start_depth;      // optional [n_seq][h][w] (dvo_batch_set_mono_start_depth_device), with start_sigma
+    const float* start_sigma;
+    const float* init_depth;       // [h][w] the start map of a later start: the host map of dvo_batch_set_initial_depth, else the default
+    const float* init_sigma;
+    float* sigma_top;              // the keyframes' top-level sigma (= RegDecArgs::sigma, written for the starts only)
+    float* age;                    // the keyframes' age map [n_seq][h][w]
+    const float* frm_gray[DVO_MAX_LEVELS];
+    float* ref_gray[DVO_MAX_LEVELS];
+    float* ring_gray;              // [n_seq][R][h][w]
+    int R;
+};
+void launch_regularize_redecimate_plan(const RegDecArgs& a, const MonoStartArgs& p, hipStream_t s);
 
 void launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
 

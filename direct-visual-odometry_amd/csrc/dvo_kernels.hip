@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     }
 }
 
-// k_pyramid_remap: k_pyramid of MONO frames (gray only, no plan) with the lens undistortion fused in (dvo_batch_set_distortion,
+// k_pyramid_remap: k_pyramid of MONO frames (gray only) with the lens undistortion fused in (dvo_batch_set_distortion,
 // dvo_vo_set_distortion).  Under nearest-neighbour remapping, kept pixel (x << culls, y << culls) of the undistorted frame is ONE
 // pixel of the distorted input: the thread reads its index from the sequence's camera table (k_undistort_map; -1 = outside the
 // image = k_undistort's INVALID border), gathers that one u8 (k_pyramid's raw conversion) or float, and writes every level as
@@ -232,6 +232,47 @@ __global__ void __launch_bounds__(256) k_pyramid_remap(PyramidArgs a)
     const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
     const int i = (int)blockIdx.x * 256 + threadIdx.x;
     if (i >= tw * th || seq >= a.n_seq) return;
+    int x, y;
+    split_index(i, tw, a.inv_tw, x, y);
+    const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
+    const int si = a.remap[(size_t)cam * tw * th + (size_t)y * tw + x];
+    float raw = kInvalid;
+    if (si >= 0) {
+        const size_t src_off = (size_t)seq * a.src_w * a.src_h + (size_t)si;
+        if (a.raw_rgb != nullptr) {
+            unsigned g8;
+            if (a.raw_channels == 1) {
+                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
+            } else {
+                const uint8_t* p = a.raw_rgb + src_off * (size_t)a.raw_channels;
+                g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
+            }
+            raw = (float)g8 * a.raw_gray_scale;
+        } else {
+            raw = __builtin_nontemporal_load(a.src[0] + src_off);
+        }
+    }
+    for (int t = 0; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if ((x & msk) | (y & msk)) break;
+        const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
+        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+        const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+        __builtin_nontemporal_store((t == 0 && a.culls == 0) ? raw : pass_valid(raw), a.dst[0][l] + o);
+    }
+}
+
+// k_pyramid_remap_plan: k_pyramid_remap in a planned mono call (dvo_batch_set_mono_actions), with one line more: the workgroups of
+// a sequence whose effective action is DVO_SEQ_SKIP return at once.  Its slot of the input is never read and its slice of the frame
+// set is left as it was: nothing downstream reads the frame of a sequence that does not track or start.  (A separate kernel rather
+// than a template parameter: k_pyramid_remap keeps its instruction stream, tests/golden/isa_pyramid_undistort.json.)
+__global__ void __launch_bounds__(256) k_pyramid_remap_plan(PyramidArgs a)
+{
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tw * th || seq >= a.n_seq) return;
+    if (a.seq_action[seq] == DVO_SEQ_SKIP) return;   // (uniform per workgroup)
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
     const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
@@ -2114,7 +2155,8 @@ void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
         return;
     }
     if (a.remap != nullptr) {   // lens undistortion fused in (mono frames): never k_pyramid_raw4 / k_pyramid
-        hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+        if (a.seq_action != nullptr) hipLaunchKernelGGL(k_pyramid_remap_plan, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
         return;
     }
     // raw 1-channel frames with the usual alignment: four kept pixels per thread, wide loads and stores

@@ -93,6 +93,63 @@ __global__ void __launch_bounds__(64) k_mono_commit(MonoSeq* meta, float* hist_x
     m.n_total += 1;
 }
 
+// k_mono_decide_plan / k_mono_commit_plan: k_mono_decide and k_mono_commit of a planned mono call (dvo_batch_set_mono_actions).
+// A TRACK sequence does exactly what they do, with its own next frame id (frame ids count from each start).  A sequence that does
+// not track parks its need flag in need_save and raises it, so that k_age_table and k_depth_update leave it alone (and it is never in
+// need_list: k_propagate_* and k_promote do not see it); k_mono_commit_plan puts the flag back.  SKIP keeps its world pose (identity
+// while it has never started) with is_keyframe = 0; RESTART becomes frame 0 of its sequence, as k_mono_commit's first-frame branch.
+__global__ void __launch_bounds__(64) k_mono_decide_plan(MonoPlanArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    MonoSeq& m = a.meta[s];
+    if (a.eff[s] == DVO_SEQ_TRACK) {
+        float rel[6], fx[6], T[16];
+        for (int i = 0; i < 6; i++) rel[i] = a.state[s].xi[i];
+        const int fid = m.frame_id + 1;
+        const int need = mono_decide_one(m, rel, fid, a.min_translation, a.max_frames, fx, T);
+        if (need) a.need_list[4 + atomicAdd(&a.need_list[0], 1)] = s;
+        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = fx[i];
+        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = T[i];
+        a.is_key[s] = need;
+        return;
+    }
+    a.need_save[s] = m.need;
+    m.need = 1;
+    a.is_key[s] = 0;
+    if (!a.started[s]) {
+        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
+        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    }
+}
+
+__global__ void __launch_bounds__(64) k_mono_commit_plan(MonoPlanArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    MonoSeq& m = a.meta[s];
+    const int eff = a.eff[s];
+    if (eff == DVO_SEQ_RESTART) {   // k_mono_commit's first-frame branch, frame id 0 of the sequence, its counters reset
+        for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
+        for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+        for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
+        for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        m.ref_id = 0; m.frame_id = 0; m.n_total = 1; m.need = 1; m.valid_updates = 0; m.clamped = 0;
+        for (int i = 0; i < 6; i++) a.hist_xi[((size_t)s * a.R) * 6 + i] = 0.0f;
+        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
+        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = m.T_world[i];
+        a.is_key[s] = 1;
+        a.started[s] = 1;
+        return;
+    }
+    if (eff != DVO_SEQ_TRACK) { m.need = a.need_save[s]; return; }
+    if (!m.need) return;   // k_mono_commit's keyframe branch
+    const int slot = m.n_total % a.R;
+    for (int i = 0; i < 6; i++) { m.ref_xi[i] = m.frame_xi[i]; a.hist_xi[((size_t)s * a.R + slot) * 6 + i] = m.frame_xi[i]; }
+    m.ref_id = m.frame_id;
+    m.n_total += 1;
+}
+
 // k_age_table: the per-keyframe part of Mapper::update (mapper.cpp:99-107) hoisted out of the pixel loop: for every retained
 // keyframe, r_xi = concatenate(obj.xi, -born.xi), the pose exp(-r_xi) that the epipolar search warps with and -r_xi's
 // translation (implement.cpp:56).  One thread per (sequence, history index).
@@ -279,11 +336,10 @@ __global__ void __launch_bounds__(256) k_regularize(const float* __restrict__ de
 // pixel as k_regularize + k_pyramid(culls = 0, depth and sigma): the regularized value is written to a second top-level buffer (the
 // 5-point stencil of the neighbours still reads the old one) and decimated on the spot into every level it lands on, with sigma,
 // and the Gauss-Newton weight -- saves one launch and the 8 B/px round trip of the intermediate map.
-__global__ void __launch_bounds__(256) k_regularize_redecimate(RegDecArgs a)
+// (the arguments by value, as in propagate_owner: k_regularize_redecimate is the code it always was)
+__device__ __forceinline__ void regularize_redecimate_px(RegDecArgs a, int seq, int i)
 {
     const int T = a.levels - 1, w = a.w[T], h = a.h[T];
-    int seq, i;
-    if (!seq_pixel(w * h, a.n_seq, seq, i)) return;
     const size_t base = (size_t)seq * w * h;
     const float* __restrict__ depth = a.depth + base;
     const float* __restrict__ sigma = a.sigma + base;
@@ -302,6 +358,60 @@ __global__ void __launch_bounds__(256) k_regularize_redecimate(RegDecArgs a)
         const int l = T - t, lx = x >> t, ly = y >> t;
         if (lx >= a.w[l] || ly >= a.h[l]) continue;
         const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+        a.depth_lv[l][o] = vd;
+        a.sigma_lv[l][o] = vs;
+        a.wgt[l][o] = gn_weight(a.step[l], a.sigma_min, a.sigma_max, vs);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_regularize_redecimate(RegDecArgs a)
+{
+    const int T = a.levels - 1;
+    int seq, i;
+    if (!seq_pixel(a.w[T] * a.h[T], a.n_seq, seq, i)) return;
+    regularize_redecimate_px(a, seq, i);
+}
+
+// k_regularize_redecimate_plan: a planned mono call (dvo_batch_set_mono_actions).  The action is uniform per workgroup (seq_grid).
+//  TRACK    k_regularize_redecimate's pixel.
+//  SKIP     the top-level depth is copied forward into depth_top_out (the host swaps the two buffers after this launch); nothing
+//           else of the keyframe is touched: it is not regularised.
+//  RESTART  what the first frame does (system.hpp:49-54, MonoBatch::odometrize's frame-0 branch): the frame's gray pyramid becomes
+//           the keyframe's and enters ring slot 0, age 0, and the start map is re-decimated with the operations of redecimate()
+//           (k_pyramid with culls = 0: the top level as given, pass_valid below, the weight of the level's sigma).
+//           Start map: the per-call rows when set; else, on a sequence's first start, its own top-level maps (what
+//           dvo_batch_set_initial_depth / _device or the default left there, kept by the copy-forward); else init_depth / init_sigma.
+__global__ void __launch_bounds__(256) k_regularize_redecimate_plan(RegDecArgs a, MonoStartArgs p)
+{
+    const int T = a.levels - 1, w = a.w[T], h = a.h[T];
+    int seq, i;
+    if (!seq_pixel(w * h, a.n_seq, seq, i)) return;
+    // the action byte through a scalar load of its aligned word (the sequence is uniform per workgroup; eff is padded to 4 bytes)
+    const int eff = (int)((load_seq_entry(reinterpret_cast<const uint32_t*>(p.eff), seq >> 2) >> ((seq & 3) * 8)) & 0xffu);
+    if (eff == DVO_SEQ_TRACK) { regularize_redecimate_px(a, seq, i); return; }
+    const size_t base = (size_t)seq * w * h;
+    if (eff != DVO_SEQ_RESTART) { a.depth_top_out[base + i] = a.depth[base + i]; return; }
+    float d, s;
+    if (p.start_depth) { d = p.start_depth[base + i]; s = p.start_sigma[base + i]; }
+    else if (!p.started[seq]) { d = a.depth[base + i]; s = a.sigma[base + i]; }
+    else { d = p.init_depth[i]; s = p.init_sigma[i]; }
+    int x, y;
+    split_row(i, w, a.inv_w, x, y);
+    const float g = p.frm_gray[T][base + i];
+    p.ref_gray[T][base + i] = g;
+    p.ring_gray[(size_t)seq * p.R * w * h + i] = g;
+    a.depth_top_out[base + i] = d;
+    p.sigma_top[base + i] = s;
+    p.age[base + i] = 0.0f;
+    a.wgt[T][base + i] = gn_weight(a.step[T], a.sigma_min, a.sigma_max, s);
+    const float vd = pass_valid(d), vs = pass_valid(s);
+    for (int t = 1; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if ((x & msk) | (y & msk)) break;
+        const int l = T - t, lx = x >> t, ly = y >> t;
+        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+        const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+        p.ref_gray[l][o] = p.frm_gray[l][o];
         a.depth_lv[l][o] = vd;
         a.sigma_lv[l][o] = vs;
         a.wgt[l][o] = gn_weight(a.step[l], a.sigma_min, a.sigma_max, vs);
@@ -745,6 +855,24 @@ void launch_regularize_redecimate(const RegDecArgs& a0, hipStream_t s)
     const int T = a.levels - 1;
     a.inv_w = 1.0f / (float)a.w[T];
     hipLaunchKernelGGL(k_regularize_redecimate, seq_grid(cdiv_u(a.w[T] * a.h[T], 256), (unsigned)a.n_seq), dim3(256), 0, s, a);
+}
+
+void launch_mono_decide_plan(const MonoPlanArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mono_decide_plan, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mono_commit_plan, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_regularize_redecimate_plan(const RegDecArgs& a0, const MonoStartArgs& p, hipStream_t s)
+{
+    RegDecArgs a = a0;
+    const int T = a.levels - 1;
+    a.inv_w = 1.0f / (float)a.w[T];
+    hipLaunchKernelGGL(k_regularize_redecimate_plan, seq_grid(cdiv_u(a.w[T] * a.h[T], 256), (unsigned)a.n_seq), dim3(256), 0, s, a, p);
 }
 
 void launch_regularize(const float* depth, const float* sigma, int w, int h, float* out, hipStream_t s)

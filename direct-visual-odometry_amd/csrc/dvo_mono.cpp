@@ -26,6 +26,12 @@ MonoBatch::~MonoBatch()
     }
     for (auto& m : map_ev)
         for (hipEvent_t e : m.e) (void)hipEventDestroy(e);
+    if (stream && (h_act[0] || h_ready)) (void)hipStreamSynchronize(stream);
+    for (int i = 0; i < 2; i++) {
+        if (h_act[i]) (void)hipHostFree(h_act[i]);
+        if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
+    }
+    if (h_ready) (void)hipHostFree(h_ready);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -155,6 +161,7 @@ int MonoBatch::set_initial_depth(const float* depth_host, const float* sigma_hos
     launch_broadcast(init_depth.as<float>(), ref.depth[T], (int)np, n_seq, stream);
     launch_broadcast(init_sigma.as<float>(), ref.sigma[T], (int)np, n_seq, stream);
     have_init = true;
+    host_init = true;
     DVO_HIP(hipGetLastError());
     return DVO_OK;
 }
@@ -224,7 +231,33 @@ int MonoBatch::odometrize(const FrameInput& in)
     // was (a failed first frame leaves it not started), so frame ids -- and with them keyframe_max_frames -- never shift
     const int frame_id = latest_id + 1;
     MonoSeq* m = meta.as<MonoSeq>();
-    if (frame_id == 0) {  // system.hpp:49-54: the first frame is the first keyframe of every sequence
+    // per-sequence path: actions or start maps pending, or actions used by an earlier call (then every call is an
+    // all-TRACK plan).  frame_id is then the number of the call; each sequence counts its own frames in MonoSeq::frame_id.
+    const bool planned = act_pending || act_used || start_depth != nullptr;
+    if (planned) {
+        if (frame_id == 0 && !have_init) {   // the slots' maps of a first start, as the plain first frame sets them
+            std::vector<float> d, s;
+            default_initial_depth(np, cfg.rng_seed, d, s);
+            DVO_TRY(set_initial_depth(d.data(), s.data()));
+        }
+        DVO_TRY(alloc_plan());
+        PlanArgs pa{};
+        pa.actions = act_pending ? act_src : nullptr;
+        pa.has_ref = has_kf.as<uint8_t>(); pa.eff = eff.as<uint8_t>(); pa.status = status.as<int>();
+        pa.state = trk.state.as<SeqState>(); pa.log = trk.log.as<dvo_track_log>(); pa.levels = g.levels;
+        const size_t set = (size_t)trk.n_sub * (size_t)(n_seq + 4);
+        pa.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
+        pa.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
+        pa.list_stride = n_seq + 4; pa.n_sub = trk.n_sub; pa.n_seq = n_seq;
+        pa.cam_changed = nullptr;                // (K and D are fixed for the life of the handle)
+        if (trk.adaptive && frame_id > 0) {      // Tracker::track waits for this word (the one of this parity was last used two plans ago)
+            h_ready[plan_parity] = 0;
+            pa.ready = d_ready + plan_parity;
+            pa.tally = plan_tally.as<int>();
+        }
+        launch_plan(pa, stream);
+    }
+    if (frame_id == 0 && !planned) {  // system.hpp:49-54: the first frame is the first keyframe of every sequence
         if (!have_init) {
             std::vector<float> d, s;
             default_initial_depth(np, cfg.rng_seed, d, s);
@@ -252,12 +285,38 @@ int MonoBatch::odometrize(const FrameInput& in)
         }
         pe = &map_ev[map_ev_used];
     }
-    { TraceRange tr("mono pyramid"); build_pyramid(frm, gin, stream); }           // Frame(gray, K, 3, 2)
-    { TraceRange tr("mono track"); DVO_TRY(trk.track(frm, ref, stream)); }           // system.hpp:57
+    {   // Frame(gray, K, 3, 2); a plan: the SKIP sequences read no input (k_pyramid<true> / k_pyramid_raw4<, true> copy their keyframe's
+        // gray forward, k_pyramid_remap_plan writes nothing)
+        TraceRange tr("mono pyramid");
+        if (planned) build_pyramid(frm, gin, stream, true, eff.as<uint8_t>(), &ref);
+        else build_pyramid(frm, gin, stream);
+    }
+    {   // system.hpp:57 (a plan: the TRACK sequences only; before the first call no sequence has a keyframe to track against)
+        TraceRange tr("mono track");
+        if (!planned) {
+            DVO_TRY(trk.track(frm, ref, stream));
+        } else if (frame_id > 0) {
+            TrackPlan tp;
+            tp.action = eff.as<uint8_t>();
+            tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
+            tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
+            tp.seq_k = trk.cam_k;
+            DVO_TRY(trk.track(frm, ref, stream, &tp));
+        }
+    }
     TraceRange tr_map("mono map (decide, propagate | update, promote, regularize)");
     DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
-    launch_mono_decide(m, trk.state.as<SeqState>(), n_seq, frame_id, cfg.keyframe_min_translation, cfg.keyframe_max_frames,
-                       xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), nullptr, stream, need_list.as<int>());
+    MonoPlanArgs ma{};
+    if (planned) {
+        ma.meta = m; ma.state = trk.state.as<SeqState>(); ma.eff = eff.as<uint8_t>(); ma.started = started.as<uint8_t>();
+        ma.need_save = need_save.as<int>(); ma.hist_xi = hist_xi.as<float>();
+        ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
+        ma.n_seq = n_seq; ma.R = R; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
+        launch_mono_decide_plan(ma, stream);
+    } else {
+        launch_mono_decide(m, trk.state.as<SeqState>(), n_seq, frame_id, cfg.keyframe_min_translation, cfg.keyframe_max_frames,
+                           xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), nullptr, stream, need_list.as<int>());
+    }
     // ---- Mapper::estimate (mapper.cpp:16-33), both branches launched, each sequence takes its own ----
     {   // need: propagate the reference maps into the frame (mapper.cpp:62-74) ...
         PropArgs a;
@@ -304,7 +363,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         pa.meta = m; pa.all = 0;
         pa.need_list = need_list.as<int>();
         launch_promote(pa, stream);
-        launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 0, frame_id, nullptr, nullptr, nullptr, stream);
+        if (!planned) launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 0, frame_id, nullptr, nullptr, nullptr, stream);
     }
     // Mapper::regularize (mapper.cpp:139-144) of the newest keyframe, then Frame::updateDepthSigma / updateDepth (frame.cpp:39-61):
     // every level of depth and sigma is a decimation of the top maps, so ONE pass re-derives both pyramids (and the
@@ -322,12 +381,124 @@ int MonoBatch::odometrize(const FrameInput& in)
         }
         ra.levels = g.levels; ra.n_seq = n_seq; ra.sigma_min = ref.sigma_min; ra.sigma_max = ref.sigma_max;
         if (pe) DVO_HIP(hipEventRecord(pe->e[4], stream));
-        launch_regularize_redecimate(ra, stream);
+        if (planned) {   // the TRACK sequences as above; SKIP copies its top-level depth forward; RESTART starts (k_regularize_redecimate_plan)
+            MonoStartArgs sa{};
+            sa.eff = eff.as<uint8_t>(); sa.started = started.as<uint8_t>();
+            sa.start_depth = start_depth; sa.start_sigma = start_sigma;
+            sa.init_depth = init_depth.as<float>(); sa.init_sigma = init_sigma.as<float>();
+            sa.sigma_top = ref.sigma[T]; sa.age = ref_age.as<float>();
+            for (int l = 0; l < g.levels; l++) { sa.frm_gray[l] = frm.gray[l]; sa.ref_gray[l] = ref.gray[l]; }
+            sa.ring_gray = ring_gray.as<float>(); sa.R = R;
+            launch_regularize_redecimate_plan(ra, sa, stream);
+        } else {
+            launch_regularize_redecimate(ra, stream);
+        }
         if (pe) { DVO_HIP(hipEventRecord(pe->e[5], stream)); map_ev_used++; }
         std::swap(ref.depth[T], depth_alt);   // the top-level depth map alternates between the arena block and `tmp`
     }
+    if (planned) {   // FrameHistory::push of the TRACK keyframes, frame 0 of the RESTART sequences, the SKIP need flags back
+        launch_mono_commit_plan(ma, stream);
+        act_pending = false; act_src = nullptr; act_used = true;
+        start_depth = start_sigma = nullptr;
+        plan_parity ^= 1;
+    }
     DVO_HIP(hipGetLastError());
     latest_id = frame_id;
+    return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ mono: per-sequence actions
+int MonoBatch::alloc_plan()
+{
+    if (has_kf.p) return DVO_OK;
+    const size_t n = (size_t)n_seq;
+    DVO_TRY(act_dev.alloc(n));
+    DVO_TRY(has_kf.alloc(n));
+    DVO_TRY(eff.alloc((n + 3) & ~(size_t)3));   // (read as 32-bit words by k_regularize_redecimate_plan)
+    DVO_TRY(started.alloc(n));
+    DVO_TRY(status.alloc(sizeof(int) * n));
+    DVO_TRY(need_save.alloc(sizeof(int) * n));
+    DVO_TRY(plan_lists.alloc(2 * sizeof(int) * (size_t)trk.n_sub * (n + 4)));
+    DVO_TRY(plan_tally.alloc(2 * sizeof(int)));
+    for (int i = 0; i < 2; i++) {
+        DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_act[i]), n, hipHostMallocDefault));
+        DVO_HIP(hipEventCreateWithFlags(&ev_act[i], hipEventDisableTiming));
+    }
+    DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_ready), 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+    h_ready[0] = h_ready[1] = 0;
+    DVO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_ready), h_ready, 0));
+    // in stream order: after plain calls every sequence has a keyframe; the list counts start at zero
+    DVO_HIP(hipMemsetAsync(has_kf.p, latest_id >= 0 ? 1 : 0, n, stream));
+    DVO_HIP(hipMemsetAsync(started.p, latest_id >= 0 ? 1 : 0, n, stream));
+    DVO_HIP(hipMemsetAsync(plan_lists.p, 0, plan_lists.bytes, stream));
+    DVO_HIP(hipMemsetAsync(plan_tally.p, 0, plan_tally.bytes, stream));
+    if (!host_init) {   // the start map of a later start without a host map: the default (what dvo_vo uses)
+        std::vector<float> d, s;
+        const size_t np = (size_t)top_pixels();
+        default_initial_depth((int)np, cfg.rng_seed, d, s);
+        DVO_HIP(hipMemcpy(init_depth.p, d.data(), np * sizeof(float), hipMemcpyHostToDevice));
+        DVO_HIP(hipMemcpy(init_sigma.p, s.data(), np * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return DVO_OK;
+}
+
+int MonoBatch::set_actions(const uint8_t* actions, bool on_device)
+{  // as Batch::set_actions
+    if (!actions) { act_pending = false; act_src = nullptr; return DVO_OK; }
+    DVO_TRY(select_device(device));
+    DVO_TRY(alloc_plan());
+    if (on_device) {
+        act_src = actions;   // read by k_plan in stream order
+    } else {
+        // copied now into pinned staging, then to the device in stream order (after the k_plan of every earlier call)
+        const int k = act_slot;
+        act_slot ^= 1;
+        if (act_staged[k]) DVO_HIP(hipEventSynchronize(ev_act[k]));   // (that copy was queued two calls ago)
+        memcpy(h_act[k], actions, (size_t)n_seq);
+        DVO_HIP(hipMemcpyAsync(act_dev.p, h_act[k], (size_t)n_seq, hipMemcpyHostToDevice, stream));
+        DVO_HIP(hipEventRecord(ev_act[k], stream));
+        act_staged[k] = true;
+        act_src = act_dev.as<uint8_t>();
+    }
+    act_pending = true;
+    return DVO_OK;
+}
+
+int MonoBatch::set_start_depth(const float* depth_dev, const float* sigma_dev)
+{
+    if (!depth_dev != !sigma_dev) { set_error("dvo_batch_set_mono_start_depth_device: depth and sigma are both set or both NULL"); return DVO_ERR_BAD_ARGUMENT; }
+    if (depth_dev) {
+        DVO_TRY(select_device(device));
+        DVO_TRY(alloc_plan());
+    }
+    start_depth = depth_dev; start_sigma = sigma_dev;
+    return DVO_OK;
+}
+
+int MonoBatch::status_of_last(int* out, bool out_on_device)
+{
+    if (latest_id < 0) { set_error("dvo_batch_mono_last_status: no frame has been consumed yet"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    if (!act_used) {   // plain calls: the first one starts every sequence, every later one tracks every sequence
+        const int v = latest_id == 0 ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
+        if (out_on_device) { DVO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), v, (size_t)n_seq, stream)); return DVO_OK; }
+        DVO_HIP(hipStreamSynchronize(stream));   // (as a read-back of the device buffer would)
+        for (int q = 0; q < n_seq; q++) out[q] = v;
+        return DVO_OK;
+    }
+    DVO_HIP(hipMemcpyAsync(out, status.p, sizeof(int) * (size_t)n_seq, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
+    if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
+    return DVO_OK;
+}
+
+int MonoBatch::started_of(int seq, bool* out)
+{
+    if (latest_id < 0) { *out = false; return DVO_OK; }
+    if (!act_used) { *out = true; return DVO_OK; }
+    uint8_t v = 0;
+    DVO_HIP(hipMemcpyAsync(&v, started.as<uint8_t>() + seq, 1, hipMemcpyDeviceToHost, stream));
+    DVO_HIP(hipStreamSynchronize(stream));
+    *out = v != 0;
     return DVO_OK;
 }
 
@@ -463,6 +634,9 @@ int dvo_batch_keyframe_get(dvo_batch* b, int seq, int level, float* gray, float*
     if (seq < 0 || seq >= M.n_seq || level < 0 || level >= M.g.levels) return DVO_ERR_BAD_ARGUMENT;
     if (M.latest_id < 0) return DVO_ERR_NOT_READY;
     DVO_TRY(select_device(M.device));
+    bool st = false;
+    DVO_TRY(M.started_of(seq, &st));
+    if (!st) { set_error("dvo_batch_keyframe_get: the sequence has not started (it was skipped on every call so far)"); return DVO_ERR_NOT_READY; }
     hipStream_t s = M.stream;
     const size_t n = (size_t)M.g.w[level] * M.g.h[level], off = n * (size_t)seq;
     if (gray) DVO_HIP(hipMemcpyAsync(gray, M.ref.gray[level] + off, n * 4, hipMemcpyDeviceToHost, s));
@@ -489,15 +663,44 @@ int dvo_batch_mono_stats(dvo_batch* b, int seq, dvo_mono_stats* out)
     if (!out || seq < 0 || seq >= M.n_seq) return DVO_ERR_BAD_ARGUMENT;
     if (M.latest_id < 0) return DVO_ERR_NOT_READY;
     DVO_TRY(select_device(M.device));
+    bool st = false;
+    DVO_TRY(M.started_of(seq, &st));
+    if (!st) { set_error("dvo_batch_mono_stats: the sequence has not started (it was skipped on every call so far)"); return DVO_ERR_NOT_READY; }
     MonoSeq m;
     DVO_HIP(hipMemcpyAsync(&m, M.meta.as<MonoSeq>() + seq, sizeof m, hipMemcpyDeviceToHost, M.stream));
     DVO_HIP(hipStreamSynchronize(M.stream));
-    out->frames = M.latest_id + 1;
+    out->frames = M.act_used ? m.frame_id + 1 : M.latest_id + 1;   // (with actions: the frames since the sequence's last start)
     out->keyframes_created = m.n_total;
     out->ring_keyframes = M.R;
     out->valid_updates_last_frame = m.valid_updates;
     out->clamped_pixels = m.clamped;
     return DVO_OK;
+}
+
+int dvo_batch_set_mono_actions(dvo_batch* b, const uint8_t* actions, int actions_on_device)
+{
+    DVO_NEED_MONO(b);
+    return b->mono->set_actions(actions, actions_on_device != 0);
+}
+
+int dvo_batch_mono_last_status(dvo_batch* b, int* status)
+{
+    DVO_NEED_MONO(b);
+    if (!status) return DVO_ERR_BAD_ARGUMENT;
+    return b->mono->status_of_last(status, false);
+}
+
+int dvo_batch_copy_mono_status_device(dvo_batch* b, int* status_dev)
+{
+    DVO_NEED_MONO(b);
+    if (!status_dev) return DVO_ERR_BAD_ARGUMENT;
+    return b->mono->status_of_last(status_dev, true);
+}
+
+int dvo_batch_set_mono_start_depth_device(dvo_batch* b, const float* depth_dev, const float* sigma_dev)
+{
+    DVO_NEED_MONO(b);
+    return b->mono->set_start_depth(depth_dev, sigma_dev);
 }
 
 int dvo_batch_profile_mapping(dvo_batch* b, dvo_map_profile* out, int reset)

@@ -101,6 +101,8 @@ EXPORTS = [
     "dvo_batch_set_intrinsics", "dvo_batch_get_intrinsics", "dvo_batch_create_mono_cameras",
     "dvo_batch_set_distortion", "dvo_batch_get_distortion", "dvo_vo_set_distortion",
     "dvo_batch_set_sensor_distortion", "dvo_batch_get_sensor_distortion",
+    "dvo_batch_set_mono_actions", "dvo_batch_mono_last_status", "dvo_batch_copy_mono_status_device",
+    "dvo_batch_set_mono_start_depth_device",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -735,6 +737,35 @@ class MonoBatch:
         else:
             a = f32(a)
             _check(lib().dvo_batch_odometrize_host(self._p, fp(a)))
+
+    def set_actions(self, actions, on_device=False):
+        """Per-sequence action of the NEXT call (SEQ_SKIP / SEQ_TRACK / SEQ_RESTART): a numpy uint8 [n_seq] (copied now), an int device
+        pointer to uint8 [n_seq] with on_device=True (read in stream order when the call runs), or None to clear
+        (dvo_batch_set_mono_actions)."""
+        if actions is None:
+            _check(lib().dvo_batch_set_mono_actions(self._p, None, 0))
+        elif on_device:
+            _check(lib().dvo_batch_set_mono_actions(self._p, C.c_void_p(int(actions)), 1))
+        else:
+            a = np.ascontiguousarray(actions, np.uint8)
+            assert a.shape == (self.n_seq,)
+            _check(lib().dvo_batch_set_mono_actions(self._p, a.ctypes.data_as(C.c_void_p), 0))
+
+    def last_status(self):
+        """int32 [n_seq]: SEQ_TRACKED / SEQ_SKIPPED / SEQ_STARTED / SEQ_BAD_ACTION of the last call (synchronises)."""
+        st = np.zeros(self.n_seq, np.int32)
+        _check(lib().dvo_batch_mono_last_status(self._p, st.ctypes.data_as(C.c_void_p)))
+        return st
+
+    def copy_status_device(self, ptr):
+        """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""
+        _check(lib().dvo_batch_copy_mono_status_device(self._p, C.c_void_p(int(ptr))))
+
+    def set_start_depth_device(self, depth_ptr, sigma_ptr):
+        """Start maps [n_seq, H/4, W/4] float32 (int device pointers) of the sequences that start in the NEXT call; 0, 0 (or None) clears
+        (dvo_batch_set_mono_start_depth_device)."""
+        _check(lib().dvo_batch_set_mono_start_depth_device(self._p, C.c_void_p(int(depth_ptr) if depth_ptr else None),
+                                                            C.c_void_p(int(sigma_ptr) if sigma_ptr else None)))
 
     def world_poses(self):
         xi = np.zeros((self.n_seq, 6), np.float32); T = np.zeros((self.n_seq, 16), np.float32); key = np.zeros(self.n_seq, np.int32)

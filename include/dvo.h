@@ -194,7 +194,8 @@ int dvo_batch_synchronize(dvo_batch* b);
  * Errors, returned before anything is enqueued: a mono batch or a NULL handle -> DVO_ERR_BAD_ARGUMENT; actions together with
  * prefetch are not supported: set_actions while a prefetched frame waits, or dvo_batch_prefetch_* while actions are pending ->
  * DVO_ERR_NOT_READY; a push with actions whose weight storage differs from the current references' (float maps after raw frames
- * or the reverse) -> DVO_ERR_BAD_ARGUMENT.  Mono batches (dvo_batch_create_mono) advance in lockstep and refuse actions. */
+ * or the reverse) -> DVO_ERR_BAD_ARGUMENT.  Mono batches (dvo_batch_create_mono) refuse these three calls: they take
+ * dvo_batch_set_mono_actions (below). */
 #define DVO_SEQ_SKIP    0   /* no frame for this sequence this step: input slot NOT read, reference kept */
 #define DVO_SEQ_TRACK   1   /* as today: track against the sequence's reference, then the frame becomes the reference */
 #define DVO_SEQ_RESTART 2   /* forget the reference: the frame is the sequence's first frame (system.hpp:83-86) */
@@ -285,8 +286,8 @@ int dvo_batch_probe_gn(dvo_batch* b, int level, int n_launches, float* avg_ms, u
 int dvo_batch_create_mono(int n_seq, const float K[9], int width, int height, int ring_keyframes, const dvo_config* cfg, dvo_batch** out);
 /* The same with one K per sequence: K[n_seq][9], host memory, row-major 3x3 (fx = K[0], cx = K[2], fy = K[4], cy = K[5]), copied
  * before the call returns.  Same arguments and results as dvo_batch_create_mono otherwise, and every other mono entry point works
- * unchanged on the handle.  A sequence's K is fixed at creation: its keyframe ring and depth maps belong to that camera (there is no
- * mono restart; dvo_batch_set_intrinsics, dvo_batch_get_intrinsics and dvo_batch_set_actions refuse a mono batch).  Each sequence
+ * unchanged on the handle.  A sequence's K is fixed at creation: its keyframe ring and depth maps belong to that camera (a restart,
+ * dvo_batch_set_mono_actions, keeps it; dvo_batch_set_intrinsics, dvo_batch_get_intrinsics and dvo_batch_set_actions refuse a mono batch).  Each sequence
  * gives the bits a dvo_vo handle created with that sequence's K and the same config gives (past `ring_keyframes` keyframes, one with
  * dvo_vo_set_history_limit(ring_keyframes)).  Frame size, pyramid shape and config stay per handle.
  * Errors, returned before anything touches the GPU: K == NULL, or a sequence's K with a non-finite entry or fx / fy <= 0 ->
@@ -344,6 +345,39 @@ typedef struct dvo_mono_stats {
     int clamped_pixels;
 } dvo_mono_stats;
 int dvo_batch_mono_stats(dvo_batch* b, int seq, dvo_mono_stats* out);
+/* ---- per-sequence skip / restart of a mono batch ------------------------------------------------------------------------------
+ * dvo_batch_set_mono_actions: actions[n_seq] (DVO_SEQ_SKIP / TRACK / RESTART) for the NEXT mono call (any dvo_batch_odometrize_*
+ * entry point); spent afterwards.  Host memory (actions_on_device = 0) is copied before the call returns; device memory
+ * (actions_on_device = 1) is read in stream order when that call runs.  NULL clears them.  Each sequence holds one piece of device
+ * state, "has a keyframe", empty at creation.
+ *   SKIP     the input slot is never read (it may hold NaN or garbage) and nothing of the sequence changes: keyframe ring, maps,
+ *            frame counter, stats.  Its world pose keeps the value of its last consumed frame (zero twist / identity if it never
+ *            started), is_keyframe = 0, track log n_iter = 0 on every level.  Status DVO_SEQ_SKIPPED.
+ *   TRACK    odometrize as a plain call.  On a sequence without a keyframe it acts as RESTART.  Status DVO_SEQ_TRACKED.
+ *   RESTART  the frame becomes the sequence's frame 0 (system.hpp:49-54): first keyframe, identity pose, is_keyframe = 1, the ring
+ *            emptied, frame ids counted from 0 again, age 0, depth and sigma from the start map.  Status DVO_SEQ_STARTED.
+ *   other    handled as SKIP.  Status DVO_SEQ_BAD_ACTION.
+ * Cut a sequence's calls at every start: each segment gives, bit for bit, what a fresh dvo_vo handle with the sequence's K (and D),
+ * the same config, dvo_vo_set_history_limit(ring_keyframes) and the segment's start map gives on the frames the sequence consumed.
+ * Start map of a start, the first rule that applies: (1) row s of dvo_batch_set_mono_start_depth_device, if set for this call;
+ * (2) on a sequence's first start only, the map its slot was given before the first call (dvo_batch_set_initial_depth,
+ * dvo_batch_set_initial_depth_device, or the default); (3) the host map of dvo_batch_set_initial_depth, if one was given;
+ * (4) the default map (the one dvo_vo uses).
+ * Once a batch has used actions, every later call runs the per-sequence path and a call without actions is an all-TRACK call.  A
+ * batch that never sets actions runs exactly the launches it always ran; its status is all STARTED after the first call and all
+ * TRACKED after later ones.  dvo_batch_keyframe_get and dvo_batch_mono_stats (frames = frames since the sequence's last start)
+ * return DVO_ERR_NOT_READY for a sequence that never started; dvo_batch_world_poses works after the first call.  K and D stay those
+ * of the handle.  A call that fails consumes no frame and spends neither actions nor start maps.
+ * Errors, returned before anything is enqueued: a NULL handle or a sensor-depth batch -> DVO_ERR_BAD_ARGUMENT (dvo_batch_set_actions,
+ * dvo_batch_last_status and dvo_batch_copy_status_device keep refusing mono batches).
+ * dvo_batch_mono_last_status: [n_seq], host, synchronises; DVO_ERR_NOT_READY before the first call.
+ * dvo_batch_copy_mono_status_device: [n_seq], asynchronous device-to-device copy on the handle's stream.
+ * dvo_batch_set_mono_start_depth_device: start maps [n_seq][height/4][width/4] in device memory, read in stream order at the NEXT call
+ * and only for the sequences that start in it; spent afterwards.  NULL, NULL clears them; exactly one NULL -> DVO_ERR_BAD_ARGUMENT. */
+int dvo_batch_set_mono_actions(dvo_batch* b, const uint8_t* actions, int actions_on_device);
+int dvo_batch_mono_last_status(dvo_batch* b, int* status);
+int dvo_batch_copy_mono_status_device(dvo_batch* b, int* status_dev);
+int dvo_batch_set_mono_start_depth_device(dvo_batch* b, const float* depth_dev, const float* sigma_dev);
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */

@@ -222,6 +222,18 @@ public:
     }
     void odometrizeDevice(const float* gray) { check(dvo_batch_odometrize_device(b_, gray)); }
     void odometrizeRawDevice(const uint8_t* rgb, int channels) { check(dvo_batch_odometrize_raw_device(b_, rgb, channels)); }
+    // per-sequence action of the next call (DVO_SEQ_SKIP / TRACK / RESTART; nullptr clears), see dvo_batch_set_mono_actions
+    void setActions(const uint8_t* actions, bool onDevice = false) { check(dvo_batch_set_mono_actions(b_, actions, onDevice ? 1 : 0)); }
+    // per-sequence outcome of the last call (DVO_SEQ_TRACKED / SKIPPED / STARTED / BAD_ACTION)
+    std::vector<int> lastStatus()
+    {
+        std::vector<int> out(n_);
+        check(dvo_batch_mono_last_status(b_, out.data()));
+        return out;
+    }
+    void copyStatusDevice(int* statusDev) { check(dvo_batch_copy_mono_status_device(b_, statusDev)); }
+    // start maps [n_seq][height/4][width/4] (device) of the sequences that start in the next call; nullptr, nullptr clears
+    void setStartDepthDevice(const float* depthDev, const float* sigmaDev) { check(dvo_batch_set_mono_start_depth_device(b_, depthDev, sigmaDev)); }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {
         std::vector<Mat4> out(n_);
