@@ -368,6 +368,40 @@ int dvo_batch_set_actions(dvo_batch* b, const uint8_t* actions, int actions_on_d
     return b->impl.set_actions(actions, actions_on_device != 0);
 }
 
+int dvo_batch_set_pose_guess_mode(dvo_batch* b, int mode)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (mode != DVO_GUESS_NONE && mode != DVO_GUESS_GIVEN && mode != DVO_GUESS_CONSTANT_VELOCITY) {
+        set_error("dvo_batch_set_pose_guess_mode: the mode is DVO_GUESS_NONE, DVO_GUESS_GIVEN or DVO_GUESS_CONSTANT_VELOCITY");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    return b->mono ? b->mono->set_guess_mode(mode) : b->impl.set_guess_mode(mode);
+}
+
+int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    PoseGuess& G = b->mono ? b->mono->guess : b->impl.guess;
+    if (xi && G.mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
+    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
+    return G.set_rows(xi, xi_on_device != 0, b->mono ? b->mono->stream : b->impl.stream);
+}
+
+int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start)
+{
+    if (!b || !xi_start) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono ? b->mono->latest_id < 0 : b->impl.n_push == 0) { set_error("dvo_batch_last_start_poses: nothing has been pushed yet"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
+    const PoseGuess& G = b->mono ? b->mono->guess : b->impl.guess;
+    if (!G.on()) {   // no mode was ever set: every push started from zero
+        const int n = b->mono ? b->mono->n_seq : b->impl.n_seq;
+        DVO_HIP(hipStreamSynchronize(b->mono ? b->mono->stream : b->impl.stream));
+        memset(xi_start, 0, sizeof(float) * 6 * (size_t)n);
+        return DVO_OK;
+    }
+    return G.last_start(xi_start, b->mono ? b->mono->stream : b->impl.stream);
+}
+
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;

@@ -558,7 +558,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     persist_used = false;
     // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
     const Intr* seq_k = plan ? plan->seq_k : cam_k;
-    if (persist_ok && !persist_failed && h_result && !plan && !cam_k) {   // the whole call in one launch (k_track_persist)
+    if (persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed) {   // the whole call in one launch (k_track_persist)
         PersistArgs pa;
         memset(&pa, 0, sizeof pa);
         pa.levels = g.levels;
@@ -594,6 +594,10 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         }
     }
     if (!plan) launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
+    if (seed) {   // the start pose of every TRACK sequence (dvo_batch_set_pose_guess_mode), before the fork
+        if (seed_mono) launch_mono_seed(*seed, s);
+        else launch_seed_pose(*seed, s);
+    }
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
     // level does not pay for its remaining (empty) launches.  Big batches run the fixed schedule sync-free.
@@ -1364,6 +1368,7 @@ Batch::~Batch()
         if (h_cam[i]) (void)hipHostFree(h_cam[i]);
         if (ev_cam[i]) (void)hipEventDestroy(ev_cam[i]);
     }
+    guess.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1497,13 +1502,19 @@ int Batch::push(const FrameInput& in)
         target = (cur < 0 && npre == 0) ? 0 : free_slot();
         if (target < 0) { set_error("dvo_batch_push_device: the frames prefetched must be pushed first, in order"); return DVO_ERR_BAD_ARGUMENT; }
     }
+    PoseSeedArgs sa{};
     if (!planned) {
         if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
         if (cur >= 0) {
-            DVO_TRY(trk.track(fs[target], fs[cur], stream));    // system.hpp:88
+            if (guess.on()) { sa = guess.args(trk.state.as<SeqState>(), nullptr, DVO_SEQ_TRACK, trk.xi_out.as<float>(), nullptr); trk.seed = &sa; }
+            const int rc = trk.track(fs[target], fs[cur], stream);    // system.hpp:88
+            trk.seed = nullptr;
+            DVO_TRY(rc);
             DVO_HIP(hipEventRecord(ev_last_track, stream));
             tracked_once = true;
             have_poses = true;
+        } else {
+            seed_untracked(nullptr, DVO_SEQ_RESTART);
         }
     } else {
         // k_plan first (it reads only the actions and has_ref), then the pyramid: SKIP sequences copy their reference forward, so the
@@ -1517,10 +1528,14 @@ int Batch::push(const FrameInput& in)
             tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
             tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
             tp.seq_k = cam_table();
-            DVO_TRY(trk.track(fs[target], fs[cur], stream, &tp));
+            if (guess.on()) { sa = guess.args(trk.state.as<SeqState>(), eff.as<uint8_t>(), 0, trk.xi_out.as<float>(), nullptr); trk.seed = &sa; }
+            const int rc = trk.track(fs[target], fs[cur], stream, &tp);
+            trk.seed = nullptr;
+            DVO_TRY(rc);
             DVO_HIP(hipEventRecord(ev_last_track, stream));
             tracked_once = true;
         } else {   // no frame set to track against yet: every sequence starts (or stays without a reference); k_plan zeroed the twists
+            seed_untracked(eff.as<uint8_t>(), 0);
             launch_export_poses(trk.state.as<SeqState>(), trk.xi_out.as<float>(), trk.T_out.as<float>(), n_seq, stream);
         }
         have_poses = true;
@@ -1530,6 +1545,7 @@ int Batch::push(const FrameInput& in)
         plan_parity ^= 1;
     }
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
+    guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
     n_push++;
     prev = cur;
     cur = target;                                           // system.hpp:91
@@ -1699,6 +1715,85 @@ int Batch::set_sensor_distortion(const float* D, bool per_sequence)
     // through the camera-changed bytes, on the per-sequence path, as dvo_batch_set_intrinsics
     if (n_push > 0) return stage_cameras(cam_K.data());
     return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: start pose of the tracking
+int PoseGuess::set_mode(int m, int n, hipStream_t s, const uint8_t* prev_eff_dev, int prev_all)
+{
+    if (!dev.p) {   // first mode set: rows, starts and history; the history starts from the push before (prev_eff_dev / prev_all)
+        n_seq = n;
+        DVO_TRY(dev.alloc(sizeof(float) * 24 * (size_t)n + 2 * (size_t)n));
+        DVO_HIP(hipMemsetAsync(dev.p, 0, dev.bytes, s));
+        if (prev_eff_dev) DVO_HIP(hipMemcpyAsync(prev_eff(), prev_eff_dev, (size_t)n, hipMemcpyDeviceToDevice, s));
+        else DVO_HIP(hipMemsetAsync(prev_eff(), prev_all, (size_t)n, s));
+        for (int i = 0; i < 2; i++) {
+            DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_rows[i]), sizeof(float) * 6 * (size_t)n, hipHostMallocDefault));
+            DVO_HIP(hipEventCreateWithFlags(&ev_rows[i], hipEventDisableTiming));
+        }
+    }
+    mode = m;
+    if (m != DVO_GUESS_GIVEN) rows_src = nullptr;
+    return DVO_OK;
+}
+
+int PoseGuess::set_rows(const float* xi, bool on_device, hipStream_t s)
+{
+    if (!xi) { rows_src = nullptr; return DVO_OK; }
+    if (mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
+    if (on_device) { rows_src = xi; return DVO_OK; }   // read by the seed kernel in stream order
+    // copied now into pinned staging, then to the device in stream order (after the seed of every earlier push), as Batch::set_actions
+    const size_t bytes = sizeof(float) * 6 * (size_t)n_seq;
+    const int k = rows_slot;
+    rows_slot ^= 1;
+    if (rows_staged[k]) DVO_HIP(hipEventSynchronize(ev_rows[k]));
+    memcpy(h_rows[k], xi, bytes);
+    DVO_HIP(hipMemcpyAsync(rows(), h_rows[k], bytes, hipMemcpyHostToDevice, s));
+    DVO_HIP(hipEventRecord(ev_rows[k], s));
+    rows_staged[k] = true;
+    rows_src = rows();
+    return DVO_OK;
+}
+
+PoseSeedArgs PoseGuess::args(SeqState* state, const uint8_t* eff, int all_eff, const float* last_xi, const MonoSeq* meta) const
+{
+    PoseSeedArgs a{};
+    a.state = state; a.eff = eff; a.all_eff = all_eff; a.mode = mode;
+    a.rows = mode == DVO_GUESS_GIVEN ? rows_src : nullptr;
+    a.start = start(); a.prev_eff = prev_eff(); a.last_xi = last_xi; a.hist = hist(); a.hist_n = hist_n(); a.meta = meta;
+    a.n_seq = n_seq;
+    return a;
+}
+
+int PoseGuess::last_start(float* out, hipStream_t s) const
+{
+    DVO_HIP(hipMemcpyAsync(out, start(), sizeof(float) * 6 * (size_t)n_seq, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+void PoseGuess::release(hipStream_t s)
+{
+    if (h_rows[0] && s) (void)hipStreamSynchronize(s);
+    for (int i = 0; i < 2; i++) {
+        if (h_rows[i]) { (void)hipEventSynchronize(ev_rows[i]); (void)hipHostFree(h_rows[i]); h_rows[i] = nullptr; }
+        if (ev_rows[i]) { (void)hipEventDestroy(ev_rows[i]); ev_rows[i] = nullptr; }
+    }
+}
+
+int Batch::set_guess_mode(int m)
+{
+    DVO_TRY(select_device(device));
+    // the push before: its effective actions (per-sequence path), else all STARTED (first push) or all TRACKED (later ones)
+    const uint8_t* pe = act_used ? eff.as<uint8_t>() : nullptr;
+    const int all = n_push == 0 ? 0xff : (n_push == 1 ? DVO_SEQ_RESTART : DVO_SEQ_TRACK);
+    return guess.set_mode(m, n_seq, stream, pe, all);
+}
+
+void Batch::seed_untracked(const uint8_t* eff_dev, int all_eff)
+{
+    if (!guess.on()) return;
+    const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), eff_dev, all_eff, trk.xi_out.as<float>(), nullptr);
+    launch_seed_pose(sa, stream);
 }
 
 }  // namespace dvo

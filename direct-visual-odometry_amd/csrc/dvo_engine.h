@@ -157,6 +157,33 @@ struct TrackPlan {
     const Intr* seq_k = nullptr;       // per-sequence intrinsics [level][n_seq] (dvo_batch_set_intrinsics); nullptr: Geometry::k
 };
 
+// Per-sequence start pose of a batch (dvo_batch_set_pose_guess_mode).  Allocated by the first mode set; from then on the
+// seed kernel runs at every push, folding each push into the history even while the mode is NONE.  A batch that never sets a mode
+// runs exactly the launches it ran before.
+struct PoseGuess {
+    int mode = DVO_GUESS_NONE;
+    int n_seq = 0;
+    DevBuf dev;                                // rows [n][6], start [n][6], hist [n][12] (float), then prev_eff [n], hist_n [n] (u8)
+    float* h_rows[2] = {nullptr, nullptr};     // pinned staging of host rows, alternately (ev_rows: their copy has been read)
+    hipEvent_t ev_rows[2] = {nullptr, nullptr};
+    bool rows_staged[2] = {false, false};
+    int rows_slot = 0;
+    const float* rows_src = nullptr;           // rows of the next push (device memory); nullptr: none
+    bool on() const { return dev.p != nullptr; }
+    float* rows() const { return dev.as<float>(); }
+    float* start() const { return dev.as<float>() + (size_t)n_seq * 6; }
+    float* hist() const { return dev.as<float>() + (size_t)n_seq * 12; }
+    uint8_t* prev_eff() const { return reinterpret_cast<uint8_t*>(dev.as<float>() + (size_t)n_seq * 24); }
+    uint8_t* hist_n() const { return prev_eff() + n_seq; }
+    // mode: the history starts from the last push: prev_eff_dev (its effective actions, device) or every sequence prev_all (0xff: none)
+    int set_mode(int m, int n, hipStream_t s, const uint8_t* prev_eff_dev, int prev_all);
+    int set_rows(const float* xi, bool on_device, hipStream_t s);
+    PoseSeedArgs args(SeqState* state, const uint8_t* eff, int all_eff, const float* last_xi, const MonoSeq* meta) const;
+    int last_start(float* out, hipStream_t s) const;
+    void release(hipStream_t s);
+    ~PoseGuess() { release(nullptr); }
+};
+
 struct Tracker {  // Track::Tracker for n_seq sequences at once
     Geometry g;
     int n_seq = 0;
@@ -200,6 +227,10 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // per-sequence intrinsics [level][n_seq] of a per-camera mono batch (dvo_batch_create_mono_cameras), used when track() has no
     // plan (a plan brings its own, TrackPlan::seq_k); nullptr: Geometry::k.  Never set together with prefer_persist.
     const Intr* cam_k = nullptr;
+    // start pose of the next track() (a batch's dvo_batch_set_pose_guess_mode): k_seed_pose, or with seed_mono k_mono_seed, runs after
+    // k_track_begin (or the caller's k_plan) and before the sub-batch fork; nullptr: every sequence starts from zero.  Never with persist.
+    const PoseSeedArgs* seed = nullptr;
+    bool seed_mono = false;
     bool prefer_persist = false;   // set before init() by the owner whose results go through enable_host_result() (VisualOdometry's sensor-depth tracker)
     bool persist_ok = false, persist_failed = false, persist_used = false;
     int persist_grid = 0, persist_spin_limit = 1 << 18;
@@ -388,6 +419,10 @@ struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sen
         return und.enabled() && memcmp(&und.D[q * 5], &und_D_used[q * 5], 5 * sizeof(float)) != 0;
     }
     const Intr* cam_table() const { return cam_used ? cam_dev.as<Intr>() : nullptr; }
+    PoseGuess guess;                            // dvo_batch_set_pose_guess_mode / dvo_batch_set_pose_guess
+    int set_guess_mode(int mode);
+    // the seed of this push outside track() (a push that tracks nothing still folds into the history)
+    void seed_untracked(const uint8_t* eff_dev, int all_eff);
     const uint8_t* cam_changed() const { return reinterpret_cast<const uint8_t*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq); }
 };
 
@@ -473,6 +508,8 @@ struct MonoBatch {
     int status_of_last(int* out, bool out_on_device);
     int odometrize_planned(const FrameInput& gin, int call_id);
     int started_of(int seq, bool* out);         // (synchronises) whether sequence `seq` has a keyframe
+    PoseGuess guess;                            // dvo_batch_set_pose_guess_mode / dvo_batch_set_pose_guess (world twists)
+    int set_guess_mode(int mode);
 };
 
 void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vector<float>& s);

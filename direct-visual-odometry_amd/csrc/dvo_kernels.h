@@ -458,6 +458,46 @@ struct PlanArgs {
     const uint8_t* cam_changed;  // optional [n_seq]: 1 = the sequence's intrinsics change at this push, so it loses its reference first
 };
 void launch_plan(const PlanArgs& a, hipStream_t s);
+
+// k_seed_pose (sensor depth) / k_mono_seed (mono): the start pose of one push (dvo_batch_set_pose_guess_mode), one
+// thread per sequence, launched after k_track_begin / k_plan.  Each first folds the previous push into the sequence's history (from
+// that push's effective action and result), then loads the start of every TRACK sequence into its SeqState as k_set_pose does.  A zero
+// start writes nothing: the state stays exactly what k_track_begin / k_plan left.  History lives here, never in SeqState or MonoSeq.
+struct PoseSeedArgs {
+    SeqState* state = nullptr;       // [n_seq]
+    const uint8_t* eff = nullptr;    // [n_seq] effective action of this push (k_plan); nullptr: every sequence takes `all_eff`
+    int all_eff = DVO_SEQ_TRACK;
+    int mode = 0;                    // DVO_GUESS_*
+    const float* rows = nullptr;     // DVO_GUESS_GIVEN: [n_seq][6] the rows of this push; nullptr: none (zero start)
+    float* start = nullptr;          // [n_seq][6] out: the start of each TRACK sequence, zero for the others
+    uint8_t* prev_eff = nullptr;     // [n_seq] in: the previous push's effective action (0xff: none to fold in); out: this push's
+    const float* last_xi = nullptr;  // [n_seq][6] what the previous push returned: relative twists (Tracker::xi_out) / world twists
+    float* hist = nullptr;           // [n_seq][12] sensor depth: [0..5] the last tracked relative twist; mono: w1, then w2
+    uint8_t* hist_n = nullptr;       // mono: [n_seq] world twists held in hist (0, 1, 2)
+    const MonoSeq* meta = nullptr;   // mono: the keyframe twist ref_xi of each sequence
+    int n_seq = 0;
+};
+void launch_seed_pose(const PoseSeedArgs& a, hipStream_t s);
+void launch_mono_seed(const PoseSeedArgs& a, hipStream_t s);
+#ifdef __HIPCC__
+// the state k_set_pose loads for twist x (not `active` / `iter`: k_track_begin / k_plan set them), and x as the reported start; a zero
+// twist writes neither the state nor anything but +0 to `start`
+__device__ __forceinline__ void seed_state(SeqState& st, float x[6], float* start)
+{
+    bool finite = true, zero = true;
+    for (int i = 0; i < 6; i++) { finite = finite && isfinite(x[i]); zero = zero && x[i] == 0.0f; }
+    if (!finite || zero) {
+        for (int i = 0; i < 6; i++) start[i] = 0.0f;
+        return;
+    }
+    double xd[6], R[9], t[3];
+    for (int i = 0; i < 6; i++) { start[i] = x[i]; st.xi[i] = x[i]; xd[i] = x[i]; }
+    pose_from_xi(x, -1.0f, st.pose);
+    se3_exp_d(xd, R, t);
+    for (int i = 0; i < 9; i++) st.Tc[i] = R[i];
+    for (int i = 0; i < 3; i++) st.Tc[9 + i] = t[i];
+}
+#endif
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s);
 void launch_gradient(const float* img, int w, int h, int xdir, float* out, hipStream_t s);
 void launch_warp_image(const float* gray, const float* depth, int w, int h, const Intr& k, const Pose& pose, float* out, hipStream_t s);

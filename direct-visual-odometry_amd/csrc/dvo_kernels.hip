@@ -1857,6 +1857,26 @@ __global__ void k_set_pose(SeqState* state, const float* xi, int n_seq)
     state[s].iter = 0;
 }
 
+// k_seed_pose: the start pose of a sensor-depth push (dvo_batch_set_pose_guess_mode), after k_track_begin / k_plan.  History: the
+// relative twist of the sequence's last TRACKED push since its last start (a RESTART zeroes it, a SKIP keeps it).
+__global__ void __launch_bounds__(256) k_seed_pose(PoseSeedArgs a)
+{
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    float* vel = a.hist + (size_t)s * 12;
+    const int pe = a.prev_eff[s];
+    if (pe == DVO_SEQ_TRACK) for (int i = 0; i < 6; i++) vel[i] = a.last_xi[(size_t)s * 6 + i];
+    else if (pe == DVO_SEQ_RESTART) for (int i = 0; i < 6; i++) vel[i] = 0.0f;
+    const int eff = a.eff ? (int)a.eff[s] : a.all_eff;
+    a.prev_eff[s] = (uint8_t)eff;
+    float x[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (eff == DVO_SEQ_TRACK) {
+        if (a.mode == DVO_GUESS_GIVEN && a.rows) for (int i = 0; i < 6; i++) x[i] = a.rows[(size_t)s * 6 + i];
+        else if (a.mode == DVO_GUESS_CONSTANT_VELOCITY) for (int i = 0; i < 6; i++) x[i] = vel[i];
+    }
+    seed_state(a.state[s], x, a.start + (size_t)s * 6);
+}
+
 // k_export_poses: relative twist + exp(xi) 4x4 (system.hpp:92) per sequence
 // host_result (optional, fine-grained mapped HOST memory, one sequence): the same 22 floats, then a sequence word written with a
 // system-scope release store -- the caller's thread polls it instead of queueing a device-to-host copy and waiting for the stream
@@ -2399,6 +2419,11 @@ void launch_plan(const PlanArgs& a, hipStream_t s)
 void launch_set_pose(SeqState* state, const float* xi_dev, int n_seq, hipStream_t s)
 {
     hipLaunchKernelGGL(k_set_pose, dim3(cdiv(n_seq, 64)), dim3(64), 0, s, state, xi_dev, n_seq);
+}
+
+void launch_seed_pose(const PoseSeedArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_seed_pose, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
 }
 
 void launch_export_poses(const SeqState* state, float* xi_out, float* T_out, int n_seq, hipStream_t s, float* host_result, int host_tag)

@@ -150,6 +150,49 @@ __global__ void __launch_bounds__(64) k_mono_commit_plan(MonoPlanArgs a)
     m.n_total += 1;
 }
 
+// k_mono_seed: the start pose of a mono call (dvo_batch_set_pose_guess_mode), after k_track_begin / k_plan.  History: the world
+// twists w1 (newest), w2 returned for the sequence's last two calls that tracked or started it since its last start.  A guess g in
+// world coordinates becomes the tracker's relative start concatenate(-ref_xi, g) against the sequence's current keyframe.
+__global__ void __launch_bounds__(64) k_mono_seed(PoseSeedArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    float* w = a.hist + (size_t)s * 12;   // w1 = w[0..5], w2 = w[6..11]
+    int n = a.hist_n[s];
+    const int pe = a.prev_eff[s];
+    if (pe == DVO_SEQ_TRACK) {
+        for (int i = 0; i < 6; i++) { w[6 + i] = w[i]; w[i] = a.last_xi[(size_t)s * 6 + i]; }
+        n = n < 2 ? n + 1 : 2;
+    } else if (pe == DVO_SEQ_RESTART) {
+        for (int i = 0; i < 6; i++) w[i] = a.last_xi[(size_t)s * 6 + i];
+        n = 1;
+    }
+    a.hist_n[s] = (uint8_t)n;
+    const int eff = a.eff ? (int)a.eff[s] : a.all_eff;
+    a.prev_eff[s] = (uint8_t)eff;
+    float x[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (eff == DVO_SEQ_TRACK) {
+        float g[6];
+        bool have = false;
+        if (a.mode == DVO_GUESS_GIVEN && a.rows) {
+            have = true;
+            for (int i = 0; i < 6; i++) { g[i] = a.rows[(size_t)s * 6 + i]; have = have && isfinite(g[i]); }
+        } else if (a.mode == DVO_GUESS_CONSTANT_VELOCITY && n >= 2) {
+            float w1[6], nw2[6], d[6];
+            for (int i = 0; i < 6; i++) { w1[i] = w[i]; nw2[i] = -w[6 + i]; }
+            se3_concatenate_f(nw2, w1, d);
+            se3_concatenate_f(w1, d, g);
+            have = true;
+        }
+        if (have) {
+            float nref[6];
+            for (int i = 0; i < 6; i++) nref[i] = -a.meta[s].ref_xi[i];
+            se3_concatenate_f(nref, g, x);
+        }
+    }
+    seed_state(a.state[s], x, a.start + (size_t)s * 6);
+}
+
 // k_age_table: the per-keyframe part of Mapper::update (mapper.cpp:99-107) hoisted out of the pixel loop: for every retained
 // keyframe, r_xi = concatenate(obj.xi, -born.xi), the pose exp(-r_xi) that the epipolar search warps with and -r_xi's
 // translation (implement.cpp:56).  One thread per (sequence, history index).
@@ -865,6 +908,11 @@ void launch_mono_decide_plan(const MonoPlanArgs& a, hipStream_t s)
 void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_mono_commit_plan, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_mono_seed(const PoseSeedArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_mono_seed, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
 }
 
 void launch_regularize_redecimate_plan(const RegDecArgs& a0, const MonoStartArgs& p, hipStream_t s)

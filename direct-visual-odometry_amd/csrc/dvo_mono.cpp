@@ -32,6 +32,7 @@ MonoBatch::~MonoBatch()
         if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
     }
     if (h_ready) (void)hipHostFree(h_ready);
+    guess.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -256,12 +257,20 @@ int MonoBatch::odometrize(const FrameInput& in)
             pa.tally = plan_tally.as<int>();
         }
         launch_plan(pa, stream);
+        if (frame_id == 0 && guess.on()) {   // nothing tracks: the seed only folds the previous call into the history
+            const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), eff.as<uint8_t>(), 0, xi_world.as<float>(), m);
+            launch_mono_seed(sa, stream);
+        }
     }
     if (frame_id == 0 && !planned) {  // system.hpp:49-54: the first frame is the first keyframe of every sequence
         if (!have_init) {
             std::vector<float> d, s;
             default_initial_depth(np, cfg.rng_seed, d, s);
             DVO_TRY(set_initial_depth(d.data(), s.data()));
+        }
+        if (guess.on()) {   // every sequence starts (the seed folds that into the history)
+            const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), nullptr, DVO_SEQ_RESTART, xi_world.as<float>(), m);
+            launch_mono_seed(sa, stream);
         }
         build_pyramid(ref, gin, stream);
         DVO_HIP(hipMemsetAsync(ref_age.p, 0, ref_age.bytes, stream));
@@ -273,6 +282,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         launch_promote(pa, stream);
         launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 1, frame_id, xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), stream);
         DVO_HIP(hipGetLastError());
+        guess.rows_src = nullptr;
         latest_id = frame_id;
         return DVO_OK;
     }
@@ -293,16 +303,24 @@ int MonoBatch::odometrize(const FrameInput& in)
     }
     {   // system.hpp:57 (a plan: the TRACK sequences only; before the first call no sequence has a keyframe to track against)
         TraceRange tr("mono track");
+        PoseSeedArgs sa{};   // the start pose (dvo_batch_set_pose_guess_mode): k_mono_seed inside track()
+        if (guess.on()) sa = guess.args(trk.state.as<SeqState>(), planned ? eff.as<uint8_t>() : nullptr, DVO_SEQ_TRACK, xi_world.as<float>(), m);
+        int rc = DVO_OK;
+        trk.seed = guess.on() ? &sa : nullptr;
+        trk.seed_mono = true;
         if (!planned) {
-            DVO_TRY(trk.track(frm, ref, stream));
+            rc = trk.track(frm, ref, stream);
         } else if (frame_id > 0) {
             TrackPlan tp;
             tp.action = eff.as<uint8_t>();
             tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
             tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
             tp.seq_k = trk.cam_k;
-            DVO_TRY(trk.track(frm, ref, stream, &tp));
+            rc = trk.track(frm, ref, stream, &tp);
         }
+        trk.seed = nullptr;
+        DVO_TRY(rc);
+        guess.rows_src = nullptr;
     }
     TraceRange tr_map("mono map (decide, propagate | update, promote, regularize)");
     DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
@@ -489,6 +507,15 @@ int MonoBatch::status_of_last(int* out, bool out_on_device)
     DVO_HIP(hipMemcpyAsync(out, status.p, sizeof(int) * (size_t)n_seq, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
     if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
     return DVO_OK;
+}
+
+int MonoBatch::set_guess_mode(int mode)
+{
+    DVO_TRY(select_device(device));
+    // the call before: its effective actions (per-sequence path), else all STARTED (first call) or all TRACKED (later ones)
+    const uint8_t* pe = act_used ? eff.as<uint8_t>() : nullptr;
+    const int all = latest_id < 0 ? 0xff : (latest_id == 0 ? DVO_SEQ_RESTART : DVO_SEQ_TRACK);
+    return guess.set_mode(mode, n_seq, stream, pe, all);
 }
 
 int MonoBatch::started_of(int seq, bool* out)

@@ -103,11 +103,14 @@ EXPORTS = [
     "dvo_batch_set_sensor_distortion", "dvo_batch_get_sensor_distortion",
     "dvo_batch_set_mono_actions", "dvo_batch_mono_last_status", "dvo_batch_copy_mono_status_device",
     "dvo_batch_set_mono_start_depth_device",
+    "dvo_batch_set_pose_guess_mode", "dvo_batch_set_pose_guess", "dvo_batch_last_start_poses",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
 SEQ_SKIP, SEQ_TRACK, SEQ_RESTART = 0, 1, 2
 SEQ_TRACKED, SEQ_SKIPPED, SEQ_STARTED, SEQ_BAD_ACTION = 0, 1, 2, 3
+# start pose of a batch's tracking (Batch / MonoBatch .set_pose_guess_mode): include/dvo.h
+GUESS_NONE, GUESS_GIVEN, GUESS_CONSTANT_VELOCITY = 0, 1, 2
 
 _lib = None
 
@@ -532,8 +535,36 @@ class VisualOdometry:
         return log.to_dict()
 
 
+class _PoseGuess:
+    """Start pose of the tracking, shared by Batch and MonoBatch (dvo_batch_set_pose_guess_mode, include/dvo.h)."""
+
+    def set_pose_guess_mode(self, mode):
+        """GUESS_NONE (zero twist, the default), GUESS_GIVEN (set_pose_guess rows) or GUESS_CONSTANT_VELOCITY, from the next push on."""
+        _check(lib().dvo_batch_set_pose_guess_mode(self._p, int(mode)))
+
+    def set_pose_guess(self, xi, on_device=False):
+        """Rows of the NEXT push (GUESS_GIVEN): float32 [n_seq, 6] (copied now), an int device pointer to float32 [n_seq, 6] with
+        on_device=True (read in stream order when the push runs), or None to clear.  Sensor depth: the relative twist of the frame,
+        as last_poses returns it; mono: its world twist, as world_poses returns it."""
+        if xi is None:
+            _check(lib().dvo_batch_set_pose_guess(self._p, None, 0))
+        elif on_device:
+            _check(lib().dvo_batch_set_pose_guess(self._p, C.c_void_p(int(xi)), 1))
+        else:
+            x = f32(xi)
+            if x.shape != (self.n_seq, 6):
+                raise ValueError("set_pose_guess: expected float[%d, 6], got shape %s" % (self.n_seq, x.shape))
+            _check(lib().dvo_batch_set_pose_guess(self._p, fp(x), 0))
+
+    def last_start_poses(self):
+        """float32 [n_seq, 6]: the twist each TRACKED sequence started from at the last push, zeros for the others (synchronises)."""
+        xi = np.zeros((self.n_seq, 6), np.float32)
+        _check(lib().dvo_batch_last_start_poses(self._p, fp(xi)))
+        return xi
+
+
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch:
+class Batch(_PoseGuess):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -664,7 +695,7 @@ class Batch:
         return ms.value, px.value
 
 
-class MonoBatch:
+class MonoBatch(_PoseGuess):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

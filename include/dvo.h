@@ -378,6 +378,35 @@ int dvo_batch_set_mono_actions(dvo_batch* b, const uint8_t* actions, int actions
 int dvo_batch_mono_last_status(dvo_batch* b, int* status);
 int dvo_batch_copy_mono_status_device(dvo_batch* b, int* status_dev);
 int dvo_batch_set_mono_start_depth_device(dvo_batch* b, const float* depth_dev, const float* sigma_dev);
+/* ---- per-sequence start pose of the tracking (both batch kinds) ----------------------------------------------------------------
+ * Every frame's Gauss-Newton starts from the zero twist (tracker.cpp:28).  dvo_batch_set_pose_guess_mode picks, per handle, where
+ * level 0's first iteration of each TRACK sequence starts instead; it takes effect at the next push / call and stays set.  The stop
+ * rules, iteration caps, track log, the meaning of the returned poses, keyframe decisions and mapping are unchanged.
+ *   DVO_GUESS_NONE              zero (tracker.cpp:28): what a batch that never sets a mode does (the same bits).
+ *   DVO_GUESS_GIVEN             the rows of dvo_batch_set_pose_guess, in the convention of what the batch returns: the relative
+ *                               twist of the frame being pushed as dvo_batch_last_poses returns it (sensor depth), or the frame's
+ *                               world twist g as dvo_batch_world_poses returns it (mono: the tracker starts from
+ *                               se3_concatenate(-ref_xi, g), ref_xi = the sequence's current keyframe twist).  Rows are spent by
+ *                               the next push / call; one without rows starts from zero.
+ *   DVO_GUESS_CONSTANT_VELOCITY computed on the device.  Sensor depth: the relative twist of the sequence's most recent TRACKED push
+ *                               since its last start (zero after STARTED / RESTART or a camera or distortion change; SKIP keeps
+ *                               it).  Mono: with w1, w2 the world twists returned for the sequence's last two calls that tracked or
+ *                               started it since its last start, g = concatenate(w1, concatenate(-w2, w1)) and the start is
+ *                               concatenate(-ref_xi, g); zero while only w1 exists.  concatenate is dvo_op_se3_concatenate's
+ *                               float function.  The history is kept from the first push after the first mode was set.
+ * dvo_batch_set_pose_guess: xi[n_seq][6].  Host rows (xi_on_device = 0) are copied before the call returns; device rows are read in
+ * stream order on the handle's stream when the next push runs (as dvo_batch_set_actions).  Rows of sequences that do not TRACK are
+ * never read (they may hold NaN); a TRACK row with a non-finite entry starts from zero.  NULL clears pending rows.
+ * dvo_batch_last_start_poses: [n_seq][6] the twist each TRACKED sequence started from at the last push (zeros for the others and in
+ * DVO_GUESS_NONE); host, synchronises; DVO_ERR_NOT_READY before the first push.
+ * Errors, returned before anything is enqueued: a NULL handle, a mode outside {0, 1, 2}, or rows while the mode is not
+ * DVO_GUESS_GIVEN -> DVO_ERR_BAD_ARGUMENT.  dvo_vo handles have no guess. */
+#define DVO_GUESS_NONE              0
+#define DVO_GUESS_GIVEN             1
+#define DVO_GUESS_CONSTANT_VELOCITY 2
+int dvo_batch_set_pose_guess_mode(dvo_batch* b, int mode);
+int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device);
+int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start);
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */

@@ -166,6 +166,16 @@ public:
         return out;
     }
     void copyStatusDevice(int* statusDev) { check(dvo_batch_copy_status_device(b_, statusDev)); }
+    // start pose of the tracking (DVO_GUESS_NONE / GIVEN / CONSTANT_VELOCITY), see dvo_batch_set_pose_guess_mode
+    void setPoseGuessMode(int mode) { check(dvo_batch_set_pose_guess_mode(b_, mode)); }
+    // relative twists [n_seq][6] of the next push (DVO_GUESS_GIVEN; nullptr clears)
+    void setPoseGuess(const float* xi, bool onDevice = false) { check(dvo_batch_set_pose_guess(b_, xi, onDevice ? 1 : 0)); }
+    std::vector<std::array<float, 6>> lastStartPoses()
+    {
+        std::vector<std::array<float, 6>> out(n_);
+        check(dvo_batch_last_start_poses(b_, out[0].data()));
+        return out;
+    }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
@@ -234,6 +244,16 @@ public:
     void copyStatusDevice(int* statusDev) { check(dvo_batch_copy_mono_status_device(b_, statusDev)); }
     // start maps [n_seq][height/4][width/4] (device) of the sequences that start in the next call; nullptr, nullptr clears
     void setStartDepthDevice(const float* depthDev, const float* sigmaDev) { check(dvo_batch_set_mono_start_depth_device(b_, depthDev, sigmaDev)); }
+    // start pose of the tracking (DVO_GUESS_NONE / GIVEN / CONSTANT_VELOCITY), see dvo_batch_set_pose_guess_mode
+    void setPoseGuessMode(int mode) { check(dvo_batch_set_pose_guess_mode(b_, mode)); }
+    // world twists [n_seq][6] of the next call (DVO_GUESS_GIVEN; nullptr clears)
+    void setPoseGuess(const float* xi, bool onDevice = false) { check(dvo_batch_set_pose_guess(b_, xi, onDevice ? 1 : 0)); }
+    std::vector<std::array<float, 6>> lastStartPoses()
+    {
+        std::vector<std::array<float, 6>> out(n_);
+        check(dvo_batch_last_start_poses(b_, out[0].data()));
+        return out;
+    }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {
         std::vector<Mat4> out(n_);
