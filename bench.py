@@ -8,10 +8,12 @@ value = sequences x steps x ranks / wall time.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
     python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR   (+ the last timed step's outputs as DIR/*.npy)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full               (+ everything listed below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-The default N = 1 run also carries, outside the timed region and in the same JSON line:
+A plain run renders the frames, warms up, times the steps and prints the result line: nothing else.  With --full, an N = 1 run
+also carries, outside the timed region and in the same JSON line:
   roofline      k_track_gn, hipEvents around every launch of an identical pass
   cpu_baseline  the CPU oracle on this box's host cores, bounded sample of the same workload
   accuracy      vs the synthetic ground truth, vs the CPU oracle on the same pairs, the oracle's own sensitivity
@@ -27,6 +29,7 @@ import argparse
 import copy
 import glob
 import json
+import math
 import os
 import sys
 import time
@@ -84,6 +87,9 @@ def parse():
     ap.add_argument("--step-scale", type=float, default=1.0, help="multiplies the reference's per-level step literals (optimize.cpp:22-26); "
                     "1 = the reference.  Used by the converging side leg only")
     ap.add_argument("--min-residual", type=float, default=-1.0, help="stop threshold on the mean squared residual (tracker.cpp:16); < 0 = the reference's 5e-3")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline figure: accuracy against the "
+                    "ground truth and the CPU oracle (the parity check fails the run), the CPU baseline, roofline, the PCIe-inclusive rate, "
+                    "and the side legs (single stream, mono batch, SYN-1080, converging configuration); a plain run only times the steps")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller (rank 0's sequences) as DIR/<name>.npy: "
                          "syn640 / syn1080 xi_rel [B][6] + T_rel [B][4][4], syn640-mono xi_world + T_world + is_keyframe; float32, at most "
@@ -190,27 +196,170 @@ def dump_outputs(path, arrays):
     return {"dir": path, "files": sorted(k + ".npy" for k in arrays), "sequences": n if rows is None else int(rows.size), "of_sequences": n}
 
 
-def render_sequences(env, B, F, W, H, K, want_depth=True, n_gt=32):
-    """synthetic sequences rendered straight into HBM as raw sensor frames: u8 gray [F][B][H][W] (+ u16 depth, 1/5000 m units)"""
+# ======================================================================================================================
+# synthetic frames: dvo_amd.synth.render_batch fused into one HIP kernel
+# ======================================================================================================================
+# synth.render_batch is a chain of ~500 elementwise torch kernels over float64 temporaries; at the headline's 98 304 frames that
+# chain is HBM bound and takes ~50 s.  The kernel below performs the same float64 operations in the same order, one rounding per
+# torch operation (no contraction, torch's scalar division = multiplication by the reciprocal computed on the host), with the
+# same device math library, and quantises as torch.round, torch.clamp and the integer casts do, so every frame is bit for bit the one the
+# torch chain renders (tests/test_bench_render.py).  It is compiled at run time with torch's own hiprtc and launched on
+# torch's current stream through its own HIP runtime.
+RENDER_SRC = r"""
+#define TWO_PI %(two_pi)s
+extern "C" __global__ void __launch_bounds__(256)
+render_frames(const double* __restrict__ pose, int nb, int b0, int B, int W, int H, double inv_fx, double inv_fy, double cx, double cy,
+              int newton_iters, void* gray, int gray_kind, void* depth, int depth_kind, int depth_frames)
+{
+    // pose: [F][nb][12] (R row-major, t) of sequences b0 .. b0 + nb - 1; grid.y = F * nb; outputs [F][B][H][W] (depth: [depth_frames][B][H][W])
+    const int px = blockIdx.x * blockDim.x + threadIdx.x;
+    if (px >= W * H) return;
+    const int f = blockIdx.y / nb, b = b0 + blockIdx.y %% nb;
+    const double* P = pose + 12 * (size_t)blockIdx.y;
+    const double rx = ((double)(px %% W) - cx) * inv_fx, ry = ((double)(px / W) - cy) * inv_fy;
+    const double dx = P[0] * rx + P[1] * ry + P[2];
+    const double dy = P[3] * rx + P[4] * ry + P[5];
+    const double dz = P[6] * rx + P[7] * ry + P[8];
+    const double t0 = P[9], t1 = P[10], t2 = P[11];
+    double lam = (1.5 - t2) / dz;
+    for (int i = 0; i < newton_iters; ++i) {            // synth.height + the Newton step of render_batch
+        const double X = t0 + lam * dx, Y = t1 + lam * dy;
+        const double ax = TWO_PI * X * %(inv_lx)s, ay = TWO_PI * Y * %(inv_ly)s;
+        const double sx = sin(ax), cxh = cos(ax), sy = sin(ay), cyh = cos(ay);
+        const double Z = 1.5 + %(amp)s * sx * cyh;
+        const double zx = %(c_zx)s * cxh * cyh, zy = %(c_zy)s * sx * sy;
+        const double Fv = t2 + lam * dz - Z;
+        const double dF = dz - (zx * dx + zy * dy);
+        lam = lam - Fv / dF;
+    }
+    const double X = t0 + lam * dx, Y = t1 + lam * dy;
+    double acc = 0.0;                                    // synth.texture
+%(waves)s
+    acc = acc * %(inv_amp_sum)s;
+    const float g = (float)(0.5 + 0.45 * tanh(2.5 * acc) * %(inv_tanh)s), d = (float)lam;
+    const size_t o = ((size_t)f * B + b) * (size_t)(W * H) + px;
+    if (gray_kind == 1)       // u8 as cv::imread delivers it
+        ((unsigned char*)gray)[o] = (unsigned char)fminf(fmaxf(rintf(g * 255.0f), 0.0f), 255.0f);
+    else if (gray_kind == 2)
+        ((float*)gray)[o] = g;
+    if (f < depth_frames) {
+        if (depth_kind == 1)  // u16 in 1/5000 m (bit pattern kept in an int16 tensor)
+            ((short*)depth)[o] = (short)(int)fminf(fmaxf(rintf(d * 5000.0f), 0.0f), 65535.0f);
+        else if (depth_kind == 2)
+            ((float*)depth)[o] = d;
+    }
+}
+"""
+_renderer = None
+
+
+def render_source():
+    """RENDER_SRC with synth's constants: every literal is the float64 torch uses, as a hexadecimal floating-point literal"""
     from dvo_amd import synth
-    dev = env.dev
-    gray8 = torch.empty((F, B, H, W), dtype=torch.uint8, device=dev)
-    depth16 = torch.empty((F, B, H, W), dtype=torch.int16, device=dev) if want_depth else None   # (bit pattern of uint16)
+    h = lambda x: float(x).hex()
+    freqs, phases, amps = synth._TEX
+    waves = "\n".join("    acc = acc + %s * sin(TWO_PI * (%s * X + %s * Y) + %s);" % (h(a), h(fx), h(fy), h(ph))
+                      for (fx, fy), ph, a in zip(freqs, phases, amps))
+    return RENDER_SRC % {"two_pi": h(2 * math.pi), "inv_lx": h(1.0 / 2.0), "inv_ly": h(1.0 / 1.5), "amp": h(0.3),
+                         "c_zx": h(0.3 * (2 * math.pi / 2.0)), "c_zy": h(-0.3 * (2 * math.pi / 1.5)), "waves": waves,
+                         "inv_amp_sum": h(1.0 / float(np.sum(amps))), "inv_tanh": h(1.0 / math.tanh(2.5))}
+
+
+def compile_renderer(arch):
+    """code object of render_frames for `arch` (e.g. gfx950), compiled by the hiprtc torch ships; raises when it cannot"""
+    import ctypes as C
+    rtc = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libhiprtc.so"))
+    prog = C.c_void_p()
+    _Renderer._ok(rtc.hiprtcCreateProgram(C.byref(prog), render_source().encode(), b"render_frames.hip", 0, None, None), "hiprtcCreateProgram")
+    try:
+        opts = [b"--offload-arch=" + arch.encode(), b"-O3", b"-ffp-contract=off"]
+        if rtc.hiprtcCompileProgram(prog, len(opts), (C.c_char_p * len(opts))(*opts)) != 0:
+            n = C.c_size_t()
+            rtc.hiprtcGetProgramLogSize(prog, C.byref(n))
+            log = C.create_string_buffer(n.value + 1)
+            rtc.hiprtcGetProgramLog(prog, log)
+            raise RuntimeError("bench.py: hiprtc could not compile the frame renderer:\n" + log.value.decode(errors="replace"))
+        n = C.c_size_t()
+        _Renderer._ok(rtc.hiprtcGetCodeSize(prog, C.byref(n)), "hiprtcGetCodeSize")
+        code = C.create_string_buffer(n.value)
+        _Renderer._ok(rtc.hiprtcGetCode(prog, code), "hiprtcGetCode")
+        return code.raw
+    finally:
+        rtc.hiprtcDestroyProgram(C.byref(prog))
+
+
+class _Renderer:
+    def __init__(self, dev):
+        import ctypes as C
+        self.C = C
+        self.hip = C.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))   # the runtime torch already runs on
+        code = compile_renderer(torch.cuda.get_device_properties(dev).gcnArchName.split(":")[0])
+        self.module, self.fn = C.c_void_p(), C.c_void_p()
+        self._ok(self.hip.hipModuleLoadData(C.byref(self.module), code), "hipModuleLoadData")
+        self._ok(self.hip.hipModuleGetFunction(C.byref(self.fn), self.module, b"render_frames"), "hipModuleGetFunction")
+
+    @staticmethod
+    def _ok(st, what):
+        if st != 0:
+            raise RuntimeError("bench.py: %s failed with status %d" % (what, st))
+
+    def launch(self, pose, nb, b0, B, W, H, K, newton_iters, gray, depth, stream):
+        """pose: float64 device tensor [F][nb][12]; gray / depth: None or contiguous device tensors [F][B][H][W] (depth: [<= F][B][H][W])
+        of uint8 / int16 (quantised as a sensor delivers them) or float32"""
+        C = self.C
+        F = pose.shape[0]
+        assert pose.dtype == torch.float64 and pose.is_contiguous() and tuple(pose.shape) == (F, nb, 12) and 0 <= b0 and b0 + nb <= B
+        kinds = {torch.uint8: 1, torch.int16: 1, torch.float32: 2}
+
+        def out(t, frames):
+            if t is None:
+                return None, 0
+            assert t.is_contiguous() and t.device == pose.device and tuple(t.shape) == (frames, B, H, W) and t.dtype in kinds
+            return t.data_ptr(), kinds[t.dtype]
+        gp, gk = out(gray, F)
+        df = 0 if depth is None else depth.shape[0]
+        assert df <= F
+        dp, dk = out(depth, df)
+        assert gray is None or gray.dtype in (torch.uint8, torch.float32)
+        assert depth is None or depth.dtype in (torch.int16, torch.float32)
+        args = [C.c_void_p(pose.data_ptr()), C.c_int(nb), C.c_int(b0), C.c_int(B), C.c_int(W), C.c_int(H),
+                C.c_double(1.0 / float(K[0][0])), C.c_double(1.0 / float(K[1][1])), C.c_double(float(K[0][2])), C.c_double(float(K[1][2])),
+                C.c_int(newton_iters), C.c_void_p(gp), C.c_int(gk), C.c_void_p(dp), C.c_int(dk), C.c_int(df)]
+        params = (C.c_void_p * len(args))(*[C.cast(C.pointer(x), C.c_void_p) for x in args])
+        assert F * nb <= 65535
+        self._ok(self.hip.hipModuleLaunchKernel(self.fn, C.c_uint((W * H + 255) // 256), C.c_uint(F * nb), C.c_uint(1), C.c_uint(256),
+                                                C.c_uint(1), C.c_uint(1), C.c_uint(0), C.c_void_p(stream), params, None),
+                 "hipModuleLaunchKernel")
+
+
+def render_frames(env, B, F, W, H, K, gray, depth=None, n_gt=32, chunk=512):
+    """Render the synthetic sequences b = 0 .. B-1 of this rank (trajectory seed 42 + 1000 rank + b, synth.render_batch with 6
+    Newton iterations) into gray [F][B][H][W] and, when given, depth [<= F][B][H][W]; uint8 / int16 outputs are quantised as
+    a sensor delivers them (u8 gray, u16 depth in 1/5000 m), float32 outputs are render_batch's values.  Returns the ground-truth
+    poses of the first n_gt sequences.  The host computes a chunk's trajectories while the device renders the chunk before."""
+    global _renderer
+    from dvo_amd import synth
+    if _renderer is None:
+        _renderer = _Renderer(env.dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    chunk = max(1, min(chunk, 65535 // F))   # sequences per launch (grid.y = F x chunk)
     gt_poses = []
-    chunk = max(1, (96 if W == 640 else 12) // F)  # sequences rendered per call (float64 temporaries: ~20 x chunk x F frames)
     for b0 in range(0, B, chunk):
         b1 = min(B, b0 + chunk)
         poses = [synth.trajectory(F, seed=42 + 1000 * env.rank + b) for b in range(b0, b1)]
-        for b, p in zip(range(b0, b1), poses):
-            if b < n_gt:
-                gt_poses.append(p)
-        Ts = np.stack([p[f] for p in poses for f in range(F)])
-        g, d = synth.render_batch(Ts, K, W, H, device=dev, newton_iters=6)
-        g = g.reshape(b1 - b0, F, H, W).permute(1, 0, 2, 3); d = d.reshape(b1 - b0, F, H, W).permute(1, 0, 2, 3)
-        gray8[:, b0:b1] = torch.clamp(torch.round(g * 255.0), 0, 255).to(torch.uint8)
-        if want_depth:
-            depth16[:, b0:b1] = torch.clamp(torch.round(d * 5000.0), 0, 65535).to(torch.int32).to(torch.int16)
+        gt_poses += poses[:max(0, n_gt - b0)]
+        P = np.stack([np.stack([np.concatenate([p[f][:3, :3].reshape(9), p[f][:3, 3]]) for p in poses]) for f in range(F)])
+        pose = torch.from_numpy(np.ascontiguousarray(P, np.float64)).pin_memory().to(env.dev, non_blocking=True)
+        _renderer.launch(pose, b1 - b0, b0, B, W, H, K, 6, gray, depth, stream)
     torch.cuda.synchronize()
+    return gt_poses
+
+
+def render_sequences(env, B, F, W, H, K, n_gt=32):
+    """synthetic sequences rendered straight into HBM as raw sensor frames: u8 gray [F][B][H][W] + u16 depth, 1/5000 m units"""
+    gray8 = torch.empty((F, B, H, W), dtype=torch.uint8, device=env.dev)
+    depth16 = torch.empty((F, B, H, W), dtype=torch.int16, device=env.dev)   # (bit pattern of uint16)
+    gt_poses = render_frames(env, B, F, W, H, K, gray8, depth16, n_gt=n_gt)
     return gray8, depth16, gt_poses
 
 
@@ -372,7 +521,7 @@ def run_depth(a, env, role="headline", data=None):
     # ---- accuracy of the timed steps against the synthetic ground truth (BASELINE metric: "ATE RMSE vs reference") ------
     step_pairs = [(ring_index(a.warmup + k, F), ring_index(1 + a.warmup + k, F)) for k in range(a.steps)]
     NS = min(len(gt_poses), B) if head else min(len(gt_poses), B, 8 if a.workload == "syn640" else 2)
-    if rank == 0 and NS > 0:
+    if a.full and rank == 0 and NS > 0:
         xs = poses_out[:, :NS].cpu().numpy()  # [steps][sample][6]
         et, er = [], []
         for b in range(NS):
@@ -384,7 +533,7 @@ def run_depth(a, env, role="headline", data=None):
                                      "(per-frame motion ~ N(0, 5 mm / 0.3 deg))" % (NS, a.steps)}
 
     # ---- PCIe-inclusive rate: the same steps fed from pinned HOST buffers, every pose read back (SURVEY.md §8d fps definition) ----
-    if head and a.pcie_steps > 0:
+    if head and a.full and a.pcie_steps > 0:
         PB = min(B, a.pcie_batch)
         # (fixed launch schedule: the adaptive one keeps the host inside push() until the GPU is nearly done with the step, so the
         #  next frame's transfer would not be queued in time to overlap it)
@@ -431,7 +580,7 @@ def run_depth(a, env, role="headline", data=None):
         del host, xi_pin
 
     # ---- roofline of the dominant kernel (k_track_gn): HIP events around every launch of an identical pass ----
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         pb = dvo.Batch(B, K, W, H, levels, culls, cfg=make_cfg(profile=1))
         push(pb, 0)
         for k in range(a.warmup):
@@ -489,10 +638,10 @@ def run_depth(a, env, role="headline", data=None):
     # ---- parity sample (oracle = checker): a small batch over the first sequences, logs read back after every step ----------
     parity_fail = None
     gpu_iters = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and NS > 0 and tracker_over:   # the oracle takes the same non-reference constants
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and NS > 0 and tracker_over:   # the oracle takes the same non-reference constants
         env.orc.set_tracker_params([tracker_over.get("step_default", 2.0), tracker_over.get("step_level1", 1.5), tracker_over.get("step_level2", 1.0)],
                                    tracker_over.get("min_residual", -1.0), -1.0)
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and NS > 0:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and NS > 0:
         orc = env.orc
         from concurrent.futures import ThreadPoolExecutor
         # same tile size as the big batch (auto picks 4 pixels per thread there): then a sequence's bits do not depend on its batch
@@ -556,7 +705,7 @@ def run_depth(a, env, role="headline", data=None):
             parity_fail = out["accuracy"]["per_iteration_parity"]
 
     # ---- secondary (N = 1 only, a few seconds): the single-sequence drop-in entry points, host frames in, pose out per call --
-    if head and env.solo and a.workload == "syn640" and not a.no_secondary:
+    if head and a.full and env.solo and a.workload == "syn640" and not a.no_secondary:
         g0, d0, s0 = host_frames(slice(None), 0)
         n_sec = 200
         vo = dvo.VisualOdometry(K, W, H, cfg=dvo.default_config(device=env.local))
@@ -630,7 +779,7 @@ def run_depth(a, env, role="headline", data=None):
                                     "from C++ through include/dvo.hpp: the reference's own API (system.hpp:77-93)"}
 
     # ---- CPU baseline: the oracle on this box's host cores, bounded sample of the same workload ----------
-    if env.solo and not a.no_cpu_baseline and NS > 0:
+    if a.full and env.solo and not a.no_cpu_baseline and NS > 0:
         orc = env.orc
         from concurrent.futures import ThreadPoolExecutor
         ncore = env.ncore
@@ -763,18 +912,17 @@ def run_mono(a, env, role="headline", gray=None):
     init_depth = None
     if gray is None:
         gray = torch.empty((F, B, H, W), dtype=torch.uint8 if raw else torch.float32, device=dev)
-        init_depth = torch.empty((B, H // 4, W // 4), dtype=torch.float32, device=dev) if a.mono_init == "gt" else None
-        chunk = max(1, 96 // F)
-        gen = torch.Generator(device=dev); gen.manual_seed(1234 + rank)
-        for b0 in range(0, B, chunk):
-            b1 = min(B, b0 + chunk)
-            Ts = np.stack([synth.trajectory(F, seed=42 + 1000 * rank + b)[f] for b in range(b0, b1) for f in range(F)])
-            g, d = synth.render_batch(Ts, K, W, H, device=dev, newton_iters=6)
-            g = g.reshape(b1 - b0, F, H, W).permute(1, 0, 2, 3)
-            gray[:, b0:b1] = torch.clamp(torch.round(g * 255.0), 0, 255).to(torch.uint8) if raw else g
-            if init_depth is not None:
-                d0 = d.reshape(b1 - b0, F, H, W)[:, 0, ::4, ::4]
+        depth0 = torch.empty((1, B, H, W), dtype=torch.float32, device=dev) if a.mono_init == "gt" else None
+        render_frames(env, B, F, W, H, K, gray, depth0)
+        if depth0 is not None:   # (the noise is drawn in the chunks of 96 // F sequences the frames were once rendered in)
+            init_depth = torch.empty((B, H // 4, W // 4), dtype=torch.float32, device=dev)
+            chunk = max(1, 96 // F)
+            gen = torch.Generator(device=dev); gen.manual_seed(1234 + rank)
+            for b0 in range(0, B, chunk):
+                b1 = min(B, b0 + chunk)
+                d0 = depth0[0, b0:b1, ::4, ::4]
                 init_depth[b0:b1] = d0 + 0.1 * torch.randn(d0.shape, generator=gen, device=dev)
+            del depth0
     else:
         assert raw and gray.dtype == torch.uint8 and gray.shape[0] == F and gray.shape[1] >= B
     init_sigma = torch.full_like(init_depth, 0.5) if init_depth is not None else None
@@ -839,7 +987,7 @@ def run_mono(a, env, role="headline", gray=None):
                       "poses_finite": bool(torch.isfinite(poses_out).all().item()), "datagen_s": round(t_gen, 2)}}
     if dumped:
         out["dump_outputs"] = dumped
-    if head and a.pcie_steps > 0:   # co-headline: every frame streamed from pinned host memory, every pose copied back
+    if head and a.full and a.pcie_steps > 0:   # co-headline: every frame streamed from pinned host memory, every pose copied back
         PB = min(B, a.pcie_batch)
         hb = dvo.MonoBatch(PB, K, W, H, ring_keyframes=a.ring, cfg=dvo.default_config(device=env.local, stream=env.stream, rng_seed=1))
         host = [gray[f, :PB].cpu().pin_memory() for f in range(min(F, 3))]
@@ -862,7 +1010,7 @@ def run_mono(a, env, role="headline", gray=None):
                            "note": "raw host frames: only the rows the pyramid keeps (every 4th: Frame(gray,K,3,2)) are transferred, by one strided copy",
                            "input": "pinned host %s gray (dvo_batch_odometrize_%shost), every world pose copied back per step" % (("u8", "raw_") if raw else ("float32", ""))}
         hb.close()
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         pb, _ = run(1)
         pr = pb.profile()
         pm = pb.profile_mapping()
@@ -907,7 +1055,7 @@ def run_mono(a, env, role="headline", gray=None):
                                              "achieved_lane_instructions_per_s": rate, "peak_lane_instructions_per_s": VALU_ISSUE_PEAK,
                                              "frac": rate / VALU_ISSUE_PEAK})
             out["mapping_kernels"] = mk
-    if env.solo and not a.no_cpu_baseline:
+    if a.full and env.solo and not a.no_cpu_baseline:
         orc = env.orc
         g0 = gray[:, 0].cpu().numpy()
         if raw:
@@ -978,7 +1126,7 @@ def main():
         out = run_mono(a, env)
     else:
         out, data, fail = run_depth(a, env, "headline")
-        if a.workload == "syn640" and env.solo and not a.no_secondary and a.input == "raw" and abs(a.sigma - 0.1) < 1e-9:
+        if a.full and a.workload == "syn640" and env.solo and not a.no_secondary and a.input == "raw" and abs(a.sigma - 0.1) < 1e-9:
             sec = out.setdefault("secondary", {})
             t_legs = time.time()
             # BASELINE configs[2]: the mono pipeline on the first 8192 sequences' gray frames (already in HBM)

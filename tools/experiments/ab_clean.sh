@@ -5,5 +5,5 @@ for rep in 1 2; do
 done
 for v in ON OFF; do
   if [ $v = ON ]; then export DVO_EXP_CLEAN_ON=1; else unset DVO_EXP_CLEAN_ON; fi
-  python3 bench.py --no-cpu-baseline --pcie-steps 0 --no-secondary --batch 4096 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench clean $v:', round(d['value']), 'frames/s', round(d['ms_per_step'],3), 'ms/step, gn avg', round(d['roofline']['avg_launch_us'],1), 'us', d['accuracy']['per_iteration_parity']['ok'] if 'accuracy' in d and 'per_iteration_parity' in d['accuracy'] else '')"
+  python3 bench.py --full --no-cpu-baseline --pcie-steps 0 --no-secondary --batch 4096 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench clean $v:', round(d['value']), 'frames/s', round(d['ms_per_step'],3), 'ms/step, gn avg', round(d['roofline']['avg_launch_us'],1), 'us', d['accuracy']['per_iteration_parity']['ok'] if 'accuracy' in d and 'per_iteration_parity' in d['accuracy'] else '')"
 done

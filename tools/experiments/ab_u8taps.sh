@@ -32,7 +32,7 @@ for rep in 1 2; do
 done
 for v in ON OFF; do
   if [ $v = OFF ]; then export DVO_EXP_U8TAPS_OFF=1; else unset DVO_EXP_U8TAPS_OFF; fi
-  python3 bench.py --no-cpu-baseline --pcie-steps 0 --no-secondary --batch 4096 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench u8 taps $v:', round(d['value']), 'frames/s', round(d['ms_per_step'],3), 'ms/step, gn avg', round(d['roofline']['avg_launch_us'],1), 'us')"
+  python3 bench.py --full --no-cpu-baseline --pcie-steps 0 --no-secondary --batch 4096 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('bench u8 taps $v:', round(d['value']), 'frames/s', round(d['ms_per_step'],3), 'ms/step, gn avg', round(d['roofline']['avg_launch_us'],1), 'us')"
 done
 unset DVO_EXP_U8TAPS_OFF
 PROBE_EXTRA=--raw bash tools/pmc_gn.sh 0.1 4 2 256 > /dev/null 2>&1; cp /tmp/pmc_all.txt gpurun_out/r03_exp_u8taps_pmc_raw_b256.txt
