@@ -14,22 +14,49 @@ def bgr2gray_u8(rgb):
     return ((r * 4899 + g * 9617 + b * 1868 + 8192) >> 14).astype(np.uint8)
 
 
-def undistort_nearest_np(img, K, D):
-    """cv::initUndistortRectifyMap(K, D, I, K) + cv::remap(INTER_NEAREST, BORDER_CONSTANT): returns (remapped, invalid mask)."""
-    h, w = img.shape
-    K = np.asarray(K, np.float64); D = np.asarray(D, np.float64)
+def undistort_coords_np(K, D, w, h):
+    """The source coordinates (mx, my), float32 [h, w], that undistort_source (csrc/dvo_math.h) computes for each destination pixel
+    before it rounds them: the radial-tangential model in float64 with the header's operation order, rounded to float32 once.
+    K and D are taken as the float32 values the library receives; only fx, fy, cx, cy of K enter (make_intr: a skew K[0, 1] is
+    ignored)."""
+    K = np.asarray(K, np.float32).reshape(3, 3).astype(np.float64)
+    k1, k2, p1, p2, k3 = (np.float64(c) for c in np.asarray(D, np.float32).reshape(5))
+    fx, fy, cx, cy = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
     v, u = np.mgrid[0:h, 0:w].astype(np.float64)
-    x = (u - K[0, 2]) / K[0, 0]
-    y = (v - K[1, 2]) / K[1, 1]
-    r2 = x * x + y * y
-    rad = 1 + r2 * (D[0] + r2 * (D[1] + r2 * D[4]))
-    xd = x * rad + 2 * D[2] * x * y + D[3] * (r2 + 2 * x * x)
-    yd = y * rad + D[2] * (r2 + 2 * y * y) + 2 * D[3] * x * y
-    mx = np.rint((xd * K[0, 0] + K[0, 2]).astype(np.float32)).astype(np.int64)
-    my = np.rint((yd * K[1, 1] + K[1, 2]).astype(np.float32)).astype(np.int64)
-    ok = (mx >= 0) & (mx < w) & (my >= 0) & (my < h)
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        x = (u - cx) / fx
+        y = (v - cy) / fy
+        r2 = x * x + y * y
+        radial = 1.0 + r2 * (k1 + r2 * (k2 + r2 * k3))
+        xd = x * radial + 2.0 * p1 * x * y + p2 * (r2 + 2.0 * x * x)
+        yd = y * radial + p1 * (r2 + 2.0 * y * y) + 2.0 * p2 * x * y
+        mx = (xd * fx + cx).astype(np.float32)
+        my = (yd * fy + cy).astype(np.float32)
+    return mx, my
+
+
+def undistort_index_np(K, D, w, h):
+    """int64 [h, w]: the source index sy * w + sx that destination pixel (x, y) takes in cv::initUndistortRectifyMap(K, D, I, K) +
+    cv::remap(INTER_NEAREST, BORDER_CONSTANT), -1 for the border.  Rounding is cvRound's, half to even (np.rint of the float32
+    coordinate); D4: a coordinate that is not finite or has |m| >= 2**30 is border."""
+    mx, my = undistort_coords_np(K, D, w, h)
+    ok = np.isfinite(mx) & np.isfinite(my)
+    with np.errstate(invalid="ignore"):
+        ok &= (np.abs(mx) < np.float32(2 ** 30)) & (np.abs(my) < np.float32(2 ** 30))
+    sx = np.where(ok, np.rint(np.where(ok, mx, 0)), -1).astype(np.int64)
+    sy = np.where(ok, np.rint(np.where(ok, my, 0)), -1).astype(np.int64)
+    ok &= (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
+    return np.where(ok, sy * w + sx, -1)
+
+
+def undistort_nearest_np(img, K, D):
+    """cv::initUndistortRectifyMap(K, D, I, K) + cv::remap(INTER_NEAREST, BORDER_CONSTANT): returns (remapped, invalid mask);
+    the border pixels of `remapped` are 0."""
+    h, w = img.shape
+    idx = undistort_index_np(K, D, w, h)
+    ok = idx >= 0
     out = np.zeros_like(img)
-    out[ok] = img[my[ok], mx[ok]]
+    out[ok] = img.reshape(-1)[idx[ok]]
     return out, ~ok
 
 

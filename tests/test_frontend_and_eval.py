@@ -175,25 +175,20 @@ def test_ingest_bit_exact(channels):
 
 @pytest.mark.gpu
 def test_undistort_nearest_remap():
+    """dvo_op_undistort against the float64 camera model (tests/real_data.py:undistort_index_np): the same source pixel for every
+    destination pixel, its value copied bit for bit, the border exactly INVALID (-2)"""
+    from real_data import undistort_index_np
     rng = np.random.RandomState(8)
     h, w = 120, 160
     img = rng.uniform(0, 1, (h, w)).astype(np.float32)
     K = np.array([[195, 0, 94.5], [0, 199, 55], [0, 0, 1]], np.float32)        # loader.cpp:17 scaled by 1/4
     D = np.array([-0.0462, 0.152, -0.00429, 0.0117, -0.0725], np.float32)      # loader.cpp:18
     got = dvo.undistort(img, K, D)
-    v, u = np.mgrid[0:h, 0:w].astype(np.float64)
-    x = (u - K[0, 2]) / K[0, 0]
-    y = (v - K[1, 2]) / K[1, 1]
-    r2 = x * x + y * y
-    rad = 1 + r2 * (D[0] + r2 * (D[1] + r2 * D[4]))
-    xd = x * rad + 2 * D[2] * x * y + D[3] * (r2 + 2 * x * x)
-    yd = y * rad + D[2] * (r2 + 2 * y * y) + 2 * D[3] * x * y
-    mx = np.rint((xd * K[0, 0] + K[0, 2]).astype(np.float32)).astype(int)
-    my = np.rint((yd * K[1, 1] + K[1, 2]).astype(np.float32)).astype(int)
-    ok = (mx >= 0) & (mx < w) & (my >= 0) & (my < h)
+    idx = undistort_index_np(K, D, w, h)
     exp = np.full((h, w), -2.0, np.float32)
-    exp[ok] = img[my[ok], mx[ok]]
-    assert (got == exp).mean() > 0.999                    # ties of rint at .5 may differ in the last double bit
+    exp[idx >= 0] = img.reshape(-1)[idx[idx >= 0]]
+    assert (idx < 0).any() and (idx >= 0).any()
+    np.testing.assert_array_equal(got.view(np.uint32), exp.view(np.uint32))
     np.testing.assert_array_equal(dvo.undistort(img, K, np.zeros(5, np.float32)), img)
 
 
