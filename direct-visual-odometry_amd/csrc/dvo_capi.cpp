@@ -674,13 +674,12 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     DVO_TRY(res.alloc(sizeof(dvo_gn_result)));
     if (mask) { DVO_TRY(mk.alloc(n)); DVO_HIP(hipMemsetAsync(mk.p, 0, n, c.s)); }
     launch_set_pose(trk.state.as<SeqState>(), xin.as<float>(), 1, c.s);
-    GnArgs ga;
+    GnArgs ga{};
     // per-pixel constants of the reference level (what build_pyramid does for whole frames)
     DevBuf wgb;
     DVO_TRY(wgb.alloc(n * 4));
     {
-        PrepArgs pa;
-        memset(&pa, 0, sizeof pa);
+        PrepArgs pa{};
         pa.depth = rd.as<float>(); pa.sigma = rs.as<float>(); pa.wgt = wgb.as<float>();
         pa.level_end[0] = n;
         pa.step[0] = trk.level_params(level).step;
@@ -700,9 +699,8 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     ga.ignore_active = 1;
     ga.tiles_x = trk.tiles_x[level]; ga.tiles_y = trk.tiles_y[level]; ga.margin = trk.tile_margin;
     trk.launch_gn(ga, level, 1, c.s);
-    SolveArgs sa;
-    sa.state = trk.state.as<SeqState>(); sa.partials = trk.partials.as<float>();
-    sa.log = nullptr; sa.result = res.as<dvo_gn_result>(); sa.counters = nullptr;
+    SolveArgs sa{};
+    sa.state = trk.state.as<SeqState>(); sa.partials = trk.partials.as<float>(); sa.result = res.as<dvo_gn_result>();
     sa.nblk = trk.nblk[level]; sa.level = level; sa.level_pixels = w * h;
     sa.max_iterations = cf.max_iterations; sa.fixed_iterations = cf.fixed_iterations;
     sa.min_update = cf.min_update; sa.min_residual = cf.min_residual; sa.ignore_active = 1;
@@ -818,14 +816,11 @@ int dvo_op_depth_update(int dev, const dvo_config* cfg, int n_hist, const float*
     DVO_HIP(hipMemcpyAsync(gtab.p, gptr.data(), sizeof(float*) * (size_t)n_hist, hipMemcpyHostToDevice, c.s));
     DVO_TRY(vd.alloc(sizeof(int)));
     DVO_HIP(hipMemsetAsync(vd.p, 0, sizeof(int), c.s));
-    UpdateArgs a;
-    memset(&a, 0, sizeof a);
+    UpdateArgs a{};
     a.ref_depth = rd.as<float>(); a.ref_sigma = rs.as<float>(); a.ref_age = ra.as<float>();
-    a.obj_gray = og.as<float>(); a.ages = ages.as<AgeEntry>();
-    a.ring_gray = nullptr; a.gray_table = gtab.as<const float*>(); a.meta = nullptr;
+    a.obj_gray = og.as<float>(); a.ages = ages.as<AgeEntry>(); a.gray_table = gtab.as<const float*>();
     a.n_seq = 1; a.R = n_hist;
     a.n_hist = n_hist; a.w = w; a.h = h; a.crop = cf.crop_enable; a.obj_id = obj_id; a.seed = cf.rng_seed;
-    a.clamp_age = 0;
     a.k = intr_of(K);
     memcpy(a.K9, K, sizeof a.K9);
     pose_from_xi(obj_rel_xi, 1.0f, a.rel_pose);

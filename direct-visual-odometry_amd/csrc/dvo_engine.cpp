@@ -206,8 +206,7 @@ int FrameSet::alloc(const Geometry& geo, int n, const dvo_config& cfg, void* mem
 // wgt of every level from the current sigma pyramid (k_prep_ref)
 static void prep_reference(FrameSet& fs, hipStream_t s)
 {
-    PrepArgs a;
-    memset(&a, 0, sizeof a);
+    PrepArgs a{};
     a.depth = fs.depth[0]; a.sigma = fs.sigma[0]; a.wgt = fs.wgt[0];  // levels are contiguous
     size_t end = 0;
     for (int l = 0; l < fs.g.levels; l++) {
@@ -239,30 +238,37 @@ static void plan_copy(PyramidArgs& a, const uint8_t* seq_action, const FrameSet*
     }
 }
 
-// the arguments of a build from float maps (the caller adds the plan's copy-forward and, optionally, the remap)
-static void float_args(PyramidArgs& a, FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, bool keep_sigma,
-                       bool rows_decimated)
+// the geometry of a build from input frames: input size, the pyramid's levels and the rows the input buffers hold (everything else zero)
+static PyramidArgs frame_args(const FrameSet& fs, bool rows_decimated)
 {
-    memset(&a, 0, sizeof a);
-    a.src[0] = gray_dev; a.src[1] = depth_dev; a.src[2] = sigma_dev;
+    PyramidArgs a{};
     a.src_w = fs.g.src_w; a.src_h = fs.g.src_h; a.culls = fs.g.culls; a.levels = fs.g.levels;
     a.src_img_rows = rows_decimated ? fs.g.src_h >> fs.g.culls : fs.g.src_h;
     a.src_row_shift = rows_decimated ? 0 : fs.g.culls;
+    for (int l = 0; l < fs.g.levels; l++) { a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l]; }
+    a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
+    return a;
+}
+
+// the arguments of a build from float maps (the caller adds the plan's copy-forward and, optionally, the remap)
+static PyramidArgs float_args(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, bool keep_sigma,
+                              bool rows_decimated)
+{
+    PyramidArgs a = frame_args(fs, rows_decimated);
+    a.src[0] = gray_dev; a.src[1] = depth_dev; a.src[2] = sigma_dev;
     for (int l = 0; l < fs.g.levels; l++) {
-        a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l];
         a.dst[0][l] = fs.gray[l]; a.dst[1][l] = fs.depth[l];
         a.dst[2][l] = (keep_sigma || !(depth_dev && sigma_dev)) ? fs.sigma[l] : nullptr;
     }
-    a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
     fs.sigma_by_validity = false;
     if (depth_dev && sigma_dev) fuse_prep(a, fs);  // wgt written by the same launch (no k_prep_ref pass)
+    return a;
 }
 
 void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma,
                    bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from)
 {
-    PyramidArgs a;
-    float_args(a, fs, gray_dev, depth_dev, sigma_dev, keep_sigma, rows_decimated);
+    PyramidArgs a = float_args(fs, gray_dev, depth_dev, sigma_dev, keep_sigma, rows_decimated);
     plan_copy(a, seq_action, copy_from);
     launch_pyramid(a, fs.n_seq, s);
 }
@@ -271,17 +277,10 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
 {
     if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
                                          // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
-        PyramidArgs a;
-        memset(&a, 0, sizeof a);
+        PyramidArgs a = frame_args(fs, false);
         a.src[0] = in.gray;
         a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);   // (k_ingest's scale)
-        a.src_w = fs.g.src_w; a.src_h = fs.g.src_h; a.culls = fs.g.culls; a.levels = fs.g.levels;
-        a.src_img_rows = fs.g.src_h; a.src_row_shift = fs.g.culls;
-        for (int l = 0; l < fs.g.levels; l++) {
-            a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l];
-            a.dst[0][l] = fs.gray[l];
-        }
-        a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
+        for (int l = 0; l < fs.g.levels; l++) a.dst[0][l] = fs.gray[l];
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         a.seq_action = seq_action;
         fs.sigma_by_validity = false;
@@ -292,29 +291,22 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     // whole frames -- launch_pyramid picks k_pyramid_remap_depth
     if (!in.raw()) {
         if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
-        PyramidArgs a;
-        float_args(a, fs, in.gray, in.depth, in.sigma, keep_sigma, false);
+        PyramidArgs a = float_args(fs, in.gray, in.depth, in.sigma, keep_sigma, false);
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         plan_copy(a, seq_action, copy_from);
         launch_pyramid(a, fs.n_seq, s);
         return;
     }
-    PyramidArgs a;
-    memset(&a, 0, sizeof a);
+    PyramidArgs a = frame_args(fs, in.rows_decimated);
     a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_depth = in.depth16;
     a.raw_gray_scale = (float)(1.0 / 255.0); a.raw_depth_scale = in.depth_scale;
     a.raw_sigma_valid = 0.1f; a.raw_sigma_invalid = 1.0f; a.raw_invalidate_gray = 1;   // transform.cpp:60-76
-    a.src_w = fs.g.src_w; a.src_h = fs.g.src_h; a.culls = fs.g.culls; a.levels = fs.g.levels;
-    a.src_img_rows = in.rows_decimated ? fs.g.src_h >> fs.g.culls : fs.g.src_h;
-    a.src_row_shift = in.rows_decimated ? 0 : fs.g.culls;
     const bool dep = in.depth16 != nullptr;
     for (int l = 0; l < fs.g.levels; l++) {
-        a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l];
         a.dst[0][l] = fs.gray[l];
         a.dst[1][l] = dep ? fs.depth[l] : nullptr;
         a.dst[2][l] = (dep && keep_sigma) ? fs.sigma[l] : nullptr;
     }
-    a.inv_tw = 1.0f / (float)fs.g.w[fs.g.top()];
     fs.sigma_by_validity = dep && !keep_sigma && fs.allow_const_weight;
     if (fs.sigma_by_validity) {  // no wgt maps: the weight of every pixel that can contribute is a constant of the level
         for (int l = 0; l < fs.g.levels; l++) fs.wgt_valid[l] = gn_weight(fs.step[l], fs.sigma_min, fs.sigma_max, a.raw_sigma_valid);
@@ -345,12 +337,11 @@ int upload_rows(void* dst, const void* src, size_t row_bytes, int img_rows, size
 
 void redecimate(FrameSet& fs, const float* depth_top, const float* sigma_top, hipStream_t s)
 {  // level i = cullImage(top, levels-1-i); the top level itself is the map handed in (frame.cpp:39-61)
-    PyramidArgs a;
-    memset(&a, 0, sizeof a);
+    PyramidArgs a{};
     const int T = fs.g.top();
     a.src[1] = depth_top; a.src[2] = sigma_top;
-    a.src_w = fs.g.w[T]; a.src_h = fs.g.h[T]; a.culls = 0; a.levels = fs.g.levels;
-    a.src_img_rows = a.src_h; a.src_row_shift = 0;
+    a.src_w = fs.g.w[T]; a.src_h = fs.g.h[T]; a.levels = fs.g.levels;
+    a.src_img_rows = a.src_h;
     fs.sigma_by_validity = false;
     for (int l = 0; l < fs.g.levels; l++) {
         a.w[l] = fs.g.w[l]; a.h[l] = fs.g.h[l];
@@ -527,7 +518,7 @@ GnParams Tracker::level_params(int level) const
 
 GnArgs Tracker::gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const
 {
-    GnArgs a;
+    GnArgs a{};
     a.obj_gray = obj.gray[level];
     a.ref_gray = ref.gray[level];
     a.ref_depth = ref.depth[level];
@@ -546,6 +537,19 @@ GnArgs Tracker::gn_args(const FrameSet& obj, const FrameSet& ref, int level, uin
     return a;
 }
 
+SolveArgs Tracker::solve_args(int level, int q0, int ignore_active) const
+{
+    SolveArgs a{};
+    a.state = state.as<SeqState>() + q0;
+    a.partials = partials.as<float>() + (size_t)q0 * part_rows * 32;   // (track()'s GnArgs view of these sequences)
+    a.log = log.as<dvo_track_log>() + q0;
+    a.nblk = nblk[level]; a.level = level; a.level_pixels = g.w[level] * g.h[level];
+    a.max_iterations = cfg.max_iterations; a.fixed_iterations = cfg.fixed_iterations;
+    a.min_update = cfg.min_update; a.min_residual = cfg.min_residual;
+    a.ignore_active = ignore_active;
+    return a;
+}
+
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
 {
     if (tile_margin > 0) launch_track_gn_tile(a, count, ppt[level], s);
@@ -559,8 +563,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
     const Intr* seq_k = plan ? plan->seq_k : cam_k;
     if (persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed) {   // the whole call in one launch (k_track_persist)
-        PersistArgs pa;
-        memset(&pa, 0, sizeof pa);
+        PersistArgs pa{};
         pa.levels = g.levels;
         for (int l = 0; l < g.levels; l++) {
             const GnArgs ga = gn_args(obj, ref, l, nullptr, 0);
@@ -683,31 +686,14 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 if (plan) ga.plan_action = plan->action + q0;
                 if (seq_k) ga.seq_k = seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
                 if (single_launch[level]) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
-                    SolveArgs fa;
-                    fa.state = state.as<SeqState>() + q0;
-                    fa.partials = ga.partials;
-                    fa.log = log.as<dvo_track_log>() + q0;
-                    fa.result = nullptr;
-                    fa.counters = nullptr;
-                    fa.nblk = nblk[level]; fa.level = level; fa.level_pixels = (int)level_px;
-                    fa.max_iterations = cfg.max_iterations; fa.fixed_iterations = cfg.fixed_iterations;
-                    fa.min_update = cfg.min_update; fa.min_residual = cfg.min_residual;
-                    fa.ignore_active = first;
+                    const SolveArgs fa = solve_args(level, q0, first);
                     if (launch_track_gn_fused(ga, fa, nq, ppt[level], group[level], ticket.as<int>(), rep_set + 2 * (level * DVO_MAX_ITERATIONS + it),
                                               adaptive ? prog_d + level * DVO_MAX_ITERATIONS + it : nullptr, sk))
                         continue;
                 }
                 if (fused[level]) {
-                    SolveArgs fa;
-                    fa.state = state.as<SeqState>() + q0;
+                    SolveArgs fa = solve_args(level, q0, 1);
                     fa.partials = nullptr;
-                    fa.log = log.as<dvo_track_log>() + q0;
-                    fa.result = nullptr;
-                    fa.counters = nullptr;  // (the profile counters describe k_track_gn launches only)
-                    fa.nblk = nblk[level]; fa.level = level; fa.level_pixels = (int)level_px;
-                    fa.max_iterations = cfg.max_iterations; fa.fixed_iterations = cfg.fixed_iterations;
-                    fa.min_update = cfg.min_update; fa.min_residual = cfg.min_residual;
-                    fa.ignore_active = 1;
                     launch_track_level(ga, fa, nq, sk);
                     continue;
                 }
@@ -730,16 +716,8 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 } else {
                     launch_gn(ga, level, nq, sk, active_ub);
                 }
-                SolveArgs sa;
-                sa.state = state.as<SeqState>() + q0;
-                sa.partials = ga.partials;
-                sa.log = log.as<dvo_track_log>() + q0;
-                sa.result = nullptr;
-                sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;
-                sa.nblk = nblk[level]; sa.level = level; sa.level_pixels = (int)level_px;
-                sa.max_iterations = cfg.max_iterations; sa.fixed_iterations = cfg.fixed_iterations;
-                sa.min_update = cfg.min_update; sa.min_residual = cfg.min_residual;
-                sa.ignore_active = first;
+                SolveArgs sa = solve_args(level, q0, first);
+                sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;   // (they describe k_track_gn launches only)
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
@@ -980,13 +958,12 @@ int VisualOdometry::init_keyframe(const float* gray, const float* depth, const f
 int VisualOdometry::map_propagate(Keyframe& frame, const Keyframe& ref)
 {  // Mapper::propagate, mapper.cpp:62-74; the pose exp(+rel_xi) is the one k_mono_decide left in meta_dev
     const int T = geoM.top(), tw = geoM.w[T], th = geoM.h[T];
-    PropArgs a;
+    PropArgs a{};
     a.ref_depth = ref.fs.depth[T]; a.ref_sigma = ref.fs.sigma[T]; a.ref_age = ref.age.as<float>();
     a.depth = frame.fs.depth[T]; a.sigma = frame.fs.sigma[T]; a.age = frame.age.as<float>();
     a.owner = owner.as<int>();
     a.w = tw; a.h = th; a.n_seq = 1; a.k = geoM.k[T];
     a.meta = meta_dev.as<MonoSeq>();
-    memset(&a.pose, 0, sizeof a.pose); a.tz = 0.0f;
     launch_propagate_batch(a, stream);
     // (Frame::updateDepthSigmaAge, frame.cpp:47-54, re-decimates both maps here; Mapper::regularize and Frame::updateDepth follow at
     //  once, mapper.cpp:26, and decimate the depth again: map_regularize() derives every level of both pyramids in its one pass)
@@ -1050,18 +1027,16 @@ int VisualOdometry::map_update(Keyframe& obj)
     // top-level gray pointers only change when FrameHistory does (a keyframe pushed, dropped or loaded): the device copies are
     // refreshed then (hist_version), not on every frame -- two uploads and a stream synchronisation less per tracked frame.
     DVO_TRY(refresh_history_tables());
-    AgeTableArgs ta;
+    AgeTableArgs ta{};
     ta.meta = meta_dev.as<MonoSeq>(); ta.hist_xi = hist_xi_dev.as<float>(); ta.ages = ages.as<AgeEntry>();
     ta.n_seq = 1; ta.R = n_hist; ta.n_hist = n_hist;
     ta.zero_word = valid_dev.as<int>();   // mapper.cpp:136's count of this update (read back when dvo_vo_last_valid_updates asks)
     if (!age_table_done) launch_age_table(ta, stream);   // (done: the tail of k_track_persist computed it, odometrize())
     age_table_done = false;
-    UpdateArgs a;
-    memset(&a, 0, sizeof a);
+    UpdateArgs a{};
     a.ref_depth = ref.fs.depth[T]; a.ref_sigma = ref.fs.sigma[T]; a.ref_age = ref.age.as<float>();
     a.obj_gray = obj.fs.gray[T];
     a.ages = ages.as<AgeEntry>();
-    a.ring_gray = nullptr;
     a.gray_table = gray_tab_dev.as<const float*>();
     a.meta = meta_dev.as<MonoSeq>();
     a.n_seq = 1; a.R = n_hist; a.n_hist = n_hist; a.w = tw; a.h = th; a.crop = cfg.crop_enable; a.obj_id = obj.id;
@@ -1081,8 +1056,7 @@ int VisualOdometry::map_regularize(Keyframe& kf)
    // preceding propagate / update left pending (frame.cpp:39-54): every level of depth and sigma is a decimation of the top maps, so one
    // pass (k_regularize_redecimate, the batched pipeline's kernel) leaves the values the reference's three re-decimations leave
     const int T = geoM.top();
-    RegDecArgs ra;
-    memset(&ra, 0, sizeof ra);
+    RegDecArgs ra{};
     ra.depth = kf.fs.depth[T]; ra.sigma = kf.fs.sigma[T];
     ra.depth_top_out = kf.depth_spare;
     for (int l = 0; l < geoM.levels; l++) {
@@ -1180,10 +1154,10 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     // FrameHistory, so the reference keyframe's pose and id go along as kernel arguments.  On the one-launch schedule they are the tail
     // of k_track_persist and everything the host needs arrives in the mapped block with the tracker's tag: no further launch, no copy,
     // no stream synchronisation.  Otherwise: k_mono_decide (the batched pipeline's kernel) + one copy.
-    MonoRef hdr;
+    MonoRef hdr{};
     memcpy(hdr.ref_xi, ref.xi, sizeof hdr.ref_xi);
     hdr.ref_id = ref.id; hdr.n_total = (int)hist.size(); hdr.valid = 1;
-    memset(&trkM.mono_tail, 0, sizeof trkM.mono_tail);
+    trkM.mono_tail = {};
     if (trkM.persist_ok && !trkM.persist_failed) {
         PersistMono& pm = trkM.mono_tail;
         pm.meta = meta_dev.as<MonoSeq>();
@@ -1603,8 +1577,7 @@ int Batch::set_actions(const uint8_t* actions, bool on_device)
 int Batch::launch_plan(bool track_follows)
 {
     DVO_TRY(alloc_plan());
-    PlanArgs a;
-    memset(&a, 0, sizeof a);
+    PlanArgs a{};
     a.actions = act_pending ? act_src : nullptr;
     a.has_ref = has_ref.as<uint8_t>(); a.eff = eff.as<uint8_t>(); a.status = status.as<int>();
     a.state = trk.state.as<SeqState>(); a.log = trk.log.as<dvo_track_log>(); a.levels = g.levels;

@@ -241,7 +241,7 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     float* h_result = nullptr;   // host view: [0..5] xi, [6..21] T, [22] tag (int), [23] tag of a persistent launch that gave up
     float* d_result = nullptr;   // device view of the same memory
     int result_tag = 0;
-    PersistMono mono_tail = {};    // armed by a mono dvo_vo handle before track(): k_track_persist also does k_mono_decide's work
+    PersistMono mono_tail{};       // armed by a mono dvo_vo handle before track(): k_track_persist also does k_mono_decide's work
     int persist_ppt = 0;           // pixels per thread of the one-launch schedule: 0 = 4, > 0 = that many, < 0 = what the other schedules pick
     int enable_host_result();
     int wait_host_result(hipStream_t s, float xi[6], float T[16]);   // of the last track() call
@@ -254,6 +254,8 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int init(const Geometry& geo, int n, const dvo_config& c);
     GnParams level_params(int level) const;
     GnArgs gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const;
+    // what every solve of a level shares, for the sequences from q0 on; each schedule adds its own fields
+    SolveArgs solve_args(int level, int q0, int ignore_active) const;
     // Tracker::track (tracker.cpp:22-85): enqueue the whole coarse-to-fine loop; poses land in xi_out / T_out
     // With a plan (Batch): k_plan has done k_track_begin's work, and a level's first iteration runs the plan's sequences, not all
     int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);

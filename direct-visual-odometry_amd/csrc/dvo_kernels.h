@@ -170,7 +170,7 @@ struct PersistMono {       // optional tail of k_track_persist for a mono dvo_vo
     int* zero_word;        // the valid-update counter of the depth update that follows (cleared here)
 };
 struct PersistArgs {
-    PersistLevel lv[DVO_MAX_LEVELS];
+    PersistLevel lv[DVO_MAX_LEVELS]{};
     int levels;
     SeqState* state;       // [1]
     float* partials;       // [max nblk][32]
@@ -181,7 +181,7 @@ struct PersistArgs {
     float* xi_out; float* T_out;
     float* host_result;    // fine-grained mapped host memory: [0..5] xi, [6..21] T, [22] tag, [23] tag of a launch that gave up;
                            // with `mono`: [24..29] frame_xi, [30..45] T_world, [46] need (written before the tag)
-    PersistMono mono;
+    PersistMono mono{};
     int host_tag;          // unique per launch: also the base of this launch's epoch numbers
     int spin_limit;        // polls of the epoch word before a workgroup gives up (every wait in the kernel is bounded)
     int dbg_worker;        // which tile worker leaves the stamps (DVO_PERSIST_TIMELINE=<index>; 0 owns a corner tile of every level)

@@ -1521,7 +1521,7 @@ __global__ void __launch_bounds__(256) k_track_persist(PersistArgs p)   // expon
 #pragma unroll
             for (int i = 0; i < 3; i++) pose.t[i] = __int_as_float(__builtin_amdgcn_readfirstlane(line_s[12 + i]));
             const PersistLevel& L = p.lv[level];
-            GnArgs a;
+            GnArgs a{};
             a.obj_gray = L.obj_gray; a.ref_gray = L.ref_gray; a.ref_depth = L.ref_depth; a.ref_wgt = L.ref_wgt; a.wgt_const = L.wgt_const;
             a.state = p.state; a.partials = p.partials; a.mask = nullptr;
             a.w = L.w; a.h = L.h; a.nblk = L.nblk; a.inv_w = L.inv_w; a.q256 = L.q256; a.r256 = L.r256; a.k = L.k; a.prm = L.prm;
@@ -1594,7 +1594,7 @@ __global__ void __launch_bounds__(256) k_track_persist(PersistArgs p)   // expon
         if (threadIdx.x == 0) {
             Pose np;
             if (status == 0) {
-                SolveArgs sa;
+                SolveArgs sa{};
                 sa.state = p.state; sa.partials = p.partials; sa.log = p.log; sa.result = nullptr; sa.counters = nullptr;
                 sa.nblk = L.nblk; sa.level = level; sa.level_pixels = L.level_pixels;
                 sa.max_iterations = p.max_iterations; sa.fixed_iterations = p.fixed_iterations;

@@ -827,8 +827,8 @@ __global__ void __launch_bounds__(256) k_broadcast(const float* __restrict__ src
 void launch_mono_decide(MonoSeq* meta, const SeqState* state, int n_seq, int frame_id, float min_translation, int max_frames,
                         float* xi_world, float* T_world, int* is_key, const MonoRef* host_ref, hipStream_t s, int* need_list)
 {
-    MonoRef r;
-    if (host_ref) r = *host_ref; else { for (int i = 0; i < 6; i++) r.ref_xi[i] = 0.0f; r.ref_id = 0; r.n_total = 0; r.valid = 0; }
+    MonoRef r{};
+    if (host_ref) r = *host_ref;
     hipLaunchKernelGGL(k_mono_decide, dim3(cdiv_u(n_seq, 64)), dim3(64), 0, s, meta, state, n_seq, frame_id, min_translation, max_frames,
                        xi_world, T_world, is_key, r, need_list);
 }
@@ -880,10 +880,10 @@ void launch_propagate_batch(const PropArgs& a0, hipStream_t s)
 void launch_propagate(const float* ref_depth, const float* ref_sigma, const float* ref_age, int w, int h, const Intr& k,
                       const Pose& pose, float tz, int* owner, float* depth, float* sigma, float* age, hipStream_t s)
 {
-    PropArgs a;
+    PropArgs a{};
     a.ref_depth = ref_depth; a.ref_sigma = ref_sigma; a.ref_age = ref_age;
     a.depth = depth; a.sigma = sigma; a.age = age; a.owner = owner;
-    a.w = w; a.h = h; a.n_seq = 1; a.k = k; a.meta = nullptr; a.pose = pose; a.tz = tz;
+    a.w = w; a.h = h; a.n_seq = 1; a.k = k; a.pose = pose; a.tz = tz;
     launch_propagate_batch(a, s);
 }
 

@@ -249,8 +249,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         const size_t set = (size_t)trk.n_sub * (size_t)(n_seq + 4);
         pa.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
         pa.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
-        pa.list_stride = n_seq + 4; pa.n_sub = trk.n_sub; pa.n_seq = n_seq;
-        pa.cam_changed = nullptr;                // (K and D are fixed for the life of the handle)
+        pa.list_stride = n_seq + 4; pa.n_sub = trk.n_sub; pa.n_seq = n_seq;   // (no cam_changed: K and D are fixed for the life of the handle)
         if (trk.adaptive && frame_id > 0) {      // Tracker::track waits for this word (the one of this parity was last used two plans ago)
             h_ready[plan_parity] = 0;
             pa.ready = d_ready + plan_parity;
@@ -275,9 +274,8 @@ int MonoBatch::odometrize(const FrameInput& in)
         build_pyramid(ref, gin, stream);
         DVO_HIP(hipMemsetAsync(ref_age.p, 0, ref_age.bytes, stream));
         redecimate(ref, ref.depth[T], ref.sigma[T], stream);
-        PromoteArgs pa;
-        memset(&pa, 0, sizeof pa);
-        pa.n_seg = 0; pa.n_seq = n_seq; pa.gray_top = ref.gray[T]; pa.ring_gray = ring_gray.as<float>(); pa.npix = np; pa.R = R;
+        PromoteArgs pa{};
+        pa.n_seq = n_seq; pa.gray_top = ref.gray[T]; pa.ring_gray = ring_gray.as<float>(); pa.npix = np; pa.R = R;
         pa.meta = m; pa.all = 1;
         launch_promote(pa, stream);
         launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 1, frame_id, xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), stream);
@@ -337,12 +335,11 @@ int MonoBatch::odometrize(const FrameInput& in)
     }
     // ---- Mapper::estimate (mapper.cpp:16-33), both branches launched, each sequence takes its own ----
     {   // need: propagate the reference maps into the frame (mapper.cpp:62-74) ...
-        PropArgs a;
+        PropArgs a{};
         a.ref_depth = ref.depth[T]; a.ref_sigma = ref.sigma[T]; a.ref_age = ref_age.as<float>();
         a.depth = frm.depth[T]; a.sigma = frm.sigma[T]; a.age = frm_age.as<float>();
         a.owner = owner.as<int>();
         a.w = tw; a.h = th; a.n_seq = n_seq; a.k = g.k[T]; a.meta = m;
-        memset(&a.pose, 0, sizeof a.pose); a.tz = 0.0f;
         a.need_list = need_list.as<int>();
         a.seq_k = cam_top();   // (per-camera batch: k_propagate_owner_cam)
         if (pe) DVO_HIP(hipEventRecord(pe->e[0], stream));
@@ -350,17 +347,16 @@ int MonoBatch::odometrize(const FrameInput& in)
         if (pe) DVO_HIP(hipEventRecord(pe->e[1], stream));
     }
     {   // !need: stereo update of the reference maps against the keyframe each pixel was born in (mapper.cpp:76-137)
-        AgeTableArgs ta;
+        AgeTableArgs ta{};
         ta.meta = m; ta.hist_xi = hist_xi.as<float>(); ta.ages = ages.as<AgeEntry>(); ta.n_seq = n_seq; ta.R = R; ta.n_hist = -1;
         if (pe) DVO_HIP(hipEventRecord(pe->e[2], stream));
         launch_age_table(ta, stream);
-        UpdateArgs a;
-        memset(&a, 0, sizeof a);
+        UpdateArgs a{};
         a.ref_depth = ref.depth[T]; a.ref_sigma = ref.sigma[T]; a.ref_age = ref_age.as<float>();
         a.obj_gray = frm.gray[T];
         a.ages = ages.as<AgeEntry>();
-        a.ring_gray = ring_gray.as<float>(); a.gray_table = nullptr; a.meta = m;
-        a.n_seq = n_seq; a.R = R; a.n_hist = 0; a.w = tw; a.h = th; a.crop = cfg.crop_enable; a.obj_id = frame_id;
+        a.ring_gray = ring_gray.as<float>(); a.meta = m;
+        a.n_seq = n_seq; a.R = R; a.w = tw; a.h = th; a.crop = cfg.crop_enable; a.obj_id = frame_id;
         a.clamp_age = 1;
         a.seed = cfg.rng_seed;
         a.k = g.k[T];
@@ -370,15 +366,14 @@ int MonoBatch::odometrize(const FrameInput& in)
         if (pe) DVO_HIP(hipEventRecord(pe->e[3], stream));
     }
     {   // ... need: the frame becomes the newest keyframe (FrameHistory::push, frame.hpp:151-157)
-        PromoteArgs pa;
-        memset(&pa, 0, sizeof pa);
+        PromoteArgs pa{};
         int sgi = 0;
         for (int l = 0; l < g.levels; l++) { pa.src[sgi] = frm.gray[l]; pa.dst[sgi] = ref.gray[l]; pa.count[sgi] = g.w[l] * g.h[l]; sgi++; }
         pa.src[sgi] = frm.depth[T]; pa.dst[sgi] = ref.depth[T]; pa.count[sgi] = np; sgi++;
         pa.src[sgi] = frm.sigma[T]; pa.dst[sgi] = ref.sigma[T]; pa.count[sgi] = np; sgi++;
         pa.src[sgi] = frm_age.as<float>(); pa.dst[sgi] = ref_age.as<float>(); pa.count[sgi] = np; sgi++;
         pa.n_seg = sgi; pa.n_seq = n_seq; pa.gray_top = frm.gray[T]; pa.ring_gray = ring_gray.as<float>(); pa.npix = np; pa.R = R;
-        pa.meta = m; pa.all = 0;
+        pa.meta = m;
         pa.need_list = need_list.as<int>();
         launch_promote(pa, stream);
         if (!planned) launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 0, frame_id, nullptr, nullptr, nullptr, stream);
@@ -387,8 +382,7 @@ int MonoBatch::odometrize(const FrameInput& in)
     // every level of depth and sigma is a decimation of the top maps, so ONE pass re-derives both pyramids (and the
     // weight) from the regularized depth and the current sigma -- the same values the reference's two re-decimations leave.
     {
-        RegDecArgs ra;
-        memset(&ra, 0, sizeof ra);
+        RegDecArgs ra{};
         ra.depth = ref.depth[T]; ra.sigma = ref.sigma[T];
         if (!depth_alt) depth_alt = tmp.as<float>();
         ra.depth_top_out = depth_alt;
