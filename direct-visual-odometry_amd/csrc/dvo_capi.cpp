@@ -378,6 +378,13 @@ int dvo_batch_set_pose_guess_mode(dvo_batch* b, int mode)
     return b->mono ? b->mono->set_guess_mode(mode) : b->impl.set_guess_mode(mode);
 }
 
+int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_keyframe_tracking: needs a sensor-depth batch (a mono batch always tracks against keyframes)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->impl.set_keyframe_tracking(enable);
+}
+
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
@@ -513,10 +520,12 @@ int dvo_batch_probe_gn(dvo_batch* b, int level, int n_launches, float* avg_ms, u
     DVO_NOT_MONO(b);
     Batch& B = b->impl;
     if (level < 0 || level >= B.g.levels) return DVO_ERR_BAD_ARGUMENT;
-    if (B.cur < 0 || !B.have_poses) return DVO_ERR_NOT_READY;
+    if (B.cur < 0 || B.prev < 0 || !B.have_poses) return DVO_ERR_NOT_READY;
     DVO_TRY(select_device(B.device));
-    // obj = the newest frame set, ref = the one before it: exactly the operands of the last track() call
-    const GnArgs ga = B.trk.gn_args(B.fs[B.cur], B.fs[B.prev], level, nullptr, 1);
+    // exactly the operands of the last track() call: obj = the newest frame set, ref = the one before it (keyframe tracking: obj = the
+    // last frame's set, prev, and ref = the keyframe set, cur)
+    const int obj = B.kf_on ? B.prev : B.cur, ref = B.kf_on ? B.cur : B.prev;
+    const GnArgs ga = B.trk.gn_args(B.fs[obj], B.fs[ref], level, nullptr, 1);
     hipEvent_t e0, e1;
     DVO_HIP(hipEventCreate(&e0));
     DVO_HIP(hipEventCreate(&e1));

@@ -1383,6 +1383,10 @@ int Batch::check_actions_input(const FrameInput& in) const
         set_error("dvo_batch_set_actions: a push with actions must keep the weight storage of the references (raw frames vs float maps)");
         return DVO_ERR_BAD_ARGUMENT;
     }
+    if (kf_on && cur >= 0 && weights_by_validity(fs[cur], in) != fs[cur].sigma_by_validity) {   // (a promotion copies the weight storage)
+        set_error("dvo_batch_set_keyframe_tracking: every push must keep the weight storage of the keyframes (raw frames vs float maps)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     return DVO_OK;
 }
 
@@ -1438,6 +1442,7 @@ int Batch::prefetch(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
     if (act_pending) { set_error("dvo_batch_prefetch: actions are pending for the next push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
+    if (kf_on) { set_error("dvo_batch_prefetch: keyframe tracking is on (prefetch and keyframe tracking do not combine)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
     const int slot = free_slot();
     if (npre >= 2 || slot < 0) { set_error("dvo_batch_prefetch_device: two prefetched frames are already waiting for their push"); return DVO_ERR_NOT_READY; }
@@ -1457,8 +1462,9 @@ int Batch::push(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(device));
-    // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan), or per-sequence intrinsics
-    const bool planned = act_pending || act_used || cam_used;
+    // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan), or per-sequence intrinsics,
+    // or keyframe tracking
+    const bool planned = act_pending || act_used || cam_used || kf_on;
     DVO_TRY(check_actions_input(in));
     if (und.enabled() && in.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
     FrameInput fin = in;
@@ -1502,7 +1508,7 @@ int Batch::push(const FrameInput& in)
             tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
             tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
             tp.seq_k = cam_table();
-            if (guess.on()) { sa = guess.args(trk.state.as<SeqState>(), eff.as<uint8_t>(), 0, trk.xi_out.as<float>(), nullptr); trk.seed = &sa; }
+            if (guess.on()) { sa = guess_args(eff.as<uint8_t>(), 0); trk.seed = &sa; }
             const int rc = trk.track(fs[target], fs[cur], stream, &tp);
             trk.seed = nullptr;
             DVO_TRY(rc);
@@ -1512,6 +1518,7 @@ int Batch::push(const FrameInput& in)
             seed_untracked(eff.as<uint8_t>(), 0);
             launch_export_poses(trk.state.as<SeqState>(), trk.xi_out.as<float>(), trk.T_out.as<float>(), n_seq, stream);
         }
+        if (kf_on) DVO_TRY(update_keyframes(target));
         have_poses = true;
         act_pending = false;
         act_used = true;
@@ -1521,8 +1528,12 @@ int Batch::push(const FrameInput& in)
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
     guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
     n_push++;
-    prev = cur;
-    cur = target;                                           // system.hpp:91
+    if (!kf_on || cur < 0) {
+        prev = cur;
+        cur = target;                                       // system.hpp:91
+    } else {                                                // keyframe tracking: the first push's set stays the keyframe set
+        prev = target;                                      // (the last frame's set: dvo_batch_probe_gn's obj)
+    }
     DVO_HIP(hipGetLastError());
     return DVO_OK;
 }
@@ -1762,11 +1773,79 @@ int Batch::set_guess_mode(int m)
     return guess.set_mode(m, n_seq, stream, pe, all);
 }
 
+PoseSeedArgs Batch::guess_args(const uint8_t* eff_dev, int all_eff)
+{
+    if (kf_on) return guess.args(trk.state.as<SeqState>(), eff_dev, all_eff, xi_world.as<float>(), kf_meta.as<MonoSeq>());
+    return guess.args(trk.state.as<SeqState>(), eff_dev, all_eff, trk.xi_out.as<float>(), nullptr);
+}
+
 void Batch::seed_untracked(const uint8_t* eff_dev, int all_eff)
 {
     if (!guess.on()) return;
-    const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), eff_dev, all_eff, trk.xi_out.as<float>(), nullptr);
-    launch_seed_pose(sa, stream);
+    const PoseSeedArgs sa = guess_args(eff_dev, all_eff);
+    if (kf_on) launch_mono_seed(sa, stream);
+    else launch_seed_pose(sa, stream);
+}
+
+// ------------------------------------------------------------------------------------------------ batch: keyframe tracking
+int Batch::set_keyframe_tracking(int enable)
+{
+    if (n_push > 0) { set_error("dvo_batch_set_keyframe_tracking: the tracking mode is chosen before the first push"); return DVO_ERR_NOT_READY; }
+    if (enable && npre > 0) {
+        set_error("dvo_batch_set_keyframe_tracking: a prefetched frame is waiting for its push (prefetch and keyframe tracking do not combine)");
+        return DVO_ERR_NOT_READY;
+    }
+    if (enable && !kf_meta.p) {
+        DVO_TRY(select_device(device));
+        const size_t n = (size_t)n_seq;
+        DVO_TRY(kf_meta.alloc(sizeof(MonoSeq) * n));
+        DVO_TRY(xi_world.alloc(sizeof(float) * 6 * n));
+        DVO_TRY(T_world.alloc(sizeof(float) * 16 * n));
+        DVO_TRY(is_key.alloc(sizeof(int) * n));
+        DVO_TRY(need_list.alloc(sizeof(int) * (n + 4)));
+        DVO_HIP(hipMemsetAsync(kf_meta.p, 0, kf_meta.bytes, stream));   // n_total = 0: no sequence has started
+    }
+    kf_on = enable != 0;
+    trk.seed_mono = kf_on;   // (a start pose is a world twist, as in a mono batch: k_mono_seed over kf_meta)
+    return DVO_OK;
+}
+
+// After the tracking of a push: the keyframe rule of every TRACK sequence and the starts (k_kf_decide), then the frames of the sequences it
+// listed -- gray, depth and (where the set stores them) wgt of every level -- over their keyframes in fs[cur] (k_promote: no ring, only
+// the listed sequences; at most DVO_PROMOTE_MAX_SEG maps per launch).  SKIP sequences are not listed: their keyframes are not written.
+int Batch::update_keyframes(int frame_set)
+{
+    const int kf = cur >= 0 ? cur : frame_set;   // (the first push: its set becomes the keyframe set, nothing to copy)
+    DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
+    MonoPlanArgs ma{};
+    ma.meta = kf_meta.as<MonoSeq>(); ma.state = trk.state.as<SeqState>(); ma.eff = eff.as<uint8_t>();
+    ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
+    ma.n_seq = n_seq; ma.R = 1; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
+    launch_kf_decide(ma, stream);
+    if (frame_set == kf) return DVO_OK;
+    const FrameSet& src = fs[frame_set];
+    FrameSet& dst = fs[kf];
+    const float* from[3 * DVO_MAX_LEVELS];
+    float* to[3 * DVO_MAX_LEVELS];
+    int count[3 * DVO_MAX_LEVELS];
+    int n = 0;
+    for (int m = 0; m < 3; m++) {
+        if (m == 2 && dst.sigma_by_validity) break;   // (raw frames with constant weights: no wgt maps)
+        for (int l = 0; l < g.levels; l++, n++) {
+            from[n] = m == 0 ? src.gray[l] : m == 1 ? src.depth[l] : src.wgt[l];
+            to[n] = m == 0 ? dst.gray[l] : m == 1 ? dst.depth[l] : dst.wgt[l];
+            count[n] = g.w[l] * g.h[l];
+        }
+    }
+    for (int first = 0; first < n; first += DVO_PROMOTE_MAX_SEG) {
+        PromoteArgs pa{};
+        pa.n_seg = n - first < DVO_PROMOTE_MAX_SEG ? n - first : DVO_PROMOTE_MAX_SEG;
+        for (int k = 0; k < pa.n_seg; k++) { pa.src[k] = from[first + k]; pa.dst[k] = to[first + k]; pa.count[k] = count[first + k]; }
+        pa.n_seq = n_seq; pa.npix = 0; pa.R = 1;
+        pa.meta = kf_meta.as<MonoSeq>(); pa.all = 0; pa.need_list = need_list.as<int>();
+        launch_promote(pa, stream);
+    }
+    return DVO_OK;
 }
 
 }  // namespace dvo

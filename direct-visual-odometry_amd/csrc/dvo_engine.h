@@ -341,7 +341,7 @@ struct VisualOdometry {  // System::VisualOdometry, system.hpp:12-104
     int map_regularize(Keyframe& kf);
 };
 
-struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sensor depth
+struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tracking with sensor depth
     int n_seq = 0, device = 0;
     dvo_config cfg;
     hipStream_t stream = nullptr;
@@ -425,7 +425,17 @@ struct Batch {  // n_seq independent sequences, frame-to-frame tracking with sen
     int set_guess_mode(int mode);
     // the seed of this push outside track() (a push that tracks nothing still folds into the history)
     void seed_untracked(const uint8_t* eff_dev, int all_eff);
+    PoseSeedArgs guess_args(const uint8_t* eff_dev, int all_eff);   // (keyframe tracking: world twists and the keyframe twists, k_mono_seed)
     const uint8_t* cam_changed() const { return reinterpret_cast<const uint8_t*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq); }
+    // Keyframe tracking (dvo_batch_set_keyframe_tracking): every push runs the per-sequence path; the first push's frame
+    // set (cur) is the keyframe set and is never rotated away, later frames are built into another set and tracked against it.  After
+    // the tracking, k_kf_decide takes the mono rule (mono_decide_one) per sequence and k_promote copies the frames of the sequences
+    // whose rule fired, and of the starts, over their keyframes.  Chosen before the first push; a batch that never sets it runs the
+    // launches it always ran.
+    bool kf_on = false;
+    DevBuf kf_meta, xi_world, T_world, is_key, need_list;   // MonoSeq [n_seq]; [n_seq][6], [n_seq][16], [n_seq]; [4 + n_seq]
+    int set_keyframe_tracking(int enable);
+    int update_keyframes(int frame_set);                     // k_kf_decide, then k_promote from fs[frame_set] into fs[cur]
 };
 
 int select_device(int device);

@@ -420,6 +420,10 @@ struct MonoPlanArgs {   // k_mono_decide_plan, k_mono_commit_plan
 };
 void launch_mono_decide_plan(const MonoPlanArgs& a, hipStream_t s);
 void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s);
+// k_kf_decide: both of them for a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_tracking): meta, state, eff,
+// xi_world, T_world, is_key, need_list (TRACK sequences whose rule fired, and the starts), n_seq, max_frames, min_translation
+// (started, need_save, hist_xi and R are not used: a sequence has started once MonoSeq::n_total > 0)
+void launch_kf_decide(const MonoPlanArgs& a, hipStream_t s);
 // k_regularize_redecimate_plan: k_regularize_redecimate for the TRACK sequences; a SKIP sequence copies its top-level depth forward to
 // depth_top_out (nothing else is written); a RESTART sequence starts: its keyframe becomes the frame's gray pyramid (ring slot 0 too),
 // the start map's depth and sigma with every level re-decimated and the weights, age 0 (the first frame of system.hpp:49-54).

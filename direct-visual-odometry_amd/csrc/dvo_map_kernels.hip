@@ -150,6 +150,50 @@ __global__ void __launch_bounds__(64) k_mono_commit_plan(MonoPlanArgs a)
     m.n_total += 1;
 }
 
+// k_kf_decide: the keyframe bookkeeping of a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_tracking, DESIGN.md
+// §19), after the push's tracking.  TRACK is k_mono_decide_plan's TRACK branch (mono_decide_one with the sequence's next frame id)
+// followed, when the rule fires, by k_mono_commit_plan's keyframe branch; RESTART is k_mono_commit_plan's start branch.  Both enter
+// need_list, whose frames k_promote then copies over the keyframe set.  SKIP changes nothing: its world pose stays (identity while the
+// sequence has never started, n_total = 0), is_keyframe = 0.  There is no ring and nothing between this kernel and the copy reads
+// MonoSeq, so decide and commit are one launch (no need_save, no started array).
+__global__ void __launch_bounds__(64) k_kf_decide(MonoPlanArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    MonoSeq& m = a.meta[s];
+    const int eff = a.eff[s];
+    if (eff == DVO_SEQ_TRACK) {
+        float rel[6], fx[6], T[16];
+        for (int i = 0; i < 6; i++) rel[i] = a.state[s].xi[i];
+        const int fid = m.frame_id + 1;
+        const int need = mono_decide_one(m, rel, fid, a.min_translation, a.max_frames, fx, T);
+        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = fx[i];
+        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = T[i];
+        a.is_key[s] = need;
+        if (!need) return;
+        for (int i = 0; i < 6; i++) m.ref_xi[i] = m.frame_xi[i];   // k_mono_commit_plan's keyframe branch
+        m.ref_id = m.frame_id;
+        m.n_total += 1;
+    } else if (eff == DVO_SEQ_RESTART) {   // k_mono_commit_plan's start branch: frame 0 of the sequence, its counters reset
+        for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
+        for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+        for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
+        for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        m.ref_id = 0; m.frame_id = 0; m.n_total = 1; m.need = 1; m.valid_updates = 0; m.clamped = 0;
+        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
+        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = m.T_world[i];
+        a.is_key[s] = 1;
+    } else {
+        a.is_key[s] = 0;
+        if (m.n_total == 0) {
+            for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
+            for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = (i % 5 == 0) ? 1.0f : 0.0f;
+        }
+        return;
+    }
+    a.need_list[4 + atomicAdd(&a.need_list[0], 1)] = s;   // (the order of the list changes no result: sequences are independent)
+}
+
 // k_mono_seed: the start pose of a mono call (dvo_batch_set_pose_guess_mode), after k_track_begin / k_plan.  History: the world
 // twists w1 (newest), w2 returned for the sequence's last two calls that tracked or started it since its last start.  A guess g in
 // world coordinates becomes the tracker's relative start concatenate(-ref_xi, g) against the sequence's current keyframe.
@@ -908,6 +952,11 @@ void launch_mono_decide_plan(const MonoPlanArgs& a, hipStream_t s)
 void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_mono_commit_plan, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_kf_decide(const MonoPlanArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kf_decide, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
 }
 
 void launch_mono_seed(const PoseSeedArgs& a, hipStream_t s)

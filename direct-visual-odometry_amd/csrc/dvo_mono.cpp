@@ -622,34 +622,85 @@ int dvo_batch_get_distortion(dvo_batch* b, float* D, int* enabled)
     return DVO_OK;
 }
 
+// The world poses of a batch: a mono batch's, or a sensor-depth batch's with keyframe tracking (dvo_batch_set_keyframe_tracking).  A plain
+// sensor-depth batch has none.
+namespace {
+struct WorldPoses {
+    const void* xi; const void* T; const void* key;
+    size_t n; hipStream_t s; int device; bool ready;
+};
+}  // namespace
+static int world_poses_of(dvo_batch* b, WorldPoses& w)
+{
+    if (b && b->mono) {
+        const MonoBatch& M = *b->mono;
+        w = {M.xi_world.p, M.T_world.p, M.is_key.p, (size_t)M.n_seq, M.stream, M.device, M.latest_id >= 0};
+        return DVO_OK;
+    }
+    if (b && b->impl.kf_on) {
+        const Batch& B = b->impl;
+        w = {B.xi_world.p, B.T_world.p, B.is_key.p, (size_t)B.n_seq, B.stream, B.device, B.n_push > 0};
+        return DVO_OK;
+    }
+    set_error("this entry point needs a mono batch (dvo_batch_create_mono) or a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_tracking)");
+    return DVO_ERR_BAD_ARGUMENT;
+}
+
 int dvo_batch_world_poses(dvo_batch* b, float* xi_world, float* T_world, int* is_keyframe)
 {
-    DVO_NEED_MONO(b);
-    MonoBatch& M = *b->mono;
-    if (M.latest_id < 0) return DVO_ERR_NOT_READY;
-    DVO_TRY(select_device(M.device));
-    if (xi_world) DVO_HIP(hipMemcpyAsync(xi_world, M.xi_world.p, sizeof(float) * 6 * (size_t)M.n_seq, hipMemcpyDeviceToHost, M.stream));
-    if (T_world) DVO_HIP(hipMemcpyAsync(T_world, M.T_world.p, sizeof(float) * 16 * (size_t)M.n_seq, hipMemcpyDeviceToHost, M.stream));
-    if (is_keyframe) DVO_HIP(hipMemcpyAsync(is_keyframe, M.is_key.p, sizeof(int) * (size_t)M.n_seq, hipMemcpyDeviceToHost, M.stream));
-    DVO_HIP(hipStreamSynchronize(M.stream));
+    WorldPoses w;
+    DVO_TRY(world_poses_of(b, w));
+    if (!w.ready) return DVO_ERR_NOT_READY;
+    DVO_TRY(select_device(w.device));
+    if (xi_world) DVO_HIP(hipMemcpyAsync(xi_world, w.xi, sizeof(float) * 6 * w.n, hipMemcpyDeviceToHost, w.s));
+    if (T_world) DVO_HIP(hipMemcpyAsync(T_world, w.T, sizeof(float) * 16 * w.n, hipMemcpyDeviceToHost, w.s));
+    if (is_keyframe) DVO_HIP(hipMemcpyAsync(is_keyframe, w.key, sizeof(int) * w.n, hipMemcpyDeviceToHost, w.s));
+    DVO_HIP(hipStreamSynchronize(w.s));
     return DVO_OK;
 }
 
 int dvo_batch_copy_world_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_dev, int* key_dst_dev)
 {
-    DVO_NEED_MONO(b);
-    MonoBatch& M = *b->mono;
-    if (M.latest_id < 0) return DVO_ERR_NOT_READY;
-    DVO_TRY(select_device(M.device));
-    if (xi_dst_dev) DVO_HIP(hipMemcpyAsync(xi_dst_dev, M.xi_world.p, sizeof(float) * 6 * (size_t)M.n_seq, hipMemcpyDeviceToDevice, M.stream));
-    if (T_dst_dev) DVO_HIP(hipMemcpyAsync(T_dst_dev, M.T_world.p, sizeof(float) * 16 * (size_t)M.n_seq, hipMemcpyDeviceToDevice, M.stream));
-    if (key_dst_dev) DVO_HIP(hipMemcpyAsync(key_dst_dev, M.is_key.p, sizeof(int) * (size_t)M.n_seq, hipMemcpyDeviceToDevice, M.stream));
+    WorldPoses w;
+    DVO_TRY(world_poses_of(b, w));
+    if (!w.ready) return DVO_ERR_NOT_READY;
+    DVO_TRY(select_device(w.device));
+    if (xi_dst_dev) DVO_HIP(hipMemcpyAsync(xi_dst_dev, w.xi, sizeof(float) * 6 * w.n, hipMemcpyDeviceToDevice, w.s));
+    if (T_dst_dev) DVO_HIP(hipMemcpyAsync(T_dst_dev, w.T, sizeof(float) * 16 * w.n, hipMemcpyDeviceToDevice, w.s));
+    if (key_dst_dev) DVO_HIP(hipMemcpyAsync(key_dst_dev, w.key, sizeof(int) * w.n, hipMemcpyDeviceToDevice, w.s));
+    return DVO_OK;
+}
+
+// the keyframe of a sensor-depth batch with keyframe tracking: gray / depth of one level of the keyframe set, its twist, id and count
+static int sensor_keyframe_get(Batch& B, int seq, int level, float* gray, float* depth, float* sigma, float* age, float xi[6], int* id,
+                               int* n_keyframes, int* valid_updates)
+{
+    if (seq < 0 || seq >= B.n_seq || level < 0 || level >= B.g.levels) return DVO_ERR_BAD_ARGUMENT;
+    if (sigma || age) {
+        set_error("dvo_batch_keyframe_get: a sensor-depth batch stores no sigma or age maps of its keyframes (pass NULL)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (B.n_push == 0) return DVO_ERR_NOT_READY;
+    DVO_TRY(select_device(B.device));
+    MonoSeq m;
+    DVO_HIP(hipMemcpyAsync(&m, B.kf_meta.as<MonoSeq>() + seq, sizeof m, hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    if (m.n_total == 0) { set_error("dvo_batch_keyframe_get: the sequence has not started (it was skipped on every push so far)"); return DVO_ERR_NOT_READY; }
+    const size_t n = (size_t)B.g.w[level] * B.g.h[level], off = n * (size_t)seq;
+    if (gray) DVO_HIP(hipMemcpyAsync(gray, B.fs[B.cur].gray[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    if (depth) DVO_HIP(hipMemcpyAsync(depth, B.fs[B.cur].depth[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    if (xi) memcpy(xi, m.ref_xi, 6 * sizeof(float));
+    if (id) *id = m.ref_id;
+    if (n_keyframes) *n_keyframes = m.n_total;
+    if (valid_updates) *valid_updates = 0;
     return DVO_OK;
 }
 
 int dvo_batch_keyframe_get(dvo_batch* b, int seq, int level, float* gray, float* depth, float* sigma, float* age, float xi[6], int* id,
                            int* n_keyframes, int* valid_updates)
 {
+    if (b && !b->mono && b->impl.kf_on) return sensor_keyframe_get(b->impl, seq, level, gray, depth, sigma, age, xi, id, n_keyframes, valid_updates);
     DVO_NEED_MONO(b);
     MonoBatch& M = *b->mono;
     if (seq < 0 || seq >= M.n_seq || level < 0 || level >= M.g.levels) return DVO_ERR_BAD_ARGUMENT;

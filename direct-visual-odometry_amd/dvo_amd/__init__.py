@@ -104,6 +104,7 @@ EXPORTS = [
     "dvo_batch_set_mono_actions", "dvo_batch_mono_last_status", "dvo_batch_copy_mono_status_device",
     "dvo_batch_set_mono_start_depth_device",
     "dvo_batch_set_pose_guess_mode", "dvo_batch_set_pose_guess", "dvo_batch_last_start_poses",
+    "dvo_batch_set_keyframe_tracking",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -563,8 +564,20 @@ class _PoseGuess:
         return xi
 
 
+class _WorldPoses:
+    """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
+
+    def world_poses(self):
+        xi = np.zeros((self.n_seq, 6), np.float32); T = np.zeros((self.n_seq, 16), np.float32); key = np.zeros(self.n_seq, np.int32)
+        _check(lib().dvo_batch_world_poses(self._p, fp(xi), fp(T), key.ctypes.data_as(C.c_void_p)))
+        return xi, T.reshape(self.n_seq, 4, 4), key.astype(bool)
+
+    def copy_world_poses_device(self, xi_ptr=0, T_ptr=0, key_ptr=0):
+        _check(lib().dvo_batch_copy_world_poses_device(self._p, C.c_void_p(xi_ptr or None), C.c_void_p(T_ptr or None), C.c_void_p(key_ptr or None)))
+
+
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess):
+class Batch(_PoseGuess, _WorldPoses):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -681,6 +694,24 @@ class Batch(_PoseGuess):
         """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""
         _check(lib().dvo_batch_copy_status_device(self._p, C.c_void_p(int(ptr))))
 
+    def set_keyframe_tracking(self, enable=True):
+        """Track every frame against its sequence's keyframe (the mono rule decides when it is replaced) instead of the previous frame;
+        before the first push (dvo_batch_set_keyframe_tracking).  world_poses(), copy_world_poses_device() and keyframe() then work."""
+        _check(lib().dvo_batch_set_keyframe_tracking(self._p, 1 if enable else 0))
+
+    def keyframe(self, seq, level=None):
+        """The keyframe of sequence `seq` (keyframe tracking): gray and depth of `level` (default: the finest), its world twist, id and the
+        number of keyframes the sequence has created."""
+        level = self.levels - 1 if level is None else level
+        if not 0 <= level < self.levels:
+            raise ValueError("keyframe: level %d is outside [0, %d)" % (level, self.levels))
+        shift = self.culls + (self.levels - 1 - level)
+        sh = (self.height >> shift, self.width >> shift)
+        g = np.zeros(sh, np.float32); d = np.zeros(sh, np.float32)
+        xi = np.zeros(6, np.float32); i = C.c_int(); n = C.c_int(); v = C.c_int()
+        _check(lib().dvo_batch_keyframe_get(self._p, seq, level, fp(g), fp(d), None, None, fp(xi), C.byref(i), C.byref(n), C.byref(v)))
+        return dict(gray=g, depth=d, xi=xi, id=i.value, n_keyframes=n.value)
+
     def synchronize(self):
         _check(lib().dvo_batch_synchronize(self._p))
 
@@ -695,7 +726,7 @@ class Batch(_PoseGuess):
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess):
+class MonoBatch(_PoseGuess, _WorldPoses):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 
@@ -797,14 +828,6 @@ class MonoBatch(_PoseGuess):
         (dvo_batch_set_mono_start_depth_device)."""
         _check(lib().dvo_batch_set_mono_start_depth_device(self._p, C.c_void_p(int(depth_ptr) if depth_ptr else None),
                                                             C.c_void_p(int(sigma_ptr) if sigma_ptr else None)))
-
-    def world_poses(self):
-        xi = np.zeros((self.n_seq, 6), np.float32); T = np.zeros((self.n_seq, 16), np.float32); key = np.zeros(self.n_seq, np.int32)
-        _check(lib().dvo_batch_world_poses(self._p, fp(xi), fp(T), key.ctypes.data_as(C.c_void_p)))
-        return xi, T.reshape(self.n_seq, 4, 4), key.astype(bool)
-
-    def copy_world_poses_device(self, xi_ptr=0, T_ptr=0, key_ptr=0):
-        _check(lib().dvo_batch_copy_world_poses_device(self._p, C.c_void_p(xi_ptr or None), C.c_void_p(T_ptr or None), C.c_void_p(key_ptr or None)))
 
     def keyframe(self, seq, level=2):
         sh = ((self.height // 4) >> (2 - level), (self.width // 4) >> (2 - level))

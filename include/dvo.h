@@ -306,7 +306,8 @@ int dvo_batch_odometrize_raw_device(dvo_batch* b, const uint8_t* rgb_dev, int ch
 int dvo_batch_odometrize_host(dvo_batch* b, const float* gray);
 int dvo_batch_odometrize_raw_host(dvo_batch* b, const uint8_t* rgb, int channels);
 /* world twists [n_seq][6], world poses exp(xi) [n_seq][16] (system.hpp:73) and keyframe flags [n_seq] of the last frame
- * (synchronises); any pointer may be NULL.  _device: asynchronous device-to-device copies on the handle's stream. */
+ * (synchronises); any pointer may be NULL.  _device: asynchronous device-to-device copies on the handle's stream.  These two and
+ * dvo_batch_keyframe_get also serve a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_tracking, below). */
 int dvo_batch_world_poses(dvo_batch* b, float* xi_world, float* T_world, int* is_keyframe);
 int dvo_batch_copy_world_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_dev, int* key_dst_dev);
 /* the newest keyframe of sequence `seq` (FrameHistory::getRefFrame, frame.hpp:159-166): maps of one pyramid level (age: top level
@@ -407,6 +408,34 @@ int dvo_batch_set_mono_start_depth_device(dvo_batch* b, const float* depth_dev, 
 int dvo_batch_set_pose_guess_mode(dvo_batch* b, int mode);
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device);
 int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start);
+/* ---- keyframe tracking of a sensor-depth batch --------------------------------------------------------------------------------
+ * A sensor-depth batch tracks frame to frame (odometrizeUsingDepth, system.hpp:77-93): every frame's tracking error stays in the
+ * trajectory.  dvo_batch_set_keyframe_tracking(b, 1) makes it track each frame against a retained KEYFRAME of its sequence instead,
+ * replaced only when the mono rule fires (Mapper::needNewFrame, mapper.cpp:45-60: |t| of the twist against the keyframe >
+ * cfg.keyframe_min_translation, or cfg.keyframe_max_frames frames since it), decided per sequence on the device with the mono batch's
+ * own function (the same bits).  enable = 0 puts the handle back on frame-to-frame tracking.  Per sequence and push:
+ *   start    (the first push, RESTART, TRACK without a keyframe, a change of K or D: as dvo_batch_set_actions resolves them) the frame
+ *            becomes the keyframe; world pose identity, frame counter 0, is_keyframe = 1; status DVO_SEQ_STARTED.
+ *   TRACK    the frame is tracked against the keyframe (from zero or the pose guess).  Frame id = the previous one + 1 (skipped pushes
+ *            do not count); world twist = se3_concatenate(keyframe twist, relative twist), as the mono batch (frame.cpp:7-14);
+ *            is_keyframe = the rule, and when it fires the frame's pyramid (gray, depth and, where stored, the weight maps of every
+ *            level) replaces the keyframe, whose twist and id become the frame's.
+ *   SKIP     the input is not read; keyframe, its pose and the frame counter stay; the world pose is kept (identity if the sequence
+ *            never started); is_keyframe = 0.
+ * Outputs: dvo_batch_last_poses / _copy_poses_device keep their convention (exp(xi) = inv(P_obj) P_ref) with the KEYFRAME as the
+ * reference; dvo_batch_last_status, _last_track_log and _gather_poses_rccl keep their meaning.  dvo_batch_world_poses and
+ * _copy_world_poses_device return the world twists / poses and keyframe flags (DVO_ERR_NOT_READY before the first push; a sensor-depth
+ * batch without keyframe tracking still gets DVO_ERR_BAD_ARGUMENT).  dvo_batch_keyframe_get returns gray and depth of any level,
+ * xi, id and n_keyframes (valid_updates = 0); sigma and age are not stored: non-NULL -> DVO_ERR_BAD_ARGUMENT; a sequence that never
+ * started -> DVO_ERR_NOT_READY.  Start pose (dvo_batch_set_pose_guess_mode) follows the mono convention: GIVEN rows are WORLD
+ * twists g and the tracker starts from se3_concatenate(-keyframe twist, g); CONSTANT_VELOCITY extrapolates the world twists;
+ * dvo_batch_last_start_poses reports the keyframe-relative start.
+ * Every push runs the per-sequence path (as after dvo_batch_set_actions).  A batch that never calls this runs exactly the launches it
+ * always ran.  Errors, returned before anything changes: a NULL handle or a mono batch -> DVO_ERR_BAD_ARGUMENT; a call after the first
+ * push, or (enable != 0) while a prefetched frame waits -> DVO_ERR_NOT_READY.  While keyframe tracking is on, dvo_batch_prefetch_* ->
+ * DVO_ERR_NOT_READY, and a push whose weight storage differs from the keyframes' (float maps after raw frames or the reverse) ->
+ * DVO_ERR_BAD_ARGUMENT. */
+int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable);   /* sensor-depth batches; before the first push */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */

@@ -126,11 +126,11 @@ private:
     int w_, h_;
 };
 
-// n_seq independent sequences on one GPU (frame-to-frame tracking with sensor depth)
+// n_seq independent sequences on one GPU (frame-to-frame tracking with sensor depth, or keyframe tracking: setKeyframeTracking)
 class BatchTracker {
 public:
     BatchTracker(int n_seq, const Mat3& K, int width, int height, int levels = 4, int culls = 1, const dvo_config* cfg = nullptr)
-        : n_(n_seq)
+        : n_(n_seq), w_(width), h_(height), levels_(levels), culls_(culls)
     {
         check(dvo_batch_create(n_seq, K.data(), width, height, levels, culls, cfg, &b_));
     }
@@ -195,11 +195,39 @@ public:
         if (!enabled) D.clear();
         return D;
     }
+    // track each frame against its sequence's keyframe instead of the previous frame, before the first push (dvo_batch_set_keyframe_tracking)
+    void setKeyframeTracking(bool enable = true) { check(dvo_batch_set_keyframe_tracking(b_, enable ? 1 : 0)); }
+    // with keyframe tracking: world poses of the last push (and its keyframe flags), as BatchMono::worldPoses
+    std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
+    {
+        std::vector<Mat4> out(n_);
+        if (is_keyframe) is_keyframe->resize(n_);
+        check(dvo_batch_world_poses(b_, nullptr, out[0].data(), is_keyframe ? is_keyframe->data() : nullptr));
+        return out;
+    }
+    // asynchronous device-to-device copies on the handle's stream: [n_seq][6], [n_seq][16], [n_seq]; any may be nullptr
+    void copyWorldPosesDevice(float* xiDev, float* TDev = nullptr, int* keyDev = nullptr) { check(dvo_batch_copy_world_poses_device(b_, xiDev, TDev, keyDev)); }
+    // the keyframe of sequence `seq`: gray and depth of one level (default: the finest), its world twist and id (no sigma or age)
+    Keyframe keyframe(int seq, int level = -1)
+    {
+        Keyframe k;
+        k.levels = levels_;
+        k.level = level < 0 ? levels_ - 1 : level;
+        if (k.level >= levels_) throw Error(DVO_ERR_BAD_ARGUMENT, "BatchTracker::keyframe: level " + std::to_string(level) + " is outside [0, levels)");
+        const int shift = culls_ + (levels_ - 1 - k.level);
+        k.width = w_ >> shift;
+        k.height = h_ >> shift;
+        const size_t n = (size_t)k.width * k.height;
+        k.gray.resize(n); k.depth.resize(n);
+        int n_keyframes = 0, valid = 0;
+        check(dvo_batch_keyframe_get(b_, seq, k.level, k.gray.data(), k.depth.data(), nullptr, nullptr, k.xi.data(), &k.id, &n_keyframes, &valid));
+        return k;
+    }
     dvo_batch* handle() { return b_; }
 
 private:
     dvo_batch* b_ = nullptr;
-    int n_;
+    int n_, w_, h_, levels_, culls_;
 };
 
 // n_seq independent MONO sequences on one GPU: System::VisualOdometry::odometrize (system.hpp:44-74: track + Mapper::estimate +
