@@ -409,6 +409,35 @@ int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start)
     return G.last_start(xi_start, b->mono ? b->mono->stream : b->impl.stream);
 }
 
+int dvo_batch_set_track_quality(dvo_batch* b, int enable)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
+    if (b->mono) return b->mono->quality.set(enable != 0, b->mono->trk, b->mono->stream);
+    return b->impl.quality.set(enable != 0, b->impl.trk, b->impl.stream);
+}
+
+// the records of the last push / call: its status (per-sequence path: the device status k_plan wrote; plain pushes: all STARTED on the
+// first, all TRACKED after), launched on the handle's stream into `out` (device) or, with to_host, through the staging buffer
+static int track_quality(dvo_batch* b, dvo_track_quality* out, bool to_host)
+{
+    if (!b || !out) return DVO_ERR_BAD_ARGUMENT;
+    const bool mono = b->mono != nullptr;
+    TrackQuality& Q = mono ? b->mono->quality : b->impl.quality;
+    if (!Q.ready) { set_error("dvo_batch_last_track_quality: the last push / call did not keep quality records (dvo_batch_set_track_quality)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(mono ? b->mono->device : b->impl.device));
+    const Tracker& trk = mono ? b->mono->trk : b->impl.trk;
+    const hipStream_t s = mono ? b->mono->stream : b->impl.stream;
+    const bool planned = mono ? b->mono->act_used : b->impl.act_used;
+    const int* status = planned ? (mono ? b->mono->status.as<int>() : b->impl.status.as<int>()) : nullptr;
+    const bool first = mono ? b->mono->latest_id == 0 : b->impl.n_push == 1;
+    const int all = first ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
+    return to_host ? Q.read_host(trk, status, all, out, s) : Q.launch(trk, status, all, out, s);
+}
+
+int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out) { return track_quality(b, out, true); }
+int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst) { return track_quality(b, dst, false); }
+
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;

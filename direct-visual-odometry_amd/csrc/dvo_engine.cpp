@@ -547,6 +547,7 @@ SolveArgs Tracker::solve_args(int level, int q0, int ignore_active) const
     a.max_iterations = cfg.max_iterations; a.fixed_iterations = cfg.fixed_iterations;
     a.min_update = cfg.min_update; a.min_residual = cfg.min_residual;
     a.ignore_active = ignore_active;
+    if (quality && level == g.levels - 1) a.result = quality + q0;   // (dvo_batch_set_track_quality: the finest level's solves)
     return a;
 }
 
@@ -1527,6 +1528,7 @@ int Batch::push(const FrameInput& in)
     }
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
     guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
+    quality.ready = quality.on;
     n_push++;
     if (!kf_on || cur < 0) {
         prev = cur;
@@ -1845,6 +1847,41 @@ int Batch::update_keyframes(int frame_set)
         pa.meta = kf_meta.as<MonoSeq>(); pa.all = 0; pa.need_list = need_list.as<int>();
         launch_promote(pa, stream);
     }
+    return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: tracking quality records
+int TrackQuality::set(bool enable, Tracker& trk, hipStream_t s)
+{
+    if (enable && !rec.p) {
+        DVO_TRY(rec.alloc(sizeof(dvo_gn_result) * (size_t)trk.n_seq));
+        DVO_TRY(stage.alloc(sizeof(dvo_track_quality) * (size_t)trk.n_seq));
+        DVO_HIP(hipMemsetAsync(rec.p, 0, rec.bytes, s));
+    }
+    on = enable;
+    trk.quality = enable ? rec.as<dvo_gn_result>() : nullptr;
+    return DVO_OK;
+}
+
+int TrackQuality::launch(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s) const
+{
+    QualityArgs a{};
+    a.rec = rec.as<dvo_gn_result>(); a.log = trk.log.as<dvo_track_log>();
+    a.status = status; a.all_status = all_status; a.out = out;
+    a.levels = trk.g.levels;
+    a.max_iterations = trk.cfg.max_iterations; a.fixed_iterations = trk.cfg.fixed_iterations;
+    a.min_update = trk.cfg.min_update; a.min_residual = trk.cfg.min_residual;
+    a.n_seq = trk.n_seq;
+    launch_track_quality(a, s);
+    DVO_HIP(hipGetLastError());
+    return DVO_OK;
+}
+
+int TrackQuality::read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s)
+{
+    DVO_TRY(launch(trk, status, all_status, stage.as<dvo_track_quality>(), s));
+    DVO_HIP(hipMemcpyAsync(out, stage.p, stage.bytes, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
     return DVO_OK;
 }
 

@@ -184,6 +184,19 @@ struct PoseGuess {
     ~PoseGuess() { release(nullptr); }
 };
 
+// Per-sequence tracking quality of a batch (dvo_batch_set_track_quality).  Allocated by the first enable; while on,
+// Tracker::quality points at `rec`.  A read launches k_track_quality on the records of the last push / call.
+struct Tracker;
+struct TrackQuality {
+    bool on = false;      // records are kept from the next push / call on
+    bool ready = false;   // the last push / call kept them
+    DevBuf rec, stage;    // [n_seq] dvo_gn_result; [n_seq] dvo_track_quality (staging of the host read)
+    int set(bool enable, Tracker& trk, hipStream_t s);
+    // status: the push's [n_seq] device status, or nullptr with every sequence `all_status`; out: device memory
+    int launch(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s) const;
+    int read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s);
+};
+
 struct Tracker {  // Track::Tracker for n_seq sequences at once
     Geometry g;
     int n_seq = 0;
@@ -231,6 +244,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // k_track_begin (or the caller's k_plan) and before the sub-batch fork; nullptr: every sequence starts from zero.  Never with persist.
     const PoseSeedArgs* seed = nullptr;
     bool seed_mono = false;
+    // a batch's quality records (dvo_batch_set_track_quality): while set, every solve of the finest level stores its sums here
+    // (SolveArgs::result, [n_seq]), so each sequence's last one remains; nullptr: no record (the plain path's kernel arguments)
+    dvo_gn_result* quality = nullptr;
     bool prefer_persist = false;   // set before init() by the owner whose results go through enable_host_result() (VisualOdometry's sensor-depth tracker)
     bool persist_ok = false, persist_failed = false, persist_used = false;
     int persist_grid = 0, persist_spin_limit = 1 << 18;
@@ -426,6 +442,7 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     // the seed of this push outside track() (a push that tracks nothing still folds into the history)
     void seed_untracked(const uint8_t* eff_dev, int all_eff);
     PoseSeedArgs guess_args(const uint8_t* eff_dev, int all_eff);   // (keyframe tracking: world twists and the keyframe twists, k_mono_seed)
+    TrackQuality quality;                       // dvo_batch_set_track_quality
     const uint8_t* cam_changed() const { return reinterpret_cast<const uint8_t*>(cam_dev.as<Intr>() + (size_t)g.levels * n_seq); }
     // Keyframe tracking (dvo_batch_set_keyframe_tracking): every push runs the per-sequence path; the first push's frame
     // set (cur) is the keyframe set and is never rotated away, later frames are built into another set and tracked against it.  After
@@ -522,6 +539,7 @@ struct MonoBatch {
     int started_of(int seq, bool* out);         // (synchronises) whether sequence `seq` has a keyframe
     PoseGuess guess;                            // dvo_batch_set_pose_guess_mode / dvo_batch_set_pose_guess (world twists)
     int set_guess_mode(int mode);
+    TrackQuality quality;                       // dvo_batch_set_track_quality
 };
 
 void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vector<float>& s);

@@ -483,6 +483,22 @@ struct PoseSeedArgs {
 };
 void launch_seed_pose(const PoseSeedArgs& a, hipStream_t s);
 void launch_mono_seed(const PoseSeedArgs& a, hipStream_t s);
+
+// k_track_quality: the dvo_track_quality records of a batch's last push (dvo_batch_set_track_quality), one thread per
+// sequence, launched by a read.  Reads the finest level's last solve (SolveArgs::result, kept by Tracker::quality), the track log and
+// the push's status; writes the records straight into `out` (the caller's device buffer, or the staging of a host read).
+struct QualityArgs {
+    const dvo_gn_result* rec = nullptr;   // [n_seq] the sums of each sequence's last finest-level solve
+    const dvo_track_log* log = nullptr;   // [n_seq]
+    const int* status = nullptr;          // [n_seq] DVO_SEQ_TRACKED ... of the push; nullptr: every sequence has `all_status`
+    int all_status = DVO_SEQ_TRACKED;
+    dvo_track_quality* out = nullptr;     // [n_seq]
+    int levels = 0;                       // the finest level is levels - 1
+    int max_iterations = 0, fixed_iterations = 0;
+    float min_update = 0.0f, min_residual = 0.0f;
+    int n_seq = 0;
+};
+void launch_track_quality(const QualityArgs& a, hipStream_t s);
 #ifdef __HIPCC__
 // the state k_set_pose loads for twist x (not `active` / `iter`: k_track_begin / k_plan set them), and x as the reported start; a zero
 // twist writes neither the state nor anything but +0 to `start`

@@ -1877,6 +1877,109 @@ __global__ void __launch_bounds__(256) k_seed_pose(PoseSeedArgs a)
     seed_state(a.state[s], x, a.start + (size_t)s * 6);
 }
 
+// solve6's choice of solve6_pinv (dvo_math.h), restated operation for operation (the build does not contract, so the same
+// expressions give the same bits): the largest diagonal entry (NaN entries skipped) is > 0 and an LDL^T pivot is <= 1e-12 times it.
+// (Factoring this out of solve6 changed the instruction streams of the solve kernels, so it is kept apart.)
+__device__ __forceinline__ bool solve6_takes_pinv(const double H[21])
+{
+    double maxd = 0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) maxd = H[tri(i, i)] > maxd ? H[tri(i, i)] : maxd;
+    if (!(maxd > 0.0)) return false;
+    double L[6][6], d[6];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+        double dj = H[tri(j, j)];
+#pragma unroll
+        for (int k = 0; k < j; k++) dj -= L[j][k] * L[j][k] * d[k];
+        ok = ok && (dj > 1e-12 * maxd);
+        d[j] = dj;
+        const double inv = 1.0 / dj;
+#pragma unroll
+        for (int i = j + 1; i < 6; i++) {
+            double v = H[tri(j, i)];
+#pragma unroll
+            for (int k = 0; k < j; k++) v -= L[i][k] * L[j][k] * d[k];
+            L[i][j] = v * inv;
+        }
+    }
+    return !ok;
+}
+
+// k_track_quality: one dvo_track_quality per sequence from the finest level's last solve (include/dvo.h).  Runs once per
+// read, not per push.  jacobi_eig6 is used as it is: inlined here, its loops unroll and A, V stay in registers (170 VGPRs, no
+// scratch: two waves per SIMD, plenty for n_seq threads).
+__global__ void __launch_bounds__(64) k_track_quality(QualityArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    dvo_track_quality& q = a.out[s];
+    const int status = a.status ? a.status[s] : a.all_status;
+    const int L = a.levels - 1;
+    const double nan = __builtin_nan("");
+    q.struct_size = (int)sizeof(dvo_track_quality);
+    q.status = status;
+    if (status != DVO_SEQ_TRACKED) {   // no solve of this push: the empty record
+        q.flags = 0; q.n_valid = 0;
+        for (int l = 0; l < DVO_MAX_LEVELS; l++) q.n_iter[l] = 0;
+        q.residual = -1.0f; q.update_norm = 0.0f; q.sum_r2 = 0.0;
+        for (int i = 0; i < 21; i++) { q.H[i] = 0.0; q.covariance[i] = nan; }
+        for (int i = 0; i < 6; i++) { q.g[i] = 0.0; q.eigenvalues[i] = nan; }
+        return;
+    }
+    const dvo_track_log& lg = a.log[s];
+    const dvo_gn_result& r = a.rec[s];
+    for (int l = 0; l < DVO_MAX_LEVELS; l++) q.n_iter[l] = l <= L ? lg.n_iter[l] : 0;
+    int it = lg.n_iter[L] - 1;   // the finest level's last iteration (every TRACKED sequence solves it at least once)
+    it = it < 0 ? 0 : (it < DVO_MAX_ITERATIONS ? it : DVO_MAX_ITERATIONS - 1);
+    const int n_valid = r.n_valid;
+    q.n_valid = n_valid;
+    q.residual = r.residual;
+    q.update_norm = lg.update_norm[L][it];
+    q.sum_r2 = r.sum_r2;
+    double H[21], A[36], V[36];
+    bool finite = isfinite(r.sum_r2);
+    for (int i = 0; i < 21; i++) { H[i] = r.H[i]; q.H[i] = H[i]; finite = finite && isfinite(H[i]); }
+    for (int i = 0; i < 6; i++) { q.g[i] = r.g[i]; finite = finite && isfinite(r.g[i]); }
+    // flags: solve_finish's stop tests on the same values (|upd| in double, as there)
+    int flags = n_valid == 0 ? DVO_QUALITY_NO_VALID : 0;
+    double nrm = 0.0;
+    bool upd_finite = true;
+    for (int i = 0; i < 6; i++) {
+        const float u = lg.xi_update[L][it][i];
+        nrm += (double)u * (double)u;
+        upd_finite = upd_finite && isfinite(u);
+    }
+    nrm = sqrt(nrm);
+    if (!upd_finite) flags |= DVO_QUALITY_NOT_FINITE;
+    if (a.fixed_iterations <= 0) {
+        if (nrm < (double)a.min_update || r.residual < a.min_residual) flags |= DVO_QUALITY_CONVERGED;
+        else if (it + 1 >= a.max_iterations) flags |= DVO_QUALITY_CAPPED;
+    }
+    const bool rank_def = n_valid > 0 && solve6_takes_pinv(H);   // (solve_finish calls solve6 only when n_valid > 0)
+    if (rank_def) flags |= DVO_QUALITY_RANK_DEFICIENT;
+    q.flags = flags;
+    // eigen-decomposition H = V diag(lambda) V^T (Jacobi, double) and covariance s2 V diag(1 / lambda) V^T
+    for (int i = 0, k = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, k++) { A[6 * i + j] = H[k]; A[6 * j + i] = H[k]; }
+    jacobi_eig6(A, V);
+    double lam[6];
+    for (int i = 0; i < 6; i++) lam[i] = finite ? A[7 * i] : nan;
+    bool cov_ok = finite && n_valid > 6 && !rank_def;
+    for (int i = 0; i < 6; i++) cov_ok = cov_ok && lam[i] > 0.0;
+    const double s2 = cov_ok ? r.sum_r2 / (double)(n_valid - 6) : nan;
+    for (int i = 0, k = 0; i < 6; i++)
+        for (int j = i; j < 6; j++, k++) {
+            double c = 0.0;
+            for (int e = 0; e < 6; e++) c += V[6 * i + e] * V[6 * j + e] / lam[e];
+            q.covariance[k] = cov_ok ? s2 * c : nan;
+        }
+    for (int i = 1; i < 6; i++)   // ascending
+        for (int j = i; j > 0 && lam[j] < lam[j - 1]; j--) { const double t = lam[j]; lam[j] = lam[j - 1]; lam[j - 1] = t; }
+    for (int i = 0; i < 6; i++) q.eigenvalues[i] = lam[i];
+}
+
 // k_export_poses: relative twist + exp(xi) 4x4 (system.hpp:92) per sequence
 // host_result (optional, fine-grained mapped HOST memory, one sequence): the same 22 floats, then a sequence word written with a
 // system-scope release store -- the caller's thread polls it instead of queueing a device-to-host copy and waiting for the stream
@@ -2363,7 +2466,7 @@ void launch_track_level(const GnArgs& ga0, const SolveArgs& sa0, int n_seq, hipS
     ga.list = nullptr; ga.next_count = nullptr; ga.mask = nullptr;
     const GnTiling tl = gn_tiling(ga.w, ga.h, 4, ga.prm.crop);  // (the caller made sure these are raster tiles: !tl.t2d)
     ga.blk_first = tl.live_first; ga.blk_count = tl.live_count;
-    sa.list_in = nullptr; sa.list_out = nullptr; sa.result = nullptr;
+    sa.list_in = nullptr; sa.list_out = nullptr;
     if (ga.seq_k) hipLaunchKernelGGL((k_track_level<4, 2, true>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
     else hipLaunchKernelGGL((k_track_level<4, 2, false>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
 }
@@ -2424,6 +2527,11 @@ void launch_set_pose(SeqState* state, const float* xi_dev, int n_seq, hipStream_
 void launch_seed_pose(const PoseSeedArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_seed_pose, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
+}
+
+void launch_track_quality(const QualityArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_track_quality, dim3(cdiv(a.n_seq, 64)), dim3(64), 0, s, a);
 }
 
 void launch_export_poses(const SeqState* state, float* xi_out, float* T_out, int n_seq, hipStream_t s, float* host_result, int host_tag)

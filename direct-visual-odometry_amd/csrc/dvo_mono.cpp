@@ -281,6 +281,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 1, frame_id, xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), stream);
         DVO_HIP(hipGetLastError());
         guess.rows_src = nullptr;
+        quality.ready = quality.on;
         latest_id = frame_id;
         return DVO_OK;
     }
@@ -415,6 +416,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         plan_parity ^= 1;
     }
     DVO_HIP(hipGetLastError());
+    quality.ready = quality.on;
     latest_id = frame_id;
     return DVO_OK;
 }

@@ -63,6 +63,21 @@ class GnResult(C.Structure):
                 ("xi_update", C.c_float * 6), ("residual", C.c_float), ("xi_next", C.c_float * 6)]
 
 
+class TrackQuality(C.Structure):
+    """dvo_track_quality (include/dvo.h): one sequence's tracking-quality record of the last push / call."""
+    _fields_ = [("struct_size", C.c_int), ("status", C.c_int), ("flags", C.c_int), ("n_valid", C.c_int),
+                ("n_iter", C.c_int * MAX_LEVELS), ("residual", C.c_float), ("update_norm", C.c_float), ("sum_r2", C.c_double),
+                ("H", C.c_double * 21), ("g", C.c_double * 6), ("eigenvalues", C.c_double * 6), ("covariance", C.c_double * 21)]
+
+
+# the same layout as a numpy structured dtype (Batch / MonoBatch .last_track_quality)
+TRACK_QUALITY_DTYPE = np.dtype({"names": [f[0] for f in TrackQuality._fields_],
+                                "formats": ["<i4", "<i4", "<i4", "<i4", ("<i4", (MAX_LEVELS,)), "<f4", "<f4", "<f8",
+                                            ("<f8", (21,)), ("<f8", (6,)), ("<f8", (6,)), ("<f8", (21,))],
+                                "offsets": [getattr(TrackQuality, f[0]).offset for f in TrackQuality._fields_],
+                                "itemsize": C.sizeof(TrackQuality)})
+
+
 class GnProfile(C.Structure):
     _fields_ = [("gn_ms", C.c_double), ("gn_launches", C.c_uint64), ("gn_pixels", C.c_uint64),
                 ("gn_iterations", C.c_uint64)]
@@ -105,6 +120,7 @@ EXPORTS = [
     "dvo_batch_set_mono_start_depth_device",
     "dvo_batch_set_pose_guess_mode", "dvo_batch_set_pose_guess", "dvo_batch_last_start_poses",
     "dvo_batch_set_keyframe_tracking",
+    "dvo_batch_set_track_quality", "dvo_batch_last_track_quality", "dvo_batch_copy_track_quality_device",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -112,6 +128,8 @@ SEQ_SKIP, SEQ_TRACK, SEQ_RESTART = 0, 1, 2
 SEQ_TRACKED, SEQ_SKIPPED, SEQ_STARTED, SEQ_BAD_ACTION = 0, 1, 2, 3
 # start pose of a batch's tracking (Batch / MonoBatch .set_pose_guess_mode): include/dvo.h
 GUESS_NONE, GUESS_GIVEN, GUESS_CONSTANT_VELOCITY = 0, 1, 2
+# flags of a tracking-quality record (TrackQuality.flags): include/dvo.h
+QUALITY_CONVERGED, QUALITY_CAPPED, QUALITY_NO_VALID, QUALITY_NOT_FINITE, QUALITY_RANK_DEFICIENT = 1, 2, 4, 8, 16
 
 _lib = None
 
@@ -564,6 +582,24 @@ class _PoseGuess:
         return xi
 
 
+class _TrackQuality:
+    """Per-sequence tracking quality of the last push / call, shared by Batch and MonoBatch (dvo_batch_set_track_quality, include/dvo.h)."""
+
+    def set_track_quality(self, enable=True):
+        """Keep the finest level's last Gauss-Newton sums of every sequence from the next push / call on (False: stop)."""
+        _check(lib().dvo_batch_set_track_quality(self._p, 1 if enable else 0))
+
+    def last_track_quality(self):
+        """numpy structured array [n_seq] of TRACK_QUALITY_DTYPE (the fields of dvo_track_quality); synchronises."""
+        out = np.zeros(self.n_seq, TRACK_QUALITY_DTYPE)
+        _check(lib().dvo_batch_last_track_quality(self._p, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def copy_track_quality_device(self, ptr):
+        """Write the records [n_seq] (C.sizeof(TrackQuality) bytes each) to device memory at int `ptr`, in stream order."""
+        _check(lib().dvo_batch_copy_track_quality_device(self._p, C.c_void_p(int(ptr))))
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -577,7 +613,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -726,7 +762,7 @@ class Batch(_PoseGuess, _WorldPoses):
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess, _WorldPoses):
+class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

@@ -436,6 +436,61 @@ int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start);
  * DVO_ERR_NOT_READY, and a push whose weight storage differs from the keyframes' (float maps after raw frames or the reverse) ->
  * DVO_ERR_BAD_ARGUMENT. */
 int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable);   /* sensor-depth batches; before the first push */
+/* ---- per-sequence tracking quality (both batch kinds) ---------------------------------------------------------------------------
+ * dvo_batch_set_track_quality(b, 1) makes every later push / call keep, per sequence, the sums of the LAST Gauss-Newton iteration of
+ * the finest level (levels - 1: the solve that produced the returned pose); enable = 0 stops keeping them.  Poses, status, world
+ * poses, track logs and every schedule are unchanged; a batch that never enables it runs exactly the launches it always ran.
+ * dvo_batch_last_track_quality (host, synchronises) and dvo_batch_copy_track_quality_device (device, asynchronous, in stream order on
+ * the handle's stream) write one record per sequence [n_seq] describing the LAST push / call; a later read of the same push gives the
+ * same records (pushes in between are what changes them).  Per record:
+ *   status       that push's DVO_SEQ_TRACKED / SKIPPED / STARTED / BAD_ACTION, as dvo_batch_last_status / _mono_last_status.
+ *   n_iter       the track log's n_iter (0 beyond the batch's levels).
+ *   H, g, sum_r2, n_valid   bit for bit the sums that iteration's 6x6 solve used: H = upper triangle of sum J^T J row by row (index
+ *                of (i, j), i <= j: i*6 - i*(i-1)/2 + j - i), g = sum J^T (w r).  They are evaluated at that iteration's INPUT pose
+ *                (the pose before its update), not at the returned pose, as Gauss-Newton forms them.
+ *   residual     sum_r2 / n_valid in float (optimize.cpp:98), -1 when n_valid == 0; update_norm = |xi_update| of that iteration.
+ *                Both are the track log's entries bit for bit.
+ *   eigenvalues  of H (symmetric), ascending, by Jacobi rotations in double.
+ *   covariance   upper triangle (as H) of s2 * H^-1, s2 = sum_r2 / (n_valid - 6), in the coordinates of the twist the tracker updates
+ *                (xi <- log(exp(xi) exp(upd)), tracker.cpp:46): relative to the reference (the keyframe in keyframe mode and mono),
+ *                as dvo_batch_last_poses and the mono tracker's relative twist.  NaN when n_valid <= 6, when RANK_DEFICIENT is set,
+ *                when a sum is not finite or when an eigenvalue is not positive.  It is the least-squares covariance of the problem as
+ *                the reference forms it: a consistent relative confidence, not a calibrated metric covariance.
+ *   flags        DVO_QUALITY_*:
+ *     CONVERGED        the finest level stopped on min_update or min_residual (tracker.cpp:68-73); fixed_iterations = 0 only.
+ *     CAPPED           the finest level ran max_iterations without either test firing; fixed_iterations = 0 only.
+ *     NO_VALID         n_valid == 0 in that iteration (residual -1, optimize.cpp:92-93).
+ *     NOT_FINITE       that iteration's update had a component that is not finite: the pose kept its value (tracker.cpp:46-51).
+ *     RANK_DEFICIENT   the 6x6 solve judged H singular and took the pseudo-inverse: the largest diagonal entry is > 0 and an LDL^T
+ *                      pivot is <= 1e-12 times it.  An all-zero (or all non-finite) diagonal gives a zero update without the
+ *                      pseudo-inverse and does not set it.
+ * A sequence that did not track at that push (SKIPPED, STARTED, BAD_ACTION) gets the empty record: n_valid = 0, n_iter all 0,
+ * flags = 0, residual -1, update_norm 0, sum_r2 / H / g zero, eigenvalues and covariance NaN -- never an earlier push's data.
+ * struct_size = sizeof(dvo_track_quality) of the library (the struct may grow at its end).
+ * Errors: a NULL handle or a NULL output -> DVO_ERR_BAD_ARGUMENT; a read before a push / call that ran with quality enabled (or after
+ * one that ran with it disabled) -> DVO_ERR_NOT_READY.  dvo_vo handles have no quality record (dvo_vo_last_track_log). */
+#define DVO_QUALITY_CONVERGED       1
+#define DVO_QUALITY_CAPPED          2
+#define DVO_QUALITY_NO_VALID        4
+#define DVO_QUALITY_NOT_FINITE      8
+#define DVO_QUALITY_RANK_DEFICIENT 16
+typedef struct dvo_track_quality {
+    int    struct_size;
+    int    status;
+    int    flags;
+    int    n_valid;
+    int    n_iter[DVO_MAX_LEVELS];
+    float  residual;
+    float  update_norm;
+    double sum_r2;
+    double H[21];
+    double g[6];
+    double eigenvalues[6];
+    double covariance[21];
+} dvo_track_quality;
+int dvo_batch_set_track_quality(dvo_batch* b, int enable);                      /* both kinds; from the next push / call on */
+int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out);         /* [n_seq], host, synchronises */
+int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst);  /* [n_seq], device, asynchronous on the handle's stream */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */

@@ -176,6 +176,15 @@ public:
         check(dvo_batch_last_start_poses(b_, out[0].data()));
         return out;
     }
+    // per-sequence tracking quality of the last push (dvo_batch_set_track_quality): records [n_seq], host (synchronises) or device
+    void setTrackQuality(bool enable = true) { check(dvo_batch_set_track_quality(b_, enable ? 1 : 0)); }
+    std::vector<dvo_track_quality> lastTrackQuality()
+    {
+        std::vector<dvo_track_quality> out(n_);
+        check(dvo_batch_last_track_quality(b_, out.data()));
+        return out;
+    }
+    void copyTrackQualityDevice(dvo_track_quality* dst) { check(dvo_batch_copy_track_quality_device(b_, dst)); }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
@@ -282,6 +291,15 @@ public:
         check(dvo_batch_last_start_poses(b_, out[0].data()));
         return out;
     }
+    // per-sequence tracking quality of the last call (dvo_batch_set_track_quality): records [n_seq], host (synchronises) or device
+    void setTrackQuality(bool enable = true) { check(dvo_batch_set_track_quality(b_, enable ? 1 : 0)); }
+    std::vector<dvo_track_quality> lastTrackQuality()
+    {
+        std::vector<dvo_track_quality> out(n_);
+        check(dvo_batch_last_track_quality(b_, out.data()));
+        return out;
+    }
+    void copyTrackQualityDevice(dvo_track_quality* dst) { check(dvo_batch_copy_track_quality_device(b_, dst)); }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {
         std::vector<Mat4> out(n_);
