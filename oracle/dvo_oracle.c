@@ -634,6 +634,13 @@ static inline float level_step(int level)
     return g_step_default;
 }
 
+/* where orc_optimize_terms collects what optimize_impl's per-pixel body produced (capacity: every pixel of the level) */
+typedef struct {
+    int n;
+    int32_t* index;
+    float *J, *r, *rw;
+} term_sink;
+
 /* per-pixel body shared by both variants: returns 1 and fills J[6], r, rw when the pixel contributes */
 static int optimize_pixel(const float* obj_gray, const float* gradx, const float* grady, const float* ref_depth,
                           const float* ref_sigma, int w, int h, const float K[9], const float Rt[12],
@@ -690,7 +697,7 @@ residual:;
 
 static void optimize_impl(const float* obj_gray, const float* ref_gray, const float* gradx, const float* grady,
                           const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
-                          const float xi[6], int level, int crop_enable, int variant, orc_outcome* out, uint8_t* mask)
+                          const float xi[6], int level, int crop_enable, int variant, orc_outcome* out, uint8_t* mask, term_sink* terms)
 {
     const float step = level_step(level);
     const int n = w * h;
@@ -707,7 +714,7 @@ static void optimize_impl(const float* obj_gray, const float* ref_gray, const fl
     }
     /* The per-pixel lambda of optimize.cpp:28-90.  One thread (the default): plain raster order.  g_threads > 1: rows are dealt
      * to threads in contiguous blocks, every thread sums into its own partial, partials are added in thread order. */
-    const int nthr = g_threads > 1 ? g_threads : 1;
+    const int nthr = (g_threads > 1 && !terms) ? g_threads : 1; /* terms: one thread, so that they come in raster order */
     orc_outcome* part = (orc_outcome*)calloc((size_t)nthr, sizeof(orc_outcome));
 #pragma omp parallel num_threads(nthr) if (nthr > 1)
     {
@@ -750,6 +757,13 @@ static void optimize_impl(const float* obj_gray, const float* ref_gray, const fl
                     for (int a = 0; a < 6; a++) A[6 * i + a] = J[a];
                     B[i] = rw;
                 }
+                if (terms) { /* the floats the sums above were formed from */
+                    const int t = terms->n++;
+                    terms->index[t] = i;
+                    for (int a = 0; a < 6; a++) terms->J[6 * t + a] = J[a];
+                    terms->r[t] = r;
+                    terms->rw[t] = rw;
+                }
             }
     }
     *out = part[0];  /* (one thread: exactly the sequential sums) */
@@ -780,8 +794,25 @@ void orc_optimize(const float* obj_gray, const float* ref_gray, const float* ref
     float* gy = (float*)malloc(sizeof(float) * (size_t)w * h);
     orc_gradiate(ref_gray, w, h, 1, gx);
     orc_gradiate(ref_gray, w, h, 0, gy);
-    optimize_impl(obj_gray, ref_gray, gx, gy, ref_depth, ref_sigma, w, h, K, xi, level, crop_enable, variant, out, mask);
+    optimize_impl(obj_gray, ref_gray, gx, gy, ref_depth, ref_sigma, w, h, K, xi, level, crop_enable, variant, out, mask, NULL);
     free(gx); free(gy);
+}
+
+int orc_optimize_terms(const float* obj_gray, const float* ref_gray, const float* ref_depth, const float* ref_sigma,
+                       int w, int h, const float K[9], const float xi[6], int level, int crop_enable,
+                       orc_outcome* out, int32_t* index, float* J, float* r, float* rw)
+{
+    const int lit = g_lit;
+    g_lit = 0; /* canonical arithmetic, whatever mode a sensitivity measurement left behind */
+    float* gx = (float*)malloc(sizeof(float) * (size_t)w * h);
+    float* gy = (float*)malloc(sizeof(float) * (size_t)w * h);
+    orc_gradiate(ref_gray, w, h, 1, gx);
+    orc_gradiate(ref_gray, w, h, 0, gy);
+    term_sink sink = {0, index, J, r, rw};
+    optimize_impl(obj_gray, ref_gray, gx, gy, ref_depth, ref_sigma, w, h, K, xi, level, crop_enable, 0, out, NULL, &sink);
+    free(gx); free(gy);
+    g_lit = lit;
+    return sink.n;
 }
 
 /* ======================================================================== */
@@ -870,7 +901,7 @@ void orc_track(const orc_frame* obj, const orc_frame* ref, int crop_enable, int 
         for (int it = 0; it < max_it && it < ORC_MAX_ITER; it++) { /* tracker.cpp:42 */
             orc_outcome o;
             optimize_impl(obj->gray[level], ref->gray[level], gx, gy, ref->depth[level], ref->sigma[level],
-                          w, h, ref->K[level], xi, level, crop_enable, variant, &o, NULL);
+                          w, h, ref->K[level], xi, level, crop_enable, variant, &o, NULL, NULL);
             float upd[6];
             if (g_nudge && level == 0 && it == 0) {
                 for (int k = 0; k < (g_nudge < 0 ? -g_nudge : g_nudge); k++)

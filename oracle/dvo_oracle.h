@@ -115,6 +115,14 @@ void orc_optimize(const float* obj_gray, const float* ref_gray, const float* ref
                   const float* ref_sigma, int w, int h, const float K[9], const float xi[6],
                   int level, int crop_enable, int variant, orc_outcome* out, uint8_t* mask);
 
+/* The per-pixel terms behind orc_optimize's sums: the hoisted variant on one thread in canonical arithmetic (whatever
+ * orc_set_threads / orc_set_literal say).  For the contributing pixels in raster order: index[t] = y * w + x, J[6 t .. 6 t + 5],
+ * r[t], rw[t] = r * weight, as the floats the per-pixel body produced; `out` is what orc_optimize returns (its H, g, sum_r2 are the
+ * double sums of exactly these products, in this order).  Every array holds w * h entries; returns the number of terms. */
+int orc_optimize_terms(const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                       const float* ref_sigma, int w, int h, const float K[9], const float xi[6],
+                       int level, int crop_enable, orc_outcome* out, int32_t* index, float* J, float* r, float* rw);
+
 /* dense least squares used by the faithful variant: x = argmin |A x + B| (min norm), returns -x. */
 void orc_lsq_svd(const float* A, const float* B, int n, float x_update[6]);
 /* 6x6 pseudo-inverse solve used by the hoisted variant */

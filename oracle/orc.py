@@ -223,6 +223,24 @@ def optimize(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, crop=True, 
     return res
 
 
+def optimize_terms(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, crop=True):
+    """The per-pixel terms of optimize() (hoisted variant, one thread, canonical arithmetic): for the contributing pixels in raster
+    order, index (y * w + x), J (n x 6), r and rw = r * weight as the float32 values the per-pixel body produced, plus n_valid and
+    the oracle's own finished sums (H, g, sum_r2: double sums of exactly these products in this order)."""
+    obj_gray = f32(obj_gray); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth); ref_sigma = f32(ref_sigma)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = Outcome()
+    index = np.empty(w * h, np.int32); J = np.empty((w * h, 6), np.float32)
+    r = np.empty(w * h, np.float32); rw = np.empty(w * h, np.float32)
+    fn = lib().orc_optimize_terms
+    fn.restype = C.c_int
+    n = fn(fp(obj_gray), fp(ref_gray), fp(ref_depth), fp(ref_sigma), w, h, fp(K), fp(xi), level, 1 if crop else 0,
+           C.byref(out), index.ctypes.data_as(C.POINTER(C.c_int32)), fp(J), fp(r), fp(rw))
+    return dict(index=index[:n].copy(), J=J[:n].copy(), r=r[:n].copy(), rw=rw[:n].copy(), n_valid=n, shape=(h, w),
+                H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2)
+
+
 def solve6(H21, g):
     H21 = np.ascontiguousarray(H21, np.float64); g = np.ascontiguousarray(g, np.float64)
     x = np.zeros(6, np.float32)

@@ -1,0 +1,146 @@
+"""Per-entry bound on the 28 Gauss-Newton sums of the device (H: 21, g: 6, sum_r2) against exact sums of the oracle's per-pixel terms.
+
+DESIGN.md §3: the per-pixel values J[6], r, r*w are the same bits on the device and in the oracle; only the reduction differs.
+DESIGN.md §6 ("The reduction bound") reads the shape of the device's reduction off the kernels and counts the float32 roundings on
+its longest path (`depth`).  Every rounding is a relative error of at most u = 2^-24 of a partial sum, and no partial sum of an entry
+exceeds that entry's sum of absolute terms A, so
+
+    |S_gpu - S_exact| <= ((1 + u)^depth - 1) * A  <=  depth * u * (1 + 2^-10) * A        per entry.
+
+The factor (1 + 2^-10) covers everything of second order (§6 has the figures): depth^2 u^2 / 2, the double-precision tails of the
+device (one 2^-53 rounding per partial row), and the error of the float64 reference sums below.  The only number in this module is
+`depth`, and it comes from the code: nothing here is tuned on a device result.
+"""
+import functools
+import re
+
+import numpy as np
+
+U32 = 2.0 ** -24                 # unit roundoff of float32 (round to nearest)
+SECOND_ORDER = 1.0 + 2.0 ** -10  # see the module docstring
+
+RATIOS = []        # (tag, largest error / bound of that call): what DESIGN.md §6 tabulates; never a pass criterion (that is <= 1)
+_nonempty_calls = 0
+_reported = 0      # RATIOS[:_reported] have been printed by an earlier report()
+
+
+def nonempty_calls():
+    """How often assert_gn_sums has passed with a non-empty term list: a test reads it before and after its work and asserts that it
+    grew, so that a helper which is silently skipped fails the test."""
+    return _nonempty_calls
+
+
+def must_be_used(test):
+    """decorator of a test that relies on assert_gn_sums: it fails unless the helper passed at least once on a non-empty term list"""
+    @functools.wraps(test)
+    def run(*args, **kw):
+        before = _nonempty_calls
+        out = test(*args, **kw)
+        assert _nonempty_calls > before, "assert_gn_sums was not called with a non-empty term list"
+        return out
+    return run
+
+
+def exact_sums(terms):
+    """The 21 + 6 + 1 sums of orc.optimize_terms() output in float64 and, beside each, the sum of the absolute values of its terms:
+    H / A_H[k] = sum J_a J_b / sum |J_a J_b| (upper triangle, row major), g / A_g[a] = sum J_a rw / sum |J_a rw|, sum_r2 = A_r = sum r^2.
+
+    The product of two float32 values is exact in float64 (48 significant bits), so only the summation rounds.  numpy sums a
+    contiguous float64 vector pairwise (blocks of 128, eight running sums each): its error is below (log2(n) + 16) * 2^-53 * A, far
+    below n * 2^-53 * A, and even that is more than four orders under the float32 bound (17 * 2^-24) at every size in the suite
+    (n <= 2.1e6 at 1080p: n * 2^-53 = 2.3e-10 against 1e-6)."""
+    J = np.ascontiguousarray(terms["J"], np.float64).reshape(-1, 6)
+    r = np.ascontiguousarray(terms["r"], np.float64); rw = np.ascontiguousarray(terms["rw"], np.float64)
+    H = np.zeros(21); A_H = np.zeros(21); g = np.zeros(6); A_g = np.zeros(6)
+    k = 0
+    for a in range(6):
+        for b in range(a, 6):
+            p = J[:, a] * J[:, b]
+            H[k] = p.sum(); A_H[k] = np.abs(p).sum(); k += 1
+        p = J[:, a] * rw
+        g[a] = p.sum(); A_g[a] = np.abs(p).sum()
+    s = float((r * r).sum())
+    return dict(H=H, g=g, sum_r2=s, A_H=A_H, A_g=A_g, A_r=s, n=int(J.shape[0]))
+
+
+def reduction_depth(ppt=None, kernel="gn_tile"):
+    """Float32 roundings on the longest path from a per-pixel term to a finished sum ("The reduction bound").
+
+    kernel = "gn_tile": k_track_gn, k_track_gn_cam, k_track_gn_fused, k_track_level and the tile loop of k_track_persist, i.e.
+      everything built on gn_tile(), for raster tiles (256 * ppt pixels) and the 64-, 32- and 16-column 2-D tiles alike:
+        ppt  Acc29::add of the thread's own pixels (one fmaf per pixel and accumulator; the gather group only reorders loads),
+      + ppt  Acc29::add in the deferred loop (e = threadIdx.x; e < total; e += 256 with total <= 256 * ppt queued pixels),
+      + 6    wave_reduce29_packed (permlane32, permlane16, row_shl/shr 8, row_shl/shr 4, two quad_perm steps: one add each),
+      + 3    ((red[0] + red[1]) + red[2]) + red[3] over the four waves;
+      the rest (sum_partial_rows / sum_partial_class, k_gn_solve) is double precision.
+    kernel = "lds_patch": k_track_gn_tile evaluates border pixels in place (gn_sample_slow) and has no deferred loop: ppt + 6 + 3.
+
+    ppt = None: the engine chose (gn_pixels_per_thread = 0).  Its choice is 1, 2 or 4 (Tracker::init halves from 4), so the largest
+    possible depth, that of 4, is used."""
+    if ppt is None or ppt == 0:
+        ppt = 4
+    assert ppt in (1, 2, 4, 8), ppt
+    assert kernel in ("gn_tile", "lds_patch"), kernel
+    return (2 * ppt if kernel == "gn_tile" else ppt) + 6 + 3
+
+
+def depth_for_cfg(cfg=None):
+    """reduction_depth of the kernel a dvo_config selects (None: the defaults)"""
+    ppt = getattr(cfg, "gn_pixels_per_thread", 0) if cfg is not None else 0
+    lds = getattr(cfg, "gn_use_lds_patch", -1) if cfg is not None else -1
+    return reduction_depth(ppt if ppt in (1, 2, 4, 8) else None, "lds_patch" if lds > 0 else "gn_tile")
+
+
+def bounds(ex, depth):
+    """the per-entry bounds (H: 21, g: 6, sum_r2) for exact_sums() output"""
+    f = depth * U32 * SECOND_ORDER
+    return f * ex["A_H"], f * ex["A_g"], f * ex["A_r"]
+
+
+def assert_gn_sums(got, terms, depth, tag=""):
+    """`got` (H, g, sum_r2, n_valid of the device) against the exact sums of `terms` (orc.optimize_terms): per entry
+    |got - exact| <= depth * 2^-24 * (1 + 2^-10) * A; an entry whose A is zero must be exactly zero; n_valid is the term count.
+    Returns the largest error / bound ratio (0.0 without terms) and appends (tag, ratio) to RATIOS."""
+    global _nonempty_calls
+    ex = exact_sums(terms)
+    assert int(got["n_valid"]) == ex["n"], "%s: n_valid %d, %d terms" % (tag, int(got["n_valid"]), ex["n"])
+    bH, bg, br = bounds(ex, depth)
+    worst = 0.0
+    for name, val, ref, bnd in (("H", got["H"], ex["H"], bH), ("g", got["g"], ex["g"], bg),
+                                ("sum_r2", [got["sum_r2"]], [ex["sum_r2"]], [br])):
+        val = np.asarray(val, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel(); bnd = np.asarray(bnd, np.float64).ravel()
+        assert np.isfinite(bnd).all() and np.isfinite(ref).all(), "%s: the reference terms of %s are not finite" % (tag, name)
+        err = np.abs(val - ref)
+        for k in range(val.size):
+            if bnd[k] == 0.0:
+                assert val[k] == 0.0, "%s: %s[%d] = %r, but every term of it is zero" % (tag, name, k, val[k])
+                continue
+            ratio = err[k] / bnd[k]
+            assert ratio <= 1.0, "%s: %s[%d] = %.17g, exact %.17g: error %.3g is %.3g times the bound %.3g (depth %d, A = %.6g)" % (
+                tag, name, k, val[k], ref[k], err[k], ratio, bnd[k], depth, bnd[k] / (depth * U32 * SECOND_ORDER))
+            worst = max(worst, float(ratio))
+    if ex["n"] > 0:
+        _nonempty_calls += 1
+    RATIOS.append((str(tag), worst))
+    return worst
+
+
+def report(title):
+    """what the last test of a file prints under -s: the ratios recorded since the previous report (the files of one pytest process
+    share this module, and each prints its own), the largest first"""
+    global _reported
+    mine = RATIOS[_reported:]
+    _reported = len(RATIOS)
+    if not mine:
+        print("\n%s: assert_gn_sums was not called" % title)
+        return
+    print("\n%s: %d calls of assert_gn_sums, largest error / bound = %.3f" % (title, len(mine), max(r for _, r in mine)))
+    groups = {}      # a tag up to its first digit names the group ("kernel variants:", "sensor batch push", ...)
+    for tag, r in mine:
+        key = re.split(r"\d", tag, maxsplit=1)[0].strip() or tag
+        n, worst = groups.get(key, (0, 0.0))
+        groups[key] = (n + 1, max(worst, r))
+    for key, (n, worst) in groups.items():
+        print("    %-40s %4d calls, largest error / bound %.3f" % (key, n, worst))
+    for tag, r in sorted(mine, key=lambda e: -e[1])[:5]:
+        print("        %-100s %.3f" % (tag[:100], r))

@@ -7,6 +7,7 @@ import pytest
 
 import dvo_amd as dvo
 import orc
+import gn_sums
 from util import K640, TOL_BACKWARD, TOL_H_REL, TOL_POSE, TOL_UPD_ABS, TOL_UPD_REL, assert_composed, backward_error, frames
 
 pytestmark = pytest.mark.gpu
@@ -82,11 +83,18 @@ def test_warp_image_bit_exact(level):
 
 
 # ---------------------------------------------------------------- Track::optimize
-def _gn_compare(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, cfg=None, crop=True):
+def _gn_compare(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, cfg=None, crop=True, group="plain levels"):
     o = orc.optimize(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, crop=crop, want_mask=True)
     r = dvo.optimize(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, cfg=cfg, want_mask=True)
     np.testing.assert_array_equal(r["mask"], o["mask"])          # pixel selection: bit exact
     assert r["n_valid"] == o["n_valid"]
+    # the comparison that binds (tests/gn_sums.py): every sum within the rounding of the kernel's own reduction
+    # tree of the exact sum of the oracle's per-pixel terms, per entry; without a contributing pixel every sum is exactly zero
+    t = orc.optimize_terms(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, crop=crop)
+    np.testing.assert_array_equal(t["index"], np.flatnonzero(o["mask"].ravel()))
+    gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), group + ": %dx%d level %d%s" % (
+        ref_gray.shape[1], ref_gray.shape[0], level, "" if cfg is None else " ppt %d lds %d crop %d" % (
+            cfg.gn_pixels_per_thread, cfg.gn_use_lds_patch, cfg.crop_enable)))
     if o["n_valid"] == 0:
         assert r["residual"] == np.float32(-1) and not r["xi_update"].any()
         return o, r
@@ -102,6 +110,7 @@ def _gn_compare(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, cfg=None
 
 
 @pytest.mark.parametrize("level", [0, 1, 2, 3])
+@gn_sums.must_be_used
 def test_gn_step_parity_every_level(level):
     g, d, s, _ = frames()
     ref = orc.OFrame(g[0], d[0], s[0], K640, 4, 1)
@@ -111,6 +120,7 @@ def test_gn_step_parity_every_level(level):
     assert o["n_valid"] > 500
 
 
+@gn_sums.must_be_used
 def test_gn_step_invalid_pixels_borders_and_crop_off():
     g, d, s, _ = frames()
     ref = orc.OFrame(g[0], d[0], s[0], K640, 3, 2)
@@ -125,12 +135,13 @@ def test_gn_step_invalid_pixels_borders_and_crop_off():
     rs[:, :80] = 0.003; rs[:, 80:] = 0.8          # both clamps of optimize.cpp:83
     rg[60, 60:70] = 0.0
     xi = np.array([0.03, -0.02, 0.01, 0.01, 0.02, -0.015], np.float32)  # large: many warps leave the image
-    _gn_compare(og, rg, rd, rs, K, xi, 2)
+    _gn_compare(og, rg, rd, rs, K, xi, 2, group="holed frame")
     cfg = dvo.default_config(crop_enable=0)
-    _gn_compare(og, rg, rd, rs, K, xi, 2, cfg=cfg, crop=False)
+    _gn_compare(og, rg, rd, rs, K, xi, 2, cfg=cfg, crop=False, group="holed frame")
 
 
 def test_gn_step_no_valid_pixels():
+    # (the one caller of _gn_compare whose term list is empty by design: there the bound demands that every sum is exactly zero)
     z = np.zeros((30, 40), np.float32)
     K = np.array([[30, 0, 20], [0, 30, 15], [0, 0, 1]], np.float32)
     _gn_compare(z + 0.5, z + 0.5, z, z + 0.5, K, np.zeros(6, np.float32), 0)
@@ -343,6 +354,7 @@ def test_bad_arguments_return_status_not_abort():
 
 # ---------------------------------------------------------------- kernel variants (tiling / LDS patch) agree
 @pytest.mark.parametrize("lds,ppt,group", [(0, 1, 1), (0, 2, 2), (0, 4, 1), (0, 4, 4), (0, 8, 4), (8, 1, 0), (8, 4, 0), (2, 2, 0), (16, 8, 0)])
+@gn_sums.must_be_used
 def test_gn_kernel_variants_match_oracle(lds, ppt, group):
     g, d, s, _ = frames()
     ref = orc.OFrame(g[0], d[0], s[0], K640, 4, 1)
@@ -353,7 +365,7 @@ def test_gn_kernel_variants_match_oracle(lds, ppt, group):
     cfg = dvo.default_config(gn_use_lds_patch=lds, gn_pixels_per_thread=ppt, gn_gather_group=group)
     for level in (1, 3):
         rgl = rg if level == 3 else ref.gray(level)
-        _gn_compare(obj.gray(level), rgl, ref.depth(level), ref.sigma(level), ref.K(level), xi, level, cfg=cfg)
+        _gn_compare(obj.gray(level), rgl, ref.depth(level), ref.sigma(level), ref.K(level), xi, level, cfg=cfg, group="kernel variants")
 
 
 # ---------------------------------------------------------------- schedule variants leave the results untouched
@@ -412,6 +424,7 @@ def test_batch_many_iterations_every_sequence_matches_single():
 
 
 # ---------------------------------------------------------------- BASELINE config 4 (1920x1080, 5 levels) and ragged sizes
+@gn_sums.must_be_used
 def test_syn1080_five_level_parity():
     """Synthetic 1920x1080 dense alignment, 5-level pyramid, culls 0 (BASELINE.json configs[3]): pyramid bit exact,
     one Gauss-Newton step per level (masks bit exact) and a fixed-iteration track against the oracle."""
@@ -428,7 +441,7 @@ def test_syn1080_five_level_parity():
     xi = np.array([0.002, -0.001, 0.003, 0.002, -0.001, 0.001], np.float32)
     cfg = dvo.default_config(crop_enable=0)
     for l in (0, 2, 4):   # 120x67, 480x270, 1920x1080
-        o, _ = _gn_compare(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False)
+        o, _ = _gn_compare(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False, group="full-HD pyramid")
         assert o["n_valid"] > 0.5 * ref.gray(l).size
     cfg = dvo.default_config(fixed_iterations=2, crop_enable=0)
     xo, lo = orc.track(obj, ref, crop=False, fixed_iters=2)
@@ -438,6 +451,7 @@ def test_syn1080_five_level_parity():
 
 
 @pytest.mark.parametrize("w,h,levels,culls", [(322, 243, 3, 0), (161, 121, 2, 0), (646, 486, 4, 1), (37, 29, 1, 0)])
+@gn_sums.must_be_used
 def test_ragged_sizes_parity(w, h, levels, culls):
     """Widths that are not multiples of 4 (unaligned rows), tiles that end mid-row, odd pyramid halvings."""
     from dvo_amd import synth
@@ -450,7 +464,7 @@ def test_ragged_sizes_parity(w, h, levels, culls):
     xi = np.array([0.004, -0.003, 0.002, 0.003, -0.002, 0.004], np.float32)
     cfg = dvo.default_config(crop_enable=0)
     for l in range(levels):
-        _gn_compare(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False)
+        _gn_compare(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False, group="ragged sizes")
     got = dvo.Transform.warpImage(xi, ref.gray(levels - 1), ref.depth(levels - 1), ref.K(levels - 1))
     np.testing.assert_array_equal(got, orc.warp_image(xi, ref.gray(levels - 1), ref.depth(levels - 1), ref.K(levels - 1)))
     xo, lo = orc.track(obj, ref, crop=False)
@@ -545,6 +559,7 @@ def test_batch_prefetch_changes_no_result():
 
 
 @pytest.mark.parametrize("w,h", [(192, 160), (96, 320)])
+@gn_sums.must_be_used
 def test_narrow_2d_tiles_parity(w, h):
     """The 32- and 16-column 2-D tiles of k_track_gn (GnTiling: widths that are multiples of 32 / 16 but not 64) at 4 pixels per
     thread -- until now only covered by the host-compiled geometry check: 192x160 -> levels 96x80 (32-wide tiles) and 192x160 (64);
@@ -561,12 +576,75 @@ def test_narrow_2d_tiles_parity(w, h):
     xi = np.array([0.004, -0.003, 0.002, 0.003, -0.002, 0.004], np.float32)
     cfg = dvo.default_config(crop_enable=0, gn_pixels_per_thread=4)
     for l in range(2):
-        _gn_compare(obj.gray(l), rg if l == 1 else ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False)
+        _gn_compare(obj.gray(l), rg if l == 1 else ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, crop=False, group="narrow tiles")
     cfg = dvo.default_config(crop_enable=0, gn_pixels_per_thread=4, fixed_iterations=3)
     xo, lo = orc.track(obj, ref, crop=False, fixed_iters=3)
     xg, lg = dvo.track(g[1], g[0], d[0], s[0], K, 2, 0, cfg=cfg)
     assert lg["n_iter"][:2] == [3, 3] == lo["n_iter"]
     np.testing.assert_allclose(xg, xo, rtol=0, atol=5e-5)
+
+
+def _blobs(shape, frac, rng, rmax):
+    """random discs (radius 0.7 .. rmax pixels) until they cover `frac` of the image"""
+    h, w = shape
+    m = np.zeros(shape, bool)
+    yy, xx = np.mgrid[0:h, 0:w]
+    while m.mean() < frac:
+        cx, cy, r = rng.uniform(0, w), rng.uniform(0, h), rng.uniform(0.7, rmax)
+        x0, x1, y0, y1 = int(max(cx - r - 1, 0)), int(min(cx + r + 2, w)), int(max(cy - r - 1, 0)), int(min(cy + r + 2, h))
+        m[y0:y1, x0:x1] |= (xx[y0:y1, x0:x1] - cx) ** 2 + (yy[y0:y1, x0:x1] - cy) ** 2 <= r * r
+    return m
+
+
+def _bad_tap_nearby(ref_gray, ref_depth, K, xi, mask):
+    """Per contributing pixel of `mask`: does the 4 x 4 neighbourhood of its warped position (columns floor(u) - 1 .. floor(u) + 2,
+    rows likewise: what the samplers may touch) hold an INVALID sample or leave the image?  The position in float64 from the
+    oracle's pose: a pixel whose float32 position rounds across an integer may be classed the other way, which a count can bear."""
+    h, w = ref_gray.shape
+    Rt = orc.pose_from_xi(xi, -1.0).astype(np.float64)
+    R, t = Rt[:9].reshape(3, 3), Rt[9:]
+    K = np.asarray(K, np.float64).reshape(3, 3)
+    y, x = np.nonzero(mask)
+    d = ref_depth[y, x].astype(np.float64)
+    Y = R @ np.stack([d * (x - K[0, 2]) / K[0, 0], d * (y - K[1, 2]) / K[1, 1], d]) + t[:, None]
+    x0 = np.floor(Y[0] * K[0, 0] / Y[2] + K[0, 2]).astype(int); y0 = np.floor(Y[1] * K[1, 1] / Y[2] + K[1, 2]).astype(int)
+    pad = np.full((h + 8, w + 8), True); pad[4:-4, 4:-4] = ref_gray == INV      # outside the image counts as bad
+    bad = np.zeros(len(x), bool)
+    for dy in range(-1, 3):
+        for dx in range(-1, 3):
+            bad |= pad[np.clip(y0 + dy, -4, h + 3) + 4, np.clip(x0 + dx, -4, w + 3) + 4]
+    return bad
+
+
+@pytest.mark.parametrize("ppt", [1, 4, 8])
+@gn_sums.must_be_used
+def test_gn_step_deferred_queue_under_tum_like_holes(ppt):
+    """Aimed at gn_tile's deferred queue (the LDS queue of border / INVALID-tap pixels evaluated after the main loop): the finest level
+    of a 4-level pyramid of the 640x480 frame without culling (level 3, 640 x 480) with about a quarter of the reference lost in blobs
+    -- an eighth of the gray INVALID, an eighth of the depth zero: the hole density DESIGN.md section 10 gives for TUM depth maps --
+    and broken strips along all four borders, at a pose that moves many pixels into the border band.  Masks bit-exact, then every
+    sum inside the reduction bound: a queue entry lost, taken twice or read from a neighbouring wave's queue is at least one
+    pixel's terms, far outside it.  The oracle's own mask must show that the case does exercise the queue."""
+    g, d, s, _ = frames()
+    ref = orc.OFrame(g[0], d[0], s[0], K640, 4, 0)
+    obj = orc.OFrame(g[1], d[1], s[1], K640, 4, 0)
+    rg, rd, rs, K = ref.gray(3), ref.depth(3), ref.sigma(3), ref.K(3)
+    og = obj.gray(3)
+    assert rg.shape == (480, 640)
+    rng = np.random.RandomState(31)
+    rg[_blobs(rg.shape, 0.125, rng, 4.0)] = INV
+    rd[_blobs(rd.shape, 0.125, rng, 4.0)] = 0.0
+    for b in (slice(0, 3), slice(-3, None)):
+        rg[b, ::2] = INV; rg[::2, b] = INV
+        rd[b, 1::3] = 0.0; rd[1::3, b] = 0.0
+    xi = np.array([0.02, -0.015, 0.01, 0.01, 0.012, -0.02], np.float32)
+    cfg = dvo.default_config(gn_pixels_per_thread=ppt)
+    o, r = _gn_compare(og, rg, rd, rs, K, xi, 3, cfg=cfg, group="deferred queue")
+    assert o["n_valid"] > 100000
+    queued = _bad_tap_nearby(rg, rd, K, xi, o["mask"])
+    assert queued.mean() >= 0.10, queued.mean()     # (about a quarter)
+    yy, xx = np.nonzero(o["mask"])
+    assert (yy < 16).any() and (yy >= 464).any() and (xx < 64).any() and (xx >= 576).any()   # tiles on all four borders contribute
 
 
 def test_levels_smaller_than_4x4_are_refused():
@@ -584,6 +662,7 @@ def test_levels_smaller_than_4x4_are_refused():
     bt.close()
 
 
+@gn_sums.must_be_used
 def test_randomized_gn_step_sweep():
     """Fixed-seed sweep of Track::optimize (optimize.cpp:10-99) over what the targeted tests fix by hand: image sizes from the
     4 x 4 minimum up (so every tile geometry of k_track_gn -- 64 / 32 / 16-column 2-D tiles, raster tiles, partial last tiles),
@@ -626,6 +705,8 @@ def test_randomized_gn_step_sweep():
         np.testing.assert_array_equal(r["mask"], o["mask"], err_msg=str(tag))
         assert r["n_valid"] == o["n_valid"], tag
         checked += 1
+        t = orc.optimize_terms(og, rg, rd, rs, K, xi, level, crop=crop)
+        gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), "sweep case %d %dx%d level %d ppt %d group %d crop %d" % tag)
         if o["n_valid"] == 0:
             assert r["residual"] == np.float32(-1) and not r["xi_update"].any(), tag
             continue
@@ -883,3 +964,9 @@ def test_single_handle_one_launch_schedule_edge_cases():
             assert res[0][2][1] == [3, 3, 3, 3]
         if name == "no_depth":
             assert res[0][1][1] == [1, 1, 1, 1] and np.array_equal(res[0][1][0], np.eye(4, dtype=np.float32))
+
+
+def test_zz_report_reduction_bound_ratios():
+    """last in the file: under -s, the largest error / bound ratio of every assert_gn_sums call of this process"""
+    gn_sums.report("test_gpu_parity")
+    assert all(r <= 1.0 for _, r in gn_sums.RATIOS)

@@ -8,6 +8,7 @@ import pytest
 import dvo_amd as dvo
 import orc
 from dvo_amd import synth
+import gn_sums
 from util import K640, TOL_BACKWARD, assert_composed, backward_error
 
 pytestmark = pytest.mark.gpu
@@ -122,6 +123,7 @@ def _rank_deficient_case(kind):
 
 
 @pytest.mark.parametrize("kind", ["ramp", "stripes"])
+@gn_sums.must_be_used
 def test_rank_deficient_solve_matches_min_norm_solution(kind):
     """No vertical image gradient => J's second column is exactly zero => H is singular: LDL^T hits a zero pivot and the device
     takes the eigen pseudo-inverse branch of solve6 (cut sqrt(lambda) <= 2 FLT_EPSILON sum, as cv::solve(DECOMP_SVD)).  The update
@@ -135,6 +137,10 @@ def test_rank_deficient_solve_matches_min_norm_solution(kind):
     f = orc.optimize(obj, ref, depth, sigma, K, xi, 0, crop=False, variant=1)
     assert r["n_valid"] == o["n_valid"] > 1000
     np.testing.assert_array_equal(r["mask"], o["mask"])
+    # every sum inside the reduction bound of its own terms (tests/gn_sums.py); the sums of the vanishing column: exactly zero
+    t = orc.optimize_terms(obj, ref, depth, sigma, K, xi, 0, crop=False)
+    assert not t["J"][:, 1].any()
+    gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), "rank deficient (%s)" % kind)
     H = orc.upper_to_full(r["H"])
     assert np.abs(H[1]).max() == 0.0 and np.abs(H[:, 1]).max() == 0.0       # exactly singular: the fast path cannot be taken
     assert np.linalg.matrix_rank(H) <= 5
@@ -147,6 +153,7 @@ def test_rank_deficient_solve_matches_min_norm_solution(kind):
     np.testing.assert_allclose(r["xi_update"], xn, rtol=0, atol=2e-4 * un + 2e-7)
 
 
+@gn_sums.must_be_used
 def test_solve_of_an_all_zero_system_is_zero():
     """A constant image has no gradient at all: H = 0, g = 0 -> zero update, residual = mean r^2 (optimize.cpp:92-98)."""
     h, w = 40, 56
@@ -157,5 +164,14 @@ def test_solve_of_an_all_zero_system_is_zero():
     r = dvo.optimize(obj, ref, depth, sigma, K, np.zeros(6, np.float32), 0, cfg=cfg)
     o = orc.optimize(obj, ref, depth, sigma, K, np.zeros(6, np.float32), 0, crop=False)
     assert r["n_valid"] == o["n_valid"] > 0
+    t = orc.optimize_terms(obj, ref, depth, sigma, K, np.zeros(6, np.float32), 0, crop=False)
+    assert not t["J"].any() and t["r"].all()
+    gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), "all-zero system")     # H and g exactly zero, sum_r2 inside its bound
     assert not r["xi_update"].any() and not o["xi_update"].any()
     np.testing.assert_allclose(r["residual"], o["residual"], rtol=2e-5)
+
+
+def test_zz_report_reduction_bound_ratios():
+    """last in the file: under -s, the largest error / bound ratio of every assert_gn_sums call of this process"""
+    gn_sums.report("test_gpu_parity_scale")
+    assert all(r <= 1.0 for _, r in gn_sums.RATIOS)

@@ -11,8 +11,10 @@ import numpy as np
 import pytest
 
 import dvo_amd as dvo
+import gn_sums
 import lockstep
 import orc
+from dvo_amd import synth
 from util import K640, TOL_BACKWARD, TOL_H_REL, backward_error, frames
 
 pytestmark = pytest.mark.gpu
@@ -51,11 +53,22 @@ def _logbits(lg, L):
 IDX = [[0, 1, 2, 3, 4], [1, 2, 3, 4, 5], [2, 3, 4, 5, 0], [3, 2, 5, 4, 1], [4, 1, 4, 3, 2]]
 
 
-def _sensor_run(cfg, B, idx, quality=True, acts=None, kf=False, feed="device", bad=None, cams=None, sigma=0.1):
+def _frames_of(size, sigma):
+    """six frames and their intrinsics: util.frames() at 640x480, the same scene rendered smaller otherwise"""
+    w, h = size
+    if size == (640, 480):
+        return frames(6, sigma=sigma)[:3] + (K640,)
+    K = np.array(K640, np.float32).copy()
+    K[0] *= w / 640.0; K[1] *= h / 480.0
+    g, d, s, _ = synth.sequence(6, width=w, height_px=h, K=K, seed=42, sigma_value=sigma)
+    return g.numpy(), d.numpy(), s.numpy(), K
+
+
+def _sensor_run(cfg, B, idx, quality=True, acts=None, kf=False, feed="device", bad=None, cams=None, sigma=0.1, size=(640, 480)):
     """idx[k][b]: frame of sequence b at push k; acts[k] or None; bad[k]: sequences fed an all-invalid frame at push k; cams: {k: K
     table}.  Returns per push dict(xi, T, status, logs, q, world)."""
-    g, d, s, _ = frames(6, sigma=sigma)
-    bt = dvo.Batch(B, K640, 640, 480, 4, 1, cfg=cfg)
+    g, d, s, K = _frames_of(size, sigma)
+    bt = dvo.Batch(B, K, size[0], size[1], 4, 1, cfg=cfg)
     if kf:
         bt.set_keyframe_tracking(True)
     if quality:
@@ -192,14 +205,31 @@ def test_sensor_record_is_the_last_solve(mode):
     assert all(q["status"] == STARTED for q in outs[0]["q"]) or acts is not None
 
 
-def _sensor_oracle(cfg, kf=False, B=3):
-    """the record of every TRACKED sequence against orc.optimize at the input pose of the finest level's last iteration (from the log);
-    with keyframes, the reference is the frame that started or last promoted the sequence"""
-    g, d, s, _ = frames(6, sigma=0.1)
-    idx = IDX[:4]
-    outs = _sensor_run(cfg, B, [r[:B] for r in idx], kf=kf)
-    ref_of = list(idx[0][:B])
+def _wide_idx(B):
+    """four pushes for B sequences: IDX itself up to five; beyond, sequence b sees frame (k + b) mod 6 at push k, so that neighbouring
+    sequences and sequences 8 apart (the same slot of the next solve workgroup) are on different frames at every push -- a partial
+    row, a solve slot or a record picked up from another sequence cannot go unnoticed"""
+    if B <= 5:
+        return [r[:B] for r in IDX[:4]]
+    idx = [[(k + b) % 6 for b in range(B)] for k in range(4)]
+    for r in idx:
+        assert all(r[b] != r[b + 1] for b in range(B - 1)) and all(r[b] != r[b + 8] for b in range(B - 8))
+    return idx
+
+
+def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1):
+    """the record of every TRACKED sequence against the oracle at the input pose of the finest level's last iteration (from the log):
+    the max-scaled comparison with orc.optimize, then the one that binds -- H, g, sum_r2 per entry inside the reduction bound of the
+    exact sums of orc.optimize_terms (tests/gn_sums.py).  The records are the batch path's own sums (k_track_gn or the LDS-patch /
+    fused / one-workgroup kernels over many sequences, then sum_partial_rows / sum_partial_class in the solve), observable nowhere
+    else.  With keyframes, the reference is the frame that started or last promoted the sequence."""
+    g, d, s, K = _frames_of(size, sigma)
+    idx = _wide_idx(B)
+    outs = _sensor_run(cfg, B, idx, kf=kf, size=size, sigma=sigma)
+    ref_of = list(idx[0])
     crop = bool(cfg.crop_enable)
+    depth = gn_sums.depth_for_cfg(cfg)
+    before = gn_sums.nonempty_calls()
     n = 0
     for k in range(1, len(idx)):
         o = outs[k]
@@ -209,14 +239,16 @@ def _sensor_oracle(cfg, kf=False, B=3):
             L = 3
             it = int(lg["n_iter"][L]) - 1
             x_in = lg["xi_after"][L][it - 1] if it > 0 else lg["xi_after"][L - 1][int(lg["n_iter"][L - 1]) - 1]
-            ref = orc.OFrame(g[ref_i], d[ref_i], s[ref_i], K640, 4, 1)
-            obj = orc.OFrame(g[obj_i], d[obj_i], s[obj_i], K640, 4, 1)
+            ref = orc.OFrame(g[ref_i], d[ref_i], s[ref_i], K, 4, 1)
+            obj = orc.OFrame(g[obj_i], d[obj_i], s[obj_i], K, 4, 1)
             r = orc.optimize(obj.gray(L), ref.gray(L), ref.depth(L), ref.sigma(L), ref.K(L), x_in, L, crop=crop)
-            where = "push %d seq %d" % (k, b)
+            where = "push %d seq %d of %d (%dx%d)" % (k, b, B, size[0], size[1])
             assert r["n_valid"] == q["n_valid"], where
             np.testing.assert_allclose(q["H"], r["H"], rtol=0, atol=TOL_H_REL * np.abs(r["H"]).max(), err_msg=where)
-            np.testing.assert_allclose(q["g"], r["g"], rtol=0, atol=TOL_H_REL * np.abs(r["H"]).max(), err_msg=where)
+            np.testing.assert_allclose(q["g"], r["g"], rtol=0, atol=TOL_H_REL * max(np.abs(r["g"]).max(), 1e-30), err_msg=where)
             np.testing.assert_allclose(q["sum_r2"], r["sum_r2"], rtol=SUM_R2_REL, err_msg=where)
+            t = orc.optimize_terms(obj.gray(L), ref.gray(L), ref.depth(L), ref.sigma(L), ref.K(L), x_in, L, crop=crop)
+            gn_sums.assert_gn_sums(q, t, depth, "sensor batch " + where)
             n += 1
         if kf:
             key = o["world"][2]
@@ -224,6 +256,7 @@ def _sensor_oracle(cfg, kf=False, B=3):
                 if key[b] or o["status"][b] == STARTED:
                     ref_of[b] = idx[k][b]
     assert n == B * (len(idx) - 1)
+    assert gn_sums.nonempty_calls() >= before + n // 2, "the reduction bound saw too few non-empty term lists"
 
 
 def test_sensor_pairs_match_the_oracle():
@@ -236,6 +269,29 @@ def test_keyframe_pairs_match_the_oracle():
 
 def test_lds_patch_matches_the_oracle():
     _sensor_oracle(_cfg(gn_use_lds_patch=1))
+
+
+def test_batch_size_off_the_solve_workgroup_matches_the_oracle():
+    """11 sequences: k_gn_solve takes 8 per workgroup, so the second workgroup is partly empty and sequences 8 .. 10 sit in other slots
+    of it than 0 .. 2 of the first"""
+    _sensor_oracle(_cfg(), B=11)
+
+
+@pytest.mark.parametrize("variant", ["adaptive_off", "streams", "fused_tiles", "single_launch"])
+def test_schedule_variants_match_the_oracle(variant):
+    """The schedules of test_schedules_give_the_same_records, each with its own sums inside the reduction bound.  Two streams need more
+    than 16 sequences (19: not a multiple of 8 either).  k_track_level (track_fused_tiles) and k_track_gn_fused (track_single_launch)
+    only take levels of a few tiles, and the record is the FINEST level's: those two run on 160x120 frames (finest level 80 x 60,
+    five raster tiles), crop off so that the 40 x 30 level keeps its pixels, and sigma 0.5: at 0.1 the ten-fold over-relaxed iteration
+    throws half of these small sequences out of the image, and a record without a contributing pixel tests no sum."""
+    if variant == "adaptive_off":
+        _sensor_oracle(_cfg(track_adaptive=-1))
+    elif variant == "streams":
+        _sensor_oracle(_cfg(track_streams=2), B=19)
+    elif variant == "fused_tiles":
+        _sensor_oracle(_cfg(track_fused_tiles=8, crop_enable=0), size=(160, 120), sigma=0.5)
+    else:
+        _sensor_oracle(_cfg(track_single_launch=1, crop_enable=0), size=(160, 120), sigma=0.5)
 
 
 def test_flags_capped_fixed_and_no_valid():
@@ -398,11 +454,13 @@ class QualityReplay(lockstep.Replay):
                 assert o["n_valid"] == int(log["n_valid"][l][it]), self._where("level %d iteration %d" % (l, it))
                 if l == lockstep.TOP:
                     self.last = o
+                    self.last_args = (obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi.copy(), l, self.crop)
                 xi = np.asarray(log["xi_after"][l][it], np.float32).copy()
                 self.n_iterations += 1
         return xi
 
 
+@gn_sums.must_be_used
 def test_mono_records_match_the_oracle():
     g, init, ml = _mono_frames()
     B = 2
@@ -428,8 +486,11 @@ def test_mono_records_match_the_oracle():
             where = "call %d seq %d" % (k, q)
             assert r["n_valid"] == o["n_valid"], where
             np.testing.assert_allclose(r["H"], o["H"], rtol=0, atol=TOL_H_REL * np.abs(o["H"]).max(), err_msg=where)
-            np.testing.assert_allclose(r["g"], o["g"], rtol=0, atol=TOL_H_REL * np.abs(o["H"]).max(), err_msg=where)
+            np.testing.assert_allclose(r["g"], o["g"], rtol=0, atol=TOL_H_REL * max(np.abs(o["g"]).max(), 1e-30), err_msg=where)
             np.testing.assert_allclose(r["sum_r2"], o["sum_r2"], rtol=SUM_R2_REL, err_msg=where)
+            a = reps[q].last_args      # ... and per entry inside the reduction bound of the exact sums at the same inputs
+            t = orc.optimize_terms(*a[:7], crop=a[7])
+            gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(None), "mono batch " + where)
             n += 1
     mb.close()
     assert n == B * (len(orders[0]) - 1)
@@ -481,3 +542,9 @@ def test_device_rule_restarts_the_lost_sequences():
     exp = np.full(B, TRACKED); exp[bad] = STARTED
     np.testing.assert_array_equal(statuses[3], exp)
     np.testing.assert_array_equal(statuses[2], np.full(B, TRACKED))
+
+
+def test_zz_report_reduction_bound_ratios():
+    """last in the file: under -s, the largest error / bound ratio of every assert_gn_sums call of this process"""
+    gn_sums.report("test_gpu_track_quality")
+    assert all(r <= 1.0 for _, r in gn_sums.RATIOS)

@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import gn_sums
 import orc
 from real_data import K_LOGICOOL, frames_from_fixture, ingest_np, undistort_nearest_np, bgr2gray_u8
 
@@ -97,6 +98,7 @@ def test_mono_pipeline_on_logicool0_frame_by_frame_given_the_oracle_state(tmp_pa
 
 
 @pytest.mark.gpu
+@gn_sums.must_be_used
 def test_gn_steps_on_logicool0_match_the_oracle_at_every_iteration():
     """Track::optimize (optimize.cpp:10-99) on the real frames, at every input pose the oracle's tracker visits: contributing-pixel
     masks bit-exact, H within 1e-6 max|H|, and the update solves the oracle's normal equations to a backward error <= 2e-6 (a
@@ -123,6 +125,9 @@ def test_gn_steps_on_logicool0_match_the_oracle_at_every_iteration():
                 np.testing.assert_array_equal(r["mask"], o["mask"])
                 assert r["n_valid"] == o["n_valid"] > 0
                 np.testing.assert_allclose(r["H"], o["H"], rtol=0, atol=1e-6 * np.abs(o["H"]).max())
+                # H, g and sum_r2 per entry inside the reduction bound of the oracle's per-pixel terms (tests/gn_sums.py): the one that binds
+                t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi_in, l)
+                gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(None), "logicool0 frame %d level %d iteration %d" % (i, l, it))
                 H = orc.upper_to_full(o["H"]); x = r["xi_update"].astype(np.float64)
                 back = np.abs(H @ x - o["g"]).max() / (np.abs(H) @ np.abs(x) + np.abs(o["g"])).max()
                 assert back <= 2e-6, (i, l, it, back)
@@ -250,6 +255,7 @@ def test_kinect_sequence_fixture_has_real_holes(name):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", KINECT_SETS)
+@gn_sums.must_be_used
 def test_sensor_depth_tracking_on_kinect_frames_matches_the_oracle_at_every_iteration(name):
     """Tracker::track (tracker.cpp:22-85) as odometrizeUsingDepth runs it (Frame(g,d,s,K,4,1), sigma 0.1 / 1.0, INVALID gray in the
     depth holes: transform.cpp:60-76) on real Kinect IR + depth frames with 6 % holes.  Along the GPU's own trajectory every
@@ -276,6 +282,8 @@ def test_sensor_depth_tracking_on_kinect_frames_matches_the_oracle_at_every_iter
             r = dvo.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg, want_mask=True)
             o = orc.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, want_mask=True)
             np.testing.assert_array_equal(r["mask"], o["mask"])
+            t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l)
+            gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), "%s frame %d level %d first pose" % (name, i, l))
             for it in range(lg["n_iter"][l]):
                 o = orc.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l)
                 assert o["n_valid"] == lg["n_valid"][l][it], (i, l, it)
@@ -287,6 +295,8 @@ def test_sensor_depth_tracking_on_kinect_frames_matches_the_oracle_at_every_iter
                 np.testing.assert_allclose(lg["residual"][l][it], o["residual"], rtol=1e-4)
                 r = dvo.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, cfg=cfg)   # the same step as an operator call
                 assert r["n_valid"] == o["n_valid"]
+                t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l)
+                gn_sums.assert_gn_sums(r, t, gn_sums.depth_for_cfg(cfg), "%s frame %d level %d iteration %d" % (name, i, l, it))
                 upd = r["xi_update"].astype(np.float64)
                 H = orc.upper_to_full(o["H"])
                 back = np.abs(H @ upd - o["g"]).max() / (np.abs(H) @ np.abs(upd) + np.abs(o["g"])).max()
@@ -296,3 +306,10 @@ def test_sensor_depth_tracking_on_kinect_frames_matches_the_oracle_at_every_iter
                 n_checked += 1
     vo_raw.close(); vo_flt.close()
     assert n_checked >= 12
+
+
+@pytest.mark.gpu
+def test_zz_report_reduction_bound_ratios():
+    """last in the file: under -s, the largest error / bound ratio of every assert_gn_sums call of this process"""
+    gn_sums.report("test_real_data")
+    assert all(r <= 1.0 for _, r in gn_sums.RATIOS)
