@@ -220,13 +220,8 @@ int dvo_batch_create(int n_seq, const float K[9], int width, int height, int lev
 int dvo_batch_destroy(dvo_batch* b)
 {
     if (!b) return DVO_OK;
-    if (b->mono) {
-        (void)select_device(b->mono->device);
-        if (b->mono->stream) (void)hipStreamSynchronize(b->mono->stream);
-    } else {
-        (void)select_device(b->impl.device);
-        if (b->impl.stream) (void)hipStreamSynchronize(b->impl.stream);
-    }
+    (void)select_device(b->device());
+    if (b->stream()) (void)hipStreamSynchronize(b->stream());
     delete b;
     return DVO_OK;
 }
@@ -286,20 +281,16 @@ int dvo_batch_push_raw_host(dvo_batch* b, const uint8_t* rgb, int channels, cons
     DVO_NOT_MONO(b);
     FrameInput in;
     DVO_TRY(raw_input(b, rgb, channels, depth16, depth_scale, in));
-    Batch& B = b->impl;
-    const size_t px = (size_t)B.n_seq * B.g.src_w * B.g.src_h;
-    return B.push_host_frame(rgb, px * (size_t)channels, depth16, px * 2, nullptr, 0, in);
+    return b->impl.push_host_frame(rgb, depth16, nullptr, in);
 }
 
 int dvo_batch_push_host(dvo_batch* b, const float* gray, const float* depth, const float* sigma)
 {
     if (!b || !gray || !depth || !sigma) return DVO_ERR_BAD_ARGUMENT;
     DVO_NOT_MONO(b);
-    Batch& B = b->impl;
-    const size_t n = (size_t)B.n_seq * B.g.src_w * B.g.src_h * sizeof(float);
     FrameInput in;
     in.gray = gray; in.depth = depth; in.sigma = sigma;   // (replaced by the staging pointers)
-    return B.push_host_frame(gray, n, depth, n, sigma, n, in);
+    return b->impl.push_host_frame(gray, depth, sigma, in);
 }
 
 int dvo_batch_last_poses(dvo_batch* b, float* xi_rel, float* T_rel)
@@ -330,34 +321,20 @@ int dvo_batch_copy_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_de
 int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log)
 {
     if (!b || !log || seq < 0) return DVO_ERR_BAD_ARGUMENT;
-    if (b->mono) {  // the log of the last tracked frame of a mono batch
-        MonoBatch& M = *b->mono;
-        if (seq >= M.n_seq) return DVO_ERR_BAD_ARGUMENT;
-        if (M.latest_id < 1) return DVO_ERR_NOT_READY;
-        DVO_TRY(select_device(M.device));
-        DVO_HIP(hipMemcpyAsync(log, M.trk.log.as<dvo_track_log>() + seq, sizeof *log, hipMemcpyDeviceToHost, M.stream));
-        DVO_HIP(hipStreamSynchronize(M.stream));
-        return DVO_OK;
-    }
-    if (seq >= b->impl.n_seq) return DVO_ERR_BAD_ARGUMENT;
-    Batch& B = b->impl;
-    if (!B.have_poses) return DVO_ERR_NOT_READY;
-    DVO_TRY(select_device(B.device));
-    DVO_HIP(hipMemcpyAsync(log, B.trk.log.as<dvo_track_log>() + seq, sizeof *log, hipMemcpyDeviceToHost, B.stream));
-    DVO_HIP(hipStreamSynchronize(B.stream));
+    if (seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    // (a mono batch: the log of the last tracked frame, so not before the second call)
+    if (b->mono ? b->mono->latest_id < 1 : !b->impl.have_poses) return DVO_ERR_NOT_READY;
+    DVO_TRY(select_device(b->device()));
+    DVO_HIP(hipMemcpyAsync(log, b->trk().log.as<dvo_track_log>() + seq, sizeof *log, hipMemcpyDeviceToHost, b->stream()));
+    DVO_HIP(hipStreamSynchronize(b->stream()));
     return DVO_OK;
 }
 
 int dvo_batch_synchronize(dvo_batch* b)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (b->mono) {
-        DVO_TRY(select_device(b->mono->device));
-        DVO_HIP(hipStreamSynchronize(b->mono->stream));
-        return DVO_OK;
-    }
-    DVO_TRY(select_device(b->impl.device));
-    DVO_HIP(hipStreamSynchronize(b->impl.stream));
+    DVO_TRY(select_device(b->device()));
+    DVO_HIP(hipStreamSynchronize(b->stream()));
     return DVO_OK;
 }
 
@@ -388,33 +365,31 @@ int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable)
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    PoseGuess& G = b->mono ? b->mono->guess : b->impl.guess;
+    PoseGuess& G = b->guess();
     if (xi && G.mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
-    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
-    return G.set_rows(xi, xi_on_device != 0, b->mono ? b->mono->stream : b->impl.stream);
+    DVO_TRY(select_device(b->device()));
+    return G.set_rows(xi, xi_on_device != 0, b->stream());
 }
 
 int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start)
 {
     if (!b || !xi_start) return DVO_ERR_BAD_ARGUMENT;
-    if (b->mono ? b->mono->latest_id < 0 : b->impl.n_push == 0) { set_error("dvo_batch_last_start_poses: nothing has been pushed yet"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
-    const PoseGuess& G = b->mono ? b->mono->guess : b->impl.guess;
+    if (b->pushes() == 0) { set_error("dvo_batch_last_start_poses: nothing has been pushed yet"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    const PoseGuess& G = b->guess();
     if (!G.on()) {   // no mode was ever set: every push started from zero
-        const int n = b->mono ? b->mono->n_seq : b->impl.n_seq;
-        DVO_HIP(hipStreamSynchronize(b->mono ? b->mono->stream : b->impl.stream));
-        memset(xi_start, 0, sizeof(float) * 6 * (size_t)n);
+        DVO_HIP(hipStreamSynchronize(b->stream()));
+        memset(xi_start, 0, sizeof(float) * 6 * (size_t)b->n_seq());
         return DVO_OK;
     }
-    return G.last_start(xi_start, b->mono ? b->mono->stream : b->impl.stream);
+    return G.last_start(xi_start, b->stream());
 }
 
 int dvo_batch_set_track_quality(dvo_batch* b, int enable)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
-    if (b->mono) return b->mono->quality.set(enable != 0, b->mono->trk, b->mono->stream);
-    return b->impl.quality.set(enable != 0, b->impl.trk, b->impl.stream);
+    DVO_TRY(select_device(b->device()));
+    return b->quality().set(enable != 0, b->trk(), b->stream());
 }
 
 // the records of the last push / call: its status (per-sequence path: the device status k_plan wrote; plain pushes: all STARTED on the
@@ -422,17 +397,12 @@ int dvo_batch_set_track_quality(dvo_batch* b, int enable)
 static int track_quality(dvo_batch* b, dvo_track_quality* out, bool to_host)
 {
     if (!b || !out) return DVO_ERR_BAD_ARGUMENT;
-    const bool mono = b->mono != nullptr;
-    TrackQuality& Q = mono ? b->mono->quality : b->impl.quality;
+    TrackQuality& Q = b->quality();
     if (!Q.ready) { set_error("dvo_batch_last_track_quality: the last push / call did not keep quality records (dvo_batch_set_track_quality)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(mono ? b->mono->device : b->impl.device));
-    const Tracker& trk = mono ? b->mono->trk : b->impl.trk;
-    const hipStream_t s = mono ? b->mono->stream : b->impl.stream;
-    const bool planned = mono ? b->mono->act_used : b->impl.act_used;
-    const int* status = planned ? (mono ? b->mono->status.as<int>() : b->impl.status.as<int>()) : nullptr;
-    const bool first = mono ? b->mono->latest_id == 0 : b->impl.n_push == 1;
-    const int all = first ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
-    return to_host ? Q.read_host(trk, status, all, out, s) : Q.launch(trk, status, all, out, s);
+    DVO_TRY(select_device(b->device()));
+    const int* status = b->plan().act_used ? b->plan().status.as<int>() : nullptr;
+    const int all = b->pushes() == 1 ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
+    return to_host ? Q.read_host(b->trk(), status, all, out, b->stream()) : Q.launch(b->trk(), status, all, out, b->stream());
 }
 
 int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out) { return track_quality(b, out, true); }
@@ -509,16 +479,10 @@ int dvo_batch_gather_poses_rccl(dvo_batch* b, void* rccl_comm, int world_size, f
         if (h) all_gather = reinterpret_cast<all_gather_fn>(dlsym(h, "ncclAllGather"));
         if (!all_gather) { set_error("librccl.so (ncclAllGather) could not be loaded"); return DVO_ERR_NOT_READY; }
     }
-    const float* src; size_t n; hipStream_t st; int dev;
-    if (b->mono) {
-        if (b->mono->latest_id < 0) return DVO_ERR_NOT_READY;
-        src = b->mono->xi_world.as<float>(); n = (size_t)b->mono->n_seq * 6; st = b->mono->stream; dev = b->mono->device;
-    } else {
-        if (!b->impl.have_poses) return DVO_ERR_NOT_READY;
-        src = b->impl.trk.xi_out.as<float>(); n = (size_t)b->impl.n_seq * 6; st = b->impl.stream; dev = b->impl.device;
-    }
-    DVO_TRY(select_device(dev));
-    const int rc = all_gather(src, xi_all_dev, n, 7 /* ncclFloat */, rccl_comm, st);
+    if (b->mono ? b->mono->latest_id < 0 : !b->impl.have_poses) return DVO_ERR_NOT_READY;
+    const float* src = b->mono ? b->mono->xi_world.as<float>() : b->impl.trk.xi_out.as<float>();   // (world twists / relative twists)
+    DVO_TRY(select_device(b->device()));
+    const int rc = all_gather(src, xi_all_dev, (size_t)b->n_seq() * 6, 7 /* ncclFloat */, rccl_comm, b->stream());
     if (rc != 0) { set_error("ncclAllGather failed"); return DVO_ERR_HIP; }
     return DVO_OK;
 }
@@ -526,10 +490,9 @@ int dvo_batch_gather_poses_rccl(dvo_batch* b, void* rccl_comm, int world_size, f
 int dvo_batch_profile(dvo_batch* b, dvo_gn_profile* out, int reset)
 {
     if (!b || !out) return DVO_ERR_BAD_ARGUMENT;
-    Tracker& trk = b->mono ? b->mono->trk : b->impl.trk;
-    hipStream_t st = b->mono ? b->mono->stream : b->impl.stream;
-    DVO_TRY(select_device(b->mono ? b->mono->device : b->impl.device));
-    DVO_TRY(trk.collect_profile(st));
+    Tracker& trk = b->trk();
+    DVO_TRY(select_device(b->device()));
+    DVO_TRY(trk.collect_profile(b->stream()));
     unsigned long long c[2] = {0, 0};
     DVO_HIP(hipMemcpy(c, trk.counters.p, sizeof c, hipMemcpyDeviceToHost));
     out->gn_ms = trk.prof_ms;

@@ -1325,24 +1325,11 @@ int VisualOdometry::odometrize_depth_staged(float T_rel[16], const FrameInput* r
 Batch::~Batch()
 {
     if (pstream) { (void)hipStreamSynchronize(pstream); (void)hipStreamDestroy(pstream); }
-    if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
-    for (auto& st : stage) {
-        if (st.copied) (void)hipEventDestroy(st.copied);
-        if (st.consumed) (void)hipEventDestroy(st.consumed);
-    }
+    host.release();
     if (ev_last_track) (void)hipEventDestroy(ev_last_track);
     for (int i = 0; i < 3; i++) if (ev_built[i]) (void)hipEventDestroy(ev_built[i]);
-    if (stream && (h_act[0] || h_ready)) (void)hipStreamSynchronize(stream);
-    for (int i = 0; i < 2; i++) {
-        if (h_act[i]) (void)hipHostFree(h_act[i]);
-        if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
-    }
-    if (h_ready) (void)hipHostFree(h_ready);
-    if (stream && h_cam[0]) (void)hipStreamSynchronize(stream);
-    for (int i = 0; i < 2; i++) {
-        if (h_cam[i]) (void)hipHostFree(h_cam[i]);
-        if (ev_cam[i]) (void)hipEventDestroy(ev_cam[i]);
-    }
+    plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
+    cam_stage.release(stream);
     guess.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
@@ -1380,7 +1367,7 @@ int Batch::init(int n, const float K9[9], int w, int h, int levels, int culls, c
 // whose copy waits until push k (pyramid build + tracking) is done with it.
 int Batch::check_actions_input(const FrameInput& in) const
 {
-    if (act_pending && cur >= 0 && weights_by_validity(fs[cur], in) != fs[cur].sigma_by_validity) {   // (a SKIP copies the weight storage)
+    if (plan.act_pending && cur >= 0 && weights_by_validity(fs[cur], in) != fs[cur].sigma_by_validity) {   // (a SKIP copies the weight storage)
         set_error("dvo_batch_set_actions: a push with actions must keep the weight storage of the references (raw frames vs float maps)");
         return DVO_ERR_BAD_ARGUMENT;
     }
@@ -1391,58 +1378,85 @@ int Batch::check_actions_input(const FrameInput& in) const
     return DVO_OK;
 }
 
-int Batch::push_host_frame(const void* p0, size_t n0, const void* p1, size_t n1, const void* p2, size_t n2, FrameInput in)
+int Batch::push_host_frame(const void* p0, const void* p1, const void* p2, FrameInput in)
 {
     DVO_TRY(check_actions_input(in));   // (before the copies are queued)
     DVO_TRY(select_device(device));
+    // The adaptive schedule keeps the host inside track() until the GPU is nearly done with the frame; a host-fed batch wants the
+    // next frame's transfer queued meanwhile, so it runs the fixed schedule (bit-identical results, tested).
+    trk.adaptive = false;
+    DVO_TRY(host.begin());
+    // Known difference from MonoBatch::odometrize_host, kept: the frame counts as taken before its copies are queued, and the slot is
+    // marked consumed below whatever push() returns (the mono batch stages a refused frame's successor into the same slot).
+    host.advance();
+    in.rows_decimated = host.decimate(g, und);
+    const size_t rb = (size_t)g.src_w * (in.raw() ? (size_t)in.channels : sizeof(float));
+    DVO_TRY(host.upload(0, p0, rb, g, n_seq, in.rows_decimated));
+    if (p1) DVO_TRY(host.upload(1, p1, in.raw() ? (size_t)g.src_w * 2 : rb, g, n_seq, in.rows_decimated));
+    if (p2) DVO_TRY(host.upload(2, p2, rb, g, n_seq, in.rows_decimated));
+    DVO_TRY(host.end_copy(stream, host_buffer_is_pinned(p0) && (!p1 || host_buffer_is_pinned(p1)) && (!p2 || host_buffer_is_pinned(p2))));
+    const HostStage::Slot& st = host.cur();
+    if (in.raw()) { in.rgb = st.buf[0].as<uint8_t>(); in.depth16 = st.buf[1].as<uint16_t>(); }
+    else { in.gray = st.buf[0].as<float>(); in.depth = st.buf[1].as<float>(); in.sigma = st.buf[2].as<float>(); }
+    const int rc = push(in);
+    DVO_TRY(host.consumed(stream));
+    return rc;
+}
+
+// ------------------------------------------------------------------------------------------------ host-frame staging
+int HostStage::begin()
+{
     if (!cstream) {
         DVO_HIP(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
-        for (auto& st : stage) {
+        for (auto& st : slot) {
             DVO_HIP(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
             DVO_HIP(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
         }
     }
-    // The adaptive schedule keeps the host inside track() until the GPU is nearly done with the frame; a host-fed batch wants the
-    // next frame's transfer queued meanwhile, so it runs the fixed schedule (bit-identical results, tested).
-    trk.adaptive = false;
-    Stage& st = stage[n_host_push & 1];
-    n_host_push++;
-    if (st.a.bytes < n0) DVO_TRY(st.a.alloc(n0));
-    if (p1 && st.b.bytes < n1) DVO_TRY(st.b.alloc(n1));
-    if (p2 && st.c.bytes < n2) DVO_TRY(st.c.alloc(n2));
-    if (st.used) DVO_HIP(hipStreamWaitEvent(cstream, st.consumed, 0));
-    // only the rows the pyramid keeps cross PCIe (the staging buffers are sized for whole frames) -- unless the frames are undistorted:
-    // the remap reads any row, so whole frames go up
-    const bool decimate = decimate_host_rows && can_decimate_rows(g) && !und.enabled();
-    if (in.raw()) {
-        in.rows_decimated = decimate;
-        DVO_TRY(upload_rows(st.a.p, p0, (size_t)g.src_w * in.channels, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-        DVO_TRY(upload_rows(st.b.p, p1, (size_t)g.src_w * 2, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-    } else {
-        in.rows_decimated = decimate;
-        const size_t rb = (size_t)g.src_w * sizeof(float);
-        DVO_TRY(upload_rows(st.a.p, p0, rb, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-        if (p1) DVO_TRY(upload_rows(st.b.p, p1, rb, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-        if (p2) DVO_TRY(upload_rows(st.c.p, p2, rb, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-    }
-    DVO_HIP(hipEventRecord(st.copied, cstream));
+    k = n_push & 1;
+    if (cur().used) DVO_HIP(hipStreamWaitEvent(cstream, cur().consumed, 0));
+    return DVO_OK;
+}
+
+int HostStage::upload(int i, const void* src, size_t row_bytes, const Geometry& g, int n_seq, bool decimate)
+{
+    DevBuf& b = cur().buf[i];
+    const size_t whole = row_bytes * (size_t)g.src_h * (size_t)n_seq;
+    if (b.bytes < whole) DVO_TRY(b.alloc(whole));
+    return upload_rows(b.p, src, row_bytes, g.src_h, (size_t)n_seq, g.culls, decimate, cstream, nullptr);
+}
+
+int HostStage::end_copy(hipStream_t tracking, bool all_sources_pinned)
+{
+    DVO_HIP(hipEventRecord(cur().copied, cstream));
     // Pageable memory: the runtime may pin it in place and return while the DMA is still reading it, and the caller is free to
     // release the buffer as soon as this call returns -- so wait for the copy (only the copy: the tracking of the previous frame
-    // keeps running on `stream`).  Pinned buffers stay asynchronous, as the header says.
-    if (!host_buffer_is_pinned(p0) || (p1 && !host_buffer_is_pinned(p1)) || (p2 && !host_buffer_is_pinned(p2))) DVO_HIP(hipStreamSynchronize(cstream));
-    DVO_HIP(hipStreamWaitEvent(stream, st.copied, 0));
-    if (in.raw()) { in.rgb = st.a.as<uint8_t>(); in.depth16 = st.b.as<uint16_t>(); }
-    else { in.gray = st.a.as<float>(); in.depth = st.b.as<float>(); in.sigma = st.c.as<float>(); }
-    const int rc = push(in);
-    DVO_HIP(hipEventRecord(st.consumed, stream));
-    st.used = true;
-    return rc;
+    // keeps running on the tracking stream).  Pinned buffers stay asynchronous, as the header says.
+    if (!all_sources_pinned) DVO_HIP(hipStreamSynchronize(cstream));
+    DVO_HIP(hipStreamWaitEvent(tracking, cur().copied, 0));
+    return DVO_OK;
+}
+
+int HostStage::consumed(hipStream_t tracking)
+{
+    DVO_HIP(hipEventRecord(cur().consumed, tracking));
+    cur().used = true;
+    return DVO_OK;
+}
+
+void HostStage::release()
+{
+    if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); cstream = nullptr; }
+    for (auto& st : slot) {
+        if (st.copied) { (void)hipEventDestroy(st.copied); st.copied = nullptr; }
+        if (st.consumed) { (void)hipEventDestroy(st.consumed); st.consumed = nullptr; }
+    }
 }
 
 int Batch::prefetch(const FrameInput& in)
 {
     if (!in.key0() || !in.has_depth()) { set_error("null device pointer"); return DVO_ERR_BAD_ARGUMENT; }
-    if (act_pending) { set_error("dvo_batch_prefetch: actions are pending for the next push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
+    if (plan.act_pending) { set_error("dvo_batch_prefetch: actions are pending for the next push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
     if (kf_on) { set_error("dvo_batch_prefetch: keyframe tracking is on (prefetch and keyframe tracking do not combine)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
     const int slot = free_slot();
@@ -1465,7 +1479,7 @@ int Batch::push(const FrameInput& in)
     DVO_TRY(select_device(device));
     // per-sequence path: actions pending, or used by an earlier push (then every push is an all-TRACK plan), or per-sequence intrinsics,
     // or keyframe tracking
-    const bool planned = act_pending || act_used || cam_used || kf_on;
+    const bool planned = plan.act_pending || plan.act_used || cam_used || kf_on;
     DVO_TRY(check_actions_input(in));
     if (und.enabled() && in.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
     FrameInput fin = in;
@@ -1500,31 +1514,26 @@ int Batch::push(const FrameInput& in)
     } else {
         // k_plan first (it reads only the actions and has_ref), then the pyramid: SKIP sequences copy their reference forward, so the
         // whole new frame set becomes the reference below (cur = target) and k_track_gn addresses frame sets as it always does
-        const bool skips = act_pending;   // (without pending actions every sequence builds: a prefetched set needs nothing more)
+        const bool skips = plan.act_pending;   // (without pending actions every sequence builds: a prefetched set needs nothing more)
         DVO_TRY(launch_plan(cur >= 0));
-        if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, skips ? eff.as<uint8_t>() : nullptr, cur >= 0 ? &fs[cur] : &fs[target]);
+        if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, skips ? plan.eff.as<uint8_t>() : nullptr, cur >= 0 ? &fs[cur] : &fs[target]);
         if (cur >= 0) {
-            TrackPlan tp;
-            tp.action = eff.as<uint8_t>();
-            tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
-            tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
+            TrackPlan tp = plan.track_plan(trk);
             tp.seq_k = cam_table();
-            if (guess.on()) { sa = guess_args(eff.as<uint8_t>(), 0); trk.seed = &sa; }
+            if (guess.on()) { sa = guess_args(plan.eff.as<uint8_t>(), 0); trk.seed = &sa; }
             const int rc = trk.track(fs[target], fs[cur], stream, &tp);
             trk.seed = nullptr;
             DVO_TRY(rc);
             DVO_HIP(hipEventRecord(ev_last_track, stream));
             tracked_once = true;
         } else {   // no frame set to track against yet: every sequence starts (or stays without a reference); k_plan zeroed the twists
-            seed_untracked(eff.as<uint8_t>(), 0);
+            seed_untracked(plan.eff.as<uint8_t>(), 0);
             launch_export_poses(trk.state.as<SeqState>(), trk.xi_out.as<float>(), trk.T_out.as<float>(), n_seq, stream);
         }
         if (kf_on) DVO_TRY(update_keyframes(target));
         have_poses = true;
-        act_pending = false;
-        act_used = true;
+        plan.consumed();
         if (cam_pending) { cam_K_used = cam_K; cam_pending = false; }   // (k_plan has read this push's camera-changed bytes)
-        plan_parity ^= 1;
     }
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
     guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
@@ -1540,70 +1549,155 @@ int Batch::push(const FrameInput& in)
     return DVO_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ batch: per-sequence actions
-int Batch::alloc_plan()
+// ------------------------------------------------------------------------------------------------ two-slot pinned staging
+int PinnedPair::alloc(size_t bytes)
 {
-    if (has_ref.p) return DVO_OK;
-    DVO_TRY(act_dev.alloc((size_t)n_seq));
-    DVO_TRY(has_ref.alloc((size_t)n_seq));
-    DVO_TRY(eff.alloc((size_t)n_seq));
-    DVO_TRY(status.alloc(sizeof(int) * (size_t)n_seq));
-    DVO_TRY(plan_lists.alloc(2 * sizeof(int) * (size_t)trk.n_sub * (size_t)(n_seq + 4)));
-    DVO_TRY(plan_tally.alloc(2 * sizeof(int)));
     for (int i = 0; i < 2; i++) {
-        DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_act[i]), (size_t)n_seq, hipHostMallocDefault));
-        DVO_HIP(hipEventCreateWithFlags(&ev_act[i], hipEventDisableTiming));
+        if (!h[i]) DVO_HIP(hipHostMalloc(&h[i], bytes, hipHostMallocDefault));
+        if (!ev[i]) DVO_HIP(hipEventCreateWithFlags(&ev[i], hipEventDisableTiming));
     }
-    DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_ready), 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    h_ready[0] = h_ready[1] = 0;
-    DVO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_ready), h_ready, 0));
-    // in stream order: every sequence that a plain push gave a frame has a reference; the list counts start at zero
-    DVO_HIP(hipMemsetAsync(has_ref.p, cur >= 0 ? 1 : 0, has_ref.bytes, stream));
-    DVO_HIP(hipMemsetAsync(plan_lists.p, 0, plan_lists.bytes, stream));
-    DVO_HIP(hipMemsetAsync(plan_tally.p, 0, plan_tally.bytes, stream));
     return DVO_OK;
 }
 
-int Batch::set_actions(const uint8_t* actions, bool on_device)
+int PinnedPair::acquire(void** host)
 {
-    if (npre > 0) { set_error("dvo_batch_set_actions: a prefetched frame is waiting for its push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
+    const int k = slot;
+    slot ^= 1;
+    if (staged[k]) DVO_HIP(hipEventSynchronize(ev[k]));   // (that copy was queued two calls ago)
+    *host = h[k];
+    return DVO_OK;
+}
+
+int PinnedPair::commit(void* dst_dev, size_t bytes, hipStream_t s)
+{
+    const int k = slot ^ 1;   // (the block acquire() handed out last)
+    DVO_HIP(hipMemcpyAsync(dst_dev, h[k], bytes, hipMemcpyHostToDevice, s));
+    DVO_HIP(hipEventRecord(ev[k], s));
+    staged[k] = true;
+    return DVO_OK;
+}
+
+void PinnedPair::release(hipStream_t s)
+{
+    if (h[0] && s) (void)hipStreamSynchronize(s);
+    for (int i = 0; i < 2; i++) {
+        if (h[i]) { (void)hipEventSynchronize(ev[i]); (void)hipHostFree(h[i]); h[i] = nullptr; }
+        if (ev[i]) { (void)hipEventDestroy(ev[i]); ev[i] = nullptr; }
+        staged[i] = false;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------ per-sequence actions (both batch kinds)
+int SeqPlan::alloc(int n_seq, int n_sub, bool has_ref_fill, hipStream_t s)
+{
+    if (has_ref.p) return DVO_OK;
+    const size_t n = (size_t)n_seq;
+    DVO_TRY(act_dev.alloc(n));
+    DVO_TRY(eff.alloc((n + 3) & ~(size_t)3));   // (read as 32-bit words by the mono batch's k_regularize_redecimate_plan)
+    DVO_TRY(status.alloc(sizeof(int) * n));
+    DVO_TRY(lists.alloc(2 * sizeof(int) * (size_t)n_sub * (n + 4)));
+    DVO_TRY(tally.alloc(2 * sizeof(int)));
+    DVO_TRY(act_stage.alloc(n));
+    if (!h_ready) {
+        DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_ready), 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+        h_ready[0] = h_ready[1] = 0;
+        DVO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_ready), h_ready, 0));
+    }
+    DVO_TRY(has_ref.alloc(n));   // (last: alloc runs again until everything before it is there)
+    // in stream order: after plain pushes / calls every sequence has a reference / keyframe; the list counts start at zero
+    DVO_HIP(hipMemsetAsync(has_ref.p, has_ref_fill ? 1 : 0, n, s));
+    DVO_HIP(hipMemsetAsync(lists.p, 0, lists.bytes, s));
+    DVO_HIP(hipMemsetAsync(tally.p, 0, tally.bytes, s));
+    return DVO_OK;
+}
+
+int SeqPlan::set_actions(const uint8_t* actions, bool on_device, int n_seq, hipStream_t s)
+{
     if (!actions) { act_pending = false; act_src = nullptr; return DVO_OK; }
-    DVO_TRY(select_device(device));
-    DVO_TRY(alloc_plan());
     if (on_device) {
         act_src = actions;   // read by k_plan in stream order
     } else {
-        // copied now into pinned staging, then to the device in stream order (after the k_plan of every earlier push)
-        const int k = act_slot;
-        act_slot ^= 1;
-        if (act_staged[k]) DVO_HIP(hipEventSynchronize(ev_act[k]));   // (that copy was queued two calls ago)
-        memcpy(h_act[k], actions, (size_t)n_seq);
-        DVO_HIP(hipMemcpyAsync(act_dev.p, h_act[k], (size_t)n_seq, hipMemcpyHostToDevice, stream));
-        DVO_HIP(hipEventRecord(ev_act[k], stream));
-        act_staged[k] = true;
+        // copied now into pinned staging, then to the device in stream order (after the k_plan of every earlier push / call)
+        void* h = nullptr;
+        DVO_TRY(act_stage.acquire(&h));
+        memcpy(h, actions, (size_t)n_seq);
+        DVO_TRY(act_stage.commit(act_dev.p, (size_t)n_seq, s));
         act_src = act_dev.as<uint8_t>();
     }
     act_pending = true;
     return DVO_OK;
 }
 
-int Batch::launch_plan(bool track_follows)
+PlanArgs SeqPlan::plan_args(const Tracker& trk, bool track_follows)
 {
-    DVO_TRY(alloc_plan());
     PlanArgs a{};
     a.actions = act_pending ? act_src : nullptr;
     a.has_ref = has_ref.as<uint8_t>(); a.eff = eff.as<uint8_t>(); a.status = status.as<int>();
-    a.state = trk.state.as<SeqState>(); a.log = trk.log.as<dvo_track_log>(); a.levels = g.levels;
-    const size_t set = (size_t)trk.n_sub * (size_t)(n_seq + 4);
-    a.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
-    a.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
-    a.list_stride = n_seq + 4; a.n_sub = trk.n_sub; a.n_seq = n_seq;
-    a.cam_changed = cam_pending ? cam_changed() : nullptr;
+    a.state = trk.state.as<SeqState>(); a.log = trk.log.as<dvo_track_log>(); a.levels = trk.g.levels;
+    a.lists = list_set(trk, parity);
+    a.lists_clear = list_set(trk, parity ^ 1);
+    a.list_stride = trk.n_seq + 4; a.n_sub = trk.n_sub; a.n_seq = trk.n_seq;
     if (trk.adaptive && track_follows) {   // Tracker::track waits for this word (the one of this parity was last used two plans ago)
-        h_ready[plan_parity] = 0;
-        a.ready = d_ready + plan_parity;
-        a.tally = plan_tally.as<int>();
+        h_ready[parity] = 0;
+        a.ready = d_ready + parity;
+        a.tally = tally.as<int>();
     }
+    return a;
+}
+
+TrackPlan SeqPlan::track_plan(const Tracker& trk) const
+{
+    TrackPlan tp;
+    tp.action = eff.as<uint8_t>();
+    tp.lists = list_set(trk, parity);
+    tp.ready = trk.adaptive ? h_ready + parity : nullptr;
+    return tp;
+}
+
+// The push / call has queued everything that reads this plan.  act_src is nulled for both kinds: it is read only while act_pending
+// is set, and set_actions always writes it before it sets act_pending.
+void SeqPlan::consumed()
+{
+    act_pending = false; act_src = nullptr; act_used = true;
+    parity ^= 1;
+}
+
+int SeqPlan::status_of_last(int* out, bool out_on_device, int n_seq, bool first_push, hipStream_t s) const
+{
+    if (!act_used) {   // plain pushes / calls: the first one starts every sequence, every later one tracks every sequence
+        const int v = first_push ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
+        if (out_on_device) { DVO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), v, (size_t)n_seq, s)); return DVO_OK; }
+        DVO_HIP(hipStreamSynchronize(s));   // (as a read-back of the device buffer would)
+        for (int q = 0; q < n_seq; q++) out[q] = v;
+        return DVO_OK;
+    }
+    DVO_HIP(hipMemcpyAsync(out, status.p, sizeof(int) * (size_t)n_seq, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s));
+    if (!out_on_device) DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+void SeqPlan::release(hipStream_t s)
+{
+    act_stage.release(s);   // (drains s: the ready words, allocated only after the staging, are no longer written either)
+    if (h_ready) { (void)hipHostFree(h_ready); h_ready = d_ready = nullptr; }
+}
+
+// ------------------------------------------------------------------------------------------------ batch: per-sequence actions
+int Batch::set_actions(const uint8_t* actions, bool on_device)
+{
+    if (npre > 0) { set_error("dvo_batch_set_actions: a prefetched frame is waiting for its push (prefetch and actions do not combine)"); return DVO_ERR_NOT_READY; }
+    if (actions) {
+        DVO_TRY(select_device(device));
+        DVO_TRY(alloc_plan());
+    }
+    return plan.set_actions(actions, on_device, n_seq, stream);
+}
+
+int Batch::launch_plan(bool track_follows)
+{
+    DVO_TRY(alloc_plan());
+    PlanArgs a = plan.plan_args(trk, track_follows);
+    a.cam_changed = cam_pending ? cam_changed() : nullptr;
     dvo::launch_plan(a, stream);
     DVO_HIP(hipGetLastError());
     return DVO_OK;
@@ -1613,17 +1707,7 @@ int Batch::status_of_last(int* out, bool out_on_device)
 {
     if (n_push == 0) { set_error("dvo_batch_last_status: nothing has been pushed yet"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
-    const size_t bytes = sizeof(int) * (size_t)n_seq;
-    if (!act_used) {   // plain pushes: the first one starts every sequence, every later one tracks every sequence
-        const int v = n_push == 1 ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
-        if (out_on_device) { DVO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), v, (size_t)n_seq, stream)); return DVO_OK; }
-        DVO_HIP(hipStreamSynchronize(stream));   // (as a read-back of the device buffer would)
-        for (int q = 0; q < n_seq; q++) out[q] = v;
-        return DVO_OK;
-    }
-    DVO_HIP(hipMemcpyAsync(out, status.p, bytes, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-    if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
-    return DVO_OK;
+    return plan.status_of_last(out, out_on_device, n_seq, n_push == 1, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ batch: per-sequence intrinsics
@@ -1655,20 +1739,14 @@ int Batch::stage_cameras(const float* K)
 {
     const size_t n = (size_t)n_seq;
     const size_t table = sizeof(Intr) * (size_t)g.levels * n, bytes = table + n;
-    if (!cam_dev.p) {
-        DVO_TRY(cam_dev.alloc(bytes));
-        for (int i = 0; i < 2; i++) {
-            DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_cam[i]), bytes, hipHostMallocDefault));
-            DVO_HIP(hipEventCreateWithFlags(&ev_cam[i], hipEventDisableTiming));
-        }
-    }
-    // pinned staging (the copy of two calls ago has been read by then), then one copy in stream order: every push queued before
-    // this call has finished reading the device table when it is overwritten, and the next push reads the new one
-    const int k = cam_slot;
-    cam_slot ^= 1;
-    if (cam_staged[k]) DVO_HIP(hipEventSynchronize(ev_cam[k]));
-    Intr* tab = reinterpret_cast<Intr*>(h_cam[k]);
-    uint8_t* changed = h_cam[k] + table;
+    if (!cam_dev.p) DVO_TRY(cam_dev.alloc(bytes));
+    DVO_TRY(cam_stage.alloc(bytes));
+    // pinned staging (the copy of two calls ago has been read by then), filled in place, then one copy in stream order: every push
+    // queued before this call has finished reading the device table when it is overwritten, and the next push reads the new one
+    void* h = nullptr;
+    DVO_TRY(cam_stage.acquire(&h));
+    Intr* tab = static_cast<Intr*>(h);
+    uint8_t* changed = static_cast<uint8_t*>(h) + table;
     for (size_t q = 0; q < n; q++) {
         const float* kq = K ? K + q * 9 : K_create;
         Intr lv[DVO_MAX_LEVELS];
@@ -1680,9 +1758,7 @@ int Batch::stage_cameras(const float* K)
                      distortion_changed(q);
         if (kq != &cam_K[q * 9]) memcpy(&cam_K[q * 9], kq, 9 * sizeof(float));
     }
-    DVO_HIP(hipMemcpyAsync(cam_dev.p, h_cam[k], bytes, hipMemcpyHostToDevice, stream));
-    DVO_HIP(hipEventRecord(ev_cam[k], stream));
-    cam_staged[k] = true;
+    DVO_TRY(cam_stage.commit(cam_dev.p, bytes, stream));
     cam_pending = true;
     cam_used = true;
     return DVO_OK;
@@ -1712,10 +1788,7 @@ int PoseGuess::set_mode(int m, int n, hipStream_t s, const uint8_t* prev_eff_dev
         DVO_HIP(hipMemsetAsync(dev.p, 0, dev.bytes, s));
         if (prev_eff_dev) DVO_HIP(hipMemcpyAsync(prev_eff(), prev_eff_dev, (size_t)n, hipMemcpyDeviceToDevice, s));
         else DVO_HIP(hipMemsetAsync(prev_eff(), prev_all, (size_t)n, s));
-        for (int i = 0; i < 2; i++) {
-            DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_rows[i]), sizeof(float) * 6 * (size_t)n, hipHostMallocDefault));
-            DVO_HIP(hipEventCreateWithFlags(&ev_rows[i], hipEventDisableTiming));
-        }
+        DVO_TRY(rows_stage.alloc(sizeof(float) * 6 * (size_t)n));
     }
     mode = m;
     if (m != DVO_GUESS_GIVEN) rows_src = nullptr;
@@ -1727,15 +1800,12 @@ int PoseGuess::set_rows(const float* xi, bool on_device, hipStream_t s)
     if (!xi) { rows_src = nullptr; return DVO_OK; }
     if (mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
     if (on_device) { rows_src = xi; return DVO_OK; }   // read by the seed kernel in stream order
-    // copied now into pinned staging, then to the device in stream order (after the seed of every earlier push), as Batch::set_actions
+    // copied now into pinned staging, then to the device in stream order (after the seed of every earlier push), as SeqPlan::set_actions
     const size_t bytes = sizeof(float) * 6 * (size_t)n_seq;
-    const int k = rows_slot;
-    rows_slot ^= 1;
-    if (rows_staged[k]) DVO_HIP(hipEventSynchronize(ev_rows[k]));
-    memcpy(h_rows[k], xi, bytes);
-    DVO_HIP(hipMemcpyAsync(rows(), h_rows[k], bytes, hipMemcpyHostToDevice, s));
-    DVO_HIP(hipEventRecord(ev_rows[k], s));
-    rows_staged[k] = true;
+    void* h = nullptr;
+    DVO_TRY(rows_stage.acquire(&h));
+    memcpy(h, xi, bytes);
+    DVO_TRY(rows_stage.commit(rows(), bytes, s));
     rows_src = rows();
     return DVO_OK;
 }
@@ -1757,20 +1827,11 @@ int PoseGuess::last_start(float* out, hipStream_t s) const
     return DVO_OK;
 }
 
-void PoseGuess::release(hipStream_t s)
-{
-    if (h_rows[0] && s) (void)hipStreamSynchronize(s);
-    for (int i = 0; i < 2; i++) {
-        if (h_rows[i]) { (void)hipEventSynchronize(ev_rows[i]); (void)hipHostFree(h_rows[i]); h_rows[i] = nullptr; }
-        if (ev_rows[i]) { (void)hipEventDestroy(ev_rows[i]); ev_rows[i] = nullptr; }
-    }
-}
-
 int Batch::set_guess_mode(int m)
 {
     DVO_TRY(select_device(device));
     // the push before: its effective actions (per-sequence path), else all STARTED (first push) or all TRACKED (later ones)
-    const uint8_t* pe = act_used ? eff.as<uint8_t>() : nullptr;
+    const uint8_t* pe = plan.act_used ? plan.eff.as<uint8_t>() : nullptr;
     const int all = n_push == 0 ? 0xff : (n_push == 1 ? DVO_SEQ_RESTART : DVO_SEQ_TRACK);
     return guess.set_mode(m, n_seq, stream, pe, all);
 }
@@ -1820,7 +1881,7 @@ int Batch::update_keyframes(int frame_set)
     const int kf = cur >= 0 ? cur : frame_set;   // (the first push: its set becomes the keyframe set, nothing to copy)
     DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
     MonoPlanArgs ma{};
-    ma.meta = kf_meta.as<MonoSeq>(); ma.state = trk.state.as<SeqState>(); ma.eff = eff.as<uint8_t>();
+    ma.meta = kf_meta.as<MonoSeq>(); ma.state = trk.state.as<SeqState>(); ma.eff = plan.eff.as<uint8_t>();
     ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
     ma.n_seq = n_seq; ma.R = 1; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
     launch_kf_decide(ma, stream);

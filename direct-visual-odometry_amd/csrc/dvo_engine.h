@@ -47,6 +47,28 @@ struct DevBuf {  // RAII hipMalloc (or a view of memory somebody else owns: adop
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// Two pinned host blocks used alternately to stage small host tables (actions, intrinsics, start-pose rows) for a copy in stream
+// order: the caller fills the block acquire() hands out and commit() queues its copy, so the call returns while the copy is pending
+// and the block is reused two calls later, once its event says the copy has read it.
+// Release order, for this and every helper that owns host staging (SeqPlan, HostStage): the owner's destructor calls release(stream)
+// BEFORE it destroys the stream, which drains the stream, waits for the staged copies and then frees.  The member destructor runs
+// after the owner's body, when the stream may be gone: it calls release(nullptr), which touches no stream, waits on the helper's own
+// events only and does nothing after an explicit release.
+struct PinnedPair {
+    void* h[2] = {nullptr, nullptr};
+    hipEvent_t ev[2] = {nullptr, nullptr};   // the copy out of h[i] has been read
+    bool staged[2] = {false, false};
+    int slot = 0;                            // the block the next acquire() hands out
+    PinnedPair() = default;
+    PinnedPair(const PinnedPair&) = delete;
+    PinnedPair& operator=(const PinnedPair&) = delete;
+    ~PinnedPair() { release(nullptr); }
+    int alloc(size_t bytes);                                   // on first use; later calls do nothing
+    int acquire(void** host);                                  // the next block, once the copy of two calls ago has read it
+    int commit(void* dst_dev, size_t bytes, hipStream_t s);    // the block acquired last -> dst_dev, in stream order
+    void release(hipStream_t s);
+};
+
 // Device memory for the keyframes of one dvo_vo handle: FrameHistory grows by one Frame per keyframe (frame.hpp:151-157), and a hipMalloc
 // per map of every new keyframe costs more than tracking a frame.  Blocks of one keyframe's size are cut from slabs of 16 and recycled
 // when a keyframe is dropped (dvo_vo_set_history_limit).
@@ -164,10 +186,7 @@ struct PoseGuess {
     int mode = DVO_GUESS_NONE;
     int n_seq = 0;
     DevBuf dev;                                // rows [n][6], start [n][6], hist [n][12] (float), then prev_eff [n], hist_n [n] (u8)
-    float* h_rows[2] = {nullptr, nullptr};     // pinned staging of host rows, alternately (ev_rows: their copy has been read)
-    hipEvent_t ev_rows[2] = {nullptr, nullptr};
-    bool rows_staged[2] = {false, false};
-    int rows_slot = 0;
+    PinnedPair rows_stage;                     // pinned staging of host rows
     const float* rows_src = nullptr;           // rows of the next push (device memory); nullptr: none
     bool on() const { return dev.p != nullptr; }
     float* rows() const { return dev.as<float>(); }
@@ -180,8 +199,7 @@ struct PoseGuess {
     int set_rows(const float* xi, bool on_device, hipStream_t s);
     PoseSeedArgs args(SeqState* state, const uint8_t* eff, int all_eff, const float* last_xi, const MonoSeq* meta) const;
     int last_start(float* out, hipStream_t s) const;
-    void release(hipStream_t s);
-    ~PoseGuess() { release(nullptr); }
+    void release(hipStream_t s) { rows_stage.release(s); }   // (PinnedPair's release order)
 };
 
 // Per-sequence tracking quality of a batch (dvo_batch_set_track_quality).  Allocated by the first enable; while on,
@@ -342,7 +360,7 @@ struct VisualOdometry {  // System::VisualOdometry, system.hpp:12-104
     hipEvent_t uevent[3] = {nullptr, nullptr};
     int upload_streams();
     bool side_built = false;   // uevent[1] marks a depth / sigma pyramid built on the side stream (odometrize_depth)
-    bool decimate_host_rows = getenv("DVO_UPLOAD_FULL_FRAMES") == nullptr;  // as Batch::decimate_host_rows
+    bool decimate_host_rows = getenv("DVO_UPLOAD_FULL_FRAMES") == nullptr;  // as HostStage::decimate_host_rows
     int init_keyframe(const float* gray, const float* depth, const float* sigma);
     int map_propagate(Keyframe& frame, const Keyframe& ref);
     int map_update(Keyframe& obj);
@@ -355,6 +373,55 @@ struct VisualOdometry {  // System::VisualOdometry, system.hpp:12-104
     size_t h_tables_bytes = 0;
     bool age_table_done = false;   // this frame's age table came out of k_track_persist's tail
     int map_regularize(Keyframe& kf);
+};
+
+// The per-sequence action plan of a batch of either kind (dvo_batch_set_actions / dvo_batch_set_mono_actions): what
+// k_plan reads and writes, the staging of host actions and the ready words of the adaptive schedule.  Allocated on first use; a batch
+// that never sets actions runs the plain path.
+struct SeqPlan {
+    // has_ref: the sequence has something to track against (sensor depth: a reference frame; mono: a keyframe)
+    DevBuf act_dev, has_ref, eff, status, lists, tally;
+    PinnedPair act_stage;                       // pinned staging of host actions
+    int* h_ready = nullptr;                     // mapped host words of TrackPlan::ready, one per parity
+    int* d_ready = nullptr;
+    const uint8_t* act_src = nullptr;           // actions of the next push / call (device memory)
+    bool act_pending = false, act_used = false;
+    int parity = 0;                             // which of the two list sets (and ready words) the next plan writes
+    int alloc(int n_seq, int n_sub, bool has_ref_fill, hipStream_t s);   // on first use; later calls do nothing
+    int set_actions(const uint8_t* actions, bool on_device, int n_seq, hipStream_t s);   // (after alloc, unless actions is null)
+    // k_plan's arguments for this push / call, all but cam_changed; with track_follows under the adaptive schedule the ready word
+    // of this parity is reset and handed to the kernel
+    PlanArgs plan_args(const Tracker& trk, bool track_follows);
+    TrackPlan track_plan(const Tracker& trk) const;   // (all but seq_k)
+    void consumed();
+    // the status of the last push / call; before any actions were used: every sequence STARTED (first_push) or TRACKED
+    int status_of_last(int* out, bool out_on_device, int n_seq, bool first_push, hipStream_t s) const;
+    void release(hipStream_t s);                // (PinnedPair's release order)
+    ~SeqPlan() { release(nullptr); }
+
+private:
+    int* list_set(const Tracker& trk, int which) const { return lists.as<int>() + (size_t)which * trk.n_sub * (size_t)(trk.n_seq + 4); }
+};
+
+// Host input of a batch of either kind: two staging slots filled on a copy stream, so the H2D transfer of frame k+1 runs beside the
+// tracking of frame k (PCIe is the bound of a host-fed batch: 0.92 MB per raw 640x480 frame).  Slot k & 1 is reused by push k + 2,
+// whose copy waits until push k (pyramid build + tracking) is done with it.
+struct HostStage {
+    struct Slot { DevBuf buf[3]; hipEvent_t copied = nullptr, consumed = nullptr; bool used = false; } slot[2];
+    hipStream_t cstream = nullptr;
+    int n_push = 0, k = 0;   // frames taken; the slot of the frame being staged (begin)
+    bool decimate_host_rows = getenv("DVO_UPLOAD_FULL_FRAMES") == nullptr;  // transfer only the rows the pyramid keeps
+    // only the rows the pyramid keeps cross PCIe (the staging buffers are sized for whole frames) -- unless the frames are undistorted:
+    // the remap reads any row, so whole frames go up (4x the bytes at cull 2)
+    bool decimate(const Geometry& g, const Undistortion& und) const { return decimate_host_rows && can_decimate_rows(g) && !und.enabled(); }
+    Slot& cur() { return slot[k]; }
+    int begin();                              // the copy stream and events on first use; this frame's slot, once its last user is done
+    int upload(int i, const void* src, size_t row_bytes, const Geometry& g, int n_seq, bool decimate);   // one map of every sequence -> buf[i]
+    int end_copy(hipStream_t tracking, bool all_sources_pinned);   // the tracking stream waits for this frame's copies
+    int consumed(hipStream_t tracking);       // everything queued on the tracking stream so far is this slot's last user
+    void advance() { n_push++; }              // (its own call: the two batch kinds differ in when a refused frame counts)
+    void release();                           // (PinnedPair's release order; the copy stream is its own)
+    ~HostStage() { release(); }
 };
 
 struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tracking with sensor depth
@@ -379,13 +446,8 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     hipEvent_t ev_last_track = nullptr, ev_built[3] = {nullptr, nullptr, nullptr};
     bool tracked_once = false;
     bool have_poses = false;
-    // Host input (push_host / push_raw_host): two staging slots filled on a copy stream, so the H2D transfer of frame k+1 runs
-    // beside the tracking of frame k (PCIe is the bound of a host-fed batch: 0.92 MB per raw 640x480 frame).
-    struct Stage { DevBuf a, b, c; hipEvent_t copied = nullptr, consumed = nullptr; bool used = false; } stage[2];
-    hipStream_t cstream = nullptr;
-    int n_host_push = 0;
-    bool decimate_host_rows = getenv("DVO_UPLOAD_FULL_FRAMES") == nullptr;  // raw host frames: transfer only the rows the pyramid keeps
-    int push_host_frame(const void* p0, size_t n0, const void* p1, size_t n1, const void* p2, size_t n2, FrameInput in);
+    HostStage host;         // host input (push_host / push_raw_host): up to three maps per frame
+    int push_host_frame(const void* p0, const void* p1, const void* p2, FrameInput in);
     ~Batch();
     int init(int n, const float K9[9], int w, int h, int levels, int culls, const dvo_config* c);
     int free_slot() const  // a frame set that is neither the reference nor waiting prefetched (-1: none)
@@ -397,17 +459,9 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     int prefetch(const FrameInput& in);
     int push(const FrameInput& in);
     // Per-sequence skip / restart (dvo_batch_set_actions).  Allocated on first use; a batch that never sets actions runs the plain path.
-    DevBuf act_dev, has_ref, eff, status, plan_lists, plan_tally;
-    uint8_t* h_act[2] = {nullptr, nullptr};     // pinned staging of host actions, alternately (ev_act: their copy has been read)
-    hipEvent_t ev_act[2] = {nullptr, nullptr};
-    bool act_staged[2] = {false, false};
-    int act_slot = 0;
-    int* h_ready = nullptr;                     // mapped host words of TrackPlan::ready, one per plan parity
-    int* d_ready = nullptr;
-    const uint8_t* act_src = nullptr;           // actions of the next push (device memory)
-    bool act_pending = false, act_used = false;
-    int plan_parity = 0, n_push = 0;
-    int alloc_plan();
+    SeqPlan plan;
+    int n_push = 0;
+    int alloc_plan() { return plan.alloc(n_seq, trk.n_sub, cur >= 0, stream); }   // (every sequence that a plain push gave a frame has a reference)
     int set_actions(const uint8_t* actions, bool on_device);
     int launch_plan(bool track_follows);
     int status_of_last(int* out, bool out_on_device);
@@ -417,10 +471,7 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     std::vector<float> cam_K;                   // [n_seq][9] the table of the next push (creation K until set)
     std::vector<float> cam_K_used;              // [n_seq][9] the table of the last push (the camera-change rule compares the two)
     DevBuf cam_dev;                             // [level][n_seq] Intr, then [n_seq] camera-changed bytes of the next push
-    uint8_t* h_cam[2] = {nullptr, nullptr};     // pinned staging of cam_dev, alternately (ev_cam: their copy has been read)
-    hipEvent_t ev_cam[2] = {nullptr, nullptr};
-    bool cam_staged[2] = {false, false};
-    int cam_slot = 0;
+    PinnedPair cam_stage;                       // pinned staging of cam_dev
     bool cam_pending = false, cam_used = false;
     int set_intrinsics(const float* K);
     int stage_cameras(const float* K);          // the table of the next push + its camera-changed bytes (K: [n_seq][9], nullptr: creation K)
@@ -501,11 +552,8 @@ struct MonoBatch {
     int set_initial_depth(const float* depth_host, const float* sigma_host);              // one map, broadcast to every sequence
     int set_initial_depth_device(const float* depth_dev, const float* sigma_dev);         // [n_seq][th][tw]
     int odometrize(const FrameInput& in);                                                  // gray [n_seq][h][w] float, or raw u8
-    int odometrize_host(const void* frames, size_t bytes, FrameInput in);                  // the same from host memory (copy stream, 2 slots)
-    struct Stage { DevBuf buf; hipEvent_t copied = nullptr, consumed = nullptr; bool used = false; } stage[2];
-    hipStream_t cstream = nullptr;
-    int n_host = 0;
-    bool decimate_host_rows = getenv("DVO_UPLOAD_FULL_FRAMES") == nullptr;  // as Batch::decimate_host_rows
+    int odometrize_host(const void* frames, FrameInput in);                                // the same from host memory (copy stream, 2 slots)
+    HostStage host;          // (one map per frame)
     int top_pixels() const { return g.w[g.top()] * g.h[g.top()]; }
     // profiling of the mapping stages (cfg.profile): hipEvent pairs on `stream` around k_depth_update (+ k_age_table),
     // k_regularize_redecimate and the three k_propagate_* passes of every frame
@@ -516,18 +564,10 @@ struct MonoBatch {
     uint64_t prof_frames = 0;
     int collect_map_profile();
     // Per-sequence skip / restart (dvo_batch_set_mono_actions).  Allocated on first use; a batch that never sets
-    // actions runs the plain path.  k_plan resolves the actions with has_kf = "has a keyframe"; started = has started before (the
+    // actions runs the plain path.  k_plan resolves the actions with plan.has_ref = "has a keyframe"; started = has started before (the
     // first start keeps the slot's own initial maps); need_save parks MonoSeq::need of the sequences that do not track.
-    DevBuf act_dev, has_kf, eff, status, plan_lists, plan_tally, started, need_save;
-    uint8_t* h_act[2] = {nullptr, nullptr};     // pinned staging of host actions, alternately (ev_act: their copy has been read)
-    hipEvent_t ev_act[2] = {nullptr, nullptr};
-    bool act_staged[2] = {false, false};
-    int act_slot = 0;
-    int* h_ready = nullptr;                     // mapped host words of TrackPlan::ready, one per plan parity
-    int* d_ready = nullptr;
-    const uint8_t* act_src = nullptr;           // actions of the next call (device memory)
-    bool act_pending = false, act_used = false;
-    int plan_parity = 0;
+    SeqPlan plan;
+    DevBuf started, need_save;
     const float* start_depth = nullptr;         // start maps of the next call (dvo_batch_set_mono_start_depth_device)
     const float* start_sigma = nullptr;
     bool host_init = false;                     // init_depth holds the host map of set_initial_depth (else, once planned, the default)
@@ -550,4 +590,13 @@ void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vec
 struct dvo_batch {
     dvo::Batch impl;
     std::unique_ptr<dvo::MonoBatch> mono;
+    // what both kinds have, of whichever is live
+    int device() const { return mono ? mono->device : impl.device; }
+    hipStream_t stream() const { return mono ? mono->stream : impl.stream; }
+    int n_seq() const { return mono ? mono->n_seq : impl.n_seq; }
+    dvo::Tracker& trk() { return mono ? mono->trk : impl.trk; }
+    dvo::PoseGuess& guess() { return mono ? mono->guess : impl.guess; }
+    dvo::TrackQuality& quality() { return mono ? mono->quality : impl.quality; }
+    dvo::SeqPlan& plan() { return mono ? mono->plan : impl.plan; }
+    int pushes() const { return mono ? mono->latest_id + 1 : impl.n_push; }   // pushes / calls that consumed a frame
 };

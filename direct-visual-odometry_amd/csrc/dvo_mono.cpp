@@ -19,19 +19,10 @@ namespace dvo {
 
 MonoBatch::~MonoBatch()
 {
-    if (cstream) { (void)hipStreamSynchronize(cstream); (void)hipStreamDestroy(cstream); }
-    for (auto& st : stage) {
-        if (st.copied) (void)hipEventDestroy(st.copied);
-        if (st.consumed) (void)hipEventDestroy(st.consumed);
-    }
+    host.release();
     for (auto& m : map_ev)
         for (hipEvent_t e : m.e) (void)hipEventDestroy(e);
-    if (stream && (h_act[0] || h_ready)) (void)hipStreamSynchronize(stream);
-    for (int i = 0; i < 2; i++) {
-        if (h_act[i]) (void)hipHostFree(h_act[i]);
-        if (ev_act[i]) (void)hipEventDestroy(ev_act[i]);
-    }
-    if (h_ready) (void)hipHostFree(h_ready);
+    plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
     guess.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
@@ -179,43 +170,26 @@ int MonoBatch::set_initial_depth_device(const float* depth_dev, const float* sig
     return DVO_OK;
 }
 
-int MonoBatch::odometrize_host(const void* frames, size_t bytes, FrameInput in)
-{  // frames of every sequence from host memory: H2D on a copy stream into one of two staging slots (as Batch::push_host_frame)
+int MonoBatch::odometrize_host(const void* frames, FrameInput in)
+{  // frames of every sequence from host memory: H2D on a copy stream into one of two staging slots (HostStage)
     if (!frames) { set_error("null host pointer"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(device));
-    if (!cstream) {
-        DVO_HIP(hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking));
-        for (auto& st : stage) {
-            DVO_HIP(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
-            DVO_HIP(hipEventCreateWithFlags(&st.consumed, hipEventDisableTiming));
-        }
-    }
     trk.adaptive = false;   // (the host must not be held inside track(): the next frame's transfer is queued meanwhile)
-    Stage& st = stage[n_host & 1];
-    if (st.buf.bytes < bytes) DVO_TRY(st.buf.alloc(bytes));
-    if (st.used) DVO_HIP(hipStreamWaitEvent(cstream, st.consumed, 0));
-    // only the rows the pyramid keeps cross PCIe (Batch::push_host_frame) -- unless the frames are undistorted: the remap reads any
-    // row, so whole frames go up (4x the bytes at cull 2)
-    const bool decimate = decimate_host_rows && can_decimate_rows(g) && !und.enabled();
-    if (in.raw()) {
-        in.rows_decimated = decimate;
-        DVO_TRY(upload_rows(st.buf.p, frames, (size_t)g.src_w * in.channels, g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-    } else {
-        in.rows_decimated = decimate;
-        DVO_TRY(upload_rows(st.buf.p, frames, (size_t)g.src_w * sizeof(float), g.src_h, (size_t)n_seq, g.culls, in.rows_decimated, cstream, nullptr));
-    }
-    DVO_HIP(hipEventRecord(st.copied, cstream));
-    if (!host_buffer_is_pinned(frames)) DVO_HIP(hipStreamSynchronize(cstream));   // pageable source: see Batch::push_host_frame
-    DVO_HIP(hipStreamWaitEvent(stream, st.copied, 0));
-    if (in.raw()) in.rgb = st.buf.as<uint8_t>(); else in.gray = st.buf.as<float>();
+    DVO_TRY(host.begin());
+    in.rows_decimated = host.decimate(g, und);
+    DVO_TRY(host.upload(0, frames, (size_t)g.src_w * (in.raw() ? (size_t)in.channels : sizeof(float)), g, n_seq, in.rows_decimated));
+    DVO_TRY(host.end_copy(stream, host_buffer_is_pinned(frames)));
+    const DevBuf& buf = host.cur().buf[0];
+    if (in.raw()) in.rgb = buf.as<uint8_t>(); else in.gray = buf.as<float>();
     const int rc = odometrize(in);
-    if (rc != DVO_OK) {   // the frame was not consumed: same staging slot next time, once whatever was queued has drained
+    // Known difference from Batch::push_host_frame, kept: a refused frame was not consumed, so it is neither counted nor recorded as
+    // this slot's last user -- the same staging slot next time, once whatever was queued has drained.
+    if (rc != DVO_OK) {
         (void)hipStreamSynchronize(stream);
         return rc;
     }
-    DVO_HIP(hipEventRecord(st.consumed, stream));
-    st.used = true;
-    n_host++;
+    DVO_TRY(host.consumed(stream));
+    host.advance();
     return DVO_OK;
 }
 
@@ -234,7 +208,7 @@ int MonoBatch::odometrize(const FrameInput& in)
     MonoSeq* m = meta.as<MonoSeq>();
     // per-sequence path: actions or start maps pending, or actions used by an earlier call (then every call is an
     // all-TRACK plan).  frame_id is then the number of the call; each sequence counts its own frames in MonoSeq::frame_id.
-    const bool planned = act_pending || act_used || start_depth != nullptr;
+    const bool planned = plan.act_pending || plan.act_used || start_depth != nullptr;
     if (planned) {
         if (frame_id == 0 && !have_init) {   // the slots' maps of a first start, as the plain first frame sets them
             std::vector<float> d, s;
@@ -242,22 +216,9 @@ int MonoBatch::odometrize(const FrameInput& in)
             DVO_TRY(set_initial_depth(d.data(), s.data()));
         }
         DVO_TRY(alloc_plan());
-        PlanArgs pa{};
-        pa.actions = act_pending ? act_src : nullptr;
-        pa.has_ref = has_kf.as<uint8_t>(); pa.eff = eff.as<uint8_t>(); pa.status = status.as<int>();
-        pa.state = trk.state.as<SeqState>(); pa.log = trk.log.as<dvo_track_log>(); pa.levels = g.levels;
-        const size_t set = (size_t)trk.n_sub * (size_t)(n_seq + 4);
-        pa.lists = plan_lists.as<int>() + (size_t)plan_parity * set;
-        pa.lists_clear = plan_lists.as<int>() + (size_t)(plan_parity ^ 1) * set;
-        pa.list_stride = n_seq + 4; pa.n_sub = trk.n_sub; pa.n_seq = n_seq;   // (no cam_changed: K and D are fixed for the life of the handle)
-        if (trk.adaptive && frame_id > 0) {      // Tracker::track waits for this word (the one of this parity was last used two plans ago)
-            h_ready[plan_parity] = 0;
-            pa.ready = d_ready + plan_parity;
-            pa.tally = plan_tally.as<int>();
-        }
-        launch_plan(pa, stream);
+        launch_plan(plan.plan_args(trk, frame_id > 0), stream);   // (no cam_changed: K and D are fixed for the life of the handle)
         if (frame_id == 0 && guess.on()) {   // nothing tracks: the seed only folds the previous call into the history
-            const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), eff.as<uint8_t>(), 0, xi_world.as<float>(), m);
+            const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), plan.eff.as<uint8_t>(), 0, xi_world.as<float>(), m);
             launch_mono_seed(sa, stream);
         }
     }
@@ -297,23 +258,20 @@ int MonoBatch::odometrize(const FrameInput& in)
     {   // Frame(gray, K, 3, 2); a plan: the SKIP sequences read no input (k_pyramid<true> / k_pyramid_raw4<, true> copy their keyframe's
         // gray forward, k_pyramid_remap_plan writes nothing)
         TraceRange tr("mono pyramid");
-        if (planned) build_pyramid(frm, gin, stream, true, eff.as<uint8_t>(), &ref);
+        if (planned) build_pyramid(frm, gin, stream, true, plan.eff.as<uint8_t>(), &ref);
         else build_pyramid(frm, gin, stream);
     }
     {   // system.hpp:57 (a plan: the TRACK sequences only; before the first call no sequence has a keyframe to track against)
         TraceRange tr("mono track");
         PoseSeedArgs sa{};   // the start pose (dvo_batch_set_pose_guess_mode): k_mono_seed inside track()
-        if (guess.on()) sa = guess.args(trk.state.as<SeqState>(), planned ? eff.as<uint8_t>() : nullptr, DVO_SEQ_TRACK, xi_world.as<float>(), m);
+        if (guess.on()) sa = guess.args(trk.state.as<SeqState>(), planned ? plan.eff.as<uint8_t>() : nullptr, DVO_SEQ_TRACK, xi_world.as<float>(), m);
         int rc = DVO_OK;
         trk.seed = guess.on() ? &sa : nullptr;
         trk.seed_mono = true;
         if (!planned) {
             rc = trk.track(frm, ref, stream);
         } else if (frame_id > 0) {
-            TrackPlan tp;
-            tp.action = eff.as<uint8_t>();
-            tp.lists = plan_lists.as<int>() + (size_t)plan_parity * trk.n_sub * (size_t)(n_seq + 4);
-            tp.ready = trk.adaptive ? h_ready + plan_parity : nullptr;
+            TrackPlan tp = plan.track_plan(trk);
             tp.seq_k = trk.cam_k;
             rc = trk.track(frm, ref, stream, &tp);
         }
@@ -325,7 +283,7 @@ int MonoBatch::odometrize(const FrameInput& in)
     DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
     MonoPlanArgs ma{};
     if (planned) {
-        ma.meta = m; ma.state = trk.state.as<SeqState>(); ma.eff = eff.as<uint8_t>(); ma.started = started.as<uint8_t>();
+        ma.meta = m; ma.state = trk.state.as<SeqState>(); ma.eff = plan.eff.as<uint8_t>(); ma.started = started.as<uint8_t>();
         ma.need_save = need_save.as<int>(); ma.hist_xi = hist_xi.as<float>();
         ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
         ma.n_seq = n_seq; ma.R = R; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
@@ -396,7 +354,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         if (pe) DVO_HIP(hipEventRecord(pe->e[4], stream));
         if (planned) {   // the TRACK sequences as above; SKIP copies its top-level depth forward; RESTART starts (k_regularize_redecimate_plan)
             MonoStartArgs sa{};
-            sa.eff = eff.as<uint8_t>(); sa.started = started.as<uint8_t>();
+            sa.eff = plan.eff.as<uint8_t>(); sa.started = started.as<uint8_t>();
             sa.start_depth = start_depth; sa.start_sigma = start_sigma;
             sa.init_depth = init_depth.as<float>(); sa.init_sigma = init_sigma.as<float>();
             sa.sigma_top = ref.sigma[T]; sa.age = ref_age.as<float>();
@@ -411,9 +369,8 @@ int MonoBatch::odometrize(const FrameInput& in)
     }
     if (planned) {   // FrameHistory::push of the TRACK keyframes, frame 0 of the RESTART sequences, the SKIP need flags back
         launch_mono_commit_plan(ma, stream);
-        act_pending = false; act_src = nullptr; act_used = true;
+        plan.consumed();
         start_depth = start_sigma = nullptr;
-        plan_parity ^= 1;
     }
     DVO_HIP(hipGetLastError());
     quality.ready = quality.on;
@@ -424,28 +381,12 @@ int MonoBatch::odometrize(const FrameInput& in)
 // ------------------------------------------------------------------------------------------------ mono: per-sequence actions
 int MonoBatch::alloc_plan()
 {
-    if (has_kf.p) return DVO_OK;
+    if (need_save.p) return DVO_OK;
     const size_t n = (size_t)n_seq;
-    DVO_TRY(act_dev.alloc(n));
-    DVO_TRY(has_kf.alloc(n));
-    DVO_TRY(eff.alloc((n + 3) & ~(size_t)3));   // (read as 32-bit words by k_regularize_redecimate_plan)
+    DVO_TRY(plan.alloc(n_seq, trk.n_sub, latest_id >= 0, stream));   // (after plain calls every sequence has a keyframe)
     DVO_TRY(started.alloc(n));
-    DVO_TRY(status.alloc(sizeof(int) * n));
     DVO_TRY(need_save.alloc(sizeof(int) * n));
-    DVO_TRY(plan_lists.alloc(2 * sizeof(int) * (size_t)trk.n_sub * (n + 4)));
-    DVO_TRY(plan_tally.alloc(2 * sizeof(int)));
-    for (int i = 0; i < 2; i++) {
-        DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_act[i]), n, hipHostMallocDefault));
-        DVO_HIP(hipEventCreateWithFlags(&ev_act[i], hipEventDisableTiming));
-    }
-    DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_ready), 2 * sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
-    h_ready[0] = h_ready[1] = 0;
-    DVO_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&d_ready), h_ready, 0));
-    // in stream order: after plain calls every sequence has a keyframe; the list counts start at zero
-    DVO_HIP(hipMemsetAsync(has_kf.p, latest_id >= 0 ? 1 : 0, n, stream));
     DVO_HIP(hipMemsetAsync(started.p, latest_id >= 0 ? 1 : 0, n, stream));
-    DVO_HIP(hipMemsetAsync(plan_lists.p, 0, plan_lists.bytes, stream));
-    DVO_HIP(hipMemsetAsync(plan_tally.p, 0, plan_tally.bytes, stream));
     if (!host_init) {   // the start map of a later start without a host map: the default (what dvo_vo uses)
         std::vector<float> d, s;
         const size_t np = (size_t)top_pixels();
@@ -457,25 +398,12 @@ int MonoBatch::alloc_plan()
 }
 
 int MonoBatch::set_actions(const uint8_t* actions, bool on_device)
-{  // as Batch::set_actions
-    if (!actions) { act_pending = false; act_src = nullptr; return DVO_OK; }
-    DVO_TRY(select_device(device));
-    DVO_TRY(alloc_plan());
-    if (on_device) {
-        act_src = actions;   // read by k_plan in stream order
-    } else {
-        // copied now into pinned staging, then to the device in stream order (after the k_plan of every earlier call)
-        const int k = act_slot;
-        act_slot ^= 1;
-        if (act_staged[k]) DVO_HIP(hipEventSynchronize(ev_act[k]));   // (that copy was queued two calls ago)
-        memcpy(h_act[k], actions, (size_t)n_seq);
-        DVO_HIP(hipMemcpyAsync(act_dev.p, h_act[k], (size_t)n_seq, hipMemcpyHostToDevice, stream));
-        DVO_HIP(hipEventRecord(ev_act[k], stream));
-        act_staged[k] = true;
-        act_src = act_dev.as<uint8_t>();
+{
+    if (actions) {
+        DVO_TRY(select_device(device));
+        DVO_TRY(alloc_plan());
     }
-    act_pending = true;
-    return DVO_OK;
+    return plan.set_actions(actions, on_device, n_seq, stream);
 }
 
 int MonoBatch::set_start_depth(const float* depth_dev, const float* sigma_dev)
@@ -493,23 +421,14 @@ int MonoBatch::status_of_last(int* out, bool out_on_device)
 {
     if (latest_id < 0) { set_error("dvo_batch_mono_last_status: no frame has been consumed yet"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
-    if (!act_used) {   // plain calls: the first one starts every sequence, every later one tracks every sequence
-        const int v = latest_id == 0 ? DVO_SEQ_STARTED : DVO_SEQ_TRACKED;
-        if (out_on_device) { DVO_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), v, (size_t)n_seq, stream)); return DVO_OK; }
-        DVO_HIP(hipStreamSynchronize(stream));   // (as a read-back of the device buffer would)
-        for (int q = 0; q < n_seq; q++) out[q] = v;
-        return DVO_OK;
-    }
-    DVO_HIP(hipMemcpyAsync(out, status.p, sizeof(int) * (size_t)n_seq, out_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, stream));
-    if (!out_on_device) DVO_HIP(hipStreamSynchronize(stream));
-    return DVO_OK;
+    return plan.status_of_last(out, out_on_device, n_seq, latest_id == 0, stream);
 }
 
 int MonoBatch::set_guess_mode(int mode)
 {
     DVO_TRY(select_device(device));
     // the call before: its effective actions (per-sequence path), else all STARTED (first call) or all TRACKED (later ones)
-    const uint8_t* pe = act_used ? eff.as<uint8_t>() : nullptr;
+    const uint8_t* pe = plan.act_used ? plan.eff.as<uint8_t>() : nullptr;
     const int all = latest_id < 0 ? 0xff : (latest_id == 0 ? DVO_SEQ_RESTART : DVO_SEQ_TRACK);
     return guess.set_mode(mode, n_seq, stream, pe, all);
 }
@@ -517,7 +436,7 @@ int MonoBatch::set_guess_mode(int mode)
 int MonoBatch::started_of(int seq, bool* out)
 {
     if (latest_id < 0) { *out = false; return DVO_OK; }
-    if (!act_used) { *out = true; return DVO_OK; }
+    if (!plan.act_used) { *out = true; return DVO_OK; }
     uint8_t v = 0;
     DVO_HIP(hipMemcpyAsync(&v, started.as<uint8_t>() + seq, 1, hipMemcpyDeviceToHost, stream));
     DVO_HIP(hipStreamSynchronize(stream));
@@ -593,7 +512,7 @@ int dvo_batch_odometrize_host(dvo_batch* b, const float* gray)
     DVO_NEED_MONO(b);
     FrameInput in;
     in.gray = gray;
-    return b->mono->odometrize_host(gray, sizeof(float) * (size_t)b->mono->n_seq * b->mono->g.src_w * b->mono->g.src_h, in);
+    return b->mono->odometrize_host(gray, in);
 }
 
 int dvo_batch_odometrize_raw_host(dvo_batch* b, const uint8_t* rgb, int channels)
@@ -602,7 +521,7 @@ int dvo_batch_odometrize_raw_host(dvo_batch* b, const uint8_t* rgb, int channels
     if (channels != 1 && channels != 3 && channels != 4) { set_error("bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
     FrameInput in;
     in.rgb = rgb; in.channels = channels;
-    return b->mono->odometrize_host(rgb, (size_t)channels * b->mono->n_seq * b->mono->g.src_w * b->mono->g.src_h, in);
+    return b->mono->odometrize_host(rgb, in);
 }
 
 int dvo_batch_set_distortion(dvo_batch* b, const float* D, int per_sequence)
@@ -743,7 +662,7 @@ int dvo_batch_mono_stats(dvo_batch* b, int seq, dvo_mono_stats* out)
     MonoSeq m;
     DVO_HIP(hipMemcpyAsync(&m, M.meta.as<MonoSeq>() + seq, sizeof m, hipMemcpyDeviceToHost, M.stream));
     DVO_HIP(hipStreamSynchronize(M.stream));
-    out->frames = M.act_used ? m.frame_id + 1 : M.latest_id + 1;   // (with actions: the frames since the sequence's last start)
+    out->frames = M.plan.act_used ? m.frame_id + 1 : M.latest_id + 1;   // (with actions: the frames since the sequence's last start)
     out->keyframes_created = m.n_total;
     out->ring_keyframes = M.R;
     out->valid_updates_last_frame = m.valid_updates;
