@@ -675,7 +675,6 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     DVO_TRY(res.alloc(sizeof(dvo_gn_result)));
     if (mask) { DVO_TRY(mk.alloc(n)); DVO_HIP(hipMemsetAsync(mk.p, 0, n, c.s)); }
     launch_set_pose(trk.state.as<SeqState>(), xin.as<float>(), 1, c.s);
-    GnArgs ga{};
     // per-pixel constants of the reference level (what build_pyramid does for whole frames)
     DevBuf wgb;
     DVO_TRY(wgb.alloc(n * 4));
@@ -688,27 +687,11 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         pa.levels = 1;
         launch_prep_ref(pa, c.s);
     }
-    ga.obj_gray = og.as<float>(); ga.ref_gray = rg.as<float>(); ga.ref_depth = rd.as<float>();
-    ga.ref_wgt = wgb.as<float>();
-    ga.state = trk.state.as<SeqState>();
-    ga.partials = trk.partials.as<float>();
-    ga.mask = mask ? mk.as<uint8_t>() : nullptr;
-    ga.w = w; ga.h = h; ga.nblk = trk.nblk[level]; ga.inv_w = 1.0f / (float)w;
-    ga.q256 = 256 / w; ga.r256 = 256 % w;
-    ga.k = gl.k[level];
-    ga.prm = trk.level_params(level);
-    ga.ignore_active = 1;
-    ga.tiles_x = trk.tiles_x[level]; ga.tiles_y = trk.tiles_y[level]; ga.margin = trk.tile_margin;
+    const GnArgs ga = trk.gn_args(og.as<float>(), rg.as<float>(), rd.as<float>(), wgb.as<float>(), 0.0f, level, mask ? mk.as<uint8_t>() : nullptr, 1);
     trk.launch_gn(ga, level, 1, c.s);
-    SolveArgs sa{};
-    sa.state = trk.state.as<SeqState>(); sa.partials = trk.partials.as<float>(); sa.result = res.as<dvo_gn_result>();
-    sa.nblk = trk.nblk[level]; sa.level = level; sa.level_pixels = w * h;
-    sa.max_iterations = cf.max_iterations; sa.fixed_iterations = cf.fixed_iterations;
-    sa.min_update = cf.min_update; sa.min_residual = cf.min_residual; sa.ignore_active = 1;
-    if (trk.tile_margin == 0) {
-        const GnTiling tl = gn_tiling(w, h, trk.ppt[level], ga.prm.crop);
-        sa.blk_first = tl.live_first; sa.blk_count = tl.live_count;
-    }
+    SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
+    sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
+    sa.result = res.as<dvo_gn_result>();
     launch_gn_solve(sa, 1, c.s);
     DVO_HIP(hipMemcpyAsync(out, res.p, sizeof *out, hipMemcpyDeviceToHost, c.s));
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));

@@ -390,17 +390,18 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     tile_margin = cfg.gn_use_lds_patch < 0 ? 0 : cfg.gn_use_lds_patch;
     if (tile_margin > 24) tile_margin = 24;
     for (int l = 0; l < g.levels; l++) {
+        LevelPlan& L = lv[l];
+        L = LevelPlan{};
         int p = cfg.gn_pixels_per_thread;
         const bool auto_p = (p != 1 && p != 2 && p != 4 && p != 8);
         if (auto_p) p = 4;  // auto: biggest tile that still gives >= 4 workgroups per CU
-        fused[l] = false;
         if (tile_margin > 0) {
-            gn_tile_geometry(g.w[l], g.h[l], p, tiles_x[l], tiles_y[l]);
-            while (auto_p && p > 1 && (size_t)n_seq * tiles_x[l] * tiles_y[l] < 1024) {
+            gn_tile_geometry(g.w[l], g.h[l], p, L.tiles_x, L.tiles_y);
+            while (auto_p && p > 1 && (size_t)n_seq * L.tiles_x * L.tiles_y < 1024) {
                 p >>= 1;
-                gn_tile_geometry(g.w[l], g.h[l], p, tiles_x[l], tiles_y[l]);
+                gn_tile_geometry(g.w[l], g.h[l], p, L.tiles_x, L.tiles_y);
             }
-            nblk[l] = tiles_x[l] * tiles_y[l];
+            L.nblk = L.tiles_x * L.tiles_y;
         } else {
             // small levels: every iteration inside one k_track_level launch (tiles of 256 x 4 pixels)
             // Off by default: measured on MI355X (512 sequences) the one-workgroup-per-sequence form runs the two coarse
@@ -410,24 +411,24 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
                                                             : (cfg.track_fused_tiles > DVO_FUSED_MAX_TILES ? DVO_FUSED_MAX_TILES : cfg.track_fused_tiles);
             const int crop_l = level_params(l).crop;
             const GnTiling t4 = gn_tiling(g.w[l], g.h[l], 4, crop_l);
-            fused[l] = fuse_max > 0 && !t4.t2d && t4.count <= fuse_max;  // (k_track_level: raster tiles)
-            if (fused[l]) p = 4;
+            L.fused = fuse_max > 0 && !t4.t2d && t4.count <= fuse_max;  // (k_track_level: raster tiles)
+            if (L.fused) p = 4;
             // (one sequence on the one-launch-per-call schedule keeps 4 pixels per thread: k_track_persist's workgroups wait for each
             //  other, and 75 of them hand over faster than 300 -- 406 against 451 us per 640x480 frame, profiles/r03_single_ab.txt)
             //  A mono handle's levels (at most 160 x 120) show no such difference -- 132-140 us per frame at 1, 2 and 4 pixels per
             //  thread -- so it keeps the tile size every other schedule picks for one sequence (persist_ppt < 0): the same bits.)
             const bool single_p4 = prefer_persist && n_seq == 1 && cfg.track_single_launch == 0 && !cfg.profile && persist_ppt >= 0;
             if (single_p4 && auto_p && persist_ppt > 0) p = persist_ppt;
-            while (!fused[l] && auto_p && !single_p4 && p > 1 && (size_t)n_seq * gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l) < 1024) p >>= 1;
-            nblk[l] = gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l);
-            tiles_x[l] = tiles_y[l] = 0;
+            while (!L.fused && auto_p && !single_p4 && p > 1 && (size_t)n_seq * gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l) < 1024) p >>= 1;
+            L.tiling = gn_tiling(g.w[l], g.h[l], p, crop_l);   // the level's tiles are decided: every launch takes them from here
+            L.nblk = L.tiling.count;
         }
-        ppt[l] = p;
+        L.ppt = p;
         int gg = cfg.gn_gather_group;
         if (gg != 1 && gg != 2 && gg != 4) gg = 2;
         while (gg > p || p % gg) gg >>= 1;
-        group[l] = gg < 1 ? 1 : gg;
-        if ((size_t)nblk[l] > max_part) max_part = nblk[l];
+        L.group = gg < 1 ? 1 : gg;
+        if ((size_t)L.nblk > max_part) max_part = L.nblk;
     }
     DVO_TRY(state.alloc(sizeof(SeqState) * (size_t)n_seq));
     part_rows = max_part;
@@ -465,18 +466,18 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     // VGPRs (two waves per SIMD), so only where the level's grid is a few dozen workgroups -- measured on one 640x480 stream:
     // 14-16 us per iteration against 17-18 us for the launch pair up to 52 workgroups, but 31 us against 18 us at 300
     for (int l = 0; l < g.levels; l++) {
-        const GnTiling tl = gn_tiling(g.w[l], g.h[l], ppt[l], level_params(l).crop);
-        single_launch[l] = cfg.track_single_launch >= 0 && n_seq <= 8 && tile_margin == 0 && !fused[l] && !cfg.profile && n_sub == 1 &&
-                           gn_fused_available(ppt[l], group[l]) && tl.live_count > 0 && (long long)n_seq * tl.live_count <= 64;
+        LevelPlan& L = lv[l];
+        L.single_launch = cfg.track_single_launch >= 0 && n_seq <= 8 && tile_margin == 0 && !L.fused && !cfg.profile && n_sub == 1 &&
+                          gn_fused_available(L.ppt, L.group) && L.tiling.live_count > 0 && (long long)n_seq * L.tiling.live_count <= 64;
     }
     // k_track_persist (one launch per track() call): one sequence, the global-gather kernel, one (ppt, group) pair on every level,
     // every level within the wide reduction's row limit, no profiling; track_single_launch: < 0 = launch pairs only, 1 = one launch per
     // iteration at most (k_track_gn_fused), 0 (default) = one launch per call where the result goes through enable_host_result()
-    persist_ok = prefer_persist && n_seq == 1 && tile_margin == 0 && !cfg.profile && cfg.track_single_launch == 0 && n_sub == 1 && track_persist_available(ppt[0], group[0]);
+    persist_ok = prefer_persist && n_seq == 1 && tile_margin == 0 && !cfg.profile && cfg.track_single_launch == 0 && n_sub == 1 && track_persist_available(lv[0].ppt, lv[0].group);
     int max_tiles = 0;
     for (int l = 0; l < g.levels && persist_ok; l++) {
-        const GnTiling tl = gn_tiling(g.w[l], g.h[l], ppt[l], level_params(l).crop);
-        if (ppt[l] != ppt[0] || group[l] != group[0] || fused[l] || nblk[l] > 320 || tl.live_count <= 0) persist_ok = false;
+        const GnTiling& tl = lv[l].tiling;
+        if (lv[l].ppt != lv[0].ppt || lv[l].group != lv[0].group || lv[l].fused || lv[l].nblk > 320 || tl.live_count <= 0) persist_ok = false;
         if (tl.live_count > max_tiles) max_tiles = tl.live_count;
     }
     // ~0.2 s of polling per wait: far beyond any iteration, short enough that a wedged launch ends.  DVO_PERSIST_SPIN_LIMIT (tests): a
@@ -486,7 +487,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     persist_timeline = getenv("DVO_PERSIST_TIMELINE") != nullptr;
     if (persist_ok) {
         int cap = 0;
-        if (track_persist_max_grid(ppt[0], group[0], &cap) != DVO_OK || cap < 1) persist_ok = false;
+        if (track_persist_max_grid(lv[0].ppt, lv[0].group, &cap) != DVO_OK || cap < 1) persist_ok = false;
         else {
             persist_grid = 1 + (max_tiles < cap - 1 ? max_tiles : cap - 1);   // the solver + one worker per tile of the largest level, all resident at once (they wait for each other)
             DVO_TRY(persist_ctl.alloc((16 + (size_t)persist_grid) * sizeof(int)));   // control line (64 B) + one arrival slot per workgroup
@@ -516,34 +517,49 @@ GnParams Tracker::level_params(int level) const
     return p;
 }
 
-GnArgs Tracker::gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const
+GnArgs Tracker::gn_args(const float* obj_gray, const float* ref_gray, const float* ref_depth, const float* ref_wgt, float wgt_const, int level,
+                        uint8_t* mask, int ignore_active) const
 {
+    const LevelPlan& L = lv[level];
     GnArgs a{};
-    a.obj_gray = obj.gray[level];
-    a.ref_gray = ref.gray[level];
-    a.ref_depth = ref.depth[level];
-    a.ref_wgt = ref.sigma_by_validity ? nullptr : ref.wgt[level];
-    a.wgt_const = ref.sigma_by_validity ? ref.wgt_valid[level] : 0.0f;
+    a.obj_gray = obj_gray;
+    a.ref_gray = ref_gray;
+    a.ref_depth = ref_depth;
+    a.ref_wgt = ref_wgt;
+    a.wgt_const = wgt_const;
     a.state = state.as<SeqState>();
     a.partials = partials.as<float>();
     a.mask = mask;
-    a.w = g.w[level]; a.h = g.h[level]; a.nblk = nblk[level];
+    a.w = g.w[level]; a.h = g.h[level]; a.nblk = L.nblk;
     a.inv_w = 1.0f / (float)g.w[level];
     a.q256 = 256 / g.w[level]; a.r256 = 256 % g.w[level];
     a.k = g.k[level];
     a.prm = level_params(level);
     a.ignore_active = ignore_active;
-    a.tiles_x = tiles_x[level]; a.tiles_y = tiles_y[level]; a.margin = tile_margin;
+    // the level's tiles (k_track_gn_tile: L.tiling is the default, whose fields are the ones GnArgs starts with)
+    a.blk_first = L.tiling.live_first; a.blk_count = L.tiling.live_count;
+    a.t_shift = L.tiling.shift; a.x_org = L.tiling.x_org; a.y_org = L.tiling.y_org;
+    a.tiles_x = L.tiling.t2d ? L.tiling.tiles_x : L.tiles_x; a.tiles_y = L.tiles_y; a.margin = tile_margin;
     return a;
 }
 
-SolveArgs Tracker::solve_args(int level, int q0, int ignore_active) const
+GnArgs Tracker::gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const
 {
+    return gn_args(obj.gray[level], ref.gray[level], ref.depth[level], ref.sigma_by_validity ? nullptr : ref.wgt[level],
+                   ref.sigma_by_validity ? ref.wgt_valid[level] : 0.0f, level, mask, ignore_active);
+}
+
+SolveArgs Tracker::solve_args(int level, int q0, int ignore_active, SolveRows rows) const
+{
+    const GnTiling& tl = lv[level].tiling;
     SolveArgs a{};
     a.state = state.as<SeqState>() + q0;
-    a.partials = partials.as<float>() + (size_t)q0 * part_rows * 32;   // (track()'s GnArgs view of these sequences)
+    a.partials = partials.as<float>() + (size_t)q0 * part_rows * 32;   // (gn_view()'s partials of these sequences)
     a.log = log.as<dvo_track_log>() + q0;
-    a.nblk = nblk[level]; a.level = level; a.level_pixels = g.w[level] * g.h[level];
+    a.nblk = lv[level].nblk; a.level = level;
+    // (profile counter: the pixels k_track_gn actually reads -- tiles outside the crop rows are never launched)
+    a.level_pixels = rows == SolveRows::LivePair ? (int)tl.live_pixels : g.w[level] * g.h[level];
+    if (rows != SolveRows::All) { a.blk_first = tl.live_first; a.blk_count = tl.live_count; }
     a.max_iterations = cfg.max_iterations; a.fixed_iterations = cfg.fixed_iterations;
     a.min_update = cfg.min_update; a.min_residual = cfg.min_residual;
     a.ignore_active = ignore_active;
@@ -553,8 +569,84 @@ SolveArgs Tracker::solve_args(int level, int q0, int ignore_active) const
 
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
 {
-    if (tile_margin > 0) launch_track_gn_tile(a, count, ppt[level], s);
-    else launch_track_gn(a, count, ppt[level], group[level], s, grid_seqs);
+    const LevelPlan& L = lv[level];
+    if (tile_margin > 0) launch_track_gn_tile(a, count, L.ppt, s);
+    else launch_track_gn(a, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+}
+
+GnArgs Tracker::gn_view(const GnArgs& all, int level, int q0, const TrackPlan* plan, const Intr* seq_k) const
+{
+    const size_t level_px = (size_t)g.w[level] * g.h[level];
+    GnArgs ga = all;
+    ga.obj_gray += q0 * level_px; ga.ref_gray += q0 * level_px; ga.ref_depth += q0 * level_px;
+    if (ga.ref_wgt) ga.ref_wgt += q0 * level_px;
+    ga.state += q0;
+    // (a level-independent stride: with q0 * nblk[level], sub-batch k at a coarse level wrote into the rows of sub-batch k - 1
+    //  at a finer level while both ran -- the nondeterminism of track_streams = 2 recorded in DESIGN.md section 12)
+    ga.partials += (size_t)q0 * part_rows * 32;
+    if (plan) ga.plan_action = plan->action + q0;
+    if (seq_k) ga.seq_k = seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
+    return ga;
+}
+
+// One level of k_track_persist: the level's GnArgs, plus what GnArgs does not carry
+static PersistLevel persist_level(const GnArgs& ga, const GnTiling& tl)
+{
+    PersistLevel L{};
+    L.obj_gray = ga.obj_gray; L.ref_gray = ga.ref_gray; L.ref_depth = ga.ref_depth; L.ref_wgt = ga.ref_wgt; L.wgt_const = ga.wgt_const;
+    L.inv_w = ga.inv_w; L.w = ga.w; L.h = ga.h; L.nblk = ga.nblk; L.q256 = ga.q256; L.r256 = ga.r256; L.k = ga.k; L.prm = ga.prm;
+    L.blk_first = ga.blk_first; L.blk_count = ga.blk_count; L.t_shift = ga.t_shift; L.x_org = ga.x_org; L.y_org = ga.y_org;
+    L.tiles_x = ga.tiles_x; L.t2d = tl.t2d; L.level_pixels = (int)tl.live_pixels;
+    return L;
+}
+
+int Tracker::next_result_tag()
+{
+    result_tag = (result_tag + 1) & 0x1fffff;
+    if (result_tag == 0) result_tag = 1;
+    return result_tag;
+}
+
+int Tracker::track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s, bool* launched)
+{
+    *launched = false;
+    PersistArgs pa{};
+    pa.levels = g.levels;
+    for (int l = 0; l < g.levels; l++) pa.lv[l] = persist_level(gn_args(obj, ref, l, nullptr, 0), lv[l].tiling);
+    pa.state = state.as<SeqState>(); pa.partials = partials.as<float>(); pa.log = log.as<dvo_track_log>();
+    pa.ctl = persist_ctl.as<int>();
+    pa.max_iterations = cfg.max_iterations; pa.fixed_iterations = cfg.fixed_iterations;
+    pa.min_update = cfg.min_update; pa.min_residual = cfg.min_residual;
+    pa.xi_out = xi_out.as<float>(); pa.T_out = T_out.as<float>(); pa.host_result = d_result;
+    pa.host_tag = next_result_tag();
+    pa.spin_limit = persist_spin_limit;
+    pa.mono = mono_tail;
+    if (persist_timeline) {   // diagnostic: stamps of the solver and of worker 0 (tools/persist_timeline.py reads them back)
+        if (!persist_dbg.p) { DVO_TRY(persist_dbg.alloc(2 * 64 * 8 * sizeof(long long))); }
+        DVO_HIP(hipMemsetAsync(persist_dbg.p, 0, persist_dbg.bytes, s));
+        pa.dbg = persist_dbg.as<long long>();
+        pa.dbg_worker = atoi(getenv("DVO_PERSIST_TIMELINE"));
+    }
+    if (!launch_track_persist(pa, lv[0].ppt, lv[0].group, persist_grid, s)) return DVO_OK;
+    persist_used = true;
+    *launched = true;
+    DVO_HIP(hipGetLastError());
+    return DVO_OK;
+}
+
+// The adaptive schedule's bounded wait for a word in mapped host memory that a kernel queued on `s` sets to a non-zero value
+static int wait_progress(const volatile int* word, hipStream_t s)
+{
+    long spins = 0;
+    while (*word == 0) {
+        if (++spins > 2000000000L) {
+            (void)hipStreamSynchronize(s);  // nothing may be left writing the progress words / state when we return
+            set_error("adaptive schedule: the GPU made no progress");
+            return DVO_ERR_HIP;
+        }
+        __builtin_ia32_pause();
+    }
+    return DVO_OK;
 }
 
 int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan)
@@ -564,38 +656,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
     const Intr* seq_k = plan ? plan->seq_k : cam_k;
     if (persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed) {   // the whole call in one launch (k_track_persist)
-        PersistArgs pa{};
-        pa.levels = g.levels;
-        for (int l = 0; l < g.levels; l++) {
-            const GnArgs ga = gn_args(obj, ref, l, nullptr, 0);
-            const GnTiling tl = gn_tiling(ga.w, ga.h, ppt[l], ga.prm.crop);
-            PersistLevel& L = pa.lv[l];
-            L.obj_gray = ga.obj_gray; L.ref_gray = ga.ref_gray; L.ref_depth = ga.ref_depth; L.ref_wgt = ga.ref_wgt; L.wgt_const = ga.wgt_const;
-            L.inv_w = ga.inv_w; L.w = ga.w; L.h = ga.h; L.nblk = ga.nblk; L.q256 = ga.q256; L.r256 = ga.r256; L.k = ga.k; L.prm = ga.prm;
-            L.blk_first = tl.live_first; L.blk_count = tl.live_count; L.t_shift = tl.shift; L.x_org = tl.x_org; L.y_org = tl.y_org;
-            L.tiles_x = tl.t2d ? tl.tiles_x : 0; L.t2d = tl.t2d; L.level_pixels = (int)tl.live_pixels;
-        }
-        pa.state = state.as<SeqState>(); pa.partials = partials.as<float>(); pa.log = log.as<dvo_track_log>();
-        pa.ctl = persist_ctl.as<int>();
-        pa.max_iterations = cfg.max_iterations; pa.fixed_iterations = cfg.fixed_iterations;
-        pa.min_update = cfg.min_update; pa.min_residual = cfg.min_residual;
-        pa.xi_out = xi_out.as<float>(); pa.T_out = T_out.as<float>(); pa.host_result = d_result;
-        result_tag = (result_tag + 1) & 0x1fffff;
-        if (result_tag == 0) result_tag = 1;
-        pa.host_tag = result_tag;
-        pa.spin_limit = persist_spin_limit;
-        pa.mono = mono_tail;
-        if (persist_timeline) {   // diagnostic: stamps of the solver and of worker 0 (tools/persist_timeline.py reads them back)
-            if (!persist_dbg.p) { DVO_TRY(persist_dbg.alloc(2 * 64 * 8 * sizeof(long long))); }
-            DVO_HIP(hipMemsetAsync(persist_dbg.p, 0, persist_dbg.bytes, s));
-            pa.dbg = persist_dbg.as<long long>();
-            pa.dbg_worker = atoi(getenv("DVO_PERSIST_TIMELINE"));
-        }
-        if (launch_track_persist(pa, ppt[0], group[0], persist_grid, s)) {
-            persist_used = true;
-            DVO_HIP(hipGetLastError());
-            return DVO_OK;
-        }
+        bool launched = false;
+        DVO_TRY(track_persist(obj, ref, s, &launched));
+        if (launched) return DVO_OK;
     }
     if (!plan) launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
     if (seed) {   // the start pose of every TRACK sequence (dvo_batch_set_pose_guess_mode), before the fork
@@ -624,7 +687,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         for (int i = 0; i < DVO_MAX_LEVELS * DVO_MAX_ITERATIONS; i++) prog_h[i] = 0;
     }
     bool any_single = false;
-    for (int l = 0; l < g.levels; l++) any_single = any_single || single_launch[l];
+    for (int l = 0; l < g.levels; l++) any_single = any_single || lv[l].single_launch;
     int* rep_set = freport.as<int>() + (size_t)(progress_set & 1) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS;
     if (any_single) DVO_HIP(hipMemsetAsync(rep_set, 0, sizeof(int) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS, s));
     static const char* const kLevelName[DVO_MAX_LEVELS] = {"track level 0", "track level 1", "track level 2", "track level 3", "track level 4",
@@ -632,22 +695,14 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     // adaptive schedule with a plan: k_plan's word says how many sequences track; with none, no level is launched at all
     int n_levels = g.levels;
     if (adaptive && plan && plan->ready) {
-        long spins = 0;
-        while (*plan->ready == 0) {
-            if (++spins > 2000000000L) {
-                (void)hipStreamSynchronize(s);
-                set_error("adaptive schedule: the GPU made no progress");
-                return DVO_ERR_HIP;
-            }
-            __builtin_ia32_pause();
-        }
+        DVO_TRY(wait_progress(plan->ready, s));
         if (*plan->ready - 1 == 0) n_levels = 0;
     }
     for (int level = 0; level < n_levels; level++) {  // tracker.cpp:32
         TraceRange tr(kLevelName[level]);
-        const bool lists = tile_margin == 0 && !single_launch[level];  // (k_track_gn_tile keeps the per-sequence active flag test)
-        const size_t level_px = (size_t)g.w[level] * g.h[level];
-        const int host_its = fused[level] ? 1 : max_it;  // a fused level iterates on the device (k_track_level)
+        const LevelPlan& L = lv[level];
+        const bool lists = tile_margin == 0 && !L.single_launch;  // (k_track_gn_tile keeps the per-sequence active flag test)
+        const int host_its = L.fused ? 1 : max_it;  // a fused level iterates on the device (k_track_level)
         for (int it = 0; it < host_its; it++) {        // tracker.cpp:42
             const int first = (it == 0) ? 1 : 0;
             // Stay `ahead` iterations ahead of the GPU: wait until launch it-ahead of this level has reported, and stop the level
@@ -657,49 +712,32 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
             // is an empty launch pair (~15 us): measured +1.6 % (mono, 1 iteration per level) / +0.7 % (sensor depth) against 4.
             const int ahead = 2;
             int active_ub = 0;   // sequences that entered iteration it - ahead: the active set only shrinks within a level, so this bounds the list of `it`
-            if (adaptive && !fused[level] && it >= ahead) {
+            if (adaptive && !L.fused && it >= ahead) {
                 volatile int* pw = prog_h + level * DVO_MAX_ITERATIONS + (it - ahead);
-                long spins = 0;
-                while (*pw == 0) {
-                    if (++spins > 2000000000L) {
-                        (void)hipStreamSynchronize(s);  // nothing may be left writing the progress words / state when we return
-                        set_error("adaptive schedule: the GPU made no progress");
-                        return DVO_ERR_HIP;
-                    }
-                    __builtin_ia32_pause();
-                }
+                DVO_TRY(wait_progress(pw, s));
                 if (*pw - 1 == 0) break;
-                if (!single_launch[level]) active_ub = *pw - 1;
+                if (!L.single_launch) active_ub = *pw - 1;
             }
             const GnArgs ga0 = gn_args(obj, ref, level, nullptr, first);
             for (int k = 0; k < subs; k++) {  // launches of the sub-batches interleave on their streams
                 const int q0 = subs > 1 ? sub_first(k) : 0, q1 = subs > 1 ? sub_first(k + 1) : n_seq, nq = q1 - q0;
                 hipStream_t sk = k == 0 ? s : sub_streams[k - 1];
-                GnArgs ga = ga0;  // view of sequences [q0, q1)
-                ga.obj_gray += q0 * level_px; ga.ref_gray += q0 * level_px; ga.ref_depth += q0 * level_px;
-                if (ga.ref_wgt) ga.ref_wgt += q0 * level_px;
-                ga.state += q0;
-                // (a level-independent stride: with q0 * nblk[level], sub-batch k at a coarse level wrote into the rows of sub-batch k - 1
-                //  at a finer level while both ran -- the nondeterminism of track_streams = 2 recorded in DESIGN.md section 12)
-                ga.partials += (size_t)q0 * part_rows * 32;
-                // with a plan a level starts with the plan's sequences of this sub-batch, not all of them
-                const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
-                if (plan) ga.plan_action = plan->action + q0;
-                if (seq_k) ga.seq_k = seq_k + (size_t)level * n_seq + q0;   // this level's row, this sub-batch
-                if (single_launch[level]) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
-                    const SolveArgs fa = solve_args(level, q0, first);
-                    if (launch_track_gn_fused(ga, fa, nq, ppt[level], group[level], ticket.as<int>(), rep_set + 2 * (level * DVO_MAX_ITERATIONS + it),
-                                              adaptive ? prog_d + level * DVO_MAX_ITERATIONS + it : nullptr, sk))
+                GnArgs ga = gn_view(ga0, level, q0, plan, seq_k);  // view of sequences [q0, q1)
+                if (L.single_launch) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
+                    const SolveArgs fa = solve_args(level, q0, first, SolveRows::Live);
+                    if (launch_track_gn_fused(ga, fa, nq, L.ppt, L.group, L.tiling.t2d != 0, ticket.as<int>(),
+                                              rep_set + 2 * (level * DVO_MAX_ITERATIONS + it), adaptive ? prog_d + level * DVO_MAX_ITERATIONS + it : nullptr, sk))
                         continue;
                 }
-                if (fused[level]) {
-                    SolveArgs fa = solve_args(level, q0, 1);
+                if (L.fused) {
+                    SolveArgs fa = solve_args(level, q0, 1, SolveRows::All);
                     fa.partials = nullptr;
                     launch_track_level(ga, fa, nq, sk);
                     continue;
                 }
-                // iteration `it` evaluates the sequences k_gn_solve(it - 1) left active (all of them when it == 0) and
-                // clears the list k_gn_solve(it) appends to
+                // iteration `it` evaluates the sequences k_gn_solve(it - 1) left active (all of them when it == 0; with a plan the
+                // plan's sequences of this sub-batch) and clears the list k_gn_solve(it) appends to
+                const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
                 const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
                 ga.list = list_prev;
                 ga.next_count = lists ? work_list(k, it) : nullptr;
@@ -717,21 +755,14 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 } else {
                     launch_gn(ga, level, nq, sk, active_ub);
                 }
-                SolveArgs sa = solve_args(level, q0, first);
+                SolveArgs sa = solve_args(level, q0, first, lists ? SolveRows::LivePair : SolveRows::All);
                 sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;   // (they describe k_track_gn launches only)
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                if (lists) {
-                    // (profile counter: the pixels k_track_gn actually reads -- tiles outside the crop rows are never launched)
-                    const GnTiling tl = gn_tiling(ga.w, ga.h, ppt[level], ga.prm.crop);
-                    sa.blk_first = tl.live_first; sa.blk_count = tl.live_count;
-                    const long long live_px = tl.live_pixels;
-                    sa.level_pixels = (int)live_px;
-                }
                 launch_gn_solve(sa, nq, sk);
             }
-            if (poll && !fused[level] && it + 1 < max_it) {
+            if (poll && !L.fused && it + 1 < max_it) {
                 DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
                 DVO_HIP(hipStreamSynchronize(s));
                 bool any = false;
@@ -745,7 +776,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         DVO_HIP(hipEventRecord(ev_join[k - 1], sub_streams[k - 1]));
         DVO_HIP(hipStreamWaitEvent(s, ev_join[k - 1], 0));
     }
-    if (h_result) { result_tag = (result_tag + 1) & 0x1fffff; if (result_tag == 0) result_tag = 1; }
+    if (h_result) next_result_tag();
     launch_export_poses(state.as<SeqState>(), xi_out.as<float>(), T_out.as<float>(), n_seq, s, d_result, result_tag);
     DVO_HIP(hipGetLastError());
     return DVO_OK;

@@ -215,6 +215,24 @@ struct TrackQuality {
     int read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s);
 };
 
+// How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
+// copy the geometry from here into every argument block, and the launchers take the kernel instance from here.
+struct LevelPlan {
+    int ppt = 0, group = 0;          // pixels per thread and gather group: the kernel instance
+    int nblk = 0;                    // tiles (= partial rows) per sequence
+    GnTiling tiling;                 // the tiles of k_track_gn and of every kernel that shares them (tile_margin == 0; else the default)
+    int tiles_x = 0, tiles_y = 0;    // the tiles of k_track_gn_tile (tile_margin > 0, gn_tile_geometry; else 0)
+    bool fused = false;              // level runs as ONE k_track_level launch (all iterations on the device)
+    bool single_launch = false;      // level runs one k_track_gn_fused launch per iteration (small handles: see dvo_kernels.hip)
+};
+
+// Which partial rows a solve sums (SolveArgs::blk_first / blk_count) and what it adds to the profile counter (SolveArgs::level_pixels)
+enum class SolveRows {
+    All,        // every row, w * h pixels: k_track_gn_tile's solves, k_track_level, the launch pair after a refused k_track_gn_fused
+    Live,       // the level's live tiles, w * h pixels: the solves that feed no profile counter (k_track_gn_fused, dvo_op_gn_step)
+    LivePair,   // the level's live tiles and the pixels they cover: the k_gn_solve after a k_track_gn
+};
+
 struct Tracker {  // Track::Tracker for n_seq sequences at once
     Geometry g;
     int n_seq = 0;
@@ -235,10 +253,7 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     hipEvent_t ev_fork = nullptr;
     std::vector<hipEvent_t> ev_join;
     int sub_first(int k) const { return (int)(((long long)n_seq * k) / n_sub); }
-    int ppt[DVO_MAX_LEVELS], nblk[DVO_MAX_LEVELS], group[DVO_MAX_LEVELS];
-    int tiles_x[DVO_MAX_LEVELS], tiles_y[DVO_MAX_LEVELS];
-    bool fused[DVO_MAX_LEVELS];  // level runs as ONE k_track_level launch (all iterations on the device)
-    bool single_launch[DVO_MAX_LEVELS];  // level runs one k_track_gn_fused launch per iteration (small handles: see dvo_kernels.hip)
+    LevelPlan lv[DVO_MAX_LEVELS];
     DevBuf ticket, freport;      // k_track_gn_fused: arrival tickets [n_seq]; (reported, active) per (set, level, iteration)
     // Adaptive schedule: progress words in mapped host memory, one per (level, iteration), two sets used alternately.
     // k_gn_solve's workgroup 0 stores (active sequences + 1); the host reads them to stay ~2 iterations ahead of the GPU and
@@ -250,11 +265,6 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     SeqState* h_state = nullptr;  // pinned host mirror of `state` for the small-batch convergence poll
     int tile_margin = 0;  // > 0: k_track_gn_tile (LDS-staged reference patch); 0: k_track_gn (global gathers)
     void launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs = 0) const;  // `a` views `count` sequences
-    // Result hand-over for a handle that returns one pose per call (dvo_vo): k_export_poses also writes xi, T and a tag into
-    // fine-grained mapped host memory, and wait_host_result() polls the tag -- no device-to-host copy, no stream synchronisation.
-    // One launch per track() call (k_track_persist) for a single sequence whose result is handed over through h_result: eligible
-    // when every level fits the kernel's wide reduction and shares one tile size; `persist_failed` = a launch gave up waiting
-    // (GPU oversubscribed): the handle then stays on the launch-per-iteration schedule.
     // per-sequence intrinsics [level][n_seq] of a per-camera mono batch (dvo_batch_create_mono_cameras), used when track() has no
     // plan (a plan brings its own, TrackPlan::seq_k); nullptr: Geometry::k.  Never set together with prefer_persist.
     const Intr* cam_k = nullptr;
@@ -265,6 +275,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // a batch's quality records (dvo_batch_set_track_quality): while set, every solve of the finest level stores its sums here
     // (SolveArgs::result, [n_seq]), so each sequence's last one remains; nullptr: no record (the plain path's kernel arguments)
     dvo_gn_result* quality = nullptr;
+    // One launch per track() call (k_track_persist) for a single sequence whose result is handed over through h_result: eligible
+    // when every level fits the kernel's wide reduction and shares one tile size; `persist_failed` = a launch gave up waiting
+    // (GPU oversubscribed): the handle then stays on the launch-per-iteration schedule.
     bool prefer_persist = false;   // set before init() by the owner whose results go through enable_host_result() (VisualOdometry's sensor-depth tracker)
     bool persist_ok = false, persist_failed = false, persist_used = false;
     int persist_grid = 0, persist_spin_limit = 1 << 18;
@@ -272,6 +285,8 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     DevBuf persist_ctl, persist_dbg;
     int read_persist_timeline(long long* out);
     const FrameSet* last_obj = nullptr; const FrameSet* last_ref = nullptr;
+    // Result hand-over for a handle that returns one pose per call (dvo_vo): k_export_poses also writes xi, T and a tag into
+    // fine-grained mapped host memory, and wait_host_result() polls the tag -- no device-to-host copy, no stream synchronisation.
     float* h_result = nullptr;   // host view: [0..5] xi, [6..21] T, [22] tag (int), [23] tag of a persistent launch that gave up
     float* d_result = nullptr;   // device view of the same memory
     int result_tag = 0;
@@ -287,9 +302,18 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     ~Tracker();
     int init(const Geometry& geo, int n, const dvo_config& c);
     GnParams level_params(int level) const;
+    // The arguments of a level's Gauss-Newton launches for all n_seq sequences, tile geometry included (lv[level]); from the level's
+    // five maps, or from the frame sets that hold them
+    GnArgs gn_args(const float* obj_gray, const float* ref_gray, const float* ref_depth, const float* ref_wgt, float wgt_const, int level,
+                   uint8_t* mask, int ignore_active) const;
     GnArgs gn_args(const FrameSet& obj, const FrameSet& ref, int level, uint8_t* mask, int ignore_active) const;
-    // what every solve of a level shares, for the sequences from q0 on; each schedule adds its own fields
-    SolveArgs solve_args(int level, int q0, int ignore_active) const;
+    // `all` as seen by the sub-batch that starts at sequence q0: its part of every per-sequence array
+    GnArgs gn_view(const GnArgs& all, int level, int q0, const TrackPlan* plan, const Intr* seq_k) const;
+    // what every solve of a level shares, for the sequences from q0 on, summing `rows`; each schedule adds its own fields
+    SolveArgs solve_args(int level, int q0, int ignore_active, SolveRows rows) const;
+    int next_result_tag();   // the tag of this call's result (never 0)
+    // the whole call in one k_track_persist launch; *launched = false: there is no instance, the caller runs the other schedules
+    int track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s, bool* launched);
     // Tracker::track (tracker.cpp:22-85): enqueue the whole coarse-to-fine loop; poses land in xi_out / T_out
     // With a plan (Batch): k_plan has done k_track_begin's work, and a level's first iteration runs the plan's sequences, not all
     int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);

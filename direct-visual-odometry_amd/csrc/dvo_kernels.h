@@ -102,10 +102,13 @@ struct GnArgs {
     const int* list = nullptr;
     int* next_count = nullptr;
     int n_seq = 1;
-    int blk_first = 0, blk_count = 0;  // live tiles of a sequence; set by launch_track_gn from gn_tiling()
+    // The level's tile geometry, filled by Tracker::gn_args from the GnTiling that Tracker::init stored (the solve that sums the rows
+    // gets the same blk_first / blk_count from Tracker::solve_args).  k_track_gn_tile reads none of it.
+    int blk_first = 0, blk_count = 0;  // live tiles of a sequence
     int t_shift = 6, x_org = 0, y_org = 0;  // 2-D tiles (with tiles_x below): see GnTiling
-    // k_track_gn_tile only: 64 x (4*PPT) pixel tiles with the reference patch staged in LDS
-    int tiles_x, tiles_y;    // nblk = tiles_x * tiles_y
+    // k_track_gn_tile: 64 x (4*PPT) pixel tiles with the reference patch staged in LDS, nblk = tiles_x * tiles_y (gn_tile_geometry);
+    // the other kernels: tiles_x = GnTiling::tiles_x of a level with 2-D tiles, else 0
+    int tiles_x, tiles_y;
     int margin;              // patch = tile grown by margin+1 (left/top) and margin+2 (right/bottom) pixels
     // Batch plan: the effective action of each sequence of the launch (k_plan); only DVO_SEQ_TRACK sequences start a level.  Read by the
     // kernels that test per-sequence flags (k_track_gn_tile, k_track_gn_fused, k_track_level); k_track_gn gets the plan's list instead.
@@ -522,7 +525,10 @@ void launch_cull(const float* src, int w, int h, int times, float* dst, hipStrea
 void launch_gradient(const float* img, int w, int h, int xdir, float* out, hipStream_t s);
 void launch_warp_image(const float* gray, const float* depth, int w, int h, const Intr& k, const Pose& pose, float* out, hipStream_t s);
 int  gn_blocks_per_seq(int w, int h, int ppt, int crop);  // = gn_tiling(...).count
-void launch_track_gn(const GnArgs& a, int n_seq, int ppt, int group, hipStream_t s, int grid_seqs = 0);
+// The launchers below take GnArgs / SolveArgs complete (Tracker::gn_args, Tracker::solve_args) and set only what is theirs: n_seq, the
+// grid, and the fields their schedule does not use (list, next_count, mask, list_in / list_out, progress).  ppt, group and t2d (the
+// level has 2-D tiles, GnTiling::t2d) pick the kernel instance.
+void launch_track_gn(const GnArgs& a, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
 void launch_prep_ref(const PrepArgs& a, hipStream_t s);
 // LDS-tiled variant: a.tiles_x/tiles_y/margin/nblk must be set (see gn_tile_geometry)
 void launch_track_gn_tile(const GnArgs& a, int n_seq, int ppt, hipStream_t s);
@@ -533,11 +539,11 @@ inline void gn_tile_geometry(int w, int h, int ppt, int& tiles_x, int& tiles_y)
 }
 void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s);
 // one Tracker::track iteration in one launch for a few sequences (k_track_gn_fused); false = no instance for (ppt, group)
-bool launch_track_gn_fused(const GnArgs& a, const SolveArgs& sa, int n_seq, int ppt, int group, int* ticket, int* report, int* progress,
-                           hipStream_t s);
-inline bool gn_fused_available(int ppt, int group) { return (ppt == 1 && group == 1) || (ppt == 2 && group == 2) || (ppt == 4 && group == 2); }
+bool launch_track_gn_fused(const GnArgs& a, const SolveArgs& sa, int n_seq, int ppt, int group, bool t2d, int* ticket, int* report,
+                           int* progress, hipStream_t s);
+bool gn_fused_available(int ppt, int group);
 // k_track_level: every iteration of one level in one launch (one workgroup per sequence); the level must have been
-// tiled with 4 pixels per thread (ga.nblk = gn_blocks_per_seq(w, h, 4)) and have at most DVO_FUSED_MAX_TILES tiles
+// tiled with raster tiles of 4 pixels per thread (ga.nblk = gn_blocks_per_seq(w, h, 4)) and have at most DVO_FUSED_MAX_TILES tiles
 #define DVO_FUSED_MAX_TILES 8
 void launch_track_level(const GnArgs& ga, const SolveArgs& sa, int n_seq, hipStream_t s);
 void launch_track_begin(SeqState* state, dvo_track_log* log, int n_seq, int levels, hipStream_t s);

@@ -6,6 +6,8 @@
 // calls written in dvo_math.h fuse.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "dvo_kernels.h"
 
 namespace dvo {
@@ -2331,106 +2333,98 @@ void launch_warp_image(const float* gray, const float* depth, int w, int h, cons
 
 int gn_blocks_per_seq(int w, int h, int ppt, int crop) { return gn_tiling(w, h, ppt, crop).count; }
 
-template <int PPT, int G>
-static void launch_track_gn_t(const GnArgs& a, unsigned tiles, hipStream_t s)
+// A runtime flag as a compile-time constant: f receives std::true_type or std::false_type, so a launcher names its kernel template
+// once and the flag's two instances follow from it
+template <class F>
+static void with_flag(bool on, F&& f)
 {
-    const unsigned g = (tiles + 7u) & ~7u;  // a multiple of 8: blockIdx % 8 is the XCD
-    if (a.seq_k) {   // per-sequence intrinsics: the same choice among the k_track_gn_cam instantiations
-        if constexpr (PPT == 4) {
-            if (gn_tiling(a.w, a.h, PPT, a.prm.crop).t2d) {
-                if (a.mask) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, true, true>), dim3(g), dim3(256), 0, s, a);
-                else hipLaunchKernelGGL((k_track_gn_cam<PPT, G, false, true>), dim3(g), dim3(256), 0, s, a);
-                return;
-            }
-        }
-        if (a.mask) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, true>), dim3(g), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_track_gn_cam<PPT, G, false>), dim3(g), dim3(256), 0, s, a);
-        return;
-    }
-    if constexpr (PPT == 4) {
-        if (gn_tiling(a.w, a.h, PPT, a.prm.crop).t2d) {  // 2-D tiles
-            if (a.mask) hipLaunchKernelGGL((k_track_gn<PPT, G, true, true>), dim3(g), dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_track_gn<PPT, G, false, true>), dim3(g), dim3(256), 0, s, a);
-            return;
-        }
-    }
-    if (a.mask) hipLaunchKernelGGL((k_track_gn<PPT, G, true>), dim3(g), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_track_gn<PPT, G, false>), dim3(g), dim3(256), 0, s, a);
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
 }
 
-void launch_track_gn(const GnArgs& a0, int n_seq, int ppt, int group, hipStream_t s, int grid_seqs)
+template <int PPT, int G>
+static void launch_track_gn_t(const GnArgs& a, bool t2d, unsigned tiles, hipStream_t s)
+{
+    const dim3 grid((tiles + 7u) & ~7u);  // a multiple of 8: blockIdx % 8 is the XCD
+    with_flag(a.mask != nullptr, [&](auto mask) {
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {   // (2-D tiles exist for 4 pixels per thread only)
+            constexpr bool MASK = decltype(mask)::value, T2D = PPT == 4 && decltype(tiles_2d)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+            else hipLaunchKernelGGL((k_track_gn<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);
+        });
+    });
+}
+
+void launch_track_gn(const GnArgs& a0, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
 {
     GnArgs a = a0;
     a.n_seq = n_seq;
-    const GnTiling tl = gn_tiling(a.w, a.h, ppt, a.prm.crop);
-    a.blk_first = tl.live_first; a.blk_count = tl.live_count;
-    a.t_shift = tl.shift; a.x_org = tl.x_org; a.y_org = tl.y_org;
-    if (tl.t2d) a.tiles_x = tl.tiles_x;
     // grid_seqs: an upper bound of the sequences on the active list (the host knows one from the progress words): the grid then only
     // holds workgroups that can find a tile -- at 16 384 sequences x 75 tiles an all-empty grid alone costs ~0.35 ms to dispatch
     const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
     unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
     if (grid == 0) grid = 8;  // (nothing live: the workgroups only clear the next list counter)
     switch (ppt * 10 + group) {
-        case 11: launch_track_gn_t<1, 1>(a, grid, s); break;
-        case 21: launch_track_gn_t<2, 1>(a, grid, s); break;
-        case 22: launch_track_gn_t<2, 2>(a, grid, s); break;
-        case 41: launch_track_gn_t<4, 1>(a, grid, s); break;
-        case 42: launch_track_gn_t<4, 2>(a, grid, s); break;
-        case 44: launch_track_gn_t<4, 4>(a, grid, s); break;
-        case 81: launch_track_gn_t<8, 1>(a, grid, s); break;
-        case 82: launch_track_gn_t<8, 2>(a, grid, s); break;
-        default: launch_track_gn_t<8, 4>(a, grid, s); break;
+        case 11: launch_track_gn_t<1, 1>(a, t2d, grid, s); break;
+        case 21: launch_track_gn_t<2, 1>(a, t2d, grid, s); break;
+        case 22: launch_track_gn_t<2, 2>(a, t2d, grid, s); break;
+        case 41: launch_track_gn_t<4, 1>(a, t2d, grid, s); break;
+        case 42: launch_track_gn_t<4, 2>(a, t2d, grid, s); break;
+        case 44: launch_track_gn_t<4, 4>(a, t2d, grid, s); break;
+        case 81: launch_track_gn_t<8, 1>(a, t2d, grid, s); break;
+        case 82: launch_track_gn_t<8, 2>(a, t2d, grid, s); break;
+        default: launch_track_gn_t<8, 4>(a, t2d, grid, s); break;
     }
 }
 
+// The (ppt, group) pairs the tiling picks for a handle of a few sequences: the ones k_track_gn_fused and k_track_persist have an
+// instance for.  f receives the pair as two std::integral_constant; false (f not called) for any other pair.
+template <class F>
+static bool with_small_handle_pair(int ppt, int group, F&& f)
+{
+    switch (ppt * 10 + group) {
+        case 11: f(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}); return true;
+        case 22: f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}); return true;
+        case 42: f(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{}); return true;
+        default: return false;
+    }
+}
+
+bool gn_fused_available(int ppt, int group) { return with_small_handle_pair(ppt, group, [](auto, auto) {}); }
+bool track_persist_available(int ppt, int group) { return gn_fused_available(ppt, group); }
+
 // k_track_gn_fused for the (ppt, group) pairs the small-batch tiling picks; returns false when there is no such instance
-bool launch_track_gn_fused(const GnArgs& a0, const SolveArgs& sa0, int n_seq, int ppt, int group, int* ticket, int* report, int* progress,
-                           hipStream_t s)
+bool launch_track_gn_fused(const GnArgs& a0, const SolveArgs& sa0, int n_seq, int ppt, int group, bool t2d, int* ticket, int* report,
+                           int* progress, hipStream_t s)
 {
     GnArgs a = a0;
     SolveArgs sa = sa0;
     a.n_seq = n_seq; a.list = nullptr; a.next_count = nullptr; a.mask = nullptr;
-    const GnTiling tl = gn_tiling(a.w, a.h, ppt, a.prm.crop);
-    a.blk_first = tl.live_first; a.blk_count = tl.live_count;
-    a.t_shift = tl.shift; a.x_org = tl.x_org; a.y_org = tl.y_org;
-    if (tl.t2d) a.tiles_x = tl.tiles_x;
     sa.n_seq = n_seq; sa.list_in = nullptr; sa.list_out = nullptr; sa.progress = nullptr;
-    sa.blk_first = tl.live_first; sa.blk_count = tl.live_count;
     if (a.blk_count <= 0) return false;
     FusedArgs f{ticket, report, progress, n_seq};
     const dim3 grid((unsigned)a.blk_count * (unsigned)n_seq);
-    const int key = ppt * 10 + group;
-    if (a.seq_k) {   // per-sequence intrinsics
-        if (key == 11) hipLaunchKernelGGL((k_track_gn_fused<1, 1, false, true>), grid, dim3(256), 0, s, a, sa, f);
-        else if (key == 22) hipLaunchKernelGGL((k_track_gn_fused<2, 2, false, true>), grid, dim3(256), 0, s, a, sa, f);
-        else if (key == 42 && tl.t2d) hipLaunchKernelGGL((k_track_gn_fused<4, 2, true, true>), grid, dim3(256), 0, s, a, sa, f);
-        else if (key == 42) hipLaunchKernelGGL((k_track_gn_fused<4, 2, false, true>), grid, dim3(256), 0, s, a, sa, f);
-        else return false;
-        return true;
-    }
-    if (key == 11) hipLaunchKernelGGL((k_track_gn_fused<1, 1, false, false>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 22) hipLaunchKernelGGL((k_track_gn_fused<2, 2, false, false>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 42 && tl.t2d) hipLaunchKernelGGL((k_track_gn_fused<4, 2, true, false>), grid, dim3(256), 0, s, a, sa, f);
-    else if (key == 42) hipLaunchKernelGGL((k_track_gn_fused<4, 2, false, false>), grid, dim3(256), 0, s, a, sa, f);
-    else return false;
-    return true;
+    return with_small_handle_pair(ppt, group, [&](auto p, auto g) {
+        with_flag(a.seq_k != nullptr, [&](auto cam) {   // per-sequence intrinsics
+            with_flag(p.value == 4 && t2d, [&](auto tiles_2d) {
+                constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+                constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value, PCAM = decltype(cam)::value;
+                hipLaunchKernelGGL((k_track_gn_fused<PPT, G, T2D, PCAM>), grid, dim3(256), 0, s, a, sa, f);
+            });
+        });
+    });
 }
 
-bool track_persist_available(int ppt, int group)
-{
-    const int key = ppt * 10 + group;
-    return key == 11 || key == 22 || key == 42;
-}
-
+// (k_track_persist's gather group only sets how many pixels' gathers are in flight together, never a result: the kernel runs one wave
+//  per SIMD whatever it does, so it takes all of a thread's pixels at once -- the instance of a pair is <ppt, ppt>)
 int track_persist_max_grid(int ppt, int group, int* out)
 {
     int per_cu = 0, dev = 0;
-    const int key = ppt * 10 + group;
     hipError_t e = hipErrorInvalidValue;
-    if (key == 11) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_persist<1, 1, true>, 256, 0);   // (the instance with more registers)
-    else if (key == 22) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_persist<2, 2, true>, 256, 0);
-    else if (key == 42) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_persist<4, 4, true>, 256, 0);
+    with_small_handle_pair(ppt, group, [&](auto p, auto) {
+        constexpr int PPT = decltype(p)::value;
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_track_persist<PPT, PPT, true>, 256, 0);   // (the instance with more registers)
+    });
     if (e != hipSuccess) return DVO_ERR_HIP;
     hipDeviceProp_t prop;
     if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return DVO_ERR_HIP;
@@ -2440,48 +2434,36 @@ int track_persist_max_grid(int ppt, int group, int* out)
 
 bool launch_track_persist(const PersistArgs& p, int ppt, int group, int grid, hipStream_t s)
 {
-    const int key = ppt * 10 + group;
     if (grid < 1) return false;
-    // (the gather group only sets how many pixels' gathers are in flight together, never a result: this kernel runs one wave per SIMD
-    //  whatever it does, so it takes all of a thread's pixels at once)
-    if (p.mono.enabled) {
-        if (key == 11) hipLaunchKernelGGL((k_track_persist<1, 1, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (key == 22) hipLaunchKernelGGL((k_track_persist<2, 2, true>), dim3(grid), dim3(256), 0, s, p);
-        else if (key == 42) hipLaunchKernelGGL((k_track_persist<4, 4, true>), dim3(grid), dim3(256), 0, s, p);
-        else return false;
-        return true;
-    }
-    if (key == 11) hipLaunchKernelGGL((k_track_persist<1, 1, false>), dim3(grid), dim3(256), 0, s, p);
-    else if (key == 22) hipLaunchKernelGGL((k_track_persist<2, 2, false>), dim3(grid), dim3(256), 0, s, p);
-    else if (key == 42) hipLaunchKernelGGL((k_track_persist<4, 4, false>), dim3(grid), dim3(256), 0, s, p);
-    else return false;
-    return true;
+    return with_small_handle_pair(ppt, group, [&](auto pp, auto) {
+        with_flag(p.mono.enabled != 0, [&](auto mono) {
+            constexpr int PPT = decltype(pp)::value;
+            hipLaunchKernelGGL((k_track_persist<PPT, PPT, decltype(mono)::value>), dim3(grid), dim3(256), 0, s, p);
+        });
+    });
 }
 
 void launch_track_level(const GnArgs& ga0, const SolveArgs& sa0, int n_seq, hipStream_t s)
 {
-    GnArgs ga = ga0;
+    GnArgs ga = ga0;   // (raster tiles of 4 pixels per thread: Tracker::init fuses no other level)
     SolveArgs sa = sa0;
     ga.n_seq = n_seq;
     ga.list = nullptr; ga.next_count = nullptr; ga.mask = nullptr;
-    const GnTiling tl = gn_tiling(ga.w, ga.h, 4, ga.prm.crop);  // (the caller made sure these are raster tiles: !tl.t2d)
-    ga.blk_first = tl.live_first; ga.blk_count = tl.live_count;
     sa.list_in = nullptr; sa.list_out = nullptr;
-    if (ga.seq_k) hipLaunchKernelGGL((k_track_level<4, 2, true>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
-    else hipLaunchKernelGGL((k_track_level<4, 2, false>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
+    with_flag(ga.seq_k != nullptr, [&](auto cam) {
+        hipLaunchKernelGGL((k_track_level<4, 2, decltype(cam)::value>), dim3((unsigned)n_seq), dim3(256), 0, s, ga, sa);
+    });
 }
 
 template <int PPT>
 static void launch_track_gn_tile_t(const GnArgs& a, const dim3& grid, hipStream_t s)
 {
     const size_t lds = (128 + (size_t)(4 * PPT + 2 * a.margin + 3) * (64 + 2 * a.margin + 3)) * sizeof(float);
-    if (a.seq_k) {   // per-sequence intrinsics
-        if (a.mask) hipLaunchKernelGGL((k_track_gn_tile<PPT, true, true>), grid, dim3(256), lds, s, a);
-        else hipLaunchKernelGGL((k_track_gn_tile<PPT, false, true>), grid, dim3(256), lds, s, a);
-        return;
-    }
-    if (a.mask) hipLaunchKernelGGL((k_track_gn_tile<PPT, true, false>), grid, dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((k_track_gn_tile<PPT, false, false>), grid, dim3(256), lds, s, a);
+    with_flag(a.mask != nullptr, [&](auto mask) {
+        with_flag(a.seq_k != nullptr, [&](auto cam) {   // per-sequence intrinsics
+            hipLaunchKernelGGL((k_track_gn_tile<PPT, decltype(mask)::value, decltype(cam)::value>), grid, dim3(256), lds, s, a);
+        });
+    });
 }
 
 void launch_track_gn_tile(const GnArgs& a, int n_seq, int ppt, hipStream_t s)
