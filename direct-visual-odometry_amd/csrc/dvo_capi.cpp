@@ -894,6 +894,22 @@ int dvo_op_se3_concatenate(int dev, const float a[6], const float b[6], float ou
     return (a && b && out) ? se3_op(dev, 2, a, 6, b, out, 6) : DVO_ERR_BAD_ARGUMENT;
 }
 
+int dvo_op_pose_algebra(int dev, int op, int n, const double* in, double* out)
+{
+    int ni, no;
+    if (!in || !out || n < 1 || !pose_algebra_row(op, ni, no)) return DVO_ERR_BAD_ARGUMENT;
+    OpCtx c; DVO_TRY(c.open(dev));
+    DevBuf din, dout;
+    const size_t bi = (size_t)n * ni * sizeof(double), bo = (size_t)n * no * sizeof(double);
+    DVO_TRY(din.alloc(bi));
+    DVO_TRY(dout.alloc(bo));
+    DVO_HIP(hipMemcpyAsync(din.p, in, bi, hipMemcpyHostToDevice, c.s));
+    launch_pose_algebra(op, n, din.as<double>(), dout.as<double>(), c.s);
+    DVO_HIP(hipMemcpyAsync(out, dout.p, bo, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipStreamSynchronize(c.s));
+    return DVO_OK;
+}
+
 int dvo_selftest_reciprocal(int dev, uint64_t* fast_path_inputs, uint64_t* mismatches, uint32_t* first_bad_bits)
 {
     if (!mismatches) return DVO_ERR_BAD_ARGUMENT;

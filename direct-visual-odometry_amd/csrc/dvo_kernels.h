@@ -550,6 +550,22 @@ void launch_track_begin(SeqState* state, dvo_track_log* log, int n_seq, int leve
 void launch_set_pose(SeqState* state, const float* xi_dev, int n_seq, hipStream_t s);
 void launch_export_poses(const SeqState* state, float* xi_out, float* T_out, int n_seq, hipStream_t s, float* host_result = nullptr, int host_tag = 0);
 void launch_se3(int op, const float* a, const float* b, float* out, hipStream_t s);
+// k_pose_algebra: doubles per case that op reads and writes (include/dvo.h, dvo_op_pose_algebra); false for an unknown op
+#define DVO_POSE_ALGEBRA_OPS 6
+DVO_HD bool pose_algebra_row(int op, int& n_in, int& n_out)
+{
+    switch (op) {
+    case 0: n_in = 6; n_out = 12; return true;
+    case 1: n_in = 12; n_out = 6; return true;
+    case 2: n_in = 12; n_out = 6; return true;
+    case 3: n_in = 12; n_out = 31; return true;
+    case 4: n_in = 27; n_out = 7; return true;
+    case 5: n_in = 21; n_out = 42; return true;
+    }
+    n_in = 0; n_out = 0;
+    return false;
+}
+void launch_pose_algebra(int op, int n, const double* in, double* out, hipStream_t s);
 void launch_propagate(const float* ref_depth, const float* ref_sigma, const float* ref_age, int w, int h, const Intr& k,
                       const Pose& pose, float tz, int* owner, float* depth, float* sigma, float* age, hipStream_t s);
 void launch_regularize(const float* depth, const float* sigma, int w, int h, float* out, hipStream_t s);

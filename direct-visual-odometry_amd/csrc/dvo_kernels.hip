@@ -2023,6 +2023,67 @@ __global__ void k_se3(int op, const float* in_a, const float* in_b, float* out)
     }
 }
 
+// k_pose_algebra: the pieces of the serial double chain that ends every Gauss-Newton iteration (solve6, se3_update_pose) and of the
+// mapping side's pose bookkeeping (se3_concatenate_f, pose_from_xi), one case per thread, doubles in and out so that nothing is
+// rounded on the way (parity op, like k_se3: tests/test_gpu_pose_algebra.py holds it to a multi-precision reference).  Rows per case
+// (pose_algebra_row): op 0 se3_exp_d  xi[6] -> R[9] t[3];  1 se3_log_d  R[9] t[3] -> xi[6];  2 se3_concatenate_f  a[6] b[6] -> out[6];
+// 3 se3_update_pose on the state seed_state sets up for xi  xi[6] upd[6] -> ok, xi'[6], Tc'[12], pose R[9] t[3];
+// 4 solve6  H[21] g[6] -> x[6], solve6_takes_pinv;  5 jacobi_eig6  H[21] -> diag[6], V[36].
+__global__ void __launch_bounds__(64) k_pose_algebra(int op, int n, const double* __restrict__ in, double* __restrict__ out)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    int ni, no;
+    pose_algebra_row(op, ni, no);
+    const double* p = in + (size_t)i * ni;
+    double* o = out + (size_t)i * no;
+    if (op == 0) {
+        double xi[6], R[9], t[3];
+        for (int k = 0; k < 6; k++) xi[k] = p[k];
+        se3_exp_d(xi, R, t);
+        for (int k = 0; k < 9; k++) o[k] = R[k];
+        for (int k = 0; k < 3; k++) o[9 + k] = t[k];
+    } else if (op == 1) {
+        double R[9], t[3], xi[6];
+        for (int k = 0; k < 9; k++) R[k] = p[k];
+        for (int k = 0; k < 3; k++) t[k] = p[9 + k];
+        se3_log_d(R, t, xi);
+        for (int k = 0; k < 6; k++) o[k] = xi[k];
+    } else if (op == 2) {
+        float a[6], b[6], c[6];
+        for (int k = 0; k < 6; k++) { a[k] = (float)p[k]; b[k] = (float)p[6 + k]; }
+        se3_concatenate_f(a, b, c);
+        for (int k = 0; k < 6; k++) o[k] = c[k];
+    } else if (op == 3) {
+        float xi[6], upd[6];
+        double xd[6], Tc[12];
+        Pose pose;
+        for (int k = 0; k < 6; k++) { xi[k] = (float)p[k]; upd[k] = (float)p[6 + k]; xd[k] = xi[k]; }
+        pose_from_xi(xi, -1.0f, pose);   // (seed_state, dvo_kernels.h)
+        se3_exp_d(xd, Tc, Tc + 9);
+        o[0] = se3_update_pose(Tc, upd, xi, pose) ? 1.0 : 0.0;
+        for (int k = 0; k < 6; k++) o[1 + k] = xi[k];
+        for (int k = 0; k < 12; k++) o[7 + k] = Tc[k];
+        for (int k = 0; k < 9; k++) o[19 + k] = pose.R[k];
+        for (int k = 0; k < 3; k++) o[28 + k] = pose.t[k];
+    } else if (op == 4) {
+        double H[21], g[6];
+        float x[6];
+        for (int k = 0; k < 21; k++) H[k] = p[k];
+        for (int k = 0; k < 6; k++) g[k] = p[21 + k];
+        solve6(H, g, x);
+        for (int k = 0; k < 6; k++) o[k] = x[k];
+        o[6] = solve6_takes_pinv(H) ? 1.0 : 0.0;
+    } else {
+        double A[36], V[36];
+        for (int r = 0, k = 0; r < 6; r++)
+            for (int c = r; c < 6; c++, k++) { A[6 * r + c] = p[k]; A[6 * c + r] = p[k]; }
+        jacobi_eig6(A, V);
+        for (int k = 0; k < 6; k++) o[k] = A[7 * k];
+        for (int k = 0; k < 36; k++) o[6 + k] = V[k];
+    }
+}
+
 // (the mapping kernels -- propagate, regularize, depth update, keyframe promotion -- live in dvo_map_kernels.hip)
 
 // ------------------------------------------------------------------------------------------------
@@ -2524,6 +2585,10 @@ void launch_export_poses(const SeqState* state, float* xi_out, float* T_out, int
 void launch_se3(int op, const float* a, const float* b, float* out, hipStream_t s)
 {
     hipLaunchKernelGGL(k_se3, dim3(1), dim3(64), 0, s, op, a, b, out);
+}
+void launch_pose_algebra(int op, int n, const double* in, double* out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_pose_algebra, dim3((n + 63) / 64), dim3(64), 0, s, op, n, in, out);
 }
 
 }  // namespace dvo

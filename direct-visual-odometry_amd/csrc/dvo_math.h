@@ -407,8 +407,8 @@ DVO_HD void se3_log_d(const double R[9], const double t[3], double xi[6])
     const double th = atan2(s, cth);
 #endif
     double w[3] = {0, 0, 0};
-    if ((float)th > 1e-6f && s > 0.0) {
-        const double k = th / s;
+    if (!((float)th <= 1e-6f) && !(s <= 0.0)) {   // theta > 1e-6f and s > 0, written so that a NaN rotation gives a NaN omega (testXi then
+        const double k = th / s;                  //  refuses it) and not omega = 0
         w[0] = a[0] * k; w[1] = a[1] * k; w[2] = a[2] * k;
     }
     const double wl2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
@@ -557,7 +557,7 @@ DVO_HD void jacobi_eig6(double A[36], double V[36])
             diag += A[7 * i] * A[7 * i];
             for (int j = i + 1; j < 6; j++) off += A[6 * i + j] * A[6 * i + j];
         }
-        if (off <= 1e-60 || off <= 1e-32 * diag) break;
+        if (!(off > 1e-32 * diag)) break;   // relative only: an absolute floor stopped matrices of norm below 1e-14 early (and NaN ends here)
         for (int p = 0; p < 5; p++)
             for (int q = p + 1; q < 6; q++) {
                 const double apq = A[6 * p + q];
@@ -665,6 +665,12 @@ DVO_HD_NOINLINE void solve6_pinv(const double H[21], const double g[6], float x[
             }
     }
     double V[36], sv[6], sum = 0;
+    double chk = 0.0;      // a NaN or an infinity among the sums: x = NaN, as on the LDL^T path (the cut below would drop every NaN eigenvalue
+    for (int i = 0; i < 21; i++) chk += H[i] * 0.0;      //  and answer 0, which the tracker takes for convergence)
+    if (chk != chk) {
+        for (int i = 0; i < 6; i++) x[i] = __builtin_nanf("");
+        return;
+    }
     jacobi_eig6(A, V);
     for (int i = 0; i < 6; i++) {
         sv[i] = sqrt(A[7 * i] > 0.0 ? A[7 * i] : 0.0);

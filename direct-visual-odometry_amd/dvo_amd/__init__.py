@@ -106,7 +106,7 @@ EXPORTS = [
     "dvo_batch_world_poses", "dvo_batch_copy_world_poses_device", "dvo_batch_keyframe_get", "dvo_batch_mono_stats", "dvo_batch_profile_mapping",
     "dvo_op_cull_image", "dvo_op_gradient", "dvo_op_warp_image", "dvo_op_pyramid", "dvo_op_gn_step", "dvo_op_track",
     "dvo_op_propagate", "dvo_op_regularize", "dvo_op_depth_update", "dvo_op_se3_exp", "dvo_op_se3_log",
-    "dvo_op_se3_concatenate",
+    "dvo_op_se3_concatenate", "dvo_op_pose_algebra",
     "dvo_png_info", "dvo_png_read", "dvo_dataset_open_tum", "dvo_dataset_open_list", "dvo_dataset_size", "dvo_dataset_entry",
     "dvo_dataset_close", "dvo_op_ingest", "dvo_vo_odometrize_depth_raw", "dvo_op_undistort",
     "dvo_eval_ate", "dvo_eval_rpe", "dvo_pose_inverse", "dvo_traj_write_tum",
@@ -196,6 +196,20 @@ class se3:
         a = f32(a); b = f32(b); o = np.zeros(6, np.float32)
         _check(lib().dvo_op_se3_concatenate(dev, fp(a), fp(b), fp(o)))
         return o
+
+
+# doubles per case (in, out) of pose_algebra's ops: include/dvo.h
+POSE_ALGEBRA_ROWS = {0: (6, 12), 1: (12, 6), 2: (12, 6), 3: (12, 31), 4: (27, 7), 5: (21, 42)}
+
+
+def pose_algebra(op, rows, dev=0):
+    """dvo_op_pose_algebra: op on every row of rows (n x POSE_ALGEBRA_ROWS[op][0] float64) -> n x POSE_ALGEBRA_ROWS[op][1] float64"""
+    ni, no = POSE_ALGEBRA_ROWS[op]
+    rows = np.ascontiguousarray(rows, dtype=np.float64).reshape(-1, ni)
+    out = np.zeros((rows.shape[0], no), np.float64)
+    DP = C.POINTER(C.c_double)
+    _check(lib().dvo_op_pose_algebra(dev, op, rows.shape[0], rows.ctypes.data_as(DP), out.ctypes.data_as(DP)))
+    return out
 
 
 # ------------------------------------------------------------------ Convert / Transform

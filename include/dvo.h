@@ -551,6 +551,18 @@ int dvo_op_depth_update(int dev, const dvo_config* cfg, int n_hist, const float*
 int dvo_op_se3_exp(int dev, const float xi[6], float T[16]);
 int dvo_op_se3_log(int dev, const float T[16], float xi[6]);
 int dvo_op_se3_concatenate(int dev, const float a[6], const float b[6], float out[6]);
+/* The tracker's serial double-precision chain, piece by piece, ON THE DEVICE for n cases at once (parity op: the tests hold it to a
+ * multi-precision reference).  Every value travels as a double (exact for the float ones); rows per case:
+ *   op 0  se3 exp in double            in xi[6]                          out R[9] t[3], before any rounding to float
+ *   op 1  se3 log in double            in R[9] t[3]                      out xi[6]
+ *   op 2  concatenate                  in a[6] b[6] (float values)       out xi[6] (float values)
+ *   op 3  one pose update of the       in xi[6] upd[6] (float values)    out ok (1 or 0), xi'[6], exp(xi') as R[9] t[3] in double,
+ *         tracker from the state                                             float(exp(-xi')) as R[9] t[3]; ok = 0 (a non-finite
+ *         of xi                                                              result) leaves all three as they were for xi
+ *   op 4  the 6x6 solve x = H^+ g      in H[21] (upper triangle by rows) g[6]   out x[6] (float values), 1 if the pseudo-inverse ran
+ *   op 5  the Jacobi eigensolver       in H[21]                          out eigenvalues[6] (unsorted), V[36] (columns, row major)
+ * DVO_ERR_BAD_ARGUMENT for a null pointer, n < 1 or another op. */
+int dvo_op_pose_algebra(int dev, int op, int n, const double* in, double* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Dataset front-end: what src/core/loader.cpp + include/core/loader.hpp do with OpenCV.

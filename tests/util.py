@@ -29,6 +29,9 @@ def level_maps(of, level):
 
 
 TOL_BACKWARD = 2e-6     # backward error of an xi_update against the oracle's normal equations (conditioning independent)
+# (It sees solve6 only through image-built systems.  The bound that binds for the solve itself -- chosen matrices at the pivot rule and the
+# pseudo-inverse's cut, condition numbers up to 1e13, scales 1e-20 to 1e12, half a float ulp plus a counted kappa term against a 60-digit
+# reference -- is tests/pose_algebra.py's, DESIGN.md §6, asserted by tests/test_gpu_pose_algebra.py and tests/test_pose_algebra_host.py.)
 
 
 def backward_error(H21, g, x):
@@ -41,7 +44,9 @@ def backward_error(H21, g, x):
 
 def assert_composed(xi_in, upd, xi_after, tag=""):
     """xi_after == log(exp(xi_in) exp(upd)) (tracker.cpp:46) up to the rounding of the result to float: both sides evaluate the
-    composition in double and round once, so the allowance is a few units in the last place of the pose, nothing pose-scaled."""
+    composition in double and round once, so the allowance is a few units in the last place of the pose, nothing pose-scaled.
+    (4 ulp of max(1, |xi|) is up to half a percent of a 1e-4 component: the bound that binds for the composition is half a float ulp of
+    each component against a 60-digit reference, tests/pose_algebra.py)"""
     import orc
     nxt = orc.se3_concatenate(xi_in, upd)
     if not np.all(np.isfinite(nxt)):
