@@ -330,6 +330,23 @@ int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log)
     return DVO_OK;
 }
 
+int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* depth)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    DVO_NOT_MONO(b);
+    Batch& B = b->impl;
+    if (seq < 0 || seq >= B.n_seq || level < 0 || level >= B.g.levels) return DVO_ERR_BAD_ARGUMENT;
+    if (B.kf_on) { set_error("dvo_batch_frame_get: keyframe tracking is on (dvo_batch_keyframe_get reads the keyframes)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (B.cur < 0) return DVO_ERR_NOT_READY;
+    DVO_TRY(select_device(B.device));
+    // (in stream order after the push, which has queued the wait for a split build's side stream)
+    const size_t n = (size_t)B.g.w[level] * B.g.h[level], off = n * (size_t)seq;
+    if (gray) DVO_HIP(hipMemcpyAsync(gray, B.fs[B.cur].gray[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    if (depth) DVO_HIP(hipMemcpyAsync(depth, B.fs[B.cur].depth[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    return DVO_OK;
+}
+
 int dvo_batch_synchronize(dvo_batch* b)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;

@@ -273,7 +273,8 @@ void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, 
     launch_pyramid(a, fs.n_seq, s);
 }
 
-void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from)
+bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from,
+                   PyramidSplit* split)
 {
     if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
                                          // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
@@ -285,17 +286,17 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         a.seq_action = seq_action;
         fs.sigma_by_validity = false;
         launch_pyramid(a, fs.n_seq, s);
-        return;
+        return false;
     }
     // sensor-depth frames with lens undistortion (dvo_batch_set_sensor_distortion): the arguments of the plain build plus the remap,
     // whole frames -- launch_pyramid picks k_pyramid_remap_depth
     if (!in.raw()) {
-        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return; }
+        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return false; }
         PyramidArgs a = float_args(fs, in.gray, in.depth, in.sigma, keep_sigma, false);
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         plan_copy(a, seq_action, copy_from);
         launch_pyramid(a, fs.n_seq, s);
-        return;
+        return false;
     }
     PyramidArgs a = frame_args(fs, in.rows_decimated);
     a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_depth = in.depth16;
@@ -315,7 +316,18 @@ void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     }
     a.remap = in.remap; a.remap_cam = in.remap_cam;   // (set only with depth here, and then on whole frames)
     plan_copy(a, seq_action, copy_from);
+    if (split && pyramid_can_split(a)) {
+        // stage A where the single kernel would run; stage B on the side stream, after everything queued on `s` so far (every earlier
+        // launch that may still read the set it overwrites)
+        launch_pyramid_coarse(a, fs.n_seq, s);
+        split->err = hipEventRecord(split->fork, s);
+        if (split->err == hipSuccess) split->err = hipStreamWaitEvent(split->side, split->fork, 0);
+        launch_pyramid_rest(a, fs.n_seq, split->err == hipSuccess ? split->side : s);
+        if (split->err == hipSuccess) split->err = hipEventRecord(split->done, split->side);
+        return split->err == hipSuccess;
+    }
     launch_pyramid(a, fs.n_seq, s);
+    return false;
 }
 
 int upload_rows(void* dst, const void* src, size_t row_bytes, int img_rows, size_t n_img, int culls, bool decimate, hipStream_t s,
@@ -655,7 +667,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     persist_used = false;
     // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
     const Intr* seq_k = plan ? plan->seq_k : cam_k;
+    bool top_waited = top_ready == nullptr;
     if (persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed) {   // the whole call in one launch (k_track_persist)
+        if (!top_waited) { DVO_HIP(hipStreamWaitEvent(s, top_ready, 0)); top_waited = true; }
         bool launched = false;
         DVO_TRY(track_persist(obj, ref, s, &launched));
         if (launched) return DVO_OK;
@@ -718,6 +732,10 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 if (*pw - 1 == 0) break;
                 if (!L.single_launch) active_ub = *pw - 1;
             }
+            if (!top_waited && level == g.levels - 1) {   // obj's top level: the split build's side stream writes it (every launch form reads it)
+                for (int k = 0; k < subs; k++) DVO_HIP(hipStreamWaitEvent(k == 0 ? s : sub_streams[k - 1], top_ready, 0));
+                top_waited = true;
+            }
             const GnArgs ga0 = gn_args(obj, ref, level, nullptr, first);
             for (int k = 0; k < subs; k++) {  // launches of the sub-batches interleave on their streams
                 const int q0 = subs > 1 ? sub_first(k) : 0, q1 = subs > 1 ? sub_first(k + 1) : n_seq, nq = q1 - q0;
@@ -776,6 +794,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         DVO_HIP(hipEventRecord(ev_join[k - 1], sub_streams[k - 1]));
         DVO_HIP(hipStreamWaitEvent(s, ev_join[k - 1], 0));
     }
+    if (!top_waited) DVO_HIP(hipStreamWaitEvent(s, top_ready, 0));   // (no level was launched: the caller's stream still orders obj's maps)
     if (h_result) next_result_tag();
     launch_export_poses(state.as<SeqState>(), xi_out.as<float>(), T_out.as<float>(), n_seq, s, d_result, result_tag);
     DVO_HIP(hipGetLastError());
@@ -1359,6 +1378,8 @@ Batch::~Batch()
     host.release();
     if (ev_last_track) (void)hipEventDestroy(ev_last_track);
     for (int i = 0; i < 3; i++) if (ev_built[i]) (void)hipEventDestroy(ev_built[i]);
+    if (split.fork) (void)hipEventDestroy(split.fork);
+    if (split.done) (void)hipEventDestroy(split.done);
     plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
     cam_stage.release(stream);
     guess.release(stream);
@@ -1387,6 +1408,13 @@ int Batch::init(int n, const float K9[9], int w, int h, int levels, int culls, c
     }
     DVO_HIP(hipEventCreateWithFlags(&ev_last_track, hipEventDisableTiming));
     for (int i = 0; i < 3; i++) DVO_HIP(hipEventCreateWithFlags(&ev_built[i], hipEventDisableTiming));
+    {
+        const char* e = getenv("DVO_PYRAMID_SPLIT");
+        split_on = (e && e[0]) ? e[0] != '0' : n >= 1024;
+        split.side = pstream;
+        DVO_HIP(hipEventCreateWithFlags(&split.fork, hipEventDisableTiming));
+        DVO_HIP(hipEventCreateWithFlags(&split.done, hipEventDisableTiming));
+    }
     return DVO_OK;
 }
 
@@ -1530,16 +1558,21 @@ int Batch::push(const FrameInput& in)
     }
     PoseSeedArgs sa{};
     if (!planned) {
-        if (!built) build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false);  // Frame(gray,depth,sigma,K,levels,culls)
+        // Frame(gray,depth,sigma,K,levels,culls); a big batch's raw frames: split, the top level and the depth maps on the side stream
+        const bool halves = !built && build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, nullptr, nullptr, split_on ? &split : nullptr);
+        DVO_HIP(split.err);
         if (cur >= 0) {
             if (guess.on()) { sa = guess.args(trk.state.as<SeqState>(), nullptr, DVO_SEQ_TRACK, trk.xi_out.as<float>(), nullptr); trk.seed = &sa; }
+            trk.top_ready = halves ? split.done : nullptr;
             const int rc = trk.track(fs[target], fs[cur], stream);    // system.hpp:88
-            trk.seed = nullptr;
+            trk.seed = nullptr; trk.top_ready = nullptr;
+            if (rc != DVO_OK && halves) (void)hipStreamWaitEvent(stream, split.done, 0);   // (a failed call may not have queued the wait)
             DVO_TRY(rc);
             DVO_HIP(hipEventRecord(ev_last_track, stream));
             tracked_once = true;
             have_poses = true;
         } else {
+            if (halves) DVO_HIP(hipStreamWaitEvent(stream, split.done, 0));   // (nothing tracks: the set is complete when the push is)
             seed_untracked(nullptr, DVO_SEQ_RESTART);
         }
     } else {

@@ -137,8 +137,18 @@ struct FrameInput {
     const void* key1() const { return raw() ? (const void*)depth16 : (const void*)depth; }
     bool has_depth() const { return raw() ? depth16 != nullptr : (depth != nullptr && sigma != nullptr); }
 };
-void build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma = true, const uint8_t* seq_action = nullptr,
-                   const FrameSet* copy_from = nullptr);
+// The split build of a big batch's plain raw frames: the gray maps below the top level are built on `s`, where the
+// tracker needs them first; the top-level gray and every depth level on `side`, which waits for `fork` (recorded on `s`, so every
+// earlier launch that may still read the set is done) and records `done`.  Whoever reads what the side stream writes waits for `done`.
+struct PyramidSplit {
+    hipStream_t side = nullptr;
+    hipEvent_t fork = nullptr, done = nullptr;
+    hipError_t err = hipSuccess;   // of the event calls
+};
+// Returns true when the build was split (only with `split`, and only where pyramid_can_split allows it: a plan, a remap, float maps
+// or an unusual alignment take the single kernel on `s`).
+bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma = true, const uint8_t* seq_action = nullptr,
+                   const FrameSet* copy_from = nullptr, PyramidSplit* split = nullptr);
 // the sigma_by_validity a build of `in` into `fs` with keep_sigma = false would leave (the weight storage of the frame set)
 inline bool weights_by_validity(const FrameSet& fs, const FrameInput& in) { return in.raw() && in.depth16 != nullptr && fs.allow_const_weight; }
 // Host -> device copy of n_img images (raw or float; rows of row_bytes bytes).  With culls > 0 and decimate set only every
@@ -272,6 +282,10 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // k_track_begin (or the caller's k_plan) and before the sub-batch fork; nullptr: every sequence starts from zero.  Never with persist.
     const PoseSeedArgs* seed = nullptr;
     bool seed_mono = false;
+    // the split pyramid build of the next track()'s obj (PyramidSplit::done): its top level and its depth maps are still being written
+    // on another stream.  track() waits for it on every stream that launches the top level, before the first such launch, and on `s`
+    // before it returns whatever the schedule did; nullptr: obj is complete in stream order.
+    hipEvent_t top_ready = nullptr;
     // a batch's quality records (dvo_batch_set_track_quality): while set, every solve of the finest level stores its sums here
     // (SolveArgs::result, [n_seq]), so each sequence's last one remains; nullptr: no record (the plain path's kernel arguments)
     dvo_gn_result* quality = nullptr;
@@ -470,6 +484,13 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     hipEvent_t ev_last_track = nullptr, ev_built[3] = {nullptr, nullptr, nullptr};
     bool tracked_once = false;
     bool have_poses = false;
+    // The split pyramid build of a plain push of raw frames: stage B runs on pstream beside the coarse-level launches.
+    // Every push queues the wait for split.done on `stream` before it returns (Tracker::track before the first top-level launch, or
+    // push itself when nothing tracks), so whatever follows on the stream -- copies, exports, the next push, destruction -- is ordered
+    // after stage B.  DVO_PYRAMID_SPLIT: 0 = never, 1 = always, unset = batches of at least 1 024 sequences (below, a level is a
+    // latency chain and a second launch only adds to it).
+    PyramidSplit split;
+    bool split_on = false;
     HostStage host;         // host input (push_host / push_raw_host): up to three maps per frame
     int push_host_frame(const void* p0, const void* p1, const void* p2, FrameInput in);
     ~Batch();

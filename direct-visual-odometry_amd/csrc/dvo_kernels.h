@@ -447,6 +447,13 @@ struct MonoStartArgs {
 void launch_regularize_redecimate_plan(const RegDecArgs& a, const MonoStartArgs& p, hipStream_t s);
 
 void launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
+// The split build: launch_pyramid_coarse (k_pyramid_raw4_coarse: the gray maps below the top level) and
+// launch_pyramid_rest (k_pyramid_raw4_rest: everything else) together write what launch_pyramid writes.  pyramid_can_split: the
+// arguments are those of a plain raw build (1-channel u8 gray + u16 depth, culls 1 or 2, no plan, no remap) with the alignment the
+// two kernels' 16-byte accesses need.
+bool pyramid_can_split(const PyramidArgs& a);
+void launch_pyramid_coarse(const PyramidArgs& a, int n_seq, hipStream_t s);
+void launch_pyramid_rest(const PyramidArgs& a, int n_seq, hipStream_t s);
 
 // k_plan: the per-sequence actions of one Batch push (dvo_batch_set_actions), resolved on the device before the pyramid is built.
 struct PlanArgs {

@@ -428,6 +428,142 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
     }
 }
 
+// The split build of a big batch's plain raw frames (u8 gray + u16 depth, no plan, no remap): k_pyramid_raw4 as two
+// kernels that together write exactly what it writes, from the same conversions and pass_valid calls on the same values.  The
+// tracker's coarse levels read only the new frame's gray below the top, so that part is built first on the tracking stream (stage
+// A, a quarter of the input rows) and everything else on the low-priority side stream beside the coarse-level launches (stage B).
+//
+// k_pyramid_raw4_coarse (stage A): the gray maps of every level below the top.  A thread owns four consecutive pixels of level
+// top - 1 = top-level pixels (2 lx, 2 ly): 8 << CULLS source pixels of one kept row in two, their gray and (for the d == 0
+// invalidation) depth fetched by 16-byte loads, the four values stored as one dwordx4; levels further down take the pixels whose
+// level top - 1 coordinates are multiples of 2^(t - 1).  pyramid_can_split checks the alignment all of this needs.
+template <int CULLS>
+__global__ void __launch_bounds__(256) k_pyramid_raw4_coarse(PyramidArgs a)
+{
+    const int T = a.levels - 1, cw = a.w[T - 1], ch = a.h[T - 1], gw = cw >> 2;
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int gi = (int)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= gw * ch || seq >= a.n_seq) return;
+    int y, xg;
+    split_index(gi, gw, a.inv_tw * 8.0f, xg, y);   // (8 / tw = 1 / gw up to an ulp: split_index corrects +-1)
+    const int x0 = xg << 2;                        // level top - 1 coordinates (x0 .. x0 + 3, y)
+    const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)((2 * y) << a.src_row_shift) * a.src_w + ((size_t)x0 << (CULLS + 1));
+    constexpr int GW = 2 << CULLS;       // 32-bit words of gray bytes this thread reads (4 or 8)
+    unsigned gwords[GW], dwords[2 * GW];
+    {
+        const u32x4* gp = reinterpret_cast<const u32x4*>(a.raw_rgb + src_off);
+        const u32x4* dp = reinterpret_cast<const u32x4*>(a.raw_depth + src_off);
+#pragma unroll
+        for (int q = 0; q < GW / 4; q++) {
+            const u32x4 v = __builtin_nontemporal_load(gp + q);
+            gwords[4 * q] = v.x; gwords[4 * q + 1] = v.y; gwords[4 * q + 2] = v.z; gwords[4 * q + 3] = v.w;
+        }
+#pragma unroll
+        for (int q = 0; q < GW / 2; q++) {
+            const u32x4 v = __builtin_nontemporal_load(dp + q);
+            dwords[4 * q] = v.x; dwords[4 * q + 1] = v.y; dwords[4 * q + 2] = v.z; dwords[4 * q + 3] = v.w;
+        }
+    }
+    f4 g;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int si = k << (CULLS + 1);                                      // source pixel of kept pixel k
+        const unsigned g8 = (gwords[si >> 2] >> ((si & 3) * 8)) & 0xffu;
+        const unsigned d = (dwords[si >> 1] >> ((si & 1) * 16)) & 0xffffu;
+        float raw = (float)g8 * a.raw_gray_scale;
+        if (a.raw_invalidate_gray && d == 0) raw = kInvalid;
+        g[k] = pass_valid(raw);
+    }
+    __builtin_nontemporal_store(g, reinterpret_cast<f4*>(a.dst[0][T - 1] + (size_t)seq * cw * ch + (size_t)y * cw + x0));
+    for (int t = 1; t < T; t++) {   // level top - 1 - t: pixels whose level top - 1 coordinates are multiples of 2^t
+        const int msk = (1 << t) - 1;
+        if (y & msk) break;
+        const int l = T - 1 - t, ly = y >> t;
+        if (ly >= a.h[l]) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = x0 + k;
+            if (x & msk) continue;
+            const int lx = x >> t;
+            if (lx >= a.w[l]) continue;
+            __builtin_nontemporal_store(g[k], a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
+        }
+    }
+}
+
+// k_pyramid_raw4_rest (stage B): k_pyramid_raw4<CULLS, false> with depth, minus the gray stores below the top.  It runs beside
+// k_track_gn, which allocates 80 of a lane's 512 registers six times over: 32 registers are left, and this kernel is held to them
+// (amdgpu_num_vgpr(32); both instances compile to 26 VGPRs, 0 AGPRs and no scratch: -Rpass-analysis=kernel-resource-usage), so a
+// wave of it can become resident without displacing a tracking wave.
+template <int CULLS>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) k_pyramid_raw4_rest(PyramidArgs a)
+{
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1], gw = tw >> 2;
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int gi = (int)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= gw * th || seq >= a.n_seq) return;
+    int y, xg;
+    split_index(gi, gw, a.inv_tw * 4.0f, xg, y);
+    const int x0 = xg << 2;
+    const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + ((size_t)x0 << CULLS);
+    constexpr int GW = 1 << CULLS;
+    unsigned gwords[GW], dwords[2 * GW];
+    {
+        const unsigned* gp = reinterpret_cast<const unsigned*>(a.raw_rgb + src_off);
+        if constexpr (CULLS == 1) { const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(gp)); gwords[0] = v.x; gwords[1] = v.y; }
+        else { const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp)); gwords[0] = v.x; gwords[1] = v.y; gwords[2] = v.z; gwords[3] = v.w; }
+        const u32x4* dp = reinterpret_cast<const u32x4*>(a.raw_depth + src_off);
+#pragma unroll
+        for (int q = 0; q < GW / 2; q++) {
+            const u32x4 v = __builtin_nontemporal_load(dp + q);
+            dwords[4 * q] = v.x; dwords[4 * q + 1] = v.y; dwords[4 * q + 2] = v.z; dwords[4 * q + 3] = v.w;
+        }
+    }
+    const bool prep = a.wgt[0] != nullptr;
+    f4 v[3];   // pass_valid of gray, depth, sigma of the four kept pixels: what every level stores
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int si = k << CULLS;
+        const unsigned g8 = (gwords[si >> 2] >> ((si & 3) * 8)) & 0xffu;
+        const unsigned d = (dwords[si >> 1] >> ((si & 1) * 16)) & 0xffffu;
+        float raw = (float)g8 * a.raw_gray_scale;
+        if (a.raw_invalidate_gray && d == 0) raw = kInvalid;
+        v[0][k] = pass_valid(raw);
+        v[1][k] = pass_valid((float)d * a.raw_depth_scale);
+        v[2][k] = pass_valid(d > 0 ? a.raw_sigma_valid : a.raw_sigma_invalid);
+    }
+    {
+        const int l = a.levels - 1;
+        const size_t o = (size_t)seq * tw * th + (size_t)y * tw + x0;
+        __builtin_nontemporal_store(v[0], reinterpret_cast<f4*>(a.dst[0][l] + o));
+        if (a.dst[1][l]) __builtin_nontemporal_store(v[1], reinterpret_cast<f4*>(a.dst[1][l] + o));
+        if (a.dst[2][l]) __builtin_nontemporal_store(v[2], reinterpret_cast<f4*>(a.dst[2][l] + o));
+        if (prep) {
+            f4 wgv;
+#pragma unroll
+            for (int k = 0; k < 4; k++) wgv[k] = gn_weight(a.step[l], a.sigma_min, a.sigma_max, v[2][k]);
+            __builtin_nontemporal_store(wgv, reinterpret_cast<f4*>(a.wgt[l] + o));
+        }
+    }
+    for (int t = 1; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if (y & msk) break;
+        const int l = a.levels - 1 - t, ly = y >> t;
+        if (ly >= a.h[l]) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = x0 + k;
+            if (x & msk) continue;
+            const int lx = x >> t;
+            if (lx >= a.w[l]) continue;
+            const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
+            if (a.dst[1][l]) __builtin_nontemporal_store(v[1][k], a.dst[1][l] + o);
+            if (a.dst[2][l]) __builtin_nontemporal_store(v[2][k], a.dst[2][l] + o);
+            if (prep) __builtin_nontemporal_store(gn_weight(a.step[l], a.sigma_min, a.sigma_max, v[2][k]), a.wgt[l] + o);
+        }
+    }
+}
+
 // k_pyramid_remap_depth: k_pyramid of SENSOR-DEPTH frames (gray + depth + sigma, float maps or raw u8 gray/RGB(A) + u16 depth)
 // with the lens undistortion fused in (dvo_batch_set_sensor_distortion).  As k_pyramid_remap, kept pixel (x << culls, y << culls)
 // of the undistorted frame is ONE source pixel: the thread reads its index from the sequence's camera table (k_undistort_map, -1 =
@@ -2374,6 +2510,41 @@ void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
     }
     if (plan) hipLaunchKernelGGL(k_pyramid<true>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_pyramid<false>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+}
+
+bool pyramid_can_split(const PyramidArgs& a)
+{
+    const int T = a.levels - 1;
+    if (a.levels < 2 || a.remap != nullptr || a.seq_action != nullptr) return false;
+    if (a.raw_rgb == nullptr || a.raw_depth == nullptr || a.raw_channels != 1 || (a.culls != 1 && a.culls != 2)) return false;
+    const int tw = a.w[T], th = a.h[T];
+    // stage B: k_pyramid_raw4's conditions; stage A: eight top-level pixels per thread, a dwordx4 store into level top - 1
+    if ((tw % 8) != 0 || (a.src_w % (8 << a.culls)) != 0 || ((size_t)tw * th % 4) != 0 || ((size_t)a.w[T - 1] * a.h[T - 1] % 4) != 0) return false;
+    if (a.w[T - 1] * 2 != tw || a.h[T - 1] * 2 > th) return false;
+    const void* ptrs[7] = {a.raw_rgb, a.raw_depth, a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T], a.dst[0][T - 1]};
+    for (const void* p : ptrs)
+        if ((reinterpret_cast<uintptr_t>(p) % 16) != 0) return false;
+    return true;
+}
+
+void launch_pyramid_coarse(const PyramidArgs& a0, int n_seq, hipStream_t s)
+{
+    PyramidArgs a = a0;
+    a.n_seq = n_seq;
+    const int T = a.levels - 1;
+    const dim3 grid = seq_grid(cdiv((a.w[T - 1] >> 2) * a.h[T - 1], 256), (unsigned)n_seq);
+    if (a.culls == 1) hipLaunchKernelGGL(k_pyramid_raw4_coarse<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_pyramid_raw4_coarse<2>, grid, dim3(256), 0, s, a);
+}
+
+void launch_pyramid_rest(const PyramidArgs& a0, int n_seq, hipStream_t s)
+{
+    PyramidArgs a = a0;
+    a.n_seq = n_seq;
+    const int T = a.levels - 1;
+    const dim3 grid = seq_grid(cdiv((a.w[T] >> 2) * a.h[T], 256), (unsigned)n_seq);
+    if (a.culls == 1) hipLaunchKernelGGL(k_pyramid_raw4_rest<1>, grid, dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_pyramid_raw4_rest<2>, grid, dim3(256), 0, s, a);
 }
 
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s)

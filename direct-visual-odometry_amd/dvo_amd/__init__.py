@@ -121,6 +121,7 @@ EXPORTS = [
     "dvo_batch_set_pose_guess_mode", "dvo_batch_set_pose_guess", "dvo_batch_last_start_poses",
     "dvo_batch_set_keyframe_tracking",
     "dvo_batch_set_track_quality", "dvo_batch_last_track_quality", "dvo_batch_copy_track_quality_device",
+    "dvo_batch_frame_get",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -761,6 +762,17 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality):
         xi = np.zeros(6, np.float32); i = C.c_int(); n = C.c_int(); v = C.c_int()
         _check(lib().dvo_batch_keyframe_get(self._p, seq, level, fp(g), fp(d), None, None, fp(xi), C.byref(i), C.byref(n), C.byref(v)))
         return dict(gray=g, depth=d, xi=xi, id=i.value, n_keyframes=n.value)
+
+    def frame(self, seq, level=None):
+        """Gray and depth of `level` (default: the finest) of the last pushed frame of sequence `seq`: the next push's reference."""
+        level = self.levels - 1 if level is None else level
+        if not 0 <= level < self.levels:
+            raise ValueError("frame: level %d is outside [0, %d)" % (level, self.levels))
+        shift = self.culls + (self.levels - 1 - level)
+        sh = (self.height >> shift, self.width >> shift)
+        g = np.zeros(sh, np.float32); d = np.zeros(sh, np.float32)
+        _check(lib().dvo_batch_frame_get(self._p, seq, level, fp(g), fp(d)))
+        return g, d
 
     def synchronize(self):
         _check(lib().dvo_batch_synchronize(self._p))

@@ -175,6 +175,10 @@ int dvo_batch_last_poses(dvo_batch* b, float* xi_rel, float* T_rel);
 int dvo_batch_copy_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_dev);
 int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log);
 int dvo_batch_synchronize(dvo_batch* b);
+/* gray and depth [h][w] of pyramid level `level` (0 = coarsest) of the frame the last push gave sequence `seq` = the reference of the
+ * next push (synchronises); either pointer may be NULL.  DVO_ERR_NOT_READY before the first push; with keyframe tracking the
+ * references are the keyframes (dvo_batch_keyframe_get): DVO_ERR_BAD_ARGUMENT. */
+int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* depth);
 /* ---- per-sequence skip and restart (sensor-depth batches) -------------------------------------------------------------------
  * dvo_batch_set_actions gives every sequence an action for the NEXT push (any of dvo_batch_push_device / _host / _raw_device /
  * _raw_host); afterwards the actions are spent.  actions[n_seq]: host memory (actions_on_device = 0) is copied before the call

@@ -21,7 +21,8 @@ def main():
     # keep whole steps only: a step starts at k_pyramid
     steps, cur = [], None
     for s, e, n in rows:
-        if "k_pyramid" in n and ("raw4" in n or "k_pyramid(" in n):
+        # (k_pyramid_raw4_rest, stage B of the split build, runs on the side stream inside the step that k_pyramid_raw4_coarse starts)
+        if "k_pyramid" in n and ("raw4" in n or "k_pyramid(" in n) and "raw4_rest" not in n:
             if cur: steps.append(cur)
             cur = []
         if cur is not None:
@@ -32,10 +33,16 @@ def main():
     gn_d, gn_gap, so_d, so_gap = defaultdict(float), defaultdict(float), defaultdict(float), defaultdict(float)
     other = defaultdict(float)
     wall = 0.0
+    side = [0.0, 0.0, 0, 0]   # stage B: start and end after the step's start (us), the positions running when it starts / ends
     for st in steps:
-        wall += (st[-1][1] - st[0][0]) / 1e3
+        wall += (max(e for _, e, _ in st) - st[0][0]) / 1e3
         pos, prev_end = -1, None
         for s, e, n in st:
+            if "raw4_rest" in n:   # beside the tracking chain, not in it
+                gn = [(s2, e2) for s2, e2, n2 in st if "k_track_gn" in n2]
+                side[0] += (s - st[0][0]) / 1e3; side[1] += (e - st[0][0]) / 1e3
+                side[2] += sum(e2 <= s for _, e2 in gn); side[3] += sum(s2 < e for s2, _ in gn)
+                continue
             gap = (s - prev_end) / 1e3 if prev_end is not None else 0.0
             if "k_track_gn" in n:
                 pos += 1
@@ -53,6 +60,9 @@ def main():
         for i in range(4): tot[i] += v[i]
         print("pos %2d  gn %7.1f us (gap %4.1f)   solve %5.1f us (gap %4.1f)" % ((p,) + v))
     print("totals: gn %.1f  gn_gap %.1f  solve %.1f  solve_gap %.1f us" % tuple(tot))
+    if side[1] > 0:
+        print("k_pyramid_raw4_rest (side stream): starts %.1f us and ends %.1f us after the step's first kernel starts; %.1f k_track_gn launches "
+              "have ended when it starts, %.1f have started when it ends" % tuple(v / n for v in side))
     for k, v in sorted(other.items(), key=lambda kv: -kv[1]):
         print("other %-40s %.1f us (incl. gap before)" % (k, v / n))
 
