@@ -425,6 +425,49 @@ static int track_quality(dvo_batch* b, dvo_track_quality* out, bool to_host)
 int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out) { return track_quality(b, out, true); }
 int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst) { return track_quality(b, dst, false); }
 
+int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg) {
+        const auto positive = [](float v) { return v > 0.0f && v < __builtin_inff(); };
+        if (cfg->struct_size != (int)sizeof(dvo_robust_config)) { set_error("dvo_batch_set_robust_weights: struct_size is not sizeof(dvo_robust_config)"); return DVO_ERR_BAD_ARGUMENT; }
+        if (cfg->kind != DVO_ROBUST_NONE && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
+            set_error("dvo_batch_set_robust_weights: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+            return DVO_ERR_BAD_ARGUMENT;
+        }
+        if (cfg->kind != DVO_ROBUST_NONE) {
+            if (cfg->scale_mode != DVO_ROBUST_SCALE_ADAPTIVE && cfg->scale_mode != DVO_ROBUST_SCALE_GIVEN) {
+                set_error("dvo_batch_set_robust_weights: the scale mode is DVO_ROBUST_SCALE_ADAPTIVE or DVO_ROBUST_SCALE_GIVEN");
+                return DVO_ERR_BAD_ARGUMENT;
+            }
+            if (!positive(cfg->param)) { set_error("dvo_batch_set_robust_weights: param (Huber k, Student-t nu) must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+            if (!positive(cfg->scale_floor)) {   // (whatever the mode: a configuration is valid or not as a whole)
+                set_error("dvo_batch_set_robust_weights: scale_floor must be finite and > 0");
+                return DVO_ERR_BAD_ARGUMENT;
+            }
+        }
+    }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_robust(cfg, b->stream());
+}
+
+int dvo_batch_set_robust_scales(dvo_batch* b, const float* s, int s_on_device)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    const RobustWeights& R = b->trk().rob;
+    if (s && !(R.on && R.mode == DVO_ROBUST_SCALE_GIVEN)) { set_error("dvo_batch_set_robust_scales: rows need the scale mode DVO_ROBUST_SCALE_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_robust_scales(s, s_on_device != 0, b->stream());
+}
+
+int dvo_batch_last_robust_scales(dvo_batch* b, float* s2)
+{
+    if (!b || !s2) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->trk().rob.ready) { set_error("dvo_batch_last_robust_scales: the last push / call did not run with robust weights (dvo_batch_set_robust_weights)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_robust_scales(s2, b->stream());
+}
+
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
@@ -664,9 +707,10 @@ int dvo_op_pyramid(int dev, const float* gray, const float* depth, const float* 
     return DVO_OK;
 }
 
-int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+// dvo_op_gn_step, and with rob (dvo_op_gn_step_robust) the weighted pair on the weighted plan with one entry of (kind, param, s2)
+static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                    const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
-                   dvo_gn_result* out, uint8_t* mask)
+                   dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2)
 {
     if (!obj_gray || !ref_gray || !ref_depth || !ref_sigma || !K || !xi || !out || w < 1 || h < 1 || level < 0 || level >= DVO_MAX_LEVELS)
         return DVO_ERR_BAD_ARGUMENT;
@@ -682,6 +726,7 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     for (int l = 0; l <= level; l++) { gl.w[l] = w; gl.h[l] = h; memcpy(gl.K9[l], g.K9[0], sizeof g.K9[0]); gl.k[l] = g.k[0]; }
     Tracker trk;
     DVO_TRY(trk.init(gl, 1, cf));
+    if (rob) DVO_TRY(trk.set_robust(rob, c.s));
     const size_t n = (size_t)w * h;
     DevBuf og, rg, rd, rs, mk, xin, res;
     DVO_TRY(upload(og, obj_gray, n, c.s));
@@ -705,16 +750,54 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         launch_prep_ref(pa, c.s);
     }
     const GnArgs ga = trk.gn_args(og.as<float>(), rg.as<float>(), rd.as<float>(), wgb.as<float>(), 0.0f, level, mask ? mk.as<uint8_t>() : nullptr, 1);
-    trk.launch_gn(ga, level, 1, c.s);
+    if (trk.rob.on) {
+        RobustBeginArgs ra{};
+        ra.table = trk.rob.table.as<RobustEntry>(); ra.last_s2 = trk.rob.last.as<float>();
+        ra.given = 1; ra.s2_all = rob_s2;
+        ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
+        launch_robust_begin(ra, c.s);
+        trk.launch_gn_rw(ga, level, 1, c.s);
+    } else {
+        trk.launch_gn(ga, level, 1, c.s);
+    }
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    launch_gn_solve(sa, 1, c.s);
+    if (trk.rob.on) trk.launch_solve_rw(sa, 1, c.s, false);
+    else launch_gn_solve(sa, 1, c.s);
     DVO_HIP(hipMemcpyAsync(out, res.p, sizeof *out, hipMemcpyDeviceToHost, c.s));
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
     DVO_HIP(hipGetLastError());
     return DVO_OK;
+}
+
+int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                   const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
+                   dvo_gn_result* out, uint8_t* mask)
+{
+    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, mask, nullptr, 0.0f);
+}
+
+int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                          const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
+                          int kind, float param, float s2, dvo_gn_result* out)
+{
+    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
+        set_error("dvo_op_gn_step_robust: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
+        set_error("dvo_op_gn_step_robust: param (Huber k, Student-t nu) must be finite and > 0");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    dvo_robust_config rc{};
+    rc.struct_size = (int)sizeof rc;
+    // (kind NONE still runs the weighted pair, with the plain entry: rho = 1)
+    rc.kind = kind == DVO_ROBUST_NONE ? DVO_ROBUST_HUBER : kind;
+    rc.scale_mode = DVO_ROBUST_SCALE_GIVEN;
+    rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
+    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2);
 }
 
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

@@ -401,13 +401,14 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     // kernel: measured on MI355X (profiles/r01_gn_variants.md) the LDS-staged variant is 10-15 % slower.
     tile_margin = cfg.gn_use_lds_patch < 0 ? 0 : cfg.gn_use_lds_patch;
     if (tile_margin > 24) tile_margin = 24;
-    for (int l = 0; l < g.levels; l++) {
-        LevelPlan& L = lv[l];
-        L = LevelPlan{};
+    margin_plain = tile_margin;
+    // robust: the weighted plan (lv_rw) -- the global-gather kernel, no fused level, the batch tiling
+    auto plan_level = [&](int l, bool robust) -> LevelPlan {
+        LevelPlan L{};
         int p = cfg.gn_pixels_per_thread;
         const bool auto_p = (p != 1 && p != 2 && p != 4 && p != 8);
         if (auto_p) p = 4;  // auto: biggest tile that still gives >= 4 workgroups per CU
-        if (tile_margin > 0) {
+        if (tile_margin > 0 && !robust) {
             gn_tile_geometry(g.w[l], g.h[l], p, L.tiles_x, L.tiles_y);
             while (auto_p && p > 1 && (size_t)n_seq * L.tiles_x * L.tiles_y < 1024) {
                 p >>= 1;
@@ -419,7 +420,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
             // Off by default: measured on MI355X (512 sequences) the one-workgroup-per-sequence form runs the two coarse
             // levels in ~1.0 ms against ~0.6 ms for the batched launches -- 2 waves per SIMD cannot hide the latency chain
             // of a tile, while the batched kernels share the whole chip among the sequences that are still active.
-            const int fuse_max = cfg.track_fused_tiles <= 0 ? 0
+            const int fuse_max = (cfg.track_fused_tiles <= 0 || robust) ? 0
                                                             : (cfg.track_fused_tiles > DVO_FUSED_MAX_TILES ? DVO_FUSED_MAX_TILES : cfg.track_fused_tiles);
             const int crop_l = level_params(l).crop;
             const GnTiling t4 = gn_tiling(g.w[l], g.h[l], 4, crop_l);
@@ -429,7 +430,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
             //  other, and 75 of them hand over faster than 300 -- 406 against 451 us per 640x480 frame, profiles/r03_single_ab.txt)
             //  A mono handle's levels (at most 160 x 120) show no such difference -- 132-140 us per frame at 1, 2 and 4 pixels per
             //  thread -- so it keeps the tile size every other schedule picks for one sequence (persist_ppt < 0): the same bits.)
-            const bool single_p4 = prefer_persist && n_seq == 1 && cfg.track_single_launch == 0 && !cfg.profile && persist_ppt >= 0;
+            const bool single_p4 = !robust && prefer_persist && n_seq == 1 && cfg.track_single_launch == 0 && !cfg.profile && persist_ppt >= 0;
             if (single_p4 && auto_p && persist_ppt > 0) p = persist_ppt;
             while (!L.fused && auto_p && !single_p4 && p > 1 && (size_t)n_seq * gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l) < 1024) p >>= 1;
             L.tiling = gn_tiling(g.w[l], g.h[l], p, crop_l);   // the level's tiles are decided: every launch takes them from here
@@ -441,6 +442,11 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
         while (gg > p || p % gg) gg >>= 1;
         L.group = gg < 1 ? 1 : gg;
         if ((size_t)L.nblk > max_part) max_part = L.nblk;
+        return L;
+    };
+    for (int l = 0; l < g.levels; l++) {
+        lv[l] = plan_level(l, false);
+        lv_rw[l] = plan_level(l, true);
     }
     DVO_TRY(state.alloc(sizeof(SeqState) * (size_t)n_seq));
     part_rows = max_part;
@@ -482,6 +488,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
         L.single_launch = cfg.track_single_launch >= 0 && n_seq <= 8 && tile_margin == 0 && !L.fused && !cfg.profile && n_sub == 1 &&
                           gn_fused_available(L.ppt, L.group) && L.tiling.live_count > 0 && (long long)n_seq * L.tiling.live_count <= 64;
     }
+    for (int l = 0; l < DVO_MAX_LEVELS; l++) lv_plain[l] = lv[l];
     // k_track_persist (one launch per track() call): one sequence, the global-gather kernel, one (ppt, group) pair on every level,
     // every level within the wide reduction's row limit, no profiling; track_single_launch: < 0 = launch pairs only, 1 = one launch per
     // iteration at most (k_track_gn_fused), 0 (default) = one launch per call where the result goes through enable_host_result()
@@ -577,6 +584,82 @@ SolveArgs Tracker::solve_args(int level, int q0, int ignore_active, SolveRows ro
     a.ignore_active = ignore_active;
     if (quality && level == g.levels - 1) a.result = quality + q0;   // (dvo_batch_set_track_quality: the finest level's solves)
     return a;
+}
+
+void Tracker::use_plan(bool robust)
+{
+    for (int l = 0; l < DVO_MAX_LEVELS; l++) lv[l] = robust ? lv_rw[l] : lv_plain[l];
+    tile_margin = robust ? 0 : margin_plain;
+}
+
+int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
+{
+    const bool enable = c && c->kind != DVO_ROBUST_NONE;
+    if (enable && !rob.table.p) {
+        DVO_TRY(rob.table.alloc(sizeof(RobustEntry) * (size_t)n_seq));
+        DVO_TRY(rob.last.alloc(sizeof(float) * (size_t)n_seq));
+        DVO_TRY(rob.scales.alloc(sizeof(float) * (size_t)n_seq));
+        DVO_TRY(rob.stage.alloc(sizeof(float) * (size_t)n_seq));
+        DVO_HIP(hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s));
+    }
+    rob.on = enable;
+    if (enable) {
+        if (rob.mode != c->scale_mode || c->scale_mode != DVO_ROBUST_SCALE_GIVEN) rob.scales_src = nullptr;   // (rows belong to one GIVEN configuration)
+        rob.kind = c->kind; rob.mode = c->scale_mode; rob.param = c->param;
+        rob.floor2 = c->scale_mode == DVO_ROBUST_SCALE_ADAPTIVE ? c->scale_floor * c->scale_floor : 0.0f;
+    } else {
+        rob.scales_src = nullptr;
+    }
+    use_plan(enable);
+    return DVO_OK;
+}
+
+int Tracker::set_robust_scales(const float* s_rows, bool on_device, hipStream_t s)
+{
+    if (!s_rows) { rob.scales_src = nullptr; return DVO_OK; }
+    if (on_device) {
+        rob.scales_src = s_rows;   // read by k_robust_begin in stream order
+    } else {
+        void* h = nullptr;
+        DVO_TRY(rob.stage.acquire(&h));
+        memcpy(h, s_rows, sizeof(float) * (size_t)n_seq);
+        DVO_TRY(rob.stage.commit(rob.scales.p, sizeof(float) * (size_t)n_seq, s));
+        rob.scales_src = rob.scales.as<float>();
+    }
+    return DVO_OK;
+}
+
+int Tracker::last_robust_scales(float* s2, hipStream_t s) const
+{
+    DVO_HIP(hipMemcpyAsync(s2, rob.last.p, sizeof(float) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+void Tracker::robust_end_push(hipStream_t s)
+{
+    if (rob.on && !rob.tracked) (void)hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s);   // nothing tracked at this push
+    rob.ready = rob.on;
+    rob.tracked = false;
+}
+
+void Tracker::launch_gn_rw(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
+{
+    const LevelPlan& L = lv[level];
+    RobustGn r{};
+    r.table = rob.table.as<RobustEntry>() + (a.state - state.as<SeqState>());
+    launch_track_gn_rw(a, r, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+}
+
+void Tracker::launch_solve_rw(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale) const
+{
+    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
+    RobustSolve r{};
+    r.table = rob.table.as<RobustEntry>() + q0;
+    r.last_s2 = rob.last.as<float>() + q0;
+    r.kind = rob.kind; r.adaptive = adaptive_scale ? 1 : 0;
+    r.param = rob.param; r.floor2 = rob.floor2;
+    launch_gn_solve_rw(sa, r, count, s);
 }
 
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
@@ -679,6 +762,17 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         if (seed_mono) launch_mono_seed(*seed, s);
         else launch_seed_pose(*seed, s);
     }
+    if (rob.on) {   // the weight table of this call (before the fork: every sub-batch reads its part)
+        RobustBeginArgs ra{};
+        ra.table = rob.table.as<RobustEntry>(); ra.last_s2 = rob.last.as<float>();
+        ra.given = rob.mode == DVO_ROBUST_SCALE_GIVEN ? 1 : 0;
+        ra.scales = ra.given ? rob.scales_src : nullptr;
+        ra.s2_all = 0.0f;
+        ra.n_seq = n_seq; ra.kind = rob.kind; ra.param = rob.param;
+        launch_robust_begin(ra, s);
+        rob.tracked = true;
+    }
+    const bool rob_adaptive = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
     // level does not pay for its remaining (empty) launches.  Big batches run the fixed schedule sync-free.
@@ -767,9 +861,12 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                         ev_pool.emplace_back(e0, e1);
                     }
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
-                    launch_gn(ga, level, nq, sk, active_ub);
+                    if (rob.on) launch_gn_rw(ga, level, nq, sk, active_ub);
+                    else launch_gn(ga, level, nq, sk, active_ub);
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
                     ev_used++;
+                } else if (rob.on) {
+                    launch_gn_rw(ga, level, nq, sk, active_ub);
                 } else {
                     launch_gn(ga, level, nq, sk, active_ub);
                 }
@@ -778,7 +875,8 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                launch_gn_solve(sa, nq, sk);
+                if (rob.on) launch_solve_rw(sa, nq, sk, rob_adaptive);
+                else launch_gn_solve(sa, nq, sk);
             }
             if (poll && !L.fused && it + 1 < max_it) {
                 DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
@@ -1383,6 +1481,7 @@ Batch::~Batch()
     plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
     cam_stage.release(stream);
     guess.release(stream);
+    trk.rob.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -1602,6 +1701,7 @@ int Batch::push(const FrameInput& in)
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
     guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
     quality.ready = quality.on;
+    trk.robust_end_push(stream);
     n_push++;
     if (!kf_on || cur < 0) {
         prev = cur;

@@ -225,6 +225,20 @@ struct TrackQuality {
     int read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s);
 };
 
+// Robust residual weights of a batch (dvo_batch_set_robust_weights).  Allocated by the first enable.  While on, the
+// tracker runs the weighted plan (Tracker::lv_rw): k_track_gn_rw + k_gn_solve_rw pairs on every level.
+struct RobustWeights {
+    bool on = false;        // the next push / call runs weighted
+    bool ready = false;     // the last push / call did
+    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every last_s2 is 0)
+    int kind = DVO_ROBUST_NONE, mode = DVO_ROBUST_SCALE_ADAPTIVE;
+    float param = 0.0f, floor2 = 0.0f;   // floor2 = scale_floor * scale_floor, once, in float
+    DevBuf table, last, scales;          // [n_seq] RobustEntry; [n_seq] float s2 of the last iteration; [n_seq] float s (host rows)
+    PinnedPair stage;                    // pinned staging of host rows
+    const float* scales_src = nullptr;   // GIVEN: the rows every later push reads (device memory); nullptr: none (plain)
+    void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
+};
+
 // How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
 // copy the geometry from here into every argument block, and the launchers take the kernel instance from here.
 struct LevelPlan {
@@ -264,6 +278,20 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     std::vector<hipEvent_t> ev_join;
     int sub_first(int k) const { return (int)(((long long)n_seq * k) / n_sub); }
     LevelPlan lv[DVO_MAX_LEVELS];
+    // Both plans are decided by init: lv_plain is what the configuration asks for, lv_rw the weighted plan (launch pairs of the
+    // global-gather kernel on every level, whatever track_fused_tiles, gn_use_lds_patch, track_single_launch and the batch size say).
+    // lv / tile_margin are whichever is in force (use_plan, called by set_robust only).
+    LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
+    int margin_plain = 0;
+    void use_plan(bool robust);
+    RobustWeights rob;
+    int set_robust(const dvo_robust_config* c, hipStream_t s);          // validated by the caller; nullptr / NONE: off
+    int set_robust_scales(const float* s_rows, bool on_device, hipStream_t s);
+    int last_robust_scales(float* s2, hipStream_t s) const;
+    void robust_end_push(hipStream_t s);    // after every push / call of the owner, whether it tracked or not
+    // the weighted pair of one iteration for the sequences `ga` / `sa` view (their SeqState offset is the table's)
+    void launch_gn_rw(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0) const;
+    void launch_solve_rw(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale) const;
     DevBuf ticket, freport;      // k_track_gn_fused: arrival tickets [n_seq]; (reported, active) per (set, level, iteration)
     // Adaptive schedule: progress words in mapped host memory, one per (level, iteration), two sets used alternately.
     // k_gn_solve's workgroup 0 stores (active sequences + 1); the host reads them to stay ~2 iterations ahead of the GPU and

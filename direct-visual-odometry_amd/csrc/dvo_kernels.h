@@ -148,6 +148,55 @@ struct SolveArgs {
     long long* dbg_stamp = nullptr;     // diagnostic (k_track_persist's timeline): [0] after the 6x6 solve, [1] after the pose update
 };
 
+// Robust residual weights (dvo_batch_set_robust_weights).  One entry per sequence: the constants of the weight
+// rho(r) the sequence's next k_track_gn_rw launch applies.  kind = DVO_ROBUST_NONE: rho = 1 ("plain"), whatever the batch's kind.
+struct RobustEntry {
+    int kind;      // DVO_ROBUST_NONE / HUBER / STUDENT_T
+    float A, B;    // Huber: A = c = k * sqrtf(s2); Student-t: A = (nu + 1) * s2, B = nu * s2
+    float s2;      // the squared scale the constants came from; +inf for a plain entry
+};
+// The entry of (kind, param, s2).  A scale that is not finite and > 0 gives the plain entry.
+DVO_HD RobustEntry robust_entry(int kind, float param, float s2)
+{
+    RobustEntry e;
+    e.kind = DVO_ROBUST_NONE; e.A = 0.0f; e.B = 0.0f; e.s2 = __builtin_inff();
+    if (kind == DVO_ROBUST_NONE || !(s2 > 0.0f) || !(s2 < __builtin_inff())) return e;
+    e.kind = kind; e.s2 = s2;
+    if (kind == DVO_ROBUST_HUBER) e.A = param * sqrtf(s2);
+    else { e.A = (param + 1.0f) * s2; e.B = param * s2; }
+    return e;
+}
+// rho(r) of one pixel: Huber fabsf(r) <= c ? 1 : c / fabsf(r); Student-t A / fmaf(r, r, B); plain 1.  One IEEE division serves both
+// kinds (the entry is wave-uniform, so the selects around it are scalar).
+DVO_HD float robust_rho(const RobustEntry& e, float r)
+{
+    const float ar = fabsf(r);
+    const float den = e.kind == DVO_ROBUST_STUDENT_T ? fmaf(r, r, e.B) : ar;
+    const float q = e.A / den;
+    const bool one = (e.kind == DVO_ROBUST_NONE) | ((e.kind == DVO_ROBUST_HUBER) & (ar <= e.A));
+    return one ? 1.0f : q;
+}
+struct RobustGn {      // second argument of k_track_gn_rw / k_track_gn_rw_cam
+    const RobustEntry* table;   // [n_seq of the launch], indexed like GnArgs::state
+};
+struct RobustSolve {   // second argument of k_gn_solve_rw
+    RobustEntry* table;         // indexed like SolveArgs::state
+    float* last_s2;             // [n_seq]: the s2 each sequence's last evaluated iteration used (+inf: plain)
+    int kind, adaptive;         // adaptive: the solve writes the next entry from this iteration's residual
+    float param, floor2;
+};
+struct RobustBeginArgs {   // k_robust_begin: the table at the start of a tracking call
+    RobustEntry* table; float* last_s2;
+    const float* scales;   // GIVEN: [n_seq] s (device), or nullptr: every sequence s2_all
+    float s2_all;
+    int n_seq, kind, given;
+    float param;
+};
+void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s);
+// the weighted twins of launch_track_gn / launch_gn_solve (launch pairs only, no mask)
+void launch_track_gn_rw(const struct GnArgs& a, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
+void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s);
+
 // k_track_persist: the whole of Tracker::track for ONE sequence in one launch (a dvo_vo handle).
 struct PersistLevel {
     const float* obj_gray; const float* ref_gray; const float* ref_depth; const float* ref_wgt;

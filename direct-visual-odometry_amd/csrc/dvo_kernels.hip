@@ -789,6 +789,25 @@ struct Acc29 {
         a[27] = fmaf(r, r, a[27]);
         a[28] += one;
     }
+    // the weighted sums of DESIGN.md §23: Jr = rho * J (one rounded multiply), then the slots and fmaf shape of add(); rho = 1 gives add()'s bits
+    __device__ __forceinline__ void add_w(const float J[6], float r, float rw, float one, float rho)
+    {
+        float Jr[6];
+#pragma unroll
+        for (int p = 0; p < 6; p++) Jr[p] = rho * J[p];
+        int idx = 0;
+#pragma unroll
+        for (int p = 0; p < 6; p++)
+#pragma unroll
+            for (int q = p; q < 6; q++) {
+                a[idx] = fmaf(Jr[p], J[q], a[idx]);
+                idx++;
+            }
+#pragma unroll
+        for (int p = 0; p < 6; p++) a[21 + p] = fmaf(Jr[p], rw, a[21 + p]);
+        a[27] = fmaf(rho * r, r, a[27]);
+        a[28] += one;
+    }
 };
 
 // dword-aligned wide loads (gfx950 global memory takes unaligned dwordx2/x4)
@@ -929,9 +948,11 @@ struct GnTileLds {
 // consecutive raster pixels.  Used when the level width is a multiple of 64: only tiles on the image border then hold
 // deferred (border) pixels, a thread's pixels share their column (one int->float conversion and one (x - cx) for PPT
 // pixels) and there is no row-wrap arithmetic.
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false>
+// ROB: every contributing pixel is weighted by robust_rho(rob, r) (k_track_gn_rw; `rob` is unused otherwise, and ROB = false is the
+// code it always was).
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row, const Intr& cam);
+                                        float* out_row, const Intr& cam, const RobustEntry& rob = RobustEntry{});
 
 #if !defined(DVO_GN_WAVES)
 #define DVO_GN_WAVES 6   /* waves per SIMD the hot variants are compiled for: 6 = up to 84 VGPRs (78 used, no scratch); at 7 (72 VGPRs) the border sampler spills 24 bytes per lane: 54 MB of extra HBM writes per full-batch launch for the same speed (profiles/r03_patch_sampler_ab.txt) */
@@ -993,9 +1014,52 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) 
     clear_next();
 }
 
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM>
+// k_track_gn_rw / k_track_gn_rw_cam: k_track_gn / k_track_gn_cam with robust residual weights (dvo_batch_set_robust_weights, DESIGN.md
+// §23): the same tiles, lists, gates and samplers, and the sequence's RobustEntry loaded once per workgroup (scalar loads) next to its
+// pose.  New kernels beside the plain ones, which stay as they are; no MASK instances (the mask at a pose is the plain kernel's).
+#if !defined(DVO_GN_RW_WAVES)
+#define DVO_GN_RW_WAVES DVO_GN_WAVES
+#endif
+template <int PPT, int G, bool T2D, bool PCAM>
+__device__ __forceinline__ void track_gn_rw_body(const GnArgs& a, const RobustGn& rg, GnTileLds<PPT>& lds)
+{
+    auto clear_next = [&]() {
+        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
+            if (threadIdx.x == 0) *a.next_count = 0;
+        }
+    };
+    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
+    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
+    const int tile_id = xcd * t8 + tile_in_xcd;
+    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
+        clear_next();
+        return;
+    }
+    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
+    const int seq = a.list ? a.list[4 + slot] : slot;
+    const Pose pose = a.state[seq].pose;
+    const RobustEntry rob = load_seq_entry(rg.table, seq);
+    Intr cam = a.k;
+    if constexpr (PCAM) cam = a.seq_k[seq];
+    gn_tile<PPT, G, false, T2D, PCAM, true>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam, rob);
+    clear_next();
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 1) k_track_gn_rw(GnArgs a, RobustGn rg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    track_gn_rw_body<PPT, G, T2D, false>(a, rg, lds);
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 1) k_track_gn_rw_cam(GnArgs a, RobustGn rg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    track_gn_rw_body<PPT, G, T2D, true>(a, rg, lds);
+}
+
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row, const Intr& cam)
+                                        float* out_row, const Intr& cam, const RobustEntry& rob)
 {
     float (&red)[4][32] = lds.red;
     int (&slow_q)[4][PPT * 64] = lds.slow_q;
@@ -1127,6 +1191,10 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             gn_jacobian_pre(seq_intr<PCAM>(a, cam), xs[k], ys[k], d[k], iz[k], wg[k], gx[k], gy[k], I1[k], I2[k], J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
+            if constexpr (ROB) {   // (a rejected pixel's rho is never used: its row is zeros, and 1 keeps a non-finite quotient out of the sums)
+                const float rs = ok ? r : 0.0f;
+                acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
+            } else
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
             if (MASK && ok) a.mask[img_off + (size_t)(ys[k] * w + xs[k])] = 1;
         }
@@ -1157,6 +1225,10 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             gn_jacobian_pre(seq_intr<PCAM>(a, cam), x, y, d, iz, wg, ss.gx, ss.gy, I1, ss.I2, J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
+            if constexpr (ROB) {   // the same operations as in the main loop
+                const float rs = ok ? r : 0.0f;
+                acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
+            } else
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
             if (MASK && ok) a.mask[img_off + i] = 1;
         }
@@ -1434,6 +1506,87 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve(SolveArgs a)
     if (!a.ignore_active && was_active == 0) return;  // converged sequence: nothing to do
     Pose np;
     (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
+}
+
+// k_gn_solve_rw: k_gn_solve for a batch with robust residual weights -- line for line k_gn_solve (a twin, so that kernel stays as it
+// is), and the serial thread also keeps the sequence's RobustEntry: it records the s2 this iteration's k_track_gn_rw used (last_s2) and,
+// with the adaptive scale, writes the entry of the next launch from this iteration's residual -- one fixed-point step of the IRLS scale:
+// s2 = max(residual, floor2), plain when the residual is not > 0 (the -1 sentinel of an iteration without pixels).
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_rw(SolveArgs a, RobustSolve rs)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
+    if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
+    const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
+    const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
+    int my_seq = 0;
+    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
+    SeqState& st = a.state[my_seq];
+    int was_active = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float used_s2 = 0.0f;
+    if (serial) {
+        was_active = st.active; it_prev = st.iter;
+#pragma unroll
+        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
+#pragma unroll
+        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
+        used_s2 = rs.table[my_seq].s2;
+    }
+    const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
+    const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
+    if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
+        const int ws = team >> 2, wg = team & 3;
+        if (ws < n_in && c < 29) {
+            const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
+            part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int ts = threadIdx.x >> 5;
+            tot[ts][c] = (ts < n_in && c < 29) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
+        }
+    } else if (t_slot < n_in && c < 29) {
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
+    } else if (c >= 29) {
+        tot[team][c] = 0.0;
+    }
+    __syncthreads();
+    if (!serial) return;
+    if (!a.ignore_active && was_active == 0) return;
+    Pose np;
+    const double* t = tot[threadIdx.x];
+    (void)solve_finish(a, my_seq, st, t, a.ignore_active, it_prev, xi, Tc, np);
+    rs.last_s2[my_seq] = used_s2;
+    if (rs.adaptive) {
+        const int n_valid = (int)t[28];
+        const float residual = n_valid > 0 ? (float)t[27] / (float)n_valid : -1.0f;   // solve_finish's own expression: the logged bits
+        const float s2 = residual > rs.floor2 ? residual : rs.floor2;
+        rs.table[my_seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
+    }
+}
+
+// k_robust_begin: the RobustEntry table at the start of a tracking call, one thread per sequence.  Adaptive scale: every sequence starts
+// plain (the first iteration of the coarsest level).  Given scale: s2 = s * s of the sequence's row (plain unless s is finite and > 0),
+// or s2_all for every sequence (dvo_op_gn_step_robust).  last_s2 = 0: "not tracked", until a solve says otherwise.
+__global__ void __launch_bounds__(256) k_robust_begin(RobustBeginArgs a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_seq) return;
+    float s2 = 0.0f;
+    if (a.given) {
+        s2 = a.s2_all;
+        if (a.scales) {
+            const float s = a.scales[i];
+            s2 = (s > 0.0f && s < __builtin_inff()) ? s * s : 0.0f;
+        }
+    }
+    a.table[i] = robust_entry(a.kind, a.param, s2);
+    a.last_s2[i] = 0.0f;
 }
 
 // The serial part of one Tracker::track iteration (tracker.cpp:44-73) for one sequence, run by ONE thread: 6x6 solve,
@@ -2607,6 +2760,49 @@ void launch_track_gn(const GnArgs& a0, int n_seq, int ppt, int group, bool t2d, 
         case 82: launch_track_gn_t<8, 2>(a, t2d, grid, s); break;
         default: launch_track_gn_t<8, 4>(a, t2d, grid, s); break;
     }
+}
+
+template <int PPT, int G>
+static void launch_track_gn_rw_t(const GnArgs& a, const RobustGn& r, bool t2d, unsigned tiles, hipStream_t s)
+{
+    const dim3 grid((tiles + 7u) & ~7u);
+    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+        if (a.seq_k) hipLaunchKernelGGL((k_track_gn_rw_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
+        else hipLaunchKernelGGL((k_track_gn_rw<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
+    });
+}
+
+void launch_track_gn_rw(const GnArgs& a0, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
+{
+    GnArgs a = a0;
+    a.n_seq = n_seq; a.mask = nullptr;
+    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
+    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
+    if (grid == 0) grid = 8;
+    switch (ppt * 10 + group) {
+        case 11: launch_track_gn_rw_t<1, 1>(a, r, t2d, grid, s); break;
+        case 21: launch_track_gn_rw_t<2, 1>(a, r, t2d, grid, s); break;
+        case 22: launch_track_gn_rw_t<2, 2>(a, r, t2d, grid, s); break;
+        case 41: launch_track_gn_rw_t<4, 1>(a, r, t2d, grid, s); break;
+        case 42: launch_track_gn_rw_t<4, 2>(a, r, t2d, grid, s); break;
+        case 44: launch_track_gn_rw_t<4, 4>(a, r, t2d, grid, s); break;
+        case 81: launch_track_gn_rw_t<8, 1>(a, r, t2d, grid, s); break;
+        case 82: launch_track_gn_rw_t<8, 2>(a, r, t2d, grid, s); break;
+        default: launch_track_gn_rw_t<8, 4>(a, r, t2d, grid, s); break;
+    }
+}
+
+void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s)
+{
+    SolveArgs b = a;
+    b.n_seq = n_seq;
+    hipLaunchKernelGGL(k_gn_solve_rw, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, r);
+}
+
+void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
 }
 
 // The (ppt, group) pairs the tiling picks for a handle of a few sequences: the ones k_track_gn_fused and k_track_persist have an

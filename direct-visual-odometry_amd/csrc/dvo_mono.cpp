@@ -24,6 +24,7 @@ MonoBatch::~MonoBatch()
         for (hipEvent_t e : m.e) (void)hipEventDestroy(e);
     plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
     guess.release(stream);
+    trk.rob.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 
@@ -243,6 +244,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         DVO_HIP(hipGetLastError());
         guess.rows_src = nullptr;
         quality.ready = quality.on;
+        trk.robust_end_push(stream);
         latest_id = frame_id;
         return DVO_OK;
     }
@@ -374,6 +376,7 @@ int MonoBatch::odometrize(const FrameInput& in)
     }
     DVO_HIP(hipGetLastError());
     quality.ready = quality.on;
+    trk.robust_end_push(stream);
     latest_id = frame_id;
     return DVO_OK;
 }

@@ -78,6 +78,11 @@ TRACK_QUALITY_DTYPE = np.dtype({"names": [f[0] for f in TrackQuality._fields_],
                                 "itemsize": C.sizeof(TrackQuality)})
 
 
+class RobustConfig(C.Structure):
+    """dvo_robust_config (include/dvo.h): robust residual weights of a batch."""
+    _fields_ = [("struct_size", C.c_int), ("kind", C.c_int), ("scale_mode", C.c_int), ("param", C.c_float), ("scale_floor", C.c_float)]
+
+
 class GnProfile(C.Structure):
     _fields_ = [("gn_ms", C.c_double), ("gn_launches", C.c_uint64), ("gn_pixels", C.c_uint64),
                 ("gn_iterations", C.c_uint64)]
@@ -122,6 +127,7 @@ EXPORTS = [
     "dvo_batch_set_keyframe_tracking",
     "dvo_batch_set_track_quality", "dvo_batch_last_track_quality", "dvo_batch_copy_track_quality_device",
     "dvo_batch_frame_get",
+    "dvo_batch_set_robust_weights", "dvo_batch_set_robust_scales", "dvo_batch_last_robust_scales", "dvo_op_gn_step_robust",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -131,6 +137,10 @@ SEQ_TRACKED, SEQ_SKIPPED, SEQ_STARTED, SEQ_BAD_ACTION = 0, 1, 2, 3
 GUESS_NONE, GUESS_GIVEN, GUESS_CONSTANT_VELOCITY = 0, 1, 2
 # flags of a tracking-quality record (TrackQuality.flags): include/dvo.h
 QUALITY_CONVERGED, QUALITY_CAPPED, QUALITY_NO_VALID, QUALITY_NOT_FINITE, QUALITY_RANK_DEFICIENT = 1, 2, 4, 8, 16
+
+# robust residual weights (Batch / MonoBatch .set_robust_weights): include/dvo.h
+ROBUST_NONE, ROBUST_HUBER, ROBUST_STUDENT_T = 0, 1, 2
+ROBUST_SCALE_ADAPTIVE, ROBUST_SCALE_GIVEN = 0, 1
 
 _lib = None
 
@@ -272,6 +282,20 @@ def optimize(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, cfg=None, w
     if want_mask:
         res["mask"] = mask
     return res
+
+
+def optimize_robust(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, kind, param, s2, cfg=None, dev=0):
+    """optimize() with every contributing pixel weighted by rho of (kind, param, s2) (dvo_op_gn_step_robust, include/dvo.h)."""
+    obj_gray = f32(obj_gray); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth); ref_sigma = f32(ref_sigma)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = GnResult()
+    _check(lib().dvo_op_gn_step_robust(dev, C.byref(cfg) if cfg is not None else None, fp(obj_gray), fp(ref_gray),
+                                       fp(ref_depth), fp(ref_sigma), w, h, fp(K), fp(xi), level, int(kind), C.c_float(param),
+                                       C.c_float(s2), C.byref(out)))
+    return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
+                xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
+                xi_next=np.array(out.xi_next[:], np.float32))
 
 
 def track(obj_gray, ref_gray, ref_depth, ref_sigma, K, levels, culls, cfg=None, dev=0):
@@ -615,6 +639,37 @@ class _TrackQuality:
         _check(lib().dvo_batch_copy_track_quality_device(self._p, C.c_void_p(int(ptr))))
 
 
+class _RobustWeights:
+    """Robust residual weights of the tracking, shared by Batch and MonoBatch (dvo_batch_set_robust_weights, include/dvo.h)."""
+
+    def set_robust_weights(self, kind=ROBUST_NONE, param=1.0, scale_mode=ROBUST_SCALE_ADAPTIVE, scale_floor=1e-3):
+        """ROBUST_HUBER (param = k) or ROBUST_STUDENT_T (param = nu) from the next push / call on; ROBUST_NONE or None: off."""
+        if kind is None:
+            _check(lib().dvo_batch_set_robust_weights(self._p, None))
+            return
+        c = RobustConfig(C.sizeof(RobustConfig), int(kind), int(scale_mode), float(param), float(scale_floor))
+        _check(lib().dvo_batch_set_robust_weights(self._p, C.byref(c)))
+
+    def set_robust_scales(self, s, on_device=False):
+        """Scales of every later push (ROBUST_SCALE_GIVEN): float32 [n_seq] (copied now), an int device pointer with on_device=True
+        (read in stream order by every push), or None to clear.  A sequence whose s is not finite and > 0 runs unweighted."""
+        if s is None:
+            _check(lib().dvo_batch_set_robust_scales(self._p, None, 0))
+        elif on_device:
+            _check(lib().dvo_batch_set_robust_scales(self._p, C.c_void_p(int(s)), 1))
+        else:
+            x = f32(s)
+            if x.shape != (self.n_seq,):
+                raise ValueError("set_robust_scales: expected float[%d], got shape %s" % (self.n_seq, x.shape))
+            _check(lib().dvo_batch_set_robust_scales(self._p, fp(x), 0))
+
+    def last_robust_scales(self):
+        """float32 [n_seq]: the s2 of the finest level's last iteration at the last push (+inf: unweighted, 0: not tracked); synchronises."""
+        s2 = np.zeros(self.n_seq, np.float32)
+        _check(lib().dvo_batch_last_robust_scales(self._p, fp(s2)))
+        return s2
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -628,7 +683,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -788,7 +843,7 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality):
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality):
+class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

@@ -495,6 +495,49 @@ typedef struct dvo_track_quality {
 int dvo_batch_set_track_quality(dvo_batch* b, int enable);                      /* both kinds; from the next push / call on */
 int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out);         /* [n_seq], host, synchronises */
 int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst);  /* [n_seq], device, asynchronous on the handle's stream */
+/* ---- robust residual weights (both batch kinds) ---------------------------------------------------------------------------------
+ * By default every contributing pixel enters the normal equations with full weight.  dvo_batch_set_robust_weights makes every later
+ * push / call run iteratively reweighted least squares: per sequence and Gauss-Newton iteration a squared scale s2 (float) and per
+ * contributing pixel a weight rho of its residual r (J, r, rw as the plain estimator forms them; gates, samplers, n_valid and the
+ * mask at a given pose are unchanged), all float32:
+ *   DVO_ROBUST_HUBER       c = param * sqrtf(s2);                  rho = fabsf(r) <= c ? 1 : c / fabsf(r)        (param = k > 0)
+ *   DVO_ROBUST_STUDENT_T   A = (param + 1) * s2, B = param * s2;   rho = A / fmaf(r, r, B)                       (param = nu > 0)
+ *   "plain"                rho = 1 exactly: the unweighted term bit for bit.
+ * The sums keep their slots and order: Jr[p] = rho * J[p]; H[p][q] += Jr[p] * J[q]; g[p] += Jr[p] * rw; sum_r2 += (rho * r) * r.
+ * residual = (float)sum_r2 / (float)n_valid is therefore the WEIGHTED mean square: that value is what the track log, the min_residual
+ * stop test and the quality record (dvo_batch_last_track_quality) see while weights are on.
+ * The scale, by scale_mode:
+ *   DVO_ROBUST_SCALE_ADAPTIVE   s2 = max(residual_prev, scale_floor * scale_floor), residual_prev = the sequence's logged residual of
+ *                               its previous iteration in this push (the same level, or the coarser level's last iteration at a
+ *                               level's first): one fixed-point step of the IRLS scale per iteration -- a weighted RMS, not a MAD.
+ *                               Plain on the first iteration of the coarsest level and whenever residual_prev is not > 0 (the -1 of an
+ *                               iteration without pixels).
+ *   DVO_ROBUST_SCALE_GIVEN      s2 = s[seq] * s[seq], the rows of dvo_batch_set_robust_scales ([n_seq]; host rows are copied before
+ *                               the call returns, device rows are read in stream order by every later push; NULL clears).  A sequence
+ *                               whose s is not finite and > 0 (or whose s * s is not), and every sequence while no rows are set, is plain.
+ * Takes effect from the next push / call; cfg == NULL or kind == DVO_ROBUST_NONE turns the weights off again, and the batch then runs
+ * exactly the launches it ran before.  A batch that never calls this runs exactly the launches it always ran.  While on, every level
+ * runs launch pairs (k_track_gn_rw + k_gn_solve_rw) whatever track_fused_tiles, gn_use_lds_patch and track_single_launch say.
+ * dvo_batch_last_robust_scales: s2[n_seq] (host, synchronises) -- the s2 of the finest level's last iteration of the last push per
+ * sequence, +inf where that iteration was plain, 0 for a sequence that did not track at that push.
+ * Errors, returned before anything is enqueued: a NULL handle, a kind or mode outside the sets, param or scale_floor not finite
+ * and > 0 (whatever the mode), struct_size != sizeof(dvo_robust_config), rows outside the GIVEN mode -> DVO_ERR_BAD_ARGUMENT;
+ * dvo_batch_last_robust_scales before a push that ran with weights on -> DVO_ERR_NOT_READY.  dvo_vo handles have no robust weights. */
+#define DVO_ROBUST_NONE      0
+#define DVO_ROBUST_HUBER     1
+#define DVO_ROBUST_STUDENT_T 2
+#define DVO_ROBUST_SCALE_ADAPTIVE 0
+#define DVO_ROBUST_SCALE_GIVEN    1
+typedef struct dvo_robust_config {
+    int   struct_size;   /* sizeof(dvo_robust_config) */
+    int   kind;          /* DVO_ROBUST_* */
+    int   scale_mode;    /* DVO_ROBUST_SCALE_* */
+    float param;         /* Huber k / Student-t nu, > 0 */
+    float scale_floor;   /* > 0; adaptive: s2 never falls below scale_floor^2 */
+} dvo_robust_config;
+int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg);   /* both kinds; from the next push / call on */
+int dvo_batch_set_robust_scales(dvo_batch* b, const float* s, int s_on_device); /* [n_seq], GIVEN mode; NULL clears */
+int dvo_batch_last_robust_scales(dvo_batch* b, float* s2);                      /* [n_seq], host, synchronises */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */
@@ -535,6 +578,11 @@ typedef struct dvo_gn_result {
 int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                    const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
                    const float xi[6], int level, dvo_gn_result* out, uint8_t* mask);
+/* dvo_op_gn_step with robust residual weights (dvo_batch_set_robust_weights): every contributing pixel weighted by rho of (kind,
+ * param, s2); kind = DVO_ROBUST_NONE, or an s2 that is not finite and > 0, is plain.  No mask: it is dvo_op_gn_step's. */
+int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
+                          const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
+                          const float xi[6], int level, int kind, float param, float s2, dvo_gn_result* out);
 /* Tracker::track, src/track/tracker.cpp:22-85, on full-resolution frames (pyramids built on device). */
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                  const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],

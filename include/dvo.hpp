@@ -185,6 +185,19 @@ public:
         return out;
     }
     void copyTrackQualityDevice(dvo_track_quality* dst) { check(dvo_batch_copy_track_quality_device(b_, dst)); }
+    // robust residual weights from the next push / call on (dvo_batch_set_robust_weights): kind DVO_ROBUST_NONE turns them off
+    void setRobustWeights(int kind, float param = 1.345f, int scale_mode = DVO_ROBUST_SCALE_ADAPTIVE, float scale_floor = 1e-3f)
+    {
+        dvo_robust_config c{(int)sizeof(dvo_robust_config), kind, scale_mode, param, scale_floor};
+        check(dvo_batch_set_robust_weights(b_, &c));
+    }
+    void setRobustScales(const float* s, bool onDevice = false) { check(dvo_batch_set_robust_scales(b_, s, onDevice ? 1 : 0)); }
+    std::vector<float> lastRobustScales()
+    {
+        std::vector<float> out(n_);
+        check(dvo_batch_last_robust_scales(b_, out.data()));
+        return out;
+    }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
@@ -300,6 +313,19 @@ public:
         return out;
     }
     void copyTrackQualityDevice(dvo_track_quality* dst) { check(dvo_batch_copy_track_quality_device(b_, dst)); }
+    // robust residual weights from the next push / call on (dvo_batch_set_robust_weights): kind DVO_ROBUST_NONE turns them off
+    void setRobustWeights(int kind, float param = 1.345f, int scale_mode = DVO_ROBUST_SCALE_ADAPTIVE, float scale_floor = 1e-3f)
+    {
+        dvo_robust_config c{(int)sizeof(dvo_robust_config), kind, scale_mode, param, scale_floor};
+        check(dvo_batch_set_robust_weights(b_, &c));
+    }
+    void setRobustScales(const float* s, bool onDevice = false) { check(dvo_batch_set_robust_scales(b_, s, onDevice ? 1 : 0)); }
+    std::vector<float> lastRobustScales()
+    {
+        std::vector<float> out(n_);
+        check(dvo_batch_last_robust_scales(b_, out.data()));
+        return out;
+    }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {
         std::vector<Mat4> out(n_);
