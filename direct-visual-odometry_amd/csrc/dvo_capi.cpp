@@ -468,6 +468,58 @@ int dvo_batch_last_robust_scales(dvo_batch* b, float* s2)
     return b->trk().last_robust_scales(s2, b->stream());
 }
 
+static bool affine_config_ok(const dvo_affine_config* cfg, const char* who)
+{
+    const auto finite = [](float v) { return v > -__builtin_inff() && v < __builtin_inff(); };
+    if (cfg->struct_size != (int)sizeof(dvo_affine_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_affine_config)"); return false; }
+    if (cfg->mode != DVO_AFFINE_OFF && cfg->mode != DVO_AFFINE_ESTIMATE && cfg->mode != DVO_AFFINE_GIVEN) {
+        set_error(std::string(who) + ": the mode is DVO_AFFINE_OFF, DVO_AFFINE_ESTIMATE or DVO_AFFINE_GIVEN");
+        return false;
+    }
+    if (cfg->mode == DVO_AFFINE_OFF) return true;
+    if (cfg->min_pixels < 2) { set_error(std::string(who) + ": min_pixels must be >= 2"); return false; }
+    if (!(cfg->min_contrast >= 0.0f && cfg->min_contrast < 1.0f)) { set_error(std::string(who) + ": min_contrast must be in [0, 1)"); return false; }
+    if (!(cfg->gain_min > 0.0f) || !finite(cfg->gain_max) || !(cfg->gain_min <= cfg->gain_max)) {
+        set_error(std::string(who) + ": the gain range needs 0 < gain_min <= gain_max < inf");
+        return false;
+    }
+    return true;
+}
+
+int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && !affine_config_ok(cfg, "dvo_batch_set_affine_brightness")) return DVO_ERR_BAD_ARGUMENT;
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_affine(cfg, b->stream());
+}
+
+int dvo_batch_set_affine_rows(dvo_batch* b, const float* ab, int ab_on_device)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    const AffineBrightness& A = b->trk().aff;
+    if (ab && !(A.on && A.mode == DVO_AFFINE_GIVEN)) { set_error("dvo_batch_set_affine_rows: rows need the mode DVO_AFFINE_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_affine_rows(ab, ab_on_device != 0, b->stream());
+}
+
+int dvo_batch_last_affine(dvo_batch* b, float* ab)
+{
+    if (!b || !ab) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->trk().aff.ready) { set_error("dvo_batch_last_affine: the last push / call did not run with affine brightness compensation (dvo_batch_set_affine_brightness)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_affine(ab, b->stream());
+}
+
+int dvo_batch_last_affine_log(dvo_batch* b, int seq, dvo_affine_log* log)
+{
+    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (log->struct_size != (int)sizeof(dvo_affine_log)) { set_error("dvo_batch_last_affine_log: struct_size is not sizeof(dvo_affine_log)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->trk().aff.ready) { set_error("dvo_batch_last_affine_log: the last push / call did not run with affine brightness compensation (dvo_batch_set_affine_brightness)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_affine_log(seq, log, b->stream());
+}
+
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
@@ -710,7 +762,9 @@ int dvo_op_pyramid(int dev, const float* gray, const float* depth, const float* 
 // dvo_op_gn_step, and with rob (dvo_op_gn_step_robust) the weighted pair on the weighted plan with one entry of (kind, param, s2)
 static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                    const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
-                   dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2)
+                   dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2,
+                   const dvo_affine_config* aff = nullptr, float aff_a = 1.0f, float aff_b = 0.0f, double* moments = nullptr,
+                   float* next_ab = nullptr)
 {
     if (!obj_gray || !ref_gray || !ref_depth || !ref_sigma || !K || !xi || !out || w < 1 || h < 1 || level < 0 || level >= DVO_MAX_LEVELS)
         return DVO_ERR_BAD_ARGUMENT;
@@ -727,6 +781,9 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     Tracker trk;
     DVO_TRY(trk.init(gl, 1, cf));
     if (rob) DVO_TRY(trk.set_robust(rob, c.s));
+    if (aff) DVO_TRY(trk.set_affine(aff, c.s));
+    DevBuf mom;
+    if (aff) DVO_TRY(mom.alloc(sizeof(double) * DVO_AFFINE_MOMENTS));
     const size_t n = (size_t)w * h;
     DevBuf og, rg, rd, rs, mk, xin, res;
     DVO_TRY(upload(og, obj_gray, n, c.s));
@@ -756,6 +813,11 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         ra.given = 1; ra.s2_all = rob_s2;
         ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
         launch_robust_begin(ra, c.s);
+    }
+    if (trk.aff.on) {
+        trk.affine_begin(c.s, true, aff_a, aff_b);
+        trk.launch_gn_ab(ga, level, 1, c.s);
+    } else if (trk.rob.on) {
         trk.launch_gn_rw(ga, level, 1, c.s);
     } else {
         trk.launch_gn(ga, level, 1, c.s);
@@ -763,8 +825,13 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    if (trk.rob.on) trk.launch_solve_rw(sa, 1, c.s, false);
+    if (trk.aff.on) trk.launch_solve_ab(sa, 1, c.s, false, false, mom.as<double>(), true);
+    else if (trk.rob.on) trk.launch_solve_rw(sa, 1, c.s, false);
     else launch_gn_solve(sa, 1, c.s);
+    if (trk.aff.on) {
+        DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
+    }
     DVO_HIP(hipMemcpyAsync(out, res.p, sizeof *out, hipMemcpyDeviceToHost, c.s));
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
@@ -798,6 +865,30 @@ int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray,
     rc.scale_mode = DVO_ROBUST_SCALE_GIVEN;
     rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
     return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2);
+}
+
+int dvo_op_gn_step_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                          const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
+                          int kind, float param, float s2, float a, float b, dvo_gn_result* out, double moments[5], float next_ab[2])
+{
+    if (!moments || !next_ab) return DVO_ERR_BAD_ARGUMENT;
+    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
+        set_error("dvo_op_gn_step_affine: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
+        set_error("dvo_op_gn_step_affine: param (Huber k, Student-t nu) must be finite and > 0");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    dvo_robust_config rc{};
+    rc.struct_size = (int)sizeof rc;
+    rc.kind = kind; rc.scale_mode = DVO_ROBUST_SCALE_GIVEN; rc.param = param;
+    dvo_affine_config ac{};   // (the guards of the next entry: the binding's defaults)
+    ac.struct_size = (int)sizeof ac;
+    ac.mode = DVO_AFFINE_GIVEN; ac.min_pixels = 64; ac.min_contrast = 1e-3f; ac.gain_min = 0.25f; ac.gain_max = 4.0f;
+    // (kind NONE runs the instance without robust weights: rho = 1, N = n_valid)
+    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, kind == DVO_ROBUST_NONE ? nullptr : &rc,
+                   s2, &ac, a, b, moments, next_ab);
 }
 
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

@@ -610,7 +610,7 @@ int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
     } else {
         rob.scales_src = nullptr;
     }
-    use_plan(enable);
+    use_plan(rob.on || aff.on);
     return DVO_OK;
 }
 
@@ -641,6 +641,139 @@ void Tracker::robust_end_push(hipStream_t s)
     if (rob.on && !rob.tracked) (void)hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s);   // nothing tracked at this push
     rob.ready = rob.on;
     rob.tracked = false;
+    if (aff.on && !aff.tracked) (void)hipMemsetAsync(aff.last.p, 0, aff.last.bytes, s);   // (affine brightness: the same rule)
+    aff.ready = aff.on;
+    aff.tracked = false;
+}
+
+int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
+{
+    const bool enable = c && c->mode != DVO_AFFINE_OFF;
+    if (enable && !aff.table.p) {
+        aff.log_its = cfg.max_iterations > cfg.fixed_iterations ? cfg.max_iterations : cfg.fixed_iterations;
+        if (aff.log_its > DVO_MAX_ITERATIONS) aff.log_its = DVO_MAX_ITERATIONS;
+        if (aff.log_its < 1) aff.log_its = 1;
+        DVO_TRY(aff.table.alloc(sizeof(AffineEntry) * (size_t)n_seq));
+        DVO_TRY(aff.last.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.prime.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.rows.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.stage.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.moments.alloc(sizeof(float) * 8 * part_rows * (size_t)n_seq));
+        DVO_TRY(aff.log.alloc(sizeof(float) * 2 * (size_t)aff.log_its * (size_t)g.levels * (size_t)n_seq));
+        DVO_HIP(hipMemsetAsync(aff.last.p, 0, aff.last.bytes, s));
+        DVO_HIP(hipMemsetAsync(aff.prime.p, 0, aff.prime.bytes, s));
+        DVO_HIP(hipMemsetAsync(aff.log.p, 0, aff.log.bytes, s));
+    }
+    aff.on = enable;
+    if (enable) {
+        if (aff.mode != c->mode || c->mode != DVO_AFFINE_GIVEN) aff.rows_src = nullptr;   // (rows belong to one GIVEN configuration)
+        aff.mode = c->mode; aff.min_pixels = c->min_pixels; aff.min_contrast = c->min_contrast;
+        aff.gain_min = c->gain_min; aff.gain_max = c->gain_max;
+    } else {
+        aff.rows_src = nullptr;
+        aff.mode = DVO_AFFINE_OFF;
+    }
+    use_plan(rob.on || aff.on);
+    return DVO_OK;
+}
+
+int Tracker::set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s)
+{
+    if (!ab_rows) { aff.rows_src = nullptr; return DVO_OK; }
+    if (on_device) {
+        aff.rows_src = ab_rows;   // read by k_affine_begin in stream order
+    } else {
+        void* h = nullptr;
+        DVO_TRY(aff.stage.acquire(&h));
+        memcpy(h, ab_rows, sizeof(float) * 2 * (size_t)n_seq);
+        DVO_TRY(aff.stage.commit(aff.rows.p, sizeof(float) * 2 * (size_t)n_seq, s));
+        aff.rows_src = aff.rows.as<float>();
+    }
+    return DVO_OK;
+}
+
+int Tracker::last_affine(float* ab, hipStream_t s) const
+{
+    DVO_HIP(hipMemcpyAsync(ab, aff.last.p, sizeof(float) * 2 * (size_t)n_seq, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+int Tracker::last_affine_log(int seq, dvo_affine_log* out, hipStream_t s) const
+{
+    std::vector<float> rows((size_t)2 * aff.log_its * g.levels);
+    std::vector<int> n_iter(DVO_MAX_LEVELS);
+    float last[2] = {0.0f, 0.0f}, prime[2] = {0.0f, 0.0f};
+    DVO_HIP(hipMemcpyAsync(rows.data(), aff.log.as<float>() + (size_t)seq * rows.size(), sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(last, aff.last.as<float>() + 2 * (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(prime, aff.prime.as<float>() + 2 * (size_t)seq, sizeof prime, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    const int size = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = size;
+    out->levels = g.levels;
+    if (last[0] == 0.0f && last[1] == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
+    out->prime_a = prime[0]; out->prime_b = prime[1];
+    for (int l = 0; l < g.levels; l++) {
+        const int n = n_iter[l] < aff.log_its ? n_iter[l] : aff.log_its;
+        out->n_iter[l] = n;
+        for (int it = 0; it < n; it++) {
+            out->a[l][it] = rows[((size_t)l * aff.log_its + it) * 2];
+            out->b[l][it] = rows[((size_t)l * aff.log_its + it) * 2 + 1];
+        }
+    }
+    return DVO_OK;
+}
+
+void Tracker::affine_begin(hipStream_t s, bool given_all, float a_all, float b_all)
+{
+    AffineBeginArgs ba{};
+    ba.table = aff.table.as<AffineEntry>(); ba.last = aff.last.as<float>(); ba.prime_ab = aff.prime.as<float>();
+    ba.rows = (!given_all && aff.mode == DVO_AFFINE_GIVEN) ? aff.rows_src : nullptr;
+    ba.a_all = given_all ? a_all : 1.0f; ba.b_all = given_all ? b_all : 0.0f;
+    ba.n_seq = n_seq;
+    launch_affine_begin(ba, s);
+    aff.tracked = true;
+}
+
+void Tracker::launch_gn_ab(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, bool prime) const
+{
+    const LevelPlan& L = lv[level];
+    const size_t q0 = (size_t)(a.state - state.as<SeqState>());
+    RobustGn r{};
+    if (rob.on) r.table = rob.table.as<RobustEntry>() + q0;
+    AffineGn f{};
+    f.table = aff.table.as<AffineEntry>() + q0;
+    f.moments = aff.moments.as<float>() + q0 * part_rows * 8;
+    f.prime = prime ? 1 : 0;
+    launch_track_gn_ab(a, r, f, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+}
+
+void Tracker::launch_solve_ab(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* moments_out,
+                              bool estimate_once) const
+{
+    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
+    RobustSolve r{};
+    if (rob.on) {
+        r.table = rob.table.as<RobustEntry>() + q0;
+        r.last_s2 = rob.last.as<float>() + q0;
+        r.kind = rob.kind; r.adaptive = adaptive_scale ? 1 : 0;
+        r.param = rob.param; r.floor2 = rob.floor2;
+    }
+    AffineSolve f{};
+    f.table = aff.table.as<AffineEntry>() + q0;
+    f.moments = aff.moments.as<float>() + q0 * part_rows * 8;
+    f.last = aff.last.as<float>() + 2 * q0;
+    f.log = (sa.log && !prime) ? aff.log.as<float>() + 2 * q0 * (size_t)aff.log_its * g.levels : nullptr;
+    f.prime_ab = aff.prime.as<float>() + 2 * q0;
+    f.moments_out = moments_out;
+    f.levels = g.levels; f.log_its = aff.log_its;
+    f.estimate = (aff.mode == DVO_AFFINE_ESTIMATE || estimate_once) ? 1 : 0;
+    f.prime = prime ? 1 : 0;
+    f.robust = rob.on ? 1 : 0;
+    f.min_pixels = aff.min_pixels; f.min_contrast = aff.min_contrast; f.gain_min = aff.gain_min; f.gain_max = aff.gain_max;
+    launch_gn_solve_ab(sa, r, f, count, s);
 }
 
 void Tracker::launch_gn_rw(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
@@ -772,6 +905,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         launch_robust_begin(ra, s);
         rob.tracked = true;
     }
+    if (aff.on) affine_begin(s);   // the brightness table of this call (before the fork, like the weight table)
     const bool rob_adaptive = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
@@ -853,6 +987,16 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
                 ga.list = list_prev;
                 ga.next_count = lists ? work_list(k, it) : nullptr;
+                if (aff.on && aff.mode == DVO_AFFINE_ESTIMATE && level == 0 && first) {
+                    // the priming pair: the moments of the start pose on the coarsest level give the first iteration's entry; it
+                    // leaves the pose, the log, the lists and the quality record alone
+                    GnArgs gp = ga;
+                    gp.next_count = nullptr;
+                    launch_gn_ab(gp, level, nq, sk, 0, true);
+                    SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
+                    sp.list_in = list_prev; sp.result = nullptr;
+                    launch_solve_ab(sp, nq, sk, false, true);
+                }
                 if (cfg.profile) {
                     if (ev_used == ev_pool.size()) {
                         hipEvent_t e0, e1;
@@ -861,10 +1005,13 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                         ev_pool.emplace_back(e0, e1);
                     }
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
-                    if (rob.on) launch_gn_rw(ga, level, nq, sk, active_ub);
+                    if (aff.on) launch_gn_ab(ga, level, nq, sk, active_ub);
+                    else if (rob.on) launch_gn_rw(ga, level, nq, sk, active_ub);
                     else launch_gn(ga, level, nq, sk, active_ub);
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
                     ev_used++;
+                } else if (aff.on) {
+                    launch_gn_ab(ga, level, nq, sk, active_ub);
                 } else if (rob.on) {
                     launch_gn_rw(ga, level, nq, sk, active_ub);
                 } else {
@@ -875,7 +1022,8 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                if (rob.on) launch_solve_rw(sa, nq, sk, rob_adaptive);
+                if (aff.on) launch_solve_ab(sa, nq, sk, rob_adaptive);
+                else if (rob.on) launch_solve_rw(sa, nq, sk, rob_adaptive);
                 else launch_gn_solve(sa, nq, sk);
             }
             if (poll && !L.fused && it + 1 < max_it) {
@@ -1482,6 +1630,7 @@ Batch::~Batch()
     cam_stage.release(stream);
     guess.release(stream);
     trk.rob.release(stream);
+    trk.aff.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 

@@ -239,6 +239,23 @@ struct RobustWeights {
     void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
 };
 
+// Affine brightness compensation of a batch (dvo_batch_set_affine_brightness).  Allocated by the first enable.  While on,
+// the tracker runs the plan of launch pairs (Tracker::lv_rw): k_track_gn_ab + k_gn_solve_ab on every level, with or without robust weights.
+struct AffineBrightness {
+    bool on = false;        // the next push / call runs compensated
+    bool ready = false;     // the last push / call did
+    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every last entry is (0, 0))
+    int mode = DVO_AFFINE_OFF;
+    int min_pixels = 0;
+    float min_contrast = 0.0f, gain_min = 0.0f, gain_max = 0.0f;
+    int log_its = 0;                      // iterations per level of the affine log
+    DevBuf table, last, prime, rows;      // [n_seq] AffineEntry; [n_seq][2] last used / priming entry; [n_seq][2] host rows
+    DevBuf moments, log;                  // [n_seq][part_rows][8] partial rows; [n_seq][levels][log_its][2]
+    PinnedPair stage;                     // pinned staging of host rows
+    const float* rows_src = nullptr;      // GIVEN: the rows every later push reads (device memory); nullptr: none ((1, 0))
+    void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
+};
+
 // How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
 // copy the geometry from here into every argument block, and the launchers take the kernel instance from here.
 struct LevelPlan {
@@ -284,6 +301,16 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
     int margin_plain = 0;
     void use_plan(bool robust);
+    AffineBrightness aff;
+    int set_affine(const dvo_affine_config* c, hipStream_t s);          // validated by the caller; nullptr / OFF: off
+    int set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s);
+    int last_affine(float* ab, hipStream_t s) const;
+    int last_affine_log(int seq, dvo_affine_log* out, hipStream_t s) const;
+    void affine_begin(hipStream_t s, bool given_all = false, float a_all = 1.0f, float b_all = 0.0f);   // k_affine_begin of a call
+    // the compensated pair of one iteration (robust weights included when they are on); prime: the priming pair of ESTIMATE mode
+    void launch_gn_ab(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, bool prime = false) const;
+    void launch_solve_ab(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* moments_out = nullptr,
+                         bool estimate_once = false) const;
     RobustWeights rob;
     int set_robust(const dvo_robust_config* c, hipStream_t s);          // validated by the caller; nullptr / NONE: off
     int set_robust_scales(const float* s_rows, bool on_device, hipStream_t s);

@@ -197,6 +197,54 @@ void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s);
 void launch_track_gn_rw(const struct GnArgs& a, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
 void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s);
 
+// Affine brightness compensation (dvo_batch_set_affine_brightness): I2(warp(x)) ~ a * I1(x) + b per sequence.  One
+// entry per sequence: the (a, b) the sequence's next k_track_gn_ab launch applies; (1, 0) is the plain residual bit for bit.
+struct AffineEntry {
+    float a, b;
+};
+// A given row: (1, 0) unless both values are finite and a > 0.
+DVO_HD AffineEntry affine_entry(float a, float b)
+{
+    AffineEntry e;
+    const float inf = __builtin_inff();
+    const bool ok = (a > 0.0f) & (a < inf) & (b > -inf) & (b < inf);
+    e.a = ok ? a : 1.0f; e.b = ok ? b : 0.0f;
+    return e;
+}
+#define DVO_AFFINE_MOMENTS 5   /* M0 = sum rho, M1 = sum rho I1, M2 = sum rho I2, M11 = sum rho I1 I1, M12 = sum rho I1 I2 */
+// The brightness moments of a launch have partial rows of their own, [n_seq][nblk][8] (slots 5..7 zero), indexed like GnArgs::partials
+// and reduced in the order of the 29 sums: wave, the four waves through LDS in wave order, then the tiles in double in the solve.
+struct AffineGn {      // last argument of k_track_gn_ab / k_track_gn_ab_cam
+    const AffineEntry* table;   // [n_seq of the launch], indexed like GnArgs::state
+    float* moments;
+    int prime;                  // the priming pair: rho = 1 whatever the robust entry says
+};
+struct AffineSolve {   // last argument of k_gn_solve_ab
+    AffineEntry* table;         // indexed like SolveArgs::state
+    const float* moments;       // indexed like SolveArgs::partials
+    float* last;                // [n_seq][2]: the entry each sequence's last evaluated iteration used ((0, 0): not tracked)
+    float* log;                 // optional [n_seq][levels][log_its][2]: the entry every logged iteration used
+    float* prime_ab;            // [n_seq][2]: the entry the priming pair wrote
+    double* moments_out;        // optional [n_seq][5] (dvo_op_gn_step_affine); [0] = the N of the closed form
+    int levels, log_its;
+    int estimate;               // the solve writes the next entry from this iteration's moments (else the entry stays: GIVEN)
+    int prime;                  // the priming pair: the entry and prime_ab only -- no pose, log, iteration count, list or record
+    int robust;                 // robust weights are on too: N = M0 and the RobustEntry is kept as k_gn_solve_rw keeps it
+    int min_pixels;
+    float min_contrast, gain_min, gain_max;
+};
+struct AffineBeginArgs {   // k_affine_begin: the table at the start of a tracking call
+    AffineEntry* table; float* last; float* prime_ab;
+    const float* rows;     // GIVEN: [n_seq][2] (device), or nullptr: every sequence (a_all, b_all)
+    float a_all, b_all;
+    int n_seq;
+};
+void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s);
+// the compensated twins of launch_track_gn / launch_gn_solve (launch pairs only, no mask); r.table == nullptr: no robust weights
+void launch_track_gn_ab(const struct GnArgs& a, const RobustGn& r, const AffineGn& f, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                        int grid_seqs = 0);
+void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s);
+
 // k_track_persist: the whole of Tracker::track for ONE sequence in one launch (a dvo_vo handle).
 struct PersistLevel {
     const float* obj_gray; const float* ref_gray; const float* ref_depth; const float* ref_wgt;

@@ -950,9 +950,12 @@ struct GnTileLds {
 // pixels) and there is no row-wrap arithmetic.
 // ROB: every contributing pixel is weighted by robust_rho(rob, r) (k_track_gn_rw; `rob` is unused otherwise, and ROB = false is the
 // code it always was).
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false>
+// AB: the residual is taken against the compensated brightness fmaf(ab.a, I1, ab.b) and the tile's brightness moments go to mom_row
+// through mred (k_track_gn_ab; unused otherwise, and AB = false is the code it always was).
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false, bool AB = false>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row, const Intr& cam, const RobustEntry& rob = RobustEntry{});
+                                        float* out_row, const Intr& cam, const RobustEntry& rob = RobustEntry{},
+                                        const AffineEntry& ab = AffineEntry{}, float* mom_row = nullptr, float (*mred)[8] = nullptr);
 
 #if !defined(DVO_GN_WAVES)
 #define DVO_GN_WAVES 6   /* waves per SIMD the hot variants are compiled for: 6 = up to 84 VGPRs (78 used, no scratch); at 7 (72 VGPRs) the border sampler spills 24 bytes per lane: 54 MB of extra HBM writes per full-batch launch for the same speed (profiles/r03_patch_sampler_ab.txt) */
@@ -1057,9 +1060,91 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 
     track_gn_rw_body<PPT, G, T2D, true>(a, rg, lds);
 }
 
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB>
+// k_track_gn_ab / k_track_gn_ab_cam: k_track_gn / k_track_gn_cam (ROB: k_track_gn_rw / k_track_gn_rw_cam) with affine brightness
+// compensation (dvo_batch_set_affine_brightness): the same tiles, lists, gates and samplers, and the sequence's
+// AffineEntry loaded once per workgroup (scalar loads) next to its pose.  New kernels beside the others, which stay as they are; no
+// MASK instances (the mask at a pose is the plain kernel's).
+#if !defined(DVO_GN_AB_WAVES)
+#define DVO_GN_AB_WAVES 5   /* the hot <4, 1|2, *, *> instances need 81-87 VGPRs for the four or five moment accumulators: at 6 waves (80 allocatable) they spill 8-28 bytes per lane, at 5 there is no scratch */
+#endif
+// One contributing pixel of k_track_gn_ab, shared by the main loop and the deferred loop: the compensated brightness c, the residual
+// against it, and the pixel's brightness moments M = (M0, M1, M2, M11, M12) with p = rho * I1 (one rounded multiply).  A rejected
+// pixel (ok = false) adds exact zeros; without ROB rho is 1 and M0 is not kept (the solve uses n_valid).
+template <bool ROB>
+__device__ __forceinline__ void affine_pixel(const AffineEntry& ab, const RobustEntry& rob, const bool ok, const float wgt, const float I1,
+                                             const float I2, float& r, float& rw, float& rho, float (&M)[DVO_AFFINE_MOMENTS])
+{
+    const float c = fmaf(ab.a, I1, ab.b);
+    r = ok ? I2 - c : 0.0f;
+    rw = ok ? r * wgt : 0.0f;
+    const float i1 = ok ? I1 : 0.0f, i2 = ok ? I2 : 0.0f;
+    if constexpr (ROB) {
+        rho = ok ? robust_rho(rob, r) : 1.0f;   // (never used for a rejected pixel: 1 keeps a non-finite quotient out of the sums)
+        const float rz = ok ? rho : 0.0f;
+        const float p = rz * i1;
+        M[0] += rz;
+        M[1] += p;
+        M[2] = fmaf(rz, i2, M[2]);
+        M[3] = fmaf(p, i1, M[3]);
+        M[4] = fmaf(p, i2, M[4]);
+    } else {   // rho = 1: p = I1 and fmaf(1, I2, M2) = M2 + I2, the same bits
+        rho = 1.0f;
+        M[1] += i1;
+        M[2] += i2;
+        M[3] = fmaf(i1, i1, M[3]);
+        M[4] = fmaf(i1, i2, M[4]);
+    }
+}
+template <int PPT, int G, bool T2D, bool PCAM, bool ROB>
+__device__ __forceinline__ void track_gn_ab_body(const GnArgs& a, const RobustGn& rg, const AffineGn& ag, GnTileLds<PPT>& lds,
+                                                 float (*mred)[8])
+{
+    auto clear_next = [&]() {
+        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
+            if (threadIdx.x == 0) *a.next_count = 0;
+        }
+    };
+    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
+    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
+    const int tile_id = xcd * t8 + tile_in_xcd;
+    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
+        clear_next();
+        return;
+    }
+    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
+    const int seq = a.list ? a.list[4 + slot] : slot;
+    const Pose pose = a.state[seq].pose;
+    const AffineEntry ab = load_seq_entry(ag.table, seq);
+    RobustEntry rob{};   // (kind 0 = DVO_ROBUST_NONE: rho = 1)
+    if constexpr (ROB) {
+        rob = load_seq_entry(rg.table, seq);
+        if (ag.prime) rob.kind = DVO_ROBUST_NONE;   // (kernel-uniform)
+    }
+    Intr cam = a.k;
+    if constexpr (PCAM) cam = a.seq_k[seq];
+    const size_t row = (size_t)seq * a.nblk + blk;
+    gn_tile<PPT, G, false, T2D, PCAM, ROB, true>(a, pose, seq, blk, lds, a.partials + row * 32, cam, rob, ab, ag.moments + row * 8, mred);
+    clear_next();
+}
+template <int PPT, int G, bool T2D = false, bool ROB = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_AB_WAVES : 1) k_track_gn_ab(GnArgs a, RobustGn rg, AffineGn ag)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_ab_body<PPT, G, T2D, false, ROB>(a, rg, ag, lds, mred);
+}
+template <int PPT, int G, bool T2D = false, bool ROB = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_AB_WAVES : 1) k_track_gn_ab_cam(GnArgs a, RobustGn rg, AffineGn ag)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_ab_body<PPT, G, T2D, true, ROB>(a, rg, ag, lds, mred);
+}
+
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
-                                        float* out_row, const Intr& cam, const RobustEntry& rob)
+                                        float* out_row, const Intr& cam, const RobustEntry& rob, const AffineEntry& ab, float* mom_row,
+                                        float (*mred)[8])
 {
     float (&red)[4][32] = lds.red;
     int (&slow_q)[4][PPT * 64] = lds.slow_q;
@@ -1077,6 +1162,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
 
     Acc29 acc;
     acc.zero();
+    float M[DVO_AFFINE_MOMENTS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // AB: the thread's brightness moments (affine_pixel)
     // G pixels per thread have their gathers in flight together (memory-level parallelism hides the L2/HBM latency)
     static_assert(PPT % G == 0, "PPT must be a multiple of G");
     // pixel k of this thread: coordinates (xA, yA), linear index iA (clamped into the image), inA = it exists
@@ -1191,6 +1277,12 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             gn_jacobian_pre(seq_intr<PCAM>(a, cam), xs[k], ys[k], d[k], iz[k], wg[k], gx[k], gy[k], I1[k], I2[k], J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
+            if constexpr (AB) {
+                float rho;
+                affine_pixel<ROB>(ab, rob, ok, wg[k], I1[k], I2[k], r, rw, rho, M);
+                if constexpr (ROB) acc.add_w(J, r, rw, ok ? 1.0f : 0.0f, rho);
+                else acc.add(J, r, rw, ok ? 1.0f : 0.0f);
+            } else
             if constexpr (ROB) {   // (a rejected pixel's rho is never used: its row is zeros, and 1 keeps a non-finite quotient out of the sums)
                 const float rs = ok ? r : 0.0f;
                 acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
@@ -1225,6 +1317,12 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             gn_jacobian_pre(seq_intr<PCAM>(a, cam), x, y, d, iz, wg, ss.gx, ss.gy, I1, ss.I2, J, r, rw);
 #pragma unroll
             for (int q = 0; q < 6; q++) J[q] = ok ? J[q] : 0.0f;
+            if constexpr (AB) {   // the same operations as in the main loop
+                float rho;
+                affine_pixel<ROB>(ab, rob, ok, wg, I1, ss.I2, r, rw, rho, M);
+                if constexpr (ROB) acc.add_w(J, r, rw, ok ? 1.0f : 0.0f, rho);
+                else acc.add(J, r, rw, ok ? 1.0f : 0.0f);
+            } else
             if constexpr (ROB) {   // the same operations as in the main loop
                 const float rs = ok ? r : 0.0f;
                 acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
@@ -1242,12 +1340,30 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             red[wave][packed_slot_index(lane, 1)] = o1;
         }
     }
+    if constexpr (AB) {   // the moments: a six-step butterfly per wave (every lane ends with the same bits), lane 0 publishes
+#pragma unroll
+        for (int m = ROB ? 0 : 1; m < DVO_AFFINE_MOMENTS; m++) {
+            float v = M[m];
+            v += __shfl_xor(v, 32); v += __shfl_xor(v, 16); v += __shfl_xor(v, 8);
+            v += __shfl_xor(v, 4); v += __shfl_xor(v, 2); v += __shfl_xor(v, 1);
+            if (lane == 0) mred[wave][m] = v;
+        }
+        if (lane == 0 && !ROB) mred[wave][0] = 0.0f;
+    }
     __syncthreads();
     if (threadIdx.x < 32) {
         const int c = threadIdx.x;
         float s = 0.0f;
         if (c < 29) s = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
         out_row[c] = s;
+    }
+    if constexpr (AB) {   // the four waves in wave order, as above (wave 1 stores: the two rows go out side by side)
+        if (threadIdx.x >= 64 && threadIdx.x < 72) {
+            const int c = threadIdx.x - 64;
+            float s = 0.0f;
+            if (c < DVO_AFFINE_MOMENTS) s = ((mred[0][c] + mred[1][c]) + mred[2][c]) + mred[3][c];
+            mom_row[c] = s;
+        }
     }
 }
 
@@ -1392,6 +1508,8 @@ __device__ __forceinline__ int solve_finish(const SolveArgs& a, const int seq, S
 // FIXED order -- four row classes (b mod 4), 32 rows per batch with all 32 loads in flight, then (s0 + s1) + (s2 + s3) -- shared by
 // k_gn_solve, k_track_gn_fused and (re-stated on LDS rows) k_track_level, so every schedule gives the same bits.
 // Rows outside [blk_first, blk_first + blk_count) were not written (crop window): they count as exact zeros in the same slots.
+// (STRIDE: floats per partial row -- 32 for the 29 sums, 8 for the brightness moments of k_track_gn_ab)
+template <int STRIDE = 32>
 __device__ __forceinline__ double sum_partial_rows(const float* p, const int nblk, const int blk_first, const int blk_count)
 {
     const int live0 = blk_count < 0 ? 0 : blk_first, live1 = blk_count < 0 ? nblk : blk_first + blk_count;
@@ -1404,7 +1522,7 @@ __device__ __forceinline__ double sum_partial_rows(const float* p, const int nbl
             for (int j = 0; j < 8; j++) {
                 const int b = b0 + g + DVO_SOLVE_GROUPS * j;
                 const bool live = (b >= live0) & (b < live1);
-                const float x = p[(size_t)(live ? b : 0) * 32];  // (always a valid address: no branch around the load)
+                const float x = p[(size_t)(live ? b : 0) * STRIDE];  // (always a valid address: no branch around the load)
                 v[g][j] = live ? x : 0.0f;
             }
 #pragma unroll
@@ -1587,6 +1705,125 @@ __global__ void __launch_bounds__(256) k_robust_begin(RobustBeginArgs a)
     }
     a.table[i] = robust_entry(a.kind, a.param, s2);
     a.last_s2[i] = 0.0f;
+}
+
+// The closed-form least-squares (a, b) of one iteration's brightness moments, in double: `e` becomes the new entry
+// when the guards hold and keeps its value otherwise.  N = M0 with robust weights, else n_valid.
+__device__ __forceinline__ void affine_next_entry(const AffineSolve& f, const int n_valid, const double N, const double* m, AffineEntry& e)
+{
+    const double M1 = m[1], M2 = m[2], M11 = m[3], M12 = m[4];
+    const double det = N * M11 - M1 * M1;
+    const double an = (N * M12 - M1 * M2) / det;
+    const double bn = (M2 - an * M1) / N;
+    const double inf = __builtin_inf();
+    const bool finite = (an > -inf) & (an < inf) & (bn > -inf) & (bn < inf);   // (false for NaN)
+    if (n_valid >= f.min_pixels && det > (double)f.min_contrast * N * M11 && finite && an >= (double)f.gain_min && an <= (double)f.gain_max) {
+        e.a = (float)an; e.b = (float)bn;
+    }
+}
+
+// k_gn_solve_ab: k_gn_solve_rw for a batch with affine brightness compensation -- line for line that kernel (a twin), and the serial
+// thread also keeps the sequence's AffineEntry: it records the entry this iteration's k_track_gn_ab used (last, and the affine log at
+// the iteration's slot of the track log) and, in ESTIMATE mode, writes the next launch's entry from this iteration's moments, which
+// team lanes 0..7 sum in double in the order of the 29 sums.  f.prime: the priming pair -- the entry and prime_ab only.  The
+// RobustEntry is kept exactly as k_gn_solve_rw keeps it when robust weights are on too (f.robust).
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_ab(SolveArgs a, RobustSolve rs, AffineSolve f)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    __shared__ double mtot[DVO_SOLVE_SEQ][8];
+    const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
+    if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
+    const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
+    const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
+    int my_seq = 0;
+    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
+    SeqState& st = a.state[my_seq];
+    int was_active = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (serial) {
+        was_active = st.active; it_prev = st.iter;
+#pragma unroll
+        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
+#pragma unroll
+        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
+    }
+    const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
+    const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
+    if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
+        const int ws = team >> 2, wg = team & 3;
+        if (ws < n_in && c < 29) {
+            const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
+            part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int ts = threadIdx.x >> 5;
+            tot[ts][c] = (ts < n_in && c < 29) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
+        }
+    } else if (t_slot < n_in && c < 29) {
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
+    } else if (c >= 29) {
+        tot[team][c] = 0.0;
+    }
+    if (t_slot < n_in && c < 8) {   // the moments of the team's sequence (every schedule: the order of sum_partial_rows)
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
+    }
+    __syncthreads();
+    if (!serial) return;
+    if (!a.ignore_active && was_active == 0) return;
+    // (the pose first, the brightness entry after it: nothing of the closed form is live across the serial chain of solve_finish)
+    if (!f.prime) {
+        Pose np;
+        (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
+    }
+    const double* t = tot[threadIdx.x];
+    const double* m = mtot[threadIdx.x];
+    const int n_valid = (int)t[28];
+    const double N = f.robust ? m[0] : (double)n_valid;
+    const AffineEntry used = f.table[my_seq];
+    AffineEntry next = used;
+    if (f.estimate) affine_next_entry(f, n_valid, N, m, next);
+    if (f.moments_out) {
+        double* mo = f.moments_out + (size_t)my_seq * DVO_AFFINE_MOMENTS;
+        mo[0] = N;
+        for (int i = 1; i < DVO_AFFINE_MOMENTS; i++) mo[i] = m[i];
+    }
+    if (f.estimate) f.table[my_seq] = next;
+    if (f.prime) {
+        f.prime_ab[2 * my_seq] = next.a; f.prime_ab[2 * my_seq + 1] = next.b;
+        return;
+    }
+    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    if (f.log && it < f.log_its) {
+        float* lg = f.log + (((size_t)my_seq * f.levels + a.level) * f.log_its + it) * 2;
+        lg[0] = used.a; lg[1] = used.b;
+    }
+    f.last[2 * my_seq] = used.a; f.last[2 * my_seq + 1] = used.b;
+    if (f.robust) {
+        rs.last_s2[my_seq] = rs.table[my_seq].s2;
+        if (rs.adaptive) {
+            const float residual = n_valid > 0 ? (float)t[27] / (float)n_valid : -1.0f;   // solve_finish's own expression: the logged bits
+            const float s2 = residual > rs.floor2 ? residual : rs.floor2;
+            rs.table[my_seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
+        }
+    }
+}
+
+// k_affine_begin: the AffineEntry table at the start of a tracking call, one thread per sequence.  ESTIMATE: every sequence starts at
+// (1, 0).  GIVEN: the sequence's row ((1, 0) unless finite with a > 0), or (a_all, b_all) for every sequence (dvo_op_gn_step_affine).
+// last = (0, 0): "not tracked", until a solve says otherwise.
+__global__ void __launch_bounds__(256) k_affine_begin(AffineBeginArgs a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_seq) return;
+    a.table[i] = a.rows ? affine_entry(a.rows[2 * i], a.rows[2 * i + 1]) : affine_entry(a.a_all, a.b_all);
+    a.last[2 * i] = 0.0f; a.last[2 * i + 1] = 0.0f;
+    a.prime_ab[2 * i] = 0.0f; a.prime_ab[2 * i + 1] = 0.0f;
 }
 
 // The serial part of one Tracker::track iteration (tracker.cpp:44-73) for one sequence, run by ONE thread: 6x6 solve,
@@ -2803,6 +3040,53 @@ void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hip
 void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
+}
+
+template <int PPT, int G>
+static void launch_track_gn_ab_t(const GnArgs& a, const RobustGn& r, const AffineGn& f, bool t2d, unsigned tiles, hipStream_t s)
+{
+    const dim3 grid((tiles + 7u) & ~7u);
+    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+        with_flag(r.table != nullptr, [&](auto robust) {
+            constexpr bool ROB = decltype(robust)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_ab_cam<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
+            else hipLaunchKernelGGL((k_track_gn_ab<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
+        });
+    });
+}
+
+void launch_track_gn_ab(const GnArgs& a0, const RobustGn& r, const AffineGn& f, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                        int grid_seqs)
+{
+    GnArgs a = a0;
+    a.n_seq = n_seq; a.mask = nullptr;
+    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
+    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
+    if (grid == 0) grid = 8;
+    switch (ppt * 10 + group) {
+        case 11: launch_track_gn_ab_t<1, 1>(a, r, f, t2d, grid, s); break;
+        case 21: launch_track_gn_ab_t<2, 1>(a, r, f, t2d, grid, s); break;
+        case 22: launch_track_gn_ab_t<2, 2>(a, r, f, t2d, grid, s); break;
+        case 41: launch_track_gn_ab_t<4, 1>(a, r, f, t2d, grid, s); break;
+        case 42: launch_track_gn_ab_t<4, 2>(a, r, f, t2d, grid, s); break;
+        case 44: launch_track_gn_ab_t<4, 4>(a, r, f, t2d, grid, s); break;
+        case 81: launch_track_gn_ab_t<8, 1>(a, r, f, t2d, grid, s); break;
+        case 82: launch_track_gn_ab_t<8, 2>(a, r, f, t2d, grid, s); break;
+        default: launch_track_gn_ab_t<8, 4>(a, r, f, t2d, grid, s); break;
+    }
+}
+
+void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s)
+{
+    SolveArgs b = a;
+    b.n_seq = n_seq;
+    hipLaunchKernelGGL(k_gn_solve_ab, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, r, f);
+}
+
+void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_affine_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
 }
 
 // The (ppt, group) pairs the tiling picks for a handle of a few sequences: the ones k_track_gn_fused and k_track_persist have an

@@ -25,6 +25,7 @@ MonoBatch::~MonoBatch()
     plan.release(stream);   // (host staging goes before the stream does: PinnedPair)
     guess.release(stream);
     trk.rob.release(stream);
+    trk.aff.release(stream);
     if (own_stream && stream) (void)hipStreamDestroy(stream);
 }
 

@@ -83,6 +83,26 @@ class RobustConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("kind", C.c_int), ("scale_mode", C.c_int), ("param", C.c_float), ("scale_floor", C.c_float)]
 
 
+class AffineConfig(C.Structure):
+    """dvo_affine_config (include/dvo.h): affine brightness compensation of a batch."""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("min_pixels", C.c_int), ("min_contrast", C.c_float),
+                ("gain_min", C.c_float), ("gain_max", C.c_float)]
+
+
+class AffineLog(C.Structure):
+    """dvo_affine_log (include/dvo.h): the (a, b) every logged iteration used, indexed like TrackLog."""
+    _fields_ = [("struct_size", C.c_int), ("levels", C.c_int), ("n_iter", C.c_int * MAX_LEVELS),
+                ("a", (C.c_float * MAX_ITERATIONS) * MAX_LEVELS), ("b", (C.c_float * MAX_ITERATIONS) * MAX_LEVELS),
+                ("prime_a", C.c_float), ("prime_b", C.c_float)]
+
+
+AFFINE_LOG_DTYPE = np.dtype({"names": [f[0] for f in AffineLog._fields_],
+                             "formats": [np.int32, np.int32, (np.int32, MAX_LEVELS), (np.float32, (MAX_LEVELS, MAX_ITERATIONS)),
+                                         (np.float32, (MAX_LEVELS, MAX_ITERATIONS)), np.float32, np.float32],
+                             "offsets": [getattr(AffineLog, f[0]).offset for f in AffineLog._fields_],
+                             "itemsize": C.sizeof(AffineLog)})
+
+
 class GnProfile(C.Structure):
     _fields_ = [("gn_ms", C.c_double), ("gn_launches", C.c_uint64), ("gn_pixels", C.c_uint64),
                 ("gn_iterations", C.c_uint64)]
@@ -128,6 +148,8 @@ EXPORTS = [
     "dvo_batch_set_track_quality", "dvo_batch_last_track_quality", "dvo_batch_copy_track_quality_device",
     "dvo_batch_frame_get",
     "dvo_batch_set_robust_weights", "dvo_batch_set_robust_scales", "dvo_batch_last_robust_scales", "dvo_op_gn_step_robust",
+    "dvo_batch_set_affine_brightness", "dvo_batch_set_affine_rows", "dvo_batch_last_affine", "dvo_batch_last_affine_log",
+    "dvo_op_gn_step_affine",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -141,6 +163,8 @@ QUALITY_CONVERGED, QUALITY_CAPPED, QUALITY_NO_VALID, QUALITY_NOT_FINITE, QUALITY
 # robust residual weights (Batch / MonoBatch .set_robust_weights): include/dvo.h
 ROBUST_NONE, ROBUST_HUBER, ROBUST_STUDENT_T = 0, 1, 2
 ROBUST_SCALE_ADAPTIVE, ROBUST_SCALE_GIVEN = 0, 1
+# affine brightness compensation (Batch / MonoBatch .set_affine_brightness): include/dvo.h
+AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
 
 _lib = None
 
@@ -296,6 +320,23 @@ def optimize_robust(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, kind
     return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
                 xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
                 xi_next=np.array(out.xi_next[:], np.float32))
+
+
+def op_gn_step_affine(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, a, b, kind=ROBUST_NONE, param=1.0, s2=0.0, cfg=None, dev=0):
+    """optimize_robust() against the compensated brightness fmaf(a, I1, b) (dvo_op_gn_step_affine, include/dvo.h); adds `moments`
+    (N, M1, M2, M11, M12 in float64) and `next_ab` (the entry the solve writes from them)."""
+    obj_gray = f32(obj_gray); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth); ref_sigma = f32(ref_sigma)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = GnResult()
+    mom = np.zeros(5, np.float64); nxt = np.zeros(2, np.float32)
+    _check(lib().dvo_op_gn_step_affine(dev, C.byref(cfg) if cfg is not None else None, fp(obj_gray), fp(ref_gray),
+                                       fp(ref_depth), fp(ref_sigma), w, h, fp(K), fp(xi), level, int(kind), C.c_float(param),
+                                       C.c_float(s2), C.c_float(a), C.c_float(b), C.byref(out),
+                                       mom.ctypes.data_as(C.POINTER(C.c_double)), fp(nxt)))
+    return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
+                xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
+                xi_next=np.array(out.xi_next[:], np.float32), moments=mom, next_ab=nxt)
 
 
 def track(obj_gray, ref_gray, ref_depth, ref_sigma, K, levels, culls, cfg=None, dev=0):
@@ -670,6 +711,47 @@ class _RobustWeights:
         return s2
 
 
+class _AffineBrightness:
+    """Affine brightness compensation of the tracking, shared by Batch and MonoBatch (dvo_batch_set_affine_brightness, include/dvo.h)."""
+
+    def set_affine_brightness(self, mode=AFFINE_OFF, min_pixels=64, min_contrast=1e-3, gain_min=0.25, gain_max=4.0):
+        """AFFINE_ESTIMATE (alternating estimate of a gain and an offset per sequence) or AFFINE_GIVEN (rows of set_affine_rows) from
+        the next push / call on; AFFINE_OFF or None: off."""
+        if mode is None:
+            _check(lib().dvo_batch_set_affine_brightness(self._p, None))
+            return
+        c = AffineConfig(C.sizeof(AffineConfig), int(mode), int(min_pixels), float(min_contrast), float(gain_min), float(gain_max))
+        _check(lib().dvo_batch_set_affine_brightness(self._p, C.byref(c)))
+
+    def set_affine_rows(self, ab, on_device=False):
+        """(a, b) of every later push (AFFINE_GIVEN): float32 [n_seq][2] (copied now), an int device pointer with on_device=True (read
+        in stream order by every push), or None to clear.  A row that is not finite or has a <= 0 is (1, 0)."""
+        if ab is None:
+            _check(lib().dvo_batch_set_affine_rows(self._p, None, 0))
+        elif on_device:
+            _check(lib().dvo_batch_set_affine_rows(self._p, C.c_void_p(int(ab)), 1))
+        else:
+            x = f32(ab)
+            if x.shape != (self.n_seq, 2):
+                raise ValueError("set_affine_rows: expected float[%d][2], got shape %s" % (self.n_seq, x.shape))
+            _check(lib().dvo_batch_set_affine_rows(self._p, fp(x), 0))
+
+    def last_affine(self):
+        """float32 [n_seq][2]: the (a, b) the finest level's last iteration used at the last push ((0, 0): not tracked); synchronises."""
+        ab = np.zeros((self.n_seq, 2), np.float32)
+        _check(lib().dvo_batch_last_affine(self._p, fp(ab)))
+        return ab
+
+    def last_affine_log(self, seq):
+        """dict of the (a, b) every logged iteration of `seq` used at the last push (dvo_affine_log); synchronises."""
+        lg = AffineLog()
+        lg.struct_size = C.sizeof(AffineLog)
+        _check(lib().dvo_batch_last_affine_log(self._p, int(seq), C.byref(lg)))
+        rec = np.frombuffer(lg, AFFINE_LOG_DTYPE)[0]
+        return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), a=rec["a"].copy(), b=rec["b"].copy(),
+                    prime_a=np.float32(rec["prime_a"]), prime_b=np.float32(rec["prime_b"]))
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -683,7 +765,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -843,7 +925,7 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights):
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights):
+class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

@@ -538,6 +538,69 @@ typedef struct dvo_robust_config {
 int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg);   /* both kinds; from the next push / call on */
 int dvo_batch_set_robust_scales(dvo_batch* b, const float* s, int s_on_device); /* [n_seq], GIVEN mode; NULL clears */
 int dvo_batch_last_robust_scales(dvo_batch* b, float* s2);                      /* [n_seq], host, synchronises */
+/* ---- affine brightness compensation: gain and offset (both batch kinds) ---------------------------------------------------------
+ * By default every residual is r = I2 - I1: brightness constancy.  dvo_batch_set_affine_brightness makes every later push / call
+ * track under the photometric model I2(warp(x)) ~ a * I1(x) + b with one (a, b) per sequence (auto-exposure, auto-gain), I1 and I2
+ * in the roles they have in the plain residual: I1 the tracked frame's own pixel, I2 the reference sampled at the warped position.
+ * All arithmetic is float32 and IEEE, with no contraction beyond the fmaf()s named.
+ * Per contributing pixel (J, the gates, the samplers, n_valid and the mask at a given pose are the plain estimator's):
+ *   c = fmaf(a, I1, b);  r = I2 - c;  rw = r * wgt.  With (a, b) = (1, 0) c is I1 exactly: every term is the plain term bit for bit.
+ *   The 29 sums keep their slots, their fmaf shape and their reduction, with this r; with robust weights on too
+ *   (dvo_batch_set_robust_weights), rho is taken of the compensated r and the sums are the weighted ones.
+ * Brightness moments of the same pixels (rho = 1 without robust weights), p = rho * I1 rounded once:
+ *   M0 += rho;  M1 += p;  M2 = fmaf(rho, I2, M2);  M11 = fmaf(p, I1, M11);  M12 = fmaf(p, I2, M12);  a rejected pixel adds exact zeros.
+ *   They are reduced in a fixed order of their own (wave, the four waves in wave order, the tiles in double), the same under every
+ *   schedule.  Without robust weights M0 is not kept: N below is n_valid.
+ * The next entry, in double from the double totals, N = M0 (robust weights on) or n_valid:
+ *   det = N * M11 - M1 * M1;  a' = (N * M12 - M1 * M2) / det;  b' = (M2 - a' * M1) / N
+ *   The entry becomes ((float)a', (float)b') only when n_valid >= min_pixels, det > min_contrast * N * M11 (a scale-free flat-image
+ *   guard), both values are finite and gain_min <= a' <= gain_max; otherwise it keeps its value.
+ * The estimate alternates: every Gauss-Newton iteration applies the (a, b) of its entry and accumulates the moments, and the solve
+ * writes the closed form of those moments as the next launch's entry.  J does not depend on (a, b): the 6x6 solve, the track log and
+ * the quality record keep their shape.  It is not a joint 8-parameter Gauss-Newton, and there is no per-pixel model (vignetting,
+ * response curve).  The mode:
+ *   DVO_AFFINE_ESTIMATE   every tracking call starts each tracked sequence at (1, 0).  A priming pair runs first, on the coarsest level
+ *                         at the start pose: it accumulates the moments with rho = 1 and writes the entry -- nothing else (no pose,
+ *                         log, iteration count, active list or quality record).  After it every iteration uses the entry the launch
+ *                         before it wrote; the entry carries across levels.  (With the adaptive robust scale the first iteration of the
+ *                         coarsest level is still unweighted: the priming pair leaves the weight table alone.)
+ *   DVO_AFFINE_GIVEN      (a, b) = the rows of dvo_batch_set_affine_rows ([n_seq][2]; host rows are copied before the call returns,
+ *                         device rows are read in stream order by every later push; NULL clears), fixed for the whole call, no priming
+ *                         pair.  A row that is not finite or has a <= 0, and every sequence while no rows are set, is (1, 0).
+ * Takes effect from the next push / call; cfg == NULL or mode == DVO_AFFINE_OFF turns it off again, and the batch then runs exactly
+ * the launches it ran before.  A batch that never calls this runs exactly the launches it always ran.  While on, every level runs
+ * launch pairs (k_track_gn_ab + k_gn_solve_ab) whatever track_fused_tiles, gn_use_lds_patch and track_single_launch say.
+ * A mono batch applies the compensation to the tracking only: the depth filter's SSD search still assumes brightness constancy.
+ * dvo_batch_last_affine: ab[n_seq][2] (host, synchronises) -- the entry the finest level's last iteration of the last push used,
+ * (0, 0) for a sequence that did not track at that push.  dvo_batch_last_affine_log: the entry every logged iteration USED, indexed
+ * like dvo_track_log (so a replay has the device's own bits), and the entry the priming pair wrote ((0, 0) in GIVEN mode); empty
+ * (n_iter all 0) for a sequence that did not track.
+ * Errors, returned before anything is enqueued: a NULL handle, a mode outside the set, struct_size != sizeof, min_pixels < 2,
+ * min_contrast outside [0, 1), a gain range without 0 < gain_min <= gain_max < inf, rows outside the GIVEN mode ->
+ * DVO_ERR_BAD_ARGUMENT; a read before a push that ran with the feature on -> DVO_ERR_NOT_READY.  dvo_vo handles have no compensation. */
+#define DVO_AFFINE_OFF      0
+#define DVO_AFFINE_ESTIMATE 1
+#define DVO_AFFINE_GIVEN    2
+typedef struct dvo_affine_config {
+    int   struct_size;    /* sizeof(dvo_affine_config) */
+    int   mode;           /* DVO_AFFINE_* */
+    int   min_pixels;     /* >= 2: fewer contributing pixels keep the entry */
+    float min_contrast;   /* [0, 1): det <= min_contrast * N * M11 keeps the entry */
+    float gain_min;       /* 0 < gain_min <= gain_max: an a' outside keeps the entry */
+    float gain_max;
+} dvo_affine_config;
+typedef struct dvo_affine_log {
+    int   struct_size;    /* sizeof(dvo_affine_log), set by the caller */
+    int   levels;
+    int   n_iter[DVO_MAX_LEVELS];
+    float a[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];
+    float b[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];
+    float prime_a, prime_b;
+} dvo_affine_log;
+int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg);  /* both kinds; from the next push / call on */
+int dvo_batch_set_affine_rows(dvo_batch* b, const float* ab, int ab_on_device);   /* [n_seq][2], GIVEN mode; NULL clears */
+int dvo_batch_last_affine(dvo_batch* b, float* ab);                               /* [n_seq][2], host, synchronises */
+int dvo_batch_last_affine_log(dvo_batch* b, int seq, dvo_affine_log* log);        /* host, synchronises */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */
@@ -583,6 +646,14 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
 int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                           const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
                           const float xi[6], int level, int kind, float param, float s2, dvo_gn_result* out);
+/* dvo_op_gn_step_robust with affine brightness compensation (dvo_batch_set_affine_brightness): the pair run once with the entry (a, b)
+ * ((1, 0) unless finite with a > 0).  moments = (N, M1, M2, M11, M12) in double, N being M0 with robust weights and n_valid with kind =
+ * DVO_ROBUST_NONE; next_ab = the entry the solve writes from them under the guards min_pixels = 64, min_contrast = 1e-3, gain range
+ * [0.25, 4] ((a, b) itself where a guard fails). */
+int dvo_op_gn_step_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
+                          const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
+                          const float xi[6], int level, int kind, float param, float s2, float a, float b,
+                          dvo_gn_result* out, double moments[5], float next_ab[2]);
 /* Tracker::track, src/track/tracker.cpp:22-85, on full-resolution frames (pyramids built on device). */
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                  const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],

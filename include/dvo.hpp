@@ -198,6 +198,26 @@ public:
         check(dvo_batch_last_robust_scales(b_, out.data()));
         return out;
     }
+    // affine brightness compensation from the next push / call on (dvo_batch_set_affine_brightness): mode DVO_AFFINE_OFF turns it off
+    void setAffineBrightness(int mode, int min_pixels = 64, float min_contrast = 1e-3f, float gain_min = 0.25f, float gain_max = 4.0f)
+    {
+        dvo_affine_config c{(int)sizeof(dvo_affine_config), mode, min_pixels, min_contrast, gain_min, gain_max};
+        check(dvo_batch_set_affine_brightness(b_, &c));
+    }
+    void setAffineRows(const float* ab, bool onDevice = false) { check(dvo_batch_set_affine_rows(b_, ab, onDevice ? 1 : 0)); }
+    std::vector<float> lastAffine()   // [n_seq][2]
+    {
+        std::vector<float> out(2 * (size_t)n_);
+        check(dvo_batch_last_affine(b_, out.data()));
+        return out;
+    }
+    dvo_affine_log lastAffineLog(int seq)
+    {
+        dvo_affine_log lg{};
+        lg.struct_size = (int)sizeof lg;
+        check(dvo_batch_last_affine_log(b_, seq, &lg));
+        return lg;
+    }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
@@ -325,6 +345,26 @@ public:
         std::vector<float> out(n_);
         check(dvo_batch_last_robust_scales(b_, out.data()));
         return out;
+    }
+    // affine brightness compensation from the next push / call on (dvo_batch_set_affine_brightness): mode DVO_AFFINE_OFF turns it off
+    void setAffineBrightness(int mode, int min_pixels = 64, float min_contrast = 1e-3f, float gain_min = 0.25f, float gain_max = 4.0f)
+    {
+        dvo_affine_config c{(int)sizeof(dvo_affine_config), mode, min_pixels, min_contrast, gain_min, gain_max};
+        check(dvo_batch_set_affine_brightness(b_, &c));
+    }
+    void setAffineRows(const float* ab, bool onDevice = false) { check(dvo_batch_set_affine_rows(b_, ab, onDevice ? 1 : 0)); }
+    std::vector<float> lastAffine()   // [n_seq][2]
+    {
+        std::vector<float> out(2 * (size_t)n_);
+        check(dvo_batch_last_affine(b_, out.data()));
+        return out;
+    }
+    dvo_affine_log lastAffineLog(int seq)
+    {
+        dvo_affine_log lg{};
+        lg.struct_size = (int)sizeof lg;
+        check(dvo_batch_last_affine_log(b_, seq, &lg));
+        return lg;
     }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {

@@ -1,0 +1,613 @@
+"""Affine brightness compensation of a batch (dvo_batch_set_affine_brightness, include/dvo.h) on the GPU, both batch kinds.
+
+Off is today's bits; the identity entry (1, 0) gives the plain batch's bits (and the weighted batch's with Huber on); the operator and
+every logged iteration of a compensated batch match the contract restated on the oracle's per-pixel terms (tests/affine_ref.py): n_valid
+is equal, the logged residual and the finest level's record sit inside the reduction bound, the logged update solves the replayed normal
+equations, and every entry is the closed form of the moments of the iteration before it inside the propagated bound; the guards keep the
+entry; the schedules give the same records; and under an exposure change the estimate beats the plain estimator.
+
+The shapes are tests/test_gpu_robust.py's (its helpers are imported): 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread --
+levels 40x30 and 80x60 (raster tiles) and 160x120 (32-column 2-D tiles), border queues live on all three -- one case at 328x248 (a
+raster finest level), B = 5 to 10, and B = 17 for a solve workgroup boundary and two sub-batches.  The frames a batch sees carry an
+exposure change per push and sequence (EXPO), so that the entries are far from (1, 0)."""
+import numpy as np
+import pytest
+
+import affine_ref as ar
+import dvo_amd as dvo
+import gn_sums
+import lockstep
+import orc
+import robust_ref as rr
+import test_gpu_robust as tr
+from dvo_amd import synth
+from test_gpu_robust import (CULLS, FLOOR, KH, LEVELS, PARAM, SIZE, STEPS, TOP, _acts, _cfg, _dev, _floor2, _frames, _logbits, _wide_idx)
+from util import K640
+
+pytestmark = pytest.mark.gpu
+
+SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
+TRACKED, SKIPPED, STARTED, BAD = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED, dvo.SEQ_BAD_ACTION
+HUBER, STUDENT = dvo.ROBUST_HUBER, dvo.ROBUST_STUDENT_T
+OFF, ESTIMATE, GIVEN = dvo.AFFINE_OFF, dvo.AFFINE_ESTIMATE, dvo.AFFINE_GIVEN
+F32 = np.float32
+EXPO = [(1.0, 0.0), (1.2, -0.03), (0.85, 0.04), (1.1, 0.02)]   # exposure of push k; sequence b scales the gain by 1 + 0.02 b
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _oracle_steps():
+    """the oracle's step literals follow the config of this file (they enter rw); back to the reference's afterwards"""
+    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
+    yield
+    orc.set_tracker_params()
+
+
+def _wp():
+    return ar.weight_params(_cfg())
+
+
+def _rob(kind):
+    return dict(kind=kind, param=PARAM[kind], scale_mode=dvo.ROBUST_SCALE_ADAPTIVE, scale_floor=FLOOR)
+
+
+def _expose(gray, k, b, expo):
+    if not expo:
+        return gray
+    a, o = EXPO[k % len(EXPO)]
+    return (F32(a * (1.0 + 0.02 * b)) * gray + F32(o)).astype(F32)
+
+
+def _gray(size, idx, k, b, expo):
+    """the gray frame sequence b sees at push k (the GPU's input and the oracle's, the same array values)"""
+    return _expose(_frames(size)[0][idx[k][b]], k, b, expo)
+
+
+def _run(cfg, B, idx, aff=None, rows=None, rows_on_device=False, clear=False, rob=None, acts=None, kf=False, feed="device", cams=None,
+         size=SIZE, expo=True, cams_at=None, obj_gray=None):
+    """idx[k][b]: frame of sequence b at push k.  aff: set_affine_brightness arguments (clear: set, then turned off before the first
+    push); rows: GIVEN rows; cams_at = (push, cams): set_intrinsics before that push; obj_gray(k, b, gray): replaces a pushed frame.
+    Returns per push dict(status, q, xi, T, logs, ab, alogs, world)."""
+    g, d, s = _frames(size)
+    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
+    if kf:
+        bt.set_keyframe_tracking(True)
+    bt.set_track_quality(True)
+    if cams is not None:
+        bt.set_intrinsics(cams)
+    keep = []
+    if rob:
+        bt.set_robust_weights(**rob)
+    if aff:
+        bt.set_affine_brightness(**aff)
+        if rows is not None:
+            if rows_on_device:
+                keep.append(_dev(np.asarray(rows, F32)))
+                bt.set_affine_rows(keep[-1].data_ptr(), on_device=True)
+            else:
+                bt.set_affine_rows(rows)
+        if clear:
+            bt.set_affine_brightness(OFF)
+    outs = []
+    for k in range(len(idx)):
+        sel = list(idx[k])
+        gi = np.stack([_gray(size, idx, k, b, expo) for b in range(B)])
+        if obj_gray is not None:
+            gi = np.stack([obj_gray(k, b, gi[b]) for b in range(B)])
+        di, si = d[sel], s[sel]
+        if acts is not None:
+            bt.set_actions(np.asarray(acts[k], np.uint8))
+        if cams_at is not None and cams_at[0] == k:
+            bt.set_intrinsics(cams_at[1])
+        if feed == "host":
+            bt.push_host(gi, di, si)
+        elif feed in ("raw", "raw_host"):
+            g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
+            if feed == "raw_host":
+                bt.push_raw_host(g8, d16)
+            else:
+                import torch
+                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
+                torch.cuda.synchronize()
+                keep.append((tg, td))
+                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
+        else:
+            t = [_dev(x) for x in (gi, di, si)]
+            keep.append(t)
+            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+        o = dict(status=bt.last_status(), q=bt.last_track_quality(), gray=gi)
+        if aff and not clear:
+            o["ab"] = bt.last_affine()
+            o["alogs"] = [bt.last_affine_log(b) for b in range(B)]
+        if k > 0 or acts is not None or kf:
+            xi, T = bt.last_poses()
+            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
+            if kf:
+                o["world"] = bt.world_poses()
+        outs.append(o)
+    bt.close()
+    return outs
+
+
+def _alogbits(al):
+    return (int(al["levels"]), tuple(int(n) for n in al["n_iter"]), al["a"].tobytes(), al["b"].tobytes(), F32(al["prime_a"]).tobytes(),
+            F32(al["prime_b"]).tobytes())
+
+
+def _same(a, b, affine=True):
+    assert len(a) == len(b)
+    for k, (x, y) in enumerate(zip(a, b)):
+        np.testing.assert_array_equal(x["status"], y["status"], err_msg="push %d" % k)
+        if "xi" in x:
+            np.testing.assert_array_equal(x["xi"], y["xi"], err_msg="push %d" % k)
+            np.testing.assert_array_equal(x["T"], y["T"], err_msg="push %d" % k)
+            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
+        if "world" in x:
+            for u, v in zip(x["world"], y["world"]):
+                np.testing.assert_array_equal(u, v, err_msg="push %d world" % k)
+        assert x["q"].tobytes() == y["q"].tobytes(), "push %d records" % k
+        if affine:
+            assert x["ab"].tobytes() == y["ab"].tobytes(), "push %d last_affine" % k
+            assert [_alogbits(l) for l in x["alogs"]] == [_alogbits(l) for l in y["alogs"]], "push %d affine logs" % k
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1: off is today
+@pytest.mark.parametrize("mode", ["plain", "actions", "keyframes"])
+def test_off_means_today(mode):
+    kw = dict(acts=_acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
+    cfg = _cfg(keyframe_max_frames=2) if mode == "keyframes" else _cfg()
+    _same(_run(cfg, 5, _wide_idx(5), **kw), _run(cfg, 5, _wide_idx(5), aff=dict(mode=ESTIMATE), clear=True, **kw), affine=False)
+
+
+def _mono_run(aff=None, clear=False):
+    g, init, ml = tr._mono_frames()
+    mb = dvo.MonoBatch(3, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tr.MONO_SEED))
+    mb.setInitialDepth(init, np.full_like(init, ml.INIT_SIGMA))
+    mb.set_track_quality(True)
+    if aff:
+        mb.set_affine_brightness(**aff)
+        if clear:
+            mb.set_affine_brightness(None)
+    outs = []
+    for k in range(len(tr.MIDX)):
+        t = _dev(g[list(tr.MIDX[k])])
+        mb.odometrize_device(t.data_ptr())
+        xi, T, key = mb.world_poses()
+        outs.append(dict(xi=xi.copy(), T=T.copy(), key=key.copy(), status=mb.last_status(), q=mb.last_track_quality(),
+                         logs=[mb.last_track_log(b) for b in range(3)] if k > 0 else []))
+    mb.close()
+    return outs
+
+
+def test_mono_off_means_today():
+    a, b = _mono_run(), _mono_run(aff=dict(mode=ESTIMATE), clear=True)
+    for k, (x, y) in enumerate(zip(a, b)):
+        for f in ("xi", "T", "status", "key"):
+            np.testing.assert_array_equal(x[f], y[f], err_msg="call %d %s" % (k, f))
+        assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], k
+        assert x["q"].tobytes() == y["q"].tobytes(), k
+
+
+# ------------------------------------------------------------------------------------------------------------------ 2: identity is plain
+@pytest.mark.parametrize("huber", [False, True])
+@pytest.mark.parametrize("variant", ["ones", "bad_rows", "no_rows"])
+def test_identity_entry_is_the_plain_batch(variant, huber):
+    B = 5
+    idx = _wide_idx(B)
+    rob = _rob(HUBER) if huber else None
+    plain = _run(_cfg(), B, idx, rob=rob)
+    rows = dict(ones=np.tile(F32([1.0, 0.0]), (B, 1)),
+                bad_rows=F32([[np.nan, 0.0], [1.0, np.inf], [0.0, 0.1], [-1.0, 0.0], [1.0, np.nan]]), no_rows=None)[variant]
+    got = _run(_cfg(), B, idx, aff=dict(mode=GIVEN), rows=rows, rob=rob)
+    _same(plain, got, affine=False)
+    for o in got[1:]:
+        np.testing.assert_array_equal(o["ab"], np.tile(F32([1.0, 0.0]), (B, 1)))
+        for al in o["alogs"]:
+            n = [int(x) for x in al["n_iter"][:LEVELS]]
+            assert min(n) >= 1 and all((al["a"][l][:n[l]] == 1).all() and not al["b"][l][:n[l]].any() for l in range(LEVELS))
+            assert al["prime_a"] == 0 and al["prime_b"] == 0
+    assert not got[0]["ab"].any()   # nothing tracked at the first push
+
+
+# ------------------------------------------------------------------------------------------------------------------ 3: the operator
+def _oframe(gray, i, K=KH, size=SIZE):
+    g, d, s = _frames(size)
+    return orc.OFrame(gray, d[i], s[i], K, LEVELS, CULLS)
+
+
+@pytest.fixture(scope="module")
+def plain_run():
+    return _run(_cfg(), 3, _wide_idx(3))
+
+
+@pytest.mark.parametrize("kind", [dvo.ROBUST_NONE, HUBER, STUDENT])
+def test_operator_matches_the_contract(kind, plain_run):
+    cfg = _cfg()
+    depth = gn_sums.depth_for_cfg(cfg)
+    before = ar.nonempty_calls()
+    idx = _wide_idx(3)
+    obj, ref = _oframe(plain_run[1]["gray"][0], idx[1][0]), _oframe(plain_run[0]["gray"][0], idx[0][0])
+    poses = tr._level_poses(plain_run[1]["logs"][0])
+    param = PARAM.get(kind, 1.0)
+    for l in range(LEVELS):
+        px = ar.pixels(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), poses[l], l, False, _wp())
+        assert px["n_valid"] > 500
+        for a, b in ((1.0, 0.0), (0.8, 0.05), (1.25, -0.04), (0.83, 0.03)):
+            got = dvo.op_gn_step_affine(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), poses[l], l, a, b, kind, param, 1e-3, cfg=cfg)
+            where = "operator kind %d level %d (a, b) = (%g, %g)" % (kind, l, a, b)
+            ex = ar.assert_step(got, got["moments"], got["next_ab"], px, a, b, kind, param, 1e-3 if kind else rr.INF, depth, tag=where)
+            assert kind == dvo.ROBUST_NONE or (ex["rho"] != 1).any()
+            assert F32(got["residual"]) == F32(got["sum_r2"]) / F32(got["n_valid"])
+            if (a, b) == (1.0, 0.0) and kind == dvo.ROBUST_NONE:   # the identity entry: the plain operator's bits
+                p = dvo.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), poses[l], l, cfg=cfg)
+                assert got["sum_r2"] == p["sum_r2"] and np.array_equal(got["H"], p["H"]) and np.array_equal(got["g"], p["g"])
+    assert ar.nonempty_calls() == before + 4 * LEVELS
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4: replay
+def _check_sequence(o, b, obj, ref, aff, rob, depth, where, given=None):
+    """one TRACKED sequence of one push: every logged iteration against the contract, last_affine, the finest level's record"""
+    lg, al = o["logs"][b], o["alogs"][b]
+    kind = rob["kind"] if rob else rr.NONE
+    guards = {k: aff.get(k, v) for k, v in ar.GUARDS.items()}
+    last, n_it = ar.replay_call(lg, al, ar.oracle_pixels(obj, ref, False, _wp()), LEVELS, aff["mode"], kind=kind, param=PARAM.get(kind, 1.0),
+                                floor2=_floor2(), given_ab=None if given is None else ar_entry(given[b]), guards=guards, depth=depth, tag=where)
+    ex, ab, l, it = last
+    assert l == TOP and it == int(lg["n_iter"][TOP]) - 1
+    assert o["ab"][b].tobytes() == np.array(ab, F32).tobytes(), (where, o["ab"][b], ab)   # the entry the finest level's last iteration used
+    q = o["q"][b]
+    assert q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
+    assert F32(q["residual"]).tobytes() == F32(lg["residual"][TOP][it]).tobytes(), where
+    rr.assert_sums(q, ex["terms"], kind, PARAM.get(kind, 1.0), rr.adaptive_s2(_prev_residual(lg), _floor2()) if rob else rr.INF, depth, where)
+    return n_it, ab
+
+
+def ar_entry(row):
+    """a given row as the device reads it: (1, 0) unless finite with a > 0"""
+    a, b = F32(row[0]), F32(row[1])
+    return (a, b) if np.isfinite(a) and np.isfinite(b) and a > 0 else (F32(1), F32(0))
+
+
+def _prev_residual(lg):
+    """the logged residual before the finest level's last iteration (what its adaptive scale followed)"""
+    it = int(lg["n_iter"][TOP]) - 1
+    return lg["residual"][TOP][it - 1] if it > 0 else lg["residual"][TOP - 1][int(lg["n_iter"][TOP - 1]) - 1]
+
+
+def _empty(o, b):
+    al = o["alogs"][b]
+    return not o["ab"][b].any() and not al["n_iter"].any() and al["prime_a"] == 0 and al["prime_b"] == 0 and not al["a"].any()
+
+
+def _replay(cfg, B, aff, rob=None, acts=None, kf=False, cams=None, size=SIZE, outs=None, min_tracked=None, given=None, rows_on_device=False,
+            cams_at=None, obj_gray=None, expo=True, iters_per_seq=3, nonempty=True):
+    idx = _wide_idx(B)
+    if outs is None:
+        outs = _run(cfg, B, idx, aff=aff, rob=rob, rows=given, rows_on_device=rows_on_device, acts=acts, kf=kf, cams=cams, size=size,
+                    cams_at=cams_at, obj_gray=obj_gray, expo=expo)
+    depth = gn_sums.depth_for_cfg(cfg)
+    before = ar.nonempty_calls()
+    ref_of = [None] * B
+    n = n_it = 0
+    far = 0
+    for k, o in enumerate(outs):
+        Ks = cams_at[1] if cams_at is not None and k >= cams_at[0] else cams
+        for b in range(B):
+            st = o["status"][b]
+            if st == TRACKED:
+                K = Ks[b] if Ks is not None else KH
+                kr = ref_of[b]
+                m, ab = _check_sequence(o, b, _oframe(o["gray"][b], idx[k][b], K, size), _oframe(outs[kr]["gray"][b], idx[kr][b], K, size),
+                                        aff, rob, depth, "push %d seq %d of %d" % (k, b, B), given=given)
+                n_it += m
+                n += 1
+                far += abs(float(ab[0]) - 1.0) > 0.05
+            else:
+                assert _empty(o, b), (k, b, st)   # SKIPPED / STARTED / BAD_ACTION: (0, 0) and an empty log
+            if kf:
+                if st == STARTED or (st == TRACKED and o["world"][2][b]):
+                    ref_of[b] = k
+            elif st in (TRACKED, STARTED):
+                ref_of[b] = k
+    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * B) and n_it > iters_per_seq * n, (n, n_it)
+    assert not nonempty or ar.nonempty_calls() >= before + iters_per_seq * n // 2   # (the helper really ran: non-empty iterations replayed)
+    if aff["mode"] == ESTIMATE and expo and obj_gray is None and aff.get("gain_max", 4.0) >= 4.0 and aff.get("min_pixels", 64) <= 64:
+        assert far >= n // 2, "the exposure changes of EXPO should move most entries away from 1"
+    return outs
+
+
+@pytest.mark.parametrize("B", [5, 17])
+def test_replay_estimate(B):
+    """B = 17: k_gn_solve_ab takes 8 sequences per workgroup, so the third workgroup holds one"""
+    _replay(_cfg(), B, dict(mode=ESTIMATE))
+
+
+def test_replay_given_rows():
+    B = 5
+    given = F32([[1.1, -0.02], [0.9, 0.03], [np.nan, 0.0], [1.3, 0.0], [0.8, 0.05]])
+    _replay(_cfg(), B, dict(mode=GIVEN), given=given, rows_on_device=True)
+
+
+def test_replay_estimate_with_huber():
+    _replay(_cfg(), 5, dict(mode=ESTIMATE), rob=_rob(HUBER))
+
+
+def test_replay_raster_finest_level():
+    _replay(_cfg(), 5, dict(mode=ESTIMATE), size=(328, 248))
+
+
+def test_replay_keyframes():
+    _replay(_cfg(keyframe_max_frames=2), 5, dict(mode=ESTIMATE), kf=True)
+
+
+def test_replay_per_sequence_intrinsics():
+    cams = np.stack([KH] * 5).astype(F32)
+    for b in range(5):
+        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
+    _replay(_cfg(), 5, dict(mode=ESTIMATE), cams=cams)
+
+
+class AffineReplay(lockstep.Replay):
+    """lockstep.Replay whose tracking step restates the compensated contract (tests/affine_ref.py) instead of the plain comparison"""
+    alog = None
+    last = None
+
+    def _track(self, obj, ref, log):
+        last, n = ar.replay_call(log, self.alog, ar.oracle_pixels(obj, ref, self.crop, ar.weight_params()), lockstep.LEVELS, ESTIMATE,
+                                 depth=gn_sums.depth_for_cfg(None), tag=self._where("affine"))
+        self.last = last
+        self.n_iterations += n
+        return np.asarray(log["xi_after"][lockstep.TOP][int(log["n_iter"][lockstep.TOP]) - 1], F32).copy()
+
+
+def test_mono_records_match_the_contract():
+    """the mono batch through tests/lockstep.py: the tracking is compensated, the mapping is the plain one (the keyframes stay the
+    oracle's bit for bit, given the GPU's poses); frames of odd calls are 15 % brighter"""
+    orc.set_tracker_params()    # the mono batch of this test runs the reference's constants
+    try:
+        g, init, ml = tr._mono_frames()
+        B = 2
+        orders = [[0, 1, 2, 3], [5, 4, 3, 2]]
+        sig = np.full_like(init, ml.INIT_SIGMA)
+        mb = dvo.MonoBatch(B, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tr.MONO_SEED))
+        mb.setInitialDepth(init, sig)
+        mb.set_track_quality(True)
+        mb.set_affine_brightness(ESTIMATE)
+        reps = [AffineReplay(K640, 640, 480, tr.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        before = ar.nonempty_calls()
+        n = 0
+        for k in range(len(orders[0])):
+            fr = np.stack([g[orders[q][k]] for q in range(B)])
+            if k % 2:
+                fr = (F32(1.15) * fr + F32(0.02)).astype(F32)
+            t = _dev(fr)
+            mb.odometrize_device(t.data_ptr())
+            rec = mb.last_track_quality()
+            ab = mb.last_affine()
+            for q, gf in enumerate(lockstep.batch_frames(mb, k == 0)):
+                reps[q].alog = mb.last_affine_log(q) if k > 0 else None
+                reps[q].last = None
+                reps[q].step(fr[q], gf)
+                if k == 0:
+                    assert rec["status"][q] == STARTED and not ab[q].any()
+                    continue
+                ex, used, l, it = reps[q].last
+                assert l == lockstep.TOP and ab[q].tobytes() == np.array(used, F32).tobytes(), (k, q, ab[q], used)
+                rr.assert_sums(rec[q], ex["terms"], rr.NONE, 1.0, rr.INF, gn_sums.depth_for_cfg(None), "mono call %d seq %d" % (k, q))
+                n += 1
+        mb.close()
+        assert n == B * (len(orders[0]) - 1) and ar.nonempty_calls() > before
+    finally:
+        orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5: the guards
+@pytest.mark.parametrize("guard", ["constant_gray", "all_invalid", "gain_max", "min_pixels"])
+def test_guards_keep_the_entry(guard):
+    """every guard keeps the previous entry -- (1, 0) from the priming pair on -- against the host derivation from the replayed moments;
+    the two guards that leave the frames alone must then give the plain batch's bits"""
+    B = 5
+    aff = dict(mode=ESTIMATE)
+    obj_gray = None
+    expo = True
+    if guard == "constant_gray":      # det = 0: I1 is one value
+        obj_gray = lambda k, b, gray: np.full_like(gray, 0.5) if k == 1 else gray
+    elif guard == "all_invalid":      # n_valid = 0
+        obj_gray = lambda k, b, gray: np.full_like(gray, orc.INVALID) if k == 1 else gray
+    elif guard == "gain_max":         # every frame is darker than its reference by 0.7: the least-squares gain is 1.14 to 1.2
+        aff["gain_max"] = 1.05
+        obj_gray = lambda k, b, gray: (F32(0.7 ** k) * gray).astype(F32)
+        expo = False
+    else:
+        aff["min_pixels"] = 320 * 240
+    outs = _run(_cfg(), B, _wide_idx(B), aff=aff, obj_gray=obj_gray, expo=expo)
+    # (an all-invalid frame ends every level after one iteration without pixels, as the object at push 1 and as the reference at push 2)
+    _replay(_cfg(), B, aff, outs=outs, obj_gray=obj_gray, expo=expo, iters_per_seq=0 if guard == "all_invalid" else 3, nonempty=guard != "all_invalid")
+    one = np.tile(F32([1.0, 0.0]), (B, 1))
+    pushes = [1] if guard in ("constant_gray", "all_invalid") else [1, 2]
+    for k in pushes:
+        np.testing.assert_array_equal(outs[k]["ab"], one)
+        for al in outs[k]["alogs"]:
+            n = [int(x) for x in al["n_iter"][:LEVELS]]
+            assert al["prime_a"] == 1 and al["prime_b"] == 0
+            assert all((al["a"][l][:n[l]] == 1).all() and not al["b"][l][:n[l]].any() for l in range(LEVELS))
+    if guard == "all_invalid":
+        assert all(int(nv) == 0 for lg in outs[1]["logs"] for l in range(LEVELS) for nv in lg["n_valid"][l][:int(lg["n_iter"][l])])
+    if guard in ("gain_max", "min_pixels"):
+        _same(_run(_cfg(), B, _wide_idx(B), obj_gray=obj_gray, expo=expo), outs, affine=False)
+    if guard == "gain_max":   # and with the default range the same frames do move the entry
+        free = _run(_cfg(), B, _wide_idx(B), aff=dict(mode=ESTIMATE), obj_gray=obj_gray, expo=expo)
+        assert (free[1]["ab"][:, 0] > 1.1).all()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6: the schedules
+@pytest.fixture(scope="module")
+def base5():
+    """ESTIMATE, five sequences on the default schedule: what the schedule variants must reproduce bit for bit"""
+    return _replay(_cfg(), 5, dict(mode=ESTIMATE))
+
+
+@pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "host_feed"])
+def test_schedule_variants_give_the_same_records(variant, base5):
+    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1)).get(variant, {})
+    other = _run(_cfg(**kw), 5, _wide_idx(5), aff=dict(mode=ESTIMATE), feed="host" if variant == "host_feed" else "device")
+    _same(base5, other)
+
+
+def test_two_streams():
+    """two sub-batches need more than 16 sequences (17: not a multiple of 8 either); the table, the moments and the log are offset per
+    sub-batch"""
+    one = _run(_cfg(), 17, _wide_idx(17), aff=dict(mode=ESTIMATE), rob=_rob(HUBER))
+    two = _run(_cfg(track_streams=2), 17, _wide_idx(17), aff=dict(mode=ESTIMATE), rob=_rob(HUBER))
+    _same(one, two)
+    assert all((o["ab"][:, 0] > 0).all() for o in one[1:])
+
+
+def test_raw_feed():
+    a = _run(_cfg(), 5, _wide_idx(5), aff=dict(mode=ESTIMATE), feed="raw")
+    b = _run(_cfg(), 5, _wide_idx(5), aff=dict(mode=ESTIMATE), feed="raw_host")
+    _same(a, b)
+    assert all((o["ab"][:, 0] > 0).all() and np.isfinite(o["ab"]).all() for o in a[1:])
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7: lifecycle
+def test_actions_leave_no_stale_entry():
+    """SKIP, RESTART and a bad action give (0, 0) and an empty log (checked in _replay); the tracked ones replay"""
+    acts = _acts(5, 3, 9)
+    assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
+    acts[2][1] = 7   # an action outside the set: BAD_ACTION, handled as SKIP
+    outs = _replay(_cfg(), 5, dict(mode=ESTIMATE), acts=acts, min_tracked=3)
+    assert outs[2]["status"][1] == BAD and (np.concatenate([o["status"] for o in outs]) == SKIPPED).any()
+
+
+def test_camera_change_restarts_the_sequence():
+    cams = np.stack([KH] * 5).astype(F32)
+    new = cams.copy()
+    new[2, 0, 0] *= 1.02
+    outs = _replay(_cfg(), 5, dict(mode=ESTIMATE), cams=cams, cams_at=(2, new), min_tracked=8)
+    assert outs[2]["status"][2] == STARTED and (outs[2]["status"][[0, 1, 3, 4]] == TRACKED).all()
+
+
+def test_device_rows_follow_the_stream():
+    """rows written on the device before each push are the rows that push uses"""
+    import torch
+    B = 3
+    g, d, s = _frames()
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    bt.set_affine_brightness(GIVEN)
+    rows = torch.zeros((B, 2), dtype=torch.float32, device="cuda")
+    bt.set_affine_rows(rows.data_ptr(), on_device=True)
+    keep = []
+    for k, val in enumerate(((1.5, 0.0), (1.1, -0.02), (0.9, 0.03))):
+        rows[:, 0] = val[0]; rows[:, 1] = val[1]
+        torch.cuda.synchronize()
+        t = [_dev(x[[k, k + 1, k + 2]]) for x in (g, d, s)]
+        keep.append(t)
+        bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+        want = np.tile(F32(val), (B, 1)) if k > 0 else np.zeros((B, 2), F32)
+        np.testing.assert_array_equal(bt.last_affine(), want)
+    bt.close()
+
+
+def test_errors_are_refused():
+    L = dvo.lib()
+    import ctypes as C
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    AC = dvo.AffineConfig
+    sz = C.sizeof(AC)
+    bad = [AC(sz, 3, 64, 1e-3, 0.25, 4.0), AC(sz, -1, 64, 1e-3, 0.25, 4.0), AC(sz, ESTIMATE, 1, 1e-3, 0.25, 4.0), AC(sz, ESTIMATE, -5, 1e-3, 0.25, 4.0),
+           AC(sz, ESTIMATE, 64, -1e-3, 0.25, 4.0), AC(sz, ESTIMATE, 64, 1.0, 0.25, 4.0), AC(sz, ESTIMATE, 64, float("nan"), 0.25, 4.0),
+           AC(sz, GIVEN, 64, 1e-3, 0.0, 4.0), AC(sz, GIVEN, 64, 1e-3, 2.0, 1.0), AC(sz, ESTIMATE, 64, 1e-3, 0.25, float("inf")),
+           AC(sz, ESTIMATE, 64, 1e-3, float("nan"), 4.0), AC(sz - 4, ESTIMATE, 64, 1e-3, 0.25, 4.0), AC(0, ESTIMATE, 64, 1e-3, 0.25, 4.0)]
+    for c in bad:
+        assert L.dvo_batch_set_affine_brightness(bt._p, C.byref(c)) == dvo.DVO_ERR_BAD_ARGUMENT, (c.struct_size, c.mode, c.min_pixels, c.min_contrast,
+                                                                                              c.gain_min, c.gain_max)
+    rows = np.tile(F32([1.0, 0.0]), (2, 1))
+    with pytest.raises(dvo.DvoError):
+        bt.set_affine_rows(rows)                    # the feature is off
+    with pytest.raises(dvo.DvoError):
+        bt.last_affine()                            # nothing pushed
+    with pytest.raises(dvo.DvoError):
+        bt.last_affine_log(0)
+    bt.set_affine_brightness(ESTIMATE)
+    with pytest.raises(dvo.DvoError):
+        bt.set_affine_rows(rows)                    # rows outside the GIVEN mode
+    bt.set_affine_rows(None)                        # clearing is always allowed
+    assert L.dvo_batch_last_affine(bt._p, None) == dvo.DVO_ERR_BAD_ARGUMENT
+    lg = dvo.AffineLog()
+    assert L.dvo_batch_last_affine_log(bt._p, 0, C.byref(lg)) == dvo.DVO_ERR_BAD_ARGUMENT    # struct_size not set
+    bt.set_affine_brightness(None)
+    g, d, s = _frames()
+    t = [_dev(x[:2]) for x in (g, d, s)]
+    bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    with pytest.raises(dvo.DvoError):
+        bt.last_affine()                            # the push ran without the feature
+    bt.set_affine_brightness(GIVEN)
+    with pytest.raises(dvo.DvoError):
+        bt.last_affine()                            # enabled from the next push on
+    bt.set_affine_rows(F32([[1.1, 0.01], [0.9, -0.02]]))
+    t2 = [_dev(x[1:3]) for x in (g, d, s)]
+    bt.push_device(t2[0].data_ptr(), t2[1].data_ptr(), t2[2].data_ptr())
+    np.testing.assert_array_equal(bt.last_affine(), F32([[1.1, 0.01], [0.9, -0.02]]))
+    with pytest.raises(dvo.DvoError):
+        bt.last_affine_log(2)                       # seq out of range
+    bt.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ 8: it helps
+OUTCOME_PAIRS = [(0.7, 0.08), (0.85, -0.05), (1.15, 0.04), (1.3, -0.08), (1.4, 0.02)]   # (a*, b*): frame 1 becomes a* gray + b*
+OUTCOME_SEEDS = (42, 43)
+# the numpy replica of the contract on the oracle (affine_ref.affine_track): ESTIMATE is closer than plain in 10 of 10
+# cases, summed error 0.0357 against plain's 2.28; the cap on the GPU's ratio is the midpoint between that ratio and 1
+REPLICA_RATIO = 0.0157
+OUTCOME_CAP = 0.5 * (REPLICA_RATIO + 1.0)
+
+
+def test_estimate_beats_plain_under_an_exposure_change():
+    """Frame 1 with its gray replaced by a* gray + b* (five pairs, two scenes), tracked against frame 0: one batch of ten sequences per
+    estimator.  ESTIMATE must be closer to the true motion than plain in at least 8 of the 10 cases and its summed error at most
+    OUTCOME_CAP times plain's; last_affine must be the closed form of the replica at the GPU's logged poses."""
+    cfg = _cfg(max_iterations=15)
+    cases, gts = [], []
+    for seed in OUTCOME_SEEDS:
+        g, d, s, poses = synth.sequence(3, 320, 240, KH, seed=seed, sigma_value=0.5, sigma_t=0.01, sigma_r_deg=0.5)
+        g, d, s = g.numpy(), d.numpy(), s.numpy()
+        gt = orc.se3_log((np.linalg.inv(poses[1]) @ poses[0]).astype(F32)).astype(np.float64)
+        for a, b in OUTCOME_PAIRS:
+            cases.append((g[0], d[0], s[0], (F32(a) * g[1] + F32(b)).astype(F32), d[1], s[1], a, b))
+            gts.append(gt)
+    B = len(cases)
+    assert B == 10 and all(c[3].min() > -1.0 for c in cases)
+    err = {}
+    for mode in (OFF, ESTIMATE):
+        bt = dvo.Batch(B, KH, 320, 240, LEVELS, CULLS, cfg=cfg)
+        if mode != OFF:
+            bt.set_affine_brightness(mode)
+        t0 = [_dev(np.stack([c[i] for c in cases])) for i in (0, 1, 2)]
+        bt.push_device(t0[0].data_ptr(), t0[1].data_ptr(), t0[2].data_ptr())
+        t1 = [_dev(np.stack([c[i] for c in cases])) for i in (3, 4, 5)]
+        bt.push_device(t1[0].data_ptr(), t1[1].data_ptr(), t1[2].data_ptr())
+        xi, _ = bt.last_poses()
+        if mode == ESTIMATE:
+            ab = bt.last_affine()
+            logs = [(bt.last_track_log(b), bt.last_affine_log(b)) for b in range(B)]
+        bt.close()
+        err[mode] = np.array([np.linalg.norm(xi[b].astype(np.float64) - gts[b]) for b in range(B)])
+    # last_affine against the replica's closed form at the GPU's own logged poses (the whole call replayed)
+    dist = []
+    for b, c in enumerate(cases):
+        obj, ref = orc.OFrame(c[3], c[4], c[5], KH, LEVELS, CULLS), orc.OFrame(c[0], c[1], c[2], KH, LEVELS, CULLS)
+        last, _ = ar.replay_call(logs[b][0], logs[b][1], ar.oracle_pixels(obj, ref, False, ar.weight_params(cfg)), LEVELS, ESTIMATE,
+                                 depth=gn_sums.depth_for_cfg(cfg), tag="outcome case %d" % b)
+        assert ab[b].tobytes() == np.array(last[1], F32).tobytes()
+        dist.append((abs(float(ab[b][0]) - 1.0 / c[6]), abs(float(ab[b][1]) + c[7] / c[6])))   # the changed frame plays I1: the inverse map
+    wins, ratio = int((err[ESTIMATE] < err[OFF]).sum()), err[ESTIMATE].sum() / err[OFF].sum()
+    print("\nESTIMATE: GPU wins %d of %d, summed error %.4g against plain %.4g, ratio %.3f (cap %.3f); |a - 1/a*| <= %.3g, |b + b*/a*| <= %.3g"
+          % (wins, B, err[ESTIMATE].sum(), err[OFF].sum(), ratio, OUTCOME_CAP, max(x for x, _ in dist), max(y for _, y in dist)))
+    assert REPLICA_RATIO <= 0.5
+    assert wins >= 8 and ratio <= OUTCOME_CAP, (wins, ratio, err)
+
+
+def test_zz_report_reduction_bound_ratios():
+    """last in the file: under -s, the largest error / bound ratio of every compensated comparison of this process"""
+    gn_sums.report("test_gpu_affine")
+    assert all(r <= 1.0 for _, r in gn_sums.RATIOS)
