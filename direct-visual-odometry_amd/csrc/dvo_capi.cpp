@@ -447,6 +447,10 @@ int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
             }
         }
     }
+    if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().geo.on) {
+        set_error("dvo_batch_set_robust_weights: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     DVO_TRY(select_device(b->device()));
     return b->trk().set_robust(cfg, b->stream());
 }
@@ -490,6 +494,10 @@ int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (cfg && !affine_config_ok(cfg, "dvo_batch_set_affine_brightness")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().geo.on) {
+        set_error("dvo_batch_set_affine_brightness: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     DVO_TRY(select_device(b->device()));
     return b->trk().set_affine(cfg, b->stream());
 }
@@ -518,6 +526,56 @@ int dvo_batch_last_affine_log(dvo_batch* b, int seq, dvo_affine_log* log)
     if (!b->trk().aff.ready) { set_error("dvo_batch_last_affine_log: the last push / call did not run with affine brightness compensation (dvo_batch_set_affine_brightness)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(b->device()));
     return b->trk().last_affine_log(seq, log, b->stream());
+}
+
+void dvo_geometric_config_default(dvo_geometric_config* cfg)
+{
+    if (!cfg) return;
+    cfg->struct_size = (int)sizeof(dvo_geometric_config);
+    cfg->mode = DVO_GEOMETRIC_ON;
+    cfg->weight = 10.0f;
+    cfg->max_diff = 0.1f;
+}
+
+static bool geometric_config_ok(const dvo_geometric_config* cfg, const char* who)
+{
+    const float inf = __builtin_inff();
+    if (cfg->struct_size != (int)sizeof(dvo_geometric_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_geometric_config)"); return false; }
+    if (cfg->mode != DVO_GEOMETRIC_OFF && cfg->mode != DVO_GEOMETRIC_ON) { set_error(std::string(who) + ": the mode is DVO_GEOMETRIC_OFF or DVO_GEOMETRIC_ON"); return false; }
+    if (cfg->mode == DVO_GEOMETRIC_OFF) return true;
+    if (!(cfg->weight >= 0.0f && cfg->weight < inf)) { set_error(std::string(who) + ": weight must be finite and >= 0"); return false; }
+    if (!(cfg->max_diff > 0.0f && cfg->max_diff < inf)) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return false; }
+    return true;
+}
+
+int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_geometric: needs a sensor-depth batch (a mono batch has no depth map to compare)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (cfg && !geometric_config_ok(cfg, "dvo_batch_set_geometric")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->mode != DVO_GEOMETRIC_OFF && (b->trk().rob.on || b->trk().aff.on)) {
+        set_error("dvo_batch_set_geometric: robust weights or affine brightness compensation are on: they do not combine with the geometric term yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_geometric(cfg, b->stream());
+}
+
+int dvo_batch_last_geometric(dvo_batch* b, dvo_geometric_record* rec)
+{
+    if (!b || !rec) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->trk().geo.ready) { set_error("dvo_batch_last_geometric: the last push did not run with the geometric term (dvo_batch_set_geometric)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_geometric(rec, b->stream());
+}
+
+int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log)
+{
+    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (log->struct_size != (int)sizeof(dvo_geometric_log)) { set_error("dvo_batch_last_geometric_log: struct_size is not sizeof(dvo_geometric_log)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->trk().geo.ready) { set_error("dvo_batch_last_geometric_log: the last push did not run with the geometric term (dvo_batch_set_geometric)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_geometric_log(seq, log, b->stream());
 }
 
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
@@ -764,7 +822,8 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
                    const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
                    dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2,
                    const dvo_affine_config* aff = nullptr, float aff_a = 1.0f, float aff_b = 0.0f, double* moments = nullptr,
-                   float* next_ab = nullptr)
+                   float* next_ab = nullptr, const dvo_geometric_config* geo = nullptr, const float* geo_ref_depth = nullptr,
+                   double* geo_sums = nullptr)
 {
     if (!obj_gray || !ref_gray || !ref_depth || !ref_sigma || !K || !xi || !out || w < 1 || h < 1 || level < 0 || level >= DVO_MAX_LEVELS)
         return DVO_ERR_BAD_ARGUMENT;
@@ -784,6 +843,13 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     if (aff) DVO_TRY(trk.set_affine(aff, c.s));
     DevBuf mom;
     if (aff) DVO_TRY(mom.alloc(sizeof(double) * DVO_AFFINE_MOMENTS));
+    // (the geometric term: ref_depth / ref_sigma are the tracked frame's own maps, geo_ref_depth the reference's depth)
+    DevBuf zr, zs;
+    if (geo) {
+        DVO_TRY(trk.set_geometric(geo, c.s));
+        DVO_TRY(upload(zr, geo_ref_depth, (size_t)w * h, c.s));
+        DVO_TRY(zs.alloc(sizeof(double) * 2));
+    }
     const size_t n = (size_t)w * h;
     DevBuf og, rg, rd, rs, mk, xin, res;
     DVO_TRY(upload(og, obj_gray, n, c.s));
@@ -814,7 +880,9 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
         launch_robust_begin(ra, c.s);
     }
-    if (trk.aff.on) {
+    if (trk.geo.on) {
+        trk.launch_gn_z(ga, zr.as<float>(), level, 1, c.s);
+    } else if (trk.aff.on) {
         trk.affine_begin(c.s, true, aff_a, aff_b);
         trk.launch_gn_ab(ga, level, 1, c.s);
     } else if (trk.rob.on) {
@@ -825,18 +893,33 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    if (trk.aff.on) trk.launch_solve_ab(sa, 1, c.s, false, false, mom.as<double>(), true);
+    if (trk.geo.on) trk.launch_solve_z(sa, 1, c.s, zs.as<double>());
+    else if (trk.aff.on) trk.launch_solve_ab(sa, 1, c.s, false, false, mom.as<double>(), true);
     else if (trk.rob.on) trk.launch_solve_rw(sa, 1, c.s, false);
     else launch_gn_solve(sa, 1, c.s);
     if (trk.aff.on) {
         DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
     }
+    if (trk.geo.on) DVO_HIP(hipMemcpyAsync(geo_sums, zs.p, sizeof(double) * 2, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipMemcpyAsync(out, res.p, sizeof *out, hipMemcpyDeviceToHost, c.s));
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
     DVO_HIP(hipGetLastError());
     return DVO_OK;
+}
+
+int dvo_op_gn_step_geometric(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth, const float* obj_sigma,
+                             const float* ref_gray, const float* ref_depth, int w, int h, const float K[9], const float xi[6], int level,
+                             float weight, float max_diff, dvo_gn_result* out, double sums[2])
+{
+    if (!ref_depth || !sums) return DVO_ERR_BAD_ARGUMENT;
+    dvo_geometric_config gc{};
+    gc.struct_size = (int)sizeof gc;
+    gc.mode = DVO_GEOMETRIC_ON; gc.weight = weight; gc.max_diff = max_diff;
+    if (!geometric_config_ok(&gc, "dvo_op_gn_step_geometric")) return DVO_ERR_BAD_ARGUMENT;
+    return gn_step(dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, nullptr, nullptr, 0.0f, nullptr, 1.0f, 0.0f,
+                   nullptr, nullptr, &gc, ref_depth, sums);
 }
 
 int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

@@ -610,7 +610,7 @@ int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
     } else {
         rob.scales_src = nullptr;
     }
-    use_plan(rob.on || aff.on);
+    use_plan(rob.on || aff.on || geo.on);
     return DVO_OK;
 }
 
@@ -644,6 +644,85 @@ void Tracker::robust_end_push(hipStream_t s)
     if (aff.on && !aff.tracked) (void)hipMemsetAsync(aff.last.p, 0, aff.last.bytes, s);   // (affine brightness: the same rule)
     aff.ready = aff.on;
     aff.tracked = false;
+    if (geo.on && !geo.tracked) (void)hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s);   // (the geometric term: the same rule)
+    geo.ready = geo.on;
+    geo.tracked = false;
+}
+
+int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
+{
+    const bool enable = c && c->mode != DVO_GEOMETRIC_OFF;
+    if (enable && !geo.last.p) {
+        geo.log_its = cfg.max_iterations > cfg.fixed_iterations ? cfg.max_iterations : cfg.fixed_iterations;
+        if (geo.log_its > DVO_MAX_ITERATIONS) geo.log_its = DVO_MAX_ITERATIONS;
+        if (geo.log_its < 1) geo.log_its = 1;
+        DVO_TRY(geo.last.alloc(sizeof(float) * 4 * (size_t)n_seq));
+        DVO_TRY(geo.log.alloc(sizeof(float) * 2 * (size_t)geo.log_its * (size_t)g.levels * (size_t)n_seq));
+        DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
+        DVO_HIP(hipMemsetAsync(geo.log.p, 0, geo.log.bytes, s));
+    }
+    geo.on = enable;
+    if (enable) { geo.weight = c->weight; geo.max_diff = c->max_diff; }
+    use_plan(rob.on || aff.on || geo.on);
+    return DVO_OK;
+}
+
+int Tracker::last_geometric(dvo_geometric_record* rec, hipStream_t s) const
+{
+    std::vector<float> rows((size_t)4 * n_seq);
+    DVO_HIP(hipMemcpyAsync(rows.data(), geo.last.p, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    for (int q = 0; q < n_seq; q++) {
+        rec[q].n_geo = (int)rows[4 * (size_t)q];
+        rec[q].mean_sq = rows[4 * (size_t)q + 1];
+    }
+    return DVO_OK;
+}
+
+int Tracker::last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const
+{
+    std::vector<float> rows((size_t)2 * geo.log_its * g.levels);
+    std::vector<int> n_iter(DVO_MAX_LEVELS);
+    float last[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    DVO_HIP(hipMemcpyAsync(rows.data(), geo.log.as<float>() + (size_t)seq * rows.size(), sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(last, geo.last.as<float>() + 4 * (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    const int size = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = size;
+    out->levels = g.levels;
+    if (last[2] == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
+    for (int l = 0; l < g.levels; l++) {
+        const int n = n_iter[l] < geo.log_its ? n_iter[l] : geo.log_its;
+        out->n_iter[l] = n;
+        for (int it = 0; it < n; it++) {
+            out->n_geo[l][it] = (int)rows[((size_t)l * geo.log_its + it) * 2];
+            out->sum_sq[l][it] = rows[((size_t)l * geo.log_its + it) * 2 + 1];
+        }
+    }
+    return DVO_OK;
+}
+
+void Tracker::launch_gn_z(const GnArgs& a, const float* ref_z, int level, int count, hipStream_t s, int grid_seqs) const
+{
+    const LevelPlan& L = lv[level];
+    const size_t q0 = (size_t)(a.state - state.as<SeqState>());
+    GeoGn z{};
+    z.ref_z = ref_z + q0 * (size_t)g.w[level] * g.h[level];   // (gn_view's offset of these sequences)
+    z.weight = geo.weight; z.max_diff = geo.max_diff;
+    launch_track_gn_z(a, z, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+}
+
+void Tracker::launch_solve_z(const SolveArgs& sa, int count, hipStream_t s, double* sums_out) const
+{
+    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
+    GeoSolve z{};
+    z.last = geo.last.as<float>() + 4 * q0;
+    z.log = sa.log ? geo.log.as<float>() + 2 * q0 * (size_t)geo.log_its * g.levels : nullptr;
+    z.sums_out = sums_out;
+    z.levels = g.levels; z.log_its = geo.log_its;
+    launch_gn_solve_z(sa, z, count, s);
 }
 
 int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
@@ -673,7 +752,7 @@ int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
         aff.rows_src = nullptr;
         aff.mode = DVO_AFFINE_OFF;
     }
-    use_plan(rob.on || aff.on);
+    use_plan(rob.on || aff.on || geo.on);
     return DVO_OK;
 }
 
@@ -906,6 +985,10 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         rob.tracked = true;
     }
     if (aff.on) affine_begin(s);   // the brightness table of this call (before the fork, like the weight table)
+    if (geo.on) {   // "not tracked" until a solve says otherwise (before the fork)
+        DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
+        geo.tracked = true;
+    }
     const bool rob_adaptive = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
@@ -964,7 +1047,10 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 for (int k = 0; k < subs; k++) DVO_HIP(hipStreamWaitEvent(k == 0 ? s : sub_streams[k - 1], top_ready, 0));
                 top_waited = true;
             }
-            const GnArgs ga0 = gn_args(obj, ref, level, nullptr, first);
+            // (the geometric term: pixel x of the tracked frame uses that frame's own depth and weight; the reference's depth is sampled)
+            const GnArgs ga0 = geo.on ? gn_args(obj.gray[level], ref.gray[level], obj.depth[level], obj.sigma_by_validity ? nullptr : obj.wgt[level],
+                                                obj.sigma_by_validity ? obj.wgt_valid[level] : 0.0f, level, nullptr, first)
+                                      : gn_args(obj, ref, level, nullptr, first);
             for (int k = 0; k < subs; k++) {  // launches of the sub-batches interleave on their streams
                 const int q0 = subs > 1 ? sub_first(k) : 0, q1 = subs > 1 ? sub_first(k + 1) : n_seq, nq = q1 - q0;
                 hipStream_t sk = k == 0 ? s : sub_streams[k - 1];
@@ -1005,11 +1091,14 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                         ev_pool.emplace_back(e0, e1);
                     }
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
-                    if (aff.on) launch_gn_ab(ga, level, nq, sk, active_ub);
+                    if (geo.on) launch_gn_z(ga, ref.depth[level], level, nq, sk, active_ub);
+                    else if (aff.on) launch_gn_ab(ga, level, nq, sk, active_ub);
                     else if (rob.on) launch_gn_rw(ga, level, nq, sk, active_ub);
                     else launch_gn(ga, level, nq, sk, active_ub);
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
                     ev_used++;
+                } else if (geo.on) {
+                    launch_gn_z(ga, ref.depth[level], level, nq, sk, active_ub);
                 } else if (aff.on) {
                     launch_gn_ab(ga, level, nq, sk, active_ub);
                 } else if (rob.on) {
@@ -1022,7 +1111,8 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                if (aff.on) launch_solve_ab(sa, nq, sk, rob_adaptive);
+                if (geo.on) launch_solve_z(sa, nq, sk);
+                else if (aff.on) launch_solve_ab(sa, nq, sk, rob_adaptive);
                 else if (rob.on) launch_solve_rw(sa, nq, sk, rob_adaptive);
                 else launch_gn_solve(sa, nq, sk);
             }
@@ -1807,7 +1897,9 @@ int Batch::push(const FrameInput& in)
     PoseSeedArgs sa{};
     if (!planned) {
         // Frame(gray,depth,sigma,K,levels,culls); a big batch's raw frames: split, the top level and the depth maps on the side stream
-        const bool halves = !built && build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, nullptr, nullptr, split_on ? &split : nullptr);
+        // (the geometric term reads the tracked frame's depth at every level: no split build while it is on)
+        const bool halves = !built && build_pyramid(fs[target], fin, stream, /*keep_sigma=*/false, nullptr, nullptr,
+                                                    (split_on && !trk.geo.on) ? &split : nullptr);
         DVO_HIP(split.err);
         if (cur >= 0) {
             if (guess.on()) { sa = guess.args(trk.state.as<SeqState>(), nullptr, DVO_SEQ_TRACK, trk.xi_out.as<float>(), nullptr); trk.seed = &sa; }

@@ -256,6 +256,18 @@ struct AffineBrightness {
     void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
 };
 
+// The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  Allocated by the first enable.  While
+// on, the tracker runs the plan of launch pairs (Tracker::lv_rw): k_track_gn_z + k_gn_solve_z on every level, on the tracked frame's
+// own depth and weight maps.
+struct GeometricTerm {
+    bool on = false;        // the next push runs with the term
+    bool ready = false;     // the last push did
+    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every record is zero)
+    float weight = 0.0f, max_diff = 0.0f;
+    int log_its = 0;        // iterations per level of the geometric log
+    DevBuf last, log;       // [n_seq][4] (n_geo, mean_sq, tracked, 0); [n_seq][levels][log_its][2] (n_geo, S29)
+};
+
 // How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
 // copy the geometry from here into every argument block, and the launchers take the kernel instance from here.
 struct LevelPlan {
@@ -301,6 +313,14 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
     int margin_plain = 0;
     void use_plan(bool robust);
+    GeometricTerm geo;
+    int set_geometric(const dvo_geometric_config* c, hipStream_t s);    // validated by the caller; nullptr / OFF: off
+    int last_geometric(dvo_geometric_record* rec, hipStream_t s) const;
+    int last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const;
+    // the pair of one iteration with the geometric term; ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray
+    // before gn_view)
+    void launch_gn_z(const GnArgs& ga, const float* ref_z, int level, int count, hipStream_t s, int grid_seqs = 0) const;
+    void launch_solve_z(const SolveArgs& sa, int count, hipStream_t s, double* sums_out = nullptr) const;
     AffineBrightness aff;
     int set_affine(const dvo_affine_config* c, hipStream_t s);          // validated by the caller; nullptr / OFF: off
     int set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s);

@@ -245,6 +245,25 @@ void launch_track_gn_ab(const struct GnArgs& a, const RobustGn& r, const AffineG
                         int grid_seqs = 0);
 void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s);
 
+// The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  While on, GnArgs::ref_depth / ref_wgt /
+// wgt_const hold the TRACKED frame's own maps and the reference's depth is sampled at the warped position: its base comes in this
+// block, a further kernel argument (GnArgs keeps its layout).  The two new sums S29 = sum rg^2 and S30 = n_geo take slots 29 and 30
+// of the 32-float partial row.
+struct GeoGn {         // last argument of k_track_gn_z / k_track_gn_z_cam
+    const float* ref_z;   // [n_seq of the launch][h][w] reference depth of the level, indexed like GnArgs::ref_gray
+    float weight;         // >= 0
+    float max_diff;       // > 0: |rz| above it has no geometric row
+};
+struct GeoSolve {      // last argument of k_gn_solve_z
+    float* last;          // [n_seq][2]: (n_geo, S29) of each sequence's last evaluated iteration ((0, 0): not tracked), like SolveArgs::state
+    float* log;           // optional [n_seq][levels][log_its][2]: (n_geo, S29) of every logged iteration
+    double* sums_out;     // optional [n_seq][2] (dvo_op_gn_step_geometric): (n_geo, S29) in double
+    int levels, log_its;
+};
+// the twins of launch_track_gn / launch_gn_solve with the geometric term (launch pairs only, no mask)
+void launch_track_gn_z(const struct GnArgs& a, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
+void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s);
+
 // k_track_persist: the whole of Tracker::track for ONE sequence in one launch (a dvo_vo handle).
 struct PersistLevel {
     const float* obj_gray; const float* ref_gray; const float* ref_depth; const float* ref_wgt;

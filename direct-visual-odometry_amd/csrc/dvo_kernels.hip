@@ -952,10 +952,14 @@ struct GnTileLds {
 // code it always was).
 // AB: the residual is taken against the compensated brightness fmaf(ab.a, I1, ab.b) and the tile's brightness moments go to mom_row
 // through mred (k_track_gn_ab; unused otherwise, and AB = false is the code it always was).
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false, bool AB = false>
+// GEO: a.ref_depth / a.ref_wgt are the tracked frame's own maps, and a contributing pixel of the fast path whose 12 reference-depth
+// taps (geo.ref_z, the gray taps' byte offsets) pass the gates adds a geometric row to slots 0..26 and to slots 29 / 30 of the partial
+// row, reduced through mred (k_track_gn_z; unused otherwise, and GEO = false is the code it always was).
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false, bool AB = false, bool GEO = false>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
                                         float* out_row, const Intr& cam, const RobustEntry& rob = RobustEntry{},
-                                        const AffineEntry& ab = AffineEntry{}, float* mom_row = nullptr, float (*mred)[8] = nullptr);
+                                        const AffineEntry& ab = AffineEntry{}, float* mom_row = nullptr, float (*mred)[8] = nullptr,
+                                        const GeoGn& geo = GeoGn{});
 
 #if !defined(DVO_GN_WAVES)
 #define DVO_GN_WAVES 6   /* waves per SIMD the hot variants are compiled for: 6 = up to 84 VGPRs (78 used, no scratch); at 7 (72 VGPRs) the border sampler spills 24 bytes per lane: 54 MB of extra HBM writes per full-batch launch for the same speed (profiles/r03_patch_sampler_ab.txt) */
@@ -1141,10 +1145,106 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_AB_WAVES : 
     track_gn_ab_body<PPT, G, T2D, true, ROB>(a, rg, ag, lds, mred);
 }
 
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB>
+// k_track_gn_z / k_track_gn_z_cam: k_track_gn / k_track_gn_cam with the geometric (depth) term of a sensor-depth batch
+// (dvo_batch_set_geometric): the same tiles, lists, gates and samplers on the tracked frame's own depth and weight,
+// plus twelve reference-depth taps per fast-path pixel.  New kernels beside the others, which stay as they are; no MASK instances.
+#if !defined(DVO_GN_Z_WAVES)
+#define DVO_GN_Z_WAVES 3   /* the hot <4, 1|2, *> instances keep 12 more taps per pixel in flight and two more accumulators: 133-144 VGPRs, no scratch at 3 waves (168 allocatable); at 4 waves (128) they spill 8-48 bytes per lane, at 5 (96) 128-172, at 6 (80) 196-228 */
+#endif
+__device__ __forceinline__ float max3_raw(float a, float b, float c)   // (min3_raw's counterpart)
+{
+    float m;
+    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c));
+    return m;
+}
+// The geometric row of one fast-path pixel (include/dvo.h, dvo_batch_set_geometric).  ok: the pixel contributes its photometric row;
+// t: the 12 reference-depth taps of its footprint; Zw: the transformed point's z.  A pixel without a geometric row has its operands
+// selected to zero first and adds exact zeros, so a NaN or inf tap never reaches a sum.
+__device__ __forceinline__ void geo_pixel(const Intr& k, const GeoGn& geo, const float min_depth, const bool ok, const int x, const int y,
+                                          const float d, const float iz, const float wgt, const Taps& t, const float u, const float v,
+                                          const int x0, const int y0, const float Zw, Acc29& acc, float& S29, float& S30)
+{
+    const float hx = u - (float)x0, vy = v - (float)y0;
+    const float Zs = blend4(t.rb.y, t.rb.z, t.rc.y, t.rc.z, hx, vy);
+    const float gzx = blend4(t.rb.z - t.rb.x, t.rb.w - t.rb.y, t.rc.z - t.rc.x, t.rc.w - t.rc.y, hx, vy);
+    const float gzy = blend4(t.rc.y - t.ra.x, t.rc.z - t.ra.y, t.rd.x - t.rb.y, t.rd.y - t.rb.z, hx, vy);
+    // all 12 taps finite and >= min_depth: the smallest and the largest tap, and a probe that a NaN or inf tap poisons (0 * inf = NaN)
+    const float mn = min3_raw(min3_raw(min3_raw(t.ra.x, t.ra.y, t.rd.x), min3_raw(t.rb.x, t.rb.y, t.rb.z), min3_raw(t.rc.x, t.rc.y, t.rc.z)),
+                              min3_raw(t.rd.y, t.rb.w, t.rc.w), t.rd.y);
+    const float mx = max3_raw(max3_raw(max3_raw(t.ra.x, t.ra.y, t.rd.x), max3_raw(t.rb.x, t.rb.y, t.rb.z), max3_raw(t.rc.x, t.rc.y, t.rc.z)),
+                              max3_raw(t.rd.y, t.rb.w, t.rc.w), t.rd.y);
+    const float probe = (Zs + gzx) + gzy;
+    const float rz = Zs - Zw;
+    const bool on = ok & (mn >= min_depth) & (mx < __builtin_inff()) & (probe == probe) & (fabsf(rz) <= geo.max_diff);   // false for NaN
+    float Jz[6], r_, rw_;
+    gn_jacobian_pre(k, x, y, d, iz, wgt, gzx, gzy, 0.0f, 0.0f, Jz, r_, rw_);
+    float X, Y, Z;
+    back_project(k, (float)x, (float)y, d, X, Y, Z);
+    Jz[2] = Jz[2] - 1.0f;
+    Jz[3] = Jz[3] - Y;
+    Jz[4] = Jz[4] + X;
+    const float lam = geo.weight * (iz * iz);
+    float Jg[6];
+#pragma unroll
+    for (int q = 0; q < 6; q++) Jg[q] = on ? lam * Jz[q] : 0.0f;
+    const float rg = on ? lam * rz : 0.0f;
+    const float rgw = on ? rg * wgt : 0.0f;
+    int idx = 0;
+#pragma unroll
+    for (int p = 0; p < 6; p++)
+#pragma unroll
+        for (int q = p; q < 6; q++) {
+            acc.a[idx] = fmaf(Jg[p], Jg[q], acc.a[idx]);
+            idx++;
+        }
+#pragma unroll
+    for (int p = 0; p < 6; p++) acc.a[21 + p] = fmaf(Jg[p], rgw, acc.a[21 + p]);
+    S29 = fmaf(rg, rg, S29);
+    S30 += on ? 1.0f : 0.0f;
+}
+template <int PPT, int G, bool T2D, bool PCAM>
+__device__ __forceinline__ void track_gn_z_body(const GnArgs& a, const GeoGn& zg, GnTileLds<PPT>& lds, float (*mred)[8])
+{
+    auto clear_next = [&]() {
+        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
+            if (threadIdx.x == 0) *a.next_count = 0;
+        }
+    };
+    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
+    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
+    const int tile_id = xcd * t8 + tile_in_xcd;
+    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
+        clear_next();
+        return;
+    }
+    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
+    const int seq = a.list ? a.list[4 + slot] : slot;
+    const Pose pose = a.state[seq].pose;
+    Intr cam = a.k;
+    if constexpr (PCAM) cam = a.seq_k[seq];
+    gn_tile<PPT, G, false, T2D, PCAM, false, false, true>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam,
+                                                          RobustEntry{}, AffineEntry{}, nullptr, mred, zg);
+    clear_next();
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_Z_WAVES : 1) k_track_gn_z(GnArgs a, GeoGn zg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_z_body<PPT, G, T2D, false>(a, zg, lds, mred);
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_Z_WAVES : 1) k_track_gn_z_cam(GnArgs a, GeoGn zg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_z_body<PPT, G, T2D, true>(a, zg, lds, mred);
+}
+
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
                                         float* out_row, const Intr& cam, const RobustEntry& rob, const AffineEntry& ab, float* mom_row,
-                                        float (*mred)[8])
+                                        float (*mred)[8], const GeoGn& geo)
 {
     float (&red)[4][32] = lds.red;
     int (&slow_q)[4][PPT * 64] = lds.slow_q;
@@ -1163,6 +1263,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
     Acc29 acc;
     acc.zero();
     float M[DVO_AFFINE_MOMENTS] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // AB: the thread's brightness moments (affine_pixel)
+    float S29 = 0.0f, S30 = 0.0f;                                    // GEO: sum rg^2 and n_geo of the thread (geo_pixel)
     // G pixels per thread have their gathers in flight together (memory-level parallelism hides the L2/HBM latency)
     static_assert(PPT % G == 0, "PPT must be a multiple of G");
     // pixel k of this thread: coordinates (xA, yA), linear index iA (clamped into the image), inA = it exists
@@ -1215,6 +1316,8 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
         int xs[G], ys[G], x0[G], y0[G];
         bool gate[G], inter[G];
         Taps t[G];
+        Taps tz[GEO ? G : 1];   // GEO: the reference-depth taps of the same footprints
+        float Zw[GEO ? G : 1];  // GEO: the transformed point's z
 #pragma unroll
         for (int k = 0; k < G; k++) {
             d[k] = dA[g0 + k]; I1[k] = I1A[g0 + k]; wg[k] = wgA[g0 + k];
@@ -1227,6 +1330,12 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             if (a.prm.crop) crop_ok = (xs[k] >= 20) & (xs[k] <= 140) & (ys[k] >= 20) & (ys[k] <= 100);  // wave-uniform branch
             gate[k] = inA[g0 + k] & crop_ok & !(d[k] < a.prm.min_depth) & !is_invalid(I1[k]);
             iz[k] = recip_gated(d[k], gate[k]);   // 1.0f / depth (optimize.cpp:70-74) of the pixels that can contribute
+            if constexpr (GEO) {   // warp()'s three operations, keeping the z they form
+                float X, Y, Z, Xw, Yw;
+                back_project(seq_intr<PCAM>(a, cam), (float)xs[k], (float)ys[k], d[k], X, Y, Z);
+                transform(pose, X, Y, Z, Xw, Yw, Zw[k]);
+                project(seq_intr<PCAM>(a, cam), Xw, Yw, Zw[k], u[k], v[k]);
+            } else
             warp(pose, seq_intr<PCAM>(a, cam), (float)xs[k], (float)ys[k], d[k], u[k], v[k]);
             inter[k] = gate[k] & (u[k] >= 1.0f) & (v[k] >= 1.0f) & (u[k] < wlim) & (v[k] < hlim);  // false for NaN
             x0[k] = inter[k] ? (int)u[k] : 1;
@@ -1239,6 +1348,13 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             t[k].rb = *reinterpret_cast<const f4u*>(rb8 + (c - 4u));
             t[k].rc = *reinterpret_cast<const f4u*>(rb8 + (c + uw - 4u));
             t[k].rd = *reinterpret_cast<const f2u*>(rb8 + (c + 2u * uw));
+            if constexpr (GEO) {   // the same byte offsets into the reference depth: in flight with the gray taps
+                const char* zb8 = reinterpret_cast<const char*>(geo.ref_z + img_off);
+                tz[k].ra = *reinterpret_cast<const f2u*>(zb8 + (c - uw));
+                tz[k].rb = *reinterpret_cast<const f4u*>(zb8 + (c - 4u));
+                tz[k].rc = *reinterpret_cast<const f4u*>(zb8 + (c + uw - 4u));
+                tz[k].rd = *reinterpret_cast<const f2u*>(zb8 + (c + 2u * uw));
+            }
         }
         // The G pixels are sampled in ONE straight-line block (independent chains interleave: ILP), the rare generic
         // sampler runs in a single separate region, then Jacobians and sums again in one straight-line block.
@@ -1288,6 +1404,9 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
                 acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
             } else
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
+            if constexpr (GEO)   // after the pixel's photometric add (ok implies the fast path: interior footprint, 12 valid gray taps)
+                geo_pixel(seq_intr<PCAM>(a, cam), geo, a.prm.min_depth, ok, xs[k], ys[k], d[k], iz[k], wg[k], tz[k], u[k], v[k], x0[k], y0[k],
+                          Zw[k], acc, S29, S30);
             if (MASK && ok) a.mask[img_off + (size_t)(ys[k] * w + xs[k])] = 1;
         }
     }
@@ -1350,11 +1469,22 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
         }
         if (lane == 0 && !ROB) mred[wave][0] = 0.0f;
     }
+    if constexpr (GEO) {   // slots 29 and 30: the moments' butterfly (every lane ends with the same bits), lane 0 publishes
+        float v29 = S29, v30 = S30;
+        v29 += __shfl_xor(v29, 32); v29 += __shfl_xor(v29, 16); v29 += __shfl_xor(v29, 8);
+        v29 += __shfl_xor(v29, 4); v29 += __shfl_xor(v29, 2); v29 += __shfl_xor(v29, 1);
+        v30 += __shfl_xor(v30, 32); v30 += __shfl_xor(v30, 16); v30 += __shfl_xor(v30, 8);
+        v30 += __shfl_xor(v30, 4); v30 += __shfl_xor(v30, 2); v30 += __shfl_xor(v30, 1);
+        if (lane == 0) { mred[wave][0] = v29; mred[wave][1] = v30; }
+    }
     __syncthreads();
     if (threadIdx.x < 32) {
         const int c = threadIdx.x;
         float s = 0.0f;
         if (c < 29) s = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
+        if constexpr (GEO) {   // the four waves in wave order, into the row's free slots
+            if (c == 29 || c == 30) s = ((mred[0][c - 29] + mred[1][c - 29]) + mred[2][c - 29]) + mred[3][c - 29];
+        }
         out_row[c] = s;
     }
     if constexpr (AB) {   // the four waves in wave order, as above (wave 1 stores: the two rows go out side by side)
@@ -1812,6 +1942,67 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_ab(SolveArgs a,
             rs.table[my_seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
         }
     }
+}
+
+// k_gn_solve_z: k_gn_solve for a sensor-depth batch with the geometric term -- line for line k_gn_solve (a twin, so that kernel stays
+// as it is), summing slots 29 (sum rg^2) and 30 (n_geo) of the partial rows beside the 29 in the same fixed order; the serial thread
+// records them (last, and the geometric log at the iteration's slot of the track log).  solve_finish reads slots 0..28 only: it solves
+// the combined H and g, and n_valid, the residual and the stop tests stay photometric.
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_z(SolveArgs a, GeoSolve z)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
+    if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
+    const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
+    const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
+    int my_seq = 0;
+    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
+    SeqState& st = a.state[my_seq];
+    int was_active = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (serial) {
+        was_active = st.active; it_prev = st.iter;
+#pragma unroll
+        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
+#pragma unroll
+        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
+    }
+    const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
+    const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
+    if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
+        const int ws = team >> 2, wg = team & 3;
+        if (ws < n_in && c < 31) {
+            const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
+            part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {
+            const int ts = threadIdx.x >> 5;
+            tot[ts][c] = (ts < n_in && c < 31) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
+        }
+    } else if (t_slot < n_in && c < 31) {
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
+    } else if (c >= 31) {
+        tot[team][c] = 0.0;
+    }
+    __syncthreads();
+    if (!serial) return;
+    if (!a.ignore_active && was_active == 0) return;
+    Pose np;
+    (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
+    const double S29 = tot[threadIdx.x][29], n_geo = tot[threadIdx.x][30];
+    if (z.sums_out) { z.sums_out[2 * (size_t)my_seq] = n_geo; z.sums_out[2 * (size_t)my_seq + 1] = S29; }
+    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    if (z.log && it < z.log_its) {
+        float* lg = z.log + (((size_t)my_seq * z.levels + a.level) * z.log_its + it) * 2;
+        lg[0] = (float)n_geo; lg[1] = (float)S29;
+    }
+    float* last = z.last + 4 * (size_t)my_seq;   // (n_geo, mean_sq, 1 = tracked, 0)
+    last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
 }
 
 // k_affine_begin: the AffineEntry table at the start of a tracking call, one thread per sequence.  ESTIMATE: every sequence starts at
@@ -3082,6 +3273,44 @@ void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSo
     SolveArgs b = a;
     b.n_seq = n_seq;
     hipLaunchKernelGGL(k_gn_solve_ab, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, r, f);
+}
+
+template <int PPT, int G>
+static void launch_track_gn_z_t(const GnArgs& a, const GeoGn& z, bool t2d, unsigned tiles, hipStream_t s)
+{
+    const dim3 grid((tiles + 7u) & ~7u);
+    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+        if (a.seq_k) hipLaunchKernelGGL((k_track_gn_z_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
+        else hipLaunchKernelGGL((k_track_gn_z<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
+    });
+}
+
+void launch_track_gn_z(const GnArgs& a0, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
+{
+    GnArgs a = a0;
+    a.n_seq = n_seq; a.mask = nullptr;
+    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
+    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
+    if (grid == 0) grid = 8;
+    switch (ppt * 10 + group) {
+        case 11: launch_track_gn_z_t<1, 1>(a, z, t2d, grid, s); break;
+        case 21: launch_track_gn_z_t<2, 1>(a, z, t2d, grid, s); break;
+        case 22: launch_track_gn_z_t<2, 2>(a, z, t2d, grid, s); break;
+        case 41: launch_track_gn_z_t<4, 1>(a, z, t2d, grid, s); break;
+        case 42: launch_track_gn_z_t<4, 2>(a, z, t2d, grid, s); break;
+        case 44: launch_track_gn_z_t<4, 4>(a, z, t2d, grid, s); break;
+        case 81: launch_track_gn_z_t<8, 1>(a, z, t2d, grid, s); break;
+        case 82: launch_track_gn_z_t<8, 2>(a, z, t2d, grid, s); break;
+        default: launch_track_gn_z_t<8, 4>(a, z, t2d, grid, s); break;
+    }
+}
+
+void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s)
+{
+    SolveArgs b = a;
+    b.n_seq = n_seq;
+    hipLaunchKernelGGL(k_gn_solve_z, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, z);
 }
 
 void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s)

@@ -103,6 +103,30 @@ AFFINE_LOG_DTYPE = np.dtype({"names": [f[0] for f in AffineLog._fields_],
                              "itemsize": C.sizeof(AffineLog)})
 
 
+class GeometricConfig(C.Structure):
+    """dvo_geometric_config (include/dvo.h): the geometric (depth) term of a sensor-depth batch."""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("weight", C.c_float), ("max_diff", C.c_float)]
+
+
+class GeometricRecord(C.Structure):
+    """dvo_geometric_record (include/dvo.h): n_geo and S29 / n_geo of the finest level's last iteration."""
+    _fields_ = [("n_geo", C.c_int), ("mean_sq", C.c_float)]
+
+
+class GeometricLog(C.Structure):
+    """dvo_geometric_log (include/dvo.h): n_geo and (float)S29 of every logged iteration, indexed like TrackLog."""
+    _fields_ = [("struct_size", C.c_int), ("levels", C.c_int), ("n_iter", C.c_int * MAX_LEVELS),
+                ("n_geo", (C.c_int * MAX_ITERATIONS) * MAX_LEVELS), ("sum_sq", (C.c_float * MAX_ITERATIONS) * MAX_LEVELS)]
+
+
+GEOMETRIC_RECORD_DTYPE = np.dtype([("n_geo", np.int32), ("mean_sq", np.float32)])
+GEOMETRIC_LOG_DTYPE = np.dtype({"names": [f[0] for f in GeometricLog._fields_],
+                                "formats": [np.int32, np.int32, (np.int32, MAX_LEVELS), (np.int32, (MAX_LEVELS, MAX_ITERATIONS)),
+                                            (np.float32, (MAX_LEVELS, MAX_ITERATIONS))],
+                                "offsets": [getattr(GeometricLog, f[0]).offset for f in GeometricLog._fields_],
+                                "itemsize": C.sizeof(GeometricLog)})
+
+
 class GnProfile(C.Structure):
     _fields_ = [("gn_ms", C.c_double), ("gn_launches", C.c_uint64), ("gn_pixels", C.c_uint64),
                 ("gn_iterations", C.c_uint64)]
@@ -150,6 +174,8 @@ EXPORTS = [
     "dvo_batch_set_robust_weights", "dvo_batch_set_robust_scales", "dvo_batch_last_robust_scales", "dvo_op_gn_step_robust",
     "dvo_batch_set_affine_brightness", "dvo_batch_set_affine_rows", "dvo_batch_last_affine", "dvo_batch_last_affine_log",
     "dvo_op_gn_step_affine",
+    "dvo_geometric_config_default", "dvo_batch_set_geometric", "dvo_batch_last_geometric", "dvo_batch_last_geometric_log",
+    "dvo_op_gn_step_geometric",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -165,6 +191,8 @@ ROBUST_NONE, ROBUST_HUBER, ROBUST_STUDENT_T = 0, 1, 2
 ROBUST_SCALE_ADAPTIVE, ROBUST_SCALE_GIVEN = 0, 1
 # affine brightness compensation (Batch / MonoBatch .set_affine_brightness): include/dvo.h
 AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
+# the geometric (depth) term (Batch.set_geometric): include/dvo.h
+GEOMETRIC_OFF, GEOMETRIC_ON = 0, 1
 
 _lib = None
 
@@ -337,6 +365,29 @@ def op_gn_step_affine(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, a,
     return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
                 xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
                 xi_next=np.array(out.xi_next[:], np.float32), moments=mom, next_ab=nxt)
+
+
+def geometric_default_config():
+    """dvo_geometric_config_default: ON, weight 10, max_diff 0.1 m"""
+    c = GeometricConfig()
+    lib().dvo_geometric_config_default(C.byref(c))
+    return c
+
+
+def op_gn_step_geometric(obj_gray, obj_depth, obj_sigma, ref_gray, ref_depth, K, xi, level, weight, max_diff, cfg=None, dev=0):
+    """optimize() with the geometric term (dvo_op_gn_step_geometric, include/dvo.h): the tracked frame's gray, depth and sigma, the
+    reference's gray and depth; adds `n_geo` and `sum_sq` (S29 in float64)."""
+    obj_gray = f32(obj_gray); obj_depth = f32(obj_depth); obj_sigma = f32(obj_sigma); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = GnResult()
+    sums = np.zeros(2, np.float64)
+    _check(lib().dvo_op_gn_step_geometric(dev, C.byref(cfg) if cfg is not None else None, fp(obj_gray), fp(obj_depth), fp(obj_sigma),
+                                          fp(ref_gray), fp(ref_depth), w, h, fp(K), fp(xi), level, C.c_float(weight),
+                                          C.c_float(max_diff), C.byref(out), sums.ctypes.data_as(C.POINTER(C.c_double))))
+    return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
+                xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
+                xi_next=np.array(out.xi_next[:], np.float32), n_geo=int(sums[0]), sum_sq=float(sums[1]))
 
 
 def track(obj_gray, ref_gray, ref_depth, ref_sigma, K, levels, culls, cfg=None, dev=0):
@@ -752,6 +803,32 @@ class _AffineBrightness:
                     prime_a=np.float32(rec["prime_a"]), prime_b=np.float32(rec["prime_b"]))
 
 
+class _GeometricTerm:
+    """The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric, include/dvo.h)."""
+
+    def set_geometric(self, mode=GEOMETRIC_ON, weight=10.0, max_diff=0.1):
+        """GEOMETRIC_ON: every later push adds a depth-error row per pixel, on the tracked frame's own depth; GEOMETRIC_OFF or None: off."""
+        if mode is None:
+            _check(lib().dvo_batch_set_geometric(self._p, None))
+            return
+        c = GeometricConfig(C.sizeof(GeometricConfig), int(mode), float(weight), float(max_diff))
+        _check(lib().dvo_batch_set_geometric(self._p, C.byref(c)))
+
+    def last_geometric(self):
+        """record array [n_seq] (n_geo, mean_sq) of the finest level's last iteration at the last push (zeros: not tracked); synchronises."""
+        rec = np.zeros(self.n_seq, GEOMETRIC_RECORD_DTYPE)
+        _check(lib().dvo_batch_last_geometric(self._p, rec.ctypes.data_as(C.POINTER(GeometricRecord))))
+        return rec
+
+    def last_geometric_log(self, seq):
+        """dict of n_geo and sum_sq of every logged iteration of `seq` at the last push (dvo_geometric_log); synchronises."""
+        lg = GeometricLog()
+        lg.struct_size = C.sizeof(GeometricLog)
+        _check(lib().dvo_batch_last_geometric_log(self._p, int(seq), C.byref(lg)))
+        rec = np.frombuffer(lg, GEOMETRIC_LOG_DTYPE)[0]
+        return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), n_geo=rec["n_geo"].copy(), sum_sq=rec["sum_sq"].copy())
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -765,7 +842,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls

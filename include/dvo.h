@@ -601,6 +601,67 @@ int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg);
 int dvo_batch_set_affine_rows(dvo_batch* b, const float* ab, int ab_on_device);   /* [n_seq][2], GIVEN mode; NULL clears */
 int dvo_batch_last_affine(dvo_batch* b, float* ab);                               /* [n_seq][2], host, synchronises */
 int dvo_batch_last_affine_log(dvo_batch* b, int seq, dvo_affine_log* log);        /* host, synchronises */
+/* ---- geometric (depth) term: sensor-depth batches only ---------------------------------------------------------------------------
+ * By default a sensor-depth batch uses a frame's depth map only as the lever arm of the photometric residual, and the depth at pixel
+ * x is the REFERENCE's (the reference's own approximation, GnArgs::ref_depth).  dvo_batch_set_geometric makes every later push add a
+ * depth-error row per pixel: dense RGB-D alignment.  All arithmetic is float32 and IEEE, with no contraction beyond the fmaf()s named.
+ * While on, pixel x of the TRACKED frame uses that frame's own values at x: d = the tracked frame's depth, wgt = the weight of the
+ * tracked frame's own sigma (or its constant for raw frames), I1 = the tracked frame's gray.  (u, v) and Zw are the outputs of
+ * warp's operations (back_project, transform, project): Zw is the transformed point's z.  I2, gx, gy are the samplers on the
+ * reference gray.  The photometric row is the plain estimator's on these inputs, bit for bit: the gates, the samplers and the
+ * Jacobian are unchanged, slots 0..28 keep their meaning, and n_valid, the residual and the stop tests stay photometric.
+ * A contributing pixel also gets a geometric row when 1 <= u < w-2 and 1 <= v < h-2, all 12 gray taps of its footprint are valid
+ * (the fast sampler decides it), all 12 taps D** of the REFERENCE depth at the same footprint are finite and >= min_depth, and
+ * fabsf(rz) <= max_diff, where with hx = u - (int)u, vy = v - (int)v and blend4 the bilinear blend of the gray sampler:
+ *   Zs  = blend4(D00, D01, D10, D11, hx, vy)
+ *   gzx = blend4 of the four unhalved horizontal differences, gzy = blend4 of the four unhalved vertical differences (the gray
+ *         sampler's three calls, applied to the depth taps)
+ *   rz  = Zs - Zw
+ *   Jp[6] = the photometric Jacobian formula with (gx, gy) := (gzx, gzy) (gn_jacobian_pre(k, x, y, d, iz, ., gzx, gzy, ., .))
+ *   Jz = Jp except Jz[2] = Jp[2] - 1, Jz[3] = Jp[3] - Y, Jz[4] = Jp[4] + X, (X, Y) the back-projected point: the z-row of [I | -X^]
+ *        under the unwarped-point convention and sign of the photometric J
+ *   lam = weight * (iz * iz);  Jg[q] = lam * Jz[q];  rg = lam * rz;  rgw = rg * wgt      (iz = 1 / d: an inverse-depth-like error)
+ * Sums, after the pixel's photometric add: slots 0..26 take (Jg, rgw) in the photometric fmaf shape (H[p][q] = fmaf(Jg[p], Jg[q], H),
+ * g[p] = fmaf(Jg[p], rgw, g)); slots 27 and 28 are untouched; S29 = fmaf(rg, rg, S29) and S30 += 1 (n_geo).  A pixel without a
+ * geometric row adds exact zeros: its operands are selected to zero first, so a NaN or inf tap never reaches a sum.  Pixels of the
+ * border band and pixels with an INVALID gray tap (the generic sampler's) keep their photometric row and never get a geometric one.
+ * S29 and S30 are reduced in a fixed order (wave, the four waves in wave order, the tiles in double), the same under every schedule.
+ * weight = 0 is allowed: the 27 sums are then the plain estimator's on own-depth inputs, bit for bit.  The 6x6 solve, the track log
+ * and the quality record keep their arithmetic: they see the combined H and g.
+ * Takes effect from the next push; cfg == NULL or mode == DVO_GEOMETRIC_OFF turns it off again, and the batch then runs exactly the
+ * launches it ran before.  A batch that never calls this runs exactly the launches it always ran.  While on, every level runs launch
+ * pairs (k_track_gn_z + k_gn_solve_z) whatever track_fused_tiles, gn_use_lds_patch and track_single_launch say, and a big batch's
+ * raw frames are not built in two halves.
+ * dvo_batch_last_geometric: rec[n_seq] (host, synchronises) -- n_geo and mean_sq = S29 / n_geo (0 when n_geo is 0) of the finest
+ * level's last iteration of the last push; zeros for a sequence that did not track at that push.  dvo_batch_last_geometric_log:
+ * n_geo and (float)S29 of every logged iteration, indexed like dvo_track_log; empty (n_iter all 0) for a sequence that did not track.
+ * Errors, returned before anything is enqueued: a NULL handle, struct_size != sizeof, a mode outside the set, a weight that is not
+ * finite and >= 0, a max_diff that is not finite and > 0, a mono batch, robust weights or affine compensation on (in either order of
+ * the two calls: dvo_batch_set_robust_weights / dvo_batch_set_affine_brightness refuse while this is on) -> DVO_ERR_BAD_ARGUMENT; a
+ * read before a push that ran with the feature on -> DVO_ERR_NOT_READY.  dvo_vo handles have no geometric term. */
+#define DVO_GEOMETRIC_OFF 0
+#define DVO_GEOMETRIC_ON  1
+typedef struct dvo_geometric_config {
+    int   struct_size;    /* sizeof(dvo_geometric_config) */
+    int   mode;           /* DVO_GEOMETRIC_* */
+    float weight;         /* >= 0, finite */
+    float max_diff;       /* > 0, finite, metres: |rz| above it has no geometric row */
+} dvo_geometric_config;
+typedef struct dvo_geometric_record {
+    int   n_geo;          /* geometric rows of the finest level's last iteration */
+    float mean_sq;        /* S29 / n_geo */
+} dvo_geometric_record;
+typedef struct dvo_geometric_log {
+    int   struct_size;    /* sizeof(dvo_geometric_log), set by the caller */
+    int   levels;
+    int   n_iter[DVO_MAX_LEVELS];
+    int   n_geo[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];
+    float sum_sq[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];   /* (float)S29 */
+} dvo_geometric_log;
+void dvo_geometric_config_default(dvo_geometric_config* cfg);                      /* ON, weight = 10, max_diff = 0.1 */
+int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg);       /* sensor-depth batches; from the next push on */
+int dvo_batch_last_geometric(dvo_batch* b, dvo_geometric_record* rec);            /* [n_seq], host, synchronises */
+int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log);  /* host, synchronises */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */
@@ -654,6 +715,12 @@ int dvo_op_gn_step_affine(int dev, const dvo_config* cfg, const float* obj_gray,
                           const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
                           const float xi[6], int level, int kind, float param, float s2, float a, float b,
                           dvo_gn_result* out, double moments[5], float next_ab[2]);
+/* The pair with the geometric term (dvo_batch_set_geometric) run once on host pointers: obj_* are the tracked frame's gray, depth and
+ * sigma, ref_* the reference's gray and depth.  sums = (n_geo, S29) in double. */
+int dvo_op_gn_step_geometric(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth,
+                             const float* obj_sigma, const float* ref_gray, const float* ref_depth, int w, int h,
+                             const float K[9], const float xi[6], int level, float weight, float max_diff,
+                             dvo_gn_result* out, double sums[2]);
 /* Tracker::track, src/track/tracker.cpp:22-85, on full-resolution frames (pyramids built on device). */
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                  const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],

@@ -218,6 +218,25 @@ public:
         check(dvo_batch_last_affine_log(b_, seq, &lg));
         return lg;
     }
+    // the geometric (depth) term from the next push on (dvo_batch_set_geometric): mode DVO_GEOMETRIC_OFF turns it off
+    void setGeometric(int mode = DVO_GEOMETRIC_ON, float weight = 10.0f, float max_diff = 0.1f)
+    {
+        dvo_geometric_config c{(int)sizeof(dvo_geometric_config), mode, weight, max_diff};
+        check(dvo_batch_set_geometric(b_, &c));
+    }
+    std::vector<dvo_geometric_record> lastGeometric()   // [n_seq]
+    {
+        std::vector<dvo_geometric_record> out(n_);
+        check(dvo_batch_last_geometric(b_, out.data()));
+        return out;
+    }
+    dvo_geometric_log lastGeometricLog(int seq)
+    {
+        dvo_geometric_log lg{};
+        lg.struct_size = (int)sizeof lg;
+        check(dvo_batch_last_geometric_log(b_, seq, &lg));
+        return lg;
+    }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
