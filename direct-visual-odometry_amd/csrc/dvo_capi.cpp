@@ -880,23 +880,12 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
         launch_robust_begin(ra, c.s);
     }
-    if (trk.geo.on) {
-        trk.launch_gn_z(ga, zr.as<float>(), level, 1, c.s);
-    } else if (trk.aff.on) {
-        trk.affine_begin(c.s, true, aff_a, aff_b);
-        trk.launch_gn_ab(ga, level, 1, c.s);
-    } else if (trk.rob.on) {
-        trk.launch_gn_rw(ga, level, 1, c.s);
-    } else {
-        trk.launch_gn(ga, level, 1, c.s);
-    }
+    if (trk.aff.on) trk.affine_begin(c.s, true, aff_a, aff_b);
+    trk.launch_gn_term(ga, level, 1, c.s, 0, zr.as<float>());
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    if (trk.geo.on) trk.launch_solve_z(sa, 1, c.s, zs.as<double>());
-    else if (trk.aff.on) trk.launch_solve_ab(sa, 1, c.s, false, false, mom.as<double>(), true);
-    else if (trk.rob.on) trk.launch_solve_rw(sa, 1, c.s, false);
-    else launch_gn_solve(sa, 1, c.s);
+    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true);
     if (trk.aff.on) {
         DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));

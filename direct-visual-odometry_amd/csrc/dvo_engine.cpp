@@ -586,10 +586,16 @@ SolveArgs Tracker::solve_args(int level, int q0, int ignore_active, SolveRows ro
     return a;
 }
 
-void Tracker::use_plan(bool robust)
+void Tracker::use_plan(bool opt_in_term)
 {
-    for (int l = 0; l < DVO_MAX_LEVELS; l++) lv[l] = robust ? lv_rw[l] : lv_plain[l];
-    tile_margin = robust ? 0 : margin_plain;
+    for (int l = 0; l < DVO_MAX_LEVELS; l++) lv[l] = opt_in_term ? lv_rw[l] : lv_plain[l];
+    tile_margin = opt_in_term ? 0 : margin_plain;
+}
+
+int Tracker::log_iterations() const
+{
+    const int its = cfg.max_iterations > cfg.fixed_iterations ? cfg.max_iterations : cfg.fixed_iterations;
+    return its > DVO_MAX_ITERATIONS ? DVO_MAX_ITERATIONS : (its < 1 ? 1 : its);
 }
 
 int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
@@ -638,24 +644,16 @@ int Tracker::last_robust_scales(float* s2, hipStream_t s) const
 
 void Tracker::robust_end_push(hipStream_t s)
 {
-    if (rob.on && !rob.tracked) (void)hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s);   // nothing tracked at this push
-    rob.ready = rob.on;
-    rob.tracked = false;
-    if (aff.on && !aff.tracked) (void)hipMemsetAsync(aff.last.p, 0, aff.last.bytes, s);   // (affine brightness: the same rule)
-    aff.ready = aff.on;
-    aff.tracked = false;
-    if (geo.on && !geo.tracked) (void)hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s);   // (the geometric term: the same rule)
-    geo.ready = geo.on;
-    geo.tracked = false;
+    rob.end_push(s);
+    aff.end_push(s);
+    geo.end_push(s);
 }
 
 int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
 {
     const bool enable = c && c->mode != DVO_GEOMETRIC_OFF;
     if (enable && !geo.last.p) {
-        geo.log_its = cfg.max_iterations > cfg.fixed_iterations ? cfg.max_iterations : cfg.fixed_iterations;
-        if (geo.log_its > DVO_MAX_ITERATIONS) geo.log_its = DVO_MAX_ITERATIONS;
-        if (geo.log_its < 1) geo.log_its = 1;
+        geo.log_its = log_iterations();
         DVO_TRY(geo.last.alloc(sizeof(float) * 4 * (size_t)n_seq));
         DVO_TRY(geo.log.alloc(sizeof(float) * 2 * (size_t)geo.log_its * (size_t)g.levels * (size_t)n_seq));
         DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
@@ -704,34 +702,29 @@ int Tracker::last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) 
     return DVO_OK;
 }
 
-void Tracker::launch_gn_z(const GnArgs& a, const float* ref_z, int level, int count, hipStream_t s, int grid_seqs) const
+GeoGn Tracker::geo_gn_args(size_t q0, int level, const float* ref_z) const
 {
-    const LevelPlan& L = lv[level];
-    const size_t q0 = (size_t)(a.state - state.as<SeqState>());
     GeoGn z{};
     z.ref_z = ref_z + q0 * (size_t)g.w[level] * g.h[level];   // (gn_view's offset of these sequences)
     z.weight = geo.weight; z.max_diff = geo.max_diff;
-    launch_track_gn_z(a, z, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+    return z;
 }
 
-void Tracker::launch_solve_z(const SolveArgs& sa, int count, hipStream_t s, double* sums_out) const
+GeoSolve Tracker::geo_solve_args(size_t q0, bool log, double* sums_out) const
 {
-    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
     GeoSolve z{};
     z.last = geo.last.as<float>() + 4 * q0;
-    z.log = sa.log ? geo.log.as<float>() + 2 * q0 * (size_t)geo.log_its * g.levels : nullptr;
+    z.log = log ? geo.log.as<float>() + 2 * q0 * (size_t)geo.log_its * g.levels : nullptr;
     z.sums_out = sums_out;
     z.levels = g.levels; z.log_its = geo.log_its;
-    launch_gn_solve_z(sa, z, count, s);
+    return z;
 }
 
 int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
 {
     const bool enable = c && c->mode != DVO_AFFINE_OFF;
     if (enable && !aff.table.p) {
-        aff.log_its = cfg.max_iterations > cfg.fixed_iterations ? cfg.max_iterations : cfg.fixed_iterations;
-        if (aff.log_its > DVO_MAX_ITERATIONS) aff.log_its = DVO_MAX_ITERATIONS;
-        if (aff.log_its < 1) aff.log_its = 1;
+        aff.log_its = log_iterations();
         DVO_TRY(aff.table.alloc(sizeof(AffineEntry) * (size_t)n_seq));
         DVO_TRY(aff.last.alloc(sizeof(float) * 2 * (size_t)n_seq));
         DVO_TRY(aff.prime.alloc(sizeof(float) * 2 * (size_t)n_seq));
@@ -816,35 +809,22 @@ void Tracker::affine_begin(hipStream_t s, bool given_all, float a_all, float b_a
     aff.tracked = true;
 }
 
-void Tracker::launch_gn_ab(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, bool prime) const
+AffineGn Tracker::affine_gn_args(size_t q0, bool prime) const
 {
-    const LevelPlan& L = lv[level];
-    const size_t q0 = (size_t)(a.state - state.as<SeqState>());
-    RobustGn r{};
-    if (rob.on) r.table = rob.table.as<RobustEntry>() + q0;
     AffineGn f{};
     f.table = aff.table.as<AffineEntry>() + q0;
     f.moments = aff.moments.as<float>() + q0 * part_rows * 8;
     f.prime = prime ? 1 : 0;
-    launch_track_gn_ab(a, r, f, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+    return f;
 }
 
-void Tracker::launch_solve_ab(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* moments_out,
-                              bool estimate_once) const
+AffineSolve Tracker::affine_solve_args(size_t q0, bool log, bool prime, double* moments_out, bool estimate_once) const
 {
-    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
-    RobustSolve r{};
-    if (rob.on) {
-        r.table = rob.table.as<RobustEntry>() + q0;
-        r.last_s2 = rob.last.as<float>() + q0;
-        r.kind = rob.kind; r.adaptive = adaptive_scale ? 1 : 0;
-        r.param = rob.param; r.floor2 = rob.floor2;
-    }
     AffineSolve f{};
     f.table = aff.table.as<AffineEntry>() + q0;
     f.moments = aff.moments.as<float>() + q0 * part_rows * 8;
     f.last = aff.last.as<float>() + 2 * q0;
-    f.log = (sa.log && !prime) ? aff.log.as<float>() + 2 * q0 * (size_t)aff.log_its * g.levels : nullptr;
+    f.log = (log && !prime) ? aff.log.as<float>() + 2 * q0 * (size_t)aff.log_its * g.levels : nullptr;
     f.prime_ab = aff.prime.as<float>() + 2 * q0;
     f.moments_out = moments_out;
     f.levels = g.levels; f.log_its = aff.log_its;
@@ -852,26 +832,41 @@ void Tracker::launch_solve_ab(const SolveArgs& sa, int count, hipStream_t s, boo
     f.prime = prime ? 1 : 0;
     f.robust = rob.on ? 1 : 0;
     f.min_pixels = aff.min_pixels; f.min_contrast = aff.min_contrast; f.gain_min = aff.gain_min; f.gain_max = aff.gain_max;
-    launch_gn_solve_ab(sa, r, f, count, s);
+    return f;
 }
 
-void Tracker::launch_gn_rw(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
+RobustSolve Tracker::robust_solve_args(size_t q0, bool adaptive) const
 {
-    const LevelPlan& L = lv[level];
-    RobustGn r{};
-    r.table = rob.table.as<RobustEntry>() + (a.state - state.as<SeqState>());
-    launch_track_gn_rw(a, r, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
-}
-
-void Tracker::launch_solve_rw(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale) const
-{
-    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
     RobustSolve r{};
     r.table = rob.table.as<RobustEntry>() + q0;
     r.last_s2 = rob.last.as<float>() + q0;
-    r.kind = rob.kind; r.adaptive = adaptive_scale ? 1 : 0;
+    r.kind = rob.kind; r.adaptive = adaptive ? 1 : 0;
     r.param = rob.param; r.floor2 = rob.floor2;
-    launch_gn_solve_rw(sa, r, count, s);
+    return r;
+}
+
+void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, const float* ref_z, bool prime) const
+{
+    const LevelPlan& L = lv[level];
+    const size_t q0 = (size_t)(a.state - state.as<SeqState>());
+    const bool t2d = L.tiling.t2d != 0;
+    RobustGn r{};   // (no table: the affine kernels run without weights)
+    if (rob.on) r.table = rob.table.as<RobustEntry>() + q0;
+    if (geo.on) launch_track_gn_z(a, geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
+    else if (aff.on) launch_track_gn_ab(a, r, affine_gn_args(q0, prime), count, L.ppt, L.group, t2d, s, grid_seqs);
+    else if (rob.on) launch_track_gn_rw(a, r, count, L.ppt, L.group, t2d, s, grid_seqs);
+    else launch_gn(a, level, count, s, grid_seqs);
+}
+
+void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* term_out,
+                                bool estimate_once) const
+{
+    const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
+    const RobustSolve r = rob.on ? robust_solve_args(q0, adaptive_scale) : RobustSolve{};
+    if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, sa.log != nullptr, term_out), count, s);
+    else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, sa.log != nullptr, prime, term_out, estimate_once), count, s);
+    else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
+    else launch_gn_solve(sa, count, s);
 }
 
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
@@ -1078,10 +1073,10 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                     // leaves the pose, the log, the lists and the quality record alone
                     GnArgs gp = ga;
                     gp.next_count = nullptr;
-                    launch_gn_ab(gp, level, nq, sk, 0, true);
+                    launch_gn_term(gp, level, nq, sk, 0, nullptr, true);
                     SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
                     sp.list_in = list_prev; sp.result = nullptr;
-                    launch_solve_ab(sp, nq, sk, false, true);
+                    launch_solve_term(sp, nq, sk, false, true);
                 }
                 if (cfg.profile) {
                     if (ev_used == ev_pool.size()) {
@@ -1091,30 +1086,18 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                         ev_pool.emplace_back(e0, e1);
                     }
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
-                    if (geo.on) launch_gn_z(ga, ref.depth[level], level, nq, sk, active_ub);
-                    else if (aff.on) launch_gn_ab(ga, level, nq, sk, active_ub);
-                    else if (rob.on) launch_gn_rw(ga, level, nq, sk, active_ub);
-                    else launch_gn(ga, level, nq, sk, active_ub);
+                }
+                launch_gn_term(ga, level, nq, sk, active_ub, ref.depth[level]);
+                if (cfg.profile) {
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
                     ev_used++;
-                } else if (geo.on) {
-                    launch_gn_z(ga, ref.depth[level], level, nq, sk, active_ub);
-                } else if (aff.on) {
-                    launch_gn_ab(ga, level, nq, sk, active_ub);
-                } else if (rob.on) {
-                    launch_gn_rw(ga, level, nq, sk, active_ub);
-                } else {
-                    launch_gn(ga, level, nq, sk, active_ub);
                 }
                 SolveArgs sa = solve_args(level, q0, first, lists ? SolveRows::LivePair : SolveRows::All);
                 sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;   // (they describe k_track_gn launches only)
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                if (geo.on) launch_solve_z(sa, nq, sk);
-                else if (aff.on) launch_solve_ab(sa, nq, sk, rob_adaptive);
-                else if (rob.on) launch_solve_rw(sa, nq, sk, rob_adaptive);
-                else launch_gn_solve(sa, nq, sk);
+                launch_solve_term(sa, nq, sk, rob_adaptive);
             }
             if (poll && !L.fused && it + 1 < max_it) {
                 DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));

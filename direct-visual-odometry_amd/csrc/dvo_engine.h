@@ -225,15 +225,27 @@ struct TrackQuality {
     int read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s);
 };
 
+// What every opt-in term of batched tracking keeps (robust weights, affine brightness, the geometric term): whether
+// it is on, and the per-sequence record of the last push / call, which is all zeros for a push that tracked nothing.
+struct OptInTerm {
+    bool on = false;        // the next push / call runs with the term
+    bool ready = false;     // the last push / call did
+    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every record in `last` is zero)
+    DevBuf last;            // [n_seq] records of the last push / call (the term says what a record is)
+    void end_push(hipStream_t s)   // after every push / call of the owner, whether it tracked or not
+    {
+        if (on && !tracked) (void)hipMemsetAsync(last.p, 0, last.bytes, s);   // nothing tracked at this push
+        ready = on;
+        tracked = false;
+    }
+};
+
 // Robust residual weights of a batch (dvo_batch_set_robust_weights).  Allocated by the first enable.  While on, the
 // tracker runs the weighted plan (Tracker::lv_rw): k_track_gn_rw + k_gn_solve_rw pairs on every level.
-struct RobustWeights {
-    bool on = false;        // the next push / call runs weighted
-    bool ready = false;     // the last push / call did
-    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every last_s2 is 0)
+struct RobustWeights : OptInTerm {
     int kind = DVO_ROBUST_NONE, mode = DVO_ROBUST_SCALE_ADAPTIVE;
     float param = 0.0f, floor2 = 0.0f;   // floor2 = scale_floor * scale_floor, once, in float
-    DevBuf table, last, scales;          // [n_seq] RobustEntry; [n_seq] float s2 of the last iteration; [n_seq] float s (host rows)
+    DevBuf table, scales;                // [n_seq] RobustEntry; [n_seq] float s (host rows).  last: [n_seq] float s2 of the last iteration
     PinnedPair stage;                    // pinned staging of host rows
     const float* scales_src = nullptr;   // GIVEN: the rows every later push reads (device memory); nullptr: none (plain)
     void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
@@ -241,15 +253,12 @@ struct RobustWeights {
 
 // Affine brightness compensation of a batch (dvo_batch_set_affine_brightness).  Allocated by the first enable.  While on,
 // the tracker runs the plan of launch pairs (Tracker::lv_rw): k_track_gn_ab + k_gn_solve_ab on every level, with or without robust weights.
-struct AffineBrightness {
-    bool on = false;        // the next push / call runs compensated
-    bool ready = false;     // the last push / call did
-    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every last entry is (0, 0))
+struct AffineBrightness : OptInTerm {
     int mode = DVO_AFFINE_OFF;
     int min_pixels = 0;
     float min_contrast = 0.0f, gain_min = 0.0f, gain_max = 0.0f;
     int log_its = 0;                      // iterations per level of the affine log
-    DevBuf table, last, prime, rows;      // [n_seq] AffineEntry; [n_seq][2] last used / priming entry; [n_seq][2] host rows
+    DevBuf table, prime, rows;            // [n_seq] AffineEntry; [n_seq][2] priming entry; [n_seq][2] host rows.  last: [n_seq][2] last used entry
     DevBuf moments, log;                  // [n_seq][part_rows][8] partial rows; [n_seq][levels][log_its][2]
     PinnedPair stage;                     // pinned staging of host rows
     const float* rows_src = nullptr;      // GIVEN: the rows every later push reads (device memory); nullptr: none ((1, 0))
@@ -259,13 +268,10 @@ struct AffineBrightness {
 // The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  Allocated by the first enable.  While
 // on, the tracker runs the plan of launch pairs (Tracker::lv_rw): k_track_gn_z + k_gn_solve_z on every level, on the tracked frame's
 // own depth and weight maps.
-struct GeometricTerm {
-    bool on = false;        // the next push runs with the term
-    bool ready = false;     // the last push did
-    bool tracked = false;   // ... and reached Tracker::track (else: nothing tracked, every record is zero)
+struct GeometricTerm : OptInTerm {
     float weight = 0.0f, max_diff = 0.0f;
     int log_its = 0;        // iterations per level of the geometric log
-    DevBuf last, log;       // [n_seq][4] (n_geo, mean_sq, tracked, 0); [n_seq][levels][log_its][2] (n_geo, S29)
+    DevBuf log;             // [n_seq][levels][log_its][2] (n_geo, S29).  last: [n_seq][4] (n_geo, mean_sq, tracked, 0)
 };
 
 // How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
@@ -309,36 +315,39 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv[DVO_MAX_LEVELS];
     // Both plans are decided by init: lv_plain is what the configuration asks for, lv_rw the weighted plan (launch pairs of the
     // global-gather kernel on every level, whatever track_fused_tiles, gn_use_lds_patch, track_single_launch and the batch size say).
-    // lv / tile_margin are whichever is in force (use_plan, called by set_robust only).
+    // lv / tile_margin are whichever is in force (use_plan, called by set_robust, set_affine and set_geometric: any opt-in term runs
+    // the weighted plan).
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
     int margin_plain = 0;
-    void use_plan(bool robust);
+    void use_plan(bool opt_in_term);
+    int log_iterations() const;   // iterations per level an opt-in term's log holds (set_affine, set_geometric)
+    // One iteration's launch pair of whichever term is on -- the geometric term, else affine brightness (with robust weights when they
+    // are on too), else robust weights, else the plain kernels: the one place that decides.  `ga` / `sa` view `count`
+    // sequences (their SeqState offset is every table's).
+    //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
+    //   prime: the priming pair of affine ESTIMATE mode
+    //   adaptive_scale: the solve writes the next RobustEntry from this iteration's residual
+    //   term_out: the one-evaluation ops' device output (geometric: 2 doubles (n_geo, S29); affine: DVO_AFFINE_MOMENTS doubles)
+    //   estimate_once: the affine solve writes the next entry whatever the mode (dvo_op_gn_step_affine)
+    void launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
+                        bool prime = false) const;
+    void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* term_out = nullptr,
+                           bool estimate_once = false) const;
     GeometricTerm geo;
     int set_geometric(const dvo_geometric_config* c, hipStream_t s);    // validated by the caller; nullptr / OFF: off
     int last_geometric(dvo_geometric_record* rec, hipStream_t s) const;
     int last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const;
-    // the pair of one iteration with the geometric term; ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray
-    // before gn_view)
-    void launch_gn_z(const GnArgs& ga, const float* ref_z, int level, int count, hipStream_t s, int grid_seqs = 0) const;
-    void launch_solve_z(const SolveArgs& sa, int count, hipStream_t s, double* sums_out = nullptr) const;
     AffineBrightness aff;
     int set_affine(const dvo_affine_config* c, hipStream_t s);          // validated by the caller; nullptr / OFF: off
     int set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s);
     int last_affine(float* ab, hipStream_t s) const;
     int last_affine_log(int seq, dvo_affine_log* out, hipStream_t s) const;
     void affine_begin(hipStream_t s, bool given_all = false, float a_all = 1.0f, float b_all = 0.0f);   // k_affine_begin of a call
-    // the compensated pair of one iteration (robust weights included when they are on); prime: the priming pair of ESTIMATE mode
-    void launch_gn_ab(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, bool prime = false) const;
-    void launch_solve_ab(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* moments_out = nullptr,
-                         bool estimate_once = false) const;
     RobustWeights rob;
     int set_robust(const dvo_robust_config* c, hipStream_t s);          // validated by the caller; nullptr / NONE: off
     int set_robust_scales(const float* s_rows, bool on_device, hipStream_t s);
     int last_robust_scales(float* s2, hipStream_t s) const;
-    void robust_end_push(hipStream_t s);    // after every push / call of the owner, whether it tracked or not
-    // the weighted pair of one iteration for the sequences `ga` / `sa` view (their SeqState offset is the table's)
-    void launch_gn_rw(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0) const;
-    void launch_solve_rw(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale) const;
+    void robust_end_push(hipStream_t s);    // after every push / call of the owner, whether it tracked or not (every opt-in term)
     DevBuf ticket, freport;      // k_track_gn_fused: arrival tickets [n_seq]; (reported, active) per (set, level, iteration)
     // Adaptive schedule: progress words in mapped host memory, one per (level, iteration), two sets used alternately.
     // k_gn_solve's workgroup 0 stores (active sequences + 1); the host reads them to stay ~2 iterations ahead of the GPU and
@@ -407,6 +416,13 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // With a plan (Batch): k_plan has done k_track_begin's work, and a level's first iteration runs the plan's sequences, not all
     int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);
     int collect_profile(hipStream_t s);
+private:
+    // the argument blocks of the opt-in terms' kernels for the sequences from q0 on (launch_gn_term, launch_solve_term)
+    RobustSolve robust_solve_args(size_t q0, bool adaptive) const;
+    GeoGn geo_gn_args(size_t q0, int level, const float* ref_z) const;
+    GeoSolve geo_solve_args(size_t q0, bool log, double* sums_out) const;
+    AffineGn affine_gn_args(size_t q0, bool prime) const;
+    AffineSolve affine_solve_args(size_t q0, bool log, bool prime, double* moments_out, bool estimate_once) const;
 };
 
 struct Keyframe {  // System::Frame of one sequence, plus the age map and pose (frame.hpp:72-144)

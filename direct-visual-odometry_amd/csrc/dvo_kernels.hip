@@ -1021,14 +1021,13 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) 
     clear_next();
 }
 
-// k_track_gn_rw / k_track_gn_rw_cam: k_track_gn / k_track_gn_cam with robust residual weights (dvo_batch_set_robust_weights, DESIGN.md
-// §23): the same tiles, lists, gates and samplers, and the sequence's RobustEntry loaded once per workgroup (scalar loads) next to its
-// pose.  New kernels beside the plain ones, which stay as they are; no MASK instances (the mask at a pose is the plain kernel's).
-#if !defined(DVO_GN_RW_WAVES)
-#define DVO_GN_RW_WAVES DVO_GN_WAVES
-#endif
-template <int PPT, int G, bool T2D, bool PCAM>
-__device__ __forceinline__ void track_gn_rw_body(const GnArgs& a, const RobustGn& rg, GnTileLds<PPT>& lds)
+// track_gn_term_body: the body of every opt-in tile kernel (k_track_gn_rw, _ab, _z and their _cam forms) -- what
+// k_track_gn / k_track_gn_cam do (those two stay written out: sharing a body rescheduled them), plus the per-sequence entries of the
+// terms that are on, loaded once per workgroup (scalar loads) next to the pose: pose, AffineEntry (AB), RobustEntry (ROB), camera.
+// rg / ag / zg and mred are read only under their flag; a kernel passes an empty block (and nullptr) for a term it does not have.
+template <int PPT, int G, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
+__device__ __forceinline__ void track_gn_term_body(const GnArgs& a, const RobustGn& rg, const AffineGn& ag, const GeoGn& zg,
+                                                   GnTileLds<PPT>& lds, float (*mred)[8])
 {
     auto clear_next = [&]() {
         if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
@@ -1045,23 +1044,41 @@ __device__ __forceinline__ void track_gn_rw_body(const GnArgs& a, const RobustGn
     const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
     const int seq = a.list ? a.list[4 + slot] : slot;
     const Pose pose = a.state[seq].pose;
-    const RobustEntry rob = load_seq_entry(rg.table, seq);
+    AffineEntry ab{};
+    if constexpr (AB) ab = load_seq_entry(ag.table, seq);
+    RobustEntry rob{};   // (kind 0 = DVO_ROBUST_NONE: rho = 1)
+    if constexpr (ROB) {
+        rob = load_seq_entry(rg.table, seq);
+        if constexpr (AB) {
+            if (ag.prime) rob.kind = DVO_ROBUST_NONE;   // (kernel-uniform: the priming pair is plain)
+        }
+    }
     Intr cam = a.k;
     if constexpr (PCAM) cam = a.seq_k[seq];
-    gn_tile<PPT, G, false, T2D, PCAM, true>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam, rob);
+    const size_t row = (size_t)seq * a.nblk + blk;
+    float* mom_row = nullptr;
+    if constexpr (AB) mom_row = ag.moments + row * 8;
+    gn_tile<PPT, G, false, T2D, PCAM, ROB, AB, GEO>(a, pose, seq, blk, lds, a.partials + row * 32, cam, rob, ab, mom_row, mred, zg);
     clear_next();
 }
+
+// k_track_gn_rw / k_track_gn_rw_cam: k_track_gn / k_track_gn_cam with robust residual weights (dvo_batch_set_robust_weights, DESIGN.md
+// §23): the same tiles, lists, gates and samplers, and the sequence's RobustEntry beside its pose.  Kernels of their own beside the
+// plain ones, which stay as they are; no MASK instances (the mask at a pose is the plain kernel's).
+#if !defined(DVO_GN_RW_WAVES)
+#define DVO_GN_RW_WAVES DVO_GN_WAVES
+#endif
 template <int PPT, int G, bool T2D = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 1) k_track_gn_rw(GnArgs a, RobustGn rg)
 {
     __shared__ GnTileLds<PPT> lds;
-    track_gn_rw_body<PPT, G, T2D, false>(a, rg, lds);
+    track_gn_term_body<PPT, G, T2D, false, true, false, false>(a, rg, AffineGn{}, GeoGn{}, lds, nullptr);
 }
 template <int PPT, int G, bool T2D = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 1) k_track_gn_rw_cam(GnArgs a, RobustGn rg)
 {
     __shared__ GnTileLds<PPT> lds;
-    track_gn_rw_body<PPT, G, T2D, true>(a, rg, lds);
+    track_gn_term_body<PPT, G, T2D, true, true, false, false>(a, rg, AffineGn{}, GeoGn{}, lds, nullptr);
 }
 
 // k_track_gn_ab / k_track_gn_ab_cam: k_track_gn / k_track_gn_cam (ROB: k_track_gn_rw / k_track_gn_rw_cam) with affine brightness
@@ -1099,50 +1116,19 @@ __device__ __forceinline__ void affine_pixel(const AffineEntry& ab, const Robust
         M[4] = fmaf(i1, i2, M[4]);
     }
 }
-template <int PPT, int G, bool T2D, bool PCAM, bool ROB>
-__device__ __forceinline__ void track_gn_ab_body(const GnArgs& a, const RobustGn& rg, const AffineGn& ag, GnTileLds<PPT>& lds,
-                                                 float (*mred)[8])
-{
-    auto clear_next = [&]() {
-        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
-            if (threadIdx.x == 0) *a.next_count = 0;
-        }
-    };
-    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
-    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
-    const int tile_id = xcd * t8 + tile_in_xcd;
-    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
-        clear_next();
-        return;
-    }
-    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
-    const int seq = a.list ? a.list[4 + slot] : slot;
-    const Pose pose = a.state[seq].pose;
-    const AffineEntry ab = load_seq_entry(ag.table, seq);
-    RobustEntry rob{};   // (kind 0 = DVO_ROBUST_NONE: rho = 1)
-    if constexpr (ROB) {
-        rob = load_seq_entry(rg.table, seq);
-        if (ag.prime) rob.kind = DVO_ROBUST_NONE;   // (kernel-uniform)
-    }
-    Intr cam = a.k;
-    if constexpr (PCAM) cam = a.seq_k[seq];
-    const size_t row = (size_t)seq * a.nblk + blk;
-    gn_tile<PPT, G, false, T2D, PCAM, ROB, true>(a, pose, seq, blk, lds, a.partials + row * 32, cam, rob, ab, ag.moments + row * 8, mred);
-    clear_next();
-}
 template <int PPT, int G, bool T2D = false, bool ROB = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_AB_WAVES : 1) k_track_gn_ab(GnArgs a, RobustGn rg, AffineGn ag)
 {
     __shared__ GnTileLds<PPT> lds;
     __shared__ float mred[4][8];
-    track_gn_ab_body<PPT, G, T2D, false, ROB>(a, rg, ag, lds, mred);
+    track_gn_term_body<PPT, G, T2D, false, ROB, true, false>(a, rg, ag, GeoGn{}, lds, mred);
 }
 template <int PPT, int G, bool T2D = false, bool ROB = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_AB_WAVES : 1) k_track_gn_ab_cam(GnArgs a, RobustGn rg, AffineGn ag)
 {
     __shared__ GnTileLds<PPT> lds;
     __shared__ float mred[4][8];
-    track_gn_ab_body<PPT, G, T2D, true, ROB>(a, rg, ag, lds, mred);
+    track_gn_term_body<PPT, G, T2D, true, ROB, true, false>(a, rg, ag, GeoGn{}, lds, mred);
 }
 
 // k_track_gn_z / k_track_gn_z_cam: k_track_gn / k_track_gn_cam with the geometric (depth) term of a sensor-depth batch
@@ -1202,43 +1188,19 @@ __device__ __forceinline__ void geo_pixel(const Intr& k, const GeoGn& geo, const
     S29 = fmaf(rg, rg, S29);
     S30 += on ? 1.0f : 0.0f;
 }
-template <int PPT, int G, bool T2D, bool PCAM>
-__device__ __forceinline__ void track_gn_z_body(const GnArgs& a, const GeoGn& zg, GnTileLds<PPT>& lds, float (*mred)[8])
-{
-    auto clear_next = [&]() {
-        if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
-            if (threadIdx.x == 0) *a.next_count = 0;
-        }
-    };
-    const int n_tiles = (a.list ? a.list[0] : a.n_seq) * a.blk_count;
-    const int t8 = (n_tiles + 7) >> 3, xcd = blockIdx.x & 7, tile_in_xcd = (int)(blockIdx.x >> 3);
-    const int tile_id = xcd * t8 + tile_in_xcd;
-    if (tile_in_xcd >= t8 || tile_id >= n_tiles) {
-        clear_next();
-        return;
-    }
-    const int slot = tile_id / a.blk_count, blk = a.blk_first + (tile_id - slot * a.blk_count);
-    const int seq = a.list ? a.list[4 + slot] : slot;
-    const Pose pose = a.state[seq].pose;
-    Intr cam = a.k;
-    if constexpr (PCAM) cam = a.seq_k[seq];
-    gn_tile<PPT, G, false, T2D, PCAM, false, false, true>(a, pose, seq, blk, lds, a.partials + ((size_t)seq * a.nblk + blk) * 32, cam,
-                                                          RobustEntry{}, AffineEntry{}, nullptr, mred, zg);
-    clear_next();
-}
 template <int PPT, int G, bool T2D = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_Z_WAVES : 1) k_track_gn_z(GnArgs a, GeoGn zg)
 {
     __shared__ GnTileLds<PPT> lds;
     __shared__ float mred[4][8];
-    track_gn_z_body<PPT, G, T2D, false>(a, zg, lds, mred);
+    track_gn_term_body<PPT, G, T2D, false, false, false, true>(a, RobustGn{}, AffineGn{}, zg, lds, mred);
 }
 template <int PPT, int G, bool T2D = false>
 __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_Z_WAVES : 1) k_track_gn_z_cam(GnArgs a, GeoGn zg)
 {
     __shared__ GnTileLds<PPT> lds;
     __shared__ float mred[4][8];
-    track_gn_z_body<PPT, G, T2D, true>(a, zg, lds, mred);
+    track_gn_term_body<PPT, G, T2D, true, false, false, true>(a, RobustGn{}, AffineGn{}, zg, lds, mred);
 }
 
 template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
@@ -1756,66 +1718,92 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve(SolveArgs a)
     (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
 }
 
-// k_gn_solve_rw: k_gn_solve for a batch with robust residual weights -- line for line k_gn_solve (a twin, so that kernel stays as it
-// is), and the serial thread also keeps the sequence's RobustEntry: it records the s2 this iteration's k_track_gn_rw used (last_s2) and,
-// with the adaptive scale, writes the entry of the next launch from this iteration's residual -- one fixed-point step of the IRLS scale:
-// s2 = max(residual, floor2), plain when the residual is not > 0 (the -1 sentinel of an iteration without pixels).
-__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_rw(SolveArgs a, RobustSolve rs)
+// solve_gather: everything of a solve kernel up to its serial tail, shared by k_gn_solve_rw, _ab and _z: the progress
+// word, the serial lanes' state loads, the second reduction stage of slots 0 .. NSUM-1 into tot (wide form for one or two sequences,
+// one team per sequence otherwise; slots NSUM .. 31 are exact zeros) and the barrier.  True for a lane that goes on to solve_finish:
+// lanes 0..7 of wave 0, one live sequence each; my_seq, it_prev, xi and Tc are that sequence's.  Every other lane is done.
+//   pre(seq):               a term's own load beside the serial lane's state loads (all requests go out up front)
+//   mid(t_slot, c, team):   a term's own sums ahead of the barrier
+// k_gn_solve is this function written out with NSUM = 29 and no callbacks, on purpose: its serial chain is the latency of every
+// iteration of the default path, and built from this helper its instruction stream is not the one that was measured (the early
+// returns move).  A change to the summation order or to the state loads is made here AND there; tools/isa_compare.py shows whether
+// k_gn_solve moved.
+template <int NSUM, class Pre, class Mid>
+__device__ __forceinline__ bool solve_gather(const SolveArgs& a, double (*tot)[32], double (*part)[DVO_SOLVE_GROUPS][32], int& my_seq,
+                                             int& it_prev, float (&xi)[6], double (&Tc)[12], Pre&& pre, Mid&& mid)
 {
-    __shared__ double tot[DVO_SOLVE_SEQ][32];
-    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
     const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
     if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
+    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return false;
     const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
     const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
-    int my_seq = 0;
     if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
-    SeqState& st = a.state[my_seq];
-    int was_active = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    float used_s2 = 0.0f;
+    const SeqState& st = a.state[my_seq];
+    int was_active = 0;
     if (serial) {
         was_active = st.active; it_prev = st.iter;
 #pragma unroll
         for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
 #pragma unroll
         for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
-        used_s2 = rs.table[my_seq].s2;
+        pre(my_seq);
     }
     const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
     const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
     if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
         const int ws = team >> 2, wg = team & 3;
-        if (ws < n_in && c < 29) {
+        if (ws < n_in && c < NSUM) {
             const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
             part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
         }
         __syncthreads();
         if (threadIdx.x < 64) {
             const int ts = threadIdx.x >> 5;
-            tot[ts][c] = (ts < n_in && c < 29) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
+            tot[ts][c] = (ts < n_in && c < NSUM) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
         }
-    } else if (t_slot < n_in && c < 29) {
+    } else if (t_slot < n_in && c < NSUM) {
         const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
         tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
-    } else if (c >= 29) {
+    } else if (c >= NSUM) {
         tot[team][c] = 0.0;
     }
+    if (t_slot < n_in) mid(t_slot, c, team);
     __syncthreads();
-    if (!serial) return;
-    if (!a.ignore_active && was_active == 0) return;
-    Pose np;
-    const double* t = tot[threadIdx.x];
-    (void)solve_finish(a, my_seq, st, t, a.ignore_active, it_prev, xi, Tc, np);
-    rs.last_s2[my_seq] = used_s2;
+    if (!serial) return false;
+    return a.ignore_active || was_active != 0;   // (a converged sequence has nothing to do)
+}
+
+// The serial lane's upkeep of its sequence's RobustEntry after solve_finish (k_gn_solve_rw, and k_gn_solve_ab with robust weights on):
+// it records the s2 this iteration's tile kernel used (last_s2) and, with the adaptive scale, writes the entry of the next launch from
+// this iteration's residual -- one fixed-point step of the IRLS scale: s2 = max(residual, floor2), plain when the residual is not > 0
+// (the -1 sentinel of an iteration without pixels).  t: the sequence's 29 sums.  (Only this lane ever writes the sequence's entry, and
+// solve_finish does not know the table: a caller may read used_s2 before or after it.)
+__device__ __forceinline__ void robust_solve_update(const RobustSolve& rs, const int seq, const float used_s2, const double* t)
+{
+    rs.last_s2[seq] = used_s2;
     if (rs.adaptive) {
         const int n_valid = (int)t[28];
         const float residual = n_valid > 0 ? (float)t[27] / (float)n_valid : -1.0f;   // solve_finish's own expression: the logged bits
         const float s2 = residual > rs.floor2 ? residual : rs.floor2;
-        rs.table[my_seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
+        rs.table[seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
     }
+}
+
+// k_gn_solve_rw: k_gn_solve for a batch with robust residual weights: solve_gather, solve_finish, and the sequence's RobustEntry
+// (robust_solve_update) with the s2 that was read beside the state.
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_rw(SolveArgs a, RobustSolve rs)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    int my_seq = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float used_s2 = 0.0f;
+    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [&](int seq) { used_s2 = rs.table[seq].s2; }, [](int, int, int) {})) return;
+    Pose np;
+    const double* t = tot[threadIdx.x];
+    (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
+    robust_solve_update(rs, my_seq, used_s2, t);
 }
 
 // k_robust_begin: the RobustEntry table at the start of a tracking call, one thread per sequence.  Adaptive scale: every sequence starts
@@ -1852,60 +1840,27 @@ __device__ __forceinline__ void affine_next_entry(const AffineSolve& f, const in
     }
 }
 
-// k_gn_solve_ab: k_gn_solve_rw for a batch with affine brightness compensation -- line for line that kernel (a twin), and the serial
-// thread also keeps the sequence's AffineEntry: it records the entry this iteration's k_track_gn_ab used (last, and the affine log at
-// the iteration's slot of the track log) and, in ESTIMATE mode, writes the next launch's entry from this iteration's moments, which
-// team lanes 0..7 sum in double in the order of the 29 sums.  f.prime: the priming pair -- the entry and prime_ab only.  The
-// RobustEntry is kept exactly as k_gn_solve_rw keeps it when robust weights are on too (f.robust).
+// k_gn_solve_ab: k_gn_solve_rw for a batch with affine brightness compensation: solve_gather, and the serial thread also keeps the
+// sequence's AffineEntry: it records the entry this iteration's k_track_gn_ab used (last, and the affine log at the iteration's slot
+// of the track log) and, in ESTIMATE mode, writes the next launch's entry from this iteration's moments, which team lanes 0..7 sum in
+// double in the order of the 29 sums.  f.prime: the priming pair -- the entry and prime_ab only.  The RobustEntry is kept exactly as
+// k_gn_solve_rw keeps it when robust weights are on too (f.robust).
 __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_ab(SolveArgs a, RobustSolve rs, AffineSolve f)
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
     __shared__ double mtot[DVO_SOLVE_SEQ][8];
-    const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
-    if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
-    const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
-    const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
-    int my_seq = 0;
-    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
-    SeqState& st = a.state[my_seq];
-    int was_active = 0, it_prev = 0;
+    int my_seq = 0, it_prev = 0;
     float xi[6] = {0, 0, 0, 0, 0, 0};
     double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (serial) {
-        was_active = st.active; it_prev = st.iter;
-#pragma unroll
-        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
-#pragma unroll
-        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
-    }
-    const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
-    const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
-    if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
-        const int ws = team >> 2, wg = team & 3;
-        if (ws < n_in && c < 29) {
-            const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
-            part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
+    const auto sum_moments = [&](int t_slot, int c, int team) {   // the moments of the team's sequence (every schedule: the order of sum_partial_rows)
+        if (c < 8) {
+            const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+            mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
         }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int ts = threadIdx.x >> 5;
-            tot[ts][c] = (ts < n_in && c < 29) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
-        }
-    } else if (t_slot < n_in && c < 29) {
-        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
-        tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
-    } else if (c >= 29) {
-        tot[team][c] = 0.0;
-    }
-    if (t_slot < n_in && c < 8) {   // the moments of the team's sequence (every schedule: the order of sum_partial_rows)
-        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
-        mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
-    }
-    __syncthreads();
-    if (!serial) return;
-    if (!a.ignore_active && was_active == 0) return;
+    };
+    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, sum_moments)) return;
+    SeqState& st = a.state[my_seq];
     // (the pose first, the brightness entry after it: nothing of the closed form is live across the serial chain of solve_finish)
     if (!f.prime) {
         Pose np;
@@ -1934,66 +1889,23 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_ab(SolveArgs a,
         lg[0] = used.a; lg[1] = used.b;
     }
     f.last[2 * my_seq] = used.a; f.last[2 * my_seq + 1] = used.b;
-    if (f.robust) {
-        rs.last_s2[my_seq] = rs.table[my_seq].s2;
-        if (rs.adaptive) {
-            const float residual = n_valid > 0 ? (float)t[27] / (float)n_valid : -1.0f;   // solve_finish's own expression: the logged bits
-            const float s2 = residual > rs.floor2 ? residual : rs.floor2;
-            rs.table[my_seq] = robust_entry(residual > 0.0f ? rs.kind : DVO_ROBUST_NONE, rs.param, s2);
-        }
-    }
+    if (f.robust) robust_solve_update(rs, my_seq, rs.table[my_seq].s2, t);
 }
 
-// k_gn_solve_z: k_gn_solve for a sensor-depth batch with the geometric term -- line for line k_gn_solve (a twin, so that kernel stays
-// as it is), summing slots 29 (sum rg^2) and 30 (n_geo) of the partial rows beside the 29 in the same fixed order; the serial thread
-// records them (last, and the geometric log at the iteration's slot of the track log).  solve_finish reads slots 0..28 only: it solves
-// the combined H and g, and n_valid, the residual and the stop tests stay photometric.
+// k_gn_solve_z: k_gn_solve for a sensor-depth batch with the geometric term: solve_gather sums slots 29 (sum rg^2) and 30 (n_geo) of
+// the partial rows beside the 29 in the same fixed order; the serial thread records them (last, and the geometric log at the
+// iteration's slot of the track log).  solve_finish reads slots 0..28 only: it solves the combined H and g, and n_valid, the residual
+// and the stop tests stay photometric.
 __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_z(SolveArgs a, GeoSolve z)
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
-    const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
-    if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return;
-    const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
-    const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
-    int my_seq = 0;
-    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
-    SeqState& st = a.state[my_seq];
-    int was_active = 0, it_prev = 0;
+    int my_seq = 0, it_prev = 0;
     float xi[6] = {0, 0, 0, 0, 0, 0};
     double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (serial) {
-        was_active = st.active; it_prev = st.iter;
-#pragma unroll
-        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
-#pragma unroll
-        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
-    }
-    const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
-    const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
-    if (n_in <= 2 && a.nblk <= 32 * DVO_WIDE_BATCHES) {
-        const int ws = team >> 2, wg = team & 3;
-        if (ws < n_in && c < 31) {
-            const int t_seq = a.list_in ? a.list_in[4 + ws] : ws;
-            part[ws][wg][c] = sum_partial_class(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count, wg);
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-            const int ts = threadIdx.x >> 5;
-            tot[ts][c] = (ts < n_in && c < 31) ? (part[ts][0][c] + part[ts][1][c]) + (part[ts][2][c] + part[ts][3][c]) : 0.0;
-        }
-    } else if (t_slot < n_in && c < 31) {
-        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
-        tot[team][c] = sum_partial_rows(a.partials + (size_t)t_seq * a.nblk * 32 + c, a.nblk, a.blk_first, a.blk_count);
-    } else if (c >= 31) {
-        tot[team][c] = 0.0;
-    }
-    __syncthreads();
-    if (!serial) return;
-    if (!a.ignore_active && was_active == 0) return;
+    if (!solve_gather<31>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, [](int, int, int) {})) return;
     Pose np;
-    (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
+    (void)solve_finish(a, my_seq, a.state[my_seq], tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
     const double S29 = tot[threadIdx.x][29], n_geo = tot[threadIdx.x][30];
     if (z.sums_out) { z.sums_out[2 * (size_t)my_seq] = n_geo; z.sums_out[2 * (size_t)my_seq + 1] = S29; }
     const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
@@ -3155,94 +3067,65 @@ static void with_flag(bool on, F&& f)
     else f(std::false_type{});
 }
 
-template <int PPT, int G>
-static void launch_track_gn_t(const GnArgs& a, bool t2d, unsigned tiles, hipStream_t s)
+// The (ppt, group) pairs the tilings pick, as compile-time constants: f receives the pair as two std::integral_constant, so a launcher
+// names its kernel template once and the nine instances follow from it.  Any other pair runs as <8, 4>.
+template <class F>
+static void with_gn_shape(int ppt, int group, F&& f)
 {
-    const dim3 grid((tiles + 7u) & ~7u);  // a multiple of 8: blockIdx % 8 is the XCD
-    with_flag(a.mask != nullptr, [&](auto mask) {
-        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {   // (2-D tiles exist for 4 pixels per thread only)
-            constexpr bool MASK = decltype(mask)::value, T2D = PPT == 4 && decltype(tiles_2d)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);   // per-sequence intrinsics
-            else hipLaunchKernelGGL((k_track_gn<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);
-        });
-    });
+    using std::integral_constant;
+    switch (ppt * 10 + group) {
+        case 11: f(integral_constant<int, 1>{}, integral_constant<int, 1>{}); break;
+        case 21: f(integral_constant<int, 2>{}, integral_constant<int, 1>{}); break;
+        case 22: f(integral_constant<int, 2>{}, integral_constant<int, 2>{}); break;
+        case 41: f(integral_constant<int, 4>{}, integral_constant<int, 1>{}); break;
+        case 42: f(integral_constant<int, 4>{}, integral_constant<int, 2>{}); break;
+        case 44: f(integral_constant<int, 4>{}, integral_constant<int, 4>{}); break;
+        case 81: f(integral_constant<int, 8>{}, integral_constant<int, 1>{}); break;
+        case 82: f(integral_constant<int, 8>{}, integral_constant<int, 2>{}); break;
+        default: f(integral_constant<int, 8>{}, integral_constant<int, 4>{}); break;
+    }
+}
+
+// The grid of a tile launch (k_track_gn and the opt-in tile kernels), a multiple of 8: blockIdx % 8 is the XCD.
+// grid_seqs: an upper bound of the sequences on the active list (the host knows one from the progress words): the grid then only
+// holds workgroups that can find a tile -- at 16 384 sequences x 75 tiles an all-empty grid alone costs ~0.35 ms to dispatch
+static dim3 gn_tile_grid(const GnArgs& a, int n_seq, int grid_seqs)
+{
+    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
+    unsigned tiles = (unsigned)a.blk_count * (unsigned)gs;
+    if (tiles == 0) tiles = 8;  // (nothing live: the workgroups only clear the next list counter)
+    return dim3((tiles + 7u) & ~7u);
 }
 
 void launch_track_gn(const GnArgs& a0, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
 {
     GnArgs a = a0;
     a.n_seq = n_seq;
-    // grid_seqs: an upper bound of the sequences on the active list (the host knows one from the progress words): the grid then only
-    // holds workgroups that can find a tile -- at 16 384 sequences x 75 tiles an all-empty grid alone costs ~0.35 ms to dispatch
-    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
-    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
-    if (grid == 0) grid = 8;  // (nothing live: the workgroups only clear the next list counter)
-    switch (ppt * 10 + group) {
-        case 11: launch_track_gn_t<1, 1>(a, t2d, grid, s); break;
-        case 21: launch_track_gn_t<2, 1>(a, t2d, grid, s); break;
-        case 22: launch_track_gn_t<2, 2>(a, t2d, grid, s); break;
-        case 41: launch_track_gn_t<4, 1>(a, t2d, grid, s); break;
-        case 42: launch_track_gn_t<4, 2>(a, t2d, grid, s); break;
-        case 44: launch_track_gn_t<4, 4>(a, t2d, grid, s); break;
-        case 81: launch_track_gn_t<8, 1>(a, t2d, grid, s); break;
-        case 82: launch_track_gn_t<8, 2>(a, t2d, grid, s); break;
-        default: launch_track_gn_t<8, 4>(a, t2d, grid, s); break;
-    }
-}
-
-template <int PPT, int G>
-static void launch_track_gn_rw_t(const GnArgs& a, const RobustGn& r, bool t2d, unsigned tiles, hipStream_t s)
-{
-    const dim3 grid((tiles + 7u) & ~7u);
-    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-        if (a.seq_k) hipLaunchKernelGGL((k_track_gn_rw_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
-        else hipLaunchKernelGGL((k_track_gn_rw<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(a.mask != nullptr, [&](auto mask) {
+            with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {   // (2-D tiles exist for 4 pixels per thread only)
+                constexpr bool MASK = decltype(mask)::value, T2D = PPT == 4 && decltype(tiles_2d)::value;
+                if (a.seq_k) hipLaunchKernelGGL((k_track_gn_cam<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+                else hipLaunchKernelGGL((k_track_gn<PPT, G, MASK, T2D>), grid, dim3(256), 0, s, a);
+            });
+        });
     });
 }
 
+// (the opt-in tile kernels have no MASK instances: a.mask = nullptr)
 void launch_track_gn_rw(const GnArgs& a0, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
 {
     GnArgs a = a0;
     a.n_seq = n_seq; a.mask = nullptr;
-    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
-    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
-    if (grid == 0) grid = 8;
-    switch (ppt * 10 + group) {
-        case 11: launch_track_gn_rw_t<1, 1>(a, r, t2d, grid, s); break;
-        case 21: launch_track_gn_rw_t<2, 1>(a, r, t2d, grid, s); break;
-        case 22: launch_track_gn_rw_t<2, 2>(a, r, t2d, grid, s); break;
-        case 41: launch_track_gn_rw_t<4, 1>(a, r, t2d, grid, s); break;
-        case 42: launch_track_gn_rw_t<4, 2>(a, r, t2d, grid, s); break;
-        case 44: launch_track_gn_rw_t<4, 4>(a, r, t2d, grid, s); break;
-        case 81: launch_track_gn_rw_t<8, 1>(a, r, t2d, grid, s); break;
-        case 82: launch_track_gn_rw_t<8, 2>(a, r, t2d, grid, s); break;
-        default: launch_track_gn_rw_t<8, 4>(a, r, t2d, grid, s); break;
-    }
-}
-
-void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s)
-{
-    SolveArgs b = a;
-    b.n_seq = n_seq;
-    hipLaunchKernelGGL(k_gn_solve_rw, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, r);
-}
-
-void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
-}
-
-template <int PPT, int G>
-static void launch_track_gn_ab_t(const GnArgs& a, const RobustGn& r, const AffineGn& f, bool t2d, unsigned tiles, hipStream_t s)
-{
-    const dim3 grid((tiles + 7u) & ~7u);
-    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-        with_flag(r.table != nullptr, [&](auto robust) {
-            constexpr bool ROB = decltype(robust)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_ab_cam<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
-            else hipLaunchKernelGGL((k_track_gn_ab<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_rw_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
+            else hipLaunchKernelGGL((k_track_gn_rw<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
         });
     });
 }
@@ -3252,37 +3135,17 @@ void launch_track_gn_ab(const GnArgs& a0, const RobustGn& r, const AffineGn& f, 
 {
     GnArgs a = a0;
     a.n_seq = n_seq; a.mask = nullptr;
-    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
-    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
-    if (grid == 0) grid = 8;
-    switch (ppt * 10 + group) {
-        case 11: launch_track_gn_ab_t<1, 1>(a, r, f, t2d, grid, s); break;
-        case 21: launch_track_gn_ab_t<2, 1>(a, r, f, t2d, grid, s); break;
-        case 22: launch_track_gn_ab_t<2, 2>(a, r, f, t2d, grid, s); break;
-        case 41: launch_track_gn_ab_t<4, 1>(a, r, f, t2d, grid, s); break;
-        case 42: launch_track_gn_ab_t<4, 2>(a, r, f, t2d, grid, s); break;
-        case 44: launch_track_gn_ab_t<4, 4>(a, r, f, t2d, grid, s); break;
-        case 81: launch_track_gn_ab_t<8, 1>(a, r, f, t2d, grid, s); break;
-        case 82: launch_track_gn_ab_t<8, 2>(a, r, f, t2d, grid, s); break;
-        default: launch_track_gn_ab_t<8, 4>(a, r, f, t2d, grid, s); break;
-    }
-}
-
-void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s)
-{
-    SolveArgs b = a;
-    b.n_seq = n_seq;
-    hipLaunchKernelGGL(k_gn_solve_ab, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, r, f);
-}
-
-template <int PPT, int G>
-static void launch_track_gn_z_t(const GnArgs& a, const GeoGn& z, bool t2d, unsigned tiles, hipStream_t s)
-{
-    const dim3 grid((tiles + 7u) & ~7u);
-    with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-        constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-        if (a.seq_k) hipLaunchKernelGGL((k_track_gn_z_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
-        else hipLaunchKernelGGL((k_track_gn_z<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+            with_flag(r.table != nullptr, [&](auto robust) {
+                constexpr bool ROB = decltype(robust)::value;
+                if (a.seq_k) hipLaunchKernelGGL((k_track_gn_ab_cam<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
+                else hipLaunchKernelGGL((k_track_gn_ab<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
+            });
+        });
     });
 }
 
@@ -3290,27 +3153,37 @@ void launch_track_gn_z(const GnArgs& a0, const GeoGn& z, int n_seq, int ppt, int
 {
     GnArgs a = a0;
     a.n_seq = n_seq; a.mask = nullptr;
-    const int gs = (grid_seqs > 0 && grid_seqs < n_seq && a.list != nullptr) ? grid_seqs : n_seq;
-    unsigned grid = (unsigned)a.blk_count * (unsigned)gs;
-    if (grid == 0) grid = 8;
-    switch (ppt * 10 + group) {
-        case 11: launch_track_gn_z_t<1, 1>(a, z, t2d, grid, s); break;
-        case 21: launch_track_gn_z_t<2, 1>(a, z, t2d, grid, s); break;
-        case 22: launch_track_gn_z_t<2, 2>(a, z, t2d, grid, s); break;
-        case 41: launch_track_gn_z_t<4, 1>(a, z, t2d, grid, s); break;
-        case 42: launch_track_gn_z_t<4, 2>(a, z, t2d, grid, s); break;
-        case 44: launch_track_gn_z_t<4, 4>(a, z, t2d, grid, s); break;
-        case 81: launch_track_gn_z_t<8, 1>(a, z, t2d, grid, s); break;
-        case 82: launch_track_gn_z_t<8, 2>(a, z, t2d, grid, s); break;
-        default: launch_track_gn_z_t<8, 4>(a, z, t2d, grid, s); break;
-    }
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_z_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
+            else hipLaunchKernelGGL((k_track_gn_z<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
+        });
+    });
 }
 
-void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s)
+// A solve kernel (k_gn_solve or an opt-in term's) over n_seq sequences, DVO_SOLVE_SEQ per workgroup; extra: the term's argument blocks
+template <class K, class... Extra>
+static void launch_solve_kernel(K kernel, const SolveArgs& a, int n_seq, hipStream_t s, const Extra&... extra)
 {
     SolveArgs b = a;
     b.n_seq = n_seq;
-    hipLaunchKernelGGL(k_gn_solve_z, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, z);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b, extra...);
+}
+
+void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve, a, n_seq, s); }
+void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_rw, a, n_seq, s, r); }
+void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s)
+{
+    launch_solve_kernel(k_gn_solve_ab, a, n_seq, s, r, f);
+}
+void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_z, a, n_seq, s, z); }
+
+void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
 }
 
 void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s)
@@ -3319,16 +3192,19 @@ void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s)
 }
 
 // The (ppt, group) pairs the tiling picks for a handle of a few sequences: the ones k_track_gn_fused and k_track_persist have an
-// instance for.  f receives the pair as two std::integral_constant; false (f not called) for any other pair.
+// instance for.  f receives the pair as with_gn_shape passes it; false (f not called) for any other pair.
 template <class F>
 static bool with_small_handle_pair(int ppt, int group, F&& f)
 {
-    switch (ppt * 10 + group) {
-        case 11: f(std::integral_constant<int, 1>{}, std::integral_constant<int, 1>{}); return true;
-        case 22: f(std::integral_constant<int, 2>{}, std::integral_constant<int, 2>{}); return true;
-        case 42: f(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{}); return true;
-        default: return false;
-    }
+    bool found = false;
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int pair = decltype(p)::value * 10 + decltype(g)::value;
+        if constexpr (pair == 11 || pair == 22 || pair == 42) {   // (no instance of f for the other six)
+            f(p, g);
+            found = true;
+        }
+    });
+    return found;
 }
 
 bool gn_fused_available(int ppt, int group) { return with_small_handle_pair(ppt, group, [](auto, auto) {}); }
@@ -3423,13 +3299,6 @@ void launch_prep_ref(const PrepArgs& a, hipStream_t s)
     const size_t n = a.level_end[a.levels - 1];
     if (n == 0) return;
     hipLaunchKernelGGL(k_prep_ref, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-}
-
-void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s)
-{
-    SolveArgs b = a;
-    b.n_seq = n_seq;
-    hipLaunchKernelGGL(k_gn_solve, dim3((unsigned)((n_seq + DVO_SOLVE_SEQ - 1) / DVO_SOLVE_SEQ)), dim3(32 * DVO_SOLVE_SEQ), 0, s, b);
 }
 
 void launch_track_begin(SeqState* state, dvo_track_log* log, int n_seq, int levels, hipStream_t s)
