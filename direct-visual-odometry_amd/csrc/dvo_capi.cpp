@@ -561,6 +561,19 @@ int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg)
     return b->trk().set_geometric(cfg, b->stream());
 }
 
+int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo, const dvo_affine_config* aff)
+{
+    static const char who[] = "dvo_batch_set_geometric_affine";
+    if (!b || !geo || !aff) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error(std::string(who) + ": needs a sensor-depth batch (a mono batch has no depth map to compare)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!geometric_config_ok(geo, who) || !affine_config_ok(aff, who)) return DVO_ERR_BAD_ARGUMENT;
+    if (geo->mode != DVO_GEOMETRIC_ON) { set_error(std::string(who) + ": the geometric mode must be DVO_GEOMETRIC_ON (dvo_batch_set_geometric turns the term off)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (aff->mode == DVO_AFFINE_OFF) { set_error(std::string(who) + ": the affine mode must be DVO_AFFINE_ESTIMATE or DVO_AFFINE_GIVEN (dvo_batch_set_affine_brightness turns the compensation off)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (b->trk().rob.on) { set_error(std::string(who) + ": robust weights are on: they do not combine with the geometric term yet"); return DVO_ERR_BAD_ARGUMENT; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_geometric_affine(geo, aff, b->stream());
+}
+
 int dvo_batch_last_geometric(dvo_batch* b, dvo_geometric_record* rec)
 {
     if (!b || !rec) return DVO_ERR_BAD_ARGUMENT;
@@ -885,7 +898,7 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true);
+    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true, mom.as<double>());
     if (trk.aff.on) {
         DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
@@ -909,6 +922,23 @@ int dvo_op_gn_step_geometric(int dev, const dvo_config* cfg, const float* obj_gr
     if (!geometric_config_ok(&gc, "dvo_op_gn_step_geometric")) return DVO_ERR_BAD_ARGUMENT;
     return gn_step(dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, nullptr, nullptr, 0.0f, nullptr, 1.0f, 0.0f,
                    nullptr, nullptr, &gc, ref_depth, sums);
+}
+
+int dvo_op_gn_step_geometric_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth, const float* obj_sigma,
+                                    const float* ref_gray, const float* ref_depth, int w, int h, const float K[9], const float xi[6],
+                                    int level, float weight, float max_diff, float a, float b, dvo_gn_result* out, double sums[2],
+                                    double moments[5], float next_ab[2])
+{
+    if (!ref_depth || !sums || !moments || !next_ab) return DVO_ERR_BAD_ARGUMENT;
+    dvo_geometric_config gc{};
+    gc.struct_size = (int)sizeof gc;
+    gc.mode = DVO_GEOMETRIC_ON; gc.weight = weight; gc.max_diff = max_diff;
+    if (!geometric_config_ok(&gc, "dvo_op_gn_step_geometric_affine")) return DVO_ERR_BAD_ARGUMENT;
+    dvo_affine_config ac{};   // (dvo_op_gn_step_affine's guards)
+    ac.struct_size = (int)sizeof ac;
+    ac.mode = DVO_AFFINE_GIVEN; ac.min_pixels = 64; ac.min_contrast = 1e-3f; ac.gain_min = 0.25f; ac.gain_max = 4.0f;
+    return gn_step(dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, nullptr, nullptr, 0.0f, &ac, a, b, moments,
+                   next_ab, &gc, ref_depth, sums);
 }
 
 int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

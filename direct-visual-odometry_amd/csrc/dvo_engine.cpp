@@ -665,6 +665,12 @@ int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
     return DVO_OK;
 }
 
+int Tracker::set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s)
+{
+    DVO_TRY(set_geometric(gc, s));
+    return set_affine(ac, s);
+}
+
 int Tracker::last_geometric(dvo_geometric_record* rec, hipStream_t s) const
 {
     std::vector<float> rows((size_t)4 * n_seq);
@@ -852,18 +858,22 @@ void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t 
     const bool t2d = L.tiling.t2d != 0;
     RobustGn r{};   // (no table: the affine kernels run without weights)
     if (rob.on) r.table = rob.table.as<RobustEntry>() + q0;
-    if (geo.on) launch_track_gn_z(a, geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
+    if (geo.on && aff.on) launch_track_gn_zab(a, affine_gn_args(q0, prime), geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
+    else if (geo.on) launch_track_gn_z(a, geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
     else if (aff.on) launch_track_gn_ab(a, r, affine_gn_args(q0, prime), count, L.ppt, L.group, t2d, s, grid_seqs);
     else if (rob.on) launch_track_gn_rw(a, r, count, L.ppt, L.group, t2d, s, grid_seqs);
     else launch_gn(a, level, count, s, grid_seqs);
 }
 
 void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* term_out,
-                                bool estimate_once) const
+                                bool estimate_once, double* moments_out) const
 {
     const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
     const RobustSolve r = rob.on ? robust_solve_args(q0, adaptive_scale) : RobustSolve{};
-    if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, sa.log != nullptr, term_out), count, s);
+    if (geo.on && aff.on)
+        launch_gn_solve_zab(sa, affine_solve_args(q0, sa.log != nullptr, prime, moments_out, estimate_once), geo_solve_args(q0, sa.log != nullptr, term_out),
+                            count, s);
+    else if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, sa.log != nullptr, term_out), count, s);
     else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, sa.log != nullptr, prime, term_out, estimate_once), count, s);
     else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
     else launch_gn_solve(sa, count, s);
@@ -1073,7 +1083,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                     // leaves the pose, the log, the lists and the quality record alone
                     GnArgs gp = ga;
                     gp.next_count = nullptr;
-                    launch_gn_term(gp, level, nq, sk, 0, nullptr, true);
+                    launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true);
                     SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
                     sp.list_in = list_prev; sp.result = nullptr;
                     launch_solve_term(sp, nq, sk, false, true);

@@ -267,7 +267,8 @@ struct AffineBrightness : OptInTerm {
 
 // The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  Allocated by the first enable.  While
 // on, the tracker runs the plan of launch pairs (Tracker::lv_rw): k_track_gn_z + k_gn_solve_z on every level, on the tracked frame's
-// own depth and weight maps.
+// own depth and weight maps.  With affine brightness on too (dvo_batch_set_geometric_affine) the pairs are
+// k_track_gn_zab + k_gn_solve_zab, on the same maps.
 struct GeometricTerm : OptInTerm {
     float weight = 0.0f, max_diff = 0.0f;
     int log_its = 0;        // iterations per level of the geometric log
@@ -321,7 +322,8 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int margin_plain = 0;
     void use_plan(bool opt_in_term);
     int log_iterations() const;   // iterations per level an opt-in term's log holds (set_affine, set_geometric)
-    // One iteration's launch pair of whichever term is on -- the geometric term, else affine brightness (with robust weights when they
+    // One iteration's launch pair of whichever term is on -- the geometric term with affine brightness, else the
+    // geometric term, else affine brightness (with robust weights when they
     // are on too), else robust weights, else the plain kernels: the one place that decides.  `ga` / `sa` view `count`
     // sequences (their SeqState offset is every table's).
     //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
@@ -329,12 +331,14 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     //   adaptive_scale: the solve writes the next RobustEntry from this iteration's residual
     //   term_out: the one-evaluation ops' device output (geometric: 2 doubles (n_geo, S29); affine: DVO_AFFINE_MOMENTS doubles)
     //   estimate_once: the affine solve writes the next entry whatever the mode (dvo_op_gn_step_affine)
+    //   moments_out: both terms on: the affine output (term_out is the geometric one; dvo_op_gn_step_geometric_affine)
     void launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
                         bool prime = false) const;
     void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* term_out = nullptr,
-                           bool estimate_once = false) const;
+                           bool estimate_once = false, double* moments_out = nullptr) const;
     GeometricTerm geo;
     int set_geometric(const dvo_geometric_config* c, hipStream_t s);    // validated by the caller; nullptr / OFF: off
+    int set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s);   // both on (validated by the caller)
     int last_geometric(dvo_geometric_record* rec, hipStream_t s) const;
     int last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const;
     AffineBrightness aff;

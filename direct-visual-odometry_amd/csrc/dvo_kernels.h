@@ -263,6 +263,10 @@ struct GeoSolve {      // last argument of k_gn_solve_z
 // the twins of launch_track_gn / launch_gn_solve with the geometric term (launch pairs only, no mask)
 void launch_track_gn_z(const struct GnArgs& a, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
 void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s);
+// both terms together (dvo_batch_set_geometric_affine): k_track_gn_zab / k_gn_solve_zab, no robust weights
+void launch_track_gn_zab(const struct GnArgs& a, const AffineGn& f, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                         int grid_seqs = 0);
+void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s);
 
 // k_track_persist: the whole of Tracker::track for ONE sequence in one launch (a dvo_vo handle).
 struct PersistLevel {

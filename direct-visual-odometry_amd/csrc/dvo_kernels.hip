@@ -1203,6 +1203,27 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_Z_WAVES : 1
     track_gn_term_body<PPT, G, T2D, true, false, false, true>(a, RobustGn{}, AffineGn{}, zg, lds, mred);
 }
 
+// k_track_gn_zab / k_track_gn_zab_cam: k_track_gn_z / k_track_gn_z_cam with affine brightness compensation on the photometric row
+// (dvo_batch_set_geometric_affine): the body with both flags.  The geometric row does not see the AffineEntry; the
+// moments are k_track_gn_ab's without robust weights.  New kernels beside the others, which stay as they are; no MASK instances.
+#if !defined(DVO_GN_ZAB_WAVES)
+#define DVO_GN_ZAB_WAVES 3   /* the hot <4, 1|2, *> instances: k_track_gn_z's registers and four moment accumulators, no scratch at 3 waves (168 allocatable) */
+#endif
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_ZAB_WAVES : 1) k_track_gn_zab(GnArgs a, AffineGn ag, GeoGn zg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_term_body<PPT, G, T2D, false, false, true, true>(a, RobustGn{}, ag, zg, lds, mred);
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_ZAB_WAVES : 1) k_track_gn_zab_cam(GnArgs a, AffineGn ag, GeoGn zg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ float mred[4][8];
+    track_gn_term_body<PPT, G, T2D, true, false, true, true>(a, RobustGn{}, ag, zg, lds, mred);
+}
+
 template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
                                         float* out_row, const Intr& cam, const RobustEntry& rob, const AffineEntry& ab, float* mom_row,
@@ -1431,13 +1452,16 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
         }
         if (lane == 0 && !ROB) mred[wave][0] = 0.0f;
     }
+    // GEO: where a wave hands over its slots 29 and 30 in mred: beside the five moments when both terms are on (k_track_gn_zab), which
+    // publish mred[wave][0..4] ahead of the same barrier
+    constexpr int ZR = (AB && GEO) ? DVO_AFFINE_MOMENTS : 0;
     if constexpr (GEO) {   // slots 29 and 30: the moments' butterfly (every lane ends with the same bits), lane 0 publishes
         float v29 = S29, v30 = S30;
         v29 += __shfl_xor(v29, 32); v29 += __shfl_xor(v29, 16); v29 += __shfl_xor(v29, 8);
         v29 += __shfl_xor(v29, 4); v29 += __shfl_xor(v29, 2); v29 += __shfl_xor(v29, 1);
         v30 += __shfl_xor(v30, 32); v30 += __shfl_xor(v30, 16); v30 += __shfl_xor(v30, 8);
         v30 += __shfl_xor(v30, 4); v30 += __shfl_xor(v30, 2); v30 += __shfl_xor(v30, 1);
-        if (lane == 0) { mred[wave][0] = v29; mred[wave][1] = v30; }
+        if (lane == 0) { mred[wave][ZR] = v29; mred[wave][ZR + 1] = v30; }
     }
     __syncthreads();
     if (threadIdx.x < 32) {
@@ -1445,7 +1469,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
         float s = 0.0f;
         if (c < 29) s = ((red[0][c] + red[1][c]) + red[2][c]) + red[3][c];
         if constexpr (GEO) {   // the four waves in wave order, into the row's free slots
-            if (c == 29 || c == 30) s = ((mred[0][c - 29] + mred[1][c - 29]) + mred[2][c - 29]) + mred[3][c - 29];
+            if (c == 29 || c == 30) s = ((mred[0][c - 29 + ZR] + mred[1][c - 29 + ZR]) + mred[2][c - 29 + ZR]) + mred[3][c - 29 + ZR];
         }
         out_row[c] = s;
     }
@@ -1915,6 +1939,62 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_z(SolveArgs a, 
     }
     float* last = z.last + 4 * (size_t)my_seq;   // (n_geo, mean_sq, 1 = tracked, 0)
     last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
+}
+
+// k_gn_solve_zab: k_gn_solve_z for a batch that also compensates brightness (k_track_gn_zab's partner): solve_gather sums the 31 slots
+// and, in mid, the brightness moments; the serial lane runs solve_finish, records the geometric sums as k_gn_solve_z does and then keeps
+// the AffineEntry as k_gn_solve_ab does without robust weights (N = n_valid).  The pose and the geometric record first, the closed form
+// last: nothing of it is live across the serial chain of solve_finish.  f.prime: the priming pair -- the entry and prime_ab only.
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_zab(SolveArgs a, AffineSolve f, GeoSolve z)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    __shared__ double mtot[DVO_SOLVE_SEQ][8];
+    int my_seq = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    const auto sum_moments = [&](int t_slot, int c, int team) {   // k_gn_solve_ab's
+        if (c < 8) {
+            const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+            mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
+        }
+    };
+    if (!solve_gather<31>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, sum_moments)) return;
+    const double* t = tot[threadIdx.x];
+    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    if (!f.prime) {
+        Pose np;
+        (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
+        const double S29 = t[29], n_geo = t[30];
+        if (z.sums_out) { z.sums_out[2 * (size_t)my_seq] = n_geo; z.sums_out[2 * (size_t)my_seq + 1] = S29; }
+        if (z.log && it < z.log_its) {
+            float* lg = z.log + (((size_t)my_seq * z.levels + a.level) * z.log_its + it) * 2;
+            lg[0] = (float)n_geo; lg[1] = (float)S29;
+        }
+        float* last = z.last + 4 * (size_t)my_seq;   // (n_geo, mean_sq, 1 = tracked, 0)
+        last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
+    }
+    const double* m = mtot[threadIdx.x];
+    const int n_valid = (int)t[28];
+    const double N = (double)n_valid;
+    const AffineEntry used = f.table[my_seq];
+    AffineEntry next = used;
+    if (f.estimate) affine_next_entry(f, n_valid, N, m, next);
+    if (f.moments_out) {
+        double* mo = f.moments_out + (size_t)my_seq * DVO_AFFINE_MOMENTS;
+        mo[0] = N;
+        for (int i = 1; i < DVO_AFFINE_MOMENTS; i++) mo[i] = m[i];
+    }
+    if (f.estimate) f.table[my_seq] = next;
+    if (f.prime) {
+        f.prime_ab[2 * my_seq] = next.a; f.prime_ab[2 * my_seq + 1] = next.b;
+        return;
+    }
+    if (f.log && it < f.log_its) {
+        float* lg = f.log + (((size_t)my_seq * f.levels + a.level) * f.log_its + it) * 2;
+        lg[0] = used.a; lg[1] = used.b;
+    }
+    f.last[2 * my_seq] = used.a; f.last[2 * my_seq + 1] = used.b;
 }
 
 // k_affine_begin: the AffineEntry table at the start of a tracking call, one thread per sequence.  ESTIMATE: every sequence starts at
@@ -3164,6 +3244,22 @@ void launch_track_gn_z(const GnArgs& a0, const GeoGn& z, int n_seq, int ppt, int
     });
 }
 
+void launch_track_gn_zab(const GnArgs& a0, const AffineGn& f, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                         int grid_seqs)
+{
+    GnArgs a = a0;
+    a.n_seq = n_seq; a.mask = nullptr;
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_zab_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, f, z);
+            else hipLaunchKernelGGL((k_track_gn_zab<PPT, G, T2D>), grid, dim3(256), 0, s, a, f, z);
+        });
+    });
+}
+
 // A solve kernel (k_gn_solve or an opt-in term's) over n_seq sequences, DVO_SOLVE_SEQ per workgroup; extra: the term's argument blocks
 template <class K, class... Extra>
 static void launch_solve_kernel(K kernel, const SolveArgs& a, int n_seq, hipStream_t s, const Extra&... extra)
@@ -3180,6 +3276,10 @@ void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSo
     launch_solve_kernel(k_gn_solve_ab, a, n_seq, s, r, f);
 }
 void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_z, a, n_seq, s, z); }
+void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s)
+{
+    launch_solve_kernel(k_gn_solve_zab, a, n_seq, s, f, z);
+}
 
 void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
 {

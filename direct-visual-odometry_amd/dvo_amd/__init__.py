@@ -176,6 +176,7 @@ EXPORTS = [
     "dvo_op_gn_step_affine",
     "dvo_geometric_config_default", "dvo_batch_set_geometric", "dvo_batch_last_geometric", "dvo_batch_last_geometric_log",
     "dvo_op_gn_step_geometric",
+    "dvo_batch_set_geometric_affine", "dvo_op_gn_step_geometric_affine",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -388,6 +389,24 @@ def op_gn_step_geometric(obj_gray, obj_depth, obj_sigma, ref_gray, ref_depth, K,
     return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
                 xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
                 xi_next=np.array(out.xi_next[:], np.float32), n_geo=int(sums[0]), sum_sq=float(sums[1]))
+
+
+def op_gn_step_geometric_affine(obj_gray, obj_depth, obj_sigma, ref_gray, ref_depth, K, xi, level, weight, max_diff, a, b, cfg=None, dev=0):
+    """op_gn_step_geometric() against the compensated brightness fmaf(a, I1, b) (dvo_op_gn_step_geometric_affine, include/dvo.h): adds
+    `n_geo`, `sum_sq`, `moments` (n_valid, M1, M2, M11, M12 in float64) and `next_ab`."""
+    obj_gray = f32(obj_gray); obj_depth = f32(obj_depth); obj_sigma = f32(obj_sigma); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = GnResult()
+    sums = np.zeros(2, np.float64); mom = np.zeros(5, np.float64); nxt = np.zeros(2, np.float32)
+    DP = C.POINTER(C.c_double)
+    _check(lib().dvo_op_gn_step_geometric_affine(dev, C.byref(cfg) if cfg is not None else None, fp(obj_gray), fp(obj_depth), fp(obj_sigma),
+                                                 fp(ref_gray), fp(ref_depth), w, h, fp(K), fp(xi), level, C.c_float(weight),
+                                                 C.c_float(max_diff), C.c_float(a), C.c_float(b), C.byref(out),
+                                                 sums.ctypes.data_as(DP), mom.ctypes.data_as(DP), fp(nxt)))
+    return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
+                xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
+                xi_next=np.array(out.xi_next[:], np.float32), n_geo=int(sums[0]), sum_sq=float(sums[1]), moments=mom, next_ab=nxt)
 
 
 def track(obj_gray, ref_gray, ref_depth, ref_sigma, K, levels, culls, cfg=None, dev=0):
@@ -813,6 +832,14 @@ class _GeometricTerm:
             return
         c = GeometricConfig(C.sizeof(GeometricConfig), int(mode), float(weight), float(max_diff))
         _check(lib().dvo_batch_set_geometric(self._p, C.byref(c)))
+
+    def set_geometric_affine(self, weight=10.0, max_diff=0.1, affine_mode=AFFINE_ESTIMATE, min_pixels=64, min_contrast=1e-3, gain_min=0.25,
+                             gain_max=4.0):
+        """The geometric term and affine brightness compensation together from the next push on (dvo_batch_set_geometric_affine,
+        include/dvo.h); set_geometric(GEOMETRIC_OFF) / set_affine_brightness(AFFINE_OFF) turn either off again."""
+        g = GeometricConfig(C.sizeof(GeometricConfig), GEOMETRIC_ON, float(weight), float(max_diff))
+        a = AffineConfig(C.sizeof(AffineConfig), int(affine_mode), int(min_pixels), float(min_contrast), float(gain_min), float(gain_max))
+        _check(lib().dvo_batch_set_geometric_affine(self._p, C.byref(g), C.byref(a)))
 
     def last_geometric(self):
         """record array [n_seq] (n_geo, mean_sq) of the finest level's last iteration at the last push (zeros: not tracked); synchronises."""

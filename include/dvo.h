@@ -662,6 +662,30 @@ void dvo_geometric_config_default(dvo_geometric_config* cfg);                   
 int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg);       /* sensor-depth batches; from the next push on */
 int dvo_batch_last_geometric(dvo_batch* b, dvo_geometric_record* rec);            /* [n_seq], host, synchronises */
 int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log);  /* host, synchronises */
+/* ---- the geometric term with affine brightness compensation: sensor-depth batches only ------------------------------------------
+ * dvo_batch_set_geometric_affine turns both terms on together (an RGB-D camera under auto-exposure): the two setters above keep
+ * refusing each other, this call is the one way to the pair.  All arithmetic is float32 and IEEE, with no contraction beyond the
+ * fmaf()s named.  The inputs are the geometric term's: pixel x of the TRACKED frame uses that frame's own depth, weight and gray I1.
+ *   The photometric row is the compensated one on those inputs: c = fmaf(a, I1, b);  r = I2 - c;  rw = r * wgt, slots 0..28, and
+ *   n_valid, the residual and the stop tests as under dvo_batch_set_affine_brightness.
+ *   The brightness moments are the ones without robust weights (M1, M2, M11, M12, N = n_valid) over the same contributing pixels,
+ *   reduced in their own fixed order; the closed form and its guards are unchanged.
+ *   The geometric row does not see (a, b): it is dvo_batch_set_geometric's bit for bit (slots 0..26, S29, S30, the same gates), and a
+ *   pixel without a geometric row adds exact zeros.
+ *   DVO_AFFINE_ESTIMATE runs the priming pair on the coarsest level at the start pose; the pair writes the affine entry and nothing
+ *   else: no pose, no track log, no geometric record or log, no affine log slot.
+ * Anchors: (a, b) = (1, 0) makes every sum the geometric term's alone, bit for bit; weight = 0 makes the 27 sums and the moments
+ * the affine estimator's on own-depth inputs, bit for bit.
+ * geo->mode must be DVO_GEOMETRIC_ON and aff->mode DVO_AFFINE_ESTIMATE or DVO_AFFINE_GIVEN.  Takes effect from the next push; the
+ * call may be repeated to reconfigure, whatever the state of the two terms.  Turning off and reading back use what exists:
+ * dvo_batch_set_geometric(OFF / NULL) leaves the affine family on, dvo_batch_set_affine_brightness(OFF / NULL) leaves the geometric
+ * family on, dvo_batch_set_affine_rows gives the rows of the GIVEN mode, and dvo_batch_last_affine, dvo_batch_last_affine_log,
+ * dvo_batch_last_geometric and dvo_batch_last_geometric_log read what they document: both terms are ready after a composed push.
+ * While on, every level runs launch pairs (k_track_gn_zab + k_gn_solve_zab).
+ * Errors, returned before anything is enqueued: a NULL handle or a NULL config, either config failing its own setter's checks, a
+ * mode that is off, a mono batch, robust weights on (dvo_batch_set_robust_weights keeps refusing while the geometric term is on)
+ * -> DVO_ERR_BAD_ARGUMENT.  Robust weights with the geometric term, mono batches and dvo_vo handles are out of scope. */
+int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo, const dvo_affine_config* aff);
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */
@@ -721,6 +745,13 @@ int dvo_op_gn_step_geometric(int dev, const dvo_config* cfg, const float* obj_gr
                              const float* obj_sigma, const float* ref_gray, const float* ref_depth, int w, int h,
                              const float K[9], const float xi[6], int level, float weight, float max_diff,
                              dvo_gn_result* out, double sums[2]);
+/* The pair with both terms (dvo_batch_set_geometric_affine) run once on host pointers: dvo_op_gn_step_geometric's inputs with the
+ * entry (a, b) of dvo_op_gn_step_affine, kind DVO_ROBUST_NONE.  sums = (n_geo, S29); moments = (n_valid, M1, M2, M11, M12); next_ab
+ * under dvo_op_gn_step_affine's guards. */
+int dvo_op_gn_step_geometric_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth,
+                                    const float* obj_sigma, const float* ref_gray, const float* ref_depth, int w, int h,
+                                    const float K[9], const float xi[6], int level, float weight, float max_diff,
+                                    float a, float b, dvo_gn_result* out, double sums[2], double moments[5], float next_ab[2]);
 /* Tracker::track, src/track/tracker.cpp:22-85, on full-resolution frames (pyramids built on device). */
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                  const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],

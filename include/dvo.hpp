@@ -224,6 +224,14 @@ public:
         dvo_geometric_config c{(int)sizeof(dvo_geometric_config), mode, weight, max_diff};
         check(dvo_batch_set_geometric(b_, &c));
     }
+    // both together from the next push on (dvo_batch_set_geometric_affine); setGeometric(OFF) / setAffineBrightness(OFF) turn either off
+    void setGeometricAffine(float weight = 10.0f, float max_diff = 0.1f, int affine_mode = DVO_AFFINE_ESTIMATE, int min_pixels = 64,
+                            float min_contrast = 1e-3f, float gain_min = 0.25f, float gain_max = 4.0f)
+    {
+        dvo_geometric_config g{(int)sizeof(dvo_geometric_config), DVO_GEOMETRIC_ON, weight, max_diff};
+        dvo_affine_config a{(int)sizeof(dvo_affine_config), affine_mode, min_pixels, min_contrast, gain_min, gain_max};
+        check(dvo_batch_set_geometric_affine(b_, &g, &a));
+    }
     std::vector<dvo_geometric_record> lastGeometric()   // [n_seq]
     {
         std::vector<dvo_geometric_record> out(n_);

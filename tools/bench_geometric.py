@@ -13,7 +13,11 @@ the finest level's kernel -- k_track_gn<4, 2, false, true> against k_track_gn_z<
 k_gn_solve_z): calls, total and average time per launch.  No cost is promised: the figures are against the plain kernel of the same
 build, and the spread of the plain rounds stands beside them.  Prints one JSON line.
 
-    python tools/bench_geometric.py --steps 8 --warmup 3 --rounds 3 --trace [--fixed-iterations 4]
+--composed adds a third estimator to the rounds (and to --trace): the geometric term with affine brightness compensation
+(dvo_batch_set_geometric_affine; ESTIMATE mode, default guards), k_track_gn_zab<4, 2, true> and k_gn_solve_zab, with
+its ratio against the geometric estimator of the same rounds and that estimator's own spread.  Without the flag nothing of it runs.
+
+    python tools/bench_geometric.py --steps 8 --warmup 3 --rounds 3 --trace [--fixed-iterations 4] [--composed]
 """
 import argparse
 import csv
@@ -36,8 +40,9 @@ from dvo_amd import synth
 
 F, W, H = 3, 640, 480
 MODES = ["plain", "geometric"]
-FINEST = {"plain": "dvo::k_track_gn<4, 2, false, true>(", "geometric": "dvo::k_track_gn_z<4, 2, true>("}
-SOLVE = {"plain": "dvo::k_gn_solve(", "geometric": "dvo::k_gn_solve_z("}
+COMPOSED = "geometric_affine"
+FINEST = {"plain": "dvo::k_track_gn<4, 2, false, true>(", "geometric": "dvo::k_track_gn_z<4, 2, true>(", COMPOSED: "dvo::k_track_gn_zab<4, 2, true>("}
+SOLVE = {"plain": "dvo::k_gn_solve(", "geometric": "dvo::k_gn_solve_z(", COMPOSED: "dvo::k_gn_solve_zab("}
 
 
 def frames(B, U, dev):
@@ -55,7 +60,10 @@ def frames(B, U, dev):
 
 def run(mode, a, B, g8, d16, stream):
     h = dvo.Batch(B, synth.K_640, W, H, 4, 1, cfg=dvo.default_config(stream=stream, fixed_iterations=a.fixed_iterations))
-    if mode != "plain":
+    if mode == COMPOSED:
+        c = dvo.geometric_default_config()
+        h.set_geometric_affine(c.weight, c.max_diff)
+    elif mode != "plain":
         c = dvo.geometric_default_config()
         h.set_geometric(c.mode, c.weight, c.max_diff)
     ev = []
@@ -112,8 +120,10 @@ def main():
                     help="N > 0: every level runs N iterations of every sequence, so both estimators run the same launches on the same "
                          "number of sequences and the per-launch times compare like for like; 0: bench.py's stop tests")
     ap.add_argument("--trace", action="store_true", help="also one traced child run per estimator (rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--composed", action="store_true", help="also the geometric term with affine brightness compensation, as a third estimator")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    modes = MODES + [COMPOSED] if a.composed else MODES
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     g8, d16 = frames(a.batch, a.unique, dev)
@@ -121,20 +131,23 @@ def main():
     if a.child:
         run(a.child, a, a.batch, g8, d16, stream)
         return 0
-    res = {m: [] for m in MODES}
+    res = {m: [] for m in modes}
     for _ in range(a.rounds):
-        for m in MODES:
+        for m in modes:
             res[m].append(run(m, a, a.batch, g8, d16, stream))
-    med = {m: float(np.median(res[m])) for m in MODES}
+    med = {m: float(np.median(res[m])) for m in modes}
     out = {"batch": a.batch, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "fixed_iterations": a.fixed_iterations,
-           "ms_per_push": {m: round(med[m], 3) for m in MODES},
-           "all_rounds": {m: [round(x, 3) for x in res[m]] for m in MODES},
+           "ms_per_push": {m: round(med[m], 3) for m in modes},
+           "all_rounds": {m: [round(x, 3) for x in res[m]] for m in modes},
            "plain_spread_ms": round(max(res["plain"]) - min(res["plain"]), 3),
-           "vs_plain": {m: round(med[m] / med["plain"], 4) for m in MODES[1:]}}
+           "vs_plain": {m: round(med[m] / med["plain"], 4) for m in modes[1:]}}
+    if a.composed:
+        out["geometric_spread_ms"] = round(max(res["geometric"]) - min(res["geometric"]), 3)
+        out["vs_geometric"] = {COMPOSED: round(med[COMPOSED] / med["geometric"], 4)}
     del g8, d16
     torch.cuda.empty_cache()
     if a.trace:
-        out["kernels"] = {m: trace(m, a) for m in MODES}
+        out["kernels"] = {m: trace(m, a) for m in modes}
     print(json.dumps(out))
     return 0
 
