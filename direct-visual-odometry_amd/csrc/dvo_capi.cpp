@@ -336,13 +336,14 @@ int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* de
     DVO_NOT_MONO(b);
     Batch& B = b->impl;
     if (seq < 0 || seq >= B.n_seq || level < 0 || level >= B.g.levels) return DVO_ERR_BAD_ARGUMENT;
-    if (B.kf_on) { set_error("dvo_batch_frame_get: keyframe tracking is on (dvo_batch_keyframe_get reads the keyframes)"); return DVO_ERR_BAD_ARGUMENT; }
     if (B.cur < 0) return DVO_ERR_NOT_READY;
     DVO_TRY(select_device(B.device));
     // (in stream order after the push, which has queued the wait for a split build's side stream)
+    // keyframe tracking: fs[cur] holds the keyframes; the last push's frame is in fs[prev] (the first push's frame is the keyframe)
+    const FrameSet& F = B.fs[(B.kf_on && B.prev >= 0) ? B.prev : B.cur];
     const size_t n = (size_t)B.g.w[level] * B.g.h[level], off = n * (size_t)seq;
-    if (gray) DVO_HIP(hipMemcpyAsync(gray, B.fs[B.cur].gray[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
-    if (depth) DVO_HIP(hipMemcpyAsync(depth, B.fs[B.cur].depth[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    if (gray) DVO_HIP(hipMemcpyAsync(gray, F.gray[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
+    if (depth) DVO_HIP(hipMemcpyAsync(depth, F.depth[level] + off, n * 4, hipMemcpyDeviceToHost, B.stream));
     DVO_HIP(hipStreamSynchronize(B.stream));
     return DVO_OK;
 }
@@ -377,6 +378,68 @@ int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable)
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (b->mono) { set_error("dvo_batch_set_keyframe_tracking: needs a sensor-depth batch (a mono batch always tracks against keyframes)"); return DVO_ERR_BAD_ARGUMENT; }
     return b->impl.set_keyframe_tracking(enable);
+}
+
+void dvo_kf_fusion_config_default(dvo_kf_fusion_config* cfg)
+{
+    if (!cfg) return;
+    cfg->mode = DVO_KF_FUSION_ON;
+    cfg->max_diff = 0.05f;
+    cfg->max_count = 16;
+}
+
+// the checks every keyframe-fusion entry point shares: a sensor-depth batch with keyframe tracking
+static int kf_fusion_handle_ok(dvo_batch* b, const char* who)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error(std::string(who) + ": needs a sensor-depth batch (a mono batch refines its keyframe maps itself)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->impl.kf_on) { set_error(std::string(who) + ": keyframe tracking is off (dvo_batch_set_keyframe_tracking)"); return DVO_ERR_NOT_READY; }
+    return DVO_OK;
+}
+
+int dvo_batch_set_keyframe_fusion(dvo_batch* b, const dvo_kf_fusion_config* cfg)
+{
+    static const char who[] = "dvo_batch_set_keyframe_fusion";
+    DVO_TRY(kf_fusion_handle_ok(b, who));
+    if (cfg) {
+        if (cfg->mode != DVO_KF_FUSION_OFF && cfg->mode != DVO_KF_FUSION_ON) { set_error(std::string(who) + ": the mode is DVO_KF_FUSION_OFF or DVO_KF_FUSION_ON"); return DVO_ERR_BAD_ARGUMENT; }
+        if (!(cfg->max_diff > 0.0f && cfg->max_diff < __builtin_inff())) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+        if (cfg->max_count < 1 || cfg->max_count > 255) { set_error(std::string(who) + ": max_count must be in [1, 255]"); return DVO_ERR_BAD_ARGUMENT; }
+    }
+    return b->impl.set_keyframe_fusion(cfg);
+}
+
+int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec)
+{
+    static const char who[] = "dvo_batch_last_keyframe_fusion";
+    if (!rec) return DVO_ERR_BAD_ARGUMENT;
+    DVO_TRY(kf_fusion_handle_ok(b, who));
+    Batch& B = b->impl;
+    if (!B.fuse.ready) { set_error(std::string(who) + ": the last push did not run with keyframe fusion (dvo_batch_set_keyframe_fusion)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(B.device));
+    std::vector<KfFuseRecord> host((size_t)B.n_seq);
+    DVO_HIP(hipMemcpyAsync(host.data(), B.fuse.rec.p, sizeof(KfFuseRecord) * host.size(), hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    for (size_t i = 0; i < host.size(); i++) {
+        rec[i].struct_size = (int)sizeof(dvo_kf_fusion_record);
+        rec[i].n_candidates = host[i].n_candidates; rec[i].n_fused = host[i].n_fused; rec[i].n_gated = host[i].n_gated;
+    }
+    return DVO_OK;
+}
+
+int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts)
+{
+    static const char who[] = "dvo_batch_keyframe_fusion_counts";
+    if (!counts) return DVO_ERR_BAD_ARGUMENT;
+    DVO_TRY(kf_fusion_handle_ok(b, who));
+    Batch& B = b->impl;
+    if (seq < 0 || seq >= B.n_seq) { set_error(std::string(who) + ": seq is out of range"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!B.fuse.ran) { set_error(std::string(who) + ": no push has run with keyframe fusion yet (dvo_batch_set_keyframe_fusion)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(B.device));
+    const size_t n = (size_t)B.g.w[B.g.top()] * B.g.h[B.g.top()];
+    DVO_HIP(hipMemcpyAsync(counts, B.fuse.counts.as<uint8_t>() + n * (size_t)seq, n, hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    return DVO_OK;
 }
 
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)

@@ -2283,7 +2283,7 @@ int Batch::update_keyframes(int frame_set)
     ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
     ma.n_seq = n_seq; ma.R = 1; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
     launch_kf_decide(ma, stream);
-    if (frame_set == kf) return DVO_OK;
+    if (frame_set == kf) return fuse_keyframes(frame_set, kf);   // (the first push: every sequence starts or stays empty)
     const FrameSet& src = fs[frame_set];
     FrameSet& dst = fs[kf];
     const float* from[3 * DVO_MAX_LEVELS];
@@ -2306,6 +2306,50 @@ int Batch::update_keyframes(int frame_set)
         pa.meta = kf_meta.as<MonoSeq>(); pa.all = 0; pa.need_list = need_list.as<int>();
         launch_promote(pa, stream);
     }
+    return fuse_keyframes(frame_set, kf);
+}
+
+// ------------------------------------------------------------------------------------------------ batch: keyframe depth fusion
+int Batch::set_keyframe_fusion(const dvo_kf_fusion_config* c)
+{
+    const bool enable = c && c->mode == DVO_KF_FUSION_ON;
+    if (enable && !fuse.on) {   // off -> on: the counts (re)start at 0
+        DVO_TRY(select_device(device));
+        const size_t n = (size_t)n_seq, npix = (size_t)g.w[g.top()] * g.h[g.top()];
+        if (!fuse.counts.p) {
+            DVO_TRY(fuse.counts.alloc(n * npix));
+            DVO_TRY(fuse.table.alloc(sizeof(KfFuseSeq) * n));
+            DVO_TRY(fuse.rec.alloc(sizeof(KfFuseRecord) * n));
+        }
+        DVO_HIP(hipMemsetAsync(fuse.counts.p, 0, n * npix, stream));
+    }
+    if (enable) fuse.cfg = *c;
+    fuse.on = enable;
+    return DVO_OK;
+}
+
+// After k_kf_decide and the promotions: k_kf_fuse_prep resolves every sequence to clear / fuse / nothing from what k_kf_decide left,
+// k_kf_fuse works on the top level of fs[kf] in place and gathers from fs[frame_set] (on the first push the two are one set, and no
+// sequence can fuse: none had a keyframe to track against).
+int Batch::fuse_keyframes(int frame_set, int kf)
+{
+    fuse.ready = fuse.on;
+    if (!fuse.on) return DVO_OK;
+    fuse.ran = true;
+    KfFusePrepArgs pa{};
+    pa.meta = kf_meta.as<MonoSeq>(); pa.eff = plan.eff.as<uint8_t>(); pa.is_key = is_key.as<int>();
+    pa.table = fuse.table.as<KfFuseSeq>(); pa.rec = fuse.rec.as<KfFuseRecord>(); pa.n_seq = n_seq;
+    launch_kf_fuse_prep(pa, stream);
+    KfFuseArgs a{};
+    const int T = g.top();
+    for (int l = 0; l < g.levels; l++) { a.kf_depth[l] = fs[kf].depth[l]; a.w[l] = g.w[l]; a.h[l] = g.h[l]; }
+    a.frame_depth = fs[frame_set].depth[T];
+    a.counts = fuse.counts.as<uint8_t>(); a.table = fuse.table.as<KfFuseSeq>(); a.rec = fuse.rec.as<KfFuseRecord>();
+    a.seq_k = cam_table() ? cam_table() + (size_t)T * n_seq : nullptr;
+    a.k = g.k[T];
+    a.levels = g.levels; a.n_seq = n_seq;
+    a.min_depth = cfg.min_depth; a.max_diff = fuse.cfg.max_diff; a.max_count = fuse.cfg.max_count;
+    launch_kf_fuse(a, stream);
     return DVO_OK;
 }
 

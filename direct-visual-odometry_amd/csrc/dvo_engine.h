@@ -644,6 +644,18 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     DevBuf kf_meta, xi_world, T_world, is_key, need_list;   // MonoSeq [n_seq]; [n_seq][6], [n_seq][16], [n_seq]; [4 + n_seq]
     int set_keyframe_tracking(int enable);
     int update_keyframes(int frame_set);                     // k_kf_decide, then k_promote from fs[frame_set] into fs[cur]
+    // Keyframe depth fusion (dvo_batch_set_keyframe_fusion): after the promotions of a push, k_kf_fuse_prep and k_kf_fuse
+    // fold the tracked frame's top-level depth into the keyframes of the sequences that tracked without firing the rule, and clear the
+    // counts of those that started or promoted.  Off (the default): update_keyframes launches what it always launched.
+    struct KfFusion {
+        bool on = false;
+        bool ready = false;      // the last push ran with fusion on (dvo_batch_last_keyframe_fusion)
+        bool ran = false;        // some push ran with fusion on (dvo_batch_keyframe_fusion_counts)
+        dvo_kf_fusion_config cfg = {DVO_KF_FUSION_OFF, 0.05f, 16};
+        DevBuf counts, table, rec;   // uint8 [n_seq][h_top][w_top]; KfFuseSeq [n_seq]; KfFuseRecord [n_seq]
+    } fuse;
+    int set_keyframe_fusion(const dvo_kf_fusion_config* c);  // (validated by the caller)
+    int fuse_keyframes(int frame_set, int kf);
 };
 
 int select_device(int device);

@@ -547,6 +547,43 @@ void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s);
 // xi_world, T_world, is_key, need_list (TRACK sequences whose rule fired, and the starts), n_seq, max_frames, min_translation
 // (started, need_save, hist_xi and R are not used: a sequence has started once MonoSeq::n_total > 0)
 void launch_kf_decide(const MonoPlanArgs& a, hipStream_t s);
+
+// ---- keyframe depth fusion of a sensor-depth batch (dvo_batch_set_keyframe_fusion) --------------------------------
+// k_kf_fuse_prep (one thread per sequence, after k_kf_decide) turns what k_kf_decide left -- eff, is_key, MonoSeq::rel_xi / rel_pose --
+// into one table entry per sequence and zeroes its record; k_kf_fuse reads the entry with a scalar load and clears, fuses or leaves.
+#define DVO_KF_FUSE_NONE  0   /* SKIP / BAD_ACTION, or a non-finite twist: nothing of the sequence is read or written */
+#define DVO_KF_FUSE_CLEAR 1   /* a start or a promotion: the count plane becomes 0 */
+#define DVO_KF_FUSE_FUSE  2
+struct KfFuseSeq {
+    Pose F;     // float(exp(+xi)): MonoSeq::rel_pose, the T_rel of the push
+    Pose Bk;    // float(exp(-xi)): pose_from_xi(xi, -1), what the tracker's kernels transform with
+    int mode;
+    int pad[3];
+};
+struct KfFuseRecord { int n_candidates, n_fused, n_gated, pad; };
+struct KfFusePrepArgs {
+    const MonoSeq* meta;
+    const uint8_t* eff;      // [n_seq] effective action of the push (k_plan)
+    const int* is_key;       // [n_seq] k_kf_decide's keyframe flag
+    KfFuseSeq* table;        // [n_seq]
+    KfFuseRecord* rec;       // [n_seq]
+    int n_seq;
+};
+struct KfFuseArgs {
+    float* kf_depth[DVO_MAX_LEVELS];   // the keyframe set's depth pyramid, [n_seq][h_l][w_l], updated in place
+    const float* frame_depth;          // the tracked set's top-level depth [n_seq][h][w] (never the keyframe set when a sequence fuses)
+    uint8_t* counts;                   // [n_seq][h][w]
+    const KfFuseSeq* table;
+    KfFuseRecord* rec;
+    const Intr* seq_k = nullptr;       // per-sequence top-level intrinsics [n_seq] (k_kf_fuse_cam), else k
+    Intr k;
+    int w[DVO_MAX_LEVELS], h[DVO_MAX_LEVELS], levels, n_seq;
+    float inv_w = 0.0f;                // 1 / top-level width (set by launch_kf_fuse)
+    float min_depth, max_diff;
+    int max_count;
+};
+void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s);
+void launch_kf_fuse(const KfFuseArgs& a, hipStream_t s);
 // k_regularize_redecimate_plan: k_regularize_redecimate for the TRACK sequences; a SKIP sequence copies its top-level depth forward to
 // depth_top_out (nothing else is written); a RESTART sequence starts: its keyframe becomes the frame's gray pyramid (ring slot 0 too),
 // the start map's depth and sigma with every level re-decimated and the weights, age 0 (the first frame of system.hpp:49-54).

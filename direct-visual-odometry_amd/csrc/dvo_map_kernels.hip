@@ -867,7 +867,175 @@ __global__ void __launch_bounds__(256) k_broadcast(const float* __restrict__ src
     dst[(size_t)seq * count + i] = src[i];
 }
 
+// ------------------------------------------------------------------------------------------------
+// Keyframe depth fusion of a sensor-depth batch (dvo_batch_set_keyframe_fusion; the contract is in include/dvo.h).
+// k_kf_fuse_prep: what k_kf_decide left of the push, as one table entry per sequence -- clear (a start or a promotion), fuse (TRACK,
+// rule not fired, finite twist: F = MonoSeq::rel_pose = float(exp(+xi)), Bk = float(exp(-xi)) through the same double-precision chain)
+// or nothing -- and the sequence's record zeroed.  k_kf_decide itself is not touched.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_kf_fuse_prep(KfFusePrepArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    const MonoSeq& m = a.meta[s];
+    const int eff = a.eff[s];
+    KfFuseSeq e;
+    for (int i = 0; i < 9; i++) { e.F.R[i] = 0.0f; e.Bk.R[i] = 0.0f; }
+    for (int i = 0; i < 3; i++) { e.F.t[i] = 0.0f; e.Bk.t[i] = 0.0f; e.pad[i] = 0; }
+    e.mode = DVO_KF_FUSE_NONE;
+    if (eff == DVO_SEQ_RESTART || (eff == DVO_SEQ_TRACK && a.is_key[s])) {
+        e.mode = DVO_KF_FUSE_CLEAR;
+    } else if (eff == DVO_SEQ_TRACK) {
+        float xi[6];
+        bool finite = true;
+        for (int i = 0; i < 6; i++) { xi[i] = m.rel_xi[i]; finite = finite && isfinite(xi[i]); }
+        if (finite) {
+            e.mode = DVO_KF_FUSE_FUSE;
+            e.F = m.rel_pose;
+            pose_from_xi(xi, -1.0f, e.Bk);
+        }
+    }
+    a.table[s] = e;
+    KfFuseRecord z;
+    z.n_candidates = 0; z.n_fused = 0; z.n_gated = 0; z.pad = 0;
+    a.rec[s] = z;
+}
+
+// k_kf_fuse: four consecutive top-level pixels per lane, the plane addressed linearly (a sequence's plane starts on a 4-byte boundary
+// only: the 16-byte and 4-byte accesses are declared unaligned); the last lane of a plane whose size is no multiple of 4 goes pixel by
+// pixel.  A pixel reads and writes its own keyframe depth and count and gathers four taps from the tracked frame's map, which nobody
+// writes: in place, no float atomics, no LDS.  The three counters are summed per wave (one packed butterfly) and added with integer
+// atomics: order-free.
+typedef float kf_f4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t kf_u32 __attribute__((aligned(1)));
+#define DVO_KF_FUSE_PER_THREAD 4
+
+template <bool PCAM>
+__device__ __forceinline__ void kf_fuse(KfFuseArgs a)
+{
+    const int seq = grid_seq();
+    if (seq >= a.n_seq) return;
+    const KfFuseSeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
+    if (e.mode == DVO_KF_FUSE_NONE) return;
+    const int T = a.levels - 1, w = a.w[T], h = a.h[T], n = w * h;
+    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_KF_FUSE_PER_THREAD;
+    const int nk = i0 >= n ? 0 : (n - i0 < DVO_KF_FUSE_PER_THREAD ? n - i0 : DVO_KF_FUSE_PER_THREAD);
+    const bool full = nk == DVO_KF_FUSE_PER_THREAD;
+    const size_t base = (size_t)seq * n;
+    uint8_t* cnt = a.counts + base + (nk ? i0 : 0);
+    if (e.mode == DVO_KF_FUSE_CLEAR) {
+        if (full) *reinterpret_cast<kf_u32*>(cnt) = 0u;
+        else for (int k = 0; k < nk; k++) cnt[k] = 0;
+        return;
+    }
+    Intr cam;
+    if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
+    float* kd = a.kf_depth[T] + base + (nk ? i0 : 0);
+    const float* __restrict__ fd = a.frame_depth + base;
+    float d[DVO_KF_FUSE_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t c4 = 0;
+    if (full) {
+        const kf_f4 v = *reinterpret_cast<const kf_f4*>(kd);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        c4 = *reinterpret_cast<const kf_u32*>(cnt);
+    } else {
+        for (int k = 0; k < nk; k++) { d[k] = kd[k]; c4 |= (uint32_t)cnt[k] << (8 * k); }
+    }
+    int x, y;
+    split_row(nk ? i0 : 0, w, a.inv_w, x, y);
+    const float md = a.min_depth, inf = __builtin_inff();
+    const float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    int tally = 0;   // candidates | fused << 10 | gated << 20 (at most 4 of each per lane, 256 per wave)
+#pragma unroll
+    for (int k = 0; k < DVO_KF_FUSE_PER_THREAD; k++) {
+        const float dk = d[k];
+        if (k < nk && dk >= md) {
+            tally += 1;
+            float X, Y, Z, Xf, Yf, Zf;
+            back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, dk, X, Y, Z);
+            transform(e.F, X, Y, Z, Xf, Yf, Zf);
+            if (Zf >= md) {
+                float u, v;
+                project(map_intr<PCAM>(a, cam), Xf, Yf, Zf, u, v);
+                if (u >= 0.0f && u < wmax && v >= 0.0f && v < hmax) {
+                    const int x0 = (int)u, y0 = (int)v;
+                    const float fa = u - (float)x0, fb = v - (float)y0;
+                    const float* p = fd + (size_t)y0 * w + x0;
+                    const float z00 = p[0], z10 = p[1], z01 = p[w], z11 = p[w + 1];
+                    bool ok = (z00 >= md) & (z00 < inf) & (z10 >= md) & (z10 < inf) & (z01 >= md) & (z01 < inf) & (z11 >= md) & (z11 < inf);
+                    const float mx = fmaxf(fmaxf(z00, z10), fmaxf(z01, z11)), mn = fminf(fminf(z00, z10), fminf(z01, z11));
+                    ok = ok && (mx - mn <= a.max_diff);
+                    if (ok) {
+                        const float top = fmaf(fa, z10 - z00, z00), bot = fmaf(fa, z11 - z01, z01);
+                        const float zi = fmaf(fb, bot - top, top);
+                        if (fabsf(zi - Zf) <= a.max_diff) {
+                            float Xo, Yo, Zo;
+                            back_project(map_intr<PCAM>(a, cam), u, v, zi, X, Y, Z);
+                            transform(e.Bk, X, Y, Z, Xo, Yo, Zo);
+                            if (Zo >= md && Zo < inf) {
+                                const int c = (int)((c4 >> (8 * k)) & 0xffu);
+                                const float r = recip_rn((float)(c + 2));
+                                const float dn = fmaf(Zo - dk, r, dk);
+                                const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
+                                d[k] = dn;
+                                c4 = (c4 & ~(0xffu << (8 * k))) | ((uint32_t)cn << (8 * k));
+                                tally += 1 << 10;
+                                for (int t = 1; t < a.levels; t++) {   // lower levels keep pixels whose coordinates are multiples of 2^t
+                                    const int msk = (1 << t) - 1;
+                                    if ((x & msk) | (y & msk)) break;
+                                    const int l = T - t, lx = x >> t, ly = y >> t;
+                                    if (lx >= a.w[l] || ly >= a.h[l]) continue;
+                                    a.kf_depth[l][(size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx] = dn;
+                                }
+                            }
+                        } else {
+                            tally += 1 << 20;
+                        }
+                    }
+                }
+            }
+        }
+        x++;
+        if (x == w) { x = 0; y++; }
+    }
+    if (tally & (0x3ff << 10)) {   // something fused: the lane's pixels and counts go back
+        if (full) {
+            kf_f4 v;
+            v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
+            *reinterpret_cast<kf_f4*>(kd) = v;
+            *reinterpret_cast<kf_u32*>(cnt) = c4;
+        } else {
+            for (int k = 0; k < nk; k++) { kd[k] = d[k]; cnt[k] = (uint8_t)(c4 >> (8 * k)); }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) tally += __shfl_xor(tally, o);   // (every lane of the wave is here: no lane left early)
+    if ((threadIdx.x & 63) == 0) {
+        KfFuseRecord* r = a.rec + seq;
+        if (tally & 0x3ff) atomicAdd(&r->n_candidates, tally & 0x3ff);
+        if ((tally >> 10) & 0x3ff) atomicAdd(&r->n_fused, (tally >> 10) & 0x3ff);
+        if ((tally >> 20) & 0x3ff) atomicAdd(&r->n_gated, (tally >> 20) & 0x3ff);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_kf_fuse(KfFuseArgs a) { kf_fuse<false>(a); }
+__global__ void __launch_bounds__(256) k_kf_fuse_cam(KfFuseArgs a) { kf_fuse<true>(a); }
+
 // ------------------------------------------------------------------------------------------------ launch wrappers
+void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kf_fuse_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_kf_fuse(const KfFuseArgs& a0, hipStream_t s)
+{
+    KfFuseArgs a = a0;
+    const int T = a.levels - 1;
+    a.inv_w = 1.0f / (float)a.w[T];
+    const dim3 grid = seq_grid(cdiv_u(a.w[T] * a.h[T], 256 * DVO_KF_FUSE_PER_THREAD), (unsigned)a.n_seq);
+    if (a.seq_k) hipLaunchKernelGGL(k_kf_fuse_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+    else hipLaunchKernelGGL(k_kf_fuse, grid, dim3(256), 0, s, a);
+}
+
 void launch_mono_decide(MonoSeq* meta, const SeqState* state, int n_seq, int frame_id, float min_translation, int max_frames,
                         float* xi_world, float* T_world, int* is_key, const MonoRef* host_ref, hipStream_t s, int* need_list)
 {

@@ -177,6 +177,7 @@ EXPORTS = [
     "dvo_geometric_config_default", "dvo_batch_set_geometric", "dvo_batch_last_geometric", "dvo_batch_last_geometric_log",
     "dvo_op_gn_step_geometric",
     "dvo_batch_set_geometric_affine", "dvo_op_gn_step_geometric_affine",
+    "dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -194,6 +195,19 @@ ROBUST_SCALE_ADAPTIVE, ROBUST_SCALE_GIVEN = 0, 1
 AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
 # the geometric (depth) term (Batch.set_geometric): include/dvo.h
 GEOMETRIC_OFF, GEOMETRIC_ON = 0, 1
+# keyframe depth fusion (Batch.set_keyframe_fusion): include/dvo.h
+KF_FUSION_OFF, KF_FUSION_ON = 0, 1
+
+
+class KfFusionConfig(C.Structure):
+    _fields_ = [("mode", C.c_int), ("max_diff", C.c_float), ("max_count", C.c_int)]
+
+
+class KfFusionRecord(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("n_candidates", C.c_int), ("n_fused", C.c_int), ("n_gated", C.c_int)]
+
+
+KF_FUSION_RECORD_DTYPE = np.dtype([("struct_size", np.int32), ("n_candidates", np.int32), ("n_fused", np.int32), ("n_gated", np.int32)])
 
 _lib = None
 
@@ -856,6 +870,32 @@ class _GeometricTerm:
         return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), n_geo=rec["n_geo"].copy(), sum_sq=rec["sum_sq"].copy())
 
 
+class _KeyframeFusion:
+    """Depth fusion into the keyframes of a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_fusion, include/dvo.h)."""
+
+    def set_keyframe_fusion(self, mode=KF_FUSION_ON, max_diff=0.05, max_count=16):
+        """KF_FUSION_ON: every later push folds the tracked frame's depth into the keyframe it was tracked against (a running mean per
+        pixel, gated by max_diff metres, at most max_count samples of memory); KF_FUSION_OFF or None: stop, the maps stay as they are."""
+        if mode is None:
+            _check(lib().dvo_batch_set_keyframe_fusion(self._p, None))
+            return
+        c = KfFusionConfig(int(mode), float(max_diff), int(max_count))
+        _check(lib().dvo_batch_set_keyframe_fusion(self._p, C.byref(c)))
+
+    def last_keyframe_fusion(self):
+        """record array [n_seq] (n_candidates, n_fused, n_gated) of the last push (zeros: started, promoted or skipped); synchronises."""
+        rec = np.zeros(self.n_seq, KF_FUSION_RECORD_DTYPE)
+        _check(lib().dvo_batch_last_keyframe_fusion(self._p, rec.ctypes.data_as(C.POINTER(KfFusionRecord))))
+        return rec
+
+    def keyframe_fusion_counts(self, seq):
+        """uint8 [h_top, w_top]: how many samples each pixel of sequence `seq`'s keyframe depth has fused (capped at max_count)."""
+        shift = self.culls
+        c = np.zeros((self.height >> shift, self.width >> shift), np.uint8)
+        _check(lib().dvo_batch_keyframe_fusion_counts(self._p, int(seq), c.ctypes.data_as(C.c_void_p)))
+        return c
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -869,7 +909,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm, _KeyframeFusion):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -1005,7 +1045,8 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrigh
         return dict(gray=g, depth=d, xi=xi, id=i.value, n_keyframes=n.value)
 
     def frame(self, seq, level=None):
-        """Gray and depth of `level` (default: the finest) of the last pushed frame of sequence `seq`: the next push's reference."""
+        """Gray and depth of `level` (default: the finest) of the last pushed frame of sequence `seq`: the next push's reference (with
+        keyframe tracking: the frame the last push tracked; the references are the keyframes)."""
         level = self.levels - 1 if level is None else level
         if not 0 <= level < self.levels:
             raise ValueError("frame: level %d is outside [0, %d)" % (level, self.levels))

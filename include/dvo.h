@@ -176,8 +176,9 @@ int dvo_batch_copy_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_dst_de
 int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log);
 int dvo_batch_synchronize(dvo_batch* b);
 /* gray and depth [h][w] of pyramid level `level` (0 = coarsest) of the frame the last push gave sequence `seq` = the reference of the
- * next push (synchronises); either pointer may be NULL.  DVO_ERR_NOT_READY before the first push; with keyframe tracking the
- * references are the keyframes (dvo_batch_keyframe_get): DVO_ERR_BAD_ARGUMENT. */
+ * next push (synchronises); either pointer may be NULL.  DVO_ERR_NOT_READY before the first push.  With keyframe tracking the
+ * references are the keyframes (dvo_batch_keyframe_get) and this returns the frame of the last push, the one it tracked (a SKIPPED
+ * sequence's slot holds a copy of its keyframe as it was before the push). */
 int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* depth);
 /* ---- per-sequence skip and restart (sensor-depth batches) -------------------------------------------------------------------
  * dvo_batch_set_actions gives every sequence an action for the NEXT push (any of dvo_batch_push_device / _host / _raw_device /
@@ -440,6 +441,54 @@ int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start);
  * DVO_ERR_NOT_READY, and a push whose weight storage differs from the keyframes' (float maps after raw frames or the reverse) ->
  * DVO_ERR_BAD_ARGUMENT. */
 int dvo_batch_set_keyframe_tracking(dvo_batch* b, int enable);   /* sensor-depth batches; before the first push */
+/* ---- keyframe depth fusion of a sensor-depth batch with keyframe tracking ---------------------------------------
+ * A keyframe's depth map is the single measurement it was promoted with; every frame tracked against it measures the same surface
+ * again.  dvo_batch_set_keyframe_fusion makes every later push fold the tracked frame's depth into the keyframe's map as a running
+ * mean, after the push's tracking and keyframe decision (two kernels: k_kf_fuse_prep, one thread per sequence, and k_kf_fuse; no kernel of the tracker changes, and the push that
+ * measured a depth never sees it: the fused map is the reference of the NEXT push).  A batch that never calls it runs exactly the
+ * launches it always ran.
+ * Contract: float32, IEEE, no contraction beyond the fmaf()s named.  T = levels - 1 (the top level, w x h), k = the sequence's
+ * level-T intrinsics (with dvo_batch_set_intrinsics: its row of the per-sequence table), xi = the push's relative twist,
+ * F = the float pose of exp(xi) (the T_rel of dvo_batch_last_poses: keyframe-camera points into the tracked frame), Bk = the float
+ * pose of exp(-xi) (bit for bit dvo_op_se3_exp(-xi): the double-precision chain, rounded once).  Per sequence, after the keyframe
+ * decision and the promotions of the push:
+ *   STARTED, or TRACKED with the keyframe rule fired: the depth was just replaced; its count plane becomes 0, its record zeros.
+ *   SKIPPED / BAD_ACTION: nothing of it is read or written; record zeros.
+ *   TRACKED, rule not fired, all six components of xi finite (otherwise nothing is fused, record zeros): for every top-level (x, y)
+ *    1. d = kf_depth[T][y][x]; the pixel is a CANDIDATE iff d >= min_depth (false for NaN: holes are never filled).
+ *    2. back_project(k, (float)x, (float)y, d), transform(F, ...) -> (Xf, Yf, Zf); Zf >= min_depth; project(k, ...) -> (u, v).
+ *    3. 0 <= u < w - 1 and 0 <= v < h - 1 (false for NaN / inf); x0 = (int)u, y0 = (int)v, a = u - (float)x0, b = v - (float)y0.
+ *    4. the taps z00, z10, z01, z11 of the TRACKED frame's top-level depth at (x0, y0) .. (x0 + 1, y0 + 1): all >= min_depth and
+ *       < inf, and max4 - min4 <= max_diff (no blend across a depth edge).
+ *    5. top = fmaf(a, z10 - z00, z00), bot = fmaf(a, z11 - z01, z01), zi = fmaf(b, bot - top, top).
+ *    6. fabsf(zi - Zf) <= max_diff.
+ *    7. back_project(k, u, v, zi), transform(Bk, ...): d_obs = its z; d_obs >= min_depth and < inf.
+ *    8. c = count[y][x], r = 1.0f / (float)(c + 2) (the IEEE quotient), d_new = fmaf(d_obs - d, r, d), c_new = min(c + 1, max_count):
+ *       the running mean of the keyframe's own sample and c fused ones; an exponential average once c has reached max_count.
+ *    9. c_new -> count; d_new -> kf_depth[T][y][x] and every coarser level l whose point decimation picks the pixel (t = T - l:
+ *       x and y multiples of 2^t, (x >> t) < w_l, (y >> t) < h_l), so dvo_batch_keyframe_get returns the fused depth at every level.
+ *   A candidate failing at 2, 3, 4 or 7 is unchanged; one failing only at 6 counts in n_gated; one reaching 9 counts in n_fused.  The
+ *   counters are integer sums: order-free, deterministic.  Gray, sigma and the weight maps are not touched.
+ * dvo_batch_set_keyframe_fusion: between any two pushes while keyframe tracking is on; from the next push on; cfg NULL or mode
+ * DVO_KF_FUSION_OFF stops fusing and leaves the maps as they are.  Turning it on (from off) allocates the uint8 count plane
+ * [n_seq][h][w] on first use and zeroes it.  dvo_batch_last_keyframe_fusion: the records [n_seq] of the last push (host,
+ * synchronises; struct_size is set to sizeof(dvo_kf_fusion_record)); dvo_batch_keyframe_fusion_counts: the count plane of one
+ * sequence (host, synchronises).
+ * Errors, returned before anything is enqueued or changed: a NULL handle (or NULL output) or a mono batch -> DVO_ERR_BAD_ARGUMENT; a
+ * sensor-depth batch without keyframe tracking -> DVO_ERR_NOT_READY; mode outside {0, 1}, max_diff not finite or <= 0, max_count
+ * outside [1, 255], seq out of range -> DVO_ERR_BAD_ARGUMENT; a reader before a push that ran with fusion on -> DVO_ERR_NOT_READY.
+ * All three fields of a non-NULL cfg are checked whatever the mode: to turn fusion off pass NULL, or a valid configuration (one from
+ * dvo_kf_fusion_config_default) with mode = DVO_KF_FUSION_OFF; a zeroed struct is refused for its max_diff and max_count.
+ * With keyframe tracking on, dvo_batch_frame_get returns the frame of the last push (the tracked frame this fusion read; on the
+ * first push the keyframe itself). */
+#define DVO_KF_FUSION_OFF 0
+#define DVO_KF_FUSION_ON  1
+typedef struct dvo_kf_fusion_config { int mode; float max_diff; int max_count; } dvo_kf_fusion_config;
+void dvo_kf_fusion_config_default(dvo_kf_fusion_config* cfg);   /* DVO_KF_FUSION_ON, max_diff = 0.05, max_count = 16 */
+int dvo_batch_set_keyframe_fusion(dvo_batch* b, const dvo_kf_fusion_config* cfg);   /* from the next push on; NULL cfg = OFF */
+typedef struct dvo_kf_fusion_record { int struct_size, n_candidates, n_fused, n_gated; } dvo_kf_fusion_record;
+int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec /*[n_seq]*/);   /* host, synchronises */
+int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts /*[h_top][w_top]*/);
 /* ---- per-sequence tracking quality (both batch kinds) ---------------------------------------------------------------------------
  * dvo_batch_set_track_quality(b, 1) makes every later push / call keep, per sequence, the sums of the LAST Gauss-Newton iteration of
  * the finest level (levels - 1: the solve that produced the returned pose); enable = 0 stops keeping them.  Poses, status, world

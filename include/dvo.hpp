@@ -266,6 +266,25 @@ public:
     }
     // track each frame against its sequence's keyframe instead of the previous frame, before the first push (dvo_batch_set_keyframe_tracking)
     void setKeyframeTracking(bool enable = true) { check(dvo_batch_set_keyframe_tracking(b_, enable ? 1 : 0)); }
+    // with keyframe tracking: fold every tracked frame's depth into its keyframe's map from the next push on (dvo_batch_set_keyframe_fusion);
+    // mode DVO_KF_FUSION_OFF stops and leaves the maps as they are
+    void setKeyframeFusion(int mode = DVO_KF_FUSION_ON, float max_diff = 0.05f, int max_count = 16)
+    {
+        dvo_kf_fusion_config c{mode, max_diff, max_count};
+        check(dvo_batch_set_keyframe_fusion(b_, &c));
+    }
+    std::vector<dvo_kf_fusion_record> lastKeyframeFusion()   // [n_seq]
+    {
+        std::vector<dvo_kf_fusion_record> out(n_);
+        check(dvo_batch_last_keyframe_fusion(b_, out.data()));
+        return out;
+    }
+    std::vector<uint8_t> keyframeFusionCounts(int seq)   // [h_top][w_top]
+    {
+        std::vector<uint8_t> out((size_t)(w_ >> culls_) * (size_t)(h_ >> culls_));
+        check(dvo_batch_keyframe_fusion_counts(b_, seq, out.data()));
+        return out;
+    }
     // with keyframe tracking: world poses of the last push (and its keyframe flags), as BatchMono::worldPoses
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {

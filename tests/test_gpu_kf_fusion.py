@@ -1,0 +1,541 @@
+"""Keyframe depth fusion of a sensor-depth batch (dvo_batch_set_keyframe_fusion, include/dvo.h) on the GPU.
+
+Every push of every test is held to the contract-exact replica (tests/kf_fusion_ref.py) bit for bit: keyframe depth of every level, the
+count plane and the record, from the device's own poses (last_poses for F, dvo_op_se3_exp(-xi) for Bk), the tracked frame's top-level
+depth (Batch.frame) and the status / keyframe flag of the push.  Shapes are tests/test_gpu_robust.py's small ones (320x240 and 328x248,
+3 levels, culls 1, batches of 5 and 17) and 326x246, whose top level 163x123 = 20 049 pixels is no multiple of 4 (the scalar tail) and
+whose coarser sizes truncate (81x61, 40x30).  keyframe_min_translation = 1.0 and keyframe_max_frames = 4: keyframes live for three
+tracked frames, so counts reach 3 and the frame rule promotes inside every schedule."""
+import functools
+
+import numpy as np
+import pytest
+
+import dvo_amd as dvo
+import kf_fusion_ref as kref
+import orc
+from dvo_amd import synth
+from util import K640
+
+pytestmark = pytest.mark.gpu
+
+SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
+TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
+SIZE = (320, 240)
+LEVELS, CULLS, TOP = 3, 1, 2
+STEPS = (1.0, 0.75, 0.5)
+KH = np.array(K640, np.float32).copy()
+KH[0] *= 0.5
+KH[1] *= 0.5
+MAX_DIFF, MAX_COUNT = 0.05, 16
+KF_ON, KF_OFF = dvo.KF_FUSION_ON, dvo.KF_FUSION_OFF   # (without the feature the file fails here, at import)
+
+
+def _cfg(**kw):
+    kw.setdefault("max_iterations", 6)
+    kw.setdefault("keyframe_min_translation", 1.0)
+    kw.setdefault("keyframe_max_frames", 4)
+    return dvo.default_config(gn_pixels_per_thread=4, crop_enable=0, step_default=STEPS[0], step_level1=STEPS[1], step_level2=STEPS[2],
+                              min_residual=0.0, min_update=2e-5, **kw)
+
+
+@functools.lru_cache(maxsize=None)
+def _frames(size=SIZE, noise=0.0):
+    g, d, s, _ = synth.sequence(6, width=size[0], height_px=size[1], K=KH, seed=42, sigma_value=0.5)
+    g, d, s = g.numpy(), d.numpy(), s.numpy()
+    if noise:
+        d = (d + np.random.RandomState(7).normal(0.0, noise, d.shape)).astype(np.float32)
+    return g, d, s
+
+
+def _dev(a):
+    import torch
+    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    torch.cuda.synchronize()
+    return t
+
+
+def _idx(B, pushes):
+    return [[(k + b) % 6 for b in range(B)] for k in range(pushes)]
+
+
+def _acts(B, n, seed):
+    rng = np.random.RandomState(seed)
+    a = rng.choice([SKIP, TRACK, RESTART], size=(n, B), p=(0.2, 0.7, 0.1)).astype(np.uint8)
+    a[0] = TRACK
+    a[0, B - 1] = SKIP          # one sequence starts late: its keyframe does not exist after the first push
+    return a
+
+
+def _push(bt, keep, maps, feed):
+    gi, di, si = maps
+    if feed == "host":
+        bt.push_host(gi, di, si)
+    elif feed in ("raw", "raw_host"):
+        g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
+        if feed == "raw_host":
+            bt.push_raw_host(g8, d16)
+        else:
+            import torch
+            tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
+            torch.cuda.synchronize()
+            keep.append((tg, td))
+            bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
+    else:
+        t = [_dev(x) for x in maps]
+        keep.append(t)
+        bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+
+
+class Mirror:
+    """The replica's copy of every sequence's keyframe depth pyramid and count plane, advanced push by push beside the device."""
+
+    def __init__(self, bt, B, cams=None, min_depth=None, max_diff=MAX_DIFF, max_count=MAX_COUNT):
+        self.bt, self.B = bt, B
+        self.levels = [None] * B
+        self.counts = [None] * B
+        self.k_top = [orc.cull_intrinsic(KH if cams is None else cams[b], CULLS) for b in range(B)]
+        self.min_depth = dvo.default_config().min_depth if min_depth is None else min_depth
+        self.max_diff, self.max_count = max_diff, max_count
+        self.fused = self.cleared = 0
+        self.fractions = []
+
+    def device_state(self, b):
+        lv = [self.bt.keyframe(b, l)["depth"] for l in range(LEVELS)]
+        return lv, self.bt.keyframe_fusion_counts(b)
+
+    def after_push(self, tag="", fusing=True):
+        """compare the device with the replica after a push that ran with fusion on (fusing = False: it ran with fusion off and the
+        maps must only follow starts and promotions, the counts stay)"""
+        bt = self.bt
+        status = bt.last_status()
+        xi, T = bt.last_poses()
+        key = bt.world_poses()[2]
+        rec = bt.last_keyframe_fusion() if fusing else None
+        for b in range(self.B):
+            what = "%s seq %d" % (tag, b)
+            zero = dict(n_candidates=0, n_fused=0, n_gated=0)
+            if status[b] == STARTED or (status[b] == TRACKED and key[b]):
+                want_lv = [bt.frame(b, l)[1] for l in range(LEVELS)]
+                h, w = want_lv[TOP].shape
+                want_c = np.zeros((h, w), np.uint8) if (fusing or self.counts[b] is None) else self.counts[b]
+                want_r = zero
+                self.cleared += 1
+            elif status[b] == TRACKED and fusing and np.all(np.isfinite(xi[b])):
+                Bk = dvo.se3.exp(-xi[b])
+                want_lv, want_c, want_r = kref.fuse(self.levels[b], self.counts[b], bt.frame(b, TOP)[1], self.k_top[b], T[b], Bk,
+                                                    self.min_depth, self.max_diff, self.max_count)
+                self.fused += 1
+                self.fractions.append(want_r["n_fused"] / max(want_r["n_candidates"], 1))
+            else:
+                want_lv, want_c, want_r = self.levels[b], self.counts[b], zero
+            if rec is not None:
+                got_r = {k: int(rec[b][k]) for k in zero}
+                assert got_r == want_r, (what, got_r, want_r)
+                assert int(rec[b]["struct_size"]) == 16
+            if want_lv is None:   # the sequence has never started: no keyframe to read
+                with pytest.raises(dvo.DvoError):
+                    bt.keyframe(b, TOP)
+                continue
+            got_lv, got_c = self.device_state(b)
+            for l in range(LEVELS):
+                assert got_lv[l].tobytes() == np.ascontiguousarray(want_lv[l], np.float32).tobytes(), (what, "level", l)
+            assert got_c.tobytes() == want_c.tobytes(), (what, "counts")
+            self.levels[b], self.counts[b] = got_lv, got_c
+
+
+def _lockstep(B=5, size=SIZE, pushes=6, feed="device", cfg_kw=None, cams=None, dist=None, seed=3, setup=None, noise=0.0, acts=True):
+    g, d, s = _frames(size, noise)
+    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=_cfg(**(cfg_kw or {})))
+    try:
+        bt.set_keyframe_tracking(True)
+        bt.set_keyframe_fusion(dvo.KF_FUSION_ON, MAX_DIFF, MAX_COUNT)
+        if cams is not None:
+            bt.set_intrinsics(cams)
+        if dist is not None:
+            bt.set_distortion(dist)
+        if setup:
+            setup(bt)
+        m = Mirror(bt, B, cams)
+        a = _acts(B, pushes, seed) if acts else None
+        keep = []
+        out = []
+        for k, sel in enumerate(_idx(B, pushes)):
+            if a is not None:
+                bt.set_actions(a[k])
+            _push(bt, keep, (g[sel], d[sel], s[sel]), feed)
+            m.after_push("push %d" % k)
+            out.append((bt.last_status().copy(), bt.last_poses()[0].copy()))
+        assert m.fused >= B and m.cleared >= B, (m.fused, m.cleared)
+        return m, out
+    finally:
+        bt.close()
+
+
+def _cams(B):
+    c = np.tile(KH.reshape(1, 9), (B, 1)).astype(np.float32)
+    c[:, 0] *= 1.0 + 0.01 * np.arange(B); c[:, 4] *= 1.0 - 0.008 * np.arange(B)
+    c[:, 2] += 0.7 * np.arange(B); c[:, 5] -= 0.4 * np.arange(B)
+    return c
+
+
+CASES = [
+    ("b5", dict()),
+    ("b17", dict(B=17, pushes=5)),
+    ("328x248", dict(size=(328, 248))),
+    ("326x246_tail", dict(size=(326, 246))),
+    ("cameras", dict(cams=_cams(5))),
+    ("undistort", dict(dist=np.array([0.08, -0.05, 0.001, -0.0015, 0.01], np.float32))),
+    ("raw_device", dict(feed="raw")),
+    ("raw_host", dict(feed="raw_host")),
+    ("host_float", dict(feed="host")),
+    ("adaptive_off", dict(cfg_kw=dict(track_adaptive=-1))),
+    ("two_streams", dict(cfg_kw=dict(track_streams=2))),
+    ("single_launch", dict(cfg_kw=dict(track_single_launch=1))),
+    ("geometric", dict(setup=lambda bt: bt.set_geometric(dvo.GEOMETRIC_ON, 10.0, 0.1))),
+    ("geometric_affine", dict(setup=lambda bt: bt.set_geometric_affine(10.0, 0.1))),
+    ("noisy_depth", dict(noise=0.01)),
+]
+
+
+@pytest.mark.parametrize("name,kw", CASES, ids=[c[0] for c in CASES])
+def test_bit_for_bit_against_the_replica(name, kw):
+    """Levels, counts and records of every push equal the replica's, under a random SKIP / TRACK / RESTART schedule."""
+    m, _ = _lockstep(**kw)
+    print("%s: fused pushes %d, cleared %d, n_fused / n_candidates min %.3f median %.3f"
+          % (name, m.fused, m.cleared, min(m.fractions), float(np.median(m.fractions))))
+
+
+def test_raw_feeds_agree():
+    """the raw feed from the device and from the host: the same statuses and twists"""
+    a = _lockstep(feed="raw")[1]
+    b = _lockstep(feed="raw_host")[1]
+    for (sa, xa), (sb, xb) in zip(a, b):
+        np.testing.assert_array_equal(sa, sb)
+        assert xa.tobytes() == xb.tobytes()
+
+
+def test_direction_fuses_most_of_the_view():
+    """On noise-free renders with the GPU's own poses the gates pass most candidates: a wrong pose direction (F and Bk swapped) would
+    leave a gate-rejected remnant.  The counts equal the replica's (after_push); the fraction is printed and must exceed one half."""
+    m, _ = _lockstep(acts=False, pushes=4)
+    print("n_fused / n_candidates per fused push:", ["%.3f" % f for f in m.fractions])
+    assert min(m.fractions) > 0.5, m.fractions
+
+
+def _holes(d, rng):
+    d = d.copy()
+    for q in range(d.shape[0]):
+        d[q, 20:40, 30:60] = 0.0                       # a hole
+        d[q, 100:110, 200:230] = np.nan
+        d[q, 150:156, 40:80] = np.inf
+        d[q, 60:120, 120:180] += np.float32(0.3)       # a 0.3 m step block
+        d[q, 200:204, 100:140] = 0.1                   # below min_depth
+    return d
+
+
+def test_holes_never_change_and_nothing_turns_non_finite():
+    """A hole, NaN, +inf, a below-min_depth patch and a 0.3 m step block in every frame (so in the keyframes and in the tracked frames):
+    records, maps and counts are the replica's, no pixel that is not a candidate changes, every finite depth stays finite."""
+    B, size = 5, SIZE
+    g, d, s = _frames(size)
+    d = _holes(d, None)
+    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=_cfg())
+    try:
+        bt.set_keyframe_tracking(True)
+        bt.set_keyframe_fusion()
+        m = Mirror(bt, B)
+        keep = []
+        for k, sel in enumerate(_idx(B, 4)):
+            before = [None if m.levels[b] is None else m.levels[b][TOP].copy() for b in range(B)]
+            _push(bt, keep, (g[sel], d[sel], s[sel]), "device")
+            m.after_push("push %d" % k)
+            if k > 0:   # pushes 1 to 3 fuse (0 starts; the frame rule fires at the fourth tracked frame)
+                for b in range(B):
+                    old, new = before[b], m.levels[b][TOP]
+                    with np.errstate(invalid="ignore"):
+                        hole = ~(old >= m.min_depth)
+                    assert old[hole].tobytes() == new[hole].tobytes()
+                    assert np.all(np.isfinite(new[np.isfinite(old)]))
+                    assert (m.counts[b][hole] == 0).all()
+                    assert (new.view(np.uint32) != old.view(np.uint32)).sum() > 1000
+        assert m.fused == 3 * B
+    finally:
+        bt.close()
+
+
+def _run_plain(B, pushes, fusion, cfg_kw=None, kf=True, maps=None, toggle=None, feed="device"):
+    """statuses, twists, keyframe flags of every push of a device-fed batch without actions; toggle: {push index: on / off} applied
+    before that push"""
+    g, d, s = _frames() if maps is None else maps
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg(**(cfg_kw or {})))
+    try:
+        if kf:
+            bt.set_keyframe_tracking(True)
+            if fusion:
+                bt.set_keyframe_fusion()
+        keep, out = [], []
+        for k, sel in enumerate(_idx(B, pushes)):
+            if toggle and k in toggle:
+                bt.set_keyframe_fusion(dvo.KF_FUSION_ON if toggle[k] else dvo.KF_FUSION_OFF)
+            _push(bt, keep, (g[sel], d[sel], s[sel]), feed)
+            o = dict(xi=bt.last_poses()[0].copy() if (k > 0 or kf) else None)
+            if kf:
+                o["key"] = bt.world_poses()[2].copy()
+                o["counts"] = [bt.keyframe_fusion_counts(b) for b in range(B)] if bt_fused(bt) else None
+                o["levels"] = [[bt.keyframe(b, l) for l in range(LEVELS)] for b in range(B)]
+                o["depth"] = [o["levels"][b][TOP]["depth"] for b in range(B)]
+            out.append(o)
+        return out
+    finally:
+        bt.close()
+
+
+def bt_fused(bt):
+    try:
+        bt.keyframe_fusion_counts(0)
+        return True
+    except dvo.DvoError:
+        return False
+
+
+def test_fusion_does_not_reach_back():
+    """The push that measures a depth never sees it: the first tracked push after every start or promotion gives the fusion-off
+    batch's twists bit for bit; later pushes of the same keyframe differ (the fused map is their reference)."""
+    B = 5
+    on = _run_plain(B, 7, True)
+    off = _run_plain(B, 7, False)
+    later_differs = False
+    for k in range(1, 7):
+        np.testing.assert_array_equal(on[k]["key"], off[k]["key"])
+        first = on[k - 1]["key"]            # the previous push started or promoted: this one is the keyframe's first tracked frame
+        for b in range(B):
+            if first[b]:
+                assert on[k]["xi"][b].tobytes() == off[k]["xi"][b].tobytes(), (k, b)
+            elif on[k]["xi"][b].tobytes() != off[k]["xi"][b].tobytes():
+                later_differs = True
+    assert later_differs
+
+
+def test_every_push_promoting_is_frame_to_frame():
+    """keyframe_max_frames = 1: every push promotes, nothing is ever fused, the twists are the frame-to-frame batch's, all counts 0."""
+    B = 5
+    on = _run_plain(B, 4, True, cfg_kw=dict(keyframe_max_frames=1))
+    f2f = _run_plain(B, 4, False, kf=False)
+    for k in range(1, 4):
+        assert on[k]["xi"].tobytes() == f2f[k]["xi"].tobytes(), k
+        assert all((c == 0).all() for c in on[k]["counts"])
+
+
+def _twice(m):
+    """[h, w] -> [2h, 2w], every value repeated 2 x 2: whichever pixel of a pair the cull picks, it returns m"""
+    return np.repeat(np.repeat(m, 2, axis=0), 2, axis=1)
+
+
+def test_toggle():
+    """Turned off mid-stream the maps stop changing and the counts stay readable and unchanged; the poses from then on equal, bit for
+    bit, a second batch that never fuses and whose keyframes were started from those maps (gray and fused depth of the top level,
+    repeated 2 x 2 so that culls = 1 returns them; the coarser levels are point decimations of it, which the test checks first);
+    turned on again the counts restart at 0.  Both batches take host float maps, so they store per-pixel `wgt` maps: a fusion that
+    touched the first batch's would show as different twists, the second batch's being freshly built from the same constant sigma."""
+    B = 5
+    cfg_kw = dict(keyframe_max_frames=100)
+    r = _run_plain(B, 6, True, cfg_kw=cfg_kw, toggle={3: False, 5: True}, feed="host")
+    for b in range(B):
+        assert r[2]["depth"][b].tobytes() != r[1]["depth"][b].tobytes()            # fusing
+        assert r[3]["depth"][b].tobytes() == r[2]["depth"][b].tobytes()            # off: the maps stay
+        assert r[4]["depth"][b].tobytes() == r[2]["depth"][b].tobytes()
+        assert r[4]["counts"][b].tobytes() == r[2]["counts"][b].tobytes()
+        assert r[2]["counts"][b].max() == 2
+        assert r[5]["counts"][b].max() == 1                                        # on again: restarted at 0, one push fused
+        assert not r[3]["key"][b] and not r[4]["key"][b]
+    g, d, s = _frames()
+    assert (s == np.float32(0.5)).all()
+    fed = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg(**cfg_kw))
+    try:
+        fed.set_keyframe_tracking(True)
+        kf = r[2]["levels"]            # [seq][level] -> dict(gray, depth): the keyframes as the last fusing push left them
+        fed.push_host(np.stack([_twice(kf[b][TOP]["gray"]) for b in range(B)]),
+                      np.stack([_twice(kf[b][TOP]["depth"]) for b in range(B)]), s[:B])
+        for b in range(B):
+            for l in range(LEVELS):
+                got = fed.keyframe(b, l)
+                assert got["gray"].tobytes() == kf[b][l]["gray"].tobytes(), (b, l)
+                assert got["depth"].tobytes() == kf[b][l]["depth"].tobytes(), (b, l)
+        for k in (3, 4):
+            sel = _idx(B, 6)[k]
+            fed.push_host(g[sel], d[sel], s[sel])
+            assert (fed.last_status() == TRACKED).all() and not fed.world_poses()[2].any()
+            xi = fed.last_poses()[0]
+            assert xi.tobytes() == r[k]["xi"].tobytes(), (k, xi, r[k]["xi"])
+        # and those twists are not what the unfused keyframes give: the comparison above can tell the maps apart
+        off = _run_plain(B, 5, False, cfg_kw=cfg_kw, feed="host")
+        assert any(off[k]["xi"].tobytes() != r[k]["xi"].tobytes() for k in (3, 4))
+    finally:
+        fed.close()
+
+
+def test_frame_get_in_keyframe_mode():
+    """dvo_batch_frame_get with keyframe tracking: after the first push the keyframe itself; after a tracked push the frame that push
+    built (every level equal to a frame-to-frame batch's frame from the same input) while the keyframe stays; a SKIPPED sequence's slot
+    holds a copy of its keyframe as it was before the push (here: a fused one)."""
+    B = 3
+    g, d, s = _frames()
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    f2f = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    try:
+        bt.set_keyframe_tracking(True)
+        bt.set_keyframe_fusion()
+        keep = []
+        for k, sel in enumerate(_idx(B, 3)):
+            before = [[bt.keyframe(b, l) for l in range(LEVELS)] for b in range(B)] if k else None
+            if k == 2:
+                bt.set_actions(np.array([TRACK, SKIP, TRACK], np.uint8))
+            _push(bt, keep, (g[sel], d[sel], s[sel]), "device")
+            _push(f2f, keep, (g[sel], d[sel], s[sel]), "device")
+            for b in range(B):
+                for l in range(LEVELS):
+                    fg, fd = bt.frame(b, l)
+                    kf = bt.keyframe(b, l)
+                    if k == 0:
+                        assert fg.tobytes() == kf["gray"].tobytes() and fd.tobytes() == kf["depth"].tobytes(), (k, b, l)
+                    elif k == 2 and b == 1:
+                        assert bt.last_status()[b] == SKIPPED
+                        assert fg.tobytes() == before[b][l]["gray"].tobytes() and fd.tobytes() == before[b][l]["depth"].tobytes(), (k, b, l)
+                        assert kf["depth"].tobytes() == before[b][l]["depth"].tobytes()
+                    else:
+                        pg, pd = f2f.frame(b, l)
+                        assert fg.tobytes() == pg.tobytes() and fd.tobytes() == pd.tobytes(), (k, b, l)
+                        assert fd.tobytes() != kf["depth"].tobytes()
+        with pytest.raises(dvo.DvoError):
+            bt.frame(B, TOP)
+    finally:
+        bt.close(); f2f.close()
+
+
+def test_errors_change_nothing():
+    B = 3
+    L = dvo.lib()
+    g, d, s = _frames()
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    plain = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    try:
+        import ctypes as C
+        ok = dvo.KfFusionConfig(dvo.KF_FUSION_ON, 0.05, 16)
+        assert L.dvo_batch_set_keyframe_fusion(plain._p, C.byref(ok)) == dvo.DVO_ERR_NOT_READY      # no keyframe tracking
+        rec = np.zeros(B, dvo.KF_FUSION_RECORD_DTYPE); cnt = np.zeros((120, 160), np.uint8)
+        recp = rec.ctypes.data_as(C.POINTER(dvo.KfFusionRecord)); cntp = cnt.ctypes.data_as(C.c_void_p)
+        assert L.dvo_batch_last_keyframe_fusion(plain._p, recp) == dvo.DVO_ERR_NOT_READY
+        assert L.dvo_batch_keyframe_fusion_counts(plain._p, 0, cntp) == dvo.DVO_ERR_NOT_READY
+        assert L.dvo_batch_set_keyframe_fusion(plain._p, None) == dvo.DVO_ERR_NOT_READY
+        mono = dvo.MonoBatch(2, K640, 640, 480)                                                     # a mono batch: refused as such
+        try:
+            for c in (C.byref(ok), None):
+                assert L.dvo_batch_set_keyframe_fusion(mono._p, c) == dvo.DVO_ERR_BAD_ARGUMENT
+            assert L.dvo_batch_last_keyframe_fusion(mono._p, recp) == dvo.DVO_ERR_BAD_ARGUMENT
+            assert L.dvo_batch_keyframe_fusion_counts(mono._p, 0, cntp) == dvo.DVO_ERR_BAD_ARGUMENT
+        finally:
+            mono.close()
+        _push(plain, [], (g[:B], d[:B], s[:B]), "host")                                             # the refused batch pushes as it did
+        _push(plain, [], (g[1:B + 1], d[1:B + 1], s[1:B + 1]), "host")
+        assert np.all(np.isfinite(plain.last_poses()[0]))
+        bt.set_keyframe_tracking(True)
+        assert L.dvo_batch_last_keyframe_fusion(bt._p, recp) == dvo.DVO_ERR_NOT_READY              # before a fusing push
+        assert L.dvo_batch_keyframe_fusion_counts(bt._p, 0, cntp) == dvo.DVO_ERR_NOT_READY
+        bt.set_keyframe_fusion()
+        assert L.dvo_batch_last_keyframe_fusion(bt._p, recp) == dvo.DVO_ERR_NOT_READY
+        keep = []
+        for k, sel in enumerate(_idx(B, 3)):
+            _push(bt, keep, (g[sel], d[sel], s[sel]), "device")
+        state = lambda: (bt.last_poses()[0].tobytes(), [bt.keyframe(b)["depth"].tobytes() for b in range(B)],
+                         [bt.keyframe_fusion_counts(b).tobytes() for b in range(B)], bt.last_keyframe_fusion().tobytes())
+        before = state()
+        bad = [dvo.KfFusionConfig(2, 0.05, 16), dvo.KfFusionConfig(-1, 0.05, 16), dvo.KfFusionConfig(1, 0.0, 16),
+               dvo.KfFusionConfig(1, -1.0, 16), dvo.KfFusionConfig(1, float("nan"), 16), dvo.KfFusionConfig(1, float("inf"), 16),
+               dvo.KfFusionConfig(1, 0.05, 0), dvo.KfFusionConfig(1, 0.05, 256),
+               dvo.KfFusionConfig(0, 0.0, 0)]   # (the fields are checked whatever the mode: a zeroed struct is no OFF)
+        for c in bad:
+            assert L.dvo_batch_set_keyframe_fusion(bt._p, C.byref(c)) == dvo.DVO_ERR_BAD_ARGUMENT, (c.mode, c.max_diff, c.max_count)
+        assert L.dvo_batch_keyframe_fusion_counts(bt._p, -1, cntp) == dvo.DVO_ERR_BAD_ARGUMENT
+        assert L.dvo_batch_keyframe_fusion_counts(bt._p, B, cntp) == dvo.DVO_ERR_BAD_ARGUMENT
+        assert L.dvo_batch_keyframe_fusion_counts(bt._p, 0, None) == dvo.DVO_ERR_BAD_ARGUMENT
+        assert L.dvo_batch_last_keyframe_fusion(bt._p, None) == dvo.DVO_ERR_BAD_ARGUMENT
+        assert state() == before
+        # and the next push still fuses with the configuration that was accepted
+        _push(bt, keep, (g[_idx(B, 4)[3]], d[_idx(B, 4)[3]], s[_idx(B, 4)[3]]), "device")
+        assert bt.last_keyframe_fusion()["n_fused"].min() > 0 or bt.world_poses()[2].all()
+    finally:
+        bt.close(); plain.close()
+
+
+# ---- outcome: the workload of kf_fusion_ref.outcome_sequence, the replica's figures measured by tools/kf_fusion_outcome.py
+R_D_REPLICA = 0.8627          # (a) mean over the four seeds of the replica's map ratio (oracle tracking + kf_fusion_ref.fuse)
+
+
+@functools.lru_cache(maxsize=None)
+def _outcome_data():
+    import geometric_ref as gref
+    seeds = gref.OUTCOME["seeds"]
+    seqs = [kref.outcome_sequence(s) for s in seeds]
+    stack = lambda i: np.stack([q[i] for q in seqs], axis=1)          # [frame][seq][h][w]
+    return stack(0), stack(1), stack(2), stack(3), seqs[0][4], np.stack([q[5] for q in seqs], axis=1)
+
+
+def _outcome_run(fusion, geometric):
+    import geometric_ref as gref
+    o, s = gref.OUTCOME, kref.OUTCOME
+    g, d, sg, clean, K, truths = _outcome_data()
+    B = g.shape[1]
+    cfg = dvo.default_config(gn_pixels_per_thread=4, crop_enable=0, step_default=o["steps"][0], step_level1=o["steps"][1],
+                             step_level2=o["steps"][2], min_residual=o["min_residual"], min_update=o["min_update"],
+                             max_iterations=o["max_iterations"], keyframe_min_translation=s["keyframe_min_translation"],
+                             keyframe_max_frames=s["keyframe_max_frames"])
+    bt = dvo.Batch(B, K, o["width"], o["height"], o["levels"], o["culls"], cfg=cfg)
+    try:
+        bt.set_keyframe_tracking(True)
+        if fusion:
+            bt.set_keyframe_fusion(dvo.KF_FUSION_ON, s["max_diff"], s["max_count"])
+        if geometric:
+            bt.set_geometric(dvo.GEOMETRIC_ON, s["geometric_weight"], s["geometric_max_diff"])
+        keep, err = [], np.zeros((s["frames"], B))
+        for k in range(s["frames"]):
+            _push(bt, keep, (g[k], d[k], sg[k]), "device")
+            if k == 0:
+                unfused = [bt.keyframe(b)["depth"] for b in range(B)]
+            else:
+                xi = bt.last_poses()[0]
+                assert not bt.world_poses()[2].any()
+                err[k] = [gref.pose_error(xi[b], truths[k][b]) for b in range(B)]
+        ratios = None
+        if fusion:
+            ratios = [kref.map_ratio(bt.keyframe(b)["depth"], unfused[b], kref.cull(clean[0][b], o["culls"]).astype(np.float64),
+                                     bt.keyframe_fusion_counts(b), s["min_count"]) for b in range(B)]
+        return err[list(s["score_frames"])].mean(axis=0), ratios
+    finally:
+        bt.close()
+
+
+R_D_REPLICA_GEOMETRIC = 0.3071   # the same with the geometric estimator's poses (geometric_ref.geometric_track, weight 10)
+
+
+@pytest.mark.parametrize("geometric,r_d", [(False, R_D_REPLICA), (True, R_D_REPLICA_GEOMETRIC)], ids=["plain", "geometric"])
+def test_outcome_map_error_shrinks(geometric, r_d):
+    """(a) With the device's own poses the fused keyframe depth is closer to the noise-free depth than the unfused one: the mean ratio
+    over the four seeds is at most the midpoint between the replica's R_d (its own tracking + kf_fusion_ref.fuse) and 1."""
+    _, ratios = _outcome_run(True, geometric)
+    print("map ratio per seed (pixels with count >= 4):", [("%.4f" % r, n) for r, n in ratios])
+    mean = float(np.mean([r for r, _ in ratios]))
+    print("mean %.4f, replica %.4f, bound %.4f" % (mean, r_d, (r_d + 1) / 2))
+    assert all(n > 5000 for _, n in ratios)
+    assert mean <= (r_d + 1) / 2
+
+
+def test_outcome_pose_is_reported():
+    """(b) The replica does not win on all four seeds with either estimator (DESIGN.md §28 has its table): nothing is asserted about the
+    pose error; the device's figures are printed for §28."""
+    for geometric in (False, True):
+        off, _ = _outcome_run(False, geometric)
+        on, _ = _outcome_run(True, geometric)
+        print("%s: mean 6-norm error of frames 5..7 per seed, off %s on %s, on/off %s" % (
+            "geometric" if geometric else "plain", np.round(off, 5), np.round(on, 5), np.round(on / off, 3)))
+        assert np.all(np.isfinite(on)) and np.all(np.isfinite(off))

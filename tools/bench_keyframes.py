@@ -10,8 +10,11 @@ for two workloads: bench.py's default constants, and the converging constants (s
 conversion keeps sigma 0.1).  ms per push and tracked frames/s come from device events on the handle's stream around the timed pushes
 (after a warm-up); the promoted fraction is the mean of is_keyframe over the timed pushes, copied on the device after each push.
 Every sequence tracks at every push after the first.  Prints one JSON line.
+--fusion adds two modes to the alternation (without the flag the tool runs what it always ran):
+  kf_long    keyframe tracking with long-lived keyframes (keyframe_min_translation 1.0, keyframe_max_frames 8)
+  kf_fused   the same with keyframe depth fusion on (dvo_batch_set_keyframe_fusion): vs_kf_long is its cost
 
-    python tools/bench_keyframes.py --batch 16384 --steps 12 --warmup 3 --rounds 2
+    python tools/bench_keyframes.py --batch 16384 --steps 12 --warmup 3 --rounds 2 [--fusion]
 """
 import argparse
 import json
@@ -31,6 +34,8 @@ from bench_lifecycle import F, H, W, frames
 
 WORKLOADS = {"default": {}, "converging": dict(step_default=1.0, step_level1=0.75, step_level2=0.5, min_residual=0.0)}
 MODES = {"plain": None, "kf": {}, "kf1": dict(keyframe_max_frames=1)}
+LONG = dict(keyframe_min_translation=1.0, keyframe_max_frames=8)
+FUSION_MODES = {"kf_long": dict(LONG), "kf_fused": dict(LONG)}
 
 
 def run(workload, mode, a, g8, d16, stream):
@@ -42,6 +47,8 @@ def run(workload, mode, a, g8, d16, stream):
     bt = dvo.Batch(B, synth.K_640, W, H, 4, 1, cfg=dvo.default_config(stream=stream, **kw))
     if kf is not None:
         bt.set_keyframe_tracking(True)
+    if mode == "kf_fused":
+        bt.set_keyframe_fusion()
     key = torch.zeros((a.steps, B), dtype=torch.int32, device="cuda")
     ev = []
     n = 1 + a.warmup + a.steps
@@ -60,10 +67,14 @@ def run(workload, mode, a, g8, d16, stream):
     torch.cuda.synchronize()
     ms = sum(e0.elapsed_time(e1) for e0, e1 in ev)
     xi, _ = bt.last_poses()
+    fused = None
+    if mode == "kf_fused":   # (of the last push)
+        rec = bt.last_keyframe_fusion()
+        fused = float(rec["n_fused"].sum()) / max(float(rec["n_candidates"].sum()), 1.0)
     bt.close()
     assert np.all(np.isfinite(xi)), "non-finite poses"
     return {"ms_per_push": ms / a.steps, "tracked_frames_per_s": B * a.steps / (ms / 1e3),
-            "promoted_fraction": float(key.float().mean().item()) if kf is not None else None}
+            "promoted_fraction": float(key.float().mean().item()) if kf is not None else None, "fused_fraction_last_push": fused}
 
 
 def main():
@@ -74,7 +85,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--workloads", default="default,converging")
+    ap.add_argument("--fusion", action="store_true", help="also alternate kf_long and kf_fused (keyframe depth fusion)")
     a = ap.parse_args()
+    if a.fusion:
+        MODES.update(FUSION_MODES)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     g8, d16 = frames(a.batch, a.unique, dev)
@@ -99,6 +113,11 @@ def main():
         base = summary[w]["plain"]["ms_per_push"]
         for m in ("kf", "kf1"):
             summary[w][m]["vs_plain"] = round(summary[w][m]["ms_per_push"] / base, 4)
+        if a.fusion:
+            for m in FUSION_MODES:
+                summary[w][m]["vs_plain"] = round(summary[w][m]["ms_per_push"] / base, 4)
+            summary[w]["kf_fused"]["vs_kf_long"] = round(summary[w]["kf_fused"]["ms_per_push"] / summary[w]["kf_long"]["ms_per_push"], 4)
+            summary[w]["kf_fused"]["fused_fraction_last_push"] = res[(w, "kf_fused")][-1]["fused_fraction_last_push"]
     print(json.dumps({"batch": a.batch, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "frames_per_sequence": F,
                       "workloads": summary}))
     return 0
