@@ -330,6 +330,22 @@ int dvo_batch_last_track_log(dvo_batch* b, int seq, dvo_track_log* log)
     return DVO_OK;
 }
 
+// diagnostic, read-only: Tracker::lv[level] as use_plan() left it -- what the next push / call launches on that level
+int dvo_debug_batch_level_plan(dvo_batch* b, int level, int* ppt, int* group, int* tiles_2d, int* tiles, int* schedule)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    const Tracker& T = b->trk();
+    if (level < 0 || level >= T.g.levels) return DVO_ERR_BAD_ARGUMENT;
+    const LevelPlan& L = T.lv[level];
+    if (ppt) *ppt = L.ppt;
+    if (group) *group = L.group;
+    if (tiles_2d) *tiles_2d = (T.tile_margin == 0 && L.tiling.t2d) ? 1 : 0;
+    if (tiles) *tiles = L.nblk;
+    if (schedule)
+        *schedule = T.tile_margin > 0 ? DVO_PLAN_LDS_PATCH : (L.fused ? DVO_PLAN_LEVEL : (L.single_launch ? DVO_PLAN_ITERATION : DVO_PLAN_PAIRS));
+    return DVO_OK;
+}
+
 int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* depth)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;

@@ -170,7 +170,7 @@ EXPORTS = [
     "dvo_batch_set_pose_guess_mode", "dvo_batch_set_pose_guess", "dvo_batch_last_start_poses",
     "dvo_batch_set_keyframe_tracking",
     "dvo_batch_set_track_quality", "dvo_batch_last_track_quality", "dvo_batch_copy_track_quality_device",
-    "dvo_batch_frame_get",
+    "dvo_batch_frame_get", "dvo_debug_batch_level_plan",
     "dvo_batch_set_robust_weights", "dvo_batch_set_robust_scales", "dvo_batch_last_robust_scales", "dvo_op_gn_step_robust",
     "dvo_batch_set_affine_brightness", "dvo_batch_set_affine_rows", "dvo_batch_last_affine", "dvo_batch_last_affine_log",
     "dvo_op_gn_step_affine",
@@ -197,6 +197,15 @@ AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
 GEOMETRIC_OFF, GEOMETRIC_ON = 0, 1
 # keyframe depth fusion (Batch.set_keyframe_fusion): include/dvo.h
 KF_FUSION_OFF, KF_FUSION_ON = 0, 1
+# launch form of a level (Batch / MonoBatch .level_plan): include/dvo.h
+PLAN_PAIRS, PLAN_ITERATION, PLAN_LEVEL, PLAN_LDS_PATCH = 0, 1, 2, 3
+
+
+def _level_plan(handle, level):
+    """dvo_debug_batch_level_plan of a batch handle: dict(ppt, group, tiles_2d, tiles, schedule) of one pyramid level"""
+    v = [C.c_int() for _ in range(5)]
+    _check(lib().dvo_debug_batch_level_plan(handle, int(level), *[C.byref(x) for x in v]))
+    return dict(ppt=v[0].value, group=v[1].value, tiles_2d=bool(v[2].value), tiles=v[3].value, schedule=v[4].value)
 
 
 class KfFusionConfig(C.Structure):
@@ -968,6 +977,11 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrigh
         _check(lib().dvo_batch_last_track_log(self._p, seq, C.byref(log)))
         return log.to_dict()
 
+    def level_plan(self, level):
+        """Diagnostic: the kernel instance and tiles the next push / call runs on pyramid level `level` (0 = coarsest), with the
+        opt-in terms as they are set now: dict(ppt, group, tiles_2d, tiles, schedule = PLAN_*).  Reads the plan only."""
+        return _level_plan(self._p, level)
+
     def set_actions(self, actions, on_device=False):
         """Per-sequence action of the NEXT push (SEQ_SKIP / SEQ_TRACK / SEQ_RESTART): a numpy uint8 [n_seq] (copied now), an int device
         pointer to uint8 [n_seq] with on_device=True (read in stream order when the push runs), or None to clear."""
@@ -1186,6 +1200,11 @@ class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineB
         log = TrackLog()
         _check(lib().dvo_batch_last_track_log(self._p, seq, C.byref(log)))
         return log.to_dict()
+
+    def level_plan(self, level):
+        """Diagnostic: the kernel instance and tiles the next push / call runs on pyramid level `level` (0 = coarsest), with the
+        opt-in terms as they are set now: dict(ppt, group, tiles_2d, tiles, schedule = PLAN_*).  Reads the plan only."""
+        return _level_plan(self._p, level)
 
     def synchronize(self):
         _check(lib().dvo_batch_synchronize(self._p))

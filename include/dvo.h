@@ -180,6 +180,16 @@ int dvo_batch_synchronize(dvo_batch* b);
  * references are the keyframes (dvo_batch_keyframe_get) and this returns the frame of the last push, the one it tracked (a SKIPPED
  * sequence's slot holds a copy of its keyframe as it was before the push). */
 int dvo_batch_frame_get(dvo_batch* b, int seq, int level, float* gray, float* depth);
+/* Diagnostic, read-only: how the Gauss-Newton launches of pyramid level `level` (0 = coarsest) are planned for the NEXT push / call of a
+ * sensor-depth or mono batch, with the opt-in terms (robust weights, affine brightness, geometric) as they are set now: pixels per
+ * thread and gather group (the kernel instance: cfg.gn_pixels_per_thread = 0 lets the engine choose per level), whether the level
+ * runs the 2-D tiles, the tiles (partial rows) per sequence, and the launch form.  Launches nothing, changes nothing; any output may
+ * be NULL.  DVO_ERR_BAD_ARGUMENT for a NULL handle or a level outside the pyramid.  The tests name the instance they ran from this. */
+#define DVO_PLAN_PAIRS     0   /* one accumulation and one solve launch per iteration, the global-gather kernel (every opt-in term) */
+#define DVO_PLAN_ITERATION 1   /* one launch per iteration (small plain handles); launch pairs where that launch is refused */
+#define DVO_PLAN_LEVEL     2   /* one launch per level (cfg.track_fused_tiles) */
+#define DVO_PLAN_LDS_PATCH 3   /* launch pairs of the LDS-patch kernel (cfg.gn_use_lds_patch > 0) */
+int dvo_debug_batch_level_plan(dvo_batch* b, int level, int* ppt, int* group, int* tiles_2d, int* tiles, int* schedule);
 /* ---- per-sequence skip and restart (sensor-depth batches) -------------------------------------------------------------------
  * dvo_batch_set_actions gives every sequence an action for the NEXT push (any of dvo_batch_push_device / _host / _raw_device /
  * _raw_host); afterwards the actions are spent.  actions[n_seq]: host memory (actions_on_device = 0) is copied before the call

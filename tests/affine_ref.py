@@ -171,19 +171,19 @@ def replay_call(log, alog, pixels_at, levels, mode, kind=rr.NONE, param=1.0, rob
     Every logged iteration, at the logged input pose and the logged (a, b): n_valid equals the term count, the logged residual is
     inside the reduction bound, the logged update solves the replayed (H, g) within TOL_BACKWARD, and the NEXT logged (a, b) is the closed
     form of the replayed moments inside the propagated bound (ESTIMATE) or the given row (GIVEN).  ESTIMATE: the first logged entry is
-    the priming entry, the closed form at the start pose from (1, 0) with rho = 1.
+    the priming entry, the closed form at the start pose from (1, 0) with rho = 1.  depth: one value or one per level
+    (gn_sums.plan_depths); an entry is held to the depth of the level whose moments it came from.
     Returns (exact sums, (a, b), level, iteration) of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
     xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
     robust = kind != rr.NONE
-    depth_u = depth * gn_sums.U32 * gn_sums.SECOND_ORDER
     assert int(alog["levels"]) == levels and [int(n) for n in alog["n_iter"][:levels]] == [int(n) for n in log["n_iter"][:levels]], \
         (tag, "the affine log is indexed like the track log", alog["n_iter"], log["n_iter"])
     one = (F32(1), F32(0))
     if mode == ESTIMATE:
         px = pixels_at(0, xi)
         exp = exact(px, 1.0, 0.0)
-        assert_next((alog["prime_a"], alog["prime_b"]), exp, depth, False, guards, one, tag + " priming pair")
+        assert_next((alog["prime_a"], alog["prime_b"]), exp, gn_sums.at_level(depth, 0), False, guards, one, tag + " priming pair")
         want = (F32(alog["prime_a"]), F32(alog["prime_b"]))
     else:
         want = one if given_ab is None else (F32(given_ab[0]), F32(given_ab[1]))
@@ -195,13 +195,15 @@ def replay_call(log, alog, pixels_at, levels, mode, kind=rr.NONE, param=1.0, rob
     for l in range(levels):
         n = int(log["n_iter"][l])
         assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
+        depth_l = gn_sums.at_level(depth, l)
+        depth_u = depth_l * gn_sums.U32 * gn_sums.SECOND_ORDER
         for it in range(n):
             where = "%s level %d iteration %d" % (tag, l, it)
             ab = (F32(alog["a"][l][it]), F32(alog["b"][l][it]))
             if ex_prev is None or mode != ESTIMATE:   # the priming entry / the given row: the device's own bits
                 assert ab[0].tobytes() == want[0].tobytes() and ab[1].tobytes() == want[1].tobytes(), (where, ab, want)
             else:
-                assert_next(ab, ex_prev[0], depth, robust, guards, ex_prev[1], where + " (entry from the iteration before)")
+                assert_next(ab, ex_prev[0], ex_prev[2], robust, guards, ex_prev[1], where + " (entry from the iteration before)")
             s2 = rr.INF
             if robust:
                 s2 = rr.adaptive_s2(prev_res, floor2) if rob_mode == rr.ADAPTIVE else rr.entry(kind, param, given_s2)[3]
@@ -224,7 +226,7 @@ def replay_call(log, alog, pixels_at, levels, mode, kind=rr.NONE, param=1.0, rob
             else:
                 assert after.tobytes() == xi.tobytes(), where
             last = (ex, ab, l, it)
-            ex_prev = (ex, ab)
+            ex_prev = (ex, ab, depth_l)
             prev_res = res
             xi = after.copy()
             n_it += 1

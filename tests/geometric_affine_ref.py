@@ -80,19 +80,17 @@ def replay_call(log, glog, alog, pixels_at, levels, weight, max_diff, mode, give
     (float)S29 are inside the reduction bound, the logged update solves the replayed combined (H, g) within TOL_BACKWARD, and the next
     logged (a, b) is the closed form of the replayed moments inside the propagated bound (ESTIMATE; the first one is the priming
     entry, the closed form at the start pose from (1, 0)) or the given row (GIVEN).
+    ppt: the pixels per thread the levels ran, one value or one per level (Batch.level_plan).
     Returns (exact sums, (a, b)) of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
     xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
-    _, dr, dS = gr.depths(ppt)
-    dM = moment_depth(ppt)
-    fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
     iters = [int(n) for n in log["n_iter"][:levels]]
     assert int(glog["levels"]) == levels and [int(n) for n in glog["n_iter"][:levels]] == iters, (tag, "geometric log", glog["n_iter"], iters)
     assert int(alog["levels"]) == levels and [int(n) for n in alog["n_iter"][:levels]] == iters, (tag, "affine log", alog["n_iter"], iters)
     one = (F32(1), F32(0))
     if mode == ESTIMATE:
         exp = exact(pixels_at(0, xi), weight, max_diff, 1.0, 0.0)
-        ar.assert_next((alog["prime_a"], alog["prime_b"]), exp, dM, False, guards, one, tag + " priming pair")
+        ar.assert_next((alog["prime_a"], alog["prime_b"]), exp, moment_depth(gn_sums.at_level(ppt, 0)), False, guards, one, tag + " priming pair")
         want = (F32(alog["prime_a"]), F32(alog["prime_b"]))
     else:
         want = one if given_ab is None else (F32(given_ab[0]), F32(given_ab[1]))
@@ -102,13 +100,16 @@ def replay_call(log, glog, alog, pixels_at, levels, weight, max_diff, mode, give
     n_it = 0
     for l in range(levels):
         assert iters[l] >= 1, "%s: level %d ran no iteration" % (tag, l)
+        _, dr, dS = gr.depths(gn_sums.at_level(ppt, l))
+        dM = moment_depth(gn_sums.at_level(ppt, l))
+        fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
         for it in range(iters[l]):
             where = "%s level %d iteration %d" % (tag, l, it)
             ab = (F32(alog["a"][l][it]), F32(alog["b"][l][it]))
             if ex_prev is None or mode != ESTIMATE:   # the priming entry / the given row: the device's own bits
                 assert ab[0].tobytes() == want[0].tobytes() and ab[1].tobytes() == want[1].tobytes(), (where, ab, want)
             else:
-                ar.assert_next(ab, ex_prev[0], dM, False, guards, ex_prev[1], where + " (entry from the iteration before)")
+                ar.assert_next(ab, ex_prev[0], ex_prev[2], False, guards, ex_prev[1], where + " (entry from the iteration before)")
             ex = exact(pixels_at(l, xi), weight, max_diff, ab[0], ab[1])
             assert ex["n"] == int(log["n_valid"][l][it]), (where, "n_valid", ex["n"], int(log["n_valid"][l][it]))
             assert ex["n_geo"] == int(glog["n_geo"][l][it]), (where, "n_geo", ex["n_geo"], int(glog["n_geo"][l][it]))
@@ -131,7 +132,7 @@ def replay_call(log, glog, alog, pixels_at, levels, weight, max_diff, mode, give
             else:
                 assert after.tobytes() == xi.tobytes(), where
             last = (ex, ab)
-            ex_prev = (ex, ab)
+            ex_prev = (ex, ab, dM)
             xi = after.copy()
             n_it += 1
     return last, n_it

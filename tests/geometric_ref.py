@@ -221,11 +221,10 @@ def replay_call(log, glog, pixels_at, levels, weight, max_diff, ppt=4, xi0=None,
     """One whole tracking call from its track log and its geometric log.  pixels_at(level, xi) -> pixels() at that level and input
     pose.  Every logged iteration, at the logged input pose: n_valid and n_geo EQUAL the replica's, the logged residual and the logged
     (float)S29 are inside the reduction bound, and the logged update solves the replayed combined (H, g) within TOL_BACKWARD.
+    ppt: the pixels per thread the levels ran, one value or one per level (Batch.level_plan).
     Returns the exact sums of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
     xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
-    _, dr, dS = depths(ppt)
-    fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
     assert int(glog["levels"]) == levels and [int(n) for n in glog["n_iter"][:levels]] == [int(n) for n in log["n_iter"][:levels]], \
         (tag, "the geometric log is indexed like the track log", glog["n_iter"], log["n_iter"])
     last = None
@@ -233,6 +232,8 @@ def replay_call(log, glog, pixels_at, levels, weight, max_diff, ppt=4, xi0=None,
     for l in range(levels):
         n = int(log["n_iter"][l])
         assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
+        _, dr, dS = depths(gn_sums.at_level(ppt, l))
+        fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
         for it in range(n):
             where = "%s level %d iteration %d" % (tag, l, it)
             px = pixels_at(l, xi)

@@ -75,8 +75,12 @@ def reduction_depth(ppt=None, kernel="gn_tile"):
       the rest (sum_partial_rows / sum_partial_class, k_gn_solve) is double precision.
     kernel = "lds_patch": k_track_gn_tile evaluates border pixels in place (gn_sample_slow) and has no deferred loop: ppt + 6 + 3.
 
-    ppt = None: the engine chose (gn_pixels_per_thread = 0).  Its choice is 1, 2 or 4 (Tracker::init halves from 4), so the largest
-    possible depth, that of 4, is used."""
+    ppt is the shape the level RAN: a test reads it per level from the plan in force (Batch.level_plan / MonoBatch.level_plan, i.e.
+    dvo_debug_batch_level_plan; plan_depths() below), whether the config fixed it or left the choice to the engine
+    (gn_pixels_per_thread = 0: Tracker::init halves from 4 per level, so the levels of one call differ).
+
+    ppt = None is the fallback of a caller without a handle (the one-evaluation operators of a default config): the engine's choice
+    is 1, 2 or 4, so the largest possible depth, that of 4, is used.  A batch test must not use it."""
     if ppt is None or ppt == 0:
         ppt = 4
     assert ppt in (1, 2, 4, 8), ppt
@@ -89,6 +93,21 @@ def depth_for_cfg(cfg=None):
     ppt = getattr(cfg, "gn_pixels_per_thread", 0) if cfg is not None else 0
     lds = getattr(cfg, "gn_use_lds_patch", -1) if cfg is not None else -1
     return reduction_depth(ppt if ppt in (1, 2, 4, 8) else None, "lds_patch" if lds > 0 else "gn_tile")
+
+
+def plan_depths(handle, levels):
+    """reduction_depth per pyramid level of the plan in force on a Batch / MonoBatch (level_plan): the shape each level runs"""
+    import dvo_amd
+    out = []
+    for l in range(levels):
+        p = handle.level_plan(l)
+        out.append(reduction_depth(p["ppt"], "lds_patch" if p["schedule"] == dvo_amd.PLAN_LDS_PATCH else "gn_tile"))
+    return out
+
+
+def at_level(x, level):
+    """x[level] of a per-level sequence, x itself of a single value (a harness takes either for its depth / ppt)"""
+    return x[level] if isinstance(x, (list, tuple)) else x
 
 
 def bounds(ex, depth):

@@ -127,18 +127,19 @@ def adaptive_s2(residual_prev, floor2):
     return rp if rp > f2 else f2
 
 
-def replay_call(log, terms_at, levels, kind, param, mode, floor2=None, given_s2=None, tag=""):
+def replay_call(log, terms_at, levels, kind, param, mode, floor2=None, given_s2=None, tag="", depth=17):
     """One whole tracking call from its track log.  terms_at(level, xi) -> orc.optimize_terms at that level and input pose.  Every
     logged iteration: the input pose is the previous xi_after (zero at the start), s2 follows the scale rule (ADAPTIVE: from the previous
     logged residual; GIVEN: given_s2), n_valid equals the term count, the logged residual is (float)sum_r2 / n of the weighted sums to
     the reduction bound, and the logged update solves the weighted normal equations within TOL_BACKWARD.
+    depth: the reduction depth that places the logged residual, one value or one per level (gn_sums.plan_depths).
     Returns (terms, s2) of the finest level's last iteration and the number of iterations replayed."""
     xi = np.zeros(6, F32)
     prev = None
     last = None
     n_it = 0
-    depth_u = 17 * gn_sums.U32 * gn_sums.SECOND_ORDER   # (only to place the logged residual; the sums themselves go through assert_sums)
     for l in range(levels):
+        depth_u = gn_sums.at_level(depth, l) * gn_sums.U32 * gn_sums.SECOND_ORDER   # (places the logged residual; the sums go through assert_sums)
         n = int(log["n_iter"][l])
         assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
         for it in range(n):

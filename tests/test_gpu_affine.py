@@ -66,7 +66,7 @@ def _run(cfg, B, idx, aff=None, rows=None, rows_on_device=False, clear=False, ro
          size=SIZE, expo=True, cams_at=None, obj_gray=None):
     """idx[k][b]: frame of sequence b at push k.  aff: set_affine_brightness arguments (clear: set, then turned off before the first
     push); rows: GIVEN rows; cams_at = (push, cams): set_intrinsics before that push; obj_gray(k, b, gray): replaces a pushed frame.
-    Returns per push dict(status, q, xi, T, logs, ab, alogs, world)."""
+    Returns per push dict(status, q, xi, T, logs, ab, alogs, world, plan); plan = level_plan of every level once the terms are set."""
     g, d, s = _frames(size)
     bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
     if kf:
@@ -87,6 +87,7 @@ def _run(cfg, B, idx, aff=None, rows=None, rows_on_device=False, clear=False, ro
                 bt.set_affine_rows(rows)
         if clear:
             bt.set_affine_brightness(OFF)
+    plan = [bt.level_plan(l) for l in range(LEVELS)]
     outs = []
     for k in range(len(idx)):
         sel = list(idx[k])
@@ -114,7 +115,7 @@ def _run(cfg, B, idx, aff=None, rows=None, rows_on_device=False, clear=False, ro
             t = [_dev(x) for x in (gi, di, si)]
             keep.append(t)
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality(), gray=gi)
+        o = dict(status=bt.last_status(), q=bt.last_track_quality(), gray=gi, plan=plan)
         if aff and not clear:
             o["ab"] = bt.last_affine()
             o["alogs"] = [bt.last_affine_log(b) for b in range(B)]
@@ -257,7 +258,8 @@ def _check_sequence(o, b, obj, ref, aff, rob, depth, where, given=None):
     q = o["q"][b]
     assert q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
     assert F32(q["residual"]).tobytes() == F32(lg["residual"][TOP][it]).tobytes(), where
-    rr.assert_sums(q, ex["terms"], kind, PARAM.get(kind, 1.0), rr.adaptive_s2(_prev_residual(lg), _floor2()) if rob else rr.INF, depth, where)
+    rr.assert_sums(q, ex["terms"], kind, PARAM.get(kind, 1.0), rr.adaptive_s2(_prev_residual(lg), _floor2()) if rob else rr.INF,
+                   gn_sums.at_level(depth, TOP), where)
     return n_it, ab
 
 
@@ -279,12 +281,14 @@ def _empty(o, b):
 
 
 def _replay(cfg, B, aff, rob=None, acts=None, kf=False, cams=None, size=SIZE, outs=None, min_tracked=None, given=None, rows_on_device=False,
-            cams_at=None, obj_gray=None, expo=True, iters_per_seq=3, nonempty=True):
+            cams_at=None, obj_gray=None, expo=True, iters_per_seq=3, nonempty=True, seqs=None, depth=None):
+    """seqs: the sequences replayed against the oracle (None: all); depth: the reduction depth, one value or one per level (None: the
+    config's)"""
     idx = _wide_idx(B)
     if outs is None:
         outs = _run(cfg, B, idx, aff=aff, rob=rob, rows=given, rows_on_device=rows_on_device, acts=acts, kf=kf, cams=cams, size=size,
                     cams_at=cams_at, obj_gray=obj_gray, expo=expo)
-    depth = gn_sums.depth_for_cfg(cfg)
+    depth = gn_sums.depth_for_cfg(cfg) if depth is None else depth
     before = ar.nonempty_calls()
     ref_of = [None] * B
     n = n_it = 0
@@ -293,7 +297,7 @@ def _replay(cfg, B, aff, rob=None, acts=None, kf=False, cams=None, size=SIZE, ou
         Ks = cams_at[1] if cams_at is not None and k >= cams_at[0] else cams
         for b in range(B):
             st = o["status"][b]
-            if st == TRACKED:
+            if st == TRACKED and (seqs is None or b in seqs):
                 K = Ks[b] if Ks is not None else KH
                 kr = ref_of[b]
                 m, ab = _check_sequence(o, b, _oframe(o["gray"][b], idx[k][b], K, size), _oframe(outs[kr]["gray"][b], idx[kr][b], K, size),
@@ -301,14 +305,14 @@ def _replay(cfg, B, aff, rob=None, acts=None, kf=False, cams=None, size=SIZE, ou
                 n_it += m
                 n += 1
                 far += abs(float(ab[0]) - 1.0) > 0.05
-            else:
+            elif st != TRACKED:
                 assert _empty(o, b), (k, b, st)   # SKIPPED / STARTED / BAD_ACTION: (0, 0) and an empty log
             if kf:
                 if st == STARTED or (st == TRACKED and o["world"][2][b]):
                     ref_of[b] = k
             elif st in (TRACKED, STARTED):
                 ref_of[b] = k
-    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * B) and n_it > iters_per_seq * n, (n, n_it)
+    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * (B if seqs is None else len(seqs))) and n_it > iters_per_seq * n, (n, n_it)
     assert not nonempty or ar.nonempty_calls() >= before + iters_per_seq * n // 2   # (the helper really ran: non-empty iterations replayed)
     if aff["mode"] == ESTIMATE and expo and obj_gray is None and aff.get("gain_max", 4.0) >= 4.0 and aff.get("min_pixels", 64) <= 64:
         assert far >= n // 2, "the exposure changes of EXPO should move most entries away from 1"
@@ -350,29 +354,36 @@ class AffineReplay(lockstep.Replay):
     """lockstep.Replay whose tracking step restates the compensated contract (tests/affine_ref.py) instead of the plain comparison"""
     alog = None
     last = None
+    depth = 17      # reduction depth, one value or one per level (gn_sums.plan_depths of the batch)
 
     def _track(self, obj, ref, log):
         last, n = ar.replay_call(log, self.alog, ar.oracle_pixels(obj, ref, self.crop, ar.weight_params()), lockstep.LEVELS, ESTIMATE,
-                                 depth=gn_sums.depth_for_cfg(None), tag=self._where("affine"))
+                                 depth=self.depth, tag=self._where("affine"))
         self.last = last
         self.n_iterations += n
         return np.asarray(log["xi_after"][lockstep.TOP][int(log["n_iter"][lockstep.TOP]) - 1], F32).copy()
 
 
-def test_mono_records_match_the_contract():
-    """the mono batch through tests/lockstep.py: the tracking is compensated, the mapping is the plain one (the keyframes stay the
-    oracle's bit for bit, given the GPU's poses); frames of odd calls are 15 % brighter"""
+def _mono_contract(per_camera):
+    """the mono batch through tests/lockstep.py, default tile config (the automatic plan): the tracking is compensated, the mapping is
+    the plain one (the keyframes stay the oracle's bit for bit, given the GPU's poses); frames of odd calls are 15 % brighter;
+    per_camera: the k_track_gn_ab_cam kernels"""
     orc.set_tracker_params()    # the mono batch of this test runs the reference's constants
     try:
         g, init, ml = tr._mono_frames()
         B = 2
         orders = [[0, 1, 2, 3], [5, 4, 3, 2]]
         sig = np.full_like(init, ml.INIT_SIGMA)
-        mb = dvo.MonoBatch(B, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tr.MONO_SEED))
+        Ks = tr.mono_cameras(B) if per_camera else [K640] * B
+        mb = dvo.MonoBatch(B, Ks if per_camera else K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tr.MONO_SEED),
+                           per_sequence_K=per_camera)
         mb.setInitialDepth(init, sig)
         mb.set_track_quality(True)
         mb.set_affine_brightness(ESTIMATE)
-        reps = [AffineReplay(K640, 640, 480, tr.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        depths = tr.mono_plan(mb)
+        reps = [AffineReplay(Ks[q], 640, 480, tr.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        for r in reps:
+            r.depth = depths
         before = ar.nonempty_calls()
         n = 0
         for k in range(len(orders[0])):
@@ -392,12 +403,20 @@ def test_mono_records_match_the_contract():
                     continue
                 ex, used, l, it = reps[q].last
                 assert l == lockstep.TOP and ab[q].tobytes() == np.array(used, F32).tobytes(), (k, q, ab[q], used)
-                rr.assert_sums(rec[q], ex["terms"], rr.NONE, 1.0, rr.INF, gn_sums.depth_for_cfg(None), "mono call %d seq %d" % (k, q))
+                rr.assert_sums(rec[q], ex["terms"], rr.NONE, 1.0, rr.INF, depths[lockstep.TOP], "mono%s call %d seq %d" % (" per-camera" if per_camera else "", k, q))
                 n += 1
         mb.close()
         assert n == B * (len(orders[0]) - 1) and ar.nonempty_calls() > before
     finally:
         orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
+
+
+def test_mono_records_match_the_contract():
+    _mono_contract(False)
+
+
+def test_mono_records_match_the_contract_per_camera():
+    _mono_contract(True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5: the guards

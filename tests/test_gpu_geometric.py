@@ -58,7 +58,7 @@ def _raw(m):
 
 def _run(cfg, B, idx, geo=None, clear=False, acts=None, kf=False, feed="device", cams=None, size=SIZE, cams_at=None, ref_depth=None, D=None):
     """idx[k][b]: frame of sequence b at push k.  geo: set_geometric arguments (clear: set, then turned off before the first push).
-    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, world)."""
+    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, world, plan); plan = level_plan of every level once the term is set."""
     bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
     if kf:
         bt.set_keyframe_tracking(True)
@@ -71,6 +71,7 @@ def _run(cfg, B, idx, geo=None, clear=False, acts=None, kf=False, feed="device",
         bt.set_geometric(**geo)
         if clear:
             bt.set_geometric(dvo.GEOMETRIC_OFF)
+    plan = [bt.level_plan(l) for l in range(LEVELS)]
     keep, outs = [], []
     for k in range(len(idx)):
         maps = [_maps(size, idx, k, b, ref_depth) for b in range(B)]
@@ -95,7 +96,7 @@ def _run(cfg, B, idx, geo=None, clear=False, acts=None, kf=False, feed="device",
             t = [_dev(x) for x in (gi, di, si)]
             keep.append(t)
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps)
+        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps, plan=plan)
         if geo and not clear:
             o["grec"] = bt.last_geometric()
             o["glogs"] = [bt.last_geometric_log(b) for b in range(B)]
@@ -198,6 +199,7 @@ def _check_sequence(o, b, obj, ref, geo, cfg, ppt, where):
     lg, gl = o["logs"][b], o["glogs"][b]
     ex, n_it = gr.replay_call(lg, gl, gr.frame_pixels(obj, ref, False, _wp(cfg)), LEVELS, geo["weight"], geo["max_diff"], ppt=ppt, tag=where)
     it = int(lg["n_iter"][TOP]) - 1
+    ppt = gn_sums.at_level(ppt, TOP)   # (from here on: the finest level's record)
     rec = o["grec"][b]
     assert int(rec["n_geo"]) == ex["n_geo"] == int(gl["n_geo"][TOP][it]), (where, rec, ex["n_geo"])
     if ex["n_geo"] > 0:

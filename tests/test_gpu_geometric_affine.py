@@ -88,7 +88,8 @@ def _run(cfg, B, idx, setup, reads=("geo", "aff"), acts=None, kf=False, feed="de
          D=None, expo=True, at=None):
     """idx[k][b]: frame of sequence b at push k.  setup(bt): the terms of the batch; at = {push: fn(bt)}: called before that push;
     reads: which families' records and logs are read after every push.
-    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, ab, alogs, world)."""
+    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, ab, alogs, world, plan); plan = level_plan of every level after
+    setup(bt)."""
     bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
     if kf:
         bt.set_keyframe_tracking(True)
@@ -98,6 +99,7 @@ def _run(cfg, B, idx, setup, reads=("geo", "aff"), acts=None, kf=False, feed="de
     if D is not None:
         bt.set_distortion(D)
     setup(bt)
+    plan = [bt.level_plan(l) for l in range(LEVELS)]
     keep, outs = [], []
     for k in range(len(idx)):
         if at and k in at:
@@ -124,7 +126,7 @@ def _run(cfg, B, idx, setup, reads=("geo", "aff"), acts=None, kf=False, feed="de
             t = [_dev(x) for x in (gi, di, si)]
             keep.append(t)
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps)
+        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps, plan=plan)
         if "geo" in reads:
             o["grec"] = bt.last_geometric()
             o["glogs"] = [bt.last_geometric_log(b) for b in range(B)]
@@ -275,6 +277,7 @@ def _check_sequence(o, b, obj, ref, geo, mode, given, cfg, ppt, where):
     (ex, ab), n_it = ga.replay_call(lg, gl, al, ga.frame_pixels(obj, ref, False, _wp(cfg)), LEVELS, geo["weight"], geo["max_diff"], mode,
                                     given_ab=None if given is None else given[b], ppt=ppt, tag=where)
     it = int(lg["n_iter"][TOP]) - 1
+    ppt = gn_sums.at_level(ppt, TOP)   # (from here on: the finest level's record)
     assert o["ab"][b].tobytes() == np.array(ab, F32).tobytes(), (where, o["ab"][b], ab)   # the entry the finest level's last iteration used
     rec = o["grec"][b]
     assert int(rec["n_geo"]) == ex["n_geo"] == int(gl["n_geo"][TOP][it]), (where, rec, ex["n_geo"])

@@ -95,7 +95,8 @@ def _given_scales(B):
 def _run(cfg, B, idx, rob=None, scales=None, scales_on_device=False, clear=False, acts=None, kf=False, feed="device", cams=None,
          size=SIZE, quality=True):
     """idx[k][b]: frame of sequence b at push k.  rob: set_robust_weights arguments (clear: set, then turned off before the first
-    push); scales: GIVEN rows.  Returns per push dict(status, xi, T, logs, q, s2, world)."""
+    push); scales: GIVEN rows.  Returns per push dict(status, xi, T, logs, q, s2, world, plan); plan = level_plan of every level, read
+    once the terms are set (the plan the pushes ran)."""
     g, d, s = _frames(size)
     bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
     if kf:
@@ -115,6 +116,7 @@ def _run(cfg, B, idx, rob=None, scales=None, scales_on_device=False, clear=False
                 bt.set_robust_scales(scales)
         if clear:
             bt.set_robust_weights(dvo.ROBUST_NONE)
+    plan = [bt.level_plan(l) for l in range(LEVELS)]
     outs = []
     for k in range(len(idx)):
         sel = list(idx[k])
@@ -137,7 +139,7 @@ def _run(cfg, B, idx, rob=None, scales=None, scales_on_device=False, clear=False
             t = [_dev(x) for x in (gi, di, si)]
             keep.append(t)
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None)
+        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None, plan=plan)
         if rob and not clear:
             o["s2"] = bt.last_robust_scales()
         if k > 0 or acts is not None or kf:
@@ -332,42 +334,46 @@ def _check_sequence(o, b, obj, ref, rob, given, depth, where):
     given_s2 = None
     if mode == GIVEN:
         given_s2 = np.float32(given[b]) * np.float32(given[b])
-    last, n_it = rr.replay_call(lg, rr.oracle_terms(obj, ref, False), LEVELS, kind, param, mode, floor2=_floor2(), given_s2=given_s2, tag=where)
+    last, n_it = rr.replay_call(lg, rr.oracle_terms(obj, ref, False), LEVELS, kind, param, mode, floor2=_floor2(), given_s2=given_s2, tag=where,
+                                depth=depth)
     t, s2, l, it = last
     assert l == TOP and it == int(lg["n_iter"][TOP]) - 1
     assert np.float32(o["s2"][b]).tobytes() == np.float32(s2).tobytes(), (where, o["s2"][b], s2)
     q = o["q"][b]
     assert q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
     assert np.float32(q["residual"]).tobytes() == np.float32(lg["residual"][TOP][it]).tobytes(), where
-    rr.assert_sums(q, t, kind, param, s2, depth, where)
+    rr.assert_sums(q, t, kind, param, s2, gn_sums.at_level(depth, TOP), where)
     return n_it
 
 
-def _lockstep(cfg, B, rob, acts=None, kf=False, cams=None, size=SIZE, scales_on_device=False, outs=None, min_tracked=None):
+def _lockstep(cfg, B, rob, acts=None, kf=False, cams=None, size=SIZE, scales_on_device=False, outs=None, min_tracked=None, seqs=None,
+              depth=None):
+    """seqs: the sequences replayed against the oracle (None: all; the others keep the no-stale-scale check); depth: the reduction depth,
+    one value or one per level (None: the config's)"""
     idx = _wide_idx(B)
     given = _given_scales(B) if rob["scale_mode"] == GIVEN else None
     if outs is None:
         outs = _run(cfg, B, idx, rob=rob, scales=given, scales_on_device=scales_on_device, acts=acts, kf=kf, cams=cams, size=size)
-    depth = gn_sums.depth_for_cfg(cfg)
+    depth = gn_sums.depth_for_cfg(cfg) if depth is None else depth
     before = rr.nonempty_calls()
     ref_of = [None] * B
     n = n_it = 0
     for k, o in enumerate(outs):
         for b in range(B):
             st = o["status"][b]
-            if st == TRACKED:
+            if st == TRACKED and (seqs is None or b in seqs):
                 K = cams[b] if cams is not None else KH
                 n_it += _check_sequence(o, b, _oframe(idx[k][b], K, size), _oframe(ref_of[b], K, size), rob, given, depth,
                                         "push %d seq %d of %d" % (k, b, B))
                 n += 1
-            else:
+            elif st != TRACKED:
                 assert o["s2"][b] == 0.0, (k, b, st)   # SKIPPED / STARTED: no stale scale
             if kf:
                 if st == STARTED or (st == TRACKED and o["world"][2][b]):
                     ref_of[b] = idx[k][b]
             elif st in (TRACKED, STARTED):
                 ref_of[b] = idx[k][b]
-    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * B) and n_it > 3 * n, (n, n_it)
+    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * (B if seqs is None else len(seqs))) and n_it > 3 * n, (n, n_it)
     assert rr.nonempty_calls() >= before + n // 2
     return outs
 
@@ -464,16 +470,36 @@ class RobustReplay(lockstep.Replay):
     """lockstep.Replay whose tracking step restates the weighted contract (tests/robust_ref.py) instead of the plain comparison"""
     rob = None
     last = None
+    depth = 17      # reduction depth, one value or one per level (gn_sums.plan_depths of the batch)
 
     def _track(self, obj, ref, log):
         last, n = rr.replay_call(log, rr.oracle_terms(obj, ref, self.crop), lockstep.LEVELS, self.rob["kind"], self.rob["param"], ADAPTIVE,
-                                 floor2=_floor2(), tag=self._where("robust"))
+                                 floor2=_floor2(), tag=self._where("robust"), depth=self.depth)
         self.last = last
         self.n_iterations += n
         return np.asarray(log["xi_after"][lockstep.TOP][int(log["n_iter"][lockstep.TOP]) - 1], np.float32).copy()
 
 
-def test_mono_records_match_the_contract():
+def mono_cameras(B):
+    """K640 for sequence 0, then a camera per sequence (the frames stay the ones rendered with K640: the batch and the oracle read
+    them with the same K)"""
+    Ks = np.stack([np.asarray(K640, np.float32).reshape(3, 3)] * B)
+    for q in range(B):
+        Ks[q, 0, 0] *= 1.0 + 0.01 * q; Ks[q, 1, 1] *= 1.0 - 0.005 * q
+    return Ks
+
+
+def mono_plan(mb):
+    """The plan of a two-sequence mono batch with the default tile config (gn_pixels_per_thread = 0) and an opt-in term: 2 x 75 tiles
+    are far below 1024, so every level (40x30, 80x60, 160x120) runs <1, 1> in launch pairs on raster tiles.  Returns the depths."""
+    for l, tiles in enumerate((5, 19, 75)):
+        assert mb.level_plan(l) == dict(ppt=1, group=1, tiles_2d=False, tiles=tiles, schedule=dvo.PLAN_PAIRS), (l, mb.level_plan(l))
+    return gn_sums.plan_depths(mb, lockstep.LEVELS)
+
+
+def _mono_contract(per_camera):
+    """a mono batch with the default tile config (the automatic plan) and Huber weights through tests/lockstep.py; per_camera: the
+    k_track_gn_rw_cam kernels"""
     orc.set_tracker_params()    # the mono batch of this test runs the reference's constants
     try:
         g, init, ml = _mono_frames()
@@ -481,11 +507,16 @@ def test_mono_records_match_the_contract():
         orders = [[0, 1, 2, 3], [5, 4, 3, 2]]
         sig = np.full_like(init, ml.INIT_SIGMA)
         rob = _rob(HUBER)
-        mb = dvo.MonoBatch(B, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=MONO_SEED))
+        Ks = mono_cameras(B) if per_camera else [K640] * B
+        mb = dvo.MonoBatch(B, Ks if per_camera else K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=MONO_SEED),
+                           per_sequence_K=per_camera)
         mb.setInitialDepth(init, sig)
         mb.set_track_quality(True)
         mb.set_robust_weights(**rob)
-        reps = [RobustReplay(K640, 640, 480, MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        depths = mono_plan(mb)
+        reps = [RobustReplay(Ks[q], 640, 480, MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        for r in reps:
+            r.depth = depths
         before = rr.nonempty_calls()
         n = 0
         for k in range(len(orders[0])):
@@ -504,12 +535,20 @@ def test_mono_records_match_the_contract():
                 terms, want, l, it = reps[q].last
                 assert l == lockstep.TOP
                 assert np.float32(s2[q]).tobytes() == np.float32(want).tobytes(), (k, q, s2[q], want)
-                rr.assert_sums(rec[q], terms, HUBER, rob["param"], want, gn_sums.depth_for_cfg(None), "mono call %d seq %d" % (k, q))
+                rr.assert_sums(rec[q], terms, HUBER, rob["param"], want, depths[lockstep.TOP], "mono%s call %d seq %d" % (" per-camera" if per_camera else "", k, q))
                 n += 1
         mb.close()
         assert n == B * (len(orders[0]) - 1) and rr.nonempty_calls() > before
     finally:
         orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
+
+
+def test_mono_records_match_the_contract():
+    _mono_contract(False)
+
+
+def test_mono_records_match_the_contract_per_camera():
+    _mono_contract(True)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6: it helps

@@ -6,6 +6,7 @@ covariance and flags follow from the record; a sequence that did not track repor
 records; and a device-side rule on a device copy restarts exactly the sequences fed an unusable frame.  One tile size throughout
 (gn_pixels_per_thread = 4), as tests/test_gpu_pose_guess.py."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -53,6 +54,7 @@ def _logbits(lg, L):
 IDX = [[0, 1, 2, 3, 4], [1, 2, 3, 4, 5], [2, 3, 4, 5, 0], [3, 2, 5, 4, 1], [4, 1, 4, 3, 2]]
 
 
+@functools.lru_cache(maxsize=None)
 def _frames_of(size, sigma):
     """six frames and their intrinsics: util.frames() at 640x480, the same scene rendered smaller otherwise"""
     w, h = size
@@ -64,15 +66,17 @@ def _frames_of(size, sigma):
     return g.numpy(), d.numpy(), s.numpy(), K
 
 
-def _sensor_run(cfg, B, idx, quality=True, acts=None, kf=False, feed="device", bad=None, cams=None, sigma=0.1, size=(640, 480)):
+def _sensor_run(cfg, B, idx, quality=True, acts=None, kf=False, feed="device", bad=None, cams=None, sigma=0.1, size=(640, 480), K=None):
     """idx[k][b]: frame of sequence b at push k; acts[k] or None; bad[k]: sequences fed an all-invalid frame at push k; cams: {k: K
-    table}.  Returns per push dict(xi, T, status, logs, q, world)."""
-    g, d, s, K = _frames_of(size, sigma)
-    bt = dvo.Batch(B, K, size[0], size[1], 4, 1, cfg=cfg)
+    table}; K: the batch's camera (None: the frames').  Returns per push dict(xi, T, status, logs, q, world, plan); plan = level_plan of
+    the four levels."""
+    g, d, s, K0 = _frames_of(size, sigma)
+    bt = dvo.Batch(B, K0 if K is None else K, size[0], size[1], 4, 1, cfg=cfg)
     if kf:
         bt.set_keyframe_tracking(True)
     if quality:
         bt.set_track_quality(True)
+    plan = [bt.level_plan(l) for l in range(4)]
     outs, keep = [], []
     for k in range(len(idx)):
         sel = list(idx[k])
@@ -99,7 +103,7 @@ def _sensor_run(cfg, B, idx, quality=True, acts=None, kf=False, feed="device", b
             t = [_dev(x) for x in (gi, di, si)]
             keep.append(t)
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None)
+        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None, plan=plan)
         if k > 0 or acts is not None or kf:
             xi, T = bt.last_poses()
             o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
@@ -217,18 +221,19 @@ def _wide_idx(B):
     return idx
 
 
-def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1):
+def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1, cams=None, depth=None, tag="sensor batch "):
     """the record of every TRACKED sequence against the oracle at the input pose of the finest level's last iteration (from the log):
     the max-scaled comparison with orc.optimize, then the one that binds -- H, g, sum_r2 per entry inside the reduction bound of the
-    exact sums of orc.optimize_terms (tests/gn_sums.py).  The records are the batch path's own sums (k_track_gn or the LDS-patch /
+    exact sums of orc.optimize_terms (tests/gn_sums.py).  cams: a K table [B, 3, 3] set before the first push (the _cam kernels; the
+    oracle takes sequence b's row); depth: the finest level's reduction depth (None: the config's).  Returns the run.  The records are the batch path's own sums (k_track_gn or the LDS-patch /
     fused / one-workgroup kernels over many sequences, then sum_partial_rows / sum_partial_class in the solve), observable nowhere
     else.  With keyframes, the reference is the frame that started or last promoted the sequence."""
-    g, d, s, K = _frames_of(size, sigma)
+    g, d, s, K0 = _frames_of(size, sigma)
     idx = _wide_idx(B)
-    outs = _sensor_run(cfg, B, idx, kf=kf, size=size, sigma=sigma)
+    outs = _sensor_run(cfg, B, idx, kf=kf, size=size, sigma=sigma, cams=None if cams is None else {0: cams})
     ref_of = list(idx[0])
     crop = bool(cfg.crop_enable)
-    depth = gn_sums.depth_for_cfg(cfg)
+    depth = gn_sums.depth_for_cfg(cfg) if depth is None else depth
     before = gn_sums.nonempty_calls()
     n = 0
     for k in range(1, len(idx)):
@@ -239,6 +244,7 @@ def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1):
             L = 3
             it = int(lg["n_iter"][L]) - 1
             x_in = lg["xi_after"][L][it - 1] if it > 0 else lg["xi_after"][L - 1][int(lg["n_iter"][L - 1]) - 1]
+            K = K0 if cams is None else cams[b]
             ref = orc.OFrame(g[ref_i], d[ref_i], s[ref_i], K, 4, 1)
             obj = orc.OFrame(g[obj_i], d[obj_i], s[obj_i], K, 4, 1)
             r = orc.optimize(obj.gray(L), ref.gray(L), ref.depth(L), ref.sigma(L), ref.K(L), x_in, L, crop=crop)
@@ -248,7 +254,7 @@ def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1):
             np.testing.assert_allclose(q["g"], r["g"], rtol=0, atol=TOL_H_REL * max(np.abs(r["g"]).max(), 1e-30), err_msg=where)
             np.testing.assert_allclose(q["sum_r2"], r["sum_r2"], rtol=SUM_R2_REL, err_msg=where)
             t = orc.optimize_terms(obj.gray(L), ref.gray(L), ref.depth(L), ref.sigma(L), ref.K(L), x_in, L, crop=crop)
-            gn_sums.assert_gn_sums(q, t, depth, "sensor batch " + where)
+            gn_sums.assert_gn_sums(q, t, depth, tag + where)
             n += 1
         if kf:
             key = o["world"][2]
@@ -257,6 +263,7 @@ def _sensor_oracle(cfg, kf=False, B=3, size=(640, 480), sigma=0.1):
                     ref_of[b] = idx[k][b]
     assert n == B * (len(idx) - 1)
     assert gn_sums.nonempty_calls() >= before + n // 2, "the reduction bound saw too few non-empty term lists"
+    return outs
 
 
 def test_sensor_pairs_match_the_oracle():
