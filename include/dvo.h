@@ -142,7 +142,25 @@ int dvo_batch_create(int n_seq, const float K[9], int width, int height, int lev
 int dvo_batch_destroy(dvo_batch* b);
 /* Frame(gray,depth,sigma,K,levels,culls) for every sequence (frame.hpp:91-106): builds the pyramids of the
  * new frames, tracks them against the previous frames (Tracker::track, tracker.cpp:22-85) and makes them the
- * new reference.  The first call only stores the reference.  Asynchronous on the handle's stream. */
+ * new reference.  The first call only stores the reference.  Asynchronous on the handle's stream.
+ * NaN and +-inf in a pushed float map (every push entry point, dvo_vo_odometrize* included) are taken as the reference takes them
+ * ("Non-finite pixels").  A cull (culls > 0, and every coarser level) reads through getPixel, which turns NaN
+ * and -inf into DVO_INVALID and keeps +inf; at culls = 0 the finest level is a copy of the map.  Of what reaches a level:
+ *   gray of the reference frame (sampled):   NaN, -inf are filled or gated like DVO_INVALID; +inf makes the sums NaN / inf: the
+ *                                            solve answers NaN and the level is refused as below -- or, when no diagonal sum of H is
+ *                                            > 0 (many such pixels), zero: "converged" with an infinite residual.
+ *   gray of the tracked frame (per pixel):   -inf is gated out; NaN and +inf pass the gates (is_invalid is false for NaN): g and
+ *                                            sum_r2 are not finite, every update of that level is refused (tracker.cpp:46-51) and the
+ *                                            pose keeps the coarser levels' value.  ONE NaN gray pixel at a culls = 0 finest level
+ *                                            freezes that level for the push: it runs max_iterations and the quality record shows
+ *                                            DVO_QUALITY_NOT_FINITE | DVO_QUALITY_CAPPED, update_norm NaN, covariance NaN.
+ *                                            With robust weights on (dvo_batch_set_robust_weights) the weight of a NaN or infinite
+ *                                            residual is itself NaN by the formulas below, so H is poisoned too: no diagonal sum
+ *                                            is > 0, the solve returns the ZERO update and the level ends after that iteration as
+ *                                            DVO_QUALITY_CONVERGED with a NaN residual and without NOT_FINITE.
+ *   depth of the reference:                  NaN, +-inf are gated out (as 0).
+ *   sigma of the reference:                  +-inf are clamped to [sigma_min, sigma_max]; NaN poisons g like a NaN gray pixel.
+ * Nothing else of the batch is affected: the other sequences' results keep their bits.  Consumers: INTEGRATION.md section 7. */
 int dvo_batch_push_device(dvo_batch* b, const float* gray_dev, const float* depth_dev, const float* sigma_dev);
 /* Optional look-ahead: build the pyramids of a frame that will be pushed later on a library-owned, low-priority side
  * stream, so that this HBM-bound pass runs beside the tracking of the frame pushed in between.  Call order per step:
@@ -513,7 +531,7 @@ int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts /*[h
  *                (the pose before its update), not at the returned pose, as Gauss-Newton forms them.
  *   residual     sum_r2 / n_valid in float (optimize.cpp:98), -1 when n_valid == 0; update_norm = |xi_update| of that iteration.
  *                Both are the track log's entries bit for bit.
- *   eigenvalues  of H (symmetric), ascending, by Jacobi rotations in double.
+ *   eigenvalues  of H (symmetric), ascending, by Jacobi rotations in double; NaN when a sum (H, g or sum_r2) is not finite.
  *   covariance   upper triangle (as H) of s2 * H^-1, s2 = sum_r2 / (n_valid - 6), in the coordinates of the twist the tracker updates
  *                (xi <- log(exp(xi) exp(upd)), tracker.cpp:46): relative to the reference (the keyframe in keyframe mode and mono),
  *                as dvo_batch_last_poses and the mono tracker's relative twist.  NaN when n_valid <= 6, when RANK_DEFICIENT is set,

@@ -144,6 +144,65 @@ def assert_gn_sums(got, terms, depth, tag=""):
     return worst
 
 
+def per_entry_products(terms):
+    """(n, 28) float64 products of the terms: 21 of H (upper triangle, row major), 6 of g, r^2.  A product of two float32 values is
+    exact in float64 when both are finite; otherwise it is the same NaN / infinity in float32 and in float64 (inf * 0 is NaN in both)."""
+    J = np.ascontiguousarray(terms["J"], np.float64).reshape(-1, 6)
+    r = np.ascontiguousarray(terms["r"], np.float64); rw = np.ascontiguousarray(terms["rw"], np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cols = [J[:, a] * J[:, b] for a in range(6) for b in range(a, 6)] + [J[:, a] * rw for a in range(6)] + [r * r]
+    return np.stack(cols, axis=1) if J.shape[0] else np.zeros((0, 28))
+
+
+def sum_class(p):
+    """Class of the exact sum of the terms p, whatever the order they are added in: 'n' (NaN) if a term is NaN or if both infinities
+    occur, '+' / '-' if infinities of one sign occur, '.' (finite) otherwise.  Finite float32 terms of the sizes at hand cannot carry
+    a partial sum to an infinity, so a float32 tree and a float64 loop agree on the class: a derivation, no tolerance."""
+    if np.isnan(p).any():
+        return "n"
+    pos, neg = bool((p == np.inf).any()), bool((p == -np.inf).any())
+    return "n" if pos and neg else "+" if pos else "-" if neg else "."
+
+
+def value_class(v):
+    return "n" if np.isnan(v) else "+" if v == np.inf else "-" if v == -np.inf else "."
+
+
+def assert_gn_sums_classes(got, terms, depth, tag=""):
+    """assert_gn_sums for terms that may hold NaN / +-inf (a non-finite pixel that passed the gates), per entry of the 28:
+    an entry whose terms are all finite obeys the bound of assert_gn_sums, depth * 2^-24 * (1 + 2^-10) * A, unchanged; every other
+    entry must be of the class of its exact sum (sum_class): NaN, +inf or -inf.  n_valid is the term count.  Returns the largest
+    error / bound ratio over the finite entries and appends (tag, ratio) to RATIOS."""
+    global _nonempty_calls
+    P = per_entry_products(terms)
+    n = P.shape[0]
+    assert int(got["n_valid"]) == n, "%s: n_valid %d, %d terms" % (tag, int(got["n_valid"]), n)
+    val = np.concatenate([np.asarray(got["H"], np.float64).ravel(), np.asarray(got["g"], np.float64).ravel(), [float(got["sum_r2"])]])
+    assert val.size == 28, val.size
+    names = ["H[%d]" % k for k in range(21)] + ["g[%d]" % k for k in range(6)] + ["sum_r2"]
+    f = depth * U32 * SECOND_ORDER
+    worst = 0.0
+    for k in range(28):
+        p = P[:, k]
+        want = sum_class(p)
+        if want != ".":
+            assert value_class(val[k]) == want, "%s: %s = %r, but the exact sum of its terms is of class %r" % (tag, names[k], val[k], want)
+            continue
+        ref = float(p.sum()); A = float(np.abs(p).sum()); bnd = f * A
+        assert np.isfinite(val[k]), "%s: %s = %r, but every term of it is finite (exact %.17g)" % (tag, names[k], val[k], ref)
+        if bnd == 0.0:
+            assert val[k] == 0.0, "%s: %s = %r, but every term of it is zero" % (tag, names[k], val[k])
+            continue
+        ratio = abs(val[k] - ref) / bnd
+        assert ratio <= 1.0, "%s: %s = %.17g, exact %.17g: error %.3g is %.3g times the bound %.3g (depth %d, A = %.6g)" % (
+            tag, names[k], val[k], ref, abs(val[k] - ref), ratio, bnd, depth, A)
+        worst = max(worst, float(ratio))
+    if n > 0:
+        _nonempty_calls += 1
+    RATIOS.append((str(tag), worst))
+    return worst
+
+
 def report(title):
     """what the last test of a file prints under -s: the ratios recorded since the previous report (the files of one pytest process
     share this module, and each prints its own), the largest first"""

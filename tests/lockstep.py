@@ -17,6 +17,7 @@ dependence of stereo matches on 1e-5 pose differences never come
 pose.  Test infrastructure only."""
 import numpy as np
 
+import nonfinite_cases
 import orc
 from util import TOL_BACKWARD, assert_composed, backward_error
 
@@ -88,6 +89,7 @@ class Replay:
         self.hist = []
         self.frame_id = -1
         self.n_key_translation = self.n_key_count = self.n_update = self.n_update_written = self.n_iterations = 0
+        self.n_nonfinite = self.n_d13 = 0     # iterations whose oracle sums were not finite; of those, D13's (NaN against the oracle's zero)
         self.updated = np.zeros((height >> CULLS, width >> CULLS), bool)   # top-map pixels some Mapper::update changed
 
     def _where(self, what):
@@ -143,7 +145,20 @@ class Replay:
                 o = orc.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=self.crop)
                 upd, after = log["xi_update"][l][it], log["xi_after"][l][it]
                 assert o["n_valid"] == int(log["n_valid"][l][it]), (where, "n_valid GPU %d oracle %d" % (log["n_valid"][l][it], o["n_valid"]))
-                if o["n_valid"] > 0:
+                if o["n_valid"] > 0 and not (np.isfinite(o["H"]).all() and np.isfinite(o["g"]).all() and np.isfinite(o["sum_r2"])):
+                    # a NaN / inf pixel passed the gates ("Non-finite pixels"): no normal equations to solve.
+                    # The residual is the oracle's within the usual tolerance where both are finite and of its class otherwise; the
+                    # update is of the class tests/nonfinite_cases.py derives from the terms
+                    res = np.float32(log["residual"][l][it])
+                    if np.isfinite(res) and np.isfinite(o["residual"]):
+                        np.testing.assert_allclose(res, o["residual"], rtol=RESIDUAL_RTOL, err_msg=where)
+                    else:
+                        assert (np.isnan(res) and np.isnan(o["residual"])) or res == o["residual"], (where, "residual class", res, o["residual"])
+                    t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=self.crop)
+                    kind = nonfinite_cases.assert_update_class(upd, o, t, where)      # (all NaN where the oracle answers zero: D13)
+                    self.n_nonfinite += 1
+                    self.n_d13 += int(kind == "nan")
+                elif o["n_valid"] > 0:
                     np.testing.assert_allclose(log["residual"][l][it], o["residual"], rtol=RESIDUAL_RTOL, err_msg=where)
                     back = backward_error(o["H"], o["g"], upd)
                     assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
@@ -174,7 +189,8 @@ class Replay:
 
     def coverage(self):
         return dict(key_translation=self.n_key_translation, key_count=self.n_key_count, updates=self.n_update,
-                    updates_written=self.n_update_written, iterations=self.n_iterations)
+                    updates_written=self.n_update_written, iterations=self.n_iterations,
+                    nonfinite_iterations=self.n_nonfinite, d13_iterations=self.n_d13)
 
 
 def total(replays):

@@ -208,3 +208,75 @@ def test_zero_terms_demand_exact_zeros_and_the_count_is_checked():
     assert gn_sums.nonempty_calls() == before + 1          # an empty term list does not count as a use of the helper
     with pytest.raises(AssertionError):
         assert_gn_sums(dict(zero, g=np.array([0, 0, 1e-30, 0, 0, 0])), none, DEPTH, "not zero")
+
+
+# ---------------------------------------------------------------- assert_gn_sums_classes: terms that hold NaN / +-inf
+def _class_case(where, value, level=1):
+    import nonfinite_cases as nf
+    _, o, t = nf.reference(where, value, "full", (96, 50), level)
+    return dict(H=o["H"].copy(), g=o["g"].copy(), sum_r2=o["sum_r2"], n_valid=o["n_valid"]), t
+
+
+@pytest.mark.parametrize("where,value", [("obj_gray", "nan"), ("obj_gray", "+inf"), ("ref_gray", "+inf"), ("ref_sigma", "nan")])
+def test_classes_accept_the_oracle_and_reject_a_moved_entry_and_a_swapped_class(where, value):
+    from gn_sums import assert_gn_sums_classes, per_entry_products, sum_class
+    good, t = _class_case(where, value)
+    depth = reduction_depth(1)
+    before = gn_sums.nonempty_calls()
+    # the oracle's own double sums: the finite entries far inside the bound, every other entry of the derived class
+    assert assert_gn_sums_classes(good, t, depth, "oracle %s %s" % (where, value)) < 1e-6
+    assert gn_sums.nonempty_calls() == before + 1
+    with pytest.raises(AssertionError):      # assert_gn_sums itself keeps refusing such terms
+        assert_gn_sums(good, t, depth, "refused")
+    P = per_entry_products(t)
+    cls = [sum_class(P[:, k]) for k in range(28)]
+    assert "." != cls[27] or where == "ref_sigma"
+    flat = lambda m: np.concatenate([m["H"], m["g"], [m["sum_r2"]]])
+    unflat = lambda v: dict(H=v[:21].copy(), g=v[21:27].copy(), sum_r2=float(v[27]), n_valid=good["n_valid"])
+    # (1) every finite entry in turn moved by twice its bound
+    finite = [k for k in range(28) if cls[k] == "."]
+    assert finite or where == "ref_gray"      # (+inf in the sampled image poisons all 28)
+    for k in finite:
+        v = flat(good)
+        v[k] += 2 * depth * U32 * SECOND_ORDER * np.abs(P[:, k]).sum()
+        with pytest.raises(AssertionError):
+            assert_gn_sums_classes(unflat(v), t, depth, "moved")
+    # (2) a finite entry turned NaN; (3) NaN <-> inf and +inf <-> -inf on every entry that is not finite
+    for k in finite[:1]:
+        v = flat(good); v[k] = np.nan
+        with pytest.raises(AssertionError):
+            assert_gn_sums_classes(unflat(v), t, depth, "finite -> NaN")
+    swapped = 0
+    for k in range(28):
+        if cls[k] == ".":
+            continue
+        for other in {"n": (np.inf, -np.inf, 0.0), "+": (np.nan, -np.inf, 1e30), "-": (np.nan, np.inf, -1e30)}[cls[k]]:
+            v = flat(good); v[k] = other
+            with pytest.raises(AssertionError):
+                assert_gn_sums_classes(unflat(v), t, depth, "swapped")
+            swapped += 1
+    assert swapped >= 3
+    with pytest.raises(AssertionError):
+        assert_gn_sums_classes(dict(good, n_valid=good["n_valid"] - 1), t, depth, "count")
+
+
+def test_classes_on_finite_terms_are_the_plain_bound():
+    from gn_sums import assert_gn_sums_classes
+    t = level_terms(2)
+    m = tree_model(t, 4)
+    assert assert_gn_sums_classes(m, t, 13, "tree") == assert_gn_sums(m, t, 13, "tree")
+    ex, muts = _mutations(t)
+    for name, mut in muts:
+        if _visible(mut, ex):
+            with pytest.raises(AssertionError):
+                assert_gn_sums_classes(mut, t, DEPTH, name)
+
+
+def test_sum_class_is_order_independent():
+    from gn_sums import sum_class
+    inf = np.inf
+    assert sum_class(np.array([1.0, inf, 2.0])) == "+" and sum_class(np.array([-inf, 1.0])) == "-"
+    assert sum_class(np.array([inf, -inf])) == "n" and sum_class(np.array([1.0, np.nan, inf])) == "n"
+    assert sum_class(np.zeros(0)) == "." and sum_class(np.array([1e30, -1e30])) == "."
+    with np.errstate(invalid="ignore"):      # 0 * inf is NaN in float32 and in float64 alike
+        assert np.isnan(np.float32(0) * np.float32(inf)) and np.isnan(0.0 * inf)
