@@ -1,6 +1,7 @@
 // dvo_capi.cpp -- the extern "C" surface declared in include/dvo.h.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <dlfcn.h>
 #include <new>
@@ -906,6 +907,135 @@ int dvo_op_pyramid(int dev, const float* gray, const float* depth, const float* 
         if (sigma && sigma_out && sigma_out[l]) DVO_TRY(download(sigma_out[l], fs.sigma[l], ln, c.s));
     }
     DVO_HIP(hipStreamSynchronize(c.s));
+    return DVO_OK;
+}
+
+namespace {
+int bad_pyramid_frames(const char* what)
+{
+    set_error(std::string("dvo_op_pyramid_frames: ") + what);
+    return DVO_ERR_BAD_ARGUMENT;
+}
+// one frame of every sequence of dvo_op_pyramid_frames on the device: `bytes` per image row times `rows` rows times n images each
+struct OpFrames {
+    DevBuf g, d, s;
+    FrameInput in;
+    int upload(const float* gray, const float* depth, const float* sigma, const uint8_t* rgb, int channels, const uint16_t* depth16,
+               float depth_scale, size_t px, bool rows_decimated, hipStream_t st)
+    {
+        auto up = [&](DevBuf& b, const void* host, size_t bytes) -> int {
+            DVO_TRY(b.alloc(bytes));
+            DVO_HIP(hipMemcpyAsync(b.p, host, bytes, hipMemcpyHostToDevice, st));
+            return DVO_OK;
+        };
+        in.rows_decimated = rows_decimated;
+        if (rgb) {
+            DVO_TRY(up(g, rgb, px * (size_t)channels));
+            in.rgb = g.as<uint8_t>(); in.channels = channels; in.depth_scale = depth_scale;
+            if (depth16) { DVO_TRY(up(d, depth16, px * sizeof(uint16_t))); in.depth16 = d.as<uint16_t>(); }
+            return DVO_OK;
+        }
+        DVO_TRY(up(g, gray, px * sizeof(float)));
+        in.gray = g.as<float>();
+        if (depth) {
+            DVO_TRY(up(d, depth, px * sizeof(float))); DVO_TRY(up(s, sigma, px * sizeof(float)));
+            in.depth = d.as<float>(); in.sigma = s.as<float>();
+        }
+        return DVO_OK;
+    }
+};
+}  // namespace
+
+int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
+                          float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran)
+{
+    if (!args) return bad_pyramid_frames("args is NULL");
+    if (args->struct_size != (int)sizeof(dvo_pyramid_frames_args)) return bad_pyramid_frames("struct_size is not sizeof(dvo_pyramid_frames_args)");
+    const dvo_pyramid_frames_args& p = *args;
+    if (p.n_seq < 1) return bad_pyramid_frames("n_seq < 1");
+    const bool raw = p.rgb != nullptr;
+    if (raw == (p.gray != nullptr)) return bad_pyramid_frames("exactly one of gray (float maps) and rgb (raw frames) must be given");
+    if (raw && (p.depth || p.sigma || p.gray2 || p.depth2 || p.sigma2)) return bad_pyramid_frames("float maps beside raw frames");
+    if (!raw && (p.depth16 || p.rgb2 || p.depth16_2)) return bad_pyramid_frames("raw frames beside float maps");
+    if ((p.depth != nullptr) != (p.sigma != nullptr)) return bad_pyramid_frames("depth and sigma come together");
+    if (raw && p.channels != 1 && p.channels != 3 && p.channels != 4) return bad_pyramid_frames("channels must be 1, 3 or 4");
+    if (!std::isfinite(p.depth_scale) || p.depth_scale < 0.0f) return bad_pyramid_frames("depth_scale must be finite and >= 0");
+    if (p.flags & ~(DVO_PYRAMID_ROWS_DECIMATED | DVO_PYRAMID_FORCE_WEIGHT_MAPS | DVO_PYRAMID_SPLIT)) return bad_pyramid_frames("unknown flag bits");
+    const bool second = raw ? p.rgb2 != nullptr : p.gray2 != nullptr;
+    if (p.seq_action) {
+        if (!second) return bad_pyramid_frames("seq_action without second frames");
+        if (raw ? (p.depth16_2 != nullptr) != (p.depth16 != nullptr)
+                : ((p.depth2 != nullptr) != (p.depth != nullptr) || (p.sigma2 != nullptr) != (p.sigma != nullptr)))
+            return bad_pyramid_frames("the second frames must carry the maps the first carry");
+        for (int q = 0; q < p.n_seq; q++)
+            if (p.seq_action[q] > DVO_SEQ_RESTART) return bad_pyramid_frames("an action is not DVO_SEQ_SKIP, DVO_SEQ_TRACK or DVO_SEQ_RESTART");
+    } else if (second || p.depth2 || p.sigma2 || p.depth16_2) {
+        return bad_pyramid_frames("second frames without seq_action");
+    }
+    const float Kid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    Geometry g;
+    DVO_TRY(make_geometry(Kid, p.w, p.h, p.levels, p.culls, g));
+    const bool dec = (p.flags & DVO_PYRAMID_ROWS_DECIMATED) != 0;
+    if (dec && !can_decimate_rows(g)) return bad_pyramid_frames("DVO_PYRAMID_ROWS_DECIMATED needs culls > 0 and a height that is a multiple of 2^culls");
+    dvo_config dc;
+    if (cfg) dc = *cfg; else dvo_config_default(&dc);
+
+    OpCtx c; DVO_TRY(c.open(dev));
+    const size_t px = (size_t)p.w * (size_t)(dec ? p.h >> p.culls : p.h) * (size_t)p.n_seq;
+    const float scale = p.depth_scale > 0.0f ? p.depth_scale : 1.0f / 5000.0f;
+    FrameSet A, B;
+    OpFrames first, next;
+    DevBuf act;
+    DVO_TRY(A.alloc(g, p.n_seq, dc));
+    DVO_HIP(hipMemsetAsync(A.arena.p, 0xff, A.arena.bytes, c.s));
+    DVO_TRY(first.upload(p.gray, p.depth, p.sigma, p.rgb, p.channels, p.depth16, scale, px, dec, c.s));
+    if (p.flags & DVO_PYRAMID_FORCE_WEIGHT_MAPS) A.allow_const_weight = false;
+    // the split build's second stream and events, as Batch owns them
+    PyramidSplit split;
+    struct SplitOwner {
+        PyramidSplit& s;
+        ~SplitOwner()
+        {
+            if (s.fork) (void)hipEventDestroy(s.fork);
+            if (s.done) (void)hipEventDestroy(s.done);
+            if (s.side) (void)hipStreamDestroy(s.side);
+        }
+    } owner{split};
+    const bool want_split = (p.flags & DVO_PYRAMID_SPLIT) != 0;
+    if (want_split) {
+        DVO_HIP(hipStreamCreate(&split.side));
+        DVO_HIP(hipEventCreateWithFlags(&split.fork, hipEventDisableTiming));
+        DVO_HIP(hipEventCreateWithFlags(&split.done, hipEventDisableTiming));
+    }
+    PyramidKernel k;
+    FrameSet* out = &A;
+    if (!p.seq_action) {
+        const bool halves = build_pyramid(A, first.in, c.s, /*keep_sigma=*/true, nullptr, nullptr, want_split ? &split : nullptr, &k);
+        if (split.err != hipSuccess) DVO_HIP(split.err);
+        if (halves) DVO_HIP(hipStreamWaitEvent(c.s, split.done, 0));
+    } else {
+        build_pyramid(A, first.in, c.s, /*keep_sigma=*/true);
+        DVO_TRY(B.alloc(g, p.n_seq, dc));
+        DVO_HIP(hipMemsetAsync(B.arena.p, 0xff, B.arena.bytes, c.s));
+        if (p.flags & DVO_PYRAMID_FORCE_WEIGHT_MAPS) B.allow_const_weight = false;
+        DVO_TRY(next.upload(p.gray2, p.depth2, p.sigma2, p.rgb2, p.channels, p.depth16_2, scale, px, dec, c.s));
+        DVO_TRY(act.alloc(((size_t)p.n_seq + 15) & ~(size_t)15));
+        DVO_HIP(hipMemcpyAsync(act.p, p.seq_action, (size_t)p.n_seq, hipMemcpyHostToDevice, c.s));
+        const bool halves = build_pyramid(B, next.in, c.s, /*keep_sigma=*/true, act.as<uint8_t>(), &A, want_split ? &split : nullptr, &k);
+        if (split.err != hipSuccess) DVO_HIP(split.err);
+        if (halves) DVO_HIP(hipStreamWaitEvent(c.s, split.done, 0));
+        out = &B;
+    }
+    for (int l = 0; l < g.levels; l++) {
+        const size_t ln = (size_t)g.w[l] * g.h[l] * (size_t)p.n_seq;
+        if (gray_out && gray_out[l]) DVO_TRY(download(gray_out[l], out->gray[l], ln, c.s));
+        if (depth_out && depth_out[l]) DVO_TRY(download(depth_out[l], out->depth[l], ln, c.s));
+        if (sigma_out && sigma_out[l]) DVO_TRY(download(sigma_out[l], out->sigma[l], ln, c.s));
+        if (wgt_out && wgt_out[l]) DVO_TRY(download(wgt_out[l], out->wgt[l], ln, c.s));
+    }
+    DVO_HIP(hipStreamSynchronize(c.s));
+    if (want_split) DVO_HIP(hipStreamSynchronize(split.side));
+    if (ran) { ran->kind = k.kind; ran->culls = k.culls; ran->plan = k.plan; }
     return DVO_OK;
 }
 

@@ -266,16 +266,19 @@ static PyramidArgs float_args(FrameSet& fs, const float* gray_dev, const float* 
 }
 
 void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma,
-                   bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from)
+                   bool rows_decimated, const uint8_t* seq_action, const FrameSet* copy_from, PyramidKernel* ran)
 {
     PyramidArgs a = float_args(fs, gray_dev, depth_dev, sigma_dev, keep_sigma, rows_decimated);
     plan_copy(a, seq_action, copy_from);
-    launch_pyramid(a, fs.n_seq, s);
+    const PyramidKernel k = launch_pyramid(a, fs.n_seq, s);
+    if (ran) *ran = k;
 }
 
 bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma, const uint8_t* seq_action, const FrameSet* copy_from,
-                   PyramidSplit* split)
+                   PyramidSplit* split, PyramidKernel* ran)
 {
+    PyramidKernel none;
+    PyramidKernel& k = ran ? *ran : none;
     if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
                                          // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
         PyramidArgs a = frame_args(fs, false);
@@ -285,17 +288,17 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         a.seq_action = seq_action;
         fs.sigma_by_validity = false;
-        launch_pyramid(a, fs.n_seq, s);
+        k = launch_pyramid(a, fs.n_seq, s);
         return false;
     }
     // sensor-depth frames with lens undistortion (dvo_batch_set_sensor_distortion): the arguments of the plain build plus the remap,
     // whole frames -- launch_pyramid picks k_pyramid_remap_depth
     if (!in.raw()) {
-        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from); return false; }
+        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from, &k); return false; }
         PyramidArgs a = float_args(fs, in.gray, in.depth, in.sigma, keep_sigma, false);
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         plan_copy(a, seq_action, copy_from);
-        launch_pyramid(a, fs.n_seq, s);
+        k = launch_pyramid(a, fs.n_seq, s);
         return false;
     }
     PyramidArgs a = frame_args(fs, in.rows_decimated);
@@ -319,6 +322,7 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     if (split && pyramid_can_split(a)) {
         // stage A where the single kernel would run; stage B on the side stream, after everything queued on `s` so far (every earlier
         // launch that may still read the set it overwrites)
+        k = {DVO_PYRAMID_KERNEL_SPLIT, a.culls, 0};
         launch_pyramid_coarse(a, fs.n_seq, s);
         split->err = hipEventRecord(split->fork, s);
         if (split->err == hipSuccess) split->err = hipStreamWaitEvent(split->side, split->fork, 0);
@@ -326,7 +330,7 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         if (split->err == hipSuccess) split->err = hipEventRecord(split->done, split->side);
         return split->err == hipSuccess;
     }
-    launch_pyramid(a, fs.n_seq, s);
+    k = launch_pyramid(a, fs.n_seq, s);
     return false;
 }
 

@@ -120,8 +120,10 @@ struct FrameSet {  // n_seq frames: gray/depth/sigma pyramids, level l stored as
 // Builds pyramids of (gray, depth, sigma) device inputs [n_seq][src_h][src_w]; depth/sigma may be null.
 // keep_sigma = false: the sigma pyramid is only folded into `wgt`, not stored (frame-to-frame tracking never reads it again)
 // seq_action / copy_from (Batch plan): the sequences whose effective action is DVO_SEQ_SKIP read no input and take copy_from's values
+// ran (optional, here and below): the kernel the launcher chose (dvo_op_pyramid_frames)
 void build_pyramid(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, hipStream_t s, bool keep_sigma = true,
-                   bool rows_decimated = false, const uint8_t* seq_action = nullptr, const FrameSet* copy_from = nullptr);
+                   bool rows_decimated = false, const uint8_t* seq_action = nullptr, const FrameSet* copy_from = nullptr,
+                   PyramidKernel* ran = nullptr);
 // One frame of every sequence as handed over by the caller: float maps (gray [+ depth + sigma]) or raw sensor frames
 // (u8 gray / RGB / RGBA [+ u16 depth], converted while the pyramid is built: loader.cpp:55-60,137-147, transform.cpp:60-76).
 struct FrameInput {
@@ -148,7 +150,7 @@ struct PyramidSplit {
 // Returns true when the build was split (only with `split`, and only where pyramid_can_split allows it: a plan, a remap, float maps
 // or an unusual alignment take the single kernel on `s`).
 bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_sigma = true, const uint8_t* seq_action = nullptr,
-                   const FrameSet* copy_from = nullptr, PyramidSplit* split = nullptr);
+                   const FrameSet* copy_from = nullptr, PyramidSplit* split = nullptr, PyramidKernel* ran = nullptr);
 // the sigma_by_validity a build of `in` into `fs` with keep_sigma = false would leave (the weight storage of the frame set)
 inline bool weights_by_validity(const FrameSet& fs, const FrameInput& in) { return in.raw() && in.depth16 != nullptr && fs.allow_const_weight; }
 // Host -> device copy of n_img images (raw or float; rows of row_bytes bytes).  With culls > 0 and decimate set only every

@@ -603,7 +603,12 @@ struct MonoStartArgs {
 };
 void launch_regularize_redecimate_plan(const RegDecArgs& a, const MonoStartArgs& p, hipStream_t s);
 
-void launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
+// Which kernel a build ran: kind = DVO_PYRAMID_KERNEL_* (include/dvo.h), culls = the CULLS instance of the raw4 family (0: the kernel has
+// none), plan = the PLAN instance.  Said by the launcher that made the choice, where it made it (dvo_op_pyramid_frames reports it).
+struct PyramidKernel {
+    int kind = DVO_PYRAMID_KERNEL_SCALAR, culls = 0, plan = 0;
+};
+PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
 // The split build: launch_pyramid_coarse (k_pyramid_raw4_coarse: the gray maps below the top level) and
 // launch_pyramid_rest (k_pyramid_raw4_rest: everything else) together write what launch_pyramid writes.  pyramid_can_split: the
 // arguments are those of a plain raw build (1-channel u8 gray + u16 depth, culls 1 or 2, no plan, no remap) with the alignment the

@@ -3040,19 +3040,19 @@ static void launch_pyramid_remap_depth(const PyramidArgs& a, hipStream_t s)
     else hipLaunchKernelGGL((k_pyramid_remap_depth<1, false>), grid, dim3(256), 0, s, a);
 }
 
-void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
+PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
 {
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
     if (a.remap != nullptr && (a.raw_depth != nullptr || a.src[1] != nullptr)) {   // sensor-depth frames, lens undistortion fused in
         launch_pyramid_remap_depth(a, s);
-        return;
+        return {DVO_PYRAMID_KERNEL_REMAP, 0, a.seq_action != nullptr};
     }
     if (a.remap != nullptr) {   // lens undistortion fused in (mono frames): never k_pyramid_raw4 / k_pyramid
         if (a.seq_action != nullptr) hipLaunchKernelGGL(k_pyramid_remap_plan, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
         else hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
-        return;
+        return {DVO_PYRAMID_KERNEL_REMAP, 0, a.seq_action != nullptr};
     }
     // raw 1-channel frames with the usual alignment: four kept pixels per thread, wide loads and stores
     const bool vec = a.raw_rgb != nullptr && a.raw_channels == 1 && (a.culls == 1 || a.culls == 2) && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 &&
@@ -3075,14 +3075,15 @@ void launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
         if (plan) {
             if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, true>), grid, dim3(256), 0, s, a);
             else hipLaunchKernelGGL((k_pyramid_raw4<2, true>), grid, dim3(256), 0, s, a);
-            return;
+            return {DVO_PYRAMID_KERNEL_RAW4, a.culls, 1};
         }
         if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, false>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((k_pyramid_raw4<2, false>), grid, dim3(256), 0, s, a);
-        return;
+        return {DVO_PYRAMID_KERNEL_RAW4, a.culls, 0};
     }
     if (plan) hipLaunchKernelGGL(k_pyramid<true>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_pyramid<false>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
+    return {DVO_PYRAMID_KERNEL_SCALAR, 0, plan ? 1 : 0};
 }
 
 bool pyramid_can_split(const PyramidArgs& a)

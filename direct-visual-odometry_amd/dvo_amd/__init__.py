@@ -178,6 +178,7 @@ EXPORTS = [
     "dvo_op_gn_step_geometric",
     "dvo_batch_set_geometric_affine", "dvo_op_gn_step_geometric_affine",
     "dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts",
+    "dvo_op_pyramid_frames",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -217,6 +218,34 @@ class KfFusionRecord(C.Structure):
 
 
 KF_FUSION_RECORD_DTYPE = np.dtype([("struct_size", np.int32), ("n_candidates", np.int32), ("n_fused", np.int32), ("n_gated", np.int32)])
+
+# the kernel a pyramid build ran and the flags of op_pyramid_frames: include/dvo.h
+PYRAMID_KERNEL_SCALAR, PYRAMID_KERNEL_RAW4, PYRAMID_KERNEL_SPLIT, PYRAMID_KERNEL_REMAP = 0, 1, 2, 3
+PYRAMID_ROWS_DECIMATED, PYRAMID_FORCE_WEIGHT_MAPS, PYRAMID_SPLIT = 1, 2, 4
+
+
+class PyramidKernel(C.Structure):
+    """dvo_pyramid_kernel (include/dvo.h): kind, and the CULLS and PLAN instance of the kernel a build ran."""
+    _fields_ = [("kind", C.c_int), ("culls", C.c_int), ("plan", C.c_int)]
+
+    def name(self):
+        plan = "true" if self.plan else "false"
+        if self.kind == PYRAMID_KERNEL_SCALAR:
+            return "k_pyramid<%s>" % plan
+        if self.kind == PYRAMID_KERNEL_RAW4:
+            return "k_pyramid_raw4<%d, %s>" % (self.culls, plan)
+        if self.kind == PYRAMID_KERNEL_SPLIT:
+            return "k_pyramid_raw4_coarse<%d> + k_pyramid_raw4_rest<%d>" % (self.culls, self.culls)
+        return "remap"
+
+
+class PyramidFramesArgs(C.Structure):
+    """dvo_pyramid_frames_args (include/dvo.h)."""
+    _fields_ = [("struct_size", C.c_int), ("n_seq", C.c_int), ("w", C.c_int), ("h", C.c_int), ("levels", C.c_int), ("culls", C.c_int),
+                ("flags", C.c_int), ("channels", C.c_int), ("depth_scale", C.c_float),
+                ("gray", C.c_void_p), ("depth", C.c_void_p), ("sigma", C.c_void_p), ("rgb", C.c_void_p), ("depth16", C.c_void_p),
+                ("seq_action", C.c_void_p), ("gray2", C.c_void_p), ("depth2", C.c_void_p), ("sigma2", C.c_void_p),
+                ("rgb2", C.c_void_p), ("depth16_2", C.c_void_p)]
 
 _lib = None
 
@@ -339,6 +368,45 @@ def pyramid(gray, depth, sigma, levels, culls, dev=0):
     _check(lib().dvo_op_pyramid(dev, fp(gray), fp(d) if d is not None else None, fp(s) if s is not None else None,
                                 w, h, levels, culls, arr(go), arr(do), arr(so)))
     return go, (do if d is not None else None), (so if s is not None else None)
+
+
+def op_pyramid_frames(w, h, levels, culls, gray=None, depth=None, sigma=None, rgb=None, depth16=None, depth_scale=0.0, flags=0,
+                      seq_action=None, second=None, cfg=None, dev=0):
+    """dvo_op_pyramid_frames (include/dvo.h): the batched pyramid build through the engine, once.  Float maps gray [+ depth + sigma]
+    [n][rows][w], or raw frames rgb u8 [n][rows][w] / [n][rows][w][3 or 4] [+ depth16 u16]; rows = h, or h >> culls with
+    PYRAMID_ROWS_DECIMATED.  seq_action [n] with second = dict(gray=, depth=, sigma=) / dict(rgb=, depth16=): the planned build.
+    Returns dict(gray, depth, sigma, wgt: lists of [n][h_l][w_l] float32 per level, kernel: PyramidKernel)."""
+    keep = []
+
+    def ptr(a, dt):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a)
+        return a.ctypes.data
+
+    first = rgb if rgb is not None else gray
+    n = int(np.shape(first)[0])
+    a = PyramidFramesArgs()
+    a.struct_size = C.sizeof(PyramidFramesArgs)
+    a.n_seq, a.w, a.h, a.levels, a.culls, a.flags = n, int(w), int(h), int(levels), int(culls), int(flags)
+    a.depth_scale = float(depth_scale)
+    if rgb is not None:
+        a.channels = 1 if np.ndim(rgb) == 3 else int(np.shape(rgb)[3])
+    a.gray, a.depth, a.sigma = ptr(gray, np.float32), ptr(depth, np.float32), ptr(sigma, np.float32)
+    a.rgb, a.depth16 = ptr(rgb, np.uint8), ptr(depth16, np.uint16)
+    a.seq_action = ptr(seq_action, np.uint8)
+    if second is not None:
+        a.gray2, a.depth2, a.sigma2 = (ptr(second.get(k), np.float32) for k in ("gray", "depth", "sigma"))
+        a.rgb2, a.depth16_2 = ptr(second.get("rgb"), np.uint8), ptr(second.get("depth16"), np.uint16)
+    shapes = [(n, (h >> culls) >> (levels - 1 - i), (w >> culls) >> (levels - 1 - i)) for i in range(levels)]
+    out = {m: [np.zeros(sh, np.float32) for sh in shapes] for m in ("gray", "depth", "sigma", "wgt")}
+    arr = lambda lst: (FP * levels)(*[fp(x) for x in lst])
+    ran = PyramidKernel()
+    _check(lib().dvo_op_pyramid_frames(dev, C.byref(cfg) if cfg is not None else None, C.byref(a), arr(out["gray"]), arr(out["depth"]),
+                                       arr(out["sigma"]), arr(out["wgt"]), C.byref(ran)))
+    out["kernel"] = ran
+    return out
 
 
 # ------------------------------------------------------------------ Track

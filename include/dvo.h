@@ -789,6 +789,65 @@ int dvo_op_warp_image(int dev, const float xi[6], const float* gray, const float
  * (w>>culls>>(levels-1-i)) x (h>>culls>>(levels-1-i))), any of depth/sigma may be NULL. */
 int dvo_op_pyramid(int dev, const float* gray, const float* depth, const float* sigma, int w, int h,
                    int levels, int culls, float* const gray_out[], float* const depth_out[], float* const sigma_out[]);
+/* The batched pyramid build of the push entry points, run once on host pointers: n_seq frames through the engine's own build (the
+ * argument blocks, the fused weight maps, the plan's copy-forward and the launch decision are the ones a batch uses), every map of
+ * every level returned, and the kernel that ran reported by the launcher that chose it.
+ * Input, one of:
+ *   float maps   gray [n_seq][rows][w], optionally depth AND sigma (both or neither), rgb = NULL
+ *   raw frames   rgb [n_seq][rows][w][channels] u8 with channels 1 (gray), 3 (R,G,B) or 4 (R,G,B,A), optionally depth16 [n_seq][rows][w]
+ *                u16 and depth_scale (0 = 1/5000); gray = depth = sigma = NULL.  Converted as the raw push entry points convert:
+ *                gray = (float)g8 * (float)(1/255) with g8 the byte (1 channel) or (R * 4899 + G * 9617 + B * 1868 + 8192) >> 14 in
+ *                integers (dvo_op_ingest's luma); with depth16: depth = (float)d16 * depth_scale, sigma = 0.1f where d16 > 0 else 1.0f,
+ *                gray = DVO_INVALID where d16 == 0.
+ * rows = h, or h >> culls with DVO_PYRAMID_ROWS_DECIMATED: the buffers hold only rows 0, 2^culls, 2 * 2^culls ... of each frame (what
+ * the host push forms upload; needs culls > 0 and h a multiple of 2^culls).
+ * Output: level l (0 = coarsest) of a map is [n_seq][h_l][w_l] with w_l = (w >> culls) >> (levels - 1 - l), h_l likewise, and holds
+ * pixel (x << s, y << s) of the converted input, s = culls + (levels - 1 - l), with NaN and every value <= DVO_INVALID replaced by
+ * DVO_INVALID -- except the top level at culls = 0, which is the input unchanged.  wgt = step_l / min(max(sigma, sigma_min),
+ * sigma_max), one float division, with step_l = step_level1 / step_level2 for l = 1 / 2 and step_default otherwise (cfg, or the
+ * defaults for NULL).  The build keeps sigma (keep_sigma = true), so with depth all four maps are written whether or not
+ * DVO_PYRAMID_FORCE_WEIGHT_MAPS is set (the flag clears the frame sets' constant-weight shortcut, as DVO_WEIGHT_MAPS does for a
+ * batch).  A map the build does not write (depth, sigma and wgt without depth) comes back as words of 0xffffffff: the frame sets are
+ * filled with them before the build, so an element the build should have written and did not shows too.
+ * Any of the four output arrays, and any entry, may be NULL.
+ * DVO_PYRAMID_SPLIT asks for the split build (k_pyramid_raw4_coarse + k_pyramid_raw4_rest, each on a stream of its own as in a
+ * batch); where it is not possible the single kernel runs, which is no error: *ran says what ran.
+ * seq_action != NULL: a planned build.  The first frames are built plainly into a set A; then the second frames (gray2 ... / rgb2,
+ * depth16_2: the same kind, shape and optional maps as the first) are built into a set B with the EFFECTIVE per-sequence actions
+ * seq_action[n_seq] (DVO_SEQ_SKIP / TRACK / RESTART) and A as the set to copy forward from, and B is returned: a SKIP sequence's maps
+ * are A's top-level values decimated as above and A's wgt, and its second input frame is not read.  *ran is B's build.
+ * ran->kind: DVO_PYRAMID_KERNEL_SCALAR k_pyramid<plan>; _RAW4 k_pyramid_raw4<culls, plan>; _SPLIT k_pyramid_raw4_coarse<culls> +
+ * k_pyramid_raw4_rest<culls>; _REMAP the undistorting kernels (never from this op).  culls is 0 where the kernel has no such instance.
+ * Errors, returned before anything is queued -> DVO_ERR_BAD_ARGUMENT: NULL args, a struct_size that is not sizeof, n_seq < 1, a
+ * geometry dvo_batch_create refuses, both or neither of gray and rgb, depth without sigma or the reverse, float maps beside raw ones,
+ * channels not 1 / 3 / 4, a depth_scale that is negative or not finite, unknown flag bits, DVO_PYRAMID_ROWS_DECIMATED where rows
+ * cannot be decimated, second frames without seq_action or of another kind than the first, seq_action without second frames, an
+ * action that is not 0 / 1 / 2. */
+#define DVO_PYRAMID_KERNEL_SCALAR 0
+#define DVO_PYRAMID_KERNEL_RAW4   1
+#define DVO_PYRAMID_KERNEL_SPLIT  2
+#define DVO_PYRAMID_KERNEL_REMAP  3
+#define DVO_PYRAMID_ROWS_DECIMATED    1
+#define DVO_PYRAMID_FORCE_WEIGHT_MAPS 2
+#define DVO_PYRAMID_SPLIT             4
+typedef struct dvo_pyramid_kernel {
+    int kind, culls, plan;
+} dvo_pyramid_kernel;
+typedef struct dvo_pyramid_frames_args {
+    int struct_size;                      /* sizeof(dvo_pyramid_frames_args) */
+    int n_seq, w, h, levels, culls, flags;
+    int channels;                         /* raw frames: 1, 3 or 4 */
+    float depth_scale;                    /* raw frames with depth16: 0 = 1/5000 */
+    const float *gray, *depth, *sigma;    /* float maps */
+    const uint8_t* rgb;                   /* raw frames */
+    const uint16_t* depth16;
+    const uint8_t* seq_action;            /* [n_seq], or NULL: one plain build */
+    const float *gray2, *depth2, *sigma2; /* the second frames of a planned build */
+    const uint8_t* rgb2;
+    const uint16_t* depth16_2;
+} dvo_pyramid_frames_args;
+int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
+                          float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran);
 /* Track::optimize, src/track/optimize.cpp:10-99: one Gauss-Newton step on one level.
  * H = upper triangle of sum J^T J (21), g = sum J^T (w r) (6).  mask (optional, w*h bytes). */
 typedef struct dvo_gn_result {
