@@ -1323,6 +1323,82 @@ int dvo_op_depth_update(int dev, const dvo_config* cfg, int n_hist, const float*
     return DVO_OK;
 }
 
+namespace {
+int bad_update_batch(const char* what)
+{
+    set_error(std::string("dvo_op_depth_update_batch: ") + what);
+    return DVO_ERR_BAD_ARGUMENT;
+}
+}  // namespace
+
+int dvo_op_depth_update_batch(int dev, const dvo_config* cfg, const dvo_depth_update_batch_args* args, float* depth, float* sigma,
+                              float* age, int* valid_updates, int* clamped)
+{
+    if (!args) return bad_update_batch("args is NULL");
+    if (args->struct_size != (int)sizeof(dvo_depth_update_batch_args)) return bad_update_batch("struct_size is not sizeof(dvo_depth_update_batch_args)");
+    const dvo_depth_update_batch_args& p = *args;
+    if (p.n_seq < 1) return bad_update_batch("n_seq < 1");
+    if (!p.K || !p.n_total || !p.kf_gray || !p.kf_xi || !p.obj_gray || !p.obj_xi || !p.obj_rel_xi || !p.need || !p.frame_id)
+        return bad_update_batch("a NULL input");
+    if (!depth || !sigma || !age) return bad_update_batch("a NULL map");
+    if (p.w < 64 || p.h < 64) return bad_update_batch("w or h < 64");
+    if (p.ring < 1 || p.ring > 64) return bad_update_batch("ring outside 1 .. 64");
+    DVO_TRY(check_intrinsics("dvo_op_depth_update_batch", p.K, p.per_camera ? (size_t)p.n_seq : 1));
+    for (int q = 0; q < p.n_seq; q++) {
+        if (p.n_total[q] < 1) return bad_update_batch("n_total < 1");
+        if (p.need[q] != 0 && p.need[q] != 1) return bad_update_batch("need is not 0 or 1");
+    }
+    dvo_config dc;
+    if (cfg) dc = *cfg; else dvo_config_default(&dc);
+    dc.device = dev;
+    dc.stream = nullptr;
+    MonoBatch mb;
+    DVO_TRY(mb.init(p.n_seq, p.K, p.w, p.h, p.ring, &dc, p.per_camera != 0));
+    const int T = mb.g.top(), R = p.ring;
+    const size_t np = (size_t)mb.top_pixels(), ns = (size_t)p.n_seq;
+    hipStream_t st = mb.stream;
+    // the sequences' state as k_mono_decide / k_mono_commit leave it: the ring by slot, the frame's poses, the flags
+    std::vector<MonoSeq> meta(ns);
+    std::vector<float> hx(ns * R * 6, 0.0f);
+    memset(meta.data(), 0, sizeof(MonoSeq) * ns);
+    DVO_HIP(hipMemsetAsync(mb.ring_gray.p, 0xff, mb.ring_gray.bytes, st));   // (a slot no keyframe was given for: NaN)
+    for (size_t q = 0; q < ns; q++) {
+        MonoSeq& m = meta[q];
+        const int n_total = p.n_total[q], n_hist = n_total < R ? n_total : R;
+        for (int i = 0; i < n_hist; i++) {
+            const int slot = (n_total - n_hist + i) % R;
+            memcpy(&hx[(q * R + slot) * 6], p.kf_xi + (q * R + i) * 6, 6 * sizeof(float));
+            DVO_HIP(hipMemcpyAsync(mb.ring_gray.as<float>() + (q * R + slot) * np, p.kf_gray + (q * R + i) * np, np * sizeof(float),
+                                   hipMemcpyHostToDevice, st));
+        }
+        for (int k = 0; k < 6; k++) {
+            m.ref_xi[k] = p.kf_xi[(q * R + (n_hist - 1)) * 6 + k];
+            m.frame_xi[k] = p.obj_xi[q * 6 + k];
+            m.rel_xi[k] = p.obj_rel_xi[q * 6 + k];
+        }
+        pose_from_xi(m.rel_xi, 1.0f, m.rel_pose);
+        m.n_total = n_total; m.frame_id = p.frame_id[q]; m.need = p.need[q];
+    }
+    DVO_HIP(hipMemcpyAsync(mb.meta.p, meta.data(), sizeof(MonoSeq) * ns, hipMemcpyHostToDevice, st));
+    DVO_HIP(hipMemcpyAsync(mb.hist_xi.p, hx.data(), hx.size() * sizeof(float), hipMemcpyHostToDevice, st));
+    DVO_HIP(hipMemcpyAsync(mb.ref.depth[T], depth, ns * np * sizeof(float), hipMemcpyHostToDevice, st));
+    DVO_HIP(hipMemcpyAsync(mb.ref.sigma[T], sigma, ns * np * sizeof(float), hipMemcpyHostToDevice, st));
+    DVO_HIP(hipMemcpyAsync(mb.ref_age.p, age, ns * np * sizeof(float), hipMemcpyHostToDevice, st));
+    DVO_HIP(hipMemcpyAsync(mb.frm.gray[T], p.obj_gray, ns * np * sizeof(float), hipMemcpyHostToDevice, st));
+    DVO_TRY(mb.queue_depth_update(0, nullptr));   // (every sequence reads its own MonoSeq::frame_id)
+    DVO_HIP(hipGetLastError());
+    DVO_TRY(download(depth, mb.ref.depth[T], ns * np, st));
+    DVO_TRY(download(sigma, mb.ref.sigma[T], ns * np, st));
+    DVO_TRY(download(age, mb.ref_age.p, ns * np, st));
+    DVO_HIP(hipMemcpyAsync(meta.data(), mb.meta.p, sizeof(MonoSeq) * ns, hipMemcpyDeviceToHost, st));
+    DVO_HIP(hipStreamSynchronize(st));
+    for (size_t q = 0; q < ns; q++) {
+        if (valid_updates) valid_updates[q] = meta[q].valid_updates;
+        if (clamped) clamped[q] = meta[q].clamped;
+    }
+    return DVO_OK;
+}
+
 int dvo_op_ingest(int dev, const uint8_t* rgb, int channels, const uint16_t* depth16, int w, int h, float depth_scale,
                   float sigma_valid, float sigma_invalid, int invalidate_gray, float* gray, float* depth, float* sigma)
 {

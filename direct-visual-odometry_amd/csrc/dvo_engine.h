@@ -717,6 +717,7 @@ struct MonoBatch {
     double prof_update_ms = 0, prof_regularize_ms = 0, prof_propagate_ms = 0;
     uint64_t prof_frames = 0;
     int collect_map_profile();
+    int queue_depth_update(int frame_id, MapEv* pe);   // k_age_table + k_depth_update[_cam] of one frame (pe: profiling events or nullptr)
     // Per-sequence skip / restart (dvo_batch_set_mono_actions).  Allocated on first use; a batch that never sets
     // actions runs the plain path.  k_plan resolves the actions with plan.has_ref = "has a keyframe"; started = has started before (the
     // first start keeps the slot's own initial maps); need_save parks MonoSeq::need of the sequences that do not track.

@@ -195,6 +195,33 @@ int MonoBatch::odometrize_host(const void* frames, FrameInput in)
     return DVO_OK;
 }
 
+// The !need branch of Mapper::estimate for every sequence: the stereo update of the reference maps against the keyframe each pixel was
+// born in (mapper.cpp:76-137) -- k_age_table over the ring, then k_depth_update (k_depth_update_cam in a per-camera batch).  Its own
+// function so that dvo_op_depth_update_batch queues exactly what odometrize() queues.
+int MonoBatch::queue_depth_update(int frame_id, MapEv* pe)
+{
+    const int T = g.top(), tw = g.w[T], th = g.h[T];
+    MonoSeq* m = meta.as<MonoSeq>();
+    AgeTableArgs ta{};
+    ta.meta = m; ta.hist_xi = hist_xi.as<float>(); ta.ages = ages.as<AgeEntry>(); ta.n_seq = n_seq; ta.R = R; ta.n_hist = -1;
+    if (pe) DVO_HIP(hipEventRecord(pe->e[2], stream));
+    launch_age_table(ta, stream);
+    UpdateArgs a{};
+    a.ref_depth = ref.depth[T]; a.ref_sigma = ref.sigma[T]; a.ref_age = ref_age.as<float>();
+    a.obj_gray = frm.gray[T];
+    a.ages = ages.as<AgeEntry>();
+    a.ring_gray = ring_gray.as<float>(); a.meta = m;
+    a.n_seq = n_seq; a.R = R; a.w = tw; a.h = th; a.crop = cfg.crop_enable; a.obj_id = frame_id;
+    a.clamp_age = 1;
+    a.seed = cfg.rng_seed;
+    a.k = g.k[T];
+    memcpy(a.K9, g.K9[T], sizeof a.K9);
+    a.seq_k = cam_top(); a.seq_K9 = cam_map();   // (per-camera batch: k_depth_update_cam)
+    launch_depth_update(a, stream);
+    if (pe) DVO_HIP(hipEventRecord(pe->e[3], stream));
+    return DVO_OK;
+}
+
 int MonoBatch::odometrize(const FrameInput& in)
 {  // system.hpp:44-74 for every sequence
     if (!in.key0() || (in.raw() && in.channels != 1 && in.channels != 3 && in.channels != 4)) { set_error("null device pointer / bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
@@ -308,25 +335,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         launch_propagate_batch(a, stream);
         if (pe) DVO_HIP(hipEventRecord(pe->e[1], stream));
     }
-    {   // !need: stereo update of the reference maps against the keyframe each pixel was born in (mapper.cpp:76-137)
-        AgeTableArgs ta{};
-        ta.meta = m; ta.hist_xi = hist_xi.as<float>(); ta.ages = ages.as<AgeEntry>(); ta.n_seq = n_seq; ta.R = R; ta.n_hist = -1;
-        if (pe) DVO_HIP(hipEventRecord(pe->e[2], stream));
-        launch_age_table(ta, stream);
-        UpdateArgs a{};
-        a.ref_depth = ref.depth[T]; a.ref_sigma = ref.sigma[T]; a.ref_age = ref_age.as<float>();
-        a.obj_gray = frm.gray[T];
-        a.ages = ages.as<AgeEntry>();
-        a.ring_gray = ring_gray.as<float>(); a.meta = m;
-        a.n_seq = n_seq; a.R = R; a.w = tw; a.h = th; a.crop = cfg.crop_enable; a.obj_id = frame_id;
-        a.clamp_age = 1;
-        a.seed = cfg.rng_seed;
-        a.k = g.k[T];
-        memcpy(a.K9, g.K9[T], sizeof a.K9);
-        a.seq_k = cam_top(); a.seq_K9 = cam_map();   // (per-camera batch: k_depth_update_cam)
-        launch_depth_update(a, stream);
-        if (pe) DVO_HIP(hipEventRecord(pe->e[3], stream));
-    }
+    DVO_TRY(queue_depth_update(frame_id, pe));   // !need: the stereo update of the reference maps (mapper.cpp:76-137)
     {   // ... need: the frame becomes the newest keyframe (FrameHistory::push, frame.hpp:151-157)
         PromoteArgs pa{};
         int sgi = 0;

@@ -179,6 +179,7 @@ EXPORTS = [
     "dvo_batch_set_geometric_affine", "dvo_op_gn_step_geometric_affine",
     "dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts",
     "dvo_op_pyramid_frames",
+    "dvo_op_depth_update_batch",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -246,6 +247,14 @@ class PyramidFramesArgs(C.Structure):
                 ("gray", C.c_void_p), ("depth", C.c_void_p), ("sigma", C.c_void_p), ("rgb", C.c_void_p), ("depth16", C.c_void_p),
                 ("seq_action", C.c_void_p), ("gray2", C.c_void_p), ("depth2", C.c_void_p), ("sigma2", C.c_void_p),
                 ("rgb2", C.c_void_p), ("depth16_2", C.c_void_p)]
+
+
+class DepthUpdateBatchArgs(C.Structure):
+    """dvo_depth_update_batch_args (include/dvo.h)."""
+    _fields_ = [("struct_size", C.c_int), ("n_seq", C.c_int), ("w", C.c_int), ("h", C.c_int), ("ring", C.c_int), ("per_camera", C.c_int),
+                ("K", C.c_void_p), ("n_total", C.c_void_p), ("kf_gray", C.c_void_p), ("kf_xi", C.c_void_p), ("obj_gray", C.c_void_p),
+                ("obj_xi", C.c_void_p), ("obj_rel_xi", C.c_void_p), ("need", C.c_void_p), ("frame_id", C.c_void_p)]
+
 
 _lib = None
 
@@ -543,6 +552,34 @@ def mapper_update(hist_gray, hist_xi, obj_gray, obj_xi, obj_rel_xi, obj_id, K, r
     _check(lib().dvo_op_depth_update(dev, C.byref(cfg) if cfg is not None else None, n, garr, fp(hx), fp(og), fp(ox),
                                      fp(orx), int(obj_id), fp(K), w, h, fp(d), fp(s), fp(a), C.byref(v)))
     return d, s, a, v.value
+
+
+def op_depth_update_batch(w, h, ring, K, n_total, kf_gray, kf_xi, obj_gray, obj_xi, obj_rel_xi, need, frame_id, depth, sigma, age,
+                          cfg=None, dev=0):
+    """dvo_op_depth_update_batch (include/dvo.h): the mapping update of one mono-batch call, on given per-sequence state.  w, h: the
+    frame size (maps are (h >> 2) x (w >> 2)); K: [3][3] at full resolution for every sequence, or [n_seq][3][3]: one per sequence
+    (the per-camera kernels); kf_gray [n_seq][ring][mh][mw] and kf_xi [n_seq][ring][6]: each sequence's retained keyframes, oldest
+    first.  Returns (depth, sigma, age, valid_updates[n_seq], clamped[n_seq])."""
+    d = f32(depth).copy(); s = f32(sigma).copy(); a = f32(age).copy()
+    n = d.shape[0]
+    K = f32(K)
+    per_camera = K.ndim == 3
+    arrs = dict(K=K.reshape(-1), n_total=np.ascontiguousarray(n_total, np.int32), kf_gray=f32(kf_gray), kf_xi=f32(kf_xi), obj_gray=f32(obj_gray),
+                obj_xi=f32(obj_xi), obj_rel_xi=f32(obj_rel_xi), need=np.ascontiguousarray(need, np.int32),
+                frame_id=np.ascontiguousarray(frame_id, np.int32))
+    mh, mw = h >> 2, w >> 2
+    assert d.shape == s.shape == a.shape == arrs["obj_gray"].shape == (n, mh, mw), (d.shape, (n, mh, mw))
+    assert arrs["kf_gray"].shape == (n, ring, mh, mw) and arrs["kf_xi"].shape == (n, ring, 6) and K.size == (9 * n if per_camera else 9)
+    assert arrs["obj_xi"].shape == arrs["obj_rel_xi"].shape == (n, 6) and all(arrs[k].shape == (n,) for k in ("n_total", "need", "frame_id"))
+    args = DepthUpdateBatchArgs()
+    args.struct_size = C.sizeof(DepthUpdateBatchArgs)
+    args.n_seq, args.w, args.h, args.ring, args.per_camera = n, w, h, ring, 1 if per_camera else 0
+    for k, v in arrs.items():
+        setattr(args, k, v.ctypes.data)
+    valid = np.full(n, -1, np.int32); clamped = np.full(n, -1, np.int32)
+    _check(lib().dvo_op_depth_update_batch(dev, C.byref(cfg) if cfg is not None else None, C.byref(args), fp(d), fp(s), fp(a),
+                                           valid.ctypes.data_as(C.POINTER(C.c_int)), clamped.ctypes.data_as(C.POINTER(C.c_int))))
+    return d, s, a, valid, clamped
 
 
 # ------------------------------------------------------------------ Core::Loader (dataset front-end) and evaluation

@@ -904,6 +904,39 @@ int dvo_op_depth_update(int dev, const dvo_config* cfg, int n_hist, const float*
                         const float* hist_xi, const float* obj_gray, const float obj_xi[6],
                         const float obj_rel_xi[6], int obj_id, const float K[9], int w, int h,
                         float* ref_depth, float* ref_sigma, float* ref_age, int* valid_updates);
+/* Mapper::update as a MONO BATCH runs it (parity op): the !need branch of one call of dvo_batch_odometrize -- k_age_table over each
+ * sequence's keyframe ring, then k_depth_update, or k_depth_update_cam with per_camera -- for n_seq sequences whose state is given
+ * instead of tracked.  The op creates a mono batch of n_seq sequences for w x h frames (3 levels, 2 culls: maps are mw x mh = (w >> 2)
+ * x (h >> 2)) with ring size `ring` and K ([9] at FULL resolution, or [n_seq][9] with per_camera != 0: the batch's own per-sequence
+ * tables), fills its buffers and queues what the batch queues.  Per sequence q:
+ *   n_total[q] >= 1   keyframes created so far.  The newest n_hist = min(n_total, ring) are retained: kf_gray[q][i] (mw x mh top-level
+ *                     gray) and kf_xi[q][i] (world twist), i = 0 .. n_hist - 1 OLDEST FIRST (entries i >= n_hist are not read), are
+ *                     stored at ring slot (n_total - n_hist + i) % ring, as the batch's commits leave them.
+ *   obj_gray[q], obj_xi[q], obj_rel_xi[q], frame_id[q]   the tracked frame: top-level gray, world twist, twist relative to the newest
+ *                     keyframe, frame id (the reset depth's hash key).
+ *   need[q]           0 or 1: 1 = the sequence creates a keyframe on this frame and takes no part: its maps come back as given.
+ *   depth, sigma, age [n_seq][mh][mw], in place: the newest keyframe's top-level maps.
+ * A pixel whose age points past the ring (n_hist - 1 - (int)age < 0) is searched against the oldest retained keyframe and counted in
+ * clamped[q] (dvo_mono_stats::clamped_pixels' contract); a negative age (>= n_hist) leaves the pixel alone.  valid_updates[q] = the accepted
+ * updates.  Both arrays are written for every sequence (0 for need = 1) and may be NULL.  cfg: crop_enable and rng_seed are used.
+ * Errors, returned before anything is queued -> DVO_ERR_BAD_ARGUMENT: NULL args, a struct_size that is not sizeof, n_seq < 1, a NULL
+ * input or map, a geometry or K dvo_batch_create_mono[_cameras] refuses (w or h < 64, ring outside 1 .. 64, K not finite or fx, fy
+ * <= 0), n_total < 1, need not 0 or 1. */
+typedef struct dvo_depth_update_batch_args {
+    int struct_size;                 /* sizeof(dvo_depth_update_batch_args) */
+    int n_seq, w, h, ring, per_camera;
+    const float* K;                  /* [9], or [n_seq][9] with per_camera */
+    const int* n_total;              /* [n_seq] */
+    const float* kf_gray;            /* [n_seq][ring][mh][mw] */
+    const float* kf_xi;              /* [n_seq][ring][6] */
+    const float* obj_gray;           /* [n_seq][mh][mw] */
+    const float* obj_xi;             /* [n_seq][6] */
+    const float* obj_rel_xi;         /* [n_seq][6] */
+    const int* need;                 /* [n_seq] */
+    const int* frame_id;             /* [n_seq] */
+} dvo_depth_update_batch_args;
+int dvo_op_depth_update_batch(int dev, const dvo_config* cfg, const dvo_depth_update_batch_args* args, float* depth, float* sigma,
+                              float* age, int* valid_updates, int* clamped);
 /* math::se3 (src/math/se3.cpp:70-131) evaluated ON THE DEVICE (the tracker's pose chain runs there) */
 int dvo_op_se3_exp(int dev, const float xi[6], float T[16]);
 int dvo_op_se3_log(int dev, const float T[16], float xi[6]);

@@ -1039,6 +1039,52 @@ void orc_regularize(const float* depth, const float* sigma, int w, int h, float*
         }
 }
 
+/* Branch census (orc_mapper_update_census): counters on the side of the sequential mapper; g_cen is NULL outside that call.  The
+ * predicates are k_depth_update's, restated literally (csrc/dvo_map_kernels.hip: depth_update_head, depth_update_tail). */
+static long long* g_cen = NULL;
+static unsigned g_cen_px;          /* classes of the pixel in flight */
+static int g_cen_px_steps;
+static float g_cen_pcx, g_cen_pcy; /* the previous step's centre target */
+static int g_cen_gate;             /* the pixel in flight reached sigmaEstimate's end */
+static inline void cen_add(int k) { g_cen[k]++; g_cen_px |= 1u << k; }
+
+/* the kernel's loop test on the oracle's values; `go` is the literal test's decision */
+static void cen_loop_test(float ddx, float ddy, float length, int go)
+{
+    const double Ld = (double)length, L2 = Ld * Ld, L2lo = L2 * (1.0 - 1e-12), L2hi = L2 * (1.0 + 1e-12);
+    const float L2f = length * length, L2f_lo = L2f * (1.0f - 1e-5f), L2f_hi = L2f * (1.0f + 1e-5f);
+    const float q2f = fmaf(ddx, ddx, ddy * ddy);
+    int kgo;
+    if (q2f < L2f_lo) { kgo = 1; cen_add(ORC_CEN_TEST_FLOAT); }
+    else if (q2f > L2f_hi) { kgo = 0; cen_add(ORC_CEN_TEST_FLOAT); }
+    else {
+        const double q2 = (double)ddx * (double)ddx + (double)ddy * (double)ddy;
+        if (q2 < L2lo) { kgo = 1; cen_add(ORC_CEN_TEST_DOUBLE); }
+        else if (q2 > L2hi) { kgo = 0; cen_add(ORC_CEN_TEST_DOUBLE); }
+        else {
+            kgo = sqrt(q2) < Ld;
+            cen_add(ORC_CEN_TEST_SQRT);
+            cen_add(kgo ? ORC_CEN_DBAND_GO : ORC_CEN_DBAND_STOP);
+        }
+        cen_add(kgo ? ORC_CEN_FBAND_GO : ORC_CEN_FBAND_STOP);
+    }
+    if (kgo != go) cen_add(ORC_CEN_SHORTCUT_DIFFERS);
+}
+
+/* one search step, after pt advanced: the kernel's need_n and inner */
+static void cen_step(float ptx, float pty, float dirx, float diry, int count, int w, int h)
+{
+    cen_add(ORC_CEN_STEPS);
+    g_cen_px_steps++;
+    const float nx = ptx + dirx * -1.0f, ny = pty + diry * -1.0f;
+    const float cx = ptx + dirx * 0.0f, cy = pty + diry * 0.0f;
+    if (count != 0 && !((nx == g_cen_pcx) & (ny == g_cen_pcy))) cen_add(ORC_CEN_NEED_N);
+    if (count == 0 && nx == 0.0f && ny == 0.0f) cen_add(ORC_CEN_FIRST_ORIGIN); /* (the kernel's previous centre starts as (0, 0)) */
+    g_cen_pcx = cx; g_cen_pcy = cy;
+    const int inner = (ptx >= 2.0f) & (ptx < (float)(w - 3)) & (pty >= 2.0f) & (pty < (float)(h - 3));
+    if (!inner) cen_add(ORC_CEN_STEP_NOT_INNER);
+}
+
 void orc_implement_update(const float* obj_gray, const float* born_gray, const float* born_gx, const float* born_gy,
                           int w, int h, const float r_xi[6], const float K[9], int qx, int qy,
                           float depth, float sigma, float* new_depth, float* new_sigma)
@@ -1061,11 +1107,18 @@ void orc_implement_update(const float* obj_gray, const float* born_gray, const f
     float bestx = ptx, besty = pty;
     float min_ssd = 6.0f; /* 2.0f * N */
     int count = 0;
+    if (g_cen) {
+        if (!(length > 0.0f)) cen_add(ORC_CEN_LENGTH_NOT_POS);
+        if (length >= 102.0f) cen_add(ORC_CEN_HEAD_103);
+    }
     for (;;) {
         const float ddx = ptx - start[0], ddy = pty - start[1];
-        if (!(sqrt((double)ddx * ddx + (double)ddy * ddy) < (double)length)) break;
+        const int go = sqrt((double)ddx * ddx + (double)ddy * ddy) < (double)length;
+        if (g_cen) cen_loop_test(ddx, ddy, length, go);
+        if (!go) break;
         float ssd = 0;
         ptx += dirx; pty += diry;
+        if (g_cen) cen_step(ptx, pty, dirx, diry, count, w, h);
         for (int i = 0; i < 3; i++) {
             const float k = (float)(i - 1);
             const float tx = ptx + dirx * k, ty = pty + diry * k;
@@ -1076,7 +1129,16 @@ void orc_implement_update(const float* obj_gray, const float* born_gray, const f
             ssd = (float)((double)ssd + 1.0 * aw / 3 * (double)(diff * diff));
         }
         if (ssd < min_ssd) { bestx = ptx; besty = pty; min_ssd = ssd; }
-        if (count++ > 100) break;
+        if (count++ > 100) {
+            if (g_cen) cen_add(ORC_CEN_CAP);
+            break;
+        }
+    }
+    if (g_cen) { /* the head's step count (depth_update_head) bounds the search: the workgroup's counting sort relies on it */
+        const int head = !(length > 0.0f) ? 1 : (length >= 102.0f ? 103 : (int)length + 2);
+        if (g_cen_px_steps > head) cen_add(ORC_CEN_HEAD_SHORT);
+        if ((double)min_ssd > 3 * 0.1) cen_add(ORC_CEN_SSD_REJECT);
+        else if (bestx < 0 || besty < 0 || bestx > (float)w || besty > (float)h) cen_add(ORC_CEN_BEST_OUTSIDE);
     }
     if ((double)min_ssd > 3 * 0.1) return; /* N * MATCHING_THRESHOLD_RATIO */
     /* implement.cpp:196-200 */
@@ -1111,9 +1173,14 @@ void orc_implement_update(const float* obj_gray, const float* born_gray, const f
         const float alpha = (dmax - dmin) / l;
         int mx = 0, my = 0;
         round_coord(bestx, &mx); round_coord(besty, &my); /* Mat_(Point2f) -> cvRound */
+        if (g_cen && (mx < 0 || mx > w - 1 || my < 0 || my > h - 1)) cen_add(ORC_CEN_D5_CLAMP);
         mx = mx < 0 ? 0 : (mx > w - 1 ? w - 1 : mx); /* D5 clamp */
         my = my < 0 ? 0 : (my > h - 1 ? h - 1 : my);
         const float gx = born_gx[my * w + mx], gy = born_gy[my * w + mx];
+        if (g_cen) {
+            if (is_invalid(gx) || is_invalid(gy)) cen_add(ORC_CEN_GRAD_INVALID);
+            else g_cen_gate = 1;
+        }
         if (is_invalid(gx) || is_invalid(gy)) { *new_sigma = -1.0f; return; }
         const float gl = (g_lit & ORC_LIT_ARITH) ? fabsf(gx * lx + gy * ly) : fabsf(fmaf(gy, ly, gx * lx));
         const float gl2 = gl * gl;
@@ -1200,7 +1267,8 @@ static void frame_top_gradients(const orc_frame* f, float** gx, float** gy)
     orc_gradiate(f->gray[L - 1], w, h, 0, *gy);
 }
 
-int orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed)
+/* px_steps / px_flags: the census's per-pixel record (NULL outside orc_mapper_update_census) */
+static int mapper_update_impl(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed, int* px_steps, unsigned* px_flags)
 { /* mapper.cpp:76-137 */
     orc_frame* ref = history[n_hist - 1];
     const int L = ref->levels, w = ref->w[L - 1], h = ref->h[L - 1];
@@ -1220,6 +1288,16 @@ int orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uin
             float p[2];
             orc_warp(Rt, (float)x, (float)y, d, K, p); /* mapper.cpp:94 */
             int qx, qy;
+            if (g_cen) { /* the pixels that leave before Implement::update, in the order of the tests below */
+                g_cen_px = 0; g_cen_px_steps = 0; g_cen_gate = 0;
+                int ax = 0, ay = 0;
+                if (!round_coord(p[0], &ax) || !round_coord(p[1], &ay)) cen_add(ORC_CEN_WARP_FAILS);
+                else if (!in_range(ax, ay, w, h)) cen_add(ORC_CEN_OUT_OF_FRAME);
+                else if (n_hist - 1 - (int)ref->age[i] < 0) cen_add(ORC_CEN_AGE_BEYOND);
+                else if (n_hist - 1 - (int)ref->age[i] >= n_hist) cen_add(ORC_CEN_AGE_NEGATIVE);
+                else cen_add(ORC_CEN_SEARCHED);
+                if (px_flags) px_flags[i] = g_cen_px;
+            }
             if (!round_coord(p[0], &qx) || !round_coord(p[1], &qy)) continue;
             if (!in_range(qx, qy, w, h)) continue;
             const int age = (int)ref->age[i]; /* mapper.cpp:99 */
@@ -1235,12 +1313,23 @@ int orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uin
             float nd, ns;
             orc_implement_update(obj->gray[obj->levels - 1], born->gray[born->levels - 1], gxs[bi], gys[bi],
                                  w, h, r_xi, K, qx, qy, depth, sigma, &nd, &ns);
+            if (g_cen && g_cen_gate) {
+                if (nd != nd || ns != ns) cen_add(ORC_CEN_GATE_NAN);
+                if (nd >= 6.0f) cen_add(ORC_CEN_GATE_ND_GE6);
+            }
             if (nd > 0.2f && nd < 6.0f && ns > 0.0f && ns < 0.5f) { /* mapper.cpp:122 */
                 float gd = depth, gs = sigma;
                 const float reset = orc_rng_depth(rng_seed, (uint32_t)obj->id, (uint32_t)i);
-                if (!orc_gaussian_update(&gd, &gs, nd, ns, reset)) ref->age[i] = 0.0f; /* mapper.cpp:124-127 */
+                const int ok = orc_gaussian_update(&gd, &gs, nd, ns, reset);
+                if (g_cen) cen_add(ok ? ORC_CEN_ACCEPTED : ORC_CEN_REJECTED);
+                if (!ok) ref->age[i] = 0.0f; /* mapper.cpp:124-127 */
                 else valid_update++;
                 rd[i] = gd; rs[i] = gs; /* mapper.cpp:130-131 */
+            }
+            if (g_cen) {
+                if (g_cen_px_steps > g_cen[ORC_CEN_LONGEST]) g_cen[ORC_CEN_LONGEST] = g_cen_px_steps;
+                if (px_steps) px_steps[i] = g_cen_px_steps;
+                if (px_flags) px_flags[i] = g_cen_px;
             }
         }
     for (int k = 0; k < n_hist; k++) { free(gxs[k]); free(gys[k]); }
@@ -1254,6 +1343,27 @@ int orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uin
         free(d); free(s);
     }
     return valid_update;
+}
+
+int orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed)
+{
+    return mapper_update_impl(history, n_hist, obj, rng_seed, NULL, NULL);
+}
+
+int orc_mapper_update_census(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed, long long* counts, int* px_steps,
+                             unsigned* px_flags)
+{ /* sequential, like the mapper itself; never while other threads run oracle calls */
+    orc_frame* ref = history[n_hist - 1];
+    const int n = ref->w[ref->levels - 1] * ref->h[ref->levels - 1];
+    for (int k = 0; k < ORC_CEN_N; k++) counts[k] = 0;
+    for (int i = 0; i < n; i++) {
+        if (px_steps) px_steps[i] = -1;
+        if (px_flags) px_flags[i] = 0;
+    }
+    g_cen = counts;
+    const int v = mapper_update_impl(history, n_hist, obj, rng_seed, px_steps, px_flags);
+    g_cen = NULL;
+    return v;
 }
 
 static void mapper_regularize(orc_frame* f)

@@ -198,6 +198,47 @@ int     orc_vo_last_valid_updates(const orc_vo* vo);
 int     orc_need_new_frame(const float rel_xi[6], int id, int ref_id);                  /* mapper.cpp:45-60 */
 /* Mapper::update (mapper.cpp:76-137): history = array of n_hist keyframes, oldest first; ref = history[n_hist-1] */
 int     orc_mapper_update(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed);
+/* Branch census of one orc_mapper_update call (test instrumentation: the call computes what orc_mapper_update computes, bit for
+ * bit, and counts on the side).  The product's k_depth_update replaces the literal loop test, the three samples per step and the
+ * range-checked sampler by shortcuts of its own; its coordinates are the oracle's bit for bit, so its predicates -- restated here
+ * literally from csrc/dvo_map_kernels.hip -- can be evaluated on the oracle's values: the census says which of the kernel's branches
+ * an input reaches.  counts[ORC_CEN_N]; px_steps / px_flags (optional, w*h of the top level): the search steps of every pixel
+ * (-1: the pixel never reached Implement::update) and the classes it was counted in, bit 1 << class (classes 0..31). */
+enum {
+    ORC_CEN_SEARCHED = 0,      /* pixels that reached Implement::update */
+    ORC_CEN_STEPS,             /* search steps (loop bodies) */
+    ORC_CEN_TEST_FLOAT,        /* loop tests decided by the float comparison */
+    ORC_CEN_TEST_DOUBLE,       /* float band entered, the double comparison decides */
+    ORC_CEN_TEST_SQRT,         /* double band entered, the literal sqrt decides */
+    ORC_CEN_FBAND_GO,          /* float band entered and go comes out true */
+    ORC_CEN_FBAND_STOP,        /* ... false */
+    ORC_CEN_DBAND_GO,          /* double band entered and go comes out true */
+    ORC_CEN_DBAND_STOP,        /* ... false */
+    ORC_CEN_LENGTH_NOT_POS,    /* pixels whose length is not > 0 (zero or NaN: the head returns 1) */
+    ORC_CEN_WARP_FAILS,        /* pixels whose warp into the frame fails round_coord */
+    ORC_CEN_AGE_BEYOND,        /* bi < 0: the age points beyond the history (the ring's clamp) */
+    ORC_CEN_AGE_NEGATIVE,      /* bi >= n_hist: negative age */
+    ORC_CEN_GATE_ND_GE6,       /* the gate of mapper.cpp:122 reached with nd >= 6 */
+    ORC_CEN_D5_CLAMP,          /* the D5 clamp of the best match changes a coordinate */
+    ORC_CEN_GATE_NAN,          /* NaN nd or ns reaching the gate */
+    ORC_CEN_CAP,               /* pixels that leave the loop through count++ > 100 */
+    ORC_CEN_NEED_N,            /* steps after a pixel's first whose pt - dir is not the previous centre (need_n) */
+    ORC_CEN_STEP_NOT_INNER,    /* steps outside the interior fast path's box */
+    ORC_CEN_SSD_REJECT,        /* min_ssd above the threshold */
+    ORC_CEN_BEST_OUTSIDE,      /* best match outside the image (implement.cpp:196-200) */
+    ORC_CEN_GRAD_INVALID,      /* INVALID gradient at the best match */
+    ORC_CEN_ACCEPTED,          /* gaussian update accepted */
+    ORC_CEN_REJECTED,          /* ... rejected: depth reset, age 0 */
+    ORC_CEN_HEAD_103,          /* pixels of the head's step-count bucket 103 (length >= 102) */
+    ORC_CEN_HEAD_SHORT,        /* pixels whose search takes more steps than the head's count (must stay 0: the LDS sort's bound) */
+    ORC_CEN_SHORTCUT_DIFFERS,  /* loop tests where the kernel's float / double / sqrt cascade and the literal test disagree (must stay 0) */
+    ORC_CEN_OUT_OF_FRAME,      /* pixels whose warp into the frame lands outside it */
+    ORC_CEN_LONGEST,           /* the longest search, in steps (a maximum, not a count) */
+    ORC_CEN_FIRST_ORIGIN,      /* pixels whose first step has pt - dir == (0, 0): need_n holds through its `first` term alone */
+    ORC_CEN_N
+};
+int     orc_mapper_update_census(orc_frame** history, int n_hist, const orc_frame* obj, uint32_t rng_seed,
+                                 long long* counts, int* px_steps, unsigned* px_flags);
 
 #ifdef __cplusplus
 }

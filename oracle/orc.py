@@ -387,6 +387,31 @@ def mapper_update(history, obj, seed):
     return lib().orc_mapper_update(arr, len(history), obj.ptr, C.c_uint32(seed))
 
 
+# classes of the branch census, in the order of the enum in dvo_oracle.h (ORC_CEN_*)
+CENSUS = ("searched", "steps", "test_float", "test_double", "test_sqrt", "fband_go", "fband_stop", "dband_go", "dband_stop",
+          "length_not_pos", "warp_fails", "age_beyond", "age_negative", "gate_nd_ge6", "d5_clamp", "gate_nan", "cap", "need_n",
+          "step_not_inner", "ssd_reject", "best_outside", "grad_invalid", "accepted", "rejected", "head_103", "head_short",
+          "shortcut_differs", "out_of_frame", "longest", "first_origin")
+
+
+def mapper_update_census(history, obj, seed):
+    """mapper_update with the branch census of dvo_oracle.h: the same in-place update and return value, plus counts {class: n},
+    steps (h x w int32: search steps per pixel, -1 where Implement::update was not reached) and flags (h x w uint32: bit
+    CENSUS.index(class) set where the pixel was counted in the class)."""
+    arr = (C.POINTER(Frame) * len(history))(*[f.ptr for f in history])
+    w, h = history[-1].size(history[-1].levels - 1)
+    counts = np.zeros(len(CENSUS), np.int64)
+    steps = np.zeros((h, w), np.int32); flags = np.zeros((h, w), np.uint32)
+    v = lib().orc_mapper_update_census(arr, len(history), obj.ptr, C.c_uint32(seed), counts.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                       steps.ctypes.data_as(C.POINTER(C.c_int)), flags.ctypes.data_as(C.POINTER(C.c_uint)))
+    return v, dict(zip(CENSUS, (int(c) for c in counts))), steps, flags
+
+
+def census_mask(flags, name):
+    """the pixels a census counted in class `name`"""
+    return (flags >> np.uint32(CENSUS.index(name))) & np.uint32(1) != 0
+
+
 def need_new_frame(rel_xi, id, ref_id):
     r = f32(rel_xi)
     return bool(lib().orc_need_new_frame(fp(r), id, ref_id))
