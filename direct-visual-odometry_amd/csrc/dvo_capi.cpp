@@ -505,28 +505,73 @@ static int track_quality(dvo_batch* b, dvo_track_quality* out, bool to_host)
 int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out) { return track_quality(b, out, true); }
 int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst) { return track_quality(b, dst, false); }
 
-int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
+// The checks of a robust configuration (dvo_batch_set_robust_weights, and with `median` dvo_batch_set_robust_median, whose only scale
+// mode is DVO_ROBUST_SCALE_MEDIAN and which has no kind NONE)
+static bool robust_config_ok(const dvo_robust_config* cfg, const char* who, bool median)
+{
+    const auto positive = [](float v) { return v > 0.0f && v < __builtin_inff(); };
+    if (cfg->struct_size != (int)sizeof(dvo_robust_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_robust_config)"); return false; }
+    if (median && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
+        set_error(std::string(who) + ": the kind is DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return false;
+    }
+    if (cfg->kind != DVO_ROBUST_NONE && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
+        set_error(std::string(who) + ": the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return false;
+    }
+    if (cfg->kind != DVO_ROBUST_NONE) {
+        if (median && cfg->scale_mode != DVO_ROBUST_SCALE_MEDIAN) {
+            set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_MEDIAN");
+            return false;
+        }
+        if (!median && cfg->scale_mode != DVO_ROBUST_SCALE_ADAPTIVE && cfg->scale_mode != DVO_ROBUST_SCALE_GIVEN) {
+            set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_ADAPTIVE or DVO_ROBUST_SCALE_GIVEN");
+            return false;
+        }
+        if (!positive(cfg->param)) { set_error(std::string(who) + ": param (Huber k, Student-t nu) must be finite and > 0"); return false; }
+        if (!positive(cfg->scale_floor)) {   // (whatever the mode: a configuration is valid or not as a whole)
+            set_error(std::string(who) + ": scale_floor must be finite and > 0");
+            return false;
+        }
+    }
+    return true;
+}
+
+int dvo_batch_set_robust_median(dvo_batch* b, const dvo_robust_config* cfg)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (cfg) {
-        const auto positive = [](float v) { return v > 0.0f && v < __builtin_inff(); };
-        if (cfg->struct_size != (int)sizeof(dvo_robust_config)) { set_error("dvo_batch_set_robust_weights: struct_size is not sizeof(dvo_robust_config)"); return DVO_ERR_BAD_ARGUMENT; }
-        if (cfg->kind != DVO_ROBUST_NONE && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
-            set_error("dvo_batch_set_robust_weights: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        if (!robust_config_ok(cfg, "dvo_batch_set_robust_median", true)) return DVO_ERR_BAD_ARGUMENT;
+        if (b->trk().aff.on || b->trk().geo.on) {
+            set_error("dvo_batch_set_robust_median: affine brightness compensation or the geometric term is on: the median scale does not combine with them");
             return DVO_ERR_BAD_ARGUMENT;
         }
-        if (cfg->kind != DVO_ROBUST_NONE) {
-            if (cfg->scale_mode != DVO_ROBUST_SCALE_ADAPTIVE && cfg->scale_mode != DVO_ROBUST_SCALE_GIVEN) {
-                set_error("dvo_batch_set_robust_weights: the scale mode is DVO_ROBUST_SCALE_ADAPTIVE or DVO_ROBUST_SCALE_GIVEN");
-                return DVO_ERR_BAD_ARGUMENT;
-            }
-            if (!positive(cfg->param)) { set_error("dvo_batch_set_robust_weights: param (Huber k, Student-t nu) must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
-            if (!positive(cfg->scale_floor)) {   // (whatever the mode: a configuration is valid or not as a whole)
-                set_error("dvo_batch_set_robust_weights: scale_floor must be finite and > 0");
-                return DVO_ERR_BAD_ARGUMENT;
-            }
-        }
     }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_robust(cfg, b->stream());
+}
+
+int dvo_batch_last_robust_log(dvo_batch* b, int seq, dvo_robust_log* log)
+{
+    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (log->struct_size != (int)sizeof(dvo_robust_log)) { set_error("dvo_batch_last_robust_log: struct_size is not sizeof(dvo_robust_log)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->trk().rob.median_ready) { set_error("dvo_batch_last_robust_log: the last push / call did not run with the median robust scale (dvo_batch_set_robust_median)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_robust_log(seq, log, b->stream());
+}
+
+int dvo_batch_last_robust_histogram(dvo_batch* b, int seq, uint32_t counts[256])
+{
+    if (!b || !counts || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->trk().rob.median_ready) { set_error("dvo_batch_last_robust_histogram: the last push / call did not run with the median robust scale (dvo_batch_set_robust_median)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_robust_histogram(seq, counts, b->stream());
+}
+
+int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && !robust_config_ok(cfg, "dvo_batch_set_robust_weights", false)) return DVO_ERR_BAD_ARGUMENT;
     if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().geo.on) {
         set_error("dvo_batch_set_robust_weights: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
         return DVO_ERR_BAD_ARGUMENT;
@@ -576,6 +621,10 @@ int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg)
     if (cfg && !affine_config_ok(cfg, "dvo_batch_set_affine_brightness")) return DVO_ERR_BAD_ARGUMENT;
     if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().geo.on) {
         set_error("dvo_batch_set_affine_brightness: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().rob.median()) {
+        set_error("dvo_batch_set_affine_brightness: the median robust scale is on (dvo_batch_set_robust_median): the two do not combine");
         return DVO_ERR_BAD_ARGUMENT;
     }
     DVO_TRY(select_device(b->device()));
@@ -1045,7 +1094,7 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
                    dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2,
                    const dvo_affine_config* aff = nullptr, float aff_a = 1.0f, float aff_b = 0.0f, double* moments = nullptr,
                    float* next_ab = nullptr, const dvo_geometric_config* geo = nullptr, const float* geo_ref_depth = nullptr,
-                   double* geo_sums = nullptr)
+                   double* geo_sums = nullptr, uint32_t* med_counts = nullptr, int* med_bin = nullptr, float* med_next_s2 = nullptr)
 {
     if (!obj_gray || !ref_gray || !ref_depth || !ref_sigma || !K || !xi || !out || w < 1 || h < 1 || level < 0 || level >= DVO_MAX_LEVELS)
         return DVO_ERR_BAD_ARGUMENT;
@@ -1102,12 +1151,24 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
         launch_robust_begin(ra, c.s);
     }
+    DevBuf mn;
+    if (trk.rob.median()) {
+        DVO_TRY(mn.alloc(sizeof(int) * 2));
+        trk.median_begin(c.s);
+    }
     if (trk.aff.on) trk.affine_begin(c.s, true, aff_a, aff_b);
     trk.launch_gn_term(ga, level, 1, c.s, 0, zr.as<float>());
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true, mom.as<double>());
+    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true, mom.as<double>(), mn.as<int>());
+    int med_mn[2] = {0, 0};
+    RobustEntry med_next{};
+    if (trk.rob.median()) {
+        DVO_HIP(hipMemcpyAsync(med_counts, trk.rob.hist_last.p, sizeof(uint32_t) * DVO_MEDIAN_BINS, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(med_mn, mn.p, sizeof med_mn, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(&med_next, trk.rob.table.p, sizeof med_next, hipMemcpyDeviceToHost, c.s));
+    }
     if (trk.aff.on) {
         DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
@@ -1117,6 +1178,7 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
     DVO_HIP(hipGetLastError());
+    if (trk.rob.median()) { *med_bin = med_mn[0]; *med_next_s2 = med_next.s2; }
     return DVO_OK;
 }
 
@@ -1176,6 +1238,30 @@ int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray,
     rc.scale_mode = DVO_ROBUST_SCALE_GIVEN;
     rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
     return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2);
+}
+
+int dvo_op_gn_step_robust_median(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                                 const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
+                                 int kind, float param, float s2, dvo_gn_result* out, uint32_t counts[256], int* median_bin, float* next_s2)
+{
+    if (!counts || !median_bin || !next_s2) return DVO_ERR_BAD_ARGUMENT;
+    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
+        set_error("dvo_op_gn_step_robust_median: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
+        set_error("dvo_op_gn_step_robust_median: param (Huber k, Student-t nu) must be finite and > 0");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    dvo_robust_config rc{};
+    rc.struct_size = (int)sizeof rc;
+    // (kind NONE still runs the pair, with the plain entry: rho = 1; the entry the solve writes is then Huber's with k = 1)
+    rc.kind = kind == DVO_ROBUST_NONE ? DVO_ROBUST_HUBER : kind;
+    rc.scale_mode = DVO_ROBUST_SCALE_MEDIAN;
+    rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
+    rc.scale_floor = 0.0f;   // (not validated here: floor2 = 0, the bin's own s2)
+    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2,
+                   nullptr, 1.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, counts, median_bin, next_s2);
 }
 
 int dvo_op_gn_step_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

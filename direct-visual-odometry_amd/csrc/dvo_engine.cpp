@@ -612,11 +612,22 @@ int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
         DVO_TRY(rob.stage.alloc(sizeof(float) * (size_t)n_seq));
         DVO_HIP(hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s));
     }
+    if (enable && c->scale_mode == DVO_ROBUST_SCALE_MEDIAN && !rob.hist.p) {
+        rob.log_its = log_iterations();
+        DVO_TRY(rob.hist.alloc(sizeof(uint32_t) * DVO_MEDIAN_BINS * (size_t)n_seq));
+        DVO_TRY(rob.hist_last.alloc(sizeof(uint32_t) * DVO_MEDIAN_BINS * (size_t)n_seq));
+        DVO_TRY(rob.mlog.alloc(sizeof(int) * 3 * (size_t)rob.log_its * (size_t)g.levels * (size_t)n_seq));
+        DVO_TRY(rob.prime_mn.alloc(sizeof(int) * 2 * (size_t)n_seq));
+        DVO_HIP(hipMemsetAsync(rob.hist.p, 0, rob.hist.bytes, s));
+        DVO_HIP(hipMemsetAsync(rob.hist_last.p, 0, rob.hist_last.bytes, s));
+        DVO_HIP(hipMemsetAsync(rob.mlog.p, 0, rob.mlog.bytes, s));
+        DVO_HIP(hipMemsetAsync(rob.prime_mn.p, 0, rob.prime_mn.bytes, s));
+    }
     rob.on = enable;
     if (enable) {
         if (rob.mode != c->scale_mode || c->scale_mode != DVO_ROBUST_SCALE_GIVEN) rob.scales_src = nullptr;   // (rows belong to one GIVEN configuration)
         rob.kind = c->kind; rob.mode = c->scale_mode; rob.param = c->param;
-        rob.floor2 = c->scale_mode == DVO_ROBUST_SCALE_ADAPTIVE ? c->scale_floor * c->scale_floor : 0.0f;
+        rob.floor2 = c->scale_mode != DVO_ROBUST_SCALE_GIVEN ? c->scale_floor * c->scale_floor : 0.0f;
     } else {
         rob.scales_src = nullptr;
     }
@@ -646,8 +657,59 @@ int Tracker::last_robust_scales(float* s2, hipStream_t s) const
     return DVO_OK;
 }
 
+int Tracker::last_robust_log(int seq, dvo_robust_log* out, hipStream_t s) const
+{
+    std::vector<int> rows((size_t)3 * rob.log_its * g.levels);
+    std::vector<int> n_iter(DVO_MAX_LEVELS);
+    float last = 0.0f;
+    int prime[2] = {0, 0};
+    DVO_HIP(hipMemcpyAsync(rows.data(), rob.mlog.as<int>() + (size_t)seq * rows.size(), sizeof(int) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(&last, rob.last.as<float>() + (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(prime, rob.prime_mn.as<int>() + 2 * (size_t)seq, sizeof prime, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    const int size = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = size;
+    out->levels = g.levels;
+    if (last == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
+    out->prime_bin = prime[0]; out->prime_count = prime[1];
+    for (int l = 0; l < g.levels; l++) {
+        const int n = n_iter[l] < rob.log_its ? n_iter[l] : rob.log_its;
+        out->n_iter[l] = n;
+        for (int it = 0; it < n; it++) {
+            const int* r = &rows[((size_t)l * rob.log_its + it) * 3];
+            memcpy(&out->s2[l][it], &r[0], sizeof(float));
+            out->median_bin[l][it] = r[1];
+            out->count[l][it] = r[2];
+        }
+    }
+    return DVO_OK;
+}
+
+int Tracker::last_robust_histogram(int seq, uint32_t* counts, hipStream_t s) const
+{
+    DVO_HIP(hipMemcpyAsync(counts, rob.hist_last.as<uint32_t>() + (size_t)seq * DVO_MEDIAN_BINS, sizeof(uint32_t) * DVO_MEDIAN_BINS,
+                           hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+void Tracker::median_begin(hipStream_t s)
+{
+    MedianBeginArgs ma{};
+    ma.hist = rob.hist.as<unsigned>(); ma.hist_last = rob.hist_last.as<unsigned>(); ma.prime_mn = rob.prime_mn.as<int>();
+    ma.n_seq = n_seq;
+    launch_median_begin(ma, s);
+}
+
 void Tracker::robust_end_push(hipStream_t s)
 {
+    if (rob.median() && !rob.tracked) {   // nothing tracked at this push: no histogram and no priming record either
+        (void)hipMemsetAsync(rob.hist_last.p, 0, rob.hist_last.bytes, s);
+        (void)hipMemsetAsync(rob.prime_mn.p, 0, rob.prime_mn.bytes, s);
+    }
+    rob.median_ready = rob.median();
     rob.end_push(s);
     aff.end_push(s);
     geo.end_push(s);
@@ -855,6 +917,19 @@ RobustSolve Tracker::robust_solve_args(size_t q0, bool adaptive) const
     return r;
 }
 
+MedianSolve Tracker::median_solve_args(size_t q0, bool log, bool prime, int* step_mn) const
+{
+    MedianSolve m{};
+    m.hist = rob.hist.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
+    m.hist_last = rob.hist_last.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
+    m.log = (log && !prime) ? rob.mlog.as<int>() + 3 * q0 * (size_t)rob.log_its * g.levels : nullptr;
+    m.prime_mn = rob.prime_mn.as<int>() + 2 * q0;
+    m.step_mn = step_mn;
+    m.levels = g.levels; m.log_its = rob.log_its;
+    m.prime = prime ? 1 : 0;
+    return m;
+}
+
 void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, const float* ref_z, bool prime) const
 {
     const LevelPlan& L = lv[level];
@@ -865,12 +940,17 @@ void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t 
     if (geo.on && aff.on) launch_track_gn_zab(a, affine_gn_args(q0, prime), geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
     else if (geo.on) launch_track_gn_z(a, geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
     else if (aff.on) launch_track_gn_ab(a, r, affine_gn_args(q0, prime), count, L.ppt, L.group, t2d, s, grid_seqs);
+    else if (rob.median()) {
+        MedianGn m{};
+        m.hist = rob.hist.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
+        launch_track_gn_md(a, r, m, count, L.ppt, L.group, t2d, s, grid_seqs);
+    }
     else if (rob.on) launch_track_gn_rw(a, r, count, L.ppt, L.group, t2d, s, grid_seqs);
     else launch_gn(a, level, count, s, grid_seqs);
 }
 
 void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* term_out,
-                                bool estimate_once, double* moments_out) const
+                                bool estimate_once, double* moments_out, int* step_mn) const
 {
     const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
     const RobustSolve r = rob.on ? robust_solve_args(q0, adaptive_scale) : RobustSolve{};
@@ -879,6 +959,7 @@ void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, b
                             count, s);
     else if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, sa.log != nullptr, term_out), count, s);
     else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, sa.log != nullptr, prime, term_out, estimate_once), count, s);
+    else if (rob.median()) launch_gn_solve_md(sa, r, median_solve_args(q0, sa.log != nullptr, prime, step_mn), count, s);
     else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
     else launch_gn_solve(sa, count, s);
 }
@@ -991,6 +1072,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         ra.s2_all = 0.0f;
         ra.n_seq = n_seq; ra.kind = rob.kind; ra.param = rob.param;
         launch_robust_begin(ra, s);
+        if (rob.median()) median_begin(s);
         rob.tracked = true;
     }
     if (aff.on) affine_begin(s);   // the brightness table of this call (before the fork, like the weight table)
@@ -1082,9 +1164,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
                 ga.list = list_prev;
                 ga.next_count = lists ? work_list(k, it) : nullptr;
-                if (aff.on && aff.mode == DVO_AFFINE_ESTIMATE && level == 0 && first) {
-                    // the priming pair: the moments of the start pose on the coarsest level give the first iteration's entry; it
-                    // leaves the pose, the log, the lists and the quality record alone
+                if (((aff.on && aff.mode == DVO_AFFINE_ESTIMATE) || rob.median()) && level == 0 && first) {
+                    // the priming pair: the moments (the median scale: the bin counts) of the start pose on the coarsest level give
+                    // the first iteration's entry; it leaves the pose, the log, the lists and the quality record alone
                     GnArgs gp = ga;
                     gp.next_count = nullptr;
                     launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true);

@@ -250,6 +250,13 @@ struct RobustWeights : OptInTerm {
     DevBuf table, scales;                // [n_seq] RobustEntry; [n_seq] float s (host rows).  last: [n_seq] float s2 of the last iteration
     PinnedPair stage;                    // pinned staging of host rows
     const float* scales_src = nullptr;   // GIVEN: the rows every later push reads (device memory); nullptr: none (plain)
+    // The median scale (mode DVO_ROBUST_SCALE_MEDIAN: dvo_batch_set_robust_median), allocated by its first enable:
+    // the pairs are k_track_gn_md + k_gn_solve_md, and the first iteration of the coarsest level follows a priming pair.
+    DevBuf hist, hist_last;              // [n_seq][256] counts of the launch in flight; of each sequence's last evaluated iteration
+    DevBuf mlog, prime_mn;               // [n_seq][levels][log_its][3] (s2 bits, m, n); [n_seq][2] the priming pair's (m, n)
+    int log_its = 0;                     // iterations per level of the robust log
+    bool median_ready = false;           // the last push / call ran with the median scale (its log and histogram can be read)
+    bool median() const { return on && mode == DVO_ROBUST_SCALE_MEDIAN; }
     void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
 };
 
@@ -329,7 +336,8 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // are on too), else robust weights, else the plain kernels: the one place that decides.  `ga` / `sa` view `count`
     // sequences (their SeqState offset is every table's).
     //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
-    //   prime: the priming pair of affine ESTIMATE mode
+    //   prime: the priming pair of affine ESTIMATE mode or of the median robust scale
+    //   step_mn: the median scale's one-evaluation output (device, 2 ints (m, n); dvo_op_gn_step_robust_median)
     //   adaptive_scale: the solve writes the next RobustEntry from this iteration's residual
     //   term_out: the one-evaluation ops' device output (geometric: 2 doubles (n_geo, S29); affine: DVO_AFFINE_MOMENTS doubles)
     //   estimate_once: the affine solve writes the next entry whatever the mode (dvo_op_gn_step_affine)
@@ -337,7 +345,7 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     void launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
                         bool prime = false) const;
     void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* term_out = nullptr,
-                           bool estimate_once = false, double* moments_out = nullptr) const;
+                           bool estimate_once = false, double* moments_out = nullptr, int* step_mn = nullptr) const;
     GeometricTerm geo;
     int set_geometric(const dvo_geometric_config* c, hipStream_t s);    // validated by the caller; nullptr / OFF: off
     int set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s);   // both on (validated by the caller)
@@ -353,6 +361,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int set_robust(const dvo_robust_config* c, hipStream_t s);          // validated by the caller; nullptr / NONE: off
     int set_robust_scales(const float* s_rows, bool on_device, hipStream_t s);
     int last_robust_scales(float* s2, hipStream_t s) const;
+    int last_robust_log(int seq, dvo_robust_log* out, hipStream_t s) const;          // the median scale
+    int last_robust_histogram(int seq, uint32_t* counts, hipStream_t s) const;
+    void median_begin(hipStream_t s);       // k_median_begin of a call
     void robust_end_push(hipStream_t s);    // after every push / call of the owner, whether it tracked or not (every opt-in term)
     DevBuf ticket, freport;      // k_track_gn_fused: arrival tickets [n_seq]; (reported, active) per (set, level, iteration)
     // Adaptive schedule: progress words in mapped host memory, one per (level, iteration), two sets used alternately.
@@ -425,6 +436,7 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
 private:
     // the argument blocks of the opt-in terms' kernels for the sequences from q0 on (launch_gn_term, launch_solve_term)
     RobustSolve robust_solve_args(size_t q0, bool adaptive) const;
+    MedianSolve median_solve_args(size_t q0, bool log, bool prime, int* step_mn) const;
     GeoGn geo_gn_args(size_t q0, int level, const float* ref_z) const;
     GeoSolve geo_solve_args(size_t q0, bool log, double* sums_out) const;
     AffineGn affine_gn_args(size_t q0, bool prime) const;

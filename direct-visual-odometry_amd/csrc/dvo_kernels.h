@@ -197,6 +197,51 @@ void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s);
 void launch_track_gn_rw(const struct GnArgs& a, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
 void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s);
 
+// The median (MAD) robust scale (dvo_batch_set_robust_median; the contract is in include/dvo.h).  Every contributing
+// pixel's |r| is binned, 16 bins per octave over [2^-16, 1), and the solve selects the median bin of the sequence's 256 exact counts:
+// the next launch's RobustEntry comes from the bin's midpoint.  Integer and float32 only, so the host replica has the same bits.
+#define DVO_MEDIAN_BINS 256
+#define DVO_MEDIAN_K0 1776   /* (127 - 16) << 4: the exponent-and-4-mantissa-bits word of 2^-16 */
+DVO_HD int median_bin(float r)
+{
+    unsigned u;
+    const float ar = fabsf(r);
+    __builtin_memcpy(&u, &ar, sizeof u);
+    const int k = (int)(u >> 19) - DVO_MEDIAN_K0;
+    return k < 0 ? 0 : (k > DVO_MEDIAN_BINS - 1 ? DVO_MEDIAN_BINS - 1 : k);
+}
+// s2 of median bin m: med = the bin's midpoint, s = 1.4826f * med, s2 = max(s * s, floor2) (no contraction: two roundings)
+DVO_HD float median_s2(int m, float floor2)
+{
+    const unsigned u = ((unsigned)(m + DVO_MEDIAN_K0) << 19) | (1u << 18);
+    float med;
+    __builtin_memcpy(&med, &u, sizeof med);
+    const float s = 1.4826f * med;
+    const float s2 = s * s;
+    return s2 > floor2 ? s2 : floor2;
+}
+struct MedianGn {      // last argument of k_track_gn_md / k_track_gn_md_cam
+    unsigned* hist;             // [n_seq of the launch][256] counts, indexed like GnArgs::state; zero before the launch
+};
+struct MedianSolve {   // last argument of k_gn_solve_md
+    unsigned* hist;             // [n_seq][256], indexed like SolveArgs::state: read, then zeroed for the next tile launch
+    unsigned* hist_last;        // [n_seq][256]: the counts of each sequence's last evaluated iteration (not written by the priming pair)
+    int* log;                   // optional [n_seq][levels][log_its][3]: (bits of the s2 used, m, n) of every logged iteration
+    int* prime_mn;              // [n_seq][2]: (m, n) of the priming pair
+    int* step_mn;               // optional [n_seq][2] (dvo_op_gn_step_robust_median): (m, n) of this solve
+    int levels, log_its;
+    int prime;                  // the priming pair: the entry and prime_mn only -- no pose, log, iteration count, list or record
+};
+struct MedianBeginArgs {   // k_median_begin: zero rows and priming slots at the start of a tracking call
+    unsigned* hist; unsigned* hist_last; int* prime_mn;
+    int n_seq;
+};
+void launch_median_begin(const MedianBeginArgs& a, hipStream_t s);
+// the twins of launch_track_gn_rw / launch_gn_solve_rw that also bin |r| and select the median (launch pairs only, no mask)
+void launch_track_gn_md(const struct GnArgs& a, const RobustGn& r, const MedianGn& m, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                        int grid_seqs = 0);
+void launch_gn_solve_md(const SolveArgs& a, const RobustSolve& r, const MedianSolve& m, int n_seq, hipStream_t s);
+
 // Affine brightness compensation (dvo_batch_set_affine_brightness): I2(warp(x)) ~ a * I1(x) + b per sequence.  One
 // entry per sequence: the (a, b) the sequence's next k_track_gn_ab launch applies; (1, 0) is the plain residual bit for bit.
 struct AffineEntry {

@@ -955,11 +955,13 @@ struct GnTileLds {
 // GEO: a.ref_depth / a.ref_wgt are the tracked frame's own maps, and a contributing pixel of the fast path whose 12 reference-depth
 // taps (geo.ref_z, the gray taps' byte offsets) pass the gates adds a geometric row to slots 0..26 and to slots 29 / 30 of the partial
 // row, reduced through mred (k_track_gn_z; unused otherwise, and GEO = false is the code it always was).
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false, bool AB = false, bool GEO = false>
+// MED: every contributing pixel's |r| is counted in its bin of `hist`, the workgroup's 256 LDS counters (k_track_gn_md, DESIGN.md §30;
+// with ROB only; unused otherwise, and MED = false is the code it always was).  The caller clears and flushes `hist`.
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM = false, bool ROB = false, bool AB = false, bool GEO = false, bool MED = false>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
                                         float* out_row, const Intr& cam, const RobustEntry& rob = RobustEntry{},
                                         const AffineEntry& ab = AffineEntry{}, float* mom_row = nullptr, float (*mred)[8] = nullptr,
-                                        const GeoGn& geo = GeoGn{});
+                                        const GeoGn& geo = GeoGn{}, unsigned* hist = nullptr);
 
 #if !defined(DVO_GN_WAVES)
 #define DVO_GN_WAVES 6   /* waves per SIMD the hot variants are compiled for: 6 = up to 84 VGPRs (78 used, no scratch); at 7 (72 VGPRs) the border sampler spills 24 bytes per lane: 54 MB of extra HBM writes per full-batch launch for the same speed (profiles/r03_patch_sampler_ab.txt) */
@@ -1025,9 +1027,12 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_WAVES : 1) 
 // k_track_gn / k_track_gn_cam do (those two stay written out: sharing a body rescheduled them), plus the per-sequence entries of the
 // terms that are on, loaded once per workgroup (scalar loads) next to the pose: pose, AffineEntry (AB), RobustEntry (ROB), camera.
 // rg / ag / zg and mred are read only under their flag; a kernel passes an empty block (and nullptr) for a term it does not have.
-template <int PPT, int G, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
+// MED (k_track_gn_md): `hist`, the workgroup's 256 bin counters in LDS, is cleared ahead of the tile, and after it (gn_tile's last
+// barrier orders every count) thread t adds a non-zero hist[t] to bin t of the sequence's row of mg.hist.
+template <int PPT, int G, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO, bool MED = false>
 __device__ __forceinline__ void track_gn_term_body(const GnArgs& a, const RobustGn& rg, const AffineGn& ag, const GeoGn& zg,
-                                                   GnTileLds<PPT>& lds, float (*mred)[8])
+                                                   GnTileLds<PPT>& lds, float (*mred)[8], const MedianGn& mg = MedianGn{},
+                                                   unsigned* hist = nullptr)
 {
     auto clear_next = [&]() {
         if (__builtin_amdgcn_readfirstlane((int)blockIdx.x) == 0 && a.next_count) {
@@ -1058,6 +1063,14 @@ __device__ __forceinline__ void track_gn_term_body(const GnArgs& a, const Robust
     const size_t row = (size_t)seq * a.nblk + blk;
     float* mom_row = nullptr;
     if constexpr (AB) mom_row = ag.moments + row * 8;
+    if constexpr (MED) {
+        hist[threadIdx.x] = 0u;
+        __syncthreads();
+        gn_tile<PPT, G, false, T2D, PCAM, ROB, AB, GEO, true>(a, pose, seq, blk, lds, a.partials + row * 32, cam, rob, ab, mom_row, mred, zg, hist);
+        const unsigned n = hist[threadIdx.x];
+        if (n != 0u)
+            __hip_atomic_fetch_add(mg.hist + (size_t)seq * DVO_MEDIAN_BINS + threadIdx.x, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else
     gn_tile<PPT, G, false, T2D, PCAM, ROB, AB, GEO>(a, pose, seq, blk, lds, a.partials + row * 32, cam, rob, ab, mom_row, mred, zg);
     clear_next();
 }
@@ -1079,6 +1092,29 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_RW_WAVES : 
 {
     __shared__ GnTileLds<PPT> lds;
     track_gn_term_body<PPT, G, T2D, true, true, false, false>(a, rg, AffineGn{}, GeoGn{}, lds, nullptr);
+}
+
+// k_track_gn_md / k_track_gn_md_cam: k_track_gn_rw / k_track_gn_rw_cam for the median scale (dvo_batch_set_robust_median, DESIGN.md
+// §30): the same weighted sums bit for bit, and every contributing pixel's |r| counted in the sequence's 256 bins.  Kernels of their
+// own beside the others, which stay as they are.  The LDS add's address and the contributing flag take the hot instances from
+// k_track_gn_rw's 78 VGPRs to 81-82, past the 80 that six waves allow (8 to 12 bytes of scratch per lane there): the family is built
+// for five waves per SIMD (up to 96 VGPRs), scratch 0.
+#if !defined(DVO_GN_MD_WAVES)
+#define DVO_GN_MD_WAVES 5
+#endif
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_MD_WAVES : 1) k_track_gn_md(GnArgs a, RobustGn rg, MedianGn mg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ unsigned hist[DVO_MEDIAN_BINS];
+    track_gn_term_body<PPT, G, T2D, false, true, false, false, true>(a, rg, AffineGn{}, GeoGn{}, lds, nullptr, mg, hist);
+}
+template <int PPT, int G, bool T2D = false>
+__global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_MD_WAVES : 1) k_track_gn_md_cam(GnArgs a, RobustGn rg, MedianGn mg)
+{
+    __shared__ GnTileLds<PPT> lds;
+    __shared__ unsigned hist[DVO_MEDIAN_BINS];
+    track_gn_term_body<PPT, G, T2D, true, true, false, false, true>(a, rg, AffineGn{}, GeoGn{}, lds, nullptr, mg, hist);
 }
 
 // k_track_gn_ab / k_track_gn_ab_cam: k_track_gn / k_track_gn_cam (ROB: k_track_gn_rw / k_track_gn_rw_cam) with affine brightness
@@ -1224,11 +1260,38 @@ __global__ void __launch_bounds__(256, (PPT <= 4 && G <= 2) ? DVO_GN_ZAB_WAVES :
     track_gn_term_body<PPT, G, T2D, true, false, true, true>(a, RobustGn{}, ag, zg, lds, mred);
 }
 
-template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO>
+// One contributing pixel into the workgroup's bin counters (k_track_gn_md): one LDS integer add without a return value per
+// contributing lane.  A tile's residuals crowd into a few bins, so lanes of a wave meet at one LDS address; the hardware's
+// serialisation of those costs +15 % per finest-level launch against k_track_gn_rw.  DVO_MD_AGGREGATE = 1 is the form that was
+// measured against it: per wave one add of the population count per distinct bin among its contributing lanes (rounds of ballot +
+// readlane, all scalar).  It keeps 78 VGPRs and six waves, but its rounds cost 3.8 times k_track_gn_rw's launch.
+// Integer sums: any order.
+#if !defined(DVO_MD_AGGREGATE)
+#define DVO_MD_AGGREGATE 0
+#endif
+__device__ __forceinline__ void median_count(unsigned* hist, const bool ok, const float r)
+{
+    const int bin = median_bin(r);
+#if DVO_MD_AGGREGATE
+    unsigned long long todo = __ballot(ok);
+    while (todo != 0ull) {   // wave-uniform: one round per distinct bin among the contributing lanes
+        const int leader = __builtin_ctzll(todo);
+        const int b = __builtin_amdgcn_readlane(bin, leader);
+        const unsigned long long same = __ballot(ok && bin == b);
+        if ((int)(threadIdx.x & 63) == leader) __hip_atomic_fetch_add(&hist[b], (unsigned)__popcll(same), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        todo &= ~same;
+    }
+#else
+    if (ok) __hip_atomic_fetch_add(&hist[bin], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
+}
+
+template <int PPT, int G, bool MASK, bool T2D, bool PCAM, bool ROB, bool AB, bool GEO, bool MED>
 __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const int seq, const int blk, GnTileLds<PPT>& lds,
                                         float* out_row, const Intr& cam, const RobustEntry& rob, const AffineEntry& ab, float* mom_row,
-                                        float (*mred)[8], const GeoGn& geo)
+                                        float (*mred)[8], const GeoGn& geo, unsigned* hist)
 {
+    static_assert(!MED || (ROB && !AB && !GEO), "the median scale bins the residual of the robust weights alone");
     float (&red)[4][32] = lds.red;
     int (&slow_q)[4][PPT * 64] = lds.slow_q;
     int (&slow_cnt)[4] = lds.slow_cnt;
@@ -1385,6 +1448,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             if constexpr (ROB) {   // (a rejected pixel's rho is never used: its row is zeros, and 1 keeps a non-finite quotient out of the sums)
                 const float rs = ok ? r : 0.0f;
                 acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
+                if constexpr (MED) median_count(hist, ok, rs);
             } else
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
             if constexpr (GEO)   // after the pixel's photometric add (ok implies the fast path: interior footprint, 12 valid gray taps)
@@ -1428,6 +1492,7 @@ __device__ __forceinline__ void gn_tile(const GnArgs& a, const Pose& pose, const
             if constexpr (ROB) {   // the same operations as in the main loop
                 const float rs = ok ? r : 0.0f;
                 acc.add_w(J, rs, ok ? rw : 0.0f, ok ? 1.0f : 0.0f, ok ? robust_rho(rob, rs) : 1.0f);
+                if constexpr (MED) median_count(hist, ok, rs);
             } else
             acc.add(J, ok ? r : 0.0f, ok ? rw : 0.0f, ok ? 1.0f : 0.0f);
             if (MASK && ok) a.mask[img_off + i] = 1;
@@ -1847,6 +1912,89 @@ __global__ void __launch_bounds__(256) k_robust_begin(RobustBeginArgs a)
     }
     a.table[i] = robust_entry(a.kind, a.param, s2);
     a.last_s2[i] = 0.0f;
+}
+
+// k_gn_solve_md: k_gn_solve_rw for the median scale.  Ahead of solve_gather's barrier the 32 lanes that summed a
+// sequence's partial rows also read its 256 counts (8 consecutive bins per lane), keep them in hist_last (not the priming pair), zero
+// the row for the next tile launch (ordered behind this kernel on the stream), scan the counts and select the median bin: n = the
+// total, m = the smallest bin with cum(m) >= (n + 1) / 2.  The serial lane then runs solve_finish, records the s2 this iteration used
+// and writes the next entry from (m, n): robust_entry(kind, param, median_s2(m, floor2)), plain when n == 0.  ms.prime: the priming
+// pair -- the entry and prime_mn only.
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_md(SolveArgs a, RobustSolve rs, MedianSolve ms)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    __shared__ int sel[DVO_SOLVE_SEQ][2];
+    int my_seq = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    float used_s2 = 0.0f;
+    const auto select = [&](int t_slot, int c, int team) {
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        uint4* row = reinterpret_cast<uint4*>(ms.hist + (size_t)t_seq * DVO_MEDIAN_BINS) + 2 * c;
+        const uint4 v0 = row[0], v1 = row[1];
+        if (!ms.prime) {
+            uint4* keep = reinterpret_cast<uint4*>(ms.hist_last + (size_t)t_seq * DVO_MEDIAN_BINS) + 2 * c;
+            keep[0] = v0; keep[1] = v1;
+        }
+        row[0] = make_uint4(0u, 0u, 0u, 0u); row[1] = make_uint4(0u, 0u, 0u, 0u);
+        const unsigned v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
+        unsigned mine = 0u;
+#pragma unroll
+        for (int i = 0; i < 8; i++) mine += v[i];
+        unsigned incl = mine;   // inclusive scan over the team's 32 lanes
+#pragma unroll
+        for (int d = 1; d < 32; d <<= 1) {
+            const unsigned up = __shfl_up(incl, d, 32);
+            if (c >= d) incl += up;
+        }
+        const unsigned n = __shfl(incl, 31, 32);
+        const unsigned target = (n + 1u) >> 1;
+        int m = DVO_MEDIAN_BINS;
+        unsigned cum = incl - mine;
+        if (n != 0u && cum < target && target <= incl) {
+#pragma unroll
+            for (int i = 0; i < 8; i++) {   // the smallest bin of this lane whose cumulative count reaches the target
+                cum += v[i];
+                if (m == DVO_MEDIAN_BINS && cum >= target) m = 8 * c + i;
+            }
+        }
+#pragma unroll
+        for (int d = 16; d >= 1; d >>= 1) {
+            const int o = __shfl_xor(m, d, 32);
+            m = o < m ? o : m;
+        }
+        if (c == 0) { sel[team][0] = n != 0u ? m : -1; sel[team][1] = (int)n; }
+    };
+    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [&](int seq) { used_s2 = rs.table[seq].s2; }, select)) return;
+    const double* t = tot[threadIdx.x];
+    if (!ms.prime) {
+        Pose np;
+        (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
+        robust_solve_update(rs, my_seq, used_s2, t);   // (rs.adaptive = 0: last_s2 only)
+    }
+    const int m = sel[threadIdx.x][0], n = sel[threadIdx.x][1];
+    rs.table[my_seq] = n > 0 ? robust_entry(rs.kind, rs.param, median_s2(m, rs.floor2)) : robust_entry(DVO_ROBUST_NONE, rs.param, 0.0f);
+    if (ms.step_mn) { ms.step_mn[2 * my_seq] = m; ms.step_mn[2 * my_seq + 1] = n; }
+    if (ms.prime) {
+        ms.prime_mn[2 * my_seq] = m; ms.prime_mn[2 * my_seq + 1] = n;
+        return;
+    }
+    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    if (ms.log && it < ms.log_its) {
+        int* lg = ms.log + (((size_t)my_seq * ms.levels + a.level) * ms.log_its + it) * 3;
+        lg[0] = __float_as_int(used_s2); lg[1] = m; lg[2] = n;
+    }
+}
+
+// k_median_begin: the median scale's rows at the start of a tracking call, one workgroup per sequence: no counts, no kept histogram,
+// no priming record.  (Beside k_robust_begin, which stays as it is and starts every sequence plain.)
+__global__ void __launch_bounds__(DVO_MEDIAN_BINS) k_median_begin(MedianBeginArgs a)
+{
+    const size_t i = (size_t)blockIdx.x * DVO_MEDIAN_BINS + threadIdx.x;
+    a.hist[i] = 0u;
+    a.hist_last[i] = 0u;
+    if (threadIdx.x < 2) a.prime_mn[2 * (size_t)blockIdx.x + threadIdx.x] = 0;
 }
 
 // The closed-form least-squares (a, b) of one iteration's brightness moments, in double: `e` becomes the new entry
@@ -3211,6 +3359,22 @@ void launch_track_gn_rw(const GnArgs& a0, const RobustGn& r, int n_seq, int ppt,
     });
 }
 
+void launch_track_gn_md(const GnArgs& a0, const RobustGn& r, const MedianGn& m, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
+                        int grid_seqs)
+{
+    GnArgs a = a0;
+    a.n_seq = n_seq; a.mask = nullptr;
+    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
+    with_gn_shape(ppt, group, [&](auto p, auto g) {
+        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
+            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
+            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_md_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r, m);
+            else hipLaunchKernelGGL((k_track_gn_md<PPT, G, T2D>), grid, dim3(256), 0, s, a, r, m);
+        });
+    });
+}
+
 void launch_track_gn_ab(const GnArgs& a0, const RobustGn& r, const AffineGn& f, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
                         int grid_seqs)
 {
@@ -3280,6 +3444,16 @@ void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStre
 void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s)
 {
     launch_solve_kernel(k_gn_solve_zab, a, n_seq, s, f, z);
+}
+
+void launch_gn_solve_md(const SolveArgs& a, const RobustSolve& r, const MedianSolve& m, int n_seq, hipStream_t s)
+{
+    launch_solve_kernel(k_gn_solve_md, a, n_seq, s, r, m);
+}
+
+void launch_median_begin(const MedianBeginArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_median_begin, dim3((unsigned)a.n_seq), dim3(DVO_MEDIAN_BINS), 0, s, a);
 }
 
 void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)

@@ -103,6 +103,21 @@ AFFINE_LOG_DTYPE = np.dtype({"names": [f[0] for f in AffineLog._fields_],
                              "itemsize": C.sizeof(AffineLog)})
 
 
+class RobustLog(C.Structure):
+    """dvo_robust_log (include/dvo.h): the median scale's s2, median bin and count of every logged iteration, indexed like TrackLog."""
+    _fields_ = [("struct_size", C.c_int), ("levels", C.c_int), ("n_iter", C.c_int * MAX_LEVELS),
+                ("s2", (C.c_float * MAX_ITERATIONS) * MAX_LEVELS), ("median_bin", (C.c_int * MAX_ITERATIONS) * MAX_LEVELS),
+                ("count", (C.c_int * MAX_ITERATIONS) * MAX_LEVELS), ("prime_bin", C.c_int), ("prime_count", C.c_int)]
+
+
+ROBUST_LOG_DTYPE = np.dtype({"names": [f[0] for f in RobustLog._fields_],
+                             "formats": [np.int32, np.int32, (np.int32, MAX_LEVELS), (np.float32, (MAX_LEVELS, MAX_ITERATIONS)),
+                                         (np.int32, (MAX_LEVELS, MAX_ITERATIONS)), (np.int32, (MAX_LEVELS, MAX_ITERATIONS)),
+                                         np.int32, np.int32],
+                             "offsets": [getattr(RobustLog, f[0]).offset for f in RobustLog._fields_],
+                             "itemsize": C.sizeof(RobustLog)})
+
+
 class GeometricConfig(C.Structure):
     """dvo_geometric_config (include/dvo.h): the geometric (depth) term of a sensor-depth batch."""
     _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("weight", C.c_float), ("max_diff", C.c_float)]
@@ -180,6 +195,7 @@ EXPORTS = [
     "dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts",
     "dvo_op_pyramid_frames",
     "dvo_op_depth_update_batch",
+    "dvo_batch_set_robust_median", "dvo_batch_last_robust_log", "dvo_batch_last_robust_histogram", "dvo_op_gn_step_robust_median",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -193,6 +209,8 @@ QUALITY_CONVERGED, QUALITY_CAPPED, QUALITY_NO_VALID, QUALITY_NOT_FINITE, QUALITY
 # robust residual weights (Batch / MonoBatch .set_robust_weights): include/dvo.h
 ROBUST_NONE, ROBUST_HUBER, ROBUST_STUDENT_T = 0, 1, 2
 ROBUST_SCALE_ADAPTIVE, ROBUST_SCALE_GIVEN = 0, 1
+ROBUST_SCALE_MEDIAN = 2   # the median (MAD) scale: Batch / MonoBatch .set_robust_median
+MEDIAN_BINS = 256
 # affine brightness compensation (Batch / MonoBatch .set_affine_brightness): include/dvo.h
 AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
 # the geometric (depth) term (Batch.set_geometric): include/dvo.h
@@ -449,6 +467,24 @@ def optimize_robust(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, kind
     return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
                 xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
                 xi_next=np.array(out.xi_next[:], np.float32))
+
+
+def op_gn_step_robust_median(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, kind, param, s2, cfg=None, dev=0):
+    """optimize_robust() through the median scale's kernel pair (dvo_op_gn_step_robust_median, include/dvo.h); adds `counts` (uint32
+    [256], the bins of the contributing pixels' |r|), `median_bin` (-1: no pixel) and `next_s2` (the s2 of the entry the solve wrote)."""
+    obj_gray = f32(obj_gray); ref_gray = f32(ref_gray); ref_depth = f32(ref_depth); ref_sigma = f32(ref_sigma)
+    K = f32(K).reshape(9); xi = f32(xi)
+    h, w = ref_gray.shape
+    out = GnResult()
+    counts = np.zeros(MEDIAN_BINS, np.uint32)
+    m = C.c_int(0)
+    nxt = C.c_float(0.0)
+    _check(lib().dvo_op_gn_step_robust_median(dev, C.byref(cfg) if cfg is not None else None, fp(obj_gray), fp(ref_gray),
+                                              fp(ref_depth), fp(ref_sigma), w, h, fp(K), fp(xi), level, int(kind), C.c_float(param),
+                                              C.c_float(s2), C.byref(out), counts.ctypes.data_as(C.c_void_p), C.byref(m), C.byref(nxt)))
+    return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
+                xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
+                xi_next=np.array(out.xi_next[:], np.float32), counts=counts, median_bin=int(m.value), next_s2=np.float32(nxt.value))
 
 
 def op_gn_step_affine(obj_gray, ref_gray, ref_depth, ref_sigma, K, xi, level, a, b, kind=ROBUST_NONE, param=1.0, s2=0.0, cfg=None, dev=0):
@@ -907,6 +943,31 @@ class _RobustWeights:
         s2 = np.zeros(self.n_seq, np.float32)
         _check(lib().dvo_batch_last_robust_scales(self._p, fp(s2)))
         return s2
+
+    def set_robust_median(self, kind=ROBUST_HUBER, param=1.0, scale_floor=1e-3):
+        """Robust weights with the median (MAD) scale from the next push / call on (dvo_batch_set_robust_median): ROBUST_HUBER (param
+        = k) or ROBUST_STUDENT_T (param = nu); None: off."""
+        if kind is None:
+            _check(lib().dvo_batch_set_robust_median(self._p, None))
+            return
+        c = RobustConfig(C.sizeof(RobustConfig), int(kind), ROBUST_SCALE_MEDIAN, float(param), float(scale_floor))
+        _check(lib().dvo_batch_set_robust_median(self._p, C.byref(c)))
+
+    def last_robust_log(self, seq):
+        """dict of the median scale's record of `seq` at the last push (dvo_robust_log): per logged iteration the s2 it used and the
+        median bin and count of its own pixels (the next entry's), and the priming pair's; synchronises."""
+        lg = RobustLog()
+        lg.struct_size = C.sizeof(RobustLog)
+        _check(lib().dvo_batch_last_robust_log(self._p, int(seq), C.byref(lg)))
+        rec = np.frombuffer(lg, ROBUST_LOG_DTYPE)[0]
+        return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), s2=rec["s2"].copy(), median_bin=rec["median_bin"].copy(),
+                    count=rec["count"].copy(), prime_bin=int(rec["prime_bin"]), prime_count=int(rec["prime_count"]))
+
+    def last_robust_histogram(self, seq):
+        """uint32 [256]: the bin counts of the finest level's last iteration of `seq` at the last push (zeros: not tracked); synchronises."""
+        counts = np.zeros(MEDIAN_BINS, np.uint32)
+        _check(lib().dvo_batch_last_robust_histogram(self._p, int(seq), counts.ctypes.data_as(C.c_void_p)))
+        return counts
 
 
 class _AffineBrightness:

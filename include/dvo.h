@@ -615,6 +615,50 @@ typedef struct dvo_robust_config {
 int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg);   /* both kinds; from the next push / call on */
 int dvo_batch_set_robust_scales(dvo_batch* b, const float* s, int s_on_device); /* [n_seq], GIVEN mode; NULL clears */
 int dvo_batch_last_robust_scales(dvo_batch* b, float* s2);                      /* [n_seq], host, synchronises */
+/* ---- the median (MAD) robust scale (both batch kinds) ----------------------------------------------------------------------------
+ * dvo_batch_set_robust_median turns the robust weights on with a third scale rule, DVO_ROBUST_SCALE_MEDIAN: per sequence and
+ * Gauss-Newton iteration s2 comes from the median of |r| over the contributing pixels of the PREVIOUS evaluation, found from 256 exact
+ * bin counts.  The residuals are treated as centred (no subtraction of a median of r).  A 50 %-breakdown scale, where the adaptive
+ * rule is a weighted RMS.  kind is DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T, scale_mode must be DVO_ROBUST_SCALE_MEDIAN, param and
+ * scale_floor are validated as dvo_batch_set_robust_weights validates them.  cfg == NULL, or dvo_batch_set_robust_weights with
+ * DVO_ROBUST_NONE / NULL, turns it off.  The contract, float32 and integer, IEEE, no contraction:
+ *   Bin.       r = the unweighted residual robust_rho sees.  K0 = (127 - 16) << 4 = 1776;
+ *              bin = clamp((int)(__float_as_uint(fabsf(r)) >> 19) - 1776, 0, 255): 16 bins per octave over [2^-16, 1), everything
+ *              smaller in bin 0, everything larger (and NaN) in bin 255.
+ *   Counts.    Every contributing pixel is counted: sum counts = n_valid exactly.  A rejected pixel (rho forced to 1) is not counted.
+ *   Histogram. counts[256] per sequence are exact integer sums over all tiles of the launch, main loop and deferred border loop
+ *              alike: independent of tile shape, launch plan, track_streams and summation order.
+ *   Median.    n = sum counts.  n == 0: the next entry is plain.  Otherwise m = the smallest bin with cum(m) >= (n + 1) / 2 (integer
+ *              division); med = __uint_as_float(((m + 1776) << 19) | (1 << 18)), the bin's midpoint; s = 1.4826f * med;
+ *              s2 = max(s * s, floor2), floor2 = scale_floor * scale_floor; the next launch's weights are those of (kind, param, s2).
+ *   Lag and priming.  Iteration i uses the entry written by the solve of iteration i - 1 (the same level, or the coarser level's last
+ *              iteration), as the adaptive rule does.  The first iteration of the coarsest level uses the entry of a priming pair: one
+ *              tile launch plus solve on the coarsest level at the start pose, which writes the entry and the priming slot of the log
+ *              and nothing else: no pose, no track log, no quality record.
+ *   Weights and sums.  Everything downstream of s2 (rho, the weighted sums, the weighted residual) is dvo_batch_set_robust_weights'.
+ * While on, every level runs launch pairs (k_track_gn_md + k_gn_solve_md).  dvo_batch_last_robust_scales reports the s2 the finest
+ * level's last solve used, as in the other modes.  dvo_batch_last_robust_log (host, synchronises): per level and iteration, indexed
+ * like dvo_track_log, the s2 the iteration USED and the median bin m and count n of that iteration's pixels, which produced the NEXT
+ * entry (m = -1 where n = 0), and the priming pair's (m, n); empty (n_iter all 0) for a sequence that did not track.
+ * dvo_batch_last_robust_histogram (host, synchronises): counts[256] of the finest level's last iteration, zeros for a sequence that
+ * did not track.
+ * Errors, returned before anything is enqueued: a NULL handle, a config that fails dvo_batch_set_robust_weights' checks, a kind of
+ * DVO_ROBUST_NONE, a scale_mode other than DVO_ROBUST_SCALE_MEDIAN, affine brightness or the geometric term on ->
+ * DVO_ERR_BAD_ARGUMENT.  While it is on, dvo_batch_set_affine_brightness, dvo_batch_set_geometric and
+ * dvo_batch_set_geometric_affine refuse, and so does dvo_batch_set_robust_scales (there are no given rows).  The readers before a push that ran in this mode -> DVO_ERR_NOT_READY. */
+#define DVO_ROBUST_SCALE_MEDIAN   2
+typedef struct dvo_robust_log {
+    int   struct_size;    /* sizeof(dvo_robust_log), set by the caller */
+    int   levels;
+    int   n_iter[DVO_MAX_LEVELS];
+    float s2[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];          /* the s2 the iteration used (+inf: plain) */
+    int   median_bin[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];  /* m of the iteration's own pixels: the next entry's (-1: n = 0) */
+    int   count[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];       /* n = sum counts = n_valid */
+    int   prime_bin, prime_count;                          /* the priming pair's (m, n) */
+} dvo_robust_log;
+int dvo_batch_set_robust_median(dvo_batch* b, const dvo_robust_config* cfg);      /* both kinds; from the next push / call on */
+int dvo_batch_last_robust_log(dvo_batch* b, int seq, dvo_robust_log* log);        /* host, synchronises */
+int dvo_batch_last_robust_histogram(dvo_batch* b, int seq, uint32_t counts[256]); /* host, synchronises */
 /* ---- affine brightness compensation: gain and offset (both batch kinds) ---------------------------------------------------------
  * By default every residual is r = I2 - I1: brightness constancy.  dvo_batch_set_affine_brightness makes every later push / call
  * track under the photometric model I2(warp(x)) ~ a * I1(x) + b with one (a, b) per sequence (auto-exposure, auto-gain), I1 and I2
@@ -867,6 +911,13 @@ int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
 int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
                           const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
                           const float xi[6], int level, int kind, float param, float s2, dvo_gn_result* out);
+/* dvo_op_gn_step_robust through the median scale's pair (dvo_batch_set_robust_median: k_track_gn_md + k_gn_solve_md), run once: the
+ * same weighted sums, plus counts[256] of the contributing pixels' |r|, the median bin the solve selected (-1 where no pixel
+ * contributed) and next_s2, the s2 of the entry it wrote (+inf: plain), with floor2 = 0. */
+int dvo_op_gn_step_robust_median(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray,
+                                 const float* ref_depth, const float* ref_sigma, int w, int h, const float K[9],
+                                 const float xi[6], int level, int kind, float param, float s2,
+                                 dvo_gn_result* out, uint32_t counts[256], int* median_bin, float* next_s2);
 /* dvo_op_gn_step_robust with affine brightness compensation (dvo_batch_set_affine_brightness): the pair run once with the entry (a, b)
  * ((1, 0) unless finite with a > 0).  moments = (N, M1, M2, M11, M12) in double, N being M0 with robust weights and n_valid with kind =
  * DVO_ROBUST_NONE; next_ab = the entry the solve writes from them under the guards min_pixels = 64, min_contrast = 1e-3, gain range

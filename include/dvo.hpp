@@ -198,6 +198,26 @@ public:
         check(dvo_batch_last_robust_scales(b_, out.data()));
         return out;
     }
+    // robust weights with the median (MAD) scale from the next push / call on (dvo_batch_set_robust_median): kind DVO_ROBUST_HUBER or
+    // DVO_ROBUST_STUDENT_T; setRobustWeights(DVO_ROBUST_NONE) turns them off
+    void setRobustMedian(int kind, float param = 1.345f, float scale_floor = 1e-3f)
+    {
+        dvo_robust_config c{(int)sizeof(dvo_robust_config), kind, DVO_ROBUST_SCALE_MEDIAN, param, scale_floor};
+        check(dvo_batch_set_robust_median(b_, &c));
+    }
+    dvo_robust_log lastRobustLog(int seq)
+    {
+        dvo_robust_log lg{};
+        lg.struct_size = (int)sizeof(dvo_robust_log);
+        check(dvo_batch_last_robust_log(b_, seq, &lg));
+        return lg;
+    }
+    std::vector<uint32_t> lastRobustHistogram(int seq)
+    {
+        std::vector<uint32_t> out(256);
+        check(dvo_batch_last_robust_histogram(b_, seq, out.data()));
+        return out;
+    }
     // affine brightness compensation from the next push / call on (dvo_batch_set_affine_brightness): mode DVO_AFFINE_OFF turns it off
     void setAffineBrightness(int mode, int min_pixels = 64, float min_contrast = 1e-3f, float gain_min = 0.25f, float gain_max = 4.0f)
     {
@@ -390,6 +410,26 @@ public:
     {
         std::vector<float> out(n_);
         check(dvo_batch_last_robust_scales(b_, out.data()));
+        return out;
+    }
+    // robust weights with the median (MAD) scale from the next push / call on (dvo_batch_set_robust_median): kind DVO_ROBUST_HUBER or
+    // DVO_ROBUST_STUDENT_T; setRobustWeights(DVO_ROBUST_NONE) turns them off
+    void setRobustMedian(int kind, float param = 1.345f, float scale_floor = 1e-3f)
+    {
+        dvo_robust_config c{(int)sizeof(dvo_robust_config), kind, DVO_ROBUST_SCALE_MEDIAN, param, scale_floor};
+        check(dvo_batch_set_robust_median(b_, &c));
+    }
+    dvo_robust_log lastRobustLog(int seq)
+    {
+        dvo_robust_log lg{};
+        lg.struct_size = (int)sizeof(dvo_robust_log);
+        check(dvo_batch_last_robust_log(b_, seq, &lg));
+        return lg;
+    }
+    std::vector<uint32_t> lastRobustHistogram(int seq)
+    {
+        std::vector<uint32_t> out(256);
+        check(dvo_batch_last_robust_histogram(b_, seq, out.data()));
         return out;
     }
     // affine brightness compensation from the next push / call on (dvo_batch_set_affine_brightness): mode DVO_AFFINE_OFF turns it off

@@ -13,7 +13,12 @@ the finest level's kernel -- k_track_gn<4, 2, false, true> against k_track_gn_rw
 k_gn_solve_rw): calls, total and average time per launch.  No cost is promised: the figures are against the plain kernel of the same
 build, and the spread of the plain rounds stands beside them.  Prints one JSON line.
 
-    python tools/bench_robust.py --steps 8 --warmup 3 --rounds 3 --trace [--fixed-iterations 4]
+--median adds a fourth series, huber_median: Huber with the median (MAD) scale (dvo_batch_set_robust_median), whose
+finest-level kernel is k_track_gn_md<4, 2, true> and whose solve is k_gn_solve_md; its push also holds the priming pair.  The
+series' figures stand against huber's (k_track_gn_rw / k_gn_solve_rw of the same build), and the spread of the huber rounds is
+reported beside them.  Without the flag the tool runs what it always ran.
+
+    python tools/bench_robust.py --steps 8 --warmup 3 --rounds 3 --trace [--fixed-iterations 4] [--median]
 """
 import argparse
 import csv
@@ -36,9 +41,14 @@ from dvo_amd import synth
 
 F, W, H = 3, 640, 480
 MODES = ["plain", "huber", "student_t"]
-ROBUST = {"huber": (dvo.ROBUST_HUBER, 1.345), "student_t": (dvo.ROBUST_STUDENT_T, 5.0)}
+ROBUST = {"huber": (dvo.ROBUST_HUBER, 1.345), "student_t": (dvo.ROBUST_STUDENT_T, 5.0), "huber_median": (dvo.ROBUST_HUBER, 1.345)}
+MEDIAN = "huber_median"
 FINEST = {"plain": "dvo::k_track_gn<4, 2, false, true>(", "huber": "dvo::k_track_gn_rw<4, 2, true>(", "student_t": "dvo::k_track_gn_rw<4, 2, true>("}
+FINEST[MEDIAN] = "dvo::k_track_gn_md<4, 2, true>("
 SOLVE = {"plain": "dvo::k_gn_solve(", "huber": "dvo::k_gn_solve_rw(", "student_t": "dvo::k_gn_solve_rw("}
+
+
+SOLVE[MEDIAN] = "dvo::k_gn_solve_md("
 
 
 def frames(B, U, dev):
@@ -56,7 +66,9 @@ def frames(B, U, dev):
 
 def run(mode, a, B, g8, d16, stream):
     h = dvo.Batch(B, synth.K_640, W, H, 4, 1, cfg=dvo.default_config(stream=stream, fixed_iterations=a.fixed_iterations))
-    if mode != "plain":
+    if mode == MEDIAN:
+        h.set_robust_median(ROBUST[mode][0], ROBUST[mode][1], a.scale_floor)
+    elif mode != "plain":
         kind, param = ROBUST[mode]
         h.set_robust_weights(kind, param, dvo.ROBUST_SCALE_ADAPTIVE, a.scale_floor)
     ev = []
@@ -114,8 +126,10 @@ def main():
                     help="N > 0: every level runs N iterations of every sequence, so the three estimators run the same launches on the same "
                          "number of sequences and the per-launch times compare like for like; 0: bench.py's stop tests")
     ap.add_argument("--trace", action="store_true", help="also one traced child run per estimator (rocprofv3 --kernel-trace --stats)")
+    ap.add_argument("--median", action="store_true", help="a fourth series: Huber with the median (MAD) scale (dvo_batch_set_robust_median)")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     a = ap.parse_args()
+    modes = MODES + ([MEDIAN] if a.median else [])
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     g8, d16 = frames(a.batch, a.unique, dev)
@@ -123,20 +137,23 @@ def main():
     if a.child:
         run(a.child, a, a.batch, g8, d16, stream)
         return 0
-    res = {m: [] for m in MODES}
+    res = {m: [] for m in modes}
     for _ in range(a.rounds):
-        for m in MODES:
+        for m in modes:
             res[m].append(run(m, a, a.batch, g8, d16, stream))
-    med = {m: float(np.median(res[m])) for m in MODES}
+    med = {m: float(np.median(res[m])) for m in modes}
     out = {"batch": a.batch, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "fixed_iterations": a.fixed_iterations,
-           "ms_per_push": {m: round(med[m], 3) for m in MODES},
-           "all_rounds": {m: [round(x, 3) for x in res[m]] for m in MODES},
+           "ms_per_push": {m: round(med[m], 3) for m in modes},
+           "all_rounds": {m: [round(x, 3) for x in res[m]] for m in modes},
            "plain_spread_ms": round(max(res["plain"]) - min(res["plain"]), 3),
-           "vs_plain": {m: round(med[m] / med["plain"], 4) for m in MODES[1:]}}
+           "vs_plain": {m: round(med[m] / med["plain"], 4) for m in modes[1:]}}
+    if a.median:
+        out["huber_spread_ms"] = round(max(res["huber"]) - min(res["huber"]), 3)
+        out["median_vs_huber"] = round(med[MEDIAN] / med["huber"], 4)
     del g8, d16
     torch.cuda.empty_cache()
     if a.trace:
-        out["kernels"] = {m: trace(m, a) for m in MODES}
+        out["kernels"] = {m: trace(m, a) for m in modes}
     print(json.dumps(out))
     return 0
 
