@@ -126,6 +126,12 @@ int dvo_vo_set_distortion(dvo_vo* vo, const float D[5])
     return vo->impl.set_distortion(D);
 }
 
+int dvo_vo_set_photometric(dvo_vo* vo, const float inv_response[256], const float* vignette)
+{
+    if (!vo) { set_error("dvo_vo_set_photometric: null handle"); return DVO_ERR_BAD_ARGUMENT; }
+    return vo->impl.set_photometric(inv_response, vignette);
+}
+
 int dvo_vo_odometrize_depth(dvo_vo* vo, const float* gray, const float* depth, const float* sigma, float T_rel[16])
 {
     if (!vo) return DVO_ERR_BAD_ARGUMENT;

@@ -9,6 +9,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <map>
+#include <utility>
 
 #include <dlfcn.h>
 
@@ -279,6 +281,18 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
 {
     PyramidKernel none;
     PyramidKernel& k = ran ? *ran : none;
+    if (in.photo.gain) {   // raw mono frame of a calibrated handle (the callers refuse float frames): the k_pyramid*_photo kernels, gray
+                           // only; with a remap whole frames and k_pyramid_remap_plan's SKIP, else k_pyramid's rows and copy-forward
+        PyramidArgs a = frame_args(fs, in.remap ? false : in.rows_decimated);
+        a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);
+        for (int l = 0; l < fs.g.levels; l++) a.dst[0][l] = fs.gray[l];
+        a.remap = in.remap; a.remap_cam = in.remap_cam;
+        if (in.remap) a.seq_action = seq_action;
+        else plan_copy(a, seq_action, copy_from);
+        fs.sigma_by_validity = false;
+        k = launch_pyramid(a, fs.n_seq, s, &in.photo);
+        return false;
+    }
     if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
                                          // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
         PyramidArgs a = frame_args(fs, false);
@@ -348,6 +362,80 @@ int upload_rows(void* dst, const void* src, size_t row_bytes, int img_rows, size
     const size_t rows = ((size_t)img_rows >> culls) * n_img;
     if (stored) *stored = row_bytes * rows;
     DVO_HIP(hipMemcpy2DAsync(dst, row_bytes, src, row_bytes << culls, row_bytes, rows, hipMemcpyHostToDevice, s));
+    return DVO_OK;
+}
+
+int Photometry::set(const char* who, int n, const float* resp, const float* vign, const int* cal_of_seq, int n_seq, const Geometry& g,
+                    const Undistortion& und, hipStream_t s)
+{
+    if (n < 0) { set_error(std::string(who) + ": n_cal is negative"); return DVO_ERR_BAD_ARGUMENT; }
+    if (n > 0 && !resp && !vign) { set_error(std::string(who) + ": n_cal > 0 needs inv_response, vignette or both"); return DVO_ERR_BAD_ARGUMENT; }
+    if (resp)
+        for (int c = 0; c < n; c++)
+            for (int i = 0; i < 256; i++) {
+                const float v = resp[(size_t)c * 256 + i];
+                if (!std::isfinite(v) || v < 0.0f) {
+                    set_error(std::string(who) + ": inv_response entry " + std::to_string(i) + " of calibration " + std::to_string(c) +
+                              " is not finite or is negative");
+                    return DVO_ERR_BAD_ARGUMENT;
+                }
+            }
+    if (cal_of_seq && n > 0)
+        for (int q = 0; q < n_seq; q++)
+            if (cal_of_seq[q] < 0 || cal_of_seq[q] >= n) {
+                set_error(std::string(who) + ": seq_cal of sequence " + std::to_string(q) + " is " + std::to_string(cal_of_seq[q]) +
+                          ", outside [0, " + std::to_string(n) + ")");
+                return DVO_ERR_BAD_ARGUMENT;
+            }
+    DVO_HIP(hipStreamSynchronize(s));   // (the previous tables may still be read by queued work: none before the first frame)
+    clear();
+    if (n == 0) return DVO_OK;
+    const size_t px = (size_t)g.src_w * g.src_h;
+    response.resize((size_t)n * 256);
+    for (int c = 0; c < n; c++)
+        for (int i = 0; i < 256; i++) response[(size_t)c * 256 + i] = resp ? resp[(size_t)c * 256 + i] : (float)i * (float)(1.0 / 255.0);
+    if (vign) vignette.assign(vign, vign + px * (size_t)n);
+    seq_cal.assign((size_t)n_seq, 0);
+    if (cal_of_seq) seq_cal.assign(cal_of_seq, cal_of_seq + n_seq);
+    n_cal = n;
+    const int rc = rebuild(n_seq, g, und, s);
+    if (rc != DVO_OK) clear();   // (no calibration rather than a half-built one)
+    return rc;
+}
+
+int Photometry::rebuild(int n_seq, const Geometry& g, const Undistortion& und, hipStream_t s)
+{
+    if (!enabled()) return DVO_OK;
+    // one gain table per distinct (calibration, undistortion camera): the integer pair, not the table's contents
+    std::map<std::pair<int, int>, int> ids;
+    std::vector<int> pairs;
+    seq_pair.assign((size_t)n_seq, 0);
+    for (int q = 0; q < n_seq; q++) {
+        const std::pair<int, int> key(seq_cal[(size_t)q], und.enabled() ? und.cam_of[(size_t)q] : 0);
+        auto it = ids.emplace(key, (int)ids.size());
+        if (it.second) { pairs.push_back(key.first); pairs.push_back(key.second); }
+        seq_pair[(size_t)q] = it.first->second;
+    }
+    n_pair = (int)ids.size();
+    const int T = g.top(), tw = g.w[T], th = g.h[T];
+    const size_t head = ((size_t)n_seq + 3) & ~(size_t)3;
+    DevBuf pairs_dev, vign_dev;
+    DVO_TRY(pairs_dev.alloc(sizeof(int) * pairs.size()));
+    if (!vignette.empty()) DVO_TRY(vign_dev.alloc(sizeof(float) * vignette.size()));
+    DVO_HIP(hipStreamSynchronize(s));
+    DVO_TRY(resp_dev.alloc(sizeof(float) * response.size()));
+    DVO_TRY(idx_dev.alloc(sizeof(int) * 2 * head));
+    DVO_TRY(gain_dev.alloc(sizeof(float) * (size_t)n_pair * tw * th));
+    DVO_HIP(hipMemcpyAsync(resp_dev.p, response.data(), sizeof(float) * response.size(), hipMemcpyHostToDevice, s));
+    DVO_HIP(hipMemsetAsync(idx_dev.p, 0, idx_dev.bytes, s));
+    DVO_HIP(hipMemcpyAsync(idx_dev.p, seq_cal.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
+    DVO_HIP(hipMemcpyAsync(idx_dev.as<int>() + head, seq_pair.data(), sizeof(int) * (size_t)n_seq, hipMemcpyHostToDevice, s));
+    DVO_HIP(hipMemcpyAsync(pairs_dev.p, pairs.data(), pairs_dev.bytes, hipMemcpyHostToDevice, s));
+    if (vign_dev.p) DVO_HIP(hipMemcpyAsync(vign_dev.p, vignette.data(), vign_dev.bytes, hipMemcpyHostToDevice, s));
+    launch_photometric_map(vign_dev.as<float>(), pairs_dev.as<int>(), n_pair, g.src_w, g.src_h, g.culls, tw, th,
+                           und.enabled() ? und.table(n_seq) : nullptr, gain_dev.as<float>(), s);
+    DVO_HIP(hipGetLastError());
+    DVO_HIP(hipStreamSynchronize(s));   // (pairs_dev and vign_dev go out of scope)
     return DVO_OK;
 }
 
@@ -1389,12 +1477,24 @@ int VisualOdometry::set_distortion(const float D[5])
 {
     if (fed) { set_error("dvo_vo_set_distortion: the handle has consumed a frame (D is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
-    return und.set("dvo_vo_set_distortion", D, false, 1, K, false, geoM, stream);
+    DVO_TRY(und.set("dvo_vo_set_distortion", D, false, 1, K, false, geoM, stream));
+    return pho.rebuild(1, geoM, und, stream);   // (a calibration set before D: its gains move to the remap's source pixels)
 }
 
-// the sensor-depth entry points and init_keyframe have no defined meaning on a handle that undistorts (include/dvo.h)
+int VisualOdometry::set_photometric(const float* resp, const float* vign)
+{
+    if (fed) { set_error("dvo_vo_set_photometric: the handle has consumed a frame (the calibration is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    return pho.set("dvo_vo_set_photometric", (resp || vign) ? 1 : 0, resp, vign, nullptr, 1, geoM, und, stream);
+}
+
+// the sensor-depth entry points and init_keyframe have no defined meaning on a handle that undistorts or calibrates (include/dvo.h)
 static int refuse_distorted(const VisualOdometry& vo, const char* who)
 {
+    if (vo.pho.enabled()) {
+        set_error(std::string(who) + ": the handle has a photometric calibration (dvo_vo_set_photometric), which needs raw mono frames (dvo_vo_odometrize_raw)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     if (!vo.und.enabled()) return DVO_OK;
     set_error(std::string(who) + ": the handle undistorts its frames (dvo_vo_set_distortion); sensor-depth input is not undistorted");
     return DVO_ERR_BAD_ARGUMENT;
@@ -1541,6 +1641,10 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
 {  // system.hpp:44-74; `raw` != nullptr: the frame arrives as u8 gray / RGB(A) and is converted while the pyramid is built
     if ((!gray && !raw) || !T_world) { set_error("null argument"); return DVO_ERR_BAD_ARGUMENT; }
     if (raw && raw_channels != 1 && raw_channels != 3 && raw_channels != 4) { set_error("bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!raw && pho.enabled()) {
+        set_error("dvo_vo_odometrize: the handle has a photometric calibration (dvo_vo_set_photometric), which needs the byte: feed raw frames (dvo_vo_odometrize_raw)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     DVO_TRY(select_device(device));
     fed = true;
     if (!trkM_ready) {   // one launch per track() call (k_track_persist), as the sensor-depth tracker
@@ -1597,6 +1701,7 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     frame.id = ++latest_id;
     for (int i = 0; i < 6; i++) { frame.xi[i] = 0; frame.rel_xi[i] = 0; }
     und.apply(fin, 1);   // dvo_vo_set_distortion: k_pyramid_remap
+    pho.apply(fin, 1);   // dvo_vo_set_photometric: k_pyramid_raw4_photo / k_pyramid_photo
     build_pyramid(frame.fs, fin, stream);
     if (is_key) *is_key = 0;
     const int T = geoM.top();

@@ -134,6 +134,9 @@ struct FrameInput {
     // gathers each kept pixel through its camera's table.  Whole frames (rows_decimated = false).
     const int* remap = nullptr;       // [n_cam][th][tw] source indices
     const int* remap_cam = nullptr;   // [n_seq] camera of each sequence
+    // raw mono frames with a photometric calibration (Photometry::apply): the k_pyramid*_photo kernels.  Rows may be decimated
+    // (the gain table is top-level sized) unless the frames are undistorted too.
+    PhotoArgs photo{};
     bool raw() const { return rgb != nullptr; }
     const void* key0() const { return raw() ? (const void*)rgb : (const void*)gray; }
     const void* key1() const { return raw() ? (const void*)depth16 : (const void*)depth; }
@@ -170,6 +173,7 @@ struct Undistortion {
     std::vector<float> D;   // [n_seq][5] as set; empty: no undistortion (the handle runs exactly the kernels it runs without)
     DevBuf dev;             // [n_seq] int camera index (padded to 16 bytes), then [n_cam][th][tw] int tables
     int n_cam = 0;
+    std::vector<int> cam_of;   // [n_seq] the camera index of each sequence, as on the device (Photometry pairs it with the calibration)
     const int* cam() const { return dev.as<int>(); }
     const int* table(int n_seq) const { return dev.as<int>() + (((size_t)n_seq + 3) & ~(size_t)3); }
     bool enabled() const { return !D.empty(); }
@@ -180,6 +184,37 @@ struct Undistortion {
     {
         if (!enabled()) return;
         in.remap = table(n_seq); in.remap_cam = cam();   // (the caller uploads whole frames: rows_decimated = false)
+    }
+};
+
+// Photometric calibration fused into the mono pyramid (dvo_batch_set_photometric, dvo_vo_set_photometric): n_cal
+// inverse-response tables and vignette maps, one of them per sequence.  k_photometric_map writes one table of gains (1 / vignette at
+// each kept pixel's source) per distinct (calibration, undistortion camera) pair of integers, once: at set, and again when D is set
+// after it (the source of a kept pixel is then the remap's).  The per-frame kernels read response[cal][g8] * gain[pair][y][x].
+struct Photometry {
+    int n_cal = 0;                 // 0: none (the handle runs exactly the kernels it runs without)
+    int n_pair = 0;
+    std::vector<float> response;   // [n_cal][256] as used (a NULL response: k_ingest's scale, filled in)
+    std::vector<float> vignette;   // [n_cal][src_h][src_w] as set; empty: 1
+    std::vector<int> seq_cal;      // [n_seq]
+    std::vector<int> seq_pair;     // [n_seq]
+    DevBuf resp_dev, idx_dev, gain_dev;   // [n_cal][256]; [n_seq] cal then [n_seq] pair (each padded to 16 bytes); [n_pair][th][tw]
+    bool enabled() const { return n_cal > 0; }
+    // n == 0 clears.  Errors (DVO_ERR_BAD_ARGUMENT naming `who` and the first bad calibration / sequence) leave everything as it was.
+    int set(const char* who, int n, const float* resp, const float* vign, const int* cal_of_seq, int n_seq, const Geometry& g,
+            const Undistortion& und, hipStream_t s);
+    int rebuild(int n_seq, const Geometry& g, const Undistortion& und, hipStream_t s);   // the gain tables from what is set now
+    void clear()
+    {
+        n_cal = n_pair = 0;
+        response.clear(); vignette.clear(); seq_cal.clear(); seq_pair.clear();
+        resp_dev.release(); idx_dev.release(); gain_dev.release();
+    }
+    void apply(FrameInput& in, int n_seq) const
+    {
+        if (!enabled()) return;
+        in.photo.response = resp_dev.as<float>(); in.photo.gain = gain_dev.as<float>();
+        in.photo.seq_cal = idx_dev.as<int>(); in.photo.seq_pair = idx_dev.as<int>() + (((size_t)n_seq + 3) & ~(size_t)3);
     }
 };
 
@@ -500,6 +535,8 @@ struct VisualOdometry {  // System::VisualOdometry, system.hpp:12-104
     Undistortion und;      // dvo_vo_set_distortion: the mono frames (odometrize) are undistorted while their pyramid is built
     bool fed = false;      // a frame went through odometrize* or init_keyframe (dvo_vo_load does not count): D is fixed from then on
     int set_distortion(const float D[5]);
+    Photometry pho;        // dvo_vo_set_photometric: the raw mono frames (odometrize) are calibrated while their pyramid is built
+    int set_photometric(const float* resp, const float* vign);
     DevBuf raw_rgb, raw_depth;
     // the maps of one frame go up on separate streams: three strided copies queued on one stream run one after the other with
     // ~9 us between them (98 us from the end of one frame's tracking to the next pyramid, profiles/r03_single_hip_trace.txt)
@@ -712,6 +749,9 @@ struct MonoBatch {
     std::vector<float> K_full;   // the creation K at full resolution: [9], or (per camera) [n_seq][9] -- the undistortion's camera
     Undistortion und;            // dvo_batch_set_distortion (before the first frame)
     int set_distortion(const float* D, bool per_sequence);
+    Photometry pho;              // dvo_batch_set_photometric (before the first frame)
+    int set_photometric(int n_cal, const float* resp, const float* vign, const int* seq_cal);
+    PyramidKernel last_build;    // what the last frame build launched (dvo_debug_batch_last_pyramid_kernel)
     // K: [9] for every sequence, or (per_camera) [n][9], one per sequence
     int init(int n, const float* K, int w, int h, int ring, const dvo_config* c, bool per_camera = false);
     ~MonoBatch();

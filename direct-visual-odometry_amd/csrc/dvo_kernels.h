@@ -51,6 +51,18 @@ struct PyramidArgs {
     const int* remap_cam = nullptr;   // [n_seq] camera (table) of each sequence
 };
 
+// Photometric calibration of raw mono frames (dvo_batch_set_photometric, dvo_vo_set_photometric): the second
+// argument block of the k_pyramid*_photo kernels, beside PyramidArgs (which stays as it is for every other kernel).  Set (gain !=
+// nullptr) only on a handle with a calibration: launch_pyramid then takes the photo kernels, and only them.
+//   gray = response[seq_cal[s]][g8] * gain[seq_pair[s]][y][x]        (one multiply; gain < 0: the pixel is DVO_INVALID)
+struct PhotoArgs {
+    const float* response = nullptr;   // [n_cal][256] inverse response in gray units
+    const float* gain = nullptr;       // [n_pair][th][tw] 1 / vignette at the kept pixel's source, kPhotoMasked where there is none
+    const int* seq_cal = nullptr;      // [n_seq] calibration of each sequence
+    const int* seq_pair = nullptr;     // [n_seq] gain table (calibration x undistortion camera) of each sequence
+};
+constexpr float kPhotoMasked = -1.0f;  // gain of a masked pixel (vignette not finite or <= 0) or of the remap's border: no 1 / V is negative
+
 // One distinct camera of the fused undistortion: the full-resolution K (fx, fy, cx, cy) and D = (k1, k2, p1, p2, k3)
 struct UndistortCam {
     Intr k;
@@ -653,7 +665,14 @@ void launch_regularize_redecimate_plan(const RegDecArgs& a, const MonoStartArgs&
 struct PyramidKernel {
     int kind = DVO_PYRAMID_KERNEL_SCALAR, culls = 0, plan = 0;
 };
-PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s);
+// photo (optional, photo->gain set): raw mono frames of a calibrated handle -- k_pyramid_raw4_photo<2, plan> (kind _PHOTO_RAW4) where
+// k_pyramid_raw4's conditions hold at culls 2 and the gain rows can be read 16 bytes at a time, else k_pyramid_photo<plan, remap>
+// (_PHOTO_SCALAR, or _PHOTO_REMAP with a.remap).  Without it: exactly the kernels chosen before there was a calibration.
+PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s, const PhotoArgs* photo = nullptr);
+// k_photometric_map: gain[p][y][x] of pair p = (cal, cam) = 1 / vignette[cal][source of kept pixel (x, y)], the source being
+// (x, y) << culls, or remap[cam][y][x] with a remap (then -1 gives kPhotoMasked).  vignette == nullptr: 1.
+void launch_photometric_map(const float* vignette, const int* pairs /*[n_pair][2]*/, int n_pair, int w, int h, int culls, int tw, int th,
+                            const int* remap, float* gain, hipStream_t s);
 // The split build: launch_pyramid_coarse (k_pyramid_raw4_coarse: the gray maps below the top level) and
 // launch_pyramid_rest (k_pyramid_raw4_rest: everything else) together write what launch_pyramid writes.  pyramid_can_split: the
 // arguments are those of a plain raw build (1-channel u8 gray + u16 depth, culls 1 or 2, no plan, no remap) with the alignment the

@@ -6,6 +6,8 @@
 // calls written in dvo_math.h fuse.
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 #include "dvo_kernels.h"
@@ -426,6 +428,145 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
             if (prep) __builtin_nontemporal_store(gn_weight(a.step[l], a.sigma_min, a.sigma_max, sg), a.wgt[l] + o);
         }
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Photometric calibration fused into the mono ingest (dvo_batch_set_photometric, dvo_vo_set_photometric).  The
+// kernels below run only on a handle with a calibration and take PhotoArgs beside PyramidArgs; every kernel above is untouched.
+// For a kept pixel with byte (or fixed-point luma) g8:  gray = response[cal][g8] * gain[pair][y][x], one float multiply, where
+// gain = 1 / vignette at the pixel's source was divided once by k_photometric_map; gain < 0 (kPhotoMasked) gives DVO_INVALID.
+// Then the levels are written exactly as the plain kernels write them (pass_valid at the top level: culls >= 1 on this path).
+//
+// The response row of the workgroup's sequence (1 KB, uniform per workgroup) is staged in LDS by the 256 threads, one entry each,
+// before any thread can leave: only the uniform seq >= n_seq exit comes first.  RESP_LDS = false is the other form, plain loads
+// from the cached table (DVO_PHOTO_RESPONSE=global: A/B runs, tools/bench_photometric.py).
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float photo_gray(float response, float gain) { return gain < 0.0f ? kInvalid : response * gain; }
+
+// k_pyramid_raw4_photo: k_pyramid_raw4 of mono frames (1-channel u8, gray only, CULLS = 2) with the calibration.  Per thread one
+// 16-byte load of source bytes, one 16-byte load of its four gains (plain: the table is shared by every sequence of the pair and
+// stays in L2), four response lookups, one 16-byte top-level store and k_pyramid_raw4's lower-level stores.
+template <int CULLS, bool PLAN, bool RESP_LDS>
+__global__ void __launch_bounds__(256) k_pyramid_raw4_photo(PyramidArgs a, PhotoArgs p)
+{
+    static_assert(CULLS == 2, "the mono geometry: Frame(gray, K, 3, 2)");
+    __shared__ float lut[256];
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1], gw = tw >> 2;
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    if (seq >= a.n_seq) return;   // (uniform per workgroup)
+    const float* resp = p.response + (size_t)load_seq_entry(p.seq_cal, seq) * 256;
+    if constexpr (RESP_LDS) {
+        lut[threadIdx.x] = resp[threadIdx.x];
+        __syncthreads();
+    }
+    const int gi = (int)blockIdx.x * 256 + threadIdx.x;
+    if (gi >= gw * th) return;
+    int y, xg;
+    split_index(gi, gw, a.inv_tw * 4.0f, xg, y);
+    const int x0 = xg << 2;
+    const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x0;
+    f4 top;
+    if (PLAN && a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy-forward (k_pyramid_raw4<, true>): the keyframe's four top-level values
+        top = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref[0][a.levels - 1] + ot));
+    } else {
+        const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + ((size_t)x0 << CULLS);
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.raw_rgb + src_off));
+        const f4 gn = *reinterpret_cast<const f4*>(p.gain + (size_t)load_seq_entry(p.seq_pair, seq) * tw * th + (size_t)y * tw + x0);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const unsigned g8 = v[k] & 0xffu;   // kept pixel k is source pixel k << 2: byte 0 of word k
+            top[k] = pass_valid(photo_gray(RESP_LDS ? lut[g8] : resp[g8], gn[k]));
+        }
+    }
+    __builtin_nontemporal_store(top, reinterpret_cast<f4*>(a.dst[0][a.levels - 1] + ot));
+    for (int t = 1; t < a.levels; t++) {   // lower levels: pixels whose coordinates are multiples of 2^t
+        const int msk = (1 << t) - 1;
+        if (y & msk) break;
+        const int l = a.levels - 1 - t, ly = y >> t;
+        if (ly >= a.h[l]) continue;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int x = x0 + k;
+            if (x & msk) continue;
+            const int lx = x >> t;
+            if (lx >= a.w[l]) continue;
+            __builtin_nontemporal_store(pass_valid(top[k]), a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
+        }
+    }
+}
+
+// k_pyramid_photo: the scalar form, one thread per top-level pixel: 3 / 4 channels (the response is applied to k_ingest's luma, not
+// per channel), the widths k_pyramid_raw4's conditions refuse, and (REMAP) every frame of a handle that also undistorts -- the byte
+// is gathered through the camera's table as in k_pyramid_remap, the gain is read at the thread's own (x, y) either way.  PLAN: a
+// DVO_SEQ_SKIP sequence copies its keyframe's gray forward as k_pyramid<true> does, or (REMAP) writes nothing as k_pyramid_remap_plan.
+template <bool PLAN, bool REMAP>
+__global__ void __launch_bounds__(256) k_pyramid_photo(PyramidArgs a, PhotoArgs p)
+{
+    __shared__ float lut[256];
+    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    if (seq >= a.n_seq) return;   // (uniform per workgroup)
+    lut[threadIdx.x] = p.response[(size_t)load_seq_entry(p.seq_cal, seq) * 256 + threadIdx.x];
+    __syncthreads();
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tw * th) return;
+    int x, y;
+    split_index(i, tw, a.inv_tw, x, y);
+    float raw;
+    if (PLAN && a.seq_action[seq] == DVO_SEQ_SKIP) {
+        if constexpr (REMAP) return;
+        raw = __builtin_nontemporal_load(a.ref[0][a.levels - 1] + (size_t)seq * tw * th + i);
+    } else {
+        const float gain = p.gain[(size_t)load_seq_entry(p.seq_pair, seq) * tw * th + i];
+        size_t src_off;
+        bool inside = true;
+        if constexpr (REMAP) {
+            const int si = a.remap[(size_t)load_seq_entry(a.remap_cam, seq) * tw * th + i];
+            inside = si >= 0;
+            src_off = (size_t)seq * a.src_w * a.src_h + (size_t)(inside ? si : 0);
+        } else {
+            src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + (x << a.culls);
+        }
+        raw = kInvalid;
+        if (inside) {
+            unsigned g8;
+            if (a.raw_channels == 1) {
+                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
+            } else {
+                const uint8_t* q = a.raw_rgb + src_off * (size_t)a.raw_channels;
+                g8 = ((unsigned)q[0] * 4899u + (unsigned)q[1] * 9617u + (unsigned)q[2] * 1868u + 8192u) >> 14;
+            }
+            raw = photo_gray(lut[g8], gain);
+        }
+    }
+    for (int t = 0; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if ((x & msk) | (y & msk)) break;
+        const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
+        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+        __builtin_nontemporal_store((t == 0 && a.culls == 0) ? raw : pass_valid(raw),
+                                    a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
+    }
+}
+
+// k_photometric_map: the gain tables, once per set of the calibration or of D.  One thread per top-level pixel per distinct
+// (calibration, undistortion camera) pair; grid seq_grid(., n_pair), the pair in place of the sequence.  The one IEEE division.
+__global__ void __launch_bounds__(256) k_photometric_map(const float* __restrict__ vignette, const int* __restrict__ pairs, int n_pair,
+                                                         int w, int h, int culls, int tw, int th, const int* __restrict__ remap,
+                                                         float* __restrict__ gain)
+{
+    const int pr = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= tw * th || pr >= n_pair) return;
+    const int cal = pairs[2 * pr], cam = pairs[2 * pr + 1];
+    const int y = i / tw, x = i - y * tw;
+    const int si = remap ? remap[(size_t)cam * tw * th + i] : (y << culls) * w + (x << culls);
+    float out = kPhotoMasked;
+    if (si >= 0) {
+        const float V = vignette ? vignette[(size_t)cal * w * h + si] : 1.0f;
+        if (V > 0.0f && V < __builtin_inff()) out = 1.0f / V;   // (NaN fails both tests)
+    }
+    gain[(size_t)pr * tw * th + i] = out;
 }
 
 // The split build of a big batch's plain raw frames (u8 gray + u16 depth, no plan, no remap): k_pyramid_raw4 as two
@@ -3188,10 +3329,53 @@ static void launch_pyramid_remap_depth(const PyramidArgs& a, hipStream_t s)
     else hipLaunchKernelGGL((k_pyramid_remap_depth<1, false>), grid, dim3(256), 0, s, a);
 }
 
-PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s)
+void launch_photometric_map(const float* vignette, const int* pairs, int n_pair, int w, int h, int culls, int tw, int th, const int* remap,
+                            float* gain, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_photometric_map, seq_grid(cdiv(tw * th, 256), (unsigned)n_pair), dim3(256), 0, s, vignette, pairs, n_pair, w, h, culls,
+                       tw, th, remap, gain);
+}
+
+// The kernels of a calibrated handle's raw mono frames (PhotoArgs set): k_pyramid_raw4_photo under k_pyramid_raw4's own conditions at
+// culls 2 plus 16-byte gain rows, else k_pyramid_photo.  A missing piece is an error of the caller (build_pyramid checks), not a
+// reason to run a plain kernel.
+static PyramidKernel launch_pyramid_photo(const PyramidArgs& a, const PhotoArgs& p, hipStream_t s)
+{
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    const bool plan = a.seq_action != nullptr;
+    if (a.remap != nullptr) {
+        const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
+        if (plan) hipLaunchKernelGGL((k_pyramid_photo<true, true>), grid, dim3(256), 0, s, a, p);
+        else hipLaunchKernelGGL((k_pyramid_photo<false, true>), grid, dim3(256), 0, s, a, p);
+        return {DVO_PYRAMID_KERNEL_PHOTO_REMAP, 0, plan ? 1 : 0};
+    }
+    bool vec = a.raw_channels == 1 && a.culls == 2 && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 && ((size_t)tw * th % 4) == 0;
+    const void* wide[4] = {a.raw_rgb, a.dst[0][T], p.gain, plan ? a.ref[0][T] : nullptr};   // the 16-byte accesses (nullptr passes: not accessed)
+    for (const void* q : wide) vec = vec && (reinterpret_cast<uintptr_t>(q) % 16) == 0;
+    if (vec) {
+        const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)a.n_seq);
+        const char* e = getenv("DVO_PHOTO_RESPONSE");
+        const bool lds = !(e && strcmp(e, "global") == 0);
+        if (plan) {
+            if (lds) hipLaunchKernelGGL((k_pyramid_raw4_photo<2, true, true>), grid, dim3(256), 0, s, a, p);
+            else hipLaunchKernelGGL((k_pyramid_raw4_photo<2, true, false>), grid, dim3(256), 0, s, a, p);
+        } else {
+            if (lds) hipLaunchKernelGGL((k_pyramid_raw4_photo<2, false, true>), grid, dim3(256), 0, s, a, p);
+            else hipLaunchKernelGGL((k_pyramid_raw4_photo<2, false, false>), grid, dim3(256), 0, s, a, p);
+        }
+        return {DVO_PYRAMID_KERNEL_PHOTO_RAW4, a.culls, plan ? 1 : 0};
+    }
+    const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
+    if (plan) hipLaunchKernelGGL((k_pyramid_photo<true, false>), grid, dim3(256), 0, s, a, p);
+    else hipLaunchKernelGGL((k_pyramid_photo<false, false>), grid, dim3(256), 0, s, a, p);
+    return {DVO_PYRAMID_KERNEL_PHOTO_SCALAR, 0, plan ? 1 : 0};
+}
+
+PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s, const PhotoArgs* photo)
 {
     PyramidArgs a = a0;
     a.n_seq = n_seq;
+    if (photo != nullptr && photo->gain != nullptr) return launch_pyramid_photo(a, *photo, s);
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
     if (a.remap != nullptr && (a.raw_depth != nullptr || a.src[1] != nullptr)) {   // sensor-depth frames, lens undistortion fused in
         launch_pyramid_remap_depth(a, s);

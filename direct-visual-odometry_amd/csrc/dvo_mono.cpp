@@ -96,7 +96,7 @@ int MonoBatch::init(int n, const float* K, int w, int h, int ring, const dvo_con
 int Undistortion::set(const char* who, const float* Dh, bool per_sequence, int n_seq, const float* K_full, bool per_camera, const Geometry& g,
                       hipStream_t s)
 {
-    if (!Dh) { D.clear(); dev.release(); n_cam = 0; return DVO_OK; }
+    if (!Dh) { D.clear(); dev.release(); n_cam = 0; this->cam_of.clear(); return DVO_OK; }
     const int nd = per_sequence ? n_seq : 1;
     for (int q = 0; q < nd; q++)
         for (int j = 0; j < 5; j++)
@@ -134,6 +134,7 @@ int Undistortion::set(const char* who, const float* Dh, bool per_sequence, int n
     DVO_HIP(hipStreamSynchronize(s));   // (cams_dev and cam_of go out of scope)
     D.resize((size_t)n_seq * 5);
     for (int q = 0; q < n_seq; q++) memcpy(&D[(size_t)q * 5], Dh + (per_sequence ? (size_t)q * 5 : 0), 5 * sizeof(float));
+    this->cam_of = cam_of;
     return DVO_OK;
 }
 
@@ -141,7 +142,15 @@ int MonoBatch::set_distortion(const float* D, bool per_sequence)
 {
     if (latest_id >= 0) { set_error("dvo_batch_set_distortion: the batch has consumed a frame (D is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
-    return und.set("dvo_batch_set_distortion", D, per_sequence, n_seq, K_full.data(), K_full.size() > 9, g, stream);
+    DVO_TRY(und.set("dvo_batch_set_distortion", D, per_sequence, n_seq, K_full.data(), K_full.size() > 9, g, stream));
+    return pho.rebuild(n_seq, g, und, stream);   // (a calibration set before D: its gains move to the remap's source pixels)
+}
+
+int MonoBatch::set_photometric(int n_cal, const float* resp, const float* vign, const int* seq_cal)
+{
+    if (latest_id >= 0) { set_error("dvo_batch_set_photometric: the batch has consumed a frame (the calibration is fixed from the first frame on)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(device));
+    return pho.set("dvo_batch_set_photometric", n_cal, resp, vign, seq_cal, n_seq, g, und, stream);
 }
 
 int MonoBatch::set_initial_depth(const float* depth_host, const float* sigma_host)
@@ -225,10 +234,15 @@ int MonoBatch::queue_depth_update(int frame_id, MapEv* pe)
 int MonoBatch::odometrize(const FrameInput& in)
 {  // system.hpp:44-74 for every sequence
     if (!in.key0() || (in.raw() && in.channels != 1 && in.channels != 3 && in.channels != 4)) { set_error("null device pointer / bad channel count"); return DVO_ERR_BAD_ARGUMENT; }
+    if (pho.enabled() && !in.raw()) {
+        set_error("the batch has a photometric calibration (dvo_batch_set_photometric), which needs the byte: feed raw frames (dvo_batch_odometrize_raw_device / _raw_host)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     FrameInput gin = in;          // mono: gray only
     gin.depth = nullptr; gin.sigma = nullptr; gin.depth16 = nullptr;
     if (und.enabled() && gin.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
     und.apply(gin, n_seq);        // dvo_batch_set_distortion: k_pyramid_remap
+    pho.apply(gin, n_seq);        // dvo_batch_set_photometric: k_pyramid_raw4_photo / k_pyramid_photo
     DVO_TRY(select_device(device));
     const int T = g.top(), tw = g.w[T], th = g.h[T], np = tw * th;
     // Frame::latest_id (frame.cpp:5) advances only once the frame's launches were queued: a call that fails leaves the batch where it
@@ -261,7 +275,7 @@ int MonoBatch::odometrize(const FrameInput& in)
             const PoseSeedArgs sa = guess.args(trk.state.as<SeqState>(), nullptr, DVO_SEQ_RESTART, xi_world.as<float>(), m);
             launch_mono_seed(sa, stream);
         }
-        build_pyramid(ref, gin, stream);
+        build_pyramid(ref, gin, stream, true, nullptr, nullptr, nullptr, &last_build);
         DVO_HIP(hipMemsetAsync(ref_age.p, 0, ref_age.bytes, stream));
         redecimate(ref, ref.depth[T], ref.sigma[T], stream);
         PromoteArgs pa{};
@@ -288,8 +302,8 @@ int MonoBatch::odometrize(const FrameInput& in)
     {   // Frame(gray, K, 3, 2); a plan: the SKIP sequences read no input (k_pyramid<true> / k_pyramid_raw4<, true> copy their keyframe's
         // gray forward, k_pyramid_remap_plan writes nothing)
         TraceRange tr("mono pyramid");
-        if (planned) build_pyramid(frm, gin, stream, true, plan.eff.as<uint8_t>(), &ref);
-        else build_pyramid(frm, gin, stream);
+        if (planned) build_pyramid(frm, gin, stream, true, plan.eff.as<uint8_t>(), &ref, nullptr, &last_build);
+        else build_pyramid(frm, gin, stream, true, nullptr, nullptr, nullptr, &last_build);
     }
     {   // system.hpp:57 (a plan: the TRACK sequences only; before the first call no sequence has a keyframe to track against)
         TraceRange tr("mono track");
@@ -542,6 +556,47 @@ int dvo_batch_set_distortion(dvo_batch* b, const float* D, int per_sequence)
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (!b->mono) { set_error("dvo_batch_set_distortion: needs a mono batch (sensor-depth batches do not undistort)"); return DVO_ERR_BAD_ARGUMENT; }
     return b->mono->set_distortion(D, per_sequence != 0);
+}
+
+int dvo_batch_set_photometric(dvo_batch* b, int n_cal, const float* inv_response, const float* vignette, const int* seq_cal)
+{
+    if (!b) { set_error("dvo_batch_set_photometric: null handle"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->mono) { set_error("dvo_batch_set_photometric: needs a mono batch (sensor-depth batches are not calibrated)"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->mono->set_photometric(n_cal, inv_response, vignette, seq_cal);
+}
+
+int dvo_batch_get_photometric(dvo_batch* b, int* n_cal, int* seq_cal)
+{
+    DVO_NEED_MONO(b);
+    const MonoBatch& M = *b->mono;
+    if (n_cal) *n_cal = M.pho.n_cal;
+    if (seq_cal) {
+        if (M.pho.enabled()) memcpy(seq_cal, M.pho.seq_cal.data(), sizeof(int) * (size_t)M.n_seq);
+        else memset(seq_cal, 0, sizeof(int) * (size_t)M.n_seq);
+    }
+    return DVO_OK;
+}
+
+int dvo_debug_batch_photometric_gain(dvo_batch* b, int seq, float* gain)
+{
+    DVO_NEED_MONO(b);
+    MonoBatch& M = *b->mono;
+    if (!gain || seq < 0 || seq >= M.n_seq) { set_error("dvo_debug_batch_photometric_gain: null output or sequence out of range"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!M.pho.enabled()) { set_error("dvo_debug_batch_photometric_gain: the batch has no photometric calibration"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(M.device));
+    const size_t np = (size_t)M.top_pixels();
+    DVO_HIP(hipMemcpyAsync(gain, M.pho.gain_dev.as<float>() + np * (size_t)M.pho.seq_pair[(size_t)seq], np * sizeof(float), hipMemcpyDeviceToHost, M.stream));
+    DVO_HIP(hipStreamSynchronize(M.stream));
+    return DVO_OK;
+}
+
+int dvo_debug_batch_last_pyramid_kernel(dvo_batch* b, dvo_pyramid_kernel* ran)
+{
+    DVO_NEED_MONO(b);
+    if (!ran) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono->latest_id < 0) return DVO_ERR_NOT_READY;
+    ran->kind = b->mono->last_build.kind; ran->culls = b->mono->last_build.culls; ran->plan = b->mono->last_build.plan;
+    return DVO_OK;
 }
 
 int dvo_batch_get_distortion(dvo_batch* b, float* D, int* enabled)

@@ -196,6 +196,8 @@ EXPORTS = [
     "dvo_op_pyramid_frames",
     "dvo_op_depth_update_batch",
     "dvo_batch_set_robust_median", "dvo_batch_last_robust_log", "dvo_batch_last_robust_histogram", "dvo_op_gn_step_robust_median",
+    "dvo_batch_set_photometric", "dvo_batch_get_photometric", "dvo_vo_set_photometric", "dvo_debug_batch_photometric_gain",
+    "dvo_debug_batch_last_pyramid_kernel",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -240,7 +242,26 @@ KF_FUSION_RECORD_DTYPE = np.dtype([("struct_size", np.int32), ("n_candidates", n
 
 # the kernel a pyramid build ran and the flags of op_pyramid_frames: include/dvo.h
 PYRAMID_KERNEL_SCALAR, PYRAMID_KERNEL_RAW4, PYRAMID_KERNEL_SPLIT, PYRAMID_KERNEL_REMAP = 0, 1, 2, 3
+# ... of a handle with a photometric calibration (MonoBatch.set_photometric)
+PYRAMID_KERNEL_PHOTO_RAW4, PYRAMID_KERNEL_PHOTO_SCALAR, PYRAMID_KERNEL_PHOTO_REMAP = 4, 5, 6
 PYRAMID_ROWS_DECIMATED, PYRAMID_FORCE_WEIGHT_MAPS, PYRAMID_SPLIT = 1, 2, 4
+
+
+def _photometric_arrays(who, n_cal, inv_response, vignette, height, width):
+    """the float32 arrays of a photometric calibration, shape-checked: ([n_cal, 256] or None, [n_cal, H, W] or None)"""
+    r = v = None
+    if inv_response is not None:
+        r = f32(inv_response).reshape(-1, 256) if np.ndim(inv_response) == 1 else f32(inv_response)
+        if r.shape != (n_cal, 256):
+            raise ValueError("%s: inv_response must be float[256] or float[%d, 256], got shape %s" % (who, n_cal, r.shape))
+    if vignette is not None:
+        v = f32(vignette)
+        if v.ndim == 2:
+            v = v.reshape((1,) + v.shape)
+        if v.shape != (n_cal, height, width):
+            raise ValueError("%s: vignette must be float[%d, %d] or float[%d, %d, %d], got shape %s"
+                             % (who, height, width, n_cal, height, width, v.shape))
+    return r, v
 
 
 class PyramidKernel(C.Structure):
@@ -255,6 +276,12 @@ class PyramidKernel(C.Structure):
             return "k_pyramid_raw4<%d, %s>" % (self.culls, plan)
         if self.kind == PYRAMID_KERNEL_SPLIT:
             return "k_pyramid_raw4_coarse<%d> + k_pyramid_raw4_rest<%d>" % (self.culls, self.culls)
+        if self.kind == PYRAMID_KERNEL_PHOTO_RAW4:
+            return "k_pyramid_raw4_photo<%d, %s>" % (self.culls, plan)
+        if self.kind == PYRAMID_KERNEL_PHOTO_SCALAR:
+            return "k_pyramid_photo<%s, false>" % plan
+        if self.kind == PYRAMID_KERNEL_PHOTO_REMAP:
+            return "k_pyramid_photo<%s, true>" % plan
         return "remap"
 
 
@@ -798,6 +825,12 @@ class VisualOdometry:
             raise ValueError("setDistortion: expected float[5], got shape %s" % (d.shape,))
         _check(lib().dvo_vo_set_distortion(self._p, fp(d)))
 
+    def set_photometric(self, inv_response=None, vignette=None):
+        """Photometric calibration of every raw mono frame: inv_response float [256] in gray units (None: i / 255) and vignette
+        float [H, W] (None: 1); both None clears.  Before the first frame; from then on feed odometrizeRaw (dvo_vo_set_photometric)."""
+        r, v = _photometric_arrays("set_photometric", 1, inv_response, vignette, self.height, self.width)
+        _check(lib().dvo_vo_set_photometric(self._p, fp(r) if r is not None else None, fp(v) if v is not None else None))
+
     def odometrize(self, gray):
         g = f32(gray); T = np.zeros(16, np.float32); key = C.c_int(0)
         _check(lib().dvo_vo_odometrize(self._p, fp(g), fp(T), C.byref(key)))
@@ -1302,6 +1335,45 @@ class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineB
         d = np.zeros((self.n_seq, 5), np.float32); en = C.c_int(0)
         _check(lib().dvo_batch_get_distortion(self._p, fp(d), C.byref(en)))
         return d, bool(en.value)
+
+    def set_photometric(self, inv_response=None, vignette=None, seq_cal=None):
+        """Photometric calibration of every raw frame (dvo_batch_set_photometric): inv_response float [n_cal, 256] (or [256]) in gray
+        units, None = i / 255; vignette float [n_cal, H, W] (or [H, W]), None = 1, an entry <= 0 or not finite masks the pixel; seq_cal
+        int [n_seq] = the calibration of each sequence, None = 0 for all.  gray = inv_response[g8] * (1 / vignette), on the luma of a
+        colour frame.  All None clears.  Before the first frame; from then on only raw frames are accepted."""
+        if inv_response is None and vignette is None:
+            _check(lib().dvo_batch_set_photometric(self._p, 0, None, None, None))
+            return
+        first = inv_response if inv_response is not None else vignette
+        lead = np.ndim(first) - (1 if inv_response is not None else 2)
+        n_cal = int(np.shape(first)[0]) if lead == 1 else 1
+        r, v = _photometric_arrays("set_photometric", n_cal, inv_response, vignette, self.height, self.width)
+        sc = None
+        if seq_cal is not None:
+            sc = np.ascontiguousarray(seq_cal, np.int32)
+            if sc.shape != (self.n_seq,):
+                raise ValueError("set_photometric: seq_cal must be int[%d], got shape %s" % (self.n_seq, sc.shape))
+        _check(lib().dvo_batch_set_photometric(self._p, n_cal, fp(r) if r is not None else None, fp(v) if v is not None else None,
+                                               sc.ctypes.data_as(C.c_void_p) if sc is not None else None))
+
+    def get_photometric(self):
+        """(n_cal, seq_cal int32 [n_seq]): the number of calibrations in use (0: none) and each sequence's."""
+        n = C.c_int(0); sc = np.zeros(self.n_seq, np.int32)
+        _check(lib().dvo_batch_get_photometric(self._p, C.byref(n), sc.ctypes.data_as(C.c_void_p)))
+        return n.value, sc
+
+    def photometric_gain(self, seq):
+        """Diagnostic: the gain table sequence `seq` reads, float32 [H/4, W/4]: 1 / vignette at each kept pixel's source, -1 where the
+        pixel is masked or outside the undistorted image (dvo_debug_batch_photometric_gain; synchronises)."""
+        g = np.zeros((self.height // 4, self.width // 4), np.float32)
+        _check(lib().dvo_debug_batch_photometric_gain(self._p, int(seq), fp(g)))
+        return g
+
+    def last_pyramid_kernel(self):
+        """Diagnostic: the PyramidKernel (kind, culls, plan) the last frame build launched (dvo_debug_batch_last_pyramid_kernel)."""
+        k = PyramidKernel()
+        _check(lib().dvo_debug_batch_last_pyramid_kernel(self._p, C.byref(k)))
+        return k
 
     def setInitialDepthDevice(self, depth_ptr, sigma_ptr):
         _check(lib().dvo_batch_set_initial_depth_device(self._p, C.c_void_p(depth_ptr), C.c_void_p(sigma_ptr)))

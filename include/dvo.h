@@ -102,6 +102,13 @@ int dvo_vo_odometrize_depth(dvo_vo* vo, const float* gray, const float* depth, c
  * handle its D again).  A handle with D set refuses dvo_vo_odometrize_depth, dvo_vo_odometrize_depth_raw and dvo_vo_init_keyframe
  * with DVO_ERR_BAD_ARGUMENT (sensor-depth frames are not undistorted). */
 int dvo_vo_set_distortion(dvo_vo* vo, const float D[5]);
+/* Photometric calibration of every raw mono frame (dvo_batch_set_photometric with one calibration and one sequence, same rules and
+ * the same arithmetic): inv_response [256] or NULL (the default scale), vignette [height][width] or NULL (1); both NULL clears.
+ * dvo_vo_odometrize_raw then gives the bits of a one-sequence calibrated mono batch, on the staged and the copied upload path alike.
+ * Before the first frame only (-> DVO_ERR_NOT_READY after one, nothing changed; dvo_vo_load is not a frame and the calibration is
+ * not stored: give a restored handle its calibration again); with or without dvo_vo_set_distortion, in either order.  Calibration needs the byte: a handle with a calibration refuses dvo_vo_odometrize and the sensor-depth entry points
+ * (dvo_vo_odometrize_depth, dvo_vo_odometrize_depth_raw, dvo_vo_init_keyframe) with DVO_ERR_BAD_ARGUMENT. */
+int dvo_vo_set_photometric(dvo_vo* vo, const float inv_response[256] /* or NULL */, const float* vignette /* [h][w] or NULL */);
 
 /* FrameHistory (include/system/frame.hpp:146-188): keyframe / depth-map access. index 0 = oldest. */
 int dvo_vo_keyframe_count(const dvo_vo* vo);
@@ -367,6 +374,42 @@ int dvo_batch_keyframe_get(dvo_batch* b, int seq, int level, float* gray, float*
  * get: D [n_seq][5] as set (zeros when none; may be NULL) and *enabled = 1 when set (may be NULL). */
 int dvo_batch_set_distortion(dvo_batch* b, const float* D, int per_sequence);
 int dvo_batch_get_distortion(dvo_batch* b, float* D /*[n_seq][5]*/, int* enabled);
+/* Photometric calibration of every raw frame of a mono batch: the camera's inverse response (a 256-entry table) and its vignette
+ * (a per-pixel attenuation map), the TUM monoVO convention (pcalib.txt, vignette.png), applied inside the pyramid kernel where each
+ * kept pixel is touched once, as a byte.  n_cal calibrations and, per sequence, which one it uses; host memory, copied before the call
+ * returns.  n_cal = 0 clears it; both arrays NULL with n_cal = 0 is the only way to turn it off.
+ * For every pixel the library keeps from a raw frame of sequence s with calibration c = seq_cal[s]:
+ *     g8   = the byte (1 channel) or the fixed-point luma of dvo_op_ingest (3 / 4 channels)          -- unchanged
+ *     p    = the frame's own pixel this kept pixel comes from: (x << 2, y << 2) without D, the remap table's source index with D
+ *            (index -1 stays DVO_INVALID)
+ *     gray = inv_response[c][g8] * (1.0f / vignette[c][p])    -- float32: one IEEE division (done once, at set time), one multiply,
+ *            no contraction
+ *     gray = DVO_INVALID  where vignette[c][p] is not finite or <= 0
+ *  - inv_response is in the library's gray units ([0, 1]).  NULL means (float)i * (float)(1.0 / 255.0), which is dvo_op_ingest's scale.
+ *  - vignette NULL means 1.  A denormal entry is positive and finite: its gain is +inf, and the product is what IEEE gives (inf, or
+ *    NaN for a zero response), which every consumer treats as it treats such a value in a float frame.
+ *  - With a multi-channel frame the response is applied to the luma, not per channel.
+ *  - Everything downstream is the existing pipeline on that gray: sequence s gives, bit for bit, the world poses, keyframe flags,
+ *    keyframe maps and mono stats of a plain handle fed the float frames `gray` above.
+ *  - A non-positive vignette entry doubles as a static per-camera mask (a bonnet, a lens hood): the pixel is DVO_INVALID in every
+ *    frame of the sequence, so it is neither tracked on nor mapped.
+ *  - Exposure times are not part of it: a known per-frame exposure is a gain, which dvo_batch_set_affine_rows in GIVEN mode takes.
+ *  - Before the first frame only: a call after the batch has consumed a frame -> DVO_ERR_NOT_READY, nothing changed.
+ *  - DVO_ERR_BAD_ARGUMENT, nothing changed: a NULL handle, a sensor-depth batch, n_cal < 0, both arrays NULL with n_cal > 0, an index
+ *    outside [0, n_cal), or a response entry that is not finite or is negative.  dvo_last_error names the first bad calibration or
+ *    sequence.
+ *  - It works with or without dvo_batch_set_distortion, set in either order: the tables that result are the same (one float table
+ *    of gains per distinct (calibration, undistortion camera) pair at top-level resolution, (width/4) x (height/4), indexed by the
+ *    kept pixel; without D the host entry points keep uploading only the rows the pyramid keeps).
+ *  - Calibration needs the byte: on a handle with a calibration the float-feed entry points (dvo_batch_odometrize_device,
+ *    dvo_batch_odometrize_host) return DVO_ERR_BAD_ARGUMENT.
+ *  - SKIP / RESTART plans, per-sequence cameras, pose guesses, robust weights, affine brightness and track quality need no knowledge
+ *    of it.  A batch that never calls the setter runs exactly the launches it runs without this entry point.
+ * get: *n_cal (0 when none; may be NULL) and seq_cal [n_seq] as set (zeros when none; may be NULL). */
+int dvo_batch_set_photometric(dvo_batch* b, int n_cal, const float* inv_response /* [n_cal][256], or NULL */,
+                              const float* vignette /* [n_cal][height][width], or NULL */,
+                              const int* seq_cal /* [n_seq] in [0, n_cal), or NULL = 0 for every sequence */);
+int dvo_batch_get_photometric(dvo_batch* b, int* n_cal, int* seq_cal /* [n_seq], may be NULL */);
 /* Per-sequence counters of a mono batch.  `clamped_pixels` makes the one deviation of the ring from the reference's unbounded
  * FrameHistory (frame.hpp:146-188) visible: a pixel older than the `ring_keyframes` retained keyframes is searched against the
  * oldest retained one instead of the keyframe it was born in (mapper.cpp:99-101, frame_history[age]); the count is cumulative and
@@ -871,6 +914,11 @@ int dvo_op_pyramid(int dev, const float* gray, const float* depth, const float* 
 #define DVO_PYRAMID_KERNEL_RAW4   1
 #define DVO_PYRAMID_KERNEL_SPLIT  2
 #define DVO_PYRAMID_KERNEL_REMAP  3
+/* the kernels of a handle with a photometric calibration (dvo_batch_set_photometric; never from dvo_op_pyramid_frames):
+ * k_pyramid_raw4_photo<2, plan>, k_pyramid_photo<plan, false> and, with lens undistortion, k_pyramid_photo<plan, true> */
+#define DVO_PYRAMID_KERNEL_PHOTO_RAW4   4
+#define DVO_PYRAMID_KERNEL_PHOTO_SCALAR 5
+#define DVO_PYRAMID_KERNEL_PHOTO_REMAP  6
 #define DVO_PYRAMID_ROWS_DECIMATED    1
 #define DVO_PYRAMID_FORCE_WEIGHT_MAPS 2
 #define DVO_PYRAMID_SPLIT             4
@@ -892,6 +940,12 @@ typedef struct dvo_pyramid_frames_args {
 } dvo_pyramid_frames_args;
 int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
                           float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran);
+/* Debug readers of a mono batch's photometric calibration (host memory; both synchronise the batch's stream).
+ * photometric_gain: the gain table sequence `seq` reads, [h_top][w_top]: 1.0f / vignette at each kept pixel's source, -1.0f where the
+ * pixel is masked (vignette not finite or <= 0) or the remap's index is -1.  DVO_ERR_NOT_READY without a calibration.
+ * last_pyramid_kernel: what the last frame build of the batch launched (DVO_ERR_NOT_READY before the first frame). */
+int dvo_debug_batch_photometric_gain(dvo_batch* b, int seq, float* gain /* [h_top][w_top] */);
+int dvo_debug_batch_last_pyramid_kernel(dvo_batch* b, dvo_pyramid_kernel* ran);
 /* Track::optimize, src/track/optimize.cpp:10-99: one Gauss-Newton step on one level.
  * H = upper triangle of sum J^T J (21), g = sum J^T (w r) (6).  mask (optional, w*h bytes). */
 typedef struct dvo_gn_result {

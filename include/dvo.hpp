@@ -66,6 +66,9 @@ public:
     // Loader::getNormalizedUndistortedImages (src/core/loader.cpp:15-42) fused into odometrize / odometrizeRaw: D = (k1, k2, p1, p2, k3)
     // with the creation K, before the first frame (dvo_vo_set_distortion)
     void setDistortion(const std::array<float, 5>& D) { check(dvo_vo_set_distortion(vo_, D.data())); }
+    // photometric calibration of every raw mono frame, before the first one: invResponse[256] (nullptr: i / 255), vignette
+    // [height][width] (nullptr: 1); both nullptr clears (dvo_vo_set_photometric).  From then on feed raw frames.
+    void setPhotometric(const float* invResponse, const float* vignette) { check(dvo_vo_set_photometric(vo_, invResponse, vignette)); }
 
     // cv::Mat1f odometrize(const cv::Mat1f& gray), system.hpp:44-74: 4x4 world pose exp(m_xi)
     Mat4 odometrize(const float* gray, bool* is_keyframe = nullptr)
@@ -365,6 +368,13 @@ public:
         check(dvo_batch_get_distortion(b_, D[0].data(), &enabled));
         if (!enabled) D.clear();
         return D;
+    }
+    // photometric calibration of every raw frame, before the first one: nCal inverse-response tables [nCal][256] (nullptr: i / 255)
+    // and vignettes [nCal][height][width] (nullptr: 1), seqCal[n_seq] picks each sequence's (nullptr: 0); nCal = 0 clears
+    // (dvo_batch_set_photometric).  From then on only raw frames are accepted.
+    void setPhotometric(int nCal, const float* invResponse, const float* vignette, const int* seqCal = nullptr)
+    {
+        check(dvo_batch_set_photometric(b_, nCal, invResponse, vignette, seqCal));
     }
     void odometrizeDevice(const float* gray) { check(dvo_batch_odometrize_device(b_, gray)); }
     void odometrizeRawDevice(const uint8_t* rgb, int channels) { check(dvo_batch_odometrize_raw_device(b_, rgb, channels)); }
