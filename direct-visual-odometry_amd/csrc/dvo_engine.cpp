@@ -252,6 +252,15 @@ static PyramidArgs frame_args(const FrameSet& fs, bool rows_decimated)
     return a;
 }
 
+// the gray side of a build from raw frames: the bytes, their channel count, k_ingest's scale and the gray pyramid they go to
+static PyramidArgs raw_gray_args(const FrameSet& fs, const FrameInput& in, bool rows_decimated)
+{
+    PyramidArgs a = frame_args(fs, rows_decimated);
+    a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);
+    for (int l = 0; l < fs.g.levels; l++) a.dst[0][l] = fs.gray[l];
+    return a;
+}
+
 // the arguments of a build from float maps (the caller adds the plan's copy-forward and, optionally, the remap)
 static PyramidArgs float_args(FrameSet& fs, const float* gray_dev, const float* depth_dev, const float* sigma_dev, bool keep_sigma,
                               bool rows_decimated)
@@ -283,9 +292,7 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     PyramidKernel& k = ran ? *ran : none;
     if (in.photo.gain) {   // raw mono frame of a calibrated handle (the callers refuse float frames): the k_pyramid*_photo kernels, gray
                            // only; with a remap whole frames and k_pyramid_remap_plan's SKIP, else k_pyramid's rows and copy-forward
-        PyramidArgs a = frame_args(fs, in.remap ? false : in.rows_decimated);
-        a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);
-        for (int l = 0; l < fs.g.levels; l++) a.dst[0][l] = fs.gray[l];
+        PyramidArgs a = raw_gray_args(fs, in, in.remap ? false : in.rows_decimated);
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         if (in.remap) a.seq_action = seq_action;
         else plan_copy(a, seq_action, copy_from);
@@ -295,10 +302,8 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     }
     if (in.remap && !in.has_depth()) {   // mono frame, lens undistortion fused in (k_pyramid_remap): gray only, whole frames
                                          // (a mono plan: k_pyramid_remap_plan, whose SKIP sequences write nothing; copy_from is not used)
-        PyramidArgs a = frame_args(fs, false);
+        PyramidArgs a = raw_gray_args(fs, in, false);
         a.src[0] = in.gray;
-        a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_gray_scale = (float)(1.0 / 255.0);   // (k_ingest's scale)
-        for (int l = 0; l < fs.g.levels; l++) a.dst[0][l] = fs.gray[l];
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         a.seq_action = seq_action;
         fs.sigma_by_validity = false;
@@ -315,13 +320,11 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         k = launch_pyramid(a, fs.n_seq, s);
         return false;
     }
-    PyramidArgs a = frame_args(fs, in.rows_decimated);
-    a.raw_rgb = in.rgb; a.raw_channels = in.channels; a.raw_depth = in.depth16;
-    a.raw_gray_scale = (float)(1.0 / 255.0); a.raw_depth_scale = in.depth_scale;
+    PyramidArgs a = raw_gray_args(fs, in, in.rows_decimated);
+    a.raw_depth = in.depth16; a.raw_depth_scale = in.depth_scale;
     a.raw_sigma_valid = 0.1f; a.raw_sigma_invalid = 1.0f; a.raw_invalidate_gray = 1;   // transform.cpp:60-76
     const bool dep = in.depth16 != nullptr;
     for (int l = 0; l < fs.g.levels; l++) {
-        a.dst[0][l] = fs.gray[l];
         a.dst[1][l] = dep ? fs.depth[l] : nullptr;
         a.dst[2][l] = (dep && keep_sigma) ? fs.sigma[l] : nullptr;
     }

@@ -665,8 +665,14 @@ void launch_regularize_redecimate_plan(const RegDecArgs& a, const MonoStartArgs&
 struct PyramidKernel {
     int kind = DVO_PYRAMID_KERNEL_SCALAR, culls = 0, plan = 0;
 };
+// The pyramid-build family: nine kernel templates, 24 instances, over one set of device helpers (raw_luma8,
+// raw_convert, RawWords, walk_levels, seq_skips) and one set of launcher helpers (pyramid_raw4_possible, aligned16, pyramid_grid,
+// with_flag, with_culls).  launch_pyramid picks: with a remap k_pyramid_remap_depth<4 or 1, plan> (depth present) or
+// k_pyramid_remap / k_pyramid_remap_plan (mono); else k_pyramid_raw4<culls, plan> where the four-pixel build is possible
+// (pyramid_raw4_possible: 1-channel bytes, culls 1 or 2, whole groups of four kept pixels, 16-byte aligned input and tops), else
+// k_pyramid<plan>.
 // photo (optional, photo->gain set): raw mono frames of a calibrated handle -- k_pyramid_raw4_photo<2, plan> (kind _PHOTO_RAW4) where
-// k_pyramid_raw4's conditions hold at culls 2 and the gain rows can be read 16 bytes at a time, else k_pyramid_photo<plan, remap>
+// the four-pixel build is possible at culls 2 and the gain rows can be read 16 bytes at a time, else k_pyramid_photo<plan, remap>
 // (_PHOTO_SCALAR, or _PHOTO_REMAP with a.remap).  Without it: exactly the kernels chosen before there was a calibration.
 PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s, const PhotoArgs* photo = nullptr);
 // k_photometric_map: gain[p][y][x] of pair p = (cal, cam) = 1 / vignette[cal][source of kept pixel (x, y)], the source being
@@ -675,8 +681,9 @@ void launch_photometric_map(const float* vignette, const int* pairs /*[n_pair][2
                             const int* remap, float* gain, hipStream_t s);
 // The split build: launch_pyramid_coarse (k_pyramid_raw4_coarse: the gray maps below the top level) and
 // launch_pyramid_rest (k_pyramid_raw4_rest: everything else) together write what launch_pyramid writes.  pyramid_can_split: the
-// arguments are those of a plain raw build (1-channel u8 gray + u16 depth, culls 1 or 2, no plan, no remap) with the alignment the
-// two kernels' 16-byte accesses need.
+// arguments are those of a plain raw build with depth (no plan, no remap) for which the four-pixel build is possible
+// (pyramid_raw4_possible: stage B), and stage A's own conditions hold: eight top-level pixels per thread, level top - 1 exactly half
+// as wide, its map 16-byte aligned.
 bool pyramid_can_split(const PyramidArgs& a);
 void launch_pyramid_coarse(const PyramidArgs& a, int n_seq, hipStream_t s);
 void launch_pyramid_rest(const PyramidArgs& a, int n_seq, hipStream_t s);

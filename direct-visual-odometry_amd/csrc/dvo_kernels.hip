@@ -8,6 +8,7 @@
 
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
 
 #include "dvo_kernels.h"
@@ -134,6 +135,110 @@ __device__ __forceinline__ void split_index(int i, int w, float inv_w, int& x, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// Building blocks of the pyramid-build kernels: what the kernels of the family below share, stated once.  A
+// kernel whose instruction stream is pinned (tests/golden/isa_*.json) keeps written out each piece under whose helper the stream
+// moves, and says so in one line: all of k_pyramid and k_pyramid_raw4, the walk of k_pyramid_remap.
+// ------------------------------------------------------------------------------------------------
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef float f4 __attribute__((ext_vector_type(4)));
+
+// The 8-bit luma of pixel `off` of a raw frame: the byte itself, or k_ingest's fixed-point weights of R, G and B (A is not read)
+__device__ __forceinline__ unsigned raw_luma8(const PyramidArgs& a, size_t off)
+{
+    unsigned g8;
+    if (a.raw_channels == 1) {
+        g8 = __builtin_nontemporal_load(a.raw_rgb + off);
+    } else {
+        const uint8_t* p = a.raw_rgb + off * (size_t)a.raw_channels;
+        g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
+    }
+    return g8;
+}
+
+// k_ingest's conversion of one raw pixel with depth (the same float operations): luma g8 and depth word d to gray, depth and
+// sigma; a pixel without a depth reading has no gray either (raw_invalidate_gray, transform.cpp:60-76).  The argument block by
+// value: through a reference the loads of its five constants repeat per pixel (k_pyramid_raw4_rest<2>: +2 VGPRs).
+struct RawPixel { float gray, depth, sigma; };
+__device__ __forceinline__ RawPixel raw_convert(const PyramidArgs a, unsigned g8, unsigned d)
+{
+    RawPixel p;
+    p.gray = (float)g8 * a.raw_gray_scale;
+    if (a.raw_invalidate_gray && d == 0) p.gray = kInvalid;
+    p.depth = (float)d * a.raw_depth_scale;
+    p.sigma = d > 0 ? a.raw_sigma_valid : a.raw_sigma_invalid;
+    return p;
+}
+
+// The packed words of the 4 << SHIFT consecutive pixels of one row that a thread of a four-pixel kernel reads from 1-channel u8
+// gray and u16 depth, 16 bytes per load (8 for the two gray words of SHIFT 1); kept pixel k of the thread is pixel k << SHIFT.
+template <int SHIFT>
+struct RawWords {
+    static constexpr int GW = 1 << SHIFT;   // 32-bit words of gray bytes
+    unsigned g[GW], d[2 * GW];
+    __device__ __forceinline__ void load_gray(const PyramidArgs& a, size_t off)
+    {
+        if constexpr (SHIFT == 1) {
+            const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(a.raw_rgb + off));
+            g[0] = v.x; g[1] = v.y;
+        } else {
+            const u32x4* gp = reinterpret_cast<const u32x4*>(a.raw_rgb + off);
+#pragma unroll
+            for (int q = 0; q < GW / 4; q++) {
+                const u32x4 v = __builtin_nontemporal_load(gp + q);
+                g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
+            }
+        }
+    }
+    __device__ __forceinline__ void load_depth(const PyramidArgs& a, size_t off)
+    {
+        const u32x4* dp = reinterpret_cast<const u32x4*>(a.raw_depth + off);
+#pragma unroll
+        for (int q = 0; q < GW / 2; q++) {
+            const u32x4 v = __builtin_nontemporal_load(dp + q);
+            d[4 * q] = v.x; d[4 * q + 1] = v.y; d[4 * q + 2] = v.z; d[4 * q + 3] = v.w;
+        }
+    }
+    __device__ __forceinline__ unsigned gray8(int k) const { const int si = k << SHIFT; return (g[si >> 2] >> ((si & 3) * 8)) & 0xffu; }
+    __device__ __forceinline__ unsigned depth16(int k) const { const int si = k << SHIFT; return (d[si >> 1] >> ((si & 1) * 16)) & 0xffffu; }
+};
+
+// The level rule: level t below a thread's own level keeps the pixels whose coordinates are multiples of 2^t.  The thread owns
+// pixels (x0 .. x0 + PPT - 1, y) of level n - 1; f(l, o, k) runs for every level l = n - 1 - t, T0 <= t < n, that keeps its pixel
+// k, with o the offset of that pixel in level l of sequence seq.  T0 = 1: the thread stores its own level itself (16-byte stores).
+template <int PPT, int T0, class F>
+__device__ __forceinline__ void walk_levels(const PyramidArgs& a, int n, int seq, int x0, int y, F&& f)
+{
+    for (int t = T0; t < n; t++) {
+        const int msk = (1 << t) - 1;
+        if constexpr (PPT == 1) {
+            if ((x0 & msk) | (y & msk)) break;
+            const int l = n - 1 - t, lx = x0 >> t, ly = y >> t;
+            if (lx >= a.w[l] || ly >= a.h[l]) continue;   // (a level of odd size has fewer pixels than its parent's even coordinates)
+            f(l, (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx, 0);
+        } else {
+            if (y & msk) break;
+            const int l = n - 1 - t, ly = y >> t;
+            if (ly >= a.h[l]) continue;
+#pragma unroll
+            for (int k = 0; k < PPT; k++) {
+                const int x = x0 + k;
+                if (x & msk) continue;
+                const int lx = x >> t;
+                if (lx >= a.w[l]) continue;
+                f(l, (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx, k);
+            }
+        }
+    }
+}
+
+// The DVO_SEQ_SKIP rule of a planned build (PyramidArgs::seq_action).  The sequence comes from blockIdx.y/z, so the answer is
+// uniform per workgroup.  A build with a reference set copies forward: the thread takes the reference's top-level values in
+// place of the ones it would build and stores them as a build does (lower levels through pass_valid, which is what the
+// reference's build stored there; wgt copied level by level).  A mono build with a remap has no reference set and writes nothing.
+__device__ __forceinline__ bool seq_skips(const PyramidArgs& a, int seq) { return a.seq_action[seq] == DVO_SEQ_SKIP; }
+
+// ------------------------------------------------------------------------------------------------
 // k_pyramid: System::Frame pyramid (frame.hpp:91-117, frame.cpp:16-37) = nearest-neighbour decimation
 // (Convert::cullImage, convert.cpp:7-20) of up to three maps, all levels in ONE launch.
 // One thread per TOP-level pixel reads src(x<<culls, y<<culls) once and writes every level it lands on
@@ -151,7 +256,7 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
     if constexpr (PLAN) {
-        if (a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy-forward: every value this thread's build would write, none of its input
+        if (a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy_forward<1> written out: under the helper the pinned stream moves
             const int T = a.levels - 1;
             const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x;
             bool have[3];
@@ -182,6 +287,7 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     float raw[3] = {0.0f, 0.0f, 0.0f};
     bool have[3];
     if (a.raw_rgb != nullptr) {  // raw sensor frame: convert exactly as k_ingest does (same float operations), only the kept pixels
+        // raw_luma8 and raw_convert written out: under either helper the pinned stream moves
         unsigned g8;
         if (a.raw_channels == 1) {
             g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
@@ -206,9 +312,9 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
     }
     // the reference-frame constants of k_prep_ref, written while depth and sigma are in registers (needs both maps)
     const bool prep = a.wgt[0] != nullptr && have[1] && have[2];
-    for (int t = 0; t < a.levels; t++) {
+    for (int t = 0; t < a.levels; t++) {   // walk_levels<1, 0> written out: under the helper the pinned stream moves
         const int msk = (1 << t) - 1;
-        if ((x & msk) | (y & msk)) break;  // level t below the top keeps pixels whose coordinates are multiples of 2^t
+        if ((x & msk) | (y & msk)) break;
         const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
         if (lx >= a.w[l] || ly >= a.h[l]) continue;
         const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
@@ -230,6 +336,20 @@ __global__ void __launch_bounds__(256) k_pyramid(PyramidArgs a)
 // k_pyramid does.  The same operations as k_undistort followed by k_pyramid: bit-identical, and no undistorted frame is stored.
 // The table is read with plain loads (it is shared by every sequence of the camera and stays in L2), the frame and the levels
 // with k_pyramid's nontemporal accesses.  The input holds whole frames (src_img_rows = src_h): the gather reads any row.
+// remap_gather_gray is that gather, shared with k_pyramid_remap_plan.
+__device__ __forceinline__ float remap_gather_gray(const PyramidArgs& a, int seq, int tw, int th, int x, int y)
+{
+    const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
+    const int si = a.remap[(size_t)cam * tw * th + (size_t)y * tw + x];
+    float raw = kInvalid;
+    if (si >= 0) {
+        const size_t src_off = (size_t)seq * a.src_w * a.src_h + (size_t)si;
+        if (a.raw_rgb != nullptr) raw = (float)raw_luma8(a, src_off) * a.raw_gray_scale;
+        else raw = __builtin_nontemporal_load(a.src[0] + src_off);
+    }
+    return raw;
+}
+
 __global__ void __launch_bounds__(256) k_pyramid_remap(PyramidArgs a)
 {
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
@@ -238,25 +358,8 @@ __global__ void __launch_bounds__(256) k_pyramid_remap(PyramidArgs a)
     if (i >= tw * th || seq >= a.n_seq) return;
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
-    const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
-    const int si = a.remap[(size_t)cam * tw * th + (size_t)y * tw + x];
-    float raw = kInvalid;
-    if (si >= 0) {
-        const size_t src_off = (size_t)seq * a.src_w * a.src_h + (size_t)si;
-        if (a.raw_rgb != nullptr) {
-            unsigned g8;
-            if (a.raw_channels == 1) {
-                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
-            } else {
-                const uint8_t* p = a.raw_rgb + src_off * (size_t)a.raw_channels;
-                g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
-            }
-            raw = (float)g8 * a.raw_gray_scale;
-        } else {
-            raw = __builtin_nontemporal_load(a.src[0] + src_off);
-        }
-    }
-    for (int t = 0; t < a.levels; t++) {
+    const float raw = remap_gather_gray(a, seq, tw, th, x, y);
+    for (int t = 0; t < a.levels; t++) {   // walk_levels<1, 0> written out: under the helper the pinned stream moves
         const int msk = (1 << t) - 1;
         if ((x & msk) | (y & msk)) break;
         const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
@@ -266,45 +369,23 @@ __global__ void __launch_bounds__(256) k_pyramid_remap(PyramidArgs a)
     }
 }
 
-// k_pyramid_remap_plan: k_pyramid_remap in a planned mono call (dvo_batch_set_mono_actions), with one line more: the workgroups of
-// a sequence whose effective action is DVO_SEQ_SKIP return at once.  Its slot of the input is never read and its slice of the frame
-// set is left as it was: nothing downstream reads the frame of a sequence that does not track or start.  (A separate kernel rather
-// than a template parameter: k_pyramid_remap keeps its instruction stream, tests/golden/isa_pyramid_undistort.json.)
+// k_pyramid_remap_plan: k_pyramid_remap in a planned mono call (dvo_batch_set_mono_actions): the workgroups of a DVO_SEQ_SKIP
+// sequence return at once.  Its slot of the input is never read and its slice of the frame set is left as it was: nothing
+// downstream reads the frame of a sequence that does not track or start.  The same gather, then the walk through the helper; a
+// kernel of its own because k_pyramid_remap's stream is pinned and moves under any shared body (by reference or by value).
 __global__ void __launch_bounds__(256) k_pyramid_remap_plan(PyramidArgs a)
 {
     const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
     const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
     const int i = (int)blockIdx.x * 256 + threadIdx.x;
     if (i >= tw * th || seq >= a.n_seq) return;
-    if (a.seq_action[seq] == DVO_SEQ_SKIP) return;   // (uniform per workgroup)
+    if (seq_skips(a, seq)) return;
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
-    const int cam = load_seq_entry(a.remap_cam, seq);   // (uniform per workgroup: one scalar load)
-    const int si = a.remap[(size_t)cam * tw * th + (size_t)y * tw + x];
-    float raw = kInvalid;
-    if (si >= 0) {
-        const size_t src_off = (size_t)seq * a.src_w * a.src_h + (size_t)si;
-        if (a.raw_rgb != nullptr) {
-            unsigned g8;
-            if (a.raw_channels == 1) {
-                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
-            } else {
-                const uint8_t* p = a.raw_rgb + src_off * (size_t)a.raw_channels;
-                g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
-            }
-            raw = (float)g8 * a.raw_gray_scale;
-        } else {
-            raw = __builtin_nontemporal_load(a.src[0] + src_off);
-        }
-    }
-    for (int t = 0; t < a.levels; t++) {
-        const int msk = (1 << t) - 1;
-        if ((x & msk) | (y & msk)) break;
-        const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
-        if (lx >= a.w[l] || ly >= a.h[l]) continue;
-        const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
-        __builtin_nontemporal_store((t == 0 && a.culls == 0) ? raw : pass_valid(raw), a.dst[0][l] + o);
-    }
+    const float raw = remap_gather_gray(a, seq, tw, th, x, y);
+    walk_levels<1, 0>(a, a.levels, seq, x, y, [&](int l, size_t o, int) {
+        __builtin_nontemporal_store((l == a.levels - 1 && a.culls == 0) ? raw : pass_valid(raw), a.dst[0][l] + o);
+    });
 }
 
 // k_pyramid_raw4: the raw-sensor form of k_pyramid for 1-channel u8 gray (+ u16 depth) with CULLS = 1 or 2, four kept pixels
@@ -312,8 +393,8 @@ __global__ void __launch_bounds__(256) k_pyramid_remap_plan(PyramidArgs a)
 // half-empty sectors); here a thread owns 4 consecutive top-level pixels = 4 << CULLS source pixels of one row, fetched by one or
 // two dwordx2/x4 loads, and writes its four top-level values per map as one dwordx4 store.  Same conversions, same float
 // operations as k_ingest + k_pyramid: bit-identical (tests/test_frontend_and_eval.py).
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
+// RawWords, raw_convert, walk_levels<4, 1> and the copy-forward written out: under each helper the pinned stream moves (DESIGN.md
+// §32).  k_pyramid_raw4_rest below is this kernel's plain build in terms of them.
 template <int CULLS, bool PLAN>
 __global__ void __launch_bounds__(256) k_pyramid_raw4(PyramidArgs a)
 {
@@ -466,33 +547,18 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4_photo(PyramidArgs a, Photo
     const int x0 = xg << 2;
     const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x0;
     f4 top;
-    if (PLAN && a.seq_action[seq] == DVO_SEQ_SKIP) {   // copy-forward (k_pyramid_raw4<, true>): the keyframe's four top-level values
+    if (PLAN && seq_skips(a, seq)) {   // copy-forward: the keyframe's four top-level values
         top = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.ref[0][a.levels - 1] + ot));
     } else {
         const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + ((size_t)x0 << CULLS);
-        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.raw_rgb + src_off));
+        RawWords<CULLS> in;
+        in.load_gray(a, src_off);
         const f4 gn = *reinterpret_cast<const f4*>(p.gain + (size_t)load_seq_entry(p.seq_pair, seq) * tw * th + (size_t)y * tw + x0);
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const unsigned g8 = v[k] & 0xffu;   // kept pixel k is source pixel k << 2: byte 0 of word k
-            top[k] = pass_valid(photo_gray(RESP_LDS ? lut[g8] : resp[g8], gn[k]));
-        }
+        for (int k = 0; k < 4; k++) top[k] = pass_valid(photo_gray(RESP_LDS ? lut[in.gray8(k)] : resp[in.gray8(k)], gn[k]));
     }
     __builtin_nontemporal_store(top, reinterpret_cast<f4*>(a.dst[0][a.levels - 1] + ot));
-    for (int t = 1; t < a.levels; t++) {   // lower levels: pixels whose coordinates are multiples of 2^t
-        const int msk = (1 << t) - 1;
-        if (y & msk) break;
-        const int l = a.levels - 1 - t, ly = y >> t;
-        if (ly >= a.h[l]) continue;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int x = x0 + k;
-            if (x & msk) continue;
-            const int lx = x >> t;
-            if (lx >= a.w[l]) continue;
-            __builtin_nontemporal_store(pass_valid(top[k]), a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
-        }
-    }
+    walk_levels<4, 1>(a, a.levels, seq, x0, y, [&](int l, size_t o, int k) { __builtin_nontemporal_store(pass_valid(top[k]), a.dst[0][l] + o); });
 }
 
 // k_pyramid_photo: the scalar form, one thread per top-level pixel: 3 / 4 channels (the response is applied to k_ingest's luma, not
@@ -513,9 +579,9 @@ __global__ void __launch_bounds__(256) k_pyramid_photo(PyramidArgs a, PhotoArgs 
     int x, y;
     split_index(i, tw, a.inv_tw, x, y);
     float raw;
-    if (PLAN && a.seq_action[seq] == DVO_SEQ_SKIP) {
-        if constexpr (REMAP) return;
-        raw = __builtin_nontemporal_load(a.ref[0][a.levels - 1] + (size_t)seq * tw * th + i);
+    if (PLAN && seq_skips(a, seq)) {
+        if constexpr (REMAP) return;   // (writes nothing)
+        raw = __builtin_nontemporal_load(a.ref[0][a.levels - 1] + (size_t)seq * tw * th + i);   // copy-forward: the keyframe's gray
     } else {
         const float gain = p.gain[(size_t)load_seq_entry(p.seq_pair, seq) * tw * th + i];
         size_t src_off;
@@ -527,26 +593,11 @@ __global__ void __launch_bounds__(256) k_pyramid_photo(PyramidArgs a, PhotoArgs 
         } else {
             src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + (x << a.culls);
         }
-        raw = kInvalid;
-        if (inside) {
-            unsigned g8;
-            if (a.raw_channels == 1) {
-                g8 = __builtin_nontemporal_load(a.raw_rgb + src_off);
-            } else {
-                const uint8_t* q = a.raw_rgb + src_off * (size_t)a.raw_channels;
-                g8 = ((unsigned)q[0] * 4899u + (unsigned)q[1] * 9617u + (unsigned)q[2] * 1868u + 8192u) >> 14;
-            }
-            raw = photo_gray(lut[g8], gain);
-        }
+        raw = inside ? photo_gray(lut[raw_luma8(a, src_off)], gain) : kInvalid;
     }
-    for (int t = 0; t < a.levels; t++) {
-        const int msk = (1 << t) - 1;
-        if ((x & msk) | (y & msk)) break;
-        const int l = a.levels - 1 - t, lx = x >> t, ly = y >> t;
-        if (lx >= a.w[l] || ly >= a.h[l]) continue;
-        __builtin_nontemporal_store((t == 0 && a.culls == 0) ? raw : pass_valid(raw),
-                                    a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
-    }
+    walk_levels<1, 0>(a, a.levels, seq, x, y, [&](int l, size_t o, int) {
+        __builtin_nontemporal_store((l == a.levels - 1 && a.culls == 0) ? raw : pass_valid(raw), a.dst[0][l] + o);
+    });
 }
 
 // k_photometric_map: the gain tables, once per set of the calibration or of D.  One thread per top-level pixel per distinct
@@ -589,47 +640,17 @@ __global__ void __launch_bounds__(256) k_pyramid_raw4_coarse(PyramidArgs a)
     split_index(gi, gw, a.inv_tw * 8.0f, xg, y);   // (8 / tw = 1 / gw up to an ulp: split_index corrects +-1)
     const int x0 = xg << 2;                        // level top - 1 coordinates (x0 .. x0 + 3, y)
     const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)((2 * y) << a.src_row_shift) * a.src_w + ((size_t)x0 << (CULLS + 1));
-    constexpr int GW = 2 << CULLS;       // 32-bit words of gray bytes this thread reads (4 or 8)
-    unsigned gwords[GW], dwords[2 * GW];
-    {
-        const u32x4* gp = reinterpret_cast<const u32x4*>(a.raw_rgb + src_off);
-        const u32x4* dp = reinterpret_cast<const u32x4*>(a.raw_depth + src_off);
-#pragma unroll
-        for (int q = 0; q < GW / 4; q++) {
-            const u32x4 v = __builtin_nontemporal_load(gp + q);
-            gwords[4 * q] = v.x; gwords[4 * q + 1] = v.y; gwords[4 * q + 2] = v.z; gwords[4 * q + 3] = v.w;
-        }
-#pragma unroll
-        for (int q = 0; q < GW / 2; q++) {
-            const u32x4 v = __builtin_nontemporal_load(dp + q);
-            dwords[4 * q] = v.x; dwords[4 * q + 1] = v.y; dwords[4 * q + 2] = v.z; dwords[4 * q + 3] = v.w;
-        }
-    }
+    RawWords<CULLS + 1> in;   // (every second kept pixel of the row)
+    in.load_gray(a, src_off);
+    in.load_depth(a, src_off);
     f4 g;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int si = k << (CULLS + 1);                                      // source pixel of kept pixel k
-        const unsigned g8 = (gwords[si >> 2] >> ((si & 3) * 8)) & 0xffu;
-        const unsigned d = (dwords[si >> 1] >> ((si & 1) * 16)) & 0xffffu;
-        float raw = (float)g8 * a.raw_gray_scale;
-        if (a.raw_invalidate_gray && d == 0) raw = kInvalid;
-        g[k] = pass_valid(raw);
+        g[k] = pass_valid(raw_convert(a, in.gray8(k), in.depth16(k)).gray);   // (depth and sigma are stage B's)
     }
     __builtin_nontemporal_store(g, reinterpret_cast<f4*>(a.dst[0][T - 1] + (size_t)seq * cw * ch + (size_t)y * cw + x0));
-    for (int t = 1; t < T; t++) {   // level top - 1 - t: pixels whose level top - 1 coordinates are multiples of 2^t
-        const int msk = (1 << t) - 1;
-        if (y & msk) break;
-        const int l = T - 1 - t, ly = y >> t;
-        if (ly >= a.h[l]) continue;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int x = x0 + k;
-            if (x & msk) continue;
-            const int lx = x >> t;
-            if (lx >= a.w[l]) continue;
-            __builtin_nontemporal_store(g[k], a.dst[0][l] + (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx);
-        }
-    }
+    // the levels below top - 1: the walk of a pyramid whose top is level top - 1
+    walk_levels<4, 1>(a, T, seq, x0, y, [&](int l, size_t o, int k) { __builtin_nontemporal_store(g[k], a.dst[0][l] + o); });
 }
 
 // k_pyramid_raw4_rest (stage B): k_pyramid_raw4<CULLS, false> with depth, minus the gray stores below the top.  It runs beside
@@ -647,31 +668,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) k_py
     split_index(gi, gw, a.inv_tw * 4.0f, xg, y);
     const int x0 = xg << 2;
     const size_t src_off = (size_t)seq * a.src_w * a.src_img_rows + (size_t)(y << a.src_row_shift) * a.src_w + ((size_t)x0 << CULLS);
-    constexpr int GW = 1 << CULLS;
-    unsigned gwords[GW], dwords[2 * GW];
-    {
-        const unsigned* gp = reinterpret_cast<const unsigned*>(a.raw_rgb + src_off);
-        if constexpr (CULLS == 1) { const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(gp)); gwords[0] = v.x; gwords[1] = v.y; }
-        else { const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(gp)); gwords[0] = v.x; gwords[1] = v.y; gwords[2] = v.z; gwords[3] = v.w; }
-        const u32x4* dp = reinterpret_cast<const u32x4*>(a.raw_depth + src_off);
-#pragma unroll
-        for (int q = 0; q < GW / 2; q++) {
-            const u32x4 v = __builtin_nontemporal_load(dp + q);
-            dwords[4 * q] = v.x; dwords[4 * q + 1] = v.y; dwords[4 * q + 2] = v.z; dwords[4 * q + 3] = v.w;
-        }
-    }
+    RawWords<CULLS> in;
+    in.load_gray(a, src_off);
+    in.load_depth(a, src_off);
     const bool prep = a.wgt[0] != nullptr;
     f4 v[3];   // pass_valid of gray, depth, sigma of the four kept pixels: what every level stores
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        const int si = k << CULLS;
-        const unsigned g8 = (gwords[si >> 2] >> ((si & 3) * 8)) & 0xffu;
-        const unsigned d = (dwords[si >> 1] >> ((si & 1) * 16)) & 0xffffu;
-        float raw = (float)g8 * a.raw_gray_scale;
-        if (a.raw_invalidate_gray && d == 0) raw = kInvalid;
-        v[0][k] = pass_valid(raw);
-        v[1][k] = pass_valid((float)d * a.raw_depth_scale);
-        v[2][k] = pass_valid(d > 0 ? a.raw_sigma_valid : a.raw_sigma_invalid);
+        const RawPixel p = raw_convert(a, in.gray8(k), in.depth16(k));
+        v[0][k] = pass_valid(p.gray); v[1][k] = pass_valid(p.depth); v[2][k] = pass_valid(p.sigma);
     }
     {
         const int l = a.levels - 1;
@@ -686,6 +691,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) k_py
             __builtin_nontemporal_store(wgv, reinterpret_cast<f4*>(a.wgt[l] + o));
         }
     }
+    // walk_levels<4, 1> written out: under the helper this kernel measured 3 % slower beside k_track_gn.  Stage A
+    // has written the gray below the top.
     for (int t = 1; t < a.levels; t++) {
         const int msk = (1 << t) - 1;
         if (y & msk) break;
@@ -717,7 +724,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(32))) k_py
 // PPT = 1 is the scalar fallback.  PLAN: the workgroups of a DVO_SEQ_SKIP sequence copy their reference forward, as k_pyramid<true>.
 // The table is read with plain loads (one table serves every sequence of the camera and stays in L2), the frames and the levels
 // with nontemporal accesses.  The input holds whole frames (src_img_rows = src_h): the gather reads any row.
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 template <int PPT, bool PLAN>
 __global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
 {
@@ -732,7 +738,7 @@ __global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
     const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x0;
     const bool prep = a.wgt[0] != nullptr;   // (depth and sigma are always present here)
     bool skip = false;
-    if constexpr (PLAN) skip = a.seq_action[seq] == DVO_SEQ_SKIP;   // (uniform per workgroup)
+    if constexpr (PLAN) skip = seq_skips(a, seq);
     float top[3][PPT];   // the top-level value of each map: what the build stores there (lower levels: pass_valid of it)
 #pragma unroll
     for (int m = 0; m < 3; m++)
@@ -765,19 +771,9 @@ __global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
             float raw[3] = {kInvalid, kInvalid, kInvalid};
             if (si[k] >= 0) {
                 const size_t so = base + (size_t)si[k];
-                if (a.raw_rgb != nullptr) {   // k_pyramid's raw conversion of the one gathered pixel
-                    unsigned g8;
-                    if (a.raw_channels == 1) {
-                        g8 = __builtin_nontemporal_load(a.raw_rgb + so);
-                    } else {
-                        const uint8_t* p = a.raw_rgb + so * (size_t)a.raw_channels;
-                        g8 = ((unsigned)p[0] * 4899u + (unsigned)p[1] * 9617u + (unsigned)p[2] * 1868u + 8192u) >> 14;
-                    }
-                    raw[0] = (float)g8 * a.raw_gray_scale;
-                    const unsigned d = __builtin_nontemporal_load(a.raw_depth + so);
-                    raw[1] = (float)d * a.raw_depth_scale;
-                    raw[2] = d > 0 ? a.raw_sigma_valid : a.raw_sigma_invalid;
-                    if (a.raw_invalidate_gray && d == 0) raw[0] = kInvalid;
+                if (a.raw_rgb != nullptr) {   // the raw conversion of the one gathered pixel
+                    const RawPixel p = raw_convert(a, raw_luma8(a, so), __builtin_nontemporal_load(a.raw_depth + so));
+                    raw[0] = p.gray; raw[1] = p.depth; raw[2] = p.sigma;
                 } else {
 #pragma unroll
                     for (int m = 0; m < 3; m++) raw[m] = __builtin_nontemporal_load(a.src[m] + so);
@@ -812,27 +808,15 @@ __global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
             __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[T] + ot) : gn_weight(a.step[T], a.sigma_min, a.sigma_max, top[2][0]),
                                         a.wgt[T] + ot);
     }
-    for (int t = 1; t < a.levels; t++) {   // lower levels: pixels whose coordinates are multiples of 2^t
-        const int msk = (1 << t) - 1;
-        if (y & msk) break;
-        const int l = a.levels - 1 - t, ly = y >> t;
-        if (ly >= a.h[l]) continue;
+    walk_levels<PPT, 1>(a, a.levels, seq, x0, y, [&](int l, size_t o, int k) {
+        const float sg = pass_valid(top[2][k]);
 #pragma unroll
-        for (int k = 0; k < PPT; k++) {
-            const int x = x0 + k;
-            if (x & msk) continue;
-            const int lx = x >> t;
-            if (lx >= a.w[l]) continue;
-            const size_t o = (size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx;
-            const float sg = pass_valid(top[2][k]);
-#pragma unroll
-            for (int m = 0; m < 3; m++)
-                if (a.dst[m][l] != nullptr) __builtin_nontemporal_store(m == 2 ? sg : pass_valid(top[m][k]), a.dst[m][l] + o);
-            if (prep)
-                __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[l] + o) : gn_weight(a.step[l], a.sigma_min, a.sigma_max, sg),
-                                            a.wgt[l] + o);
-        }
-    }
+        for (int m = 0; m < 3; m++)
+            if (a.dst[m][l] != nullptr) __builtin_nontemporal_store(m == 2 ? sg : pass_valid(top[m][k]), a.dst[m][l] + o);
+        if (prep)
+            __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[l] + o) : gn_weight(a.step[l], a.sigma_min, a.sigma_max, sg),
+                                        a.wgt[l] + o);
+    });
 }
 
 // k_cull: a single Convert::cullImage (operator-level parity)
@@ -3309,26 +3293,6 @@ void launch_undistort_map(const UndistortCam* cams_dev, int n_cam, int w, int h,
     hipLaunchKernelGGL(k_undistort_map, seq_grid(cdiv(tw * th, 256), (unsigned)n_cam), dim3(256), 0, s, cams_dev, n_cam, w, h, culls, tw, th, table);
 }
 
-// k_pyramid_remap_depth: four kept pixels per thread where the top-level width and every 16-byte access allow it, else one
-// (DVO_REMAP_DEPTH_SCALAR set: always one -- A/B runs, tools/bench_sensor_undistort.py)
-static void launch_pyramid_remap_depth(const PyramidArgs& a, hipStream_t s)
-{
-    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
-    bool vec = (tw % 4) == 0 && (reinterpret_cast<uintptr_t>(a.remap) % 16) == 0 && getenv("DVO_REMAP_DEPTH_SCALAR") == nullptr;
-    const void* tops[8] = {a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T], a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]};
-    for (const void* p : tops) vec = vec && (reinterpret_cast<uintptr_t>(p) % 16) == 0;   // (nullptr passes: not accessed)
-    const bool plan = a.seq_action != nullptr;
-    if (vec) {
-        const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)a.n_seq);
-        if (plan) hipLaunchKernelGGL((k_pyramid_remap_depth<4, true>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_pyramid_remap_depth<4, false>), grid, dim3(256), 0, s, a);
-        return;
-    }
-    const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
-    if (plan) hipLaunchKernelGGL((k_pyramid_remap_depth<1, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((k_pyramid_remap_depth<1, false>), grid, dim3(256), 0, s, a);
-}
-
 void launch_photometric_map(const float* vignette, const int* pairs, int n_pair, int w, int h, int culls, int tw, int th, const int* remap,
                             float* gain, hipStream_t s)
 {
@@ -3336,39 +3300,81 @@ void launch_photometric_map(const float* vignette, const int* pairs, int n_pair,
                        tw, th, remap, gain);
 }
 
-// The kernels of a calibrated handle's raw mono frames (PhotoArgs set): k_pyramid_raw4_photo under k_pyramid_raw4's own conditions at
-// culls 2 plus 16-byte gain rows, else k_pyramid_photo.  A missing piece is an error of the caller (build_pyramid checks), not a
+// A runtime flag as a compile-time constant: f receives std::true_type or std::false_type, so a launcher names its kernel template
+// once and the flag's two instances follow from it
+template <class F>
+static void with_flag(bool on, F&& f)
+{
+    if (on) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// The CULLS of the four-pixel pyramid kernels (1 or 2, pyramid_raw4_possible) as a compile-time constant, like with_flag
+template <class F>
+static void with_culls(int culls, F&& f)
+{
+    if (culls == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+
+// Every pointer is 16-byte aligned (nullptr passes: not accessed)
+static bool aligned16(std::initializer_list<const void*> ptrs)
+{
+    for (const void* p : ptrs)
+        if ((reinterpret_cast<uintptr_t>(p) % 16) != 0) return false;
+    return true;
+}
+
+// The grid of a pyramid kernel whose threads own ppt consecutive pixels of a w x h level (ppt = 4: w is a multiple of 4)
+static dim3 pyramid_grid(int w, int h, int ppt, int n_seq) { return seq_grid(cdiv((w / ppt) * h, 256), (unsigned)n_seq); }
+
+// The four-pixel build (k_pyramid_raw4, _photo, _rest) is possible for these arguments: 1-channel bytes, CULLS 1 or 2, whole
+// groups of four kept pixels in whole 16-byte source words, and 16-byte aligned input and top-level maps; `more` are the
+// caller's kernel's further 16-byte accesses.
+static bool pyramid_raw4_possible(const PyramidArgs& a, std::initializer_list<const void*> more)
+{
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    return a.raw_rgb != nullptr && a.raw_channels == 1 && (a.culls == 1 || a.culls == 2) && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 &&
+           ((size_t)tw * th % 4) == 0 && aligned16({a.raw_rgb, a.raw_depth, a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T]}) && aligned16(more);
+}
+
+// k_pyramid_remap_depth: four kept pixels per thread where the top-level width and every 16-byte access allow it, else one
+// (DVO_REMAP_DEPTH_SCALAR set: always one -- A/B runs, tools/bench_sensor_undistort.py)
+static void launch_pyramid_remap_depth(const PyramidArgs& a, hipStream_t s)
+{
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    const bool vec = (tw % 4) == 0 && getenv("DVO_REMAP_DEPTH_SCALAR") == nullptr &&
+                     aligned16({a.remap, a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T], a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]});
+    with_flag(a.seq_action != nullptr, [&](auto plan) {
+        constexpr bool PLAN = decltype(plan)::value;
+        if (vec) hipLaunchKernelGGL((k_pyramid_remap_depth<4, PLAN>), pyramid_grid(tw, th, 4, a.n_seq), dim3(256), 0, s, a);
+        else hipLaunchKernelGGL((k_pyramid_remap_depth<1, PLAN>), pyramid_grid(tw, th, 1, a.n_seq), dim3(256), 0, s, a);
+    });
+}
+
+// The kernels of a calibrated handle's raw mono frames (PhotoArgs set): k_pyramid_raw4_photo where the four-pixel build is possible
+// at culls 2 with 16-byte gain rows, else k_pyramid_photo.  A missing piece is an error of the caller (build_pyramid checks), not a
 // reason to run a plain kernel.
 static PyramidKernel launch_pyramid_photo(const PyramidArgs& a, const PhotoArgs& p, hipStream_t s)
 {
     const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
-    const bool plan = a.seq_action != nullptr;
-    if (a.remap != nullptr) {
-        const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
-        if (plan) hipLaunchKernelGGL((k_pyramid_photo<true, true>), grid, dim3(256), 0, s, a, p);
-        else hipLaunchKernelGGL((k_pyramid_photo<false, true>), grid, dim3(256), 0, s, a, p);
-        return {DVO_PYRAMID_KERNEL_PHOTO_REMAP, 0, plan ? 1 : 0};
-    }
-    bool vec = a.raw_channels == 1 && a.culls == 2 && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 && ((size_t)tw * th % 4) == 0;
-    const void* wide[4] = {a.raw_rgb, a.dst[0][T], p.gain, plan ? a.ref[0][T] : nullptr};   // the 16-byte accesses (nullptr passes: not accessed)
-    for (const void* q : wide) vec = vec && (reinterpret_cast<uintptr_t>(q) % 16) == 0;
-    if (vec) {
-        const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)a.n_seq);
-        const char* e = getenv("DVO_PHOTO_RESPONSE");
-        const bool lds = !(e && strcmp(e, "global") == 0);
-        if (plan) {
-            if (lds) hipLaunchKernelGGL((k_pyramid_raw4_photo<2, true, true>), grid, dim3(256), 0, s, a, p);
-            else hipLaunchKernelGGL((k_pyramid_raw4_photo<2, true, false>), grid, dim3(256), 0, s, a, p);
-        } else {
-            if (lds) hipLaunchKernelGGL((k_pyramid_raw4_photo<2, false, true>), grid, dim3(256), 0, s, a, p);
-            else hipLaunchKernelGGL((k_pyramid_raw4_photo<2, false, false>), grid, dim3(256), 0, s, a, p);
+    const bool plan = a.seq_action != nullptr, remap = a.remap != nullptr;
+    PyramidKernel ran = {remap ? DVO_PYRAMID_KERNEL_PHOTO_REMAP : DVO_PYRAMID_KERNEL_PHOTO_SCALAR, 0, plan ? 1 : 0};
+    with_flag(plan, [&](auto plan_c) {
+        constexpr bool PLAN = decltype(plan_c)::value;
+        if (!remap && a.culls == 2 && pyramid_raw4_possible(a, {p.gain, PLAN ? a.ref[0][T] : nullptr})) {
+            const char* e = getenv("DVO_PHOTO_RESPONSE");
+            with_flag(!(e && strcmp(e, "global") == 0), [&](auto lds) {
+                hipLaunchKernelGGL((k_pyramid_raw4_photo<2, PLAN, decltype(lds)::value>), pyramid_grid(tw, th, 4, a.n_seq), dim3(256), 0, s, a, p);
+            });
+            ran = {DVO_PYRAMID_KERNEL_PHOTO_RAW4, a.culls, plan ? 1 : 0};
+            return;
         }
-        return {DVO_PYRAMID_KERNEL_PHOTO_RAW4, a.culls, plan ? 1 : 0};
-    }
-    const dim3 grid = seq_grid(cdiv(tw * th, 256), (unsigned)a.n_seq);
-    if (plan) hipLaunchKernelGGL((k_pyramid_photo<true, false>), grid, dim3(256), 0, s, a, p);
-    else hipLaunchKernelGGL((k_pyramid_photo<false, false>), grid, dim3(256), 0, s, a, p);
-    return {DVO_PYRAMID_KERNEL_PHOTO_SCALAR, 0, plan ? 1 : 0};
+        with_flag(remap, [&](auto remap_c) {
+            hipLaunchKernelGGL((k_pyramid_photo<PLAN, decltype(remap_c)::value>), pyramid_grid(tw, th, 1, a.n_seq), dim3(256), 0, s, a, p);
+        });
+    });
+    return ran;
 }
 
 PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s, const PhotoArgs* photo)
@@ -3376,61 +3382,39 @@ PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s, co
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     if (photo != nullptr && photo->gain != nullptr) return launch_pyramid_photo(a, *photo, s);
-    const int tw = a.w[a.levels - 1], th = a.h[a.levels - 1];
-    if (a.remap != nullptr && (a.raw_depth != nullptr || a.src[1] != nullptr)) {   // sensor-depth frames, lens undistortion fused in
-        launch_pyramid_remap_depth(a, s);
-        return {DVO_PYRAMID_KERNEL_REMAP, 0, a.seq_action != nullptr};
-    }
-    if (a.remap != nullptr) {   // lens undistortion fused in (mono frames): never k_pyramid_raw4 / k_pyramid
-        if (a.seq_action != nullptr) hipLaunchKernelGGL(k_pyramid_remap_plan, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
-        else hipLaunchKernelGGL(k_pyramid_remap, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
-        return {DVO_PYRAMID_KERNEL_REMAP, 0, a.seq_action != nullptr};
-    }
-    // raw 1-channel frames with the usual alignment: four kept pixels per thread, wide loads and stores
-    const bool vec = a.raw_rgb != nullptr && a.raw_channels == 1 && (a.culls == 1 || a.culls == 2) && (tw % 4) == 0 && (a.src_w % (4 << a.culls)) == 0 &&
-                     (reinterpret_cast<uintptr_t>(a.raw_rgb) % 16) == 0 && (reinterpret_cast<uintptr_t>(a.raw_depth) % 16) == 0;
-    bool aligned = true;   // the 16-byte top-level stores
-    {
-        const int T = a.levels - 1;
-        const void* tops[4] = {a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T]};
-        for (const void* p : tops) aligned = aligned && (reinterpret_cast<uintptr_t>(p) % 16) == 0;
-        aligned = aligned && ((size_t)tw * th % 4) == 0;
-    }
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
     const bool plan = a.seq_action != nullptr;
-    if (plan) {   // copy-forward: the reference tops are read with the same 16-byte accesses
-        const int T = a.levels - 1;
-        const void* tops[4] = {a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]};
-        for (const void* p : tops) aligned = aligned && (reinterpret_cast<uintptr_t>(p) % 16) == 0;
+    if (a.remap != nullptr) {   // lens undistortion fused in: never k_pyramid_raw4 / k_pyramid
+        if (a.raw_depth != nullptr || a.src[1] != nullptr) launch_pyramid_remap_depth(a, s);   // sensor-depth frames
+        else if (plan) hipLaunchKernelGGL(k_pyramid_remap_plan, pyramid_grid(tw, th, 1, n_seq), dim3(256), 0, s, a);   // mono frames
+        else hipLaunchKernelGGL(k_pyramid_remap, pyramid_grid(tw, th, 1, n_seq), dim3(256), 0, s, a);
+        return {DVO_PYRAMID_KERNEL_REMAP, 0, plan ? 1 : 0};
     }
-    if (vec && aligned) {
-        const dim3 grid = seq_grid(cdiv((tw >> 2) * th, 256), (unsigned)n_seq);
-        if (plan) {
-            if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, true>), grid, dim3(256), 0, s, a);
-            else hipLaunchKernelGGL((k_pyramid_raw4<2, true>), grid, dim3(256), 0, s, a);
-            return {DVO_PYRAMID_KERNEL_RAW4, a.culls, 1};
+    PyramidKernel ran = {DVO_PYRAMID_KERNEL_SCALAR, 0, plan ? 1 : 0};
+    with_flag(plan, [&](auto plan_c) {
+        constexpr bool PLAN = decltype(plan_c)::value;
+        // raw 1-channel frames with the usual alignment: four kept pixels per thread, wide loads and stores (with a plan the
+        // copy-forward reads the reference tops with the same 16-byte accesses)
+        if (PLAN ? pyramid_raw4_possible(a, {a.ref[0][T], a.ref[1][T], a.ref[2][T], a.ref_wgt[T]}) : pyramid_raw4_possible(a, {})) {
+            with_culls(a.culls, [&](auto culls) {
+                hipLaunchKernelGGL((k_pyramid_raw4<decltype(culls)::value, PLAN>), pyramid_grid(tw, th, 4, n_seq), dim3(256), 0, s, a);
+            });
+            ran = {DVO_PYRAMID_KERNEL_RAW4, a.culls, plan ? 1 : 0};
+            return;
         }
-        if (a.culls == 1) hipLaunchKernelGGL((k_pyramid_raw4<1, false>), grid, dim3(256), 0, s, a);
-        else hipLaunchKernelGGL((k_pyramid_raw4<2, false>), grid, dim3(256), 0, s, a);
-        return {DVO_PYRAMID_KERNEL_RAW4, a.culls, 0};
-    }
-    if (plan) hipLaunchKernelGGL(k_pyramid<true>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_pyramid<false>, seq_grid(cdiv(tw * th, 256), (unsigned)n_seq), dim3(256), 0, s, a);
-    return {DVO_PYRAMID_KERNEL_SCALAR, 0, plan ? 1 : 0};
+        hipLaunchKernelGGL(k_pyramid<PLAN>, pyramid_grid(tw, th, 1, n_seq), dim3(256), 0, s, a);
+    });
+    return ran;
 }
 
 bool pyramid_can_split(const PyramidArgs& a)
 {
     const int T = a.levels - 1;
-    if (a.levels < 2 || a.remap != nullptr || a.seq_action != nullptr) return false;
-    if (a.raw_rgb == nullptr || a.raw_depth == nullptr || a.raw_channels != 1 || (a.culls != 1 && a.culls != 2)) return false;
+    if (a.levels < 2 || a.remap != nullptr || a.seq_action != nullptr || a.raw_depth == nullptr) return false;
+    // stage B: the four-pixel build; stage A: eight top-level pixels per thread, a dwordx4 store into level top - 1
+    if (!pyramid_raw4_possible(a, {a.dst[0][T - 1]})) return false;
     const int tw = a.w[T], th = a.h[T];
-    // stage B: k_pyramid_raw4's conditions; stage A: eight top-level pixels per thread, a dwordx4 store into level top - 1
-    if ((tw % 8) != 0 || (a.src_w % (8 << a.culls)) != 0 || ((size_t)tw * th % 4) != 0 || ((size_t)a.w[T - 1] * a.h[T - 1] % 4) != 0) return false;
-    if (a.w[T - 1] * 2 != tw || a.h[T - 1] * 2 > th) return false;
-    const void* ptrs[7] = {a.raw_rgb, a.raw_depth, a.dst[0][T], a.dst[1][T], a.dst[2][T], a.wgt[T], a.dst[0][T - 1]};
-    for (const void* p : ptrs)
-        if ((reinterpret_cast<uintptr_t>(p) % 16) != 0) return false;
-    return true;
+    return (tw % 8) == 0 && (a.src_w % (8 << a.culls)) == 0 && ((size_t)a.w[T - 1] * a.h[T - 1] % 4) == 0 && a.w[T - 1] * 2 == tw && a.h[T - 1] * 2 <= th;
 }
 
 void launch_pyramid_coarse(const PyramidArgs& a0, int n_seq, hipStream_t s)
@@ -3438,9 +3422,9 @@ void launch_pyramid_coarse(const PyramidArgs& a0, int n_seq, hipStream_t s)
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     const int T = a.levels - 1;
-    const dim3 grid = seq_grid(cdiv((a.w[T - 1] >> 2) * a.h[T - 1], 256), (unsigned)n_seq);
-    if (a.culls == 1) hipLaunchKernelGGL(k_pyramid_raw4_coarse<1>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_pyramid_raw4_coarse<2>, grid, dim3(256), 0, s, a);
+    with_culls(a.culls, [&](auto culls) {
+        hipLaunchKernelGGL(k_pyramid_raw4_coarse<decltype(culls)::value>, pyramid_grid(a.w[T - 1], a.h[T - 1], 4, n_seq), dim3(256), 0, s, a);
+    });
 }
 
 void launch_pyramid_rest(const PyramidArgs& a0, int n_seq, hipStream_t s)
@@ -3448,9 +3432,9 @@ void launch_pyramid_rest(const PyramidArgs& a0, int n_seq, hipStream_t s)
     PyramidArgs a = a0;
     a.n_seq = n_seq;
     const int T = a.levels - 1;
-    const dim3 grid = seq_grid(cdiv((a.w[T] >> 2) * a.h[T], 256), (unsigned)n_seq);
-    if (a.culls == 1) hipLaunchKernelGGL(k_pyramid_raw4_rest<1>, grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL(k_pyramid_raw4_rest<2>, grid, dim3(256), 0, s, a);
+    with_culls(a.culls, [&](auto culls) {
+        hipLaunchKernelGGL(k_pyramid_raw4_rest<decltype(culls)::value>, pyramid_grid(a.w[T], a.h[T], 4, n_seq), dim3(256), 0, s, a);
+    });
 }
 
 void launch_cull(const float* src, int w, int h, int times, float* dst, hipStream_t s)
@@ -3470,15 +3454,6 @@ void launch_warp_image(const float* gray, const float* depth, int w, int h, cons
 }
 
 int gn_blocks_per_seq(int w, int h, int ppt, int crop) { return gn_tiling(w, h, ppt, crop).count; }
-
-// A runtime flag as a compile-time constant: f receives std::true_type or std::false_type, so a launcher names its kernel template
-// once and the flag's two instances follow from it
-template <class F>
-static void with_flag(bool on, F&& f)
-{
-    if (on) f(std::true_type{});
-    else f(std::false_type{});
-}
 
 // The (ppt, group) pairs the tilings pick, as compile-time constants: f receives the pair as two std::integral_constant, so a launcher
 // names its kernel template once and the nine instances follow from it.  Any other pair runs as <8, 4>.

@@ -254,6 +254,14 @@ def test_keyframe_pyramids_equal_replica(shape, ch, feed, planned, with_D, kind)
     assert skipped == (1 if planned else 0), skipped
 
 
+@pytest.mark.parametrize("planned", [False, True], ids=["plain", "planned"])
+def test_keyframe_pyramids_with_the_response_read_by_plain_loads(planned, monkeypatch):
+    """k_pyramid_raw4_photo<2, planned, false>: DVO_PHOTO_RESPONSE=global (read at every launch) takes the instance without the LDS
+    stage, held to the same replica by the same case; the reported kind does not tell the two instances apart, the variable does"""
+    monkeypatch.setenv("DVO_PHOTO_RESPONSE", "global")
+    test_keyframe_pyramids_equal_replica(RAW4, 1, "device", planned, False, dvo.PYRAMID_KERNEL_PHOTO_RAW4)
+
+
 # ---------------------------------------------------------------- 3. equal to two passes
 def _run(mb, B, frames_of, feed="device"):
     out = []

@@ -146,6 +146,27 @@ def test_mono_keyframe_pyramids_equal_reference(feed, ch, planned):
     assert skipped == (1 if planned else 0), skipped
 
 
+@pytest.mark.parametrize("planned", [False, True], ids=["k_pyramid_remap", "k_pyramid_remap_plan"])
+def test_mono_build_reports_the_remap_kernel(planned):
+    """which kernel the cases above reach: a mono handle with D reports kind REMAP, and the PLAN instance exactly when actions are set;
+    the first keyframe's pyramid of every sequence is the reference's"""
+    B = len(MONO_K)
+    mb = dvo.MonoBatch(B, np.stack(MONO_K), 640, 480, cfg=dvo.default_config(rng_seed=3, gn_pixels_per_thread=4), per_sequence_K=True)
+    init = _init_depth()
+    mb.setInitialDepth(init, np.full_like(init, 0.5))
+    mb.set_distortion(np.stack(MONO_D))
+    if planned:
+        mb.set_actions(np.full(B, TRACK, np.uint8))
+    _mono_feed(mb, np.stack([_rgb(q % N_RENDER, 1) for q in range(B)]), "host", 1)
+    ran = mb.last_pyramid_kernel()
+    assert (ran.kind, ran.plan) == (dvo.PYRAMID_KERNEL_REMAP, 1 if planned else 0), ran.name()
+    for q in range(B):
+        exp = _ref_pyramid(q % N_RENDER, 1, MONO_K[q].tobytes(), MONO_D[q].tobytes())
+        for lv in range(LEVELS):
+            _assert_bits(mb.keyframe(q, lv)["gray"], exp[lv], "sequence %d level %d" % (q, lv))
+    mb.close()
+
+
 @pytest.mark.parametrize("raw", [False, True], ids=["float", "raw1"])
 def test_dvo_vo_keyframe_pyramids_equal_reference(raw):
     order = _orders(1)[0]
@@ -204,7 +225,7 @@ def _sensor_maps(i, ch, w, h):
     return ingest_np(*_sensor_raw(i, ch, w, h))
 
 
-def _sensor_run(levels, culls, w, h, feed, ch, frames, D):
+def _sensor_run(levels, culls, w, h, feed, ch, frames, D, actions=None):
     import torch
     B = len(SENSOR_K)
     bt = dvo.Batch(B, SENSOR_K[0], w, h, levels, culls, cfg=dvo.default_config(gn_pixels_per_thread=4))
@@ -214,6 +235,8 @@ def _sensor_run(levels, culls, w, h, feed, ch, frames, D):
     out = []
     for k in range(N_PUSH):
         maps = [np.ascontiguousarray(np.stack(m)) for m in zip(*frames(k))]
+        if actions is not None and actions[k] is not None:
+            bt.set_actions(np.array(actions[k], np.uint8))
         if feed == "host":
             bt.push_host(*maps)
         elif feed == "device":
@@ -266,3 +289,41 @@ def test_sensor_batch_equals_plain_batch_fed_reference(levels, culls, w, h, feed
             assert got[k][3][q] == ref[k][3][q], where
     # the pushes after the first tracked
     assert all((got[k][2] == dvo.SEQ_TRACKED).all() for k in range(1, N_PUSH)), [g[2] for g in got]
+
+
+@pytest.mark.parametrize("feed,ch", [("device", 0), ("raw_device", 1), ("raw_host", 3)], ids=["float", "raw1", "raw3"])
+def test_sensor_scalar_kernel_copies_skipped_sequences_forward(feed, ch):
+    """k_pyramid_remap_depth<1, true> with SKIP in the plan.  The batch reports no kernel: the 323-pixel top level of a 646-pixel
+    frame admits only the scalar kernel, and the intrinsics table makes every build a planned one.  A skipped sequence's slot holds
+    garbage and its reference is copied forward, so every later twist of that sequence depends on the copy: the twists, poses,
+    status and track logs equal, byte for byte, those of a plain batch with the same actions fed the numpy-undistorted maps."""
+    levels, culls, w, h = 4, 1, 646, 486
+    assert (w >> culls) % 4 != 0 and ((w >> culls) - 1) >> 2 >= (w >> culls) >> 2    # scalar kernel; a lower level drops a column
+    B = len(SENSOR_K)
+    Ks = _sensor_K(w, h)
+    orders = [[(q + k) % 4 for k in range(N_PUSH)] for q in range(B)]
+    S, T = SKIP, TRACK
+    actions = [None, (T, S, T, T), (S, T, T, S), (T, T, S, T), (T, T, T, T)]
+
+    def dist(k):
+        fr = [_sensor_raw(orders[q][k], ch, w, h) if ch else _sensor_maps(orders[q][k], 0, w, h) for q in range(B)]
+        for q in range(B):
+            if actions[k] is not None and actions[k][q] == S:    # a skipped slot is never read
+                fr[q] = tuple(np.full_like(m, 0xA5 if ch else 12345.0) for m in fr[q])
+        return fr
+
+    def und(k):
+        return [tuple(_undistort_np(m, Ks[q], SENSOR_D[q]) for m in _sensor_maps(orders[q][k], ch, w, h)) for q in range(B)]
+
+    got = _sensor_run(levels, culls, w, h, feed, ch, dist, np.stack(SENSOR_D), actions)
+    ref = _sensor_run(levels, culls, w, h, "device", 0, und, None, actions)
+    for k in range(N_PUSH):
+        for q in range(B):
+            where = "push %d sequence %d" % (k, q)
+            assert got[k][0][q].tobytes() == ref[k][0][q].tobytes(), (where, got[k][0][q], ref[k][0][q])
+            assert got[k][1][q].tobytes() == ref[k][1][q].tobytes(), where
+            assert got[k][2][q] == ref[k][2][q], where
+            assert got[k][3][q] == ref[k][3][q], where
+        if actions[k] is not None:
+            assert [int(x) for x in got[k][2]] == [SKIPPED if a == S else dvo.SEQ_TRACKED for a in actions[k]], (k, got[k][2])
+
