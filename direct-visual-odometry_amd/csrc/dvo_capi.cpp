@@ -548,6 +548,10 @@ int dvo_batch_set_robust_median(dvo_batch* b, const dvo_robust_config* cfg)
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (cfg) {
         if (!robust_config_ok(cfg, "dvo_batch_set_robust_median", true)) return DVO_ERR_BAD_ARGUMENT;
+        if (b->trk().lm.on) {
+            set_error("dvo_batch_set_robust_median: step control is on (dvo_batch_set_step_control): the two do not combine yet");
+            return DVO_ERR_BAD_ARGUMENT;
+        }
         if (b->trk().aff.on || b->trk().geo.on) {
             set_error("dvo_batch_set_robust_median: affine brightness compensation or the geometric term is on: the median scale does not combine with them");
             return DVO_ERR_BAD_ARGUMENT;
@@ -578,6 +582,10 @@ int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (cfg && !robust_config_ok(cfg, "dvo_batch_set_robust_weights", false)) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().lm.on) {
+        set_error("dvo_batch_set_robust_weights: step control is on (dvo_batch_set_step_control): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().geo.on) {
         set_error("dvo_batch_set_robust_weights: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
         return DVO_ERR_BAD_ARGUMENT;
@@ -625,6 +633,10 @@ int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (cfg && !affine_config_ok(cfg, "dvo_batch_set_affine_brightness")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().lm.on) {
+        set_error("dvo_batch_set_affine_brightness: step control is on (dvo_batch_set_step_control): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().geo.on) {
         set_error("dvo_batch_set_affine_brightness: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
         return DVO_ERR_BAD_ARGUMENT;
@@ -688,6 +700,10 @@ int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg)
     if (!b) return DVO_ERR_BAD_ARGUMENT;
     if (b->mono) { set_error("dvo_batch_set_geometric: needs a sensor-depth batch (a mono batch has no depth map to compare)"); return DVO_ERR_BAD_ARGUMENT; }
     if (cfg && !geometric_config_ok(cfg, "dvo_batch_set_geometric")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->mode != DVO_GEOMETRIC_OFF && b->trk().lm.on) {
+        set_error("dvo_batch_set_geometric: step control is on (dvo_batch_set_step_control): the two do not combine yet");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     if (cfg && cfg->mode != DVO_GEOMETRIC_OFF && (b->trk().rob.on || b->trk().aff.on)) {
         set_error("dvo_batch_set_geometric: robust weights or affine brightness compensation are on: they do not combine with the geometric term yet");
         return DVO_ERR_BAD_ARGUMENT;
@@ -705,6 +721,7 @@ int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo
     if (geo->mode != DVO_GEOMETRIC_ON) { set_error(std::string(who) + ": the geometric mode must be DVO_GEOMETRIC_ON (dvo_batch_set_geometric turns the term off)"); return DVO_ERR_BAD_ARGUMENT; }
     if (aff->mode == DVO_AFFINE_OFF) { set_error(std::string(who) + ": the affine mode must be DVO_AFFINE_ESTIMATE or DVO_AFFINE_GIVEN (dvo_batch_set_affine_brightness turns the compensation off)"); return DVO_ERR_BAD_ARGUMENT; }
     if (b->trk().rob.on) { set_error(std::string(who) + ": robust weights are on: they do not combine with the geometric term yet"); return DVO_ERR_BAD_ARGUMENT; }
+    if (b->trk().lm.on) { set_error(std::string(who) + ": step control is on (dvo_batch_set_step_control): the two do not combine yet"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(b->device()));
     return b->trk().set_geometric_affine(geo, aff, b->stream());
 }
@@ -724,6 +741,71 @@ int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log)
     if (!b->trk().geo.ready) { set_error("dvo_batch_last_geometric_log: the last push did not run with the geometric term (dvo_batch_set_geometric)"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(b->device()));
     return b->trk().last_geometric_log(seq, log, b->stream());
+}
+
+void dvo_lm_config_default(dvo_lm_config* cfg)
+{
+    if (!cfg) return;
+    cfg->struct_size = (int)sizeof(dvo_lm_config);
+    cfg->mode = DVO_LM_ON;
+    cfg->lambda0 = 1.0f;
+    cfg->lambda_up = 4.0f;
+    cfg->lambda_down = 0.5f;
+    cfg->lambda_floor = 1e-4f;
+    cfg->lambda_max = 1e6f;
+    cfg->min_valid_fraction = 0.5f;
+}
+
+static bool lm_config_ok(const dvo_lm_config* cfg, const char* who)
+{
+    const float inf = __builtin_inff();
+    const auto bad = [&](const char* what) { set_error(std::string(who) + ": " + what); return false; };
+    if (cfg->struct_size != (int)sizeof(dvo_lm_config)) return bad("struct_size is not sizeof(dvo_lm_config)");
+    if (cfg->mode != DVO_LM_OFF && cfg->mode != DVO_LM_ON) return bad("the mode is DVO_LM_OFF or DVO_LM_ON");
+    if (cfg->mode == DVO_LM_OFF) return true;
+    if (!(cfg->lambda0 >= 0.0f && cfg->lambda0 < inf)) return bad("lambda0 must be finite and >= 0");
+    if (!(cfg->lambda_up > 1.0f && cfg->lambda_up < inf)) return bad("lambda_up must be finite and > 1");
+    if (!(cfg->lambda_down > 0.0f && cfg->lambda_down <= 1.0f)) return bad("lambda_down must be in (0, 1]");
+    if (!(cfg->lambda_floor > 0.0f && cfg->lambda_floor < inf)) return bad("lambda_floor must be finite and > 0");
+    if (!(cfg->lambda_max >= cfg->lambda_floor && cfg->lambda_max < inf)) return bad("lambda_max must be finite and >= lambda_floor");
+    if (!(cfg->min_valid_fraction >= 0.0f && cfg->min_valid_fraction <= 1.0f)) return bad("min_valid_fraction must be in [0, 1]");
+    return true;
+}
+
+int dvo_batch_set_step_control(dvo_batch* b, const dvo_lm_config* cfg)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && !lm_config_ok(cfg, "dvo_batch_set_step_control")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg && cfg->mode != DVO_LM_OFF) {
+        const Tracker& t = b->trk();
+        const char* other = t.geo.on ? "the geometric term is on (dvo_batch_set_geometric)"
+                          : t.aff.on ? "affine brightness compensation is on (dvo_batch_set_affine_brightness)"
+                          : t.rob.median() ? "the median robust scale is on (dvo_batch_set_robust_median)"
+                          : t.rob.on ? "robust weights are on (dvo_batch_set_robust_weights)" : nullptr;
+        if (other) {
+            set_error(std::string("dvo_batch_set_step_control: ") + other + ": the two do not combine yet");
+            return DVO_ERR_BAD_ARGUMENT;
+        }
+    }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().set_step_control(cfg, b->stream());
+}
+
+int dvo_batch_last_step_control(dvo_batch* b, dvo_lm_record* rec)
+{
+    if (!b || !rec) return DVO_ERR_BAD_ARGUMENT;
+    if (!b->trk().lm.ready) { set_error("dvo_batch_last_step_control: the last push / call did not run with step control (dvo_batch_set_step_control)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_step_control(rec, b->stream());
+}
+
+int dvo_batch_last_step_control_log(dvo_batch* b, int seq, dvo_lm_log* log)
+{
+    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (log->struct_size != (int)sizeof(dvo_lm_log)) { set_error("dvo_batch_last_step_control_log: struct_size is not sizeof(dvo_lm_log)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (!b->trk().lm.ready) { set_error("dvo_batch_last_step_control_log: the last push / call did not run with step control (dvo_batch_set_step_control)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(b->device()));
+    return b->trk().last_step_control_log(seq, log, b->stream());
 }
 
 int dvo_batch_set_intrinsics(dvo_batch* b, const float* K)
@@ -1577,6 +1659,56 @@ int dvo_op_pose_algebra(int dev, int op, int n, const double* in, double* out)
     launch_pose_algebra(op, n, din.as<double>(), dout.as<double>(), c.s);
     DVO_HIP(hipMemcpyAsync(out, dout.p, bo, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
+    return DVO_OK;
+}
+
+int dvo_op_lm_step(int dev, int n, const double* sums, const float* xi_eval, const dvo_lm_entry* entry_in, const dvo_lm_config* cfg,
+                   int level_first, int it_prev, int max_iterations, int fixed_iterations, float min_update, float min_residual,
+                   dvo_lm_entry* entry_out, float* update, float* xi_next, int* decision, int* active)
+{
+    if (!sums || !xi_eval || !entry_in || !cfg || !entry_out || !update || !xi_next || !decision || !active || n < 1) return DVO_ERR_BAD_ARGUMENT;
+    if (!lm_config_ok(cfg, "dvo_op_lm_step")) return DVO_ERR_BAD_ARGUMENT;
+    if (cfg->mode != DVO_LM_ON) { set_error("dvo_op_lm_step: the mode must be DVO_LM_ON"); return DVO_ERR_BAD_ARGUMENT; }
+    OpCtx c; DVO_TRY(c.open(dev));
+    const size_t N = (size_t)n;
+    DevBuf dsums, dxi, table, state, last, upd, dec;
+    DVO_TRY(dsums.alloc(N * 29 * sizeof(double)));
+    DVO_TRY(dxi.alloc(N * 6 * sizeof(float)));
+    DVO_TRY(table.alloc(N * sizeof(dvo_lm_entry)));
+    DVO_TRY(state.alloc(N * sizeof(SeqState)));
+    DVO_TRY(last.alloc(N * sizeof(dvo_lm_record)));
+    DVO_TRY(upd.alloc(N * 6 * sizeof(float)));
+    DVO_TRY(dec.alloc(N * sizeof(int)));
+    DVO_HIP(hipMemcpyAsync(dsums.p, sums, dsums.bytes, hipMemcpyHostToDevice, c.s));
+    DVO_HIP(hipMemcpyAsync(dxi.p, xi_eval, dxi.bytes, hipMemcpyHostToDevice, c.s));
+    DVO_HIP(hipMemcpyAsync(table.p, entry_in, table.bytes, hipMemcpyHostToDevice, c.s));
+    DVO_HIP(hipMemsetAsync(state.p, 0, state.bytes, c.s));
+    DVO_HIP(hipMemsetAsync(last.p, 0, last.bytes, c.s));
+    SolveArgs sa{};
+    sa.state = state.as<SeqState>();
+    sa.level = 0;
+    sa.max_iterations = max_iterations; sa.fixed_iterations = fixed_iterations;
+    sa.min_update = min_update; sa.min_residual = min_residual;
+    sa.ignore_active = level_first ? 1 : 0;
+    sa.n_seq = n;
+    LmSolve m{};
+    m.table = table.as<dvo_lm_entry>(); m.last = last.as<dvo_lm_record>();
+    m.upd_out = upd.as<float>(); m.decision_out = dec.as<int>();
+    m.levels = 1; m.log_its = 0;
+    m.lambda_up = cfg->lambda_up; m.lambda_down = cfg->lambda_down; m.lambda_floor = cfg->lambda_floor;
+    m.lambda_max = cfg->lambda_max; m.min_valid_fraction = cfg->min_valid_fraction;
+    launch_lm_step(sa, m, dsums.as<double>(), dxi.as<float>(), n, it_prev, c.s);
+    DVO_HIP(hipGetLastError());
+    std::vector<SeqState> hs(N);
+    DVO_HIP(hipMemcpyAsync(entry_out, table.p, table.bytes, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipMemcpyAsync(update, upd.p, upd.bytes, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipMemcpyAsync(decision, dec.p, dec.bytes, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipMemcpyAsync(hs.data(), state.p, state.bytes, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipStreamSynchronize(c.s));
+    for (size_t i = 0; i < N; i++) {
+        memcpy(xi_next + 6 * i, hs[i].xi, sizeof(float) * 6);
+        active[i] = hs[i].active;
+    }
     return DVO_OK;
 }
 

@@ -722,7 +722,7 @@ int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
     } else {
         rob.scales_src = nullptr;
     }
-    use_plan(rob.on || aff.on || geo.on);
+    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
 }
 
@@ -804,6 +804,70 @@ void Tracker::robust_end_push(hipStream_t s)
     rob.end_push(s);
     aff.end_push(s);
     geo.end_push(s);
+    lm.end_push(s);
+}
+
+int Tracker::set_step_control(const dvo_lm_config* c, hipStream_t s)
+{
+    const bool enable = c && c->mode != DVO_LM_OFF;
+    if (enable && !lm.table.p) {
+        lm.log_its = log_iterations();
+        DVO_TRY(lm.table.alloc(sizeof(dvo_lm_entry) * (size_t)n_seq));
+        DVO_TRY(lm.last.alloc(sizeof(dvo_lm_record) * (size_t)n_seq));
+        DVO_TRY(lm.log.alloc(sizeof(int) * 2 * (size_t)lm.log_its * (size_t)g.levels * (size_t)n_seq));
+        DVO_HIP(hipMemsetAsync(lm.table.p, 0, lm.table.bytes, s));
+        DVO_HIP(hipMemsetAsync(lm.last.p, 0, lm.last.bytes, s));
+        DVO_HIP(hipMemsetAsync(lm.log.p, 0, lm.log.bytes, s));
+    }
+    lm.on = enable;
+    if (enable) lm.cfg = *c;
+    use_plan(rob.on || aff.on || geo.on || lm.on);
+    return DVO_OK;
+}
+
+int Tracker::last_step_control(dvo_lm_record* rec, hipStream_t s) const
+{
+    DVO_HIP(hipMemcpyAsync(rec, lm.last.p, sizeof(dvo_lm_record) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+int Tracker::last_step_control_log(int seq, dvo_lm_log* out, hipStream_t s) const
+{
+    std::vector<int> rows((size_t)2 * lm.log_its * g.levels);
+    std::vector<int> n_iter(DVO_MAX_LEVELS);
+    dvo_lm_record last{};
+    DVO_HIP(hipMemcpyAsync(rows.data(), lm.log.as<int>() + (size_t)seq * rows.size(), sizeof(int) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(&last, lm.last.as<dvo_lm_record>() + (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    const int size = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = size;
+    out->levels = g.levels;
+    if (last.n_first == 0) return DVO_OK;   // the sequence did not track at that push: an empty log
+    for (int l = 0; l < g.levels; l++) {
+        const int n = n_iter[l] < lm.log_its ? n_iter[l] : lm.log_its;
+        out->n_iter[l] = n;
+        for (int it = 0; it < n; it++) {
+            const int* r = &rows[((size_t)l * lm.log_its + it) * 2];
+            memcpy(&out->lambda[l][it], &r[0], sizeof(float));
+            out->decision[l][it] = r[1];
+        }
+    }
+    return DVO_OK;
+}
+
+LmSolve Tracker::lm_solve_args(size_t q0, bool log) const
+{
+    LmSolve m{};
+    m.table = lm.table.as<dvo_lm_entry>() + q0;
+    m.last = lm.last.as<dvo_lm_record>() + q0;
+    m.log = log ? lm.log.as<int>() + 2 * q0 * (size_t)lm.log_its * g.levels : nullptr;
+    m.levels = g.levels; m.log_its = lm.log_its;
+    m.lambda_up = lm.cfg.lambda_up; m.lambda_down = lm.cfg.lambda_down; m.lambda_floor = lm.cfg.lambda_floor;
+    m.lambda_max = lm.cfg.lambda_max; m.min_valid_fraction = lm.cfg.min_valid_fraction;
+    return m;
 }
 
 int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
@@ -818,7 +882,7 @@ int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
     }
     geo.on = enable;
     if (enable) { geo.weight = c->weight; geo.max_diff = c->max_diff; }
-    use_plan(rob.on || aff.on || geo.on);
+    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
 }
 
@@ -908,7 +972,7 @@ int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
         aff.rows_src = nullptr;
         aff.mode = DVO_AFFINE_OFF;
     }
-    use_plan(rob.on || aff.on || geo.on);
+    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
 }
 
@@ -1052,6 +1116,7 @@ void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, b
     else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, sa.log != nullptr, prime, term_out, estimate_once), count, s);
     else if (rob.median()) launch_gn_solve_md(sa, r, median_solve_args(q0, sa.log != nullptr, prime, step_mn), count, s);
     else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
+    else if (lm.on) launch_gn_solve_lm(sa, lm_solve_args(q0, sa.log != nullptr), count, s);
     else launch_gn_solve(sa, count, s);
 }
 
@@ -1170,6 +1235,13 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
     if (geo.on) {   // "not tracked" until a solve says otherwise (before the fork)
         DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
         geo.tracked = true;
+    }
+    if (lm.on) {    // lambda0 and empty records (before the fork: every sub-batch reads its part)
+        LmBeginArgs la{};
+        la.table = lm.table.as<dvo_lm_entry>(); la.last = lm.last.as<dvo_lm_record>();
+        la.lambda0 = lm.cfg.lambda0; la.n_seq = n_seq;
+        launch_lm_begin(la, s);
+        lm.tracked = true;
     }
     const bool rob_adaptive = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;

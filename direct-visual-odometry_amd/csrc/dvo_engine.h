@@ -319,6 +319,15 @@ struct GeometricTerm : OptInTerm {
     DevBuf log;             // [n_seq][levels][log_its][2] (n_geo, S29).  last: [n_seq][4] (n_geo, mean_sq, tracked, 0)
 };
 
+// Step control of a batch: damped Gauss-Newton with step acceptance (dvo_batch_set_step_control).  Allocated by the
+// first enable.  While on, the tracker runs the plan of launch pairs (Tracker::lv_rw): the plain k_track_gn + k_gn_solve_lm on every
+// level.  The tables are offset by the sub-batch's first sequence, like RobustEntry.
+struct StepControl : OptInTerm {
+    dvo_lm_config cfg{};
+    int log_its = 0;        // iterations per level of the step-control log
+    DevBuf table, log;      // [n_seq] dvo_lm_entry; [n_seq][levels][log_its][2] (lambda bits, decision).  last: [n_seq] dvo_lm_record
+};
+
 // How one pyramid level is launched.  Decided once by Tracker::init and fixed from then on: Tracker::gn_args and Tracker::solve_args
 // copy the geometry from here into every argument block, and the launchers take the kernel instance from here.
 struct LevelPlan {
@@ -360,15 +369,16 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv[DVO_MAX_LEVELS];
     // Both plans are decided by init: lv_plain is what the configuration asks for, lv_rw the weighted plan (launch pairs of the
     // global-gather kernel on every level, whatever track_fused_tiles, gn_use_lds_patch, track_single_launch and the batch size say).
-    // lv / tile_margin are whichever is in force (use_plan, called by set_robust, set_affine and set_geometric: any opt-in term runs
-    // the weighted plan).
+    // lv / tile_margin are whichever is in force (use_plan, called by set_robust, set_affine, set_geometric and set_step_control: any
+    // opt-in term runs the weighted plan).
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
     int margin_plain = 0;
     void use_plan(bool opt_in_term);
     int log_iterations() const;   // iterations per level an opt-in term's log holds (set_affine, set_geometric)
     // One iteration's launch pair of whichever term is on -- the geometric term with affine brightness, else the
     // geometric term, else affine brightness (with robust weights when they
-    // are on too), else robust weights, else the plain kernels: the one place that decides.  `ga` / `sa` view `count`
+    // are on too), else robust weights, else step control (the plain tile kernel with k_gn_solve_lm), else the plain
+    // kernels: the one place that decides.  `ga` / `sa` view `count`
     // sequences (their SeqState offset is every table's).
     //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
     //   prime: the priming pair of affine ESTIMATE mode or of the median robust scale
@@ -386,6 +396,10 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s);   // both on (validated by the caller)
     int last_geometric(dvo_geometric_record* rec, hipStream_t s) const;
     int last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const;
+    StepControl lm;
+    int set_step_control(const dvo_lm_config* c, hipStream_t s);        // validated by the caller; nullptr / OFF: off
+    int last_step_control(dvo_lm_record* rec, hipStream_t s) const;
+    int last_step_control_log(int seq, dvo_lm_log* out, hipStream_t s) const;
     AffineBrightness aff;
     int set_affine(const dvo_affine_config* c, hipStream_t s);          // validated by the caller; nullptr / OFF: off
     int set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s);
@@ -476,6 +490,7 @@ private:
     GeoSolve geo_solve_args(size_t q0, bool log, double* sums_out) const;
     AffineGn affine_gn_args(size_t q0, bool prime) const;
     AffineSolve affine_solve_args(size_t q0, bool log, bool prime, double* moments_out, bool estimate_once) const;
+    LmSolve lm_solve_args(size_t q0, bool log) const;
 };
 
 struct Keyframe {  // System::Frame of one sequence, plus the age map and pose (frame.hpp:72-144)

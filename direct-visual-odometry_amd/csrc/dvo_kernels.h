@@ -325,6 +325,30 @@ void launch_track_gn_zab(const struct GnArgs& a, const AffineGn& f, const GeoGn&
                          int grid_seqs = 0);
 void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s);
 
+// Step control: damped Gauss-Newton with step acceptance (dvo_batch_set_step_control; the contract is in include/dvo.h).
+// One dvo_lm_entry per sequence: the accepted pose, its sums and lambda.  The tile kernel is the plain k_track_gn; only the solve
+// differs.  Float32 and integer decisions, so the host replica has the same bits.
+struct LmSolve {       // last argument of k_gn_solve_lm
+    dvo_lm_entry* table;        // indexed like SolveArgs::state
+    dvo_lm_record* last;        // [n_seq]: decision counts, lambda and the finest level's accepted residual (n_first == 0: not tracked)
+    int* log;                   // optional [n_seq][levels][log_its][2]: (bits of the lambda the solve used, decision) of every logged iteration
+    float* upd_out;             // optional [n_seq][6] (dvo_op_lm_step): the step
+    int* decision_out;          // optional [n_seq] (dvo_op_lm_step)
+    int levels, log_its;
+    float lambda_up, lambda_down, lambda_floor, lambda_max, min_valid_fraction;
+};
+struct LmBeginArgs {   // k_lm_begin: the table and the records at the start of a tracking call
+    dvo_lm_entry* table; dvo_lm_record* last;
+    float lambda0;
+    int n_seq;
+};
+void launch_lm_begin(const LmBeginArgs& a, hipStream_t s);
+// the twin of launch_gn_solve with step control (launch pairs only; its tile launch is launch_track_gn)
+void launch_gn_solve_lm(const SolveArgs& a, const LmSolve& m, int n_seq, hipStream_t s);
+// dvo_op_lm_step: k_gn_solve_lm's serial tail on given sums, one case per thread.  a.state: [n] scratch SeqState, set up by the kernel
+// from xi_eval (Tc = exp(xi), pose = float(exp(-xi)), iter = it_prev); m.table: the entries, updated in place.
+void launch_lm_step(const SolveArgs& a, const LmSolve& m, const double* sums, const float* xi_eval, int n, int it_prev, hipStream_t s);
+
 // k_track_persist: the whole of Tracker::track for ONE sequence in one launch (a dvo_vo handle).
 struct PersistLevel {
     const float* obj_gray; const float* ref_gray; const float* ref_depth; const float* ref_wgt;

@@ -3066,6 +3066,178 @@ __global__ void __launch_bounds__(64) k_pose_algebra(int op, int n, const double
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Step control (dvo_batch_set_step_control; the contract is in include/dvo.h): damped Gauss-Newton with step acceptance.
+// (Kept behind every older kernel of this file on purpose: the device code of the kernels above is then laid out as it was.)
+// lm_solve_finish: solve_finish for a batch with step control, by ONE thread per sequence.  `tot` = the 29 sums of the evaluation at the
+// pose the state holds (xi / Tc on entry).  It decides (FIRST / ACCEPT / REJECT against the sequence's entry, float32 and integers),
+// selects the 27 sums of whichever evaluation the entry now holds into ONE set, the lane's own row `tot` (overwritten) -- the entry is
+// written before the serial chain, so no second system is live across solve6 and the SE(3) chain -- damps the diagonal, solves and
+// composes the trial pose from the entry's Tc.  A sequence that stays active gets the trial pose, one that stops the accepted pose, read back from the entry.
+// Shared by k_gn_solve_lm and k_lm_step (dvo_op_lm_step).
+__device__ __forceinline__ void lm_solve_finish(const SolveArgs& a, const LmSolve& lm, const int seq, SeqState& st, double* tot,
+                                                const int first, const int it_prev, float (&xi)[6], double (&Tc)[12])
+{
+    dvo_lm_entry& e = lm.table[seq];
+    const int n_valid = (int)tot[28];
+    const float residual = n_valid > 0 ? (float)tot[27] / (float)n_valid : -1.0f;   // solve_finish's own expression: the logged bits
+    float lambda = e.lambda;
+    int n_acc = e.n_valid;
+    float res_acc = e.residual;
+    int decision = DVO_LM_FIRST;
+    if (!first) {
+        const bool ok = n_valid > 0 && (float)n_valid >= lm.min_valid_fraction * (float)n_acc && residual <= res_acc;   // (false for NaN)
+        decision = ok ? DVO_LM_ACCEPT : DVO_LM_REJECT;
+        lambda = ok ? lambda * lm.lambda_down : fminf(fmaxf(lambda, lm.lambda_floor) * lm.lambda_up, lm.lambda_max);
+    }
+    double* S = tot;   // (the lane's own row: the system lives there, as in solve_finish, so solve6's out-of-line branch needs no copy)
+    double sum_r2;
+    if (decision != DVO_LM_REJECT) {   // this evaluation becomes the entry
+#pragma unroll
+        for (int i = 0; i < 21; i++) e.H[i] = S[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { e.g[i] = S[21 + i]; e.xi[i] = xi[i]; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) e.Tc[i] = Tc[i];
+#pragma unroll
+        for (int i = 0; i < 9; i++) e.pose[i] = st.pose.R[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) e.pose[9 + i] = st.pose.t[i];
+        sum_r2 = tot[27]; n_acc = n_valid; res_acc = residual;
+        e.sum_r2 = sum_r2; e.n_valid = n_acc; e.residual = res_acc;
+    } else {                           // the entry stays: step from it again, with more damping
+#pragma unroll
+        for (int i = 0; i < 21; i++) S[i] = e.H[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) { S[21 + i] = e.g[i]; xi[i] = e.xi[i]; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) Tc[i] = e.Tc[i];
+        sum_r2 = e.sum_r2;
+    }
+    e.lambda = lambda;
+    if (a.result) {  // the quality record: the accepted sums (the step and the pose follow below)
+        dvo_gn_result& r = a.result[seq];
+        for (int i = 0; i < 21; i++) r.H[i] = S[i];
+        for (int i = 0; i < 6; i++) r.g[i] = S[21 + i];
+        r.sum_r2 = sum_r2;
+        r.n_valid = n_acc;
+        r.residual = res_acc;
+    }
+    const double damp = 1.0 + (double)lambda;
+    S[0] *= damp; S[6] *= damp; S[11] *= damp; S[15] *= damp; S[18] *= damp; S[20] *= damp;   // the diagonal of the upper triangle
+    float upd[6] = {0, 0, 0, 0, 0, 0};
+    if (n_acc > 0) solve6(S, S + 21, upd);
+    Pose np;
+    const bool updated = se3_update_pose(Tc, upd, xi, np);   // xi / Tc: the accepted pose on entry, the trial pose when it returns true
+    double nrm = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; i++) nrm += (double)upd[i] * (double)upd[i];
+    nrm = sqrt(nrm);
+    const int it = first ? 0 : it_prev;
+    int active = 1;
+    if (a.fixed_iterations > 0) {
+        active = (it + 1 < a.fixed_iterations) ? 1 : 0;
+    } else if (nrm < (double)a.min_update || res_acc < a.min_residual || it + 1 >= a.max_iterations) {
+        active = 0;
+    }
+    if (!updated || !(nrm < __builtin_inf())) active = 0;   // a non-finite update ends the level
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) st.xi[i] = xi[i];
+#pragma unroll
+        for (int i = 0; i < 12; i++) st.Tc[i] = Tc[i];
+        st.pose = np;
+    } else {         // the level ends on the accepted pose
+#pragma unroll
+        for (int i = 0; i < 6; i++) { xi[i] = e.xi[i]; st.xi[i] = xi[i]; }
+#pragma unroll
+        for (int i = 0; i < 12; i++) st.Tc[i] = e.Tc[i];
+#pragma unroll
+        for (int i = 0; i < 9; i++) st.pose.R[i] = e.pose[i];
+#pragma unroll
+        for (int i = 0; i < 3; i++) st.pose.t[i] = e.pose[9 + i];
+    }
+    if (a.log && it < DVO_MAX_ITERATIONS) {
+        dvo_track_log& lg = a.log[seq];
+        lg.n_iter[a.level] = it + 1;
+        lg.residual[a.level][it] = residual;
+        lg.update_norm[a.level][it] = (float)nrm;
+        lg.n_valid[a.level][it] = n_valid;
+#pragma unroll
+        for (int i = 0; i < 6; i++) lg.xi_after[a.level][it][i] = xi[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) lg.xi_update[a.level][it][i] = upd[i];
+    }
+    if (a.result) {
+        dvo_gn_result& r = a.result[seq];
+        for (int i = 0; i < 6; i++) { r.xi_update[i] = upd[i]; r.xi_next[i] = xi[i]; }
+    }
+    if (lm.log && it < lm.log_its) {
+        int* lg = lm.log + (((size_t)seq * lm.levels + a.level) * lm.log_its + it) * 2;
+        lg[0] = __float_as_int(lambda); lg[1] = decision;
+    }
+    dvo_lm_record& rec = lm.last[seq];
+    if (decision == DVO_LM_FIRST) rec.n_first += 1;
+    else if (decision == DVO_LM_ACCEPT) rec.n_accepted += 1;
+    else rec.n_rejected += 1;
+    rec.lambda = lambda;
+    if (a.level == lm.levels - 1) rec.residual = res_acc;
+    if (lm.upd_out) {
+#pragma unroll
+        for (int i = 0; i < 6; i++) lm.upd_out[6 * (size_t)seq + i] = upd[i];
+    }
+    if (lm.decision_out) lm.decision_out[seq] = decision;
+    st.iter = it + 1;
+    st.active = active;
+    if (active && a.list_out) a.list_out[4 + atomicAdd(&a.list_out[0], 1)] = seq;
+    if (a.counters) {  // profile: evaluated pixels / sequence-iterations
+        atomicAdd(&a.counters[0], (unsigned long long)a.level_pixels);
+        atomicAdd(&a.counters[1], 1ull);
+    }
+}
+
+// k_gn_solve_lm: k_gn_solve for a batch with step control: solve_gather, then lm_solve_finish.
+__global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_lm(SolveArgs a, LmSolve lm)
+{
+    __shared__ double tot[DVO_SOLVE_SEQ][32];
+    __shared__ double part[2][DVO_SOLVE_GROUPS][32];
+    int my_seq = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, [](int, int, int) {})) return;
+    lm_solve_finish(a, lm, my_seq, a.state[my_seq], tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc);
+}
+
+// k_lm_begin: the entry table and the records at the start of a tracking call, one thread per sequence: lambda = lambda0, nothing
+// accepted yet (the first evaluation of the coarsest level is FIRST and overwrites the rest), and "not tracked" until a solve says
+// otherwise.
+__global__ void __launch_bounds__(256) k_lm_begin(LmBeginArgs a)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= a.n_seq) return;
+    dvo_lm_entry& e = a.table[i];
+    e.lambda = a.lambda0; e.n_valid = 0; e.residual = -1.0f; e.reserved = 0;
+    dvo_lm_record& r = a.last[i];
+    r.n_first = 0; r.n_accepted = 0; r.n_rejected = 0; r.lambda = 0.0f; r.residual = 0.0f;
+}
+
+// k_lm_step: lm_solve_finish on given sums, one case per thread (dvo_op_lm_step): the state of xi_eval is set up as seed_state does.
+__global__ void __launch_bounds__(64) k_lm_step(SolveArgs a, LmSolve lm, const double* __restrict__ sums, const float* __restrict__ xi_eval,
+                                                int n, int it_prev)
+{
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    SeqState& st = a.state[i];
+    float xi[6];
+    double xd[6], Tc[12], tot[29];
+    for (int k = 0; k < 6; k++) { xi[k] = xi_eval[6 * (size_t)i + k]; xd[k] = xi[k]; st.xi[k] = xi[k]; }
+    pose_from_xi(xi, -1.0f, st.pose);
+    se3_exp_d(xd, Tc, Tc + 9);
+    for (int k = 0; k < 12; k++) st.Tc[k] = Tc[k];
+    for (int k = 0; k < 29; k++) tot[k] = sums[29 * (size_t)i + k];
+    lm_solve_finish(a, lm, i, st, tot, a.ignore_active, it_prev, xi, Tc);
+}
+
 // (the mapping kernels -- propagate, regularize, depth update, keyframe promotion -- live in dvo_map_kernels.hip)
 
 // ------------------------------------------------------------------------------------------------
@@ -3618,6 +3790,18 @@ void launch_median_begin(const MedianBeginArgs& a, hipStream_t s)
 void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
+}
+
+void launch_gn_solve_lm(const SolveArgs& a, const LmSolve& m, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_lm, a, n_seq, s, m); }
+
+void launch_lm_begin(const LmBeginArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_lm_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
+}
+
+void launch_lm_step(const SolveArgs& a, const LmSolve& m, const double* sums, const float* xi_eval, int n, int it_prev, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_lm_step, dim3(cdiv(n, 64)), dim3(64), 0, s, a, m, sums, xi_eval, n, it_prev);
 }
 
 void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s)

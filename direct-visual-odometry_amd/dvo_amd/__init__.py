@@ -142,6 +142,43 @@ GEOMETRIC_LOG_DTYPE = np.dtype({"names": [f[0] for f in GeometricLog._fields_],
                                 "itemsize": C.sizeof(GeometricLog)})
 
 
+class LmConfig(C.Structure):
+    """dvo_lm_config (include/dvo.h): step control (damped Gauss-Newton with step acceptance) of a batch."""
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("lambda0", C.c_float), ("lambda_up", C.c_float), ("lambda_down", C.c_float),
+                ("lambda_floor", C.c_float), ("lambda_max", C.c_float), ("min_valid_fraction", C.c_float)]
+
+
+class LmRecord(C.Structure):
+    """dvo_lm_record (include/dvo.h): the decisions of the last push / call, the final lambda and the finest level's accepted residual."""
+    _fields_ = [("n_first", C.c_int), ("n_accepted", C.c_int), ("n_rejected", C.c_int), ("lambda_", C.c_float), ("residual", C.c_float)]
+
+
+class LmLog(C.Structure):
+    """dvo_lm_log (include/dvo.h): the lambda every logged iteration's solve used and its decision, indexed like TrackLog."""
+    _fields_ = [("struct_size", C.c_int), ("levels", C.c_int), ("n_iter", C.c_int * MAX_LEVELS),
+                ("lambda_", (C.c_float * MAX_ITERATIONS) * MAX_LEVELS), ("decision", (C.c_int * MAX_ITERATIONS) * MAX_LEVELS)]
+
+
+class LmEntry(C.Structure):
+    """dvo_lm_entry (include/dvo.h): a sequence's accepted pose, the sums of its evaluation and lambda."""
+    _fields_ = [("Tc", C.c_double * 12), ("H", C.c_double * 21), ("g", C.c_double * 6), ("sum_r2", C.c_double), ("xi", C.c_float * 6),
+                ("pose", C.c_float * 12), ("n_valid", C.c_int), ("residual", C.c_float), ("lambda_", C.c_float), ("reserved", C.c_int)]
+
+
+LM_RECORD_DTYPE = np.dtype([("n_first", np.int32), ("n_accepted", np.int32), ("n_rejected", np.int32), ("lambda", np.float32),
+                            ("residual", np.float32)])
+LM_LOG_DTYPE = np.dtype({"names": ["struct_size", "levels", "n_iter", "lambda", "decision"],
+                         "formats": [np.int32, np.int32, (np.int32, MAX_LEVELS), (np.float32, (MAX_LEVELS, MAX_ITERATIONS)),
+                                     (np.int32, (MAX_LEVELS, MAX_ITERATIONS))],
+                         "offsets": [getattr(LmLog, f[0]).offset for f in LmLog._fields_],
+                         "itemsize": C.sizeof(LmLog)})
+LM_ENTRY_DTYPE = np.dtype({"names": ["Tc", "H", "g", "sum_r2", "xi", "pose", "n_valid", "residual", "lambda", "reserved"],
+                           "formats": [("<f8", (12,)), ("<f8", (21,)), ("<f8", (6,)), "<f8", ("<f4", (6,)), ("<f4", (12,)), "<i4", "<f4",
+                                       "<f4", "<i4"],
+                           "offsets": [getattr(LmEntry, f[0]).offset for f in LmEntry._fields_],
+                           "itemsize": C.sizeof(LmEntry)})
+
+
 class GnProfile(C.Structure):
     _fields_ = [("gn_ms", C.c_double), ("gn_launches", C.c_uint64), ("gn_pixels", C.c_uint64),
                 ("gn_iterations", C.c_uint64)]
@@ -198,6 +235,8 @@ EXPORTS = [
     "dvo_batch_set_robust_median", "dvo_batch_last_robust_log", "dvo_batch_last_robust_histogram", "dvo_op_gn_step_robust_median",
     "dvo_batch_set_photometric", "dvo_batch_get_photometric", "dvo_vo_set_photometric", "dvo_debug_batch_photometric_gain",
     "dvo_debug_batch_last_pyramid_kernel",
+    "dvo_lm_config_default", "dvo_batch_set_step_control", "dvo_batch_last_step_control", "dvo_batch_last_step_control_log",
+    "dvo_op_lm_step",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -217,6 +256,9 @@ MEDIAN_BINS = 256
 AFFINE_OFF, AFFINE_ESTIMATE, AFFINE_GIVEN = 0, 1, 2
 # the geometric (depth) term (Batch.set_geometric): include/dvo.h
 GEOMETRIC_OFF, GEOMETRIC_ON = 0, 1
+# step control (Batch / MonoBatch .set_step_control) and its decisions: include/dvo.h
+LM_OFF, LM_ON = 0, 1
+LM_FIRST, LM_ACCEPT, LM_REJECT = 1, 2, 3
 # keyframe depth fusion (Batch.set_keyframe_fusion): include/dvo.h
 KF_FUSION_OFF, KF_FUSION_ON = 0, 1
 # launch form of a level (Batch / MonoBatch .level_plan): include/dvo.h
@@ -570,6 +612,33 @@ def op_gn_step_geometric_affine(obj_gray, obj_depth, obj_sigma, ref_gray, ref_de
     return dict(H=np.array(out.H[:]), g=np.array(out.g[:]), sum_r2=out.sum_r2, n_valid=out.n_valid,
                 xi_update=np.array(out.xi_update[:], np.float32), residual=np.float32(out.residual),
                 xi_next=np.array(out.xi_next[:], np.float32), n_geo=int(sums[0]), sum_sq=float(sums[1]), moments=mom, next_ab=nxt)
+
+
+def lm_default_config():
+    """dvo_lm_config_default: ON, lambda0 1, up 4, down 0.5, floor 1e-4, max 1e6, min_valid_fraction 0.5"""
+    c = LmConfig()
+    lib().dvo_lm_config_default(C.byref(c))
+    return c
+
+
+def op_lm_step(sums, xi_eval, entries, lm=None, level_first=False, it_prev=0, cfg=None, dev=0):
+    """The serial tail of the step-control solve on given sums (dvo_op_lm_step, include/dvo.h): sums float64 [n][29], xi_eval float32
+    [n][6], entries an array [n] of LM_ENTRY_DTYPE; lm an LmConfig (None: the defaults), cfg a Config for the stop constants.
+    -> dict(entry [n] LM_ENTRY_DTYPE, update [n][6], xi_next [n][6], decision [n], active [n])"""
+    sums = np.ascontiguousarray(sums, dtype=np.float64).reshape(-1, 29)
+    n = sums.shape[0]
+    xi_eval = f32(xi_eval).reshape(n, 6)
+    entries = np.ascontiguousarray(entries, dtype=LM_ENTRY_DTYPE).reshape(n)
+    lm = lm if lm is not None else lm_default_config()
+    cfg = cfg if cfg is not None else default_config()
+    out = np.zeros(n, LM_ENTRY_DTYPE)
+    upd = np.zeros((n, 6), np.float32); nxt = np.zeros((n, 6), np.float32)
+    dec = np.zeros(n, np.int32); act = np.zeros(n, np.int32)
+    _check(lib().dvo_op_lm_step(dev, n, sums.ctypes.data_as(C.c_void_p), fp(xi_eval), entries.ctypes.data_as(C.c_void_p), C.byref(lm),
+                                1 if level_first else 0, int(it_prev), int(cfg.max_iterations), int(cfg.fixed_iterations),
+                                C.c_float(cfg.min_update), C.c_float(cfg.min_residual), out.ctypes.data_as(C.c_void_p), fp(upd), fp(nxt),
+                                dec.ctypes.data_as(C.c_void_p), act.ctypes.data_as(C.c_void_p)))
+    return dict(entry=out, update=upd, xi_next=nxt, decision=dec, active=act)
 
 
 def track(obj_gray, ref_gray, ref_depth, ref_sigma, K, levels, culls, cfg=None, dev=0):
@@ -1078,6 +1147,37 @@ class _GeometricTerm:
         return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), n_geo=rec["n_geo"].copy(), sum_sq=rec["sum_sq"].copy())
 
 
+class _StepControl:
+    """Step control of the tracking, shared by Batch and MonoBatch (dvo_batch_set_step_control, include/dvo.h)."""
+
+    def set_step_control(self, mode=LM_ON, lambda0=1.0, lambda_up=4.0, lambda_down=0.5, lambda_floor=1e-4, lambda_max=1e6,
+                         min_valid_fraction=0.5):
+        """LM_ON: from the next push / call on every Gauss-Newton step is damped, compared with the pose it started from and taken
+        only when it did not make the residual worse; LM_OFF or None: the plain iteration."""
+        if mode is None:
+            _check(lib().dvo_batch_set_step_control(self._p, None))
+            return
+        c = LmConfig(C.sizeof(LmConfig), int(mode), float(lambda0), float(lambda_up), float(lambda_down), float(lambda_floor),
+                     float(lambda_max), float(min_valid_fraction))
+        _check(lib().dvo_batch_set_step_control(self._p, C.byref(c)))
+
+    def last_step_control(self):
+        """record array [n_seq] (n_first, n_accepted, n_rejected, lambda, residual) of the last push (zeros: not tracked); synchronises."""
+        rec = np.zeros(self.n_seq, LM_RECORD_DTYPE)
+        _check(lib().dvo_batch_last_step_control(self._p, rec.ctypes.data_as(C.c_void_p)))
+        return rec
+
+    def last_step_control_log(self, seq):
+        """dict of the lambda and the decision of every logged iteration of `seq` at the last push (dvo_lm_log); synchronises."""
+        lg = LmLog()
+        lg.struct_size = C.sizeof(LmLog)
+        _check(lib().dvo_batch_last_step_control_log(self._p, int(seq), C.byref(lg)))
+        rec = np.frombuffer(lg, LM_LOG_DTYPE)[0]
+        return dict(levels=int(rec["levels"]), n_iter=rec["n_iter"].copy(), lambda_=rec["lambda"].copy(), decision=rec["decision"].copy())
+
+    op_lm_step = staticmethod(op_lm_step)
+
+
 class _KeyframeFusion:
     """Depth fusion into the keyframes of a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_fusion, include/dvo.h)."""
 
@@ -1117,7 +1217,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm, _KeyframeFusion):
+class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm, _KeyframeFusion, _StepControl):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -1283,7 +1383,7 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrigh
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness):
+class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _StepControl):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

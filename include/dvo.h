@@ -850,6 +850,91 @@ int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log);
  * mode that is off, a mono batch, robust weights on (dvo_batch_set_robust_weights keeps refusing while the geometric term is on)
  * -> DVO_ERR_BAD_ARGUMENT.  Robust weights with the geometric term, mono batches and dvo_vo handles are out of scope. */
 int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo, const dvo_affine_config* aff);
+/* ---- step control: damped Gauss-Newton with step acceptance (both batch kinds) ---------------------------------------------------
+ * By default the tracker takes every Gauss-Newton step it computes.  dvo_batch_set_step_control makes every later push / call compare
+ * the cost at the new pose with the cost at the old one, keep the better pose and damp when it got worse (Levenberg-Marquardt).  The
+ * per-pixel kernels do not change: every evaluation is the plain one, at the pose the sequence holds.  Decisions are float32 and
+ * integer, IEEE, no contraction, so a host replica has the device's bits.
+ * Per sequence a dvo_lm_entry lives on the device: the accepted twist xi with its Tc = exp(xi) in double and pose = float(exp(-xi)),
+ * the accepted evaluation's 21 + 6 sums, sum_r2, n_valid and residual ((float)sum_r2 / (float)n_valid, -1 without pixels), and lambda.
+ * Every tracking call starts with lambda = lambda0; lambda carries across levels.  Each iteration of a level evaluates the pose the
+ * sequence holds; with residual and n_valid of that evaluation, and residual_acc and n_acc of the entry, the solve then does:
+ *   1. Decide.  The first evaluation of a level is DVO_LM_FIRST: accepted unconditionally, lambda unchanged.  Otherwise
+ *      DVO_LM_ACCEPT iff n_valid > 0 && (float)n_valid >= min_valid_fraction * (float)n_acc && residual <= residual_acc (a NaN
+ *      residual rejects, a tie accepts), else DVO_LM_REJECT.  FIRST and ACCEPT store this evaluation as the entry; ACCEPT sets
+ *      lambda = lambda * lambda_down; REJECT keeps the entry and sets lambda = fminf(fmaxf(lambda, lambda_floor) * lambda_up, lambda_max).
+ *   2. Step.  From the entry, whichever evaluation it now holds: the six diagonal sums of H times 1.0 + (double)lambda, the 6x6 solve
+ *      of the plain tracker, trial = log(exp(xi_acc) exp(upd)) by the plain tracker's pose update on the entry's Tc.  With n_acc == 0
+ *      the update is zero.
+ *   3. Stop tests.  fixed_iterations > 0: the level runs that many evaluations.  Otherwise it stops when |upd| < min_update, when
+ *      residual_acc < min_residual, or after max_iterations evaluations.  In either mode a non-finite update (a component of upd or of
+ *      the composed twist that is not finite) also ends the level.  A sequence that stays active holds the trial pose; a sequence that
+ *      stops holds the accepted pose.
+ * A level therefore always ends on an evaluated, accepted pose, and on each level the accepted residuals never increase.  The step
+ * computed in the iteration that stops is not taken: with min_residual above a level's first residual the level ends on the pose it
+ * started from, so step control is meant to run with min_residual = 0 (stop on the update norm).
+ * The track log keeps its meaning per evaluation (residual, n_valid of the evaluation; xi_update, update_norm of the step computed in
+ * that iteration); xi_after is the pose the sequence holds after the iteration.  The quality record (dvo_batch_set_track_quality)
+ * receives the accepted sums of the finest level: H, g, sum_r2, n_valid, residual and the covariance describe the returned pose.
+ * Anchor: with lambda0 = 0, inputs that never reject and a level started at the same pose, every evaluated pose and every logged
+ * sum of that level equals the plain batch's bit for bit; only the pose the level ends on is one step behind.
+ * Takes effect from the next push / call; cfg == NULL or mode == DVO_LM_OFF goes back to the plain launches, and a batch that never
+ * calls this runs exactly the launches it always ran.  While on, every level runs launch pairs (k_track_gn + k_gn_solve_lm) whatever
+ * track_fused_tiles, gn_use_lds_patch and track_single_launch say.
+ * dvo_batch_last_step_control: rec[n_seq] (host, synchronises) -- per sequence of the last push / call the FIRST, ACCEPT and REJECT
+ * decisions counted over all levels, the lambda it ended on and the accepted residual of the finest level; all zeros for a sequence
+ * that did not track.  dvo_batch_last_step_control_log: per level and logged iteration, indexed like dvo_track_log, the lambda that
+ * iteration's solve used (after its decision) and the decision; empty (n_iter all 0) for a sequence that did not track.
+ * Errors, returned before anything is enqueued: a NULL handle, struct_size != sizeof(dvo_lm_config), a mode outside the set, a lambda
+ * parameter that is not finite or negative, lambda_up <= 1, lambda_down outside (0, 1], lambda_floor <= 0, lambda_max < lambda_floor,
+ * min_valid_fraction outside [0, 1], robust weights, the median scale, affine brightness or the geometric term on ->
+ * DVO_ERR_BAD_ARGUMENT; while step control is on, dvo_batch_set_robust_weights, dvo_batch_set_robust_median,
+ * dvo_batch_set_affine_brightness, dvo_batch_set_geometric and dvo_batch_set_geometric_affine refuse to turn their term on.  A read
+ * before a push / call that ran with step control on -> DVO_ERR_NOT_READY.  Step control together with those terms, and dvo_vo
+ * handles, are out of scope. */
+#define DVO_LM_OFF 0
+#define DVO_LM_ON  1
+#define DVO_LM_FIRST  1
+#define DVO_LM_ACCEPT 2
+#define DVO_LM_REJECT 3
+typedef struct dvo_lm_config {
+    int   struct_size;          /* sizeof(dvo_lm_config) */
+    int   mode;                 /* DVO_LM_* */
+    float lambda0;              /* >= 0: lambda at the start of every tracking call */
+    float lambda_up;            /* > 1 */
+    float lambda_down;          /* (0, 1] */
+    float lambda_floor;         /* > 0: a rejected step raises lambda from at least this */
+    float lambda_max;           /* >= lambda_floor */
+    float min_valid_fraction;   /* [0, 1]: an evaluation with fewer pixels than this fraction of the accepted one's is rejected */
+} dvo_lm_config;
+typedef struct dvo_lm_record {
+    int   n_first, n_accepted, n_rejected;   /* decisions of the last push / call, all levels */
+    float lambda;                            /* the lambda the sequence ended on */
+    float residual;                          /* the accepted residual of the finest level */
+} dvo_lm_record;
+typedef struct dvo_lm_log {
+    int   struct_size;    /* sizeof(dvo_lm_log), set by the caller */
+    int   levels;
+    int   n_iter[DVO_MAX_LEVELS];
+    float lambda[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];     /* the lambda the iteration's solve used */
+    int   decision[DVO_MAX_LEVELS][DVO_MAX_ITERATIONS];   /* DVO_LM_FIRST / ACCEPT / REJECT */
+} dvo_lm_log;
+typedef struct dvo_lm_entry {
+    double Tc[12];        /* exp(xi) in double: R row major, then t */
+    double H[21];         /* the accepted evaluation's sums, as dvo_gn_result */
+    double g[6];
+    double sum_r2;
+    float  xi[6];         /* the accepted twist */
+    float  pose[12];      /* float(exp(-xi)): R row major, then t */
+    int    n_valid;
+    float  residual;
+    float  lambda;
+    int    reserved;
+} dvo_lm_entry;
+void dvo_lm_config_default(dvo_lm_config* cfg);   /* ON, lambda0 1, up 4, down 0.5, floor 1e-4, max 1e6, min_valid_fraction 0.5 */
+int dvo_batch_set_step_control(dvo_batch* b, const dvo_lm_config* cfg);            /* both kinds; from the next push / call on */
+int dvo_batch_last_step_control(dvo_batch* b, dvo_lm_record* rec);                /* [n_seq], host, synchronises */
+int dvo_batch_last_step_control_log(dvo_batch* b, int seq, dvo_lm_log* log);      /* host, synchronises */
 /* Profile of the mapping stages (cfg.profile = 1): hipEvent-bracketed durations on the handle's stream, summed over the frames
  * since the last reset.  depth_update = k_age_table + k_depth_update (Mapper::update), regularize = k_regularize_redecimate
  * (Mapper::regularize + Frame::updateDepth*), propagate = the three k_propagate_* passes (Mapper::propagate). */
@@ -1058,6 +1143,16 @@ int dvo_op_se3_concatenate(int dev, const float a[6], const float b[6], float ou
  *   op 5  the Jacobi eigensolver       in H[21]                          out eigenvalues[6] (unsorted), V[36] (columns, row major)
  * DVO_ERR_BAD_ARGUMENT for a null pointer, n < 1 or another op. */
 int dvo_op_pose_algebra(int dev, int op, int n, const double* in, double* out);
+/* The serial tail of the step-control solve (dvo_batch_set_step_control: k_gn_solve_lm's decide / step / stop rules) ON THE DEVICE for
+ * n cases at once, on given sums: sums[n][29] (H[21], g[6], sum_r2, n_valid as a double) of an evaluation at the twist xi_eval[n][6],
+ * against the entry entry_in[n] (of which xi, Tc, pose, the sums, n_valid, residual and lambda are read as they are).  level_first:
+ * the evaluation is a level's first; it_prev: the iterations the level has done before it (ignored with level_first); the stop
+ * constants are dvo_config's.  Out: entry_out[n], update[n][6] (the step computed from the entry), xi_next[n][6] (the pose the
+ * sequence holds after the iteration), decision[n] (DVO_LM_*) and active[n] (1: the level goes on).  cfg as validated by
+ * dvo_batch_set_step_control, mode DVO_LM_ON.  DVO_ERR_BAD_ARGUMENT for a null pointer, n < 1 or a config that is refused there. */
+int dvo_op_lm_step(int dev, int n, const double* sums, const float* xi_eval, const dvo_lm_entry* entry_in, const dvo_lm_config* cfg,
+                   int level_first, int it_prev, int max_iterations, int fixed_iterations, float min_update, float min_residual,
+                   dvo_lm_entry* entry_out, float* update, float* xi_next, int* decision, int* active);
 
 /* ------------------------------------------------------------------------------------------------
  * Dataset front-end: what src/core/loader.cpp + include/core/loader.hpp do with OpenCV.

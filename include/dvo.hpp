@@ -268,6 +268,26 @@ public:
         check(dvo_batch_last_geometric_log(b_, seq, &lg));
         return lg;
     }
+    // step control from the next push / call on (dvo_batch_set_step_control): damped Gauss-Newton with step acceptance; DVO_LM_OFF turns it off
+    void setStepControl(int mode = DVO_LM_ON, float lambda0 = 1.0f, float lambda_up = 4.0f, float lambda_down = 0.5f, float lambda_floor = 1e-4f,
+                        float lambda_max = 1e6f, float min_valid_fraction = 0.5f)
+    {
+        dvo_lm_config c{(int)sizeof(dvo_lm_config), mode, lambda0, lambda_up, lambda_down, lambda_floor, lambda_max, min_valid_fraction};
+        check(dvo_batch_set_step_control(b_, &c));
+    }
+    std::vector<dvo_lm_record> lastStepControl()   // [n_seq]
+    {
+        std::vector<dvo_lm_record> out(n_);
+        check(dvo_batch_last_step_control(b_, out.data()));
+        return out;
+    }
+    dvo_lm_log lastStepControlLog(int seq)
+    {
+        dvo_lm_log lg{};
+        lg.struct_size = (int)sizeof lg;
+        check(dvo_batch_last_step_control_log(b_, seq, &lg));
+        return lg;
+    }
     // per-sequence camera intrinsics from the next push on ([n_seq]; nullptr: the creation K for every sequence), see dvo_batch_set_intrinsics
     void setIntrinsics(const Mat3* K) { check(dvo_batch_set_intrinsics(b_, K ? K[0].data() : nullptr)); }
     std::vector<Mat3> intrinsics()
@@ -460,6 +480,26 @@ public:
         dvo_affine_log lg{};
         lg.struct_size = (int)sizeof lg;
         check(dvo_batch_last_affine_log(b_, seq, &lg));
+        return lg;
+    }
+    // step control from the next push / call on (dvo_batch_set_step_control): damped Gauss-Newton with step acceptance; DVO_LM_OFF turns it off
+    void setStepControl(int mode = DVO_LM_ON, float lambda0 = 1.0f, float lambda_up = 4.0f, float lambda_down = 0.5f, float lambda_floor = 1e-4f,
+                        float lambda_max = 1e6f, float min_valid_fraction = 0.5f)
+    {
+        dvo_lm_config c{(int)sizeof(dvo_lm_config), mode, lambda0, lambda_up, lambda_down, lambda_floor, lambda_max, min_valid_fraction};
+        check(dvo_batch_set_step_control(b_, &c));
+    }
+    std::vector<dvo_lm_record> lastStepControl()   // [n_seq]
+    {
+        std::vector<dvo_lm_record> out(n_);
+        check(dvo_batch_last_step_control(b_, out.data()));
+        return out;
+    }
+    dvo_lm_log lastStepControlLog(int seq)
+    {
+        dvo_lm_log lg{};
+        lg.struct_size = (int)sizeof lg;
+        check(dvo_batch_last_step_control_log(b_, seq, &lg));
         return lg;
     }
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
