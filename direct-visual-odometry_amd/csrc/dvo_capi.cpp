@@ -471,7 +471,7 @@ int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)
     PoseGuess& G = b->guess();
     if (xi && G.mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(b->device()));
-    return G.set_rows(xi, xi_on_device != 0, b->stream());
+    return G.given.set(xi, xi_on_device != 0, sizeof(float) * 6 * (size_t)b->n_seq(), b->stream());
 }
 
 int dvo_batch_last_start_poses(dvo_batch* b, float* xi_start)
@@ -511,104 +511,125 @@ static int track_quality(dvo_batch* b, dvo_track_quality* out, bool to_host)
 int dvo_batch_last_track_quality(dvo_batch* b, dvo_track_quality* out) { return track_quality(b, out, true); }
 int dvo_batch_copy_track_quality_device(dvo_batch* b, dvo_track_quality* dst) { return track_quality(b, dst, false); }
 
+// ------------------------------------------------------------------------------------------------ batch: the opt-in tracking terms
+// Which terms combine is the engine's table (Tracker::refusal): the setters validate their configuration and hand it
+// over with their own name, which the refusal's message starts with.
+
+// What every dvo_batch_last_* reader of a term checks before it reads, in this order: the handle, the output and (log readers) the
+// sequence; the caller's struct_size (log readers: want_size and the type's name); that the last push / call ran with the term, else
+// DVO_ERR_NOT_READY naming the term and its setter; the device.
+static int reader_begin(dvo_batch* b, const void* out, const char* who, Term term, int seq = 0, int struct_size = 0, size_t want_size = 0,
+                        const char* type = "")
+{
+    if (!b || !out || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
+    if (struct_size != (int)want_size) { set_error(std::string(who) + ": struct_size is not sizeof(" + type + ")"); return DVO_ERR_BAD_ARGUMENT; }
+    const Tracker& t = b->trk();
+    bool ready = false;
+    const char* with = "";
+    switch (term) {
+    case TERM_ROBUST:       ready = t.rob.ready;        with = "robust weights (dvo_batch_set_robust_weights)"; break;
+    case TERM_MEDIAN:       ready = t.rob.median_ready; with = "the median robust scale (dvo_batch_set_robust_median)"; break;
+    case TERM_AFFINE:       ready = t.aff.ready;        with = "affine brightness compensation (dvo_batch_set_affine_brightness)"; break;
+    case TERM_GEOMETRIC:    ready = t.geo.ready;        with = "the geometric term (dvo_batch_set_geometric)"; break;
+    case TERM_STEP_CONTROL: ready = t.lm.ready;         with = "step control (dvo_batch_set_step_control)"; break;
+    }
+    if (!ready) { set_error(std::string(who) + ": the last push / call did not run with " + with); return DVO_ERR_NOT_READY; }
+    return select_device(b->device());
+}
+#define DVO_LOG_READER(b, log, who, term, seq, type) reader_begin(b, log, who, term, seq, (log) ? (log)->struct_size : 0, sizeof(type), #type)
+
+// kind and param of robust weights, wherever they come from (a dvo_robust_config, the arguments of the dvo_op_gn_step_* operators)
+static bool robust_kind_param_ok(const char* who, int kind, float param)
+{
+    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
+        set_error(std::string(who) + ": the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+        return false;
+    }
+    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
+        set_error(std::string(who) + ": param (Huber k, Student-t nu) must be finite and > 0");
+        return false;
+    }
+    return true;
+}
+
 // The checks of a robust configuration (dvo_batch_set_robust_weights, and with `median` dvo_batch_set_robust_median, whose only scale
 // mode is DVO_ROBUST_SCALE_MEDIAN and which has no kind NONE)
 static bool robust_config_ok(const dvo_robust_config* cfg, const char* who, bool median)
 {
-    const auto positive = [](float v) { return v > 0.0f && v < __builtin_inff(); };
     if (cfg->struct_size != (int)sizeof(dvo_robust_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_robust_config)"); return false; }
     if (median && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
         set_error(std::string(who) + ": the kind is DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
         return false;
     }
-    if (cfg->kind != DVO_ROBUST_NONE && cfg->kind != DVO_ROBUST_HUBER && cfg->kind != DVO_ROBUST_STUDENT_T) {
-        set_error(std::string(who) + ": the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
+    if (!robust_kind_param_ok(who, cfg->kind, cfg->param)) return false;
+    if (cfg->kind == DVO_ROBUST_NONE) return true;
+    if (median && cfg->scale_mode != DVO_ROBUST_SCALE_MEDIAN) {
+        set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_MEDIAN");
         return false;
     }
-    if (cfg->kind != DVO_ROBUST_NONE) {
-        if (median && cfg->scale_mode != DVO_ROBUST_SCALE_MEDIAN) {
-            set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_MEDIAN");
-            return false;
-        }
-        if (!median && cfg->scale_mode != DVO_ROBUST_SCALE_ADAPTIVE && cfg->scale_mode != DVO_ROBUST_SCALE_GIVEN) {
-            set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_ADAPTIVE or DVO_ROBUST_SCALE_GIVEN");
-            return false;
-        }
-        if (!positive(cfg->param)) { set_error(std::string(who) + ": param (Huber k, Student-t nu) must be finite and > 0"); return false; }
-        if (!positive(cfg->scale_floor)) {   // (whatever the mode: a configuration is valid or not as a whole)
-            set_error(std::string(who) + ": scale_floor must be finite and > 0");
-            return false;
-        }
+    if (!median && cfg->scale_mode != DVO_ROBUST_SCALE_ADAPTIVE && cfg->scale_mode != DVO_ROBUST_SCALE_GIVEN) {
+        set_error(std::string(who) + ": the scale mode is DVO_ROBUST_SCALE_ADAPTIVE or DVO_ROBUST_SCALE_GIVEN");
+        return false;
+    }
+    if (!(cfg->scale_floor > 0.0f && cfg->scale_floor < __builtin_inff())) {   // (whatever the mode: a configuration is valid or not as a whole)
+        set_error(std::string(who) + ": scale_floor must be finite and > 0");
+        return false;
     }
     return true;
 }
 
 int dvo_batch_set_robust_median(dvo_batch* b, const dvo_robust_config* cfg)
 {
+    static const char who[] = "dvo_batch_set_robust_median";
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg) {
-        if (!robust_config_ok(cfg, "dvo_batch_set_robust_median", true)) return DVO_ERR_BAD_ARGUMENT;
-        if (b->trk().lm.on) {
-            set_error("dvo_batch_set_robust_median: step control is on (dvo_batch_set_step_control): the two do not combine yet");
-            return DVO_ERR_BAD_ARGUMENT;
-        }
-        if (b->trk().aff.on || b->trk().geo.on) {
-            set_error("dvo_batch_set_robust_median: affine brightness compensation or the geometric term is on: the median scale does not combine with them");
-            return DVO_ERR_BAD_ARGUMENT;
-        }
-    }
+    if (cfg && !robust_config_ok(cfg, who, true)) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_robust(cfg, b->stream());
+    return b->trk().set_robust(who, cfg, b->stream());
 }
 
 int dvo_batch_last_robust_log(dvo_batch* b, int seq, dvo_robust_log* log)
 {
-    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
-    if (log->struct_size != (int)sizeof(dvo_robust_log)) { set_error("dvo_batch_last_robust_log: struct_size is not sizeof(dvo_robust_log)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (!b->trk().rob.median_ready) { set_error("dvo_batch_last_robust_log: the last push / call did not run with the median robust scale (dvo_batch_set_robust_median)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(DVO_LOG_READER(b, log, "dvo_batch_last_robust_log", TERM_MEDIAN, seq, dvo_robust_log));
     return b->trk().last_robust_log(seq, log, b->stream());
 }
 
 int dvo_batch_last_robust_histogram(dvo_batch* b, int seq, uint32_t counts[256])
 {
-    if (!b || !counts || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
-    if (!b->trk().rob.median_ready) { set_error("dvo_batch_last_robust_histogram: the last push / call did not run with the median robust scale (dvo_batch_set_robust_median)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(reader_begin(b, counts, "dvo_batch_last_robust_histogram", TERM_MEDIAN, seq));
     return b->trk().last_robust_histogram(seq, counts, b->stream());
 }
 
 int dvo_batch_set_robust_weights(dvo_batch* b, const dvo_robust_config* cfg)
 {
+    static const char who[] = "dvo_batch_set_robust_weights";
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && !robust_config_ok(cfg, "dvo_batch_set_robust_weights", false)) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().lm.on) {
-        set_error("dvo_batch_set_robust_weights: step control is on (dvo_batch_set_step_control): the two do not combine yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (cfg && cfg->kind != DVO_ROBUST_NONE && b->trk().geo.on) {
-        set_error("dvo_batch_set_robust_weights: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
+    if (cfg && !robust_config_ok(cfg, who, false)) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_robust(cfg, b->stream());
+    return b->trk().set_robust(who, cfg, b->stream());
 }
 
 int dvo_batch_set_robust_scales(dvo_batch* b, const float* s, int s_on_device)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    const RobustWeights& R = b->trk().rob;
+    RobustWeights& R = b->trk().rob;
     if (s && !(R.on && R.mode == DVO_ROBUST_SCALE_GIVEN)) { set_error("dvo_batch_set_robust_scales: rows need the scale mode DVO_ROBUST_SCALE_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_robust_scales(s, s_on_device != 0, b->stream());
+    return R.scales.set(s, s_on_device != 0, sizeof(float) * (size_t)b->n_seq(), b->stream());
 }
 
 int dvo_batch_last_robust_scales(dvo_batch* b, float* s2)
 {
-    if (!b || !s2) return DVO_ERR_BAD_ARGUMENT;
-    if (!b->trk().rob.ready) { set_error("dvo_batch_last_robust_scales: the last push / call did not run with robust weights (dvo_batch_set_robust_weights)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(reader_begin(b, s2, "dvo_batch_last_robust_scales", TERM_ROBUST));
     return b->trk().last_robust_scales(s2, b->stream());
+}
+
+// the guards of the next (a, b) entry where no configuration sets them: the operators', and the bindings' defaults
+static dvo_affine_config affine_config_given()
+{
+    dvo_affine_config ac{};
+    ac.struct_size = (int)sizeof ac;
+    ac.mode = DVO_AFFINE_GIVEN; ac.min_pixels = 64; ac.min_contrast = 1e-3f; ac.gain_min = 0.25f; ac.gain_max = 4.0f;
+    return ac;
 }
 
 static bool affine_config_ok(const dvo_affine_config* cfg, const char* who)
@@ -631,47 +652,31 @@ static bool affine_config_ok(const dvo_affine_config* cfg, const char* who)
 
 int dvo_batch_set_affine_brightness(dvo_batch* b, const dvo_affine_config* cfg)
 {
+    static const char who[] = "dvo_batch_set_affine_brightness";
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && !affine_config_ok(cfg, "dvo_batch_set_affine_brightness")) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().lm.on) {
-        set_error("dvo_batch_set_affine_brightness: step control is on (dvo_batch_set_step_control): the two do not combine yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().geo.on) {
-        set_error("dvo_batch_set_affine_brightness: the geometric term is on (dvo_batch_set_geometric): the two do not combine yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (cfg && cfg->mode != DVO_AFFINE_OFF && b->trk().rob.median()) {
-        set_error("dvo_batch_set_affine_brightness: the median robust scale is on (dvo_batch_set_robust_median): the two do not combine");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
+    if (cfg && !affine_config_ok(cfg, who)) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_affine(cfg, b->stream());
+    return b->trk().set_affine(who, cfg, b->stream());
 }
 
 int dvo_batch_set_affine_rows(dvo_batch* b, const float* ab, int ab_on_device)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    const AffineBrightness& A = b->trk().aff;
+    AffineBrightness& A = b->trk().aff;
     if (ab && !(A.on && A.mode == DVO_AFFINE_GIVEN)) { set_error("dvo_batch_set_affine_rows: rows need the mode DVO_AFFINE_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_affine_rows(ab, ab_on_device != 0, b->stream());
+    return A.rows.set(ab, ab_on_device != 0, sizeof(float) * 2 * (size_t)b->n_seq(), b->stream());
 }
 
 int dvo_batch_last_affine(dvo_batch* b, float* ab)
 {
-    if (!b || !ab) return DVO_ERR_BAD_ARGUMENT;
-    if (!b->trk().aff.ready) { set_error("dvo_batch_last_affine: the last push / call did not run with affine brightness compensation (dvo_batch_set_affine_brightness)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(reader_begin(b, ab, "dvo_batch_last_affine", TERM_AFFINE));
     return b->trk().last_affine(ab, b->stream());
 }
 
 int dvo_batch_last_affine_log(dvo_batch* b, int seq, dvo_affine_log* log)
 {
-    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
-    if (log->struct_size != (int)sizeof(dvo_affine_log)) { set_error("dvo_batch_last_affine_log: struct_size is not sizeof(dvo_affine_log)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (!b->trk().aff.ready) { set_error("dvo_batch_last_affine_log: the last push / call did not run with affine brightness compensation (dvo_batch_set_affine_brightness)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(DVO_LOG_READER(b, log, "dvo_batch_last_affine_log", TERM_AFFINE, seq, dvo_affine_log));
     return b->trk().last_affine_log(seq, log, b->stream());
 }
 
@@ -697,19 +702,12 @@ static bool geometric_config_ok(const dvo_geometric_config* cfg, const char* who
 
 int dvo_batch_set_geometric(dvo_batch* b, const dvo_geometric_config* cfg)
 {
+    static const char who[] = "dvo_batch_set_geometric";
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (b->mono) { set_error("dvo_batch_set_geometric: needs a sensor-depth batch (a mono batch has no depth map to compare)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (cfg && !geometric_config_ok(cfg, "dvo_batch_set_geometric")) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && cfg->mode != DVO_GEOMETRIC_OFF && b->trk().lm.on) {
-        set_error("dvo_batch_set_geometric: step control is on (dvo_batch_set_step_control): the two do not combine yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (cfg && cfg->mode != DVO_GEOMETRIC_OFF && (b->trk().rob.on || b->trk().aff.on)) {
-        set_error("dvo_batch_set_geometric: robust weights or affine brightness compensation are on: they do not combine with the geometric term yet");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
+    if (b->mono) { set_error(std::string(who) + ": needs a sensor-depth batch (a mono batch has no depth map to compare)"); return DVO_ERR_BAD_ARGUMENT; }
+    if (cfg && !geometric_config_ok(cfg, who)) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_geometric(cfg, b->stream());
+    return b->trk().set_geometric(who, cfg, b->stream());
 }
 
 int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo, const dvo_affine_config* aff)
@@ -720,26 +718,19 @@ int dvo_batch_set_geometric_affine(dvo_batch* b, const dvo_geometric_config* geo
     if (!geometric_config_ok(geo, who) || !affine_config_ok(aff, who)) return DVO_ERR_BAD_ARGUMENT;
     if (geo->mode != DVO_GEOMETRIC_ON) { set_error(std::string(who) + ": the geometric mode must be DVO_GEOMETRIC_ON (dvo_batch_set_geometric turns the term off)"); return DVO_ERR_BAD_ARGUMENT; }
     if (aff->mode == DVO_AFFINE_OFF) { set_error(std::string(who) + ": the affine mode must be DVO_AFFINE_ESTIMATE or DVO_AFFINE_GIVEN (dvo_batch_set_affine_brightness turns the compensation off)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (b->trk().rob.on) { set_error(std::string(who) + ": robust weights are on: they do not combine with the geometric term yet"); return DVO_ERR_BAD_ARGUMENT; }
-    if (b->trk().lm.on) { set_error(std::string(who) + ": step control is on (dvo_batch_set_step_control): the two do not combine yet"); return DVO_ERR_BAD_ARGUMENT; }
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_geometric_affine(geo, aff, b->stream());
+    return b->trk().set_geometric_affine(who, geo, aff, b->stream());
 }
 
 int dvo_batch_last_geometric(dvo_batch* b, dvo_geometric_record* rec)
 {
-    if (!b || !rec) return DVO_ERR_BAD_ARGUMENT;
-    if (!b->trk().geo.ready) { set_error("dvo_batch_last_geometric: the last push did not run with the geometric term (dvo_batch_set_geometric)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(reader_begin(b, rec, "dvo_batch_last_geometric", TERM_GEOMETRIC));
     return b->trk().last_geometric(rec, b->stream());
 }
 
 int dvo_batch_last_geometric_log(dvo_batch* b, int seq, dvo_geometric_log* log)
 {
-    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
-    if (log->struct_size != (int)sizeof(dvo_geometric_log)) { set_error("dvo_batch_last_geometric_log: struct_size is not sizeof(dvo_geometric_log)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (!b->trk().geo.ready) { set_error("dvo_batch_last_geometric_log: the last push did not run with the geometric term (dvo_batch_set_geometric)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(DVO_LOG_READER(b, log, "dvo_batch_last_geometric_log", TERM_GEOMETRIC, seq, dvo_geometric_log));
     return b->trk().last_geometric_log(seq, log, b->stream());
 }
 
@@ -774,37 +765,22 @@ static bool lm_config_ok(const dvo_lm_config* cfg, const char* who)
 
 int dvo_batch_set_step_control(dvo_batch* b, const dvo_lm_config* cfg)
 {
+    static const char who[] = "dvo_batch_set_step_control";
     if (!b) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && !lm_config_ok(cfg, "dvo_batch_set_step_control")) return DVO_ERR_BAD_ARGUMENT;
-    if (cfg && cfg->mode != DVO_LM_OFF) {
-        const Tracker& t = b->trk();
-        const char* other = t.geo.on ? "the geometric term is on (dvo_batch_set_geometric)"
-                          : t.aff.on ? "affine brightness compensation is on (dvo_batch_set_affine_brightness)"
-                          : t.rob.median() ? "the median robust scale is on (dvo_batch_set_robust_median)"
-                          : t.rob.on ? "robust weights are on (dvo_batch_set_robust_weights)" : nullptr;
-        if (other) {
-            set_error(std::string("dvo_batch_set_step_control: ") + other + ": the two do not combine yet");
-            return DVO_ERR_BAD_ARGUMENT;
-        }
-    }
+    if (cfg && !lm_config_ok(cfg, who)) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(select_device(b->device()));
-    return b->trk().set_step_control(cfg, b->stream());
+    return b->trk().set_step_control(who, cfg, b->stream());
 }
 
 int dvo_batch_last_step_control(dvo_batch* b, dvo_lm_record* rec)
 {
-    if (!b || !rec) return DVO_ERR_BAD_ARGUMENT;
-    if (!b->trk().lm.ready) { set_error("dvo_batch_last_step_control: the last push / call did not run with step control (dvo_batch_set_step_control)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(reader_begin(b, rec, "dvo_batch_last_step_control", TERM_STEP_CONTROL));
     return b->trk().last_step_control(rec, b->stream());
 }
 
 int dvo_batch_last_step_control_log(dvo_batch* b, int seq, dvo_lm_log* log)
 {
-    if (!b || !log || seq < 0 || seq >= b->n_seq()) return DVO_ERR_BAD_ARGUMENT;
-    if (log->struct_size != (int)sizeof(dvo_lm_log)) { set_error("dvo_batch_last_step_control_log: struct_size is not sizeof(dvo_lm_log)"); return DVO_ERR_BAD_ARGUMENT; }
-    if (!b->trk().lm.ready) { set_error("dvo_batch_last_step_control_log: the last push / call did not run with step control (dvo_batch_set_step_control)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(b->device()));
+    DVO_TRY(DVO_LOG_READER(b, log, "dvo_batch_last_step_control_log", TERM_STEP_CONTROL, seq, dvo_lm_log));
     return b->trk().last_step_control_log(seq, log, b->stream());
 }
 
@@ -1176,14 +1152,24 @@ int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_fram
     return DVO_OK;
 }
 
-// dvo_op_gn_step, and with rob (dvo_op_gn_step_robust) the weighted pair on the weighted plan with one entry of (kind, param, s2)
-static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
-                   const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
-                   dvo_gn_result* out, uint8_t* mask, const dvo_robust_config* rob, float rob_s2,
-                   const dvo_affine_config* aff = nullptr, float aff_a = 1.0f, float aff_b = 0.0f, double* moments = nullptr,
-                   float* next_ab = nullptr, const dvo_geometric_config* geo = nullptr, const float* geo_ref_depth = nullptr,
-                   double* geo_sums = nullptr, uint32_t* med_counts = nullptr, int* med_bin = nullptr, float* med_next_s2 = nullptr)
+// The optional inputs and outputs of one evaluation, by term (value-initialised; each dvo_op_gn_step* fills what it uses):
+//   rob: the weighted pair on the weighted plan with one entry of (kind, param, s2); with the median scale, the bin counts, the
+//        median bin and the next entry's s2 come back through med_*
+//   aff: the pair with one entry (a, b); the moments and the next entry come back
+//   geo: the geometric pair -- ref_depth / ref_sigma are then the tracked frame's own maps and geo.ref_depth the reference's depth --
+//        and its sums; with aff too, the combined pair
+struct StepTerms {
+    uint8_t* mask;
+    struct { const dvo_robust_config* cfg; float s2; uint32_t* med_counts; int* med_bin; float* med_next_s2; } rob;
+    struct { const dvo_affine_config* cfg; float a, b; double* moments; float* next_ab; } aff;
+    struct { const dvo_geometric_config* cfg; const float* ref_depth; double* sums; } geo;
+};
+
+// dvo_op_gn_step and its per-term forms: one Gauss-Newton evaluation of one level at `xi`, through the launch pair a batch would run
+static int gn_step(const char* who, int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
+                   const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level, dvo_gn_result* out, const StepTerms& t)
 {
+    uint8_t* const mask = t.mask;
     if (!obj_gray || !ref_gray || !ref_depth || !ref_sigma || !K || !xi || !out || w < 1 || h < 1 || level < 0 || level >= DVO_MAX_LEVELS)
         return DVO_ERR_BAD_ARGUMENT;
     dvo_config cf;
@@ -1198,17 +1184,17 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
     for (int l = 0; l <= level; l++) { gl.w[l] = w; gl.h[l] = h; memcpy(gl.K9[l], g.K9[0], sizeof g.K9[0]); gl.k[l] = g.k[0]; }
     Tracker trk;
     DVO_TRY(trk.init(gl, 1, cf));
-    if (rob) DVO_TRY(trk.set_robust(rob, c.s));
-    if (aff) DVO_TRY(trk.set_affine(aff, c.s));
-    DevBuf mom;
-    if (aff) DVO_TRY(mom.alloc(sizeof(double) * DVO_AFFINE_MOMENTS));
-    // (the geometric term: ref_depth / ref_sigma are the tracked frame's own maps, geo_ref_depth the reference's depth)
-    DevBuf zr, zs;
-    if (geo) {
-        DVO_TRY(trk.set_geometric(geo, c.s));
-        DVO_TRY(upload(zr, geo_ref_depth, (size_t)w * h, c.s));
+    if (t.rob.cfg) DVO_TRY(trk.set_robust(who, t.rob.cfg, c.s));
+    if (t.geo.cfg && t.aff.cfg) DVO_TRY(trk.set_geometric_affine(who, t.geo.cfg, t.aff.cfg, c.s));
+    else if (t.aff.cfg) DVO_TRY(trk.set_affine(who, t.aff.cfg, c.s));
+    else if (t.geo.cfg) DVO_TRY(trk.set_geometric(who, t.geo.cfg, c.s));
+    DevBuf mom, zr, zs, mn;   // the terms' device outputs, and the reference's depth
+    if (trk.aff.on) DVO_TRY(mom.alloc(sizeof(double) * DVO_AFFINE_MOMENTS));
+    if (trk.geo.on) {
+        DVO_TRY(upload(zr, t.geo.ref_depth, (size_t)w * h, c.s));
         DVO_TRY(zs.alloc(sizeof(double) * 2));
     }
+    if (trk.rob.median()) DVO_TRY(mn.alloc(sizeof(int) * 2));
     const size_t n = (size_t)w * h;
     DevBuf og, rg, rd, rs, mk, xin, res;
     DVO_TRY(upload(og, obj_gray, n, c.s));
@@ -1232,55 +1218,67 @@ static int gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const 
         launch_prep_ref(pa, c.s);
     }
     const GnArgs ga = trk.gn_args(og.as<float>(), rg.as<float>(), rd.as<float>(), wgb.as<float>(), 0.0f, level, mask ? mk.as<uint8_t>() : nullptr, 1);
-    if (trk.rob.on) {
-        RobustBeginArgs ra{};
-        ra.table = trk.rob.table.as<RobustEntry>(); ra.last_s2 = trk.rob.last.as<float>();
-        ra.given = 1; ra.s2_all = rob_s2;
-        ra.n_seq = 1; ra.kind = trk.rob.kind; ra.param = trk.rob.param;
-        launch_robust_begin(ra, c.s);
-    }
-    DevBuf mn;
-    if (trk.rob.median()) {
-        DVO_TRY(mn.alloc(sizeof(int) * 2));
-        trk.median_begin(c.s);
-    }
-    if (trk.aff.on) trk.affine_begin(c.s, true, aff_a, aff_b);
+    const Tracker::GivenOnce once{t.rob.s2, t.aff.a, t.aff.b};
+    DVO_TRY(trk.begin_terms(c.s, &once));
     trk.launch_gn_term(ga, level, 1, c.s, 0, zr.as<float>());
     SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
-    trk.launch_solve_term(sa, 1, c.s, false, false, trk.geo.on ? zs.as<double>() : mom.as<double>(), true, mom.as<double>(), mn.as<int>());
+    Tracker::SolveTerm st{};
+    st.estimate_once = true;
+    st.geo_sums = zs.as<double>(); st.affine_moments = mom.as<double>(); st.step_mn = mn.as<int>();
+    trk.launch_solve_term(sa, 1, c.s, st);
     int med_mn[2] = {0, 0};
     RobustEntry med_next{};
     if (trk.rob.median()) {
-        DVO_HIP(hipMemcpyAsync(med_counts, trk.rob.hist_last.p, sizeof(uint32_t) * DVO_MEDIAN_BINS, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(t.rob.med_counts, trk.rob.hist_last.p, sizeof(uint32_t) * DVO_MEDIAN_BINS, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(med_mn, mn.p, sizeof med_mn, hipMemcpyDeviceToHost, c.s));
         DVO_HIP(hipMemcpyAsync(&med_next, trk.rob.table.p, sizeof med_next, hipMemcpyDeviceToHost, c.s));
     }
     if (trk.aff.on) {
-        DVO_HIP(hipMemcpyAsync(moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
-        DVO_HIP(hipMemcpyAsync(next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(t.aff.moments, mom.p, sizeof(double) * DVO_AFFINE_MOMENTS, hipMemcpyDeviceToHost, c.s));
+        DVO_HIP(hipMemcpyAsync(t.aff.next_ab, trk.aff.table.p, sizeof(float) * 2, hipMemcpyDeviceToHost, c.s));
     }
-    if (trk.geo.on) DVO_HIP(hipMemcpyAsync(geo_sums, zs.p, sizeof(double) * 2, hipMemcpyDeviceToHost, c.s));
+    if (trk.geo.on) DVO_HIP(hipMemcpyAsync(t.geo.sums, zs.p, sizeof(double) * 2, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipMemcpyAsync(out, res.p, sizeof *out, hipMemcpyDeviceToHost, c.s));
     if (mask) DVO_HIP(hipMemcpyAsync(mask, mk.p, n, hipMemcpyDeviceToHost, c.s));
     DVO_HIP(hipStreamSynchronize(c.s));
     DVO_HIP(hipGetLastError());
-    if (trk.rob.median()) { *med_bin = med_mn[0]; *med_next_s2 = med_next.s2; }
+    if (trk.rob.median()) { *t.rob.med_bin = med_mn[0]; *t.rob.med_next_s2 = med_next.s2; }
     return DVO_OK;
+}
+
+// kind NONE still runs the weighted pair of the robust operators, with the plain entry (rho = 1; an entry the solve writes is then
+// Huber's with k = 1): the configuration and the s2 they hand to gn_step
+static dvo_robust_config op_robust_config(int kind, float param, int scale_mode)
+{
+    dvo_robust_config rc{};
+    rc.struct_size = (int)sizeof rc;
+    rc.kind = kind == DVO_ROBUST_NONE ? DVO_ROBUST_HUBER : kind;
+    rc.scale_mode = scale_mode;
+    rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
+    return rc;   // (scale_floor 0, not validated here: GIVEN ignores it, the median scale then keeps the bin's own s2)
+}
+
+static dvo_geometric_config op_geometric_config(float weight, float max_diff)
+{
+    dvo_geometric_config gc{};
+    gc.struct_size = (int)sizeof gc;
+    gc.mode = DVO_GEOMETRIC_ON; gc.weight = weight; gc.max_diff = max_diff;
+    return gc;
 }
 
 int dvo_op_gn_step_geometric(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth, const float* obj_sigma,
                              const float* ref_gray, const float* ref_depth, int w, int h, const float K[9], const float xi[6], int level,
                              float weight, float max_diff, dvo_gn_result* out, double sums[2])
 {
+    static const char who[] = "dvo_op_gn_step_geometric";
     if (!ref_depth || !sums) return DVO_ERR_BAD_ARGUMENT;
-    dvo_geometric_config gc{};
-    gc.struct_size = (int)sizeof gc;
-    gc.mode = DVO_GEOMETRIC_ON; gc.weight = weight; gc.max_diff = max_diff;
-    if (!geometric_config_ok(&gc, "dvo_op_gn_step_geometric")) return DVO_ERR_BAD_ARGUMENT;
-    return gn_step(dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, nullptr, nullptr, 0.0f, nullptr, 1.0f, 0.0f,
-                   nullptr, nullptr, &gc, ref_depth, sums);
+    const dvo_geometric_config gc = op_geometric_config(weight, max_diff);
+    if (!geometric_config_ok(&gc, who)) return DVO_ERR_BAD_ARGUMENT;
+    StepTerms t{};
+    t.geo = {&gc, ref_depth, sums};
+    return gn_step(who, dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_gn_step_geometric_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* obj_depth, const float* obj_sigma,
@@ -1288,92 +1286,64 @@ int dvo_op_gn_step_geometric_affine(int dev, const dvo_config* cfg, const float*
                                     int level, float weight, float max_diff, float a, float b, dvo_gn_result* out, double sums[2],
                                     double moments[5], float next_ab[2])
 {
+    static const char who[] = "dvo_op_gn_step_geometric_affine";
     if (!ref_depth || !sums || !moments || !next_ab) return DVO_ERR_BAD_ARGUMENT;
-    dvo_geometric_config gc{};
-    gc.struct_size = (int)sizeof gc;
-    gc.mode = DVO_GEOMETRIC_ON; gc.weight = weight; gc.max_diff = max_diff;
-    if (!geometric_config_ok(&gc, "dvo_op_gn_step_geometric_affine")) return DVO_ERR_BAD_ARGUMENT;
-    dvo_affine_config ac{};   // (dvo_op_gn_step_affine's guards)
-    ac.struct_size = (int)sizeof ac;
-    ac.mode = DVO_AFFINE_GIVEN; ac.min_pixels = 64; ac.min_contrast = 1e-3f; ac.gain_min = 0.25f; ac.gain_max = 4.0f;
-    return gn_step(dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, nullptr, nullptr, 0.0f, &ac, a, b, moments,
-                   next_ab, &gc, ref_depth, sums);
+    const dvo_geometric_config gc = op_geometric_config(weight, max_diff);
+    if (!geometric_config_ok(&gc, who)) return DVO_ERR_BAD_ARGUMENT;
+    const dvo_affine_config ac = affine_config_given();
+    StepTerms t{};
+    t.geo = {&gc, ref_depth, sums};
+    t.aff = {&ac, a, b, moments, next_ab};
+    return gn_step(who, dev, cfg, obj_gray, ref_gray, obj_depth, obj_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_gn_step(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                    const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
                    dvo_gn_result* out, uint8_t* mask)
 {
-    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, mask, nullptr, 0.0f);
+    StepTerms t{};
+    t.mask = mask;
+    return gn_step("dvo_op_gn_step", dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_gn_step_robust(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                           const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
                           int kind, float param, float s2, dvo_gn_result* out)
 {
-    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
-        set_error("dvo_op_gn_step_robust: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
-        set_error("dvo_op_gn_step_robust: param (Huber k, Student-t nu) must be finite and > 0");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    dvo_robust_config rc{};
-    rc.struct_size = (int)sizeof rc;
-    // (kind NONE still runs the weighted pair, with the plain entry: rho = 1)
-    rc.kind = kind == DVO_ROBUST_NONE ? DVO_ROBUST_HUBER : kind;
-    rc.scale_mode = DVO_ROBUST_SCALE_GIVEN;
-    rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
-    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2);
+    static const char who[] = "dvo_op_gn_step_robust";
+    if (!robust_kind_param_ok(who, kind, param)) return DVO_ERR_BAD_ARGUMENT;
+    const dvo_robust_config rc = op_robust_config(kind, param, DVO_ROBUST_SCALE_GIVEN);
+    StepTerms t{};
+    t.rob.cfg = &rc; t.rob.s2 = kind == DVO_ROBUST_NONE ? 0.0f : s2;
+    return gn_step(who, dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_gn_step_robust_median(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                                  const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
                                  int kind, float param, float s2, dvo_gn_result* out, uint32_t counts[256], int* median_bin, float* next_s2)
 {
+    static const char who[] = "dvo_op_gn_step_robust_median";
     if (!counts || !median_bin || !next_s2) return DVO_ERR_BAD_ARGUMENT;
-    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
-        set_error("dvo_op_gn_step_robust_median: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
-        set_error("dvo_op_gn_step_robust_median: param (Huber k, Student-t nu) must be finite and > 0");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    dvo_robust_config rc{};
-    rc.struct_size = (int)sizeof rc;
-    // (kind NONE still runs the pair, with the plain entry: rho = 1; the entry the solve writes is then Huber's with k = 1)
-    rc.kind = kind == DVO_ROBUST_NONE ? DVO_ROBUST_HUBER : kind;
-    rc.scale_mode = DVO_ROBUST_SCALE_MEDIAN;
-    rc.param = kind == DVO_ROBUST_NONE ? 1.0f : param;
-    rc.scale_floor = 0.0f;   // (not validated here: floor2 = 0, the bin's own s2)
-    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, &rc, kind == DVO_ROBUST_NONE ? 0.0f : s2,
-                   nullptr, 1.0f, 0.0f, nullptr, nullptr, nullptr, nullptr, nullptr, counts, median_bin, next_s2);
+    if (!robust_kind_param_ok(who, kind, param)) return DVO_ERR_BAD_ARGUMENT;
+    const dvo_robust_config rc = op_robust_config(kind, param, DVO_ROBUST_SCALE_MEDIAN);
+    StepTerms t{};
+    t.rob = {&rc, kind == DVO_ROBUST_NONE ? 0.0f : s2, counts, median_bin, next_s2};
+    return gn_step(who, dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_gn_step_affine(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,
                           const float* ref_sigma, int w, int h, const float K[9], const float xi[6], int level,
                           int kind, float param, float s2, float a, float b, dvo_gn_result* out, double moments[5], float next_ab[2])
 {
+    static const char who[] = "dvo_op_gn_step_affine";
     if (!moments || !next_ab) return DVO_ERR_BAD_ARGUMENT;
-    if (kind != DVO_ROBUST_NONE && kind != DVO_ROBUST_HUBER && kind != DVO_ROBUST_STUDENT_T) {
-        set_error("dvo_op_gn_step_affine: the kind is DVO_ROBUST_NONE, DVO_ROBUST_HUBER or DVO_ROBUST_STUDENT_T");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    if (kind != DVO_ROBUST_NONE && !(param > 0.0f && param < __builtin_inff())) {
-        set_error("dvo_op_gn_step_affine: param (Huber k, Student-t nu) must be finite and > 0");
-        return DVO_ERR_BAD_ARGUMENT;
-    }
-    dvo_robust_config rc{};
-    rc.struct_size = (int)sizeof rc;
-    rc.kind = kind; rc.scale_mode = DVO_ROBUST_SCALE_GIVEN; rc.param = param;
-    dvo_affine_config ac{};   // (the guards of the next entry: the binding's defaults)
-    ac.struct_size = (int)sizeof ac;
-    ac.mode = DVO_AFFINE_GIVEN; ac.min_pixels = 64; ac.min_contrast = 1e-3f; ac.gain_min = 0.25f; ac.gain_max = 4.0f;
-    // (kind NONE runs the instance without robust weights: rho = 1, N = n_valid)
-    return gn_step(dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, nullptr, kind == DVO_ROBUST_NONE ? nullptr : &rc,
-                   s2, &ac, a, b, moments, next_ab);
+    if (!robust_kind_param_ok(who, kind, param)) return DVO_ERR_BAD_ARGUMENT;
+    const dvo_robust_config rc = op_robust_config(kind, param, DVO_ROBUST_SCALE_GIVEN);
+    const dvo_affine_config ac = affine_config_given();
+    StepTerms t{};
+    if (kind != DVO_ROBUST_NONE) { t.rob.cfg = &rc; t.rob.s2 = s2; }   // (kind NONE runs the instance without robust weights: rho = 1, N = n_valid)
+    t.aff = {&ac, a, b, moments, next_ab};
+    return gn_step(who, dev, cfg, obj_gray, ref_gray, ref_depth, ref_sigma, w, h, K, xi, level, out, t);
 }
 
 int dvo_op_track(int dev, const dvo_config* cfg, const float* obj_gray, const float* ref_gray, const float* ref_depth,

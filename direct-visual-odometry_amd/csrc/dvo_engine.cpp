@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdio>
@@ -681,10 +682,63 @@ SolveArgs Tracker::solve_args(int level, int q0, int ignore_active, SolveRows ro
     return a;
 }
 
-void Tracker::use_plan(bool opt_in_term)
+void Tracker::use_plan()
 {
+    const bool opt_in_term = terms_on() != 0;
     for (int l = 0; l < DVO_MAX_LEVELS; l++) lv[l] = opt_in_term ? lv_rw[l] : lv_plain[l];
     tile_margin = opt_in_term ? 0 : margin_plain;
+}
+
+unsigned Tracker::terms_on() const
+{
+    return (rob.on ? (rob.median() ? TERM_MEDIAN : TERM_ROBUST) : 0u) | (aff.on ? TERM_AFFINE : 0u) | (geo.on ? TERM_GEOMETRIC : 0u) |
+           (lm.on ? TERM_STEP_CONTROL : 0u);
+}
+
+const TermName* Tracker::refusal(unsigned on, TermSetter want)
+{
+    // the terms, in the order a refusal names them when several are on
+    static const TermName kTerms[] = {{TERM_STEP_CONTROL, "step control is on", "dvo_batch_set_step_control"},
+                                      {TERM_GEOMETRIC, "the geometric term is on", "dvo_batch_set_geometric"},
+                                      {TERM_AFFINE, "affine brightness compensation is on", "dvo_batch_set_affine_brightness"},
+                                      {TERM_MEDIAN, "the median robust scale is on", "dvo_batch_set_robust_median"},
+                                      {TERM_ROBUST, "robust weights are on", "dvo_batch_set_robust_weights"}};
+    // the table: the terms that refuse each setter's "on" call (a setter's own term never does: setting again reconfigures)
+    unsigned refused_by = 0;
+    switch (want) {
+    case TermSetter::RobustWeights:    refused_by = TERM_STEP_CONTROL | TERM_GEOMETRIC; break;
+    case TermSetter::RobustMedian:     refused_by = TERM_STEP_CONTROL | TERM_GEOMETRIC | TERM_AFFINE; break;
+    case TermSetter::AffineBrightness: refused_by = TERM_STEP_CONTROL | TERM_GEOMETRIC | TERM_MEDIAN; break;
+    case TermSetter::Geometric:        refused_by = TERM_STEP_CONTROL | TERM_AFFINE | TERM_MEDIAN | TERM_ROBUST; break;
+    case TermSetter::GeometricAffine:  refused_by = TERM_STEP_CONTROL | TERM_MEDIAN | TERM_ROBUST; break;
+    case TermSetter::StepControl:      refused_by = TERM_GEOMETRIC | TERM_AFFINE | TERM_MEDIAN | TERM_ROBUST; break;
+    }
+    for (const TermName& t : kTerms)
+        if (on & refused_by & t.term) return &t;
+    return nullptr;
+}
+
+template <class Apply> int Tracker::set_term(const char* who, TermSetter want, bool enable, Apply&& apply)
+{
+    if (enable)
+        if (const TermName* t = refusal(terms_on(), want)) {
+            set_error(std::string(who) + ": " + t->is_on + " (" + t->setter + "): the two do not combine");
+            return DVO_ERR_BAD_ARGUMENT;
+        }
+    const int rc = apply();
+    use_plan();
+    return rc;
+}
+
+int HostRows::set(const float* rows, bool on_device, size_t bytes, hipStream_t s)
+{
+    if (!rows || on_device) { src = rows; return DVO_OK; }   // (device rows: read by the term's begin kernel in stream order)
+    void* h = nullptr;
+    DVO_TRY(stage.acquire(&h));
+    memcpy(h, rows, bytes);
+    DVO_TRY(stage.commit(dev.p, bytes, s));   // in stream order: after the begin kernel of every earlier push
+    src = dev.as<float>();
+    return DVO_OK;
 }
 
 int Tracker::log_iterations() const
@@ -693,14 +747,44 @@ int Tracker::log_iterations() const
     return its > DVO_MAX_ITERATIONS ? DVO_MAX_ITERATIONS : (its < 1 ? 1 : its);
 }
 
-int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
+int Tracker::set_robust(const char* who, const dvo_robust_config* c, hipStream_t s)
+{
+    const bool enable = c && c->kind != DVO_ROBUST_NONE;
+    const TermSetter want = enable && c->scale_mode == DVO_ROBUST_SCALE_MEDIAN ? TermSetter::RobustMedian : TermSetter::RobustWeights;
+    return set_term(who, want, enable, [&] { return apply_robust(c, s); });
+}
+
+int Tracker::set_affine(const char* who, const dvo_affine_config* c, hipStream_t s)
+{
+    return set_term(who, TermSetter::AffineBrightness, c && c->mode != DVO_AFFINE_OFF, [&] { return apply_affine(c, s); });
+}
+
+int Tracker::set_geometric(const char* who, const dvo_geometric_config* c, hipStream_t s)
+{
+    return set_term(who, TermSetter::Geometric, c && c->mode != DVO_GEOMETRIC_OFF, [&] { return apply_geometric(c, s); });
+}
+
+int Tracker::set_geometric_affine(const char* who, const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s)
+{
+    return set_term(who, TermSetter::GeometricAffine, true, [&] {
+        DVO_TRY(apply_geometric(gc, s));
+        return apply_affine(ac, s);
+    });
+}
+
+int Tracker::set_step_control(const char* who, const dvo_lm_config* c, hipStream_t s)
+{
+    return set_term(who, TermSetter::StepControl, c && c->mode != DVO_LM_OFF, [&] { return apply_step_control(c, s); });
+}
+
+int Tracker::apply_robust(const dvo_robust_config* c, hipStream_t s)
 {
     const bool enable = c && c->kind != DVO_ROBUST_NONE;
     if (enable && !rob.table.p) {
         DVO_TRY(rob.table.alloc(sizeof(RobustEntry) * (size_t)n_seq));
         DVO_TRY(rob.last.alloc(sizeof(float) * (size_t)n_seq));
-        DVO_TRY(rob.scales.alloc(sizeof(float) * (size_t)n_seq));
-        DVO_TRY(rob.stage.alloc(sizeof(float) * (size_t)n_seq));
+        DVO_TRY(rob.scales.dev.alloc(sizeof(float) * (size_t)n_seq));
+        DVO_TRY(rob.scales.stage.alloc(sizeof(float) * (size_t)n_seq));
         DVO_HIP(hipMemsetAsync(rob.last.p, 0, rob.last.bytes, s));
     }
     if (enable && c->scale_mode == DVO_ROBUST_SCALE_MEDIAN && !rob.hist.p) {
@@ -716,98 +800,122 @@ int Tracker::set_robust(const dvo_robust_config* c, hipStream_t s)
     }
     rob.on = enable;
     if (enable) {
-        if (rob.mode != c->scale_mode || c->scale_mode != DVO_ROBUST_SCALE_GIVEN) rob.scales_src = nullptr;   // (rows belong to one GIVEN configuration)
+        if (rob.mode != c->scale_mode || c->scale_mode != DVO_ROBUST_SCALE_GIVEN) rob.scales.clear();   // (rows belong to one GIVEN configuration)
         rob.kind = c->kind; rob.mode = c->scale_mode; rob.param = c->param;
         rob.floor2 = c->scale_mode != DVO_ROBUST_SCALE_GIVEN ? c->scale_floor * c->scale_floor : 0.0f;
     } else {
-        rob.scales_src = nullptr;
-    }
-    use_plan(rob.on || aff.on || geo.on || lm.on);
-    return DVO_OK;
-}
-
-int Tracker::set_robust_scales(const float* s_rows, bool on_device, hipStream_t s)
-{
-    if (!s_rows) { rob.scales_src = nullptr; return DVO_OK; }
-    if (on_device) {
-        rob.scales_src = s_rows;   // read by k_robust_begin in stream order
-    } else {
-        void* h = nullptr;
-        DVO_TRY(rob.stage.acquire(&h));
-        memcpy(h, s_rows, sizeof(float) * (size_t)n_seq);
-        DVO_TRY(rob.stage.commit(rob.scales.p, sizeof(float) * (size_t)n_seq, s));
-        rob.scales_src = rob.scales.as<float>();
+        rob.scales.clear();
     }
     return DVO_OK;
 }
 
-int Tracker::last_robust_scales(float* s2, hipStream_t s) const
+template <class W, class Last, class Log, class Tracked, class Unpack>
+int Tracker::read_term_log(const W* log_dev, int words, int log_its, int seq, const Last* last_dev, Log* out, hipStream_t s, Tracked tracked,
+                           Unpack unpack, LogCopy extra, bool* did_track) const
 {
-    DVO_HIP(hipMemcpyAsync(s2, rob.last.p, sizeof(float) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    return DVO_OK;
-}
-
-int Tracker::last_robust_log(int seq, dvo_robust_log* out, hipStream_t s) const
-{
-    std::vector<int> rows((size_t)3 * rob.log_its * g.levels);
-    std::vector<int> n_iter(DVO_MAX_LEVELS);
-    float last = 0.0f;
-    int prime[2] = {0, 0};
-    DVO_HIP(hipMemcpyAsync(rows.data(), rob.mlog.as<int>() + (size_t)seq * rows.size(), sizeof(int) * rows.size(), hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(&last, rob.last.as<float>() + (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(prime, rob.prime_mn.as<int>() + 2 * (size_t)seq, sizeof prime, hipMemcpyDeviceToHost, s));
+    static_assert(sizeof(W) == 4, "a log is made of 4-byte words");
+    std::vector<W> rows((size_t)words * log_its * g.levels);
+    int n_iter[DVO_MAX_LEVELS] = {0};
+    Last last{};
+    DVO_HIP(hipMemcpyAsync(rows.data(), log_dev + (size_t)seq * rows.size(), sizeof(W) * rows.size(), hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(n_iter, log.as<dvo_track_log>()[seq].n_iter, sizeof n_iter, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipMemcpyAsync(&last, last_dev + seq, sizeof last, hipMemcpyDeviceToHost, s));
+    if (extra.bytes) DVO_HIP(hipMemcpyAsync(extra.dst, extra.src, extra.bytes, hipMemcpyDeviceToHost, s));
     DVO_HIP(hipStreamSynchronize(s));
     const int size = out->struct_size;
     memset(out, 0, sizeof *out);
     out->struct_size = size;
     out->levels = g.levels;
-    if (last == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
-    out->prime_bin = prime[0]; out->prime_count = prime[1];
-    for (int l = 0; l < g.levels; l++) {
-        const int n = n_iter[l] < rob.log_its ? n_iter[l] : rob.log_its;
+    const bool did = tracked(last);   // else the sequence did not track at that push: an empty log
+    if (did_track) *did_track = did;
+    for (int l = 0; did && l < g.levels; l++) {
+        const int n = n_iter[l] < log_its ? n_iter[l] : log_its;
         out->n_iter[l] = n;
-        for (int it = 0; it < n; it++) {
-            const int* r = &rows[((size_t)l * rob.log_its + it) * 3];
-            memcpy(&out->s2[l][it], &r[0], sizeof(float));
-            out->median_bin[l][it] = r[1];
-            out->count[l][it] = r[2];
-        }
+        for (int it = 0; it < n; it++) unpack(l, it, &rows[((size_t)l * log_its + it) * words]);
     }
+    return DVO_OK;
+}
+
+// device -> host on `s`, then the synchronize every read of a record ends with
+static int read_back(void* dst, const void* src, size_t bytes, hipStream_t s)
+{
+    DVO_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+    DVO_HIP(hipStreamSynchronize(s));
+    return DVO_OK;
+}
+
+int Tracker::last_robust_scales(float* s2, hipStream_t s) const { return read_back(s2, rob.last.p, sizeof(float) * (size_t)n_seq, s); }
+
+int Tracker::last_robust_log(int seq, dvo_robust_log* out, hipStream_t s) const
+{
+    int prime[2] = {0, 0};
+    bool tracked = false;
+    DVO_TRY(read_term_log(rob.mlog.as<int>(), 3, rob.log_its, seq, rob.last.as<float>(), out, s, [](float s2) { return s2 != 0.0f; },
+                          [&](int l, int it, const int* r) {
+                              memcpy(&out->s2[l][it], &r[0], sizeof(float));
+                              out->median_bin[l][it] = r[1];
+                              out->count[l][it] = r[2];
+                          },
+                          {prime, rob.prime_mn.as<int>() + 2 * (size_t)seq, sizeof prime}, &tracked));
+    if (tracked) { out->prime_bin = prime[0]; out->prime_count = prime[1]; }
     return DVO_OK;
 }
 
 int Tracker::last_robust_histogram(int seq, uint32_t* counts, hipStream_t s) const
 {
-    DVO_HIP(hipMemcpyAsync(counts, rob.hist_last.as<uint32_t>() + (size_t)seq * DVO_MEDIAN_BINS, sizeof(uint32_t) * DVO_MEDIAN_BINS,
-                           hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
+    return read_back(counts, rob.hist_last.as<uint32_t>() + (size_t)seq * DVO_MEDIAN_BINS, sizeof(uint32_t) * DVO_MEDIAN_BINS, s);
+}
+
+int Tracker::begin_terms(hipStream_t s, const GivenOnce* once)
+{
+    if (rob.on) {
+        RobustBeginArgs ra{};
+        ra.table = rob.table.as<RobustEntry>(); ra.last_s2 = rob.last.as<float>();
+        ra.given = (once || rob.mode == DVO_ROBUST_SCALE_GIVEN) ? 1 : 0;
+        ra.scales = (!once && ra.given) ? rob.scales.src : nullptr;
+        ra.s2_all = once ? once->s2 : 0.0f;
+        ra.n_seq = n_seq; ra.kind = rob.kind; ra.param = rob.param;
+        launch_robust_begin(ra, s);
+        rob.tracked = true;
+    }
+    if (rob.median()) {
+        MedianBeginArgs ma{};
+        ma.hist = rob.hist.as<unsigned>(); ma.hist_last = rob.hist_last.as<unsigned>(); ma.prime_mn = rob.prime_mn.as<int>();
+        ma.n_seq = n_seq;
+        launch_median_begin(ma, s);
+    }
+    if (aff.on) {
+        AffineBeginArgs ba{};
+        ba.table = aff.table.as<AffineEntry>(); ba.last = aff.last.as<float>(); ba.prime_ab = aff.prime.as<float>();
+        ba.rows = (!once && aff.mode == DVO_AFFINE_GIVEN) ? aff.rows.src : nullptr;
+        ba.a_all = once ? once->a : 1.0f; ba.b_all = once ? once->b : 0.0f;
+        ba.n_seq = n_seq;
+        launch_affine_begin(ba, s);
+        aff.tracked = true;
+    }
+    if (geo.on) {
+        DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
+        geo.tracked = true;
+    }
+    if (lm.on) {
+        LmBeginArgs la{};
+        la.table = lm.table.as<dvo_lm_entry>(); la.last = lm.last.as<dvo_lm_record>();
+        la.lambda0 = lm.cfg.lambda0; la.n_seq = n_seq;
+        launch_lm_begin(la, s);
+        lm.tracked = true;
+    }
     return DVO_OK;
 }
 
-void Tracker::median_begin(hipStream_t s)
+void Tracker::end_terms(hipStream_t s)
 {
-    MedianBeginArgs ma{};
-    ma.hist = rob.hist.as<unsigned>(); ma.hist_last = rob.hist_last.as<unsigned>(); ma.prime_mn = rob.prime_mn.as<int>();
-    ma.n_seq = n_seq;
-    launch_median_begin(ma, s);
-}
-
-void Tracker::robust_end_push(hipStream_t s)
-{
-    if (rob.median() && !rob.tracked) {   // nothing tracked at this push: no histogram and no priming record either
-        (void)hipMemsetAsync(rob.hist_last.p, 0, rob.hist_last.bytes, s);
-        (void)hipMemsetAsync(rob.prime_mn.p, 0, rob.prime_mn.bytes, s);
-    }
-    rob.median_ready = rob.median();
     rob.end_push(s);
     aff.end_push(s);
     geo.end_push(s);
     lm.end_push(s);
 }
 
-int Tracker::set_step_control(const dvo_lm_config* c, hipStream_t s)
+int Tracker::apply_step_control(const dvo_lm_config* c, hipStream_t s)
 {
     const bool enable = c && c->mode != DVO_LM_OFF;
     if (enable && !lm.table.p) {
@@ -821,41 +929,19 @@ int Tracker::set_step_control(const dvo_lm_config* c, hipStream_t s)
     }
     lm.on = enable;
     if (enable) lm.cfg = *c;
-    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
 }
 
-int Tracker::last_step_control(dvo_lm_record* rec, hipStream_t s) const
-{
-    DVO_HIP(hipMemcpyAsync(rec, lm.last.p, sizeof(dvo_lm_record) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    return DVO_OK;
-}
+int Tracker::last_step_control(dvo_lm_record* rec, hipStream_t s) const { return read_back(rec, lm.last.p, sizeof(dvo_lm_record) * (size_t)n_seq, s); }
 
 int Tracker::last_step_control_log(int seq, dvo_lm_log* out, hipStream_t s) const
 {
-    std::vector<int> rows((size_t)2 * lm.log_its * g.levels);
-    std::vector<int> n_iter(DVO_MAX_LEVELS);
-    dvo_lm_record last{};
-    DVO_HIP(hipMemcpyAsync(rows.data(), lm.log.as<int>() + (size_t)seq * rows.size(), sizeof(int) * rows.size(), hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(&last, lm.last.as<dvo_lm_record>() + (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    const int size = out->struct_size;
-    memset(out, 0, sizeof *out);
-    out->struct_size = size;
-    out->levels = g.levels;
-    if (last.n_first == 0) return DVO_OK;   // the sequence did not track at that push: an empty log
-    for (int l = 0; l < g.levels; l++) {
-        const int n = n_iter[l] < lm.log_its ? n_iter[l] : lm.log_its;
-        out->n_iter[l] = n;
-        for (int it = 0; it < n; it++) {
-            const int* r = &rows[((size_t)l * lm.log_its + it) * 2];
-            memcpy(&out->lambda[l][it], &r[0], sizeof(float));
-            out->decision[l][it] = r[1];
-        }
-    }
-    return DVO_OK;
+    return read_term_log(lm.log.as<int>(), 2, lm.log_its, seq, lm.last.as<dvo_lm_record>(), out, s,
+                         [](const dvo_lm_record& r) { return r.n_first != 0; },
+                         [&](int l, int it, const int* r) {
+                             memcpy(&out->lambda[l][it], &r[0], sizeof(float));
+                             out->decision[l][it] = r[1];
+                         });
 }
 
 LmSolve Tracker::lm_solve_args(size_t q0, bool log) const
@@ -870,7 +956,7 @@ LmSolve Tracker::lm_solve_args(size_t q0, bool log) const
     return m;
 }
 
-int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
+int Tracker::apply_geometric(const dvo_geometric_config* c, hipStream_t s)
 {
     const bool enable = c && c->mode != DVO_GEOMETRIC_OFF;
     if (enable && !geo.last.p) {
@@ -882,21 +968,13 @@ int Tracker::set_geometric(const dvo_geometric_config* c, hipStream_t s)
     }
     geo.on = enable;
     if (enable) { geo.weight = c->weight; geo.max_diff = c->max_diff; }
-    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
-}
-
-int Tracker::set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s)
-{
-    DVO_TRY(set_geometric(gc, s));
-    return set_affine(ac, s);
 }
 
 int Tracker::last_geometric(dvo_geometric_record* rec, hipStream_t s) const
 {
     std::vector<float> rows((size_t)4 * n_seq);
-    DVO_HIP(hipMemcpyAsync(rows.data(), geo.last.p, sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
+    DVO_TRY(read_back(rows.data(), geo.last.p, sizeof(float) * rows.size(), s));
     for (int q = 0; q < n_seq; q++) {
         rec[q].n_geo = (int)rows[4 * (size_t)q];
         rec[q].mean_sq = rows[4 * (size_t)q + 1];
@@ -906,27 +984,12 @@ int Tracker::last_geometric(dvo_geometric_record* rec, hipStream_t s) const
 
 int Tracker::last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const
 {
-    std::vector<float> rows((size_t)2 * geo.log_its * g.levels);
-    std::vector<int> n_iter(DVO_MAX_LEVELS);
-    float last[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    DVO_HIP(hipMemcpyAsync(rows.data(), geo.log.as<float>() + (size_t)seq * rows.size(), sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(last, geo.last.as<float>() + 4 * (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    const int size = out->struct_size;
-    memset(out, 0, sizeof *out);
-    out->struct_size = size;
-    out->levels = g.levels;
-    if (last[2] == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
-    for (int l = 0; l < g.levels; l++) {
-        const int n = n_iter[l] < geo.log_its ? n_iter[l] : geo.log_its;
-        out->n_iter[l] = n;
-        for (int it = 0; it < n; it++) {
-            out->n_geo[l][it] = (int)rows[((size_t)l * geo.log_its + it) * 2];
-            out->sum_sq[l][it] = rows[((size_t)l * geo.log_its + it) * 2 + 1];
-        }
-    }
-    return DVO_OK;
+    using Last = std::array<float, 4>;   // (n_geo, mean_sq, tracked, 0)
+    return read_term_log(geo.log.as<float>(), 2, geo.log_its, seq, geo.last.as<Last>(), out, s, [](const Last& r) { return r[2] != 0.0f; },
+                         [&](int l, int it, const float* r) {
+                             out->n_geo[l][it] = (int)r[0];
+                             out->sum_sq[l][it] = r[1];
+                         });
 }
 
 GeoGn Tracker::geo_gn_args(size_t q0, int level, const float* ref_z) const
@@ -947,7 +1010,7 @@ GeoSolve Tracker::geo_solve_args(size_t q0, bool log, double* sums_out) const
     return z;
 }
 
-int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
+int Tracker::apply_affine(const dvo_affine_config* c, hipStream_t s)
 {
     const bool enable = c && c->mode != DVO_AFFINE_OFF;
     if (enable && !aff.table.p) {
@@ -955,8 +1018,8 @@ int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
         DVO_TRY(aff.table.alloc(sizeof(AffineEntry) * (size_t)n_seq));
         DVO_TRY(aff.last.alloc(sizeof(float) * 2 * (size_t)n_seq));
         DVO_TRY(aff.prime.alloc(sizeof(float) * 2 * (size_t)n_seq));
-        DVO_TRY(aff.rows.alloc(sizeof(float) * 2 * (size_t)n_seq));
-        DVO_TRY(aff.stage.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.rows.dev.alloc(sizeof(float) * 2 * (size_t)n_seq));
+        DVO_TRY(aff.rows.stage.alloc(sizeof(float) * 2 * (size_t)n_seq));
         DVO_TRY(aff.moments.alloc(sizeof(float) * 8 * part_rows * (size_t)n_seq));
         DVO_TRY(aff.log.alloc(sizeof(float) * 2 * (size_t)aff.log_its * (size_t)g.levels * (size_t)n_seq));
         DVO_HIP(hipMemsetAsync(aff.last.p, 0, aff.last.bytes, s));
@@ -965,75 +1028,32 @@ int Tracker::set_affine(const dvo_affine_config* c, hipStream_t s)
     }
     aff.on = enable;
     if (enable) {
-        if (aff.mode != c->mode || c->mode != DVO_AFFINE_GIVEN) aff.rows_src = nullptr;   // (rows belong to one GIVEN configuration)
+        if (aff.mode != c->mode || c->mode != DVO_AFFINE_GIVEN) aff.rows.clear();   // (rows belong to one GIVEN configuration)
         aff.mode = c->mode; aff.min_pixels = c->min_pixels; aff.min_contrast = c->min_contrast;
         aff.gain_min = c->gain_min; aff.gain_max = c->gain_max;
     } else {
-        aff.rows_src = nullptr;
+        aff.rows.clear();
         aff.mode = DVO_AFFINE_OFF;
     }
-    use_plan(rob.on || aff.on || geo.on || lm.on);
     return DVO_OK;
 }
 
-int Tracker::set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s)
-{
-    if (!ab_rows) { aff.rows_src = nullptr; return DVO_OK; }
-    if (on_device) {
-        aff.rows_src = ab_rows;   // read by k_affine_begin in stream order
-    } else {
-        void* h = nullptr;
-        DVO_TRY(aff.stage.acquire(&h));
-        memcpy(h, ab_rows, sizeof(float) * 2 * (size_t)n_seq);
-        DVO_TRY(aff.stage.commit(aff.rows.p, sizeof(float) * 2 * (size_t)n_seq, s));
-        aff.rows_src = aff.rows.as<float>();
-    }
-    return DVO_OK;
-}
-
-int Tracker::last_affine(float* ab, hipStream_t s) const
-{
-    DVO_HIP(hipMemcpyAsync(ab, aff.last.p, sizeof(float) * 2 * (size_t)n_seq, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    return DVO_OK;
-}
+int Tracker::last_affine(float* ab, hipStream_t s) const { return read_back(ab, aff.last.p, sizeof(float) * 2 * (size_t)n_seq, s); }
 
 int Tracker::last_affine_log(int seq, dvo_affine_log* out, hipStream_t s) const
 {
-    std::vector<float> rows((size_t)2 * aff.log_its * g.levels);
-    std::vector<int> n_iter(DVO_MAX_LEVELS);
-    float last[2] = {0.0f, 0.0f}, prime[2] = {0.0f, 0.0f};
-    DVO_HIP(hipMemcpyAsync(rows.data(), aff.log.as<float>() + (size_t)seq * rows.size(), sizeof(float) * rows.size(), hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(n_iter.data(), log.as<dvo_track_log>()[seq].n_iter, sizeof(int) * DVO_MAX_LEVELS, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(last, aff.last.as<float>() + 2 * (size_t)seq, sizeof last, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipMemcpyAsync(prime, aff.prime.as<float>() + 2 * (size_t)seq, sizeof prime, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    const int size = out->struct_size;
-    memset(out, 0, sizeof *out);
-    out->struct_size = size;
-    out->levels = g.levels;
-    if (last[0] == 0.0f && last[1] == 0.0f) return DVO_OK;   // the sequence did not track at that push: an empty log
-    out->prime_a = prime[0]; out->prime_b = prime[1];
-    for (int l = 0; l < g.levels; l++) {
-        const int n = n_iter[l] < aff.log_its ? n_iter[l] : aff.log_its;
-        out->n_iter[l] = n;
-        for (int it = 0; it < n; it++) {
-            out->a[l][it] = rows[((size_t)l * aff.log_its + it) * 2];
-            out->b[l][it] = rows[((size_t)l * aff.log_its + it) * 2 + 1];
-        }
-    }
+    using Last = std::array<float, 2>;   // the last used (a, b)
+    float prime[2] = {0.0f, 0.0f};
+    bool tracked = false;
+    DVO_TRY(read_term_log(aff.log.as<float>(), 2, aff.log_its, seq, aff.last.as<Last>(), out, s,
+                          [](const Last& ab) { return !(ab[0] == 0.0f && ab[1] == 0.0f); },
+                          [&](int l, int it, const float* r) {
+                              out->a[l][it] = r[0];
+                              out->b[l][it] = r[1];
+                          },
+                          {prime, aff.prime.as<float>() + 2 * (size_t)seq, sizeof prime}, &tracked));
+    if (tracked) { out->prime_a = prime[0]; out->prime_b = prime[1]; }
     return DVO_OK;
-}
-
-void Tracker::affine_begin(hipStream_t s, bool given_all, float a_all, float b_all)
-{
-    AffineBeginArgs ba{};
-    ba.table = aff.table.as<AffineEntry>(); ba.last = aff.last.as<float>(); ba.prime_ab = aff.prime.as<float>();
-    ba.rows = (!given_all && aff.mode == DVO_AFFINE_GIVEN) ? aff.rows_src : nullptr;
-    ba.a_all = given_all ? a_all : 1.0f; ba.b_all = given_all ? b_all : 0.0f;
-    ba.n_seq = n_seq;
-    launch_affine_begin(ba, s);
-    aff.tracked = true;
 }
 
 AffineGn Tracker::affine_gn_args(size_t q0, bool prime) const
@@ -1104,19 +1124,18 @@ void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t 
     else launch_gn(a, level, count, s, grid_seqs);
 }
 
-void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime, double* term_out,
-                                bool estimate_once, double* moments_out, int* step_mn) const
+void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& t) const
 {
     const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
-    const RobustSolve r = rob.on ? robust_solve_args(q0, adaptive_scale) : RobustSolve{};
+    const bool log = sa.log != nullptr;
+    const RobustSolve r = rob.on ? robust_solve_args(q0, t.adaptive_scale) : RobustSolve{};
     if (geo.on && aff.on)
-        launch_gn_solve_zab(sa, affine_solve_args(q0, sa.log != nullptr, prime, moments_out, estimate_once), geo_solve_args(q0, sa.log != nullptr, term_out),
-                            count, s);
-    else if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, sa.log != nullptr, term_out), count, s);
-    else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, sa.log != nullptr, prime, term_out, estimate_once), count, s);
-    else if (rob.median()) launch_gn_solve_md(sa, r, median_solve_args(q0, sa.log != nullptr, prime, step_mn), count, s);
+        launch_gn_solve_zab(sa, affine_solve_args(q0, log, t.prime, t.affine_moments, t.estimate_once), geo_solve_args(q0, log, t.geo_sums), count, s);
+    else if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, log, t.geo_sums), count, s);
+    else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, log, t.prime, t.affine_moments, t.estimate_once), count, s);
+    else if (rob.median()) launch_gn_solve_md(sa, r, median_solve_args(q0, log, t.prime, t.step_mn), count, s);
     else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
-    else if (lm.on) launch_gn_solve_lm(sa, lm_solve_args(q0, sa.log != nullptr), count, s);
+    else if (lm.on) launch_gn_solve_lm(sa, lm_solve_args(q0, log), count, s);
     else launch_gn_solve(sa, count, s);
 }
 
@@ -1220,30 +1239,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
         if (seed_mono) launch_mono_seed(*seed, s);
         else launch_seed_pose(*seed, s);
     }
-    if (rob.on) {   // the weight table of this call (before the fork: every sub-batch reads its part)
-        RobustBeginArgs ra{};
-        ra.table = rob.table.as<RobustEntry>(); ra.last_s2 = rob.last.as<float>();
-        ra.given = rob.mode == DVO_ROBUST_SCALE_GIVEN ? 1 : 0;
-        ra.scales = ra.given ? rob.scales_src : nullptr;
-        ra.s2_all = 0.0f;
-        ra.n_seq = n_seq; ra.kind = rob.kind; ra.param = rob.param;
-        launch_robust_begin(ra, s);
-        if (rob.median()) median_begin(s);
-        rob.tracked = true;
-    }
-    if (aff.on) affine_begin(s);   // the brightness table of this call (before the fork, like the weight table)
-    if (geo.on) {   // "not tracked" until a solve says otherwise (before the fork)
-        DVO_HIP(hipMemsetAsync(geo.last.p, 0, geo.last.bytes, s));
-        geo.tracked = true;
-    }
-    if (lm.on) {    // lambda0 and empty records (before the fork: every sub-batch reads its part)
-        LmBeginArgs la{};
-        la.table = lm.table.as<dvo_lm_entry>(); la.last = lm.last.as<dvo_lm_record>();
-        la.lambda0 = lm.cfg.lambda0; la.n_seq = n_seq;
-        launch_lm_begin(la, s);
-        lm.tracked = true;
-    }
-    const bool rob_adaptive = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
+    DVO_TRY(begin_terms(s));
+    SolveTerm iteration{};   // every iteration's solve
+    iteration.adaptive_scale = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
     const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
     // level does not pay for its remaining (empty) launches.  Big batches run the fixed schedule sync-free.
@@ -1335,7 +1333,9 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                     launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true);
                     SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
                     sp.list_in = list_prev; sp.result = nullptr;
-                    launch_solve_term(sp, nq, sk, false, true);
+                    SolveTerm tp{};
+                    tp.prime = true;
+                    launch_solve_term(sp, nq, sk, tp);
                 }
                 if (cfg.profile) {
                     if (ev_used == ev_pool.size()) {
@@ -1356,7 +1356,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                launch_solve_term(sa, nq, sk, rob_adaptive);
+                launch_solve_term(sa, nq, sk, iteration);
             }
             if (poll && !L.fused && it + 1 < max_it) {
                 DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
@@ -2199,9 +2199,9 @@ int Batch::push(const FrameInput& in)
         if (cam_pending) { cam_K_used = cam_K; cam_pending = false; }   // (k_plan has read this push's camera-changed bytes)
     }
     if (und_pending) { und_D_used = und.D; und_pending = false; }   // (the D this push used: the camera-change rule's reference)
-    guess.rows_src = nullptr;   // (rows are spent by the push that follows them)
+    guess.given.clear();   // (rows are spent by the push that follows them)
     quality.ready = quality.on;
-    trk.robust_end_push(stream);
+    trk.end_terms(stream);
     n_push++;
     if (!kf_on || cur < 0) {
         prev = cur;
@@ -2452,25 +2452,11 @@ int PoseGuess::set_mode(int m, int n, hipStream_t s, const uint8_t* prev_eff_dev
         DVO_HIP(hipMemsetAsync(dev.p, 0, dev.bytes, s));
         if (prev_eff_dev) DVO_HIP(hipMemcpyAsync(prev_eff(), prev_eff_dev, (size_t)n, hipMemcpyDeviceToDevice, s));
         else DVO_HIP(hipMemsetAsync(prev_eff(), prev_all, (size_t)n, s));
-        DVO_TRY(rows_stage.alloc(sizeof(float) * 6 * (size_t)n));
+        given.dev.adopt(rows(), sizeof(float) * 6 * (size_t)n);
+        DVO_TRY(given.stage.alloc(sizeof(float) * 6 * (size_t)n));
     }
     mode = m;
-    if (m != DVO_GUESS_GIVEN) rows_src = nullptr;
-    return DVO_OK;
-}
-
-int PoseGuess::set_rows(const float* xi, bool on_device, hipStream_t s)
-{
-    if (!xi) { rows_src = nullptr; return DVO_OK; }
-    if (mode != DVO_GUESS_GIVEN) { set_error("dvo_batch_set_pose_guess: rows need the mode DVO_GUESS_GIVEN"); return DVO_ERR_BAD_ARGUMENT; }
-    if (on_device) { rows_src = xi; return DVO_OK; }   // read by the seed kernel in stream order
-    // copied now into pinned staging, then to the device in stream order (after the seed of every earlier push), as SeqPlan::set_actions
-    const size_t bytes = sizeof(float) * 6 * (size_t)n_seq;
-    void* h = nullptr;
-    DVO_TRY(rows_stage.acquire(&h));
-    memcpy(h, xi, bytes);
-    DVO_TRY(rows_stage.commit(rows(), bytes, s));
-    rows_src = rows();
+    if (m != DVO_GUESS_GIVEN) given.clear();
     return DVO_OK;
 }
 
@@ -2478,7 +2464,7 @@ PoseSeedArgs PoseGuess::args(SeqState* state, const uint8_t* eff, int all_eff, c
 {
     PoseSeedArgs a{};
     a.state = state; a.eff = eff; a.all_eff = all_eff; a.mode = mode;
-    a.rows = mode == DVO_GUESS_GIVEN ? rows_src : nullptr;
+    a.rows = mode == DVO_GUESS_GIVEN ? given.src : nullptr;
     a.start = start(); a.prev_eff = prev_eff(); a.last_xi = last_xi; a.hist = hist(); a.hist_n = hist_n(); a.meta = meta;
     a.n_seq = n_seq;
     return a;
@@ -2486,9 +2472,7 @@ PoseSeedArgs PoseGuess::args(SeqState* state, const uint8_t* eff, int all_eff, c
 
 int PoseGuess::last_start(float* out, hipStream_t s) const
 {
-    DVO_HIP(hipMemcpyAsync(out, start(), sizeof(float) * 6 * (size_t)n_seq, hipMemcpyDeviceToHost, s));
-    DVO_HIP(hipStreamSynchronize(s));
-    return DVO_OK;
+    return read_back(out, start(), sizeof(float) * 6 * (size_t)n_seq, s);
 }
 
 int Batch::set_guess_mode(int m)

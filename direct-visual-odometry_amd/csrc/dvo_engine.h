@@ -69,6 +69,18 @@ struct PinnedPair {
     void release(hipStream_t s);
 };
 
+// Host rows that every later push / call reads (the robust weights' GIVEN scales, the GIVEN (a, b) rows, the start poses): either the
+// caller's own device pointer, or host rows copied now into pinned staging and from there, in stream order, into `dev`.
+struct HostRows {
+    DevBuf dev;                   // where staged rows land (PoseGuess: a view of the rows inside its own block, DevBuf::adopt)
+    PinnedPair stage;             // pinned staging of host rows
+    const float* src = nullptr;   // the rows every later push / call reads (device memory); nullptr: none
+    // rows: `bytes` of host memory (copied before the call returns), or with on_device device memory read in stream order; nullptr clears
+    int set(const float* rows, bool on_device, size_t bytes, hipStream_t s);
+    void clear() { src = nullptr; }
+    void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
+};
+
 // Device memory for the keyframes of one dvo_vo handle: FrameHistory grows by one Frame per keyframe (frame.hpp:151-157), and a hipMalloc
 // per map of every new keyframe costs more than tracking a frame.  Blocks of one keyframe's size are cut from slabs of 16 and recycled
 // when a keyframe is dropped (dvo_vo_set_history_limit).
@@ -233,8 +245,7 @@ struct PoseGuess {
     int mode = DVO_GUESS_NONE;
     int n_seq = 0;
     DevBuf dev;                                // rows [n][6], start [n][6], hist [n][12] (float), then prev_eff [n], hist_n [n] (u8)
-    PinnedPair rows_stage;                     // pinned staging of host rows
-    const float* rows_src = nullptr;           // rows of the next push (device memory); nullptr: none
+    HostRows given;                            // the rows of the next push (GIVEN); given.dev views rows()
     bool on() const { return dev.p != nullptr; }
     float* rows() const { return dev.as<float>(); }
     float* start() const { return dev.as<float>() + (size_t)n_seq * 6; }
@@ -243,10 +254,9 @@ struct PoseGuess {
     uint8_t* hist_n() const { return prev_eff() + n_seq; }
     // mode: the history starts from the last push: prev_eff_dev (its effective actions, device) or every sequence prev_all (0xff: none)
     int set_mode(int m, int n, hipStream_t s, const uint8_t* prev_eff_dev, int prev_all);
-    int set_rows(const float* xi, bool on_device, hipStream_t s);
     PoseSeedArgs args(SeqState* state, const uint8_t* eff, int all_eff, const float* last_xi, const MonoSeq* meta) const;
     int last_start(float* out, hipStream_t s) const;
-    void release(hipStream_t s) { rows_stage.release(s); }   // (PinnedPair's release order)
+    void release(hipStream_t s) { given.release(s); }   // (PinnedPair's release order)
 };
 
 // Per-sequence tracking quality of a batch (dvo_batch_set_track_quality).  Allocated by the first enable; while on,
@@ -262,8 +272,9 @@ struct TrackQuality {
     int read_host(const Tracker& trk, const int* status, int all_status, dvo_track_quality* out, hipStream_t s);
 };
 
-// What every opt-in term of batched tracking keeps (robust weights, affine brightness, the geometric term): whether
-// it is on, and the per-sequence record of the last push / call, which is all zeros for a push that tracked nothing.
+// What every opt-in term of batched tracking keeps (robust weights with any of their scales, affine brightness, the geometric term,
+// step control): whether it is on, and the per-sequence record of the last push / call, which is all zeros for a
+// push that tracked nothing.
 struct OptInTerm {
     bool on = false;        // the next push / call runs with the term
     bool ready = false;     // the last push / call did
@@ -277,14 +288,20 @@ struct OptInTerm {
     }
 };
 
+// Which terms combine.  A batch's state is the set of terms that are on; the robust weights count as TERM_ROBUST with
+// the adaptive or a given scale and as TERM_MEDIAN with the median scale.  Each setter's "on" call is refused while one of the terms of
+// its row of the table is on (Tracker::refusal); turning a term off never consults the table.
+enum Term : unsigned { TERM_ROBUST = 1, TERM_MEDIAN = 2, TERM_AFFINE = 4, TERM_GEOMETRIC = 8, TERM_STEP_CONTROL = 16 };
+enum class TermSetter { RobustWeights, RobustMedian, AffineBrightness, Geometric, GeometricAffine, StepControl };
+struct TermName { unsigned term; const char* is_on; const char* setter; };   // how a refusal names a term that is on
+
 // Robust residual weights of a batch (dvo_batch_set_robust_weights).  Allocated by the first enable.  While on, the
 // tracker runs the weighted plan (Tracker::lv_rw): k_track_gn_rw + k_gn_solve_rw pairs on every level.
 struct RobustWeights : OptInTerm {
     int kind = DVO_ROBUST_NONE, mode = DVO_ROBUST_SCALE_ADAPTIVE;
     float param = 0.0f, floor2 = 0.0f;   // floor2 = scale_floor * scale_floor, once, in float
-    DevBuf table, scales;                // [n_seq] RobustEntry; [n_seq] float s (host rows).  last: [n_seq] float s2 of the last iteration
-    PinnedPair stage;                    // pinned staging of host rows
-    const float* scales_src = nullptr;   // GIVEN: the rows every later push reads (device memory); nullptr: none (plain)
+    DevBuf table;                        // [n_seq] RobustEntry.  last: [n_seq] float s2 of the last iteration
+    HostRows scales;                     // GIVEN: [n_seq] float s; none: plain
     // The median scale (mode DVO_ROBUST_SCALE_MEDIAN: dvo_batch_set_robust_median), allocated by its first enable:
     // the pairs are k_track_gn_md + k_gn_solve_md, and the first iteration of the coarsest level follows a priming pair.
     DevBuf hist, hist_last;              // [n_seq][256] counts of the launch in flight; of each sequence's last evaluated iteration
@@ -292,7 +309,16 @@ struct RobustWeights : OptInTerm {
     int log_its = 0;                     // iterations per level of the robust log
     bool median_ready = false;           // the last push / call ran with the median scale (its log and histogram can be read)
     bool median() const { return on && mode == DVO_ROBUST_SCALE_MEDIAN; }
-    void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
+    void end_push(hipStream_t s)         // OptInTerm's, and the median scale's own records
+    {
+        if (median() && !tracked) {   // nothing tracked at this push: no histogram and no priming record either
+            (void)hipMemsetAsync(hist_last.p, 0, hist_last.bytes, s);
+            (void)hipMemsetAsync(prime_mn.p, 0, prime_mn.bytes, s);
+        }
+        median_ready = median();
+        OptInTerm::end_push(s);
+    }
+    void release(hipStream_t s) { scales.release(s); }   // (PinnedPair's release order)
 };
 
 // Affine brightness compensation of a batch (dvo_batch_set_affine_brightness).  Allocated by the first enable.  While on,
@@ -302,11 +328,10 @@ struct AffineBrightness : OptInTerm {
     int min_pixels = 0;
     float min_contrast = 0.0f, gain_min = 0.0f, gain_max = 0.0f;
     int log_its = 0;                      // iterations per level of the affine log
-    DevBuf table, prime, rows;            // [n_seq] AffineEntry; [n_seq][2] priming entry; [n_seq][2] host rows.  last: [n_seq][2] last used entry
+    DevBuf table, prime;                  // [n_seq] AffineEntry; [n_seq][2] priming entry.  last: [n_seq][2] last used entry
     DevBuf moments, log;                  // [n_seq][part_rows][8] partial rows; [n_seq][levels][log_its][2]
-    PinnedPair stage;                     // pinned staging of host rows
-    const float* rows_src = nullptr;      // GIVEN: the rows every later push reads (device memory); nullptr: none ((1, 0))
-    void release(hipStream_t s) { stage.release(s); }   // (PinnedPair's release order)
+    HostRows rows;                        // GIVEN: [n_seq][2] (a, b); none: (1, 0)
+    void release(hipStream_t s) { rows.release(s); }   // (PinnedPair's release order)
 };
 
 // The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  Allocated by the first enable.  While
@@ -369,51 +394,57 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv[DVO_MAX_LEVELS];
     // Both plans are decided by init: lv_plain is what the configuration asks for, lv_rw the weighted plan (launch pairs of the
     // global-gather kernel on every level, whatever track_fused_tiles, gn_use_lds_patch, track_single_launch and the batch size say).
-    // lv / tile_margin are whichever is in force (use_plan, called by set_robust, set_affine, set_geometric and set_step_control: any
-    // opt-in term runs the weighted plan).
+    // lv / tile_margin are whichever is in force (use_plan, called by set_term: any opt-in term runs the weighted plan).
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
     int margin_plain = 0;
-    void use_plan(bool opt_in_term);
-    int log_iterations() const;   // iterations per level an opt-in term's log holds (set_affine, set_geometric)
+    void use_plan();
+    int log_iterations() const;   // iterations per level an opt-in term's log holds (fixed by the term's first enable)
     // One iteration's launch pair of whichever term is on -- the geometric term with affine brightness, else the
-    // geometric term, else affine brightness (with robust weights when they
-    // are on too), else robust weights, else step control (the plain tile kernel with k_gn_solve_lm), else the plain
-    // kernels: the one place that decides.  `ga` / `sa` view `count`
-    // sequences (their SeqState offset is every table's).
+    // geometric term, else affine brightness (with robust weights when they are on too), else robust weights (with the median scale:
+    // DESIGN.md §30), else step control (the plain tile kernel with k_gn_solve_lm), else the plain kernels: the one
+    // place that decides.  `ga` / `sa` view `count` sequences (their SeqState offset is every table's).
     //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
     //   prime: the priming pair of affine ESTIMATE mode or of the median robust scale
-    //   step_mn: the median scale's one-evaluation output (device, 2 ints (m, n); dvo_op_gn_step_robust_median)
-    //   adaptive_scale: the solve writes the next RobustEntry from this iteration's residual
-    //   term_out: the one-evaluation ops' device output (geometric: 2 doubles (n_geo, S29); affine: DVO_AFFINE_MOMENTS doubles)
-    //   estimate_once: the affine solve writes the next entry whatever the mode (dvo_op_gn_step_affine)
-    //   moments_out: both terms on: the affine output (term_out is the geometric one; dvo_op_gn_step_geometric_affine)
+    struct SolveTerm {   // what a solve's caller chooses, value-initialised; the outputs are the one-evaluation ops' (device memory)
+        bool adaptive_scale;      // the solve writes the next RobustEntry from this iteration's residual
+        bool prime;               // the priming pair
+        bool estimate_once;       // the affine solve writes the next entry whatever the mode (dvo_op_gn_step_affine)
+        double* geo_sums;         // the geometric term: 2 doubles (n_geo, S29)
+        double* affine_moments;   // affine brightness: DVO_AFFINE_MOMENTS doubles
+        int* step_mn;             // the median scale: 2 ints (m, n)
+    };
     void launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
                         bool prime = false) const;
-    void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, bool adaptive_scale, bool prime = false, double* term_out = nullptr,
-                           bool estimate_once = false, double* moments_out = nullptr, int* step_mn = nullptr) const;
+    void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& t) const;
+    // The terms' begin of a call, before the fork (every sub-batch reads its part of the tables): the weight table (k_robust_begin),
+    // the median scale's counts, the brightness table (k_affine_begin), the geometric records cleared ("not tracked" until a solve
+    // says otherwise), step control's lambda0 and empty records.  once: the one-evaluation ops' given s2 and (a, b) of every sequence.
+    struct GivenOnce { float s2, a, b; };
+    int begin_terms(hipStream_t s, const GivenOnce* once = nullptr);
+    void end_terms(hipStream_t s);          // after every push / call of the owner, whether it tracked or not (every opt-in term)
+    // The setters (configurations validated by the caller; nullptr or the term's OFF / NONE mode: off).  Every one goes through
+    // set_term: an "on" call is refused with DVO_ERR_BAD_ARGUMENT, naming `who`, the offending term and its setter, while a term it
+    // does not combine with is on (refusal: the table) and then changes nothing; the plan follows what is on.
+    unsigned terms_on() const;
+    static const TermName* refusal(unsigned on, TermSetter want);   // the term that refuses `want`, nullptr: allowed
     GeometricTerm geo;
-    int set_geometric(const dvo_geometric_config* c, hipStream_t s);    // validated by the caller; nullptr / OFF: off
-    int set_geometric_affine(const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s);   // both on (validated by the caller)
+    int set_geometric(const char* who, const dvo_geometric_config* c, hipStream_t s);
+    int set_geometric_affine(const char* who, const dvo_geometric_config* gc, const dvo_affine_config* ac, hipStream_t s);   // both on
     int last_geometric(dvo_geometric_record* rec, hipStream_t s) const;
     int last_geometric_log(int seq, dvo_geometric_log* out, hipStream_t s) const;
     StepControl lm;
-    int set_step_control(const dvo_lm_config* c, hipStream_t s);        // validated by the caller; nullptr / OFF: off
+    int set_step_control(const char* who, const dvo_lm_config* c, hipStream_t s);
     int last_step_control(dvo_lm_record* rec, hipStream_t s) const;
     int last_step_control_log(int seq, dvo_lm_log* out, hipStream_t s) const;
     AffineBrightness aff;
-    int set_affine(const dvo_affine_config* c, hipStream_t s);          // validated by the caller; nullptr / OFF: off
-    int set_affine_rows(const float* ab_rows, bool on_device, hipStream_t s);
+    int set_affine(const char* who, const dvo_affine_config* c, hipStream_t s);
     int last_affine(float* ab, hipStream_t s) const;
     int last_affine_log(int seq, dvo_affine_log* out, hipStream_t s) const;
-    void affine_begin(hipStream_t s, bool given_all = false, float a_all = 1.0f, float b_all = 0.0f);   // k_affine_begin of a call
     RobustWeights rob;
-    int set_robust(const dvo_robust_config* c, hipStream_t s);          // validated by the caller; nullptr / NONE: off
-    int set_robust_scales(const float* s_rows, bool on_device, hipStream_t s);
+    int set_robust(const char* who, const dvo_robust_config* c, hipStream_t s);   // (the median scale is c->scale_mode)
     int last_robust_scales(float* s2, hipStream_t s) const;
     int last_robust_log(int seq, dvo_robust_log* out, hipStream_t s) const;          // the median scale
     int last_robust_histogram(int seq, uint32_t* counts, hipStream_t s) const;
-    void median_begin(hipStream_t s);       // k_median_begin of a call
-    void robust_end_push(hipStream_t s);    // after every push / call of the owner, whether it tracked or not (every opt-in term)
     DevBuf ticket, freport;      // k_track_gn_fused: arrival tickets [n_seq]; (reported, active) per (set, level, iteration)
     // Adaptive schedule: progress words in mapped host memory, one per (level, iteration), two sets used alternately.
     // k_gn_solve's workgroup 0 stores (active sequences + 1); the host reads them to stay ~2 iterations ahead of the GPU and
@@ -483,6 +514,20 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);
     int collect_profile(hipStream_t s);
 private:
+    // the one place every setter goes through: the table (an "on" call only), the term's own `apply`, the plan of what is on now
+    template <class Apply> int set_term(const char* who, TermSetter want, bool enable, Apply&& apply);
+    int apply_robust(const dvo_robust_config* c, hipStream_t s);
+    int apply_affine(const dvo_affine_config* c, hipStream_t s);
+    int apply_geometric(const dvo_geometric_config* c, hipStream_t s);
+    int apply_step_control(const dvo_lm_config* c, hipStream_t s);
+    // The log of sequence `seq` at the last push / call: `words` values of W per logged iteration in `log_dev`
+    // ([n_seq][levels][log_its][words]) and the term's record of the sequence, last_dev; `extra`: one more copy ahead of the one
+    // synchronize (a priming record).  Zeroes *out but its struct_size, sets levels and, when tracked(record) says the sequence
+    // tracked at that push, n_iter (clamped to log_its) and calls unpack(level, it, row) for every logged iteration.
+    struct LogCopy { void* dst; const void* src; size_t bytes; };
+    template <class W, class Last, class Log, class Tracked, class Unpack>
+    int read_term_log(const W* log_dev, int words, int log_its, int seq, const Last* last_dev, Log* out, hipStream_t s, Tracked tracked,
+                      Unpack unpack, LogCopy extra = {}, bool* did_track = nullptr) const;
     // the argument blocks of the opt-in terms' kernels for the sequences from q0 on (launch_gn_term, launch_solve_term)
     RobustSolve robust_solve_args(size_t q0, bool adaptive) const;
     MedianSolve median_solve_args(size_t q0, bool log, bool prime, int* step_mn) const;

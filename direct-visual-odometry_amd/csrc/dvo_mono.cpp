@@ -284,9 +284,9 @@ int MonoBatch::odometrize(const FrameInput& in)
         launch_promote(pa, stream);
         launch_mono_commit(m, hist_xi.as<float>(), n_seq, R, 1, frame_id, xi_world.as<float>(), T_world.as<float>(), is_key.as<int>(), stream);
         DVO_HIP(hipGetLastError());
-        guess.rows_src = nullptr;
+        guess.given.clear();
         quality.ready = quality.on;
-        trk.robust_end_push(stream);
+        trk.end_terms(stream);
         latest_id = frame_id;
         return DVO_OK;
     }
@@ -321,7 +321,7 @@ int MonoBatch::odometrize(const FrameInput& in)
         }
         trk.seed = nullptr;
         DVO_TRY(rc);
-        guess.rows_src = nullptr;
+        guess.given.clear();
     }
     TraceRange tr_map("mono map (decide, propagate | update, promote, regularize)");
     DVO_HIP(hipMemsetAsync(need_list.p, 0, 4 * sizeof(int), stream));
@@ -400,7 +400,7 @@ int MonoBatch::odometrize(const FrameInput& in)
     }
     DVO_HIP(hipGetLastError());
     quality.ready = quality.on;
-    trk.robust_end_push(stream);
+    trk.end_terms(stream);
     latest_id = frame_id;
     return DVO_OK;
 }
