@@ -2603,6 +2603,53 @@ int Batch::fuse_keyframes(int frame_set, int kf)
     return DVO_OK;
 }
 
+// ------------------------------------------------------------------------------------------------ keyframe maps as point clouds
+int PointsExport::run(const Source& src, const dvo_points_config& cfg, uint32_t capacity, float* xyzg, uint32_t* src_idx, float* sigma_out,
+                      uint32_t* offsets_out, hipStream_t s)
+{
+    const size_t n = (size_t)src.n_seq;
+    if (!table.p) {   // (the top level has the most chunks: one allocation serves every level)
+        DVO_TRY(table.alloc(sizeof(PointsSeq) * n));
+        DVO_TRY(seq_total.alloc(sizeof(uint32_t) * n));
+        DVO_TRY(chunk_count.alloc(sizeof(uint32_t) * n * (size_t)points_chunks(src.top_w, src.top_h)));
+        DVO_TRY(offsets.alloc(sizeof(uint32_t) * (n + 1)));
+    }
+    PointsPrepArgs pa{};
+    pa.meta = src.meta; pa.started = src.started; pa.started_by_total = src.started_by_total; pa.is_key = src.is_key;
+    pa.select_new = cfg.select == DVO_POINTS_NEW ? 1 : 0;
+    pa.table = table.as<PointsSeq>(); pa.seq_total = seq_total.as<uint32_t>(); pa.n_seq = src.n_seq;
+    launch_points_prep(pa, s);
+    PointsArgs a{};
+    a.depth = src.depth; a.gray = src.gray; a.sigma = src.sigma;
+    a.age = cfg.min_age > 0.0f ? src.age : nullptr;
+    a.counts = cfg.min_count > 0 ? src.counts : nullptr;
+    a.table = table.as<PointsSeq>(); a.chunk_count = chunk_count.as<uint32_t>(); a.seq_total = seq_total.as<uint32_t>();
+    a.offsets = offsets.as<uint32_t>();
+    a.xyzg = xyzg; a.src = src_idx; a.sigma_out = sigma_out; a.capacity = capacity;
+    a.seq_k = src.seq_k; a.k = src.k;
+    a.w = src.w; a.h = src.h; a.n_seq = src.n_seq; a.stride = cfg.stride; a.min_count = cfg.min_count;
+    a.gate_sigma = cfg.max_sigma < __builtin_inff() ? 1 : 0;
+    a.min_depth = cfg.min_depth; a.max_depth = cfg.max_depth; a.max_sigma = cfg.max_sigma; a.min_age = cfg.min_age;
+    launch_points(a, offsets_out, s);
+    DVO_HIP(hipGetLastError());
+    ready = true;
+    return DVO_OK;
+}
+
+// the keyframes of a sensor-depth batch with keyframe tracking: fs[cur], kf_meta; no sigma or age maps, the fusion's counts
+PointsExport::Source Batch::points_source(int level) const
+{
+    PointsExport::Source src;
+    const FrameSet& F = fs[cur];
+    src.meta = kf_meta.as<MonoSeq>(); src.started_by_total = 1; src.is_key = is_key.as<int>();
+    src.depth = F.depth[level]; src.gray = F.gray[level];
+    src.counts = fuse.ran ? fuse.counts.as<uint8_t>() : nullptr;
+    src.seq_k = cam_table() ? cam_table() + (size_t)level * n_seq : nullptr;
+    src.k = g.k[level];
+    src.w = g.w[level]; src.h = g.h[level]; src.top_w = g.w[g.top()]; src.top_h = g.h[g.top()]; src.n_seq = n_seq;
+    return src;
+}
+
 // ------------------------------------------------------------------------------------------------ batch: tracking quality records
 int TrackQuality::set(bool enable, Tracker& trk, hipStream_t s)
 {

@@ -668,6 +668,26 @@ struct HostStage {
     ~HostStage() { release(); }
 };
 
+// Keyframe maps as compacted world-frame point clouds (dvo_batch_export_points), shared by both batch kinds: each
+// kind fills a Source (where its keyframes' planes, twists, flags and intrinsics live) and run() launches k_points_prep and
+// launch_points on the handle's stream.  Allocated on first use; a batch that never exports runs the launches it always ran.
+struct PointsExport {
+    DevBuf table, seq_total, chunk_count, offsets;   // PointsSeq [n_seq]; uint32 [n_seq]; uint32 [n_seq][chunks of the top level]; uint32 [n_seq + 1]
+    bool ready = false;                              // an export has been queued (dvo_batch_last_points)
+    struct Source {
+        const MonoSeq* meta = nullptr;
+        const uint8_t* started = nullptr; int started_by_total = 0;   // PointsPrepArgs
+        const int* is_key = nullptr;
+        const float* depth = nullptr; const float* gray = nullptr; const float* sigma = nullptr; const float* age = nullptr;
+        const uint8_t* counts = nullptr;
+        const Intr* seq_k = nullptr; Intr k{};
+        int w = 0, h = 0, top_w = 0, top_h = 0, n_seq = 0;
+    };
+    // cfg: validated, level and min_depth resolved (dvo_capi)
+    int run(const Source& src, const dvo_points_config& cfg, uint32_t capacity, float* xyzg, uint32_t* src_idx, float* sigma_out,
+            uint32_t* offsets_out, hipStream_t s);
+};
+
 struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tracking with sensor depth
     int n_seq = 0, device = 0;
     dvo_config cfg;
@@ -767,6 +787,8 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     } fuse;
     int set_keyframe_fusion(const dvo_kf_fusion_config* c);  // (validated by the caller)
     int fuse_keyframes(int frame_set, int kf);
+    PointsExport points;                                     // dvo_batch_export_points (keyframe tracking)
+    PointsExport::Source points_source(int level) const;
 };
 
 int select_device(int device);
@@ -847,6 +869,8 @@ struct MonoBatch {
     PoseGuess guess;                            // dvo_batch_set_pose_guess_mode / dvo_batch_set_pose_guess (world twists)
     int set_guess_mode(int mode);
     TrackQuality quality;                       // dvo_batch_set_track_quality
+    PointsExport points;                        // dvo_batch_export_points
+    PointsExport::Source points_source(int level) const;
 };
 
 void default_initial_depth(int n, uint32_t seed, std::vector<float>& d, std::vector<float>& s);

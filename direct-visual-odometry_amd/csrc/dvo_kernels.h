@@ -665,6 +665,53 @@ struct KfFuseArgs {
 };
 void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s);
 void launch_kf_fuse(const KfFuseArgs& a, hipStream_t s);
+// ---- keyframe maps as compacted world-frame point clouds (dvo_batch_export_points) ---------------------------------
+// k_points_prep (one thread per sequence) selects the sequence, writes Wk = float(exp(-ref_xi)) to its table entry and zeroes its
+// total.  k_points_count (grid = chunks x sequences, a chunk = 256 lanes x 4 consecutive pixels of the linearly addressed level
+// plane) evaluates the gates and writes one count per chunk; the counts of a sequence are also added to its total (an integer sum:
+// order-free).  k_points_scan (one workgroup) turns the totals into offsets [n_seq + 1].  k_points_write evaluates the gates again,
+// sums its sequence's chunk counts below its own in its head, ranks its points, stages them in LDS in rank order and stores them with
+// consecutive lanes on consecutive points.  Nothing is ordered by an atomic.
+#define DVO_POINTS_PER_THREAD 4
+#define DVO_POINTS_CHUNK (256 * DVO_POINTS_PER_THREAD)
+#define DVO_POINTS_MAX_PLANE (1 << 24)   /* split_row's range: pixels of one level plane */
+inline int points_chunks(int w, int h) { return (w * h + DVO_POINTS_CHUNK - 1) / DVO_POINTS_CHUNK; }
+struct PointsSeq {
+    Pose Wk;    // float(exp(-ref_xi)): pose_from_xi(ref_xi, -1), keyframe camera -> world
+    int on;     // the sequence contributes: started, and under DVO_POINTS_NEW its keyframe flag is set
+    int pad[3];
+};
+struct PointsPrepArgs {
+    const MonoSeq* meta;
+    const uint8_t* started;   // [n_seq] (a planned mono batch); nullptr: started_by_total, else every sequence
+    int started_by_total;     // a sequence has started once MonoSeq::n_total > 0 (sensor depth, as k_kf_decide)
+    const int* is_key;        // [n_seq] keyframe flag of the last push / call
+    int select_new;           // DVO_POINTS_NEW
+    PointsSeq* table;         // [n_seq]
+    uint32_t* seq_total;      // [n_seq] zeroed here
+    int n_seq;
+};
+struct PointsArgs {
+    const float* depth; const float* gray;   // the level's planes [n_seq][h][w]
+    const float* sigma;                      // mono: the level's sigma plane (gate and / or output), else nullptr
+    const float* age;                        // the age gate's plane (min_age > 0), else nullptr
+    const uint8_t* counts;                   // the count gate's plane (min_count > 0), else nullptr
+    const PointsSeq* table;
+    uint32_t* chunk_count;                   // [n_seq][chunks]
+    uint32_t* seq_total;                     // [n_seq]
+    uint32_t* offsets;                       // [n_seq + 1] (the handle's)
+    float* xyzg; uint32_t* src; float* sigma_out;   // [capacity][4], [capacity] or nullptr, [capacity] or nullptr
+    uint32_t capacity;
+    const Intr* seq_k = nullptr;             // per-sequence intrinsics of the level [n_seq] (k_points_write_cam), else k
+    Intr k;
+    int w, h, n_seq, stride, min_count, gate_sigma;
+    int chunks = 0;                          // points_chunks(w, h)   } set by launch_points
+    float inv_w = 0.0f;                      // 1 / w                 }
+    float min_depth, max_depth, max_sigma, min_age;
+};
+void launch_points_prep(const PointsPrepArgs& a, hipStream_t s);
+// count, scan and (capacity > 0) write; offsets_out: the caller's copy of the offsets [n_seq + 1]
+void launch_points(const PointsArgs& a, uint32_t* offsets_out, hipStream_t s);
 // k_regularize_redecimate_plan: k_regularize_redecimate for the TRACK sequences; a SKIP sequence copies its top-level depth forward to
 // depth_top_out (nothing else is written); a RESTART sequence starts: its keyframe becomes the frame's gray pyramid (ring slot 0 too),
 // the start map's depth and sigma with every level re-decimated and the weights, age 0 (the first frame of system.hpp:49-54).

@@ -1020,7 +1020,226 @@ __device__ __forceinline__ void kf_fuse(KfFuseArgs a)
 __global__ void __launch_bounds__(256) k_kf_fuse(KfFuseArgs a) { kf_fuse<false>(a); }
 __global__ void __launch_bounds__(256) k_kf_fuse_cam(KfFuseArgs a) { kf_fuse<true>(a); }
 
+// ------------------------------------------------------------------------------------------------
+// Keyframe maps as compacted world-frame point clouds (dvo_batch_export_points; the contract is in include/dvo.h).
+// Sequences in index order, raster order within a sequence: the order comes from ranks and prefix sums only.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_points_prep(PointsPrepArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    const MonoSeq& m = a.meta[s];
+    bool on = a.started ? a.started[s] != 0 : (a.started_by_total ? m.n_total > 0 : true);
+    if (a.select_new) on = on && a.is_key[s] != 0;
+    PointsSeq e;
+    for (int i = 0; i < 9; i++) e.Wk.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+    for (int i = 0; i < 3; i++) { e.Wk.t[i] = 0.0f; e.pad[i] = 0; }
+    e.on = on ? 1 : 0;
+    if (on) {
+        float xi[6];
+        for (int i = 0; i < 6; i++) xi[i] = m.ref_xi[i];
+        pose_from_xi(xi, -1.0f, e.Wk);
+    }
+    a.table[s] = e;
+    a.seq_total[s] = 0u;
+}
+
+// The gates of a lane's four consecutive pixels i0 .. i0 + nk - 1 of sequence plane `base`, as a bit mask; d[] = their depths and
+// (x, y) = the first pixel.  The planes move as 16-byte (counts: 4-byte) accesses declared unaligned, as k_kf_fuse's; the last lane
+// of a plane whose size is no multiple of 4 goes pixel by pixel.
+__device__ __forceinline__ uint32_t points_gates(const PointsArgs& a, size_t base, int i0, int nk, float d[DVO_POINTS_PER_THREAD], int& x, int& y)
+{
+    const size_t o = base + (size_t)(nk ? i0 : 0);
+    float sg[DVO_POINTS_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f}, ag[DVO_POINTS_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
+    uint32_t c4 = 0;
+    for (int k = 0; k < DVO_POINTS_PER_THREAD; k++) d[k] = 0.0f;
+    if (nk == DVO_POINTS_PER_THREAD) {
+        const kf_f4 v = *reinterpret_cast<const kf_f4*>(a.depth + o);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        if (a.gate_sigma) {
+            const kf_f4 t = *reinterpret_cast<const kf_f4*>(a.sigma + o);
+            sg[0] = t.x; sg[1] = t.y; sg[2] = t.z; sg[3] = t.w;
+        }
+        if (a.age) {
+            const kf_f4 t = *reinterpret_cast<const kf_f4*>(a.age + o);
+            ag[0] = t.x; ag[1] = t.y; ag[2] = t.z; ag[3] = t.w;
+        }
+        if (a.counts) c4 = *reinterpret_cast<const kf_u32*>(a.counts + o);
+    } else {
+        for (int k = 0; k < nk; k++) {
+            d[k] = a.depth[o + k];
+            if (a.gate_sigma) sg[k] = a.sigma[o + k];
+            if (a.age) ag[k] = a.age[o + k];
+            if (a.counts) c4 |= (uint32_t)a.counts[o + k] << (8 * k);
+        }
+    }
+    split_row(nk ? i0 : 0, a.w, a.inv_w, x, y);
+    const int st = a.stride;
+    int xx = x, xm = x % st, ym = y % st;
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < DVO_POINTS_PER_THREAD; k++) {
+        bool ok = (k < nk) & (d[k] >= a.min_depth) & (d[k] <= a.max_depth) & (d[k] < __builtin_inff()) & (xm == 0) & (ym == 0);
+        if (a.gate_sigma) ok = ok & (sg[k] <= a.max_sigma);
+        if (a.age) ok = ok & (ag[k] >= a.min_age);
+        if (a.counts) ok = ok & ((int)((c4 >> (8 * k)) & 0xffu) >= a.min_count);
+        m |= (ok ? 1u : 0u) << k;
+        xx++; xm++;
+        if (xm == st) xm = 0;
+        if (xx == a.w) { xx = 0; xm = 0; ym++; if (ym == st) ym = 0; }
+    }
+    return m;
+}
+
+__global__ void __launch_bounds__(256) k_points_count(PointsArgs a)
+{
+    const int seq = grid_seq();
+    if (seq >= a.n_seq) return;
+    if (!load_seq_entry(a.table, seq).on) return;   // uniform per workgroup
+    const int n = a.w * a.h;
+    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_POINTS_PER_THREAD;
+    const int nk = i0 >= n ? 0 : (n - i0 < DVO_POINTS_PER_THREAD ? n - i0 : DVO_POINTS_PER_THREAD);
+    float d[DVO_POINTS_PER_THREAD];
+    int x, y;
+    const uint32_t m = points_gates(a, (size_t)seq * n, i0, nk, d, x, y);
+    uint32_t c = 0;   // the wave's points: four ballots (every lane of the wave is here)
+#pragma unroll
+    for (int k = 0; k < DVO_POINTS_PER_THREAD; k++) c += (uint32_t)__popcll(__ballot((m >> k) & 1u));
+    __shared__ uint32_t wave_n[4];
+    if ((threadIdx.x & 63) == 0) wave_n[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];
+        a.chunk_count[(size_t)seq * a.chunks + blockIdx.x] = t;
+        if (t) atomicAdd(a.seq_total + seq, t);   // (an integer sum: the same total in any order)
+    }
+}
+
+// offsets[s] = the totals of the sequences below s, offsets[n_seq] = the grand total: one workgroup, each thread a run of consecutive
+// sequences, the 1 024 run sums scanned in LDS.
+__global__ void __launch_bounds__(1024) k_points_scan(const uint32_t* __restrict__ seq_total, int n_seq, uint32_t* __restrict__ offsets,
+                                                      uint32_t* __restrict__ offsets_out)
+{
+    __shared__ uint32_t part[1024];
+    const int t = (int)threadIdx.x;
+    const int per = (n_seq + 1023) / 1024;
+    const int s0 = t * per < n_seq ? t * per : n_seq, s1 = s0 + per < n_seq ? s0 + per : n_seq;
+    uint32_t sum = 0;
+    for (int s = s0; s < s1; s++) sum += seq_total[s];
+    part[t] = sum;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        const uint32_t v = t >= o ? part[t - o] : 0u;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[t] - sum;
+    for (int s = s0; s < s1; s++) {
+        offsets[s] = run;
+        if (offsets_out) offsets_out[s] = run;
+        run += seq_total[s];
+    }
+    if (t == 1023) {
+        offsets[n_seq] = part[1023];
+        if (offsets_out) offsets_out[n_seq] = part[1023];
+    }
+}
+
+typedef float pt_f4 __attribute__((ext_vector_type(4)));
+
+template <bool PCAM>
+__device__ __forceinline__ void points_write(PointsArgs a)
+{
+    const int seq = grid_seq();
+    if (seq >= a.n_seq) return;
+    const PointsSeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
+    if (!e.on) return;
+    const uint32_t* cc = a.chunk_count + (size_t)seq * a.chunks;
+    const int chunk = (int)blockIdx.x;
+    if (load_seq_entry(cc, chunk) == 0u) return;        // (the count pass found nothing here)
+    uint32_t below = 0;   // this wave's share of the sequence's chunks below this one
+    for (int c = (int)threadIdx.x; c < chunk; c += 256) below += cc[c];
+    for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
+    const int n = a.w * a.h;
+    const int i0 = (chunk * 256 + (int)threadIdx.x) * DVO_POINTS_PER_THREAD;
+    const int nk = i0 >= n ? 0 : (n - i0 < DVO_POINTS_PER_THREAD ? n - i0 : DVO_POINTS_PER_THREAD);
+    const size_t base = (size_t)seq * n;
+    float d[DVO_POINTS_PER_THREAD];
+    int x, y;
+    const uint32_t m = points_gates(a, base, i0, nk, d, x, y);
+    uint32_t lanes_below = 0, wave_total = 0;   // points of the wave's lower lanes (mbcnt of each ballot), and of the wave
+#pragma unroll
+    for (int k = 0; k < DVO_POINTS_PER_THREAD; k++) {
+        const unsigned long long b = __ballot((m >> k) & 1u);
+        lanes_below = __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, lanes_below));
+        wave_total += (uint32_t)__popcll(b);
+    }
+    __shared__ uint32_t wave_below[4], wave_n[4];
+    // the workgroup's points, staged in rank order: a lane's points are consecutive in the output, so storing them from the lane that
+    // made them would put the 64 stores of a wave 64 bytes apart; out of LDS consecutive lanes store consecutive points
+    __shared__ pt_f4 stage_p[DVO_POINTS_CHUNK];
+    __shared__ uint32_t stage_src[DVO_POINTS_CHUNK];
+    __shared__ float stage_sigma[DVO_POINTS_CHUNK];
+    const int wv = (int)threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { wave_below[wv] = below; wave_n[wv] = wave_total; }
+    __syncthreads();
+    const uint32_t first = load_seq_entry(a.offsets, seq) + wave_below[0] + wave_below[1] + wave_below[2] + wave_below[3];
+    const uint32_t total = wave_n[0] + wave_n[1] + wave_n[2] + wave_n[3];   // (at most DVO_POINTS_CHUNK)
+    if (first >= a.capacity) return;   // uniform: every point of the workgroup is at or past the capacity (counted, never written)
+    uint32_t local = lanes_below;      // rank within the workgroup
+    for (int v = 0; v < wv; v++) local += wave_n[v];
+    Intr cam;
+    if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
+#pragma unroll
+    for (int k = 0; k < DVO_POINTS_PER_THREAD; k++) {
+        if ((m >> k) & 1u) {
+            float X, Y, Z, Xw, Yw, Zw;
+            back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, d[k], X, Y, Z);
+            transform(e.Wk, X, Y, Z, Xw, Yw, Zw);
+            pt_f4 p;
+            p.x = Xw; p.y = Yw; p.z = Zw; p.w = a.gray[base + i0 + k];
+            stage_p[local] = p;
+            stage_src[local] = (uint32_t)(i0 + k);
+            if (a.sigma_out) stage_sigma[local] = a.sigma[base + i0 + k];
+            local++;
+        }
+        x++;
+        if (x == a.w) { x = 0; y++; }
+    }
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < total; j += 256) {
+        const uint32_t r = first + j;
+        if (r < a.capacity) {   // (a point at or past the capacity is counted, never written)
+            reinterpret_cast<pt_f4*>(a.xyzg)[r] = stage_p[j];
+            if (a.src) a.src[r] = stage_src[j];
+            if (a.sigma_out) a.sigma_out[r] = stage_sigma[j];
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_points_write(PointsArgs a) { points_write<false>(a); }
+__global__ void __launch_bounds__(256) k_points_write_cam(PointsArgs a) { points_write<true>(a); }
+
 // ------------------------------------------------------------------------------------------------ launch wrappers
+void launch_points_prep(const PointsPrepArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_points_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_points(const PointsArgs& a0, uint32_t* offsets_out, hipStream_t s)
+{
+    PointsArgs a = a0;
+    a.inv_w = 1.0f / (float)a.w;
+    a.chunks = points_chunks(a.w, a.h);
+    const dim3 grid = seq_grid((unsigned)a.chunks, (unsigned)a.n_seq);
+    hipLaunchKernelGGL(k_points_count, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_points_scan, dim3(1), dim3(1024), 0, s, a.seq_total, a.n_seq, a.offsets, offsets_out);
+    if (a.capacity == 0) return;   // the counting call
+    if (a.seq_k) hipLaunchKernelGGL(k_points_write_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+    else hipLaunchKernelGGL(k_points_write, grid, dim3(256), 0, s, a);
+}
+
 void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kf_fuse_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);

@@ -471,6 +471,20 @@ int MonoBatch::started_of(int seq, bool* out)
     return DVO_OK;
 }
 
+// the keyframes of a mono batch (dvo_batch_export_points): `ref`, its age map, `meta`; `started` once actions have been used
+PointsExport::Source MonoBatch::points_source(int level) const
+{
+    PointsExport::Source src;
+    src.meta = meta.as<MonoSeq>(); src.is_key = is_key.as<int>();
+    src.started = plan.act_used ? started.as<uint8_t>() : nullptr;   // (plain calls: every sequence has a keyframe)
+    src.depth = ref.depth[level]; src.gray = ref.gray[level]; src.sigma = ref.sigma[level];
+    src.age = level == g.top() ? ref_age.as<float>() : nullptr;
+    src.seq_k = cam_dev.p ? cam_dev.as<Intr>() + (size_t)level * n_seq : nullptr;
+    src.k = g.k[level];
+    src.w = g.w[level]; src.h = g.h[level]; src.top_w = g.w[g.top()]; src.top_h = g.h[g.top()]; src.n_seq = n_seq;
+    return src;
+}
+
 }  // namespace dvo
 
 using namespace dvo;
@@ -657,6 +671,77 @@ int dvo_batch_copy_world_poses_device(dvo_batch* b, float* xi_dst_dev, float* T_
     if (xi_dst_dev) DVO_HIP(hipMemcpyAsync(xi_dst_dev, w.xi, sizeof(float) * 6 * w.n, hipMemcpyDeviceToDevice, w.s));
     if (T_dst_dev) DVO_HIP(hipMemcpyAsync(T_dst_dev, w.T, sizeof(float) * 16 * w.n, hipMemcpyDeviceToDevice, w.s));
     if (key_dst_dev) DVO_HIP(hipMemcpyAsync(key_dst_dev, w.key, sizeof(int) * w.n, hipMemcpyDeviceToDevice, w.s));
+    return DVO_OK;
+}
+
+// ---- keyframe maps as compacted world-frame point clouds -----------------------------------------------------------
+void dvo_points_config_default(dvo_points_config* cfg)
+{
+    if (!cfg) return;
+    cfg->struct_size = (int)sizeof(dvo_points_config);
+    cfg->select = DVO_POINTS_ALL;
+    cfg->level = -1;           // the top level
+    cfg->stride = 1;
+    cfg->min_depth = -1.0f;    // the handle's dvo_config::min_depth
+    cfg->max_depth = __builtin_inff();
+    cfg->max_sigma = __builtin_inff();
+    cfg->min_age = 0.0f;
+    cfg->min_count = 0;
+}
+
+int dvo_batch_export_points(dvo_batch* b, const dvo_points_config* cfg, uint32_t capacity, float* xyzg_dev, uint32_t* src_dev, float* sigma_dev,
+                            uint32_t* offsets_dev)
+{
+    static const char who[] = "dvo_batch_export_points";
+    const auto bad = [](const char* what) { set_error(std::string(who) + ": " + what); return DVO_ERR_BAD_ARGUMENT; };
+    if (!b || !cfg || !offsets_dev) return DVO_ERR_BAD_ARGUMENT;
+    WorldPoses wp;
+    DVO_TRY(world_poses_of(b, wp));   // a mono batch, or a sensor-depth batch with keyframe tracking
+    const bool mono = b->mono != nullptr;
+    const Geometry& g = mono ? b->mono->g : b->impl.g;
+    const float inf = __builtin_inff();
+    if (cfg->struct_size != (int)sizeof(dvo_points_config)) return bad("struct_size is not sizeof(dvo_points_config)");
+    if (cfg->select != DVO_POINTS_ALL && cfg->select != DVO_POINTS_NEW) return bad("select is DVO_POINTS_ALL or DVO_POINTS_NEW");
+    if (cfg->level < -1 || cfg->level >= g.levels) return bad("level is outside [0, levels) (-1: the top level)");
+    if (cfg->stride < 1) return bad("stride must be >= 1");
+    dvo_points_config c = *cfg;
+    if (c.level < 0) c.level = g.top();
+    if (!(fabsf(c.min_depth) < inf)) return bad("min_depth must be finite");
+    if (c.min_depth < 0.0f) c.min_depth = mono ? b->mono->cfg.min_depth : b->impl.cfg.min_depth;
+    if (!(c.max_depth >= c.min_depth)) return bad("max_depth must be >= min_depth");
+    if (c.max_sigma != c.max_sigma) return bad("max_sigma must not be NaN");
+    const bool top = c.level == g.top();
+    if (!mono && (c.max_sigma != inf || sigma_dev)) return bad("a sensor-depth batch stores no sigma maps of its keyframes (max_sigma = +inf, sigma_dev = NULL)");
+    if (!(c.min_age >= 0.0f && c.min_age < inf)) return bad("min_age must be finite and >= 0");
+    if (c.min_age != 0.0f && !(mono && top)) return bad("min_age applies to the top level of a mono batch only");
+    if (c.min_count < 0 || c.min_count > 255) return bad("min_count is outside [0, 255]");
+    if (c.min_count != 0 && !(!mono && top && b->impl.fuse.ran)) return bad("min_count applies to the top level of a sensor-depth batch that has fused (dvo_batch_set_keyframe_fusion) only");
+    if (capacity > 0x7fffffffu) return bad("capacity is above 2^31 - 1");
+    if (capacity > 0 && (!xyzg_dev || (reinterpret_cast<uintptr_t>(xyzg_dev) & 15u))) return bad("xyzg_dev must be a 16-byte aligned device buffer when capacity > 0");
+    const long long plane = (long long)g.w[c.level] * g.h[c.level];
+    if (plane > DVO_POINTS_MAX_PLANE) return bad("the level has more than 2^24 pixels");
+    if (plane * (long long)wp.n > 0x7fffffffLL) return bad("n_seq * w_l * h_l is above 2^31 - 1");
+    if (!wp.ready) return DVO_ERR_NOT_READY;
+    if (!mono && b->impl.cam_pending) {
+        set_error(std::string(who) + ": the per-sequence intrinsics changed since the last push (the keyframes belong to that push's cameras): export before dvo_batch_set_intrinsics or after the next push");
+        return DVO_ERR_NOT_READY;
+    }
+    DVO_TRY(select_device(wp.device));
+    if (capacity == 0) { xyzg_dev = nullptr; src_dev = nullptr; sigma_dev = nullptr; }
+    if (mono) return b->mono->points.run(b->mono->points_source(c.level), c, capacity, xyzg_dev, src_dev, sigma_dev, offsets_dev, wp.s);
+    return b->impl.points.run(b->impl.points_source(c.level), c, capacity, xyzg_dev, src_dev, sigma_dev, offsets_dev, wp.s);
+}
+
+int dvo_batch_last_points(dvo_batch* b, uint32_t* offsets)
+{
+    if (!b || !offsets) return DVO_ERR_BAD_ARGUMENT;
+    WorldPoses wp;
+    DVO_TRY(world_poses_of(b, wp));
+    const PointsExport& P = b->mono ? b->mono->points : b->impl.points;
+    if (!P.ready) { set_error("dvo_batch_last_points: no dvo_batch_export_points call yet"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(wp.device));
+    DVO_HIP(hipMemcpyAsync(offsets, P.offsets.p, sizeof(uint32_t) * (wp.n + 1), hipMemcpyDeviceToHost, wp.s));
+    DVO_HIP(hipStreamSynchronize(wp.s));
     return DVO_OK;
 }
 

@@ -237,6 +237,7 @@ EXPORTS = [
     "dvo_debug_batch_last_pyramid_kernel",
     "dvo_lm_config_default", "dvo_batch_set_step_control", "dvo_batch_last_step_control", "dvo_batch_last_step_control_log",
     "dvo_op_lm_step",
+    "dvo_points_config_default", "dvo_batch_export_points", "dvo_batch_last_points",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -1204,6 +1205,63 @@ class _KeyframeFusion:
         return c
 
 
+class PointsConfig(C.Structure):
+    """dvo_points_config (include/dvo.h): which keyframe pixels dvo_batch_export_points exports."""
+    _fields_ = [("struct_size", C.c_int), ("select", C.c_int), ("level", C.c_int), ("stride", C.c_int), ("min_depth", C.c_float),
+                ("max_depth", C.c_float), ("max_sigma", C.c_float), ("min_age", C.c_float), ("min_count", C.c_int)]
+
+
+# which sequences an export selects (PointsConfig.select): include/dvo.h
+POINTS_ALL, POINTS_NEW = 0, 1
+
+
+def points_config(**kw):
+    """dvo_points_config_default (every started sequence, top level, stride 1, the handle's min_depth, no other gate) with `kw` set"""
+    c = PointsConfig()
+    lib().dvo_points_config_default(C.byref(c))
+    for k, v in kw.items():
+        if not hasattr(c, k):
+            raise AttributeError(k)
+        setattr(c, k, v)
+    return c
+
+
+class _PointsExport:
+    """The keyframe maps as compacted world-frame point clouds, shared by MonoBatch and a Batch with keyframe tracking
+    (dvo_batch_export_points, include/dvo.h)."""
+
+    def export_points(self, cfg, capacity, xyzg_ptr, src_ptr, sigma_ptr, offsets_ptr):
+        """Device pointers (ints): float32 [capacity, 4], uint32 [capacity] or 0, float32 [capacity] or 0 (mono only), uint32 [n_seq + 1].
+        Asynchronous on the handle's stream; cfg None = points_config()."""
+        c = cfg if cfg is not None else points_config()
+        _check(lib().dvo_batch_export_points(self._p, C.byref(c), C.c_uint32(int(capacity)), C.c_void_p(xyzg_ptr or None),
+                                             C.c_void_p(src_ptr or None), C.c_void_p(sigma_ptr or None), C.c_void_p(offsets_ptr or None)))
+
+    def last_points(self):
+        """uint32 [n_seq + 1]: the offsets of the last export_points (the last entry is the total); synchronises."""
+        off = np.zeros(self.n_seq + 1, np.uint32)
+        _check(lib().dvo_batch_last_points(self._p, off.ctypes.data_as(C.c_void_p)))
+        return off
+
+    def export_points_torch(self, cfg=None, capacity=None, want_src=True, want_sigma=False, device="cuda"):
+        """Allocates torch tensors and exports into them: (xyzg float32 [n, 4], src int32 [n] or None, sigma float32 [n] or None,
+        offsets int32 [n_seq + 1]), n = min(total, capacity).  capacity None: a counting call first, then exactly the total
+        (two synchronisations); otherwise one call and one synchronisation."""
+        import torch
+        off = torch.empty(self.n_seq + 1, dtype=torch.int32, device=device)
+        if capacity is None:
+            self.export_points(cfg, 0, 0, 0, 0, off.data_ptr())
+            capacity = int(self.last_points()[-1])
+        cap = int(capacity)
+        xyzg = torch.empty((max(cap, 1), 4), dtype=torch.float32, device=device)
+        src = torch.empty(max(cap, 1), dtype=torch.int32, device=device) if want_src else None
+        sig = torch.empty(max(cap, 1), dtype=torch.float32, device=device) if want_sigma else None
+        torch.cuda.synchronize()   # (the handle works on its own stream: nothing of torch's may still be pending on these blocks)
+        self.export_points(cfg, cap, xyzg.data_ptr(), src.data_ptr() if want_src else 0, sig.data_ptr() if want_sigma else 0, off.data_ptr())
+        n = min(int(self.last_points()[-1]), cap)
+        return xyzg[:n], (src[:n] if want_src else None), (sig[:n] if want_sigma else None), off
+
+
 class _WorldPoses:
     """World poses of the last frame, shared by MonoBatch and a Batch with keyframe tracking (dvo_batch_world_poses, include/dvo.h)."""
 
@@ -1217,7 +1275,7 @@ class _WorldPoses:
 
 
 # ------------------------------------------------------------------ batched tracking (n_seq sequences per GPU)
-class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm, _KeyframeFusion, _StepControl):
+class Batch(_PoseGuess, _WorldPoses, _PointsExport, _TrackQuality, _RobustWeights, _AffineBrightness, _GeometricTerm, _KeyframeFusion, _StepControl):
     def __init__(self, n_seq, K, width, height, levels=4, culls=1, cfg=None):
         K = f32(K).reshape(9)
         self.n_seq, self.width, self.height, self.levels, self.culls = n_seq, width, height, levels, culls
@@ -1383,7 +1441,7 @@ class Batch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrigh
         return ms.value, px.value
 
 
-class MonoBatch(_PoseGuess, _WorldPoses, _TrackQuality, _RobustWeights, _AffineBrightness, _StepControl):
+class MonoBatch(_PoseGuess, _WorldPoses, _PointsExport, _TrackQuality, _RobustWeights, _AffineBrightness, _StepControl):
     """n_seq mono sequences per GPU: System::VisualOdometry::odometrize (track + Mapper::estimate + regularize, system.hpp:44-74,
     src/map/mapper.cpp:16-144) for every sequence per call, keyframe decisions on the device (dvo_batch_create_mono)."""
 

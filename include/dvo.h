@@ -560,6 +560,55 @@ int dvo_batch_set_keyframe_fusion(dvo_batch* b, const dvo_kf_fusion_config* cfg)
 typedef struct dvo_kf_fusion_record { int struct_size, n_candidates, n_fused, n_gated; } dvo_kf_fusion_record;
 int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec /*[n_seq]*/);   /* host, synchronises */
 int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts /*[h_top][w_top]*/);
+/* ---- keyframe maps as compacted world-frame point clouds, on the device ------------------------------------------
+ * dvo_batch_export_points writes the semi-dense point set of every sequence's current keyframe into the caller's device buffers:
+ * a mono batch, or a sensor-depth batch with keyframe tracking.  Asynchronous, in stream order on the handle's stream; it reads the
+ * state the last push / call left and changes nothing in the handle's maps.  A batch that never calls it runs exactly the launches
+ * it always ran.
+ * Candidates: pixel (x, y) of level `level` (w_l x h_l) of a selected sequence with x % stride == 0 && y % stride == 0, d = the
+ * keyframe depth of that level (what dvo_batch_keyframe_get returns) with d >= min_depth && d <= max_depth (false for NaN / inf),
+ * and, where set: sigma[level][y][x] <= max_sigma (mono; +inf = no gate: the map is not read), age[y][x] >= min_age (mono, top level;
+ * 0 = no gate), count[y][x] >= min_count (sensor depth after a push that ran with keyframe fusion, top level; 0 = no gate).
+ * Selected: DVO_POINTS_ALL every sequence that has started; DVO_POINTS_NEW those of them whose last push / call made a keyframe
+ * (is_keyframe = 1 of dvo_batch_world_poses).  The others contribute no points.
+ * Order: sequences in index order, within a sequence raster order of the level.  offsets[s] = index of sequence s's first point,
+ * offsets[n_seq] = the total; for point i of sequence s: src[i] = y * w_l + x, xyzg[i] = (Xw, Yw, Zw, gray[level][y][x]),
+ * sigma[i] = sigma[level][y][x] (mono only).
+ * Arithmetic: float32, IEEE, no contraction beyond the fmaf()s named (as above): back_project(k_l, (float)x, (float)y, d) with the
+ * sequence's own level intrinsics (its row of the per-sequence table where the batch has one), then transform(Wk, ...), Wk = the
+ * float pose of exp(-ref_xi), bit for bit dvo_op_se3_exp(-ref_xi), ref_xi = the keyframe's world twist (xi of
+ * dvo_batch_keyframe_get): exp(ref_xi) takes world points into the keyframe camera (frame_xi = concatenate(ref_xi, rel_xi) and
+ * exp(rel_xi) takes keyframe-camera points into the tracked frame), so exp(-ref_xi) takes keyframe-camera points into the world.  The
+ * first keyframe sits at the identity.  A keyframe twist that is not finite gives coordinates that are not finite.
+ * Capacity: the offsets are always the full ones; a point whose index is >= capacity is not written and nothing at or past capacity
+ * is touched; capacity = 0 with NULL xyzg / src / sigma is the counting call.  dvo_batch_last_points copies the offsets of the last
+ * export to the host (synchronises), so the caller can compare offsets[n_seq] with its capacity.
+ * Errors, returned before anything is enqueued: a NULL handle, cfg or offsets_dev, or a plain sensor-depth batch ->
+ * DVO_ERR_BAD_ARGUMENT; before the first push / call -> DVO_ERR_NOT_READY; struct_size != sizeof(dvo_points_config), select outside
+ * {0, 1}, level outside [0, levels) and not -1, stride < 1, min_depth not finite, max_depth NaN or < min_depth, max_sigma NaN, a gate set where
+ * it does not apply (max_sigma != +inf or sigma_dev on a sensor-depth batch; min_age != 0 off a mono batch's top level, or negative
+ * or not finite; min_count != 0 off the top level of a sensor-depth batch that has fused, or outside [0, 255]), capacity > 0 with a
+ * NULL xyzg_dev or one not 16-byte aligned, capacity > 2^31 - 1, n_seq * w_l * h_l > 2^31 - 1, w_l * h_l > 2^24 ->
+ * DVO_ERR_BAD_ARGUMENT; per-sequence intrinsics changed (dvo_batch_set_intrinsics) since the last push -> DVO_ERR_NOT_READY (the
+ * keyframes belong to the cameras of that push); dvo_batch_last_points before an export -> DVO_ERR_NOT_READY. */
+#define DVO_POINTS_ALL 0   /* every started sequence's current keyframe */
+#define DVO_POINTS_NEW 1   /* only sequences whose last push / call made a keyframe (is_keyframe = 1) */
+typedef struct dvo_points_config {
+    int   struct_size;     /* sizeof(dvo_points_config) */
+    int   select;          /* DVO_POINTS_ALL / _NEW */
+    int   level;           /* pyramid level of the keyframe maps, 0 .. levels-1; -1 (the default) = levels-1, the top level */
+    int   stride;          /* >= 1: pixel (x, y) is a candidate iff x % stride == 0 && y % stride == 0 */
+    float min_depth, max_depth;   /* candidate iff d >= min_depth && d <= max_depth (false for NaN / inf); min_depth < 0 (the
+                                     default, -1) = the handle's dvo_config::min_depth */
+    float max_sigma;       /* mono: sigma[level] <= max_sigma; +inf = no gate.  Sensor depth: must be +inf */
+    float min_age;         /* mono, top level only: age >= min_age; 0 = no gate.  Elsewhere must be 0 */
+    int   min_count;       /* sensor depth with keyframe fusion on, top level only: count >= min_count; 0 = no gate.  Elsewhere must be 0 */
+} dvo_points_config;
+void dvo_points_config_default(dvo_points_config* cfg);   /* ALL, top level, stride 1, the handle's min_depth, max_depth +inf, no other gate */
+int dvo_batch_export_points(dvo_batch* b, const dvo_points_config* cfg, uint32_t capacity,
+                            float* xyzg_dev /*[capacity][4]*/, uint32_t* src_dev /*[capacity] or NULL*/,
+                            float* sigma_dev /*[capacity] or NULL; mono only*/, uint32_t* offsets_dev /*[n_seq + 1]*/);
+int dvo_batch_last_points(dvo_batch* b, uint32_t* offsets /*[n_seq + 1], host; synchronises*/);
 /* ---- per-sequence tracking quality (both batch kinds) ---------------------------------------------------------------------------
  * dvo_batch_set_track_quality(b, 1) makes every later push / call keep, per sequence, the sums of the LAST Gauss-Newton iteration of
  * the finest level (levels - 1: the solve that produced the returned pose); enable = 0 stops keeping them.  Poses, status, world

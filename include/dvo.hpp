@@ -328,6 +328,18 @@ public:
         check(dvo_batch_keyframe_fusion_counts(b_, seq, out.data()));
         return out;
     }
+    // with keyframe tracking: the keyframe maps as compacted world-frame points in the caller's DEVICE buffers (dvo_batch_export_points:
+    // asynchronous on the handle's stream; cfg from dvo_points_config_default); lastPoints: the offsets of that export (synchronises)
+    void exportPoints(const dvo_points_config& cfg, uint32_t capacity, float* xyzg_dev, uint32_t* src_dev, uint32_t* offsets_dev)
+    {
+        check(dvo_batch_export_points(b_, &cfg, capacity, xyzg_dev, src_dev, nullptr, offsets_dev));
+    }
+    std::vector<uint32_t> lastPoints()   // [n_seq + 1]
+    {
+        std::vector<uint32_t> out((size_t)n_ + 1);
+        check(dvo_batch_last_points(b_, out.data()));
+        return out;
+    }
     // with keyframe tracking: world poses of the last push (and its keyframe flags), as BatchMono::worldPoses
     std::vector<Mat4> worldPoses(std::vector<int>* is_keyframe = nullptr)
     {
@@ -507,6 +519,17 @@ public:
         std::vector<Mat4> out(n_);
         if (is_keyframe) is_keyframe->resize(n_);
         check(dvo_batch_world_poses(b_, nullptr, out[0].data(), is_keyframe ? is_keyframe->data() : nullptr));
+        return out;
+    }
+    // the keyframe maps as compacted world-frame points, as BatchTracker::exportPoints (sigma_dev may be set here)
+    void exportPoints(const dvo_points_config& cfg, uint32_t capacity, float* xyzg_dev, uint32_t* src_dev, float* sigma_dev, uint32_t* offsets_dev)
+    {
+        check(dvo_batch_export_points(b_, &cfg, capacity, xyzg_dev, src_dev, sigma_dev, offsets_dev));
+    }
+    std::vector<uint32_t> lastPoints()   // [n_seq + 1]
+    {
+        std::vector<uint32_t> out((size_t)n_ + 1);
+        check(dvo_batch_last_points(b_, out.data()));
         return out;
     }
     dvo_batch* handle() { return b_; }
