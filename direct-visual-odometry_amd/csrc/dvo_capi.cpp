@@ -465,6 +465,52 @@ int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts)
     return DVO_OK;
 }
 
+void dvo_kf_carry_config_default(dvo_kf_carry_config* cfg)
+{
+    if (!cfg) return;
+    cfg->struct_size = (int)sizeof(dvo_kf_carry_config);
+    cfg->mode = DVO_KF_CARRY_ON;
+    cfg->max_diff = 0.05f;
+}
+
+// the checks both keyframe-carry entry points share: a sensor-depth batch with keyframe tracking and fusion on
+static int kf_carry_handle_ok(dvo_batch* b, const char* who)
+{
+    DVO_TRY(kf_fusion_handle_ok(b, who));
+    if (!b->impl.fuse.on) { set_error(std::string(who) + ": keyframe fusion is off (dvo_batch_set_keyframe_fusion)"); return DVO_ERR_NOT_READY; }
+    return DVO_OK;
+}
+
+int dvo_batch_set_keyframe_carry(dvo_batch* b, const dvo_kf_carry_config* cfg)
+{
+    static const char who[] = "dvo_batch_set_keyframe_carry";
+    DVO_TRY(kf_carry_handle_ok(b, who));
+    if (cfg) {
+        if (cfg->struct_size != (int)sizeof(dvo_kf_carry_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_kf_carry_config)"); return DVO_ERR_BAD_ARGUMENT; }
+        if (cfg->mode != DVO_KF_CARRY_OFF && cfg->mode != DVO_KF_CARRY_ON) { set_error(std::string(who) + ": the mode is DVO_KF_CARRY_OFF or DVO_KF_CARRY_ON"); return DVO_ERR_BAD_ARGUMENT; }
+        if (!(cfg->max_diff > 0.0f && cfg->max_diff < __builtin_inff())) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+    }
+    return b->impl.set_keyframe_carry(cfg);
+}
+
+int dvo_batch_last_keyframe_carry(dvo_batch* b, dvo_kf_carry_record* rec)
+{
+    static const char who[] = "dvo_batch_last_keyframe_carry";
+    if (!rec) return DVO_ERR_BAD_ARGUMENT;
+    DVO_TRY(kf_carry_handle_ok(b, who));
+    Batch& B = b->impl;
+    if (!B.carry.ready) { set_error(std::string(who) + ": the last push did not run with keyframe carry (dvo_batch_set_keyframe_carry)"); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(B.device));
+    std::vector<KfCarryRecord> host((size_t)B.n_seq);
+    DVO_HIP(hipMemcpyAsync(host.data(), B.carry.rec.p, sizeof(KfCarryRecord) * host.size(), hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    for (size_t i = 0; i < host.size(); i++) {
+        rec[i].struct_size = (int)sizeof(dvo_kf_carry_record);
+        rec[i].n_candidates = host[i].n_candidates; rec[i].n_carried = host[i].n_carried; rec[i].n_gated = host[i].n_gated;
+    }
+    return DVO_OK;
+}
+
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;

@@ -2533,6 +2533,7 @@ int Batch::update_keyframes(int frame_set)
     ma.xi_world = xi_world.as<float>(); ma.T_world = T_world.as<float>(); ma.is_key = is_key.as<int>(); ma.need_list = need_list.as<int>();
     ma.n_seq = n_seq; ma.R = 1; ma.max_frames = cfg.keyframe_max_frames; ma.min_translation = cfg.keyframe_min_translation;
     launch_kf_decide(ma, stream);
+    const bool carried = carry_keyframes(frame_set, kf);   // (before the copy: the old keyframe is still there to gather from)
     if (frame_set == kf) return fuse_keyframes(frame_set, kf);   // (the first push: every sequence starts or stays empty)
     const FrameSet& src = fs[frame_set];
     FrameSet& dst = fs[kf];
@@ -2556,7 +2557,9 @@ int Batch::update_keyframes(int frame_set)
         pa.meta = kf_meta.as<MonoSeq>(); pa.all = 0; pa.need_list = need_list.as<int>();
         launch_promote(pa, stream);
     }
-    return fuse_keyframes(frame_set, kf);
+    DVO_TRY(fuse_keyframes(frame_set, kf));
+    if (carried) commit_carry();   // (k_kf_fuse has cleared the promoted sequences' counts)
+    return DVO_OK;
 }
 
 // ------------------------------------------------------------------------------------------------ batch: keyframe depth fusion
@@ -2575,6 +2578,7 @@ int Batch::set_keyframe_fusion(const dvo_kf_fusion_config* c)
     }
     if (enable) fuse.cfg = *c;
     fuse.on = enable;
+    if (!enable) carry.on = false;   // (the carry needs the count plane kept up to date)
     return DVO_OK;
 }
 
@@ -2601,6 +2605,56 @@ int Batch::fuse_keyframes(int frame_set, int kf)
     a.min_depth = cfg.min_depth; a.max_diff = fuse.cfg.max_diff; a.max_count = fuse.cfg.max_count;
     launch_kf_fuse(a, stream);
     return DVO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ batch: keyframe carry
+int Batch::set_keyframe_carry(const dvo_kf_carry_config* c)
+{
+    const bool enable = c && c->mode == DVO_KF_CARRY_ON;
+    if (enable && !carry.staged.p) {
+        DVO_TRY(select_device(device));
+        const size_t n = (size_t)n_seq, npix = (size_t)g.w[g.top()] * g.h[g.top()];
+        DVO_TRY(carry.staged.alloc(n * npix));
+        DVO_TRY(carry.table.alloc(sizeof(KfCarrySeq) * n));
+        DVO_TRY(carry.rec.alloc(sizeof(KfCarryRecord) * n));
+    }
+    if (enable) carry.cfg = *c;
+    carry.on = enable;
+    return DVO_OK;
+}
+
+// After k_kf_decide and before the promotions: k_kf_carry_prep resolves every sequence to carry / nothing, k_kf_carry works on the depth
+// pyramid of fs[frame_set] in place and gathers depth and counts from fs[kf] and the count plane, which nothing writes before k_promote
+// and k_kf_fuse (on the first push the two sets are one and no sequence can carry: only the records are zeroed).
+bool Batch::carry_keyframes(int frame_set, int kf)
+{
+    carry.ready = carry.on;
+    if (!carry.on) return false;
+    KfCarryPrepArgs pa{};
+    pa.meta = kf_meta.as<MonoSeq>(); pa.eff = plan.eff.as<uint8_t>(); pa.is_key = is_key.as<int>();
+    pa.table = carry.table.as<KfCarrySeq>(); pa.rec = carry.rec.as<KfCarryRecord>(); pa.n_seq = n_seq;
+    launch_kf_carry_prep(pa, stream);
+    if (frame_set == kf) return false;
+    KfCarryArgs a{};
+    const int T = g.top();
+    for (int l = 0; l < g.levels; l++) { a.frame_depth[l] = fs[frame_set].depth[l]; a.w[l] = g.w[l]; a.h[l] = g.h[l]; }
+    a.kf_depth = fs[kf].depth[T];
+    a.counts = fuse.counts.as<uint8_t>(); a.staged = carry.staged.as<uint8_t>();
+    a.table = carry.table.as<KfCarrySeq>(); a.rec = carry.rec.as<KfCarryRecord>();
+    a.seq_k = cam_table() ? cam_table() + (size_t)T * n_seq : nullptr;
+    a.k = g.k[T];
+    a.levels = g.levels; a.n_seq = n_seq;
+    a.min_depth = cfg.min_depth; a.max_diff = carry.cfg.max_diff; a.max_count = fuse.cfg.max_count;
+    launch_kf_carry(a, stream);
+    return true;
+}
+
+void Batch::commit_carry()
+{
+    KfCarryCommitArgs a{};
+    a.staged = carry.staged.as<uint8_t>(); a.counts = fuse.counts.as<uint8_t>(); a.table = carry.table.as<KfCarrySeq>();
+    a.npix = g.w[g.top()] * g.h[g.top()]; a.n_seq = n_seq;
+    launch_kf_carry_commit(a, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ keyframe maps as point clouds

@@ -787,6 +787,18 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     } fuse;
     int set_keyframe_fusion(const dvo_kf_fusion_config* c);  // (validated by the caller)
     int fuse_keyframes(int frame_set, int kf);
+    // Keyframe carry (dvo_batch_set_keyframe_carry): on a promotion k_kf_carry blends the old keyframe's fused depth,
+    // warped into the tracked frame, into the tracked set's depth pyramid before k_promote copies it, and the counts follow through a
+    // staging plane (k_kf_carry_commit, after k_kf_fuse has cleared).  Needs fusion; off (the default): no launch is added.
+    struct KfCarry {
+        bool on = false;
+        bool ready = false;      // the last push ran with carry on (dvo_batch_last_keyframe_carry)
+        dvo_kf_carry_config cfg = {(int)sizeof(dvo_kf_carry_config), DVO_KF_CARRY_OFF, 0.05f};
+        DevBuf staged, table, rec;   // uint8 [n_seq][h_top][w_top]; KfCarrySeq [n_seq]; KfCarryRecord [n_seq]
+    } carry;
+    int set_keyframe_carry(const dvo_kf_carry_config* c);    // (validated by the caller)
+    bool carry_keyframes(int frame_set, int kf);             // carry prep + carry; true when the commit has to follow the fusion
+    void commit_carry();
     PointsExport points;                                     // dvo_batch_export_points (keyframe tracking)
     PointsExport::Source points_source(int level) const;
 };

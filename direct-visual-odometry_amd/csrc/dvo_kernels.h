@@ -665,6 +665,51 @@ struct KfFuseArgs {
 };
 void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s);
 void launch_kf_fuse(const KfFuseArgs& a, hipStream_t s);
+// ---- keyframe carry of a sensor-depth batch (dvo_batch_set_keyframe_carry) ----------------------------------------
+// k_kf_carry_prep (one thread per sequence, after k_kf_decide) resolves every sequence to carry (TRACK, rule fired, finite twist) or
+// nothing into a table of its own and zeroes its record; k_kf_carry (before k_promote) blends the old keyframe's depth, warped into
+// the tracked frame, into the tracked set's depth pyramid in place and stages the new counts; k_kf_carry_commit (after k_kf_fuse has
+// cleared) copies the staged counts of the carrying sequences over the count plane.
+#define DVO_KF_CARRY_NONE  0
+#define DVO_KF_CARRY_CARRY 1
+struct KfCarrySeq {
+    Pose F;     // float(exp(+xi)): MonoSeq::rel_pose, old keyframe -> tracked frame
+    Pose Bk;    // float(exp(-xi)): pose_from_xi(xi, -1), tracked frame -> old keyframe
+    int mode;
+    int pad[3];
+};
+struct KfCarryRecord { int n_candidates, n_carried, n_gated, pad; };
+struct KfCarryPrepArgs {
+    const MonoSeq* meta;
+    const uint8_t* eff;      // [n_seq] effective action of the push (k_plan)
+    const int* is_key;       // [n_seq] k_kf_decide's keyframe flag
+    KfCarrySeq* table;       // [n_seq]
+    KfCarryRecord* rec;      // [n_seq]
+    int n_seq;
+};
+struct KfCarryArgs {
+    float* frame_depth[DVO_MAX_LEVELS];   // the tracked set's depth pyramid, [n_seq][h_l][w_l], updated in place
+    const float* kf_depth;                // the old keyframe's top-level depth [n_seq][h][w] (never the tracked set when a sequence carries)
+    const uint8_t* counts;                // the old keyframe's counts [n_seq][h][w]
+    uint8_t* staged;                      // the new counts [n_seq][h][w]
+    const KfCarrySeq* table;
+    KfCarryRecord* rec;
+    const Intr* seq_k = nullptr;          // per-sequence top-level intrinsics [n_seq] (k_kf_carry_cam), else k
+    Intr k;
+    int w[DVO_MAX_LEVELS], h[DVO_MAX_LEVELS], levels, n_seq;
+    float inv_w = 0.0f;                   // 1 / top-level width (set by launch_kf_carry)
+    float min_depth, max_diff;
+    int max_count;
+};
+struct KfCarryCommitArgs {
+    const uint8_t* staged;
+    uint8_t* counts;
+    const KfCarrySeq* table;
+    int npix, n_seq;
+};
+void launch_kf_carry_prep(const KfCarryPrepArgs& a, hipStream_t s);
+void launch_kf_carry(const KfCarryArgs& a, hipStream_t s);
+void launch_kf_carry_commit(const KfCarryCommitArgs& a, hipStream_t s);
 // ---- keyframe maps as compacted world-frame point clouds (dvo_batch_export_points) ---------------------------------
 // k_points_prep (one thread per sequence) selects the sequence, writes Wk = float(exp(-ref_xi)) to its table entry and zeroes its
 // total.  k_points_count (grid = chunks x sequences, a chunk = 256 lanes x 4 consecutive pixels of the linearly addressed level

@@ -1021,6 +1021,167 @@ __global__ void __launch_bounds__(256) k_kf_fuse(KfFuseArgs a) { kf_fuse<false>(
 __global__ void __launch_bounds__(256) k_kf_fuse_cam(KfFuseArgs a) { kf_fuse<true>(a); }
 
 // ------------------------------------------------------------------------------------------------
+// Keyframe carry of a sensor-depth batch (dvo_batch_set_keyframe_carry; the contract is in include/dvo.h): on a
+// promotion the old keyframe's fused depth and counts are warped into the frame that becomes the keyframe, before k_promote copies it.
+// k_kf_carry_prep: carry (TRACK, rule fired, finite twist: F and Bk as k_kf_fuse_prep's) or nothing, and the sequence's record zeroed.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(64) k_kf_carry_prep(KfCarryPrepArgs a)
+{
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= a.n_seq) return;
+    const MonoSeq& m = a.meta[s];
+    KfCarrySeq e;
+    for (int i = 0; i < 9; i++) { e.F.R[i] = 0.0f; e.Bk.R[i] = 0.0f; }
+    for (int i = 0; i < 3; i++) { e.F.t[i] = 0.0f; e.Bk.t[i] = 0.0f; e.pad[i] = 0; }
+    e.mode = DVO_KF_CARRY_NONE;
+    if (a.eff[s] == DVO_SEQ_TRACK && a.is_key[s]) {
+        float xi[6];
+        bool finite = true;
+        for (int i = 0; i < 6; i++) { xi[i] = m.rel_xi[i]; finite = finite && isfinite(xi[i]); }
+        if (finite) {
+            e.mode = DVO_KF_CARRY_CARRY;
+            e.F = m.rel_pose;
+            pose_from_xi(xi, -1.0f, e.Bk);
+        }
+    }
+    a.table[s] = e;
+    KfCarryRecord z;
+    z.n_candidates = 0; z.n_carried = 0; z.n_gated = 0; z.pad = 0;
+    a.rec[s] = z;
+}
+
+// k_kf_carry: k_kf_fuse's shape with the roles swapped.  A lane's own four pixels are the tracked frame's (the keyframe-to-be): it
+// reads and writes their depth in place and gathers four depth taps (two 8-byte pairs) and four count taps (bytes) from the old
+// keyframe, which nobody writes during this launch.  Neighbouring lanes gather the old counts, so the new counts go to a staging
+// plane (every pixel of a carrying sequence: 0 where nothing was carried) that k_kf_carry_commit copies after k_kf_fuse has cleared.
+typedef float kf_f2 __attribute__((ext_vector_type(2), aligned(4)));
+
+template <bool PCAM>
+__device__ __forceinline__ void kf_carry(KfCarryArgs a)
+{
+    const int seq = grid_seq();
+    if (seq >= a.n_seq) return;
+    const KfCarrySeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
+    if (e.mode != DVO_KF_CARRY_CARRY) return;
+    const int T = a.levels - 1, w = a.w[T], h = a.h[T], n = w * h;
+    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_KF_FUSE_PER_THREAD;
+    const int nk = i0 >= n ? 0 : (n - i0 < DVO_KF_FUSE_PER_THREAD ? n - i0 : DVO_KF_FUSE_PER_THREAD);
+    const bool full = nk == DVO_KF_FUSE_PER_THREAD;
+    const size_t base = (size_t)seq * n;
+    Intr cam;
+    if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
+    float* fd = a.frame_depth[T] + base + (nk ? i0 : 0);
+    uint8_t* st = a.staged + base + (nk ? i0 : 0);
+    const float* __restrict__ kd = a.kf_depth + base;
+    const uint8_t* __restrict__ kc = a.counts + base;
+    float d[DVO_KF_FUSE_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (full) {
+        const kf_f4 v = *reinterpret_cast<const kf_f4*>(fd);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    } else {
+        for (int k = 0; k < nk; k++) d[k] = fd[k];
+    }
+    int x, y;
+    split_row(nk ? i0 : 0, w, a.inv_w, x, y);
+    const float md = a.min_depth, inf = __builtin_inff();
+    const float wmax = (float)(w - 1), hmax = (float)(h - 1);
+    uint32_t c4 = 0;
+    int tally = 0;   // candidates | carried << 10 | gated << 20 (at most 4 of each per lane, 256 per wave)
+#pragma unroll
+    for (int k = 0; k < DVO_KF_FUSE_PER_THREAD; k++) {
+        const float dk = d[k];
+        if (k < nk && dk >= md && dk < inf) {
+            tally += 1;
+            float X, Y, Z, Xk, Yk, Zk;
+            back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, dk, X, Y, Z);
+            transform(e.Bk, X, Y, Z, Xk, Yk, Zk);
+            if (Zk >= md) {
+                float u, v;
+                project(map_intr<PCAM>(a, cam), Xk, Yk, Zk, u, v);
+                if (u >= 0.0f && u < wmax && v >= 0.0f && v < hmax) {
+                    const int x0 = (int)u, y0 = (int)v;
+                    const float fa = u - (float)x0, fb = v - (float)y0;
+                    const size_t o = (size_t)y0 * w + x0;
+                    const kf_f2 r0 = *reinterpret_cast<const kf_f2*>(kd + o), r1 = *reinterpret_cast<const kf_f2*>(kd + o + w);
+                    const float z00 = r0.x, z10 = r0.y, z01 = r1.x, z11 = r1.y;
+                    bool ok = (z00 >= md) & (z00 < inf) & (z10 >= md) & (z10 < inf) & (z01 >= md) & (z01 < inf) & (z11 >= md) & (z11 < inf);
+                    const float mx = fmaxf(fmaxf(z00, z10), fmaxf(z01, z11)), mn = fminf(fminf(z00, z10), fminf(z01, z11));
+                    ok = ok && (mx - mn <= a.max_diff);
+                    if (ok) {
+                        const float top = fmaf(fa, z10 - z00, z00), bot = fmaf(fa, z11 - z01, z01);
+                        const float zi = fmaf(fb, bot - top, top);
+                        if (fabsf(zi - Zk) <= a.max_diff) {
+                            float Xp, Yp, Zp;
+                            back_project(map_intr<PCAM>(a, cam), u, v, zi, X, Y, Z);
+                            transform(e.F, X, Y, Z, Xp, Yp, Zp);
+                            if (Zp >= md && Zp < inf) {
+                                const int c00 = kc[o], c10 = kc[o + 1], c01 = kc[o + w], c11 = kc[o + w + 1];
+                                const int ca = c00 < c10 ? c00 : c10, cb = c01 < c11 ? c01 : c11;
+                                const int c = ca < cb ? ca : cb;   // the old map stands for c + 1 samples, the pixel's own for one
+                                const float r = (float)(c + 1) * recip_rn((float)(c + 2));
+                                const float dn = fmaf(Zp - dk, r, dk);
+                                if (dn >= md && dn < inf) {
+                                    const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
+                                    d[k] = dn;
+                                    c4 |= (uint32_t)cn << (8 * k);
+                                    tally += 1 << 10;
+                                    for (int t = 1; t < a.levels; t++) {   // lower levels keep pixels whose coordinates are multiples of 2^t
+                                        const int msk = (1 << t) - 1;
+                                        if ((x & msk) | (y & msk)) break;
+                                        const int l = T - t, lx = x >> t, ly = y >> t;
+                                        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+                                        a.frame_depth[l][(size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx] = dn;
+                                    }
+                                }
+                            }
+                        } else {
+                            tally += 1 << 20;
+                        }
+                    }
+                }
+            }
+        }
+        x++;
+        if (x == w) { x = 0; y++; }
+    }
+    if (full) {
+        *reinterpret_cast<kf_u32*>(st) = c4;
+        if (tally & (0x3ff << 10)) {   // something carried: the lane's pixels go back
+            kf_f4 v;
+            v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
+            *reinterpret_cast<kf_f4*>(fd) = v;
+        }
+    } else {
+        for (int k = 0; k < nk; k++) { st[k] = (uint8_t)(c4 >> (8 * k)); fd[k] = d[k]; }
+    }
+    for (int o = 32; o > 0; o >>= 1) tally += __shfl_xor(tally, o);   // (every lane of the wave is here: no lane left early)
+    if ((threadIdx.x & 63) == 0) {
+        KfCarryRecord* r = a.rec + seq;
+        if (tally & 0x3ff) atomicAdd(&r->n_candidates, tally & 0x3ff);
+        if ((tally >> 10) & 0x3ff) atomicAdd(&r->n_carried, (tally >> 10) & 0x3ff);
+        if ((tally >> 20) & 0x3ff) atomicAdd(&r->n_gated, (tally >> 20) & 0x3ff);
+    }
+}
+
+__global__ void __launch_bounds__(256) k_kf_carry(KfCarryArgs a) { kf_carry<false>(a); }
+__global__ void __launch_bounds__(256) k_kf_carry_cam(KfCarryArgs a) { kf_carry<true>(a); }
+
+// k_kf_carry_commit: the staged counts of the carrying sequences over the count plane (which k_kf_fuse has just cleared), four bytes
+// per lane, declared unaligned; the last lane of a plane whose size is no multiple of 4 goes byte by byte.
+__global__ void __launch_bounds__(256) k_kf_carry_commit(KfCarryCommitArgs a)
+{
+    const int seq = grid_seq();
+    if (seq >= a.n_seq) return;
+    if (load_seq_entry(a.table, seq).mode != DVO_KF_CARRY_CARRY) return;   // uniform per workgroup
+    const int n = a.npix;
+    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const size_t o = (size_t)seq * n + i0;
+    if (n - i0 >= 4) *reinterpret_cast<kf_u32*>(a.counts + o) = *reinterpret_cast<const kf_u32*>(a.staged + o);
+    else for (int k = 0; k < n - i0; k++) a.counts[o + k] = a.staged[o + k];
+}
+
+// ------------------------------------------------------------------------------------------------
 // Keyframe maps as compacted world-frame point clouds (dvo_batch_export_points; the contract is in include/dvo.h).
 // Sequences in index order, raster order within a sequence: the order comes from ranks and prefix sums only.
 // ------------------------------------------------------------------------------------------------
@@ -1253,6 +1414,26 @@ void launch_kf_fuse(const KfFuseArgs& a0, hipStream_t s)
     const dim3 grid = seq_grid(cdiv_u(a.w[T] * a.h[T], 256 * DVO_KF_FUSE_PER_THREAD), (unsigned)a.n_seq);
     if (a.seq_k) hipLaunchKernelGGL(k_kf_fuse_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
     else hipLaunchKernelGGL(k_kf_fuse, grid, dim3(256), 0, s, a);
+}
+
+void launch_kf_carry_prep(const KfCarryPrepArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kf_carry_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
+}
+
+void launch_kf_carry(const KfCarryArgs& a0, hipStream_t s)
+{
+    KfCarryArgs a = a0;
+    const int T = a.levels - 1;
+    a.inv_w = 1.0f / (float)a.w[T];
+    const dim3 grid = seq_grid(cdiv_u(a.w[T] * a.h[T], 256 * DVO_KF_FUSE_PER_THREAD), (unsigned)a.n_seq);
+    if (a.seq_k) hipLaunchKernelGGL(k_kf_carry_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
+    else hipLaunchKernelGGL(k_kf_carry, grid, dim3(256), 0, s, a);
+}
+
+void launch_kf_carry_commit(const KfCarryCommitArgs& a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_kf_carry_commit, seq_grid(cdiv_u(a.npix, 256 * 4), (unsigned)a.n_seq), dim3(256), 0, s, a);
 }
 
 void launch_mono_decide(MonoSeq* meta, const SeqState* state, int n_seq, int frame_id, float min_translation, int max_frames,

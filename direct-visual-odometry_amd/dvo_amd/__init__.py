@@ -230,6 +230,7 @@ EXPORTS = [
     "dvo_op_gn_step_geometric",
     "dvo_batch_set_geometric_affine", "dvo_op_gn_step_geometric_affine",
     "dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts",
+    "dvo_kf_carry_config_default", "dvo_batch_set_keyframe_carry", "dvo_batch_last_keyframe_carry",
     "dvo_op_pyramid_frames",
     "dvo_op_depth_update_batch",
     "dvo_batch_set_robust_median", "dvo_batch_last_robust_log", "dvo_batch_last_robust_histogram", "dvo_op_gn_step_robust_median",
@@ -262,6 +263,8 @@ LM_OFF, LM_ON = 0, 1
 LM_FIRST, LM_ACCEPT, LM_REJECT = 1, 2, 3
 # keyframe depth fusion (Batch.set_keyframe_fusion): include/dvo.h
 KF_FUSION_OFF, KF_FUSION_ON = 0, 1
+# keyframe carry (Batch.set_keyframe_carry): include/dvo.h
+KF_CARRY_OFF, KF_CARRY_ON = 0, 1
 # launch form of a level (Batch / MonoBatch .level_plan): include/dvo.h
 PLAN_PAIRS, PLAN_ITERATION, PLAN_LEVEL, PLAN_LDS_PATCH = 0, 1, 2, 3
 
@@ -282,6 +285,21 @@ class KfFusionRecord(C.Structure):
 
 
 KF_FUSION_RECORD_DTYPE = np.dtype([("struct_size", np.int32), ("n_candidates", np.int32), ("n_fused", np.int32), ("n_gated", np.int32)])
+
+
+
+class KfCarryConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("mode", C.c_int), ("max_diff", C.c_float)]
+
+    def __init__(self, mode=KF_CARRY_ON, max_diff=0.05, struct_size=None):
+        super().__init__(C.sizeof(KfCarryConfig) if struct_size is None else int(struct_size), int(mode), float(max_diff))
+
+
+class KfCarryRecord(C.Structure):
+    _fields_ = [("struct_size", C.c_int), ("n_candidates", C.c_int), ("n_carried", C.c_int), ("n_gated", C.c_int)]
+
+
+KF_CARRY_RECORD_DTYPE = np.dtype([("struct_size", np.int32), ("n_candidates", np.int32), ("n_carried", np.int32), ("n_gated", np.int32)])
 
 # the kernel a pyramid build ran and the flags of op_pyramid_frames: include/dvo.h
 PYRAMID_KERNEL_SCALAR, PYRAMID_KERNEL_RAW4, PYRAMID_KERNEL_SPLIT, PYRAMID_KERNEL_REMAP = 0, 1, 2, 3
@@ -1203,6 +1221,22 @@ class _KeyframeFusion:
         c = np.zeros((self.height >> shift, self.width >> shift), np.uint8)
         _check(lib().dvo_batch_keyframe_fusion_counts(self._p, int(seq), c.ctypes.data_as(C.c_void_p)))
         return c
+
+    def set_keyframe_carry(self, mode=KF_CARRY_ON, max_diff=0.05):
+        """KF_CARRY_ON (needs fusion on): every later promotion blends the old keyframe's fused depth, warped into the frame that becomes
+        the keyframe, into that frame's depth and carries the counts along, so the map outlives its keyframe; KF_CARRY_OFF or None:
+        stop, maps and counts stay as they are.  After a carrying push frame() returns the carried depth for the promoted sequences."""
+        if mode is None:
+            _check(lib().dvo_batch_set_keyframe_carry(self._p, None))
+            return
+        c = KfCarryConfig(int(mode), float(max_diff))
+        _check(lib().dvo_batch_set_keyframe_carry(self._p, C.byref(c)))
+
+    def last_keyframe_carry(self):
+        """record array [n_seq] (n_candidates, n_carried, n_gated) of the last push (zeros: the sequence did not promote); synchronises."""
+        rec = np.zeros(self.n_seq, KF_CARRY_RECORD_DTYPE)
+        _check(lib().dvo_batch_last_keyframe_carry(self._p, rec.ctypes.data_as(C.POINTER(KfCarryRecord))))
+        return rec
 
 
 class PointsConfig(C.Structure):

@@ -560,6 +560,48 @@ int dvo_batch_set_keyframe_fusion(dvo_batch* b, const dvo_kf_fusion_config* cfg)
 typedef struct dvo_kf_fusion_record { int struct_size, n_candidates, n_fused, n_gated; } dvo_kf_fusion_record;
 int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec /*[n_seq]*/);   /* host, synchronises */
 int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts /*[h_top][w_top]*/);
+/* ---- keyframe carry: fused depth and counts survive a promotion --------------------------------------------------
+ * Without it a promotion copies the tracked frame's single measurement over the fused map and the counts restart at 0.
+ * dvo_batch_set_keyframe_carry makes every later promotion blend the old keyframe's fused depth, warped into the frame that becomes
+ * the keyframe, into that frame's depth before it is copied, and carry the counts along (three kernels: k_kf_carry_prep, k_kf_carry,
+ * k_kf_carry_commit; no existing kernel changes).  A batch that never calls it runs exactly the launches it always ran.
+ * Contract: float32, IEEE, no contraction beyond the fmaf()s named; T, k, xi, F = the float pose of exp(xi) and Bk = the float pose
+ * of exp(-xi) (bit for bit dvo_op_se3_exp(-xi)) as for the fusion above.  The carry runs on a push that TRACKED the sequence with the
+ * keyframe rule fired and all six components of xi finite, after the keyframe decision and BEFORE the tracked frame is copied over
+ * the keyframe.  For every top-level pixel (x, y) of the TRACKED frame (the keyframe-to-be):
+ *    1. d = frame_depth[T][y][x]; the pixel is a CANDIDATE iff d >= min_depth and d < inf (false for NaN: holes are never filled).
+ *    2. back_project(k, (float)x, (float)y, d), transform(Bk, ...) -> (Xk, Yk, Zk); Zk >= min_depth; project(k, ...) -> (u, v).
+ *    3. 0 <= u < w - 1 and 0 <= v < h - 1 (false for NaN / inf); x0 = (int)u, y0 = (int)v, a = u - (float)x0, b = v - (float)y0.
+ *    4. the taps z00, z10, z01, z11 of the OLD keyframe's top-level depth at (x0, y0) .. (x0 + 1, y0 + 1): all >= min_depth and
+ *       < inf, and max4 - min4 <= max_diff.
+ *    5. top = fmaf(a, z10 - z00, z00), bot = fmaf(a, z11 - z01, z01), zi = fmaf(b, bot - top, top).
+ *    6. fabsf(zi - Zk) <= max_diff (the carry's own max_diff).
+ *    7. back_project(k, u, v, zi), transform(F, ...): d_prior = its z; d_prior >= min_depth and < inf.
+ *    8. c_prior = the minimum of the four taps' counts: the old map stands for c_prior + 1 samples, the pixel's own measurement for
+ *       one.  r = (float)(c_prior + 1) * (1.0f / (float)(c_prior + 2)) (the IEEE quotient, then one rounded product),
+ *       d_new = fmaf(d_prior - d, r, d); d_new >= min_depth and < inf.
+ *    9. c_new = min(c_prior + 1, max_count) with the fusion's max_count; d_new -> the frame's depth at level T and at every coarser
+ *       level whose point decimation picks the pixel, as the fusion's step 9; the copy then makes it the keyframe.
+ *   A pixel that fails anywhere keeps d and gets count 0; a candidate failing only at 6 counts in n_gated, one reaching 9 in
+ *   n_carried.  The counters are integer sums: order-free, deterministic.  Gray, sigma and the weight maps are not touched.
+ *   STARTED sequences, and TRACKED ones whose rule fired with a non-finite xi, clear as without the carry; SKIPPED / BAD_ACTION: nothing
+ *   is read or written; TRACKED without the rule firing: the fusion above.  Records of sequences that did not carry are zeros.
+ * The carried depth is written into the tracked frame's own pyramid: after a carrying push dvo_batch_frame_get returns the carried
+ * depth for the promoted sequences (it is what became the keyframe) and the untouched frame for the others.
+ * dvo_batch_set_keyframe_carry: between any two pushes while keyframe tracking and fusion are on; from the next push on; cfg NULL or
+ * mode DVO_KF_CARRY_OFF stops carrying and leaves maps and counts as they are; turning fusion off turns the carry off.  The first
+ * use allocates a uint8 staging plane [n_seq][h][w].  dvo_batch_last_keyframe_carry: the records [n_seq] of the last push (host,
+ * synchronises; struct_size is set to sizeof(dvo_kf_carry_record)).
+ * Errors, returned before anything is enqueued or changed: a NULL handle (or NULL output) or a mono batch -> DVO_ERR_BAD_ARGUMENT;
+ * no keyframe tracking, or fusion not on -> DVO_ERR_NOT_READY; struct_size != sizeof(dvo_kf_carry_config), mode outside {0, 1},
+ * max_diff not finite or <= 0 -> DVO_ERR_BAD_ARGUMENT; the reader before a push that ran with carry on -> DVO_ERR_NOT_READY. */
+#define DVO_KF_CARRY_OFF 0
+#define DVO_KF_CARRY_ON  1
+typedef struct dvo_kf_carry_config { int struct_size; int mode; float max_diff; } dvo_kf_carry_config;
+void dvo_kf_carry_config_default(dvo_kf_carry_config* cfg);   /* struct_size, DVO_KF_CARRY_ON, max_diff = 0.05 */
+int dvo_batch_set_keyframe_carry(dvo_batch* b, const dvo_kf_carry_config* cfg);   /* from the next push on; NULL cfg = OFF */
+typedef struct dvo_kf_carry_record { int struct_size, n_candidates, n_carried, n_gated; } dvo_kf_carry_record;
+int dvo_batch_last_keyframe_carry(dvo_batch* b, dvo_kf_carry_record* rec /*[n_seq]*/);   /* host, synchronises */
 /* ---- keyframe maps as compacted world-frame point clouds, on the device ------------------------------------------
  * dvo_batch_export_points writes the semi-dense point set of every sequence's current keyframe into the caller's device buffers:
  * a mono batch, or a sensor-depth batch with keyframe tracking.  Asynchronous, in stream order on the handle's stream; it reads the

@@ -328,6 +328,19 @@ public:
         check(dvo_batch_keyframe_fusion_counts(b_, seq, out.data()));
         return out;
     }
+    // with keyframe fusion: carry the fused depth and the counts into the next keyframe at every promotion from the next push on
+    // (dvo_batch_set_keyframe_carry); mode DVO_KF_CARRY_OFF stops and leaves maps and counts as they are
+    void setKeyframeCarry(int mode = DVO_KF_CARRY_ON, float max_diff = 0.05f)
+    {
+        dvo_kf_carry_config c{(int)sizeof(dvo_kf_carry_config), mode, max_diff};
+        check(dvo_batch_set_keyframe_carry(b_, &c));
+    }
+    std::vector<dvo_kf_carry_record> lastKeyframeCarry()   // [n_seq]
+    {
+        std::vector<dvo_kf_carry_record> out(n_);
+        check(dvo_batch_last_keyframe_carry(b_, out.data()));
+        return out;
+    }
     // with keyframe tracking: the keyframe maps as compacted world-frame points in the caller's DEVICE buffers (dvo_batch_export_points:
     // asynchronous on the handle's stream; cfg from dvo_points_config_default); lastPoints: the offsets of that export (synchronises)
     void exportPoints(const dvo_points_config& cfg, uint32_t capacity, float* xyzg_dev, uint32_t* src_dev, uint32_t* offsets_dev)

@@ -13,8 +13,12 @@ Every sequence tracks at every push after the first.  Prints one JSON line.
 --fusion adds two modes to the alternation (without the flag the tool runs what it always ran):
   kf_long    keyframe tracking with long-lived keyframes (keyframe_min_translation 1.0, keyframe_max_frames 8)
   kf_fused   the same with keyframe depth fusion on (dvo_batch_set_keyframe_fusion): vs_kf_long is its cost
+--carry (with --fusion) adds one more:
+  kf_carry   kf_fused with the keyframe carry on (dvo_batch_set_keyframe_carry): vs_kf_fused is its cost; the
+             carry kernels run on the promoting pushes only (one in eight here), carried_fraction is n_carried / n_candidates of the
+             last promoting push (read after the push's closing event: not timed)
 
-    python tools/bench_keyframes.py --batch 16384 --steps 12 --warmup 3 --rounds 2 [--fusion]
+    python tools/bench_keyframes.py --batch 16384 --steps 12 --warmup 3 --rounds 2 [--fusion [--carry]]
 """
 import argparse
 import json
@@ -36,6 +40,7 @@ WORKLOADS = {"default": {}, "converging": dict(step_default=1.0, step_level1=0.7
 MODES = {"plain": None, "kf": {}, "kf1": dict(keyframe_max_frames=1)}
 LONG = dict(keyframe_min_translation=1.0, keyframe_max_frames=8)
 FUSION_MODES = {"kf_long": dict(LONG), "kf_fused": dict(LONG)}
+CARRY_MODES = {"kf_carry": dict(LONG)}
 
 
 def run(workload, mode, a, g8, d16, stream):
@@ -47,8 +52,11 @@ def run(workload, mode, a, g8, d16, stream):
     bt = dvo.Batch(B, synth.K_640, W, H, 4, 1, cfg=dvo.default_config(stream=stream, **kw))
     if kf is not None:
         bt.set_keyframe_tracking(True)
-    if mode == "kf_fused":
+    if mode in ("kf_fused", "kf_carry"):
         bt.set_keyframe_fusion()
+    if mode == "kf_carry":
+        bt.set_keyframe_carry()
+    carried = None
     key = torch.zeros((a.steps, B), dtype=torch.int32, device="cuda")
     ev = []
     n = 1 + a.warmup + a.steps
@@ -64,6 +72,10 @@ def run(workload, mode, a, g8, d16, stream):
             ev.append((e0, e1))
             if kf is not None:   # (after the event: the copy is not timed)
                 bt.copy_world_poses_device(0, 0, key[k - a.warmup - 1].data_ptr())
+            if mode == "kf_carry":
+                rec = bt.last_keyframe_carry()
+                if rec["n_candidates"].any():
+                    carried = float(rec["n_carried"].sum()) / float(rec["n_candidates"].sum())
     torch.cuda.synchronize()
     ms = sum(e0.elapsed_time(e1) for e0, e1 in ev)
     xi, _ = bt.last_poses()
@@ -74,7 +86,8 @@ def run(workload, mode, a, g8, d16, stream):
     bt.close()
     assert np.all(np.isfinite(xi)), "non-finite poses"
     return {"ms_per_push": ms / a.steps, "tracked_frames_per_s": B * a.steps / (ms / 1e3),
-            "promoted_fraction": float(key.float().mean().item()) if kf is not None else None, "fused_fraction_last_push": fused}
+            "promoted_fraction": float(key.float().mean().item()) if kf is not None else None, "fused_fraction_last_push": fused,
+            "carried_fraction": carried}
 
 
 def main():
@@ -86,9 +99,14 @@ def main():
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--workloads", default="default,converging")
     ap.add_argument("--fusion", action="store_true", help="also alternate kf_long and kf_fused (keyframe depth fusion)")
+    ap.add_argument("--carry", action="store_true", help="with --fusion: also alternate kf_carry (keyframe carry)")
     a = ap.parse_args()
+    if a.carry and not a.fusion:
+        ap.error("--carry needs --fusion")
     if a.fusion:
         MODES.update(FUSION_MODES)
+    if a.carry:
+        MODES.update(CARRY_MODES)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream().cuda_stream
     g8, d16 = frames(a.batch, a.unique, dev)
@@ -118,6 +136,10 @@ def main():
                 summary[w][m]["vs_plain"] = round(summary[w][m]["ms_per_push"] / base, 4)
             summary[w]["kf_fused"]["vs_kf_long"] = round(summary[w]["kf_fused"]["ms_per_push"] / summary[w]["kf_long"]["ms_per_push"], 4)
             summary[w]["kf_fused"]["fused_fraction_last_push"] = res[(w, "kf_fused")][-1]["fused_fraction_last_push"]
+        if a.carry:
+            summary[w]["kf_carry"]["vs_plain"] = round(summary[w]["kf_carry"]["ms_per_push"] / base, 4)
+            summary[w]["kf_carry"]["vs_kf_fused"] = round(summary[w]["kf_carry"]["ms_per_push"] / summary[w]["kf_fused"]["ms_per_push"], 4)
+            summary[w]["kf_carry"]["carried_fraction"] = res[(w, "kf_carry")][-1]["carried_fraction"]
     print(json.dumps({"batch": a.batch, "steps": a.steps, "warmup": a.warmup, "rounds": a.rounds, "frames_per_sequence": F,
                       "workloads": summary}))
     return 0
