@@ -420,16 +420,38 @@ static int kf_fusion_handle_ok(dvo_batch* b, const char* who)
     return DVO_OK;
 }
 
+static int kf_max_diff_ok(float max_diff, const char* who)
+{
+    if (!(max_diff > 0.0f && max_diff < __builtin_inff())) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+    return DVO_OK;
+}
+
 int dvo_batch_set_keyframe_fusion(dvo_batch* b, const dvo_kf_fusion_config* cfg)
 {
     static const char who[] = "dvo_batch_set_keyframe_fusion";
     DVO_TRY(kf_fusion_handle_ok(b, who));
     if (cfg) {
         if (cfg->mode != DVO_KF_FUSION_OFF && cfg->mode != DVO_KF_FUSION_ON) { set_error(std::string(who) + ": the mode is DVO_KF_FUSION_OFF or DVO_KF_FUSION_ON"); return DVO_ERR_BAD_ARGUMENT; }
-        if (!(cfg->max_diff > 0.0f && cfg->max_diff < __builtin_inff())) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+        DVO_TRY(kf_max_diff_ok(cfg->max_diff, who));
         if (cfg->max_count < 1 || cfg->max_count > 255) { set_error(std::string(who) + ": max_count must be in [1, 255]"); return DVO_ERR_BAD_ARGUMENT; }
     }
     return b->impl.set_keyframe_fusion(cfg);
+}
+
+// dvo_batch_last_keyframe_fusion / _carry: the stage's records of the last push as the public record type, whose middle counter is `done`
+extern "C++" template <class Rec>
+static int kf_last_records(Batch& B, const Batch::KfStage& st, const char* who, const char* not_ready, Rec* rec, int Rec::*done)
+{
+    if (!st.ready) { set_error(std::string(who) + not_ready); return DVO_ERR_NOT_READY; }
+    DVO_TRY(select_device(B.device));
+    std::vector<KfRecord> host((size_t)B.n_seq);
+    DVO_HIP(hipMemcpyAsync(host.data(), st.rec.p, sizeof(KfRecord) * host.size(), hipMemcpyDeviceToHost, B.stream));
+    DVO_HIP(hipStreamSynchronize(B.stream));
+    for (size_t i = 0; i < host.size(); i++) {
+        rec[i].struct_size = (int)sizeof(Rec);
+        rec[i].n_candidates = host[i].n_candidates; rec[i].*done = host[i].n_done; rec[i].n_gated = host[i].n_gated;
+    }
+    return DVO_OK;
 }
 
 int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec)
@@ -437,17 +459,8 @@ int dvo_batch_last_keyframe_fusion(dvo_batch* b, dvo_kf_fusion_record* rec)
     static const char who[] = "dvo_batch_last_keyframe_fusion";
     if (!rec) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(kf_fusion_handle_ok(b, who));
-    Batch& B = b->impl;
-    if (!B.fuse.ready) { set_error(std::string(who) + ": the last push did not run with keyframe fusion (dvo_batch_set_keyframe_fusion)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(B.device));
-    std::vector<KfFuseRecord> host((size_t)B.n_seq);
-    DVO_HIP(hipMemcpyAsync(host.data(), B.fuse.rec.p, sizeof(KfFuseRecord) * host.size(), hipMemcpyDeviceToHost, B.stream));
-    DVO_HIP(hipStreamSynchronize(B.stream));
-    for (size_t i = 0; i < host.size(); i++) {
-        rec[i].struct_size = (int)sizeof(dvo_kf_fusion_record);
-        rec[i].n_candidates = host[i].n_candidates; rec[i].n_fused = host[i].n_fused; rec[i].n_gated = host[i].n_gated;
-    }
-    return DVO_OK;
+    return kf_last_records(b->impl, b->impl.fuse, who, ": the last push did not run with keyframe fusion (dvo_batch_set_keyframe_fusion)", rec,
+                           &dvo_kf_fusion_record::n_fused);
 }
 
 int dvo_batch_keyframe_fusion_counts(dvo_batch* b, int seq, uint8_t* counts)
@@ -488,7 +501,7 @@ int dvo_batch_set_keyframe_carry(dvo_batch* b, const dvo_kf_carry_config* cfg)
     if (cfg) {
         if (cfg->struct_size != (int)sizeof(dvo_kf_carry_config)) { set_error(std::string(who) + ": struct_size is not sizeof(dvo_kf_carry_config)"); return DVO_ERR_BAD_ARGUMENT; }
         if (cfg->mode != DVO_KF_CARRY_OFF && cfg->mode != DVO_KF_CARRY_ON) { set_error(std::string(who) + ": the mode is DVO_KF_CARRY_OFF or DVO_KF_CARRY_ON"); return DVO_ERR_BAD_ARGUMENT; }
-        if (!(cfg->max_diff > 0.0f && cfg->max_diff < __builtin_inff())) { set_error(std::string(who) + ": max_diff must be finite and > 0"); return DVO_ERR_BAD_ARGUMENT; }
+        DVO_TRY(kf_max_diff_ok(cfg->max_diff, who));
     }
     return b->impl.set_keyframe_carry(cfg);
 }
@@ -498,17 +511,8 @@ int dvo_batch_last_keyframe_carry(dvo_batch* b, dvo_kf_carry_record* rec)
     static const char who[] = "dvo_batch_last_keyframe_carry";
     if (!rec) return DVO_ERR_BAD_ARGUMENT;
     DVO_TRY(kf_carry_handle_ok(b, who));
-    Batch& B = b->impl;
-    if (!B.carry.ready) { set_error(std::string(who) + ": the last push did not run with keyframe carry (dvo_batch_set_keyframe_carry)"); return DVO_ERR_NOT_READY; }
-    DVO_TRY(select_device(B.device));
-    std::vector<KfCarryRecord> host((size_t)B.n_seq);
-    DVO_HIP(hipMemcpyAsync(host.data(), B.carry.rec.p, sizeof(KfCarryRecord) * host.size(), hipMemcpyDeviceToHost, B.stream));
-    DVO_HIP(hipStreamSynchronize(B.stream));
-    for (size_t i = 0; i < host.size(); i++) {
-        rec[i].struct_size = (int)sizeof(dvo_kf_carry_record);
-        rec[i].n_candidates = host[i].n_candidates; rec[i].n_carried = host[i].n_carried; rec[i].n_gated = host[i].n_gated;
-    }
-    return DVO_OK;
+    return kf_last_records(b->impl, b->impl.carry, who, ": the last push did not run with keyframe carry (dvo_batch_set_keyframe_carry)", rec,
+                           &dvo_kf_carry_record::n_carried);
 }
 
 int dvo_batch_set_pose_guess(dvo_batch* b, const float* xi, int xi_on_device)

@@ -2562,18 +2562,43 @@ int Batch::update_keyframes(int frame_set)
     return DVO_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ batch: keyframe depth fusion
+// ------------------------------------------------------------------------------------------------ batch: keyframe depth fusion and carry
+int Batch::KfStage::alloc(DevBuf& plane, size_t n_seq, size_t npix)
+{
+    if (plane.p) return DVO_OK;
+    DVO_TRY(plane.alloc(n_seq * npix));
+    DVO_TRY(table.alloc(sizeof(KfSeq) * n_seq));
+    DVO_TRY(rec.alloc(sizeof(KfRecord) * n_seq));
+    return DVO_OK;
+}
+
+KfPrepArgs Batch::kf_prep_args(const KfStage& st) const
+{
+    KfPrepArgs pa{};
+    pa.meta = kf_meta.as<MonoSeq>(); pa.eff = plan.eff.as<uint8_t>(); pa.is_key = is_key.as<int>();
+    pa.table = st.table.as<KfSeq>(); pa.rec = st.rec.as<KfRecord>(); pa.n_seq = n_seq;
+    return pa;
+}
+
+template <class Args>
+void Batch::kf_pixel_args(Args& a, const KfStage& st, float max_diff) const
+{
+    const int T = g.top();
+    for (int l = 0; l < g.levels; l++) { a.w[l] = g.w[l]; a.h[l] = g.h[l]; }
+    a.table = st.table.as<KfSeq>(); a.rec = st.rec.as<KfRecord>();
+    a.seq_k = cam_table() ? cam_table() + (size_t)T * n_seq : nullptr;
+    a.k = g.k[T];
+    a.levels = g.levels; a.n_seq = n_seq;
+    a.min_depth = cfg.min_depth; a.max_diff = max_diff; a.max_count = fuse.cfg.max_count;
+}
+
 int Batch::set_keyframe_fusion(const dvo_kf_fusion_config* c)
 {
     const bool enable = c && c->mode == DVO_KF_FUSION_ON;
     if (enable && !fuse.on) {   // off -> on: the counts (re)start at 0
         DVO_TRY(select_device(device));
         const size_t n = (size_t)n_seq, npix = (size_t)g.w[g.top()] * g.h[g.top()];
-        if (!fuse.counts.p) {
-            DVO_TRY(fuse.counts.alloc(n * npix));
-            DVO_TRY(fuse.table.alloc(sizeof(KfFuseSeq) * n));
-            DVO_TRY(fuse.rec.alloc(sizeof(KfFuseRecord) * n));
-        }
+        DVO_TRY(fuse.alloc(fuse.counts, n, npix));
         DVO_HIP(hipMemsetAsync(fuse.counts.p, 0, n * npix, stream));
     }
     if (enable) fuse.cfg = *c;
@@ -2590,35 +2615,24 @@ int Batch::fuse_keyframes(int frame_set, int kf)
     fuse.ready = fuse.on;
     if (!fuse.on) return DVO_OK;
     fuse.ran = true;
-    KfFusePrepArgs pa{};
-    pa.meta = kf_meta.as<MonoSeq>(); pa.eff = plan.eff.as<uint8_t>(); pa.is_key = is_key.as<int>();
-    pa.table = fuse.table.as<KfFuseSeq>(); pa.rec = fuse.rec.as<KfFuseRecord>(); pa.n_seq = n_seq;
-    launch_kf_fuse_prep(pa, stream);
+    launch_kf_fuse_prep(kf_prep_args(fuse), stream);
     KfFuseArgs a{};
-    const int T = g.top();
-    for (int l = 0; l < g.levels; l++) { a.kf_depth[l] = fs[kf].depth[l]; a.w[l] = g.w[l]; a.h[l] = g.h[l]; }
-    a.frame_depth = fs[frame_set].depth[T];
-    a.counts = fuse.counts.as<uint8_t>(); a.table = fuse.table.as<KfFuseSeq>(); a.rec = fuse.rec.as<KfFuseRecord>();
-    a.seq_k = cam_table() ? cam_table() + (size_t)T * n_seq : nullptr;
-    a.k = g.k[T];
-    a.levels = g.levels; a.n_seq = n_seq;
-    a.min_depth = cfg.min_depth; a.max_diff = fuse.cfg.max_diff; a.max_count = fuse.cfg.max_count;
+    kf_pixel_args(a, fuse, fuse.cfg.max_diff);
+    for (int l = 0; l < g.levels; l++) a.kf_depth[l] = fs[kf].depth[l];
+    a.frame_depth = fs[frame_set].depth[g.top()];
+    a.counts = fuse.counts.as<uint8_t>();
     launch_kf_fuse(a, stream);
     return DVO_OK;
 }
 
-// ------------------------------------------------------------------------------------------------ batch: keyframe carry
 int Batch::set_keyframe_carry(const dvo_kf_carry_config* c)
 {
     const bool enable = c && c->mode == DVO_KF_CARRY_ON;
-    if (enable && !carry.staged.p) {
+    if (enable) {
         DVO_TRY(select_device(device));
-        const size_t n = (size_t)n_seq, npix = (size_t)g.w[g.top()] * g.h[g.top()];
-        DVO_TRY(carry.staged.alloc(n * npix));
-        DVO_TRY(carry.table.alloc(sizeof(KfCarrySeq) * n));
-        DVO_TRY(carry.rec.alloc(sizeof(KfCarryRecord) * n));
+        DVO_TRY(carry.alloc(carry.staged, (size_t)n_seq, (size_t)g.w[g.top()] * g.h[g.top()]));
+        carry.cfg = *c;
     }
-    if (enable) carry.cfg = *c;
     carry.on = enable;
     return DVO_OK;
 }
@@ -2630,21 +2644,13 @@ bool Batch::carry_keyframes(int frame_set, int kf)
 {
     carry.ready = carry.on;
     if (!carry.on) return false;
-    KfCarryPrepArgs pa{};
-    pa.meta = kf_meta.as<MonoSeq>(); pa.eff = plan.eff.as<uint8_t>(); pa.is_key = is_key.as<int>();
-    pa.table = carry.table.as<KfCarrySeq>(); pa.rec = carry.rec.as<KfCarryRecord>(); pa.n_seq = n_seq;
-    launch_kf_carry_prep(pa, stream);
+    launch_kf_carry_prep(kf_prep_args(carry), stream);
     if (frame_set == kf) return false;
     KfCarryArgs a{};
-    const int T = g.top();
-    for (int l = 0; l < g.levels; l++) { a.frame_depth[l] = fs[frame_set].depth[l]; a.w[l] = g.w[l]; a.h[l] = g.h[l]; }
-    a.kf_depth = fs[kf].depth[T];
+    kf_pixel_args(a, carry, carry.cfg.max_diff);
+    for (int l = 0; l < g.levels; l++) a.frame_depth[l] = fs[frame_set].depth[l];
+    a.kf_depth = fs[kf].depth[g.top()];
     a.counts = fuse.counts.as<uint8_t>(); a.staged = carry.staged.as<uint8_t>();
-    a.table = carry.table.as<KfCarrySeq>(); a.rec = carry.rec.as<KfCarryRecord>();
-    a.seq_k = cam_table() ? cam_table() + (size_t)T * n_seq : nullptr;
-    a.k = g.k[T];
-    a.levels = g.levels; a.n_seq = n_seq;
-    a.min_depth = cfg.min_depth; a.max_diff = carry.cfg.max_diff; a.max_count = fuse.cfg.max_count;
     launch_kf_carry(a, stream);
     return true;
 }
@@ -2652,7 +2658,7 @@ bool Batch::carry_keyframes(int frame_set, int kf)
 void Batch::commit_carry()
 {
     KfCarryCommitArgs a{};
-    a.staged = carry.staged.as<uint8_t>(); a.counts = fuse.counts.as<uint8_t>(); a.table = carry.table.as<KfCarrySeq>();
+    a.staged = carry.staged.as<uint8_t>(); a.counts = fuse.counts.as<uint8_t>(); a.table = carry.table.as<KfSeq>();
     a.npix = g.w[g.top()] * g.h[g.top()]; a.n_seq = n_seq;
     launch_kf_carry_commit(a, stream);
 }

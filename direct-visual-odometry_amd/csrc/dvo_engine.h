@@ -775,30 +775,36 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     DevBuf kf_meta, xi_world, T_world, is_key, need_list;   // MonoSeq [n_seq]; [n_seq][6], [n_seq][16], [n_seq]; [4 + n_seq]
     int set_keyframe_tracking(int enable);
     int update_keyframes(int frame_set);                     // k_kf_decide, then k_promote from fs[frame_set] into fs[cur]
+    // What keyframe fusion and keyframe carry both keep: the switch, the table their prep kernel fills and the records of the last push.
+    struct KfStage {
+        bool on = false;
+        bool ready = false;      // the last push ran with it on (dvo_batch_last_keyframe_fusion / _carry)
+        DevBuf table, rec;       // KfSeq [n_seq]; KfRecord [n_seq]
+        int alloc(DevBuf& plane, size_t n_seq, size_t npix);   // the stage's uint8 [n_seq][npix] plane, its table and records: once
+    };
     // Keyframe depth fusion (dvo_batch_set_keyframe_fusion): after the promotions of a push, k_kf_fuse_prep and k_kf_fuse
     // fold the tracked frame's top-level depth into the keyframes of the sequences that tracked without firing the rule, and clear the
     // counts of those that started or promoted.  Off (the default): update_keyframes launches what it always launched.
-    struct KfFusion {
-        bool on = false;
-        bool ready = false;      // the last push ran with fusion on (dvo_batch_last_keyframe_fusion)
+    struct KfFusion : KfStage {
         bool ran = false;        // some push ran with fusion on (dvo_batch_keyframe_fusion_counts)
         dvo_kf_fusion_config cfg = {DVO_KF_FUSION_OFF, 0.05f, 16};
-        DevBuf counts, table, rec;   // uint8 [n_seq][h_top][w_top]; KfFuseSeq [n_seq]; KfFuseRecord [n_seq]
+        DevBuf counts;           // uint8 [n_seq][h_top][w_top]
     } fuse;
     int set_keyframe_fusion(const dvo_kf_fusion_config* c);  // (validated by the caller)
     int fuse_keyframes(int frame_set, int kf);
     // Keyframe carry (dvo_batch_set_keyframe_carry): on a promotion k_kf_carry blends the old keyframe's fused depth,
     // warped into the tracked frame, into the tracked set's depth pyramid before k_promote copies it, and the counts follow through a
     // staging plane (k_kf_carry_commit, after k_kf_fuse has cleared).  Needs fusion; off (the default): no launch is added.
-    struct KfCarry {
-        bool on = false;
-        bool ready = false;      // the last push ran with carry on (dvo_batch_last_keyframe_carry)
+    struct KfCarry : KfStage {
         dvo_kf_carry_config cfg = {(int)sizeof(dvo_kf_carry_config), DVO_KF_CARRY_OFF, 0.05f};
-        DevBuf staged, table, rec;   // uint8 [n_seq][h_top][w_top]; KfCarrySeq [n_seq]; KfCarryRecord [n_seq]
+        DevBuf staged;           // uint8 [n_seq][h_top][w_top]
     } carry;
     int set_keyframe_carry(const dvo_kf_carry_config* c);    // (validated by the caller)
     bool carry_keyframes(int frame_set, int kf);             // carry prep + carry; true when the commit has to follow the fusion
     void commit_carry();
+    KfPrepArgs kf_prep_args(const KfStage& st) const;
+    // what KfFuseArgs and KfCarryArgs share: geometry, intrinsics, thresholds, the stage's table and records (max_diff is the stage's own)
+    template <class Args> void kf_pixel_args(Args& a, const KfStage& st, float max_diff) const;
     PointsExport points;                                     // dvo_batch_export_points (keyframe tracking)
     PointsExport::Source points_source(int level) const;
 };

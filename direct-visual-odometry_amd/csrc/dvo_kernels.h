@@ -488,6 +488,55 @@ __device__ __forceinline__ int mono_decide_one(MonoSeq& m, const float rel[6], i
     return need;
 }
 
+// The building blocks of the per-sequence bookkeeping kernels (k_mono_decide / k_mono_commit, their _plan forms and k_kf_decide), one
+// thread per sequence s.  xi_world [n_seq][6], T_world [n_seq][16] and is_key [n_seq] are the call's outputs; one a caller does not
+// want is null.
+__device__ __forceinline__ void mono_identity_world(int s, float* xi_world, float* T_world)
+{
+    if (xi_world) for (int i = 0; i < 6; i++) xi_world[s * 6 + i] = 0.0f;
+    if (T_world) for (int i = 0; i < 16; i++) T_world[s * 16 + i] = (i % 5 == 0) ? 1.0f : 0.0f;
+}
+
+// Start: the frame is frame `frame_id` and the first keyframe of the sequence, at the identity; `ring` = the sequence's [R][6] keyframe
+// twists (slot 0 is written) or null.  MonoSeq::clamped is the caller's: a restart clears it, the first frame of a batch finds it 0.
+__device__ __forceinline__ void mono_start_one(MonoSeq& m, int frame_id, float* ring, int s, float* xi_world, float* T_world, int* is_key)
+{
+    for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
+    for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
+    for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
+    for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    m.ref_id = frame_id; m.frame_id = frame_id; m.n_total = 1; m.need = 1; m.valid_updates = 0;
+    if (ring) for (int i = 0; i < 6; i++) ring[i] = 0.0f;
+    mono_identity_world(s, xi_world, T_world);
+    if (is_key) is_key[s] = 1;
+}
+
+// Track: mono_decide_one on the tracker's twist, the frame's world pose and keyframe flag published.  Returns the flag.
+__device__ __forceinline__ int mono_track_one(MonoSeq& m, const SeqState& st, int frame_id, float min_translation, int max_frames, int s,
+                                              float* xi_world, float* T_world, int* is_key)
+{
+    float rel[6], fx[6], T[16];
+    for (int i = 0; i < 6; i++) rel[i] = st.xi[i];
+    const int need = mono_decide_one(m, rel, frame_id, min_translation, max_frames, fx, T);
+    if (xi_world) for (int i = 0; i < 6; i++) xi_world[s * 6 + i] = fx[i];
+    if (T_world) for (int i = 0; i < 16; i++) T_world[s * 16 + i] = T[i];
+    if (is_key) is_key[s] = need;
+    return need;
+}
+
+// FrameHistory::setRefFrame / push (frame.hpp:151-157): the frame becomes the reference keyframe and, with a ring (as mono_start_one's),
+// its twist enters slot n_total % R.
+__device__ __forceinline__ void mono_frame_to_ref(MonoSeq& m, float* ring, int R)
+{
+    const int slot = ring ? m.n_total % R : 0;
+    for (int i = 0; i < 6; i++) {
+        m.ref_xi[i] = m.frame_xi[i];
+        if (ring) ring[slot * 6 + i] = m.frame_xi[i];
+    }
+    m.ref_id = m.frame_id;
+    m.n_total += 1;
+}
+
 struct AgeEntry {      // one keyframe as seen from the current frame (Mapper::update, mapper.cpp:99-107)
     Pose  pose;        // exp(-r_xi), r_xi = concatenate(obj.xi, -born.xi)
     float tneg[3];     // -r_xi[0:3] (twist part; implement.cpp:56)
@@ -629,33 +678,37 @@ void launch_mono_commit_plan(const MonoPlanArgs& a, hipStream_t s);
 // (started, need_save, hist_xi and R are not used: a sequence has started once MonoSeq::n_total > 0)
 void launch_kf_decide(const MonoPlanArgs& a, hipStream_t s);
 
-// ---- keyframe depth fusion of a sensor-depth batch (dvo_batch_set_keyframe_fusion) --------------------------------
-// k_kf_fuse_prep (one thread per sequence, after k_kf_decide) turns what k_kf_decide left -- eff, is_key, MonoSeq::rel_xi / rel_pose --
-// into one table entry per sequence and zeroes its record; k_kf_fuse reads the entry with a scalar load and clears, fuses or leaves.
+// ---- keyframe depth fusion and keyframe carry of a sensor-depth batch ----------------------------------
+// Both have a prep kernel (one thread per sequence, after k_kf_decide) that turns what k_kf_decide left -- eff, is_key, MonoSeq::rel_xi /
+// rel_pose -- into one table entry per sequence, in a table of its own, and zeroes the sequence's record; the pixel kernels read the
+// entry with a scalar load.
 #define DVO_KF_FUSE_NONE  0   /* SKIP / BAD_ACTION, or a non-finite twist: nothing of the sequence is read or written */
 #define DVO_KF_FUSE_CLEAR 1   /* a start or a promotion: the count plane becomes 0 */
-#define DVO_KF_FUSE_FUSE  2
-struct KfFuseSeq {
-    Pose F;     // float(exp(+xi)): MonoSeq::rel_pose, the T_rel of the push
-    Pose Bk;    // float(exp(-xi)): pose_from_xi(xi, -1), what the tracker's kernels transform with
-    int mode;
+#define DVO_KF_FUSE_FUSE  2   /* TRACK, rule not fired, finite twist */
+#define DVO_KF_CARRY_NONE  0
+#define DVO_KF_CARRY_CARRY 1  /* TRACK, rule fired, finite twist */
+struct KfSeq {
+    Pose F;     // float(exp(+xi)): MonoSeq::rel_pose, the T_rel of the push: keyframe -> tracked frame
+    Pose Bk;    // float(exp(-xi)): pose_from_xi(xi, -1), what the tracker's kernels transform with: tracked frame -> keyframe
+    int mode;   // DVO_KF_FUSE_* in the fusion's table, DVO_KF_CARRY_* in the carry's
     int pad[3];
 };
-struct KfFuseRecord { int n_candidates, n_fused, n_gated, pad; };
-struct KfFusePrepArgs {
+struct KfRecord { int n_candidates, n_done, n_gated, pad; };   // n_done: dvo_kf_fusion_record::n_fused, dvo_kf_carry_record::n_carried
+struct KfPrepArgs {
     const MonoSeq* meta;
     const uint8_t* eff;      // [n_seq] effective action of the push (k_plan)
     const int* is_key;       // [n_seq] k_kf_decide's keyframe flag
-    KfFuseSeq* table;        // [n_seq]
-    KfFuseRecord* rec;       // [n_seq]
+    KfSeq* table;            // [n_seq]
+    KfRecord* rec;           // [n_seq]
     int n_seq;
 };
+// k_kf_fuse (dvo_batch_set_keyframe_fusion) clears, fuses or leaves.
 struct KfFuseArgs {
     float* kf_depth[DVO_MAX_LEVELS];   // the keyframe set's depth pyramid, [n_seq][h_l][w_l], updated in place
     const float* frame_depth;          // the tracked set's top-level depth [n_seq][h][w] (never the keyframe set when a sequence fuses)
     uint8_t* counts;                   // [n_seq][h][w]
-    const KfFuseSeq* table;
-    KfFuseRecord* rec;
+    const KfSeq* table;
+    KfRecord* rec;
     const Intr* seq_k = nullptr;       // per-sequence top-level intrinsics [n_seq] (k_kf_fuse_cam), else k
     Intr k;
     int w[DVO_MAX_LEVELS], h[DVO_MAX_LEVELS], levels, n_seq;
@@ -663,37 +716,18 @@ struct KfFuseArgs {
     float min_depth, max_diff;
     int max_count;
 };
-void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s);
+void launch_kf_fuse_prep(const KfPrepArgs& a, hipStream_t s);
 void launch_kf_fuse(const KfFuseArgs& a, hipStream_t s);
-// ---- keyframe carry of a sensor-depth batch (dvo_batch_set_keyframe_carry) ----------------------------------------
-// k_kf_carry_prep (one thread per sequence, after k_kf_decide) resolves every sequence to carry (TRACK, rule fired, finite twist) or
-// nothing into a table of its own and zeroes its record; k_kf_carry (before k_promote) blends the old keyframe's depth, warped into
-// the tracked frame, into the tracked set's depth pyramid in place and stages the new counts; k_kf_carry_commit (after k_kf_fuse has
-// cleared) copies the staged counts of the carrying sequences over the count plane.
-#define DVO_KF_CARRY_NONE  0
-#define DVO_KF_CARRY_CARRY 1
-struct KfCarrySeq {
-    Pose F;     // float(exp(+xi)): MonoSeq::rel_pose, old keyframe -> tracked frame
-    Pose Bk;    // float(exp(-xi)): pose_from_xi(xi, -1), tracked frame -> old keyframe
-    int mode;
-    int pad[3];
-};
-struct KfCarryRecord { int n_candidates, n_carried, n_gated, pad; };
-struct KfCarryPrepArgs {
-    const MonoSeq* meta;
-    const uint8_t* eff;      // [n_seq] effective action of the push (k_plan)
-    const int* is_key;       // [n_seq] k_kf_decide's keyframe flag
-    KfCarrySeq* table;       // [n_seq]
-    KfCarryRecord* rec;      // [n_seq]
-    int n_seq;
-};
+// k_kf_carry (dvo_batch_set_keyframe_carry; before k_promote) blends the old keyframe's depth, warped into the tracked frame, into the
+// tracked set's depth pyramid in place and stages the new counts; k_kf_carry_commit (after k_kf_fuse has cleared) copies the staged
+// counts of the carrying sequences over the count plane.
 struct KfCarryArgs {
     float* frame_depth[DVO_MAX_LEVELS];   // the tracked set's depth pyramid, [n_seq][h_l][w_l], updated in place
     const float* kf_depth;                // the old keyframe's top-level depth [n_seq][h][w] (never the tracked set when a sequence carries)
     const uint8_t* counts;                // the old keyframe's counts [n_seq][h][w]
     uint8_t* staged;                      // the new counts [n_seq][h][w]
-    const KfCarrySeq* table;
-    KfCarryRecord* rec;
+    const KfSeq* table;
+    KfRecord* rec;
     const Intr* seq_k = nullptr;          // per-sequence top-level intrinsics [n_seq] (k_kf_carry_cam), else k
     Intr k;
     int w[DVO_MAX_LEVELS], h[DVO_MAX_LEVELS], levels, n_seq;
@@ -704,10 +738,10 @@ struct KfCarryArgs {
 struct KfCarryCommitArgs {
     const uint8_t* staged;
     uint8_t* counts;
-    const KfCarrySeq* table;
+    const KfSeq* table;
     int npix, n_seq;
 };
-void launch_kf_carry_prep(const KfCarryPrepArgs& a, hipStream_t s);
+void launch_kf_carry_prep(const KfPrepArgs& a, hipStream_t s);
 void launch_kf_carry(const KfCarryArgs& a, hipStream_t s);
 void launch_kf_carry_commit(const KfCarryCommitArgs& a, hipStream_t s);
 // ---- keyframe maps as compacted world-frame point clouds (dvo_batch_export_points) ---------------------------------

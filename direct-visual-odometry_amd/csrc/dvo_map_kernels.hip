@@ -57,70 +57,43 @@ __global__ void __launch_bounds__(64) k_mono_decide(MonoSeq* meta, const SeqStat
         for (int i = 0; i < 6; i++) m.ref_xi[i] = host_ref.ref_xi[i];
         m.ref_id = host_ref.ref_id; m.n_total = host_ref.n_total;
     }
-    float rel[6], fx[6], T[16];
-    for (int i = 0; i < 6; i++) rel[i] = state[s].xi[i];
-    const int need = mono_decide_one(m, rel, frame_id, min_translation, max_frames, fx, T);
+    const int need = mono_track_one(m, state[s], frame_id, min_translation, max_frames, s, xi_world, T_world, is_key);
     if (need && need_list) need_list[4 + atomicAdd(&need_list[0], 1)] = s;   // (the order of the list changes no result: sequences are independent)
-    if (xi_world) for (int i = 0; i < 6; i++) xi_world[s * 6 + i] = fx[i];
-    if (T_world) for (int i = 0; i < 16; i++) T_world[s * 16 + i] = T[i];
-    if (is_key) is_key[s] = need;
 }
 
 // k_mono_commit: FrameHistory::setRefFrame / push (frame.hpp:151-157) for the sequences that created a keyframe: the frame's
-// pose becomes the reference pose and enters the ring.  all = 1: first frame (identity pose, every sequence).
+// pose becomes the reference pose and enters the ring.  all = 1: first frame (identity pose, every sequence; the frame id is the
+// caller's and MonoSeq::clamped is left as it is).
 __global__ void __launch_bounds__(64) k_mono_commit(MonoSeq* meta, float* hist_xi, int n_seq, int R, int all, int frame_id, float* xi_world,
                                                     float* T_world, int* is_key)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n_seq) return;
     MonoSeq& m = meta[s];
-    if (all) {
-        for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
-        for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
-        for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
-        for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        m.ref_id = frame_id; m.frame_id = frame_id; m.n_total = 1; m.need = 1; m.valid_updates = 0;
-        for (int i = 0; i < 6; i++) hist_xi[((size_t)s * R) * 6 + i] = 0.0f;
-        if (xi_world) for (int i = 0; i < 6; i++) xi_world[s * 6 + i] = 0.0f;
-        if (T_world) for (int i = 0; i < 16; i++) T_world[s * 16 + i] = m.T_world[i];
-        if (is_key) is_key[s] = 1;
-        return;
-    }
-    if (!m.need) return;
-    const int slot = m.n_total % R;
-    for (int i = 0; i < 6; i++) { m.ref_xi[i] = m.frame_xi[i]; hist_xi[((size_t)s * R + slot) * 6 + i] = m.frame_xi[i]; }
-    m.ref_id = m.frame_id;
-    m.n_total += 1;
+    float* ring = hist_xi + (size_t)s * R * 6;
+    if (all) mono_start_one(m, frame_id, ring, s, xi_world, T_world, is_key);
+    else if (m.need) mono_frame_to_ref(m, ring, R);
 }
 
 // k_mono_decide_plan / k_mono_commit_plan: k_mono_decide and k_mono_commit of a planned mono call (dvo_batch_set_mono_actions).
 // A TRACK sequence does exactly what they do, with its own next frame id (frame ids count from each start).  A sequence that does
 // not track parks its need flag in need_save and raises it, so that k_age_table and k_depth_update leave it alone (and it is never in
 // need_list: k_propagate_* and k_promote do not see it); k_mono_commit_plan puts the flag back.  SKIP keeps its world pose (identity
-// while it has never started) with is_keyframe = 0; RESTART becomes frame 0 of its sequence, as k_mono_commit's first-frame branch.
+// while it has never started) with is_keyframe = 0; RESTART becomes frame 0 of its sequence, its counters reset.
 __global__ void __launch_bounds__(64) k_mono_decide_plan(MonoPlanArgs a)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_seq) return;
     MonoSeq& m = a.meta[s];
     if (a.eff[s] == DVO_SEQ_TRACK) {
-        float rel[6], fx[6], T[16];
-        for (int i = 0; i < 6; i++) rel[i] = a.state[s].xi[i];
-        const int fid = m.frame_id + 1;
-        const int need = mono_decide_one(m, rel, fid, a.min_translation, a.max_frames, fx, T);
+        const int need = mono_track_one(m, a.state[s], m.frame_id + 1, a.min_translation, a.max_frames, s, a.xi_world, a.T_world, a.is_key);
         if (need) a.need_list[4 + atomicAdd(&a.need_list[0], 1)] = s;
-        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = fx[i];
-        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = T[i];
-        a.is_key[s] = need;
         return;
     }
     a.need_save[s] = m.need;
     m.need = 1;
     a.is_key[s] = 0;
-    if (!a.started[s]) {
-        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
-        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = (i % 5 == 0) ? 1.0f : 0.0f;
-    }
+    if (!a.started[s]) mono_identity_world(s, a.xi_world, a.T_world);
 }
 
 __global__ void __launch_bounds__(64) k_mono_commit_plan(MonoPlanArgs a)
@@ -129,33 +102,24 @@ __global__ void __launch_bounds__(64) k_mono_commit_plan(MonoPlanArgs a)
     if (s >= a.n_seq) return;
     MonoSeq& m = a.meta[s];
     const int eff = a.eff[s];
-    if (eff == DVO_SEQ_RESTART) {   // k_mono_commit's first-frame branch, frame id 0 of the sequence, its counters reset
-        for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
-        for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
-        for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
-        for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        m.ref_id = 0; m.frame_id = 0; m.n_total = 1; m.need = 1; m.valid_updates = 0; m.clamped = 0;
-        for (int i = 0; i < 6; i++) a.hist_xi[((size_t)s * a.R) * 6 + i] = 0.0f;
-        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
-        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = m.T_world[i];
-        a.is_key[s] = 1;
+    float* ring = a.hist_xi + (size_t)s * a.R * 6;
+    if (eff == DVO_SEQ_RESTART) {
+        mono_start_one(m, 0, ring, s, a.xi_world, a.T_world, a.is_key);
+        m.clamped = 0;
         a.started[s] = 1;
-        return;
+    } else if (eff != DVO_SEQ_TRACK) {
+        m.need = a.need_save[s];
+    } else if (m.need) {
+        mono_frame_to_ref(m, ring, a.R);
     }
-    if (eff != DVO_SEQ_TRACK) { m.need = a.need_save[s]; return; }
-    if (!m.need) return;   // k_mono_commit's keyframe branch
-    const int slot = m.n_total % a.R;
-    for (int i = 0; i < 6; i++) { m.ref_xi[i] = m.frame_xi[i]; a.hist_xi[((size_t)s * a.R + slot) * 6 + i] = m.frame_xi[i]; }
-    m.ref_id = m.frame_id;
-    m.n_total += 1;
 }
 
 // k_kf_decide: the keyframe bookkeeping of a sensor-depth batch with keyframe tracking (dvo_batch_set_keyframe_tracking, DESIGN.md
-// §19), after the push's tracking.  TRACK is k_mono_decide_plan's TRACK branch (mono_decide_one with the sequence's next frame id)
-// followed, when the rule fires, by k_mono_commit_plan's keyframe branch; RESTART is k_mono_commit_plan's start branch.  Both enter
-// need_list, whose frames k_promote then copies over the keyframe set.  SKIP changes nothing: its world pose stays (identity while the
-// sequence has never started, n_total = 0), is_keyframe = 0.  There is no ring and nothing between this kernel and the copy reads
-// MonoSeq, so decide and commit are one launch (no need_save, no started array).
+// §19), after the push's tracking.  TRACK tracks with the sequence's next frame id and, when the rule fires, makes the frame the
+// reference at once; RESTART starts the sequence as frame 0, its counters reset.  Both enter need_list, whose frames k_promote then
+// copies over the keyframe set.  SKIP changes nothing: its world pose stays (identity while the sequence has never started,
+// n_total = 0), is_keyframe = 0.  There is no ring and nothing between this kernel and the copy reads MonoSeq, so decide and commit
+// are one launch (no need_save, no started array).
 __global__ void __launch_bounds__(64) k_kf_decide(MonoPlanArgs a)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
@@ -163,32 +127,14 @@ __global__ void __launch_bounds__(64) k_kf_decide(MonoPlanArgs a)
     MonoSeq& m = a.meta[s];
     const int eff = a.eff[s];
     if (eff == DVO_SEQ_TRACK) {
-        float rel[6], fx[6], T[16];
-        for (int i = 0; i < 6; i++) rel[i] = a.state[s].xi[i];
-        const int fid = m.frame_id + 1;
-        const int need = mono_decide_one(m, rel, fid, a.min_translation, a.max_frames, fx, T);
-        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = fx[i];
-        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = T[i];
-        a.is_key[s] = need;
-        if (!need) return;
-        for (int i = 0; i < 6; i++) m.ref_xi[i] = m.frame_xi[i];   // k_mono_commit_plan's keyframe branch
-        m.ref_id = m.frame_id;
-        m.n_total += 1;
-    } else if (eff == DVO_SEQ_RESTART) {   // k_mono_commit_plan's start branch: frame 0 of the sequence, its counters reset
-        for (int i = 0; i < 6; i++) { m.ref_xi[i] = 0.0f; m.frame_xi[i] = 0.0f; m.rel_xi[i] = 0.0f; }
-        for (int i = 0; i < 9; i++) m.rel_pose.R[i] = (i % 4 == 0) ? 1.0f : 0.0f;
-        for (int i = 0; i < 3; i++) m.rel_pose.t[i] = 0.0f;
-        for (int i = 0; i < 16; i++) m.T_world[i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        m.ref_id = 0; m.frame_id = 0; m.n_total = 1; m.need = 1; m.valid_updates = 0; m.clamped = 0;
-        for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
-        for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = m.T_world[i];
-        a.is_key[s] = 1;
+        if (!mono_track_one(m, a.state[s], m.frame_id + 1, a.min_translation, a.max_frames, s, a.xi_world, a.T_world, a.is_key)) return;
+        mono_frame_to_ref(m, nullptr, 1);
+    } else if (eff == DVO_SEQ_RESTART) {
+        mono_start_one(m, 0, nullptr, s, a.xi_world, a.T_world, a.is_key);
+        m.clamped = 0;
     } else {
         a.is_key[s] = 0;
-        if (m.n_total == 0) {
-            for (int i = 0; i < 6; i++) a.xi_world[s * 6 + i] = 0.0f;
-            for (int i = 0; i < 16; i++) a.T_world[s * 16 + i] = (i % 5 == 0) ? 1.0f : 0.0f;
-        }
+        if (m.n_total == 0) mono_identity_world(s, a.xi_world, a.T_world);
         return;
     }
     a.need_list[4 + atomicAdd(&a.need_list[0], 1)] = s;   // (the order of the list changes no result: sequences are independent)
@@ -868,299 +814,284 @@ __global__ void __launch_bounds__(256) k_broadcast(const float* __restrict__ src
 }
 
 // ------------------------------------------------------------------------------------------------
-// Keyframe depth fusion of a sensor-depth batch (dvo_batch_set_keyframe_fusion; the contract is in include/dvo.h).
-// k_kf_fuse_prep: what k_kf_decide left of the push, as one table entry per sequence -- clear (a start or a promotion), fuse (TRACK,
-// rule not fired, finite twist: F = MonoSeq::rel_pose = float(exp(+xi)), Bk = float(exp(-xi)) through the same double-precision chain)
-// or nothing -- and the sequence's record zeroed.  k_kf_decide itself is not touched.
+// Keyframe depth fusion and keyframe carry of a sensor-depth batch (dvo_batch_set_keyframe_fusion, dvo_batch_set_keyframe_carry; the
+// contracts are in include/dvo.h).  Both work on a lane's own four pixels of one map in place and gather
+// from the other map through the push's relative pose; what they share is below, what each keeps for itself is at its kernel.
+// Prep (one thread per sequence): what k_kf_decide left of the push as one table entry -- F = MonoSeq::rel_pose = float(exp(+xi)),
+// Bk = float(exp(-xi)) through the same double-precision chain, for a TRACK sequence with a finite twist that the kernel works on --
+// and the sequence's record zeroed.  k_kf_decide itself is not touched.
+//   k_kf_fuse_prep:  clear (a start or a promotion), fuse (TRACK, rule not fired) or nothing.
+//   k_kf_carry_prep: carry (TRACK, rule fired) or nothing.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_kf_fuse_prep(KfFusePrepArgs a)
+template <bool CARRY>
+__device__ __forceinline__ void kf_prep(KfPrepArgs a)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= a.n_seq) return;
     const MonoSeq& m = a.meta[s];
     const int eff = a.eff[s];
-    KfFuseSeq e;
+    const bool track = eff == DVO_SEQ_TRACK;
+    KfSeq e;
     for (int i = 0; i < 9; i++) { e.F.R[i] = 0.0f; e.Bk.R[i] = 0.0f; }
     for (int i = 0; i < 3; i++) { e.F.t[i] = 0.0f; e.Bk.t[i] = 0.0f; e.pad[i] = 0; }
-    e.mode = DVO_KF_FUSE_NONE;
-    if (eff == DVO_SEQ_RESTART || (eff == DVO_SEQ_TRACK && a.is_key[s])) {
+    e.mode = CARRY ? DVO_KF_CARRY_NONE : DVO_KF_FUSE_NONE;
+    if (!CARRY && (eff == DVO_SEQ_RESTART || (track && a.is_key[s]))) {
         e.mode = DVO_KF_FUSE_CLEAR;
-    } else if (eff == DVO_SEQ_TRACK) {
+    } else if (track && (!CARRY || a.is_key[s])) {
         float xi[6];
         bool finite = true;
         for (int i = 0; i < 6; i++) { xi[i] = m.rel_xi[i]; finite = finite && isfinite(xi[i]); }
         if (finite) {
-            e.mode = DVO_KF_FUSE_FUSE;
+            e.mode = CARRY ? DVO_KF_CARRY_CARRY : DVO_KF_FUSE_FUSE;
             e.F = m.rel_pose;
             pose_from_xi(xi, -1.0f, e.Bk);
         }
     }
     a.table[s] = e;
-    KfFuseRecord z;
-    z.n_candidates = 0; z.n_fused = 0; z.n_gated = 0; z.pad = 0;
+    KfRecord z;
+    z.n_candidates = 0; z.n_done = 0; z.n_gated = 0; z.pad = 0;
     a.rec[s] = z;
 }
 
-// k_kf_fuse: four consecutive top-level pixels per lane, the plane addressed linearly (a sequence's plane starts on a 4-byte boundary
-// only: the 16-byte and 4-byte accesses are declared unaligned); the last lane of a plane whose size is no multiple of 4 goes pixel by
-// pixel.  A pixel reads and writes its own keyframe depth and count and gathers four taps from the tracked frame's map, which nobody
-// writes: in place, no float atomics, no LDS.  The three counters are summed per wave (one packed butterfly) and added with integer
-// atomics: order-free.
+__global__ void __launch_bounds__(64) k_kf_fuse_prep(KfPrepArgs a) { kf_prep<false>(a); }
+__global__ void __launch_bounds__(64) k_kf_carry_prep(KfPrepArgs a) { kf_prep<true>(a); }
+
+// A lane: four consecutive top-level pixels, the plane addressed linearly (a sequence's plane starts on a 4-byte boundary only: the
+// 16-byte, 8-byte and 4-byte accesses are declared unaligned); the last lane of a plane whose size is no multiple of 4 goes pixel by
+// pixel.  No float atomics, no LDS.
 typedef float kf_f4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef float kf_f2 __attribute__((ext_vector_type(2), aligned(4)));
 typedef uint32_t kf_u32 __attribute__((aligned(1)));
 #define DVO_KF_FUSE_PER_THREAD 4
 
+struct KfLane {
+    int first, nk;   // the lane's first pixel (0 for a lane past the plane) and how many it has
+    bool full;
+    size_t base;     // the sequence's plane
+    int x, y;        // (column, row) of `first`
+};
+__device__ __forceinline__ KfLane kf_lane(int seq, int w, int h, float inv_w)
+{
+    const int n = w * h;
+    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_KF_FUSE_PER_THREAD;
+    KfLane L;
+    L.nk = i0 >= n ? 0 : (n - i0 < DVO_KF_FUSE_PER_THREAD ? n - i0 : DVO_KF_FUSE_PER_THREAD);
+    L.first = L.nk ? i0 : 0;
+    L.full = L.nk == DVO_KF_FUSE_PER_THREAD;
+    L.base = (size_t)seq * n;
+    split_row(L.first, w, inv_w, L.x, L.y);
+    return L;
+}
+// The lane's pixels at p and their count bytes at cb, packed into c4: a pixel the lane does not have reads as 0 and is not written.
+// Either pointer may be null (a constant at every call): that half is left out.
+__device__ __forceinline__ void kf_load_lane(const KfLane& L, const float* p, const uint8_t* cb, float d[DVO_KF_FUSE_PER_THREAD], uint32_t& c4)
+{
+    for (int k = 0; k < DVO_KF_FUSE_PER_THREAD; k++) d[k] = 0.0f;
+    c4 = 0;
+    if (L.full) {
+        const kf_f4 v = *reinterpret_cast<const kf_f4*>(p);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+        if (cb) c4 = *reinterpret_cast<const kf_u32*>(cb);
+    } else {
+        for (int k = 0; k < L.nk; k++) {
+            d[k] = p[k];
+            if (cb) c4 |= (uint32_t)cb[k] << (8 * k);
+        }
+    }
+}
+__device__ __forceinline__ void kf_store_lane(const KfLane& L, float* p, const float* d, uint8_t* cb, uint32_t c4)
+{
+    if (L.full) {
+        if (p) {
+            kf_f4 v;
+            v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
+            *reinterpret_cast<kf_f4*>(p) = v;
+        }
+        if (cb) *reinterpret_cast<kf_u32*>(cb) = c4;
+    } else {
+        for (int k = 0; k < L.nk; k++) {
+            if (p) p[k] = d[k];
+            if (cb) cb[k] = (uint8_t)(c4 >> (8 * k));
+        }
+    }
+}
+
+// Pixel (x, y) of one map at depth dk, through pose `go` into the other map's top-level plane `other` and back through pose `back`:
+// KF_MISS when it lands behind min_depth or outside the plane, or a tap is below min_depth, not finite, or the four spread more than
+// max_diff; KF_GATED when the bilinear depth there disagrees with the warped point's by more than max_diff; KF_MISS again when the
+// point that comes back is out of range; else KF_HIT with zr = its depth back in the pixel's own map and o = the offset of the first
+// tap within the plane (a plane has fewer than 2^24 pixels: split_row).  PAIRED: the taps are two 8-byte loads, not four 4-byte ones
+// (each caller keeps the loads it was measured with).
+enum { KF_MISS = 0, KF_GATED = 1, KF_HIT = 2 };
+template <bool PCAM, bool PAIRED, class Args>
+__device__ __forceinline__ int kf_warp_gate(const Args& a, const Intr& cam, const Pose& go, const Pose& back, const float* __restrict__ other,
+                                            int w, int h, int x, int y, float dk, float& zr, int& o)
+{
+    const float md = a.min_depth, inf = __builtin_inff();
+    float X, Y, Z, Xg, Yg, Zg;
+    back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, dk, X, Y, Z);
+    transform(go, X, Y, Z, Xg, Yg, Zg);
+    if (!(Zg >= md)) return KF_MISS;
+    float u, v;
+    project(map_intr<PCAM>(a, cam), Xg, Yg, Zg, u, v);
+    if (!(u >= 0.0f && u < (float)(w - 1) && v >= 0.0f && v < (float)(h - 1))) return KF_MISS;
+    const int x0 = (int)u, y0 = (int)v;
+    const float fa = u - (float)x0, fb = v - (float)y0;
+    o = y0 * w + x0;
+    float z00, z10, z01, z11;
+    if constexpr (PAIRED) {
+        const kf_f2 r0 = *reinterpret_cast<const kf_f2*>(other + o), r1 = *reinterpret_cast<const kf_f2*>(other + o + w);
+        z00 = r0.x; z10 = r0.y; z01 = r1.x; z11 = r1.y;
+    } else {
+        const float* p = other + o;
+        z00 = p[0]; z10 = p[1]; z01 = p[w]; z11 = p[w + 1];
+    }
+    bool ok = (z00 >= md) & (z00 < inf) & (z10 >= md) & (z10 < inf) & (z01 >= md) & (z01 < inf) & (z11 >= md) & (z11 < inf);
+    const float mx = fmaxf(fmaxf(z00, z10), fmaxf(z01, z11)), mn = fminf(fminf(z00, z10), fminf(z01, z11));
+    ok = ok && (mx - mn <= a.max_diff);
+    if (!ok) return KF_MISS;
+    const float top = fmaf(fa, z10 - z00, z00), bot = fmaf(fa, z11 - z01, z01);
+    const float zi = fmaf(fb, bot - top, top);
+    if (!(fabsf(zi - Zg) <= a.max_diff)) return KF_GATED;
+    float Xb, Yb;
+    back_project(map_intr<PCAM>(a, cam), u, v, zi, X, Y, Z);
+    transform(back, X, Y, Z, Xb, Yb, zr);
+    return (zr >= md && zr < inf) ? KF_HIT : KF_MISS;
+}
+
+// dn at top-level pixel (x, y) into the lower levels of `pyr`: they keep the pixels whose coordinates are multiples of 2^t
+template <class Args>
+__device__ __forceinline__ void kf_write_lower(const Args& a, float* const* pyr, int seq, int x, int y, float dn)
+{
+    const int T = a.levels - 1;
+    for (int t = 1; t < a.levels; t++) {
+        const int msk = (1 << t) - 1;
+        if ((x & msk) | (y & msk)) break;
+        const int l = T - t, lx = x >> t, ly = y >> t;
+        if (lx >= a.w[l] || ly >= a.h[l]) continue;
+        pyr[l][(size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx] = dn;
+    }
+}
+
+// A lane's tally is candidates | done << 10 | gated << 20 (at most 4 of each per lane, 256 per wave): summed per wave by one packed
+// butterfly (every lane of the wave must be here) and added to the sequence's record with integer atomics: order-free.
+#define DVO_KF_TALLY_DONE  (1 << 10)
+#define DVO_KF_TALLY_GATED (1 << 20)
+__device__ __forceinline__ void kf_tally(int tally, KfRecord* r)
+{
+    for (int o = 32; o > 0; o >>= 1) tally += __shfl_xor(tally, o);
+    if ((threadIdx.x & 63) == 0) {
+        if (tally & 0x3ff) atomicAdd(&r->n_candidates, tally & 0x3ff);
+        if ((tally >> 10) & 0x3ff) atomicAdd(&r->n_done, (tally >> 10) & 0x3ff);
+        if ((tally >> 20) & 0x3ff) atomicAdd(&r->n_gated, (tally >> 20) & 0x3ff);
+    }
+}
+
+// k_kf_fuse: the lane's pixels are the keyframe's, read and written in place with their own counts; it goes through F, gathers four
+// scalar taps from the tracked frame's map (which nobody writes) and comes back through Bk.  Its own: the clear mode; a candidate is
+// any depth >= min_depth; the count is the pixel's own byte; the blend moves 1 / (c + 2) of the way to the returned depth; depth and
+// counts go back only from a lane that fused something.
 template <bool PCAM>
 __device__ __forceinline__ void kf_fuse(KfFuseArgs a)
 {
     const int seq = grid_seq();
     if (seq >= a.n_seq) return;
-    const KfFuseSeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
+    const KfSeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
     if (e.mode == DVO_KF_FUSE_NONE) return;
-    const int T = a.levels - 1, w = a.w[T], h = a.h[T], n = w * h;
-    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_KF_FUSE_PER_THREAD;
-    const int nk = i0 >= n ? 0 : (n - i0 < DVO_KF_FUSE_PER_THREAD ? n - i0 : DVO_KF_FUSE_PER_THREAD);
-    const bool full = nk == DVO_KF_FUSE_PER_THREAD;
-    const size_t base = (size_t)seq * n;
-    uint8_t* cnt = a.counts + base + (nk ? i0 : 0);
-    if (e.mode == DVO_KF_FUSE_CLEAR) {
-        if (full) *reinterpret_cast<kf_u32*>(cnt) = 0u;
-        else for (int k = 0; k < nk; k++) cnt[k] = 0;
-        return;
-    }
+    const int T = a.levels - 1, w = a.w[T], h = a.h[T];
+    const KfLane L = kf_lane(seq, w, h, a.inv_w);
+    uint8_t* cnt = a.counts + L.base + L.first;
+    if (e.mode == DVO_KF_FUSE_CLEAR) { kf_store_lane(L, nullptr, nullptr, cnt, 0u); return; }
     Intr cam;
     if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
-    float* kd = a.kf_depth[T] + base + (nk ? i0 : 0);
-    const float* __restrict__ fd = a.frame_depth + base;
-    float d[DVO_KF_FUSE_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
-    uint32_t c4 = 0;
-    if (full) {
-        const kf_f4 v = *reinterpret_cast<const kf_f4*>(kd);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-        c4 = *reinterpret_cast<const kf_u32*>(cnt);
-    } else {
-        for (int k = 0; k < nk; k++) { d[k] = kd[k]; c4 |= (uint32_t)cnt[k] << (8 * k); }
-    }
-    int x, y;
-    split_row(nk ? i0 : 0, w, a.inv_w, x, y);
-    const float md = a.min_depth, inf = __builtin_inff();
-    const float wmax = (float)(w - 1), hmax = (float)(h - 1);
-    int tally = 0;   // candidates | fused << 10 | gated << 20 (at most 4 of each per lane, 256 per wave)
+    float* kd = a.kf_depth[T] + L.base + L.first;
+    float d[DVO_KF_FUSE_PER_THREAD];
+    uint32_t c4;
+    kf_load_lane(L, kd, cnt, d, c4);
+    int x = L.x, y = L.y, tally = 0;
 #pragma unroll
     for (int k = 0; k < DVO_KF_FUSE_PER_THREAD; k++) {
         const float dk = d[k];
-        if (k < nk && dk >= md) {
+        if (k < L.nk && dk >= a.min_depth) {
+            float Zo;
+            int o;
+            const int g = kf_warp_gate<PCAM, false>(a, cam, e.F, e.Bk, a.frame_depth + L.base, w, h, x, y, dk, Zo, o);
             tally += 1;
-            float X, Y, Z, Xf, Yf, Zf;
-            back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, dk, X, Y, Z);
-            transform(e.F, X, Y, Z, Xf, Yf, Zf);
-            if (Zf >= md) {
-                float u, v;
-                project(map_intr<PCAM>(a, cam), Xf, Yf, Zf, u, v);
-                if (u >= 0.0f && u < wmax && v >= 0.0f && v < hmax) {
-                    const int x0 = (int)u, y0 = (int)v;
-                    const float fa = u - (float)x0, fb = v - (float)y0;
-                    const float* p = fd + (size_t)y0 * w + x0;
-                    const float z00 = p[0], z10 = p[1], z01 = p[w], z11 = p[w + 1];
-                    bool ok = (z00 >= md) & (z00 < inf) & (z10 >= md) & (z10 < inf) & (z01 >= md) & (z01 < inf) & (z11 >= md) & (z11 < inf);
-                    const float mx = fmaxf(fmaxf(z00, z10), fmaxf(z01, z11)), mn = fminf(fminf(z00, z10), fminf(z01, z11));
-                    ok = ok && (mx - mn <= a.max_diff);
-                    if (ok) {
-                        const float top = fmaf(fa, z10 - z00, z00), bot = fmaf(fa, z11 - z01, z01);
-                        const float zi = fmaf(fb, bot - top, top);
-                        if (fabsf(zi - Zf) <= a.max_diff) {
-                            float Xo, Yo, Zo;
-                            back_project(map_intr<PCAM>(a, cam), u, v, zi, X, Y, Z);
-                            transform(e.Bk, X, Y, Z, Xo, Yo, Zo);
-                            if (Zo >= md && Zo < inf) {
-                                const int c = (int)((c4 >> (8 * k)) & 0xffu);
-                                const float r = recip_rn((float)(c + 2));
-                                const float dn = fmaf(Zo - dk, r, dk);
-                                const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
-                                d[k] = dn;
-                                c4 = (c4 & ~(0xffu << (8 * k))) | ((uint32_t)cn << (8 * k));
-                                tally += 1 << 10;
-                                for (int t = 1; t < a.levels; t++) {   // lower levels keep pixels whose coordinates are multiples of 2^t
-                                    const int msk = (1 << t) - 1;
-                                    if ((x & msk) | (y & msk)) break;
-                                    const int l = T - t, lx = x >> t, ly = y >> t;
-                                    if (lx >= a.w[l] || ly >= a.h[l]) continue;
-                                    a.kf_depth[l][(size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx] = dn;
-                                }
-                            }
-                        } else {
-                            tally += 1 << 20;
-                        }
-                    }
-                }
+            if (g == KF_GATED) tally += DVO_KF_TALLY_GATED;
+            if (g == KF_HIT) {
+                const int c = (int)((c4 >> (8 * k)) & 0xffu);
+                const float dn = fmaf(Zo - dk, recip_rn((float)(c + 2)), dk);
+                const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
+                d[k] = dn;
+                c4 = (c4 & ~(0xffu << (8 * k))) | ((uint32_t)cn << (8 * k));
+                tally += DVO_KF_TALLY_DONE;
+                kf_write_lower(a, a.kf_depth, seq, x, y, dn);
             }
         }
         x++;
         if (x == w) { x = 0; y++; }
     }
-    if (tally & (0x3ff << 10)) {   // something fused: the lane's pixels and counts go back
-        if (full) {
-            kf_f4 v;
-            v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
-            *reinterpret_cast<kf_f4*>(kd) = v;
-            *reinterpret_cast<kf_u32*>(cnt) = c4;
-        } else {
-            for (int k = 0; k < nk; k++) { kd[k] = d[k]; cnt[k] = (uint8_t)(c4 >> (8 * k)); }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) tally += __shfl_xor(tally, o);   // (every lane of the wave is here: no lane left early)
-    if ((threadIdx.x & 63) == 0) {
-        KfFuseRecord* r = a.rec + seq;
-        if (tally & 0x3ff) atomicAdd(&r->n_candidates, tally & 0x3ff);
-        if ((tally >> 10) & 0x3ff) atomicAdd(&r->n_fused, (tally >> 10) & 0x3ff);
-        if ((tally >> 20) & 0x3ff) atomicAdd(&r->n_gated, (tally >> 20) & 0x3ff);
-    }
+    if (tally & (0x3ff << 10)) kf_store_lane(L, kd, d, cnt, c4);
+    kf_tally(tally, a.rec + seq);
 }
 
 __global__ void __launch_bounds__(256) k_kf_fuse(KfFuseArgs a) { kf_fuse<false>(a); }
 __global__ void __launch_bounds__(256) k_kf_fuse_cam(KfFuseArgs a) { kf_fuse<true>(a); }
 
-// ------------------------------------------------------------------------------------------------
-// Keyframe carry of a sensor-depth batch (dvo_batch_set_keyframe_carry; the contract is in include/dvo.h): on a
-// promotion the old keyframe's fused depth and counts are warped into the frame that becomes the keyframe, before k_promote copies it.
-// k_kf_carry_prep: carry (TRACK, rule fired, finite twist: F and Bk as k_kf_fuse_prep's) or nothing, and the sequence's record zeroed.
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(64) k_kf_carry_prep(KfCarryPrepArgs a)
-{
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= a.n_seq) return;
-    const MonoSeq& m = a.meta[s];
-    KfCarrySeq e;
-    for (int i = 0; i < 9; i++) { e.F.R[i] = 0.0f; e.Bk.R[i] = 0.0f; }
-    for (int i = 0; i < 3; i++) { e.F.t[i] = 0.0f; e.Bk.t[i] = 0.0f; e.pad[i] = 0; }
-    e.mode = DVO_KF_CARRY_NONE;
-    if (a.eff[s] == DVO_SEQ_TRACK && a.is_key[s]) {
-        float xi[6];
-        bool finite = true;
-        for (int i = 0; i < 6; i++) { xi[i] = m.rel_xi[i]; finite = finite && isfinite(xi[i]); }
-        if (finite) {
-            e.mode = DVO_KF_CARRY_CARRY;
-            e.F = m.rel_pose;
-            pose_from_xi(xi, -1.0f, e.Bk);
-        }
-    }
-    a.table[s] = e;
-    KfCarryRecord z;
-    z.n_candidates = 0; z.n_carried = 0; z.n_gated = 0; z.pad = 0;
-    a.rec[s] = z;
-}
-
-// k_kf_carry: k_kf_fuse's shape with the roles swapped.  A lane's own four pixels are the tracked frame's (the keyframe-to-be): it
-// reads and writes their depth in place and gathers four depth taps (two 8-byte pairs) and four count taps (bytes) from the old
-// keyframe, which nobody writes during this launch.  Neighbouring lanes gather the old counts, so the new counts go to a staging
-// plane (every pixel of a carrying sequence: 0 where nothing was carried) that k_kf_carry_commit copies after k_kf_fuse has cleared.
-typedef float kf_f2 __attribute__((ext_vector_type(2), aligned(4)));
-
+// k_kf_carry: the lane's pixels are the tracked frame's (the keyframe-to-be), read and written in place before k_promote copies
+// them; it goes through Bk, gathers two 8-byte tap pairs from the old keyframe (which nobody writes during this launch) and comes back
+// through F.  Its own: a candidate must also be finite; the count is the minimum of the four tap bytes (the old map stands for c + 1
+// samples, the pixel's own for one: the blend moves (c + 1) / (c + 2) of the way); the blended depth must itself be in range; and,
+// because neighbouring lanes gather the old counts, the new counts go to a staging plane -- every pixel of a carrying sequence, 0 where
+// nothing was carried -- that k_kf_carry_commit copies after k_kf_fuse has cleared.
 template <bool PCAM>
 __device__ __forceinline__ void kf_carry(KfCarryArgs a)
 {
     const int seq = grid_seq();
     if (seq >= a.n_seq) return;
-    const KfCarrySeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
+    const KfSeq e = load_seq_entry(a.table, seq);   // uniform per workgroup: scalar loads
     if (e.mode != DVO_KF_CARRY_CARRY) return;
-    const int T = a.levels - 1, w = a.w[T], h = a.h[T], n = w * h;
-    const int i0 = ((int)blockIdx.x * 256 + (int)threadIdx.x) * DVO_KF_FUSE_PER_THREAD;
-    const int nk = i0 >= n ? 0 : (n - i0 < DVO_KF_FUSE_PER_THREAD ? n - i0 : DVO_KF_FUSE_PER_THREAD);
-    const bool full = nk == DVO_KF_FUSE_PER_THREAD;
-    const size_t base = (size_t)seq * n;
+    const int T = a.levels - 1, w = a.w[T], h = a.h[T];
+    const KfLane L = kf_lane(seq, w, h, a.inv_w);
     Intr cam;
     if constexpr (PCAM) cam = load_seq_entry(a.seq_k, seq);
-    float* fd = a.frame_depth[T] + base + (nk ? i0 : 0);
-    uint8_t* st = a.staged + base + (nk ? i0 : 0);
-    const float* __restrict__ kd = a.kf_depth + base;
-    const uint8_t* __restrict__ kc = a.counts + base;
-    float d[DVO_KF_FUSE_PER_THREAD] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (full) {
-        const kf_f4 v = *reinterpret_cast<const kf_f4*>(fd);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else {
-        for (int k = 0; k < nk; k++) d[k] = fd[k];
-    }
-    int x, y;
-    split_row(nk ? i0 : 0, w, a.inv_w, x, y);
+    float* fd = a.frame_depth[T] + L.base + L.first;
+    uint8_t* st = a.staged + L.base + L.first;
+    const uint8_t* __restrict__ kc = a.counts + L.base;
+    float d[DVO_KF_FUSE_PER_THREAD];
+    uint32_t c4;
+    kf_load_lane(L, fd, nullptr, d, c4);
     const float md = a.min_depth, inf = __builtin_inff();
-    const float wmax = (float)(w - 1), hmax = (float)(h - 1);
-    uint32_t c4 = 0;
-    int tally = 0;   // candidates | carried << 10 | gated << 20 (at most 4 of each per lane, 256 per wave)
+    int x = L.x, y = L.y, tally = 0;
 #pragma unroll
     for (int k = 0; k < DVO_KF_FUSE_PER_THREAD; k++) {
         const float dk = d[k];
-        if (k < nk && dk >= md && dk < inf) {
+        if (k < L.nk && dk >= md && dk < inf) {
+            float Zp;
+            int o;
+            const int g = kf_warp_gate<PCAM, true>(a, cam, e.Bk, e.F, a.kf_depth + L.base, w, h, x, y, dk, Zp, o);
             tally += 1;
-            float X, Y, Z, Xk, Yk, Zk;
-            back_project(map_intr<PCAM>(a, cam), (float)x, (float)y, dk, X, Y, Z);
-            transform(e.Bk, X, Y, Z, Xk, Yk, Zk);
-            if (Zk >= md) {
-                float u, v;
-                project(map_intr<PCAM>(a, cam), Xk, Yk, Zk, u, v);
-                if (u >= 0.0f && u < wmax && v >= 0.0f && v < hmax) {
-                    const int x0 = (int)u, y0 = (int)v;
-                    const float fa = u - (float)x0, fb = v - (float)y0;
-                    const size_t o = (size_t)y0 * w + x0;
-                    const kf_f2 r0 = *reinterpret_cast<const kf_f2*>(kd + o), r1 = *reinterpret_cast<const kf_f2*>(kd + o + w);
-                    const float z00 = r0.x, z10 = r0.y, z01 = r1.x, z11 = r1.y;
-                    bool ok = (z00 >= md) & (z00 < inf) & (z10 >= md) & (z10 < inf) & (z01 >= md) & (z01 < inf) & (z11 >= md) & (z11 < inf);
-                    const float mx = fmaxf(fmaxf(z00, z10), fmaxf(z01, z11)), mn = fminf(fminf(z00, z10), fminf(z01, z11));
-                    ok = ok && (mx - mn <= a.max_diff);
-                    if (ok) {
-                        const float top = fmaf(fa, z10 - z00, z00), bot = fmaf(fa, z11 - z01, z01);
-                        const float zi = fmaf(fb, bot - top, top);
-                        if (fabsf(zi - Zk) <= a.max_diff) {
-                            float Xp, Yp, Zp;
-                            back_project(map_intr<PCAM>(a, cam), u, v, zi, X, Y, Z);
-                            transform(e.F, X, Y, Z, Xp, Yp, Zp);
-                            if (Zp >= md && Zp < inf) {
-                                const int c00 = kc[o], c10 = kc[o + 1], c01 = kc[o + w], c11 = kc[o + w + 1];
-                                const int ca = c00 < c10 ? c00 : c10, cb = c01 < c11 ? c01 : c11;
-                                const int c = ca < cb ? ca : cb;   // the old map stands for c + 1 samples, the pixel's own for one
-                                const float r = (float)(c + 1) * recip_rn((float)(c + 2));
-                                const float dn = fmaf(Zp - dk, r, dk);
-                                if (dn >= md && dn < inf) {
-                                    const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
-                                    d[k] = dn;
-                                    c4 |= (uint32_t)cn << (8 * k);
-                                    tally += 1 << 10;
-                                    for (int t = 1; t < a.levels; t++) {   // lower levels keep pixels whose coordinates are multiples of 2^t
-                                        const int msk = (1 << t) - 1;
-                                        if ((x & msk) | (y & msk)) break;
-                                        const int l = T - t, lx = x >> t, ly = y >> t;
-                                        if (lx >= a.w[l] || ly >= a.h[l]) continue;
-                                        a.frame_depth[l][(size_t)seq * a.w[l] * a.h[l] + (size_t)ly * a.w[l] + lx] = dn;
-                                    }
-                                }
-                            }
-                        } else {
-                            tally += 1 << 20;
-                        }
-                    }
+            if (g == KF_GATED) tally += DVO_KF_TALLY_GATED;
+            if (g == KF_HIT) {
+                const int c00 = kc[o], c10 = kc[o + 1], c01 = kc[o + w], c11 = kc[o + w + 1];
+                const int ca = c00 < c10 ? c00 : c10, cb = c01 < c11 ? c01 : c11;
+                const int c = ca < cb ? ca : cb;
+                const float dn = fmaf(Zp - dk, (float)(c + 1) * recip_rn((float)(c + 2)), dk);
+                if (dn >= md && dn < inf) {
+                    const int cn = c + 1 < a.max_count ? c + 1 : a.max_count;
+                    d[k] = dn;
+                    c4 |= (uint32_t)cn << (8 * k);
+                    tally += DVO_KF_TALLY_DONE;
+                    kf_write_lower(a, a.frame_depth, seq, x, y, dn);
                 }
             }
         }
         x++;
         if (x == w) { x = 0; y++; }
     }
-    if (full) {
-        *reinterpret_cast<kf_u32*>(st) = c4;
-        if (tally & (0x3ff << 10)) {   // something carried: the lane's pixels go back
-            kf_f4 v;
-            v.x = d[0]; v.y = d[1]; v.z = d[2]; v.w = d[3];
-            *reinterpret_cast<kf_f4*>(fd) = v;
-        }
-    } else {
-        for (int k = 0; k < nk; k++) { st[k] = (uint8_t)(c4 >> (8 * k)); fd[k] = d[k]; }
-    }
-    for (int o = 32; o > 0; o >>= 1) tally += __shfl_xor(tally, o);   // (every lane of the wave is here: no lane left early)
-    if ((threadIdx.x & 63) == 0) {
-        KfCarryRecord* r = a.rec + seq;
-        if (tally & 0x3ff) atomicAdd(&r->n_candidates, tally & 0x3ff);
-        if ((tally >> 10) & 0x3ff) atomicAdd(&r->n_carried, (tally >> 10) & 0x3ff);
-        if ((tally >> 20) & 0x3ff) atomicAdd(&r->n_gated, (tally >> 20) & 0x3ff);
-    }
+    // (the staged counts always, the pixels from a lane that carried something; a tail lane writes its pixels back either way)
+    kf_store_lane(L, !L.full || (tally & (0x3ff << 10)) ? fd : nullptr, d, st, c4);
+    kf_tally(tally, a.rec + seq);
 }
 
 __global__ void __launch_bounds__(256) k_kf_carry(KfCarryArgs a) { kf_carry<false>(a); }
@@ -1401,35 +1332,28 @@ void launch_points(const PointsArgs& a0, uint32_t* offsets_out, hipStream_t s)
     else hipLaunchKernelGGL(k_points_write, grid, dim3(256), 0, s, a);
 }
 
-void launch_kf_fuse_prep(const KfFusePrepArgs& a, hipStream_t s)
+void launch_kf_fuse_prep(const KfPrepArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kf_fuse_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
 }
 
-void launch_kf_fuse(const KfFuseArgs& a0, hipStream_t s)
-{
-    KfFuseArgs a = a0;
-    const int T = a.levels - 1;
-    a.inv_w = 1.0f / (float)a.w[T];
-    const dim3 grid = seq_grid(cdiv_u(a.w[T] * a.h[T], 256 * DVO_KF_FUSE_PER_THREAD), (unsigned)a.n_seq);
-    if (a.seq_k) hipLaunchKernelGGL(k_kf_fuse_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
-    else hipLaunchKernelGGL(k_kf_fuse, grid, dim3(256), 0, s, a);
-}
-
-void launch_kf_carry_prep(const KfCarryPrepArgs& a, hipStream_t s)
+void launch_kf_carry_prep(const KfPrepArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_kf_carry_prep, dim3(cdiv_u(a.n_seq, 64)), dim3(64), 0, s, a);
 }
 
-void launch_kf_carry(const KfCarryArgs& a0, hipStream_t s)
+// the pixel kernels of the fusion and of the carry: one lane per four top-level pixels; `cam` with per-sequence intrinsics
+template <class Args>
+static void launch_kf_pixels(void (*plain)(Args), void (*cam)(Args), const Args& a0, hipStream_t s)
 {
-    KfCarryArgs a = a0;
+    Args a = a0;
     const int T = a.levels - 1;
     a.inv_w = 1.0f / (float)a.w[T];
     const dim3 grid = seq_grid(cdiv_u(a.w[T] * a.h[T], 256 * DVO_KF_FUSE_PER_THREAD), (unsigned)a.n_seq);
-    if (a.seq_k) hipLaunchKernelGGL(k_kf_carry_cam, grid, dim3(256), 0, s, a);   // per-sequence intrinsics
-    else hipLaunchKernelGGL(k_kf_carry, grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL(a.seq_k ? cam : plain, grid, dim3(256), 0, s, a);
 }
+void launch_kf_fuse(const KfFuseArgs& a, hipStream_t s) { launch_kf_pixels(k_kf_fuse, k_kf_fuse_cam, a, s); }
+void launch_kf_carry(const KfCarryArgs& a, hipStream_t s) { launch_kf_pixels(k_kf_carry, k_kf_carry_cam, a, s); }
 
 void launch_kf_carry_commit(const KfCarryCommitArgs& a, hipStream_t s)
 {

@@ -16,98 +16,26 @@ import pytest
 
 import dvo_amd as dvo
 import kf_carry_ref as cref
+import kf_common as kfc
 import kf_fusion_ref as kref
 import orc
 import points_ref as pref
-from dvo_amd import synth
+from kf_common import (CULLS, KH, LEVELS, MAX_COUNT, MAX_DIFF, RESTART, SKIP, STARTED, TOP, TRACK, TRACKED, cams as _cams, idx as _idx,
+                       push as _push)
 from util import K640
 
 pytestmark = pytest.mark.gpu
 
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
 SIZE = (328, 248)
 TAIL = (326, 246)
-LEVELS, CULLS, TOP = 3, 1, 2
-STEPS = (1.0, 0.75, 0.5)
-KH = np.array(K640, np.float32).copy()
-KH[0] *= 0.5
-KH[1] *= 0.5
-MAX_DIFF, MAX_COUNT = 0.05, 16
 KC_ON, KC_OFF = dvo.KF_CARRY_ON, dvo.KF_CARRY_OFF   # (without the feature the file fails here, at import)
 ZF = dict(n_candidates=0, n_fused=0, n_gated=0)
+_cfg = functools.partial(kfc.cfg, 2)                # keyframe_max_frames = 2 unless a test sets it
+_acts = functools.partial(kfc.acts, p=(0.15, 0.75, 0.1))
 
 
-def _cfg(**kw):
-    kw.setdefault("max_iterations", 6)
-    kw.setdefault("keyframe_min_translation", 1.0)
-    kw.setdefault("keyframe_max_frames", 2)
-    return dvo.default_config(gn_pixels_per_thread=4, crop_enable=0, step_default=STEPS[0], step_level1=STEPS[1], step_level2=STEPS[2],
-                              min_residual=0.0, min_update=2e-5, **kw)
-
-
-def _holes(d):
-    """0, NaN, +inf, below min_depth and a 0.3 m step block in every frame: in the old keyframes and in the promoting frames"""
-    d = d.copy()
-    d[:, 20:40, 30:60] = 0.0
-    d[:, 100:110, 200:230] = np.nan
-    d[:, 150:156, 40:80] = np.inf
-    d[:, 60:120, 120:180] += np.float32(0.3)
-    d[:, 200:204, 100:140] = 0.1
-    return d
-
-
-@functools.lru_cache(maxsize=None)
 def _frames(size=SIZE, holes=False, big=False):
-    kw = dict(sigma_t=0.02, sigma_r_deg=1.2) if big else {}
-    g, d, s, _ = synth.sequence(6, width=size[0], height_px=size[1], K=KH, seed=42, sigma_value=0.5, **kw)
-    g, d, s = g.numpy(), d.numpy(), s.numpy()
-    if holes:
-        d = _holes(d)
-    for a in (g, d, s):
-        a.setflags(write=False)
-    return g, d, s
-
-
-def _dev(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def _idx(B, pushes):
-    return [[(k + b) % 6 for b in range(B)] for k in range(pushes)]
-
-
-def _acts(B, n, seed):
-    rng = np.random.RandomState(seed)
-    a = rng.choice([SKIP, TRACK, RESTART], size=(n, B), p=(0.15, 0.75, 0.1)).astype(np.uint8)
-    a[0] = TRACK
-    a[0, B - 1] = SKIP          # one sequence starts late: its keyframe does not exist after the first push
-    return a
-
-
-def _push(bt, keep, maps, feed):
-    gi, di, si = maps
-    if feed == "host":
-        bt.push_host(gi, di, si)
-    elif feed in ("raw", "raw_host"):
-        with np.errstate(invalid="ignore"):
-            g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8)
-            d16 = np.clip(np.rint(np.nan_to_num(di, nan=0.0, posinf=0.0) * 5000), 0, 65535).astype(np.uint16)
-        if feed == "raw_host":
-            bt.push_raw_host(g8, d16)
-        else:
-            import torch
-            tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-            torch.cuda.synchronize()
-            keep.append((tg, td))
-            bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-    else:
-        t = [_dev(x) for x in maps]
-        keep.append(t)
-        bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    return kfc.frames(size, 0.0, holes, big)
 
 
 def _make(B, size, cfg_kw=None, cams=None, dist=None, setup=None, max_count=MAX_COUNT, carry=True, fusion=True):
@@ -229,13 +157,6 @@ def _lockstep(B=5, size=SIZE, pushes=6, feed="device", cfg_kw=None, cams=None, d
         return m, out
     finally:
         bt.close(); sh.close()
-
-
-def _cams(B):
-    c = np.tile(KH.reshape(1, 9), (B, 1)).astype(np.float32)
-    c[:, 0] *= 1.0 + 0.01 * np.arange(B); c[:, 4] *= 1.0 - 0.008 * np.arange(B)
-    c[:, 2] += 0.7 * np.arange(B); c[:, 5] -= 0.4 * np.arange(B)
-    return c
 
 
 CASES = [

@@ -12,79 +12,23 @@ import numpy as np
 import pytest
 
 import dvo_amd as dvo
+import kf_common as kfc
 import kf_fusion_ref as kref
 import orc
-from dvo_amd import synth
+from kf_common import (CULLS, KH, LEVELS, MAX_COUNT, MAX_DIFF, RESTART, SKIP, SKIPPED, STARTED, TOP, TRACK, TRACKED, cams as _cams, holes as _holes,
+                       idx as _idx, push as _push)
 from util import K640
 
 pytestmark = pytest.mark.gpu
 
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
 SIZE = (320, 240)
-LEVELS, CULLS, TOP = 3, 1, 2
-STEPS = (1.0, 0.75, 0.5)
-KH = np.array(K640, np.float32).copy()
-KH[0] *= 0.5
-KH[1] *= 0.5
-MAX_DIFF, MAX_COUNT = 0.05, 16
 KF_ON, KF_OFF = dvo.KF_FUSION_ON, dvo.KF_FUSION_OFF   # (without the feature the file fails here, at import)
+_cfg = functools.partial(kfc.cfg, 4)                  # keyframe_max_frames = 4 unless a test sets it
+_acts = functools.partial(kfc.acts, p=(0.2, 0.7, 0.1))
 
 
-def _cfg(**kw):
-    kw.setdefault("max_iterations", 6)
-    kw.setdefault("keyframe_min_translation", 1.0)
-    kw.setdefault("keyframe_max_frames", 4)
-    return dvo.default_config(gn_pixels_per_thread=4, crop_enable=0, step_default=STEPS[0], step_level1=STEPS[1], step_level2=STEPS[2],
-                              min_residual=0.0, min_update=2e-5, **kw)
-
-
-@functools.lru_cache(maxsize=None)
 def _frames(size=SIZE, noise=0.0):
-    g, d, s, _ = synth.sequence(6, width=size[0], height_px=size[1], K=KH, seed=42, sigma_value=0.5)
-    g, d, s = g.numpy(), d.numpy(), s.numpy()
-    if noise:
-        d = (d + np.random.RandomState(7).normal(0.0, noise, d.shape)).astype(np.float32)
-    return g, d, s
-
-
-def _dev(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-def _idx(B, pushes):
-    return [[(k + b) % 6 for b in range(B)] for k in range(pushes)]
-
-
-def _acts(B, n, seed):
-    rng = np.random.RandomState(seed)
-    a = rng.choice([SKIP, TRACK, RESTART], size=(n, B), p=(0.2, 0.7, 0.1)).astype(np.uint8)
-    a[0] = TRACK
-    a[0, B - 1] = SKIP          # one sequence starts late: its keyframe does not exist after the first push
-    return a
-
-
-def _push(bt, keep, maps, feed):
-    gi, di, si = maps
-    if feed == "host":
-        bt.push_host(gi, di, si)
-    elif feed in ("raw", "raw_host"):
-        g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
-        if feed == "raw_host":
-            bt.push_raw_host(g8, d16)
-        else:
-            import torch
-            tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-            torch.cuda.synchronize()
-            keep.append((tg, td))
-            bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-    else:
-        t = [_dev(x) for x in maps]
-        keep.append(t)
-        bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
+    return kfc.frames(size, noise)
 
 
 class Mirror:
@@ -172,13 +116,6 @@ def _lockstep(B=5, size=SIZE, pushes=6, feed="device", cfg_kw=None, cams=None, d
         bt.close()
 
 
-def _cams(B):
-    c = np.tile(KH.reshape(1, 9), (B, 1)).astype(np.float32)
-    c[:, 0] *= 1.0 + 0.01 * np.arange(B); c[:, 4] *= 1.0 - 0.008 * np.arange(B)
-    c[:, 2] += 0.7 * np.arange(B); c[:, 5] -= 0.4 * np.arange(B)
-    return c
-
-
 CASES = [
     ("b5", dict()),
     ("b17", dict(B=17, pushes=5)),
@@ -223,23 +160,12 @@ def test_direction_fuses_most_of_the_view():
     assert min(m.fractions) > 0.5, m.fractions
 
 
-def _holes(d, rng):
-    d = d.copy()
-    for q in range(d.shape[0]):
-        d[q, 20:40, 30:60] = 0.0                       # a hole
-        d[q, 100:110, 200:230] = np.nan
-        d[q, 150:156, 40:80] = np.inf
-        d[q, 60:120, 120:180] += np.float32(0.3)       # a 0.3 m step block
-        d[q, 200:204, 100:140] = 0.1                   # below min_depth
-    return d
-
-
 def test_holes_never_change_and_nothing_turns_non_finite():
     """A hole, NaN, +inf, a below-min_depth patch and a 0.3 m step block in every frame (so in the keyframes and in the tracked frames):
     records, maps and counts are the replica's, no pixel that is not a candidate changes, every finite depth stays finite."""
     B, size = 5, SIZE
     g, d, s = _frames(size)
-    d = _holes(d, None)
+    d = _holes(d)
     bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=_cfg())
     try:
         bt.set_keyframe_tracking(True)

@@ -7,7 +7,6 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,9 +14,9 @@ import pytest
 import dvo_amd as dvo
 import kf_carry_ref as cref
 import kf_fusion_ref as kref
+from kf_common import assert_map_kernels_fit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "direct-visual-odometry_amd")
 NAMES = ("dvo_kf_carry_config_default", "dvo_batch_set_keyframe_carry", "dvo_batch_last_keyframe_carry")
 F32 = np.float32
 KC_ON, KC_OFF = dvo.KF_CARRY_ON, dvo.KF_CARRY_OFF   # (without the feature the file fails here, at import)
@@ -257,29 +256,7 @@ def test_step_composes_the_push():
 
 
 # ---- register pins ----------------------------------------------------------------------------------------------------------------
-def _meta(txt, name):
-    m = re.search(r"\.amdhsa_kernel %s\n.*?\.end_amdhsa_kernel" % name, txt, re.S)
-    assert m, "kernel not found: " + name
-    body = m.group(0)
-    g = lambda k: int(re.search(r"\.amdhsa_%s (\d+)" % k, body).group(1))
-    return g("next_free_vgpr"), g("private_segment_fixed_size"), g("group_segment_fixed_size")
-
-
 def test_kernels_fit_the_budget():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    cont = open(os.path.join(PKG, "Makefile")).read().split("FLAGS   =", 1)[1].split("\n")
-    flags = (cont[0].rstrip("\\") + " " + cont[1]).split()
-    flags = [f.replace("$(ARCH)", "gfx950") for f in flags if f != "-fPIC"]
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "map.s")
-        subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(PKG, "csrc", "dvo_map_kernels.hip")],
-                       check=True, capture_output=True, timeout=900)
-        asm = open(out).read()
-    for name, budget in (("_ZN3dvo10k_kf_carryENS_11KfCarryArgsE", 31 + 8), ("_ZN3dvo14k_kf_carry_camENS_11KfCarryArgsE", 31 + 8),
-                         ("_ZN3dvo15k_kf_carry_prepENS_15KfCarryPrepArgsE", 60 + 8),
-                         ("_ZN3dvo17k_kf_carry_commitENS_17KfCarryCommitArgsE", 8 + 8)):
-        v, scratch, lds = _meta(asm, name)
-        assert scratch == 0 and lds == 0, (name, scratch, lds)
-        assert v <= budget, (name, v, budget)
+    assert_map_kernels_fit((("_ZN3dvo10k_kf_carryENS_11KfCarryArgsE", 31 + 8), ("_ZN3dvo14k_kf_carry_camENS_11KfCarryArgsE", 31 + 8),
+                            ("_ZN3dvo15k_kf_carry_prepENS_10KfPrepArgsE", 60 + 8),
+                            ("_ZN3dvo17k_kf_carry_commitENS_17KfCarryCommitArgsE", 8 + 8)))

@@ -7,16 +7,15 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import dvo_amd as dvo
 import kf_fusion_ref as kref
+from kf_common import assert_map_kernels_fit
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "direct-visual-odometry_amd")
 NAMES = ("dvo_kf_fusion_config_default", "dvo_batch_set_keyframe_fusion", "dvo_batch_last_keyframe_fusion", "dvo_batch_keyframe_fusion_counts")
 F32 = np.float32
 KF_ON, KF_OFF = dvo.KF_FUSION_ON, dvo.KF_FUSION_OFF   # (without the feature the file fails here, at import)
@@ -191,28 +190,6 @@ def test_coarser_levels_are_culls_of_the_top():
 
 
 # ---- register pins ----------------------------------------------------------------------------------------------------------------
-def _meta(txt, name):
-    m = re.search(r"\.amdhsa_kernel %s\n.*?\.end_amdhsa_kernel" % name, txt, re.S)
-    assert m, "kernel not found: " + name
-    body = m.group(0)
-    g = lambda k: int(re.search(r"\.amdhsa_%s (\d+)" % k, body).group(1))
-    return g("next_free_vgpr"), g("private_segment_fixed_size"), g("group_segment_fixed_size")
-
-
 def test_kernels_fit_the_budget():
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    cont = open(os.path.join(PKG, "Makefile")).read().split("FLAGS   =", 1)[1].split("\n")
-    flags = (cont[0].rstrip("\\") + " " + cont[1]).split()
-    flags = [f.replace("$(ARCH)", "gfx950") for f in flags if f != "-fPIC"]
-    with tempfile.TemporaryDirectory() as td:
-        out = os.path.join(td, "map.s")
-        subprocess.run([hipcc] + flags + ["-S", "--cuda-device-only", "-o", out, os.path.join(PKG, "csrc", "dvo_map_kernels.hip")],
-                       check=True, capture_output=True, timeout=900)
-        asm = open(out).read()
-    for name, budget in (("_ZN3dvo9k_kf_fuseENS_10KfFuseArgsE", 31 + 8), ("_ZN3dvo13k_kf_fuse_camENS_10KfFuseArgsE", 31 + 8),
-                         ("_ZN3dvo14k_kf_fuse_prepENS_14KfFusePrepArgsE", 58 + 8)):
-        v, scratch, lds = _meta(asm, name)
-        assert scratch == 0 and lds == 0, (name, scratch, lds)
-        assert v <= budget, (name, v, budget)
+    assert_map_kernels_fit((("_ZN3dvo9k_kf_fuseENS_10KfFuseArgsE", 31 + 8), ("_ZN3dvo13k_kf_fuse_camENS_10KfFuseArgsE", 31 + 8),
+                            ("_ZN3dvo14k_kf_fuse_prepENS_10KfPrepArgsE", 58 + 8)))
