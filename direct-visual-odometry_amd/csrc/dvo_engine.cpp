@@ -1105,38 +1105,40 @@ MedianSolve Tracker::median_solve_args(size_t q0, bool log, bool prime, int* ste
     return m;
 }
 
-void Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, const float* ref_z, bool prime) const
+// false from the kernel file's tables: a set of terms without a kernel pair (Tracker::refusal lets none through)
+static int term_launch_status(bool launched)
+{
+    if (launched) return DVO_OK;
+    set_error("internal error: no kernel pair for the opt-in terms that are on");
+    return DVO_ERR_HIP;
+}
+
+int Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs, const float* ref_z, bool prime) const
 {
     const LevelPlan& L = lv[level];
     const size_t q0 = (size_t)(a.state - state.as<SeqState>());
-    const bool t2d = L.tiling.t2d != 0;
-    RobustGn r{};   // (no table: the affine kernels run without weights)
-    if (rob.on) r.table = rob.table.as<RobustEntry>() + q0;
-    if (geo.on && aff.on) launch_track_gn_zab(a, affine_gn_args(q0, prime), geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
-    else if (geo.on) launch_track_gn_z(a, geo_gn_args(q0, level, ref_z), count, L.ppt, L.group, t2d, s, grid_seqs);
-    else if (aff.on) launch_track_gn_ab(a, r, affine_gn_args(q0, prime), count, L.ppt, L.group, t2d, s, grid_seqs);
-    else if (rob.median()) {
-        MedianGn m{};
-        m.hist = rob.hist.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
-        launch_track_gn_md(a, r, m, count, L.ppt, L.group, t2d, s, grid_seqs);
-    }
-    else if (rob.on) launch_track_gn_rw(a, r, count, L.ppt, L.group, t2d, s, grid_seqs);
-    else launch_gn(a, level, count, s, grid_seqs);
+    TileTerms t{};
+    t.on = terms_on();
+    if (!t.on) { launch_gn(a, level, count, s, grid_seqs); return DVO_OK; }   // (the tile_margin path is the plain plan's)
+    if (rob.on) t.rob.table = rob.table.as<RobustEntry>() + q0;
+    if (rob.median()) t.med.hist = rob.hist.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
+    if (aff.on) t.aff = affine_gn_args(q0, prime);
+    if (geo.on) t.geo = geo_gn_args(q0, level, ref_z);
+    return term_launch_status(launch_track_gn_terms(a, t, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs));
 }
 
-void Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& t) const
+int Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& st) const
 {
     const size_t q0 = (size_t)(sa.state - state.as<SeqState>());
     const bool log = sa.log != nullptr;
-    const RobustSolve r = rob.on ? robust_solve_args(q0, t.adaptive_scale) : RobustSolve{};
-    if (geo.on && aff.on)
-        launch_gn_solve_zab(sa, affine_solve_args(q0, log, t.prime, t.affine_moments, t.estimate_once), geo_solve_args(q0, log, t.geo_sums), count, s);
-    else if (geo.on) launch_gn_solve_z(sa, geo_solve_args(q0, log, t.geo_sums), count, s);
-    else if (aff.on) launch_gn_solve_ab(sa, r, affine_solve_args(q0, log, t.prime, t.affine_moments, t.estimate_once), count, s);
-    else if (rob.median()) launch_gn_solve_md(sa, r, median_solve_args(q0, log, t.prime, t.step_mn), count, s);
-    else if (rob.on) launch_gn_solve_rw(sa, r, count, s);
-    else if (lm.on) launch_gn_solve_lm(sa, lm_solve_args(q0, log), count, s);
-    else launch_gn_solve(sa, count, s);
+    SolveTerms t{};
+    t.on = terms_on();
+    if (rob.on) t.rob = robust_solve_args(q0, st.adaptive_scale);
+    if (rob.median()) t.med = median_solve_args(q0, log, st.prime, st.step_mn);
+    if (aff.on) t.aff = affine_solve_args(q0, log, st.prime, st.affine_moments, st.estimate_once);
+    if (geo.on) t.geo = geo_solve_args(q0, log, st.geo_sums);
+    if (lm.on) t.lm = lm_solve_args(q0, log);
+    return term_launch_status(launch_gn_solve_terms(sa, t, count, s));
 }
 
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
@@ -1330,12 +1332,12 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                     // the first iteration's entry; it leaves the pose, the log, the lists and the quality record alone
                     GnArgs gp = ga;
                     gp.next_count = nullptr;
-                    launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true);
+                    DVO_TRY(launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true));
                     SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
                     sp.list_in = list_prev; sp.result = nullptr;
                     SolveTerm tp{};
                     tp.prime = true;
-                    launch_solve_term(sp, nq, sk, tp);
+                    DVO_TRY(launch_solve_term(sp, nq, sk, tp));
                 }
                 if (cfg.profile) {
                     if (ev_used == ev_pool.size()) {
@@ -1346,7 +1348,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                     }
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
                 }
-                launch_gn_term(ga, level, nq, sk, active_ub, ref.depth[level]);
+                DVO_TRY(launch_gn_term(ga, level, nq, sk, active_ub, ref.depth[level]));
                 if (cfg.profile) {
                     DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
                     ev_used++;
@@ -1356,7 +1358,7 @@ int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, cons
                 sa.list_in = list_prev;
                 sa.list_out = lists ? work_list(k, it) : nullptr;
                 if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                launch_solve_term(sa, nq, sk, iteration);
+                DVO_TRY(launch_solve_term(sa, nq, sk, iteration));
             }
             if (poll && !L.fused && it + 1 < max_it) {
                 DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));

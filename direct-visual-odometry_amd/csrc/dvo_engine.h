@@ -288,10 +288,8 @@ struct OptInTerm {
     }
 };
 
-// Which terms combine.  A batch's state is the set of terms that are on; the robust weights count as TERM_ROBUST with
-// the adaptive or a given scale and as TERM_MEDIAN with the median scale.  Each setter's "on" call is refused while one of the terms of
-// its row of the table is on (Tracker::refusal); turning a term off never consults the table.
-enum Term : unsigned { TERM_ROBUST = 1, TERM_MEDIAN = 2, TERM_AFFINE = 4, TERM_GEOMETRIC = 8, TERM_STEP_CONTROL = 16 };
+// Which terms combine.  A batch's state is the set of terms that are on (Term, dvo_kernels.h).  Each setter's "on" call
+// is refused while one of the terms of its row of the table is on (Tracker::refusal); turning a term off never consults the table.
 enum class TermSetter { RobustWeights, RobustMedian, AffineBrightness, Geometric, GeometricAffine, StepControl };
 struct TermName { unsigned term; const char* is_on; const char* setter; };   // how a refusal names a term that is on
 
@@ -399,10 +397,10 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int margin_plain = 0;
     void use_plan();
     int log_iterations() const;   // iterations per level an opt-in term's log holds (fixed by the term's first enable)
-    // One iteration's launch pair of whichever term is on -- the geometric term with affine brightness, else the
-    // geometric term, else affine brightness (with robust weights when they are on too), else robust weights (with the median scale:
-    // DESIGN.md §30), else step control (the plain tile kernel with k_gn_solve_lm), else the plain kernels: the one
-    // place that decides.  `ga` / `sa` view `count` sequences (their SeqState offset is every table's).
+    // One iteration's launch pair of the terms that are on: each fills the block of every such term and makes one call, and the
+    // kernel file's table picks the pair (launch_track_gn_terms / launch_gn_solve_terms); with nothing on, launch_gn
+    // and launch_gn_solve.  `ga` / `sa` view `count` sequences (their SeqState offset is every table's).  DVO_ERR_HIP, and nothing
+    // launched, for a set of terms without a kernel pair (an internal error: refusal lets none through).
     //   ref_z: the reference's depth of the level (whole batch, like GnArgs::ref_gray before gn_view; the geometric term only)
     //   prime: the priming pair of affine ESTIMATE mode or of the median robust scale
     struct SolveTerm {   // what a solve's caller chooses, value-initialised; the outputs are the one-evaluation ops' (device memory)
@@ -413,9 +411,9 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
         double* affine_moments;   // affine brightness: DVO_AFFINE_MOMENTS doubles
         int* step_mn;             // the median scale: 2 ints (m, n)
     };
-    void launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
-                        bool prime = false) const;
-    void launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& t) const;
+    int launch_gn_term(const GnArgs& ga, int level, int count, hipStream_t s, int grid_seqs = 0, const float* ref_z = nullptr,
+                       bool prime = false) const;
+    int launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, const SolveTerm& t) const;
     // The terms' begin of a call, before the fork (every sub-batch reads its part of the tables): the weight table (k_robust_begin),
     // the median scale's counts, the brightness table (k_affine_begin), the geometric records cleared ("not tracked" until a solve
     // says otherwise), step control's lambda0 and empty records.  once: the one-evaluation ops' given s2 and (a, b) of every sequence.

@@ -205,9 +205,6 @@ struct RobustBeginArgs {   // k_robust_begin: the table at the start of a tracki
     float param;
 };
 void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s);
-// the weighted twins of launch_track_gn / launch_gn_solve (launch pairs only, no mask)
-void launch_track_gn_rw(const struct GnArgs& a, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
-void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s);
 
 // The median (MAD) robust scale (dvo_batch_set_robust_median; the contract is in include/dvo.h).  Every contributing
 // pixel's |r| is binned, 16 bins per octave over [2^-16, 1), and the solve selects the median bin of the sequence's 256 exact counts:
@@ -249,10 +246,6 @@ struct MedianBeginArgs {   // k_median_begin: zero rows and priming slots at the
     int n_seq;
 };
 void launch_median_begin(const MedianBeginArgs& a, hipStream_t s);
-// the twins of launch_track_gn_rw / launch_gn_solve_rw that also bin |r| and select the median (launch pairs only, no mask)
-void launch_track_gn_md(const struct GnArgs& a, const RobustGn& r, const MedianGn& m, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                        int grid_seqs = 0);
-void launch_gn_solve_md(const SolveArgs& a, const RobustSolve& r, const MedianSolve& m, int n_seq, hipStream_t s);
 
 // Affine brightness compensation (dvo_batch_set_affine_brightness): I2(warp(x)) ~ a * I1(x) + b per sequence.  One
 // entry per sequence: the (a, b) the sequence's next k_track_gn_ab launch applies; (1, 0) is the plain residual bit for bit.
@@ -297,10 +290,6 @@ struct AffineBeginArgs {   // k_affine_begin: the table at the start of a tracki
     int n_seq;
 };
 void launch_affine_begin(const AffineBeginArgs& a, hipStream_t s);
-// the compensated twins of launch_track_gn / launch_gn_solve (launch pairs only, no mask); r.table == nullptr: no robust weights
-void launch_track_gn_ab(const struct GnArgs& a, const RobustGn& r, const AffineGn& f, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                        int grid_seqs = 0);
-void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s);
 
 // The geometric (depth) term of a sensor-depth batch (dvo_batch_set_geometric).  While on, GnArgs::ref_depth / ref_wgt /
 // wgt_const hold the TRACKED frame's own maps and the reference's depth is sampled at the warped position: its base comes in this
@@ -317,13 +306,6 @@ struct GeoSolve {      // last argument of k_gn_solve_z
     double* sums_out;     // optional [n_seq][2] (dvo_op_gn_step_geometric): (n_geo, S29) in double
     int levels, log_its;
 };
-// the twins of launch_track_gn / launch_gn_solve with the geometric term (launch pairs only, no mask)
-void launch_track_gn_z(const struct GnArgs& a, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
-void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s);
-// both terms together (dvo_batch_set_geometric_affine): k_track_gn_zab / k_gn_solve_zab, no robust weights
-void launch_track_gn_zab(const struct GnArgs& a, const AffineGn& f, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                         int grid_seqs = 0);
-void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s);
 
 // Step control: damped Gauss-Newton with step acceptance (dvo_batch_set_step_control; the contract is in include/dvo.h).
 // One dvo_lm_entry per sequence: the accepted pose, its sums and lambda.  The tile kernel is the plain k_track_gn; only the solve
@@ -343,8 +325,6 @@ struct LmBeginArgs {   // k_lm_begin: the table and the records at the start of 
     int n_seq;
 };
 void launch_lm_begin(const LmBeginArgs& a, hipStream_t s);
-// the twin of launch_gn_solve with step control (launch pairs only; its tile launch is launch_track_gn)
-void launch_gn_solve_lm(const SolveArgs& a, const LmSolve& m, int n_seq, hipStream_t s);
 // dvo_op_lm_step: k_gn_solve_lm's serial tail on given sums, one case per thread.  a.state: [n] scratch SeqState, set up by the kernel
 // from xi_eval (Tc = exp(xi), pose = float(exp(-xi)), iter = it_prev); m.table: the entries, updated in place.
 void launch_lm_step(const SolveArgs& a, const LmSolve& m, const double* sums, const float* xi_eval, int n, int it_prev, hipStream_t s);
@@ -928,6 +908,17 @@ inline void gn_tile_geometry(int w, int h, int ppt, int& tiles_x, int& tiles_y)
     tiles_y = (h + 4 * ppt - 1) / (4 * ppt);
 }
 void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s);
+// The opt-in terms of a launch pair.  `on` is the set of Term bits that are on -- robust weights count as
+// TERM_ROBUST with the adaptive or a given scale and as TERM_MEDIAN with the median scale -- and the block of every term that is on is
+// filled (the median scale fills rob as well; every other block stays value-initialised: rob.table == nullptr is "no robust weights"
+// to the affine kernels).  The two launchers hold the table "set of terms -> kernel pair" once each: nothing on and TERM_STEP_CONTROL
+// run the plain tile kernel (launch_track_gn: the mask stays), every other pair has no mask; false, and nothing launched, for a set
+// without a kernel pair (Tracker::refusal lets none through).
+enum Term : unsigned { TERM_ROBUST = 1, TERM_MEDIAN = 2, TERM_AFFINE = 4, TERM_GEOMETRIC = 8, TERM_STEP_CONTROL = 16 };
+struct TileTerms  { unsigned on; RobustGn rob; MedianGn med; AffineGn aff; GeoGn geo; };
+struct SolveTerms { unsigned on; RobustSolve rob; MedianSolve med; AffineSolve aff; GeoSolve geo; LmSolve lm; };
+bool launch_track_gn_terms(const GnArgs& a, const TileTerms& t, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs = 0);
+bool launch_gn_solve_terms(const SolveArgs& a, const SolveTerms& t, int n_seq, hipStream_t s);
 // one Tracker::track iteration in one launch for a few sequences (k_track_gn_fused); false = no instance for (ppt, group)
 bool launch_track_gn_fused(const GnArgs& a, const SolveArgs& sa, int n_seq, int ppt, int group, bool t2d, int* ticket, int* report,
                            int* progress, hipStream_t s);

@@ -1932,10 +1932,20 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve(SolveArgs a)
     (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
 }
 
+// SolveLane: what the serial lane holds when solve_gather returns true -- its sequence and that sequence's iteration count, twist and
+// exp(+xi) as the state held them before this solve.  (The __shared__ rows stay in the kernels: _md and the _ab kernels add their own.)
+struct SolveLane {
+    int seq = 0, it_prev = 0;
+    float xi[6] = {0, 0, 0, 0, 0, 0};
+    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+// The slot of the track log a solve writes, and with it the slot of every term's own log
+__device__ __forceinline__ int term_log_slot(const SolveArgs& a, const SolveLane& ln) { return a.ignore_active ? 0 : ln.it_prev; }
+
 // solve_gather: everything of a solve kernel up to its serial tail, shared by k_gn_solve_rw, _ab and _z: the progress
 // word, the serial lanes' state loads, the second reduction stage of slots 0 .. NSUM-1 into tot (wide form for one or two sequences,
 // one team per sequence otherwise; slots NSUM .. 31 are exact zeros) and the barrier.  True for a lane that goes on to solve_finish:
-// lanes 0..7 of wave 0, one live sequence each; my_seq, it_prev, xi and Tc are that sequence's.  Every other lane is done.
+// lanes 0..7 of wave 0, one live sequence each; ln is that sequence's.  Every other lane is done.
 //   pre(seq):               a term's own load beside the serial lane's state loads (all requests go out up front)
 //   mid(t_slot, c, team):   a term's own sums ahead of the barrier
 // k_gn_solve is this function written out with NSUM = 29 and no callbacks, on purpose: its serial chain is the latency of every
@@ -1943,24 +1953,24 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve(SolveArgs a)
 // returns move).  A change to the summation order or to the state loads is made here AND there; tools/isa_compare.py shows whether
 // k_gn_solve moved.
 template <int NSUM, class Pre, class Mid>
-__device__ __forceinline__ bool solve_gather(const SolveArgs& a, double (*tot)[32], double (*part)[DVO_SOLVE_GROUPS][32], int& my_seq,
-                                             int& it_prev, float (&xi)[6], double (&Tc)[12], Pre&& pre, Mid&& mid)
+__device__ __forceinline__ bool solve_gather(const SolveArgs& a, double (*tot)[32], double (*part)[DVO_SOLVE_GROUPS][32], SolveLane& ln,
+                                             Pre&& pre, Mid&& mid)
 {
     const int n_in = a.list_in ? a.list_in[0] : a.n_seq;
     if (a.progress && blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_store(a.progress, n_in + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if ((int)blockIdx.x * DVO_SOLVE_SEQ >= n_in) return false;
     const int my_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + (int)threadIdx.x;
     const bool serial = threadIdx.x < DVO_SOLVE_SEQ && my_slot < n_in;
-    if (serial) my_seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
-    const SeqState& st = a.state[my_seq];
+    if (serial) ln.seq = a.list_in ? a.list_in[4 + my_slot] : my_slot;
+    const SeqState& st = a.state[ln.seq];
     int was_active = 0;
     if (serial) {
-        was_active = st.active; it_prev = st.iter;
+        was_active = st.active; ln.it_prev = st.iter;
 #pragma unroll
-        for (int i = 0; i < 6; i++) xi[i] = st.xi[i];
+        for (int i = 0; i < 6; i++) ln.xi[i] = st.xi[i];
 #pragma unroll
-        for (int i = 0; i < 12; i++) Tc[i] = st.Tc[i];
-        pre(my_seq);
+        for (int i = 0; i < 12; i++) ln.Tc[i] = st.Tc[i];
+        pre(ln.seq);
     }
     const int c = threadIdx.x & 31, team = threadIdx.x >> 5;
     const int t_slot = (int)blockIdx.x * DVO_SOLVE_SEQ + team;
@@ -2003,21 +2013,25 @@ __device__ __forceinline__ void robust_solve_update(const RobustSolve& rs, const
     }
 }
 
+// The serial lane's solve_finish on its own row of tot (every term's solve kernel)
+__device__ __forceinline__ void lane_solve_finish(const SolveArgs& a, SolveLane& ln, const double* t)
+{
+    Pose np;
+    (void)solve_finish(a, ln.seq, a.state[ln.seq], t, a.ignore_active, ln.it_prev, ln.xi, ln.Tc, np);
+}
+
 // k_gn_solve_rw: k_gn_solve for a batch with robust residual weights: solve_gather, solve_finish, and the sequence's RobustEntry
 // (robust_solve_update) with the s2 that was read beside the state.
 __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_rw(SolveArgs a, RobustSolve rs)
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    SolveLane ln;
     float used_s2 = 0.0f;
-    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [&](int seq) { used_s2 = rs.table[seq].s2; }, [](int, int, int) {})) return;
-    Pose np;
+    if (!solve_gather<29>(a, tot, part, ln, [&](int seq) { used_s2 = rs.table[seq].s2; }, [](int, int, int) {})) return;
     const double* t = tot[threadIdx.x];
-    (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
-    robust_solve_update(rs, my_seq, used_s2, t);
+    lane_solve_finish(a, ln, t);
+    robust_solve_update(rs, ln.seq, used_s2, t);
 }
 
 // k_robust_begin: the RobustEntry table at the start of a tracking call, one thread per sequence.  Adaptive scale: every sequence starts
@@ -2050,9 +2064,7 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_md(SolveArgs a,
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
     __shared__ int sel[DVO_SOLVE_SEQ][2];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    SolveLane ln;
     float used_s2 = 0.0f;
     const auto select = [&](int t_slot, int c, int team) {
         const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
@@ -2091,11 +2103,11 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_md(SolveArgs a,
         }
         if (c == 0) { sel[team][0] = n != 0u ? m : -1; sel[team][1] = (int)n; }
     };
-    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [&](int seq) { used_s2 = rs.table[seq].s2; }, select)) return;
+    if (!solve_gather<29>(a, tot, part, ln, [&](int seq) { used_s2 = rs.table[seq].s2; }, select)) return;
+    const int my_seq = ln.seq;
     const double* t = tot[threadIdx.x];
     if (!ms.prime) {
-        Pose np;
-        (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
+        lane_solve_finish(a, ln, t);
         robust_solve_update(rs, my_seq, used_s2, t);   // (rs.adaptive = 0: last_s2 only)
     }
     const int m = sel[threadIdx.x][0], n = sel[threadIdx.x][1];
@@ -2105,7 +2117,7 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_md(SolveArgs a,
         ms.prime_mn[2 * my_seq] = m; ms.prime_mn[2 * my_seq + 1] = n;
         return;
     }
-    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    const int it = term_log_slot(a, ln);
     if (ms.log && it < ms.log_its) {
         int* lg = ms.log + (((size_t)my_seq * ms.levels + a.level) * ms.log_its + it) * 3;
         lg[0] = __float_as_int(used_s2); lg[1] = m; lg[2] = n;
@@ -2137,81 +2149,89 @@ __device__ __forceinline__ void affine_next_entry(const AffineSolve& f, const in
     }
 }
 
-// k_gn_solve_ab: k_gn_solve_rw for a batch with affine brightness compensation: solve_gather, and the serial thread also keeps the
-// sequence's AffineEntry: it records the entry this iteration's k_track_gn_ab used (last, and the affine log at the iteration's slot
-// of the track log) and, in ESTIMATE mode, writes the next launch's entry from this iteration's moments, which team lanes 0..7 sum in
-// double in the order of the 29 sums.  f.prime: the priming pair -- the entry and prime_ab only.  The RobustEntry is kept exactly as
-// k_gn_solve_rw keeps it when robust weights are on too (f.robust).
+// The brightness moments of team `team`'s sequence, ahead of solve_gather's barrier (its `mid`): lanes 0..7 of the team sum them in
+// double in the order of the 29 sums (every schedule: the order of sum_partial_rows).
+__device__ __forceinline__ void affine_sum_moments(const SolveArgs& a, const AffineSolve& f, double (*mtot)[8], const int t_slot, const int c,
+                                                   const int team)
+{
+    if (c < 8) {
+        const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
+        mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
+    }
+}
+
+// Affine upkeep of one sequence and iteration by its serial lane, after solve_finish: records the entry this iteration's tile kernel
+// used (last, and the affine log at slot `it`) and, in ESTIMATE mode, writes the next launch's entry from this iteration's moments m.
+// N: m[0] with robust weights, else n_valid.  True for the priming pair (f.prime): the entry and prime_ab only, and the caller is done.
+__device__ __forceinline__ bool affine_solve_update(const AffineSolve& f, const SolveArgs& a, const int seq, const int it, const int n_valid,
+                                                    const double N, const double* m)
+{
+    const AffineEntry used = f.table[seq];
+    AffineEntry next = used;
+    if (f.estimate) affine_next_entry(f, n_valid, N, m, next);
+    if (f.moments_out) {
+        double* mo = f.moments_out + (size_t)seq * DVO_AFFINE_MOMENTS;
+        mo[0] = N;
+        for (int i = 1; i < DVO_AFFINE_MOMENTS; i++) mo[i] = m[i];
+    }
+    if (f.estimate) f.table[seq] = next;
+    if (f.prime) {
+        f.prime_ab[2 * seq] = next.a; f.prime_ab[2 * seq + 1] = next.b;
+        return true;
+    }
+    if (f.log && it < f.log_its) {
+        float* lg = f.log + (((size_t)seq * f.levels + a.level) * f.log_its + it) * 2;
+        lg[0] = used.a; lg[1] = used.b;
+    }
+    f.last[2 * seq] = used.a; f.last[2 * seq + 1] = used.b;
+    return false;
+}
+
+// Geometric record of one sequence and iteration by its serial lane, after solve_finish: slots 29 (sum rg^2) and 30 (n_geo) of its sums
+// t go to sums_out, to the geometric log at slot `it` and to last.
+__device__ __forceinline__ void geo_solve_record(const GeoSolve& z, const SolveArgs& a, const int seq, const int it, const double* t)
+{
+    const double S29 = t[29], n_geo = t[30];
+    if (z.sums_out) { z.sums_out[2 * (size_t)seq] = n_geo; z.sums_out[2 * (size_t)seq + 1] = S29; }
+    if (z.log && it < z.log_its) {
+        float* lg = z.log + (((size_t)seq * z.levels + a.level) * z.log_its + it) * 2;
+        lg[0] = (float)n_geo; lg[1] = (float)S29;
+    }
+    float* last = z.last + 4 * (size_t)seq;   // (n_geo, mean_sq, 1 = tracked, 0)
+    last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
+}
+
+// k_gn_solve_ab: k_gn_solve_rw for a batch with affine brightness compensation: solve_gather with the moments in mid, solve_finish,
+// then the sequence's AffineEntry (affine_solve_update).  The pose first, the brightness entry after it: nothing of the closed form is
+// live across the serial chain of solve_finish.  f.prime: the priming pair -- the entry and prime_ab only.  The RobustEntry is kept
+// exactly as k_gn_solve_rw keeps it when robust weights are on too (f.robust).
 __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_ab(SolveArgs a, RobustSolve rs, AffineSolve f)
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
     __shared__ double mtot[DVO_SOLVE_SEQ][8];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const auto sum_moments = [&](int t_slot, int c, int team) {   // the moments of the team's sequence (every schedule: the order of sum_partial_rows)
-        if (c < 8) {
-            const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
-            mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
-        }
-    };
-    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, sum_moments)) return;
-    SeqState& st = a.state[my_seq];
-    // (the pose first, the brightness entry after it: nothing of the closed form is live across the serial chain of solve_finish)
-    if (!f.prime) {
-        Pose np;
-        (void)solve_finish(a, my_seq, st, tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
-    }
+    SolveLane ln;
+    if (!solve_gather<29>(a, tot, part, ln, [](int) {}, [&](int t_slot, int c, int team) { affine_sum_moments(a, f, mtot, t_slot, c, team); })) return;
     const double* t = tot[threadIdx.x];
+    if (!f.prime) lane_solve_finish(a, ln, t);
     const double* m = mtot[threadIdx.x];
     const int n_valid = (int)t[28];
-    const double N = f.robust ? m[0] : (double)n_valid;
-    const AffineEntry used = f.table[my_seq];
-    AffineEntry next = used;
-    if (f.estimate) affine_next_entry(f, n_valid, N, m, next);
-    if (f.moments_out) {
-        double* mo = f.moments_out + (size_t)my_seq * DVO_AFFINE_MOMENTS;
-        mo[0] = N;
-        for (int i = 1; i < DVO_AFFINE_MOMENTS; i++) mo[i] = m[i];
-    }
-    if (f.estimate) f.table[my_seq] = next;
-    if (f.prime) {
-        f.prime_ab[2 * my_seq] = next.a; f.prime_ab[2 * my_seq + 1] = next.b;
-        return;
-    }
-    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
-    if (f.log && it < f.log_its) {
-        float* lg = f.log + (((size_t)my_seq * f.levels + a.level) * f.log_its + it) * 2;
-        lg[0] = used.a; lg[1] = used.b;
-    }
-    f.last[2 * my_seq] = used.a; f.last[2 * my_seq + 1] = used.b;
-    if (f.robust) robust_solve_update(rs, my_seq, rs.table[my_seq].s2, t);
+    if (affine_solve_update(f, a, ln.seq, term_log_slot(a, ln), n_valid, f.robust ? m[0] : (double)n_valid, m)) return;
+    if (f.robust) robust_solve_update(rs, ln.seq, rs.table[ln.seq].s2, t);
 }
 
 // k_gn_solve_z: k_gn_solve for a sensor-depth batch with the geometric term: solve_gather sums slots 29 (sum rg^2) and 30 (n_geo) of
-// the partial rows beside the 29 in the same fixed order; the serial thread records them (last, and the geometric log at the
-// iteration's slot of the track log).  solve_finish reads slots 0..28 only: it solves the combined H and g, and n_valid, the residual
-// and the stop tests stay photometric.
+// the partial rows beside the 29 in the same fixed order; the serial thread records them (geo_solve_record).  solve_finish reads slots
+// 0..28 only: it solves the combined H and g, and n_valid, the residual and the stop tests stay photometric.
 __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_z(SolveArgs a, GeoSolve z)
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!solve_gather<31>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, [](int, int, int) {})) return;
-    Pose np;
-    (void)solve_finish(a, my_seq, a.state[my_seq], tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc, np);
-    const double S29 = tot[threadIdx.x][29], n_geo = tot[threadIdx.x][30];
-    if (z.sums_out) { z.sums_out[2 * (size_t)my_seq] = n_geo; z.sums_out[2 * (size_t)my_seq + 1] = S29; }
-    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
-    if (z.log && it < z.log_its) {
-        float* lg = z.log + (((size_t)my_seq * z.levels + a.level) * z.log_its + it) * 2;
-        lg[0] = (float)n_geo; lg[1] = (float)S29;
-    }
-    float* last = z.last + 4 * (size_t)my_seq;   // (n_geo, mean_sq, 1 = tracked, 0)
-    last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
+    SolveLane ln;
+    if (!solve_gather<31>(a, tot, part, ln, [](int) {}, [](int, int, int) {})) return;
+    const double* t = tot[threadIdx.x];
+    lane_solve_finish(a, ln, t);
+    geo_solve_record(z, a, ln.seq, term_log_slot(a, ln), t);
 }
 
 // k_gn_solve_zab: k_gn_solve_z for a batch that also compensates brightness (k_track_gn_zab's partner): solve_gather sums the 31 slots
@@ -2223,51 +2243,16 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_zab(SolveArgs a
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
     __shared__ double mtot[DVO_SOLVE_SEQ][8];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    const auto sum_moments = [&](int t_slot, int c, int team) {   // k_gn_solve_ab's
-        if (c < 8) {
-            const int t_seq = a.list_in ? a.list_in[4 + t_slot] : t_slot;
-            mtot[team][c] = sum_partial_rows<8>(f.moments + (size_t)t_seq * a.nblk * 8 + c, a.nblk, a.blk_first, a.blk_count);
-        }
-    };
-    if (!solve_gather<31>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, sum_moments)) return;
+    SolveLane ln;
+    if (!solve_gather<31>(a, tot, part, ln, [](int) {}, [&](int t_slot, int c, int team) { affine_sum_moments(a, f, mtot, t_slot, c, team); })) return;
     const double* t = tot[threadIdx.x];
-    const int it = a.ignore_active ? 0 : it_prev;   // solve_finish's slot of the track log
+    const int it = term_log_slot(a, ln);
     if (!f.prime) {
-        Pose np;
-        (void)solve_finish(a, my_seq, a.state[my_seq], t, a.ignore_active, it_prev, xi, Tc, np);
-        const double S29 = t[29], n_geo = t[30];
-        if (z.sums_out) { z.sums_out[2 * (size_t)my_seq] = n_geo; z.sums_out[2 * (size_t)my_seq + 1] = S29; }
-        if (z.log && it < z.log_its) {
-            float* lg = z.log + (((size_t)my_seq * z.levels + a.level) * z.log_its + it) * 2;
-            lg[0] = (float)n_geo; lg[1] = (float)S29;
-        }
-        float* last = z.last + 4 * (size_t)my_seq;   // (n_geo, mean_sq, 1 = tracked, 0)
-        last[0] = (float)n_geo; last[1] = n_geo > 0.0 ? (float)(S29 / n_geo) : 0.0f; last[2] = 1.0f;
+        lane_solve_finish(a, ln, t);
+        geo_solve_record(z, a, ln.seq, it, t);
     }
-    const double* m = mtot[threadIdx.x];
     const int n_valid = (int)t[28];
-    const double N = (double)n_valid;
-    const AffineEntry used = f.table[my_seq];
-    AffineEntry next = used;
-    if (f.estimate) affine_next_entry(f, n_valid, N, m, next);
-    if (f.moments_out) {
-        double* mo = f.moments_out + (size_t)my_seq * DVO_AFFINE_MOMENTS;
-        mo[0] = N;
-        for (int i = 1; i < DVO_AFFINE_MOMENTS; i++) mo[i] = m[i];
-    }
-    if (f.estimate) f.table[my_seq] = next;
-    if (f.prime) {
-        f.prime_ab[2 * my_seq] = next.a; f.prime_ab[2 * my_seq + 1] = next.b;
-        return;
-    }
-    if (f.log && it < f.log_its) {
-        float* lg = f.log + (((size_t)my_seq * f.levels + a.level) * f.log_its + it) * 2;
-        lg[0] = used.a; lg[1] = used.b;
-    }
-    f.last[2 * my_seq] = used.a; f.last[2 * my_seq + 1] = used.b;
+    (void)affine_solve_update(f, a, ln.seq, it, n_valid, (double)n_valid, mtot[threadIdx.x]);
 }
 
 // k_affine_begin: the AffineEntry table at the start of a tracking call, one thread per sequence.  ESTIMATE: every sequence starts at
@@ -2280,6 +2265,44 @@ __global__ void __launch_bounds__(256) k_affine_begin(AffineBeginArgs a)
     a.table[i] = a.rows ? affine_entry(a.rows[2 * i], a.rows[2 * i + 1]) : affine_entry(a.a_all, a.b_all);
     a.last[2 * i] = 0.0f; a.last[2 * i + 1] = 0.0f;
     a.prime_ab[2 * i] = 0.0f; a.prime_ab[2 * i + 1] = 0.0f;
+}
+
+// What solve_finish and lm_solve_finish share.  The iteration's row of the track log:
+__device__ __forceinline__ void track_log_write(const SolveArgs& a, const int seq, const int it, const float residual, const double nrm,
+                                                const int n_valid, const float* xi, const float* upd)
+{
+    if (a.log && it < DVO_MAX_ITERATIONS) {
+        dvo_track_log& lg = a.log[seq];
+        lg.n_iter[a.level] = it + 1;
+        lg.residual[a.level][it] = residual;
+        lg.update_norm[a.level][it] = (float)nrm;
+        lg.n_valid[a.level][it] = n_valid;
+#pragma unroll
+        for (int i = 0; i < 6; i++) lg.xi_after[a.level][it][i] = xi[i];
+#pragma unroll
+        for (int i = 0; i < 6; i++) lg.xi_update[a.level][it][i] = upd[i];
+    }
+}
+// The stop test of iteration `it`: the new active flag
+__device__ __forceinline__ int solve_stays_active(const SolveArgs& a, const int it, const double nrm, const float residual)
+{
+    int active = 1;
+    if (a.fixed_iterations > 0) {
+        active = (it + 1 < a.fixed_iterations) ? 1 : 0;
+    } else if (nrm < (double)a.min_update || residual < a.min_residual || it + 1 >= a.max_iterations) {
+        active = 0;  // tracker.cpp:68-73 (the wall-clock term is disabled, D1)
+    }
+    return active;
+}
+// The end of a sequence's solve: its active flag, its slot on the next launch's list, the profile counters
+__device__ __forceinline__ void solve_epilogue(const SolveArgs& a, const int seq, SeqState& st, const int active)
+{
+    st.active = active;
+    if (active && a.list_out) a.list_out[4 + atomicAdd(&a.list_out[0], 1)] = seq;
+    if (a.counters) {  // profile: evaluated pixels / sequence-iterations
+        atomicAdd(&a.counters[0], (unsigned long long)a.level_pixels);
+        atomicAdd(&a.counters[1], 1ull);
+    }
 }
 
 // The serial part of one Tracker::track iteration (tracker.cpp:44-73) for one sequence, run by ONE thread: 6x6 solve,
@@ -2313,17 +2336,7 @@ __device__ __forceinline__ int solve_finish(const SolveArgs& a, const int seq, S
     nrm = sqrt(nrm);
 
     const int it = first ? 0 : it_prev;
-    if (a.log && it < DVO_MAX_ITERATIONS) {
-        dvo_track_log& lg = a.log[seq];
-        lg.n_iter[a.level] = it + 1;
-        lg.residual[a.level][it] = residual;
-        lg.update_norm[a.level][it] = (float)nrm;
-        lg.n_valid[a.level][it] = n_valid;
-#pragma unroll
-        for (int i = 0; i < 6; i++) lg.xi_after[a.level][it][i] = xi[i];
-#pragma unroll
-        for (int i = 0; i < 6; i++) lg.xi_update[a.level][it][i] = upd[i];
-    }
+    track_log_write(a, seq, it, residual, nrm, n_valid, xi, upd);
     if (a.result) {  // operator-level output (dvo_op_gn_step)
         dvo_gn_result& r = a.result[seq];
         for (int i = 0; i < 21; i++) r.H[i] = tot[i];
@@ -2333,18 +2346,8 @@ __device__ __forceinline__ int solve_finish(const SolveArgs& a, const int seq, S
         r.residual = residual;
     }
     st.iter = it + 1;
-    int active = 1;
-    if (a.fixed_iterations > 0) {
-        active = (it + 1 < a.fixed_iterations) ? 1 : 0;
-    } else if (nrm < (double)a.min_update || residual < a.min_residual || it + 1 >= a.max_iterations) {
-        active = 0;  // tracker.cpp:68-73 (the wall-clock term is disabled, D1)
-    }
-    st.active = active;
-    if (active && a.list_out) a.list_out[4 + atomicAdd(&a.list_out[0], 1)] = seq;
-    if (a.counters) {  // profile: evaluated pixels / sequence-iterations
-        atomicAdd(&a.counters[0], (unsigned long long)a.level_pixels);
-        atomicAdd(&a.counters[1], 1ull);
-    }
+    const int active = solve_stays_active(a, it, nrm, residual);
+    solve_epilogue(a, seq, st, active);
     return active | (updated ? 2 : 0);
 }
 
@@ -3134,12 +3137,7 @@ __device__ __forceinline__ void lm_solve_finish(const SolveArgs& a, const LmSolv
     for (int i = 0; i < 6; i++) nrm += (double)upd[i] * (double)upd[i];
     nrm = sqrt(nrm);
     const int it = first ? 0 : it_prev;
-    int active = 1;
-    if (a.fixed_iterations > 0) {
-        active = (it + 1 < a.fixed_iterations) ? 1 : 0;
-    } else if (nrm < (double)a.min_update || res_acc < a.min_residual || it + 1 >= a.max_iterations) {
-        active = 0;
-    }
+    int active = solve_stays_active(a, it, nrm, res_acc);
     if (!updated || !(nrm < __builtin_inf())) active = 0;   // a non-finite update ends the level
     if (active) {
 #pragma unroll
@@ -3157,17 +3155,7 @@ __device__ __forceinline__ void lm_solve_finish(const SolveArgs& a, const LmSolv
 #pragma unroll
         for (int i = 0; i < 3; i++) st.pose.t[i] = e.pose[9 + i];
     }
-    if (a.log && it < DVO_MAX_ITERATIONS) {
-        dvo_track_log& lg = a.log[seq];
-        lg.n_iter[a.level] = it + 1;
-        lg.residual[a.level][it] = residual;
-        lg.update_norm[a.level][it] = (float)nrm;
-        lg.n_valid[a.level][it] = n_valid;
-#pragma unroll
-        for (int i = 0; i < 6; i++) lg.xi_after[a.level][it][i] = xi[i];
-#pragma unroll
-        for (int i = 0; i < 6; i++) lg.xi_update[a.level][it][i] = upd[i];
-    }
+    track_log_write(a, seq, it, residual, nrm, n_valid, xi, upd);
     if (a.result) {
         dvo_gn_result& r = a.result[seq];
         for (int i = 0; i < 6; i++) { r.xi_update[i] = upd[i]; r.xi_next[i] = xi[i]; }
@@ -3188,12 +3176,7 @@ __device__ __forceinline__ void lm_solve_finish(const SolveArgs& a, const LmSolv
     }
     if (lm.decision_out) lm.decision_out[seq] = decision;
     st.iter = it + 1;
-    st.active = active;
-    if (active && a.list_out) a.list_out[4 + atomicAdd(&a.list_out[0], 1)] = seq;
-    if (a.counters) {  // profile: evaluated pixels / sequence-iterations
-        atomicAdd(&a.counters[0], (unsigned long long)a.level_pixels);
-        atomicAdd(&a.counters[1], 1ull);
-    }
+    solve_epilogue(a, seq, st, active);
 }
 
 // k_gn_solve_lm: k_gn_solve for a batch with step control: solve_gather, then lm_solve_finish.
@@ -3201,11 +3184,9 @@ __global__ void __launch_bounds__(32 * DVO_SOLVE_SEQ) k_gn_solve_lm(SolveArgs a,
 {
     __shared__ double tot[DVO_SOLVE_SEQ][32];
     __shared__ double part[2][DVO_SOLVE_GROUPS][32];
-    int my_seq = 0, it_prev = 0;
-    float xi[6] = {0, 0, 0, 0, 0, 0};
-    double Tc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    if (!solve_gather<29>(a, tot, part, my_seq, it_prev, xi, Tc, [](int) {}, [](int, int, int) {})) return;
-    lm_solve_finish(a, lm, my_seq, a.state[my_seq], tot[threadIdx.x], a.ignore_active, it_prev, xi, Tc);
+    SolveLane ln;
+    if (!solve_gather<29>(a, tot, part, ln, [](int) {}, [](int, int, int) {})) return;
+    lm_solve_finish(a, lm, ln.seq, a.state[ln.seq], tot[threadIdx.x], a.ignore_active, ln.it_prev, ln.xi, ln.Tc);
 }
 
 // k_lm_begin: the entry table and the records at the start of a tracking call, one thread per sequence: lambda = lambda0, nothing
@@ -3674,86 +3655,67 @@ void launch_track_gn(const GnArgs& a0, int n_seq, int ppt, int group, bool t2d, 
     });
 }
 
+// One tile launch of an opt-in term.  pair(p, g, tiles_2d, cam) is the term's kernel instance for the (ppt, group) pair, the 2-D tiles
+// flag (PPT = 4 only) and the per-sequence intrinsics (_cam); blocks: the term's argument blocks, forwarded behind GnArgs.
 // (the opt-in tile kernels have no MASK instances: a.mask = nullptr)
-void launch_track_gn_rw(const GnArgs& a0, const RobustGn& r, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
+template <class Pair, class... Blocks>
+static void launch_term_tiles(const GnArgs& a0, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs, Pair&& pair,
+                              const Blocks&... blocks)
 {
     GnArgs a = a0;
     a.n_seq = n_seq; a.mask = nullptr;
     const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
     with_gn_shape(ppt, group, [&](auto p, auto g) {
-        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
+        constexpr int PPT = decltype(p)::value;
         with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_rw_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
-            else hipLaunchKernelGGL((k_track_gn_rw<PPT, G, T2D>), grid, dim3(256), 0, s, a, r);
+            constexpr std::bool_constant<PPT == 4 && decltype(tiles_2d)::value> t2d_c{};
+            hipLaunchKernelGGL(pair(p, g, t2d_c, a.seq_k != nullptr), grid, dim3(256), 0, s, a, blocks...);
         });
     });
 }
 
-void launch_track_gn_md(const GnArgs& a0, const RobustGn& r, const MedianGn& m, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                        int grid_seqs)
+// The table "set of terms -> tile kernel pair" (the solve side's is launch_gn_solve_terms)
+bool launch_track_gn_terms(const GnArgs& a, const TileTerms& t, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
 {
-    GnArgs a = a0;
-    a.n_seq = n_seq; a.mask = nullptr;
-    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
-    with_gn_shape(ppt, group, [&](auto p, auto g) {
-        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
-        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_md_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, r, m);
-            else hipLaunchKernelGGL((k_track_gn_md<PPT, G, T2D>), grid, dim3(256), 0, s, a, r, m);
+    const auto tiles = [&](auto&& pair, const auto&... blocks) {
+        launch_term_tiles(a, n_seq, ppt, group, t2d, s, grid_seqs, pair, blocks...);
+        return true;
+    };
+    // (a pair: the instance of a term's kernel and of its _cam twin, from the constants with_gn_shape and with_flag pass)
+    switch (t.on) {
+    case 0:
+    case TERM_STEP_CONTROL: launch_track_gn(a, n_seq, ppt, group, t2d, s, grid_seqs); return true;   // (only the solve differs)
+    case TERM_ROBUST:
+        return tiles([](auto p, auto g, auto t2, bool cam) {
+            constexpr int P = p, G = g; constexpr bool T = t2;
+            return cam ? k_track_gn_rw_cam<P, G, T> : k_track_gn_rw<P, G, T>;
+        }, t.rob);
+    case TERM_MEDIAN:
+        return tiles([](auto p, auto g, auto t2, bool cam) {
+            constexpr int P = p, G = g; constexpr bool T = t2;
+            return cam ? k_track_gn_md_cam<P, G, T> : k_track_gn_md<P, G, T>;
+        }, t.rob, t.med);
+    case TERM_AFFINE:
+    case TERM_ROBUST | TERM_AFFINE:
+        with_flag(t.rob.table != nullptr, [&](auto robust) {
+            tiles([](auto p, auto g, auto t2, bool cam) {
+                constexpr int P = p, G = g; constexpr bool T = t2, ROB = decltype(robust)::value;
+                return cam ? k_track_gn_ab_cam<P, G, T, ROB> : k_track_gn_ab<P, G, T, ROB>;
+            }, t.rob, t.aff);
         });
-    });
-}
-
-void launch_track_gn_ab(const GnArgs& a0, const RobustGn& r, const AffineGn& f, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                        int grid_seqs)
-{
-    GnArgs a = a0;
-    a.n_seq = n_seq; a.mask = nullptr;
-    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
-    with_gn_shape(ppt, group, [&](auto p, auto g) {
-        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
-        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-            with_flag(r.table != nullptr, [&](auto robust) {
-                constexpr bool ROB = decltype(robust)::value;
-                if (a.seq_k) hipLaunchKernelGGL((k_track_gn_ab_cam<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
-                else hipLaunchKernelGGL((k_track_gn_ab<PPT, G, T2D, ROB>), grid, dim3(256), 0, s, a, r, f);
-            });
-        });
-    });
-}
-
-void launch_track_gn_z(const GnArgs& a0, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s, int grid_seqs)
-{
-    GnArgs a = a0;
-    a.n_seq = n_seq; a.mask = nullptr;
-    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
-    with_gn_shape(ppt, group, [&](auto p, auto g) {
-        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
-        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_z_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
-            else hipLaunchKernelGGL((k_track_gn_z<PPT, G, T2D>), grid, dim3(256), 0, s, a, z);
-        });
-    });
-}
-
-void launch_track_gn_zab(const GnArgs& a0, const AffineGn& f, const GeoGn& z, int n_seq, int ppt, int group, bool t2d, hipStream_t s,
-                         int grid_seqs)
-{
-    GnArgs a = a0;
-    a.n_seq = n_seq; a.mask = nullptr;
-    const dim3 grid = gn_tile_grid(a, n_seq, grid_seqs);
-    with_gn_shape(ppt, group, [&](auto p, auto g) {
-        constexpr int PPT = decltype(p)::value, G = decltype(g)::value;
-        with_flag(PPT == 4 && t2d, [&](auto tiles_2d) {
-            constexpr bool T2D = PPT == 4 && decltype(tiles_2d)::value;
-            if (a.seq_k) hipLaunchKernelGGL((k_track_gn_zab_cam<PPT, G, T2D>), grid, dim3(256), 0, s, a, f, z);
-            else hipLaunchKernelGGL((k_track_gn_zab<PPT, G, T2D>), grid, dim3(256), 0, s, a, f, z);
-        });
-    });
+        return true;
+    case TERM_GEOMETRIC:
+        return tiles([](auto p, auto g, auto t2, bool cam) {
+            constexpr int P = p, G = g; constexpr bool T = t2;
+            return cam ? k_track_gn_z_cam<P, G, T> : k_track_gn_z<P, G, T>;
+        }, t.geo);
+    case TERM_GEOMETRIC | TERM_AFFINE:
+        return tiles([](auto p, auto g, auto t2, bool cam) {
+            constexpr int P = p, G = g; constexpr bool T = t2;
+            return cam ? k_track_gn_zab_cam<P, G, T> : k_track_gn_zab<P, G, T>;
+        }, t.aff, t.geo);
+    default: return false;
+    }
 }
 
 // A solve kernel (k_gn_solve or an opt-in term's) over n_seq sequences, DVO_SOLVE_SEQ per workgroup; extra: the term's argument blocks
@@ -3766,20 +3728,21 @@ static void launch_solve_kernel(K kernel, const SolveArgs& a, int n_seq, hipStre
 }
 
 void launch_gn_solve(const SolveArgs& a, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve, a, n_seq, s); }
-void launch_gn_solve_rw(const SolveArgs& a, const RobustSolve& r, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_rw, a, n_seq, s, r); }
-void launch_gn_solve_ab(const SolveArgs& a, const RobustSolve& r, const AffineSolve& f, int n_seq, hipStream_t s)
-{
-    launch_solve_kernel(k_gn_solve_ab, a, n_seq, s, r, f);
-}
-void launch_gn_solve_z(const SolveArgs& a, const GeoSolve& z, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_z, a, n_seq, s, z); }
-void launch_gn_solve_zab(const SolveArgs& a, const AffineSolve& f, const GeoSolve& z, int n_seq, hipStream_t s)
-{
-    launch_solve_kernel(k_gn_solve_zab, a, n_seq, s, f, z);
-}
 
-void launch_gn_solve_md(const SolveArgs& a, const RobustSolve& r, const MedianSolve& m, int n_seq, hipStream_t s)
+// The table "set of terms -> solve kernel" (launch_track_gn_terms's partner)
+bool launch_gn_solve_terms(const SolveArgs& a, const SolveTerms& t, int n_seq, hipStream_t s)
 {
-    launch_solve_kernel(k_gn_solve_md, a, n_seq, s, r, m);
+    switch (t.on) {
+    case 0: launch_solve_kernel(k_gn_solve, a, n_seq, s); return true;
+    case TERM_ROBUST: launch_solve_kernel(k_gn_solve_rw, a, n_seq, s, t.rob); return true;
+    case TERM_MEDIAN: launch_solve_kernel(k_gn_solve_md, a, n_seq, s, t.rob, t.med); return true;
+    case TERM_AFFINE:
+    case TERM_ROBUST | TERM_AFFINE: launch_solve_kernel(k_gn_solve_ab, a, n_seq, s, t.rob, t.aff); return true;
+    case TERM_GEOMETRIC: launch_solve_kernel(k_gn_solve_z, a, n_seq, s, t.geo); return true;
+    case TERM_GEOMETRIC | TERM_AFFINE: launch_solve_kernel(k_gn_solve_zab, a, n_seq, s, t.aff, t.geo); return true;
+    case TERM_STEP_CONTROL: launch_solve_kernel(k_gn_solve_lm, a, n_seq, s, t.lm); return true;
+    default: return false;
+    }
 }
 
 void launch_median_begin(const MedianBeginArgs& a, hipStream_t s)
@@ -3791,8 +3754,6 @@ void launch_robust_begin(const RobustBeginArgs& a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_robust_begin, dim3(cdiv(a.n_seq, 256)), dim3(256), 0, s, a);
 }
-
-void launch_gn_solve_lm(const SolveArgs& a, const LmSolve& m, int n_seq, hipStream_t s) { launch_solve_kernel(k_gn_solve_lm, a, n_seq, s, m); }
 
 void launch_lm_begin(const LmBeginArgs& a, hipStream_t s)
 {

@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "direct-visual-odometry_amd", "csrc")
 
 # argument blocks whose names do not end in "Args"; every struct named *Args is one as well (arg_types)
-EXTRA_TYPES = ("PersistLevel", "PersistMono", "MonoRef")
+EXTRA_TYPES = ("PersistLevel", "PersistMono", "MonoRef", "TileTerms", "SolveTerms")
 NOT_A_TYPE = {"return", "sizeof", "else", "case", "delete", "new", "goto", "throw", "struct", "class", "typename"}
 
 
