@@ -856,6 +856,21 @@ int dvo_batch_set_sensor_distortion(dvo_batch* b, const float* D, int per_sequen
     return b->impl.set_sensor_distortion(D, per_sequence != 0);
 }
 
+int dvo_batch_set_pyramid_filter(dvo_batch* b, int filter)
+{
+    if (!b) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_set_pyramid_filter: needs a sensor-depth batch"); return DVO_ERR_BAD_ARGUMENT; }
+    return b->impl.set_pyramid_filter(filter);
+}
+
+int dvo_batch_pyramid_filter(dvo_batch* b, int* filter)
+{
+    if (!b || !filter) return DVO_ERR_BAD_ARGUMENT;
+    if (b->mono) { set_error("dvo_batch_pyramid_filter: needs a sensor-depth batch"); return DVO_ERR_BAD_ARGUMENT; }
+    *filter = b->impl.pyr_filter;
+    return DVO_OK;
+}
+
 int dvo_batch_get_sensor_distortion(dvo_batch* b, float* D, int* enabled)
 {
     if (!b) return DVO_ERR_BAD_ARGUMENT;
@@ -1109,7 +1124,8 @@ struct OpFrames {
 };
 }  // namespace
 
-int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
+// dvo_op_pyramid_frames and, with a filter, dvo_op_pyramid_frames_filtered: the one body of both
+static int pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, int filter, float* const gray_out[],
                           float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran)
 {
     if (!args) return bad_pyramid_frames("args is NULL");
@@ -1124,6 +1140,11 @@ int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_fram
     if (raw && p.channels != 1 && p.channels != 3 && p.channels != 4) return bad_pyramid_frames("channels must be 1, 3 or 4");
     if (!std::isfinite(p.depth_scale) || p.depth_scale < 0.0f) return bad_pyramid_frames("depth_scale must be finite and >= 0");
     if (p.flags & ~(DVO_PYRAMID_ROWS_DECIMATED | DVO_PYRAMID_FORCE_WEIGHT_MAPS | DVO_PYRAMID_SPLIT)) return bad_pyramid_frames("unknown flag bits");
+    if (filter != DVO_PYRAMID_FILTER_NONE) {
+        if (filter != DVO_PYRAMID_FILTER_BINOMIAL3) return bad_pyramid_frames("filter is not DVO_PYRAMID_FILTER_NONE or DVO_PYRAMID_FILTER_BINOMIAL3");
+        if (p.flags & (DVO_PYRAMID_ROWS_DECIMATED | DVO_PYRAMID_SPLIT)) return bad_pyramid_frames("a filtered build takes whole frames and is not split");
+        if (p.culls > 2) return bad_pyramid_frames("the filtered build supports culls 0, 1 and 2");
+    }
     const bool second = raw ? p.rgb2 != nullptr : p.gray2 != nullptr;
     if (p.seq_action) {
         if (!second) return bad_pyramid_frames("seq_action without second frames");
@@ -1152,6 +1173,7 @@ int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_fram
     DVO_TRY(A.alloc(g, p.n_seq, dc));
     DVO_HIP(hipMemsetAsync(A.arena.p, 0xff, A.arena.bytes, c.s));
     DVO_TRY(first.upload(p.gray, p.depth, p.sigma, p.rgb, p.channels, p.depth16, scale, px, dec, c.s));
+    first.in.filter = next.in.filter = filter;
     if (p.flags & DVO_PYRAMID_FORCE_WEIGHT_MAPS) A.allow_const_weight = false;
     // the split build's second stream and events, as Batch owns them
     PyramidSplit split;
@@ -1200,6 +1222,19 @@ int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_fram
     if (want_split) DVO_HIP(hipStreamSynchronize(split.side));
     if (ran) { ran->kind = k.kind; ran->culls = k.culls; ran->plan = k.plan; }
     return DVO_OK;
+}
+
+int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
+                          float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran)
+{
+    return pyramid_frames(dev, cfg, args, DVO_PYRAMID_FILTER_NONE, gray_out, depth_out, sigma_out, wgt_out, ran);
+}
+
+int dvo_op_pyramid_frames_filtered(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, int filter,
+                                   float* const gray_out[], float* const depth_out[], float* const sigma_out[],
+                                   float* const wgt_out[], dvo_pyramid_kernel* ran)
+{
+    return pyramid_frames(dev, cfg, args, filter, gray_out, depth_out, sigma_out, wgt_out, ran);
 }
 
 // The optional inputs and outputs of one evaluation, by term (value-initialised; each dvo_op_gn_step* fills what it uses):

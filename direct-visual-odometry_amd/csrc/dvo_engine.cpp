@@ -314,14 +314,14 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     // sensor-depth frames with lens undistortion (dvo_batch_set_sensor_distortion): the arguments of the plain build plus the remap,
     // whole frames -- launch_pyramid picks k_pyramid_remap_depth
     if (!in.raw()) {
-        if (!in.remap) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from, &k); return false; }
-        PyramidArgs a = float_args(fs, in.gray, in.depth, in.sigma, keep_sigma, false);
+        if (!in.remap && !in.filter) { build_pyramid(fs, in.gray, in.depth, in.sigma, s, keep_sigma, in.rows_decimated, seq_action, copy_from, &k); return false; }
+        PyramidArgs a = float_args(fs, in.gray, in.depth, in.sigma, keep_sigma, false);   // (remap or filter: whole frames)
         a.remap = in.remap; a.remap_cam = in.remap_cam;
         plan_copy(a, seq_action, copy_from);
-        k = launch_pyramid(a, fs.n_seq, s);
+        k = launch_pyramid(a, fs.n_seq, s, nullptr, in.filter);
         return false;
     }
-    PyramidArgs a = raw_gray_args(fs, in, in.rows_decimated);
+    PyramidArgs a = raw_gray_args(fs, in, in.filter ? false : in.rows_decimated);
     a.raw_depth = in.depth16; a.raw_depth_scale = in.depth_scale;
     a.raw_sigma_valid = 0.1f; a.raw_sigma_invalid = 1.0f; a.raw_invalidate_gray = 1;   // transform.cpp:60-76
     const bool dep = in.depth16 != nullptr;
@@ -337,7 +337,7 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
     }
     a.remap = in.remap; a.remap_cam = in.remap_cam;   // (set only with depth here, and then on whole frames)
     plan_copy(a, seq_action, copy_from);
-    if (split && pyramid_can_split(a)) {
+    if (split && !in.filter && pyramid_can_split(a)) {
         // stage A where the single kernel would run; stage B on the side stream, after everything queued on `s` so far (every earlier
         // launch that may still read the set it overwrites)
         k = {DVO_PYRAMID_KERNEL_SPLIT, a.culls, 0};
@@ -348,7 +348,7 @@ bool build_pyramid(FrameSet& fs, const FrameInput& in, hipStream_t s, bool keep_
         if (split->err == hipSuccess) split->err = hipEventRecord(split->done, split->side);
         return split->err == hipSuccess;
     }
-    k = launch_pyramid(a, fs.n_seq, s);
+    k = launch_pyramid(a, fs.n_seq, s, nullptr, in.filter);
     return false;
 }
 
@@ -2047,7 +2047,7 @@ int Batch::push_host_frame(const void* p0, const void* p1, const void* p2, Frame
     // Known difference from MonoBatch::odometrize_host, kept: the frame counts as taken before its copies are queued, and the slot is
     // marked consumed below whatever push() returns (the mono batch stages a refused frame's successor into the same slot).
     host.advance();
-    in.rows_decimated = host.decimate(g, und);
+    in.rows_decimated = host.decimate(g, und) && pyr_filter == DVO_PYRAMID_FILTER_NONE;   // (the filter reads every source row)
     const size_t rb = (size_t)g.src_w * (in.raw() ? (size_t)in.channels : sizeof(float));
     DVO_TRY(host.upload(0, p0, rb, g, n_seq, in.rows_decimated));
     if (p1) DVO_TRY(host.upload(1, p1, in.raw() ? (size_t)g.src_w * 2 : rb, g, n_seq, in.rows_decimated));
@@ -2120,6 +2120,7 @@ int Batch::prefetch(const FrameInput& in)
     const int slot = free_slot();
     if (npre >= 2 || slot < 0) { set_error("dvo_batch_prefetch_device: two prefetched frames are already waiting for their push"); return DVO_ERR_NOT_READY; }
     FrameInput fin = in;
+    fin.filter = pyr_filter;
     und.apply(fin, n_seq);   // dvo_batch_set_sensor_distortion: k_pyramid_remap_depth (device frames: whole)
     if (tracked_once) DVO_HIP(hipStreamWaitEvent(pstream, ev_last_track, 0));
     build_pyramid(fs[slot], fin, pstream, /*keep_sigma=*/false);
@@ -2140,7 +2141,9 @@ int Batch::push(const FrameInput& in)
     const bool planned = plan.act_pending || plan.act_used || cam_used || kf_on;
     DVO_TRY(check_actions_input(in));
     if (und.enabled() && in.rows_decimated) { set_error("internal: an undistorted frame needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
+    if (pyr_filter && in.rows_decimated) { set_error("internal: a filtered pyramid needs whole frames"); return DVO_ERR_BAD_ARGUMENT; }
     FrameInput fin = in;
+    fin.filter = pyr_filter;
     und.apply(fin, n_seq);   // dvo_batch_set_sensor_distortion: k_pyramid_remap_depth
     int target;
     bool built = false;
@@ -2431,8 +2434,34 @@ int Batch::stage_cameras(const float* K)
 }
 
 // ------------------------------------------------------------------------------------------------ batch: lens undistortion
+int Batch::set_pyramid_filter(int filter)
+{
+    if (filter != DVO_PYRAMID_FILTER_NONE && filter != DVO_PYRAMID_FILTER_BINOMIAL3) {
+        set_error("dvo_batch_set_pyramid_filter: filter is not DVO_PYRAMID_FILTER_NONE or DVO_PYRAMID_FILTER_BINOMIAL3");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if ((n_push > 0 || npre > 0) && filter != pyr_filter) {
+        set_error("dvo_batch_set_pyramid_filter: the filter is fixed once the batch has seen a frame");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (filter != DVO_PYRAMID_FILTER_NONE && und.enabled()) {
+        set_error("dvo_batch_set_pyramid_filter: the batch undistorts its frames (the filter and dvo_batch_set_sensor_distortion do not combine)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    if (filter != DVO_PYRAMID_FILTER_NONE && g.culls > 2) {
+        set_error("dvo_batch_set_pyramid_filter: the filtered build supports culls 0, 1 and 2");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
+    pyr_filter = filter;
+    return DVO_OK;
+}
+
 int Batch::set_sensor_distortion(const float* D, bool per_sequence)
 {
+    if (pyr_filter != DVO_PYRAMID_FILTER_NONE) {
+        set_error("dvo_batch_set_sensor_distortion: the batch filters its gray pyramid (dvo_batch_set_pyramid_filter does not combine with it)");
+        return DVO_ERR_BAD_ARGUMENT;
+    }
     if (npre > 0) { set_error("dvo_batch_set_sensor_distortion: a prefetched frame is waiting for its push"); return DVO_ERR_NOT_READY; }
     DVO_TRY(select_device(device));
     // Synchronous: the tables are replaced only once no queued push or (consumed) prefetch can still read them

@@ -149,6 +149,9 @@ struct FrameInput {
     // raw mono frames with a photometric calibration (Photometry::apply): the k_pyramid*_photo kernels.  Rows may be decimated
     // (the gain table is top-level sized) unless the frames are undistorted too.
     PhotoArgs photo{};
+    // sensor-depth frames of a batch with dvo_batch_set_pyramid_filter: the gray pyramid is low-pass filtered before each halving
+    // (k_pyramid_filter_top / _down).  Whole frames, no remap, never the split build.
+    int filter = DVO_PYRAMID_FILTER_NONE;
     bool raw() const { return rgb != nullptr; }
     const void* key0() const { return raw() ? (const void*)rgb : (const void*)gray; }
     const void* key1() const { return raw() ? (const void*)depth16 : (const void*)depth; }
@@ -751,6 +754,10 @@ struct Batch {  // n_seq independent sequences, frame-to-frame (or keyframe) tra
     std::vector<float> und_D_used;              // [n_seq][5] the D of the last push (empty: none)
     bool und_pending = false;                   // und changed since the last push
     int set_sensor_distortion(const float* D, bool per_sequence);
+    // The gray pyramid's low-pass filter (dvo_batch_set_pyramid_filter): fixed once a frame was pushed or prefetched.
+    // While it is on every build takes launch_pyramid's filter branch on whole frames (host feeds upload every row) and is not split.
+    int pyr_filter = DVO_PYRAMID_FILTER_NONE;
+    int set_pyramid_filter(int filter);
     bool distortion_changed(size_t q) const
     {
         if (und.enabled() != !und_D_used.empty()) return true;

@@ -804,7 +804,11 @@ struct PyramidKernel {
 // photo (optional, photo->gain set): raw mono frames of a calibrated handle -- k_pyramid_raw4_photo<2, plan> (kind _PHOTO_RAW4) where
 // the four-pixel build is possible at culls 2 and the gain rows can be read 16 bytes at a time, else k_pyramid_photo<plan, remap>
 // (_PHOTO_SCALAR, or _PHOTO_REMAP with a.remap).  Without it: exactly the kernels chosen before there was a calibration.
-PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s, const PhotoArgs* photo = nullptr);
+// filter (DVO_PYRAMID_FILTER_*; not NONE only without a remap and without a photo block): the binomial-filtered gray pyramid of
+// DESIGN.md §39 -- k_pyramid_filter_top<culls, raw, plan, wide> and one k_pyramid_filter_down<plan> per lower level (kind _FILTER,
+// plan = PLAN | WIDE << 1 | RAW << 2).  NONE: exactly the launches above.
+PyramidKernel launch_pyramid(const PyramidArgs& a, int n_seq, hipStream_t s, const PhotoArgs* photo = nullptr,
+                             int filter = DVO_PYRAMID_FILTER_NONE);
 // k_photometric_map: gain[p][y][x] of pair p = (cal, cam) = 1 / vignette[cal][source of kept pixel (x, y)], the source being
 // (x, y) << culls, or remap[cam][y][x] with a remap (then -1 gives kPhotoMasked).  vignette == nullptr: 1.
 void launch_photometric_map(const float* vignette, const int* pairs /*[n_pair][2]*/, int n_pair, int w, int h, int culls, int tw, int th,

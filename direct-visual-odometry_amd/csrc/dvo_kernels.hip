@@ -819,6 +819,212 @@ __global__ void __launch_bounds__(256) k_pyramid_remap_depth(PyramidArgs a)
     });
 }
 
+// ------------------------------------------------------------------------------------------------
+// The binomial-filtered gray pyramid of a sensor-depth batch (dvo_batch_set_pyramid_filter, DVO_PYRAMID_FILTER_BINOMIAL3;
+// include/dvo.h states the contract, DESIGN.md §39 the design).  Gray only: depth, sigma and wgt are the plain build's values.
+// ------------------------------------------------------------------------------------------------
+// One tap of a halving: an invalid tap (NaN, <= kInvalid; a tap outside the map is held as kInvalid) is skipped
+__device__ __forceinline__ void filter_tap(float g, int k, float& S, int& W)
+{
+    if (is_valid(g)) { S = fmaf((float)k, g, S); W += k; }
+}
+
+// One halving H at centre tap c[0] of a map with `pitch` floats per row whose 3x3 neighbourhood is readable: rows j = -1, 0, 1
+// outside, columns i = -1, 0, 1 inside, weights (2 - |i|)(2 - |j|), one division
+__device__ __forceinline__ float filter_halve(const float* c, int pitch)
+{
+    if (!is_valid(c[0])) return kInvalid;
+    float S = 0.0f;
+    int W = 0;
+#pragma unroll
+    for (int j = -1; j <= 1; j++)
+#pragma unroll
+        for (int i = -1; i <= 1; i++) filter_tap(c[j * pitch + i], (2 - (i < 0 ? -i : i)) * (2 - (j < 0 ? -j : j)), S, W);
+    return S / (float)W;
+}
+
+// The converted source gray G0 of pixel `off` of a whole input frame: raw_convert's gray (kInvalid where the depth word is 0) or
+// the float map's value
+template <bool RAW>
+__device__ __forceinline__ float filter_source_gray(const PyramidArgs& a, size_t off)
+{
+    if constexpr (RAW) {
+        const unsigned d = a.raw_depth != nullptr ? (unsigned)__builtin_nontemporal_load(a.raw_depth + off) : 1u;
+        return raw_convert(a, raw_luma8(a, off), d).gray;
+    } else {
+        return __builtin_nontemporal_load(a.src[0] + off);
+    }
+}
+
+// k_pyramid_filter_top: the top level of every map, and depth / sigma / wgt of every level.  A workgroup owns a 32 x 8 tile of
+// the top level.  It stages the tile's footprint of G0 (the tile << CULLS plus 2^CULLS - 1 rows and columns ahead of it: 3 x 3
+// per halving) in LDS, out-of-frame pixels as kInvalid, reduces it there (CULLS = 2: through the 65 x 17 intermediate tile, also
+// in LDS; no map at source or intermediate resolution exists in memory), and each thread stores its pixel.  Depth and sigma are
+// read at the kept pixel and stored at every level with k_pyramid's operations.  CULLS = 0: the top level is the input.
+// WIDE: the footprint is staged in 16-byte loads (16 raw pixels: one gray and two depth loads, or 4 float pixels), from a
+// 16-byte aligned column ahead of the tile; needs 1-channel bytes, src_w a multiple of the chunk and 16-byte aligned inputs
+// (pyramid_filter_wide).  Otherwise one pixel per load.  The input holds whole frames.
+// PLAN: the workgroups of a DVO_SEQ_SKIP sequence copy the reference's top-level values forward as k_pyramid<true> does
+// (k_pyramid_filter_down<true> copies the gray of the lower levels).
+template <int CULLS, bool RAW, bool PLAN, bool WIDE>
+__global__ void __launch_bounds__(256) k_pyramid_filter_top(PyramidArgs a)
+{
+    static_assert(CULLS >= 0 && CULLS <= 2 && !(WIDE && CULLS == 0), "culls 0 stages nothing");
+    constexpr int TX = 32, TY = 8;
+    constexpr int HALO = (1 << CULLS) - 1;
+    constexpr int C = WIDE ? (RAW ? 16 : 4) : 1;     // pixels per staging load
+    constexpr int LEFT = WIDE ? C : HALO;            // columns staged ahead of the tile's first source column
+    constexpr int SW = (TX << CULLS) + LEFT, SH = (TY << CULLS) + HALO;
+    constexpr int IW = 2 * TX + 1, IH = 2 * TY + 1;  // the intermediate tile of CULLS = 2
+    __shared__ __attribute__((aligned(16))) float s_src[CULLS > 0 ? SH * SW : 4];
+    __shared__ float s_mid[CULLS == 2 ? IH * IW : 1];
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    if (seq >= a.n_seq) return;
+    const int tiles_x = (tw + TX - 1) / TX;
+    const int by = (int)blockIdx.x / tiles_x, bx = (int)blockIdx.x - by * tiles_x;
+    const int X0 = bx * TX, Y0 = by * TY;
+    const int tx = threadIdx.x & (TX - 1), ty = threadIdx.x / TX;
+    const int x = X0 + tx, y = Y0 + ty;
+    bool skip = false;
+    if constexpr (PLAN) skip = seq_skips(a, seq);   // (uniform per workgroup: the barriers below are too)
+    const size_t base = (size_t)seq * a.src_w * a.src_h;
+    float gray = kInvalid;
+    if constexpr (CULLS > 0) if (!skip) {
+        const int sx0 = (X0 << CULLS) - LEFT, sy0 = (Y0 << CULLS) - HALO;
+        constexpr int CPR = SW / C;
+        for (int i = threadIdx.x; i < SH * CPR; i += 256) {
+            const int r = i / CPR, c = (i - r * CPR) * C;
+            const int sy = sy0 + r, sx = sx0 + c;
+            const bool in = sy >= 0 && sy < a.src_h && sx >= 0 && sx < a.src_w;   // (WIDE: src_w % C == 0, a chunk is in or out whole)
+            const size_t off = base + (size_t)sy * a.src_w + sx;
+            float* out = s_src + r * SW + c;
+            if constexpr (!WIDE) {
+                out[0] = in ? filter_source_gray<RAW>(a, off) : kInvalid;
+            } else if constexpr (RAW) {
+                f4 v[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) v[q] = f4{kInvalid, kInvalid, kInvalid, kInvalid};
+                if (in) {
+                    const u32x4 g = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.raw_rgb + off));
+                    u32x4 d[2] = {u32x4{0x00010001u, 0x00010001u, 0x00010001u, 0x00010001u}, u32x4{0x00010001u, 0x00010001u, 0x00010001u, 0x00010001u}};
+                    if (a.raw_depth != nullptr) {
+                        d[0] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.raw_depth + off));
+                        d[1] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a.raw_depth + off) + 1);
+                    }
+#pragma unroll
+                    for (int k = 0; k < 16; k++) {
+                        const unsigned g8 = (g[k >> 2] >> ((k & 3) * 8)) & 0xffu;
+                        const unsigned dk = (d[k >> 3][(k >> 1) & 3] >> ((k & 1) * 16)) & 0xffffu;
+                        v[k >> 2][k & 3] = raw_convert(a, g8, dk).gray;
+                    }
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) reinterpret_cast<f4*>(out)[q] = v[q];
+            } else {
+                f4 v = f4{kInvalid, kInvalid, kInvalid, kInvalid};
+                if (in) v = __builtin_nontemporal_load(reinterpret_cast<const f4*>(a.src[0] + off));
+                *reinterpret_cast<f4*>(out) = v;
+            }
+        }
+        __syncthreads();
+        if constexpr (CULLS == 2) {
+            const int mx0 = 2 * X0 - 1, my0 = 2 * Y0 - 1, mw = a.src_w >> 1, mh = a.src_h >> 1;
+            for (int i = threadIdx.x; i < IH * IW; i += 256) {
+                const int r = i / IW, c = i - r * IW;
+                const int mx = mx0 + c, my = my0 + r;
+                float v = kInvalid;   // (outside the intermediate map: skipped by the second halving)
+                if (mx >= 0 && mx < mw && my >= 0 && my < mh) v = filter_halve(s_src + (2 * my - sy0) * SW + (2 * mx - sx0), SW);
+                s_mid[i] = v;
+            }
+            __syncthreads();
+            gray = filter_halve(s_mid + (2 * ty + 1) * IW + (2 * tx + 1), IW);
+        } else {
+            gray = filter_halve(s_src + (2 * y - sy0) * SW + (2 * x - sx0), SW);
+        }
+    }
+    if (x >= tw || y >= th) return;
+    bool have[3];
+    have[0] = true;
+    if constexpr (RAW) have[1] = have[2] = a.raw_depth != nullptr;
+    else { have[1] = a.src[1] != nullptr; have[2] = a.src[2] != nullptr; }
+    const bool prep = a.wgt[0] != nullptr && have[1] && have[2];
+    const size_t ot = (size_t)seq * tw * th + (size_t)y * tw + x;
+    float top[3] = {0.0f, 0.0f, 0.0f};
+    if (skip) {
+#pragma unroll
+        for (int m = 0; m < 3; m++)
+            if (have[m] && a.dst[m][T] != nullptr) top[m] = __builtin_nontemporal_load(a.ref[m][T] + ot);
+    } else {
+        const size_t so = base + (size_t)(y << CULLS) * a.src_w + (x << CULLS);
+        float raw[3] = {0.0f, 0.0f, 0.0f};
+        if constexpr (RAW) {
+            if (have[1]) {
+                const RawPixel p = raw_convert(a, 0u, __builtin_nontemporal_load(a.raw_depth + so));
+                raw[1] = p.depth; raw[2] = p.sigma;
+            }
+        } else {
+#pragma unroll
+            for (int m = 1; m < 3; m++)
+                if (have[m]) raw[m] = __builtin_nontemporal_load(a.src[m] + so);
+        }
+        // top level: cullImage(src, culls); culls == 0 aliases the input (convert.cpp:9-10), no pass_valid
+        if constexpr (CULLS == 0) raw[0] = filter_source_gray<RAW>(a, so);
+        top[0] = CULLS == 0 ? raw[0] : gray;
+        top[1] = CULLS == 0 ? raw[1] : pass_valid(raw[1]);
+        top[2] = CULLS == 0 ? raw[2] : pass_valid(raw[2]);
+    }
+    if (a.dst[0][T] != nullptr) __builtin_nontemporal_store(top[0], a.dst[0][T] + ot);
+    walk_levels<1, 0>(a, a.levels, seq, x, y, [&](int l, size_t o, int) {
+        float val[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+        for (int m = 1; m < 3; m++) {
+            val[m] = l == T ? top[m] : pass_valid(top[m]);
+            if (have[m] && a.dst[m][l] != nullptr) __builtin_nontemporal_store(val[m], a.dst[m][l] + o);
+        }
+        if (prep)
+            __builtin_nontemporal_store(skip ? __builtin_nontemporal_load(a.ref_wgt[l] + o) : gn_weight(a.step[l], a.sigma_min, a.sigma_max, val[2]),
+                                        a.wgt[l] + o);
+    });
+}
+
+// k_pyramid_filter_down: gray of level l = H(stored gray of level l + 1), one thread per pixel of level l, one launch per level
+// below the top (each reads what the launch before it stored; the nine taps of neighbouring threads overlap in L2).
+// PLAN: a DVO_SEQ_SKIP sequence copies the reference's gray of level l.
+template <bool PLAN>
+__global__ void __launch_bounds__(256) k_pyramid_filter_down(PyramidArgs a, int l, float inv_w)
+{
+    const int w = a.w[l], h = a.h[l], iw = a.w[l + 1], ih = a.h[l + 1];
+    const int seq = (int)(blockIdx.z * DVO_GRID_SEQ_Y + blockIdx.y);
+    const int i = (int)blockIdx.x * 256 + threadIdx.x;
+    if (i >= w * h || seq >= a.n_seq) return;
+    const size_t o = (size_t)seq * w * h + i;
+    if constexpr (PLAN) {
+        if (seq_skips(a, seq)) {
+            __builtin_nontemporal_store(__builtin_nontemporal_load(a.ref[0][l] + o), a.dst[0][l] + o);
+            return;
+        }
+    }
+    int x, y;
+    split_index(i, w, inv_w, x, y);
+    const float* in = a.dst[0][l + 1] + (size_t)seq * iw * ih;
+    float out = kInvalid;
+    if (is_valid(in[(size_t)(2 * y) * iw + 2 * x])) {
+        float S = 0.0f;
+        int W = 0;
+#pragma unroll
+        for (int j = -1; j <= 1; j++)
+#pragma unroll
+            for (int k = -1; k <= 1; k++) {
+                const int xx = 2 * x + k, yy = 2 * y + j;
+                if (xx < 0 || xx >= iw || yy < 0 || yy >= ih) continue;
+                filter_tap(in[(size_t)yy * iw + xx], (2 - (k < 0 ? -k : k)) * (2 - (j < 0 ? -j : j)), S, W);
+            }
+        out = S / (float)W;
+    }
+    __builtin_nontemporal_store(out, a.dst[0][l] + o);
+}
+
 // k_cull: a single Convert::cullImage (operator-level parity)
 __global__ void __launch_bounds__(256) k_cull(const float* __restrict__ src, int w, int h, int times, float* __restrict__ dst)
 {
@@ -3530,10 +3736,48 @@ static PyramidKernel launch_pyramid_photo(const PyramidArgs& a, const PhotoArgs&
     return ran;
 }
 
-PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s, const PhotoArgs* photo)
+// k_pyramid_filter_top's 16-byte staging loads are possible: whole chunks (16 one-channel bytes with their two depth words, or 4
+// floats) per row and 16-byte aligned inputs.  The level maps are stored one float at a time, so their alignment (a batch whose
+// size is no multiple of 4) does not matter here.
+static bool pyramid_filter_wide(const PyramidArgs& a)
+{
+    if (a.culls < 1 || getenv("DVO_PYRAMID_FILTER_SCALAR") != nullptr) return false;   // (the variable: A/B runs, tests)
+    if (a.raw_rgb != nullptr) return a.raw_channels == 1 && (a.src_w % 16) == 0 && aligned16({a.raw_rgb, a.raw_depth});
+    return (a.src_w % 4) == 0 && aligned16({a.src[0]});
+}
+
+// The binomial-filtered build: k_pyramid_filter_top on 32 x 8 tiles of the top level, then one
+// k_pyramid_filter_down per level below it.  PyramidKernel::plan carries the instance: bit 0 PLAN, bit 1 WIDE, bit 2 RAW.
+static PyramidKernel launch_pyramid_filter(const PyramidArgs& a, hipStream_t s)
+{
+    const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
+    const bool plan = a.seq_action != nullptr, raw = a.raw_rgb != nullptr, wide = pyramid_filter_wide(a);
+    const dim3 grid = seq_grid(cdiv(tw, 32) * cdiv(th, 8), (unsigned)a.n_seq);
+    with_flag(plan, [&](auto plan_c) {
+        with_flag(raw, [&](auto raw_c) {
+            constexpr bool PLAN = decltype(plan_c)::value, RAW = decltype(raw_c)::value;
+            if (a.culls == 0) {
+                hipLaunchKernelGGL((k_pyramid_filter_top<0, RAW, PLAN, false>), grid, dim3(256), 0, s, a);
+                return;
+            }
+            with_culls(a.culls, [&](auto culls) {
+                with_flag(wide, [&](auto wide_c) {
+                    hipLaunchKernelGGL((k_pyramid_filter_top<decltype(culls)::value, RAW, PLAN, decltype(wide_c)::value>), grid, dim3(256), 0, s, a);
+                });
+            });
+        });
+        for (int l = T - 1; l >= 0; l--)
+            hipLaunchKernelGGL(k_pyramid_filter_down<decltype(plan_c)::value>, pyramid_grid(a.w[l], a.h[l], 1, a.n_seq), dim3(256), 0, s, a, l,
+                               1.0f / (float)a.w[l]);
+    });
+    return {DVO_PYRAMID_KERNEL_FILTER, a.culls, (plan ? 1 : 0) | (wide ? 2 : 0) | (raw ? 4 : 0)};
+}
+
+PyramidKernel launch_pyramid(const PyramidArgs& a0, int n_seq, hipStream_t s, const PhotoArgs* photo, int filter)
 {
     PyramidArgs a = a0;
     a.n_seq = n_seq;
+    if (filter != DVO_PYRAMID_FILTER_NONE) return launch_pyramid_filter(a, s);   // (the callers refuse it with a photo block or a remap)
     if (photo != nullptr && photo->gain != nullptr) return launch_pyramid_photo(a, *photo, s);
     const int T = a.levels - 1, tw = a.w[T], th = a.h[T];
     const bool plan = a.seq_action != nullptr;

@@ -239,6 +239,7 @@ EXPORTS = [
     "dvo_lm_config_default", "dvo_batch_set_step_control", "dvo_batch_last_step_control", "dvo_batch_last_step_control_log",
     "dvo_op_lm_step",
     "dvo_points_config_default", "dvo_batch_export_points", "dvo_batch_last_points",
+    "dvo_batch_set_pyramid_filter", "dvo_batch_pyramid_filter", "dvo_op_pyramid_frames_filtered",
 ]
 
 # per-sequence action of the next Batch push (Batch.set_actions) and outcome of the last one (Batch.last_status): include/dvo.h
@@ -306,6 +307,9 @@ PYRAMID_KERNEL_SCALAR, PYRAMID_KERNEL_RAW4, PYRAMID_KERNEL_SPLIT, PYRAMID_KERNEL
 # ... of a handle with a photometric calibration (MonoBatch.set_photometric)
 PYRAMID_KERNEL_PHOTO_RAW4, PYRAMID_KERNEL_PHOTO_SCALAR, PYRAMID_KERNEL_PHOTO_REMAP = 4, 5, 6
 PYRAMID_ROWS_DECIMATED, PYRAMID_FORCE_WEIGHT_MAPS, PYRAMID_SPLIT = 1, 2, 4
+# the low-pass filter of a sensor-depth batch's gray pyramid (Batch.set_pyramid_filter, op_pyramid_frames_filtered) and its kernels
+PYRAMID_FILTER_NONE, PYRAMID_FILTER_BINOMIAL3 = 0, 1
+PYRAMID_KERNEL_FILTER = 7
 
 
 def _photometric_arrays(who, n_cal, inv_response, vignette, height, width):
@@ -343,6 +347,9 @@ class PyramidKernel(C.Structure):
             return "k_pyramid_photo<%s, false>" % plan
         if self.kind == PYRAMID_KERNEL_PHOTO_REMAP:
             return "k_pyramid_photo<%s, true>" % plan
+        if self.kind == PYRAMID_KERNEL_FILTER:   # plan = PLAN | WIDE << 1 | RAW << 2: <CULLS, RAW, PLAN, WIDE>
+            b = lambda bit: "true" if self.plan & bit else "false"
+            return "k_pyramid_filter_top<%d, %s, %s, %s>" % (self.culls, b(4), b(1), b(2))
         return "remap"
 
 
@@ -485,8 +492,14 @@ def pyramid(gray, depth, sigma, levels, culls, dev=0):
     return go, (do if d is not None else None), (so if s is not None else None)
 
 
+def op_pyramid_frames_filtered(w, h, levels, culls, filter=PYRAMID_FILTER_BINOMIAL3, **kw):
+    """dvo_op_pyramid_frames_filtered (include/dvo.h): op_pyramid_frames with the gray pyramid low-pass filtered before each
+    halving; the same arguments and result.  filter = PYRAMID_FILTER_NONE is op_pyramid_frames."""
+    return op_pyramid_frames(w, h, levels, culls, _filter=int(filter), **kw)
+
+
 def op_pyramid_frames(w, h, levels, culls, gray=None, depth=None, sigma=None, rgb=None, depth16=None, depth_scale=0.0, flags=0,
-                      seq_action=None, second=None, cfg=None, dev=0):
+                      seq_action=None, second=None, cfg=None, dev=0, _filter=None):
     """dvo_op_pyramid_frames (include/dvo.h): the batched pyramid build through the engine, once.  Float maps gray [+ depth + sigma]
     [n][rows][w], or raw frames rgb u8 [n][rows][w] / [n][rows][w][3 or 4] [+ depth16 u16]; rows = h, or h >> culls with
     PYRAMID_ROWS_DECIMATED.  seq_action [n] with second = dict(gray=, depth=, sigma=) / dict(rgb=, depth16=): the planned build.
@@ -518,8 +531,11 @@ def op_pyramid_frames(w, h, levels, culls, gray=None, depth=None, sigma=None, rg
     out = {m: [np.zeros(sh, np.float32) for sh in shapes] for m in ("gray", "depth", "sigma", "wgt")}
     arr = lambda lst: (FP * levels)(*[fp(x) for x in lst])
     ran = PyramidKernel()
-    _check(lib().dvo_op_pyramid_frames(dev, C.byref(cfg) if cfg is not None else None, C.byref(a), arr(out["gray"]), arr(out["depth"]),
-                                       arr(out["sigma"]), arr(out["wgt"]), C.byref(ran)))
+    outs = (arr(out["gray"]), arr(out["depth"]), arr(out["sigma"]), arr(out["wgt"]), C.byref(ran))
+    if _filter is None:
+        _check(lib().dvo_op_pyramid_frames(dev, C.byref(cfg) if cfg is not None else None, C.byref(a), *outs))
+    else:
+        _check(lib().dvo_op_pyramid_frames_filtered(dev, C.byref(cfg) if cfg is not None else None, C.byref(a), _filter, *outs))
     out["kernel"] = ran
     return out
 
@@ -1426,6 +1442,17 @@ class Batch(_PoseGuess, _WorldPoses, _PointsExport, _TrackQuality, _RobustWeight
         d = np.zeros((self.n_seq, 5), np.float32); en = C.c_int(0)
         _check(lib().dvo_batch_get_sensor_distortion(self._p, fp(d), C.byref(en)))
         return d, bool(en.value)
+
+    def set_pyramid_filter(self, filter=PYRAMID_FILTER_BINOMIAL3):
+        """Build the gray pyramid of every frame with a 3x3 binomial filter before each halving (PYRAMID_FILTER_BINOMIAL3) or by
+        decimation (PYRAMID_FILTER_NONE, the default); before the first push or prefetch (dvo_batch_set_pyramid_filter)."""
+        _check(lib().dvo_batch_set_pyramid_filter(self._p, int(filter)))
+
+    def pyramid_filter(self):
+        """The PYRAMID_FILTER_* in force (dvo_batch_pyramid_filter)."""
+        f = C.c_int(-1)
+        _check(lib().dvo_batch_pyramid_filter(self._p, C.byref(f)))
+        return f.value
 
     def copy_status_device(self, ptr):
         """Async D2D copy of last_status() into device memory int32 [n_seq] (int = device pointer)."""

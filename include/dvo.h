@@ -293,6 +293,35 @@ int dvo_batch_get_intrinsics(dvo_batch* b, float* K);         /* [n_seq][9] */
  * get: the D the next push uses, [n_seq][5] (zeros when none; may be NULL), and *enabled = 1 when set (may be NULL). */
 int dvo_batch_set_sensor_distortion(dvo_batch* b, const float* D, int per_sequence);
 int dvo_batch_get_sensor_distortion(dvo_batch* b, float* D /*[n_seq][5], may be NULL*/, int* enabled /*may be NULL*/);
+/* ---- low-pass filtered gray pyramid of sensor-depth frames (opt-in) ---------------------------------------------------------
+ * By default every pyramid level is a decimation (level l holds pixel (x << s, y << s) of the input), so a coarse level carries
+ * the full per-pixel noise of the source.  dvo_batch_set_pyramid_filter(b, DVO_PYRAMID_FILTER_BINOMIAL3) makes every push and
+ * prefetch of a sensor-depth batch (dvo_batch_create; float or raw, device or host) build its GRAY pyramid with a 3x3 binomial
+ * filter before each halving.  Depth, sigma and the weight maps of every level stay the plain build's, bit for bit, and
+ * everything downstream (actions, cameras, keyframes, fusion, carry, export, every opt-in term) reads the frame sets as before.
+ * Contract (all arithmetic float32, IEEE, no contraction but the fmaf named):
+ *  - G0 is the converted source gray at input resolution (never stored): for raw frames the gray of the raw conversion (see
+ *    dvo_op_pyramid_frames), DVO_INVALID where d16 == 0; for float feeds the float map.
+ *  - A pixel is invalid if it is NaN or <= DVO_INVALID.
+ *  - One halving H of a w_in x h_in map gives, for 0 <= x < w_in >> 1 and 0 <= y < h_in >> 1: DVO_INVALID if the centre tap
+ *    G(2x, 2y) is invalid; else S = 0.0f, W = 0, and for j = -1, 0, 1 (outer) and i = -1, 0, 1 (inner), skipping a tap
+ *    (2x + i, 2y + j) that is outside the map or invalid: k = (2 - |i|)(2 - |j|), S = fmaf((float)k, g, S), W += k; the result is
+ *    S / (float)W, one IEEE division.
+ *  - The top-level gray is H applied `culls` times to G0 (culls = 0: the input unchanged, as without the filter); the gray of level
+ *    l - 1 is H of the STORED level l.
+ *  - So the valid set of every level equals the plain build's, and below an unchanged top no result is NaN.
+ *  - A DVO_SEQ_SKIP sequence copies its reference's gray forward level by level.
+ * The host entry points upload whole frames while the filter is on, and the split build of big batches is not used.
+ * The filter is fixed once the handle has seen a frame: the setter succeeds before the first push or prefetch, afterwards only
+ * with the value in force.  DVO_ERR_BAD_ARGUMENT, before anything is queued: a NULL handle or out pointer, a value outside the
+ * set, a mono batch, another value after the first frame, a batch with dvo_batch_set_sensor_distortion on
+ * (dvo_batch_set_sensor_distortion refuses likewise while the filter is on), a batch created with culls > 2.
+ * Out of scope: mono batches, the dvo_vo handles, the combination with lens undistortion.
+ * A batch that never calls the setter, or sets NONE, runs exactly the launches it runs without this call. */
+#define DVO_PYRAMID_FILTER_NONE      0
+#define DVO_PYRAMID_FILTER_BINOMIAL3 1
+int dvo_batch_set_pyramid_filter(dvo_batch* b, int filter);   /* sensor-depth batches */
+int dvo_batch_pyramid_filter(dvo_batch* b, int* filter);
 /* ---- one block of sequences per GPU (BASELINE config 5) -------------------------------------------
  * The path shards across sequences only (frame t of a sequence tracks against state from frames < t: system.hpp:48,57,67): every
  * rank -- one process per GPU -- owns a contiguous block of the sequences and tracks it with no communication.
@@ -1116,6 +1145,16 @@ typedef struct dvo_pyramid_frames_args {
 } dvo_pyramid_frames_args;
 int dvo_op_pyramid_frames(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, float* const gray_out[],
                           float* const depth_out[], float* const sigma_out[], float* const wgt_out[], dvo_pyramid_kernel* ran);
+/* dvo_op_pyramid_frames with the gray pyramid filtered as dvo_batch_set_pyramid_filter states (same arguments, planned builds
+ * included; the first frames of a planned build are filtered too).  filter = DVO_PYRAMID_FILTER_NONE: dvo_op_pyramid_frames, byte
+ * for byte.  With a filter: ran->kind = DVO_PYRAMID_KERNEL_FILTER (k_pyramid_filter_top<culls, raw, plan, wide> and one
+ * k_pyramid_filter_down<plan> per level below the top), ran->culls = culls and ran->plan = PLAN | WIDE << 1 | RAW << 2 (WIDE: the
+ * source footprint is staged with 16-byte loads -- 1-channel bytes with w a multiple of 16, or float maps with w a multiple of 4,
+ * culls > 0); DVO_PYRAMID_ROWS_DECIMATED, DVO_PYRAMID_SPLIT, culls > 2 and a filter outside the set -> DVO_ERR_BAD_ARGUMENT. */
+#define DVO_PYRAMID_KERNEL_FILTER 7
+int dvo_op_pyramid_frames_filtered(int dev, const dvo_config* cfg, const dvo_pyramid_frames_args* args, int filter,
+                                   float* const gray_out[], float* const depth_out[], float* const sigma_out[],
+                                   float* const wgt_out[], dvo_pyramid_kernel* ran);
 /* Debug readers of a mono batch's photometric calibration (host memory; both synchronise the batch's stream).
  * photometric_gain: the gain table sequence `seq` reads, [h_top][w_top]: 1.0f / vignette at each kept pixel's source, -1.0f where the
  * pixel is masked (vignette not finite or <= 0) or the remap's index is -1.  DVO_ERR_NOT_READY without a calibration.

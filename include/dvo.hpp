@@ -299,6 +299,15 @@ public:
     // lens undistortion of every frame from the next push on: D[5] for every sequence, or (perSequence) D[n_seq][5]; nullptr clears
     // (dvo_batch_set_sensor_distortion).  distortion(): the [n_seq][5] coefficients the next push uses (empty when none).
     void setDistortion(const float* D, bool perSequence = false) { check(dvo_batch_set_sensor_distortion(b_, D, perSequence ? 1 : 0)); }
+    // the gray pyramid of every frame low-pass filtered before each halving (DVO_PYRAMID_FILTER_BINOMIAL3) or decimated (_NONE, the
+    // default); before the first push or prefetch, not together with setDistortion (dvo_batch_set_pyramid_filter)
+    void setPyramidFilter(int filter = DVO_PYRAMID_FILTER_BINOMIAL3) { check(dvo_batch_set_pyramid_filter(b_, filter)); }
+    int pyramidFilter()
+    {
+        int f = DVO_PYRAMID_FILTER_NONE;
+        check(dvo_batch_pyramid_filter(b_, &f));
+        return f;
+    }
     std::vector<std::array<float, 5>> distortion()
     {
         std::vector<std::array<float, 5>> D(n_);
