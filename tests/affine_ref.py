@@ -9,8 +9,9 @@ summed exactly in float64, beside the sum of its absolute values.  Only the devi
 DESIGN.md §6, and the moments are reduced in the same shape -- 2 * ppt per-thread accumulations (main loop and deferred loop), a six-step
 butterfly over the wave, three additions over the four waves, the tiles in double -- so the same depth holds for them
 (gn_sums.reduction_depth).  The bound of the next entry is propagated from the moment bounds through the closed form: it is evaluated at
-the ends of the moment intervals, and one float ulp is added for the cast.  Nothing here is tuned on a device result.  Test
-infrastructure only."""
+the ends of the moment intervals, and one float ulp is added for the cast.  This module owns the compensated terms, the moments, the
+closed form and the entry chain (EntryChain, shared with geometric_affine_ref); the per-entry bound loop is gn_sums.assert_entries,
+the log walker and the tracking loop are tests/term_replay.py's.  Nothing here is tuned on a device result.  Test infrastructure only."""
 import itertools
 
 import numpy as np
@@ -18,7 +19,7 @@ import numpy as np
 import gn_sums
 import orc
 import robust_ref as rr
-from util import TOL_BACKWARD, assert_composed, backward_error
+import term_replay
 
 OFF, ESTIMATE, GIVEN = 0, 1, 2
 F32 = np.float32
@@ -101,7 +102,7 @@ def closed_form(N, M, n_valid, guards, prev):
 def next_entry_bounds(ex, depth, robust, guards, prev):
     """(lo[2], hi[2], verdicts): the closed form at every end of the moment intervals (N = M0 with robust weights, else the exact
     n_valid), widened by one float32 ulp for the cast; verdicts = the set of guard outcomes met on the way."""
-    f = depth * gn_sums.U32 * gn_sums.SECOND_ORDER
+    f = gn_sums.factor(depth)
     iv = [(ex["M"][k] - f * ex["A_M"][k], ex["M"][k] + f * ex["A_M"][k]) for k in range(5)]
     if not robust:
         iv[0] = (float(ex["n"]), float(ex["n"]))
@@ -119,19 +120,10 @@ def next_entry_bounds(ex, depth, robust, guards, prev):
 def assert_moments(got, ex, depth, robust, tag=""):
     """device moments (N, M1, M2, M11, M12 in double) per entry inside depth * 2^-24 * (1 + 2^-10) * A; N is exact without weights"""
     got = np.asarray(got, np.float64)
-    f = depth * gn_sums.U32 * gn_sums.SECOND_ORDER
-    worst = 0.0
-    for k in range(5):
-        if k == 0 and not robust:
-            assert got[0] == ex["n"], (tag, "N", got[0], ex["n"])
-            continue
-        bnd = f * ex["A_M"][k]
-        if bnd == 0.0:
-            assert got[k] == 0.0, (tag, k, got[k])
-            continue
-        ratio = abs(got[k] - ex["M"][k]) / bnd
-        assert ratio <= 1.0, "%s: moment %d = %.17g, exact %.17g: %.3g times the bound %.3g (depth %d)" % (tag, k, got[k], ex["M"][k], ratio, bnd, depth)
-        worst = max(worst, ratio)
+    if not robust:
+        assert got[0] == ex["n"], (tag, "N", got[0], ex["n"])
+    f = gn_sums.factor(depth)
+    worst = gn_sums.assert_entries([("moment %d" % k, [got[k]], [ex["M"][k]], [f * ex["A_M"][k]]) for k in range(0 if robust else 1, 5)], depth, tag)
     gn_sums.RATIOS.append(("affine moments " + str(tag), worst))
 
 
@@ -165,6 +157,38 @@ def assert_step(got, moments, next_ab, px, a, b, kind, param, s2, depth, guards=
     return ex
 
 
+class EntryChain:
+    """The logged (a, b) of one call against the rule (replay_call here and geometric_affine_ref's): the first entry is the priming pair
+    (ESTIMATE) and every entry the given row (GIVEN) in the device's own bits; a later ESTIMATE entry is the closed form of the moments
+    of the iteration before, inside the propagated bound (assert_next)."""
+
+    def __init__(self, alog, mode, given_ab, guards, tag):
+        self.alog, self.mode, self.guards, self.tag = alog, mode, guards, tag
+        self.prev = None   # (exact sums, (a, b), moment depth) of the iteration before
+        if mode == ESTIMATE:
+            self.want = (F32(alog["prime_a"]), F32(alog["prime_b"]))
+        else:
+            self.want = (F32(1), F32(0)) if given_ab is None else (F32(given_ab[0]), F32(given_ab[1]))
+            assert alog["prime_a"] == 0 and alog["prime_b"] == 0, (tag, "no priming pair in GIVEN mode")
+
+    def prime(self, ex, depth):
+        """the priming pair: the closed form at the start pose from (1, 0) with rho = 1 (ex: the exact moments there)"""
+        assert_next((self.alog["prime_a"], self.alog["prime_b"]), ex, depth, False, self.guards, (F32(1), F32(0)), self.tag + " priming pair")
+
+    def entry(self, st, robust=False):
+        """the checked (a, b) that iteration st of the walker used"""
+        ab = (F32(self.alog["a"][st.l][st.it]), F32(self.alog["b"][st.l][st.it]))
+        if self.prev is None or self.mode != ESTIMATE:   # the priming entry / the given row: the device's own bits
+            assert ab[0].tobytes() == self.want[0].tobytes() and ab[1].tobytes() == self.want[1].tobytes(), (st.where, ab, self.want)
+        else:
+            assert_next(ab, self.prev[0], self.prev[2], robust, self.guards, self.prev[1], st.where + " (entry from the iteration before)")
+        return ab
+
+    def wrote(self, ex, ab, depth):
+        """iteration st ran with the entry ab and left the moments of ex, reduced at `depth`"""
+        self.prev = (ex, ab, depth)
+
+
 def replay_call(log, alog, pixels_at, levels, mode, kind=rr.NONE, param=1.0, rob_mode=rr.ADAPTIVE, floor2=None, given_s2=None,
                 given_ab=None, guards=GUARDS, depth=17, xi0=None, tag=""):
     """One whole tracking call from its track log and its affine log.  pixels_at(level, xi) -> pixels() at that level and input pose.
@@ -175,72 +199,33 @@ def replay_call(log, alog, pixels_at, levels, mode, kind=rr.NONE, param=1.0, rob
     (gn_sums.plan_depths); an entry is held to the depth of the level whose moments it came from.
     Returns (exact sums, (a, b), level, iteration) of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
-    xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
+    walk = term_replay.Replay(log, levels, xi0, tag)
     robust = kind != rr.NONE
-    assert int(alog["levels"]) == levels and [int(n) for n in alog["n_iter"][:levels]] == [int(n) for n in log["n_iter"][:levels]], \
-        (tag, "the affine log is indexed like the track log", alog["n_iter"], log["n_iter"])
-    one = (F32(1), F32(0))
+    term_replay.assert_indexed_like(alog, log, levels, "affine", tag)
+    chain = EntryChain(alog, mode, given_ab, guards, tag)
     if mode == ESTIMATE:
-        px = pixels_at(0, xi)
-        exp = exact(px, 1.0, 0.0)
-        assert_next((alog["prime_a"], alog["prime_b"]), exp, gn_sums.at_level(depth, 0), False, guards, one, tag + " priming pair")
-        want = (F32(alog["prime_a"]), F32(alog["prime_b"]))
-    else:
-        want = one if given_ab is None else (F32(given_ab[0]), F32(given_ab[1]))
-        assert alog["prime_a"] == 0 and alog["prime_b"] == 0, (tag, "no priming pair in GIVEN mode")
+        chain.prime(exact(pixels_at(0, walk.xi), 1.0, 0.0), gn_sums.at_level(depth, 0))
     prev_res = None
-    ex_prev = None
     last = None
-    n_it = 0
-    for l in range(levels):
-        n = int(log["n_iter"][l])
-        assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
-        depth_l = gn_sums.at_level(depth, l)
-        depth_u = depth_l * gn_sums.U32 * gn_sums.SECOND_ORDER
-        for it in range(n):
-            where = "%s level %d iteration %d" % (tag, l, it)
-            ab = (F32(alog["a"][l][it]), F32(alog["b"][l][it]))
-            if ex_prev is None or mode != ESTIMATE:   # the priming entry / the given row: the device's own bits
-                assert ab[0].tobytes() == want[0].tobytes() and ab[1].tobytes() == want[1].tobytes(), (where, ab, want)
-            else:
-                assert_next(ab, ex_prev[0], ex_prev[2], robust, guards, ex_prev[1], where + " (entry from the iteration before)")
-            s2 = rr.INF
-            if robust:
-                s2 = rr.adaptive_s2(prev_res, floor2) if rob_mode == rr.ADAPTIVE else rr.entry(kind, param, given_s2)[3]
-            px = pixels_at(l, xi)
-            assert px["n_valid"] == int(log["n_valid"][l][it]), (where, px["n_valid"], int(log["n_valid"][l][it]))
-            ex = exact(px, ab[0], ab[1], kind, param, s2)
-            res = F32(log["residual"][l][it])
-            upd = log["xi_update"][l][it]
-            if ex["n"] > 0:
-                assert abs(float(res) - ex["sum_r2"] / ex["n"]) <= (depth_u * ex["A_r"] + 2 * float(np.spacing(F32(ex["sum_r2"])))) / ex["n"] \
-                    + float(np.spacing(res)), (where, float(res), ex["sum_r2"] / ex["n"])
-                back = backward_error(ex["H"], ex["g"], upd)
-                assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
-                _nonempty_calls += 1
-            else:
-                assert res == F32(-1.0) and not np.any(upd), where
-            after = np.asarray(log["xi_after"][l][it], F32)
-            if np.all(np.isfinite(orc.se3_concatenate(xi, upd))):
-                assert_composed(xi, upd, after, tag=where)
-            else:
-                assert after.tobytes() == xi.tobytes(), where
-            last = (ex, ab, l, it)
-            ex_prev = (ex, ab, depth_l)
-            prev_res = res
-            xi = after.copy()
-            n_it += 1
-    return last, n_it
+    for st in walk:
+        depth_l = gn_sums.at_level(depth, st.l)
+        ab = chain.entry(st, robust)
+        s2 = rr.INF
+        if robust:
+            s2 = rr.adaptive_s2(prev_res, floor2) if rob_mode == rr.ADAPTIVE else rr.entry(kind, param, given_s2)[3]
+        ex = exact(pixels_at(st.l, st.xi), ab[0], ab[1], kind, param, s2)
+        st.check(ex, gn_sums.factor(depth_l))
+        if ex["n"] > 0:
+            _nonempty_calls += 1
+        last = (ex, ab, st.l, st.it)
+        chain.wrote(ex, ab, depth_l)
+        prev_res = st.res
+    return last, walk.n_it
 
 
 def oracle_pixels(obj, ref, crop, wp):
     """pixels_at for two orc.OFrame"""
     return lambda l, xi: pixels(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop, wp)
-
-
-def _seq_sum(p):
-    """the sum of a float64 vector in index order (np.cumsum accumulates sequentially): the oracle's own double loop"""
-    return float(np.cumsum(p)[-1]) if p.size else 0.0
 
 
 def affine_track(obj, ref, levels, mode, crop, max_iterations, min_update, min_residual=0.0, wp=None, kind=rr.NONE, param=1.0, floor2=None,
@@ -249,43 +234,30 @@ def affine_track(obj, ref, levels, mode, crop, max_iterations, min_update, min_r
     orc.se3_concatenate, the stop tests of tracker.cpp:68-73 and the alternating estimate (priming pair included).  mode GIVEN with
     (1, 0) and kind NONE is orc.track bit for bit.  Returns (xi, log) with log["ab"] the entry every iteration used."""
     wp = weight_params() if wp is None else wp
-    xi = np.zeros(6, F32)
     robust = kind != rr.NONE
     ab = (F32(given_ab[0]), F32(given_ab[1]))
     if mode == ESTIMATE:
-        px = pixels(obj.gray(0), ref.gray(0), ref.depth(0), ref.sigma(0), ref.K(0), xi, 0, crop, wp)
+        px = pixels(obj.gray(0), ref.gray(0), ref.depth(0), ref.sigma(0), ref.K(0), np.zeros(6, F32), 0, crop, wp)
         ex = exact(px, 1.0, 0.0)
         ab, _ = closed_form(ex["n"], ex["M"], ex["n"], guards, (F32(1), F32(0)))
+    prime = ab
     prev = None
-    log = dict(n_iter=[], residual=[], xi_after=[], ab=[], prime=ab)
-    for l in range(levels):
-        res_l, xi_l, ab_l = [], [], []
-        for it in range(max_iterations):
-            px = pixels(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop, wp)
-            s2 = rr.adaptive_s2(prev, floor2) if robust else rr.INF
-            ex = exact(px, ab[0], ab[1], kind, param, s2)
-            ab_l.append(ab)
-            upd = np.zeros(6, F32); res = F32(-1.0)
-            if ex["n"] > 0:
-                t = ex["terms"]
-                J = t["J"].astype(np.float64)
-                Jr = (ex["rho"][:, None] * t["J"]).astype(F32).astype(np.float64) if robust else J
-                H = [_seq_sum(Jr[:, p] * J[:, q]) for p in range(6) for q in range(p, 6)]
-                g = [_seq_sum(Jr[:, p] * t["rw"].astype(np.float64)) for p in range(6)]
-                wr = (ex["rho"] * t["r"]).astype(F32).astype(np.float64) if robust else t["r"].astype(np.float64)
-                sr2 = _seq_sum(wr * t["r"].astype(np.float64))
-                upd = orc.solve6(np.array(H), np.array(g))
-                res = F32(F32(sr2) / F32(ex["n"]))
-            if mode == ESTIMATE:
-                ab, _ = closed_form(ex["M"][0] if robust else ex["n"], ex["M"], ex["n"], guards, ab)
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            prev = res
-            res_l.append(res); xi_l.append(xi.copy())
-            nrm = float(np.sqrt(np.sum(upd.astype(np.float64) ** 2)))
-            if nrm < float(F32(min_update)) or res < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-        log["ab"].append(ab_l)
+
+    def evaluate(l, xi):
+        nonlocal ab, prev
+        px = pixels(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop, wp)
+        s2 = rr.adaptive_s2(prev, floor2) if robust else rr.INF
+        used = ab
+        ex = exact(px, ab[0], ab[1], kind, param, s2)
+        t = ex["terms"]
+        J = t["J"].astype(np.float64)
+        Jr = (ex["rho"][:, None] * t["J"]).astype(F32).astype(np.float64) if robust else J
+        H, g = term_replay.raster_sums(J, Jr, t["rw"].astype(np.float64))
+        wr = (ex["rho"] * t["r"]).astype(F32).astype(np.float64) if robust else t["r"].astype(np.float64)
+        upd, prev = term_replay.gn_step(ex["n"], H, g, term_replay.seq_sum(wr * t["r"].astype(np.float64)))
+        if mode == ESTIMATE:
+            ab, _ = closed_form(ex["M"][0] if robust else ex["n"], ex["M"], ex["n"], guards, ab)
+        return upd, prev, dict(n_valid=ex["n"], ab=used)
+    xi, log = term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
+    log["prime"] = prime
     return xi, log

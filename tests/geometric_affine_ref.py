@@ -10,14 +10,15 @@ values; only the device's reduction differs.
 Reduction depths, from the code (gn_tile with both flags): H and g take the photometric add and the geometric add of every main-loop
 pixel and the photometric add of every deferred pixel, 3 * ppt + 9 as in DESIGN.md §25; sum_r2 keeps 2 * ppt + 9; S29 has ppt + 9; n_geo
 is exact.  The moments are accumulated in the main loop and in the deferred loop and reduced like the 29 sums: 2 * ppt + 9 as in
-DESIGN.md §24.  Nothing here is tuned on a device result.  Test infrastructure only."""
+DESIGN.md §24.  replay_call and geometric_affine_track compose the pieces only: geometric_ref.replay_step / combined_step,
+affine_ref.EntryChain / closed_form, and the log walker and tracking loop of tests/term_replay.py.  Nothing here is tuned on a device
+result.  Test infrastructure only."""
 import numpy as np
 
 import affine_ref as ar
 import geometric_ref as gr
 import gn_sums
-import orc
-from util import TOL_BACKWARD, assert_composed, backward_error
+import term_replay
 
 F32 = np.float32
 ESTIMATE, GIVEN = ar.ESTIMATE, ar.GIVEN
@@ -83,59 +84,21 @@ def replay_call(log, glog, alog, pixels_at, levels, weight, max_diff, mode, give
     ppt: the pixels per thread the levels ran, one value or one per level (Batch.level_plan).
     Returns (exact sums, (a, b)) of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
-    xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
-    iters = [int(n) for n in log["n_iter"][:levels]]
-    assert int(glog["levels"]) == levels and [int(n) for n in glog["n_iter"][:levels]] == iters, (tag, "geometric log", glog["n_iter"], iters)
-    assert int(alog["levels"]) == levels and [int(n) for n in alog["n_iter"][:levels]] == iters, (tag, "affine log", alog["n_iter"], iters)
-    one = (F32(1), F32(0))
+    walk = term_replay.Replay(log, levels, xi0, tag)
+    term_replay.assert_indexed_like(glog, log, levels, "geometric", tag)
+    term_replay.assert_indexed_like(alog, log, levels, "affine", tag)
+    chain = ar.EntryChain(alog, mode, given_ab, guards, tag)
     if mode == ESTIMATE:
-        exp = exact(pixels_at(0, xi), weight, max_diff, 1.0, 0.0)
-        ar.assert_next((alog["prime_a"], alog["prime_b"]), exp, moment_depth(gn_sums.at_level(ppt, 0)), False, guards, one, tag + " priming pair")
-        want = (F32(alog["prime_a"]), F32(alog["prime_b"]))
-    else:
-        want = one if given_ab is None else (F32(given_ab[0]), F32(given_ab[1]))
-        assert alog["prime_a"] == 0 and alog["prime_b"] == 0, (tag, "no priming pair in GIVEN mode")
-    ex_prev = None
+        chain.prime(exact(pixels_at(0, walk.xi), weight, max_diff, 1.0, 0.0), moment_depth(gn_sums.at_level(ppt, 0)))
     last = None
-    n_it = 0
-    for l in range(levels):
-        assert iters[l] >= 1, "%s: level %d ran no iteration" % (tag, l)
-        _, dr, dS = gr.depths(gn_sums.at_level(ppt, l))
-        dM = moment_depth(gn_sums.at_level(ppt, l))
-        fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
-        for it in range(iters[l]):
-            where = "%s level %d iteration %d" % (tag, l, it)
-            ab = (F32(alog["a"][l][it]), F32(alog["b"][l][it]))
-            if ex_prev is None or mode != ESTIMATE:   # the priming entry / the given row: the device's own bits
-                assert ab[0].tobytes() == want[0].tobytes() and ab[1].tobytes() == want[1].tobytes(), (where, ab, want)
-            else:
-                ar.assert_next(ab, ex_prev[0], ex_prev[2], False, guards, ex_prev[1], where + " (entry from the iteration before)")
-            ex = exact(pixels_at(l, xi), weight, max_diff, ab[0], ab[1])
-            assert ex["n"] == int(log["n_valid"][l][it]), (where, "n_valid", ex["n"], int(log["n_valid"][l][it]))
-            assert ex["n_geo"] == int(glog["n_geo"][l][it]), (where, "n_geo", ex["n_geo"], int(glog["n_geo"][l][it]))
-            s29 = F32(glog["sum_sq"][l][it])
-            assert abs(float(s29) - ex["S29"]) <= fS * ex["S29"] + float(np.spacing(s29)), (where, "S29", float(s29), ex["S29"])
-            res = F32(log["residual"][l][it])
-            upd = log["xi_update"][l][it]
-            if ex["n"] > 0:
-                assert abs(float(res) - ex["sum_r2"] / ex["n"]) <= (fr * ex["A_r"] + 2 * float(np.spacing(F32(ex["sum_r2"])))) / ex["n"] \
-                    + float(np.spacing(res)), (where, float(res), ex["sum_r2"] / ex["n"])
-                back = backward_error(ex["H"], ex["g"], upd)
-                assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
-                if ex["n_geo"] > 0:
-                    _nonempty_calls += 1
-            else:
-                assert res == F32(-1.0) and not np.any(upd), where
-            after = np.asarray(log["xi_after"][l][it], F32)
-            if np.all(np.isfinite(orc.se3_concatenate(xi, upd))):
-                assert_composed(xi, upd, after, tag=where)
-            else:
-                assert after.tobytes() == xi.tobytes(), where
-            last = (ex, ab)
-            ex_prev = (ex, ab, dM)
-            xi = after.copy()
-            n_it += 1
-    return last, n_it
+    for st in walk:
+        ab = chain.entry(st)
+        ex = exact(pixels_at(st.l, st.xi), weight, max_diff, ab[0], ab[1])
+        if gr.replay_step(st, glog, ex, ppt):
+            _nonempty_calls += 1
+        last = (ex, ab)
+        chain.wrote(ex, ab, moment_depth(gn_sums.at_level(ppt, st.l)))
+    return last, walk.n_it
 
 
 def frame_pixels(obj, ref, crop, wp):
@@ -159,44 +122,23 @@ def geometric_affine_track(obj, ref, levels, weight, max_diff, mode, crop, max_i
     bit for bit.  Returns (xi, log) with log["ab"] the entry every iteration used."""
     wp = gr.weight_params() if wp is None else wp
     at = frame_pixels(obj, ref, crop, wp)
-    seq = gr._seq_sum
-    xi = np.zeros(6, F32)
     ab = (F32(given_ab[0]), F32(given_ab[1]))
     if mode == ESTIMATE:
-        m = ar.exact(at(0, xi)["aff"], 1.0, 0.0)
+        m = ar.exact(at(0, np.zeros(6, F32))["aff"], 1.0, 0.0)
         ab, _ = ar.closed_form(m["n"], m["M"], m["n"], guards, (F32(1), F32(0)))
-    log = dict(n_iter=[], residual=[], xi_after=[], n_valid=[], n_geo=[], ab=[], prime=ab)
-    for l in range(levels):
-        res_l, xi_l, nv_l, ng_l, ab_l = [], [], [], [], []
-        for it in range(max_iterations):
-            px = at(l, xi)
-            m = ar.exact(px["aff"], ab[0], ab[1])
-            t = m["terms"]
-            ab_l.append(ab)
-            upd = np.zeros(6, F32); res = F32(-1.0)
-            n_geo = 0
-            if t["n_valid"] > 0:
-                J = t["J"].astype(np.float64); rw = t["rw"].astype(np.float64); r = t["r"].astype(np.float64)
-                H = np.array([seq(J[:, p] * J[:, q]) for p in range(6) for q in range(p, 6)])
-                g = np.array([seq(J[:, p] * rw) for p in range(6)])
-                Jg, rg, rgw, on = gr.rows(px, weight, max_diff)
-                n_geo = int(on.sum())
-                Jd = Jg.astype(np.float64); wd = rgw.astype(np.float64)
-                H = H + np.array([seq(Jd[:, p] * Jd[:, q]) for p in range(6) for q in range(p, 6)])
-                g = g + np.array([seq(Jd[:, p] * wd) for p in range(6)])
-                upd = orc.solve6(H, g)
-                res = F32(F32(seq(r * r)) / F32(t["n_valid"]))
-            if mode == ESTIMATE:
-                ab, _ = ar.closed_form(m["n"], m["M"], m["n"], guards, ab)
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            res_l.append(res); xi_l.append(xi.copy()); nv_l.append(t["n_valid"]); ng_l.append(n_geo)
-            nrm = float(np.sqrt(np.sum(upd.astype(np.float64) ** 2)))
-            if nrm < float(F32(min_update)) or res < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-        log["n_valid"].append(np.array(nv_l)); log["n_geo"].append(np.array(ng_l)); log["ab"].append(ab_l)
+    prime = ab
+
+    def evaluate(l, xi):
+        nonlocal ab
+        px = at(l, xi)
+        used = ab
+        m = ar.exact(px["aff"], ab[0], ab[1])
+        upd, res, n_geo = gr.combined_step(px, m["terms"], weight, max_diff)
+        if mode == ESTIMATE:
+            ab, _ = ar.closed_form(m["n"], m["M"], m["n"], guards, ab)
+        return upd, res, dict(n_valid=m["terms"]["n_valid"], n_geo=n_geo, ab=used)
+    xi, log = term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
+    log["prime"] = prime
     return xi, log
 
 

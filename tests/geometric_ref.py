@@ -12,13 +12,15 @@ Reduction depth (gn_sums.reduction_depth counts the float32 roundings on the lon
 accumulations per pixel into slots 0..26 (the photometric add, then the geometric one), its deferred loop still one (deferred pixels
 have no geometric row): 2 * ppt + ppt, then the 6 + 3 of the wave and workgroup steps -- 3 * ppt + 9 (21 for ppt = 4) for H and g.
 sum_r2 (slot 27) keeps the plain depth 2 * ppt + 9; S29 has ppt fmafs, a six-step butterfly and three additions: ppt + 9.  n_geo is a
-sum of ones below 2^24: exact.  Nothing here is tuned on a device result.  Test infrastructure only."""
+sum of ones below 2^24: exact.  This module owns the geometric rows, their exact sums and what a geometric log adds to a replayed
+iteration (replay_step, shared with geometric_affine_ref); the per-entry bound loop is gn_sums.assert_entries, the log walker and the
+tracking loop are tests/term_replay.py's.  Nothing here is tuned on a device result.  Test infrastructure only."""
 import numpy as np
 
 import gn_sums
 import orc
 import robust_ref as rr
-from util import TOL_BACKWARD, assert_composed, backward_error
+import term_replay
 
 F32 = np.float32
 OFF, ON = 0, 1
@@ -187,22 +189,13 @@ def assert_exact(got, ex, ppt=4, tag=""):
     dH, dr, dS = depths(ppt)
     bH, bg, _ = gn_sums.bounds(ex, dH)
     br = gn_sums.bounds(ex, dr)[2]
-    bS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER * ex["S29"]
+    bS = gn_sums.factor(dS) * ex["S29"]
     # (S29 as a float of the log: one more rounding)
     bS += float(np.spacing(F32(ex["S29"]))) if got.get("sum_sq_is_float") else 0.0
-    worst = 0.0
-    for name, val, ref, bnd in (("H", got["H"], ex["H"], bH), ("g", got["g"], ex["g"], bg), ("sum_r2", [got["sum_r2"]], [ex["sum_r2"]], [br]),
-                                ("S29", [got["sum_sq"]], [ex["S29"]], [bS])):
-        val = np.asarray(val, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel(); bnd = np.asarray(bnd, np.float64).ravel()
-        assert np.isfinite(val).all(), "%s: %s of the device is not finite" % (tag, name)
-        assert np.isfinite(bnd).all() and np.isfinite(ref).all(), "%s: the reference terms of %s are not finite" % (tag, name)
-        for k in range(val.size):
-            if bnd[k] == 0.0:
-                assert val[k] == 0.0, "%s: %s[%d] = %r, but every term of it is zero" % (tag, name, k, val[k])
-                continue
-            ratio = abs(val[k] - ref[k]) / bnd[k]
-            assert ratio <= 1.0, "%s: %s[%d] = %.17g, exact %.17g: %.3g times the bound %.3g" % (tag, name, k, val[k], ref[k], ratio, bnd[k])
-            worst = max(worst, float(ratio))
+    groups = gn_sums.sum_groups(got, ex, bH, bg, br) + [("S29", [got["sum_sq"]], [ex["S29"]], [bS])]
+    for name, val, _, _ in groups:
+        assert np.isfinite(np.asarray(val, np.float64)).all(), "%s: %s of the device is not finite" % (tag, name)
+    worst = gn_sums.assert_entries(groups, "%d for H and g, %d for sum_r2, %d for S29" % (dH, dr, dS), tag)
     gn_sums.RATIOS.append(("geometric " + str(tag), worst))
     return worst
 
@@ -224,44 +217,26 @@ def replay_call(log, glog, pixels_at, levels, weight, max_diff, ppt=4, xi0=None,
     ppt: the pixels per thread the levels ran, one value or one per level (Batch.level_plan).
     Returns the exact sums of the last iteration and the number of iterations replayed."""
     global _nonempty_calls
-    xi = np.zeros(6, F32) if xi0 is None else np.asarray(xi0, F32).copy()
-    assert int(glog["levels"]) == levels and [int(n) for n in glog["n_iter"][:levels]] == [int(n) for n in log["n_iter"][:levels]], \
-        (tag, "the geometric log is indexed like the track log", glog["n_iter"], log["n_iter"])
+    walk = term_replay.Replay(log, levels, xi0, tag)
+    term_replay.assert_indexed_like(glog, log, levels, "geometric", tag)
     last = None
-    n_it = 0
-    for l in range(levels):
-        n = int(log["n_iter"][l])
-        assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
-        _, dr, dS = depths(gn_sums.at_level(ppt, l))
-        fr = dr * gn_sums.U32 * gn_sums.SECOND_ORDER; fS = dS * gn_sums.U32 * gn_sums.SECOND_ORDER
-        for it in range(n):
-            where = "%s level %d iteration %d" % (tag, l, it)
-            px = pixels_at(l, xi)
-            ex = exact(px, weight, max_diff)
-            assert ex["n"] == int(log["n_valid"][l][it]), (where, "n_valid", ex["n"], int(log["n_valid"][l][it]))
-            assert ex["n_geo"] == int(glog["n_geo"][l][it]), (where, "n_geo", ex["n_geo"], int(glog["n_geo"][l][it]))
-            s29 = F32(glog["sum_sq"][l][it])
-            assert abs(float(s29) - ex["S29"]) <= fS * ex["S29"] + float(np.spacing(s29)), (where, "S29", float(s29), ex["S29"])
-            res = F32(log["residual"][l][it])
-            upd = log["xi_update"][l][it]
-            if ex["n"] > 0:
-                assert abs(float(res) - ex["sum_r2"] / ex["n"]) <= (fr * ex["A_r"] + 2 * float(np.spacing(F32(ex["sum_r2"])))) / ex["n"] \
-                    + float(np.spacing(res)), (where, float(res), ex["sum_r2"] / ex["n"])
-                back = backward_error(ex["H"], ex["g"], upd)
-                assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
-                if ex["n_geo"] > 0:
-                    _nonempty_calls += 1
-            else:
-                assert res == F32(-1.0) and not np.any(upd), where
-            after = np.asarray(log["xi_after"][l][it], F32)
-            if np.all(np.isfinite(orc.se3_concatenate(xi, upd))):
-                assert_composed(xi, upd, after, tag=where)
-            else:
-                assert after.tobytes() == xi.tobytes(), where
-            last = ex
-            xi = after.copy()
-            n_it += 1
-    return last, n_it
+    for st in walk:
+        last = ex = exact(pixels_at(st.l, st.xi), weight, max_diff)
+        if replay_step(st, glog, ex, ppt):
+            _nonempty_calls += 1
+    return last, walk.n_it
+
+
+def replay_step(st, glog, ex, ppt):
+    """One iteration of term_replay's walker with a geometric log: n_geo EQUALS the replica's and the logged (float)S29 is inside the
+    reduction bound, then the walker's own checks at sum_r2's depth.  True where the evaluation had a geometric row."""
+    _, dr, dS = depths(gn_sums.at_level(ppt, st.l))
+    n_geo = int(glog["n_geo"][st.l][st.it])
+    assert ex["n_geo"] == n_geo, (st.where, "n_geo", ex["n_geo"], n_geo)
+    s29 = F32(glog["sum_sq"][st.l][st.it])
+    assert abs(float(s29) - ex["S29"]) <= gn_sums.factor(dS) * ex["S29"] + float(np.spacing(s29)), (st.where, "S29", float(s29), ex["S29"])
+    st.check(ex, gn_sums.factor(dr))
+    return ex["n"] > 0 and ex["n_geo"] > 0
 
 
 def frame_pixels(obj, ref, crop, wp, own_depth=True):
@@ -270,9 +245,15 @@ def frame_pixels(obj, ref, crop, wp, own_depth=True):
     return lambda l, xi: pixels(obj.gray(l), src.depth(l), src.sigma(l), ref.gray(l), ref.depth(l), ref.K(l), xi, l, crop, wp)
 
 
-def _seq_sum(p):
-    """the sum of a float64 vector in index order (np.cumsum accumulates sequentially): the oracle's own double loop"""
-    return float(np.cumsum(p)[-1]) if p.size else 0.0
+def combined_step(px, t, weight, max_diff):
+    """(update, residual, n_geo) of one evaluation: the photometric products of the terms t summed in double in raster order (the
+    oracle's own loop), the geometric products of px's rows added to them, orc.solve6; the residual is the photometric one"""
+    J = t["J"].astype(np.float64); rw = t["rw"].astype(np.float64); r = t["r"].astype(np.float64)
+    H, g = term_replay.raster_sums(J, J, rw)
+    Jg, rg, rgw, on = rows(px, weight, max_diff)
+    Jd = Jg.astype(np.float64); wd = rgw.astype(np.float64)
+    Hg, gg = term_replay.raster_sums(Jd, Jd, wd)
+    return term_replay.gn_step(t["n_valid"], H + Hg, g + gg, term_replay.seq_sum(r * r)) + (int(on.sum()),)
 
 
 def geometric_track(obj, ref, levels, weight, max_diff, crop, max_iterations, min_update, min_residual=0.0, wp=None, own_depth=True):
@@ -281,36 +262,12 @@ def geometric_track(obj, ref, levels, weight, max_diff, crop, max_iterations, mi
     weight = 0 with own_depth = False is orc.track bit for bit.  Returns (xi, log)."""
     wp = weight_params() if wp is None else wp
     at = frame_pixels(obj, ref, crop, wp, own_depth)
-    xi = np.zeros(6, F32)
-    log = dict(n_iter=[], residual=[], xi_after=[], n_valid=[], n_geo=[])
-    for l in range(levels):
-        res_l, xi_l, nv_l, ng_l = [], [], [], []
-        for it in range(max_iterations):
-            px = at(l, xi)
-            t = px["terms"]
-            upd = np.zeros(6, F32); res = F32(-1.0)
-            n_geo = 0
-            if t["n_valid"] > 0:
-                J = t["J"].astype(np.float64); rw = t["rw"].astype(np.float64); r = t["r"].astype(np.float64)
-                H = np.array([_seq_sum(J[:, p] * J[:, q]) for p in range(6) for q in range(p, 6)])
-                g = np.array([_seq_sum(J[:, p] * rw) for p in range(6)])
-                Jg, rg, rgw, on = rows(px, weight, max_diff)
-                n_geo = int(on.sum())
-                Jd = Jg.astype(np.float64); wd = rgw.astype(np.float64)
-                H = H + np.array([_seq_sum(Jd[:, p] * Jd[:, q]) for p in range(6) for q in range(p, 6)])
-                g = g + np.array([_seq_sum(Jd[:, p] * wd) for p in range(6)])
-                upd = orc.solve6(H, g)
-                res = F32(F32(_seq_sum(r * r)) / F32(t["n_valid"]))
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            res_l.append(res); xi_l.append(xi.copy()); nv_l.append(t["n_valid"]); ng_l.append(n_geo)
-            nrm = float(np.sqrt(np.sum(upd.astype(np.float64) ** 2)))
-            if nrm < float(F32(min_update)) or res < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-        log["n_valid"].append(np.array(nv_l)); log["n_geo"].append(np.array(ng_l))
-    return xi, log
+
+    def evaluate(l, xi):
+        px = at(l, xi)
+        upd, res, n_geo = combined_step(px, px["terms"], weight, max_diff)
+        return upd, res, dict(n_valid=px["terms"]["n_valid"], n_geo=n_geo)
+    return term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
 
 
 # ---- the outcome scene of DESIGN.md §25: a weakly textured pair with sensor noise ---------------------------------------------------

@@ -110,10 +110,41 @@ def at_level(x, level):
     return x[level] if isinstance(x, (list, tuple)) else x
 
 
+def factor(depth):
+    """depth * 2^-24 * (1 + 2^-10): what multiplies an entry's sum of absolute terms A in its bound"""
+    return depth * U32 * SECOND_ORDER
+
+
 def bounds(ex, depth):
     """the per-entry bounds (H: 21, g: 6, sum_r2) for exact_sums() output"""
-    f = depth * U32 * SECOND_ORDER
+    f = factor(depth)
     return f * ex["A_H"], f * ex["A_g"], f * ex["A_r"]
+
+
+def sum_groups(got, ex, bH, bg, br):
+    """the (name, values, exact, bound) groups of the 28 sums for assert_entries"""
+    return [("H", got["H"], ex["H"], bH), ("g", got["g"], ex["g"], bg), ("sum_r2", [got["sum_r2"]], [ex["sum_r2"]], [br])]
+
+
+def assert_entries(groups, depth, tag=""):
+    """The per-entry bound check, for (name, values, exact, bound) groups of device sums: an entry whose bound is zero (every term of
+    it is zero) must be exactly zero, every other entry has error / bound <= 1.  depth only labels a failure (one value, or text where
+    the groups differ).  Returns the largest ratio (0.0 without entries); the caller records it under its own tag."""
+    worst = 0.0
+    for name, val, ref, bnd in groups:
+        val = np.asarray(val, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel(); bnd = np.asarray(bnd, np.float64).ravel()
+        assert np.isfinite(bnd).all() and np.isfinite(ref).all(), "%s: the reference terms of %s are not finite" % (tag, name)
+        err = np.abs(val - ref)
+        for k in range(val.size):
+            entry = "%s[%d]" % (name, k) if val.size > 1 else name
+            if bnd[k] == 0.0:
+                assert val[k] == 0.0, "%s: %s = %r, but every term of it is zero" % (tag, entry, val[k])
+                continue
+            ratio = err[k] / bnd[k]
+            assert ratio <= 1.0, "%s: %s = %.17g, exact %.17g: error %.3g is %.3g times the bound %.3g (depth %s)" % (
+                tag, entry, val[k], ref[k], err[k], ratio, bnd[k], depth)
+            worst = max(worst, float(ratio))
+    return worst
 
 
 def assert_gn_sums(got, terms, depth, tag=""):
@@ -123,21 +154,7 @@ def assert_gn_sums(got, terms, depth, tag=""):
     global _nonempty_calls
     ex = exact_sums(terms)
     assert int(got["n_valid"]) == ex["n"], "%s: n_valid %d, %d terms" % (tag, int(got["n_valid"]), ex["n"])
-    bH, bg, br = bounds(ex, depth)
-    worst = 0.0
-    for name, val, ref, bnd in (("H", got["H"], ex["H"], bH), ("g", got["g"], ex["g"], bg),
-                                ("sum_r2", [got["sum_r2"]], [ex["sum_r2"]], [br])):
-        val = np.asarray(val, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel(); bnd = np.asarray(bnd, np.float64).ravel()
-        assert np.isfinite(bnd).all() and np.isfinite(ref).all(), "%s: the reference terms of %s are not finite" % (tag, name)
-        err = np.abs(val - ref)
-        for k in range(val.size):
-            if bnd[k] == 0.0:
-                assert val[k] == 0.0, "%s: %s[%d] = %r, but every term of it is zero" % (tag, name, k, val[k])
-                continue
-            ratio = err[k] / bnd[k]
-            assert ratio <= 1.0, "%s: %s[%d] = %.17g, exact %.17g: error %.3g is %.3g times the bound %.3g (depth %d, A = %.6g)" % (
-                tag, name, k, val[k], ref[k], err[k], ratio, bnd[k], depth, bnd[k] / (depth * U32 * SECOND_ORDER))
-            worst = max(worst, float(ratio))
+    worst = assert_entries(sum_groups(got, ex, *bounds(ex, depth)), depth, tag)
     if ex["n"] > 0:
         _nonempty_calls += 1
     RATIOS.append((str(tag), worst))
@@ -180,23 +197,17 @@ def assert_gn_sums_classes(got, terms, depth, tag=""):
     val = np.concatenate([np.asarray(got["H"], np.float64).ravel(), np.asarray(got["g"], np.float64).ravel(), [float(got["sum_r2"])]])
     assert val.size == 28, val.size
     names = ["H[%d]" % k for k in range(21)] + ["g[%d]" % k for k in range(6)] + ["sum_r2"]
-    f = depth * U32 * SECOND_ORDER
-    worst = 0.0
+    finite = []
     for k in range(28):
         p = P[:, k]
         want = sum_class(p)
         if want != ".":
             assert value_class(val[k]) == want, "%s: %s = %r, but the exact sum of its terms is of class %r" % (tag, names[k], val[k], want)
             continue
-        ref = float(p.sum()); A = float(np.abs(p).sum()); bnd = f * A
+        ref = float(p.sum())
         assert np.isfinite(val[k]), "%s: %s = %r, but every term of it is finite (exact %.17g)" % (tag, names[k], val[k], ref)
-        if bnd == 0.0:
-            assert val[k] == 0.0, "%s: %s = %r, but every term of it is zero" % (tag, names[k], val[k])
-            continue
-        ratio = abs(val[k] - ref) / bnd
-        assert ratio <= 1.0, "%s: %s = %.17g, exact %.17g: error %.3g is %.3g times the bound %.3g (depth %d, A = %.6g)" % (
-            tag, names[k], val[k], ref, abs(val[k] - ref), ratio, bnd, depth, A)
-        worst = max(worst, float(ratio))
+        finite.append((names[k], [val[k]], [ref], [factor(depth) * float(np.abs(p).sum())]))
+    worst = assert_entries(finite, depth, tag)
     if n > 0:
         _nonempty_calls += 1
     RATIOS.append((str(tag), worst))

@@ -3,11 +3,14 @@
 The contract's decisions are float32 and integer operations on the logged residual and n_valid, so the decision and lambda chains
 are restated here with numpy float32 operations (each correctly rounded, as the device's) and have the device's bits.  The sums come
 from the oracle (orc.optimize, or the exact sums of orc.optimize_terms), the solve is orc.solve6 on the damped system and the pose
-composition orc.se3_concatenate.  Nothing here is tuned on a device result.  Test infrastructure only."""
+composition orc.se3_concatenate.  lm_track and replay_call are an algorithm of their own (steps are accepted and rejected, a level ends
+on the accepted pose) and stay whole here; only plain_track, the iteration without step control, runs in tests/term_replay.py's loop.
+Nothing here is tuned on a device result.  Test infrastructure only."""
 import numpy as np
 
 import orc
 import robust_ref as rr
+import term_replay
 from util import TOL_BACKWARD, assert_composed, backward_error
 
 F32 = np.float32
@@ -112,21 +115,11 @@ def lm_track(sums_at, levels, P, max_iterations, min_update, min_residual=0.0, f
 
 def plain_track(sums_at, levels, max_iterations, min_update, min_residual=0.0):
     """the plain iteration on the same sums (tracker.cpp:42-73): every step taken.  Returns (xi, evaluations)."""
-    xi = np.zeros(6, F32)
-    n = 0
-    for l in range(levels):
-        for it in range(max_iterations):
-            s = sums_at(l, xi)
-            n += 1
-            upd = orc.solve6(s["H"], s["g"]) if s["n_valid"] > 0 else np.zeros(6, F32)
-            res = residual_of(s["sum_r2"], s["n_valid"])
-            with np.errstate(all="ignore"):
-                nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            if float(np.sqrt(np.sum(upd.astype(np.float64) ** 2))) < float(F32(min_update)) or res < F32(min_residual):
-                break
-    return xi, n
+    def evaluate(l, xi):
+        s = sums_at(l, xi)
+        return term_replay.gn_step(s["n_valid"], s["H"], s["g"], s["sum_r2"]) + (dict(n_valid=s["n_valid"]),)
+    xi, log = term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
+    return xi, sum(log["n_iter"])
 
 
 def replay_call(track_log, lm_log, sums_at, levels, P, max_iterations, min_update, min_residual=0.0, fixed_iterations=0, xi0=None, tag=""):

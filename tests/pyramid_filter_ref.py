@@ -6,8 +6,8 @@ is skipped; S = fmaf((float)k, g, S), correctly rounded (fmaf_k), W += k, one fl
 top-level gray is H applied `culls` times to the converted source gray, the gray of level l - 1 is H of level l; depth, sigma and
 wgt are the plain build's (tests/pyramid_ref.py).  Everything is exact, so the device is held to it bit for bit.
 
-filtered_track is one tracking call on these maps: orc.optimize per level, orc.se3_concatenate and the stop tests of
-tracker.cpp:68-73.  The outcome scene of DESIGN.md §39 lives here too, so that the CPU test recomputes the numbers the GPU test is
+filtered_track is one tracking call on these maps: orc.optimize per level inside the tracking loop of tests/term_replay.py
+(orc.se3_concatenate and the stop tests of tracker.cpp:68-73).  The outcome scene of DESIGN.md §39 lives here too, so that the CPU test recomputes the numbers the GPU test is
 held to.  Test infrastructure only."""
 import numpy as np
 
@@ -139,22 +139,12 @@ def filtered_track(obj, ref, levels, max_iterations, min_update, min_residual=0.
     """One tracking call on two Frames: orc.optimize per level at the running pose, orc.se3_concatenate (a non-finite composition
     leaves the pose), stop on the update norm or the residual (tracker.cpp:68-73).  On plain frames it is orc.track.  (xi, log)."""
     import orc
-    xi = np.zeros(6, F32)
-    log = dict(n_iter=[], residual=[], xi_after=[], n_valid=[], xi_update=[])
-    for l in range(levels):
-        res_l, xi_l, nv_l, up_l = [], [], [], []
-        for _ in range(max_iterations):
-            o = orc.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
-            upd = o["xi_update"]
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            res_l.append(o["residual"]); xi_l.append(xi.copy()); nv_l.append(o["n_valid"]); up_l.append(upd.copy())
-            if float(np.sqrt(np.sum(upd.astype(np.float64) ** 2))) < float(F32(min_update)) or o["residual"] < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-        log["n_valid"].append(np.array(nv_l)); log["xi_update"].append(np.array(up_l, F32))
-    return xi, log
+    import term_replay
+
+    def evaluate(l, xi):
+        o = orc.optimize(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
+        return o["xi_update"], o["residual"], dict(n_valid=o["n_valid"])
+    return term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
 
 
 # ---- the outcome scene of DESIGN.md §39: camera noise on the gray of synth's pairs ---------------------------------------------------

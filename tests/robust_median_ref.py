@@ -3,13 +3,14 @@
 The bin of a residual, the counts, the selection of the median bin and the s2 it gives are integer and float32 operations, restated
 here with numpy on the r of orc.optimize_terms; everything downstream of s2 is tests/robust_ref.py's.  median_track is
 robust_ref.irls_track with this rule and the priming evaluation; replay_call replays a device call from its track log and robust log.
+Both keep the rule only: the tracking loop and the log walker are tests/term_replay.py's.
 Nothing here is tuned on a device result.  Test infrastructure only."""
 import numpy as np
 
 import gn_sums
 import orc
 import robust_ref as rr
-from util import TOL_BACKWARD, assert_composed, backward_error
+import term_replay
 
 NONE, HUBER, STUDENT_T = rr.NONE, rr.HUBER, rr.STUDENT_T
 MEDIAN = 2
@@ -66,27 +67,17 @@ def median_track(obj, ref, levels, kind, param, floor2, crop, max_iterations, mi
     xi = np.zeros(6, F32)
     t = orc.optimize_terms(obj.gray(0), ref.gray(0), ref.depth(0), ref.sigma(0), ref.K(0), xi, 0, crop=crop)
     s2, pm, pn = next_s2(counts(t["r"]), floor2)
-    log = dict(n_iter=[], residual=[], xi_after=[], s2=[], median_bin=[], count=[], prime=(pm, pn))
-    for l in range(levels):
-        res_l, xi_l, s2_l, m_l, n_l = [], [], [], [], []
-        for it in range(max_iterations):
-            t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
-            used = F32(force_s2) if force_s2 is not None else s2
-            ex = rr.exact_sums(t, kind, param, used)
-            s2, m, n = next_s2(counts(t["r"]), floor2)
-            upd = np.zeros(6, F32); res = F32(-1.0)
-            if ex["n"] > 0:
-                upd = orc.solve6(ex["H"], ex["g"])
-                res = F32(F32(ex["sum_r2"]) / F32(ex["n"]))
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            res_l.append(res); xi_l.append(xi.copy()); s2_l.append(rr.entry(kind, param, used)[3]); m_l.append(m); n_l.append(n)
-            nrm = float(np.sqrt(np.sum(upd.astype(np.float64) ** 2)))
-            if nrm < float(F32(min_update)) or res < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-        log["s2"].append(np.array(s2_l, F32)); log["median_bin"].append(m_l); log["count"].append(n_l)
+
+    def evaluate(l, xi):
+        nonlocal s2
+        t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
+        used = F32(force_s2) if force_s2 is not None else s2
+        ex = rr.exact_sums(t, kind, param, used)
+        s2, m, n = next_s2(counts(t["r"]), floor2)
+        upd, res = term_replay.gn_step(ex["n"], ex["H"], ex["g"], ex["sum_r2"])
+        return upd, res, dict(n_valid=ex["n"], s2=rr.entry(kind, param, used)[3], median_bin=m, count=n)
+    xi, log = term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
+    log["prime"] = (pm, pn)
     return xi, log
 
 
@@ -113,40 +104,20 @@ def replay_call(log, rlog, terms_at, levels, kind, param, tag="", depth=17):
     weighted normal equations within TOL_BACKWARD, and the median bin is the one of the reference's own residuals (the device's r is
     the oracle's bit for bit).  Returns (terms, s2, level, it) of the finest level's last iteration and the number of iterations
     replayed."""
-    xi = np.zeros(6, F32)
+    term_replay.assert_indexed_like(rlog, log, levels, "robust", tag, has_levels=False)
+    walk = term_replay.Replay(log, levels, tag=tag)
     last = None
-    n_it = 0
-    for l in range(levels):
-        depth_u = gn_sums.at_level(depth, l) * gn_sums.U32 * gn_sums.SECOND_ORDER
-        n = int(log["n_iter"][l])
-        assert n >= 1 and n == int(rlog["n_iter"][l]), "%s: level %d ran %d iterations, the robust log has %d" % (tag, l, n, int(rlog["n_iter"][l]))
-        for it in range(n):
-            where = "%s level %d iteration %d" % (tag, l, it)
-            s2 = F32(rlog["s2"][l][it])
-            t = terms_at(l, xi)
-            assert t["n_valid"] == int(log["n_valid"][l][it]) == int(rlog["count"][l][it]), (where, t["n_valid"], int(log["n_valid"][l][it]))
-            ex = rr.exact_sums(t, kind, param, s2)
-            res = F32(log["residual"][l][it])
-            upd = log["xi_update"][l][it]
-            if ex["n"] > 0:
-                assert abs(float(res) - ex["sum_r2"] / ex["n"]) <= (depth_u * ex["A_r"] + 2 * float(np.spacing(F32(ex["sum_r2"])))) / ex["n"] \
-                    + float(np.spacing(res)), (where, float(res), ex["sum_r2"] / ex["n"])
-                back = backward_error(ex["H"], ex["g"], upd)
-                assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
-                m_ref = select(counts(t["r"]))[0]
-                m_dev = int(rlog["median_bin"][l][it])
-                assert m_dev == m_ref, (where, m_dev, m_ref)
-            else:
-                assert res == F32(-1.0) and not np.any(upd) and int(rlog["median_bin"][l][it]) == -1, where
-            after = np.asarray(log["xi_after"][l][it], F32)
-            if np.all(np.isfinite(orc.se3_concatenate(xi, upd))):
-                assert_composed(xi, upd, after, tag=where)
-            else:
-                assert after.tobytes() == xi.tobytes(), where
-            last = (t, s2, l, it)
-            xi = after.copy()
-            n_it += 1
-    return last, n_it
+    for st in walk:
+        s2 = F32(rlog["s2"][st.l][st.it])
+        t = terms_at(st.l, st.xi)
+        assert st.n_valid == int(rlog["count"][st.l][st.it]), (st.where, "count", st.n_valid, int(rlog["count"][st.l][st.it]))
+        st.check(rr.exact_sums(t, kind, param, s2), gn_sums.factor(gn_sums.at_level(depth, st.l)))
+        # (an empty evaluation has no median: select() gives -1 there)
+        m_ref = select(counts(t["r"]))[0]
+        m_dev = int(rlog["median_bin"][st.l][st.it])
+        assert m_dev == m_ref, (st.where, m_dev, m_ref)
+        last = (t, s2, st.l, st.it)
+    return last, walk.n_it
 
 
 def edge_slack(r, ulp=4):

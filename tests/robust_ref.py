@@ -3,15 +3,16 @@
 The contract is float32 arithmetic on values the device and the oracle share bit for bit (J[6], r, rw of orc.optimize_terms), so the
 weight rho of every pixel and the weighted per-pixel terms Jr[p] * J[q], Jr[p] * rw, (rho * r) * r are restated here with numpy float32
 operations (each correctly rounded, as the device's) and summed exactly in float64.  Only the device's reduction differs, and its shape
-is the plain kernel's: the per-entry bound is tests/gn_sums.py's, with the depth it reads off the code.  Nothing here is tuned on a
-device result.  Test infrastructure only."""
+is the plain kernel's: the per-entry bound is tests/gn_sums.py's (assert_entries), with the depth it reads off the code.  This module
+owns the weights, the weighted exact sums and the scale rule; replay_call hands them to tests/term_replay.py's walker and irls_track
+to its tracking loop.  Nothing here is tuned on a device result.  Test infrastructure only."""
 from fractions import Fraction
 
 import numpy as np
 
 import gn_sums
 import orc
-from util import TOL_BACKWARD, assert_composed, backward_error
+import term_replay
 
 NONE, HUBER, STUDENT_T = 0, 1, 2
 ADAPTIVE, GIVEN = 0, 1
@@ -98,20 +99,7 @@ def assert_sums(got, terms, kind, param, s2, depth, tag=""):
     global _nonempty_calls
     ex = exact_sums(terms, kind, param, s2)
     assert int(got["n_valid"]) == ex["n"], "%s: n_valid %d, %d terms" % (tag, int(got["n_valid"]), ex["n"])
-    bH, bg, br = gn_sums.bounds(ex, depth)
-    worst = 0.0
-    for name, val, ref, bnd in (("H", got["H"], ex["H"], bH), ("g", got["g"], ex["g"], bg),
-                                ("sum_r2", [got["sum_r2"]], [ex["sum_r2"]], [br])):
-        val = np.asarray(val, np.float64).ravel(); ref = np.asarray(ref, np.float64).ravel(); bnd = np.asarray(bnd, np.float64).ravel()
-        assert np.isfinite(bnd).all() and np.isfinite(ref).all(), "%s: the reference terms of %s are not finite" % (tag, name)
-        for k in range(val.size):
-            if bnd[k] == 0.0:
-                assert val[k] == 0.0, "%s: %s[%d] = %r, but every term of it is zero" % (tag, name, k, val[k])
-                continue
-            ratio = abs(val[k] - ref[k]) / bnd[k]
-            assert ratio <= 1.0, "%s: %s[%d] = %.17g, exact %.17g: %.3g times the bound %.3g (depth %d)" % (
-                tag, name, k, val[k], ref[k], ratio, bnd[k], depth)
-            worst = max(worst, float(ratio))
+    worst = gn_sums.assert_entries(gn_sums.sum_groups(got, ex, *gn_sums.bounds(ex, depth)), depth, tag)
     if ex["n"] > 0:
         _nonempty_calls += 1
     gn_sums.RATIOS.append(("robust " + str(tag), worst))
@@ -134,39 +122,16 @@ def replay_call(log, terms_at, levels, kind, param, mode, floor2=None, given_s2=
     the reduction bound, and the logged update solves the weighted normal equations within TOL_BACKWARD.
     depth: the reduction depth that places the logged residual, one value or one per level (gn_sums.plan_depths).
     Returns (terms, s2) of the finest level's last iteration and the number of iterations replayed."""
-    xi = np.zeros(6, F32)
+    walk = term_replay.Replay(log, levels, tag=tag)
     prev = None
     last = None
-    n_it = 0
-    for l in range(levels):
-        depth_u = gn_sums.at_level(depth, l) * gn_sums.U32 * gn_sums.SECOND_ORDER   # (places the logged residual; the sums go through assert_sums)
-        n = int(log["n_iter"][l])
-        assert n >= 1, "%s: level %d ran no iteration" % (tag, l)
-        for it in range(n):
-            where = "%s level %d iteration %d" % (tag, l, it)
-            s2 = adaptive_s2(prev, floor2) if mode == ADAPTIVE else entry(kind, param, given_s2)[3]
-            t = terms_at(l, xi)
-            assert t["n_valid"] == int(log["n_valid"][l][it]), (where, t["n_valid"], int(log["n_valid"][l][it]))
-            ex = exact_sums(t, kind, param, s2)
-            res = F32(log["residual"][l][it])
-            upd = log["xi_update"][l][it]
-            if ex["n"] > 0:
-                assert abs(float(res) - ex["sum_r2"] / ex["n"]) <= (depth_u * ex["A_r"] + 2 * float(np.spacing(F32(ex["sum_r2"])))) / ex["n"] \
-                    + float(np.spacing(res)), (where, float(res), ex["sum_r2"] / ex["n"])
-                back = backward_error(ex["H"], ex["g"], upd)
-                assert back <= TOL_BACKWARD, (where, "backward error %.3g" % back)
-            else:
-                assert res == F32(-1.0) and not np.any(upd), where
-            after = np.asarray(log["xi_after"][l][it], F32)
-            if np.all(np.isfinite(orc.se3_concatenate(xi, upd))):
-                assert_composed(xi, upd, after, tag=where)
-            else:                                # testXi (tracker.cpp:47-51): the pose is left unchanged
-                assert after.tobytes() == xi.tobytes(), where
-            last = (t, s2, l, it)
-            prev = res
-            xi = after.copy()
-            n_it += 1
-    return last, n_it
+    for st in walk:
+        s2 = adaptive_s2(prev, floor2) if mode == ADAPTIVE else entry(kind, param, given_s2)[3]
+        t = terms_at(st.l, st.xi)
+        st.check(exact_sums(t, kind, param, s2), gn_sums.factor(gn_sums.at_level(depth, st.l)))
+        last = (t, s2, st.l, st.it)
+        prev = st.res
+    return last, walk.n_it
 
 
 def oracle_terms(obj, ref, crop):
@@ -177,25 +142,12 @@ def oracle_terms(obj, ref, crop):
 def irls_track(obj, ref, levels, kind, param, floor2, crop, max_iterations, min_update, min_residual=0.0):
     """A numpy replica of one ADAPTIVE tracking call on the oracle: orc.optimize_terms, the weighted sums in float64, orc.solve6,
     orc.se3_concatenate and the stop tests of tracker.cpp:68-73.  kind = NONE is orc.track.  Returns (xi, log)."""
-    xi = np.zeros(6, F32)
     prev = None
-    log = dict(n_iter=[], residual=[], xi_after=[])
-    for l in range(levels):
-        res_l, xi_l = [], []
-        for it in range(max_iterations):
-            t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
-            ex = exact_sums(t, kind, param, adaptive_s2(prev, floor2) if kind != NONE else INF)
-            upd = np.zeros(6, F32); res = F32(-1.0)
-            if ex["n"] > 0:
-                upd = orc.solve6(ex["H"], ex["g"])
-                res = F32(F32(ex["sum_r2"]) / F32(ex["n"]))
-            nxt = orc.se3_concatenate(xi, upd)
-            if np.all(np.isfinite(nxt)):
-                xi = nxt
-            prev = res
-            res_l.append(res); xi_l.append(xi.copy())
-            nrm = float(np.sqrt(np.sum(upd.astype(np.float64) ** 2)))
-            if nrm < float(F32(min_update)) or res < F32(min_residual):
-                break
-        log["n_iter"].append(len(res_l)); log["residual"].append(np.array(res_l, F32)); log["xi_after"].append(np.array(xi_l, F32))
-    return xi, log
+
+    def evaluate(l, xi):
+        nonlocal prev
+        t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), xi, l, crop=crop)
+        ex = exact_sums(t, kind, param, adaptive_s2(prev, floor2) if kind != NONE else INF)
+        upd, prev = term_replay.gn_step(ex["n"], ex["H"], ex["g"], ex["sum_r2"])
+        return upd, prev, dict(n_valid=ex["n"])
+    return term_replay.track(levels, max_iterations, min_update, min_residual, evaluate)
