@@ -7,7 +7,7 @@ combined normal equations; holes, NaN, +inf and steps in the reference depth tak
 give the same records; sequences that did not track have a zero record and an empty log; every refusal is returned; and on a weakly
 textured pair with sensor noise the default config beats the plain batch.
 
-The shapes are tests/test_gpu_robust.py's (its helpers are imported): 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread --
+The shapes are tests/term_batch.py's (its fixture and driver are shared): 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread --
 levels 40x30 and 80x60 (raster tiles) and 160x120 (32-column 2-D tiles), border queues live on all three -- one case at 328x248 (a
 raster finest level), B = 5, and B = 17 for a solve workgroup boundary and two sub-batches.  Every instantiated (PPT, G, T2D, cam)
 kernel instance runs once on a batch of two."""
@@ -19,141 +19,60 @@ import pytest
 import dvo_amd as dvo
 import geometric_ref as gr
 import gn_sums
-import orc
-import test_gpu_robust as tr
-from test_gpu_robust import CULLS, KH, LEVELS, SIZE, STEPS, TOP, _acts, _cfg, _dev, _frames, _logbits, _wide_idx
+import term_batch as tb
+from term_batch import BAD, CULLS, D_LENS, F32, GEO, KH, LEVELS, SIZE, SKIP, SKIPPED, RESTART, STARTED, TOP, TRACKED
 
 pytestmark = pytest.mark.gpu
-
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED, BAD = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED, dvo.SEQ_BAD_ACTION
-F32 = np.float32
-GEO = dict(weight=10.0, max_diff=0.1)     # the default config
-D_LENS = np.array([0.05, -0.02, 0.001, -0.001, 0.0], F32)
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    """the oracle's step literals follow the config of this file (they enter rw); back to the reference's afterwards"""
-    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
+    with tb.oracle_steps():
+        yield
 
 
 def _wp(cfg=None):
-    return gr.weight_params(cfg if cfg is not None else _cfg())
+    return gr.weight_params(cfg if cfg is not None else tb.cfg())
 
 
-def _maps(size, idx, k, b, ref_depth=None):
-    """(gray, depth, sigma) sequence b is given at push k; ref_depth(k, b, depth) replaces a pushed depth map"""
-    g, d, s = _frames(size)
-    i = idx[k][b]
-    dep = d[i] if ref_depth is None else ref_depth(k, b, d[i].copy())
-    return g[i], dep, s[i]
-
-
-def _raw(m):
-    return np.clip(np.rint(m[0] * 255), 0, 255).astype(np.uint8), np.clip(np.rint(m[1] * 5000), 0, 65535).astype(np.uint16)
-
-
-def _run(cfg, B, idx, geo=None, clear=False, acts=None, kf=False, feed="device", cams=None, size=SIZE, cams_at=None, ref_depth=None, D=None):
-    """idx[k][b]: frame of sequence b at push k.  geo: set_geometric arguments (clear: set, then turned off before the first push).
-    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, world, plan); plan = level_plan of every level once the term is set."""
-    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
-    if kf:
-        bt.set_keyframe_tracking(True)
-    bt.set_track_quality(True)
-    if cams is not None:
-        bt.set_intrinsics(cams)
-    if D is not None:
-        bt.set_distortion(D)
-    if geo:
+def _term(geo, clear=False):
+    """run() keywords of a batch with the geometric term.  geo: set_geometric arguments (clear: set, then turned off before the first push)"""
+    def setup(bt, keep):
         bt.set_geometric(**geo)
         if clear:
             bt.set_geometric(dvo.GEOMETRIC_OFF)
-    plan = [bt.level_plan(l) for l in range(LEVELS)]
-    keep, outs = [], []
-    for k in range(len(idx)):
-        maps = [_maps(size, idx, k, b, ref_depth) for b in range(B)]
-        gi, di, si = (np.ascontiguousarray(np.stack([m[j] for m in maps])) for j in range(3))
-        if acts is not None:
-            bt.set_actions(np.asarray(acts[k], np.uint8))
-        if cams_at is not None and cams_at[0] == k:
-            bt.set_intrinsics(cams_at[1])
-        if feed == "host":
-            bt.push_host(gi, di, si)
-        elif feed in ("raw", "raw_host"):
-            g8 = np.stack([_raw(m)[0] for m in maps]); d16 = np.stack([_raw(m)[1] for m in maps])
-            if feed == "raw_host":
-                bt.push_raw_host(g8, d16)
-            else:
-                import torch
-                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-                torch.cuda.synchronize()
-                keep.append((tg, td))
-                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-        else:
-            t = [_dev(x) for x in (gi, di, si)]
-            keep.append(t)
-            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps, plan=plan)
-        if geo and not clear:
-            o["grec"] = bt.last_geometric()
-            o["glogs"] = [bt.last_geometric_log(b) for b in range(B)]
-        if k > 0 or acts is not None or kf:
-            xi, T = bt.last_poses()
-            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
-            if kf:
-                o["world"] = bt.world_poses()
-        outs.append(o)
-    bt.close()
-    return outs
+    return dict(setup=setup, reads=() if clear else ("geometric",))
 
 
-def _glogbits(gl):
-    return (int(gl["levels"]), tuple(int(n) for n in gl["n_iter"]), gl["n_geo"].tobytes(), gl["sum_sq"].tobytes())
+def _depth_maps(idx, size, ref_depth):
+    """maps of run(): ref_depth(k, b, depth) replaces a pushed depth map"""
+    frame = tb.frame_maps(idx, size)
 
-
-def _same(a, b, geometric=True):
-    assert len(a) == len(b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        np.testing.assert_array_equal(x["status"], y["status"], err_msg="push %d" % k)
-        if "xi" in x:
-            np.testing.assert_array_equal(x["xi"], y["xi"], err_msg="push %d" % k)
-            np.testing.assert_array_equal(x["T"], y["T"], err_msg="push %d" % k)
-            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
-        if "world" in x:
-            for u, v in zip(x["world"], y["world"]):
-                np.testing.assert_array_equal(u, v, err_msg="push %d world" % k)
-        assert x["q"].tobytes() == y["q"].tobytes(), "push %d records" % k
-        if geometric:
-            assert x["grec"].tobytes() == y["grec"].tobytes(), "push %d last_geometric" % k
-            assert [_glogbits(l) for l in x["glogs"]] == [_glogbits(l) for l in y["glogs"]], "push %d geometric logs" % k
+    def maps(k, b):
+        g, d, s = frame(k, b)
+        return g, ref_depth(k, b, d.copy()), s
+    return maps if ref_depth is not None else None
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1: off is today
 @pytest.mark.parametrize("mode", ["plain", "actions", "keyframes"])
 def test_set_and_cleared_is_never_set(mode):
-    kw = dict(acts=_acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
-    cfg = _cfg(keyframe_max_frames=2) if mode == "keyframes" else _cfg()
-    _same(_run(cfg, 5, _wide_idx(5), **kw), _run(cfg, 5, _wide_idx(5), geo=GEO, clear=True, **kw), geometric=False)
+    kw = dict(acts=tb.acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
+    cfg = tb.cfg(keyframe_max_frames=2) if mode == "keyframes" else tb.cfg()
+    tb.same(tb.run(cfg, 5, tb.wide_idx(5), **kw), tb.run(cfg, 5, tb.wide_idx(5), **_term(GEO, clear=True), **kw), families=())
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2, 3: the operator
-def _oframe(m, K=KH):
-    return orc.OFrame(m[0], m[1], m[2], K, LEVELS, CULLS)
-
-
 @pytest.fixture(scope="module")
 def geo_run():
     """three sequences with the default config: the poses the operator tests evaluate at"""
-    return _run(_cfg(), 3, _wide_idx(3), geo=GEO)
+    return tb.run(tb.cfg(), 3, tb.wide_idx(3), **_term(GEO))
 
 
 def test_operator_with_weight_zero_is_the_plain_operator_on_own_depth(geo_run):
-    cfg = _cfg()
-    obj, ref = _oframe(geo_run[1]["maps"][0]), _oframe(geo_run[0]["maps"][0])
-    poses = tr._level_poses(geo_run[1]["logs"][0])
+    cfg = tb.cfg()
+    obj, ref = tb.oframe_of(geo_run[1]["maps"][0]), tb.oframe_of(geo_run[0]["maps"][0])
+    poses = tb.level_poses(geo_run[1]["logs"][0])
     for l in range(LEVELS):
         got = dvo.op_gn_step_geometric(obj.gray(l), obj.depth(l), obj.sigma(l), ref.gray(l), ref.depth(l), ref.K(l), poses[l], l, 0.0, 0.1, cfg=cfg)
         p = dvo.optimize(obj.gray(l), ref.gray(l), obj.depth(l), obj.sigma(l), ref.K(l), poses[l], l, cfg=cfg)
@@ -164,10 +83,10 @@ def test_operator_with_weight_zero_is_the_plain_operator_on_own_depth(geo_run):
 
 
 def test_operator_matches_the_contract(geo_run):
-    cfg = _cfg()
+    cfg = tb.cfg()
     before = gr.nonempty_calls()
-    obj, ref = _oframe(geo_run[1]["maps"][0]), _oframe(geo_run[0]["maps"][0])
-    poses = tr._level_poses(geo_run[1]["logs"][0])
+    obj, ref = tb.oframe_of(geo_run[1]["maps"][0]), tb.oframe_of(geo_run[0]["maps"][0])
+    poses = tb.level_poses(geo_run[1]["logs"][0])
     at = gr.frame_pixels(obj, ref, False, _wp())
     n = cut = 0
     for l in range(LEVELS):
@@ -217,33 +136,17 @@ def _check_sequence(o, b, obj, ref, geo, cfg, ppt, where):
 
 def _replay(cfg, B, geo, acts=None, kf=False, cams=None, size=SIZE, outs=None, min_tracked=None, cams_at=None, ref_depth=None, feed="device",
             D=None, ppt=4, seqs=None, frame_of=None):
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     if outs is None:
-        outs = _run(cfg, B, idx, geo=geo, acts=acts, kf=kf, cams=cams, size=size, cams_at=cams_at, ref_depth=ref_depth, feed=feed, D=D)
+        outs = tb.run(cfg, B, idx, acts=acts, kf=kf, cams=cams, size=size, cams_at=cams_at, feed=feed, D=D, maps=_depth_maps(idx, size, ref_depth),
+                      **_term(geo))
     before = gr.nonempty_calls()
-    frame_of = frame_of or (lambda m, K: _oframe(m, K))
-    ref_of = [None] * B
-    n = n_it = 0
-    for k, o in enumerate(outs):
-        Ks = cams_at[1] if cams_at is not None and k >= cams_at[0] else cams
-        for b in range(B):
-            st = o["status"][b]
-            if st == TRACKED and (seqs is None or b in seqs):
-                K = Ks[b] if Ks is not None else KH
-                kr = ref_of[b]
-                m, _ = _check_sequence(o, b, frame_of(o["maps"][b], K), frame_of(outs[kr]["maps"][b], K), geo, cfg, ppt,
-                                          "push %d seq %d of %d" % (k, b, B))
-                n_it += m
-                n += 1
-            elif st != TRACKED:
-                assert _empty(o, b), (k, b, st)   # SKIPPED / STARTED / BAD_ACTION: a zero record and an empty log
-            if kf:
-                if st == STARTED or (st == TRACKED and o["world"][2][b]):
-                    ref_of[b] = k
-            elif st in (TRACKED, STARTED):
-                ref_of[b] = k
-    want = min_tracked if min_tracked is not None else (len(idx) - 1) * (B if seqs is None else len(seqs))
-    assert n >= want and n_it > 3 * n, (n, n_it)
+    frame_of = frame_of or tb.oframe_of
+
+    def check(k, b, kr, o, K):
+        return _check_sequence(o, b, frame_of(o["maps"][b], K), frame_of(outs[kr]["maps"][b], K), geo, cfg, ppt, "push %d seq %d of %d" % (k, b, B))[0]
+    # (SKIPPED / STARTED / BAD_ACTION: a zero record and an empty log)
+    _, n_it = tb.walk(outs, B, check, _empty, kf=kf, cams=cams, cams_at=cams_at, seqs=seqs, min_tracked=min_tracked)
     assert gr.nonempty_calls() >= before + n_it // 2   # (the helper really ran: iterations with geometric rows replayed)
     return outs
 
@@ -251,39 +154,36 @@ def _replay(cfg, B, geo, acts=None, kf=False, cams=None, size=SIZE, outs=None, m
 @pytest.mark.parametrize("B", [5, 17])
 def test_replay(B):
     """B = 17: k_gn_solve_z takes 8 sequences per workgroup, so the third workgroup holds one"""
-    _replay(_cfg(), B, GEO, seqs=None if B == 5 else (0, 7, 8, 15, 16))
+    _replay(tb.cfg(), B, GEO, seqs=None if B == 5 else (0, 7, 8, 15, 16))
 
 
 def test_replay_raster_finest_level():
-    _replay(_cfg(), 5, GEO, size=(328, 248), seqs=(0, 3))
+    _replay(tb.cfg(), 5, GEO, size=(328, 248), seqs=(0, 3))
 
 
 def test_replay_other_weight_and_gate():
-    _replay(_cfg(), 5, dict(weight=1.0, max_diff=0.01), seqs=(1, 4))
+    _replay(tb.cfg(), 5, dict(weight=1.0, max_diff=0.01), seqs=(1, 4))
 
 
 def test_replay_keyframes():
-    _replay(_cfg(keyframe_max_frames=2), 5, GEO, kf=True)
+    _replay(tb.cfg(keyframe_max_frames=2), 5, GEO, kf=True)
 
 
 def test_replay_per_sequence_intrinsics():
-    cams = np.stack([KH] * 5).astype(F32)
-    for b in range(5):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    _replay(_cfg(), 5, GEO, cams=cams)
+    _replay(tb.cfg(), 5, GEO, cams=tb.sequence_cams(5))
 
 
 def test_replay_sensor_undistortion():
     """the frames the batch tracks are dvo_op_undistort of the pushed maps (tests/test_gpu_sensor_undistort.py holds that equality)"""
-    und = lambda m, K: _oframe(tuple(dvo.undistort(x, K, D_LENS) for x in m), K)
-    _replay(_cfg(), 5, GEO, D=D_LENS, seqs=(0, 2), frame_of=und)
+    und = lambda m, K: tb.oframe_of(tuple(dvo.undistort(x, K, D_LENS) for x in m), K)
+    _replay(tb.cfg(), 5, GEO, D=D_LENS, seqs=(0, 2), frame_of=und)
 
 
 def test_replay_raw_feed():
     """raw frames: the maps are dvo_op_ingest of the u8 / u16 frames, and every contributing pixel carries the one weight of sigma 0.1"""
-    raw = lambda m, K: _oframe(dvo.ingest(*_raw(m)), K)
-    a = _replay(_cfg(), 5, GEO, feed="raw", seqs=(0, 3), frame_of=raw)
-    _same(a, _run(_cfg(), 5, _wide_idx(5), geo=GEO, feed="raw_host"))
+    raw = lambda m, K: tb.oframe_of(dvo.ingest(*tb.raw_of(m)), K)
+    a = _replay(tb.cfg(), 5, GEO, feed="raw", seqs=(0, 3), frame_of=raw)
+    tb.same(a, tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw_host", **_term(GEO)))
 
 
 @pytest.mark.parametrize("cam", [False, True])
@@ -291,7 +191,7 @@ def test_replay_raw_feed():
 def test_every_kernel_instance(ppt, group, cam):
     """each (PPT, G) pair of k_track_gn_z and k_track_gn_z_cam on a batch of two: the 160x120 level takes the 2-D tiles of PPT = 4, the
     two coarser levels the raster tiles"""
-    cfg = _cfg(gn_gather_group=group)
+    cfg = tb.cfg(gn_gather_group=group)
     cfg.gn_pixels_per_thread = ppt    # (_cfg fixes 4 pixels per thread)
     cams = np.stack([KH, KH]).astype(F32) if cam else None
     if cam:
@@ -300,28 +200,17 @@ def test_every_kernel_instance(ppt, group, cam):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5: the gates
-def _defect(d, kind):
-    """a block of the depth map d (rows h/4 .. h/2, columns w/4 .. w/2) becomes a hole, NaN, +inf or steps back by 0.5 m; returns its size"""
-    h, w = d.shape
-    blk = (slice(h // 4, h // 2), slice(w // 4, w // 2))
-    if kind == "step":
-        d[blk] += F32(0.5)
-    else:
-        d[blk] = dict(hole=0.0, nan=np.nan, inf=np.inf)[kind]
-    return (h // 2 - h // 4) * (w // 2 - w // 4)
-
-
 @pytest.mark.parametrize("defect", ["hole", "nan", "inf", "step"])
 def test_gates_of_the_reference_depth(defect, geo_run):
     """A block of the reference's depth is a hole (zeros), NaN, +inf or a step of 0.5 m (> max_diff): at every level n_geo equals the
     replica's and is below the clean reference's by about the block, n_valid and sum_r2 are the clean ones, every sum is finite."""
-    cfg = _cfg()
+    cfg = tb.cfg()
     before = gr.nonempty_calls()
-    obj, ref = _oframe(geo_run[1]["maps"][0]), _oframe(geo_run[0]["maps"][0])
-    poses = tr._level_poses(geo_run[1]["logs"][0])
+    obj, ref = tb.oframe_of(geo_run[1]["maps"][0]), tb.oframe_of(geo_run[0]["maps"][0])
+    poses = tb.level_poses(geo_run[1]["logs"][0])
     for l in range(LEVELS):
         bad = ref.depth(l).copy()
-        n_blk = _defect(bad, defect)
+        n_blk = tb.defect(bad, defect)
         clean = dvo.op_gn_step_geometric(obj.gray(l), obj.depth(l), obj.sigma(l), ref.gray(l), ref.depth(l), ref.K(l), poses[l], l, 10.0, 0.1, cfg=cfg)
         got = dvo.op_gn_step_geometric(obj.gray(l), obj.depth(l), obj.sigma(l), ref.gray(l), bad, ref.K(l), poses[l], l, 10.0, 0.1, cfg=cfg)
         px = gr.pixels(obj.gray(l), obj.depth(l), obj.sigma(l), ref.gray(l), bad, ref.K(l), poses[l], l, False, _wp())
@@ -336,41 +225,41 @@ def test_gates_of_the_reference_depth(defect, geo_run):
 def test_gates_in_a_batch(defect):
     """the same defects in the frames a batch is given (every push, so in the tracked frame's own depth as well): the replay holds"""
     def ref_depth(k, b, d):
-        _defect(d, defect)
+        tb.defect(d, defect)
         return d
-    _replay(_cfg(), 5, GEO, ref_depth=ref_depth, seqs=(0, 2))
+    _replay(tb.cfg(), 5, GEO, ref_depth=ref_depth, seqs=(0, 2))
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6: the schedules
 @pytest.fixture(scope="module")
 def base5():
-    return _run(_cfg(), 5, _wide_idx(5), geo=GEO)
+    return tb.run(tb.cfg(), 5, tb.wide_idx(5), **_term(GEO))
 
 
 @pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "host_feed"])
 def test_schedule_variants_give_the_same_records(variant, base5):
-    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1)).get(variant, {})
-    other = _run(_cfg(**kw), 5, _wide_idx(5), geo=GEO, feed="host" if variant == "host_feed" else "device")
-    _same(base5, other)
+    other = tb.run(tb.cfg(**tb.SCHEDULE_VARIANTS.get(variant, {})), 5, tb.wide_idx(5), feed="host" if variant == "host_feed" else "device",
+                   **_term(GEO))
+    tb.same(base5, other)
     assert all((o["grec"]["n_geo"] > 1000).all() for o in base5[1:])
 
 
 def test_two_streams():
     """two sub-batches need more than 16 sequences (17: not a multiple of 8 either); the depth base, the record and the log are offset
     per sub-batch"""
-    one = _run(_cfg(), 17, _wide_idx(17), geo=GEO)
-    two = _run(_cfg(track_streams=2), 17, _wide_idx(17), geo=GEO)
-    _same(one, two)
+    one = tb.run(tb.cfg(), 17, tb.wide_idx(17), **_term(GEO))
+    two = tb.run(tb.cfg(track_streams=2), 17, tb.wide_idx(17), **_term(GEO))
+    tb.same(one, two)
     assert all((o["grec"]["n_geo"] > 1000).all() for o in one[1:])
 
 
 # ------------------------------------------------------------------------------------------------------------------ 7: lifecycle
 def test_actions_leave_no_stale_record():
     """SKIP, RESTART and a bad action give a zero record and an empty log (checked in _replay); the tracked ones replay"""
-    acts = _acts(5, 3, 9)
+    acts = tb.acts(5, 3, 9)
     assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
     acts[2][1] = 7   # an action outside the set: BAD_ACTION, handled as SKIP
-    outs = _replay(_cfg(), 5, GEO, acts=acts, min_tracked=3)
+    outs = _replay(tb.cfg(), 5, GEO, acts=acts, min_tracked=3)
     assert outs[2]["status"][1] == BAD and (np.concatenate([o["status"] for o in outs]) == SKIPPED).any()
 
 
@@ -378,14 +267,14 @@ def test_camera_change_restarts_the_sequence():
     cams = np.stack([KH] * 5).astype(F32)
     new = cams.copy()
     new[2, 0, 0] *= 1.02
-    outs = _replay(_cfg(), 5, GEO, cams=cams, cams_at=(2, new), min_tracked=8)
+    outs = _replay(tb.cfg(), 5, GEO, cams=cams, cams_at=(2, new), min_tracked=8)
     assert outs[2]["status"][2] == STARTED and (outs[2]["status"][[0, 1, 3, 4]] == TRACKED).all()
 
 
 # ------------------------------------------------------------------------------------------------------------------ 8: refusals
 def test_errors_are_refused():
     L = dvo.lib()
-    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
     GC = dvo.GeometricConfig
     sz = C.sizeof(GC)
     bad = [GC(sz, 2, 10.0, 0.1), GC(sz, -1, 10.0, 0.1), GC(sz, 1, -1.0, 0.1), GC(sz, 1, float("nan"), 0.1), GC(sz, 1, float("inf"), 0.1),
@@ -420,15 +309,15 @@ def test_errors_are_refused():
     lg = dvo.GeometricLog()
     assert L.dvo_batch_last_geometric_log(bt._p, 0, C.byref(lg)) == dvo.DVO_ERR_BAD_ARGUMENT    # struct_size not set
     bt.set_geometric(None)
-    g, d, s = _frames()
-    t = [_dev(x[:2]) for x in (g, d, s)]
+    g, d, s = tb.frames()
+    t = [tb.dev(x[:2]) for x in (g, d, s)]
     bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     with pytest.raises(dvo.DvoError):
         bt.last_geometric()                         # the push ran without the feature
     bt.set_geometric(**GEO)
     with pytest.raises(dvo.DvoError):
         bt.last_geometric()                         # enabled from the next push on
-    t2 = [_dev(x[1:3]) for x in (g, d, s)]
+    t2 = [tb.dev(x[1:3]) for x in (g, d, s)]
     bt.push_device(t2[0].data_ptr(), t2[1].data_ptr(), t2[2].data_ptr())
     assert (bt.last_geometric()["n_geo"] > 1000).all()
     with pytest.raises(dvo.DvoError):
@@ -471,7 +360,7 @@ def test_default_config_beats_plain_on_a_weakly_textured_pair():
             c = dvo.geometric_default_config()
             bt.set_geometric(c.mode, c.weight, c.max_diff)
         for k in (0, 1):
-            t = [_dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
+            t = [tb.dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
             bt.synchronize()
         xi, _ = bt.last_poses()

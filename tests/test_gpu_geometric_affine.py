@@ -10,170 +10,77 @@ and nothing else; the schedules give the same records and logs; sequences that d
 turning one term off leaves the other family's batch; every refusal is returned; and under an exposure change on a weakly textured
 pair the composed batch beats the geometric one.
 
-The shapes are tests/test_gpu_robust.py's (its helpers are imported): 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread --
+The shapes are tests/term_batch.py's (its fixture and driver are shared): 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread --
 levels 40x30 and 80x60 (raster tiles) and 160x120 (32-column 2-D tiles), border queues live on all three -- one case at 328x248 (a
 raster finest level), B = 5, and B = 17 for a solve workgroup boundary and two sub-batches.  The frames a batch sees carry an exposure
-change per push and sequence (tests/test_gpu_affine.py's EXPO), so that the entries are far from (1, 0).  Every instantiated (PPT, G,
+change per push and sequence (tests/term_batch.py's EXPO), so that the entries are far from (1, 0).  Every instantiated (PPT, G,
 T2D, cam) kernel instance runs once on a batch of two."""
 import ctypes as C
 
 import numpy as np
 import pytest
 
-import affine_ref as ar
 import dvo_amd as dvo
 import geometric_affine_ref as ga
 import geometric_ref as gr
 import gn_sums
-import orc
-import test_gpu_robust as tr
-from test_gpu_affine import EXPO, _alogbits
-from test_gpu_geometric import D_LENS, _defect, _glogbits, _raw
-from test_gpu_robust import CULLS, KH, LEVELS, SIZE, STEPS, TOP, _acts, _cfg, _dev, _frames, _logbits, _wide_idx
+import term_batch as tb
+from term_batch import BAD, CULLS, D_LENS, F32, GEO, KH, LEVELS, SIZE, SKIP, SKIPPED, RESTART, STARTED, TOP, TRACKED
 
 pytestmark = pytest.mark.gpu
 
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED, BAD = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED, dvo.SEQ_BAD_ACTION
 ESTIMATE, GIVEN = dvo.AFFINE_ESTIMATE, dvo.AFFINE_GIVEN
-F32 = np.float32
-GEO = dict(weight=10.0, max_diff=0.1)     # the default geometric config
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    """the oracle's step literals follow the config of this file (they enter rw); back to the reference's afterwards"""
-    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
+    with tb.oracle_steps():
+        yield
 
 
 def _wp(cfg=None):
-    return gr.weight_params(cfg if cfg is not None else _cfg())
+    return gr.weight_params(cfg if cfg is not None else tb.cfg())
 
 
 def _zab(mode=ESTIMATE, rows=None, **geo):
     """setup of a composed batch"""
     geo = geo or GEO
 
-    def setup(bt):
+    def setup(bt, keep):
         bt.set_geometric_affine(affine_mode=mode, **geo)
         if rows is not None:
             bt.set_affine_rows(rows)
     return setup
 
 
-def _z(bt):
+def _z(bt, keep):
     bt.set_geometric(**GEO)
 
 
-def _ab(bt):
+def _ab(bt, keep):
     bt.set_affine_brightness(ESTIMATE)
 
 
-def _maps(size, idx, k, b, expo, ref_depth=None):
-    """(gray, depth, sigma) sequence b is given at push k: the gray under the exposure of the push; ref_depth(k, b, depth) replaces a
-    pushed depth map"""
-    g, d, s = _frames(size)
-    i = idx[k][b]
-    gray = g[i]
-    if expo:
-        a, o = EXPO[k % len(EXPO)]
-        gray = (F32(a * (1.0 + 0.02 * b)) * gray + F32(o)).astype(F32)
-    dep = d[i] if ref_depth is None else ref_depth(k, b, d[i].copy())
-    return gray, dep, s[i]
+def _term(idx, setup, reads=("geometric", "affine"), size=SIZE, ref_depth=None):
+    """run() keywords of a batch with the terms of setup, whose records are read after every push: the gray it is given is under the
+    exposure of the push and sequence; ref_depth(k, b, depth) replaces a pushed depth map"""
+    g, d, s = tb.frames(size)
 
-
-def _run(cfg, B, idx, setup, reads=("geo", "aff"), acts=None, kf=False, feed="device", cams=None, size=SIZE, cams_at=None, ref_depth=None,
-         D=None, expo=True, at=None):
-    """idx[k][b]: frame of sequence b at push k.  setup(bt): the terms of the batch; at = {push: fn(bt)}: called before that push;
-    reads: which families' records and logs are read after every push.
-    Returns per push dict(status, q, maps, xi, T, logs, grec, glogs, ab, alogs, world, plan); plan = level_plan of every level after
-    setup(bt)."""
-    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
-    if kf:
-        bt.set_keyframe_tracking(True)
-    bt.set_track_quality(True)
-    if cams is not None:
-        bt.set_intrinsics(cams)
-    if D is not None:
-        bt.set_distortion(D)
-    setup(bt)
-    plan = [bt.level_plan(l) for l in range(LEVELS)]
-    keep, outs = [], []
-    for k in range(len(idx)):
-        if at and k in at:
-            at[k](bt)
-        maps = [_maps(size, idx, k, b, expo, ref_depth) for b in range(B)]
-        gi, di, si = (np.ascontiguousarray(np.stack([m[j] for m in maps])) for j in range(3))
-        if acts is not None:
-            bt.set_actions(np.asarray(acts[k], np.uint8))
-        if cams_at is not None and cams_at[0] == k:
-            bt.set_intrinsics(cams_at[1])
-        if feed == "host":
-            bt.push_host(gi, di, si)
-        elif feed in ("raw", "raw_host"):
-            g8 = np.stack([_raw(m)[0] for m in maps]); d16 = np.stack([_raw(m)[1] for m in maps])
-            if feed == "raw_host":
-                bt.push_raw_host(g8, d16)
-            else:
-                import torch
-                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-                torch.cuda.synchronize()
-                keep.append((tg, td))
-                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-        else:
-            t = [_dev(x) for x in (gi, di, si)]
-            keep.append(t)
-            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality(), maps=maps, plan=plan)
-        if "geo" in reads:
-            o["grec"] = bt.last_geometric()
-            o["glogs"] = [bt.last_geometric_log(b) for b in range(B)]
-        if "aff" in reads:
-            o["ab"] = bt.last_affine()
-            o["alogs"] = [bt.last_affine_log(b) for b in range(B)]
-        if k > 0 or acts is not None or kf:
-            xi, T = bt.last_poses()
-            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
-            if kf:
-                o["world"] = bt.world_poses()
-        outs.append(o)
-    bt.close()
-    return outs
-
-
-def _same(a, b, families=("geo", "aff"), pushes=None):
-    assert len(a) == len(b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        if pushes is not None and k not in pushes:
-            continue
-        np.testing.assert_array_equal(x["status"], y["status"], err_msg="push %d" % k)
-        if "xi" in x:
-            np.testing.assert_array_equal(x["xi"], y["xi"], err_msg="push %d" % k)
-            np.testing.assert_array_equal(x["T"], y["T"], err_msg="push %d" % k)
-            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
-        if "world" in x:
-            for u, v in zip(x["world"], y["world"]):
-                np.testing.assert_array_equal(u, v, err_msg="push %d world" % k)
-        assert x["q"].tobytes() == y["q"].tobytes(), "push %d records" % k
-        if "geo" in families:
-            assert x["grec"].tobytes() == y["grec"].tobytes(), "push %d last_geometric" % k
-            assert [_glogbits(l) for l in x["glogs"]] == [_glogbits(l) for l in y["glogs"]], "push %d geometric logs" % k
-        if "aff" in families:
-            assert x["ab"].tobytes() == y["ab"].tobytes(), "push %d last_affine" % k
-            assert [_alogbits(l) for l in x["alogs"]] == [_alogbits(l) for l in y["alogs"]], "push %d affine logs" % k
+    def maps(k, b):
+        i = idx[k][b]
+        return tb.expose(g[i], k, b), d[i] if ref_depth is None else ref_depth(k, b, d[i].copy()), s[i]
+    return dict(setup=setup, reads=reads, maps=maps)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1: identity is geometric
 @pytest.mark.parametrize("variant", ["no_rows", "ones"])
 def test_identity_entry_is_the_geometric_batch(variant):
     B = 5
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     rows = np.tile(F32([1.0, 0.0]), (B, 1)) if variant == "ones" else None
-    geo = _run(_cfg(), B, idx, _z, reads=("geo",))
-    got = _run(_cfg(), B, idx, _zab(GIVEN, rows))
-    _same(geo, got, families=("geo",))
+    geo = tb.run(tb.cfg(), B, idx, **_term(idx, _z, reads=("geometric",)))
+    got = tb.run(tb.cfg(), B, idx, **_term(idx, _zab(GIVEN, rows)))
+    tb.same(geo, got, families=("geometric",))
     assert all((o["grec"]["n_geo"] > 1000).all() for o in got[1:])
     for o in got[1:]:
         np.testing.assert_array_equal(o["ab"], np.tile(F32([1.0, 0.0]), (B, 1)))
@@ -185,14 +92,10 @@ def test_identity_entry_is_the_geometric_batch(variant):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 2, 3, 4: the operator
-def _oframe(m, K=KH):
-    return orc.OFrame(m[0], m[1], m[2], K, LEVELS, CULLS)
-
-
 @pytest.fixture(scope="module")
 def zab_run():
     """three sequences with the default config, ESTIMATE: the poses the operator tests evaluate at"""
-    return _run(_cfg(), 3, _wide_idx(3), _zab())
+    return tb.run(tb.cfg(), 3, tb.wide_idx(3), **_term(tb.wide_idx(3), _zab()))
 
 
 def _op(obj, ref, l, xi, weight, max_diff, a, b, cfg, ref_depth=None):
@@ -208,9 +111,9 @@ def _same_result(got, p, where):
 
 
 def test_operator_with_weight_zero_is_the_affine_operator_on_own_depth(zab_run):
-    cfg = _cfg()
-    obj, ref = _oframe(zab_run[1]["maps"][0]), _oframe(zab_run[0]["maps"][0])
-    poses = tr._level_poses(zab_run[1]["logs"][0])
+    cfg = tb.cfg()
+    obj, ref = tb.oframe_of(zab_run[1]["maps"][0]), tb.oframe_of(zab_run[0]["maps"][0])
+    poses = tb.level_poses(zab_run[1]["logs"][0])
     for l in range(LEVELS):
         for a, b in ((0.9, 0.03), (1.2, -0.05)):
             got = _op(obj, ref, l, poses[l], 0.0, 0.1, a, b, cfg)
@@ -221,9 +124,9 @@ def test_operator_with_weight_zero_is_the_affine_operator_on_own_depth(zab_run):
 
 
 def test_operator_with_the_identity_entry_is_the_geometric_operator(zab_run):
-    cfg = _cfg()
-    obj, ref = _oframe(zab_run[1]["maps"][0]), _oframe(zab_run[0]["maps"][0])
-    poses = tr._level_poses(zab_run[1]["logs"][0])
+    cfg = tb.cfg()
+    obj, ref = tb.oframe_of(zab_run[1]["maps"][0]), tb.oframe_of(zab_run[0]["maps"][0])
+    poses = tb.level_poses(zab_run[1]["logs"][0])
     for l in range(LEVELS):
         for weight, max_diff in ((10.0, 0.1), (1.0, 0.001)):
             got = _op(obj, ref, l, poses[l], weight, max_diff, 1.0, 0.0, cfg)
@@ -235,7 +138,7 @@ def test_operator_with_the_identity_entry_is_the_geometric_operator(zab_run):
 @pytest.mark.parametrize("entry", ["0.9_0.03", "1.2_-0.05", "guard"])
 def test_operator_matches_the_contract(entry, zab_run):
     """guard: the tracked frame's gray is one value, so det = 0 fails the contrast guard and the next entry is the entry given"""
-    cfg = _cfg()
+    cfg = tb.cfg()
     before = ga.nonempty_calls()
     mo = zab_run[1]["maps"][0]
     if entry == "guard":
@@ -243,8 +146,8 @@ def test_operator_matches_the_contract(entry, zab_run):
         mo = (np.full_like(mo[0], 0.5), mo[1], mo[2])
     else:
         a, b = (float(v) for v in entry.split("_"))
-    obj, ref = _oframe(mo), _oframe(zab_run[0]["maps"][0])
-    poses = tr._level_poses(zab_run[1]["logs"][0])
+    obj, ref = tb.oframe_of(mo), tb.oframe_of(zab_run[0]["maps"][0])
+    poses = tb.level_poses(zab_run[1]["logs"][0])
     at = ga.frame_pixels(obj, ref, False, _wp())
     n = 0
     for l in range(LEVELS):
@@ -295,31 +198,18 @@ def _check_sequence(o, b, obj, ref, geo, mode, given, cfg, ppt, where):
 
 def _replay(cfg, B, mode=ESTIMATE, given=None, geo=GEO, acts=None, kf=False, cams=None, size=SIZE, outs=None, min_tracked=None, cams_at=None,
             ref_depth=None, feed="device", D=None, ppt=4, seqs=None, frame_of=None):
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     if outs is None:
-        outs = _run(cfg, B, idx, _zab(mode, given, **geo), acts=acts, kf=kf, cams=cams, size=size, cams_at=cams_at, ref_depth=ref_depth, feed=feed, D=D)
+        outs = tb.run(cfg, B, idx, acts=acts, kf=kf, cams=cams, size=size, cams_at=cams_at, feed=feed, D=D,
+                      **_term(idx, _zab(mode, given, **geo), size=size, ref_depth=ref_depth))
     before = ga.nonempty_calls()
-    frame_of = frame_of or (lambda m, K: _oframe(m, K))
-    ref_of = [None] * B
-    n = n_it = 0
-    for k, o in enumerate(outs):
-        Ks = cams_at[1] if cams_at is not None and k >= cams_at[0] else cams
-        for b in range(B):
-            st = o["status"][b]
-            if st == TRACKED and (seqs is None or b in seqs):
-                K = Ks[b] if Ks is not None else KH
-                n_it += _check_sequence(o, b, frame_of(o["maps"][b], K), frame_of(outs[ref_of[b]]["maps"][b], K), geo, mode, given, cfg, ppt,
-                                        "push %d seq %d of %d" % (k, b, B))
-                n += 1
-            elif st != TRACKED:
-                assert _empty(o, b), (k, b, st)   # SKIPPED / STARTED / BAD_ACTION: zero records and empty logs
-            if kf:
-                if st == STARTED or (st == TRACKED and o["world"][2][b]):
-                    ref_of[b] = k
-            elif st in (TRACKED, STARTED):
-                ref_of[b] = k
-    want = min_tracked if min_tracked is not None else (len(idx) - 1) * (B if seqs is None else len(seqs))
-    assert n >= want and n_it > 3 * n, (n, n_it)
+    frame_of = frame_of or tb.oframe_of
+
+    def check(k, b, kr, o, K):
+        return _check_sequence(o, b, frame_of(o["maps"][b], K), frame_of(outs[kr]["maps"][b], K), geo, mode, given, cfg, ppt,
+                               "push %d seq %d of %d" % (k, b, B))
+    # (SKIPPED / STARTED / BAD_ACTION: zero records and empty logs)
+    _, n_it = tb.walk(outs, B, check, _empty, kf=kf, cams=cams, cams_at=cams_at, seqs=seqs, min_tracked=min_tracked)
     assert ga.nonempty_calls() >= before + n_it // 2   # (the helper really ran: iterations with geometric rows replayed)
     return outs
 
@@ -334,38 +224,35 @@ def test_replay(B, mode):
     """B = 17: k_gn_solve_zab takes 8 sequences per workgroup, so the third workgroup holds one"""
     seqs = (0, 3) if B == 5 else (7, 8, 16)
     if mode == "estimate":
-        outs = _replay(_cfg(), B, seqs=seqs)
+        outs = _replay(tb.cfg(), B, seqs=seqs)
         assert all(abs(float(o["alogs"][b]["prime_a"]) - 1.0) > 0.02 for o in outs[1:] for b in seqs)   # the exposure change is seen
     else:
-        _replay(_cfg(), B, GIVEN, _rows(B), seqs=seqs)
+        _replay(tb.cfg(), B, GIVEN, _rows(B), seqs=seqs)
 
 
 def test_replay_raster_finest_level():
-    _replay(_cfg(), 5, size=(328, 248), seqs=(1,))
+    _replay(tb.cfg(), 5, size=(328, 248), seqs=(1,))
 
 
 def test_replay_keyframes():
-    _replay(_cfg(keyframe_max_frames=2), 5, kf=True, seqs=(0, 4))
+    _replay(tb.cfg(keyframe_max_frames=2), 5, kf=True, seqs=(0, 4))
 
 
 def test_replay_per_sequence_intrinsics():
-    cams = np.stack([KH] * 5).astype(F32)
-    for b in range(5):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    _replay(_cfg(), 5, GIVEN, _rows(5), cams=cams, seqs=(2, 4))
+    _replay(tb.cfg(), 5, GIVEN, _rows(5), cams=tb.sequence_cams(5), seqs=(2, 4))
 
 
 def test_replay_sensor_undistortion():
     """the frames the batch tracks are dvo_op_undistort of the pushed maps (tests/test_gpu_sensor_undistort.py holds that equality)"""
-    und = lambda m, K: _oframe(tuple(dvo.undistort(x, K, D_LENS) for x in m), K)
-    _replay(_cfg(), 5, D=D_LENS, seqs=(2,), frame_of=und)
+    und = lambda m, K: tb.oframe_of(tuple(dvo.undistort(x, K, D_LENS) for x in m), K)
+    _replay(tb.cfg(), 5, D=D_LENS, seqs=(2,), frame_of=und)
 
 
 def test_replay_raw_feed():
     """raw frames: the maps are dvo_op_ingest of the u8 / u16 frames, and every contributing pixel carries the one weight of sigma 0.1"""
-    raw = lambda m, K: _oframe(dvo.ingest(*_raw(m)), K)
-    a = _replay(_cfg(), 5, feed="raw", seqs=(3,), frame_of=raw)
-    _same(a, _run(_cfg(), 5, _wide_idx(5), _zab(), feed="raw_host"))
+    raw = lambda m, K: tb.oframe_of(dvo.ingest(*tb.raw_of(m)), K)
+    a = _replay(tb.cfg(), 5, feed="raw", seqs=(3,), frame_of=raw)
+    tb.same(a, tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw_host", **_term(tb.wide_idx(5), _zab())))
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6: every instance
@@ -374,7 +261,7 @@ def test_replay_raw_feed():
 def test_every_kernel_instance(ppt, group, cam):
     """each (PPT, G) pair of k_track_gn_zab and k_track_gn_zab_cam on a batch of two: the 160x120 level takes the 2-D tiles of PPT = 4,
     the two coarser levels the raster tiles"""
-    cfg = _cfg(gn_gather_group=group)
+    cfg = tb.cfg(gn_gather_group=group)
     cfg.gn_pixels_per_thread = ppt    # (_cfg fixes 4 pixels per thread)
     cams = np.stack([KH, KH]).astype(F32) if cam else None
     if cam:
@@ -388,14 +275,14 @@ def test_gates_of_the_reference_depth(defect, zab_run):
     """A block of the reference's depth is a hole (zeros), NaN, +inf or a step of 0.5 m (> max_diff): at every level n_geo equals the
     replica's and is below the clean reference's by about the block; n_valid, sum_r2, the moments and the next entry are the clean
     ones; every sum is finite."""
-    cfg = _cfg()
+    cfg = tb.cfg()
     before = ga.nonempty_calls()
-    obj, ref = _oframe(zab_run[1]["maps"][0]), _oframe(zab_run[0]["maps"][0])
-    poses = tr._level_poses(zab_run[1]["logs"][0])
+    obj, ref = tb.oframe_of(zab_run[1]["maps"][0]), tb.oframe_of(zab_run[0]["maps"][0])
+    poses = tb.level_poses(zab_run[1]["logs"][0])
     a, b = 0.9, 0.03
     for l in range(LEVELS):
         bad = ref.depth(l).copy()
-        n_blk = _defect(bad, defect)
+        n_blk = tb.defect(bad, defect)
         clean = _op(obj, ref, l, poses[l], 10.0, 0.1, a, b, cfg)
         got = _op(obj, ref, l, poses[l], 10.0, 0.1, a, b, cfg, ref_depth=bad)
         px = ga.pixels(obj.gray(l), obj.depth(l), obj.sigma(l), ref.gray(l), bad, ref.K(l), poses[l], l, False, _wp())
@@ -411,26 +298,25 @@ def test_gates_of_the_reference_depth(defect, zab_run):
 # ------------------------------------------------------------------------------------------------------------------ 8: the schedules
 @pytest.fixture(scope="module")
 def base17():
-    return _run(_cfg(), 17, _wide_idx(17), _zab())
+    return tb.run(tb.cfg(), 17, tb.wide_idx(17), **_term(tb.wide_idx(17), _zab()))
 
 
 @pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "host_feed", "two_streams"])
 def test_schedule_variants_give_the_same_records(variant, base17):
     """17 sequences: two sub-batches with track_streams = 2, and a third solve workgroup of one"""
-    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1),
-              two_streams=dict(track_streams=2)).get(variant, {})
-    other = _run(_cfg(**kw), 17, _wide_idx(17), _zab(), feed="host" if variant == "host_feed" else "device")
-    _same(base17, other)
+    idx = tb.wide_idx(17)
+    other = tb.run(tb.cfg(**tb.SCHEDULE_VARIANTS.get(variant, {})), 17, idx, feed="host" if variant == "host_feed" else "device", **_term(idx, _zab()))
+    tb.same(base17, other)
     assert all((o["grec"]["n_geo"] > 1000).all() and (np.abs(o["ab"][:, 0] - 1.0) > 0.02).all() for o in base17[1:])
 
 
 # ------------------------------------------------------------------------------------------------------------------ 9: lifecycle
 def test_actions_leave_no_stale_record():
     """SKIP, RESTART and a bad action give zero records and empty logs in both families (checked in _replay); the tracked ones replay"""
-    acts = _acts(5, 3, 9)
+    acts = tb.acts(5, 3, 9)
     assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
     acts[2][1] = 7   # an action outside the set: BAD_ACTION, handled as SKIP
-    outs = _replay(_cfg(), 5, acts=acts, min_tracked=2, seqs=(0, 2, 3))
+    outs = _replay(tb.cfg(), 5, acts=acts, min_tracked=2, seqs=(0, 2, 3))
     assert outs[2]["status"][1] == BAD and (np.concatenate([o["status"] for o in outs]) == SKIPPED).any()
 
 
@@ -438,7 +324,7 @@ def test_camera_change_restarts_the_sequence():
     cams = np.stack([KH] * 5).astype(F32)
     new = cams.copy()
     new[2, 0, 0] *= 1.02
-    outs = _replay(_cfg(), 5, cams=cams, cams_at=(2, new), min_tracked=3, seqs=(2, 3))
+    outs = _replay(tb.cfg(), 5, cams=cams, cams_at=(2, new), min_tracked=3, seqs=(2, 3))
     assert outs[2]["status"][2] == STARTED and (outs[2]["status"][[0, 1, 3, 4]] == TRACKED).all()
 
 
@@ -447,16 +333,16 @@ def test_turning_one_term_off_leaves_the_other_family(off):
     """two pushes composed, then one term is turned off through its own setter: from the next push on the batch is bit for bit the batch
     that only ever had the other term"""
     B = 5
-    idx = _wide_idx(B, pushes=4)
+    idx = tb.wide_idx(B, pushes=4)
     if off == "geometric":
-        got = _run(_cfg(), B, idx, _zab(), reads=("aff",), at={2: lambda bt: bt.set_geometric(dvo.GEOMETRIC_OFF)})
-        only = _run(_cfg(), B, idx, _ab, reads=("aff",))
-        _same(only, got, families=("aff",), pushes=(2, 3))
+        got = tb.run(tb.cfg(), B, idx, at={2: lambda bt: bt.set_geometric(dvo.GEOMETRIC_OFF)}, **_term(idx, _zab(), reads=("affine",)))
+        only = tb.run(tb.cfg(), B, idx, **_term(idx, _ab, reads=("affine",)))
+        tb.same(only, got, families=("affine",), pushes=(2, 3))
         assert all((np.abs(o["ab"][:, 0] - 1.0) > 0.02).all() for o in got[2:])
     else:
-        got = _run(_cfg(), B, idx, _zab(), reads=("geo",), at={2: lambda bt: bt.set_affine_brightness(None)})
-        only = _run(_cfg(), B, idx, _z, reads=("geo",))
-        _same(only, got, families=("geo",), pushes=(2, 3))
+        got = tb.run(tb.cfg(), B, idx, at={2: lambda bt: bt.set_affine_brightness(None)}, **_term(idx, _zab(), reads=("geometric",)))
+        only = tb.run(tb.cfg(), B, idx, **_term(idx, _z, reads=("geometric",)))
+        tb.same(only, got, families=("geometric",), pushes=(2, 3))
         assert all((o["grec"]["n_geo"] > 1000).all() for o in got[2:])
     # (while both were on, the batch was neither)
     assert any(not np.array_equal(got[1]["xi"][b], only[1]["xi"][b]) for b in range(B))
@@ -465,7 +351,7 @@ def test_turning_one_term_off_leaves_the_other_family(off):
 # ------------------------------------------------------------------------------------------------------------------ 10: refusals
 def test_errors_are_refused():
     L = dvo.lib()
-    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
     GC, AC = dvo.GeometricConfig, dvo.AffineConfig
     gs, as_ = C.sizeof(GC), C.sizeof(AC)
     good_g, good_a = GC(gs, 1, 10.0, 0.1), AC(as_, ESTIMATE, 64, 1e-3, 0.25, 4.0)
@@ -511,9 +397,9 @@ def test_errors_are_refused():
     bt.set_geometric_affine()
     with pytest.raises(dvo.DvoError):
         bt.last_affine()                            # enabled from the next push on
-    g, d, s = _frames()
+    g, d, s = tb.frames()
     for k in (0, 1):
-        t = [_dev(x[k:k + 2]) for x in (g, d, s)]
+        t = [tb.dev(x[k:k + 2]) for x in (g, d, s)]
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         bt.synchronize()
     assert (bt.last_geometric()["n_geo"] > 1000).all() and (bt.last_affine()[:, 0] > 0.5).all()   # both terms are ready
@@ -556,7 +442,7 @@ def test_composed_beats_geometric_under_an_exposure_change():
         else:
             bt.set_geometric()
         for k in (0, 1):
-            t = [_dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
+            t = [tb.dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
             bt.synchronize()
         xi, _ = bt.last_poses()

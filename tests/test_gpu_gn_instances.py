@@ -25,18 +25,20 @@ import dvo_amd as dvo
 import gn_sums
 import orc
 import robust_ref as rr
+import term_batch as tb
 import test_gpu_affine as ta
 import test_gpu_geometric as tg
 import test_gpu_geometric_affine as tz
 import test_gpu_robust as tr
 import test_gpu_track_quality as tq
-from test_gpu_robust import HUBER, KH, LEVELS, STEPS, STUDENT, TOP, _cfg, _wide_idx
+from term_batch import GEO, HUBER, KH, LEVELS, STEPS, STUDENT, TOP
 
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
 TRACKED = dvo.SEQ_TRACKED
 ESTIMATE = dvo.AFFINE_ESTIMATE
+IDX2 = tb.wide_idx(2)
 SHAPES = [(1, 1), (2, 1), (2, 2), (4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4)]
 GROUPS = {2: (1, 2), 4: (1, 2, 4), 8: (1, 2, 4)}
 LEVEL_SIZES = ((40, 30), (80, 60), (160, 120))                 # 320x240, 3 levels, culls 1
@@ -46,10 +48,8 @@ PLAIN_LEVEL_SIZES = ((20, 15), (40, 30), (80, 60), (160, 120))  # 320x240, 4 lev
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    """the oracle's step literals follow tests/test_gpu_robust.py's config (they enter rw); back to the reference's afterwards"""
-    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
+    with tb.oracle_steps():
+        yield
 
 
 @contextlib.contextmanager
@@ -73,7 +73,7 @@ def _group(name):
 
 
 def _shape_cfg(ppt, group, **kw):
-    cfg = _cfg(gn_gather_group=group, **kw)
+    cfg = tb.cfg(gn_gather_group=group, **kw)
     cfg.gn_pixels_per_thread = ppt    # (_cfg fixes 4 pixels per thread; 0: the engine chooses per level)
     return cfg
 
@@ -101,12 +101,7 @@ def _assert_plan(plan, shapes, sizes=LEVEL_SIZES, schedule=dvo.PLAN_PAIRS):
 
 def _cams(B, cam, K=KH):
     """per-sequence cameras (the _cam kernels): sequence 0 keeps K, the others differ from it and from each other"""
-    if not cam:
-        return None
-    cams = np.stack([np.asarray(K, F32)] * B).astype(F32)
-    for b in range(B):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    return cams
+    return tb.sequence_cams(B, K) if cam else None
 
 
 # ------------------------------------------------------------------------------------------------------------------ the accessor
@@ -114,18 +109,18 @@ def test_level_plan_follows_the_plan_in_force():
     """level_plan reads Tracker::lv as use_plan() left it: the plain plan of the config, the launch-pair plan while an opt-in term is
     on, the plain plan again once it is off.  A level outside the pyramid is refused, on both batch kinds."""
     L = dvo.lib()
-    bt = dvo.Batch(2, KH, 320, 240, LEVELS, 1, cfg=_cfg(track_fused_tiles=8))
+    bt = dvo.Batch(2, KH, 320, 240, LEVELS, 1, cfg=tb.cfg(track_fused_tiles=8))
     plain = [bt.level_plan(l) for l in range(LEVELS)]
     assert [p["schedule"] for p in plain] == [dvo.PLAN_LEVEL, dvo.PLAN_LEVEL, dvo.PLAN_ITERATION], plain   # 2, 5 and 20 tiles of two sequences
     assert [(p["ppt"], p["group"], p["tiles"], p["tiles_2d"]) for p in plain] == [(4, 2, 2, False), (4, 2, 5, False), (4, 2, 20, True)]
-    bt.set_robust_weights(**tr._rob(HUBER))
+    bt.set_robust_weights(**tb.rob(HUBER))
     _assert_plan([bt.level_plan(l) for l in range(LEVELS)], [(4, 2)] * 3)
     bt.set_robust_weights(dvo.ROBUST_NONE)
     assert [bt.level_plan(l) for l in range(LEVELS)] == plain
     bt.set_affine_brightness(ESTIMATE)
     _assert_plan([bt.level_plan(l) for l in range(LEVELS)], [(4, 2)] * 3)
     bt.set_affine_brightness(None)
-    bt.set_geometric(**tg.GEO)
+    bt.set_geometric(**GEO)
     _assert_plan([bt.level_plan(l) for l in range(LEVELS)], [(4, 2)] * 3)
     for level in (-1, LEVELS, 1000):
         assert L.dvo_debug_batch_level_plan(bt._p, level, None, None, None, None, None) == dvo.DVO_ERR_BAD_ARGUMENT, level
@@ -133,9 +128,9 @@ def test_level_plan_follows_the_plan_in_force():
             bt.level_plan(level)
     assert L.dvo_debug_batch_level_plan(bt._p, 0, None, None, None, None, None) == 0    # every output may be NULL
     bt.close()
-    bt = dvo.Batch(2, KH, 320, 240, LEVELS, 1, cfg=_cfg(gn_use_lds_patch=2))
+    bt = dvo.Batch(2, KH, 320, 240, LEVELS, 1, cfg=tb.cfg(gn_use_lds_patch=2))
     assert all(bt.level_plan(l)["schedule"] == dvo.PLAN_LDS_PATCH and not bt.level_plan(l)["tiles_2d"] for l in range(LEVELS))
-    bt.set_robust_weights(**tr._rob(HUBER))    # (no LDS patch under an opt-in term)
+    bt.set_robust_weights(**tb.rob(HUBER))    # (no LDS patch under an opt-in term)
     _assert_plan([bt.level_plan(l) for l in range(LEVELS)], [(4, 2)] * 3)
     bt.close()
     from util import K640
@@ -155,22 +150,22 @@ def _kind(ppt, cam):
 
 @functools.lru_cache(maxsize=None)
 def _robust_run(ppt, group, cam):
-    return tr._run(_shape_cfg(ppt, group), 2, _wide_idx(2), rob=tr._rob(_kind(ppt, cam)), cams=_cams(2, cam))
+    return tb.run(_shape_cfg(ppt, group), 2, IDX2, cams=_cams(2, cam), **tr._weights(tb.rob(_kind(ppt, cam))))
 
 
 @functools.lru_cache(maxsize=None)
 def _affine_run(ppt, group, cam, rob):
-    return ta._run(_shape_cfg(ppt, group), 2, _wide_idx(2), aff=dict(mode=ESTIMATE), rob=ta._rob(HUBER) if rob else None, cams=_cams(2, cam))
+    return tb.run(_shape_cfg(ppt, group), 2, IDX2, cams=_cams(2, cam), **ta._term(IDX2, dict(mode=ESTIMATE), rob=tb.rob(HUBER) if rob else None))
 
 
 @functools.lru_cache(maxsize=None)
 def _geometric_run(ppt, group, cam):
-    return tg._run(_shape_cfg(ppt, group), 2, _wide_idx(2), geo=tg.GEO, cams=_cams(2, cam))
+    return tb.run(_shape_cfg(ppt, group), 2, IDX2, cams=_cams(2, cam), **tg._term(GEO))
 
 
 @functools.lru_cache(maxsize=None)
 def _geometric_affine_run(ppt, group, cam):
-    return tz._run(_shape_cfg(ppt, group), 2, _wide_idx(2), tz._zab(), cams=_cams(2, cam))
+    return tb.run(_shape_cfg(ppt, group), 2, IDX2, cams=_cams(2, cam), **tz._term(IDX2, tz._zab()))
 
 
 def _plain_cfg(ppt, group):
@@ -199,7 +194,7 @@ def test_every_robust_kernel_instance(ppt, group, cam):
     outs = _robust_run(ppt, group, cam)
     depths = _assert_plan(outs[0]["plan"], [(ppt, group)] * LEVELS)
     with _group("robust instances"):
-        tr._lockstep(_shape_cfg(ppt, group), 2, tr._rob(_kind(ppt, cam)), cams=_cams(2, cam), outs=outs, seqs=(1,), depth=depths)
+        tr._lockstep(_shape_cfg(ppt, group), 2, tb.rob(_kind(ppt, cam)), cams=_cams(2, cam), outs=outs, seqs=(1,), depth=depths)
 
 
 @pytest.mark.parametrize("rob", [False, True])
@@ -211,7 +206,7 @@ def test_every_affine_kernel_instance(ppt, group, cam, rob):
     outs = _affine_run(ppt, group, cam, rob)
     depths = _assert_plan(outs[0]["plan"], [(ppt, group)] * LEVELS)
     with _group("affine instances"):
-        ta._replay(_shape_cfg(ppt, group), 2, dict(mode=ESTIMATE), rob=ta._rob(HUBER) if rob else None, cams=_cams(2, cam), outs=outs, seqs=(1,),
+        ta._replay(_shape_cfg(ppt, group), 2, dict(mode=ESTIMATE), rob=tb.rob(HUBER) if rob else None, cams=_cams(2, cam), outs=outs, seqs=(1,),
                    depth=depths)
 
 
@@ -253,7 +248,7 @@ AUTO_SMALL = dict(B=5, shapes=[(1, 1)] * 3, seqs=(1, 4))
 def _plain_lockstep(outs, B, seqs, depths):
     """the plain family through robust_ref with kind NONE (rho = 1: the plain sums): every logged iteration of `seqs` at its level's
     depth, the finest level's record inside the bound"""
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     before = rr.nonempty_calls()
     n = n_it = 0
     for k in range(1, len(outs)):
@@ -262,8 +257,8 @@ def _plain_lockstep(outs, B, seqs, depths):
         for b in seqs:
             where = "push %d seq %d of %d" % (k, b, B)
             lg, q = o["logs"][b], o["q"][b]
-            last, m = rr.replay_call(lg, rr.oracle_terms(tr._oframe(idx[k][b]), tr._oframe(idx[k - 1][b]), False), LEVELS, rr.NONE, 1.0, rr.ADAPTIVE,
-                                     floor2=tr._floor2(), tag=where, depth=depths)
+            last, m = rr.replay_call(lg, rr.oracle_terms(tb.oframe(idx[k][b]), tb.oframe(idx[k - 1][b]), False), LEVELS, rr.NONE, 1.0, rr.ADAPTIVE,
+                                     floor2=tb.floor2(), tag=where, depth=depths)
             t, _, l, it = last
             assert l == TOP and it == int(lg["n_iter"][TOP]) - 1
             assert q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
@@ -279,24 +274,24 @@ def _auto_case(family, case):
     B, shapes, seqs = case["B"], case["shapes"], case["seqs"]
     cfg = _shape_cfg(0, 0)
     assert cfg.gn_pixels_per_thread == 0
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     schedule = None if family == "plain" else dvo.PLAN_PAIRS    # (a small plain batch may take one launch per iteration)
     with _group("automatic plan " + family):
         if family == "plain":
-            outs = tr._run(cfg, B, idx)
+            outs = tb.run(cfg, B, idx)
             _plain_lockstep(outs, B, seqs, _assert_plan(outs[0]["plan"], shapes, schedule=schedule))
         elif family == "robust":
-            outs = tr._run(cfg, B, idx, rob=tr._rob(STUDENT))
-            tr._lockstep(cfg, B, tr._rob(STUDENT), outs=outs, seqs=seqs, depth=_assert_plan(outs[0]["plan"], shapes))
+            outs = tb.run(cfg, B, idx, **tr._weights(tb.rob(STUDENT)))
+            tr._lockstep(cfg, B, tb.rob(STUDENT), outs=outs, seqs=seqs, depth=_assert_plan(outs[0]["plan"], shapes))
         elif family == "affine":
-            outs = ta._run(cfg, B, idx, aff=dict(mode=ESTIMATE))
+            outs = tb.run(cfg, B, idx, **ta._term(idx, dict(mode=ESTIMATE)))
             ta._replay(cfg, B, dict(mode=ESTIMATE), outs=outs, seqs=seqs, depth=_assert_plan(outs[0]["plan"], shapes))
         elif family == "geometric":
-            outs = tg._run(cfg, B, idx, geo=tg.GEO)
+            outs = tb.run(cfg, B, idx, **tg._term(GEO))
             _assert_plan(outs[0]["plan"], shapes)
-            tg._replay(cfg, B, tg.GEO, outs=outs, seqs=seqs, ppt=[p["ppt"] for p in outs[0]["plan"]])
+            tg._replay(cfg, B, GEO, outs=outs, seqs=seqs, ppt=[p["ppt"] for p in outs[0]["plan"]])
         else:
-            outs = tz._run(cfg, B, idx, tz._zab())
+            outs = tb.run(cfg, B, idx, **tz._term(idx, tz._zab()))
             _assert_plan(outs[0]["plan"], shapes)
             tz._replay(cfg, B, outs=outs, seqs=seqs, ppt=[p["ppt"] for p in outs[0]["plan"]])
     if B > 8:
@@ -328,18 +323,12 @@ def _same_plain(a, b):
             assert [_logbits4(l) for l in x["logs"]] == [_logbits4(l) for l in y["logs"]], "push %d logs" % k
 
 
-def _same_robust(a, b):
-    tr._same(a, b)
-    for x, y in zip(a, b):
-        assert x["s2"].tobytes() == y["s2"].tobytes()
-
-
 GROUP_RUNS = dict(
     plain=(lambda ppt, g: [_plain_run(ppt, g, cam) for cam in (False, True)], _same_plain),
-    robust=(lambda ppt, g: [_robust_run(ppt, g, cam) for cam in (False, True)], _same_robust),
-    affine=(lambda ppt, g: [_affine_run(ppt, g, cam, rob) for cam in (False, True) for rob in (False, True)], ta._same),
-    geometric=(lambda ppt, g: [_geometric_run(ppt, g, cam) for cam in (False, True)], tg._same),
-    geometric_affine=(lambda ppt, g: [_geometric_affine_run(ppt, g, cam) for cam in (False, True)], tz._same),
+    robust=(lambda ppt, g: [_robust_run(ppt, g, cam) for cam in (False, True)], tb.same),
+    affine=(lambda ppt, g: [_affine_run(ppt, g, cam, rob) for cam in (False, True) for rob in (False, True)], tb.same),
+    geometric=(lambda ppt, g: [_geometric_run(ppt, g, cam) for cam in (False, True)], tb.same),
+    geometric_affine=(lambda ppt, g: [_geometric_affine_run(ppt, g, cam) for cam in (False, True)], tb.same),
 )
 
 

@@ -13,7 +13,7 @@ The operator's shapes are those of tests/test_gpu_pyramid_build.py (the lx >= w[
 runs: k_pyramid_filter_top<CULLS, RAW, PLAN, WIDE>; WIDE (16-byte staging loads) needs culls > 0 and one-channel bytes with a width
 that is a multiple of 16, or float maps with a width that is a multiple of 4 -- 144 and 176 for bytes, 88 and 176 for floats; 88 (bytes),
 90 and 178 are the ragged widths of the scalar fallback.  The level maps are stored one float at a time, so a batch of 3 (level
-pointers off 16 bytes) runs the same instance as a batch of 4; both run.  The batch tests use tests/test_gpu_robust.py's 320x240
+pointers off 16 bytes) runs the same instance as a batch of 4; both run.  The batch tests use tests/term_batch.py's 320x240
 frames, 3 levels, culls 1."""
 import ctypes as C
 import functools
@@ -29,7 +29,8 @@ import pyramid_filter_ref as fref
 import pyramid_ref as pref
 import robust_ref as rr
 import test_gpu_pyramid_build as tb
-from test_gpu_robust import CULLS, KH, LEVELS, SIZE, STEPS, TOP, _cfg, _dev, _frames, _logbits, _wide_idx
+import term_batch as tm
+from term_batch import CULLS, KH, LEVELS, SIZE, TOP
 from util import K640, TOL_BACKWARD, backward_error
 
 pytestmark = pytest.mark.gpu
@@ -43,10 +44,8 @@ BAD = dvo.DVO_ERR_BAD_ARGUMENT
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    """the oracle's step literals follow the config of this file (they enter rw); back to the reference's afterwards"""
-    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
+    with tm.oracle_steps():
+        yield
 
 
 def _name(culls, raw, plan, wide):
@@ -267,8 +266,8 @@ def _run(B, idx, filt=BINOMIAL3, set_it=True, feed="device", cfg=None, kf=False,
     float maps, prefetched before their push).  garbage: a SKIP sequence's slot of the input holds garbage.
     Per push: dict(status, xi, T, logs, frames[b][l] = (gray, depth), kf[b][l], maps[b] = the float (gray, depth, sigma) the push is
     equivalent to, ...)"""
-    g, d, s = _frames()
-    cfg = cfg if cfg is not None else _cfg()
+    g, d, s = tm.frames()
+    cfg = cfg if cfg is not None else tm.cfg()
     bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=cfg)
     if kf:
         bt.set_keyframe_tracking(True)
@@ -313,7 +312,7 @@ def _run(B, idx, filt=BINOMIAL3, set_it=True, feed="device", cfg=None, kf=False,
                 bt.push_raw_host(g8, d16)
             else:
                 import torch
-                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
+                tg = tm.dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
                 torch.cuda.synchronize()
                 keep.append((tg, td))
                 bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
@@ -327,7 +326,7 @@ def _run(B, idx, filt=BINOMIAL3, set_it=True, feed="device", cfg=None, kf=False,
         if feed == "host":
             bt.push_host(*arr)
             return
-        t = [_dev(x) for x in arr]
+        t = [tm.dev(x) for x in arr]
         keep.append(t)
         if prefetch_only:
             bt.prefetch_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
@@ -370,14 +369,14 @@ def _same(a, b):
                 assert fx[l][0].tobytes() == fy[l][0].tobytes() and fx[l][1].tobytes() == fy[l][1].tobytes(), (k, bq, l)
         if "xi" in x:
             assert x["xi"].tobytes() == y["xi"].tobytes() and x["T"].tobytes() == y["T"].tobytes(), "push %d poses" % k
-            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
+            assert [tm.logbits(l) for l in x["logs"]] == [tm.logbits(l) for l in y["logs"]], "push %d logs" % k
             assert x["q"].tobytes() == y["q"].tobytes(), "push %d records" % k
 
 
 @pytest.mark.parametrize("mode", ["plain", "keyframes", "raw"])
 def test_a_batch_with_none_set_is_a_batch_that_never_called_the_setter(mode):
     kw = dict(kf=mode == "keyframes", feed="raw" if mode == "raw" else "device")
-    _same(_run(5, _wide_idx(5), NONE, **kw), _run(5, _wide_idx(5), set_it=False, **kw))
+    _same(_run(5, tm.wide_idx(5), NONE, **kw), _run(5, tm.wide_idx(5), set_it=False, **kw))
 
 
 # ------------------------------------------------------------------------------------------------------------------ batch maps
@@ -401,7 +400,7 @@ def _assert_frames(outs, what):
 @pytest.mark.parametrize("feed", ["device", "host", "raw", "raw_host", "prefetch"])
 @pytest.mark.parametrize("B", [3, 4])
 def test_batch_frames_equal_the_replica(feed, B):
-    outs = _run(B, _wide_idx(B), feed=feed, holes=True)
+    outs = _run(B, tm.wide_idx(B), feed=feed, holes=True)
     _assert_frames(outs, feed)
     top = outs[1]["frames"][0][TOP][0]
     assert (top == pref.INVALID).any() and fref.valid(top).sum() > top.size // 2
@@ -409,8 +408,8 @@ def test_batch_frames_equal_the_replica(feed, B):
 
 
 def test_the_raw_path_equals_the_ingested_float_path():
-    a = _run(4, _wide_idx(4), feed="raw", holes=True)
-    b = _run(4, _wide_idx(4), feed="ingested", holes=True, cfg=_cfg())
+    a = _run(4, tm.wide_idx(4), feed="raw", holes=True)
+    b = _run(4, tm.wide_idx(4), feed="ingested", holes=True, cfg=tm.cfg())
     # (raw frames keep no weight maps where min_depth allows: the estimator's inputs are the same values, the poses the same bits)
     for k, (x, y) in enumerate(zip(a, b)):
         for bq in range(4):
@@ -422,7 +421,7 @@ def test_the_raw_path_equals_the_ingested_float_path():
 
 
 def test_keyframe_maps_equal_the_replica():
-    outs = _run(4, _wide_idx(4), kf=True, holes=True)
+    outs = _run(4, tm.wide_idx(4), kf=True, holes=True)
     _assert_frames(outs, "keyframes")
     made = [0] * 4      # the push that made each sequence's current keyframe
     for k, o in enumerate(outs):
@@ -442,7 +441,7 @@ ACTS = [[T, T, T, T, T], [S, T, R, T, S], [T, S, T, R, S], [T, T, S, T, T]]
 @pytest.mark.parametrize("feed", ["device", "raw"])
 def test_skip_copies_every_level_forward_and_restart_builds(feed):
     """garbage in the skipped input slots; a skipped sequence keeps the frame set of its last built push at every level"""
-    idx = [r[:5] for r in (_wide_idx(5) + [[4, 1, 4, 3, 2]])]
+    idx = [r[:5] for r in (tm.wide_idx(5) + [[4, 1, 4, 3, 2]])]
     outs = _run(5, idx, feed=feed, acts=ACTS, holes=True, garbage=True)
     last = [0] * 5
     n_skip = 0
@@ -461,7 +460,7 @@ def test_skip_copies_every_level_forward_and_restart_builds(feed):
 
 def test_per_sequence_intrinsics_table():
     cams = np.stack([KH.reshape(3, 3) * np.array([[1 + 0.01 * b], [1 - 0.01 * b], [1]], F32) for b in range(4)]).astype(F32)
-    outs = _run(4, _wide_idx(4), cams=cams, holes=True)
+    outs = _run(4, tm.wide_idx(4), cams=cams, holes=True)
     _assert_frames(outs, "intrinsics table")
     assert all((o["status"] == TRACKED).all() for o in outs[1:])
 
@@ -515,7 +514,7 @@ def _lockstep_call(lg, obj, ref, where):
 
 @pytest.mark.parametrize("B", [5, 17])
 def test_tracking_in_lockstep_with_the_oracle_on_the_replica_maps(B):
-    idx = _wide_idx(B)
+    idx = tm.wide_idx(B)
     outs = _run(B, idx)
     seqs = range(B) if B == 5 else (0, 7, 8, 15, 16)
     n_it = 0
@@ -535,8 +534,8 @@ def test_tracking_in_lockstep_with_the_oracle_on_the_replica_maps(B):
 # ------------------------------------------------------------------------------------------------------------------ composition
 def test_robust_weights_on_the_filtered_maps():
     rob = dict(kind=dvo.ROBUST_HUBER, param=1.345, scale_mode=dvo.ROBUST_SCALE_ADAPTIVE, scale_floor=1e-3)
-    cfg = _cfg()
-    outs = _run(5, _wide_idx(5), rob=rob, cfg=cfg)
+    cfg = tm.cfg()
+    outs = _run(5, tm.wide_idx(5), rob=rob, cfg=cfg)
     depth = gn_sums.depth_for_cfg(cfg)
     n = 0
     for k in range(1, len(outs)):
@@ -551,8 +550,8 @@ def test_robust_weights_on_the_filtered_maps():
 
 def test_geometric_term_on_the_filtered_maps():
     geo = dict(weight=10.0, max_diff=0.1)
-    cfg = _cfg()
-    outs = _run(5, _wide_idx(5), geo=geo, cfg=cfg)
+    cfg = tm.cfg()
+    outs = _run(5, tm.wide_idx(5), geo=geo, cfg=cfg)
     n = 0
     for k in range(1, len(outs)):
         for b in range(5):
@@ -569,8 +568,8 @@ def test_refusals():
     L = dvo.lib()
     f = C.c_int(-7)
     D = np.array([0.05, -0.02, 0.001, -0.001, 0.0], F32)
-    g, d, s = _frames()
-    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    g, d, s = tm.frames()
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tm.cfg())
     assert L.dvo_batch_set_pyramid_filter(None, BINOMIAL3) == BAD and L.dvo_batch_pyramid_filter(None, C.byref(f)) == BAD
     assert L.dvo_batch_pyramid_filter(bt._p, None) == BAD
     for bad in (-1, 2, 7):
@@ -586,14 +585,14 @@ def test_refusals():
         bt.set_distortion(D)
     assert not bt.distortion()[1] and bt.pyramid_filter() == BINOMIAL3
     bt.set_pyramid_filter(NONE); bt.set_pyramid_filter(BINOMIAL3)   # free until the first frame
-    t = [_dev(x[:2]) for x in (g, d, s)]
+    t = [tm.dev(x[:2]) for x in (g, d, s)]
     bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     assert L.dvo_batch_set_pyramid_filter(bt._p, NONE) == BAD and bt.pyramid_filter() == BINOMIAL3     # fixed by the first push
     bt.set_pyramid_filter(BINOMIAL3)                              # (the value in force: allowed)
     bt.close()
     # ... and by the first prefetch; a plain batch cannot turn it on later
     for first in ("prefetch", "push"):
-        bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+        bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tm.cfg())
         if first == "prefetch":
             bt.prefetch_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         else:
@@ -638,7 +637,7 @@ def test_filtered_batch_beats_plain_on_noisy_pairs():
         bt = dvo.Batch(B, pairs[0][3], o["width"], o["height"], o["levels"], o["culls"], cfg=cfg)
         bt.set_pyramid_filter(filt)
         for k in (0, 1):
-            t = [_dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
+            t = [tm.dev(np.stack([p[j][k] for p in pairs])) for j in (0, 1, 2)]
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
             bt.synchronize()
         xi, _ = bt.last_poses()

@@ -10,8 +10,6 @@ gn_tiling takes 16-column tiles only from 128 rows up) and 160x120 (32-column 2-
 case runs at 328x248, where the finest level (164x124) is raster as well.  The step and stop constants are the converging ones of
 bench.py (steps 1.0 / 0.75 / 0.5, stop on the update norm), so that a level runs several iterations and the adaptive scale has a
 previous residual of the same level to follow."""
-import functools
-
 import numpy as np
 import pytest
 
@@ -20,187 +18,53 @@ import gn_sums
 import lockstep
 import orc
 import robust_ref as rr
+import term_batch as tb
 from dvo_amd import synth
+from term_batch import CULLS, FLOOR, HUBER, KH, LEVELS, PARAM, SIZE, SKIP, RESTART, STARTED, STEPS, STUDENT, TOP, TRACKED
 from util import K640
 
 pytestmark = pytest.mark.gpu
 
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
-HUBER, STUDENT = dvo.ROBUST_HUBER, dvo.ROBUST_STUDENT_T
 ADAPTIVE, GIVEN = dvo.ROBUST_SCALE_ADAPTIVE, dvo.ROBUST_SCALE_GIVEN
-SIZE = (320, 240)
-LEVELS, CULLS, TOP = 3, 1, 2
-STEPS = (1.0, 0.75, 0.5)
-FLOOR = 1e-3
-KH = np.array(K640, np.float32).copy()
-KH[0] *= 0.5
-KH[1] *= 0.5
-PARAM = {HUBER: 1.345, STUDENT: 5.0}
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    """the oracle's step literals follow the config of this file (they enter rw); back to the reference's afterwards"""
-    orc.set_tracker_params(step3=STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
-
-
-def _cfg(**kw):
-    kw.setdefault("max_iterations", 6)
-    return dvo.default_config(gn_pixels_per_thread=4, crop_enable=0, step_default=STEPS[0], step_level1=STEPS[1], step_level2=STEPS[2],
-                              min_residual=0.0, min_update=2e-5, **kw)
-
-
-def _rob(kind, mode=ADAPTIVE):
-    return dict(kind=kind, param=PARAM[kind], scale_mode=mode, scale_floor=FLOOR)
-
-
-def _floor2():
-    return np.float32(FLOOR) * np.float32(FLOOR)
-
-
-@functools.lru_cache(maxsize=None)
-def _frames(size=SIZE):
-    g, d, s, _ = synth.sequence(6, width=size[0], height_px=size[1], K=KH, seed=42, sigma_value=0.5)
-    return g.numpy(), d.numpy(), s.numpy()
-
-
-def _dev(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
-IDX = [[0, 1, 2, 3, 4], [1, 2, 3, 4, 5], [2, 3, 4, 5, 0], [3, 2, 5, 4, 1]]
-
-
-def _wide_idx(B, pushes=3):
-    """the frame assignment of tests/test_gpu_track_quality.py: neighbouring sequences and sequences 8 apart (the same slot of the next
-    solve workgroup) are on different frames at every push"""
-    if B <= 5:
-        return [r[:B] for r in IDX[:pushes]]
-    idx = [[(k + b) % 6 for b in range(B)] for k in range(pushes)]
-    for r in idx:
-        assert all(r[b] != r[b + 1] for b in range(B - 1)) and all(r[b] != r[b + 8] for b in range(B - 8))
-    return idx
+    with tb.oracle_steps():
+        yield
 
 
 def _given_scales(B):
     return (0.012 + 0.004 * np.arange(B)).astype(np.float32)
 
 
-def _run(cfg, B, idx, rob=None, scales=None, scales_on_device=False, clear=False, acts=None, kf=False, feed="device", cams=None,
-         size=SIZE, quality=True):
-    """idx[k][b]: frame of sequence b at push k.  rob: set_robust_weights arguments (clear: set, then turned off before the first
-    push); scales: GIVEN rows.  Returns per push dict(status, xi, T, logs, q, s2, world, plan); plan = level_plan of every level, read
-    once the terms are set (the plan the pushes ran)."""
-    g, d, s = _frames(size)
-    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
-    if kf:
-        bt.set_keyframe_tracking(True)
-    if quality:
-        bt.set_track_quality(True)
-    if cams is not None:
-        bt.set_intrinsics(cams)
-    keep = []
-    if rob:
+def _weights(rob=None, scales=None, scales_on_device=False, clear=False):
+    """run() keywords of a weighted batch.  rob: set_robust_weights arguments (clear: set, then turned off before the first push);
+    scales: GIVEN rows"""
+    def setup(bt, keep):
         bt.set_robust_weights(**rob)
         if scales is not None:
             if scales_on_device:
-                keep.append(_dev(np.asarray(scales, np.float32)))
+                keep.append(tb.dev(np.asarray(scales, np.float32)))
                 bt.set_robust_scales(keep[-1].data_ptr(), on_device=True)
             else:
                 bt.set_robust_scales(scales)
         if clear:
             bt.set_robust_weights(dvo.ROBUST_NONE)
-    plan = [bt.level_plan(l) for l in range(LEVELS)]
-    outs = []
-    for k in range(len(idx)):
-        sel = list(idx[k])
-        gi, di, si = g[sel], d[sel], s[sel]
-        if acts is not None:
-            bt.set_actions(np.asarray(acts[k], np.uint8))
-        if feed == "host":
-            bt.push_host(gi, di, si)
-        elif feed in ("raw", "raw_host"):
-            g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
-            if feed == "raw_host":
-                bt.push_raw_host(g8, d16)
-            else:
-                import torch
-                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-                torch.cuda.synchronize()
-                keep.append((tg, td))
-                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-        else:
-            t = [_dev(x) for x in (gi, di, si)]
-            keep.append(t)
-            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None, plan=plan)
-        if rob and not clear:
-            o["s2"] = bt.last_robust_scales()
-        if k > 0 or acts is not None or kf:
-            xi, T = bt.last_poses()
-            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
-            if kf:
-                o["world"] = bt.world_poses()
-        outs.append(o)
-    bt.close()
-    return outs
-
-
-def _logbits(lg):
-    return (tuple(int(n) for n in lg["n_iter"][:LEVELS]),) + tuple(
-        tuple(np.asarray(x, np.float32).tobytes() for x in lg[f][:LEVELS]) for f in ("residual", "upd_norm", "xi_after", "xi_update")) + (
-        tuple(np.asarray(x, np.int32).tobytes() for x in lg["n_valid"][:LEVELS]),)
-
-
-def _same(a, b, records=True):
-    assert len(a) == len(b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        np.testing.assert_array_equal(x["status"], y["status"], err_msg="push %d" % k)
-        if "xi" in x:
-            np.testing.assert_array_equal(x["xi"], y["xi"], err_msg="push %d" % k)
-            np.testing.assert_array_equal(x["T"], y["T"], err_msg="push %d" % k)
-            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
-        if "world" in x:
-            for u, v in zip(x["world"], y["world"]):
-                np.testing.assert_array_equal(u, v, err_msg="push %d world" % k)
-        if records:
-            assert x["q"].tobytes() == y["q"].tobytes(), "push %d records" % k
-
-
-def _acts(B, n, seed):
-    rng = np.random.RandomState(seed)
-    a = rng.choice([SKIP, TRACK, RESTART], size=(n, B), p=(0.2, 0.65, 0.15)).astype(np.uint8)
-    a[0] = TRACK
-    return a
+    return dict(setup=setup, reads=() if clear else ("robust",)) if rob else {}
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1: off is today
 @pytest.mark.parametrize("mode", ["plain", "actions", "keyframes"])
 def test_off_means_today(mode):
-    kw = dict(acts=_acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
-    cfg = _cfg(keyframe_max_frames=2) if mode == "keyframes" else _cfg()
-    _same(_run(cfg, 5, _wide_idx(5), **kw), _run(cfg, 5, _wide_idx(5), rob=_rob(HUBER), clear=True, **kw))
-
-
-def _mono_frames():
-    import test_gpu_mono_lockstep as ml
-    g, _ = ml.render(K640)
-    return g, ml.init_depth(K640), ml
-
-
-MONO_SEED = 3
-MIDX = [[0, 1, 2], [1, 2, 3], [2, 3, 4], [3, 4, 5]]
+    kw = dict(acts=tb.acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
+    cfg = tb.cfg(keyframe_max_frames=2) if mode == "keyframes" else tb.cfg()
+    tb.same(tb.run(cfg, 5, tb.wide_idx(5), **kw), tb.run(cfg, 5, tb.wide_idx(5), **_weights(tb.rob(HUBER), clear=True), **kw))
 
 
 def _mono_run(rob=None, clear=False):
-    g, init, ml = _mono_frames()
-    mb = dvo.MonoBatch(3, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=MONO_SEED))
+    g, init, ml = tb.mono_frames()
+    mb = dvo.MonoBatch(3, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tb.MONO_SEED))
     mb.setInitialDepth(init, np.full_like(init, ml.INIT_SIGMA))
     mb.set_track_quality(True)
     if rob:
@@ -208,8 +72,8 @@ def _mono_run(rob=None, clear=False):
         if clear:
             mb.set_robust_weights(None)
     outs = []
-    for k in range(len(MIDX)):
-        t = _dev(g[list(MIDX[k])])
+    for k in range(len(tb.MIDX)):
+        t = tb.dev(g[list(tb.MIDX[k])])
         mb.odometrize_device(t.data_ptr())
         xi, T, key = mb.world_poses()
         outs.append(dict(xi=xi.copy(), T=T.copy(), key=key.copy(), status=mb.last_status(), q=mb.last_track_quality(),
@@ -219,11 +83,11 @@ def _mono_run(rob=None, clear=False):
 
 
 def test_mono_off_means_today():
-    a, b = _mono_run(), _mono_run(rob=_rob(STUDENT), clear=True)
+    a, b = _mono_run(), _mono_run(rob=tb.rob(STUDENT), clear=True)
     for k, (x, y) in enumerate(zip(a, b)):
         for f in ("xi", "T", "status", "key"):
             np.testing.assert_array_equal(x[f], y[f], err_msg="call %d %s" % (k, f))
-        assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], k
+        assert [tb.logbits(l) for l in x["logs"]] == [tb.logbits(l) for l in y["logs"]], k
         assert x["q"].tobytes() == y["q"].tobytes(), k
 
 
@@ -231,39 +95,25 @@ def test_mono_off_means_today():
 @pytest.mark.parametrize("variant", ["huber_huge_scale", "bad_scales", "student_inf_scale"])
 def test_unit_weights_are_the_plain_batch(variant):
     B = 5
-    idx = _wide_idx(B)
-    plain = _run(_cfg(), B, idx)
+    idx = tb.wide_idx(B)
+    plain = tb.run(tb.cfg(), B, idx)
     if variant == "huber_huge_scale":
-        sc = np.full(B, 1e6, np.float32); rob = _rob(HUBER, GIVEN); want = np.float32(1e6) * np.float32(1e6)
+        sc = np.full(B, 1e6, np.float32); rob = tb.rob(HUBER, GIVEN); want = np.float32(1e6) * np.float32(1e6)
     elif variant == "bad_scales":
-        sc = np.float32([0.0, -1.0, np.nan, -np.inf, 0.0]); rob = _rob(HUBER, GIVEN); want = np.float32(np.inf)
+        sc = np.float32([0.0, -1.0, np.nan, -np.inf, 0.0]); rob = tb.rob(HUBER, GIVEN); want = np.float32(np.inf)
     else:
-        sc = np.full(B, np.inf, np.float32); rob = _rob(STUDENT, GIVEN); want = np.float32(np.inf)
-    got = _run(_cfg(), B, idx, rob=rob, scales=sc)
-    _same(plain, got)
+        sc = np.full(B, np.inf, np.float32); rob = tb.rob(STUDENT, GIVEN); want = np.float32(np.inf)
+    got = tb.run(tb.cfg(), B, idx, **_weights(rob, sc))
+    tb.same(plain, got, families=())
     for o in got[1:]:
         np.testing.assert_array_equal(o["s2"], np.full(B, want, np.float32))
     assert not got[0]["s2"].any()   # nothing tracked at the first push
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3: the operator
-def _oframe(i, K=KH, size=SIZE):
-    g, d, s = _frames(size)
-    return orc.OFrame(g[i], d[i], s[i], K, LEVELS, CULLS)
-
-
-def _level_poses(lg):
-    """the input pose of each level's last logged iteration"""
-    out = []
-    for l in range(LEVELS):
-        it = int(lg["n_iter"][l]) - 1
-        out.append(lg["xi_after"][l][it - 1] if it > 0 else (lg["xi_after"][l - 1][int(lg["n_iter"][l - 1]) - 1] if l > 0 else np.zeros(6, np.float32)))
-    return out
-
-
 @pytest.fixture(scope="module")
 def plain_run():
-    return _run(_cfg(), 3, _wide_idx(3))
+    return tb.run(tb.cfg(), 3, tb.wide_idx(3))
 
 
 def _op(obj, ref, l, xi, kind, param, s2, cfg):
@@ -272,12 +122,12 @@ def _op(obj, ref, l, xi, kind, param, s2, cfg):
 
 @pytest.mark.parametrize("kind", [HUBER, STUDENT])
 def test_operator_matches_the_contract(kind, plain_run):
-    cfg = _cfg()
+    cfg = tb.cfg()
     depth = gn_sums.depth_for_cfg(cfg)
     before = rr.nonempty_calls()
-    idx = _wide_idx(3)
-    obj, ref = _oframe(idx[1][0]), _oframe(idx[0][0])
-    poses = _level_poses(plain_run[1]["logs"][0])
+    idx = tb.wide_idx(3)
+    obj, ref = tb.oframe(idx[1][0]), tb.oframe(idx[0][0])
+    poses = tb.level_poses(plain_run[1]["logs"][0])
     for l in range(LEVELS):
         t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), poses[l], l, crop=False)
         assert t["n_valid"] > 500
@@ -290,11 +140,11 @@ def test_operator_matches_the_contract(kind, plain_run):
 
 
 def test_operator_edge_cases(plain_run):
-    cfg = _cfg()
+    cfg = tb.cfg()
     depth = gn_sums.depth_for_cfg(cfg)
-    idx = _wide_idx(3)
-    obj, ref = _oframe(idx[1][1]), _oframe(idx[0][1])
-    poses = _level_poses(plain_run[1]["logs"][1])
+    idx = tb.wide_idx(3)
+    obj, ref = tb.oframe(idx[1][1]), tb.oframe(idx[0][1])
+    poses = tb.level_poses(plain_run[1]["logs"][1])
     for l in range(LEVELS):
         t = orc.optimize_terms(obj.gray(l), ref.gray(l), ref.depth(l), ref.sigma(l), ref.K(l), poses[l], l, crop=False)
         # every pixel beyond the Huber threshold: c = k * sqrt(1e-30)
@@ -334,7 +184,7 @@ def _check_sequence(o, b, obj, ref, rob, given, depth, where):
     given_s2 = None
     if mode == GIVEN:
         given_s2 = np.float32(given[b]) * np.float32(given[b])
-    last, n_it = rr.replay_call(lg, rr.oracle_terms(obj, ref, False), LEVELS, kind, param, mode, floor2=_floor2(), given_s2=given_s2, tag=where,
+    last, n_it = rr.replay_call(lg, rr.oracle_terms(obj, ref, False), LEVELS, kind, param, mode, floor2=tb.floor2(), given_s2=given_s2, tag=where,
                                 depth=depth)
     t, s2, l, it = last
     assert l == TOP and it == int(lg["n_iter"][TOP]) - 1
@@ -350,30 +200,18 @@ def _lockstep(cfg, B, rob, acts=None, kf=False, cams=None, size=SIZE, scales_on_
               depth=None):
     """seqs: the sequences replayed against the oracle (None: all; the others keep the no-stale-scale check); depth: the reduction depth,
     one value or one per level (None: the config's)"""
-    idx = _wide_idx(B)
+    idx = tb.wide_idx(B)
     given = _given_scales(B) if rob["scale_mode"] == GIVEN else None
     if outs is None:
-        outs = _run(cfg, B, idx, rob=rob, scales=given, scales_on_device=scales_on_device, acts=acts, kf=kf, cams=cams, size=size)
+        outs = tb.run(cfg, B, idx, acts=acts, kf=kf, cams=cams, size=size, **_weights(rob, given, scales_on_device))
     depth = gn_sums.depth_for_cfg(cfg) if depth is None else depth
     before = rr.nonempty_calls()
-    ref_of = [None] * B
-    n = n_it = 0
-    for k, o in enumerate(outs):
-        for b in range(B):
-            st = o["status"][b]
-            if st == TRACKED and (seqs is None or b in seqs):
-                K = cams[b] if cams is not None else KH
-                n_it += _check_sequence(o, b, _oframe(idx[k][b], K, size), _oframe(ref_of[b], K, size), rob, given, depth,
-                                        "push %d seq %d of %d" % (k, b, B))
-                n += 1
-            elif st != TRACKED:
-                assert o["s2"][b] == 0.0, (k, b, st)   # SKIPPED / STARTED: no stale scale
-            if kf:
-                if st == STARTED or (st == TRACKED and o["world"][2][b]):
-                    ref_of[b] = idx[k][b]
-            elif st in (TRACKED, STARTED):
-                ref_of[b] = idx[k][b]
-    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * (B if seqs is None else len(seqs))) and n_it > 3 * n, (n, n_it)
+
+    def check(k, b, kr, o, K):
+        return _check_sequence(o, b, tb.oframe(idx[k][b], K, size), tb.oframe(idx[kr][b], K, size), rob, given, depth,
+                               "push %d seq %d of %d" % (k, b, B))
+    # (SKIPPED / STARTED: no stale scale)
+    n, _ = tb.walk(outs, B, check, lambda o, b: o["s2"][b] == 0.0, kf=kf, cams=cams, seqs=seqs, min_tracked=min_tracked)
     assert rr.nonempty_calls() >= before + n // 2
     return outs
 
@@ -383,80 +221,71 @@ def _lockstep(cfg, B, rob, acts=None, kf=False, cams=None, size=SIZE, scales_on_
 @pytest.mark.parametrize("kind", [HUBER, STUDENT])
 def test_batch_lockstep(kind, mode, B):
     """B = 11: k_gn_solve_rw takes 8 sequences per workgroup, so the second workgroup is partly filled"""
-    _lockstep(_cfg(), B, _rob(kind, mode))
+    _lockstep(tb.cfg(), B, tb.rob(kind, mode))
 
 
 def test_batch_lockstep_raster_finest_level():
-    _lockstep(_cfg(), 3, _rob(HUBER), size=(328, 248))
+    _lockstep(tb.cfg(), 3, tb.rob(HUBER), size=(328, 248))
 
 
 @pytest.fixture(scope="module")
 def base5():
     """Huber, adaptive scale, five sequences on the default schedule: what the schedule variants must reproduce bit for bit"""
-    return _lockstep(_cfg(), 5, _rob(HUBER))
+    return _lockstep(tb.cfg(), 5, tb.rob(HUBER))
 
 
 @pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "lds_patch", "host_feed"])
 def test_schedule_variants_give_the_same_records(variant, base5):
-    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1),
-              lds_patch=dict(gn_use_lds_patch=2)).get(variant, {})
-    cfg = _cfg(**kw)
-    other = _run(cfg, 5, _wide_idx(5), rob=_rob(HUBER), feed="host" if variant == "host_feed" else "device")
-    _same(base5, other)
-    for x, y in zip(base5, other):
-        np.testing.assert_array_equal(x["s2"], y["s2"])
-    _lockstep(_cfg(), 5, _rob(HUBER), outs=other)
+    cfg = tb.cfg(**tb.SCHEDULE_VARIANTS.get(variant, {}))
+    other = tb.run(cfg, 5, tb.wide_idx(5), **_weights(tb.rob(HUBER)), feed="host" if variant == "host_feed" else "device")
+    tb.same(base5, other)   # (the scales included)
+    _lockstep(tb.cfg(), 5, tb.rob(HUBER), outs=other)
 
 
 def test_two_streams():
     """two sub-batches need more than 16 sequences (19: not a multiple of 8 either); the table is offset per sub-batch"""
-    one = _lockstep(_cfg(), 19, _rob(STUDENT))
-    two = _run(_cfg(track_streams=2), 19, _wide_idx(19), rob=_rob(STUDENT))
-    _same(one, two)
-    for x, y in zip(one, two):
-        np.testing.assert_array_equal(x["s2"], y["s2"])
+    one = _lockstep(tb.cfg(), 19, tb.rob(STUDENT))
+    two = tb.run(tb.cfg(track_streams=2), 19, tb.wide_idx(19), **_weights(tb.rob(STUDENT)))
+    tb.same(one, two)   # (the scales included)
 
 
 def test_raw_feed():
-    a = _run(_cfg(), 5, _wide_idx(5), rob=_rob(STUDENT), feed="raw")
-    b = _run(_cfg(), 5, _wide_idx(5), rob=_rob(STUDENT), feed="raw_host")
-    _same(a, b)
+    a = tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw", **_weights(tb.rob(STUDENT)))
+    b = tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw_host", **_weights(tb.rob(STUDENT)))
+    tb.same(a, b)
     assert all((o["s2"] > 0).all() and np.isfinite(o["s2"]).all() for o in a[1:])
 
 
 def test_per_sequence_intrinsics():
-    cams = np.stack([KH] * 5).astype(np.float32)
-    for b in range(5):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    _lockstep(_cfg(), 5, _rob(HUBER), cams=cams)
+    _lockstep(tb.cfg(), 5, tb.rob(HUBER), cams=tb.sequence_cams(5))
 
 
 def test_actions_and_device_scales():
     """SKIP / RESTART leave no stale scale (checked in _lockstep), and device-resident scale rows are read in stream order"""
-    for rob, seed, dev in ((_rob(STUDENT, GIVEN), 9, True), (_rob(HUBER), 4, False)):
-        acts = _acts(5, 3, seed)
+    for rob, seed, dev in ((tb.rob(STUDENT, GIVEN), 9, True), (tb.rob(HUBER), 4, False)):
+        acts = tb.acts(5, 3, seed)
         assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
-        _lockstep(_cfg(), 5, rob, acts=acts, scales_on_device=dev, min_tracked=3)
+        _lockstep(tb.cfg(), 5, rob, acts=acts, scales_on_device=dev, min_tracked=3)
 
 
 def test_keyframes():
-    _lockstep(_cfg(keyframe_max_frames=2), 5, _rob(HUBER), kf=True)
+    _lockstep(tb.cfg(keyframe_max_frames=2), 5, tb.rob(HUBER), kf=True)
 
 
 def test_device_scales_follow_the_stream():
     """rows written on the device before each push are the rows that push uses"""
     import torch
     B = 3
-    g, d, s = _frames()
-    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
-    bt.set_robust_weights(**_rob(HUBER, GIVEN))
+    g, d, s = tb.frames()
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
+    bt.set_robust_weights(**tb.rob(HUBER, GIVEN))
     rows = torch.zeros(B, dtype=torch.float32, device="cuda")
     bt.set_robust_scales(rows.data_ptr(), on_device=True)
     keep = []
     for k, val in enumerate((0.5, 0.02, 0.07)):
         rows.fill_(val)
         torch.cuda.synchronize()
-        t = [_dev(x[[k, k + 1, k + 2]]) for x in (g, d, s)]
+        t = [tb.dev(x[[k, k + 1, k + 2]]) for x in (g, d, s)]
         keep.append(t)
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         s2 = bt.last_robust_scales()
@@ -474,27 +303,10 @@ class RobustReplay(lockstep.Replay):
 
     def _track(self, obj, ref, log):
         last, n = rr.replay_call(log, rr.oracle_terms(obj, ref, self.crop), lockstep.LEVELS, self.rob["kind"], self.rob["param"], ADAPTIVE,
-                                 floor2=_floor2(), tag=self._where("robust"), depth=self.depth)
+                                 floor2=tb.floor2(), tag=self._where("robust"), depth=self.depth)
         self.last = last
         self.n_iterations += n
         return np.asarray(log["xi_after"][lockstep.TOP][int(log["n_iter"][lockstep.TOP]) - 1], np.float32).copy()
-
-
-def mono_cameras(B):
-    """K640 for sequence 0, then a camera per sequence (the frames stay the ones rendered with K640: the batch and the oracle read
-    them with the same K)"""
-    Ks = np.stack([np.asarray(K640, np.float32).reshape(3, 3)] * B)
-    for q in range(B):
-        Ks[q, 0, 0] *= 1.0 + 0.01 * q; Ks[q, 1, 1] *= 1.0 - 0.005 * q
-    return Ks
-
-
-def mono_plan(mb):
-    """The plan of a two-sequence mono batch with the default tile config (gn_pixels_per_thread = 0) and an opt-in term: 2 x 75 tiles
-    are far below 1024, so every level (40x30, 80x60, 160x120) runs <1, 1> in launch pairs on raster tiles.  Returns the depths."""
-    for l, tiles in enumerate((5, 19, 75)):
-        assert mb.level_plan(l) == dict(ppt=1, group=1, tiles_2d=False, tiles=tiles, schedule=dvo.PLAN_PAIRS), (l, mb.level_plan(l))
-    return gn_sums.plan_depths(mb, lockstep.LEVELS)
 
 
 def _mono_contract(per_camera):
@@ -502,26 +314,26 @@ def _mono_contract(per_camera):
     k_track_gn_rw_cam kernels"""
     orc.set_tracker_params()    # the mono batch of this test runs the reference's constants
     try:
-        g, init, ml = _mono_frames()
+        g, init, ml = tb.mono_frames()
         B = 2
         orders = [[0, 1, 2, 3], [5, 4, 3, 2]]
         sig = np.full_like(init, ml.INIT_SIGMA)
-        rob = _rob(HUBER)
-        Ks = mono_cameras(B) if per_camera else [K640] * B
-        mb = dvo.MonoBatch(B, Ks if per_camera else K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=MONO_SEED),
+        rob = tb.rob(HUBER)
+        Ks = tb.sequence_cams(B, K640) if per_camera else [K640] * B
+        mb = dvo.MonoBatch(B, Ks if per_camera else K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tb.MONO_SEED),
                            per_sequence_K=per_camera)
         mb.setInitialDepth(init, sig)
         mb.set_track_quality(True)
         mb.set_robust_weights(**rob)
-        depths = mono_plan(mb)
-        reps = [RobustReplay(Ks[q], 640, 480, MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        depths = tb.mono_plan(mb)
+        reps = [RobustReplay(Ks[q], 640, 480, tb.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
         for r in reps:
             r.depth = depths
         before = rr.nonempty_calls()
         n = 0
         for k in range(len(orders[0])):
             fr = np.stack([g[orders[q][k]] for q in range(B)])
-            t = _dev(fr)
+            t = tb.dev(fr)
             mb.odometrize_device(t.data_ptr())
             rec = mb.last_track_quality()
             s2 = mb.last_robust_scales()
@@ -552,10 +364,6 @@ def test_mono_records_match_the_contract_per_camera():
 
 
 # ------------------------------------------------------------------------------------------------------------------ 6: it helps
-def _se3_log_rel(P1, P0):
-    return orc.se3_log((np.linalg.inv(P1) @ P0).astype(np.float32)).astype(np.float64)
-
-
 def test_robust_weights_beat_plain_under_an_occluder():
     """Ten object frames with a random-texture rectangle over a fifth to a quarter of the view, one batch of ten sequences per estimator.
     Each robust kind must be closer to the true motion than plain in at least 8 of the 10 cases and its summed error at most 0.7 times
@@ -563,7 +371,7 @@ def test_robust_weights_beat_plain_under_an_occluder():
     the GPU here so that a miss can be told from a difference of the two."""
     g, d, s, poses = synth.sequence(3, 320, 240, KH, seed=42, sigma_value=0.5, sigma_t=0.01, sigma_r_deg=0.5)
     g, d, s = g.numpy(), d.numpy(), s.numpy()
-    gt = _se3_log_rel(poses[1], poses[0])
+    gt = tb.se3_log_rel(poses[1], poses[0])
     cases = [(f, seed) for f in (0.2, 0.25) for seed in range(7, 12)]
     obj = []
     for f, seed in cases:
@@ -574,22 +382,22 @@ def test_robust_weights_beat_plain_under_an_occluder():
         obj.append(im)
     obj = np.stack(obj)
     B = len(cases)
-    cfg = _cfg(max_iterations=15)
+    cfg = tb.cfg(max_iterations=15)
     err, rep = {}, {}
     ref = orc.OFrame(g[0], d[0], s[0], KH, LEVELS, CULLS)
     for kind in (dvo.ROBUST_NONE, HUBER, STUDENT):
         bt = dvo.Batch(B, KH, 320, 240, LEVELS, CULLS, cfg=cfg)
         if kind != dvo.ROBUST_NONE:
             bt.set_robust_weights(kind, PARAM[kind], ADAPTIVE, FLOOR)
-        t0 = [_dev(np.stack([x[0]] * B)) for x in (g, d, s)]
+        t0 = [tb.dev(np.stack([x[0]] * B)) for x in (g, d, s)]
         bt.push_device(t0[0].data_ptr(), t0[1].data_ptr(), t0[2].data_ptr())
-        t1 = [_dev(obj), _dev(np.stack([d[1]] * B)), _dev(np.stack([s[1]] * B))]
+        t1 = [tb.dev(obj), tb.dev(np.stack([d[1]] * B)), tb.dev(np.stack([s[1]] * B))]
         bt.push_device(t1[0].data_ptr(), t1[1].data_ptr(), t1[2].data_ptr())
         xi, _ = bt.last_poses()
         bt.close()
         err[kind] = np.array([np.linalg.norm(xi[b].astype(np.float64) - gt) for b in range(B)])
         rep[kind] = np.array([np.linalg.norm(rr.irls_track(orc.OFrame(obj[b], d[1], s[1], KH, LEVELS, CULLS), ref, LEVELS, kind,
-                                                           PARAM.get(kind, 1.0), _floor2(), False, 15, 2e-5)[0].astype(np.float64) - gt)
+                                                           PARAM.get(kind, 1.0), tb.floor2(), False, 15, 2e-5)[0].astype(np.float64) - gt)
                               for b in range(B)])
     for kind in (HUBER, STUDENT):
         wins, ratio = int((err[kind] < err[0]).sum()), err[kind].sum() / err[0].sum()
@@ -603,7 +411,7 @@ def test_robust_weights_beat_plain_under_an_occluder():
 def test_errors_are_refused():
     L = dvo.lib()
     import ctypes as C
-    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg())
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
     RC = dvo.RobustConfig
     sz = C.sizeof(RC)
     bad = [RC(sz, 3, ADAPTIVE, 1.0, 1e-3), RC(sz, -1, ADAPTIVE, 1.0, 1e-3), RC(sz, HUBER, 2, 1.0, 1e-3), RC(sz, HUBER, -1, 1.0, 1e-3),
@@ -617,23 +425,23 @@ def test_errors_are_refused():
         bt.set_robust_scales(rows)                  # weights are off
     with pytest.raises(dvo.DvoError):
         bt.last_robust_scales()                     # nothing pushed
-    bt.set_robust_weights(**_rob(HUBER, ADAPTIVE))
+    bt.set_robust_weights(**tb.rob(HUBER, ADAPTIVE))
     with pytest.raises(dvo.DvoError):
         bt.set_robust_scales(rows)                  # rows outside the GIVEN mode
     bt.set_robust_scales(None)                      # clearing is always allowed
     assert L.dvo_batch_last_robust_scales(bt._p, None) == dvo.DVO_ERR_BAD_ARGUMENT
     bt.set_robust_weights(None)
-    g, d, s = _frames()
-    t = [_dev(x[:2]) for x in (g, d, s)]
+    g, d, s = tb.frames()
+    t = [tb.dev(x[:2]) for x in (g, d, s)]
     bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     with pytest.raises(dvo.DvoError):
         bt.last_robust_scales()                     # the push ran without weights
     assert L.dvo_batch_set_robust_weights(bt._p, C.byref(RC(sz, HUBER, GIVEN, 1.345, 0.0))) == dvo.DVO_ERR_BAD_ARGUMENT
-    bt.set_robust_weights(**_rob(HUBER, GIVEN))
+    bt.set_robust_weights(**tb.rob(HUBER, GIVEN))
     with pytest.raises(dvo.DvoError):
         bt.last_robust_scales()                     # enabled from the next push on
     bt.set_robust_scales(np.float32([0.05, 0.02]))
-    t2 = [_dev(x[1:3]) for x in (g, d, s)]
+    t2 = [tb.dev(x[1:3]) for x in (g, d, s)]
     bt.push_device(t2[0].data_ptr(), t2[1].data_ptr(), t2[2].data_ptr())
     np.testing.assert_array_equal(bt.last_robust_scales(), np.float32([0.05, 0.02]) * np.float32([0.05, 0.02]))
     bt.close()

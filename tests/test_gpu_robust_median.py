@@ -1,6 +1,6 @@
 """The median (MAD) robust scale of a batch (dvo_batch_set_robust_median, include/dvo.h) on the GPU, both batch kinds.
 
-The shapes are tests/test_gpu_robust.py's: 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread (40x30 and 80x60 raster
+The shapes are tests/term_batch.py's: 320x240 frames, 3 levels, culls 1, crop off, 4 pixels per thread (40x30 and 80x60 raster
 levels, 160x120 2-D tiles), one case at 328x248 where the finest level is raster too.  The device's per-pixel r is the oracle's bit for
 bit (tests/robust_ref.py), so the bin counts are compared for EQUALITY with the replica's (tests/robust_median_ref.py), not within the
 edge slack e_k; the slack condition sum e_k <= n / 1000 is asserted all the same, so that the inputs would not hide a wrong histogram
@@ -17,99 +17,30 @@ import lockstep
 import orc
 import robust_median_ref as mr
 import robust_ref as rr
-import test_gpu_robust as tr
+import term_batch as tb
 from dvo_amd import synth
+from term_batch import CULLS, FLOOR, HUBER, KH, LEVELS, PARAM, SIZE, SKIP, RESTART, STARTED, STUDENT, TOP, TRACKED
+from util import K640
 
 pytestmark = pytest.mark.gpu
 
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
-HUBER, STUDENT = dvo.ROBUST_HUBER, dvo.ROBUST_STUDENT_T
-SIZE, LEVELS, CULLS, TOP, KH, PARAM, FLOOR = tr.SIZE, tr.LEVELS, tr.CULLS, tr.TOP, tr.KH, tr.PARAM, tr.FLOOR
 BIND = 0.2     # a floor that binds: s2 = 0.04 is above every median scale of these frames (|r| medians are below 0.05)
 F32 = np.float32
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _oracle_steps():
-    orc.set_tracker_params(step3=tr.STEPS, min_residual=0.0, min_update=2e-5)
-    yield
-    orc.set_tracker_params()
+    with tb.oracle_steps():
+        yield
 
 
-def _md(kind, floor=FLOOR):
-    return dict(kind=kind, param=PARAM[kind], scale_floor=floor)
-
-
-def _floor2(floor=FLOOR):
-    return F32(floor) * F32(floor)
-
-
-def _run(cfg, B, idx, md=None, clear=False, acts=None, kf=False, feed="device", cams=None, size=SIZE):
-    """tests/test_gpu_robust.py's _run with the median scale: per push dict(status, xi, T, logs, q, s2, rlogs, hist, world)"""
-    g, d, s = tr._frames(size)
-    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
-    if kf:
-        bt.set_keyframe_tracking(True)
-    bt.set_track_quality(True)
-    if cams is not None:
-        bt.set_intrinsics(cams)
-    keep = []
-    if md:
+def _median(md, clear=False):
+    """run() keywords of a batch with the median scale (clear: set, then turned off before the first push)"""
+    def setup(bt, keep):
         bt.set_robust_median(**md)
         if clear:
             bt.set_robust_weights(dvo.ROBUST_NONE)
-    outs = []
-    for k in range(len(idx)):
-        sel = list(idx[k])
-        gi, di, si = g[sel], d[sel], s[sel]
-        if acts is not None:
-            bt.set_actions(np.asarray(acts[k], np.uint8))
-        if feed == "host":
-            bt.push_host(gi, di, si)
-        elif feed in ("raw", "raw_host"):
-            g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
-            if feed == "raw_host":
-                bt.push_raw_host(g8, d16)
-            else:
-                import torch
-                tg = tr._dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-                torch.cuda.synchronize()
-                keep.append((tg, td))
-                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-        else:
-            t = [tr._dev(x) for x in (gi, di, si)]
-            keep.append(t)
-            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality())
-        if md and not clear:
-            o["s2"] = bt.last_robust_scales()
-            o["rlogs"] = [bt.last_robust_log(b) for b in range(B)]
-            o["hist"] = np.stack([bt.last_robust_histogram(b) for b in range(B)])
-        if k > 0 or acts is not None or kf:
-            xi, T = bt.last_poses()
-            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
-            if kf:
-                o["world"] = bt.world_poses()
-        outs.append(o)
-    bt.close()
-    return outs
-
-
-def _rlogbits(lg):
-    return (tuple(int(n) for n in lg["n_iter"][:LEVELS]), lg["s2"].tobytes(), lg["median_bin"].tobytes(), lg["count"].tobytes(),
-            lg["prime_bin"], lg["prime_count"])
-
-
-def _same(a, b):
-    """poses, track logs, quality records, scales, robust logs and histograms of two runs, bit for bit"""
-    tr._same(a, b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        assert ("rlogs" in x) == ("rlogs" in y)
-        if "rlogs" in x:
-            np.testing.assert_array_equal(x["s2"], y["s2"], err_msg="push %d" % k)
-            np.testing.assert_array_equal(x["hist"], y["hist"], err_msg="push %d" % k)
-            assert [_rlogbits(l) for l in x["rlogs"]] == [_rlogbits(l) for l in y["rlogs"]], "push %d robust logs" % k
+    return dict(setup=setup, reads=() if clear else ("median",))
 
 
 def _empty(rlog):
@@ -144,18 +75,18 @@ def _assert_counts(got, t, where):
 @pytest.fixture(scope="module")
 def huber3():
     """Huber, median scale, three sequences on the default schedule"""
-    return _run(tr._cfg(), 3, tr._wide_idx(3), md=_md(HUBER))
+    return tb.run(tb.cfg(), 3, tb.wide_idx(3), **_median(tb.md(HUBER)))
 
 
 @pytest.mark.parametrize("size", [SIZE, (328, 248)])
 def test_operator_counts_equal_the_replica(size, huber3):
     """at the start pose and at the logged poses of a real run, on every level; 328x248: every level is raster and the deferred border
     loop bins as well"""
-    cfg = tr._cfg()
+    cfg = tb.cfg()
     depth = gn_sums.depth_for_cfg(cfg)
-    idx = tr._wide_idx(3)
-    obj, ref = tr._oframe(idx[1][0], size=size), tr._oframe(idx[0][0], size=size)
-    poses = tr._level_poses(huber3[1]["logs"][0])
+    idx = tb.wide_idx(3)
+    obj, ref = tb.oframe(idx[1][0], size=size), tb.oframe(idx[0][0], size=size)
+    poses = tb.level_poses(huber3[1]["logs"][0])
     for l in range(LEVELS):
         for xi in (np.zeros(6, F32), poses[l]):
             t = _terms(obj, ref, l, xi)
@@ -168,8 +99,8 @@ def test_operator_counts_equal_the_replica(size, huber3):
 
 
 def test_operator_extreme_bins():
-    cfg = tr._cfg()
-    ref = tr._oframe(0)
+    cfg = tb.cfg()
+    ref = tb.oframe(0)
     z = np.zeros(6, F32)
     for l in range(LEVELS):
         # identical frames: every residual is below 2^-16 (zero up to the warp's rounding): bin 0
@@ -196,7 +127,7 @@ def _check_sequence(o, b, obj, ref, md, depth, where):
     the robust log's s2, the reported scale, the kept histogram and the finest level's record"""
     kind, param = md["kind"], md["param"]
     lg, rl = o["logs"][b], o["rlogs"][b]
-    n_sel = mr.assert_selection(rl, LEVELS, kind, param, _floor2(md["scale_floor"]), where)
+    n_sel = mr.assert_selection(rl, LEVELS, kind, param, tb.floor2(md["scale_floor"]), where)
     last, n_it = mr.replay_call(lg, rl, rr.oracle_terms(obj, ref, False), LEVELS, kind, param, tag=where, depth=depth)
     assert n_sel == n_it
     t, s2, l, it = last
@@ -214,29 +145,17 @@ def _check_sequence(o, b, obj, ref, md, depth, where):
 
 
 def _lockstep(cfg, B, md, acts=None, kf=False, cams=None, size=SIZE, outs=None, min_tracked=None):
-    idx = tr._wide_idx(B)
+    idx = tb.wide_idx(B)
     if outs is None:
-        outs = _run(cfg, B, idx, md=md, acts=acts, kf=kf, cams=cams, size=size)
+        outs = tb.run(cfg, B, idx, acts=acts, kf=kf, cams=cams, size=size, **_median(md))
     depth = gn_sums.depth_for_cfg(cfg)
     before = rr.nonempty_calls()
-    ref_of = [None] * B
-    n = n_it = 0
-    for k, o in enumerate(outs):
-        for b in range(B):
-            st = o["status"][b]
-            if st == TRACKED:
-                K = cams[b] if cams is not None else KH
-                n_it += _check_sequence(o, b, tr._oframe(idx[k][b], K, size), tr._oframe(ref_of[b], K, size), md, depth,
-                                        "push %d seq %d of %d" % (k, b, B))
-                n += 1
-            else:   # SKIPPED / STARTED: no stale scale, a zero histogram, an empty log
-                assert o["s2"][b] == 0.0 and not o["hist"][b].any() and _empty(o["rlogs"][b]), (k, b, st)
-            if kf:
-                if st == STARTED or (st == TRACKED and o["world"][2][b]):
-                    ref_of[b] = idx[k][b]
-            elif st in (TRACKED, STARTED):
-                ref_of[b] = idx[k][b]
-    assert n >= (min_tracked if min_tracked is not None else (len(idx) - 1) * B) and n_it > 3 * n, (n, n_it)
+
+    def check(k, b, kr, o, K):
+        return _check_sequence(o, b, tb.oframe(idx[k][b], K, size), tb.oframe(idx[kr][b], K, size), md, depth, "push %d seq %d of %d" % (k, b, B))
+    # (SKIPPED / STARTED: no stale scale, a zero histogram, an empty log)
+    n, _ = tb.walk(outs, B, check, lambda o, b: o["s2"][b] == 0.0 and not o["hist"][b].any() and _empty(o["rlogs"][b]), kf=kf, cams=cams,
+                   min_tracked=min_tracked)
     assert rr.nonempty_calls() >= before + n // 2
     return outs
 
@@ -245,29 +164,22 @@ def _lockstep(cfg, B, md, acts=None, kf=False, cams=None, size=SIZE, outs=None, 
 def test_batch_lockstep(B, kind, floor):
     """11 and 17: k_gn_solve_md takes 8 sequences per workgroup, so the last workgroup is partly filled.  floor 0.2 binds at every
     iteration, 1e-3 at none"""
-    outs = _lockstep(tr._cfg(), B, _md(kind, floor))
+    outs = _lockstep(tb.cfg(), B, tb.md(kind, floor))
     s2 = np.concatenate([o["s2"] for o in outs[1:]])
-    assert (s2 == _floor2(BIND)).all() if floor == BIND else (s2 > _floor2()).all() and np.isfinite(s2).all()
+    assert (s2 == tb.floor2(BIND)).all() if floor == BIND else (s2 > tb.floor2()).all() and np.isfinite(s2).all()
 
 
 def test_batch_lockstep_raster_finest_level():
-    _lockstep(tr._cfg(), 3, _md(HUBER), size=(328, 248))
+    _lockstep(tb.cfg(), 3, tb.md(HUBER), size=(328, 248))
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3: plan independence
 PAIRS = [(1, 1), (2, 1), (2, 2), (4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4)]
 
 
-def _cams(B):
-    cams = np.stack([KH] * B).astype(F32)
-    for b in range(B):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    return cams
-
-
 @pytest.fixture(scope="module")
 def pair_base():
-    return _run(tr._cfg(), 2, tr._wide_idx(2, pushes=2), md=_md(STUDENT))
+    return tb.run(tb.cfg(), 2, tb.wide_idx(2, pushes=2), **_median(tb.md(STUDENT)))
 
 
 @pytest.mark.parametrize("ppt,group", PAIRS)
@@ -280,68 +192,69 @@ def test_every_tile_shape_gives_the_same_records(ppt, group, pair_base):
     everything decided at the start pose (the priming pair's (m, n) and the first iteration's s2, m, n are the default plan's), and
     the contract itself -- every pair's run is replayed against the oracle at its own poses, its kept histograms equal the
     replica's counts bin for bin."""
-    cfg = tr._cfg(gn_gather_group=group)
+    cfg = tb.cfg(gn_gather_group=group)
     cfg.gn_pixels_per_thread = ppt
-    idx = tr._wide_idx(2, pushes=2)
-    plain = _run(cfg, 2, idx, md=_md(STUDENT))
-    cams = _run(cfg, 2, idx, md=_md(STUDENT), cams=np.stack([KH] * 2).astype(F32).reshape(2, 3, 3))
-    _same(plain, cams)
+    idx = tb.wide_idx(2, pushes=2)
+    plain = tb.run(cfg, 2, idx, **_median(tb.md(STUDENT)))
+    cams = tb.run(cfg, 2, idx, cams=np.stack([KH] * 2).astype(F32).reshape(2, 3, 3), **_median(tb.md(STUDENT)))
+    tb.same(plain, cams)
     for b in range(2):
         x, y = pair_base[1]["rlogs"][b], plain[1]["rlogs"][b]
         assert y["prime_count"] > 0 and (x["prime_bin"], x["prime_count"]) == (y["prime_bin"], y["prime_count"])
         assert (x["s2"][0][0].tobytes(), x["median_bin"][0][0], x["count"][0][0]) == (y["s2"][0][0].tobytes(), y["median_bin"][0][0], y["count"][0][0])
-    _lockstep(cfg, 2, _md(STUDENT), outs=plain, min_tracked=2)
-    _lockstep(cfg, 2, _md(STUDENT), outs=cams, cams=np.stack([KH] * 2).astype(F32).reshape(2, 3, 3), min_tracked=2)
+    _lockstep(cfg, 2, tb.md(STUDENT), outs=plain, min_tracked=2)
+    _lockstep(cfg, 2, tb.md(STUDENT), outs=cams, cams=np.stack([KH] * 2).astype(F32).reshape(2, 3, 3), min_tracked=2)
 
 
 @pytest.fixture(scope="module")
 def base5():
-    return _lockstep(tr._cfg(), 5, _md(HUBER))
+    return _lockstep(tb.cfg(), 5, tb.md(HUBER))
 
 
 @pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "host_feed"])
 def test_schedule_variants_give_the_same_records(variant, base5):
-    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1)).get(variant, {})
-    _same(base5, _run(tr._cfg(**kw), 5, tr._wide_idx(5), md=_md(HUBER), feed="host" if variant == "host_feed" else "device"))
+    other = tb.run(tb.cfg(**tb.SCHEDULE_VARIANTS.get(variant, {})), 5, tb.wide_idx(5), feed="host" if variant == "host_feed" else "device",
+                   **_median(tb.md(HUBER)))
+    tb.same(base5, other)
 
 
 def test_raw_feed():
-    a = _run(tr._cfg(), 5, tr._wide_idx(5), md=_md(STUDENT), feed="raw")
-    b = _run(tr._cfg(), 5, tr._wide_idx(5), md=_md(STUDENT), feed="raw_host")
-    _same(a, b)
+    a = tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw", **_median(tb.md(STUDENT)))
+    b = tb.run(tb.cfg(), 5, tb.wide_idx(5), feed="raw_host", **_median(tb.md(STUDENT)))
+    tb.same(a, b)
     assert all((o["s2"] > 0).all() and np.isfinite(o["s2"]).all() and o["hist"].any(axis=1).all() for o in a[1:])
 
 
 def test_two_streams():
     """two sub-batches need more than 16 sequences (19: not a multiple of 8 either); the tables are offset per sub-batch"""
-    one = _run(tr._cfg(), 19, tr._wide_idx(19), md=_md(STUDENT))
-    two = _run(tr._cfg(track_streams=2), 19, tr._wide_idx(19), md=_md(STUDENT))
-    _same(one, two)
+    one = tb.run(tb.cfg(), 19, tb.wide_idx(19), **_median(tb.md(STUDENT)))
+    two = tb.run(tb.cfg(track_streams=2), 19, tb.wide_idx(19), **_median(tb.md(STUDENT)))
+    tb.same(one, two)
     assert all(o["hist"].any(axis=1).all() for o in one[1:])
-    _lockstep(tr._cfg(), 19, _md(STUDENT), outs=two, min_tracked=38)
+    _lockstep(tb.cfg(), 19, tb.md(STUDENT), outs=two, min_tracked=38)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5: lifecycle
 def test_set_then_cleared_is_never_set():
-    tr._same(tr._run(tr._cfg(), 5, tr._wide_idx(5)), _run(tr._cfg(), 5, tr._wide_idx(5), md=_md(HUBER), clear=True))
+    tb.same(tb.run(tb.cfg(), 5, tb.wide_idx(5)), tb.run(tb.cfg(), 5, tb.wide_idx(5), **_median(tb.md(HUBER), clear=True)))
 
 
 def test_actions_leave_nothing_stale():
-    acts = tr._acts(5, 3, 4)
+    acts = tb.acts(5, 3, 4)
     assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
-    _lockstep(tr._cfg(), 5, _md(HUBER), acts=acts, min_tracked=3)
+    _lockstep(tb.cfg(), 5, tb.md(HUBER), acts=acts, min_tracked=3)
 
 
 def test_camera_change_restarts_without_a_stale_record():
     B = 2
-    g, d, s = tr._frames()
-    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tr._cfg())
-    bt.set_robust_median(**_md(STUDENT))
-    cams = _cams(B + 1)[1:]   # (both sequences' focal lengths change)
+    g, d, s = tb.frames()
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
+    bt.set_robust_median(**tb.md(STUDENT))
+    cams = tb.sequence_cams(B + 1)[1:]   # (both sequences' focal lengths change)
     for k in range(3):
         if k == 2:
             bt.set_intrinsics(cams)   # the references no longer fit: every sequence restarts
-        t = [tr._dev(x[[k, k + 1]]) for x in (g, d, s)]
+        t = [tb.dev(x[[k, k + 1]]) for x in (g, d, s)]
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         st = bt.last_status()
         for b in range(B):
@@ -354,7 +267,7 @@ def test_camera_change_restarts_without_a_stale_record():
 
 
 def test_keyframes():
-    _lockstep(tr._cfg(keyframe_max_frames=2), 5, _md(HUBER), kf=True)
+    _lockstep(tb.cfg(keyframe_max_frames=2), 5, tb.md(HUBER), kf=True)
 
 
 class MedianReplay(lockstep.Replay):
@@ -365,7 +278,7 @@ class MedianReplay(lockstep.Replay):
     depth = 17
 
     def _track(self, obj, ref, log):
-        n_sel = mr.assert_selection(self.rlog, lockstep.LEVELS, self.md["kind"], self.md["param"], _floor2(), self._where("median"))
+        n_sel = mr.assert_selection(self.rlog, lockstep.LEVELS, self.md["kind"], self.md["param"], tb.floor2(), self._where("median"))
         last, n = mr.replay_call(log, self.rlog, rr.oracle_terms(obj, ref, self.crop), lockstep.LEVELS, self.md["kind"], self.md["param"],
                                  tag=self._where("median"), depth=self.depth)
         assert n_sel == n
@@ -377,21 +290,21 @@ class MedianReplay(lockstep.Replay):
 def test_mono_batch_matches_the_contract():
     orc.set_tracker_params()    # the mono batch runs the reference's constants
     try:
-        g, init, ml = tr._mono_frames()
+        g, init, ml = tb.mono_frames()
         B = 2
         orders = [[0, 1, 2, 3], [5, 4, 3, 2]]
         sig = np.full_like(init, ml.INIT_SIGMA)
-        md = _md(HUBER)
-        mb = dvo.MonoBatch(B, tr.K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tr.MONO_SEED))
+        md = tb.md(HUBER)
+        mb = dvo.MonoBatch(B, K640, 640, 480, ring_keyframes=16, cfg=dvo.default_config(rng_seed=tb.MONO_SEED))
         mb.setInitialDepth(init, sig)
         mb.set_track_quality(True)
         mb.set_robust_median(**md)
-        depths = tr.mono_plan(mb)
-        reps = [MedianReplay(tr.K640, 640, 480, tr.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
+        depths = tb.mono_plan(mb)
+        reps = [MedianReplay(K640, 640, 480, tb.MONO_SEED, init, sig, name="sequence %d" % q) for q in range(B)]
         n = 0
         for k in range(len(orders[0])):
             fr = np.stack([g[orders[q][k]] for q in range(B)])
-            t = tr._dev(fr)
+            t = tb.dev(fr)
             mb.odometrize_device(t.data_ptr())
             rec = mb.last_track_quality()
             s2 = mb.last_robust_scales()
@@ -411,12 +324,12 @@ def test_mono_batch_matches_the_contract():
         mb.close()
         assert n == B * (len(orders[0]) - 1)
     finally:
-        orc.set_tracker_params(step3=tr.STEPS, min_residual=0.0, min_update=2e-5)
+        orc.set_tracker_params(step3=tb.STEPS, min_residual=0.0, min_update=2e-5)
 
 
 def test_errors_are_refused():
     L = dvo.lib()
-    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tr._cfg())
+    bt = dvo.Batch(2, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg())
     RC = dvo.RobustConfig
     sz = C.sizeof(RC)
     MED, ADA, GIV = dvo.ROBUST_SCALE_MEDIAN, dvo.ROBUST_SCALE_ADAPTIVE, dvo.ROBUST_SCALE_GIVEN
@@ -433,13 +346,13 @@ def test_errors_are_refused():
     # the other terms on: refused; and the other terms' setters refuse while the median scale is on
     bt.set_affine_brightness(dvo.AFFINE_ESTIMATE)
     with pytest.raises(dvo.DvoError):
-        bt.set_robust_median(**_md(HUBER))
+        bt.set_robust_median(**tb.md(HUBER))
     bt.set_affine_brightness(dvo.AFFINE_OFF)
     bt.set_geometric(dvo.GEOMETRIC_ON)
     with pytest.raises(dvo.DvoError):
-        bt.set_robust_median(**_md(HUBER))
+        bt.set_robust_median(**tb.md(HUBER))
     bt.set_geometric(dvo.GEOMETRIC_OFF)
-    bt.set_robust_median(**_md(HUBER))
+    bt.set_robust_median(**tb.md(HUBER))
     for call in (lambda: bt.set_affine_brightness(dvo.AFFINE_ESTIMATE), lambda: bt.set_geometric(dvo.GEOMETRIC_ON),
                  lambda: bt.set_geometric_affine(), lambda: bt.set_robust_scales(np.ones(2, F32))):
         with pytest.raises(dvo.DvoError):
@@ -454,14 +367,14 @@ def test_errors_are_refused():
     assert L.dvo_batch_last_robust_log(bt._p, 0, None) == dvo.DVO_ERR_BAD_ARGUMENT
     assert L.dvo_batch_last_robust_histogram(bt._p, 2, (C.c_uint32 * 256)()) == dvo.DVO_ERR_BAD_ARGUMENT
     assert L.dvo_batch_last_robust_histogram(bt._p, 0, None) == dvo.DVO_ERR_BAD_ARGUMENT
-    g, d, s = tr._frames()
+    g, d, s = tb.frames()
     for k in range(2):
-        t = [tr._dev(x[k:k + 2]) for x in (g, d, s)]
+        t = [tb.dev(x[k:k + 2]) for x in (g, d, s)]
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     assert bt.last_robust_histogram(1).any() and bt.last_robust_log(1)["prime_count"] > 0
     # back to the adaptive scale through the existing setter: the next push leaves the median readers not ready
     bt.set_robust_weights(HUBER, 1.345, ADA, 1e-3)
-    t = [tr._dev(x[2:4]) for x in (g, d, s)]
+    t = [tb.dev(x[2:4]) for x in (g, d, s)]
     bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     assert (bt.last_robust_scales() > 0).all()
     with pytest.raises(dvo.DvoError):
@@ -479,7 +392,7 @@ def test_median_scale_beats_the_adaptive_scale_under_a_large_occluder():
     DESIGN.md §24 / §25: the losing estimator's error moves by tens of percent between seeds).  The figures are in DESIGN.md §30."""
     g, d, s, poses = synth.sequence(3, 320, 240, KH, seed=42, sigma_value=0.5, sigma_t=0.01, sigma_r_deg=0.5)
     g, d, s = g.numpy(), d.numpy(), s.numpy()
-    gt = tr._se3_log_rel(poses[1], poses[0])
+    gt = tb.se3_log_rel(poses[1], poses[0])
     cases = [(f, seed) for f in (0.4, 0.5) for seed in range(7, 12)]
     obj = []
     for f, seed in cases:
@@ -490,7 +403,7 @@ def test_median_scale_beats_the_adaptive_scale_under_a_large_occluder():
         obj.append(im)
     obj = np.stack(obj)
     B = len(cases)
-    cfg = tr._cfg(max_iterations=15)
+    cfg = tb.cfg(max_iterations=15)
     ref = orc.OFrame(g[0], d[0], s[0], KH, LEVELS, CULLS)
     err, rep = {}, {}
     for kind in (HUBER, STUDENT):
@@ -500,16 +413,16 @@ def test_median_scale_beats_the_adaptive_scale_under_a_large_occluder():
                 bt.set_robust_weights(kind, PARAM[kind], dvo.ROBUST_SCALE_ADAPTIVE, FLOOR)
             else:
                 bt.set_robust_median(kind, PARAM[kind], FLOOR)
-            t0 = [tr._dev(np.stack([x[0]] * B)) for x in (g, d, s)]
+            t0 = [tb.dev(np.stack([x[0]] * B)) for x in (g, d, s)]
             bt.push_device(t0[0].data_ptr(), t0[1].data_ptr(), t0[2].data_ptr())
-            t1 = [tr._dev(obj), tr._dev(np.stack([d[1]] * B)), tr._dev(np.stack([s[1]] * B))]
+            t1 = [tb.dev(obj), tb.dev(np.stack([d[1]] * B)), tb.dev(np.stack([s[1]] * B))]
             bt.push_device(t1[0].data_ptr(), t1[1].data_ptr(), t1[2].data_ptr())
             xi, _ = bt.last_poses()
             bt.close()
             err[kind, rule] = np.array([np.linalg.norm(xi[b].astype(np.float64) - gt) for b in range(B)])
             track = rr.irls_track if rule == "adaptive" else mr.median_track
             rep[kind, rule] = np.array([np.linalg.norm(track(orc.OFrame(obj[b], d[1], s[1], KH, LEVELS, CULLS), ref, LEVELS, kind, PARAM[kind],
-                                                             _floor2(), False, 15, 2e-5)[0].astype(np.float64) - gt) for b in range(B)])
+                                                             tb.floor2(), False, 15, 2e-5)[0].astype(np.float64) - gt) for b in range(B)])
     claimed = 0
     for kind in (HUBER, STUDENT):
         e_m, e_a, r_m, r_a = err[kind, "median"], err[kind, "adaptive"], rep[kind, "median"], rep[kind, "adaptive"]

@@ -12,12 +12,8 @@ import numpy as np
 import pytest
 
 import dvo_amd as dvo
-from test_gpu_affine import _alogbits
-from test_gpu_geometric import GEO, _glogbits
-from test_gpu_robust import CULLS, HUBER, KH, LEVELS, SIZE, _cfg, _dev, _frames, _logbits, _rob
-from test_gpu_robust_median import _md, _rlogbits
-from test_gpu_step_control import _lmbits
-from test_gpu_term_combinations import STATES
+import term_batch as tb
+from term_batch import CULLS, GEO, HUBER, KH, LEVELS, SIZE, STATES
 
 pytestmark = pytest.mark.gpu
 
@@ -26,37 +22,37 @@ PUSHES = (0, 1, 2)    # the frame every sequence is given at each push
 AFF = dict(mode=dvo.AFFINE_ESTIMATE)
 
 # how each setter of STATES is called, and what each state records: (name, read(bt, b) -> bytes or a tuple of them)
-SET = dict(robust_weights=lambda bt: bt.set_robust_weights(**_rob(HUBER)),
-           robust_median=lambda bt: bt.set_robust_median(**_md(HUBER)),
+SET = dict(robust_weights=lambda bt: bt.set_robust_weights(**tb.rob(HUBER)),
+           robust_median=lambda bt: bt.set_robust_median(**tb.md(HUBER)),
            affine_brightness=lambda bt: bt.set_affine_brightness(**AFF),
            geometric=lambda bt: bt.set_geometric(**GEO),
            geometric_affine=lambda bt: bt.set_geometric_affine(affine_mode=AFF["mode"], **GEO),
            step_control=lambda bt: bt.set_step_control())
 ROBUST = [("last_robust_scales", lambda bt, b: bt.last_robust_scales()[b].tobytes())]
-MEDIAN = ROBUST + [("last_robust_log", lambda bt, b: _rlogbits(bt.last_robust_log(b)))]
-AFFINE = [("last_affine", lambda bt, b: bt.last_affine()[b].tobytes()), ("last_affine_log", lambda bt, b: _alogbits(bt.last_affine_log(b)))]
+MEDIAN = ROBUST + [("last_robust_log", lambda bt, b: tb.rlogbits(bt.last_robust_log(b)))]
+AFFINE = [("last_affine", lambda bt, b: bt.last_affine()[b].tobytes()), ("last_affine_log", lambda bt, b: tb.alogbits(bt.last_affine_log(b)))]
 GEOMETRIC = [("last_geometric", lambda bt, b: bt.last_geometric()[b].tobytes()),
-             ("last_geometric_log", lambda bt, b: _glogbits(bt.last_geometric_log(b)))]
+             ("last_geometric_log", lambda bt, b: tb.glogbits(bt.last_geometric_log(b)))]
 STEP = [("last_step_control", lambda bt, b: bt.last_step_control()[b].tobytes()),
-        ("last_step_control_log", lambda bt, b: _lmbits(bt.last_step_control_log(b)))]
+        ("last_step_control_log", lambda bt, b: tb.lmbits(bt.last_step_control_log(b)))]
 RECORDS = dict(N=[], R=ROBUST, M=MEDIAN, A=AFFINE, RA=ROBUST + AFFINE, G=GEOMETRIC, GA=GEOMETRIC + AFFINE, L=STEP)
 
 
 def _run(state, B):
     """per tracking push and sequence: dict(xi, T, log, <the state's records>), everything as bytes"""
-    g, d, s = _frames(SIZE)
-    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg(fixed_iterations=0))
+    g, d, s = tb.frames(SIZE)
+    bt = dvo.Batch(B, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=tb.cfg(fixed_iterations=0))
     for setter in STATES[state]:
         SET[setter](bt)
     keep, outs = [], []
     for k, frame in enumerate(PUSHES):
-        t = [_dev(np.repeat(x[frame][None], B, axis=0)) for x in (g, d, s)]
+        t = [tb.dev(np.repeat(x[frame][None], B, axis=0)) for x in (g, d, s)]
         keep.append(t)
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         if k == 0:
             continue
         xi, T = bt.last_poses()
-        outs.append([dict([("xi", xi[b].tobytes()), ("T", T[b].tobytes()), ("log", _logbits(bt.last_track_log(b)))] +
+        outs.append([dict([("xi", xi[b].tobytes()), ("T", T[b].tobytes()), ("log", tb.logbits(bt.last_track_log(b)))] +
                           [(name, read(bt, b)) for name, read in RECORDS[state]]) for b in range(B)])
     bt.close()
     return outs

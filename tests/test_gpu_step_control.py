@@ -18,23 +18,15 @@ import gn_sums
 import lm_ref as lr
 import lockstep
 import orc
+import term_batch as tb
 from dvo_amd import synth
+from term_batch import CULLS, F32, KH, LEVELS, MIN_UPDATE, SIZE, SKIP, RESTART, STEPS, TOP, TRACK, TRACKED
 from util import K640, TOL_BACKWARD, assert_composed, backward_error
 
 pytestmark = pytest.mark.gpu
 
-F32 = np.float32
-SKIP, TRACK, RESTART = dvo.SEQ_SKIP, dvo.SEQ_TRACK, dvo.SEQ_RESTART
-TRACKED, SKIPPED, STARTED = dvo.SEQ_TRACKED, dvo.SEQ_SKIPPED, dvo.SEQ_STARTED
 FIRST, ACCEPT, REJECT = dvo.LM_FIRST, dvo.LM_ACCEPT, dvo.LM_REJECT
-SIZE = (320, 240)
-LEVELS, CULLS, TOP = 3, 1, 2
-STEPS = (1.0, 0.75, 0.5)
-KH = np.array(K640, np.float32).copy()
-KH[0] *= 0.5
-KH[1] *= 0.5
 WORK = dict(ref=dict(sigma=0.1, steps=None, its=8), conv=dict(sigma=0.5, steps=STEPS, its=6))
-MIN_UPDATE = 2e-5
 
 
 def _oracle(work):
@@ -48,6 +40,7 @@ def _oracle_back():
 
 
 def _cfg(work="ref", **kw):
+    """(not term_batch.cfg: the "ref" workload keeps the reference's step constants, and max_iterations follows the workload)"""
     kw.setdefault("max_iterations", WORK[work]["its"])
     kw.setdefault("gn_pixels_per_thread", 4)
     if WORK[work]["steps"]:
@@ -55,118 +48,20 @@ def _cfg(work="ref", **kw):
     return dvo.default_config(crop_enable=0, min_residual=0.0, min_update=MIN_UPDATE, **kw)
 
 
-@functools.lru_cache(maxsize=None)
-def _frames(size=SIZE, sigma=0.1):
-    g, d, s, _ = synth.sequence(6, width=size[0], height_px=size[1], K=KH, seed=42, sigma_value=sigma)
-    return g.numpy(), d.numpy(), s.numpy()
-
-
-def _dev(a):
-    import torch
-    t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
-    torch.cuda.synchronize()
-    return t
-
-
 def _wide_idx(B, pushes=3):
-    """neighbouring sequences and sequences 8 apart (the same slot of the next solve workgroup) are on different frames at every push"""
-    idx = [[(k + b) % 6 for b in range(B)] for k in range(pushes)]
-    for r in idx:
-        assert all(r[b] != r[b + 1] for b in range(B - 1)) and all(r[b] != r[b + 8] for b in range(B - 8))
-    return idx
+    """(without term_batch's table for up to five sequences)"""
+    return tb.wide_idx(B, pushes, table=False)
 
 
-def _run(cfg, B, idx, work="ref", lm=None, clear=False, acts=None, kf=False, feed="device", cams=None, size=SIZE, quality=True, guess=None):
-    """idx[k][b]: frame of sequence b at push k.  lm: set_step_control arguments ({} = the defaults; None: never set; clear: set, then
-    turned off before the first push).  Returns per push dict(status, xi, T, logs, q, rec, lmlogs, plan)."""
-    g, d, s = _frames(size, WORK[work]["sigma"])
-    bt = dvo.Batch(B, KH, size[0], size[1], LEVELS, CULLS, cfg=cfg)
-    if kf:
-        bt.set_keyframe_tracking(True)
-    if quality:
-        bt.set_track_quality(True)
-    if cams is not None:
-        bt.set_intrinsics(cams)
-    if guess is not None:
-        bt.set_pose_guess_mode(dvo.GUESS_GIVEN)
-    on = lm is not None and not clear
-    if lm is not None:
+def _term(idx, work="ref", lm=None, clear=False, size=SIZE, guess=None):
+    """run() keywords of a batch on the frames of a workload.  lm: set_step_control arguments ({} = the defaults; None: never set;
+    clear: set, then turned off before the first push); guess[k]: the given start poses of push k, read back as `start`"""
+    def setup(bt, keep):
         bt.set_step_control(**lm)
         if clear:
             bt.set_step_control(dvo.LM_OFF)
-    plan = [bt.level_plan(l) for l in range(LEVELS)]
-    keep, outs = [], []
-    for k in range(len(idx)):
-        sel = list(idx[k])
-        gi, di, si = g[sel], d[sel], s[sel]
-        if acts is not None:
-            bt.set_actions(np.asarray(acts[k], np.uint8))
-        if guess is not None:
-            bt.set_pose_guess(np.asarray(guess[k], np.float32))
-        if feed == "host":
-            bt.push_host(gi, di, si)
-        elif feed in ("raw", "raw_host"):
-            g8 = np.clip(np.rint(gi * 255), 0, 255).astype(np.uint8); d16 = np.clip(np.rint(di * 5000), 0, 65535).astype(np.uint16)
-            if feed == "raw_host":
-                bt.push_raw_host(g8, d16)
-            else:
-                import torch
-                tg = _dev(g8); td = torch.from_numpy(d16.view(np.int16)).cuda()
-                torch.cuda.synchronize()
-                keep.append((tg, td))
-                bt.push_raw_device(tg.data_ptr(), 1, td.data_ptr())
-        else:
-            t = [_dev(x) for x in (gi, di, si)]
-            keep.append(t)
-            bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
-        o = dict(status=bt.last_status(), q=bt.last_track_quality() if quality else None, plan=plan)
-        if guess is not None:
-            o["start"] = bt.last_start_poses()
-        if on:
-            o["rec"] = bt.last_step_control()
-            o["lmlogs"] = [bt.last_step_control_log(b) for b in range(B)]
-        if k > 0 or acts is not None or kf:
-            xi, T = bt.last_poses()
-            o.update(xi=xi.copy(), T=T.copy(), logs=[bt.last_track_log(b) for b in range(B)])
-            if kf:
-                o["world"] = bt.world_poses()
-        outs.append(o)
-    bt.close()
-    return outs
-
-
-def _logbits(lg):
-    return (tuple(int(n) for n in lg["n_iter"][:LEVELS]),) + tuple(
-        tuple(np.asarray(x, np.float32).tobytes() for x in lg[f][:LEVELS]) for f in ("residual", "upd_norm", "xi_after", "xi_update")) + (
-        tuple(np.asarray(x, np.int32).tobytes() for x in lg["n_valid"][:LEVELS]),)
-
-
-def _lmbits(lg):
-    return (tuple(int(n) for n in lg["n_iter"]), lg["lambda_"].tobytes(), lg["decision"].tobytes())
-
-
-def _same(a, b):
-    assert len(a) == len(b)
-    for k, (x, y) in enumerate(zip(a, b)):
-        np.testing.assert_array_equal(x["status"], y["status"], err_msg="push %d" % k)
-        if "xi" in x:
-            np.testing.assert_array_equal(x["xi"], y["xi"], err_msg="push %d" % k)
-            np.testing.assert_array_equal(x["T"], y["T"], err_msg="push %d" % k)
-            assert [_logbits(l) for l in x["logs"]] == [_logbits(l) for l in y["logs"]], "push %d logs" % k
-        if "world" in x:
-            for u, v in zip(x["world"], y["world"]):
-                np.testing.assert_array_equal(u, v, err_msg="push %d world" % k)
-        if x["q"] is not None:
-            assert x["q"].tobytes() == y["q"].tobytes(), "push %d quality records" % k
-        assert ("rec" in x) == ("rec" in y)
-        if "rec" in x:
-            assert x["rec"].tobytes() == y["rec"].tobytes(), "push %d step-control records" % k
-            assert [_lmbits(l) for l in x["lmlogs"]] == [_lmbits(l) for l in y["lmlogs"]], "push %d step-control logs" % k
-
-
-def _oframe(i, work, K=KH, size=SIZE):
-    g, d, s = _frames(size, WORK[work]["sigma"])
-    return orc.OFrame(g[i], d[i], s[i], K, LEVELS, CULLS)
+    reads = (("start",) if guess is not None else ()) + (("step",) if lm is not None and not clear else ())
+    return dict(setup=setup if lm is not None else None, reads=reads, maps=tb.frame_maps(idx, size, WORK[work]["sigma"]), size=size, guess=guess)
 
 
 def _empty(o, b):
@@ -175,6 +70,7 @@ def _empty(o, b):
     assert (r["n_first"], r["n_accepted"], r["n_rejected"], r["lambda"], r["residual"]) == (0, 0, 0, 0.0, 0.0), (b, r)
     lg = o["lmlogs"][b]
     assert not lg["n_iter"].any() and not lg["lambda_"].any() and not lg["decision"].any() and lg["levels"] == LEVELS
+    return True
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1: the serial tail
@@ -318,47 +214,36 @@ def _replay(outs, cfg, B, work, lm=None, cams=None, size=SIZE, kf=False, guess=N
     idx = _wide_idx(B, len(outs)) if idx is None else idx
     P = lr.params(**(lm or {}))
     depth = gn_sums.depth_for_cfg(cfg)
-    ref_of = [None] * B
     tot = dict(n=0, rejects=0, early_stops=0, iterations=0, accepts=0)
-    for k, o in enumerate(outs):
-        for b in range(B):
-            st = o["status"][b]
-            where = "push %d seq %d of %d" % (k, b, B)
-            if st == TRACKED and (seqs is None or b in seqs):
-                K = cams[b] if cams is not None else KH
-                obj, ref = _oframe(idx[k][b], work, K, size), _oframe(ref_of[b], work, K, size)
-                lg, ll, rec = o["logs"][b], o["lmlogs"][b], o["rec"][b]
-                r = lr.replay_call(lg, ll, lr.oracle_sums(obj, ref), LEVELS, P, cfg.max_iterations, cfg.min_update, cfg.min_residual,
-                                   cfg.fixed_iterations, xi0=o.get("start", [None] * B)[b], tag=where)
-                # the returned pose is the last accepted one; the record counts the decisions and keeps lambda and the accepted residual
-                assert o["xi"][b].tobytes() == r["xi"].tobytes(), where
-                assert (rec["n_first"], rec["n_accepted"], rec["n_rejected"]) == (LEVELS, r["accepts"], r["rejects"]), (where, rec)
-                assert F32(rec["lambda"]).tobytes() == F32(r["lam"]).tobytes() and F32(rec["residual"]).tobytes() == F32(r["residual"]).tobytes(), where
-                if o["q"] is not None:   # the quality record: the accepted evaluation's sums of the finest level
-                    l, it, xa, _ = r["accepted"][TOP]
-                    q = o["q"][b]
-                    assert l == TOP and q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
-                    assert F32(q["residual"]).tobytes() == F32(lg["residual"][TOP][it]).tobytes(), where
-                    t = orc.optimize_terms(obj.gray(TOP), ref.gray(TOP), ref.depth(TOP), ref.sigma(TOP), ref.K(TOP), xa, TOP, crop=False)
-                    gn_sums.assert_gn_sums(q, t, gn_sums.at_level(depth, TOP), "step control " + where)
-                for f in ("rejects", "early_stops", "iterations", "accepts"):
-                    tot[f] += r[f]
-                tot["n"] += 1
-            elif st != TRACKED:
-                _empty(o, b)
-            if kf:
-                if st == STARTED or (st == TRACKED and o["world"][2][b]):
-                    ref_of[b] = idx[k][b]
-            elif st in (TRACKED, STARTED):
-                ref_of[b] = idx[k][b]
-    want = (len(outs) - 1) * (B if seqs is None else len(seqs)) if min_tracked is None else min_tracked
-    assert tot["n"] >= want and tot["iterations"] > 3 * tot["n"], tot
+
+    def check(k, b, kr, o, K):
+        where = "push %d seq %d of %d" % (k, b, B)
+        sigma = WORK[work]["sigma"]
+        obj, ref = tb.oframe(idx[k][b], K, size, sigma), tb.oframe(idx[kr][b], K, size, sigma)
+        lg, ll, rec = o["logs"][b], o["lmlogs"][b], o["rec"][b]
+        r = lr.replay_call(lg, ll, lr.oracle_sums(obj, ref), LEVELS, P, cfg.max_iterations, cfg.min_update, cfg.min_residual,
+                           cfg.fixed_iterations, xi0=o.get("start", [None] * B)[b], tag=where)
+        # the returned pose is the last accepted one; the record counts the decisions and keeps lambda and the accepted residual
+        assert o["xi"][b].tobytes() == r["xi"].tobytes(), where
+        assert (rec["n_first"], rec["n_accepted"], rec["n_rejected"]) == (LEVELS, r["accepts"], r["rejects"]), (where, rec)
+        assert F32(rec["lambda"]).tobytes() == F32(r["lam"]).tobytes() and F32(rec["residual"]).tobytes() == F32(r["residual"]).tobytes(), where
+        if o["q"] is not None:   # the quality record: the accepted evaluation's sums of the finest level
+            l, it, xa, _ = r["accepted"][TOP]
+            q = o["q"][b]
+            assert l == TOP and q["status"] == TRACKED and q["n_valid"] == int(lg["n_valid"][TOP][it]), where
+            assert F32(q["residual"]).tobytes() == F32(lg["residual"][TOP][it]).tobytes(), where
+            t = orc.optimize_terms(obj.gray(TOP), ref.gray(TOP), ref.depth(TOP), ref.sigma(TOP), ref.K(TOP), xa, TOP, crop=False)
+            gn_sums.assert_gn_sums(q, t, gn_sums.at_level(depth, TOP), "step control " + where)
+        for f in ("rejects", "early_stops", "iterations", "accepts"):
+            tot[f] += r[f]
+        return r["iterations"]
+    tot["n"], _ = tb.walk(outs, B, check, _empty, kf=kf, cams=cams, seqs=seqs, min_tracked=min_tracked)
     return tot
 
 
 @functools.lru_cache(maxsize=None)
 def _base(work, B):
-    return _run(_cfg(work), B, _wide_idx(B), work, lm={})
+    return tb.run(_cfg(work), B, _wide_idx(B), **_term(_wide_idx(B), work, lm={}))
 
 
 @pytest.mark.parametrize("B", [5, 17])
@@ -375,32 +260,32 @@ def test_whole_pushes_replay(work, B):
 
 
 def test_whole_pushes_replay_ragged_size():
-    outs = _run(_cfg("ref"), 3, _wide_idx(3), "ref", lm={}, size=(328, 248))
+    outs = tb.run(_cfg("ref"), 3, _wide_idx(3), **_term(_wide_idx(3), "ref", lm={}, size=(328, 248)))
     _replay(outs, _cfg("ref"), 3, "ref", size=(328, 248))
 
 
 @pytest.mark.parametrize("work", ["ref", "conv"])
 def test_feeds_are_bit_identical(work):
-    _same(_base(work, 5), _run(_cfg(work), 5, _wide_idx(5), work, lm={}, feed="host"))
-    a = _run(_cfg(work), 5, _wide_idx(5), work, lm={}, feed="raw")
-    _same(a, _run(_cfg(work), 5, _wide_idx(5), work, lm={}, feed="raw_host"))
+    idx = _wide_idx(5)
+    tb.same(_base(work, 5), tb.run(_cfg(work), 5, idx, feed="host", **_term(idx, work, lm={})))
+    a = tb.run(_cfg(work), 5, idx, feed="raw", **_term(idx, work, lm={}))
+    tb.same(a, tb.run(_cfg(work), 5, idx, feed="raw_host", **_term(idx, work, lm={})))
     assert all((o["rec"]["n_first"] == LEVELS).all() for o in a[1:])
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3: configurations
 @pytest.fixture(scope="module")
 def base19():
-    return _run(_cfg("ref"), 19, _wide_idx(19), "ref", lm={})
+    return tb.run(_cfg("ref"), 19, _wide_idx(19), **_term(_wide_idx(19), "ref", lm={}))
 
 
 @pytest.mark.parametrize("variant", ["adaptive_off", "fused_tiles", "single_launch", "two_streams"])
 def test_configurations_give_the_same_records(variant, base19):
     """19 sequences: two sub-batches need more than 16, and 19 is no multiple of 8; the tables are offset per sub-batch"""
-    kw = dict(adaptive_off=dict(track_adaptive=-1), fused_tiles=dict(track_fused_tiles=8), single_launch=dict(track_single_launch=1),
-              two_streams=dict(track_streams=2))[variant]
-    other = _run(_cfg("ref", **kw), 19, _wide_idx(19), "ref", lm={})
+    kw = tb.SCHEDULE_VARIANTS[variant]
+    other = tb.run(_cfg("ref", **kw), 19, _wide_idx(19), **_term(_wide_idx(19), "ref", lm={}))
     assert all(p["schedule"] == dvo.PLAN_PAIRS for p in other[0]["plan"])
-    _same(base19, other)
+    tb.same(base19, other)
     assert sum(int(o["rec"]["n_rejected"].sum()) for o in base19[1:]) >= 1
 
 
@@ -416,7 +301,7 @@ SHAPES = [(1, 1), (2, 1), (2, 2), (4, 1), (4, 2), (4, 4), (8, 1), (8, 2), (8, 4)
 def test_every_tile_shape(ppt, group):
     """each (PPT, G) pair of the plain k_track_gn under step control on a batch of two, held to the contract at its own poses"""
     cfg = _cfg("ref", gn_gather_group=group, gn_pixels_per_thread=ppt)
-    outs = _run(cfg, 2, _wide_idx(2), "ref", lm={})
+    outs = tb.run(cfg, 2, _wide_idx(2), **_term(_wide_idx(2), "ref", lm={}))
     assert all((p["ppt"], p["group"], p["schedule"]) == (ppt, group, dvo.PLAN_PAIRS) for p in outs[0]["plan"]), outs[0]["plan"]
     _replay(outs, cfg, 2, "ref")
 
@@ -424,21 +309,19 @@ def test_every_tile_shape(ppt, group):
 def test_equal_cameras_are_the_plain_path():
     """the _cam kernels with a table of equal K's: bit for bit the batch without a table"""
     cams = np.stack([KH] * 5).astype(np.float32)
-    _same(_base("ref", 5), _run(_cfg("ref"), 5, _wide_idx(5), "ref", lm={}, cams=cams))
+    tb.same(_base("ref", 5), tb.run(_cfg("ref"), 5, _wide_idx(5), cams=cams, **_term(_wide_idx(5), "ref", lm={})))
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5: batch features
 def test_per_sequence_intrinsics():
-    cams = np.stack([KH] * 5).astype(np.float32)
-    for b in range(5):
-        cams[b, 0, 0] *= 1.0 + 0.01 * b; cams[b, 1, 1] *= 1.0 - 0.005 * b
-    outs = _run(_cfg("ref"), 5, _wide_idx(5), "ref", lm={}, cams=cams)
+    cams = tb.sequence_cams(5)
+    outs = tb.run(_cfg("ref"), 5, _wide_idx(5), cams=cams, **_term(_wide_idx(5), "ref", lm={}))
     _replay(outs, _cfg("ref"), 5, "ref", cams=cams)
 
 
 def test_keyframes():
     cfg = _cfg("conv", keyframe_max_frames=2)
-    outs = _run(cfg, 5, _wide_idx(5), "conv", lm={}, kf=True)
+    outs = tb.run(cfg, 5, _wide_idx(5), kf=True, **_term(_wide_idx(5), "conv", lm={}))
     _replay(outs, cfg, 5, "conv", kf=True)
 
 
@@ -446,27 +329,20 @@ def test_pose_guess():
     B = 5
     rng = np.random.default_rng(5)
     guess = [(rng.normal(size=(B, 6)) * 2e-3).astype(np.float32) for _ in range(3)]
-    outs = _run(_cfg("conv"), B, _wide_idx(B), "conv", lm={}, guess=guess)
+    outs = tb.run(_cfg("conv"), B, _wide_idx(B), **_term(_wide_idx(B), "conv", lm={}, guess=guess))
     for k in (1, 2):
         assert outs[k]["start"].tobytes() == guess[k].tobytes()
     _replay(outs, _cfg("conv"), B, "conv", guess=guess)
 
 
-def _acts(B, n, seed):
-    rng = np.random.RandomState(seed)
-    a = rng.choice([SKIP, TRACK, RESTART], size=(n, B), p=(0.2, 0.65, 0.15)).astype(np.uint8)
-    a[0] = TRACK
-    return a
-
-
 def test_actions_and_camera_change_leave_zero_records():
-    acts = _acts(5, 3, 9)
+    acts = tb.acts(5, 3, 9)
     assert (acts[1:] == SKIP).any() and (acts[1:] == RESTART).any()
-    outs = _run(_cfg("ref"), 5, _wide_idx(5), "ref", lm={}, acts=acts)
+    outs = tb.run(_cfg("ref"), 5, _wide_idx(5), acts=acts, **_term(_wide_idx(5), "ref", lm={}))
     tot = _replay(outs, _cfg("ref"), 5, "ref", min_tracked=3)
     assert sum(int((o["status"] != TRACKED).sum()) for o in outs[1:]) >= 2 and tot["n"] >= 3
     # a camera change restarts the sequence: a zero record and an empty log; a bad action likewise
-    g, d, s = _frames()
+    g, d, s = tb.frames(SIZE, 0.1)
     bt = dvo.Batch(3, KH, SIZE[0], SIZE[1], LEVELS, CULLS, cfg=_cfg("ref"))
     bt.set_step_control()
     for k in range(3):
@@ -475,7 +351,7 @@ def test_actions_and_camera_change_leave_zero_records():
             cams[1, 0, 0] *= 1.02
             bt.set_intrinsics(cams)
             bt.set_actions(np.array([TRACK, TRACK, 7], np.uint8))
-        t = [_dev(x[[k, k + 1, k + 2]]) for x in (g, d, s)]
+        t = [tb.dev(x[[k, k + 1, k + 2]]) for x in (g, d, s)]
         bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         o = dict(rec=bt.last_step_control(), lmlogs=[bt.last_step_control_log(b) for b in range(3)], status=bt.last_status())
         for b in range(3):
@@ -489,9 +365,10 @@ def test_actions_and_camera_change_leave_zero_records():
 
 @pytest.mark.parametrize("mode", ["plain", "actions", "keyframes"])
 def test_set_then_cleared_is_never_set(mode):
-    kw = dict(acts=_acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
+    kw = dict(acts=tb.acts(5, 3, 3) if mode == "actions" else None, kf=mode == "keyframes")
     cfg = _cfg("conv", keyframe_max_frames=2) if mode == "keyframes" else _cfg("conv")
-    _same(_run(cfg, 5, _wide_idx(5), "conv", **kw), _run(cfg, 5, _wide_idx(5), "conv", lm={}, clear=True, **kw))
+    idx = _wide_idx(5)
+    tb.same(tb.run(cfg, 5, idx, **_term(idx, "conv"), **kw), tb.run(cfg, 5, idx, **_term(idx, "conv", lm={}, clear=True), **kw))
 
 
 class StepControlReplay(lockstep.Replay):
@@ -526,7 +403,7 @@ def test_mono_batch_follows_the_contract():
     n = 0
     for k in range(len(orders[0])):
         fr = np.stack([g[orders[q][k]] for q in range(B)])
-        t = _dev(fr)
+        t = tb.dev(fr)
         mb.odometrize_device(t.data_ptr())
         rec = mb.last_step_control()
         for q, gf in enumerate(lockstep.batch_frames(mb, k == 0)):
@@ -579,15 +456,15 @@ def test_errors_are_refused():
             on()
         off()                                       # (turning the other term off is allowed while step control is on)
         bt.set_step_control(None)
-    g, d, s = _frames(SIZE, 0.5)
-    t = [_dev(x[:2]) for x in (g, d, s)]
+    g, d, s = tb.frames(SIZE, 0.5)
+    t = [tb.dev(x[:2]) for x in (g, d, s)]
     bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
     with pytest.raises(dvo.DvoError):
         bt.last_step_control()                      # the push ran without step control
     bt.set_step_control()
     with pytest.raises(dvo.DvoError):
         bt.last_step_control()                      # enabled from the next push on
-    t2 = [_dev(x[1:3]) for x in (g, d, s)]
+    t2 = [tb.dev(x[1:3]) for x in (g, d, s)]
     bt.push_device(t2[0].data_ptr(), t2[1].data_ptr(), t2[2].data_ptr())
     assert (bt.last_step_control()["n_first"] == LEVELS).all()
     lg = dvo.LmLog()
@@ -653,7 +530,7 @@ def test_step_control_wins_where_the_plain_iteration_diverges():
         if name == "lm":
             bt.set_step_control()
         for frames in (refs, obj):
-            t = [_dev(np.stack([f[i] for f in frames])) for i in range(3)]
+            t = [tb.dev(np.stack([f[i] for f in frames])) for i in range(3)]
             bt.push_device(t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr())
         xi, _ = bt.last_poses()
         got[name] = xi.copy()

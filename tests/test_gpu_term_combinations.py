@@ -8,14 +8,12 @@ import ctypes as C
 import pytest
 
 import dvo_amd as dvo
-from test_gpu_step_control import CULLS, KH, LEVELS, SIZE
+from term_batch import CULLS, KH, LEVELS, SIZE, STATES
 from util import K640
 
 pytestmark = pytest.mark.gpu
 
-# The setters that make up each reachable state, from "everything off"
-STATES = dict(N=[], R=["robust_weights"], M=["robust_median"], A=["affine_brightness"], RA=["robust_weights", "affine_brightness"],
-              G=["geometric"], GA=["geometric_affine"], L=["step_control"])
+# (STATES, tests/term_batch.py: the setters that make up each reachable state, from "everything off")
 # An offender: the word the message must contain and the setter it must name
 ROBUST = ("robust", "dvo_batch_set_robust_weights")
 MEDIAN = ("median", "dvo_batch_set_robust_median")
