@@ -346,10 +346,9 @@ int dvo_debug_batch_level_plan(dvo_batch* b, int level, int* ppt, int* group, in
     const LevelPlan& L = T.lv[level];
     if (ppt) *ppt = L.ppt;
     if (group) *group = L.group;
-    if (tiles_2d) *tiles_2d = (T.tile_margin == 0 && L.tiling.t2d) ? 1 : 0;
+    if (tiles_2d) *tiles_2d = L.tiling.t2d ? 1 : 0;   // (the LDS-patch schedule leaves the default tiling: not 2-D)
     if (tiles) *tiles = L.nblk;
-    if (schedule)
-        *schedule = T.tile_margin > 0 ? DVO_PLAN_LDS_PATCH : (L.fused ? DVO_PLAN_LEVEL : (L.single_launch ? DVO_PLAN_ITERATION : DVO_PLAN_PAIRS));
+    if (schedule) *schedule = L.schedule;
     return DVO_OK;
 }
 
@@ -1306,7 +1305,7 @@ static int gn_step(const char* who, int dev, const dvo_config* cfg, const float*
     const Tracker::GivenOnce once{t.rob.s2, t.aff.a, t.aff.b};
     DVO_TRY(trk.begin_terms(c.s, &once));
     trk.launch_gn_term(ga, level, 1, c.s, 0, zr.as<float>());
-    SolveArgs sa = trk.solve_args(level, 0, 1, trk.tile_margin == 0 ? SolveRows::Live : SolveRows::All);
+    SolveArgs sa = trk.solve_args(level, 0, 1, trk.pair_rows(level, SolveRows::Live));
     sa.log = nullptr;   // (one evaluation: the sums go to `res`, no iteration record)
     sa.result = res.as<dvo_gn_result>();
     Tracker::SolveTerm st{};

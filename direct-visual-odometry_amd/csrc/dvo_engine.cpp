@@ -495,16 +495,17 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     size_t max_part = 0;
     // gn_use_lds_patch: -1 = auto, 0 = global gathers, N > 0 = LDS patch with margin N.  Auto is the global-gather
     // kernel: measured on MI355X (profiles/r01_gn_variants.md) the LDS-staged variant is 10-15 % slower.
-    tile_margin = cfg.gn_use_lds_patch < 0 ? 0 : cfg.gn_use_lds_patch;
-    if (tile_margin > 24) tile_margin = 24;
-    margin_plain = tile_margin;
+    // The configured margin decides n_sub, adaptive, DVO_PLAN_ITERATION and persist_ok below for the handle's whole life, whichever
+    // plan is in force later; a level's own margin (LevelPlan::margin) is what its launches use.
+    const int margin = cfg.gn_use_lds_patch < 0 ? 0 : (cfg.gn_use_lds_patch > 24 ? 24 : cfg.gn_use_lds_patch);
     // robust: the weighted plan (lv_rw) -- the global-gather kernel, no fused level, the batch tiling
     auto plan_level = [&](int l, bool robust) -> LevelPlan {
         LevelPlan L{};
         int p = cfg.gn_pixels_per_thread;
         const bool auto_p = (p != 1 && p != 2 && p != 4 && p != 8);
         if (auto_p) p = 4;  // auto: biggest tile that still gives >= 4 workgroups per CU
-        if (tile_margin > 0 && !robust) {
+        if (margin > 0 && !robust) {
+            L.schedule = DVO_PLAN_LDS_PATCH; L.margin = margin;
             gn_tile_geometry(g.w[l], g.h[l], p, L.tiles_x, L.tiles_y);
             while (auto_p && p > 1 && (size_t)n_seq * L.tiles_x * L.tiles_y < 1024) {
                 p >>= 1;
@@ -520,15 +521,16 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
                                                             : (cfg.track_fused_tiles > DVO_FUSED_MAX_TILES ? DVO_FUSED_MAX_TILES : cfg.track_fused_tiles);
             const int crop_l = level_params(l).crop;
             const GnTiling t4 = gn_tiling(g.w[l], g.h[l], 4, crop_l);
-            L.fused = fuse_max > 0 && !t4.t2d && t4.count <= fuse_max;  // (k_track_level: raster tiles)
-            if (L.fused) p = 4;
+            const bool fused = fuse_max > 0 && !t4.t2d && t4.count <= fuse_max;  // (k_track_level: raster tiles)
+            L.schedule = fused ? DVO_PLAN_LEVEL : DVO_PLAN_PAIRS;
+            if (fused) p = 4;
             // (one sequence on the one-launch-per-call schedule keeps 4 pixels per thread: k_track_persist's workgroups wait for each
             //  other, and 75 of them hand over faster than 300 -- 406 against 451 us per 640x480 frame, profiles/r03_single_ab.txt)
             //  A mono handle's levels (at most 160 x 120) show no such difference -- 132-140 us per frame at 1, 2 and 4 pixels per
             //  thread -- so it keeps the tile size every other schedule picks for one sequence (persist_ppt < 0): the same bits.)
             const bool single_p4 = !robust && prefer_persist && n_seq == 1 && cfg.track_single_launch == 0 && !cfg.profile && persist_ppt >= 0;
             if (single_p4 && auto_p && persist_ppt > 0) p = persist_ppt;
-            while (!L.fused && auto_p && !single_p4 && p > 1 && (size_t)n_seq * gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l) < 1024) p >>= 1;
+            while (!fused && auto_p && !single_p4 && p > 1 && (size_t)n_seq * gn_blocks_per_seq(g.w[l], g.h[l], p, crop_l) < 1024) p >>= 1;
             L.tiling = gn_tiling(g.w[l], g.h[l], p, crop_l);   // the level's tiles are decided: every launch takes them from here
             L.nblk = L.tiling.count;
         }
@@ -553,7 +555,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     n_sub = cfg.track_streams;
     if (n_sub <= 0) n_sub = 1;
     if (n_sub > 8) n_sub = 8;
-    if (n_seq <= 8 || tile_margin > 0) n_sub = 1;
+    if (n_seq <= 8 || margin > 0) n_sub = 1;
     while (n_sub > 1 && n_seq / n_sub < 8) n_sub--;
     for (int k = 1; k < n_sub; k++) {
         hipStream_t st = nullptr;
@@ -567,7 +569,7 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     DVO_TRY(work.alloc(2 * sizeof(int) * (size_t)n_sub * (size_t)(n_seq + 4)));
     DVO_HIP(hipMemset(work.p, 0, work.bytes));
     // adaptive schedule (see dvo_engine.h): one launch chain only, global-gather kernel only, reference stop tests only
-    adaptive = cfg.track_adaptive >= 0 && n_sub == 1 && tile_margin == 0 && cfg.fixed_iterations <= 0;
+    adaptive = cfg.track_adaptive >= 0 && n_sub == 1 && margin == 0 && cfg.fixed_iterations <= 0;
     if (adaptive) {
         const size_t words = 2 * (size_t)DVO_MAX_LEVELS * DVO_MAX_ITERATIONS;
         // fine-grained (coherent) host memory: the device publishes a word with a system-scope release store and the host
@@ -581,25 +583,27 @@ int Tracker::init(const Geometry& geo, int n, const dvo_config& c)
     // 14-16 us per iteration against 17-18 us for the launch pair up to 52 workgroups, but 31 us against 18 us at 300
     for (int l = 0; l < g.levels; l++) {
         LevelPlan& L = lv[l];
-        L.single_launch = cfg.track_single_launch >= 0 && n_seq <= 8 && tile_margin == 0 && !L.fused && !cfg.profile && n_sub == 1 &&
-                          gn_fused_available(L.ppt, L.group) && L.tiling.live_count > 0 && (long long)n_seq * L.tiling.live_count <= 64;
+        if (cfg.track_single_launch >= 0 && n_seq <= 8 && margin == 0 && L.schedule == DVO_PLAN_PAIRS && !cfg.profile && n_sub == 1 &&
+            gn_fused_available(L.ppt, L.group) && L.tiling.live_count > 0 && (long long)n_seq * L.tiling.live_count <= 64)
+            L.schedule = DVO_PLAN_ITERATION;
     }
     for (int l = 0; l < DVO_MAX_LEVELS; l++) lv_plain[l] = lv[l];
-    // k_track_persist (one launch per track() call): one sequence, the global-gather kernel, one (ppt, group) pair on every level,
-    // every level within the wide reduction's row limit, no profiling; track_single_launch: < 0 = launch pairs only, 1 = one launch per
-    // iteration at most (k_track_gn_fused), 0 (default) = one launch per call where the result goes through enable_host_result()
-    persist_ok = prefer_persist && n_seq == 1 && tile_margin == 0 && !cfg.profile && cfg.track_single_launch == 0 && n_sub == 1 && track_persist_available(lv[0].ppt, lv[0].group);
-    int max_tiles = 0;
-    for (int l = 0; l < g.levels && persist_ok; l++) {
-        const GnTiling& tl = lv[l].tiling;
-        if (lv[l].ppt != lv[0].ppt || lv[l].group != lv[0].group || lv[l].fused || lv[l].nblk > 320 || tl.live_count <= 0) persist_ok = false;
-        if (tl.live_count > max_tiles) max_tiles = tl.live_count;
-    }
     // ~0.2 s of polling per wait: far beyond any iteration, short enough that a wedged launch ends.  DVO_PERSIST_SPIN_LIMIT (tests): a
     // limit of 0 makes every launch give up at once, so the fallback path runs; DVO_PERSIST_TIMELINE: in-kernel stamps (diagnostic).
     persist_spin_limit = 1 << 18;
     if (const char* e = getenv("DVO_PERSIST_SPIN_LIMIT")) persist_spin_limit = atoi(e);
-    persist_timeline = getenv("DVO_PERSIST_TIMELINE") != nullptr;
+    if (const char* e = getenv("DVO_PERSIST_TIMELINE")) { persist_timeline = true; persist_dbg_worker = atoi(e); }
+    // k_track_persist (one launch per track() call): one sequence, the global-gather kernel, one (ppt, group) pair on every level,
+    // every level within the wide reduction's row limit, no profiling; track_single_launch: < 0 = launch pairs only, 1 = one launch per
+    // iteration at most (k_track_gn_fused), 0 (default) = one launch per call where the result goes through enable_host_result().
+    // This is the handle's half of the decision; persist_call() adds the call's.
+    persist_ok = prefer_persist && n_seq == 1 && margin == 0 && !cfg.profile && cfg.track_single_launch == 0 && n_sub == 1 && track_persist_available(lv[0].ppt, lv[0].group);
+    int max_tiles = 0;
+    for (int l = 0; l < g.levels && persist_ok; l++) {
+        const GnTiling& tl = lv[l].tiling;
+        if (lv[l].ppt != lv[0].ppt || lv[l].group != lv[0].group || lv[l].schedule == DVO_PLAN_LEVEL || lv[l].nblk > 320 || tl.live_count <= 0) persist_ok = false;
+        if (tl.live_count > max_tiles) max_tiles = tl.live_count;
+    }
     if (persist_ok) {
         int cap = 0;
         if (track_persist_max_grid(lv[0].ppt, lv[0].group, &cap) != DVO_OK || cap < 1) persist_ok = false;
@@ -654,7 +658,7 @@ GnArgs Tracker::gn_args(const float* obj_gray, const float* ref_gray, const floa
     // the level's tiles (k_track_gn_tile: L.tiling is the default, whose fields are the ones GnArgs starts with)
     a.blk_first = L.tiling.live_first; a.blk_count = L.tiling.live_count;
     a.t_shift = L.tiling.shift; a.x_org = L.tiling.x_org; a.y_org = L.tiling.y_org;
-    a.tiles_x = L.tiling.t2d ? L.tiling.tiles_x : L.tiles_x; a.tiles_y = L.tiles_y; a.margin = tile_margin;
+    a.tiles_x = L.tiling.t2d ? L.tiling.tiles_x : L.tiles_x; a.tiles_y = L.tiles_y; a.margin = L.margin;
     return a;
 }
 
@@ -686,8 +690,9 @@ void Tracker::use_plan()
 {
     const bool opt_in_term = terms_on() != 0;
     for (int l = 0; l < DVO_MAX_LEVELS; l++) lv[l] = opt_in_term ? lv_rw[l] : lv_plain[l];
-    tile_margin = opt_in_term ? 0 : margin_plain;
 }
+
+SolveRows Tracker::pair_rows(int level, SolveRows live) const { return lv[level].schedule == DVO_PLAN_LDS_PATCH ? SolveRows::All : live; }
 
 unsigned Tracker::terms_on() const
 {
@@ -1105,11 +1110,12 @@ MedianSolve Tracker::median_solve_args(size_t q0, bool log, bool prime, int* ste
     return m;
 }
 
-// false from the kernel file's tables: a set of terms without a kernel pair (Tracker::refusal lets none through)
-static int term_launch_status(bool launched)
+// false from the kernel file's tables: a set of terms without a kernel pair (Tracker::refusal lets none through), or `what`: a level
+// planned as DVO_PLAN_ITERATION without a k_track_gn_fused instance (Tracker::init plans none)
+static int term_launch_status(bool launched, const char* what = "no kernel pair for the opt-in terms that are on")
 {
     if (launched) return DVO_OK;
-    set_error("internal error: no kernel pair for the opt-in terms that are on");
+    set_error(std::string("internal error: ") + what);
     return DVO_ERR_HIP;
 }
 
@@ -1119,7 +1125,7 @@ int Tracker::launch_gn_term(const GnArgs& a, int level, int count, hipStream_t s
     const size_t q0 = (size_t)(a.state - state.as<SeqState>());
     TileTerms t{};
     t.on = terms_on();
-    if (!t.on) { launch_gn(a, level, count, s, grid_seqs); return DVO_OK; }   // (the tile_margin path is the plain plan's)
+    if (!t.on) { launch_gn(a, level, count, s, grid_seqs); return DVO_OK; }   // (the LDS-patch schedule is the plain plan's)
     if (rob.on) t.rob.table = rob.table.as<RobustEntry>() + q0;
     if (rob.median()) t.med.hist = rob.hist.as<unsigned>() + q0 * DVO_MEDIAN_BINS;
     if (aff.on) t.aff = affine_gn_args(q0, prime);
@@ -1144,8 +1150,8 @@ int Tracker::launch_solve_term(const SolveArgs& sa, int count, hipStream_t s, co
 void Tracker::launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs) const
 {
     const LevelPlan& L = lv[level];
-    if (tile_margin > 0) launch_track_gn_tile(a, count, L.ppt, s);
-    else launch_track_gn(a, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);
+    if (L.schedule == DVO_PLAN_LDS_PATCH) launch_track_gn_tile(a, count, L.ppt, s);
+    else launch_track_gn(a, count, L.ppt, L.group, L.tiling.t2d != 0, s, grid_seqs);   // (the probe and the one-evaluation ops: any level)
 }
 
 GnArgs Tracker::gn_view(const GnArgs& all, int level, int q0, const TrackPlan* plan, const Intr* seq_k) const
@@ -1181,9 +1187,8 @@ int Tracker::next_result_tag()
     return result_tag;
 }
 
-int Tracker::track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s, bool* launched)
+int Tracker::track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s)
 {
-    *launched = false;
     PersistArgs pa{};
     pa.levels = g.levels;
     for (int l = 0; l < g.levels; l++) pa.lv[l] = persist_level(gn_args(obj, ref, l, nullptr, 0), lv[l].tiling);
@@ -1199,11 +1204,10 @@ int Tracker::track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t
         if (!persist_dbg.p) { DVO_TRY(persist_dbg.alloc(2 * 64 * 8 * sizeof(long long))); }
         DVO_HIP(hipMemsetAsync(persist_dbg.p, 0, persist_dbg.bytes, s));
         pa.dbg = persist_dbg.as<long long>();
-        pa.dbg_worker = atoi(getenv("DVO_PERSIST_TIMELINE"));
+        pa.dbg_worker = persist_dbg_worker;
     }
     if (!launch_track_persist(pa, lv[0].ppt, lv[0].group, persist_grid, s)) return DVO_OK;
     persist_used = true;
-    *launched = true;
     DVO_HIP(hipGetLastError());
     return DVO_OK;
 }
@@ -1223,158 +1227,209 @@ static int wait_progress(const volatile int* word, hipStream_t s)
     return DVO_OK;
 }
 
-int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan)
+// One track() call's state, shared by the pieces of Tracker::track
+struct TrackCall {
+    hipStream_t s; const TrackPlan* plan;     // the caller's stream (sub-batch 0's) and plan
+    const Intr* seq_k;                        // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
+    int subs, n_levels, max_it;               // sub-batches (on s and sub_streams[0 .. subs - 2]), levels and iterations per level this call queues
+    bool poll, top_waited;                    // the <= 8-sequence read-back paces this call; no stream has to wait for top_ready any more
+    volatile int* prog_h; int* prog_d;        // adaptive: this call's progress words, host and device view
+    int* rep_set;                             // k_track_gn_fused: this call's report words
+    Tracker::SolveTerm iteration;             // every iteration's solve
+};
+
+static const char* const kLevelName[DVO_MAX_LEVELS] = {"track level 0", "track level 1", "track level 2", "track level 3", "track level 4",
+                                                       "track level 5", "track level 6", "track level 7"};
+
+// obj's top level: the split build's side stream writes it (every launch form reads it).  The first `streams` of the call wait, once.
+int Tracker::wait_top(TrackCall& c, int streams)
 {
-    last_obj = &obj; last_ref = &ref;
-    persist_used = false;
-    // per-sequence intrinsics: the plan's table, or without a plan the per-camera mono batch's (nullptr: Geometry::k)
-    const Intr* seq_k = plan ? plan->seq_k : cam_k;
-    bool top_waited = top_ready == nullptr;
-    if (persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed) {   // the whole call in one launch (k_track_persist)
-        if (!top_waited) { DVO_HIP(hipStreamWaitEvent(s, top_ready, 0)); top_waited = true; }
-        bool launched = false;
-        DVO_TRY(track_persist(obj, ref, s, &launched));
-        if (launched) return DVO_OK;
-    }
-    if (!plan) launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
+    if (c.top_waited) return DVO_OK;
+    for (int k = 0; k < streams; k++) DVO_HIP(hipStreamWaitEvent(k == 0 ? c.s : sub_streams[k - 1], top_ready, 0));
+    c.top_waited = true;
+    return DVO_OK;
+}
+
+int Tracker::track_prologue(TrackCall& c)
+{
+    hipStream_t s = c.s;
+    if (!c.plan) launch_track_begin(state.as<SeqState>(), log.as<dvo_track_log>(), n_seq, g.levels, s);
     if (seed) {   // the start pose of every TRACK sequence (dvo_batch_set_pose_guess_mode), before the fork
         if (seed_mono) launch_mono_seed(*seed, s);
         else launch_seed_pose(*seed, s);
     }
     DVO_TRY(begin_terms(s));
-    SolveTerm iteration{};   // every iteration's solve
-    iteration.adaptive_scale = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
-    const int max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
+    c.iteration.adaptive_scale = rob.on && rob.mode == DVO_ROBUST_SCALE_ADAPTIVE;
+    c.max_it = cfg.fixed_iterations > 0 ? cfg.fixed_iterations : cfg.max_iterations;
     // Small batches: every few iterations ask the device whether anything is still active, so a converged
     // level does not pay for its remaining (empty) launches.  Big batches run the fixed schedule sync-free.
-    const bool poll = (cfg.fixed_iterations <= 0) && n_seq <= 8 && !adaptive;
-    if (poll && !h_state) DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_state), sizeof(SeqState) * (size_t)n_seq, hipHostMallocDefault));
-    SeqState* host_state = h_state;  // pinned: the read-back is one async copy + one stream sync, no staging
+    c.poll = (cfg.fixed_iterations <= 0) && n_seq <= 8 && !adaptive;
+    // (pinned: the read-back is one async copy + one stream sync, no staging)
+    if (c.poll && !h_state) DVO_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_state), sizeof(SeqState) * (size_t)n_seq, hipHostMallocDefault));
     // fork: the sub-batch streams start once everything queued on `s` so far (pyramids, k_track_begin) is done
-    const int subs = poll ? 1 : n_sub;
-    if (subs > 1) {
+    c.subs = c.poll ? 1 : n_sub;
+    if (c.subs > 1) {
         DVO_HIP(hipEventRecord(ev_fork, s));
-        for (int k = 1; k < subs; k++) DVO_HIP(hipStreamWaitEvent(sub_streams[k - 1], ev_fork, 0));
+        for (int k = 1; k < c.subs; k++) DVO_HIP(hipStreamWaitEvent(sub_streams[k - 1], ev_fork, 0));
     }
     // adaptive: this call's progress words (the other set may still be written by the tail of the previous call)
-    volatile int* prog_h = nullptr;
-    int* prog_d = nullptr;
     if (adaptive) {
         progress_set ^= 1;
         const size_t off = (size_t)progress_set * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS;
-        prog_h = h_progress + off; prog_d = d_progress + off;
-        for (int i = 0; i < DVO_MAX_LEVELS * DVO_MAX_ITERATIONS; i++) prog_h[i] = 0;
+        c.prog_h = h_progress + off; c.prog_d = d_progress + off;
+        for (int i = 0; i < DVO_MAX_LEVELS * DVO_MAX_ITERATIONS; i++) c.prog_h[i] = 0;
     }
-    bool any_single = false;
-    for (int l = 0; l < g.levels; l++) any_single = any_single || lv[l].single_launch;
-    int* rep_set = freport.as<int>() + (size_t)(progress_set & 1) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS;
-    if (any_single) DVO_HIP(hipMemsetAsync(rep_set, 0, sizeof(int) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS, s));
-    static const char* const kLevelName[DVO_MAX_LEVELS] = {"track level 0", "track level 1", "track level 2", "track level 3", "track level 4",
-                                                           "track level 5", "track level 6", "track level 7"};
+    bool any_iteration = false;
+    for (int l = 0; l < g.levels; l++) any_iteration = any_iteration || lv[l].schedule == DVO_PLAN_ITERATION;
+    c.rep_set = freport.as<int>() + (size_t)(progress_set & 1) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS;
+    if (any_iteration) DVO_HIP(hipMemsetAsync(c.rep_set, 0, sizeof(int) * 2 * DVO_MAX_LEVELS * DVO_MAX_ITERATIONS, s));
     // adaptive schedule with a plan: k_plan's word says how many sequences track; with none, no level is launched at all
-    int n_levels = g.levels;
-    if (adaptive && plan && plan->ready) {
-        DVO_TRY(wait_progress(plan->ready, s));
-        if (*plan->ready - 1 == 0) n_levels = 0;
+    c.n_levels = g.levels;
+    if (adaptive && c.plan && c.plan->ready) {
+        DVO_TRY(wait_progress(c.plan->ready, s));
+        if (*c.plan->ready - 1 == 0) c.n_levels = 0;
     }
-    for (int level = 0; level < n_levels; level++) {  // tracker.cpp:32
+    return DVO_OK;
+}
+
+// Pacing ahead of iteration `it`, the adaptive schedule's: stay `ahead` iterations ahead of the GPU.  Wait until launch it-ahead of
+// this level has reported: the caller stops the level if it had no active sequence -- every later launch of the level would be
+// empty.  Skipping empty launches changes no result.  Two iterations ahead for every batch size: a batch iteration takes >= 20 us on
+// the GPU, the host needs ~10 us to see a progress word and queue the next pair, and every iteration queued beyond the last useful
+// one is an empty launch pair (~15 us): measured +1.6 % (mono, 1 iteration per level) / +0.7 % (sensor depth) against 4.
+// Returns that word, the sequences that entered iteration it - ahead plus one (the active set only shrinks within a level, so they bound
+// the list of `it`); 0: nothing to wait for; -1: the wait failed (the error is set).
+int Tracker::wait_ahead(const TrackCall& c, int level, int it)
+{
+    const int ahead = 2;
+    if (!adaptive || it < ahead) return 0;   // (k_track_level has no second iteration on the host)
+    volatile int* pw = c.prog_h + level * DVO_MAX_ITERATIONS + (it - ahead);
+    return wait_progress(pw, c.s) == DVO_OK ? *pw : -1;
+}
+
+// Pacing behind iteration `it`, a small batch's: ask the device whether anything is still active (*go = false: nothing is)
+int Tracker::poll_active(const TrackCall& c, int level, int it, bool* go)
+{
+    if (!c.poll || lv[level].schedule == DVO_PLAN_LEVEL || it + 1 >= c.max_it) return DVO_OK;
+    DVO_HIP(hipMemcpyAsync(h_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, c.s));
+    DVO_HIP(hipStreamSynchronize(c.s));
+    *go = false;
+    for (int q = 0; q < n_seq; q++) *go = *go || h_state[q].active != 0;
+    return DVO_OK;
+}
+
+// DVO_PLAN_LEVEL: the level iterates on the device, one k_track_level launch
+void Tracker::queue_level(const GnArgs& ga, int level, int q0, int nq, hipStream_t sk)
+{
+    SolveArgs fa = solve_args(level, q0, 1, SolveRows::All);
+    fa.partials = nullptr;
+    launch_track_level(ga, fa, nq, sk);
+}
+
+// DVO_PLAN_ITERATION: GN accumulation + solve of this iteration in one launch (k_track_gn_fused).  init gives a level this schedule
+// only where the launcher has an instance, so a refusal is an internal error.
+int Tracker::queue_iteration(const TrackCall& c, const GnArgs& ga, int level, int it, int q0, int nq, hipStream_t sk)
+{
+    const LevelPlan& L = lv[level];
+    const int word = level * DVO_MAX_ITERATIONS + it;
+    const SolveArgs fa = solve_args(level, q0, it == 0, SolveRows::Live);
+    return term_launch_status(launch_track_gn_fused(ga, fa, nq, L.ppt, L.group, L.tiling.t2d != 0, ticket.as<int>(), c.rep_set + 2 * word,
+                                                    adaptive ? c.prog_d + word : nullptr, sk),
+                              "no k_track_gn_fused instance for a level planned as DVO_PLAN_ITERATION");
+}
+
+// DVO_PLAN_PAIRS, DVO_PLAN_LDS_PATCH: one accumulation and one solve launch, through the opt-in terms that are on
+//   ga: the sub-batch's view of the level (by value: the lists are filled in here); ref_z: the reference's depth of the level
+int Tracker::queue_pair(const TrackCall& c, GnArgs ga, int level, int it, int k, int q0, int nq, hipStream_t sk, int active_ub, const float* ref_z)
+{
+    const bool lists = lv[level].schedule == DVO_PLAN_PAIRS;  // (k_track_gn_tile keeps the per-sequence active flag test)
+    const SolveRows rows = pair_rows(level, SolveRows::LivePair);
+    const int first = (it == 0) ? 1 : 0;
+    // iteration `it` evaluates the sequences k_gn_solve(it - 1) left active (all of them when it == 0; with a plan the
+    // plan's sequences of this sub-batch) and clears the list k_gn_solve(it) appends to
+    const int* plan_list = c.plan ? c.plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
+    const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
+    ga.list = list_prev;
+    if (((aff.on && aff.mode == DVO_AFFINE_ESTIMATE) || rob.median()) && level == 0 && first) {
+        // the priming pair: the moments (the median scale: the bin counts) of the start pose on the coarsest level give
+        // the first iteration's entry; it leaves the pose, the log, the lists and the quality record alone
+        DVO_TRY(launch_gn_term(ga, level, nq, sk, 0, ref_z, true));
+        SolveArgs sp = solve_args(level, q0, 1, rows);
+        sp.list_in = list_prev; sp.result = nullptr;
+        SolveTerm tp{};
+        tp.prime = true;
+        DVO_TRY(launch_solve_term(sp, nq, sk, tp));
+    }
+    ga.next_count = lists ? work_list(k, it) : nullptr;
+    if (cfg.profile) {
+        if (ev_used == ev_pool.size()) {
+            hipEvent_t e0, e1;
+            DVO_HIP(hipEventCreate(&e0));
+            DVO_HIP(hipEventCreate(&e1));
+            ev_pool.emplace_back(e0, e1);
+        }
+        DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
+    }
+    DVO_TRY(launch_gn_term(ga, level, nq, sk, active_ub, ref_z));
+    if (cfg.profile) DVO_HIP(hipEventRecord(ev_pool[ev_used++].second, sk));
+    SolveArgs sa = solve_args(level, q0, first, rows);
+    sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;   // (they describe k_track_gn launches only)
+    sa.list_in = list_prev;
+    sa.list_out = ga.next_count;
+    if (adaptive) sa.progress = c.prog_d + level * DVO_MAX_ITERATIONS + it;
+    return launch_solve_term(sa, nq, sk, c.iteration);
+}
+
+int Tracker::track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan)
+{
+    TrackCall c{s, plan, plan ? plan->seq_k : cam_k};
+    last_obj = &obj; last_ref = &ref;
+    persist_used = false;
+    c.top_waited = top_ready == nullptr;
+    if (persist_call(plan)) {   // the whole call in one launch (k_track_persist)
+        DVO_TRY(wait_top(c, 1));
+        DVO_TRY(track_persist(obj, ref, s));
+        if (persist_used) return DVO_OK;
+    }
+    DVO_TRY(track_prologue(c));
+    for (int level = 0; level < c.n_levels; level++) {  // tracker.cpp:32
         TraceRange tr(kLevelName[level]);
-        const LevelPlan& L = lv[level];
-        const bool lists = tile_margin == 0 && !L.single_launch;  // (k_track_gn_tile keeps the per-sequence active flag test)
-        const int host_its = L.fused ? 1 : max_it;  // a fused level iterates on the device (k_track_level)
+        const int schedule = lv[level].schedule;
+        const int host_its = schedule == DVO_PLAN_LEVEL ? 1 : c.max_it;  // (k_track_level iterates on the device)
         for (int it = 0; it < host_its; it++) {        // tracker.cpp:42
             const int first = (it == 0) ? 1 : 0;
-            // Stay `ahead` iterations ahead of the GPU: wait until launch it-ahead of this level has reported, and stop the level
-            // if it had no active sequence -- every later launch of the level would be empty.  Skipping empty launches
-            // changes no result.  Two iterations ahead for every batch size: a batch iteration takes >= 20 us on the GPU, the host
-            // needs ~10 us to see a progress word and queue the next pair, and every iteration queued beyond the last useful one
-            // is an empty launch pair (~15 us): measured +1.6 % (mono, 1 iteration per level) / +0.7 % (sensor depth) against 4.
-            const int ahead = 2;
-            int active_ub = 0;   // sequences that entered iteration it - ahead: the active set only shrinks within a level, so this bounds the list of `it`
-            if (adaptive && !L.fused && it >= ahead) {
-                volatile int* pw = prog_h + level * DVO_MAX_ITERATIONS + (it - ahead);
-                DVO_TRY(wait_progress(pw, s));
-                if (*pw - 1 == 0) break;
-                if (!L.single_launch) active_ub = *pw - 1;
-            }
-            if (!top_waited && level == g.levels - 1) {   // obj's top level: the split build's side stream writes it (every launch form reads it)
-                for (int k = 0; k < subs; k++) DVO_HIP(hipStreamWaitEvent(k == 0 ? s : sub_streams[k - 1], top_ready, 0));
-                top_waited = true;
-            }
+            const int entered = wait_ahead(c, level, it);
+            if (entered < 0) return DVO_ERR_HIP;
+            if (entered == 1) break;
+            const int active_ub = (entered && schedule != DVO_PLAN_ITERATION) ? entered - 1 : 0;
+            if (level == g.levels - 1) DVO_TRY(wait_top(c, c.subs));   // before the top level's first launch, on every stream that launches it
             // (the geometric term: pixel x of the tracked frame uses that frame's own depth and weight; the reference's depth is sampled)
             const GnArgs ga0 = geo.on ? gn_args(obj.gray[level], ref.gray[level], obj.depth[level], obj.sigma_by_validity ? nullptr : obj.wgt[level],
                                                 obj.sigma_by_validity ? obj.wgt_valid[level] : 0.0f, level, nullptr, first)
                                       : gn_args(obj, ref, level, nullptr, first);
-            for (int k = 0; k < subs; k++) {  // launches of the sub-batches interleave on their streams
-                const int q0 = subs > 1 ? sub_first(k) : 0, q1 = subs > 1 ? sub_first(k + 1) : n_seq, nq = q1 - q0;
+            for (int k = 0; k < c.subs; k++) {  // launches of the sub-batches interleave on their streams
+                const int q0 = c.subs > 1 ? sub_first(k) : 0, nq = (c.subs > 1 ? sub_first(k + 1) : n_seq) - q0;
                 hipStream_t sk = k == 0 ? s : sub_streams[k - 1];
-                GnArgs ga = gn_view(ga0, level, q0, plan, seq_k);  // view of sequences [q0, q1)
-                if (L.single_launch) {   // GN accumulation + solve of this iteration in one launch (k_track_gn_fused)
-                    const SolveArgs fa = solve_args(level, q0, first, SolveRows::Live);
-                    if (launch_track_gn_fused(ga, fa, nq, L.ppt, L.group, L.tiling.t2d != 0, ticket.as<int>(),
-                                              rep_set + 2 * (level * DVO_MAX_ITERATIONS + it), adaptive ? prog_d + level * DVO_MAX_ITERATIONS + it : nullptr, sk))
-                        continue;
+                const GnArgs ga = gn_view(ga0, level, q0, plan, c.seq_k);  // view of sequences [q0, q0 + nq)
+                switch (schedule) {
+                case DVO_PLAN_LEVEL: queue_level(ga, level, q0, nq, sk); break;
+                case DVO_PLAN_ITERATION: DVO_TRY(queue_iteration(c, ga, level, it, q0, nq, sk)); break;
+                case DVO_PLAN_PAIRS:
+                case DVO_PLAN_LDS_PATCH: DVO_TRY(queue_pair(c, ga, level, it, k, q0, nq, sk, active_ub, ref.depth[level])); break;
+                default: return term_launch_status(false, "a level without a schedule");
                 }
-                if (L.fused) {
-                    SolveArgs fa = solve_args(level, q0, 1, SolveRows::All);
-                    fa.partials = nullptr;
-                    launch_track_level(ga, fa, nq, sk);
-                    continue;
-                }
-                // iteration `it` evaluates the sequences k_gn_solve(it - 1) left active (all of them when it == 0; with a plan the
-                // plan's sequences of this sub-batch) and clears the list k_gn_solve(it) appends to
-                const int* plan_list = plan ? plan->lists + (size_t)k * (size_t)(n_seq + 4) : nullptr;
-                const int* list_prev = first ? plan_list : (lists ? work_list(k, it - 1) : nullptr);
-                ga.list = list_prev;
-                ga.next_count = lists ? work_list(k, it) : nullptr;
-                if (((aff.on && aff.mode == DVO_AFFINE_ESTIMATE) || rob.median()) && level == 0 && first) {
-                    // the priming pair: the moments (the median scale: the bin counts) of the start pose on the coarsest level give
-                    // the first iteration's entry; it leaves the pose, the log, the lists and the quality record alone
-                    GnArgs gp = ga;
-                    gp.next_count = nullptr;
-                    DVO_TRY(launch_gn_term(gp, level, nq, sk, 0, ref.depth[level], true));
-                    SolveArgs sp = solve_args(level, q0, 1, lists ? SolveRows::LivePair : SolveRows::All);
-                    sp.list_in = list_prev; sp.result = nullptr;
-                    SolveTerm tp{};
-                    tp.prime = true;
-                    DVO_TRY(launch_solve_term(sp, nq, sk, tp));
-                }
-                if (cfg.profile) {
-                    if (ev_used == ev_pool.size()) {
-                        hipEvent_t e0, e1;
-                        DVO_HIP(hipEventCreate(&e0));
-                        DVO_HIP(hipEventCreate(&e1));
-                        ev_pool.emplace_back(e0, e1);
-                    }
-                    DVO_HIP(hipEventRecord(ev_pool[ev_used].first, sk));
-                }
-                DVO_TRY(launch_gn_term(ga, level, nq, sk, active_ub, ref.depth[level]));
-                if (cfg.profile) {
-                    DVO_HIP(hipEventRecord(ev_pool[ev_used].second, sk));
-                    ev_used++;
-                }
-                SolveArgs sa = solve_args(level, q0, first, lists ? SolveRows::LivePair : SolveRows::All);
-                sa.counters = cfg.profile ? counters.as<unsigned long long>() : nullptr;   // (they describe k_track_gn launches only)
-                sa.list_in = list_prev;
-                sa.list_out = lists ? work_list(k, it) : nullptr;
-                if (adaptive) sa.progress = prog_d + level * DVO_MAX_ITERATIONS + it;
-                DVO_TRY(launch_solve_term(sa, nq, sk, iteration));
             }
-            if (poll && !L.fused && it + 1 < max_it) {
-                DVO_HIP(hipMemcpyAsync(host_state, state.p, sizeof(SeqState) * (size_t)n_seq, hipMemcpyDeviceToHost, s));
-                DVO_HIP(hipStreamSynchronize(s));
-                bool any = false;
-                for (int q = 0; q < n_seq; q++) any = any || host_state[q].active != 0;
-                if (!any) break;
-            }
+            bool go = true;
+            DVO_TRY(poll_active(c, level, it, &go));
+            if (!go) break;
         }
     }
     // join: `s` continues (pose export, the caller's next frame) only after every sub-batch chain has finished
-    for (int k = 1; k < subs; k++) {
+    for (int k = 1; k < c.subs; k++) {
         DVO_HIP(hipEventRecord(ev_join[k - 1], sub_streams[k - 1]));
         DVO_HIP(hipStreamWaitEvent(s, ev_join[k - 1], 0));
     }
-    if (!top_waited) DVO_HIP(hipStreamWaitEvent(s, top_ready, 0));   // (no level was launched: the caller's stream still orders obj's maps)
+    DVO_TRY(wait_top(c, 1));   // (no level was launched: the caller's stream still orders obj's maps)
     if (h_result) next_result_tag();
     launch_export_poses(state.as<SeqState>(), xi_out.as<float>(), T_out.as<float>(), n_seq, s, d_result, result_tag);
     DVO_HIP(hipGetLastError());
@@ -1806,7 +1861,7 @@ int VisualOdometry::odometrize(const float* gray, float T_world[16], int* is_key
     memcpy(hdr.ref_xi, ref.xi, sizeof hdr.ref_xi);
     hdr.ref_id = ref.id; hdr.n_total = (int)hist.size(); hdr.valid = 1;
     trkM.mono_tail = {};
-    if (trkM.persist_ok && !trkM.persist_failed) {
+    if (trkM.persist_call()) {
         PersistMono& pm = trkM.mono_tail;
         pm.meta = meta_dev.as<MonoSeq>();
         memcpy(pm.ref_xi, ref.xi, sizeof pm.ref_xi);

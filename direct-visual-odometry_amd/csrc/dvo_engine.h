@@ -359,18 +359,23 @@ struct StepControl : OptInTerm {
 struct LevelPlan {
     int ppt = 0, group = 0;          // pixels per thread and gather group: the kernel instance
     int nblk = 0;                    // tiles (= partial rows) per sequence
-    GnTiling tiling;                 // the tiles of k_track_gn and of every kernel that shares them (tile_margin == 0; else the default)
-    int tiles_x = 0, tiles_y = 0;    // the tiles of k_track_gn_tile (tile_margin > 0, gn_tile_geometry; else 0)
-    bool fused = false;              // level runs as ONE k_track_level launch (all iterations on the device)
-    bool single_launch = false;      // level runs one k_track_gn_fused launch per iteration (small handles: see dvo_kernels.hip)
+    GnTiling tiling;                 // the tiles of k_track_gn and of every kernel that shares them (margin == 0; else the default)
+    int tiles_x = 0, tiles_y = 0;    // the tiles of k_track_gn_tile (margin > 0, gn_tile_geometry; else 0)
+    // The level's launch form, a DVO_PLAN_* value of include/dvo.h: PAIRS = k_track_gn + k_gn_solve per iteration,
+    // ITERATION = one k_track_gn_fused per iteration (small handles: see dvo_kernels.hip), LEVEL = ONE k_track_level launch (all
+    // iterations on the device), LDS_PATCH = k_track_gn_tile + k_gn_solve per iteration.  Everything that launches reads it from here.
+    int schedule = DVO_PLAN_PAIRS;
+    int margin = 0;                  // the LDS-staged reference patch's margin: 0 unless schedule == DVO_PLAN_LDS_PATCH
 };
 
 // Which partial rows a solve sums (SolveArgs::blk_first / blk_count) and what it adds to the profile counter (SolveArgs::level_pixels)
 enum class SolveRows {
-    All,        // every row, w * h pixels: k_track_gn_tile's solves, k_track_level, the launch pair after a refused k_track_gn_fused
+    All,        // every row, w * h pixels: k_track_gn_tile's solves, k_track_level
     Live,       // the level's live tiles, w * h pixels: the solves that feed no profile counter (k_track_gn_fused, dvo_op_gn_step)
     LivePair,   // the level's live tiles and the pixels they cover: the k_gn_solve after a k_track_gn
 };
+
+struct TrackCall;   // one track() call's state (dvo_engine.cpp)
 
 struct Tracker {  // Track::Tracker for n_seq sequences at once
     Geometry g;
@@ -395,10 +400,12 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     LevelPlan lv[DVO_MAX_LEVELS];
     // Both plans are decided by init: lv_plain is what the configuration asks for, lv_rw the weighted plan (launch pairs of the
     // global-gather kernel on every level, whatever track_fused_tiles, gn_use_lds_patch, track_single_launch and the batch size say).
-    // lv / tile_margin are whichever is in force (use_plan, called by set_term: any opt-in term runs the weighted plan).
+    // lv is whichever is in force (use_plan, called by set_term: any opt-in term runs the weighted plan).  What init decided from
+    // the configuration alone -- n_sub, adaptive, persist_ok -- stays as it is under either plan.
     LevelPlan lv_plain[DVO_MAX_LEVELS], lv_rw[DVO_MAX_LEVELS];
-    int margin_plain = 0;
     void use_plan();
+    // the rows a level's solve sums behind its k_track_gn (`live`: Live or LivePair) or k_track_gn_tile (All) launch
+    SolveRows pair_rows(int level, SolveRows live) const;
     int log_iterations() const;   // iterations per level an opt-in term's log holds (fixed by the term's first enable)
     // One iteration's launch pair of the terms that are on: each fills the block of every such term and makes one call, and the
     // kernel file's table picks the pair (launch_track_gn_terms / launch_gn_solve_terms); with nothing on, launch_gn
@@ -455,7 +462,7 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     int progress_set = 0;
     bool adaptive = false;
     SeqState* h_state = nullptr;  // pinned host mirror of `state` for the small-batch convergence poll
-    int tile_margin = 0;  // > 0: k_track_gn_tile (LDS-staged reference patch); 0: k_track_gn (global gathers)
+    // k_track_gn_tile (the level's schedule is DVO_PLAN_LDS_PATCH) or k_track_gn (global gathers: every other schedule)
     void launch_gn(const GnArgs& a, int level, int count, hipStream_t s, int grid_seqs = 0) const;  // `a` views `count` sequences
     // per-sequence intrinsics [level][n_seq] of a per-camera mono batch (dvo_batch_create_mono_cameras), used when track() has no
     // plan (a plan brings its own, TrackPlan::seq_k); nullptr: Geometry::k.  Never set together with prefer_persist.
@@ -476,8 +483,11 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // (GPU oversubscribed): the handle then stays on the launch-per-iteration schedule.
     bool prefer_persist = false;   // set before init() by the owner whose results go through enable_host_result() (VisualOdometry's sensor-depth tracker)
     bool persist_ok = false, persist_failed = false, persist_used = false;
+    // this track() call runs as k_track_persist (an owner arms mono_tail by it, with plan = nullptr: what it then passes to track())
+    bool persist_call(const TrackPlan* plan = nullptr) const { return persist_ok && !persist_failed && h_result && !plan && !cam_k && !seed; }
     int persist_grid = 0, persist_spin_limit = 1 << 18;
-    bool persist_timeline = false;
+    bool persist_timeline = false;   // DVO_PERSIST_TIMELINE is set, to the worker whose stamps are kept beside the solver's
+    int persist_dbg_worker = 0;
     DevBuf persist_ctl, persist_dbg;
     int read_persist_timeline(long long* out);
     const FrameSet* last_obj = nullptr; const FrameSet* last_ref = nullptr;
@@ -508,13 +518,22 @@ struct Tracker {  // Track::Tracker for n_seq sequences at once
     // what every solve of a level shares, for the sequences from q0 on, summing `rows`; each schedule adds its own fields
     SolveArgs solve_args(int level, int q0, int ignore_active, SolveRows rows) const;
     int next_result_tag();   // the tag of this call's result (never 0)
-    // the whole call in one k_track_persist launch; *launched = false: there is no instance, the caller runs the other schedules
-    int track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s, bool* launched);
+    // the whole call in one k_track_persist launch; persist_used stays false: there is no instance, the caller runs the other schedules
+    int track_persist(const FrameSet& obj, const FrameSet& ref, hipStream_t s);
     // Tracker::track (tracker.cpp:22-85): enqueue the whole coarse-to-fine loop; poses land in xi_out / T_out
     // With a plan (Batch): k_plan has done k_track_begin's work, and a level's first iteration runs the plan's sequences, not all
     int track(const FrameSet& obj, const FrameSet& ref, hipStream_t s, const TrackPlan* plan = nullptr);
     int collect_profile(hipStream_t s);
 private:
+    // The pieces of track(), around one call's TrackCall: what is queued ahead of the levels, the three launch forms
+    // of one sub-batch (switch (lv[level].schedule)), and the host's two pacing mechanisms ahead of and behind an iteration
+    int track_prologue(TrackCall& c);
+    int wait_top(TrackCall& c, int streams);
+    void queue_level(const GnArgs& ga, int level, int q0, int nq, hipStream_t sk);
+    int queue_iteration(const TrackCall& c, const GnArgs& ga, int level, int it, int q0, int nq, hipStream_t sk);
+    int queue_pair(const TrackCall& c, GnArgs ga, int level, int it, int k, int q0, int nq, hipStream_t sk, int active_ub, const float* ref_z);
+    int wait_ahead(const TrackCall& c, int level, int it);
+    int poll_active(const TrackCall& c, int level, int it, bool* go);
     // the one place every setter goes through: the table (an "on" call only), the term's own `apply`, the plan of what is on now
     template <class Apply> int set_term(const char* who, TermSetter want, bool enable, Apply&& apply);
     int apply_robust(const dvo_robust_config* c, hipStream_t s);

@@ -528,6 +528,39 @@ def test_adaptive_schedule_changes_no_result():
     assert res[0][3] == res[1][3]
 
 
+def test_profile_counts_every_launch_and_changes_no_result():
+    """cfg.profile: an event pair around every k_track_gn launch, and the solves count iterations and pixels.  Nine sequences on one
+    chain with the fixed schedule (no convergence poll, every iteration queued): the counters follow from the track logs exactly, and
+    poses and logs equal the unprofiled run's bit for bit (profiling changes no tile size of a batch)."""
+    g, d, s, _ = frames(3, sigma=0.1)
+    B, levels, max_it = 9, 4, 15
+    res = []
+    for profile in (1, 0):
+        cfg = dvo.default_config(gn_pixels_per_thread=4, track_adaptive=-1, track_streams=1, crop_enable=0, profile=profile)
+        assert cfg.max_iterations == max_it
+        bt = dvo.Batch(B, K640, 640, 480, levels, 1, cfg=cfg)
+        poses, n_iter = [], []
+        for step in range(3):
+            bt.push_host(np.stack([g[(b + step) % 3] for b in range(B)]), np.stack([d[(b + step) % 3] for b in range(B)]),
+                         np.stack([s[(b + step) % 3] for b in range(B)]))
+            if step == 0:
+                bt.profile(reset=True)
+            else:
+                poses.append(bt.last_poses()[0].copy())
+                n_iter.append([list(bt.last_track_log(b)["n_iter"][:levels]) for b in range(B)])
+        res.append((np.stack(poses), np.array(n_iter, np.int64), bt.profile()))
+        bt.close()
+    (x1, n1, prof), (x0, n0, _) = res
+    np.testing.assert_array_equal(x1, x0)
+    np.testing.assert_array_equal(n1, n0)
+    per_level = n1.sum(axis=(0, 1))   # iterations of every sequence at both tracked pushes, per level
+    assert per_level.sum() > 2 * B * levels
+    assert prof["gn_launches"] == 2 * levels * max_it
+    assert prof["gn_iterations"] == per_level.sum()
+    level_px = [((640 >> 1) >> (levels - 1 - l)) * ((480 >> 1) >> (levels - 1 - l)) for l in range(levels)]
+    assert prof["gn_pixels"] == sum(int(p) * int(n) for p, n in zip(level_px, per_level))
+
+
 def test_batch_prefetch_changes_no_result():
     """dvo_batch_prefetch_device only moves the pyramid build of the next frame onto a side stream: poses are bit-identical."""
     import torch
